@@ -2,7 +2,7 @@
 """Benchmark of the MI355X TokenConditionedTransformer hot path (BASELINE.json metric:
 "train steps/sec + AR tokens/sec, coarse-stage musiclm_small, 1/2/4/8 MI355X").
 
-    python bench.py --gpus N --steps K --warmup W [--precision fp16|bf16|bf16x3] [--batch B] [--accum A]
+    python bench.py --gpus N --steps K --warmup W [--precision fp16|bf16|bf16x3] [--batch B] [--accum A] [--dump-outputs DIR]
 
 One "step" = one optimizer step of the coarse stage of musiclm_small (dim 1024, depth 6, heads 8, conv-GEGLU FF,
 N = 1116 positions = 3 start + 13 clap + 200 semantic + 900 coarse ids -- the exact length the reference's data
@@ -36,6 +36,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 N_SEQ = 1116
@@ -140,10 +141,27 @@ class TrainLeg:
         self.dp.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+        self.last_loss = loss                                  # the last timed step's loss (dump_outputs)
         tmax = torch.tensor([dt], device=self.dev)
         if self.dp.is_distributed:
             torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         return float(tmax.item()), float(loss.item())
+
+    def dump_outputs(self, out_dir, sample=1 << 22):
+        """What the last timed step computed, as .npy files under out_dir (about 16 MB): its loss, the global gradient norm the
+        optimizer clipped by (the fused AdamW zeroes the gradients themselves), and the parameters it wrote -- all of them flattened
+        in parameter-name order, a fixed seeded sample of `sample` entries of that vector when it is longer."""
+        os.makedirs(out_dir, exist_ok=True)
+        params = torch.cat([p.detach().reshape(-1).float() for _, p in sorted(self.model.named_parameters())])
+        if params.numel() > sample:
+            idx = torch.randint(0, params.numel(), (sample,), generator=torch.Generator().manual_seed(0)).sort().values
+            params = params[idx.to(params.device)]
+        outs = {"loss": self.last_loss.detach().float().reshape(-1),
+                "grad_norm": self.optim.last_grad_norm_sq.double().reshape(-1).sqrt(),      # step() clips: the norm is always formed
+                "params": params}
+        for name, t in outs.items():
+            np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
+        return sorted(outs)
 
     def gemm_roofline(self, k0, traffic=None, tag=""):
         """HIP events (torch events on the stream the kernels are launched on) around every MFMA GEMM launch of two extra,
@@ -403,7 +421,11 @@ def main():
     ap.add_argument("--legs", default="fp16,bf16,bf16x3,large_fine,e2e_generate")
     ap.add_argument("--large-batch", type=int, default=16, help="samples per step of the large_fine leg")
     ap.add_argument("--decode-ids", type=int, default=48)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed (loss, gradient norm, a seeded sample "
+                                                          "of the updated parameters) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU over RCCL; rank 0 prints the JSON line)
@@ -445,6 +467,8 @@ def main():
              (f" ({main_leg.fb.capture_error})" if main_leg.fb.capture_error else ""))
     dt, final_loss = main_leg.timed(args.steps, args.warmup)
     progress(f"timed region: {args.steps} steps in {dt:.3f}s")
+    if rank == 0 and args.dump_outputs:                    # before the roofline probe's extra steps move the parameters
+        progress(f"outputs of the last timed step: {main_leg.dump_outputs(args.dump_outputs)} in {args.dump_outputs}")
 
     ms_per_step = 1e3 * dt / args.steps
     steps_per_s = args.steps / dt
