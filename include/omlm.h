@@ -382,7 +382,8 @@ typedef struct omlm_decode_args {
     const void* const* W1p_lo; const void* const* W2p_lo; const void* head_W_lo;
     /* optional scratch of the batched FF-out launch (2 <= B <= 16, matrix-core kernels, ln_parts given): with it a tile of 16 output rows
      * is cut into four k-slices (256 workgroups instead of 64) that meet through fp32 slabs, added in slice order by the last to arrive.
-     * splitk_ws: OMLM_DECODE_SPLITK_FLOATS(D) floats, contents irrelevant; splitk_cnt: ceil(D / 16) ints, ZERO before the first step
+     * splitk_ws: OMLM_DECODE_SPLITK_FLOATS(D) floats, contents irrelevant; splitk_cnt: max(ceil(D / 16), 16) ints (the attention kernel's combine
+     * counts per sample b < B <= 16 in the same array), ZERO before the first step
      * (every step leaves them zero).  One decode stream at a time per scratch pair.  NULL: one workgroup per tile walks the whole row. */
     float* splitk_ws; int* splitk_cnt;
 } omlm_decode_args;

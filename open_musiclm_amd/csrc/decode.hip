@@ -57,7 +57,7 @@ struct omlm_decode_args {
     // activation rows and h1 un-rounded, like the three-product forward of the batched path (W1p_lo == NULL: plain 16-bit step)
     const void* const* W1p_lo; const void* const* W2p_lo; const void* head_W_lo;
     // split-K scratch of the batched FF-out launch (optional; NULL: one workgroup per 16 output rows walks the whole row):
-    // splitk_ws 4 * ceil(D / 16) * 256 floats, contents irrelevant; splitk_cnt ceil(D / 16) ints, ZERO before the first step (every launch
+    // splitk_ws 4 * ceil(D / 16) * 256 floats, contents irrelevant; splitk_cnt max(ceil(D / 16), 16) ints (the attention combine counts per sample in it too), ZERO before the first step (every launch
     // leaves them zero)
     float* splitk_ws; int* splitk_cnt;
 };

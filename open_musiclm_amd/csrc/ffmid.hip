@@ -729,6 +729,8 @@ extern "C" int omlm_ffmid_fwd_mx(const void* h1, const void* h1_lo, const void* 
     OMLM_CHECK_ARG(nseq > 0 && M % nseq == 0, "M must be batch * nseq");
     OMLM_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || drop_bits), "dropout p (keep bits required when p > 0)");
     OMLM_CHECK_ARG(h2_8_stride >= (long long)M * 2 * Fp && h2_8_stride % 16 == 0, "ffmid_fwd_mx: fp8 plane stride");
+    // the kernel zeroes every fp8 row out to a whole 128-byte k-tile: the row pitch 2 Fp must hold it (Fp >= 64)
+    OMLM_CHECK_ARG(2 * Fp >= (Fp + 127) / 128 * 128, "ffmid_fwd_mx: an fp8 plane row (pitch 2 * Fp bytes) must hold Fp rounded up to 128 bytes");
     OMLM_CHECK_ARG((((uintptr_t)h1 | (uintptr_t)h1_lo | (uintptr_t)convw | (uintptr_t)convw_lo | (uintptr_t)gamma | (uintptr_t)gamma_lo |
                      (uintptr_t)h2 | (uintptr_t)h2_8) % 16) == 0, "ffmid_fwd_mx: 16-byte aligned planes");
     return ffmid2_fwd_mx_launch(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_8, h2_8_stride, scale8, mean, rstd, M, nseq, F, Fp, eps, p, seed,

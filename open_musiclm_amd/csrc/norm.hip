@@ -232,6 +232,8 @@ extern "C" int omlm_layernorm_fwd_mx(const float* x, const float* gamma, void* y
     OMLM_CHECK_ARG(x && gamma && y && y8 && scale8 && mean && rstd, "null pointer");
     OMLM_CHECK_ARG(D % 4 == 0 && D <= 4 * LN_THREADS * LN_MAXV, "D must be a multiple of 4 and <= 4096");
     OMLM_CHECK_ARG(ldy >= D && ldy % 4 == 0 && y8_stride >= (long long)M * 2 * ldy, "ldy / plane stride");
+    // the kernel zeroes every fp8 row out to a whole 128-byte k-tile: the row pitch must hold it (else the tail runs into the next row)
+    OMLM_CHECK_ARG(2 * ldy >= (D + 127) / 128 * 128, "an fp8 plane row (pitch 2 * ldy bytes) must hold D rounded up to 128 bytes");
     dim3 grid(M < 2048 ? M : 2048), block(LN_THREADS);
     if (D <= 4 * LN_THREADS)
         hipLaunchKernelGGL((ln_fwd_mx_kernel<1>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (unsigned char*)y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps);

@@ -41,26 +41,63 @@ class DecodeArgs(C.Structure):
                 [("splitk_ws", C.c_void_p), ("splitk_cnt", C.c_void_p)])
 
 
-def max_batch(model, precision: str) -> int:
-    """Samples one decode call holds: 8 on the VALU step kernels; 16 where the matrix-core kernels serve the model (16-bit weights, dim 1024,
-    at most 16 heads, feed-forward width <= 3072: omlm_decode_step's own conditions)."""
+MAX_DECODE_HEADS = 16              # omlm_decode_step: H <= 16
+DEC4_NB = 16                       # decode.hip: samples of the matrix-core step kernels (their split-K counters are indexed by sample too)
+_LDS_BYTES = 150 * 1024            # omlm_decode_step: B * Fp * 4 + 1024 bytes of LDS for the first-generation step kernels (B <= 8)
+
+
+def _geometry(model):
     tr = model.transformer
     inner = getattr(tr.layers[0][2], "inner_dim", 0) if len(tr.layers) else 0
-    wide = (precision in ("bf16", "fp16", "fp16ff") and tr.dim == 1024 and tr.heads * engine.DIM_HEAD <= 1024 and 0 < engine.ceil_to(inner, 64) <= 3072
-            and os.environ.get("OMLM_DECODE_MFMA", "1") != "0" and os.environ.get("OMLM_DECODE_V1", "0") != "1")
-    return 16 if wide else MAX_DECODE_BATCH
+    return tr.dim, tr.heads, engine.ceil_to(inner, 64)
+
+
+def _second_generation(D: int, H: int, Fp: int) -> bool:
+    """omlm_decode_step's v2_ok: the dec2 / dec3 / dec4 step kernels serve dim 1024 only; everything else runs on the first-generation kernels."""
+    return D == 1024 and H * 64 <= 1024 and Fp <= 4096 and os.environ.get("OMLM_DECODE_V1", "0") != "1"
+
+
+def _matrix_core(B: int, D: int, H: int, Fp: int) -> bool:
+    """decode.hip dec4_ok (16-bit weights, the LayerNorm partials always given): the matrix-core step kernels."""
+    return (os.environ.get("OMLM_DECODE_MFMA", "1") != "0" and 2 <= B <= DEC4_NB and D % 32 == 0 and D <= 1024 and H * 64 <= 1024
+            and Fp % 32 == 0 and Fp <= 3072)
+
+
+def lo_planes_ok(model, batch: int) -> bool:
+    """"fp16ff": whether omlm_decode_step takes the lo planes of FF-in / FF-out / head at this geometry (its own checks: on the second-generation
+    kernels Fp <= 3072, and at B >= 2 the matrix-core kernels), and the batched forward keeps h1's lo plane for the prefill (Fp <= 4096).
+    Elsewhere the steps run on the fp16 kernels with the hi planes, as "fp16" does."""
+    D, H, Fp = _geometry(model)
+    if not engine.ff_planes_ok(Fp):
+        return False
+    if not _second_generation(D, H, Fp):
+        return True
+    return Fp <= 3072 and (batch == 1 or _matrix_core(batch, D, H, Fp))
+
+
+def max_batch(model, precision: str) -> int:
+    """Samples one decode call holds: 16 where the matrix-core kernels serve the model (16-bit weights, dim 1024, at most 16 heads,
+    feed-forward width <= 3072); otherwise 8, or fewer where B * Fp floats exceed the first-generation kernels' LDS."""
+    D, H, Fp = _geometry(model)
+    wide = (precision in ("bf16", "fp16", "fp16ff") and _second_generation(D, H, Fp) and 0 < Fp and _matrix_core(2, D, H, Fp))
+    if wide:
+        return DEC4_NB
+    return max(0, min(MAX_DECODE_BATCH, (_LDS_BYTES - 1024) // (4 * max(Fp, 1))))
 
 
 def supports(model, batch: int, precision: Optional[str] = None) -> bool:
+    """Whether CachedDecoder (omlm_decode_step) serves `batch` samples of this model; where it does not, generate() re-runs the forward."""
     tr = model.transformer
-    limit = max_batch(model, precision) if precision is not None else MAX_DECODE_BATCH
-    return batch <= limit and tr.non_causal_prefix_size == 0
+    limit = max_batch(model, precision) if precision is not None else min(MAX_DECODE_BATCH, max_batch(model, "bf16x3"))
+    return 1 <= batch <= limit and tr.non_causal_prefix_size == 0 and 1 <= tr.heads <= MAX_DECODE_HEADS
 
 
 class CachedDecoder:
     def __init__(self, model, batch: int, max_rows: int, precision: str):
-        if batch > max_batch(model, precision):
-            raise ValueError(f"cached decode handles up to {max_batch(model, precision)} samples per call here; got {batch}")
+        if not supports(model, batch, precision):
+            tr = model.transformer
+            raise ValueError(f"cached decode does not serve this model with {batch} samples per call (at most {max_batch(model, precision)} "
+                             f"samples, at most {MAX_DECODE_HEADS} heads, no non-causal prefix; got {tr.heads} heads)")
         self.model, self.B, self.Nmax, self.precision = model, batch, int(max_rows), precision
         tr = model.transformer
         dev = model.start_tokens[0].device
@@ -68,8 +105,9 @@ class CachedDecoder:
         self.pw = engine.prepared_weights(model, precision)
         self.T = self.pw.T
         # "fp16ff": the steps read the FF-in / FF-out / head weights as hi + lo planes and keep LayerNorm outputs and h1 un-rounded, like the
-        # three-product forward of the batched path (omlm_decode_args::W1p_lo)
-        self.planes = bool(self.pw.ff3)
+        # three-product forward of the batched path (omlm_decode_args::W1p_lo) -- where the step kernels take lo planes (lo_planes_ok); elsewhere
+        # they run on the fp16 kernels with the hi planes
+        self.planes = bool(self.pw.ff3) and bool(self.pw.ff_planes) and lo_planes_ok(model, batch)
         L, D, H = len(tr.layers), tr.dim, tr.heads
         F, Fp = self.pw.layers[0]["F"], self.pw.layers[0]["Fp"]
         self.L, self.D, self.H, self.F, self.Fp = L, D, H, F, Fp
@@ -139,9 +177,10 @@ class CachedDecoder:
         # per-workgroup LayerNorm partial sums of the batched step kernels (OMLM_DECODE_LN_PARTS(D, Fp) floats x 3 producers)
         self.ln_parts = torch.zeros(3 * max((a.D + 15) // 16, (a.Fp + 7) // 8) * 32, device=self.x.device)      # [partial][16 samples][2]
         a.ln_parts = self.ln_parts.data_ptr()
-        # split-K scratch of the batched FF-out launch (OMLM_DECODE_SPLITK_FLOATS): slabs + one zeroed arrival counter per 16 output rows
+        # split-K scratch of the batched FF-out launch (OMLM_DECODE_SPLITK_FLOATS): slabs + one zeroed arrival counter per 16 output rows; the
+        # attention kernel's combine counts per sample in the same array, so it holds at least DEC4_NB counters
         self.splitk_ws = torch.empty(4 * ((a.D + 15) // 16) * 256, device=self.x.device)
-        self.splitk_cnt = torch.zeros((a.D + 15) // 16, dtype=torch.int32, device=self.x.device)
+        self.splitk_cnt = torch.zeros(max((a.D + 15) // 16, DEC4_NB), dtype=torch.int32, device=self.x.device)
         a.splitk_ws, a.splitk_cnt = self.splitk_ws.data_ptr(), self.splitk_cnt.data_ptr()
         self.args = a
 

@@ -31,6 +31,8 @@ DIM_HEAD = 64
 # "fp16ff" (round 5): "fp16" whose two ConvFeedForward linears run the FORWARD on hi/lo half planes (three products, omlm_gemm_planes16) with
 # h1 / h2 un-rounded in between (omlm_ffmid_fwd_planes): those two GEMMs carry 86-88 % of the fp16 logits-error variance at depth 6 and 24
 # (profiles/r05_error_budget.md).  Everything else, and the whole backward (which reads the hi planes), is "fp16".
+# The plane kernels of the feed-forward forward hold rows of at most FF_PLANES_MAX_FP (padded) columns: a wider feed-forward (plain FeedForward
+# at dim >= 1032) runs its forward as "fp16" in this mode; the final LayerNorm and the logit heads keep their planes (PreparedWeights.ff_planes).
 _PRECISIONS = {"bf16": torch.bfloat16, "bf16x3": torch.float32, "fp16": torch.float16, "fp16ff": torch.float16}
 
 
@@ -77,6 +79,22 @@ def ff_mx_enabled() -> bool:
     of three half products (ops.gemm_planes16, round 5).  What the fp8 corrections leave in the logits: profiles/r06_error_budget_fp8corr.md.
     OMLM_FF_MX=0 (read when the weights are prepared): the three-product form."""
     return os.environ.get("OMLM_FF_MX", "1") == "1"
+
+
+FF_PLANES_MAX_FP = 4096      # omlm_ffmid_fwd_planes / omlm_ffmid_fwd_mx: Fp <= 4096 (ffmid2_supported)
+
+
+def ff_planes_ok(Fp: int) -> bool:
+    """"fp16ff": the feed-forward forward of a layer with padded inner width Fp can run on hi/lo planes."""
+    return Fp <= FF_PLANES_MAX_FP
+
+
+def ff_mx_ok(D: int, Fp: int) -> bool:
+    """The fp8-corrected route's own limits: omlm_gemm_mx16 takes K % 64 == 0 (FF-in: K = D; FF-out: K = Fp, a multiple of 64), and its fp8 A
+    rows of 2 D bytes written by omlm_layernorm_fwd_mx must hold D rounded up to 128 (true for D % 64 == 0, D <= 4096)."""
+    return D % 64 == 0 and D <= 4096 and Fp % 64 == 0 and ff_planes_ok(Fp)
+
+
 _SIDE_STREAMS: Dict[int, "torch.cuda.Stream"] = {}
 
 
@@ -245,12 +263,17 @@ class PreparedWeights:
         tr = model.transformer
         self.precision = precision
         self.T = _PRECISIONS[precision]
-        self.ff3 = precision == "fp16ff"          # FF forward on hi/lo planes: lo planes of W1p / W2p / taps / gamma next to the usual images
-        self.mx = self.ff3 and ff_mx_enabled()    # ... with the FF GEMMs' correction products on fp8 planes (W1p8 / W2p8: ops.Fp8Planes)
-        quants = ops.QuantRowsGroup()
+        self.ff3 = precision == "fp16ff"          # final LayerNorm + logit heads on hi/lo planes
         T = self.T
         dev = model.start_tokens[0].device
         D = tr.dim
+        Fp_all = {ceil_to(ff.inner_dim, 64) for _, _, ff in tr.layers}
+        # FF forward on hi/lo planes: lo planes of W1p / W2p / taps / gamma next to the usual images, where the plane kernels hold the width
+        self.ff_planes = self.ff3 and all(ff_planes_ok(f) for f in Fp_all)
+        # ... with the FF GEMMs' correction products on fp8 planes (W1p8 / W2p8: ops.Fp8Planes), where omlm_gemm_mx16 takes the geometry
+        # (otherwise the three-product omlm_gemm_planes16 route)
+        self.mx = self.ff_planes and ff_mx_enabled() and all(ff_mx_ok(D, f) for f in Fp_all)
+        quants = ops.QuantRowsGroup()
         self.layers = []
         # padded operand images are persistent per (layer, operand type): their pad rows / columns are zeroed once, a step only rewrites the
         # real entries (was: an 11 MB zero fill + ~10 small torch launches per layer per step)
@@ -280,7 +303,7 @@ class PreparedWeights:
             packs.add(w1.detach()[F:], W1p[Fp:], F, D, D, D)
             packs.add(w2.detach(), W2p, D, F, F, Fp)
             ent["W1p"], ent["W2p"], ent["F"], ent["Fp"] = W1p, W2p, F, Fp
-            if self.ff3:
+            if self.ff_planes:
                 lkey = bkey + ("lo",)
                 if not persistent or lkey not in wbuf:
                     lo = (torch.zeros(2 * Fp, D, dtype=T, device=dev), torch.zeros(D, Fp, dtype=T, device=dev),
@@ -329,7 +352,7 @@ class PreparedWeights:
             packs.add(cw[F:], convp[:, Fp:], F, 3, 3, 2 * Fp, transpose=True)
             packs.add(ff.norm_mid.gamma.detach(), gammap, 1, F, F, Fp)
             ent["convw"], ent["gamma_mid"] = convp, gammap
-            if self.ff3:
+            if self.ff_planes:
                 packs.add(cw, ent["convw_lo"], F, 3, 3, 2 * Fp, transpose=True, lo=True)
                 packs.add(cw[F:], ent["convw_lo"][:, Fp:], F, 3, 3, 2 * Fp, transpose=True, lo=True)
                 packs.add(ff.norm_mid.gamma.detach(), ent["gamma_mid_lo"], 1, F, F, Fp, lo=True)
@@ -625,7 +648,7 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
             ops.layernorm_fwd_mx(x1, ff.norm_in.gamma.detach(), xn2, P1, m2, r2)
             h1_lo = torch.empty(M, 2 * Fp, dtype=torch.uint8, device=dev)      # the lo plane as bf8 (e5m2) bytes: h1 = hi + lo to 2^-14
             ops.gemm_mx16(xn2, P1, w["W1p"], w["W1p8"], h1, h1_lo, M=M, N=2 * Fp, K=D)
-        elif pw.ff3:
+        elif pw.ff_planes:
             # "fp16ff": LN output, h1 and h2 exist as hi/lo planes during this layer's forward; the lo planes die with the layer (their
             # consumers are the next launches of this stream), the hi planes are what the fp16 backward keeps
             xn2_lo = torch.empty(M, D, dtype=T, device=dev)
@@ -640,12 +663,12 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
         p = float(ff.dropout_p) if training else 0.0
         seed = seeds[li] if (p > 0 and seeds is not None) else 0
         # (the plane forward of "fp16ff" exists on the strip kernels only, which hand the keep mask over through drop_bits: present whenever p > 0)
-        drop_bits = torch.empty(M, Fp // 8, dtype=torch.uint8, device=dev) if (p > 0 and (save or pw.ff3)) else None
+        drop_bits = torch.empty(M, Fp // 8, dtype=torch.uint8, device=dev) if (p > 0 and (save or pw.ff_planes)) else None
         # the normalised GEGLU output is saved for the backward: its row-sum prepass reads it instead of recomputing conv + GELU, and
         # the fused second-generation backward (csrc/ffmid2.hip) requires it
         gh = torch.empty(M, Fp, dtype=T, device=dev) if (save and _FF_SAVE_GH) else None
         x2 = torch.empty(M, D, device=dev)
-        if pw.ff3:
+        if pw.ff_planes:
             if pw.mx:
                 P2 = ops.Fp8Planes(M, Fp, dev, zero=False)
                 ops.ffmid_fwd_mx(h1, h1_lo, w["convw"], w["convw_lo"], w["gamma_mid"], w["gamma_mid_lo"], h2, P2, m3, r3, N, F, Fp, p, seed,

@@ -239,6 +239,9 @@ class Transformer(nn.Module):
         self.relative_position_bias_type = relative_position_bias_type
         self.layers = nn.ModuleList([])
         if relative_position_bias_type == 'continuous':
+            # the MLP's hidden width dim / 2 is the row pitch of its GEMM operands, which the kernels take in multiples of 8 elements
+            if dim % 16 != 0:
+                raise ValueError(f"relative_position_bias_type='continuous' needs dim % 16 == 0 (MLP width dim / 2 a multiple of 8); got dim={dim}")
             self.rel_pos_bias = RelativePositionBias(dim=dim // 2, heads=heads)
         elif relative_position_bias_type == 't5':
             self.rel_pos_bias = T5RelativePositionBias(heads=heads, num_buckets=32, max_distance=128)

@@ -1616,6 +1616,50 @@ def test_ffmid_fwd_mx(ops, dev, F, nseq, Bn, p):
     report(f"ffmid_fwd_mx[{F},{nseq},{p}]", lo8_rel_err=err)
 
 
+def test_mx_writers_refuse_rows_shorter_than_an_fp8_k_tile(ops, dev):
+    """omlm_layernorm_fwd_mx / omlm_ffmid_fwd_mx zero every fp8 row out to a whole 128-byte k-tile (what omlm_gemm_mx16 reads).  A row pitch of
+    2 ld bytes below that (2 ldy < ceil128(D), 2 Fp < 128) would make the tail store run into the next row -- and past the plane on the last
+    one -- so such calls are refused before any launch.  (The planes here carry spare rows and far more than 128 bytes of slack behind the
+    last row: a build without the checks still stays inside the allocation.)  One width at the limit (2 ldy = 128) still runs."""
+    M = 40
+    g = torch.Generator().manual_seed(5)
+    for D, ldy in ((32, 32), (40, 48), (56, 56)):
+        x = torch.randn(M, D, generator=g).to(dev)
+        gamma = torch.ones(D, device=dev)
+        y = torch.zeros(M, ldy, device=dev, dtype=torch.float16)
+        P = ops.Fp8Planes(M, ldy, dev)
+        assert P.planes.shape[1] > M and P.planes[1, M:].numel() >= 128
+        m, r = torch.empty(M, device=dev), torch.empty(M, device=dev)
+        with pytest.raises(RuntimeError, match="128"):
+            ops.layernorm_fwd_mx(x, gamma, y, P, m, r)
+        torch.cuda.synchronize()
+        assert float(P.planes.max()) == 0 and float(y.abs().max()) == 0, (D, ldy)          # nothing launched
+    # at the limit: D = 64, ldy = 64 -- a full row plus no tail
+    x = torch.randn(M, 64, generator=g).to(dev)
+    y = torch.empty(M, 64, device=dev, dtype=torch.float16)
+    P = ops.Fp8Planes(M, 64, dev)
+    m, r = torch.empty(M, device=dev), torch.empty(M, device=dev)
+    ops.layernorm_fwd_mx(x, torch.ones(64, device=dev), y, P, m, r)
+    ref = torch.nn.functional.layer_norm(x.double(), (64,), None, None, 1e-5)
+    assert relerr(y, ref) < 6e-4
+    # ffmid: Fp < 64 (F = Fp = 32, 48)
+    nseq, Bn = 20, 2
+    for F in (32, 48):
+        Fp = F
+        h1 = torch.randn(nseq * Bn, 2 * Fp, generator=g).to(dev).half()
+        h1l8 = torch.zeros(nseq * Bn, 2 * Fp, dtype=torch.uint8, device=dev)
+        taps = torch.zeros(3, 2 * Fp, device=dev, dtype=torch.float16)
+        taps[2] = 1
+        gam = torch.ones(Fp, device=dev, dtype=torch.float16)
+        h2 = torch.zeros(nseq * Bn, Fp, device=dev, dtype=torch.float16)
+        P = ops.Fp8Planes(nseq * Bn, Fp, dev)
+        m, r = torch.empty(nseq * Bn, device=dev), torch.empty(nseq * Bn, device=dev)
+        with pytest.raises(RuntimeError, match="128"):
+            ops.ffmid_fwd_mx(h1, h1l8, taps, torch.zeros_like(taps), gam, torch.zeros_like(gam), h2, P, m, r, nseq, F, Fp, 0.0, 1)
+        torch.cuda.synchronize()
+        assert float(P.planes.max()) == 0 and float(h2.abs().max()) == 0, F
+
+
 def test_quant_rows_mx(ops, dev):
     """omlm_quant_rows_mx (the per-step fp8 re-pack of the FF weights): rows of an fp32 matrix -> hi8 / lo8 / scale at a row offset of the
     planes, two problems in one launch (the value / gate halves of W1), ragged C."""
