@@ -157,9 +157,9 @@ __device__ __forceinline__ void pack_acc(const f32x16& p, int s, h16x8& hi, h16x
 // =============================================================================================================
 // forward
 // =============================================================================================================
-// AT_LEAN=1 (forward, the mask / bias part of the dQ kernel, the score loop of the dK/dV kernel; default since it ran through
-// the parity tests on the GPU): the ISA of the forward shows ~400 VALU
-// instructions per 8 MFMAs (one 32-key subtile), i.e. the kernel is VALU-bound 3:1.  The lean variant removes, without changing
+// Lean inner loops (forward, the mask / bias part of the dQ kernel, the score loop of the dK/dV kernel; round 2: parity tests
+// identical, forward 206 -> 145 us, backward 694 -> 643 us per layer).  The ISA of the straightforward forward showed ~400 VALU
+// instructions per 8 MFMAs (one 32-key subtile), i.e. the kernel was VALU-bound 3:1.  The lean form removes, without changing
 // a single result bit except where noted:
 //   * 80 v_accvgpr_read/write per subtile: without an occupancy hint hipcc keeps the accumulators in AGPRs and copies them out
 //     and back for the alpha rescale and the softmax -> amdgpu_waves_per_eu(2) (VGPR-form MFMA, as in the backward kernels);
@@ -168,42 +168,11 @@ __device__ __forceinline__ void pack_acc(const f32x16& p, int s, h16x8& hi, h16x
 //     which only masked scores reach (they are 0 either way);
 //   * on subtiles entirely below the diagonal (all but one per query tile): the causal compare, the clamp of the bias index and
 //     the per-score address arithmetic (constant LDS offsets from one base), and the 64-bit mask-bit test (one 32-bit word).
-#ifndef AT_DKV_FENCE
-#define AT_DKV_FENCE 1
-#endif
-#ifndef AT_DQ_BATCH
-#define AT_DQ_BATCH 1
-#endif
-#ifndef AT_DQ_WPE
-#define AT_DQ_WPE 2        /* waves per SIMD the backward kernels are compiled for (2 = 256 registers; 1 = 512: experiment builds) */
-#endif
-#ifndef AT_DQP_WPE
+#define AT_DQ_WPE 2        /* waves per SIMD the backward kernels are compiled for (2 = 256 registers) */
 #define AT_DQP_WPE 2
-#endif
-#ifndef AT_DKV_WPE
 #define AT_DKV_WPE 2
-#endif
-#ifndef AT_DQ_LATE_SCALE
-#define AT_DQ_LATE_SCALE 0
-#endif
-#ifndef AT_DBIAS_CARRY
-#define AT_DBIAS_CARRY 0   /* bf16 dQ kernel: d(bias) bins finalised in registers and stored once (no per-block LDS read-modify-write); unmeasured, off */
-#endif
-#ifndef AT_ABLATE
-#define AT_ABLATE 0        /* timing builds only (bf16 dQ kernel): 1 = no diagonal sums, 2 = no global d(bias) flush, 4 = no per-block table update */
-#endif
-#ifndef AT_LEAN
-#define AT_LEAN 1      /* round 2, first GPU call: parity tests identical, forward 206 -> 145 us, backward 694 -> 643 us per layer */
-#endif
-#if AT_LEAN
-#define AT_FWD_OCC __attribute__((amdgpu_waves_per_eu(2)))
-#define AT_EXP2(x) __builtin_amdgcn_exp2f(x)
-#else
-#define AT_FWD_OCC
-#define AT_EXP2(x) exp2f(x)
-#endif
 template <typename T>
-__global__ __launch_bounds__(AT_THREADS) AT_FWD_OCC void attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
+__global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2))) void attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                               const T* __restrict__ v, const float* __restrict__ bias,
                                                               const unsigned char* __restrict__ keymask, T* __restrict__ out,
                                                               float* __restrict__ lse, int B, int N, int H, float scale, int bias_ld) {
@@ -280,7 +249,7 @@ __global__ __launch_bounds__(AT_THREADS) AT_FWD_OCC void attn_fwd_kernel(const T
                 st = MFMA(ka, qh[s], st);
             }
             float mloc = NEG_BIG;
-            if (AT_LEAN && jb + 31 <= i0) {
+            if (jb + 31 <= i0) {
                 // every key of the subtile precedes every query of the wave: 0 <= rel = qi - key < nb without a test
                 const unsigned w32 = (unsigned)(bits >> (32 * sub)) >> (4 * hi);
                 const float* bp = bl + (qi - jb - 4 * hi);
@@ -305,13 +274,13 @@ __global__ __launch_bounds__(AT_THREADS) AT_FWD_OCC void attn_fwd_kernel(const T
             }
             mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64));
             const float mnew = fmaxf(m, mloc);
-            const float alpha = AT_EXP2(m - mnew);
+            const float alpha = __builtin_amdgcn_exp2f(m - mnew);
             m = mnew;
             float psum = 0.f;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { st[r] = AT_EXP2(st[r] - mnew); psum += st[r]; }
+            for (int r = 0; r < 16; ++r) { st[r] = __builtin_amdgcn_exp2f(st[r] - mnew); psum += st[r]; }
             lsum = lsum * alpha + psum;
-            if (!AT_LEAN || !__all(alpha == 1.0f)) {
+            if (!__all(alpha == 1.0f)) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) { acc[0][e] *= alpha; acc[1][e] *= alpha; }
             }
@@ -405,10 +374,6 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 #pragma unroll
     for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
     const float c = scale * LOG2E;
-#if AT_DBIAS_CARRY
-    float dcarry = 0.f;                    // lower half (t = -31..0) of the previous block's diagonal sums
-    int dcarry_base = i0 + 32;             // i0 - jb of that block (none yet: its bins lie above the table)
-#endif
 
     const int nkt = (i0 + TQ + TKV - 1) / TKV;
     KVRegs<T, false> kr, vr;
@@ -440,7 +405,6 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
             f32x16 st, dp;
 #pragma unroll
             for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
-#if AT_DQ_BATCH
             {   // all eight fragment reads in flight before the first MFMA, retired in two groups: left to hipcc (at the register
                 // ceiling here) every fragment went through the same four registers, one read -> wait -> MFMA at a time (ISA)
                 h16x8 kfr[4], vfr[4];
@@ -453,23 +417,13 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                     dp = MFMA(vfr[s], dof[s], dp);                               // dP^T = V dO^T
                 }
             }
-#else
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                st = MFMA(frag_rows(Ks, 32 * sub, s, lane), qf[s], st);      // S^T  = K Q^T
-                dp = MFMA(frag_rows(Vs, 32 * sub, s, lane), dof[s], dp);     // dP^T = V dO^T
-            }
-#endif
             // three straight passes (gather bias, arithmetic, scatter d(bias)): a fused per-element loop compiled to 16
             // serialised LDS round trips (read -> wait -> exp -> atomic), ~3k cycles per 32x32 block
-#if AT_LEAN
             float bv[16];
             auto element = [&](int r, bool ok) {
                 const float p = __builtin_amdgcn_exp2f(ok ? st[r] * c + bv[r] - L : NEG_BIG);
                 bv[r] = p * (dp[r] - dl);
-#if !AT_DQ_LATE_SCALE
                 st[r] = bv[r] * scale;
-#endif
             };
             if (jb + 31 <= i0) {
                 // subtile entirely below the diagonal (see the forward): constant LDS offsets from one base, one 32-bit mask word
@@ -489,51 +443,16 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                     element(r, (rel >= 0) && ((bits >> kr) & 1ull) && (qi < N));
                 }
             }
-#else
-            float bv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bv[r] = bias_l[max(min(qi - (j0 + 32 * sub + crow(r, hi)), nb - 1), 0)];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int kr = 32 * sub + crow(r, hi);
-                const int rel = qi - (j0 + kr);
-                const bool ok = (rel >= 0) && ((bits >> kr) & 1ull) && (qi < N);
-                const float p = __builtin_amdgcn_exp2f(ok ? st[r] * c + bv[r] - L : NEG_BIG);   // branch-free: 2^-inf = 0
-                bv[r] = p * (dp[r] - dl);                                     // dS (0 where masked)
-                st[r] = bv[r] * scale;
-            }
-#endif
             if (dbias) {
                 // d(bias)[rel] = sum of dS over the diagonal rel = i - j.  LDS float atomics (one per element) cost 930 us
                 // per layer (measured: 1496 -> 565 us without them), so the 63 diagonals of the 32x32 block are summed in
                 // registers instead: output lane L stands for t = q - kr = L - 31 and pulls row kr's element from query
                 // column q = t + kr through the cross-lane permute (no LDS memory access); then ONE plain read-add-write
                 // of the wave-private table, predicated so that every lane owns a distinct bin.
-                const float dsum = (AT_ABLATE & 1) ? bv[0] + bv[15] : diag_sum_32x32(bv, lane);
+                const float dsum = diag_sum_32x32(bv, lane);
                 const int rel = (i0 - j0 - 32 * sub) + (lane - 31);
-#if AT_DBIAS_CARRY
-                // A wave walks its key blocks in order (jb = 0, 32, ...), so a bin rel receives exactly two contributions: lanes
-                // 0..31 of one block (t = -31..0) and lanes 32..63 of the NEXT block (t = 1..32).  The lower half is carried in a
-                // register, moved to the upper lanes with one VALU half-swap and added there: every bin is then WRITTEN once (plain
-                // store) instead of read-modified-written per block (the read -> wait -> add -> write chain measured ~55 us per layer).
-                {
-                    const auto sw = __builtin_amdgcn_permlane32_swap(0u, __float_as_uint(dcarry), false, false);   // [0].hi = dcarry.lo
-                    const float fin = dsum + __uint_as_float(sw[0]);
-                    if (lane >= 32 && rel >= 0 && rel < nb) dbias_l[rel] = fin;
-                    dcarry = dsum;
-                    dcarry_base = i0 - j0 - 32 * sub;
-                }
-#else
-                if (!(AT_ABLATE & 4) && rel >= 0 && rel < nb) dbias_l[rel] += dsum;
-                if (AT_ABLATE & 4) acc[0][0] += dsum * 1e-30f;
-#endif
+                if (rel >= 0 && rel < nb) dbias_l[rel] += dsum;
             }
-#if AT_DQ_LATE_SCALE && AT_LEAN
-            // dS * scale formed only now: during the diagonal sums above only bv (unscaled dS) is live, not bv and st
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { asm volatile("" : "+v"(bv[r])); st[r] = bv[r] * scale; }
-#endif
-#if AT_DQ_BATCH
             {   // the four K^T fragments requested together, the packing of dS under their latency, retired pair by pair
                 h16x8 ktf[2][2], dsb[2];
 #pragma unroll
@@ -549,16 +468,6 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                     for (int dt = 0; dt < 2; ++dt) acc[dt] = MFMA(ktf[s][dt], dsb[s], acc[dt]);   // dQ^T += K^T dS^T
                 }
             }
-#else
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                h16x8 dsb;
-                pack_acc<false>(st, s, dsb, dummy);
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt)
-                    acc[dt] = MFMA(frag_cols_tr(Kt, 32 * sub, s, 32 * dt, lane), dsb, acc[dt]);   // dQ^T += K^T dS^T
-            }
-#endif
         }
     }
     if (!active) return;
@@ -572,13 +481,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                 *(float4*)(drow + d) = make_float4(acc[dt][4 * g4], acc[dt][4 * g4 + 1], acc[dt][4 * g4 + 2], acc[dt][4 * g4 + 3]);
             }
     }
-#if AT_DBIAS_CARRY
-    if (dbias) {        // the last block's lower half: bins dcarry_base - 31 .. dcarry_base (only rel >= 0 exist)
-        const int rel = dcarry_base + (lane - 31);
-        if (lane < 32 && rel >= 0 && rel < nb) dbias_l[rel] = dcarry;
-    }
-#endif
-    if (dbias && !(AT_ABLATE & 2)) {
+    if (dbias) {
         // LDS atomics of this wave are complete in program order for this wave's own later reads
         __builtin_amdgcn_s_waitcnt(0xc07f);
         if (dpart) {
@@ -708,7 +611,6 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
             }
             // three straight passes (gather bias, arithmetic, scatter d(bias)): a fused per-element loop compiled to 16
             // serialised LDS round trips (read -> wait -> exp -> atomic), ~3k cycles per 32x32 block
-#if AT_LEAN
             float bv[16];
             auto element = [&](int r, bool ok) {
                 const float p = __builtin_amdgcn_exp2f(ok ? st[r] * c + bv[r] - L : NEG_BIG);
@@ -733,20 +635,6 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                     element(r, (rel >= 0) && ((bits >> kr) & 1ull) && (qi < N));
                 }
             }
-#else
-            float bv[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bv[r] = bias_l[max(min(qi - (j0 + 32 * sub + crow(r, hi)), nb - 1), 0)];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int kr = 32 * sub + crow(r, hi);
-                const int rel = qi - (j0 + kr);
-                const bool ok = (rel >= 0) && ((bits >> kr) & 1ull) && (qi < N);
-                const float p = __builtin_amdgcn_exp2f(ok ? st[r] * c + bv[r] - L : NEG_BIG);   // branch-free: 2^-inf = 0
-                bv[r] = p * (dp[r] - dl);                                     // dS (0 where masked)
-                st[r] = bv[r] * scale;
-            }
-#endif
             if (dbias) {
                 // d(bias)[rel] = sum of dS over the diagonal rel = i - j.  LDS float atomics (one per element) cost 930 us
                 // per layer (measured: 1496 -> 565 us without them), so the 63 diagonals of the 32x32 block are summed in
@@ -827,7 +715,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
     // an item's 63 bias values are one coalesced load per lane, fetched with the item's Q / dO and parked in a 64-float LDS patch
     // per wave.  Without it the whole [H][N - j0] column set is staged below: 117 KiB for musiclm_large's fine stage
     // (H = 16, N = 1817), i.e. ONE 4-wave workgroup per CU.
-    const bool WIN = AT_LEAN && biasT != nullptr;
+    const bool WIN = biasT != nullptr;
 
     // The rel-pos column of every head goes to LDS once.  (Per-element global gathers of bias / lse / delta -- 48
     // dependent L2 round trips per work item -- were >95 % of this kernel: 26k cycles per item for 16 MFMAs.)
@@ -868,15 +756,10 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
         if (WIN) {      // window of rel = i - j for the item: from (i0 - j0 - 31); table index 64 + rel; lse made relative to m_h
             const float* row = biasT + (size_t)hh * ldT;
             fb = row[64 + ((jt + item / H) * TQ - j0 - 31) + min(lane, 62)];
-#if AT_DKV_FENCE
             fm = row[ldT - 1];      // subtracted where the item is consumed: an arithmetic use here waits for every load issued above
-#else
-            fl -= row[ldT - 1];
-#endif
         }
     };
     if (wave < nitems) fetch(wave, qa, doa, La, Da, Ba, Ma);
-#if AT_DKV_FENCE
     // Consume the first item's loads HERE.  Left pending into the loop, hipcc's wait-count pass has to assume at the loop header
     // that qa / doa / La / Da may still be in flight from this block; its conservative counts (vmcnt(3) ... vmcnt(0) in front of
     // the first MFMA of EVERY item, seen in the ISA) then also drain the NEXT item's loads that the loop has just issued: the
@@ -884,7 +767,6 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 #pragma unroll
     for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(qa[s]), "+v"(doa[s]));
     asm volatile("" : "+v"(La), "+v"(Da), "+v"(Ba), "+v"(Ma));
-#endif
     __syncthreads();                           // bias_s staged
     for (int item = wave; item < nitems; item += 4) {
         const int it = jt + item / H, h = item % H;
@@ -895,8 +777,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
             *(h16x8*)(Qs + tile_off_blk(lane & 31, (2 * s + hi) * 16)) = qa[s];
             *(h16x8*)(dOs + tile_off_blk(lane & 31, (2 * s + hi) * 16)) = doa[s];
         }
-#if AT_LEAN
-        // lean variant (see the forward): the tile's lse / delta go through a 64-float per-wave LDS patch instead of 4 v_readlane +
+        // lean form (see the forward): the tile's lse / delta go through a 64-float per-wave LDS patch instead of 4 v_readlane +
         // 2 selects per score row, and items whose queries all follow this workgroup's keys (all but the first query tile) skip the
         // causal compare, the i < N compare and the clamp of the bias index (constant LDS offsets from one base)
         const float* bh = bias_s + h * nbk;
@@ -917,7 +798,6 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
         const float* lp = ld_l + 4 * hi;
         if (i0 >= j0 + 31 && i0 + 31 < N) {
             const float* bp = WIN ? bwp : bh + (i0 - kj + 4 * hi);
-#if AT_DKV_FENCE
             // gather pass, values pinned, then the arithmetic: with the reads inside `keylive ? ... : NEG_BIG` hipcc wrapped each
             // element's two LDS reads in its own exec-masked block (read, read, wait, fma, wait, subtract: sixteen exposed LDS round
             // trips per item, seen in the ISA); all indices are in range for every lane here, so the reads need no predicate
@@ -938,17 +818,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                 pp[r] = p;
                 st[r] = p * (dp[r] - lp[32 + cr]) * scale;
             }
-#else
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int cr = (r & 3) + 8 * (r >> 2);                     // crow(r, hi) - 4 hi
-                const float p = __builtin_amdgcn_exp2f(keylive ? st[r] * c + bp[cr] - lp[cr] : NEG_BIG);
-                pp[r] = p;
-                st[r] = p * (dp[r] - lp[32 + cr]) * scale;
-            }
-#endif
         } else {
-#if AT_DKV_FENCE
             // diagonal / tail items (16 of a workgroup's items: the first query tile, and the last one when N % 32 != 0).  Written as
             // one loop, `ok ? (expression with two LDS reads) : NEG_BIG` compiled to 16 branches, each around its own read -> wait ->
             // read -> wait (seen in the ISA).  Two passes, the gathered values pinned in registers in between: straight-line code with
@@ -972,48 +842,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                 pp[r] = p;
                 st[r] = p * (dp[r] - lp[32 + cr]) * scale;
             }
-#else
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int cr = (r & 3) + 8 * (r >> 2);
-                const int i = i0 + crow(r, hi);
-                const bool ok = (i >= kj) && keylive && (i < N);
-                const float bvr = WIN ? bwp[cr] : bh[max(min(i - kj, nbk - 1), 0)];
-                const float p = __builtin_amdgcn_exp2f(ok ? st[r] * c + bvr - lp[cr] : NEG_BIG);
-                pp[r] = p;
-                st[r] = p * (dp[r] - lp[32 + cr]) * scale;
-            }
-#endif
         }
-#else
-        const float* bh = bias_s + h * nbk;
-        float bv[16];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) bv[r] = bh[max(min(i0 + crow(r, hi) - kj, nbk - 1), 0)];
-        f32x16 st, dp;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            st = MFMA(qa[s], kf[s], st);       // S  = Q K^T   (rows i, column = this lane's key)
-            dp = MFMA(doa[s], vf[s], dp);      // dP = dO V^T
-        }
-        f32x16 pp;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            // row i = i0 + crow(r, hi): its lse / delta sit in lane crow(r, hi) of La / Da (a wave-uniform lane per half)
-            const float l0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, La), crow(r, 0)));
-            const float l1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, La), crow(r, 1)));
-            const float d0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, Da), crow(r, 0)));
-            const float d1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, Da), crow(r, 1)));
-            const float Li = hi ? l1 : l0, Di = hi ? d1 : d0;
-            const int i = i0 + crow(r, hi);
-            const bool ok = (i >= kj) && keylive && (i < N);
-            const float p = __builtin_amdgcn_exp2f(ok ? st[r] * c + bv[r] - Li : NEG_BIG);      // branch-free: 2^-inf = 0
-            pp[r] = p;
-            st[r] = p * (dp[r] - Di) * scale;     // dS * d(sim)/d(dot)
-        }
-#endif
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             h16x8 pb, dsb;
@@ -1062,7 +891,6 @@ static int set_lds(K kernel, size_t bytes) {
 
 int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                      void* out, float* lse, int B, int N, int H, float scale, hipStream_t st);        // attention2.hip
-static bool attn_v1_forced() { static int f = -1; if (f < 0) { const char* e = getenv("OMLM_ATTN_V1"); f = (e && e[0] == '1') ? 1 : 0; } return f == 1; }
 
 // q [B*N, H*64], k, v [B*N, 64] (dtype), bias [N, bias_ld] fp32 (row = i - j, column = head) or null, keymask [B, N] uint8 or null (1 = attend)
 // biasT: the table prepared by omlm_attn_bias_prepare (bf16 operands take the attention2.hip kernel, which reads it; may be null
@@ -1082,7 +910,7 @@ extern "C" int OMLM_API(omlm_mqa_attn_fwd)(const void* q, const void* k, const v
     if (B <= 0 || N <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
     OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
-    if (dtype == 1 && (biasT || !bias) && !attn_v1_forced())
+    if (dtype == 1 && (biasT || !bias))
         return attn2_fwd_launch(q, k, v, biasT, keymask, out, lse, B, N, H, scale, as_stream(stream));
     dim3 grid((N + TQ - 1) / TQ, (H + 3) / 4, B), block(AT_THREADS);
     int rc;
@@ -1131,8 +959,8 @@ extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const v
     dim3 gridq((N + TQ - 1) / TQ, (H + 3) / 4, B), gridk((N + 31) / 32, 1, B), block(AT_THREADS);
     // windowed bias in the dK / dV kernel only where staging every head's column would cost occupancy (> 80 KiB: one workgroup per CU);
     // below that the staged form measured 2 % faster (B=32, N=1116, H=8: 656 vs 670 us), above it 16 % slower (B=8, N=1817, H=16)
-    const size_t ldsk_staged = 32 * 1024 + (size_t)H * ((N + TQ - 1) / TQ * TQ) * sizeof(float) + (AT_LEAN ? 1024 : 0);
-    const bool win = AT_LEAN && biasT != nullptr && !attn_v1_forced() && ldsk_staged > 80 * 1024;
+    const size_t ldsk_staged = 32 * 1024 + (size_t)H * ((N + TQ - 1) / TQ * TQ) * sizeof(float) + 1024;
+    const bool win = biasT != nullptr && ldsk_staged > 80 * 1024;
     const int ldT = ((64 + N + 2 * 128 + 3) / 4) * 4;                      // layout of omlm_attn_bias_prepare (attention2.hip)
     const size_t ldsq = dq_lds(N, dtype == 0);
     const size_t ldsk = win ? 32 * 1024 + 4 * 128 * sizeof(float)
@@ -1158,11 +986,7 @@ extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const v
         // The attention2.hip kernel (8 heads per workgroup sharing LDS-DMA-staged K / V tiles) wherever its LDS plan fits: with the Horner
         // diagonal sums and the d(bias) workspace it is the faster one at both bench shapes (B=32, N=1116, H=8: whole backward 432 against
         // 456 us; before those two changes both kernels spent ~160 us per layer in d(bias) and the first-generation kernel led 316 : 334).
-        // OMLM_ATTN_DQ2=0 keeps the first-generation kernel (A/B).
-        static int dq2 = -1;
-        if (dq2 < 0) { const char* e = getenv("OMLM_ATTN_DQ2"); dq2 = (e && e[0] == '0') ? 0 : 1; }
-        const bool use2 = dq2 == 1;
-        if (use2 && (biasT || !bias) && !attn_v1_forced()) {
+        if (biasT || !bias) {
             r2 = attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st);
             if (r2 < 0) return r2;
         }
@@ -1174,7 +998,7 @@ extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const v
         // dK / dV: the third-generation kernel (attention3.hip: 128 keys per workgroup, Q / dO staged once per workgroup by LDS-DMA) where the
         // prepared table is there (or there is no bias); else the second-generation kernel
         int r3 = 1;
-        if ((biasT || !bias) && !attn_v1_forced()) {
+        if (biasT || !bias) {
             r3 = attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st);
             if (r3 < 0) return r3;
         }

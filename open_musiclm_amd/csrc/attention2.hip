@@ -25,19 +25,6 @@ namespace OMLM_NS {
 #define A2_LOG2E 1.4426950408889634f
 #define A2_STAGE (8192 + 8192 + 8 * A2_BWIN * 4)     /* K rows | V blocked | bias window = 20 KiB */
 #define A2_NST 3
-#ifndef A2_DQ_PK
-#define A2_DQ_PK 1           /* backward dQ kernel: element arithmetic on register pairs (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32), -lse and -delta carried
-                                in by the accumulators' initial values, the softmax scale applied once to dQ instead of to every dS */
-#endif
-#ifndef A2_DQ_BATCH
-#define A2_DQ_BATCH 1        /* backward dQ kernel: fragment / bias reads issued in batches (scheduling only, same arithmetic) */
-#endif
-#ifndef A2_SUBFENCE
-#define A2_SUBFENCE 0
-#endif
-#ifndef A2_ABLATE
-#define A2_ABLATE 0          /* profiling builds only: 1 = skip the tile arithmetic, 2 = skip the steady-state DMA, 4 = no exp2; dQ kernel: 8 = no diagonal sums, 16 = no per-block table update, 32 = no global d(bias) flush */
-#endif
 
 #define MFMA16(a, b, c) OMLM_MFMA_32x32x16(a, b, c)
 
@@ -254,7 +241,7 @@ __device__ __forceinline__ void a4_tile(A4Acc& A, const h16x8 (&qf)[2][4], const
             if (FIXED) {
                 if (!diag) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) st[r] = (A2_ABLATE & 4) ? st[r] * c + bp[27 - ((r & 3) + 8 * (r >> 2))] : __builtin_amdgcn_exp2f(st[r] * c + bp[27 - ((r & 3) + 8 * (r >> 2))]);
+                    for (int r = 0; r < 16; ++r) st[r] = __builtin_amdgcn_exp2f(st[r] * c + bp[27 - ((r & 3) + 8 * (r >> 2))]);
                 } else {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
@@ -472,8 +459,7 @@ __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* _
         __builtin_amdgcn_s_barrier();
         int lane_ = lane;                                      // opaque per tile: every lane-derived address is rebuilt, none carried (see A4Stager)
         asm volatile("" : "+v"(lane_));
-        if (t + 2 < nkt && !(A2_ABLATE & 2)) issue(t + 2, lane_);
-        if (A2_ABLATE & 1) continue;
+        if (t + 2 < nkt) issue(t + 2, lane_);
         const char* Ks = ring + (t % A2_NST) * A2_STAGE;
         const int j0 = t * A2_TKV;
         const bool full = j0 + A2_TKV - 1 <= i0;               // every block of the tile lies below the diagonal
@@ -613,7 +599,6 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
 #pragma unroll
     for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
     const float c = scale * A2_LOG2E;
-    const float qscale = (A2_DQ_PK && A2_DQ_BATCH) ? scale : 1.f;      // dQ = scale dS K: taken out of the element loop
 
     for (int t = 0; t < nkt; ++t) {
         if (t + 1 < nkt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -633,7 +618,6 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
             f32x16 st, dp;
 #pragma unroll
             for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
-#if A2_DQ_BATCH
             {   // all eight fragment reads in flight before the first MFMA, retired in two groups (hipcc issued them one at a time
                 // through the same four registers: read -> wait -> MFMA, seen in the ISA)
                 h16x8 kfr[4], vfr[4];
@@ -646,13 +630,6 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
                     dp = MFMA16(vfr[s], dof[s], dp);                              // dP^T = V dO^T
                 }
             }
-#else
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                st = MFMA16(a2_frag_rows(Kr, 32 * sub, s, lane), qf[s], st);      // S^T  = K Q^T
-                dp = MFMA16(a2_frag_rows(Vr, 32 * sub, s, lane), dof[s], dp);     // dP^T = V dO^T
-            }
-#endif
             const float* bp = bw + (64 - 32 * sub) + ql - 4 * hi;
             const float* mp = mb + jb + 4 * hi;
             float bv[16];
@@ -661,22 +638,19 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
             float4 m4s[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) m4s[g] = *(const float4*)(mp + 8 * g);
-#if A2_DQ_BATCH
             float bpv[16];                     // bias window gathered in one pass (see m4s: nothing waits element by element)
 #pragma unroll
             for (int r = 0; r < 16; ++r) bpv[r] = bp[-((r & 3) + 8 * (r >> 2))];
 #pragma unroll
             for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(bpv[r]));
-#if A2_DQ_PK
             if (diag) {                        // the block on the diagonal: keys above it leave through the bias term (a real branch: one block in nkt)
                 int d0v = d0;
                 asm volatile("" : "+v"(d0v));             // the selects depend on a value defined inside the branch: hipcc otherwise hoists all 16 of them in front of it
 #pragma unroll
                 for (int r = 0; r < 16; ++r) bpv[r] = (d0v - ((r & 3) + 8 * (r >> 2)) >= 0) ? bpv[r] : A2_NEG;
             }
-#endif
-#endif
-#if A2_DQ_PK && A2_DQ_BATCH
+            // element arithmetic on register pairs (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32); the softmax scale is applied once to
+            // dQ (dQ = scale dS K) instead of to every dS
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const float4 m4 = m4s[g];
@@ -692,36 +666,14 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
                     st[r] = ds2[0]; st[r + 1] = ds2[1];
                 }
             }
-#else
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 m4 = m4s[g];
-                const float mm[4] = {m4.x, m4.y, m4.z, m4.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * g + e, cr = e + 8 * g;
-#if A2_DQ_BATCH
-                    float x = st[r] * c + bpv[r] + (mm[e] - Lp);
-#else
-                    float x = st[r] * c + bp[-cr] + (mm[e] - Lp);
-#endif
-                    if (diag) x = (d0 - cr >= 0) ? x : A2_NEG;
-                    const float pr = __builtin_amdgcn_exp2f(x);
-                    bv[r] = pr * (dp[r] - dl);                                    // dS (0 where masked)
-                    st[r] = bv[r] * scale;
-                }
-            }
-#endif
             if (dbias) {
                 // d(bias)[rel] = sum of dS over the diagonal rel = i - j: output lane L stands for t = q - kr = L - 31 and pulls row
                 // kr's element from query column q = t + kr through the cross-lane permute; then one read-add-write of this
                 // wave's private table (every lane owns a distinct bin)
-                const float dsum = (A2_ABLATE & 8) ? bv[0] + bv[15] : diag_sum_32x32(bv, lane);
+                const float dsum = diag_sum_32x32(bv, lane);
                 const int rel = (i0 - jb) + (lane - 31);
-                if (!(A2_ABLATE & 16) && rel >= 0 && rel < nb) dbw[rel] += dsum;
-                if (A2_ABLATE & 16) acc[0][0] += dsum * 1e-30f;      // (ds_add_f32 instead of this read-add-write: measured 20 us per layer SLOWER)
+                if (rel >= 0 && rel < nb) dbw[rel] += dsum;      // (ds_add_f32 instead of this read-add-write: measured 20 us per layer SLOWER)
             }
-#if A2_DQ_BATCH
             {
                 h16x8 ktf[2][2], dsb[2];
 #pragma unroll
@@ -735,14 +687,6 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
                     acc[1] = MFMA16(ktf[s][1], dsb[s], acc[1]);
                 }
             }
-#else
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const h16x8 dsb = a2_pack(st, s);
-                acc[0] = MFMA16(a2_frag_cols_tr(Kb, 32 * sub, s, 0, lane), dsb, acc[0]);       // dQ^T += K^T dS^T
-                acc[1] = MFMA16(a2_frag_cols_tr(Kb, 32 * sub, s, 32, lane), dsb, acc[1]);
-            }
-#endif
         }
     }
     if (!active) return;
@@ -753,10 +697,10 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
                 const int d = 32 * dt + 8 * g4 + 4 * hi;
-                *(float4*)(drow + d) = make_float4(qscale * acc[dt][4 * g4], qscale * acc[dt][4 * g4 + 1], qscale * acc[dt][4 * g4 + 2], qscale * acc[dt][4 * g4 + 3]);
+                *(float4*)(drow + d) = make_float4(scale * acc[dt][4 * g4], scale * acc[dt][4 * g4 + 1], scale * acc[dt][4 * g4 + 2], scale * acc[dt][4 * g4 + 3]);
             }
     }
-    if (dbias && !(A2_ABLATE & 32)) {
+    if (dbias) {
         __builtin_amdgcn_s_waitcnt(0xc07f);                   // this wave's LDS updates are complete for its own reads
         if (dpart) {                                          // one row of the partial buffer (see attention.hip's dQ kernel): plain stores
             float* prow = dpart + (((size_t)b * H + h) * nqt + qt) * (size_t)(nqt * 32);

@@ -94,13 +94,11 @@ void attn3_bwd_dkv_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__
     // XCD-aware: the workgroups of one sample share its Q / dO tiles through an XCD's L2 (workgroup i runs on XCD i % 8); dealt in launch
     // order every XCD fetched every sample's Q and dO
     int lg = blockIdx.x;
-#ifndef A3_NOXCD
     {
         const int total = B * wg_per_sample, lin = blockIdx.x;
         const int qq = total >> 3, rr = total & 7, xcd = lin & 7, idx = lin >> 3;
         lg = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
     }
-#endif
     const int b = lg / wg_per_sample;
     int rem = lg - b * wg_per_sample, r = 0, chunk = 0;
     for (;; ++r) {                                            // uniform scalar scan: which key range this workgroup belongs to
@@ -285,9 +283,6 @@ __global__ __launch_bounds__(256) void a3_zero_kernel(float4* __restrict__ p, si
 }
 
 static int a3_chunk(int B, int N) {
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("OMLM_ATTN3_CH"); forced = e ? atoi(e) : 0; }
-    if (forced > 0) return forced;
     const int nqt = (N + 31) / 32, nr = (N + A3_KR - 1) / A3_KR;
     long long units = 0;
     for (int r = 0; r < nr; ++r) units += nqt - 4 * r;
@@ -302,9 +297,7 @@ static int a3_chunk(int B, int N) {
 int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                          const void* dout, const float* lse, const float* delta, float* dk, float* dv,
                          int B, int N, int H, float scale, hipStream_t st) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("OMLM_ATTN_DKV3"); off = (e && e[0] == '0') ? 1 : 0; }
-    if (off || N < 32 || (long long)B * N * H * 128 >= (1ll << 32)) return 1;      // (32-bit byte offsets into q / dout)
+    if (N < 32 || (long long)B * N * H * 128 >= (1ll << 32)) return 1;      // (32-bit byte offsets into q / dout)
     const int ldT = ((A3_PAD + N + 2 * 128 + 3) / 4) * 4;    // layout of omlm_attn_bias_prepare (attention2.hip)
     const int CH = a3_chunk(B, N);
     const int nqt = (N + 31) / 32, nr = (N + A3_KR - 1) / A3_KR;
@@ -316,8 +309,7 @@ int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const floa
     // Zero fill by a KERNEL of this library, not hipMemsetAsync: as a memset node of a captured micro-step the fill detached everything
     // behind it from the graph's completion -- the rest of the backward (this layer's dK / dV onwards) was still running when the launch
     // had "finished" and the optimizer's kernels started (round 4: after one fp16 overflow the skipped step's gradient clear raced with
-    // those late writes and every later step stayed non-finite; OMLM_ATTN_DKV3=0, i.e. no memset node, or a host sync after the replay,
-    // cured it).  A kernel node is ordered like every other launch.
+    // those late writes and every later step stayed non-finite; no memset node, or a host sync after the replay, cured it).  A kernel node is ordered like every other launch.
     const size_t gfloats = (size_t)B * N * 64;
     auto fill = [&](float* p, size_t n) {
         const size_t n4 = n / 4;                               // n = B N 64: a multiple of 4; rows are 256-byte aligned

@@ -135,58 +135,32 @@ __device__ __forceinline__ float wave_max_dpp(float v) {
     return fmaxf(fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 0)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 16))),
                  fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 32)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 48))));
 }
-// OMLM_WAVE_DPP=1: every wave_sum / wave_max of the library takes the DPP form (build-time A/B switch)
-#ifndef OMLM_WAVE_DPP
-#define OMLM_WAVE_DPP 0
-#endif
+// wave_sum / wave_max: __shfl_xor ladders, correct in partial waves; the DPP forms above serve kernels whose waves are always full
 __device__ __forceinline__ float wave_sum(float v) {
-#if OMLM_WAVE_DPP
-    return wave_sum_dpp(v);
-#else
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
-#endif
 }
 __device__ __forceinline__ float wave_max(float v) {
-#if OMLM_WAVE_DPP
-    return wave_max_dpp(v);
-#else
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
-#endif
 }
 
 // d(bias) of the attention backward: the 63 diagonal sums of a 32x32 block of dS^T held in the MFMA C-layout (lane = query column
-// q = lane & 31, bv[r] = key row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)).  Output lane L stands for t = q - kr = L - 31 and pulls row
-// kr's element from query column q = t + kr of the half-wave that holds that row: source lane (L - 31 + kr + 32 hh) mod 64 with
-// hh = (kr >> 2) & 1.  ds_bpermute_b32 adds its immediate offset to the byte address, so ONE address register (4 * lane) serves all 32
-// permutes; hipcc's __shfl form spends an index register plus two address VALU ops per permute (32 VGPRs, 64 of the ~130 VALU
-// instructions of the loop, seen in the ISA; with the asm form the bf16 dQ kernel stops spilling: 20 -> 0 VGPRs).  The permutes are
-// inline asm, i.e. invisible to hipcc's lgkmcnt bookkeeping: issued back to back and retired by the s_waitcnt of this function.
-// MEASURED (MI355X, B = 32, N = 1116, H = 8): parity green (6 / 6 attention tests), backward 665.6 us against 665.4 us with __shfl --
-// no gain: the ~150 us of d(bias) are the 32 LDS-crossbar permutes themselves, not their address arithmetic or the spills.  The asm
-// form is therefore OFF by default (a hidden load is a liability where registers spill: the fp32 kernel still spills 48);
-// -DOMLM_DIAG_ASM=1 selects it.
-#ifndef OMLM_DIAG_ASM
-#define OMLM_DIAG_ASM 0
-#endif
-#define OMLM_BPERM(KR) asm volatile("ds_bpermute_b32 %0, %1, %2 offset:%3" : "=v"(got[KR]) : "v"(base), \
-        "v"(bv[4 * ((KR) >> 3) + ((KR) & 3)]), "i"(4 * (((KR) - 31 + 32 * (((KR) >> 2) & 1)) & 63)))
+// q = lane & 31, bv[r] = key row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)).  Output lane L stands for t = q - kr = L - 31.
+// MEASURED (MI355X, B = 32, N = 1116, H = 8): the ~150 us of d(bias) in the backward were the 32 LDS-crossbar permutes per block of a
+// __shfl form (an inline-asm ds_bpermute form changed nothing: 665.6 against 665.4 us); the Horner form below takes 42 us per layer.
 // Horner form on the VALU (no LDS crossbar): row kr's 32 values must move from lanes q (rows of the lower half-wave) / 32 + q (rows of
 // the upper half-wave) to lanes q - kr + 31.  For the lower rows that is a right shift by 31 - kr, for the upper rows a left shift by
 // kr + 1; taken in order of decreasing shift, each row is added after the running sum has been shifted by the difference (1 inside a
 // group of four rows, 5 between groups): two chains of 15 DPP adds + 16 plain DPP shifts (wave_shr:1 / wave_shl:1, zero fill) on
-// half-masked copies of the registers.  -DOMLM_DIAG_HORNER=1.
-#ifndef OMLM_DIAG_HORNER
-#define OMLM_DIAG_HORNER 1
-#endif
+// half-masked copies of the registers.
 template <int CTRL>
 __device__ __forceinline__ float dpp_shift1(float v) {       // CTRL 0x138: lane i <- lane i - 1 (lane 0 <- 0); 0x130: lane i <- lane i + 1
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
 }
-__device__ __forceinline__ float diag_sum_32x32_horner(const float (&bv)[16], int lane) {
+__device__ __forceinline__ float diag_sum_32x32(const float (&bv)[16], int lane) {
     // half-masked copies by packed multiplies with {1, 0} lane constants (16 v_pk_mul_f32 instead of 32 v_cndmask_b32; dS is finite)
     const float mlo = lane < 32 ? 1.f : 0.f, mhi = 1.f - mlo;
     float va[16], vb[16];
@@ -220,41 +194,6 @@ __device__ __forceinline__ float diag_sum_32x32_horner(const float (&bv)[16], in
     for (int g = 0; g < 5; ++g) b = dpp_shift1<0x130>(b);    // the last row (kr = 4) needs 4 + 1
     return a + b;
 }
-__device__ __forceinline__ float diag_sum_32x32(const float (&bv)[16], int lane) {
-#if OMLM_DIAG_HORNER
-    return diag_sum_32x32_horner(bv, lane);
-#endif
-    float dsum = 0.f;
-#if OMLM_DIAG_ASM
-    float got[32];
-    const int base = lane << 2;
-    OMLM_BPERM(0); OMLM_BPERM(1); OMLM_BPERM(2); OMLM_BPERM(3); OMLM_BPERM(4); OMLM_BPERM(5); OMLM_BPERM(6); OMLM_BPERM(7);
-    OMLM_BPERM(8); OMLM_BPERM(9); OMLM_BPERM(10); OMLM_BPERM(11); OMLM_BPERM(12); OMLM_BPERM(13); OMLM_BPERM(14); OMLM_BPERM(15);
-    OMLM_BPERM(16); OMLM_BPERM(17); OMLM_BPERM(18); OMLM_BPERM(19); OMLM_BPERM(20); OMLM_BPERM(21); OMLM_BPERM(22); OMLM_BPERM(23);
-    OMLM_BPERM(24); OMLM_BPERM(25); OMLM_BPERM(26); OMLM_BPERM(27); OMLM_BPERM(28); OMLM_BPERM(29); OMLM_BPERM(30); OMLM_BPERM(31);
-    // retire them: the wait names the first 16 destinations, the empty statement behind it the other 16, so that no consumer of
-    // any of them is scheduled above the wait (cdna_hip_programming.md 5.7: loads hidden from hipcc, form (ii))
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(got[0]), "+v"(got[1]), "+v"(got[2]), "+v"(got[3]), "+v"(got[4]), "+v"(got[5]), "+v"(got[6]),
-                 "+v"(got[7]), "+v"(got[8]), "+v"(got[9]), "+v"(got[10]), "+v"(got[11]), "+v"(got[12]), "+v"(got[13]), "+v"(got[14]), "+v"(got[15]));
-    asm volatile("" : "+v"(got[16]), "+v"(got[17]), "+v"(got[18]), "+v"(got[19]), "+v"(got[20]), "+v"(got[21]), "+v"(got[22]), "+v"(got[23]),
-                 "+v"(got[24]), "+v"(got[25]), "+v"(got[26]), "+v"(got[27]), "+v"(got[28]), "+v"(got[29]), "+v"(got[30]), "+v"(got[31]));
-#pragma unroll
-    for (int kr = 0; kr < 32; ++kr) {
-        const int src = lane - 31 + kr;
-        dsum += (src >= 0 && src < 32) ? got[kr] : 0.f;
-    }
-#else
-#pragma unroll
-    for (int kr = 0; kr < 32; ++kr) {
-        const int r = 4 * (kr >> 3) + (kr & 3), hh = (kr >> 2) & 1;
-        const int src = lane - 31 + kr;
-        const float got = __shfl(bv[r], (32 * hh + src) & 63, 64);
-        dsum += (src >= 0 && src < 32) ? got : 0.f;
-    }
-#endif
-    return dsum;
-}
-
 // block-wide sum for blockDim.x == NT (multiple of 64); `red` is >= NT/64 floats of LDS.
 template <int NT>
 __device__ __forceinline__ float block_sum(float v, float* red) {

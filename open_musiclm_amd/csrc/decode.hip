@@ -20,14 +20,8 @@
 // The step kernels are single dependent chains (load -> LayerNorm statistics -> dot products -> reduction -> store): the wave
 // reductions run on the VALU (DPP row steps + readlanes) instead of six dependent ds_bpermute round trips each.  Measured on the
 // B = 1 step (MI355X, tools/decode_probe.py, same box): 154.6 -> 145.8 us per id with the three reductions of the GEMV kernels alone.
-// -DDEC_DPP_SUM=0 restores the __shfl ladders.
-#ifndef DEC_DPP_SUM
-#define DEC_DPP_SUM 1
-#endif
-#if DEC_DPP_SUM
 #define wave_sum(x) wave_sum_dpp(x)
 #define wave_max(x) wave_max_dpp(x)
-#endif
 #include <stdlib.h>
 #include <type_traits>
 
@@ -500,7 +494,7 @@ __global__ __launch_bounds__(DEC_T) void dec_ffin_kernel(const float* __restrict
 }
 
 // =========================================================================================================================
-// Second-generation step kernels (default; OMLM_DECODE_V1=1 selects the ones above).  The first generation measured 8-15 us per
+// Second-generation step kernels (every geometry they serve; the ones above take the rest).  The first generation measured 8-15 us per
 // launch for ~1 us of memory time, because every latency in a workgroup was serialised: stage the activation (global load ->
 // two block reductions for LayerNorm -> barrier), THEN start the weight loads, 16 rows per workgroup in a rolled loop of
 // load -> wait -> FMA (5.4 round trips for the FF-out rows), then 4 x B serial wave reductions.  Here
@@ -512,16 +506,9 @@ __global__ __launch_bounds__(DEC_T) void dec_ffin_kernel(const float* __restrict
 #define DEC2_ROWS 4
 
 template <typename TW> struct dec_wreg;
-#ifndef OMLM_DEC_NT
-#define OMLM_DEC_NT 0          // 1: weight rows of the B = 1 kernels as non-temporal loads (A/B: tools/build_ab.sh nt decode.hip -DOMLM_DEC_NT=1)
-#endif
 template <> struct dec_wreg<h16_t> { u32x4 r;
     __device__ __forceinline__ void load(const h16_t* p) {
-#if OMLM_DEC_NT
-        r = __builtin_nontemporal_load((const u32x4*)p);
-#else
         r = *(const u32x4*)p;
-#endif
     }
     __device__ __forceinline__ void zero() { r[0] = r[1] = r[2] = r[3] = 0u; }
     __device__ __forceinline__ void unpack(float* w) const {
@@ -739,24 +726,22 @@ static void dec2_launch(const dec2_args& a, int grid, hipStream_t st) {
 
 // ---- B == 1 fast path: no LDS, no barrier.  Every wave loads the whole activation row itself (L2 hits; exactly the pieces its
 // dot product multiplies), takes the LayerNorm statistics with two wave reductions, and finishes its own output element:
-// one memory round trip between launch and store.  FF-in: a wave owns one CHANNEL (its value row and its gate row), so the
-// conv / GEGLU epilogue needs no exchange either.
+// one memory round trip between launch and store.  FF-in rows: dec3_ffin_kernel below.
 
 template <typename TW, int NI, int MODE, bool PL = false>
 __global__ __launch_bounds__(DEC_T) void dec3_kernel(dec2_args a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int K = a.K, nch = K >> 3;
-    const int unit = blockIdx.x * 4 + wave;           // output row (FF-in: channel)
+    const int unit = blockIdx.x * 4 + wave;           // output row
     const int HD = a.H * 64;
-    if (unit >= (MODE == DEC2_FFIN ? a.Fp : a.Nout)) return;
+    if (unit >= a.Nout) return;
     bool ln_row = a.gamma != nullptr;
     const TW* wrow;
-    const TW* wrow2 = nullptr;
-    if (MODE == DEC2_FFIN) { wrow = (const TW*)a.W + (size_t)unit * a.ldw; wrow2 = (const TW*)a.W + (size_t)(a.Fp + unit) * a.ldw; }
-    else if (MODE == DEC2_QKV) { ln_row = unit < HD; wrow = unit < HD ? (const TW*)a.W + (size_t)unit * a.ldw : (const TW*)a.W2 + (size_t)(unit - HD) * a.ldw; }
+    if (MODE == DEC2_QKV) { ln_row = unit < HD; wrow = unit < HD ? (const TW*)a.W + (size_t)unit * a.ldw : (const TW*)a.W2 + (size_t)(unit - HD) * a.ldw; }
     else wrow = (const TW*)a.W + (size_t)unit * a.ldw;
-    static_assert(!PL || MODE == DEC2_LNGEMV, "lo planes: the LayerNorm + row-product launches (FF-out, head); FF-in has dec3_ffin_kernel");
-    dec_wreg<TW> wr[NI], wr2[MODE == DEC2_FFIN ? NI : 1], wl[PL ? NI : 1];
+    static_assert(MODE != DEC2_FFIN, "FF-in rows have dec3_ffin_kernel");
+    static_assert(!PL || MODE == DEC2_LNGEMV, "lo planes: the LayerNorm + row-product launches (FF-out, head)");
+    dec_wreg<TW> wr[NI], wl[PL ? NI : 1];
     float4 g0[NI], g1[NI], x0[NI], x1[NI];
     // activation row and gamma FIRST, the weight rows behind them: vector-memory results retire in issue order, so the LayerNorm
     // statistics (two wave reductions) start when the L2-resident row has landed and run under the weight fetch from HBM
@@ -778,22 +763,15 @@ __global__ __launch_bounds__(DEC_T) void dec3_kernel(dec2_args a) {
         const int cc = ok ? c : 0;
         wr[i].load(wrow + cc * 8);
         if (PL) { wl[i].load((const TW*)a.Wlo + (size_t)unit * a.ldw + cc * 8); if (!ok) wl[i].zero(); }
-        if (MODE == DEC2_FFIN) wr2[i].load(wrow2 + cc * 8);
-        if (!ok) { wr[i].zero(); if (MODE == DEC2_FFIN) wr2[i].zero(); }
+        if (!ok) wr[i].zero();
     }
     __builtin_amdgcn_sched_barrier(0);
     // epilogue operands requested now as well (lane 0 consumes them)
-    float resv = 0.f, h0v = 0.f, h0g = 0.f, h1v = 0.f, h1g = 0.f, cw[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float resv = 0.f;
     int pos = 0;
-    const int ld = 2 * a.Fp;
     if (lane == 0) {
         if (MODE == DEC2_LNGEMV && a.res) resv = a.res[unit];
         if (MODE == DEC2_QKV) pos = *a.pos_dev;
-        if (MODE == DEC2_FFIN) {
-            h0v = a.hist[unit]; h0g = a.hist[a.Fp + unit]; h1v = a.hist[ld + unit]; h1g = a.hist[ld + a.Fp + unit];
-#pragma unroll
-            for (int t = 0; t < 3; ++t) { cw[t] = a.convw[(size_t)t * ld + unit]; cw[3 + t] = a.convw[(size_t)t * ld + a.Fp + unit]; }
-        }
     }
     float mean = 0.f, rstd = 1.f;
     if (ln_row) {
@@ -809,10 +787,10 @@ __global__ __launch_bounds__(DEC_T) void dec3_kernel(dec2_args a) {
         mean = s / (float)a.Kstat;
         rstd = rsqrtf(fmaxf(q / (float)a.Kstat - mean * mean, 0.f) + a.eps);
     }
-    float acc = 0.f, acc2 = 0.f;
+    float acc = 0.f;
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-        float w[8], w2[8];
+        float w[8];
         wr[i].unpack(w);
         if (PL) {
             float wlo[8];
@@ -820,7 +798,6 @@ __global__ __launch_bounds__(DEC_T) void dec3_kernel(dec2_args a) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) w[e] += wlo[e];
         }
-        if (MODE == DEC2_FFIN) wr2[i].unpack(w2);
         float x[8] = {x0[i].x, x0[i].y, x0[i].z, x0[i].w, x1[i].x, x1[i].y, x1[i].z, x1[i].w};
         if (ln_row) {
             const float gm[8] = {g0[i].x, g0[i].y, g0[i].z, g0[i].w, g1[i].x, g1[i].y, g1[i].z, g1[i].w};
@@ -831,19 +808,11 @@ __global__ __launch_bounds__(DEC_T) void dec3_kernel(dec2_args a) {
             for (int e = 0; e < 8; ++e) x[e] = round_if(x[e], 1);
         }
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { acc += w[e] * x[e]; if (MODE == DEC2_FFIN) acc2 += w2[e] * x[e]; }
+        for (int e = 0; e < 8; ++e) acc += w[e] * x[e];
     }
     acc = wave_sum(acc);
-    if (MODE == DEC2_FFIN) acc2 = wave_sum(acc2);
     if (lane != 0) return;
-    if (MODE == DEC2_FFIN) {
-        const float hv = round_if(acc, a.round_bf16), hg = round_if(acc2, a.round_bf16);
-        const float uv = cw[0] * h0v + cw[1] * h1v + cw[2] * hv;
-        const float ug = cw[3] * h0g + cw[4] * h1g + cw[5] * hg;
-        a.u[unit] = dec_gelu(ug) * uv;
-        a.hist[unit] = h1v;            a.hist[a.Fp + unit] = h1g;
-        a.hist[ld + unit] = hv;        a.hist[ld + a.Fp + unit] = hg;
-    } else if (MODE == DEC2_QKV) {
+    if (MODE == DEC2_QKV) {
         if (unit < HD) a.q[unit] = acc;
         else if (unit < HD + 64) a.Kc[(size_t)pos * 64 + (unit - HD)] = acc;                     // raw: normalised by dec_attn
         else a.Vc[(size_t)pos * 64 + (unit - HD - 64)] = round_if(acc, a.round_bf16);
@@ -1393,12 +1362,10 @@ static void dec4_launch(const dec2_args& a, int grid, hipStream_t st) {
 }
 // the matrix-core step kernels serve 16-bit weights with D, H * 64, Fp multiples of 32 and k-loops of at most 4 x 24 steps
 static bool dec4_ok(const omlm_decode_args& a) {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("OMLM_DECODE_MFMA"); off = (e && e[0] == '0') ? 1 : 0; }
     // B > 8: every LayerNorm in front of a matrix-core kernel must find its statistics in the producers' partials (the own-reduction
     // path stages fp32 rows for at most 8 samples): a.ln_parts given
     const bool wide_ok = a.B <= 8 || a.ln_parts != nullptr;
-    return !off && a.B >= 2 && a.B <= DEC4_NB && wide_ok && a.D % 32 == 0 && a.D <= 1024 && (a.H * 64) % 32 == 0 && a.H * 64 <= 1024 &&
+    return a.B >= 2 && a.B <= DEC4_NB && wide_ok && a.D % 32 == 0 && a.D <= 1024 && (a.H * 64) % 32 == 0 && a.H * 64 <= 1024 &&
            a.Fp % 32 == 0 && a.Fp <= 3072 && a.Fp % 8 == 0;
 }
 
@@ -1433,12 +1400,10 @@ static int decode_step2_t(const omlm_decode_args& a, const long long* ids, hipSt
     // "fp16ff": FF-in / FF-out / head read W = hi + lo and keep their activations and h1 un-rounded (round_bf16 = 0 for those launches)
     const bool pl = a.W1p_lo != nullptr;
     // FF-out rows cut into four k-slices (see dec4_kernel): the matrix-core kernels with the producers' LayerNorm partials, scratch given
-    static int sk_off = -1;
-    if (sk_off < 0) { const char* e = getenv("OMLM_DECODE_SPLITK"); sk_off = (e && e[0] == '0') ? 1 : 0; }
-    const bool split = !sk_off && mfma && st_x && a.splitk_ws && a.splitk_cnt && (Fp >> 5) >= 8;
+    const bool split = mfma && st_x && a.splitk_ws && a.splitk_cnt && (Fp >> 5) >= 8;
     if (pl) {
         OMLM_CHECK_ARG(sizeof(TW) == 2 && a.W2p_lo && (!a.head_W || a.head_W_lo), "lo planes: 16-bit weights, all three families");
-        OMLM_CHECK_ARG(B == 1 || (mfma && st_x), "lo planes at B >= 2 run on the matrix-core step kernels (ln_parts given, OMLM_DECODE_MFMA unset)");
+        OMLM_CHECK_ARG(B == 1 || (mfma && st_x), "lo planes at B >= 2 run on the matrix-core step kernels (ln_parts given)");
         OMLM_CHECK_ARG(Fp <= 3072, "lo planes: feed-forward width <= 3072");
     }
     for (int l = 0; l < a.L; ++l) {
@@ -1468,22 +1433,12 @@ static int decode_step2_t(const omlm_decode_args& a, const long long* ids, hipSt
         if (st_x1) { f.stat_in = st_x1; f.nstat_in = npd; f.stat_out = st_u; }
         if (pl) { f.Wlo = a.W1p_lo[l]; f.round_bf16 = 0; }
         if constexpr (sizeof(TW) == 2) {
-            if (pl && B == 1) {
-                static int cpwl = -1;
-                if (cpwl < 0) { const char* e = getenv("OMLM_DECODE_CPW_PL"); cpwl = e ? atoi(e) : 2; }
-                if (cpwl == 4) hipLaunchKernelGGL((dec3_ffin_kernel<TW, 4, true>), dim3((Fp + 15) / 16), dim3(DEC_T), 0, st, f);
-                else           hipLaunchKernelGGL((dec3_ffin_kernel<TW, 2, true>), dim3((Fp + 7) / 8), dim3(DEC_T), 0, st, f);
-            }
+            if (pl && B == 1) hipLaunchKernelGGL((dec3_ffin_kernel<TW, 2, true>), dim3((Fp + 7) / 8), dim3(DEC_T), 0, st, f);
             else if (pl)      dec4_launch<8, DEC2_FFIN, true>(f, (Fp + 7) / 8, st);
         }
         if (pl) {
-        } else if (B == 1) {
-            static int cpw = -1;
-            if (cpw < 0) { const char* e = getenv("OMLM_DECODE_CPW"); cpw = e ? atoi(e) : 4; }
-            if (cpw == 4)      hipLaunchKernelGGL((dec3_ffin_kernel<TW, 4>), dim3((Fp + 15) / 16), dim3(DEC_T), 0, st, f);
-            else if (cpw == 2) hipLaunchKernelGGL((dec3_ffin_kernel<TW, 2>), dim3((Fp + 7) / 8), dim3(DEC_T), 0, st, f);
-            else               dec3_launch<TW, 2, DEC2_FFIN>(f, Fp, st);
-        } else if (mfma) dec4_launch<8, DEC2_FFIN>(f, (Fp + 7) / 8, st);
+        } else if (B == 1) hipLaunchKernelGGL((dec3_ffin_kernel<TW, 4>), dim3((Fp + 15) / 16), dim3(DEC_T), 0, st, f);
+        else if (mfma) dec4_launch<8, DEC2_FFIN>(f, (Fp + 7) / 8, st);
         else dec2_launch<TW, 2, DEC2_FFIN>(f, Fp / 2, st);
         dec2_args w = g;                                                               // x = x1 + LN(u) W2^T
         w.in = a.u; w.ldin = Fp; w.K = Fp; w.Kstat = a.F; w.gamma = a.mid_gamma[l]; w.W = a.W2p[l]; w.ldw = Fp; w.Nout = D;
@@ -1606,13 +1561,11 @@ extern "C" int OMLM_API(omlm_decode_step)(const omlm_decode_args* a, const long 
     OMLM_CHECK_ARG(a->nsplit * DEC_KS >= a->Nmax, "nsplit must cover Nmax keys");
     OMLM_CHECK_ARG(a->B > DEC_BMAX || (size_t)a->B * a->Fp * sizeof(float) + 1024 <= 150 * 1024, "B * Fp exceeds the LDS budget");
     OMLM_CHECK_ARG(!a->emb_table || ids, "ids required with an embedding table");
-    static int v1 = -1;
-    if (v1 < 0) { const char* e = getenv("OMLM_DECODE_V1"); v1 = (e && e[0] == '1') ? 1 : 0; }
     const bool v2_ok = a->D == 1024 && a->H * 64 <= 1024 && a->Fp <= 4096 && a->Fp % 2 == 0 && (a->H * 64 + 128) % DEC2_ROWS == 0;
     // batches of 9..16 exist only on the second-generation path's matrix-core kernels: the first-generation kernels below are sized for
-    // DEC_BMAX samples (LDS B * Fp floats, DEC_ROWS * DEC_BMAX tail) -- refuse instead of overrunning them (OMLM_DECODE_V1=1, odd geometries)
-    OMLM_CHECK_ARG(a->B <= DEC_BMAX || (!v1 && v2_ok), "decode batches above 8 need the second-generation step kernels (D = 1024, OMLM_DECODE_V1 unset)");
-    if (!v1 && v2_ok) {
+    // DEC_BMAX samples (LDS B * Fp floats, DEC_ROWS * DEC_BMAX tail) -- refuse instead of overrunning them (odd geometries)
+    OMLM_CHECK_ARG(a->B <= DEC_BMAX || v2_ok, "decode batches above 8 need the second-generation step kernels (D = 1024)");
+    if (v2_ok) {
 #if OMLM_FP16
         const int rc = decode_step2_t<h16_t>(*a, ids, as_stream(stream));
 #else

@@ -55,23 +55,12 @@ __device__ __forceinline__ void zero8(float* v) {
 // v_rcp_f32 (1 ulp) instead of __frcp_rn / '/', which hipcc expands to the full IEEE division sequence (v_div_scale x2, v_rcp,
 // 4 fma, v_div_fmas, v_div_fixup: 164 of the 958 static VALU instructions of the forward, found in the ISA).  The erf argument
 // is >= 1 and the change is below the 1.5e-7 approximation error: the kernel parity tests report the same errors to all
-// printed digits with either build; forward 328 -> 304 us at the bench shape.  FF_FAST_RCP=0 restores the exact quotients.
-#ifndef FF_FAST_RCP
-#define FF_FAST_RCP 1
-#endif
+// printed digits with either form; forward 328 -> 304 us at the bench shape.
 __device__ __forceinline__ float ff_rcp(float x) {
-#if FF_FAST_RCP
     return __builtin_amdgcn_rcpf(x);
-#else
-    return __frcp_rn(x);
-#endif
 }
-__device__ __forceinline__ float ff_div(float a, float b) {       // same switch for the Welford quotients
-#if FF_FAST_RCP
+__device__ __forceinline__ float ff_div(float a, float b) {       // the same for the Welford quotients
     return a * __builtin_amdgcn_rcpf(b);
-#else
-    return a / b;
-#endif
 }
 __device__ __forceinline__ float fast_erf(float x) {
     const float ax = fabsf(x);
@@ -216,7 +205,7 @@ __device__ __forceinline__ void dropout8_from_bits(unsigned bits, float p, float
 __device__ __forceinline__ void welford_merge(float& n, float& mean, float& m2, float nb, float meanb, float m2b) {
     const float nt = n + nb;
     if (nt > 0.f) {
-        const float d = meanb - mean, r = ff_div(nb, nt);   // (FF_FAST_RCP: a 1-ulp error in r enters mean / M2 at the 1e-7 relative level)
+        const float d = meanb - mean, r = ff_div(nb, nt);   // (v_rcp_f32: a 1-ulp error in r enters mean / M2 at the 1e-7 relative level)
         mean += d * r;
         m2 += m2b + d * d * n * r;
     }
@@ -610,10 +599,10 @@ int ffmid2_fwd_launch(const void* h1, const void* convw, const void* gamma, void
 int ffmid2_bwd_launch(const void* dh2, const void* h1, const void* convw, const void* gamma, const float* rstd, float* bc,
                       void* dh1, float* part_g, int max_g_rows, float* part_c, int max_c_rows, int* g_rows, int* c_rows,
                       int M, int nseq, int F, int Fp, float p, const unsigned char* drop_bits, const void* gh, int dtype, hipStream_t st);
-// 1 (default): the column-strip kernels (both operand dtypes) where their preconditions hold; 0: the wave-per-row kernels.  $OMLM_FFMID_IMPL or
-// omlm_ffmid_set_impl (A/B runs, tests).  The two generations share every buffer layout; their dropout streams differ
+// 1 (default): the column-strip kernels (both operand dtypes) where their preconditions hold; 0: the wave-per-row kernels.  Set by
+// omlm_ffmid_set_impl (tests).  The two generations share every buffer layout; their dropout streams differ
 // (the keep-mask travels from forward to backward as drop_bits, so a step may not mix them only when drop_bits is null).
-static int g_ffmid_impl = -1;
+static int g_ffmid_impl = 1;
 #if !OMLM_FP16
 extern "C" int omlm_ffmid_set_impl_h(int impl);
 #endif
@@ -626,10 +615,7 @@ extern "C" int OMLM_API(omlm_ffmid_set_impl)(int impl) {
     return OMLM_OK;
 #endif
 }
-static int ffmid_impl() {
-    if (g_ffmid_impl < 0) { const char* e = getenv("OMLM_FFMID_IMPL"); g_ffmid_impl = (e && e[0] == '0') ? 0 : 1; }
-    return g_ffmid_impl;
-}
+static int ffmid_impl() { return g_ffmid_impl; }
 
 #if !OMLM_FP16
 extern "C" long long omlm_ffmid_bwd_workspace_bytes(int F, int Fp) {

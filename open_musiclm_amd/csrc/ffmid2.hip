@@ -144,8 +144,6 @@ __device__ __forceinline__ void store_mx8(h16_t* hi, unsigned char* p8h, unsigne
 }
 __device__ __forceinline__ void store_mx8(float*, unsigned char*, unsigned char*, const v2 (&)[4], float, float) {}
 
-__device__ __forceinline__ void pin_regs(Ch8<h16_t>& a, Ch8<h16_t>& b) { asm volatile("" : "+v"(a.r), "+v"(b.r)); }
-__device__ __forceinline__ void pin_regs(Ch8<float>&, Ch8<float>&) {}
 
 // GELU pieces of a gate pair u:  h = Phi(u) = 0.5 (1 + erf(u / sqrt 2)),  ex = exp(-u^2 / 2).
 // erf by Abramowitz-Stegun 7.1.26 like ffmid.hip (|abs err| <= 1.5e-7), with the 1/sqrt2 and the 0.5 folded into constants.
@@ -181,27 +179,8 @@ __device__ __forceinline__ void keep_words(unsigned long long seed, unsigned lon
     x = (x ^ (x >> 14)) * 0x85ebca6bu; w[3] = x ^ (x >> 16);
 }
 
-#ifndef FS_R
 #define FS_R 4            // rows per batch of the forward (one barrier per batch)
-#endif
-#ifndef FS_OCC
 #define FS_OCC 1          // workgroups per CU the forward's register budget is sized for
-#endif
-#ifndef FS_SPLIT
-#define FS_SPLIT 1        // 1: full batches run in a steady-state loop without row conditions (counted waits), the general body takes the strip's tail
-#endif
-#ifndef FS_DIAG
-#define FS_DIAG 0         // diagnostic builds only (tools/ab_variant.sh): forward -- 1 / 2 / 4 = the keep-bit / h2 / normalised-output stores are skipped at run
-#endif                    // time (values still computed), 8 = no GELU and no hash arithmetic
-#ifndef FS_PACKW
-#define FS_PACKW 0        // 1: the forward keeps the conv taps of 16-bit operands packed (see the kernel)
-#endif
-#ifndef FS_PIN
-#define FS_PIN 1          // 1: the early re-requests of the steady-state loop are pinned behind their row's arithmetic
-#endif
-#ifndef FS_EARLY
-#define FS_EARLY 1        // 1: a row's registers are re-requested (next batch) the moment sweep 1 has consumed them -- the loads are in flight
-#endif                    //    through the rest of the sweep too, not only through the reduction / barrier / store phase (0: the round-2 order)
 
 // ---------------------------------------------------------------------------------------------------------------------
 // forward.  grid: B * strips workgroups of NT threads (NT = chunks of 8 channels rounded up to waves); strip s of sample b
@@ -231,34 +210,22 @@ __global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kern
     // so no memory instruction of the row loop sits under a divergent branch and hipcc's s_waitcnt bookkeeping can count the stores that
     // follow a load instead of assuming none (see the steady-state loop below).  Lanes the hardware never started read as 0 in the
     // ds_bpermute steps of wave_sum.
-#if OMLM_WAVE_DPP
-    // wave_sum_dpp finishes with v_readlane of lanes 16 / 32 / 48, which ignores EXEC: in a PARTIAL last wave (Fp = 2752: 24 lanes) it would
-    // read the never-written registers of absent lanes -- wrong LayerNorm statistics.  This forward needs the bpermute ladder.
-#error "ffmid2_fwd_kernel launches a partial last wave: build it with the ds_bpermute wave_sum (OMLM_WAVE_DPP=0)"
-#endif
     const int col = threadIdx.x * 8;
     const int ld = 2 * Fp;
     const size_t row0 = (size_t)b * nseq;
     const float inv = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
     const unsigned thr = (unsigned)(p * 65536.0f + 0.5f);
 
-    // taps / gamma: registers for the whole strip.  FS_PACKW (16-bit operands): the taps stay PACKED (24 registers instead of 48) and are
-    // unpacked where they are used -- 2 VALU instructions per pair and use, ~12 % more issue, for a register budget that admits a
-    // second workgroup per CU (6 + 6 waves = 3 per SIMD instead of the 2 / 2 / 1 / 1 of a lone 6-wave workgroup).
-    constexpr bool PACKW = FS_PACKW && sizeof(T) == 2 && !PL;
-    v2 wv[PACKW ? 1 : 3][4], wg[PACKW ? 1 : 3][4], gm[4];
+    // taps / gamma: registers for the whole strip
+    v2 wv[3][4], wg[3][4], gm[4];
     Row8<T, PL> tv[3], tg[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         tv[k].load(convw + (size_t)k * ld + col, pl.convw_lo);
         tg[k].load(convw + (size_t)k * ld + Fp + col, pl.convw_lo);
-        if constexpr (!PACKW) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { wv[k][i] = tv[k].get(i); wg[k][i] = tg[k].get(i); }
-        }
+        for (int i = 0; i < 4; ++i) { wv[k][i] = tv[k].get(i); wg[k][i] = tg[k].get(i); }
     }
-    auto WV = [&](int k, int i) -> v2 { if constexpr (PACKW) return tv[k].get(i); else return wv[k][i]; };
-    auto WG = [&](int k, int i) -> v2 { if constexpr (PACKW) return tg[k].get(i); else return wg[k][i]; };
     {
         Row8<T, PL> a;
         a.load(gamma + col, pl.gamma_lo);
@@ -312,22 +279,14 @@ __global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kern
             ls[r] = 0.f; lq[r] = 0.f;
             if (FULL || tb + r < t1) {
                 v2 s2 = splat2(0.f), q2 = splat2(0.f);
-                if constexpr (PACKW) {                   // opaque per row: the unpacked taps must not be hoisted back into loop-invariant registers
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) pin_regs(tv[k].h, tg[k].h);
-                }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const v2 xv = rv[r].get(i), xg = rg[r].get(i);
-                    const v2 uv = fma2(WV(2, i), xv, fma2(WV(1, i), x1v[i], WV(0, i) * x2v[i]));
-                    const v2 ug = fma2(WG(2, i), xg, fma2(WG(1, i), x1g[i], WG(0, i) * x2g[i]));
+                    const v2 uv = fma2(wv[2][i], xv, fma2(wv[1][i], x1v[i], wv[0][i] * x2v[i]));
+                    const v2 ug = fma2(wg[2][i], xg, fma2(wg[1][i], x1g[i], wg[0][i] * x2g[i]));
                     x2v[i] = x1v[i]; x1v[i] = xv; x2g[i] = x1g[i]; x1g[i] = xg;
                     v2 h, ex;
-#if FS_DIAG & 8
-                    h = ug; ex = ug;                     // diagnostic build: no GELU arithmetic
-#else
                     gelu_parts(ug, h, ex);
-#endif
                     const v2 gv = (ug * h) * uv;
                     g[r][i] = gv;
                     s2 += gv;
@@ -339,28 +298,13 @@ __global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kern
 #pragma unroll
                 for (int i = 0; i < 4; ++i) g[r][i] = splat2(0.f);
             }
-#if FS_EARLY
             if (FULL || tb + RB_ + r < t1) {             // this row's registers are free: the next batch's row r leaves now
-#if FS_PIN
                 if (FULL) __builtin_amdgcn_sched_barrier(0);     // (hipcc's scheduler otherwise sinks the four requests below the whole sweep)
-#endif
                 rv[r].load(h1, (row0 + tb + RB_ + r) * ld + col, pl);
                 rg[r].load(h1, (row0 + tb + RB_ + r) * ld + Fp + col, pl);
-#if FS_PIN
                 if (FULL) __builtin_amdgcn_sched_barrier(0);
-#endif
             }
-#endif
         }
-#if !FS_EARLY
-        // next batch's rows: in flight during the reduction and the second sweep
-#pragma unroll
-        for (int r = 0; r < RB_; ++r)
-            if (FULL || tb + RB_ + r < t1) {
-                rv[r].load(h1, (row0 + tb + RB_ + r) * ld + col, pl);
-                rg[r].load(h1, (row0 + tb + RB_ + r) * ld + Fp + col, pl);
-            }
-#endif
 #pragma unroll
         for (int r = 0; r < RB_; ++r) { ls[r] = wave_sum(ls[r]); lq[r] = wave_sum(lq[r]); }
         if (lane == 0) {
@@ -398,11 +342,7 @@ __global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kern
             for (int i = 0; i < 4; ++i) y[i] = gh[i] * gm[i];
             if (TRAIN || p > 0.f) {
                 unsigned w[4], bits = 0;
-#if FS_DIAG & 8
-                w[0] = w[1] = w[2] = w[3] = (unsigned)row * 0x9E3779B9u + (unsigned)col;     // diagnostic build: no hash
-#else
                 keep_words(seed, row * (unsigned long long)(Fp >> 3) + (unsigned)(col >> 3), w);
-#endif
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const bool k0 = (w[i] & 0xFFFFu) >= thr, k1 = (w[i] >> 16) >= thr;
@@ -411,18 +351,8 @@ __global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kern
                     bits |= (k0 ? 1u : 0u) << (2 * i);
                     bits |= (k1 ? 1u : 0u) << (2 * i + 1);
                 }
-#if FS_DIAG
-                asm volatile("" :: "v"(bits));           // diagnostic builds: the value stays computed although its store may be skipped
-                if (!(FS_DIAG & 1) || eps < 0.f)
-#endif
                 if (TRAIN || drop_bits) drop_bits[row * (size_t)(Fp >> 3) + (col >> 3)] = (unsigned char)bits;
             }
-#if FS_DIAG
-#pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("" :: "v"(y[i]), "v"(gh[i]));
-            if (!(FS_DIAG & 2) || eps < 0.f) Ch8<T>::store(h2 + row * Fp + col, y);
-            if (!(FS_DIAG & 4) || eps < 0.f) { if (TRAIN || gh_out) Ch8<T>::store(gh_out + row * Fp + col, gh); }
-#else
             if constexpr (MX) {
                 store_mx8(h2 + row * Fp + col, pl.h2_8 + row * (2 * (size_t)Fp) + col, pl.h2_8 + pl.h2_8_stride + row * (2 * (size_t)Fp) + col, y, sh, sl);
                 // the row's tail up to a whole 128-byte fp8 k-tile is zero (omlm_gemm_mx16 reads it): written here, the planes need no zero fill
@@ -436,7 +366,6 @@ __global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kern
             else if constexpr (PL) store_planes8(h2 + row * Fp + col, (T*)pl.h2_lo + row * Fp + col, y);
             else Ch8<T>::store(h2 + row * Fp + col, y);
             if (TRAIN || gh_out) Ch8<T>::store(gh_out + row * Fp + col, gh);
-#endif
         }
         if (FULL) {
             // the batch's statistics: lane l of EVERY wave stores row (l mod RB_)'s pair -- the same values to the same addresses from
@@ -451,13 +380,11 @@ __global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kern
         }
     };
     int it = 0, tb = t0;
-#if FS_SPLIT
     // The loop header joins the entry edge with the back edge: with the prologue's (conditional) loads still pending on entry, the join
     // would again see "nothing behind this load" for every iteration.  Draining them once per strip leaves the back edge's counts.
     __builtin_amdgcn_s_waitcnt(0x0F70);                                        // vmcnt(0)
 #pragma unroll 1
     for (; tb + 2 * RB_ <= t1; tb += RB_, ++it) batch(std::true_type{}, tb, it);
-#endif
 #pragma unroll 1
     for (; tb < t1; tb += RB_, ++it) batch(std::false_type{}, tb, it);
 }
@@ -700,9 +627,6 @@ __global__ __launch_bounds__(256) void ffmid2_bwd_kernel(const T* __restrict__ d
 // main pass of the previous row.  d(gamma) = sum_rows dropout^T(dh2) gh joins d(conv taps) in registers: one partial row per workgroup
 // of each.  Same element arithmetic and the same summation order inside a row as prepass + main (wave sums, then the waves in order).
 // ---------------------------------------------------------------------------------------------------------------------
-#ifndef FF3_DPP
-#define FF3_DPP 1
-#endif
 template <typename T> struct Bwd3Row { Ch4<T> dy, gh, xv, xg; unsigned bits; float a; };
 // "defined here" for the optimiser: what is derived from the registers after this point is not hoisted above it
 __device__ __forceinline__ void opaque(Ch4<h16_t>& c) { asm volatile("" : "+v"(c.r[0]), "+v"(c.r[1])); }
@@ -775,13 +699,9 @@ __global__ __launch_bounds__(NT) void ffmid3_bwd_kernel(const T* __restrict__ dh
             s1 += gy;
             s2 = fma2(gy, R.gh.get(i), s2);
         }
-#if FF3_DPP
         // (every lane of the NT-thread workgroup exists -- inactive channels carry zeros --, so the VALU form is safe here: four DPP adds + four
         // readlanes per sum instead of six dependent LDS-crossbar round trips on the row's critical path)
         const float t1 = wave_sum_dpp(s1[0] + s1[1]), t2 = wave_sum_dpp(s2[0] + s2[1]);
-#else
-        const float t1 = wave_sum(s1[0] + s1[1]), t2 = wave_sum(s2[0] + s2[1]);
-#endif
         if (lane == 0) { red[buf][wave][0] = t1; red[buf][wave][1] = t2; }
     };
 
@@ -977,9 +897,7 @@ static int bwd_launch_t(const void* dh2, const void* h1, const void* convw, cons
                         void* dh1, float* part_g, int max_g_rows, float* part_c, int max_c_rows, int* g_rows, int* c_rows,
                         int M, int nseq, int F, int Fp, float p, const unsigned char* drop_bits, const void* gh, hipStream_t st) {
     const int B = M / nseq;
-    static int fused = -1;
-    if (fused < 0) { const char* e = getenv("OMLM_FFMID_BWD_FUSED"); fused = (e && e[0] == '0') ? 0 : 1; }
-    if (fused && Fp / 4 <= 768) {
+    if (Fp / 4 <= 768) {
         // one pass: a workgroup covers all channels of its rows (ffmid3_bwd_kernel); `bc` is not used
         const int RB = strip_rows(nseq, 35);
         const int strips = (nseq + RB - 1) / RB;

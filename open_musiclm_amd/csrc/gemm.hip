@@ -42,11 +42,10 @@
 namespace OMLM_NS {
 
 // One workgroup's share of C = alpha A B^T (+ Cin).  lg: logical workgroup id inside this problem's (tiles x K-splits, split-major)
-// space; split: partial sums are added to fp32 C with atomics; bal_wgs: workgroup count of the balanced split-K form (BAL only).
+// space; split: partial sums are added to fp32 C with atomics.
 // FASTK: K is a multiple of the k-tile depth (host-checked): the DMA pieces take their k offset from an SGPR (DmaStagerT::issue_one)
-template <int BM_, int BN_, int WM_, int WN_, bool A_KMAJ, bool B_KMAJ, typename TOUT, bool DBG, bool KMAP, bool BAL, bool SPLIT3 = false, bool FASTK = false, int EPI = 0>
-__device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, const int lg, const bool split, const int bal_wgs, char* smem) {
-    const int dbg = DBG ? g.debug : 0;      // ablation switches exist only in the DBG instantiation (OMLM_GEMM_DEBUG set)
+template <int BM_, int BN_, int WM_, int WN_, bool A_KMAJ, bool B_KMAJ, typename TOUT, bool KMAP, bool SPLIT3 = false, bool FASTK = false, int EPI = 0>
+__device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, const int lg, const bool split, char* smem) {
     constexpr int NWN = BN_ / WN_, NWAVES = (BM_ / WM_) * NWN;
     constexpr int MI = WM_ / 32, NJ = WN_ / 32;
     constexpr int A_BYTES = BM_ * BK * 2, B_BYTES = BN_ * BK * 2, STAGE = A_BYTES + B_BYTES;
@@ -56,21 +55,6 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, const int lg, 
     const int nwg = tiles_m * tiles_n;
     const int nk1 = (g.K + BK - 1) / BK;
     const int nk_all = SPLIT3 ? 3 * nk1 : nk1;            // split3: k-tile t reads planes (t / nk1) at k = (t % nk1) * BK
-    constexpr bool bal = BAL;          // balanced split-K is its own instantiation: the plain kernels keep their code and registers
-    // Balanced split-K: the (K chunk, tile, k-tile) units are numbered chunk-major and cut into bal_wgs equal contiguous
-    // ranges; a workgroup walks its range segment by segment (a segment = consecutive k-tiles of one output tile) and adds each
-    // partial tile to C.  Every workgroup does the same number of k-tiles (no partial last round), co-resident workgroups sit
-    // in the same K chunk (shared panels), and a tile receives ~chunks + 1 partial sums instead of one per split.
-    int u = 0, u1 = 0;                 // host guarantees tiles x k-tiles < 2^31 / workgroups
-    if (bal) {
-        const long long U = (long long)nwg * nk_all;
-        u = (int)(U * lg / bal_wgs);
-        u1 = (int)(U * (lg + 1) / bal_wgs);
-        if (u >= u1) return;
-    }
-#ifndef OMLM_SUPER_ROWS
-#define OMLM_SUPER_ROWS 1024       /* C rows per super-tile (tile rows walked column-major inside it) */
-#endif
     constexpr int GROUP = OMLM_SUPER_ROWS / BM_;                       // tile rows per super-tile (same footprint as the 128 kernel's 8)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -80,27 +64,11 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, const int lg, 
     const dma_rsrc rsAl = make_dma_rsrc(SPLIT3 ? g.A_lo : g.A, (unsigned long long)g.a_rows * g.lda * 2);      // (plain kernels: never used)
     const dma_rsrc rsBl = make_dma_rsrc(SPLIT3 ? g.B_lo : g.B, (unsigned long long)g.b_rows * g.ldb * 2);
 
-    for (;;) {
-        int bid, kt0, kt1, ksplit_id = 0;
-        if (bal) {
-            const int per_chunk = nwg * g.bal_ck;
-            int c = u / per_chunk;
-            if (c > g.bal_chunks - 1) c = g.bal_chunks - 1;
-            const int len_c = min(g.bal_ck, nk_all - c * g.bal_ck);
-            const int r = u - c * per_chunk;
-            bid = r / len_c;
-            const int kk = r - bid * len_c;
-            const int seg_end = min(u1, u + (len_c - kk));
-            kt0 = c * g.bal_ck + kk;
-            kt1 = kt0 + (seg_end - u);
-            u = seg_end;
-        } else {
-            const int ksplit = lg / nwg;
-            ksplit_id = ksplit;
-            bid = lg - ksplit * nwg;
-            kt0 = ksplit * g.kt_per_split;
-            kt1 = min(nk_all, kt0 + g.kt_per_split);
-        }
+    {
+        const int ksplit_id = lg / nwg;
+        const int bid = lg - ksplit_id * nwg;
+        const int kt0 = ksplit_id * g.kt_per_split;
+        const int kt1 = min(nk_all, kt0 + g.kt_per_split);
         const int gsz = GROUP * tiles_n;
         const int grp = bid / gsz, first_m = grp * GROUP;
         const int rows_in = min(GROUP, tiles_m - first_m);
@@ -154,7 +122,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, const int lg, 
                 const int cur = (kt - kt0) & 1;
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();      // tile kt landed everywhere; every wave's reads of the other stage (incl. its last step) are complete
-                const bool live = kt + 1 < kt1 && !(dbg & 1);        // dbg (DBG instantiation only): bit 0 = no DMA after the first tile, bit 1 = no MFMAs
+                const bool live = kt + 1 < kt1;
                 char* nxt = smem + (cur ^ 1) * STAGE;
                 bool pan, pbn;
                 const int knext = tile_at(kt + 1, pan, pbn);
@@ -167,7 +135,7 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, const int lg, 
                     for (int i = 0; i < MI; ++i)
 #pragma unroll
                         for (int j = 0; j < NJ; ++j) {
-                            if (mul && !(dbg & 2)) acc[i][j] = OMLM_MFMA_32x32x16(a[fi][i], b[fi][j], acc[i][j]);
+                            if (mul) acc[i][j] = OMLM_MFMA_32x32x16(a[fi][i], b[fi][j], acc[i][j]);
                             else if (mul) asm volatile("" :: "v"(a[fi][i]), "v"(b[fi][j]));
                             const int midx = ph * MPS + i * NJ + j;
                             if (midx % STRIDE == 0 && midx / STRIDE < NLOAD) {
@@ -211,28 +179,23 @@ __device__ __forceinline__ void gemm_tile_body(const GemmArgs& g, const int lg, 
         // bookkeeping, so without this wait nothing orders them before the epilogue's ds_writes: a late zero-fill wiped staged output
         // values (round 3: intermittent 30-70 % error in the rel-pos MLP's gradient -- its GEMMs run on the second stream next to the
         // trunk's HBM-bound kernels, whose traffic delays the pieces past the ~500 cycles the remaining MFMAs of a 128x128 tile take).
-        // -DOMLM_GEMM_TAIL_WAIT=0 rebuilds the old behaviour (tests/stress_gemm_tail.py reproduces the defect with it).
-#if OMLM_GEMM_TAIL_WAIT
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
         __syncthreads();
-        constexpr bool SLICE = BM_ == 128 && BN_ == 128 && std::is_same<TOUT, float>::value && !BAL && EPI == 0;
-        tile_epilogue<MI, NJ, WN_, TOUT, EPI, (OMLM_EPI_CIN_AHEAD != 0) && (MI * NJ <= 4), SLICE>(g, acc, smem, m0, n0, wm, wn, wave, lane, dbg, bal || split, nullptr,
-                                                                                                   SLICE ? ksplit_id : 0);
-        if (!bal || u >= u1) break;
-        __syncthreads();              // the non-split epilogue stages through LDS; the next segment's DMA must not overtake it
+        constexpr bool SLICE = BM_ == 128 && BN_ == 128 && std::is_same<TOUT, float>::value && EPI == 0;
+        tile_epilogue<MI, NJ, WN_, TOUT, EPI, (MI * NJ <= 4), SLICE>(g, acc, smem, m0, n0, wm, wn, wave, lane, split, nullptr,
+                                                                     SLICE ? ksplit_id : 0);
     }
 }
 
 // For split-K GEMMs the split-major XCD order puts all co-resident workgroups of an XCD on the SAME K range (they share A and B
 // panels through its L2); with a tile-only remap an XCD held 3 unrelated K ranges at a time (measured L2 hit 48 % on the dW1 GEMM).
-template <int BM_, int BN_, int WM_, int WN_, bool A_KMAJ, bool B_KMAJ, typename TOUT, bool DBG, bool KMAP, bool BAL = false, bool SPLIT3 = false, bool FASTK = false, int EPI = 0>
+template <int BM_, int BN_, int WM_, int WN_, bool A_KMAJ, bool B_KMAJ, typename TOUT, bool KMAP, bool SPLIT3 = false, bool FASTK = false, int EPI = 0>
 __global__ __launch_bounds__((BM_ / WM_) * (BN_ / WN_) * 64) void gemm_bf16_tile_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 stages][A | B]
-    const int nwg = gridDim.x;                                     // tiles (plain) / workgroups (balanced)
-    const int total = BAL ? (int)gridDim.x : nwg * (int)gridDim.y;
+    const int nwg = gridDim.x;                                     // tiles
+    const int total = nwg * (int)gridDim.y;
     const int lg = xcd_logical_id(blockIdx.y * nwg + blockIdx.x, total);
-    gemm_tile_body<BM_, BN_, WM_, WN_, A_KMAJ, B_KMAJ, TOUT, DBG, KMAP, BAL, SPLIT3, FASTK, EPI>(g, lg, gridDim.y > 1, (int)gridDim.x, smem);
+    gemm_tile_body<BM_, BN_, WM_, WN_, A_KMAJ, B_KMAJ, TOUT, KMAP, SPLIT3, FASTK, EPI>(g, lg, gridDim.y > 1, smem);
 }
 
 
@@ -249,9 +212,7 @@ __global__ __launch_bounds__((BM_ / WM_) * (BN_ / WN_) * 64) void gemm_bf16_tile
 // tile, iteration 0: vmcnt wait + barrier, DMA(k-tile 1) -> stage X^1, multiply from stage X].  The barrier of iteration 0 is what
 // orders every wave's patch traffic before the first piece of k-tile 1 lands in stage X^1.
 // Only the shape the host sends here is built: whole k-tiles (K % 64 == 0), no row / k-row / scatter maps, no split-K, plain epilogue.
-#ifndef OMLM_PERSIST_COUNTED
-#define OMLM_PERSIST_COUNTED 1     // 1: iteration 0 of a follow-up tile waits for its DMA pieces only (counted), not for the epilogue's stores behind them
-#endif
+// Iteration 0 of a follow-up tile waits for its DMA pieces only (counted), not for the epilogue's stores behind them.
 // CIN: the epilogue adds a residual.  It is a template switch because the residual loads are what hipcc has to protect in the NEXT
 // tile's first iteration (their registers are re-used; paths that skip a row leave a load unconsumed): with them in the code,
 // iteration 0 carries compiler waits that drain the epilogue's stores whatever the run-time pointer is (seen in the ISA).
@@ -350,7 +311,7 @@ __global__ __launch_bounds__((BM_ / WM_) * (BN_ / WN_) * 64) void gemm_bf16_tile
             constexpr int STRIDE = (SPREAD * MPS) / NLOAD > 0 ? (SPREAD * MPS) / NLOAD : 1;
             for (int kt = 0; kt < nk; ++kt) {
                 const int cur = (par + kt) & 1;
-                if (OMLM_PERSIST_COUNTED && kt == 0 && counted) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NSTORE) : "memory");
+                if (kt == 0 && counted) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NSTORE) : "memory");
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
                 const bool last = kt + 1 == nk;
@@ -418,7 +379,7 @@ __global__ __launch_bounds__((BM_ / WM_) * (BN_ / WN_) * 64) void gemm_bf16_tile
         GemmArgs ge = g;
         ge.c_map = nullptr;                                        // host: no scatter map on this route
         if constexpr (!CIN) ge.Cin = nullptr;
-        tile_epilogue<MI, NJ, WN_, TOUT, EPI, false>(ge, acc, smem, m0, n0, wm, wn, wave, lane, 0, false, patch);    // (no second residual set: registers)
+        tile_epilogue<MI, NJ, WN_, TOUT, EPI, false>(ge, acc, smem, m0, n0, wm, wn, wave, lane, false, patch);    // (no second residual set: registers)
         if (!has_next) break;
         // a full interior tile's epilogue issued exactly NSTORE 16-byte stores per wave behind the next tile's pieces (more on the scalar
         // path): `vmcnt(NSTORE)` then covers the pieces; an edge tile skips stores, so its successor drains everything
@@ -456,9 +417,6 @@ __global__ __launch_bounds__((BM_ / WM_) * (BN_ / WN_) * 64) void gemm_bf16_tile
 //        been retired by their `lgkmcnt(0)` behind the phase's first barrier, two and one barriers before the request respectively.
 // Requests past the last k-tile are issued dead (out-of-bounds offset: zeros, no traffic) so that the counts stay uniform; they are
 // drained in front of the epilogue (the tail race of round 4).  Whole k-tiles only (K % 64 == 0), no row maps on the operands.
-#ifndef OMLM_T8_SETPRIO
-#define OMLM_T8_SETPRIO 1
-#endif
 template <bool A_KMAJ, bool B_KMAJ, typename TOUT, bool SPLIT3 = false>
 __device__ __forceinline__ void gemm_tile8_body(const GemmArgs& g, const int m0, const int n0, const int kt0, const int kt1, const bool split, char* smem) {
     constexpr int A_BYTES = 256 * BK * 2, STAGE = 2 * A_BYTES;
@@ -525,16 +483,12 @@ __device__ __forceinline__ void gemm_tile8_body(const GemmArgs& g, const int m0,
         for (int st = 0; st < 4; ++st) b[st] = read_frag<B_KMAJ>(Bs, hb * 128 + wc * 32, st, lane);
     };
     auto mma = [&](f32x16 (&c)[2], const h16x8 (&b)[4]) {
-#if OMLM_T8_SETPRIO
         __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int st = 0; st < 4; ++st)
 #pragma unroll
             for (int i = 0; i < 2; ++i) c[i] = OMLM_MFMA_32x32x16(a[i][st], b[st], c[i]);
-#if OMLM_T8_SETPRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
     };
     // the synchronisation of one phase: (reads and the request were just issued) counted wait -> barrier -> fragments in -> MFMAs -> barrier
 #define T8_SYNC_IN()                                                           \
@@ -584,7 +538,7 @@ __device__ __forceinline__ void gemm_tile8_body(const GemmArgs& g, const int m0,
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb)
             tile_epilogue<2, 1, 32, TOUT>(g, reinterpret_cast<f32x16 (&)[2][1]>(acc[ha][hb]), smem, m0, n0, ha * 128 + wr * 64, hb * 128 + wc * 32,
-                                          wave, lane, 0, split);
+                                          wave, lane, split);
 }
 
 // one output tile per workgroup, the tile / split order of gemm_bf16_tile_kernel
@@ -617,13 +571,6 @@ struct omlm_gemm_wgrad_desc { const void* A; const void* B; float* C; const int*
 struct GroupProb { const void* A; const void* B; float* C; const int* c_map; int M, N, K, lda, ldb, ldc, kt_per_split, start; };
 struct GroupArgs { int n, total; GroupProb p[OMLM_GROUP_MAX]; };
 
-// OMLM_GEMM_FASTK=0: the general DMA address form everywhere (A/B lever)
-static bool gemm_fastk_off() {
-    static int off = -1;
-    if (off < 0) { const char* e = getenv("OMLM_GEMM_FASTK"); off = (e && e[0] == '0') ? 1 : 0; }
-    return off == 1;
-}
-
 template <bool FASTK, bool T8 = false>
 __global__ __launch_bounds__(512) void gemm_wgrad_group_kernel(GroupArgs ga) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -650,7 +597,7 @@ __global__ __launch_bounds__(512) void gemm_wgrad_group_kernel(GroupArgs ga) {
         const int tm = first_m + (bid - grp * gsz) % rows_in, tn = (bid - grp * gsz) / rows_in;
         if (kt0 < kt1) gemm_tile8_body<true, true, float>(g, tm * 256, tn * 256, kt0, kt1, q.kt_per_split < nk, smem);
     } else {
-        gemm_tile_body<256, 256, 128, 64, true, true, float, false, false, false, false, FASTK>(g, lg - q.start, q.kt_per_split < nk, 0, smem);
+        gemm_tile_body<256, 256, 128, 64, true, true, float, false, false, FASTK>(g, lg - q.start, q.kt_per_split < nk, smem);
     }
 }
 
@@ -679,7 +626,7 @@ static int gemm_persist_slots() {
         int dev = 0, n = 0;
         ncu8 = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8) ? n / 8 * 8 : 0;
     }
-    const char* e = getenv("OMLM_GEMM_PERSIST");                   // read per call like the other levers: tests toggle it inside one process
+    const char* e = getenv("OMLM_GEMM_PERSIST");                   // read per call: tests toggle it inside one process
     return (e && e[0] == '0') ? 0 : ncu8;
 }
 
@@ -687,7 +634,7 @@ static int gemm_persist_slots() {
 // where it measured faster (profiles/r05b_gemm_t8_ab.md, same box, bit-identical results): the grouped weight gradients (557 k-tiles per
 // tile: +6 %) and multi-round launches with K >= 2048 (d(xn2), K = 5504: +3 %; FF-out, K = 2752: +2 %; 8192^3: +15 %).  Short contractions
 // (K = 1024: 16 k-tiles per tile) stay on the persistent walk of the rotated loop, which hides the per-tile prologue / epilogue that this
-// one-tile-per-workgroup form exposes (FF-in 373 vs 399 us).  Read per call like the other levers (tests and tools/lib_ab toggle it).
+// one-tile-per-workgroup form exposes (FF-in 373 vs 399 us).  Read per call (tests and tools/lib_ab toggle it).
 static int gemm_t8_mode() {
     const char* e = getenv("OMLM_GEMM_T8");
     return e ? atoi(e) : OMLM_GEMM_T8_DEFAULT;
@@ -711,9 +658,9 @@ static int launch_tile(const GemmArgs& g, int a_kmaj, int b_kmaj, int splits, hi
     const int tiles = ((g.M + BM_ - 1) / BM_) * ((g.N + BN_ - 1) / BN_);
     dim3 grid(tiles, splits), block(NTH);
     if constexpr (BM_ == 256 && BN_ == 256) {
-        // whole k-tiles, no maps on the operand side (a scatter map of C and split-K are fine), no ablation / plane / balanced modes
+        // whole k-tiles, no maps on the operand side (a scatter map of C and split-K are fine)
         // (the hi/lo-plane route runs a 3x k-loop: K >= 704 already is a long contraction for it; its instantiations exist in the bf16 copy only)
-        if (gemm_t8_wanted(g.split3 ? 3 * g.K : g.K, tiles, splits) && g.K % BK == 0 && !g.a_map && !g.b_map && g.bal_ck == 0 && !g.debug && !gemm_fastk_off() &&
+        if (gemm_t8_wanted(g.split3 ? 3 * g.K : g.K, tiles, splits) && g.K % BK == 0 && !g.a_map && !g.b_map &&
             (!g.split3 || !OMLM_FP16)) {
 #define OMLM_T8_LAUNCH(AK, BKM)                                                                                       \
             do {                                                                                                       \
@@ -736,16 +683,15 @@ static int launch_tile(const GemmArgs& g, int a_kmaj, int b_kmaj, int splits, hi
             return omlm_post_launch("omlm_gemm");
         }
     }
-    if (g.bal_ck > 0) grid = dim3(splits, 1);          // balanced split-K: `splits` carries the workgroup count
     const bool need_kmap = (a_kmaj && g.a_map) || (b_kmaj && g.b_map);       // host routes these to the 128x128 tile
     if (need_kmap && BM_ != 128) { omlm_set_error("omlm_gemm: k-row maps are only built for the 128x128 tile"); return OMLM_ERR_UNSUPPORTED; }
-    // The fp16 copy of this file (common.h: OMLM_FP16) instantiates only the production kernel and its k-row-map form: the ablation
-    // (DBG), balanced split-K (BAL) and hi/lo-plane (SPLIT3) instantiations exist once, in the bf16 copy.
+    // The fp16 copy of this file (common.h: OMLM_FP16) instantiates only the production kernel and its k-row-map form: the hi/lo-plane
+    // (SPLIT3) instantiations exist once, in the bf16 copy.
 #define OMLM_TILE_LAUNCH(AK, BKM)                                                                                          \
     do {                                                                                                                    \
-        auto kfn = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, false>;                                 \
-        auto kmap = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, (AK || BKM) && BM_ == 128>;            \
-        auto kfast = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, false, false, false, true>;           \
+        auto kfn = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false>;                                        \
+        auto kmap = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, (AK || BKM) && BM_ == 128>;                   \
+        auto kfast = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, false, true>;                         \
         static bool attr = false;                                                                                           \
         if (!attr) {                                                                                                        \
             (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);             \
@@ -753,32 +699,21 @@ static int launch_tile(const GemmArgs& g, int a_kmaj, int b_kmaj, int splits, hi
             (void)hipFuncSetAttribute((const void*)kmap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);            \
         }                                                                                                                   \
         if constexpr (!OMLM_FP16) {                                                                                         \
-            auto kdbg = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, true, false>;                             \
-            auto kbal = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, false, sizeof(TOUT) == 4>;        \
-            auto kbalmap = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, (AK || BKM) && BM_ == 128, sizeof(TOUT) == 4>; \
-            auto ks3 = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, false, false, true>;                 \
-            if (!attr) {                                                                                                    \
-                (void)hipFuncSetAttribute((const void*)kdbg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);        \
-                (void)hipFuncSetAttribute((const void*)kbal, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);        \
-                (void)hipFuncSetAttribute((const void*)kbalmap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);     \
-                (void)hipFuncSetAttribute((const void*)ks3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);         \
-            }                                                                                                               \
+            auto ks3 = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, true>;                               \
+            if (!attr) (void)hipFuncSetAttribute((const void*)ks3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);  \
             attr = true;                                                                                                    \
             if (g.split3) { hipLaunchKernelGGL(ks3, grid, block, LDS, st, g); break; }                                     \
-            if (g.bal_ck > 0 && sizeof(TOUT) == 4) { hipLaunchKernelGGL(need_kmap ? kbalmap : kbal, grid, block, LDS, st, g); break; } \
-            if (g.debug && !need_kmap) { hipLaunchKernelGGL(kdbg, grid, block, LDS, st, g); break; }                       \
         }                                                                                                                   \
         attr = true;                                                                                                        \
         if (need_kmap) hipLaunchKernelGGL(kmap, grid, block, LDS, st, g);                                                  \
-        else if (g.K % BK == 0 && !gemm_fastk_off()) hipLaunchKernelGGL(kfast, grid, block, LDS, st, g);                   \
+        else if (g.K % BK == 0) hipLaunchKernelGGL(kfast, grid, block, LDS, st, g);                                        \
         else           hipLaunchKernelGGL(kfn, grid, block, LDS, st, g);                                                   \
     } while (0)
     // Persistent walk (gemm_bf16_tile_persist_kernel) for the wide tile when the problem is more than one round of the machine:
-    // whole k-tiles, k-contiguous A, no maps on the k side, no split, no ablation / plane modes.  OMLM_GEMM_PERSIST=0 keeps the one-tile grid.
+    // whole k-tiles, k-contiguous A, no maps on the k side, no split, no plane mode.  OMLM_GEMM_PERSIST=0 keeps the one-tile grid.
     if constexpr ((BM_ == 256 && BN_ == 256) || (BM_ == 128 && BN_ == 128)) {
         const int slots = gemm_persist_slots() * (BM_ == 128 ? 2 : 1);             // 64 KiB tiles: two workgroups per CU
-        if (slots > 0 && !a_kmaj && splits == 1 && g.bal_ck == 0 && !g.split3 && !g.debug && !g.a_map && !g.b_map && !g.c_map && g.K % BK == 0 &&
-            !gemm_fastk_off() && tiles > slots) {
+        if (slots > 0 && !a_kmaj && splits == 1 && !g.split3 && !g.a_map && !g.b_map && !g.c_map && g.K % BK == 0 && tiles > slots) {
             constexpr size_t LDSP = LDS + 32 * (WN_ + 4) * 4;
             static bool pattr = false;
             auto k0 = gemm_bf16_tile_persist_kernel<BM_, BN_, WM_, WN_, false, false, TOUT, false>;
@@ -814,7 +749,7 @@ static int launch_tile_s3(const GemmArgs& g, hipStream_t st, int splits = 1) {
     const int tiles = ((g.M + BM_ - 1) / BM_) * ((g.N + BN_ - 1) / BN_);
     dim3 grid(tiles, splits), block(NTH);
     if constexpr (BM_ == 256 && BN_ == 256) {
-        if (gemm_t8_mode() > 0 && g.K % BK == 0 && !gemm_fastk_off() && !g.a_map && splits == 1) {
+        if (gemm_t8_mode() > 0 && g.K % BK == 0 && !g.a_map && splits == 1) {
             auto k8 = gemm_tile8_kernel<false, false, TOUT, true>;
             static bool attr8 = false;
             if (!attr8) { (void)hipFuncSetAttribute((const void*)k8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); attr8 = true; }
@@ -822,7 +757,7 @@ static int launch_tile_s3(const GemmArgs& g, hipStream_t st, int splits = 1) {
             return omlm_post_launch("omlm_gemm_planes16");
         }
     }
-    auto ks3 = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, false, false, TOUT, false, false, false, true>;
+    auto ks3 = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, false, false, TOUT, false, true>;
     static bool attr = false;
     if (!attr) { (void)hipFuncSetAttribute((const void*)ks3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); attr = true; }
     hipLaunchKernelGGL(ks3, grid, block, LDS, st, g);
@@ -853,7 +788,7 @@ static int launch_layout(const GemmArgs& g, int a_kmaj, int b_kmaj, int splits, 
 // caller and to ONE stream at a time (the library keeps no pointer: two streams pass two buffers); OMLM_GEMM_TAIL_SPLIT=0 or no workspace keeps the one-launch tail.
 
 static bool gemm_tail_split_on() {
-    const char* e = getenv("OMLM_GEMM_TAIL_SPLIT");                // read per call like the other levers
+    const char* e = getenv("OMLM_GEMM_TAIL_SPLIT");                // read per call (tests toggle it)
     return !(e && e[0] == '0');
 }
 
@@ -883,7 +818,7 @@ static int gemm_impl(const void* A, const void* B, void* C, const float* Cin,
     g.A = A; g.B = B; g.C = C; g.Cin = Cin; g.a_map = a_map; g.b_map = b_map; g.c_map = c_map;
     g.a_rows = a_rows; g.b_rows = b_rows; g.M = M; g.N = N; g.K = K;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin; g.alpha = alpha;
-    { const char* dbg = getenv("OMLM_GEMM_DEBUG"); g.debug = dbg ? atoi(dbg) : 0; }
+    g.bal_ck = 0; g.bal_chunks = 0; g.debug = 0;
     g.split3 = split3; g.A_lo = A_lo; g.B_lo = B_lo; g.C_lo = C_lo; g.c_lo8 = 0; g.c_split_stride = 0;
     g.epi_scale = nullptr; g.epi_norm = nullptr; g.epi_groups = 0; g.epi_ldnorm = 0; g.C2 = nullptr; g.c2_col0 = 0; g.ldc2 = 0;
     hipStream_t st = as_stream(stream);
@@ -895,10 +830,8 @@ static int gemm_impl(const void* A, const void* B, void* C, const float* Cin,
         if (force && force[0]) { if (!strcmp(force, "256x256")) { bm = 256; bn = 256; } else if (!strcmp(force, "256x128")) { bm = 256; bn = 128; } }
         // Short contractions onto narrow outputs (to_out, d(xn), d(x) of k | v: K <= 512, N <= 1024): with the persistent walk the 128x128
         // tiles (two walkers per CU, 4 x the tiles to balance) beat the wide ones -- to_out 103 -> 92 us, d(xn) 57 -> 50 us (round 4 probe).
-        // OMLM_GEMM_SMALLK=0 keeps the old choice.
         else if (K <= 512 && N <= 1024 && K % BK == 0 && !a_kmajor && !a_map && !b_map && !c_map && !split3 && Cin != (const float*)C &&
-                 ((M + 127) / 128) * ((N + 127) / 128) > 2 * gemm_persist_slots() && gemm_persist_slots() > 0 && !gemm_fastk_off() &&
-                 !(getenv("OMLM_GEMM_SMALLK") && getenv("OMLM_GEMM_SMALLK")[0] == '0')) { bm = 128; bn = 128; }
+                 ((M + 127) / 128) * ((N + 127) / 128) > 2 * gemm_persist_slots() && gemm_persist_slots() > 0) { bm = 128; bn = 128; }
         else if (M >= 1024 && N >= 1024) { bm = 256; bn = 256; }   // measured (probe, N = 1024): 256x256 514 us, 128x128 543, 256x128 657
         // N = 512 outputs (q-proj, d(o)): 128x128 (two workgroups per CU) measured 54 / 54 us against 60 / 59 for 256x128 (round 4 tile probe)
         else if (M >= 2048 && N > 512) { bm = 256; bn = 128; }
@@ -933,29 +866,10 @@ static int gemm_impl(const void* A, const void* B, void* C, const float* Cin,
             if (util > best) { best = util; splits = sp; }
         }
     }
-    { const char* e = getenv("OMLM_GEMM_SPLITS"); if (e && atoi(e) > 0 && splits > 1) splits = atoi(e); }     // tuning override
     g.kt_per_split = (nk + splits - 1) / splits;
     splits = (nk + g.kt_per_split - 1) / g.kt_per_split;
-    // Balanced split-K for the same GEMMs (bf16 tile kernels): one workgroup per slot, every workgroup the same number of k-tiles,
-    // K cut into round(slots / tiles) chunks so that co-resident workgroups read the same K range.
-    g.bal_ck = 0; g.bal_chunks = 0;
-    if (splits > 1 && in_dtype == 1 && !split3) {
-        static int bal_on = -1;
-        // measured (MI355X, dW1: 88 tiles x 558 k-tiles): 665 us balanced vs 642 us with the 8-split grid, train step 36.9 vs 36.7 ms --
-        // the k-major main loop, not the partial last round or the atomic volume, is what holds these GEMMs at ~620 TFLOP/s.
-        // Off by default; OMLM_GEMM_BAL=1 selects it.
-        if (bal_on < 0) { const char* e = getenv("OMLM_GEMM_BAL"); bal_on = (e && e[0] == '1') ? 1 : 0; }
-        if (bal_on && !OMLM_FP16) {
-            const int slots = (bm == 256 ? 1 : 2) * ncu;
-            const long long U = (long long)tiles * nk;
-            long long G = slots;
-            if (U / 24 < G) G = U / 24 > 0 ? U / 24 : 1;            // at least ~24 k-tiles per workgroup: prologue + atomic epilogue amortised
-            int chunks = (int)((G + tiles / 2) / tiles); if (chunks < 1) chunks = 1; if (chunks > nk) chunks = nk;
-            g.bal_ck = (nk + chunks - 1) / chunks;
-            g.bal_chunks = (nk + g.bal_ck - 1) / g.bal_ck;
-            splits = (int)G;
-        }
-    }
+    // (A balanced split-K grid -- every workgroup the same number of k-tiles -- measured slower on dW1: 665 against 642 us; the k-major
+    // main loop, not the partial last round or the atomic volume, is what holds these GEMMs at ~620 TFLOP/s.)
     if (in_dtype == 0) {
 #if OMLM_FP16
         omlm_set_error("omlm_gemm: fp32 operands are served by the bf16 copy of the library");
@@ -1118,8 +1032,8 @@ extern "C" int OMLM_API(omlm_gemm_qknorm)(const void* A, const void* B, void* C,
     g.kt_per_split = nk;
     constexpr size_t LDS = 2 * (size_t)(128 + 128) * BK * 2;
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    auto kfast = gemm_bf16_tile_kernel<128, 128, 64, 64, false, false, h16_t, false, false, false, false, true, 1>;
-    auto kgen = gemm_bf16_tile_kernel<128, 128, 64, 64, false, false, h16_t, false, false, false, false, false, 1>;
+    auto kfast = gemm_bf16_tile_kernel<128, 128, 64, 64, false, false, h16_t, false, false, true, 1>;
+    auto kgen = gemm_bf16_tile_kernel<128, 128, 64, 64, false, false, h16_t, false, false, false, 1>;
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute((const void*)kfast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
@@ -1127,14 +1041,14 @@ extern "C" int OMLM_API(omlm_gemm_qknorm)(const void* A, const void* B, void* C,
         attr = true;
     }
     const int slots = 2 * gemm_persist_slots();                    // persistent walk, two workgroups per CU (see gemm_bf16_tile_persist_kernel)
-    if (slots > 0 && tiles > slots && K % BK == 0 && !gemm_fastk_off()) {
+    if (slots > 0 && tiles > slots && K % BK == 0) {
         constexpr size_t LDSP = LDS + 32 * (64 + 4) * 4;
         auto kp = gemm_bf16_tile_persist_kernel<128, 128, 64, 64, false, false, h16_t, false, 1>;
         static bool pattr = false;
         if (!pattr) { (void)hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSP); pattr = true; }
         hipLaunchKernelGGL(kp, dim3(slots), dim3(256), LDSP, as_stream(stream), g);
     }
-    else if (K % BK == 0 && !gemm_fastk_off()) hipLaunchKernelGGL(kfast, dim3(tiles, 1), dim3(256), LDS, as_stream(stream), g);
+    else if (K % BK == 0) hipLaunchKernelGGL(kfast, dim3(tiles, 1), dim3(256), LDS, as_stream(stream), g);
     else                                        hipLaunchKernelGGL(kgen, dim3(tiles, 1), dim3(256), LDS, as_stream(stream), g);
     return omlm_post_launch("omlm_gemm_qknorm");
 }
@@ -1250,12 +1164,11 @@ extern "C" int OMLM_API(omlm_gemm_wgrad_group)(const omlm_gemm_wgrad_desc* d, in
         (void)hipFuncSetAttribute((const void*)gemm_wgrad_group_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
         attr = true;
     }
-    { const char* e = getenv("OMLM_GROUP_SPLITS"); if (e && atoi(e) > 0) splits = atoi(e); }
     for (int base = 0; base < count; base += OMLM_GROUP_MAX) {
         const int n = count - base < OMLM_GROUP_MAX ? count - base : OMLM_GROUP_MAX;
         long long units = 0;
         int nk_min = 1 << 30;
-        bool fastk = !gemm_fastk_off();                       // every problem's K a multiple of the k-tile depth: SGPR-offset DMA form
+        bool fastk = true;                                    // every problem's K a multiple of the k-tile depth: SGPR-offset DMA form
         for (int i = 0; i < n; ++i) {
             const omlm_gemm_wgrad_desc& q = d[base + i];
             if (q.K % BK != 0) fastk = false;

@@ -7,15 +7,8 @@
 
 namespace OMLM_NS {
 
-#ifndef OMLM_GEMM_TAIL_WAIT
-#define OMLM_GEMM_TAIL_WAIT 1
-#endif
-#ifndef OMLM_GEMM_T8_DEFAULT
 #define OMLM_GEMM_T8_DEFAULT 2     // round 5: gemm_tile8_body for the 256 x 256 tiles (see gemm_t8_mode): 2 = where it measured faster
-#endif
-#ifndef OMLM_EPI_CIN_AHEAD
-#define OMLM_EPI_CIN_AHEAD 1       // epilogue: the residual pieces of strip i + 1 are requested before the stores of strip i (tile_epilogue)
-#endif
+#define OMLM_SUPER_ROWS 1024       /* C rows per super-tile (tile rows walked column-major inside it) */
 #define BM 128
 #define BN 128
 #define BK 64
@@ -31,9 +24,9 @@ struct GemmArgs {
     int lda, ldb, ldc, ldcin;
     float alpha;
     int kt_per_split;   // k-tiles handled by one blockIdx.y slice (split-K); gridDim.y == 1 -> all
-    int bal_ck;         // > 0: balanced split-K ("chunked stream-K"): gridDim.x workgroups share tiles x k-tiles evenly; k-tiles per K chunk
-    int bal_chunks;     //      number of K chunks
-    int debug;          // profiling ablations only (OMLM_GEMM_DEBUG): bit 0 = skip the per-tile DMA, bit 1 = skip the MFMAs
+    int bal_ck;         // always 0 (a retired balanced split-K form; the field keeps the kernel argument layout)
+    int bal_chunks;     // always 0 (likewise)
+    int debug;          // always 0 (a retired ablation switch; likewise)
     // hi/lo operand planes ("bf16x3" through the tile kernels; round 5: the ConvFeedForward forward of "fp16ff" on IEEE-half planes): A and B
     // point at a 16-bit hi plane, A_lo / B_lo at the matching lo plane (same layout, its own buffer descriptor: the planes may be separate
     // allocations), and the k-loop runs 3 x the k-tiles: (A_hi, B_hi), (A_hi, B_lo), (A_lo, B_hi).  C_lo (TOUT = h16pl_t instantiations):
@@ -381,11 +374,12 @@ struct h16pl_t { h16_t v; };
 // scatters (measured: ~480 of 650 us of the FF-in GEMM).  Each 32-row strip of the wave's tile is therefore transposed
 // through a per-wave LDS patch (the k-loop stages are dead: the caller has passed a barrier) and written as 16-byte
 // row-contiguous stores: 8 bf16 / 4 fp32 per lane, full 128-byte lines per row.
+// AHEAD: the residual pieces of strip i + 1 are requested before the stores of strip i.
 // SLICE: the instantiation may be launched as the slice-storing split-K of a peeled tail (GemmArgs::c_split_stride; 128 x 128 fp32-output kernels
 // only -- every other kernel keeps the code and registers it was measured with)
-template <int MI, int NJ, int WN_, typename TOUT, int EPI = 0, bool AHEAD = (OMLM_EPI_CIN_AHEAD != 0) && (MI * NJ <= 4), bool SLICE = false>
+template <int MI, int NJ, int WN_, typename TOUT, int EPI = 0, bool AHEAD = (MI * NJ <= 4), bool SLICE = false>
 __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, f32x16 (&acc)[MI][NJ], char* smem, int m0, int n0,
-                                              int wm, int wn, int wave, int lane, int dbg, bool split, float* patch = nullptr, int ksplit = 0) {
+                                              int wm, int wn, int wave, int lane, bool split, float* patch = nullptr, int ksplit = 0) {
     constexpr int SROW = WN_ + 4;                                  // padded row (floats), keeps 16-B alignment
     float* stg = patch ? patch : (float*)smem + (size_t)wave * 32 * SROW;      // (persistent kernel: the patch sits where no DMA lands)
     constexpr int VEC = sizeof(TOUT) == 2 ? 8 : 4;                 // elements per 16-byte store
@@ -397,7 +391,6 @@ __device__ __forceinline__ void tile_epilogue(const GemmArgs& g, f32x16 (&acc)[M
     const bool vec_ok = (g.ldc % VEC == 0) && (((uintptr_t)g.C & 15) == 0) &&
                         (!g.Cin || ((g.ldcin % 4 == 0) && (((uintptr_t)g.Cin & 15) == 0)));
     const int hi = lane >> 5;
-    if (dbg & 4) return;
     if (split) {      // split-K slices accumulate into fp32 C (Cin == C): the C-layout already gives 128-B coalesced atomics
 #pragma unroll
         for (int i = 0; i < MI; ++i)

@@ -209,7 +209,7 @@ __device__ __forceinline__ void gemm_mx_body(const GemmMxArgs& g, const int m0, 
 #pragma unroll
                 for (int hb = 0; hb < 2; ++hb)
                     tile_epilogue<2, 1, 32, float, 0, true, true>(g, reinterpret_cast<f32x16 (&)[2][1]>(acc[ha][hb]), smem, m0, n0, ha * 128 + wr * 64,
-                                                                  hb * 128 + wc * 32, wave, lane, 0, true, nullptr, ksplit);
+                                                                  hb * 128 + wc * 32, wave, lane, true, nullptr, ksplit);
             return;
         }
     }
@@ -218,7 +218,7 @@ __device__ __forceinline__ void gemm_mx_body(const GemmMxArgs& g, const int m0, 
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb)
             tile_epilogue<2, 1, 32, TOUT, 0, true, SLICE>(g, reinterpret_cast<f32x16 (&)[2][1]>(acc[ha][hb]), smem, m0, n0, ha * 128 + wr * 64,
-                                                          hb * 128 + wc * 32, wave, lane, 0, split, nullptr, ksplit);
+                                                          hb * 128 + wc * 32, wave, lane, split, nullptr, ksplit);
 }
 
 template <typename TOUT, bool SLICE>
@@ -230,9 +230,6 @@ __global__ __launch_bounds__(512) void gemm_mx_kernel(GemmMxArgs g) {
     const int ksplit = lg / nwg, bid = lg - ksplit * nwg;
     const int nk_all = ((g.K / BK + 1) & ~1) + 2 * ((g.K + 127) / 128);
     const int kt0 = ksplit * g.kt_per_split, kt1 = min(nk_all, kt0 + g.kt_per_split);
-#ifndef OMLM_SUPER_ROWS
-#define OMLM_SUPER_ROWS 1024
-#endif
     constexpr int GROUP = OMLM_SUPER_ROWS / 256;
     const int gsz = GROUP * tiles_n;
     const int grp = bid / gsz, first_m = grp * GROUP;

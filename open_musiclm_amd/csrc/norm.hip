@@ -438,10 +438,7 @@ extern "C" int OMLM_API(omlm_layernorm_fwd)(const float* x, const float* gamma, 
     OMLM_CHECK_ARG(D % 4 == 0 && D <= 4 * LN_THREADS * LN_MAXV, "D must be a multiple of 4 and <= 4096");
     OMLM_CHECK_ARG(ldy >= D, "ldy < D");
     dim3 grid(ln_grid(M)), block(LN_THREADS);
-#ifndef OMLM_LN_ROW1
-#define OMLM_LN_ROW1 1          /* 1: D == 1024 rows take the row-pair kernels (next-row prefetch, fewer barriers); 0: the general kernels */
-#endif
-    if (OMLM_LN_ROW1 && D == 4 * LN_THREADS && mean && rstd) {
+    if (D == 4 * LN_THREADS && mean && rstd) {        // the row-pair kernels (next-row prefetch, fewer barriers)
         if (out_dtype == 0) {
             if (xcast) hipLaunchKernelGGL((ln_fwd_row1_kernel<float, true>), grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, ldy, eps);
             else       hipLaunchKernelGGL((ln_fwd_row1_kernel<float, false>), grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, ldy, eps);
@@ -509,10 +506,7 @@ extern "C" int OMLM_API(omlm_layernorm_bwd2)(const void* dy, const float* x, con
     dim3 grid(blocks), block(LN_THREADS);
     float* part = two_level ? workspace : nullptr;
     OMLM_CHECK_ARG(dy_dtype == 0 || dy_dtype == 1, "dy_dtype: 0 = fp32, 1 = bf16, 2 = fp16 (same 16-bit type as the cast output)");
-#ifndef OMLM_LN_ROW1
-#define OMLM_LN_ROW1 1          /* 1: D == 1024 rows take ln_bwd_row1_kernel (next-row prefetch, one barrier per row) */
-#endif
-    if (OMLM_LN_ROW1 && D == 4 * LN_THREADS) {
+    if (D == 4 * LN_THREADS) {                        // ln_bwd_row1_kernel (next-row prefetch, one barrier per row)
         const int fl = (dres ? 1 : 0) | (dres2 ? 2 : 0) | (dxcast ? 4 : 0);
 #define LN_ROW1(TT, TD, F) hipLaunchKernelGGL((ln_bwd_row1_kernel<TT, TD, F>), grid, block, 0, as_stream(stream), (const TD*)dy, x, gamma, mean, rstd, dres, \
                                               (const TT*)dres2, dx, (TT*)dxcast, dgamma, part, M, dx_scale)
@@ -598,12 +592,8 @@ __global__ __launch_bounds__(256) void qk_norm_bwd_kernel(const float* __restric
     float aq[4] = {0.f, 0.f, 0.f, 0.f}, ak[4] = {0.f, 0.f, 0.f, 0.f};
     // several vectors per lane per trip, all their loads requested before the first reduction (one vector per trip with a 64-bit
     // division in front of its loads ran at 2.7 TB/s -- 83 us at M = 35712, H = 8: one dependent round trip at a time per wave; now 51 us)
-#ifndef QKB_U
 #define QKB_U 4                 /* vectors per lane per trip */
-#endif
-#ifndef QKB_BLOCKS
 #define QKB_BLOCKS 512          /* workgroups: each ends with 128 atomics into the two scale gradients (2048 workgroups: 69 us, 512: 51 us) */
-#endif
     constexpr int U = QKB_U;
     const unsigned stride = gridDim.x * 16u;
     for (unsigned base = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 4u; base < nvec; base += stride * U) {
@@ -669,92 +659,16 @@ __global__ __launch_bounds__(256) void qk_norm_bwd_kernel(const float* __restric
 // The same backward from what the fused projection epilogue (omlm_gemm_qknorm) leaves behind: y = s * x / n in the 16-bit operand type
 // and n = max(|x|, 1e-12) in fp32 -- xh = y / s (one operand rounding, like every other operand of the 16-bit modes; a zero scale
 // gives xh = 0: its dx is 0 anyway, only its d(scale) is lost).  No fp32 pre-norm projections are read (146 -> 64 MB per layer).
-template <typename T>
-__global__ __launch_bounds__(256) void qk_norm_bwd2_mixed_kernel(const float* __restrict__ dq, const float* __restrict__ dk,
-                                                           const float* __restrict__ dv, const T* __restrict__ q, const T* __restrict__ k,
-                                                           const float* __restrict__ qn, const float* __restrict__ kn,
-                                                           const float* __restrict__ q_scale, const float* __restrict__ k_scale,
-                                                           T* __restrict__ dq_raw, T* __restrict__ dkv_raw, float* __restrict__ dq_scale,
-                                                           float* __restrict__ dk_scale, int M, int H) {
-    const int lane = threadIdx.x & 63, sub = lane >> 4, d0 = 4 * (lane & 15);
-    const unsigned nvec = (unsigned)M * (unsigned)(H + 2), hp2 = (unsigned)(H + 2);
-    const float4 qs = *(const float4*)(q_scale + d0), ks = *(const float4*)(k_scale + d0);
-    auto rcp0 = [](float v) { return v != 0.f ? 1.0f / v : 0.f; };
-    const float4 qsi = make_float4(rcp0(qs.x), rcp0(qs.y), rcp0(qs.z), rcp0(qs.w)), ksi = make_float4(rcp0(ks.x), rcp0(ks.y), rcp0(ks.z), rcp0(ks.w));
-    float aq[4] = {0.f, 0.f, 0.f, 0.f}, ak[4] = {0.f, 0.f, 0.f, 0.f};
-    constexpr int U = QKB_U;
-    const unsigned stride = gridDim.x * 16u;
-    for (unsigned base = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 4u; base < nvec; base += stride * U) {
-        bool live[U], isq[U], isk[U];
-        int row[U], j[U];
-        float4 y[U], dy[U];
-        float nr[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const unsigned vec = base + u * stride + sub;
-            live[u] = vec < nvec;
-            row[u] = live[u] ? (int)(vec / hp2) : 0;
-            j[u] = live[u] ? (int)(vec - (unsigned)row[u] * hp2) : H + 1;
-            isq[u] = j[u] < H; isk[u] = j[u] == H;
-            y[u] = make_float4(0.f, 0.f, 0.f, 0.f); dy[u] = y[u]; nr[u] = 1.f;
-            if (live[u]) {
-                if (isq[u])      { y[u] = load4f(q + (size_t)row[u] * H * 64 + j[u] * 64, d0 >> 2); dy[u] = *(const float4*)(dq + (size_t)row[u] * H * 64 + j[u] * 64 + d0); nr[u] = qn[(size_t)row[u] * H + j[u]]; }
-                else if (isk[u]) { y[u] = load4f(k + (size_t)row[u] * 64, d0 >> 2);               dy[u] = *(const float4*)(dk + (size_t)row[u] * 64 + d0); nr[u] = kn[row[u]]; }
-                else             { dy[u] = *(const float4*)(dv + (size_t)row[u] * 64 + d0); }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float4 s = isq[u] ? qs : ks, si = isq[u] ? qsi : ksi;
-            const bool clamped = nr[u] <= 1e-12f;
-            const float inv = 1.0f / nr[u];
-            const float xh[4] = {y[u].x * si.x, y[u].y * si.y, y[u].z * si.z, y[u].w * si.w};
-            const float gy[4] = {s.x * dy[u].x, s.y * dy[u].y, s.z * dy[u].z, s.w * dy[u].w};
-            float proj = group16_sum(xh[0] * gy[0] + xh[1] * gy[1] + xh[2] * gy[2] + xh[3] * gy[3]);      // all lanes take part
-            if (clamped) proj = 0.f;
-            if (!live[u]) continue;
-            if (isq[u] || isk[u]) {
-                const float o0 = (gy[0] - xh[0] * proj) * inv, o1 = (gy[1] - xh[1] * proj) * inv;
-                const float o2 = (gy[2] - xh[2] * proj) * inv, o3 = (gy[3] - xh[3] * proj) * inv;
-                if (isq[u]) {
-                    store4(dq_raw + (size_t)row[u] * H * 64 + j[u] * 64 + d0, o0, o1, o2, o3);
-                    aq[0] += dy[u].x * xh[0]; aq[1] += dy[u].y * xh[1]; aq[2] += dy[u].z * xh[2]; aq[3] += dy[u].w * xh[3];
-                } else {
-                    store4(dkv_raw + (size_t)row[u] * 128 + d0, o0, o1, o2, o3);
-                    ak[0] += dy[u].x * xh[0]; ak[1] += dy[u].y * xh[1]; ak[2] += dy[u].z * xh[2]; ak[3] += dy[u].w * xh[3];
-                }
-            } else {
-                store4(dkv_raw + (size_t)row[u] * 128 + 64 + d0, dy[u].x, dy[u].y, dy[u].z, dy[u].w);
-            }
-        }
-    }
-    __shared__ float sq[4][64], sk[4][64];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        aq[i] += __shfl_xor(aq[i], 16, 64); aq[i] += __shfl_xor(aq[i], 32, 64);
-        ak[i] += __shfl_xor(ak[i], 16, 64); ak[i] += __shfl_xor(ak[i], 32, 64);
-        if (lane < 16) { sq[threadIdx.x >> 6][d0 + i] = aq[i]; sk[threadIdx.x >> 6][d0 + i] = ak[i]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        unsafeAtomicAdd(dq_scale + lane, sq[0][lane] + sq[1][lane] + sq[2][lane] + sq[3][lane]);
-        unsafeAtomicAdd(dk_scale + lane, sk[0][lane] + sk[1][lane] + sk[2][lane] + sk[3][lane]);
-    }
-}
-
-
-// Round 4, second form (QKB2_STREAM, default): the mixed kernel above walks one list of (row, head | k | v) vectors, so every load and
-// store of its trip sits behind a per-vector kind test; hipcc's s_waitcnt bookkeeping then has to assume the shortest path ("nothing
-// was issued behind this load") and the four vectors of a trip were in fact requested one after the other, each wait also draining
-// the stores before it (seen in the ISA: vmcnt(0) between the units; 62 us per layer = 2.9 TB/s).  Here the q vectors are what they
+// Round 4: a first form walked one list of (row, head | k | v) vectors, so every load and store of its trip sat behind a per-vector
+// kind test; hipcc's s_waitcnt bookkeeping then had to assume the shortest path ("nothing was issued behind this load") and the four
+// vectors of a trip were in fact requested one after the other, each wait also draining the stores before it (seen in the ISA:
+// vmcnt(0) between the units; 62 us per layer = 2.9 TB/s).  Here the q vectors are what they
 // are in memory -- ONE contiguous stream of M * H 64-wide vectors with identical work -- and a unit is 8 consecutive vectors: lane l
 // holds elements 8 (l & 7) .. + 7 of vector (l >> 3), a wave-instruction reads 1 KiB of q / 2 x 1 KiB of dq contiguously.  Whole units
 // run two at a time without a single condition (counted waits); the ragged tail and the k | v rows (1 / (H + 1) of the bytes) take
 // the predicated body.
-#ifndef QKB2_THREADS
 #define QKB2_THREADS 1024       /* 16 waves per workgroup: a quarter of the atomics of 256-thread workgroups at the same waves per CU (1024 workgroups x 128 atomics onto 128
                                    addresses were ~10 us of serialised tail) */
-#endif
 struct QkUnit { u32x4 y; float4 d0, d1; float nr; };
 
 template <typename T>
@@ -885,22 +799,11 @@ extern "C" int OMLM_API(omlm_qk_norm_bwd2)(const float* dq, const float* dk, con
     OMLM_CHECK_ARG(dq && dk && dv && q && k && qn && kn && dq_raw && dkv_raw && dq_scale && dk_scale, "null pointer");
     long long nvec = (long long)M * (H + 2);
     OMLM_CHECK_ARG(nvec < (1ll << 31), "qk_norm_bwd2: M * (H + 2) must stay below 2^31 (32-bit vector index)");
-#ifndef QKB2_STREAM
-#define QKB2_STREAM 1           /* 1: the stream form (qk_norm_bwd2_kernel), 0: the mixed-vector form of round 4's first half */
-#endif
-#ifndef QKB2_BLOCKS
-#define QKB2_BLOCKS 256         /* workgroups of the stream form (QKB2_THREADS / 64 waves each; 128 atomics per workgroup at the end) */
-#endif
-#if QKB2_STREAM
+#define QKB2_BLOCKS 256         /* workgroups (QKB2_THREADS / 64 waves each; 128 atomics per workgroup at the end) */
     long long want = ((long long)M * H / 8 + 2 * (QKB2_THREADS / 64) - 1) / (2 * (QKB2_THREADS / 64));      // ~2 units per wave at least
     int blocks = want > QKB2_BLOCKS ? QKB2_BLOCKS : (want < 1 ? 1 : (int)want);
     hipLaunchKernelGGL(qk_norm_bwd2_kernel<h16_t>, dim3(blocks), dim3(QKB2_THREADS), 0, as_stream(stream), dq, dk, dv, (const h16_t*)q, (const h16_t*)k, qn, kn,
                        q_scale, k_scale, (h16_t*)dq_raw, (h16_t*)dkv_raw, dq_scale, dk_scale, M, H);
-#else
-    int blocks = (int)((nvec + 15) / 16); if (blocks > QKB_BLOCKS) blocks = QKB_BLOCKS;
-    hipLaunchKernelGGL(qk_norm_bwd2_mixed_kernel<h16_t>, dim3(blocks), dim3(256), 0, as_stream(stream), dq, dk, dv, (const h16_t*)q, (const h16_t*)k, qn, kn,
-                       q_scale, k_scale, (h16_t*)dq_raw, (h16_t*)dkv_raw, dq_scale, dk_scale, M, H);
-#endif
     return omlm_post_launch("omlm_qk_norm_bwd2");
 }
 

@@ -14,7 +14,6 @@ counter advance; the row index lives on the device so that a step can be capture
 from __future__ import annotations
 
 import ctypes as C
-import os
 from typing import List, Optional, Sequence
 
 import torch
@@ -54,13 +53,12 @@ def _geometry(model):
 
 def _second_generation(D: int, H: int, Fp: int) -> bool:
     """omlm_decode_step's v2_ok: the dec2 / dec3 / dec4 step kernels serve dim 1024 only; everything else runs on the first-generation kernels."""
-    return D == 1024 and H * 64 <= 1024 and Fp <= 4096 and os.environ.get("OMLM_DECODE_V1", "0") != "1"
+    return D == 1024 and H * 64 <= 1024 and Fp <= 4096
 
 
 def _matrix_core(B: int, D: int, H: int, Fp: int) -> bool:
     """decode.hip dec4_ok (16-bit weights, the LayerNorm partials always given): the matrix-core step kernels."""
-    return (os.environ.get("OMLM_DECODE_MFMA", "1") != "0" and 2 <= B <= DEC4_NB and D % 32 == 0 and D <= 1024 and H * 64 <= 1024
-            and Fp % 32 == 0 and Fp <= 3072)
+    return 2 <= B <= DEC4_NB and D % 32 == 0 and D <= 1024 and H * 64 <= 1024 and Fp % 32 == 0 and Fp <= 3072
 
 
 def lo_planes_ok(model, batch: int) -> bool:

@@ -40,45 +40,26 @@ def is_half(precision: str) -> bool:
     """The IEEE-half modes: loss scale in the backward, fp16 weight shadow in the optimizer, fp16 decode kernels."""
     return precision in ("fp16", "fp16ff")
 _H16 = (torch.bfloat16, torch.float16)
-_WT = os.environ.get("OMLM_WT", "0") == "1"
-_FF_SAVE_GH = os.environ.get("OMLM_FF_SAVE_GH", "1") == "1"        # forward keeps the normalised GEGLU output for the backward (bf16 mode)
-_WGRAD_GROUP = os.environ.get("OMLM_WGRAD_GROUP", "1") == "1"      # grouped weight-gradient GEMMs (0: one split-K GEMM per weight)
-# The rel-pos-bias MLP (transformer.py:36-67: 3 x Linear(dim/2)+SiLU + Linear(heads) on N distances) is ~20 tiny fp32 kernels per
-# step, 4..36 workgroups each: ~0.4 ms of pure launch-to-launch latency when they sit in the trunk's stream.  They depend on
-# nothing but the weights (forward) / the finished d(table) (backward), so they run on a second HIP stream, forked and joined with
-# events (captured as a parallel branch of the micro-step graph): OMLM_RELPOS_ASYNC=1.  OFF since round 4: with the trunk's kernels now
-# filling the machine the branch contends for CUs more than it hides (same-box A/B, graph replay: 24.81 ms with it, 24.58 without), and
-# a single stream has no cross-stream hazards at all.
-_RELPOS_ASYNC = os.environ.get("OMLM_RELPOS_ASYNC", "0") == "1"
-# The MLP's 0.3-GFLOP fp32 GEMMs stay on the register-staged fp32 kernel (csrc/gemm.hip gemm_kernel<float>): 42 us either way, and the
-# hi/lo plane route (ops.operand_planes: extra buffers + a cache shared with the trunk's stream) buys nothing at this size.
-# OMLM_RELPOS_PLANES=1: the plane route (what rounds 2-3 ran).
-_RELPOS_PLANES = os.environ.get("OMLM_RELPOS_PLANES", "0") == "1"
-# bf16 mode: d(LN output) leaves the input-gradient GEMMs as bf16 (fp32 accumulate, one rounding) instead of fp32 -- it is read once,
-# by the LayerNorm backward, and every other GEMM operand of that mode is rounded the same way.  OMLM_BF16_LN_GRAD=0: fp32 as before.
-_BF16_LN_GRAD = os.environ.get("OMLM_BF16_LN_GRAD", "1") == "1"
-# 16-bit modes: the K/V projection's input gradient leaves its GEMM as a 16-bit tensor and is added to the residual gradient inside the
-# attention LayerNorm's backward (ops.layernorm_bwd dres2) instead of by the GEMM's own fp32 read-add-write epilogue (0: that form)
-_KV_DGRAD_H16 = os.environ.get("OMLM_KV_DGRAD_H16", "1") == "1"
-# 16-bit modes: the attention's l2-norm + learned scale of q / k (transformer.py:265-271) is the epilogue of the projection GEMMs
-# (ops.gemm_qknorm): q, k, v leave them in the operand type with the per-(row, head) norms in fp32 -- no fp32 q_raw / kv_raw, no qk_norm
-# forward launch, and the backward derives xh = y / scale from the saved operand.  OMLM_QKNORM_FUSED=0: separate kernels on fp32 projections.
-_QKNORM_FUSED = os.environ.get("OMLM_QKNORM_FUSED", "1") == "1"
-# The rel-pos MLP as one fused forward launch + two backward launches (round 5; Hd = 256 / 512; exact fp32 matrix instruction, every
-# gradient element owned by one lane: deterministic) instead of the layer-by-layer path (7 + 14 launches, three register-staged fp32 GEMMs
-# each way, split-K atomics in the backward).  Measured same box: forward 93 us, backward 276 us, the step equal within noise (23.60 / 23.74
-# vs 23.62 / 23.66 ms): a row-block workgroup has to stream both 1 MB weight matrices through its own L2 -> CU path (~2 MB at ~40 GB/s per
-# CU), which bounds it whatever does the arithmetic (VALU FMAs and MFMAs measured the same).  On by default for the launch count and the
-# determinism; OMLM_RELPOS_FUSED=0: the layer-by-layer path.
-_RELPOS_FUSED = os.environ.get("OMLM_RELPOS_FUSED", "1") == "1"
-_LN_COLSUM_GROUP = os.environ.get("OMLM_LN_COLSUM_GROUP", "1") == "1"    # 0: every LayerNorm backward sums its own d(gamma) partial rows
 
-
-def ff_mx_enabled() -> bool:
-    """precision "fp16ff": FF-in / FF-out as one half product + two fp8 correction products at twice the matrix rate (ops.gemm_mx16, round 6) instead
-    of three half products (ops.gemm_planes16, round 5).  What the fp8 corrections leave in the logits: profiles/r06_error_budget_fp8corr.md.
-    OMLM_FF_MX=0 (read when the weights are prepared): the three-product form."""
-    return os.environ.get("OMLM_FF_MX", "1") == "1"
+# Routes of the trunk that were settled by measurement (profiles/, commit history):
+# * The rel-pos-bias MLP (transformer.py:36-67) runs on the trunk's stream.  A second stream forked and joined with events measured slower
+#   once the trunk's kernels filled the machine (round 4, same-box A/B, graph replay: 24.81 ms with it, 24.58 without).
+# * Its fp32 GEMMs on the layer-by-layer path stay on the register-staged fp32 kernel (csrc/gemm.hip gemm_kernel<float>): 42 us either
+#   way, and the hi/lo plane route buys nothing at this size.
+# * Where the geometry allows it the MLP is one fused forward launch + two backward launches (round 5; Hd = 256 / 512; exact fp32 matrix
+#   instruction, every gradient element owned by one lane: deterministic) instead of the layer-by-layer path (7 + 14 launches).  Measured
+#   same box: the step equal within noise (23.60 / 23.74 vs 23.62 / 23.66 ms); kept for the launch count and the determinism.
+# * 16-bit modes: d(LN output) leaves the input-gradient GEMMs in the operand type (fp32 accumulate, one rounding) -- it is read once, by
+#   the LayerNorm backward, and every other GEMM operand of those modes is rounded the same way.
+# * 16-bit modes: the K/V projection's input gradient leaves its GEMM as a 16-bit tensor and is added to the residual gradient inside the
+#   attention LayerNorm's backward (ops.layernorm_bwd dres2) instead of by the GEMM's own fp32 read-add-write epilogue.
+# * 16-bit modes: the attention's l2-norm + learned scale of q / k (transformer.py:265-271) is the epilogue of the projection GEMMs
+#   (ops.gemm_qknorm): q, k, v leave them in the operand type with the per-(row, head) norms in fp32 -- no fp32 q_raw / kv_raw, no qk_norm
+#   forward launch, and the backward derives xh = y / scale from the saved operand.  "bf16x3" keeps the separate kernels.
+# * 16-bit modes: the weight gradients are issued as grouped launches of full-K tiles (ops.WgradGroup), not one split-K GEMM per weight.
+# * "fp16ff": FF-in / FF-out as one half product + two fp8 correction products at twice the matrix rate (ops.gemm_mx16, round 6) instead of
+#   three half products (ops.gemm_planes16, round 5) wherever ff_mx_ok holds.  What the fp8 corrections leave in the logits:
+#   profiles/r06_error_budget_fp8corr.md.
 
 
 FF_PLANES_MAX_FP = 4096      # omlm_ffmid_fwd_planes / omlm_ffmid_fwd_mx: Fp <= 4096 (ffmid2_supported)
@@ -93,17 +74,6 @@ def ff_mx_ok(D: int, Fp: int) -> bool:
     """The fp8-corrected route's own limits: omlm_gemm_mx16 takes K % 64 == 0 (FF-in: K = D; FF-out: K = Fp, a multiple of 64), and its fp8 A
     rows of 2 D bytes written by omlm_layernorm_fwd_mx must hold D rounded up to 128 (true for D % 64 == 0, D <= 4096)."""
     return D % 64 == 0 and D <= 4096 and Fp % 64 == 0 and ff_planes_ok(Fp)
-
-
-_SIDE_STREAMS: Dict[int, "torch.cuda.Stream"] = {}
-
-
-def side_stream(dev: torch.device) -> "torch.cuda.Stream":
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    st = _SIDE_STREAMS.get(idx)
-    if st is None:
-        st = _SIDE_STREAMS[idx] = torch.cuda.Stream(device=dev)
-    return st
 
 
 def default_precision() -> str:
@@ -256,7 +226,7 @@ def h16_operand(w: torch.Tensor, T: torch.dtype) -> torch.Tensor:
 
 
 class PreparedWeights:
-    def __init__(self, model, precision: str, with_transposes: bool = False, persistent: bool = True):
+    def __init__(self, model, precision: str, persistent: bool = True):
         """persistent: the padded FF / tap / gamma images live in per-model buffers that EVERY persistent instance rewrites in place (the
         training step: one instance alive at a time, forward -> backward).  Instances that outlive a step (the no_grad cache below, a
         CachedDecoder) take persistent=False: private images, so a later training step cannot change the weights under them."""
@@ -272,7 +242,7 @@ class PreparedWeights:
         self.ff_planes = self.ff3 and all(ff_planes_ok(f) for f in Fp_all)
         # ... with the FF GEMMs' correction products on fp8 planes (W1p8 / W2p8: ops.Fp8Planes), where omlm_gemm_mx16 takes the geometry
         # (otherwise the three-product omlm_gemm_planes16 route)
-        self.mx = self.ff_planes and ff_mx_enabled() and all(ff_mx_ok(D, f) for f in Fp_all)
+        self.mx = self.ff_planes and all(ff_mx_ok(D, f) for f in Fp_all)
         quants = ops.QuantRowsGroup()
         self.layers = []
         # padded operand images are persistent per (layer, operand type): their pad rows / columns are zeroed once, a step only rewrites the
@@ -330,21 +300,6 @@ class PreparedWeights:
                 quants.add(w1.detach()[F:], m8[0], Fp, F, D, D)
                 quants.add(w2.detach(), m8[1], 0, D, F, F)
                 ent["W1p8"], ent["W2p8"] = m8
-            if T in _H16 and with_transposes:
-                # k-contiguous W^T copies: every input-gradient GEMM (dX = dY W) then runs in the fast NT form
-                def wt(w, R, C, rows_pad=None, cols_pad=None):
-                    t = torch.zeros(rows_pad or C, cols_pad or R, dtype=T, device=dev)
-                    ops.transpose_cast(w.detach(), t, R, C, w.shape[-1], t.shape[-1])
-                    return t
-                HD = attn.to_q.weight.shape[0]
-                ent["WqT"] = wt(attn.to_q.weight, HD, D)                      # [D, H*dh]
-                ent["WkvT"] = wt(attn.to_kv.weight, attn.to_kv.weight.shape[0], D)
-                ent["WoT"] = wt(attn.to_out[0].weight, D, HD)                 # [H*dh, D]
-                W1pT = torch.zeros(D, 2 * Fp, dtype=T, device=dev)            # [D, 2Fp]: value half cols [0,F), gate half [Fp, Fp+F)
-                ops.transpose_cast(w1.detach(), W1pT, F, D, D, 2 * Fp)
-                ops.transpose_cast(w1.detach()[F:], W1pT[:, Fp:], F, D, D, 2 * Fp)
-                ent["W1pT"] = W1pT
-                ent["W2pT"] = wt(w2, D, F, rows_pad=Fp, cols_pad=D)           # [Fp, D], rows >= F zero
             # taps [3, 2Fp] (identity taps for plain FeedForward) and the padded LN gamma travel in the operand dtype: they are
             # re-read for every row, and as fp32 they were 70 % of the L2->L1 bytes of the conv-GEGLU-LN kernels
             cw = ff.conv_weight().detach().reshape(2 * F, 3)                 # reference ds_conv.weight [2F, 1, 3] -> tap-major [3, 2Fp]
@@ -372,20 +327,7 @@ class PreparedWeights:
                 self.heads_lo.append(lo)
         packs.flush()
         quants.flush()
-        self.heads = []
-        self.headsT = []
-        for w in model.logit_weights:
-            if T == torch.float32:
-                self.heads.append(w)
-            else:
-                self.heads.append(h16_operand(w, T))
-                if with_transposes:                                          # [Q, D, ldV], pad columns zero
-                    Q, V1 = w.shape[0], w.shape[1]
-                    ldV = ceil_to(V1, 8)
-                    t = torch.zeros(Q, D, ldV, dtype=T, device=dev)
-                    for qq in range(Q):
-                        ops.transpose_cast(w.detach()[qq], t[qq], V1, D, D, ldV)
-                    self.headsT.append(t)
+        self.heads = [w if T == torch.float32 else h16_operand(w, T) for w in model.logit_weights]
 
 
 def prepared_weights(model, precision: str) -> PreparedWeights:
@@ -473,7 +415,7 @@ def relpos_forward(tr, n: int, save: bool):
         return table, ("t5", bucket)
     lin = [rp.net[0][0], rp.net[1][0], rp.net[2][0], rp.net[3]]
     Hd = lin[0].weight.shape[0]
-    if _RELPOS_FUSED and Hd in (256, 512) and H <= 16 and len(rp.net) == 4:
+    if Hd in (256, 512) and H <= 16 and len(rp.net) == 4:
         # one launch for the whole MLP (csrc/optim_misc.hip relpos_mlp_fwd_kernel; round 5): a workgroup carries 8 rows through all layers
         saves = [torch.empty(n, Hd, device=dev) for _ in range(6)] if save else None
         table = torch.empty(n, ldb, device=dev)
@@ -489,7 +431,7 @@ def relpos_forward(tr, n: int, save: bool):
         # (the FORWARD GEMMs stay unsplit: a split-K sum is order-of-arrival, and 1e-7 of noise in the table is amplified by the 16-bit
         # roundings downstream -- run-to-run d(table) went from 2e-3 to 2e-2 in bf16 when they were split; the backward's GEMMs below do split)
         a = torch.empty(n, Hd, device=dev)
-        ops.gemm(zs[-1], lin[k].weight.detach(), a, M=n, N=Hd, K=Hd, planes=_RELPOS_PLANES)
+        ops.gemm(zs[-1], lin[k].weight.detach(), a, M=n, N=Hd, K=Hd, planes=False)
         pre = torch.empty(n, Hd, device=dev)
         z = torch.empty(n, Hd, device=dev)
         ops.bias_silu_fwd(a, lin[k].bias.detach(), pre, z, n, Hd)
@@ -531,9 +473,9 @@ def relpos_backward(tr, n: int, saved, dtable: torch.Tensor):
         ops.silu_bwd(dz, pres[k], ds, n * Hd)
         ops.colsum_accumulate(ds, grad_of(lin[k].bias), n, Hd, Hd)
         gw = grad_of(lin[k].weight)
-        ops.gemm(ds, zs[k - 1], gw, M=Hd, N=Hd, K=n, a_kmajor=True, b_kmajor=True, Cin=gw, planes=_RELPOS_PLANES)
+        ops.gemm(ds, zs[k - 1], gw, M=Hd, N=Hd, K=n, a_kmajor=True, b_kmajor=True, Cin=gw, planes=False)
         dz = torch.zeros(n, Hd, device=dev)        # zero-filled + Cin == C: lets the fp32 GEMM split its K over more workgroups (gemm.hip: `fine`)
-        ops.gemm(ds, lin[k].weight.detach(), dz, M=n, N=Hd, K=Hd, b_kmajor=True, Cin=dz, planes=_RELPOS_PLANES)
+        ops.gemm(ds, lin[k].weight.detach(), dz, M=n, N=Hd, K=Hd, b_kmajor=True, Cin=dz, planes=False)
     ds = torch.empty(n, Hd, device=dev)
     ops.silu_bwd(dz, pres[0], ds, n * Hd)
     ops.colsum_accumulate(ds, grad_of(lin[0].bias), n, Hd, Hd)
@@ -573,25 +515,17 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
     dev = x.device
     M, D = x.shape
     H = tr.heads
-    side = None
-    if _RELPOS_ASYNC and tr.rel_pos_bias is not None and tr.relative_position_bias_type != "t5":
-        main = torch.cuda.current_stream(dev)
-        side = side_stream(dev)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            table, rp_saved = relpos_forward(tr, N, save)       # joined in front of the first attention kernel
+    rc = tr.__dict__.get("_omlm_relpos_cache")
+    if rc is not None and save and training and rc.usable(N):
+        table, rp_saved = rc.table, ("cached", rc)                # (RelposStepCache: computed once for this optimizer step)
     else:
-        rc = tr.__dict__.get("_omlm_relpos_cache")
-        if rc is not None and save and training and rc.usable(N):
-            table, rp_saved = rc.table, ("cached", rc)            # (RelposStepCache: computed once for this optimizer step)
-        else:
-            table, rp_saved = relpos_forward(tr, N, save)
-            # the FIRST training forward is adopted, once: a captured micro-step holds the addresses of the cache's buffers, so they are
-            # never replaced (a stale cache -- validation between two optimizer steps -- computes in line and leaves the cache alone)
-            if (rc is not None and rc.enabled and rc.n is None and save and training and rp_saved is not None and rp_saved[0] != "t5"
-                    and not torch.cuda.is_current_stream_capturing()):
-                rc.adopt(N, table, rp_saved)
-                rp_saved = ("cached", rc)
+        table, rp_saved = relpos_forward(tr, N, save)
+        # the FIRST training forward is adopted, once: a captured micro-step holds the addresses of the cache's buffers, so they are
+        # never replaced (a stale cache -- validation between two optimizer steps -- computes in line and leaves the cache alone)
+        if (rc is not None and rc.enabled and rc.n is None and save and training and rp_saved is not None and rp_saved[0] != "t5"
+                and not torch.cuda.is_current_stream_capturing()):
+            rc.adopt(N, table, rp_saved)
+            rp_saved = ("cached", rc)
     saved_layers: List[LayerSaved] = []
     abiases = None
     salt, seeds = (None, None)
@@ -607,7 +541,7 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
         q = torch.empty(M, H * DIM_HEAD, dtype=T, device=dev)
         k = torch.empty(M, DIM_HEAD, dtype=T, device=dev)
         v = torch.empty(M, DIM_HEAD, dtype=T, device=dev)
-        fused_qk = T in _H16 and _QKNORM_FUSED
+        fused_qk = T in _H16
         if fused_qk:
             qn = torch.empty(M, H, device=dev)
             kn = torch.empty(M, device=dev)
@@ -622,10 +556,6 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
             ops.qk_norm_fwd(q_raw, kv_raw, attn.q_scale.detach(), attn.k_scale.detach(), q, k, v, H)
         o = torch.empty(M, H * DIM_HEAD, dtype=T, device=dev)
         lse = torch.empty(B, H, N, device=dev)
-        if side is not None:
-            torch.cuda.current_stream(dev).wait_stream(side)
-            table.record_stream(torch.cuda.current_stream(dev))      # allocated under the side stream, read by the trunk's kernels
-            side = None
         # the layer's bias table in the kernels' layout, with the fixed softmax reference point its scales allow (fp16: 15 octaves below the
         # bound, so that the probability numerators use half's normal range -- at the bound itself typical ones sat around 2^-12)
         # (round 6: the tables of all layers leave in ONE launch in front of the first attention kernel -- they differ only through the layers'
@@ -666,7 +596,7 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
         drop_bits = torch.empty(M, Fp // 8, dtype=torch.uint8, device=dev) if (p > 0 and (save or pw.ff_planes)) else None
         # the normalised GEGLU output is saved for the backward: its row-sum prepass reads it instead of recomputing conv + GELU, and
         # the fused second-generation backward (csrc/ffmid2.hip) requires it
-        gh = torch.empty(M, Fp, dtype=T, device=dev) if (save and _FF_SAVE_GH) else None
+        gh = torch.empty(M, Fp, dtype=T, device=dev) if save else None
         x2 = torch.empty(M, D, device=dev)
         if pw.ff_planes:
             if pw.mx:
@@ -700,9 +630,6 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
             sv.gh = gh
             saved_layers.append(sv)
         x = x2
-    if side is not None:                                         # depth 0: nothing consumed the table
-        torch.cuda.current_stream(dev).wait_stream(side)
-        table.record_stream(torch.cuda.current_stream(dev))
     mf = torch.empty(M, device=dev); rf = torch.empty(M, device=dev)
     y = torch.empty(M, D, dtype=T, device=dev)
     if pw.ff3:                                                   # the lo plane rides on the tensor until heads_forward has read it
@@ -726,19 +653,17 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
     rp_cached = saved["rp"] is not None and saved["rp"][0] == "cached"
     dtable = (saved["rp"][1].dtable if rp_cached else torch.zeros_like(table)) if table is not None else None
     nl = len(saved["layers"])
-    rp_async = (_RELPOS_ASYNC and nl > 0 and dtable is not None and saved["rp"] is not None and saved["rp"][0] == "mlp")
-    rp_side = None
     dres = torch.empty(M, D, device=dev)
     dres_c = dres if T == torch.float32 else torch.empty(M, D, dtype=T, device=dev)
     # the d(gamma) partial rows of every LayerNorm backward of this pass are summed by ONE launch at its end (13 launches of ~8 us before)
-    cg = ops.ColsumGroup() if _LN_COLSUM_GROUP else None
+    cg = ops.ColsumGroup()
     ops.layernorm_bwd(dy, saved["xL"], tr.norm.gamma.detach(), saved["mf"], saved["rf"], None, dres,
                       None if T == torch.float32 else dres_c, grad_of(tr.norm.gamma),
                       dx_scale=out_scale if nl == 0 else 1.0, defer=cg)
     ws = None
     # weight gradients have no consumer before the optimizer: in bf16 mode they are collected and issued as grouped launches of
     # full-K tiles (ops.WgradGroup) instead of 5 split-K GEMMs per layer; their operands stay alive until the flush
-    wg = ops.WgradGroup() if (T in _H16 and _WGRAD_GROUP) else None
+    wg = ops.WgradGroup() if T in _H16 else None
     for dYh, Xh, dWh, Mo, No in (head_wgrads or []):             # the logit heads' weight gradients (heads_backward) ride in the same launch
         if wg is not None:
             wg.add(dYh, Xh, dWh, M=Mo, N=No, K=dYh.shape[0])
@@ -759,8 +684,7 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
         F, Fp = w["F"], w["Fp"]
         # ---- feed-forward block: x2 = x1 + h2 W2^T ----
         dh2 = torch.empty(M, Fp, dtype=T, device=dev)
-        if "W2pT" in w: ops.gemm(dres_c, w["W2pT"], dh2, M=M, N=Fp, K=D)
-        else: ops.gemm(dres_c, w["W2p"], dh2, M=M, N=Fp, K=D, b_kmajor=True)
+        ops.gemm(dres_c, w["W2p"], dh2, M=M, N=Fp, K=D, b_kmajor=True)
         gW2 = grad_of(ff.w_out.weight)                                              # [D, F]
         wgrad(dres_c, sv.h2, gW2, D, F)
         if ws is None or ws.numel() < ops.ffmid_bwd_workspace_floats(F, Fp):
@@ -772,9 +696,8 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
                       grad_of(ff.norm_mid.gamma), gconv, ws, N, F, Fp, sv.p, sv.seed,
                       seed_dev=saved["salt"] if sv.p > 0 else None, drop_bits=sv.drop_bits, gh=sv.gh)
         del du, dh2
-        dxn2 = torch.empty(M, D, dtype=T if _BF16_LN_GRAD else torch.float32, device=dev)     # consumed only by the LayerNorm backward
-        if "W1pT" in w: ops.gemm(dh1, w["W1pT"], dxn2, M=M, N=D, K=2 * Fp)
-        else: ops.gemm(dh1, w["W1p"], dxn2, M=M, N=D, K=2 * Fp, b_kmajor=True)
+        dxn2 = torch.empty(M, D, dtype=T, device=dev)                                 # consumed only by the LayerNorm backward
+        ops.gemm(dh1, w["W1p"], dxn2, M=M, N=D, K=2 * Fp, b_kmajor=True)
         gW1 = grad_of(ff.w_in.weight)                                               # [2F, D]
         wgrad(dh1, sv.xn2, gW1, 2 * Fp, D, c_map=w["dW1_cmap"])
         del dh1
@@ -784,8 +707,7 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
                           None if T == torch.float32 else dx1_c, grad_of(ff.norm_in.gamma), defer=cg)
         # ---- attention block: x1 = x + o Wo^T ----
         do = torch.empty(M, H * DIM_HEAD, dtype=T, device=dev)
-        if "WoT" in w: ops.gemm(dx1_c, w["WoT"], do, M=M, N=H * DIM_HEAD, K=D)
-        else: ops.gemm(dx1_c, w["Wo"], do, M=M, N=H * DIM_HEAD, K=D, b_kmajor=True)
+        ops.gemm(dx1_c, w["Wo"], do, M=M, N=H * DIM_HEAD, K=D, b_kmajor=True)
         gWo = grad_of(attn.to_out[0].weight)
         wgrad(dx1_c, sv.o, gWo, D, H * DIM_HEAD)
         dq = torch.empty(M, H * DIM_HEAD, device=dev)
@@ -793,35 +715,19 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
         dk, dv = dkv[0], dkv[1]
         delta = torch.empty(B, H, N, device=dev)
         ops.attn_bwd(sv.q, sv.k, sv.v, sv.abias, keymask, sv.o, do, sv.lse, delta, dq, dk, dv, dtable, B, N, H, ATTN_SCALE)
-        if li == 0 and rp_async:
-            # d(table) is complete: the MLP's backward leaves for the second stream while the trunk finishes this layer and the
-            # grouped weight gradients (dtable / saved["rp"] stay referenced until the join at the end of this function)
-            rp_side = side_stream(dev)
-            for p_ in tr.rel_pos_bias.parameters():                # gradient buffers belong to the trunk's stream (allocated + zeroed
-                grad_of(p_)                                         # here, before the fork), whoever accumulates into them
-            rp_side.wait_stream(torch.cuda.current_stream(dev))
-            dtable.record_stream(rp_side)
-            for p_ in tr.rel_pos_bias.parameters():
-                p_.grad.record_stream(rp_side)
-            with torch.cuda.stream(rp_side):
-                relpos_backward(tr, N, saved["rp"], dtable)
         dq_raw = torch.empty(M, H * DIM_HEAD, dtype=T, device=dev)
         dkv_raw = torch.empty(M, 2 * DIM_HEAD, dtype=T, device=dev)
-        if T in _H16 and _QKNORM_FUSED:                                  # sv.q_raw / sv.kv_raw hold the norms [M, H] / [M]
+        if T in _H16:                                                    # sv.q_raw / sv.kv_raw hold the norms [M, H] / [M]
             ops.qk_norm_bwd2(dq, dk, dv, sv.q, sv.k, sv.q_raw, sv.kv_raw, attn.q_scale.detach(), attn.k_scale.detach(),
                              dq_raw, dkv_raw, grad_of(attn.q_scale), grad_of(attn.k_scale), H)
         else:
             ops.qk_norm_bwd(dq, dk, dv, sv.q_raw, sv.kv_raw, attn.q_scale.detach(), attn.k_scale.detach(),
                             dq_raw, dkv_raw, grad_of(attn.q_scale), grad_of(attn.k_scale), H)
-        dxn = torch.empty(M, D, dtype=T if _BF16_LN_GRAD else torch.float32, device=dev)
-        kv16 = T in _H16 and _KV_DGRAD_H16
+        dxn = torch.empty(M, D, dtype=T, device=dev)
+        kv16 = T in _H16
         tmp = torch.empty(M, D, dtype=T if kv16 else torch.float32, device=dev)      # kv16: the K/V term alone; else dx1 + the K/V term
-        if "WqT" in w:
-            ops.gemm(dq_raw, w["WqT"], dxn, M=M, N=D, K=H * DIM_HEAD)
-            ops.gemm(dkv_raw, w["WkvT"], tmp, M=M, N=D, K=2 * DIM_HEAD, Cin=None if kv16 else dx1)
-        else:
-            ops.gemm(dq_raw, w["Wq"], dxn, M=M, N=D, K=H * DIM_HEAD, b_kmajor=True)
-            ops.gemm(dkv_raw, w["Wkv"], tmp, M=M, N=D, K=2 * DIM_HEAD, b_kmajor=True, Cin=None if kv16 else dx1)
+        ops.gemm(dq_raw, w["Wq"], dxn, M=M, N=D, K=H * DIM_HEAD, b_kmajor=True)
+        ops.gemm(dkv_raw, w["Wkv"], tmp, M=M, N=D, K=2 * DIM_HEAD, b_kmajor=True, Cin=None if kv16 else dx1)
         gWq = grad_of(attn.to_q.weight)
         wgrad(dq_raw, sv.xn, gWq, H * DIM_HEAD, D)
         gWkv = grad_of(attn.to_kv.weight)
@@ -832,13 +738,10 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
         ops.layernorm_bwd(dxn, sv.x, attn.norm.gamma.detach(), sv.m1, sv.r1, dx1 if kv16 else tmp, dres,
                           None if (T == torch.float32 or last) else dres_c, grad_of(attn.norm.gamma),
                           dx_scale=out_scale if last else 1.0, dres2=tmp if kv16 else None, defer=cg)
-    if cg is not None:
-        cg.flush()
+    cg.flush()
     if wg is not None:
         wg.flush()
-    if rp_side is not None:
-        torch.cuda.current_stream(dev).wait_stream(rp_side)
-    elif dtable is not None and saved["rp"] is not None and not rp_cached:      # (cached: RelposStepCache.flush runs it once per optimizer step)
+    if dtable is not None and saved["rp"] is not None and not rp_cached:      # (cached: RelposStepCache.flush runs it once per optimizer step)
         relpos_backward(tr, N, saved["rp"], dtable)
     return dres
 
@@ -949,11 +852,8 @@ def heads_backward(model, pw: PreparedWeights, y: torch.Tensor, lay: SeqLayout, 
                 continue
             a_map, c_map, rows = ent
             # dy[rows] = dlogits[rows] @ W_q          (each hidden row belongs to exactly one head)
-            if pw.headsT:
-                ops.gemm(dl, pw.headsT[s][qq], dy, M=rows, N=D, K=ldV, a_map=c_map, c_map=a_map, a_rows=dl.shape[0])
-            else:
-                ops.gemm(dl, pw.heads[s][qq], dy, M=rows, N=D, K=ldV, b_kmajor=True, a_map=c_map, c_map=a_map,
-                         a_rows=dl.shape[0], b_rows=V1)
+            ops.gemm(dl, pw.heads[s][qq], dy, M=rows, N=D, K=ldV, b_kmajor=True, a_map=c_map, c_map=a_map,
+                     a_rows=dl.shape[0], b_rows=V1)
             # dW_q += dlogits[rows]^T @ y[rows]
             if deferred is not None and rows >= 1024:
                 # gathered into contiguous rows, zero-padded to whole 64-row k-tiles (the grouped launch then keeps its SGPR-offset DMA form)
@@ -993,8 +893,8 @@ def run_forward(model, all_token_ids, self_attn_mask, only_final: bool, save: bo
     lay = get_layout(model, B, lens, ids32.device, final_rows_only)
     # k-contiguous W^T copies for the input-gradient GEMMs were worth 795 vs 644 TFLOP/s while the k-major GEMM path stalled on
     # its own DMA (gemm.hip: dma_issue); with that fixed, dX = dY W reads W k-major at the same rate (795 vs 778 TFLOP/s on the FF
-    # shape) and the per-step transposes (183 MB written, 52 launches) are skipped.  OMLM_WT=1 brings them back (A/B).
-    pw = prepared_weights(model, precision) if not save else PreparedWeights(model, precision, with_transposes=_WT)
+    # shape) and the per-step transposes (183 MB written, 52 launches) are skipped.
+    pw = prepared_weights(model, precision) if not save else PreparedWeights(model, precision)
     keymask = None
     if self_attn_mask is not None:
         assert self_attn_mask.shape == (B, N), f"self_attn_mask must be [{B}, {N}]"
@@ -1016,7 +916,7 @@ def run_forward(model, all_token_ids, self_attn_mask, only_final: bool, save: bo
 
 def run_backward(st: ForwardState, dlogits: Sequence[Optional[torch.Tensor]]):
     model = st.model
-    deferred = [] if (st.pw.T in _H16 and _WGRAD_GROUP) else None
+    deferred = [] if st.pw.T in _H16 else None
     dy = heads_backward(model, st.pw, st.y, st.lay, dlogits, deferred)
     alpha = float(model.transformer.grad_shrink_alpha)
     dx = trunk_backward(model.transformer, st.pw, st.trunk, dy, st.B, st.N, out_scale=alpha, head_wgrads=deferred)

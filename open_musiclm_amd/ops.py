@@ -246,12 +246,6 @@ class CastPadGroup:
         n = len(self.items)
         if n == 0:
             return
-        if os.environ.get("OMLM_PACK_GROUP", "1") == "0":            # A/B lever: one launch per re-pack
-            assert not any(it[7] for it in self.items), "lo planes exist in the grouped launch only"
-            for src, dst, R, C_, ld_src, ld_dst, tr, _ in self.items:
-                (transpose_cast if tr else cast_pad)(src, dst, R, C_, ld_src, ld_dst)
-            self.items = []
-            return
         arr = (_CastDesc * n)()
         for d, (src, dst, R, C_, ld_src, ld_dst, tr, lo) in zip(arr, self.items):
             d.src, d.dst, d.R, d.C, d.ld_src, d.ld_dst, d.transpose, d.lo = ptr(src), ptr(dst), R, C_, ld_src, ld_dst, tr, lo

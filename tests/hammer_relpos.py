@@ -5,7 +5,7 @@ rel-pos-bias MLP, `transformer.py:36-67`, seen only inside long pytest processes
 
 One process, full-size coarse-small step (B = 2, N = 1116, the shapes of test_full_size_coarse_small_vs_oracle) repeated `iters` times,
 cycling bf16 / fp16 / bf16x3, with the caching allocator POISONED between iterations: blocks of many sizes are allocated on the
-trunk's stream and on the engine's side stream, filled with NaN (or a large finite value) and freed, so that every torch.empty() of
+trunk's stream, filled with NaN (or a large finite value) and freed, so that every torch.empty() of
 the step hands out garbage instead of the zeros a fresh hipMalloc returns.  Every iteration compares all eight `rel_pos_bias.*`
 gradients (and a few trunk gradients) with the CPU oracle; phases:
 
@@ -15,7 +15,7 @@ gradients (and a few trunk gradients) with the CPU oracle; phases:
        run to run
     C  HIP-graph replays of the step into a FusedAdam flat gradient buffer (the trainer's flow)
 
-Levers for bisecting (environment, read by the library / engine): OMLM_RELPOS_ASYNC=0, OMLM_X3_PLANES=0, OMLM_GEMM_SPLITS=1.
+Lever for bisecting (environment, read by the engine): OMLM_X3_PLANES=0.
 Test infrastructure: it imports the oracle; nothing in the product imports this file.
 """
 import argparse
@@ -186,8 +186,7 @@ def main():
     dev = torch.device("cuda:0")
     rng = random.Random(args.seed)
     ids, noise, o_loss, ogr = oracle_reference()
-    side = engine.side_stream(dev)
-    streams = [torch.cuda.current_stream(dev), side]
+    streams = [torch.cuda.current_stream(dev)]
     precisions = ["bf16", "fp16", "bf16x3"]
     models = {p: build(p, dev) for p in precisions}
     res = dict(env={k: v for k, v in os.environ.items() if k.startswith("OMLM_")}, iters=args.iters, failures=[], phases={})

@@ -8,8 +8,8 @@ Before the fix nothing ordered those zero-fills before the epilogue's LDS writes
 traffic on the same CU) they wiped staged output values.  Non-split GEMMs are deterministic, so ANY bit that differs from the result of
 the same launch on an otherwise idle GPU is corruption.  This script runs the rel-pos MLP's GEMM shapes (fp32 operands through the hi/lo
 plane route, 128x128 tiles) and two 16-bit trunk shapes on a second stream while the first stream runs HBM-bound copies, and counts
-differing elements.  `.variants/libomlm_notailwait.so` (tools/ab_variant.sh notailwait gemm -DOMLM_GEMM_TAIL_WAIT=0) is the library
-without the fix.  Test infrastructure only.
+differing elements.  A library without the fix (the `s_waitcnt vmcnt(0)` in front of gemm_tile_body's epilogue) failed ~45 % of these
+launches: profiles/r04_stress_gemm_tail_unfixed.json.  Test infrastructure only.
 """
 import argparse
 import json

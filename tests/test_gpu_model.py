@@ -603,8 +603,8 @@ def test_full_size_backward_is_reproducible(dev, precision, bar):
 
 def test_gemm_epilogue_survives_concurrent_streams(dev):
     """The GEMM tail race of round 3: non-split GEMMs launched on a second stream next to HBM-bound copies must
-    return bit for bit what the same launch returns on an idle GPU (tests/stress_gemm_tail.py; the library built with
-    -DOMLM_GEMM_TAIL_WAIT=0 fails ~45 % of these launches, profiles/r04_stress_gemm_tail_unfixed.json)."""
+    return bit for bit what the same launch returns on an idle GPU (tests/stress_gemm_tail.py; a library without the tail wait in front of
+    gemm_tile_body's epilogue failed ~45 % of these launches, profiles/r04_stress_gemm_tail_unfixed.json)."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("stress_gemm_tail", os.path.join(ROOT, "tests", "stress_gemm_tail.py"))
     mod = importlib.util.module_from_spec(spec)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds the library with extra compile flags for the named source files into .variants/ (travels with gpurun), for an A/B through
 # tools/lib_ab or OMLM_LIB_PATH:
-#   tools/ab_variant.sh NAME "attention attention2" -DOMLM_DIAG_HORNER=1     -> .variants/libomlm_NAME.so
+#   tools/ab_variant.sh NAME "attention attention2" -DEXPERIMENT=1          -> .variants/libomlm_NAME.so
 # Every other object is taken from the in-tree build (made up to date first).
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -14,6 +14,6 @@ for grp in \
   "FETCH_SIZE" "WRITE_SIZE SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE" \
   "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES"; do
   i=$((i+1))
-  ( cd $R && REPS=3 PITCH_AB=0 ABLATE=0 TILES=${TILES:-256x256} timeout 200 rocprofv3 --pmc $grp -d $OUT/g$i -o p --output-format csv -- python tools/gemm_probe.py > $OUT/g$i.log 2>&1 )
+  ( cd $R && REPS=3 PITCH_AB=0 TILES=${TILES:-256x256} timeout 200 rocprofv3 --pmc $grp -d $OUT/g$i -o p --output-format csv -- python tools/gemm_probe.py > $OUT/g$i.log 2>&1 )
 done
 cd $R && python tools/prof_summary.py pmc $OUT $OUT/summary.md && cat $OUT/summary.md
