@@ -132,6 +132,41 @@ int omlm_mqa_attn_bwd(const void* q, const void* k, const void* v, const float* 
                       float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
                       int B, int N, int H, float scale, int bias_ld, int dtype, void* stream);
 
+/* Attention dropout (transformer.py:198,211: nn.Dropout(attn_dropout) on the softmax probabilities before P V).
+ * out = (P o Z / (1 - p)) V with Z the keep-mask below; lse stays that of the undropped P (bit-identical to p = 0), and the backward
+ * regenerates Z: dV = (P o Z / (1 - p))^T dO, dS = P o (Z o dP~ / (1 - p) - delta), delta = rowsum(dO o O) as before.  Arguments as
+ * omlm_mqa_attn_fwd / _bwd plus p in [0, 1) (round(p * 65536) < 65536), seed and the optional per-forward salt seed_dev (one uint64 in
+ * device memory, read by the kernels: a captured graph draws new masks when the salt is bumped).  p == 0 is exactly the plain entry.
+ *
+ * Keep-mask of probability (b, h, i, j) -- sample b, head h, query i, key j (i < 2^17, j < 2^16):
+ *   hash(x)  = lowbias32: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (uint32 arithmetic)
+ *   s        = seed + (seed_dev ? *seed_dev * 0x9E3779B97F4A7C15 : 0)                                (uint64, wrapping)
+ *   headkey  = hash(hash(hash(lo32(s) ^ b) ^ hi32(s)) + h)
+ *   w        = hash(headkey ^ (i << 15) ^ (j >> 1))
+ *   draw     = (j & 1) ? w >> 16 : w & 0xFFFF
+ *   Z        = draw >= round(p * 65536)                                                            (the FF dropout's rule)
+ * It depends on nothing else (not on N, the tile shapes, the dtype or the kernel).  Keys j, j + 1 share one hash (16 bits each), and
+ * headkey ^ (i << 15) is a per-(b, h, i) key hoisted out of the kernels' key loops. */
+int omlm_mqa_attn_fwd_dropout(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
+                              const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale, int bias_ld,
+                              int dtype, float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream);
+int omlm_mqa_attn_bwd_dropout(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
+                              const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
+                              float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
+                              int B, int N, int H, float scale, int bias_ld, int dtype, float p, unsigned long long seed,
+                              const unsigned long long* seed_dev, void* stream);
+/* keep [B, H, N, N] uint8 (1 = kept): the mask above, as the attention kernels apply it (a test / integration hook for small shapes). */
+int omlm_attn_dropout_keep(unsigned char* keep, int B, int N, int H, float p, unsigned long long seed,
+                           const unsigned long long* seed_dev, void* stream);
+/* Dropout of to_out (transformer.py:211,333: Sequential(Linear, Dropout)) with the residual add: x1 = x + Z' o y / (1 - p), x, y, x1 [M, D]
+ * fp32 (D even).  Z' of element (row, c): w = hash(hash(hash(lo32(s) ^ row) ^ hi32(s)) ^ (c >> 1)), draw and rule as above, s = seed +
+ * *seed_dev * 0x9E3779B97F4A7C15 -- seed is the layer's own, so Z' and the attention mask are independent.
+ * bwd: dy = Z' o dx1 / (1 - p) in out_dtype (0 fp32, 1 bf16, 2 fp16), dx1 [M, D] fp32. */
+int omlm_dropout_residual_fwd(const float* x, const float* y, float* x1, long long M, int D, float p, unsigned long long seed,
+                              const unsigned long long* seed_dev, void* stream);
+int omlm_dropout_residual_bwd(const float* dx1, void* dy, long long M, int D, float p, unsigned long long seed,
+                              const unsigned long long* seed_dev, int out_dtype, void* stream);
+
 /* Middle of ConvFeedForward: CausalDSConv -> GEGLU -> LayerNorm(F) -> Dropout (transformer.py:122-148).
  * h1: [M, 2*Fp] (value half cols [0,F), gate half cols [Fp, Fp+F)); h2: [M, Fp]; convw: taps re-packed tap-major and
  * padded, [3, 2*Fp] in h1's column layout (from the reference ds_conv.weight [2F,1,3]); gamma padded to [Fp] with zeros; both in

@@ -171,11 +171,12 @@ __device__ __forceinline__ void pack_acc(const f32x16& p, int s, h16x8& hi, h16x
 #define AT_DQ_WPE 2        /* waves per SIMD the backward kernels are compiled for (2 = 256 registers) */
 #define AT_DQP_WPE 2
 #define AT_DKV_WPE 2
-template <typename T>
+template <typename T, bool DROP = false>
 __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2))) void attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                               const T* __restrict__ v, const float* __restrict__ bias,
                                                               const unsigned char* __restrict__ keymask, T* __restrict__ out,
-                                                              float* __restrict__ lse, int B, int N, int H, float scale, int bias_ld) {
+                                                              float* __restrict__ lse, int B, int N, int H, float scale, int bias_ld,
+                                                              const AttnDrop drop) {
     constexpr bool PRECISE = elt_traits<T>::precise;
     constexpr int PLANE = TKV * 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -212,6 +213,8 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
     float m = NEG_BIG, lsum = 0.f;
     const float c = scale * LOG2E;
     const float* bl = bias_l + (size_t)wave * nb;
+    // DROP: row key of (b, h, qi) with this half-wave's key bit 4 hi / 2 (common.h); the pair (r, r + 1), r even, is keys j, j + 1
+    const unsigned rk = DROP ? attn_drop_headkey(attn_drop_seed(drop), b, active ? h : 0) ^ ((unsigned)qi << 15) ^ (2u * (unsigned)hi) : 0u;
 
     const int nkt = (i0 + TQ + TKV - 1) / TKV;
     KVRegs<T, PRECISE> kr, vr;
@@ -280,6 +283,15 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
 #pragma unroll
             for (int r = 0; r < 16; ++r) { st[r] = __builtin_amdgcn_exp2f(st[r] - mnew); psum += st[r]; }
             lsum = lsum * alpha + psum;
+            if (DROP) {                        // the denominator took every P; the numerator takes P Z (1 / (1 - p) at the store)
+                const unsigned kb = rk ^ (unsigned)(jb >> 1);
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const unsigned w = omlm_hash32(kb ^ (unsigned)(((r & 3) + 8 * (r >> 2)) >> 1));
+                    st[r] = (w << 16) >= drop.thr16 ? st[r] : 0.f;
+                    st[r + 1] = w >= drop.thr16 ? st[r + 1] : 0.f;
+                }
+            }
             if (!__all(alpha == 1.0f)) {
 #pragma unroll
                 for (int e = 0; e < 16; ++e) { acc[0][e] *= alpha; acc[1][e] *= alpha; }
@@ -303,7 +315,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
     }
     if (!active || qi >= N) return;
     lsum += __shfl_xor(lsum, 32, 64);
-    const float inv = 1.0f / lsum;
+    const float inv = (DROP ? drop.rs : 1.0f) / lsum;
     T* orow = out + (rowbase + qi) * (size_t)(H * 64) + h * 64;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
@@ -312,20 +324,21 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
             const int d = 32 * dt + 8 * g4 + 4 * hi;
             store4_from_float(orow + d, acc[dt][4 * g4] * inv, acc[dt][4 * g4 + 1] * inv, acc[dt][4 * g4 + 2] * inv, acc[dt][4 * g4 + 3] * inv);
         }
-    if (hi == 0 && lse) lse[((size_t)b * H + h) * N + qi] = m + log2f(lsum);   // log2 domain
+    if (hi == 0 && lse) lse[((size_t)b * H + h) * N + qi] = m + log2f(lsum);   // log2 domain (DROP: the same value)
 }
 
 // =============================================================================================================
 // backward, kernel B: dQ, d(bias table), delta_i = sum_d dO[i,d] O[i,d]     (same geometry as the forward)
 // =============================================================================================================
-template <typename T>
+template <typename T, bool DROP = false>
 __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_DQ_WPE))) void attn_bwd_dq_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                                  const T* __restrict__ v, const float* __restrict__ bias,
                                                                  const unsigned char* __restrict__ keymask,
                                                                  const T* __restrict__ out, const T* __restrict__ dout,
                                                                  const float* __restrict__ lse, float* __restrict__ delta,
                                                                  float* __restrict__ dq, float* __restrict__ dbias,
-                                                                 int B, int N, int H, float scale, int bias_ld, float* __restrict__ dpart) {
+                                                                 int B, int N, int H, float scale, int bias_ld, float* __restrict__ dpart,
+                                                                 const AttnDrop drop) {
     constexpr int PLANE = TKV * 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;                       // K rows  (S^T = K Q^T)
@@ -374,6 +387,8 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 #pragma unroll
     for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
     const float c = scale * LOG2E;
+    // DROP: row key of (b, h, qi) with this half-wave's key bit (see the forward)
+    const unsigned rk = DROP ? attn_drop_headkey(attn_drop_seed(drop), b, active ? h : 0) ^ ((unsigned)qi << 15) ^ (2u * (unsigned)hi) : 0u;
 
     const int nkt = (i0 + TQ + TKV - 1) / TKV;
     KVRegs<T, false> kr, vr;
@@ -415,6 +430,15 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                     if ((s & 1) == 0) asm volatile("" : "+v"(kfr[s]), "+v"(vfr[s]), "+v"(kfr[s + 1]), "+v"(vfr[s + 1]));
                     st = MFMA(kfr[s], qf[s], st);                                // S^T  = K Q^T
                     dp = MFMA(vfr[s], dof[s], dp);                               // dP^T = V dO^T
+                }
+            }
+            if (DROP) {                        // dP~ -> Z dP~ / (1 - p): then dS = P (Z dP~ / (1 - p) - delta) below
+                const unsigned kb = rk ^ (unsigned)(jb >> 1);
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const unsigned w = omlm_hash32(kb ^ (unsigned)(((r & 3) + 8 * (r >> 2)) >> 1));
+                    dp[r] = (w << 16) >= drop.thr16 ? dp[r] * drop.rs : 0.f;
+                    dp[r + 1] = w >= drop.thr16 ? dp[r + 1] * drop.rs : 0.f;
                 }
             }
             // three straight passes (gather bias, arithmetic, scatter d(bias)): a fused per-element loop compiled to 16
@@ -500,14 +524,15 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 
 // The same kernel for fp32 ("bf16x3") operands with hi/lo S and dP, kept as its own function so that the bf16 kernel's code and
 // register allocation (already at the 256-register limit) stay exactly as measured.
-template <typename T>
+template <typename T, bool DROP = false>
 __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_DQP_WPE))) void attn_bwd_dq_precise_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                                  const T* __restrict__ v, const float* __restrict__ bias,
                                                                  const unsigned char* __restrict__ keymask,
                                                                  const T* __restrict__ out, const T* __restrict__ dout,
                                                                  const float* __restrict__ lse, float* __restrict__ delta,
                                                                  float* __restrict__ dq, float* __restrict__ dbias,
-                                                                 int B, int N, int H, float scale, int bias_ld, float* __restrict__ dpart) {
+                                                                 int B, int N, int H, float scale, int bias_ld, float* __restrict__ dpart,
+                                                                 const AttnDrop drop) {
     // fp32 operands ("bf16x3"): S and dP -- the two products the probabilities and d(bias) are made of -- are formed from
     // hi/lo splits (3 MFMAs per product), so p, dS and the rel-pos bias gradient are fp32-grade; dQ = dS K itself stays a
     // single bf16 pass (dS rounded once), like every other gradient GEMM operand of this mode's backward.
@@ -563,6 +588,8 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 #pragma unroll
     for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
     const float c = scale * LOG2E;
+    // DROP: row key of (b, h, qi) with this half-wave's key bit (see the forward)
+    const unsigned rk = DROP ? attn_drop_headkey(attn_drop_seed(drop), b, active ? h : 0) ^ ((unsigned)qi << 15) ^ (2u * (unsigned)hi) : 0u;
 
     const int nkt = (i0 + TQ + TKV - 1) / TKV;
     KVRegs<T, PRECISE> kr, vr;
@@ -607,6 +634,15 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                 } else {
                     st = MFMA(frag_rows(Ks, 32 * sub, s, lane), qf[s], st);      // S^T  = K Q^T
                     dp = MFMA(frag_rows(Vs, 32 * sub, s, lane), dof[s], dp);     // dP^T = V dO^T
+                }
+            }
+            if (DROP) {                        // dP~ -> Z dP~ / (1 - p): then dS = P (Z dP~ / (1 - p) - delta) below
+                const unsigned kb = rk ^ (unsigned)(jb >> 1);
+#pragma unroll
+                for (int r = 0; r < 16; r += 2) {
+                    const unsigned w = omlm_hash32(kb ^ (unsigned)(((r & 3) + 8 * (r >> 2)) >> 1));
+                    dp[r] = (w << 16) >= drop.thr16 ? dp[r] * drop.rs : 0.f;
+                    dp[r + 1] = w >= drop.thr16 ? dp[r + 1] * drop.rs : 0.f;
                 }
             }
             // three straight passes (gather bias, arithmetic, scatter d(bias)): a fused per-element loop compiled to 16
@@ -687,14 +723,14 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 // backward, kernel A: dK, dV.  One workgroup per (sample, 32-key tile); its 4 waves split the (query tile, head)
 // work items and reduce their partial dK^T / dV^T through LDS at the end -- no atomics on dK / dV.
 // =============================================================================================================
-template <typename T>
+template <typename T, bool DROP = false>
 __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_DKV_WPE))) void attn_bwd_dkv_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                                   const T* __restrict__ v, const float* __restrict__ bias,
                                                                   const unsigned char* __restrict__ keymask,
                                                                   const T* __restrict__ dout, const float* __restrict__ lse,
                                                                   const float* __restrict__ delta, float* __restrict__ dk,
                                                                   float* __restrict__ dv, int B, int N, int H, float scale, int bias_ld,
-                                                                  const float* __restrict__ biasT, int ldT) {
+                                                                  const float* __restrict__ biasT, int ldT, const AttnDrop drop) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hi = lane >> 5;
     char* Qs = smem + wave * 8192;            // per-wave private [32][64] bf16 tiles (Q, dO) for the transpose reads
@@ -732,6 +768,9 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
         load_row8<T, false>(v + (rowbase + min(kj, N - 1)) * 64 + 16 * s + 8 * hi, kj < N, vf[s], dummy);
     }
     const bool keylive = kj < N && (keymask ? keymask[rowbase + kj] != 0 : true);
+    // DROP: the draw of (i, kj) is the (kj & 1) half of omlm_hash32(row key ^ (kj >> 1)), the upper half of (word << dsh) (common.h)
+    const unsigned long long dseed = DROP ? attn_drop_seed(drop) : 0ull;
+    const unsigned dsh = (kj & 1) ? 0u : 16u;
 
     f32x16 dkacc[2], dvacc[2];
 #pragma unroll
@@ -786,13 +825,23 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
         if (WIN) ld_l[64 + lane] = Ba;
         // window index of (query row crow(r, hi), this lane's key): cr + 4 hi - (lane & 31) + 31
         const float* bwp = ld_l + 64 + 31 + 4 * hi - (lane & 31);
-        f32x16 st, dp;
+        f32x16 st, dp, zz;
 #pragma unroll
         for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             st = MFMA(qa[s], kf[s], st);       // S  = Q K^T   (rows i, column = this lane's key)
             dp = MFMA(doa[s], vf[s], dp);      // dP = dO V^T
+        }
+        if (DROP) {                            // dP~ -> Z dP~ / (1 - p) (dS below), zz = Z / (1 - p) for dV's P Z / (1 - p)
+            const unsigned lk = attn_drop_headkey(dseed, b, h) ^ ((unsigned)kj >> 1) ^ ((unsigned)(i0 + 4 * hi) << 15);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const unsigned w = omlm_hash32(lk ^ ((unsigned)((r & 3) + 8 * (r >> 2)) << 15));
+                const float z = (w << dsh) >= drop.thr16 ? drop.rs : 0.f;
+                dp[r] *= z;
+                zz[r] = z;
+            }
         }
         f32x16 pp;
         const float* lp = ld_l + 4 * hi;
@@ -815,7 +864,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                 const int cr = (r & 3) + 8 * (r >> 2);
                 const float x = st[r] * c + bvv[r] - lvv[r];
                 const float p = __builtin_amdgcn_exp2f(keylive ? x : NEG_BIG);
-                pp[r] = p;
+                pp[r] = DROP ? p * zz[r] : p;
                 st[r] = p * (dp[r] - lp[32 + cr]) * scale;
             }
         } else {
@@ -839,7 +888,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                 const bool ok = (i >= kj) && keylive && (i < N);
                 const float x = st[r] * c + bvv[r] - lvv[r];
                 const float p = __builtin_amdgcn_exp2f(ok ? x : NEG_BIG);
-                pp[r] = p;
+                pp[r] = DROP ? p * zz[r] : p;
                 st[r] = p * (dp[r] - lp[32 + cr]) * scale;
             }
         }
@@ -890,7 +939,40 @@ static int set_lds(K kernel, size_t bytes) {
 }
 
 int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
-                     void* out, float* lse, int B, int N, int H, float scale, hipStream_t st);        // attention2.hip
+                     void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop);   // attention2.hip
+
+// the forward of omlm_mqa_attn_fwd (drop == NULL) and omlm_mqa_attn_fwd_dropout (drop: p > 0)
+static int attn_fwd_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
+                         const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale,
+                         int bias_ld, int dtype, void* stream, const AttnDrop* drop) {
+    if (B <= 0 || N <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
+    OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
+    if (dtype == 1 && (biasT || !bias))
+        return attn2_fwd_launch(q, k, v, biasT, keymask, out, lse, B, N, H, scale, as_stream(stream), drop);
+    dim3 grid((N + TQ - 1) / TQ, (H + 3) / 4, B), block(AT_THREADS);
+    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
+    const AttnDrop& dr = drop ? *drop : nd;
+    int rc;
+    if (dtype == 0) {
+#if OMLM_FP16
+        omlm_set_error("omlm_mqa_attn_fwd: fp32 operands are served by the bf16 copy of the library");
+        return OMLM_ERR_UNSUPPORTED;
+#else
+        const size_t lds = fwd_lds(N, true);
+        auto kern = drop ? attn_fwd_kernel<float, true> : attn_fwd_kernel<float, false>;
+        if ((rc = set_lds(kern, lds))) return rc;
+        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const float*)q, (const float*)k, (const float*)v, bias, keymask, (float*)out, lse, B, N, H, scale, bias_ld, dr);
+#endif
+    } else {
+        const size_t lds = fwd_lds(N, false);
+        auto kern = drop ? attn_fwd_kernel<h16_t, true> : attn_fwd_kernel<h16_t, false>;
+        if ((rc = set_lds(kern, lds))) return rc;
+        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (h16_t*)out, lse, B, N, H, scale, bias_ld, dr);
+    }
+    return omlm_post_launch("omlm_mqa_attn_fwd");
+}
+
 
 // q [B*N, H*64], k, v [B*N, 64] (dtype), bias [N, bias_ld] fp32 (row = i - j, column = head) or null, keymask [B, N] uint8 or null (1 = attend)
 // biasT: the table prepared by omlm_attn_bias_prepare (bf16 operands take the attention2.hip kernel, which reads it; may be null
@@ -907,53 +989,48 @@ extern "C" int OMLM_API(omlm_mqa_attn_fwd)(const void* q, const void* k, const v
 #if !OMLM_FP16
     if (dtype == OMLM_DT_F16) return omlm_mqa_attn_fwd_h(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, 1, stream);
 #endif
-    if (B <= 0 || N <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
-    OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
-    if (dtype == 1 && (biasT || !bias))
-        return attn2_fwd_launch(q, k, v, biasT, keymask, out, lse, B, N, H, scale, as_stream(stream));
-    dim3 grid((N + TQ - 1) / TQ, (H + 3) / 4, B), block(AT_THREADS);
-    int rc;
-    if (dtype == 0) {
-#if OMLM_FP16
-        omlm_set_error("omlm_mqa_attn_fwd: fp32 operands are served by the bf16 copy of the library");
-        return OMLM_ERR_UNSUPPORTED;
-#else
-        const size_t lds = fwd_lds(N, true);
-        if ((rc = set_lds(attn_fwd_kernel<float>, lds))) return rc;
-        hipLaunchKernelGGL(attn_fwd_kernel<float>, grid, block, lds, as_stream(stream), (const float*)q, (const float*)k, (const float*)v, bias, keymask, (float*)out, lse, B, N, H, scale, bias_ld);
+    return attn_fwd_impl(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, dtype, stream, nullptr);
+}
+
+// attention dropout (include/omlm.h): p == 0 is omlm_mqa_attn_fwd itself
+#if !OMLM_FP16
+extern "C" int omlm_mqa_attn_fwd_dropout_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
+                                           const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale,
+                                           int bias_ld, int dtype, float p, unsigned long long seed, const unsigned long long* seed_dev,
+                                           void* stream);
 #endif
-    } else {
-        const size_t lds = fwd_lds(N, false);
-        if ((rc = set_lds(attn_fwd_kernel<h16_t>, lds))) return rc;
-        hipLaunchKernelGGL(attn_fwd_kernel<h16_t>, grid, block, lds, as_stream(stream), (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (h16_t*)out, lse, B, N, H, scale, bias_ld);
-    }
-    return omlm_post_launch("omlm_mqa_attn_fwd");
+extern "C" int OMLM_API(omlm_mqa_attn_fwd_dropout)(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
+                                                   const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale,
+                                                   int bias_ld, int dtype, float p, unsigned long long seed,
+                                                   const unsigned long long* seed_dev, void* stream) {
+#if !OMLM_FP16
+    if (dtype == OMLM_DT_F16)
+        return omlm_mqa_attn_fwd_dropout_h(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, 1, p, seed, seed_dev, stream);
+#endif
+    AttnDrop d;
+    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
+    return attn_fwd_impl(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, dtype, stream, p > 0.f ? &d : nullptr);
 }
 
 // dq [B*N, H*64] fp32, dk, dv [B*N, 64] fp32 (overwritten), dbias [N, bias_ld] fp32 (accumulated, +=), delta [B, H, N] scratch
 int attn2_bwd_dq_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                         const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dbias, int bias_ld,
-                        float* dpart, int B, int N, int H, float scale, hipStream_t st);               // attention2.hip
+                        float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop);   // attention2.hip
 extern "C" __attribute__((visibility("hidden"))) int omlm_attn_dbias_reduce_launch(const float* dpart, float* dbias, int bias_ld, int B, int N, int H, void* stream);   // attention2.hip (bf16 copy)
 
 int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                          const void* dout, const float* lse, const float* delta, float* dk, float* dv,
-                         int B, int N, int H, float scale, hipStream_t st);                            // attention3.hip
+                         int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop);      // attention3.hip
 #if !OMLM_FP16
 extern "C" int omlm_mqa_attn_bwd_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
                                    const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
                                    float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
                                    int B, int N, int H, float scale, int bias_ld, int dtype, void* stream);
 #endif
-extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                                 const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
-                                 float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
-                                 int B, int N, int H, float scale, int bias_ld, int dtype, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16)
-        return omlm_mqa_attn_bwd_h(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, 1, stream);
-#endif
+static int attn_bwd_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
+                         const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
+                         float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
+                         int B, int N, int H, float scale, int bias_ld, int dtype, void* stream, const AttnDrop* drop) {
     if (B <= 0 || N <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(q && k && v && out && dout && lse && delta && dq && dk && dv, "null pointer");
     dim3 gridq((N + TQ - 1) / TQ, (H + 3) / 4, B), gridk((N + 31) / 32, 1, B), block(AT_THREADS);
@@ -968,44 +1045,85 @@ extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const v
     int rc;
     hipStream_t st = as_stream(stream);
     float* dpart = dbias ? dbias_ws : nullptr;      // per-(sample, head, query tile) d(bias) rows, summed by attn_dbias_reduce_launch below
+    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
+    const AttnDrop& dr = drop ? *drop : nd;
     if (dtype == 0) {
 #if OMLM_FP16
         omlm_set_error("omlm_mqa_attn_bwd: fp32 operands are served by the bf16 copy of the library");
         return OMLM_ERR_UNSUPPORTED;
 #else
-        if ((rc = set_lds(attn_bwd_dq_precise_kernel<float>, ldsq))) return rc;
-        if ((rc = set_lds(attn_bwd_dkv_kernel<float>, ldsk))) return rc;
-        hipLaunchKernelGGL(attn_bwd_dq_precise_kernel<float>, gridq, block, ldsq, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)out, (const float*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart);
+        auto kq = drop ? attn_bwd_dq_precise_kernel<float, true> : attn_bwd_dq_precise_kernel<float, false>;
+        auto kk = drop ? attn_bwd_dkv_kernel<float, true> : attn_bwd_dkv_kernel<float, false>;
+        if ((rc = set_lds(kq, ldsq))) return rc;
+        if ((rc = set_lds(kk, ldsk))) return rc;
+        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)out, (const float*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr);
         if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<float>, gridk, block, ldsk, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT);
+        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr);
 #endif
     } else {
-        if ((rc = set_lds(attn_bwd_dkv_kernel<h16_t>, ldsk))) return rc;
+        auto kk = drop ? attn_bwd_dkv_kernel<h16_t, true> : attn_bwd_dkv_kernel<h16_t, false>;
+        if ((rc = set_lds(kk, ldsk))) return rc;
         // dQ / d(bias) / delta: the attention2.hip kernel when the prepared table is there and the sample fits its LDS plan
         int r2 = 1;
         // The attention2.hip kernel (8 heads per workgroup sharing LDS-DMA-staged K / V tiles) wherever its LDS plan fits: with the Horner
         // diagonal sums and the d(bias) workspace it is the faster one at both bench shapes (B=32, N=1116, H=8: whole backward 432 against
         // 456 us; before those two changes both kernels spent ~160 us per layer in d(bias) and the first-generation kernel led 316 : 334).
         if (biasT || !bias) {
-            r2 = attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st);
+            r2 = attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, drop);
             if (r2 < 0) return r2;
         }
         if (r2 != 0) {
-        if ((rc = set_lds(attn_bwd_dq_kernel<h16_t>, ldsq))) return rc;
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<h16_t>, gridq, block, ldsq, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart);
+        auto kq = drop ? attn_bwd_dq_kernel<h16_t, true> : attn_bwd_dq_kernel<h16_t, false>;
+        if ((rc = set_lds(kq, ldsq))) return rc;
+        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr);
         }
         if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
         // dK / dV: the third-generation kernel (attention3.hip: 128 keys per workgroup, Q / dO staged once per workgroup by LDS-DMA) where the
         // prepared table is there (or there is no bias); else the second-generation kernel
         int r3 = 1;
         if (biasT || !bias) {
-            r3 = attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st);
+            r3 = attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, drop);
             if (r3 < 0) return r3;
         }
         if (r3 != 0)
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<h16_t>, gridk, block, ldsk, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT);
+        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr);
     }
     return omlm_post_launch("omlm_mqa_attn_bwd");
+}
+
+extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
+                                 const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
+                                 float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
+                                 int B, int N, int H, float scale, int bias_ld, int dtype, void* stream) {
+#if !OMLM_FP16
+    if (dtype == OMLM_DT_F16)
+        return omlm_mqa_attn_bwd_h(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, 1, stream);
+#endif
+    return attn_bwd_impl(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, dtype,
+                         stream, nullptr);
+}
+
+#if !OMLM_FP16
+extern "C" int omlm_mqa_attn_bwd_dropout_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
+                                           const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
+                                           float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
+                                           int B, int N, int H, float scale, int bias_ld, int dtype, float p, unsigned long long seed,
+                                           const unsigned long long* seed_dev, void* stream);
+#endif
+extern "C" int OMLM_API(omlm_mqa_attn_bwd_dropout)(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
+                                                   const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
+                                                   float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
+                                                   int B, int N, int H, float scale, int bias_ld, int dtype, float p, unsigned long long seed,
+                                                   const unsigned long long* seed_dev, void* stream) {
+#if !OMLM_FP16
+    if (dtype == OMLM_DT_F16)
+        return omlm_mqa_attn_bwd_dropout_h(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale,
+                                           bias_ld, 1, p, seed, seed_dev, stream);
+#endif
+    AttnDrop d;
+    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
+    return attn_bwd_impl(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, dtype,
+                         stream, p > 0.f ? &d : nullptr);
 }
 
 }   // namespace OMLM_NS

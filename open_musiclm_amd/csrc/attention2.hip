@@ -209,9 +209,11 @@ struct A4Acc {
 //   base below its lowest entry (the 64 window reads of a tile had an address add each), the live vectors from a per-head base that
 //   points at the sample's liveness array for the lanes whose accumulator rows belong to that head and at a block of zeros for the
 //   others (instead of 32 per-value selects): ~70 of ~260 VALU instructions per tile less in a loop that is VALU-issue bound.
-template <bool FIXED, bool FULL, int QSEL = -1>
+//   DROP: the numerator MFMAs take P with the dropped keys' entries zeroed (attn_drop_pair_mask on the packed pairs; rk: the two heads' row
+//   keys, see common.h), the denominator MFMA the undropped P -- the 1 / (1 - p) scale is applied with 1 / denominator at the store.
+template <bool FIXED, bool FULL, int QSEL = -1, bool DROP = false>
 __device__ __forceinline__ void a4_tile(A4Acc& A, const h16x8 (&qf)[2][4], const char* Ks, const h16_t* live0, const h16_t* live1,
-                                        float c, int i0, int j0, int wave, int lane) {
+                                        float c, int i0, int j0, int wave, int lane, const unsigned (&rk)[2], unsigned thr16) {
     const char* Vs = Ks + 8192;
     const int hi = lane >> 5, ql = lane & 31;
     // window index of (head hb, query ql, key 32 sub + 4 hi + cr): hb 128 + 64 + ql - 32 sub - 4 hi - cr, cr = crow(r, 0) <= 27
@@ -295,8 +297,16 @@ __device__ __forceinline__ void a4_tile(A4Acc& A, const h16x8 (&qf)[2][4], const
                 const u32x2 l0 = *(const u32x2*)lp, l1 = *(const u32x2*)(lp + 8);
                 u32x4 lv4;
                 lv4[0] = l0[0]; lv4[1] = l0[1]; lv4[2] = l1[0]; lv4[3] = l1[1];
-                A.acc[hb][0] = MFMA16(va0, pb[hb][s], A.acc[hb][0]);
-                A.acc[hb][1] = MFMA16(va1, pb[hb][s], A.acc[hb][1]);
+                h16x8 pn = pb[hb][s];
+                if (DROP) {                                     // pair e holds keys jb + 4 hi + 16 s + 8 (e >> 1) + 2 (e & 1) + {0, 1}
+                    u32x4 u = __builtin_bit_cast(u32x4, pn);
+                    const unsigned kb = rk[hb] ^ (unsigned)(jb >> 1);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) u[e] &= attn_drop_pair_mask(omlm_hash32(kb ^ (unsigned)(8 * s + 4 * (e >> 1) + (e & 1))), thr16);
+                    pn = __builtin_bit_cast(h16x8, u);
+                }
+                A.acc[hb][0] = MFMA16(va0, pn, A.acc[hb][0]);
+                A.acc[hb][1] = MFMA16(va1, pn, A.acc[hb][1]);
                 A.accl = MFMA16(__builtin_bit_cast(h16x8, lv4), pb[hb][s], A.accl);      // sum over live keys of P
             }
         }
@@ -344,11 +354,11 @@ struct A4Stager {
 // the fixed form 10 % slower than this split (103 vs 92 us).
 //   FIXED: both heads in one straight line.  Online (more live state: running maxima, rescale factors): the two heads one after the
 //   other (QSEL), re-reading the K / V fragments per head.
-template <bool FIXED>
+template <bool FIXED, bool DROP = false>
 __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__ k,
                                                                   const h16_t* __restrict__ v, const float* __restrict__ biasT, int ldT,
                                                                   const unsigned char* __restrict__ keymask, h16_t* __restrict__ out,
-                                                                  float* __restrict__ lse, int B, int N, int H, float scale) {
+                                                                  float* __restrict__ lse, int B, int N, int H, float scale, const AttnDrop drop) {
     // the flag of head 0: omlm_attn_bias_prepare decides once for all heads
     if ((biasT && __builtin_amdgcn_readfirstlane(__float_as_int(biasT[ldT - 2])) != 0) != FIXED) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -450,6 +460,12 @@ __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* _
             mfix[hb] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(biasT[(size_t)(h0 + hb) * ldT + (ldT - 1)])));
     }
     asm volatile("" : "+s"(mfix[0]), "+s"(mfix[1]));          // loaded (and waited for) before the tile loop
+    unsigned rk[2] = {0u, 0u};                               // DROP: row keys of (b, h0 + hb, qi), with this half-wave's key bit (4 hi) / 2
+    if (DROP) {
+        const unsigned long long sd = attn_drop_seed(drop);
+#pragma unroll
+        for (int hb = 0; hb < 2; ++hb) rk[hb] = attn_drop_headkey(sd, b, h0 + hb) ^ ((unsigned)qi << 15) ^ (2u * (unsigned)hi);
+    }
 
     for (int t = 0; t < nkt; ++t) {
         // own DMA of tile t retired (tile t+1's five may stay in flight), then everybody's; the barrier also says that all
@@ -467,16 +483,16 @@ __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* _
         const h16_t* live0 = (lane_ & 1) == 0 ? lv : (const h16_t*)zeros;
         const h16_t* live1 = (lane_ & 1) == 1 ? lv : (const h16_t*)zeros;
         if (FIXED) {
-            if (full) a4_tile<true, true>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_);
-            else      a4_tile<true, false>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_);
+            if (full) a4_tile<true, true, -1, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
+            else      a4_tile<true, false, -1, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
         } else if (full) {
-            a4_tile<false, true, 0>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_);
+            a4_tile<false, true, 0, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
             __builtin_amdgcn_sched_barrier(0);
-            a4_tile<false, true, 1>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_);
+            a4_tile<false, true, 1, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
         } else {
-            a4_tile<false, false, 0>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_);
+            a4_tile<false, false, 0, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
             __builtin_amdgcn_sched_barrier(0);
-            a4_tile<false, false, 1>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_);
+            a4_tile<false, false, 1, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
         }
     }
     if (qi >= N) return;
@@ -487,7 +503,7 @@ __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* _
         const float lsum = A.accl[hb];                  // element e = hb: row crow(hb, hi) has parity hb
         const float mref = FIXED ? mfix[hb] : A.m[hb];
         // a query without any live causal key has no defined softmax: emit zeros and an lse that zeroes its backward
-        const float inv = lsum > 0.f ? 1.0f / lsum : 0.f;
+        const float inv = lsum > 0.f ? (DROP ? drop.rs : 1.0f) / lsum : 0.f;
         h16_t* orow = out + (rowbase + qi) * (size_t)(H * 64) + (size_t)h * 64;
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
@@ -507,12 +523,14 @@ __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* _
 // bias window.  The key mask is an additive 0 / -1e30 vector in LDS (one aligned 16-byte read per 4 scores); the probabilities
 // come straight from the stored log-sum-exp (no maximum to track), so the blocks of a tile are independent.
 #define A2B_STAGE (3 * 8192 + 8 * A2_BWIN * 4)       /* 28 KiB */
+template <bool DROP = false>
 __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__ k,
                                                                   const h16_t* __restrict__ v, const float* __restrict__ biasT, int ldT,
                                                                   const unsigned char* __restrict__ keymask, const h16_t* __restrict__ out,
                                                                   const h16_t* __restrict__ dout, const float* __restrict__ lse,
                                                                   float* __restrict__ delta, float* __restrict__ dq, float* __restrict__ dbias,
-                                                                  int bias_ld, float* __restrict__ dpart, int B, int N, int H, float scale) {
+                                                                  int bias_ld, float* __restrict__ dpart, int B, int N, int H, float scale,
+                                                                  const AttnDrop drop) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ring = smem;
     char* scratch = smem + A2_NST * A2B_STAGE;
@@ -594,6 +612,8 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
 #pragma unroll
     for (int s = 0; s < 4; ++s) { asm volatile("" : "+v"(qf[s])); asm volatile("" : "+v"(dof[s])); }
     asm volatile("" : "+v"(Lp), "+v"(dl));                    // every prologue load is consumed before the tile loop
+    unsigned rk = 0u;                                         // DROP: row key of (b, h, qi) with this half-wave's key bit (see the forward)
+    if (DROP) rk = attn_drop_headkey(attn_drop_seed(drop), b, h) ^ ((unsigned)qi << 15) ^ (2u * (unsigned)hi);
 
     f32x16 acc[2];
 #pragma unroll
@@ -661,7 +681,13 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
                     const f32x2 t2 = (f32x2{bpv[r], bpv[r + 1]} + mm2[pq]) - f32x2{Lp, Lp};
                     const f32x2 x2 = __builtin_elementwise_fma(f32x2{st[r], st[r + 1]}, f32x2{c, c}, t2);
                     const f32x2 pr2 = {__builtin_amdgcn_exp2f(x2[0]), __builtin_amdgcn_exp2f(x2[1])};
-                    const f32x2 ds2 = pr2 * (f32x2{dp[r], dp[r + 1]} - f32x2{dl, dl});   // dS = P (dP - delta), 0 where masked; scale: see the dQ store
+                    f32x2 dp2 = {dp[r], dp[r + 1]};
+                    if (DROP) {                // dropout: dS = P (Z dP~ / (1 - p) - delta); keys jb + 4 hi + cr + {0, 1} share one word
+                        const unsigned w = omlm_hash32(rk ^ (unsigned)(jb >> 1) ^ (unsigned)(cr >> 1));
+                        dp2 = dp2 * f32x2{drop.rs, drop.rs};
+                        dp2 = f32x2{(w << 16) >= drop.thr16 ? dp2[0] : 0.f, w >= drop.thr16 ? dp2[1] : 0.f};
+                    }
+                    const f32x2 ds2 = pr2 * (dp2 - f32x2{dl, dl});   // dS = P (dP - delta), 0 where masked; scale: see the dQ store
                     bv[r] = ds2[0]; bv[r + 1] = ds2[1];
                     st[r] = ds2[0]; st[r + 1] = ds2[1];
                 }
@@ -715,15 +741,24 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
 
 int attn2_bwd_dq_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                         const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dbias, int bias_ld,
-                        float* dpart, int B, int N, int H, float scale, hipStream_t st) {
+                        float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop) {
     const int ldT = (A2_PAD + N + 2 * A2_BWIN + 3) / 4 * 4;
     const int nqt = (N + 31) / 32, ny = (H + 7) / 8, npad = (N + 63) / 64 * 64;
     const size_t lds = (size_t)A2_NST * A2B_STAGE + 4096 + (size_t)npad * 4 + (size_t)8 * (nqt * 32) * 4;
     if (lds > 160 * 1024 || N > 4096) return 1;                // caller falls back to the first-generation kernel
     static bool a1 = false;
-    if (!a1) { (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); a1 = true; }
-    hipLaunchKernelGGL(attn2_bwd_dq_kernel, dim3(nqt * ny * B), dim3(A2_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
-                       biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale);
+    if (!a1) {
+        (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        a1 = true;
+    }
+    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
+    if (drop)
+        hipLaunchKernelGGL(attn2_bwd_dq_kernel<true>, dim3(nqt * ny * B), dim3(A2_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
+                           biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, *drop);
+    else
+        hipLaunchKernelGGL(attn2_bwd_dq_kernel<false>, dim3(nqt * ny * B), dim3(A2_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
+                           biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, nd);
     return omlm_post_launch("omlm_mqa_attn_bwd");
 }
 
@@ -815,11 +850,86 @@ extern "C" __attribute__((visibility("hidden"))) int omlm_attn_dbias_reduce_laun
     return omlm_post_launch("omlm_mqa_attn_bwd");
 }
 
+// ---- attention dropout: the keep-mask the attention kernels apply, written out (a test / integration hook), and the to_out dropout ------
+__global__ __launch_bounds__(256) void attn_dropout_keep_kernel(unsigned char* __restrict__ keep, int B, int N, int H, const AttnDrop d) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x, n = (long long)B * H * N * N;
+    if (e >= n) return;
+    const int j = (int)(e % N), i = (int)((e / N) % N), h = (int)((e / ((long long)N * N)) % H), b = (int)(e / ((long long)N * N * H));
+    const unsigned w = omlm_hash32(attn_drop_headkey(attn_drop_seed(d), b, h) ^ ((unsigned)i << 15) ^ ((unsigned)j >> 1));
+    keep[e] = ((w << ((j & 1) ? 0 : 16)) >= d.thr16) ? 1 : 0;
+}
+extern "C" int omlm_attn_dropout_keep(unsigned char* keep, int B, int N, int H, float p, unsigned long long seed,
+                                      const unsigned long long* seed_dev, void* stream) {
+    if (B <= 0 || N <= 0 || H <= 0) return OMLM_OK;
+    AttnDrop d;
+    OMLM_CHECK_ARG(keep, "null pointer");
+    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
+    const long long n = (long long)B * H * N * N;
+    hipLaunchKernelGGL(attn_dropout_keep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), keep, B, N, H, d);
+    return omlm_post_launch("omlm_attn_dropout_keep");
+}
+
+// to_out dropout, keyed by (seed'', row, column): the draws of columns c (even) and c + 1 are the low and high halves of
+// omlm_hash32(omlm_hash32(omlm_hash32(lo32(seed'') ^ row) ^ hi32(seed'')) ^ (c >> 1)).  One thread per column pair.
+__device__ __forceinline__ unsigned resid_drop_word(unsigned long long s, long long row, int c) {
+    const unsigned rk = omlm_hash32(omlm_hash32((unsigned)s ^ (unsigned)row) ^ (unsigned)(s >> 32));
+    return omlm_hash32(rk ^ ((unsigned)c >> 1));
+}
+__global__ __launch_bounds__(256) void dropout_residual_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ x1,
+                                                                   long long M, int D, const AttnDrop d) {
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (e >= M * D) return;
+    const long long row = e / D;
+    const int c = (int)(e - row * D);
+    const unsigned w = resid_drop_word(attn_drop_seed(d), row, c);
+    const float2 xv = *(const float2*)(x + e), yv = *(const float2*)(y + e);
+    const float z0 = (w << 16) >= d.thr16 ? d.rs : 0.f, z1 = w >= d.thr16 ? d.rs : 0.f;
+    *(float2*)(x1 + e) = make_float2(xv.x + z0 * yv.x, xv.y + z1 * yv.y);
+}
+template <typename TO>
+__global__ __launch_bounds__(256) void dropout_residual_bwd_kernel(const float* __restrict__ dx1, TO* __restrict__ dy, long long M, int D,
+                                                                   const AttnDrop d) {
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * 2;
+    if (e >= M * D) return;
+    const long long row = e / D;
+    const int c = (int)(e - row * D);
+    const unsigned w = resid_drop_word(attn_drop_seed(d), row, c);
+    const float2 g = *(const float2*)(dx1 + e);
+    store_from_float(dy + e, (w << 16) >= d.thr16 ? g.x * d.rs : 0.f);
+    store_from_float(dy + e + 1, w >= d.thr16 ? g.y * d.rs : 0.f);
+}
+extern "C" int omlm_dropout_residual_fwd(const float* x, const float* y, float* x1, long long M, int D, float p, unsigned long long seed,
+                                         const unsigned long long* seed_dev, void* stream) {
+    if (M <= 0 || D <= 0) return OMLM_OK;
+    AttnDrop d;
+    OMLM_CHECK_ARG(x && y && x1, "null pointer");
+    OMLM_CHECK_ARG(D % 2 == 0, "D even");
+    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
+    const long long pairs = M * D / 2;
+    hipLaunchKernelGGL(dropout_residual_fwd_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, as_stream(stream), x, y, x1, M, D, d);
+    return omlm_post_launch("omlm_dropout_residual_fwd");
+}
+extern "C" int omlm_dropout_residual_bwd(const float* dx1, void* dy, long long M, int D, float p, unsigned long long seed,
+                                         const unsigned long long* seed_dev, int out_dtype, void* stream) {
+    if (M <= 0 || D <= 0) return OMLM_OK;
+    AttnDrop d;
+    OMLM_CHECK_ARG(dx1 && dy, "null pointer");
+    OMLM_CHECK_ARG(D % 2 == 0, "D even");
+    OMLM_CHECK_ARG(out_dtype >= 0 && out_dtype <= 2, "dtype");
+    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
+    const long long pairs = M * D / 2;
+    const dim3 grid((unsigned)((pairs + 255) / 256));
+    if (out_dtype == OMLM_DT_F32) hipLaunchKernelGGL(dropout_residual_bwd_kernel<float>, grid, dim3(256), 0, as_stream(stream), dx1, (float*)dy, M, D, d);
+    else if (out_dtype == OMLM_DT_BF16) hipLaunchKernelGGL(dropout_residual_bwd_kernel<h16_t>, grid, dim3(256), 0, as_stream(stream), dx1, (h16_t*)dy, M, D, d);
+    else hipLaunchKernelGGL(dropout_residual_bwd_kernel<f16_t>, grid, dim3(256), 0, as_stream(stream), dx1, (f16_t*)dy, M, D, d);
+    return omlm_post_launch("omlm_dropout_residual_bwd");
+}
+
 #endif
 
 // bf16 forward.  biasT from omlm_attn_bias_prepare (or null: no bias).
 int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
-                     void* out, float* lse, int B, int N, int H, float scale, hipStream_t st) {
+                     void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop) {
     const int ldT = (A2_PAD + N + 2 * A2_BWIN + 3) / 4 * 4;
     if (N > 64 * 64) { omlm_set_error("attention: N > 4096 keys per sample is not supported (liveness prologue covers 4096 keys)"); return OMLM_ERR_UNSUPPORTED; }
     const int nqt = (N + 31) / 32, ny = (H + 7) / 8;
@@ -828,13 +938,24 @@ int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* b
     if (!a4) {
         (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         a4 = true;
     }
     // both softmax forms: the one the table's flag does not name returns at its first instruction (no table: online only)
+    const dim3 grid(nqt * ny * B);
+    if (drop) {
+        if (biasT) hipLaunchKernelGGL((attn4_fwd_kernel<true, true>), grid, dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k,
+                                      (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, *drop);
+        hipLaunchKernelGGL((attn4_fwd_kernel<false, true>), grid, dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
+                           biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, *drop);
+        return omlm_post_launch("omlm_mqa_attn_fwd");
+    }
+    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
     if (biasT) hipLaunchKernelGGL(attn4_fwd_kernel<true>, dim3(nqt * ny * B), dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k,
-                                  (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale);
+                                  (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, nd);
     hipLaunchKernelGGL(attn4_fwd_kernel<false>, dim3(nqt * ny * B), dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
-                       biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale);
+                       biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, nd);
     return omlm_post_launch("omlm_mqa_attn_fwd");
 }
 

@@ -82,11 +82,13 @@ __device__ __forceinline__ void a3_dma4(const void* gsrc, unsigned lds_dst) {
 #ifndef A3_WAVES
 #define A3_WAVES 2                     /* waves per SIMD the register allocation aims at */
 #endif
+template <bool DROP = false>
 __global__ __launch_bounds__(A3_T) __attribute__((amdgpu_waves_per_eu(A3_WAVES)))
 void attn3_bwd_dkv_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__ k, const h16_t* __restrict__ v,
                           const unsigned char* __restrict__ keymask, const h16_t* __restrict__ dout,
                           const float* __restrict__ lse, const float* __restrict__ delta, float* __restrict__ dk, float* __restrict__ dv,
-                          const float* __restrict__ biasT, int ldT, int B, int N, int H, float scale, int CH, int wg_per_sample) {
+                          const float* __restrict__ biasT, int ldT, int B, int N, int H, float scale, int CH, int wg_per_sample,
+                          const AttnDrop drop) {
     extern __shared__ __attribute__((aligned(16))) char smem3[];
     const int lane = threadIdx.x & 63, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -114,6 +116,10 @@ void attn3_bwd_dkv_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__
     const size_t rowbase = (size_t)b * N;
     const float c = scale * A3_LOG2E;
     const bool has_bias = biasT != nullptr;
+    // DROP: this lane holds key kj of 16 query rows; the draw of (i, kj) is the (kj & 1) half of omlm_hash32(row key ^ (kj >> 1)), taken
+    // as the upper half of (word << dsh) (see AttnDrop); dseed: the salted seed, hashed into a head key once per item
+    const unsigned long long dseed = DROP ? attn_drop_seed(drop) : 0ull;
+    const unsigned dsh = (kj & 1) ? 0u : 16u;
 
     // K^T, V^T B-operands: lane n = key kj, dims 16 s + 8 hi .. +7 -- resident for the whole kernel
     h16x8 kf[4], vf[4];
@@ -236,13 +242,23 @@ void attn3_bwd_dkv_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__
                 bvv[rr] = (i >= kjv && i < N) ? bvv[rr] : A3_NEG;
             }
         }
+        // DROP: the lane's key part of the row keys, rows i0 + 4 hi + cr (cr = crow(rr, hi) - 4 hi: bits disjoint from i0 and 4 hi)
+        const unsigned lk = DROP ? attn_drop_headkey(dseed, b, hcur) ^ ((unsigned)kj >> 1) ^ ((unsigned)(i0 + 4 * hi) << 15) : 0u;
 #pragma unroll
         for (int rr = 0; rr < 16; rr += 2) {
             const f32x2 t2 = f32x2{bvv[rr], bvv[rr + 1]} - (f32x2{lvv[rr], lvv[rr + 1]} - f32x2{mhk, mhk});
             const f32x2 x2 = __builtin_elementwise_fma(f32x2{st[rr], st[rr + 1]}, f32x2{c, c}, t2);
             const f32x2 p2 = {__builtin_amdgcn_exp2f(x2[0]), __builtin_amdgcn_exp2f(x2[1])};
-            const f32x2 ds2 = p2 * (f32x2{dp[rr], dp[rr + 1]} - f32x2{dvv[rr], dvv[rr + 1]});
-            pr[rr] = p2[0]; pr[rr + 1] = p2[1];
+            f32x2 dp2 = {dp[rr], dp[rr + 1]}, z2 = {1.f, 1.f};
+            if (DROP) {                                       // Z / (1 - p) of (rows cr, cr + 1; key kj): dV takes P Z / (1 - p), dS = P (Z dP~ / (1 - p) - delta)
+                const int cr = (rr & 3) + 8 * (rr >> 2);
+                const unsigned w0 = omlm_hash32(lk ^ ((unsigned)cr << 15)), w1 = omlm_hash32(lk ^ ((unsigned)(cr + 1) << 15));
+                z2 = f32x2{(w0 << dsh) >= drop.thr16 ? drop.rs : 0.f, (w1 << dsh) >= drop.thr16 ? drop.rs : 0.f};
+                dp2 = dp2 * z2;
+            }
+            const f32x2 ds2 = p2 * (dp2 - f32x2{dvv[rr], dvv[rr + 1]});
+            const f32x2 pz2 = DROP ? p2 * z2 : p2;
+            pr[rr] = pz2[0]; pr[rr + 1] = pz2[1];
             st[rr] = ds2[0]; st[rr + 1] = ds2[1];
         }
 #pragma unroll
@@ -296,7 +312,7 @@ static int a3_chunk(int B, int N) {
 // is not served (caller falls back to the second-generation kernel).
 int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                          const void* dout, const float* lse, const float* delta, float* dk, float* dv,
-                         int B, int N, int H, float scale, hipStream_t st) {
+                         int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop) {
     if (N < 32 || (long long)B * N * H * 128 >= (1ll << 32)) return 1;      // (32-bit byte offsets into q / dout)
     const int ldT = ((A3_PAD + N + 2 * 128 + 3) / 4) * 4;    // layout of omlm_attn_bias_prepare (attention2.hip)
     const int CH = a3_chunk(B, N);
@@ -305,7 +321,11 @@ int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const floa
     for (int r = 0; r < nr; ++r) wps += (nqt - 4 * r + CH - 1) / CH;
     const size_t lds = (size_t)A3_NST * A3_STAGE;             // 48 KiB (the final transposes reuse it: 4 x 8448 B)
     static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr = true;
+    }
     // Zero fill by a KERNEL of this library, not hipMemsetAsync: as a memset node of a captured micro-step the fill detached everything
     // behind it from the graph's completion -- the rest of the backward (this layer's dK / dV onwards) was still running when the launch
     // had "finished" and the optimizer's kernels started (round 4: after one fp16 overflow the skipped step's gradient clear raced with
@@ -318,8 +338,13 @@ int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const floa
     };
     if (dv == dk + gfloats) fill(dk, 2 * gfloats);            // one allocation (the host's usual case): one fill launch instead of two
     else { fill(dk, gfloats); fill(dv, gfloats); }
-    hipLaunchKernelGGL(attn3_bwd_dkv_kernel, dim3(B * wps), dim3(A3_T), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask,
-                       (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps);
+    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
+    if (drop)
+        hipLaunchKernelGGL(attn3_bwd_dkv_kernel<true>, dim3(B * wps), dim3(A3_T), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask,
+                           (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps, *drop);
+    else
+        hipLaunchKernelGGL(attn3_bwd_dkv_kernel<false>, dim3(B * wps), dim3(A3_T), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask,
+                           (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps, nd);
     return omlm_post_launch("omlm_mqa_attn_bwd");
 }
 

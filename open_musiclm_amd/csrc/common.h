@@ -226,6 +226,45 @@ __device__ __forceinline__ void philox4x32(unsigned c0, unsigned c1, unsigned c2
     }
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
+// ---- attention dropout keep-mask (include/omlm.h states it in full) -----------------------------------------------------------------
+// 32-bit integer hash lowbias32 (Wellons; the FF dropout of ffmid2.hip draws from the same function).
+__device__ __forceinline__ unsigned omlm_hash32(unsigned x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+// Kernel argument of every DROP instantiation.  thr16 = round(p * 65536) << 16: a draw d (16 bits) is kept iff d >= round(p * 65536),
+// i.e. for the upper half of a word w iff w >= thr16 and for the lower half iff (w << 16) >= thr16.  rs = 1 / (1 - p).
+struct AttnDrop {
+    unsigned long long seed;
+    const unsigned long long* seed_dev;          // optional per-forward salt: seed' = seed + *seed_dev * 0x9E3779B97F4A7C15
+    unsigned thr16;
+    float rs;
+};
+// Key of (sample b, head h): everything of the mask that does not depend on (i, j).  The key of query row i is hk ^ (i << 15); the
+// draws of keys j (even) and j + 1 are the low and high halves of omlm_hash32(row key ^ (j >> 1)).  Rows i < 2^17 and keys j < 2^16 keep
+// the (i, j) pairs of one head distinct.
+__device__ __forceinline__ unsigned long long attn_drop_seed(const AttnDrop& d) {
+    return d.seed_dev ? d.seed + d.seed_dev[0] * 0x9E3779B97F4A7C15ull : d.seed;
+}
+__device__ __forceinline__ unsigned attn_drop_headkey(unsigned long long s /* attn_drop_seed */, int b, int h) {
+    unsigned x = omlm_hash32((unsigned)s ^ (unsigned)b);
+    x = omlm_hash32(x ^ (unsigned)(s >> 32));
+    return omlm_hash32(x + (unsigned)h);
+}
+// host: p in [0, 1) -> the kernels' argument; false when p is out of range (round(p * 65536) must stay below 65536)
+static inline bool attn_drop_args(float p, unsigned long long seed, const unsigned long long* seed_dev, AttnDrop& d) {
+    if (!(p >= 0.f && p < 1.f)) return false;
+    const unsigned thr = (unsigned)(p * 65536.0f + 0.5f);
+    if (thr > 65535u) return false;
+    d.seed = seed; d.seed_dev = seed_dev; d.thr16 = thr << 16; d.rs = 1.0f / (1.0f - p);
+    return true;
+}
+// packed 16-bit operand pair -> the same pair with dropped halves zeroed (w: the pair's word, low half = even key)
+__device__ __forceinline__ unsigned attn_drop_pair_mask(unsigned w, unsigned thr16) {
+    const unsigned mh = w >= thr16 ? 0xFFFF0000u : 0u;
+    return (w << 16) >= thr16 ? (mh | 0xFFFFu) : mh;
+}
+
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned long long bytes) {
     unsigned n = bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)bytes;
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)n, 0x00020000);

@@ -487,23 +487,48 @@ def relpos_backward(tr, n: int, saved, dtable: torch.Tensor):
 # ------------------------------------------------------------------------------------------------------
 class LayerSaved:
     __slots__ = ("x", "m1", "r1", "xn", "xc", "q_raw", "kv_raw", "q", "k", "v", "o", "lse", "abias",
-                 "x1", "m2", "r2", "xn2", "h1", "h2", "m3", "r3", "seed", "p", "drop_bits", "gh", "h1_lo_tail")
+                 "x1", "m2", "r2", "xn2", "h1", "h2", "m3", "r3", "seed", "p", "drop_bits", "gh", "h1_lo_tail",
+                 "pa", "sa", "po", "so")          # attention dropout: p / seed of the probabilities, p / seed of to_out
 
 
-def dropout_salt(tr, dev) -> torch.Tensor:
-    """Per-forward dropout salt living in DEVICE memory: a counter bumped by a (graph-capturable) torch op on every
-    training forward, snapshotted so that the backward of THIS forward regenerates the same masks.  Per-layer base
-    seeds are fixed host constants; kernels combine both (omlm_ffmid_*: seed + *seed_dev * phi)."""
+def _dropout_state(tr, dev):
     st = tr.__dict__.get("_omlm_dropout")
     if st is None or st["counter"].device != dev:
         # the rank is mixed in: data-parallel replicas see different samples and must not share dropout masks
         rank = int(os.environ.get("RANK", "0"))
         g = torch.Generator().manual_seed((int(torch.initial_seed()) + 0x9E3779B1 * rank) & 0x7FFFFFFF)
+        L = len(tr.layers)
         st = dict(counter=torch.zeros(1, dtype=torch.int64, device=dev),
-                  seeds=[int(v) for v in torch.randint(1, 2 ** 62, (len(tr.layers),), generator=g)])
+                  seeds=[int(v) for v in torch.randint(1, 2 ** 62, (L,), generator=g)])
+        # attention seeds come AFTER the FF seeds from the same generator: the FF seeds (and masks) do not depend on them
+        a = [int(v) for v in torch.randint(1, 2 ** 62, (2 * L,), generator=g)]
+        st["attn_seeds"], st["out_seeds"] = a[:L], a[L:]
+        st["last"] = None
         tr.__dict__["_omlm_dropout"] = st
+    return st
+
+
+def dropout_salt(tr, dev) -> torch.Tensor:
+    """Per-forward dropout salt living in DEVICE memory: a counter bumped by a (graph-capturable) torch op on every
+    training forward, snapshotted so that the backward of THIS forward regenerates the same masks.  Per-layer base
+    seeds are fixed host constants; kernels combine both (omlm_ffmid_*, omlm_mqa_attn_*_dropout: seed + *seed_dev * phi)."""
+    st = _dropout_state(tr, dev)
     st["counter"].add_(1)
-    return st["counter"].clone(), st["seeds"]
+    st["last"] = st["counter"].clone()
+    return st["last"], st["seeds"]
+
+
+def dropout_state(tr, dev=None) -> dict:
+    """The dropout keys of the trunk `tr` (a Transformer): per layer the FF seed (`ff`), the attention-probability seed (`attn`) and the
+    to_out seed (`out`), and `salt`, the device salt of the last training forward that dropped anything (an int; None before the first).
+    A layer's masks are functions of (seed, salt) alone (include/omlm.h), so these rebuild them: e.g. ops.attn_dropout_keep(B, N, H, p,
+    attn[l], salt tensor).  Reading `salt` synchronises with the device."""
+    st = tr.__dict__.get("_omlm_dropout")
+    if st is None:
+        st = _dropout_state(tr, dev if dev is not None else torch.device("cpu"))
+    last = st["last"]
+    return dict(ff=list(st["seeds"]), attn=list(st["attn_seeds"]), out=list(st["out_seeds"]),
+                salt=int(last.item()) if last is not None else None)
 
 
 def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[torch.Tensor], B: int, N: int,
@@ -528,9 +553,13 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
             rp_saved = ("cached", rc)
     saved_layers: List[LayerSaved] = []
     abiases = None
-    salt, seeds = (None, None)
-    if training and any(float(ff.dropout_p) > 0 for _, _, ff in tr.layers):
+    salt, seeds, aseeds, oseeds = (None, None, None, None)
+    # attention dropout (probabilities, to_out), read at every forward like the FF dropout: off in eval mode
+    aps = [(float(a_.attn_dropout.p), float(a_.to_out[1].p)) if training else (0.0, 0.0) for a_, _, _ in tr.layers]
+    if training and (any(float(ff.dropout_p) > 0 for _, _, ff in tr.layers) or any(pa > 0 or po > 0 for pa, po in aps)):
         salt, seeds = dropout_salt(tr, dev)
+        st_ = tr.__dict__["_omlm_dropout"]
+        aseeds, oseeds = st_["attn_seeds"], st_["out_seeds"]
     for li, ((attn, _, ff), w) in enumerate(zip(tr.layers, pw.layers)):
         sv = LayerSaved()
         F, Fp = w["F"], w["Fp"]
@@ -564,9 +593,18 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
             abiases = ops.AttnBias.group(table, N, H, dev, [a_.q_scale.detach() for a_, _, _ in tr.layers],
                                          [a_.k_scale.detach() for a_, _, _ in tr.layers], scale=ATTN_SCALE, half=T == torch.float16)
         abias = abiases[li]
-        ops.attn_fwd(q, k, v, abias, keymask, o, lse, B, N, H, ATTN_SCALE)
+        pa, po = aps[li]
+        sa = aseeds[li] if pa > 0 else 0
+        so = oseeds[li] if po > 0 else 0
+        ops.attn_fwd(q, k, v, abias, keymask, o, lse, B, N, H, ATTN_SCALE, p=pa, seed=sa, seed_dev=salt if pa > 0 else None)
         x1 = torch.empty(M, D, device=dev)
-        ops.gemm(o, w["Wo"], x1, M=M, N=D, K=H * DIM_HEAD, Cin=x)
+        if po > 0:                                                # to_out's dropout: x1 = x + keep o (o Wo^T) / (1 - p)
+            yo = torch.empty(M, D, device=dev)
+            ops.gemm(o, w["Wo"], yo, M=M, N=D, K=H * DIM_HEAD)
+            ops.dropout_residual_fwd(x, yo, x1, po, so, seed_dev=salt)
+            del yo
+        else:
+            ops.gemm(o, w["Wo"], x1, M=M, N=D, K=H * DIM_HEAD, Cin=x)
         # feed-forward
         m2 = torch.empty(M, device=dev); r2 = torch.empty(M, device=dev)
         xn2 = torch.empty(M, D, dtype=T, device=dev)
@@ -628,6 +666,7 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
             sv.x1, sv.m2, sv.r2, sv.xn2, sv.h1, sv.h2, sv.m3, sv.r3, sv.seed, sv.p = x1, m2, r2, xn2, h1, h2, m3, r3, seed, p
             sv.drop_bits = drop_bits
             sv.gh = gh
+            sv.pa, sv.sa, sv.po, sv.so = pa, sa, po, so
             saved_layers.append(sv)
         x = x2
     mf = torch.empty(M, device=dev); rf = torch.empty(M, device=dev)
@@ -706,15 +745,20 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
         ops.layernorm_bwd(dxn2, sv.x1, ff.norm_in.gamma.detach(), sv.m2, sv.r2, dres, dx1,
                           None if T == torch.float32 else dx1_c, grad_of(ff.norm_in.gamma), defer=cg)
         # ---- attention block: x1 = x + o Wo^T ----
+        dyo = dx1_c
+        if sv.po > 0:                                              # through to_out's dropout: dy = keep o dx1 / (1 - p)
+            dyo = torch.empty(M, D, dtype=T, device=dev)
+            ops.dropout_residual_bwd(dx1, dyo, sv.po, sv.so, seed_dev=saved["salt"])
         do = torch.empty(M, H * DIM_HEAD, dtype=T, device=dev)
-        ops.gemm(dx1_c, w["Wo"], do, M=M, N=H * DIM_HEAD, K=D, b_kmajor=True)
+        ops.gemm(dyo, w["Wo"], do, M=M, N=H * DIM_HEAD, K=D, b_kmajor=True)
         gWo = grad_of(attn.to_out[0].weight)
-        wgrad(dx1_c, sv.o, gWo, D, H * DIM_HEAD)
+        wgrad(dyo, sv.o, gWo, D, H * DIM_HEAD)
         dq = torch.empty(M, H * DIM_HEAD, device=dev)
         dkv = torch.empty(2, M, DIM_HEAD, device=dev)          # one allocation: the dK/dV kernel zero-fills both with one fill
         dk, dv = dkv[0], dkv[1]
         delta = torch.empty(B, H, N, device=dev)
-        ops.attn_bwd(sv.q, sv.k, sv.v, sv.abias, keymask, sv.o, do, sv.lse, delta, dq, dk, dv, dtable, B, N, H, ATTN_SCALE)
+        ops.attn_bwd(sv.q, sv.k, sv.v, sv.abias, keymask, sv.o, do, sv.lse, delta, dq, dk, dv, dtable, B, N, H, ATTN_SCALE,
+                     p=sv.pa, seed=sv.sa, seed_dev=saved["salt"] if sv.pa > 0 else None)
         dq_raw = torch.empty(M, H * DIM_HEAD, dtype=T, device=dev)
         dkv_raw = torch.empty(M, 2 * DIM_HEAD, dtype=T, device=dev)
         if T in _H16:                                                    # sv.q_raw / sv.kv_raw hold the norms [M, H] / [M]

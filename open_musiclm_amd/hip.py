@@ -51,6 +51,11 @@ SIGNATURES = {
     "omlm_mqa_attn_fwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp],
     "omlm_mqa_attn_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp],
     "omlm_mqa_attn_bwd_workspace_bytes": [i32, i32, i32],
+    "omlm_mqa_attn_fwd_dropout": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, f32, u64, vp, vp],
+    "omlm_mqa_attn_bwd_dropout": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, f32, u64, vp, vp],
+    "omlm_attn_dropout_keep": [vp, i32, i32, i32, f32, u64, vp, vp],
+    "omlm_dropout_residual_fwd": [vp, vp, vp, i64, i32, f32, u64, vp, vp],
+    "omlm_dropout_residual_bwd": [vp, vp, i64, i32, f32, u64, vp, i32, vp],
     "omlm_ffmid_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, u64, vp, vp, vp, i32, vp],
     "omlm_ffmid_bwd_workspace_bytes": [i32, i32],
     "omlm_ffmid_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, u64, vp, vp, vp, i32, vp],

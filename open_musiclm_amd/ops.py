@@ -446,22 +446,53 @@ def _attn_bias(bias, N, H, device) -> "AttnBias":
     return bias if isinstance(bias, AttnBias) else AttnBias(bias, N, H, device)
 
 
-def attn_fwd(q, k, v, bias, keymask, out, lse, B, N, H, scale):
-    """bias: an AttnBias (built once per forward by the engine), a raw [N, ld] table, or None."""
+def attn_fwd(q, k, v, bias, keymask, out, lse, B, N, H, scale, p=0.0, seed=0, seed_dev=None):
+    """bias: an AttnBias (built once per forward by the engine), a raw [N, ld] table, or None.
+    p > 0: dropout on the probabilities with the keep-mask of include/omlm.h (seed, optional device salt seed_dev: int64 [1])."""
     ab = _attn_bias(bias, N, H, q.device)
+    if p > 0:
+        call("omlm_mqa_attn_fwd_dropout", ptr(q), ptr(k), ptr(v), ptr(ab.table), ptr(ab.tableT), ptr(keymask), ptr(out), ptr(lse),
+             B, N, H, float(scale), ab.table.shape[-1] if ab.table is not None else 0, dcode(q.dtype), float(p), int(seed),
+             ptr(seed_dev), stream_ptr())
+        return
     call("omlm_mqa_attn_fwd", ptr(q), ptr(k), ptr(v), ptr(ab.table), ptr(ab.tableT), ptr(keymask), ptr(out), ptr(lse),
          B, N, H, float(scale), ab.table.shape[-1] if ab.table is not None else 0, dcode(q.dtype), stream_ptr())
 
 
-def attn_bwd(q, k, v, bias, keymask, out, dout, lse, delta, dq, dk, dv, dbias, B, N, H, scale, workspace=True):
+def attn_bwd(q, k, v, bias, keymask, out, dout, lse, delta, dq, dk, dv, dbias, B, N, H, scale, workspace=True, p=0.0, seed=0,
+             seed_dev=None):
     """bias: the AttnBias the forward used (its tableT carries the reference point lse is relative to), a raw table, or None.
-    workspace=False: d(bias) by device-scope atomics straight into the table (the C ABI's null-workspace form; slower)."""
+    workspace=False: d(bias) by device-scope atomics straight into the table (the C ABI's null-workspace form; slower).
+    p, seed, seed_dev: those of the forward (the kernels regenerate its keep-mask)."""
     ab = _attn_bias(bias, N, H, q.device)
     bias = ab.table
     ws = ab.dbias_workspace(B, N, H) if dbias is not None and workspace else None
+    if p > 0:
+        call("omlm_mqa_attn_bwd_dropout", ptr(q), ptr(k), ptr(v), ptr(bias), ptr(ab.tableT), ptr(keymask), ptr(out), ptr(dout), ptr(lse),
+             ptr(delta), ptr(dq), ptr(dk), ptr(dv), ptr(dbias), ptr(ws), B, N, H, float(scale),
+             bias.shape[-1] if bias is not None else 0, dcode(q.dtype), float(p), int(seed), ptr(seed_dev), stream_ptr())
+        return
     call("omlm_mqa_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(bias), ptr(ab.tableT), ptr(keymask), ptr(out), ptr(dout), ptr(lse),
          ptr(delta), ptr(dq), ptr(dk), ptr(dv), ptr(dbias), ptr(ws), B, N, H, float(scale),
          bias.shape[-1] if bias is not None else 0, dcode(q.dtype), stream_ptr())
+
+
+def attn_dropout_keep(B, N, H, p, seed, seed_dev=None, device=None) -> torch.Tensor:
+    """The keep-mask [B, H, N, N] uint8 the attention kernels apply (omlm_attn_dropout_keep; small shapes)."""
+    keep = torch.empty(B, H, N, N, dtype=torch.uint8, device=device if device is not None else seed_dev.device)
+    call("omlm_attn_dropout_keep", ptr(keep), B, N, H, float(p), int(seed), ptr(seed_dev), stream_ptr())
+    return keep
+
+
+def dropout_residual_fwd(x, y, x1, p, seed, seed_dev=None):
+    """x1 = x + keep o y / (1 - p) (to_out dropout), fp32 [M, D]."""
+    call("omlm_dropout_residual_fwd", ptr(x), ptr(y), ptr(x1), x.shape[0], x.shape[1], float(p), int(seed), ptr(seed_dev), stream_ptr())
+
+
+def dropout_residual_bwd(dx1, dy, p, seed, seed_dev=None):
+    """dy = keep o dx1 / (1 - p) in dy's dtype; dx1 fp32 [M, D]."""
+    call("omlm_dropout_residual_bwd", ptr(dx1), ptr(dy), dx1.shape[0], dx1.shape[1], float(p), int(seed), ptr(seed_dev), dcode(dy.dtype),
+         stream_ptr())
 
 
 def pack_conv_taps(convw: torch.Tensor, F: int, Fp: int) -> torch.Tensor:

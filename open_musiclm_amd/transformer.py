@@ -173,11 +173,13 @@ class Attention(nn.Module):
             raise ValueError("the MI355X attention kernel is specialised for dim_head=64, scale=8 (reference defaults)")
         if num_null_kv != 0 or norm_context or (dim_context is not None and dim_context != dim):
             raise NotImplementedError("cross-attention / null-kv are not on the TokenConditionedTransformer path")
-        if dropout != 0.0:
-            raise NotImplementedError("attn_dropout > 0 is not supported (every shipped config uses 0.0)")
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"attention dropout must lie in [0, 1); got {dropout}")
         self.heads, self.scale, self.causal = heads, scale, causal
         self.non_causal_prefix = non_causal_prefix
         self.dropout = dropout
+        # attn_dropout (probabilities) and to_out[1] (output projection) are read by the engine at every training forward: .p may be changed
+        # after construction.  Eval mode, generate and the cached decoder never drop.
         # accepted for config compatibility: the flash-style HIP kernel already is the memory-efficient path
         self.use_memory_efficient_attention = use_memory_efficient_attention
         inner_dim = dim_head * heads
