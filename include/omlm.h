@@ -155,6 +155,30 @@ int omlm_mqa_attn_bwd_dropout(const void* q, const void* k, const void* v, const
                               float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
                               int B, int N, int H, float scale, int bias_ld, int dtype, float p, unsigned long long seed,
                               const unsigned long long* seed_dev, void* stream);
+/* Non-causal prefix (transformer.py:315-322, non_causal_prefix_size = P >= 1): score (i, j) is live iff
+ *   j <= i   or   (i < P and j < P)
+ * and the key mask keeps j (the key mask applies inside the prefix too); P >= N: every row sees every live key.  With Pn = min(P, N), the
+ * rel-pos table bias / dbias is [N + Pn - 1, bias_ld] fp32, row = i - j + Pn - 1 (distances -(Pn - 1) .. N - 1 in ascending order: the
+ * negative distances of the scores above the diagonal inside the prefix, then the table of omlm_mqa_attn_fwd); dbias is accumulated (+=)
+ * over all its rows.  p > 0: attention dropout with the keep-mask above, for the prefix's extra scores as for the others (p = 0: none).
+ * biasT: the prepared table of omlm_attn_bias_prepare_group_prefix (omlm_attn_bias_table_floats_prefix(N, H, P) floats: the causal layout
+ * with the Pn - 1 negative distances in front; the fixed reference point covers them), or NULL.  16-bit operands with biasT (or without any
+ * bias) run the second-generation kernels while their plans fit -- N >= 32, N <= 4096 and the dQ kernel's LDS, which holds
+ * 8 (ceil32(N) + Pn - 1) d(bias) bins: about N + Pn <= 4000 -- and otherwise, like fp32 operands, the first-generation kernels on the plain
+ * table, whose bf16x3 dQ kernel caps ceil32(N) + Pn - 1 at about 3800 (an error beyond).  The forward and the backward decide alike, so a
+ * backward is always handed the lse its forward wrote.  Other arguments as omlm_mqa_attn_fwd / _bwd.  P = 0 is refused: the causal
+ * entries above serve it. */
+int omlm_mqa_attn_fwd_prefix(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                             void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
+                             unsigned long long seed, const unsigned long long* seed_dev, void* stream);
+int omlm_mqa_attn_bwd_prefix(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                             const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv, float* dbias,
+                             float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p, unsigned long long seed,
+                             const unsigned long long* seed_dev, void* stream);
+long long omlm_attn_bias_table_floats_prefix(int N, int H, int P);
+int omlm_attn_bias_prepare_group_prefix(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
+                                        const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
+                                        int p_max_log2, int P, void* stream);
 /* keep [B, H, N, N] uint8 (1 = kept): the mask above, as the attention kernels apply it (a test / integration hook for small shapes). */
 int omlm_attn_dropout_keep(unsigned char* keep, int B, int N, int H, float p, unsigned long long seed,
                            const unsigned long long* seed_dev, void* stream);
@@ -327,6 +351,9 @@ int omlm_gemm_wgrad_group(const omlm_gemm_wgrad_desc* problems, int count, int s
 /* RelativePositionBias MLP helpers (transformer.py:55-64): SiLU layers around omlm_gemm. */
 int omlm_relpos_first_fwd(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, void* stream);
 int omlm_relpos_first_bwd(const float* ds, float* dw0, int n, int Hd, void* stream);
+/* The same over the distances x0 .. x0 + n - 1 (row r is distance x0 + r; x0 = -(min(P, N) - 1) gives the non-causal prefix's table). */
+int omlm_relpos_first_fwd_from(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, int x0, void* stream);
+int omlm_relpos_first_bwd_from(const float* ds, float* dw0, int n, int Hd, int x0, void* stream);
 int omlm_bias_silu_fwd(const float* a, const float* b, float* pre, float* z, long long R, int C, void* stream);
 int omlm_silu_bwd(const float* dz, const float* pre, float* ds, long long total, void* stream);
 int omlm_bias_add(const float* a, const float* b, float* out, int R, int C, int ld, void* stream);
@@ -342,6 +369,14 @@ int omlm_relpos_mlp_fwd(const float* w0, const float* b0, const float* W1, const
 int omlm_relpos_mlp_bwd(const float* dtable, const float* W1, const float* W2, const float* W3, const float* pre0, const float* z0,
                         const float* pre1, const float* z1, const float* pre2, const float* z2, float* scratch, float* gw0, float* gb0,
                         float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, void* stream);
+/* The fused MLP over the distances x0 .. x0 + n - 1: table[r, h] = net(x0 + r)[h] (omlm_relpos_mlp_fwd / _bwd: x0 = 0). */
+int omlm_relpos_mlp_fwd_from(const float* w0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
+                             const float* W3, const float* b3, float* pre0, float* z0, float* pre1, float* z1, float* pre2, float* z2,
+                             float* table, int n, int Hd, int H, int ldb, int x0, void* stream);
+int omlm_relpos_mlp_bwd_from(const float* dtable, const float* W1, const float* W2, const float* W3, const float* pre0, const float* z0,
+                             const float* pre1, const float* z1, const float* pre2, const float* z2, float* scratch, float* gw0, float* gb0,
+                             float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, int x0,
+                             void* stream);
 
 /* Nearest-codeword kernels: ClapQuantized.quantize -> ResidualVQ eval path (clap_quantized.py:75-87) and
  * HfHubertWithKmeans assign (hf_hubert_kmeans.py:87).  codebooks_T: [nstage][D][C] (transposed); indices int32 [n, nstage].

@@ -171,12 +171,15 @@ __device__ __forceinline__ void pack_acc(const f32x16& p, int s, h16x8& hi, h16x
 #define AT_DQ_WPE 2        /* waves per SIMD the backward kernels are compiled for (2 = 256 registers) */
 #define AT_DQP_WPE 2
 #define AT_DKV_WPE 2
-template <typename T, bool DROP = false>
+// PFX: the non-causal prefix (include/omlm.h): score (i, j) is live iff j <= i or (i < P and j < P), P = Pn = min(P, N) > 0.  bias points
+// at the table's rel = 0 row; rows rel = -(Pn - 1) .. -1 precede it.  The wave's LDS bias table covers rel in [-(Pn - 1), nb) (index
+// rel + off, off = Pn - 1), and a query tile with i0 < Pn walks its keys up to max(i0 + TQ, Pn).  PFX = false is the causal kernel as it was.
+template <typename T, bool DROP = false, bool PFX = false>
 __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2))) void attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                               const T* __restrict__ v, const float* __restrict__ bias,
                                                               const unsigned char* __restrict__ keymask, T* __restrict__ out,
                                                               float* __restrict__ lse, int B, int N, int H, float scale, int bias_ld,
-                                                              const AttnDrop drop) {
+                                                              const AttnDrop drop, int Pn) {
     constexpr bool PRECISE = elt_traits<T>::precise;
     constexpr int PLANE = TKV * 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -196,10 +199,16 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
     const int qi = i0 + (lane & 31);
     const int nb = i0 + TQ;                             // bias bins needed: rel in [0, i0 + 31]
     const size_t rowbase = (size_t)b * N;
+    const int off = PFX ? Pn - 1 : 0;                   // PFX: negative-distance bins in front
+    const int kend = PFX && i0 < Pn ? max(i0 + TQ, Pn) : i0 + TQ;      // keys [0, kend) can be live for this tile
 
     if (active) {
-        float* bl = bias_l + (size_t)wave * nb;
-        for (int r = lane; r < nb; r += 64) bl[r] = bias ? bias[(size_t)min(r, N - 1) * bias_ld + h] * LOG2E : 0.f;
+        float* bl = bias_l + (size_t)wave * (nb + off);
+        if (PFX) {
+            for (int r = lane; r < nb + off; r += 64) bl[r] = bias ? bias[(ptrdiff_t)min(r - off, N - 1) * bias_ld + h] * LOG2E : 0.f;
+        } else {
+            for (int r = lane; r < nb; r += 64) bl[r] = bias ? bias[(size_t)min(r, N - 1) * bias_ld + h] * LOG2E : 0.f;
+        }
     }
     h16x8 qh[4], ql[4];
     if (active) {
@@ -212,11 +221,11 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
     for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
     float m = NEG_BIG, lsum = 0.f;
     const float c = scale * LOG2E;
-    const float* bl = bias_l + (size_t)wave * nb;
+    const float* bl = bias_l + (size_t)wave * (nb + off) + off;
     // DROP: row key of (b, h, qi) with this half-wave's key bit 4 hi / 2 (common.h); the pair (r, r + 1), r even, is keys j, j + 1
     const unsigned rk = DROP ? attn_drop_headkey(attn_drop_seed(drop), b, active ? h : 0) ^ ((unsigned)qi << 15) ^ (2u * (unsigned)hi) : 0u;
 
-    const int nkt = (i0 + TQ + TKV - 1) / TKV;
+    const int nkt = (kend + TKV - 1) / TKV;
     KVRegs<T, PRECISE> kr, vr;
     kr.load(k + rowbase * 64, 0, N);
     vr.load(v + rowbase * 64, 0, N);
@@ -237,7 +246,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int jb = j0 + 32 * sub;
-            if (jb > i0 + TQ - 1) break;
+            if (jb > kend - 1) break;
             f32x16 st;
 #pragma unroll
             for (int e = 0; e < 16; ++e) st[e] = 0.f;
@@ -269,8 +278,8 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
                     const int kr = 32 * sub + crow(r, hi);
                     const int key = j0 + kr;
                     const int rel = qi - key;
-                    const bool ok = (rel >= 0) && ((bits >> kr) & 1ull);
-                    const float val = st[r] * c + bl[max(min(rel, nb - 1), 0)];
+                    const bool ok = (rel >= 0 || (PFX && qi < Pn && key < Pn)) && ((bits >> kr) & 1ull);
+                    const float val = st[r] * c + bl[max(min(rel, nb - 1), -off)];
                     st[r] = ok ? val : NEG_BIG;
                     mloc = fmaxf(mloc, st[r]);
                 }
@@ -330,7 +339,9 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
 // =============================================================================================================
 // backward, kernel B: dQ, d(bias table), delta_i = sum_d dO[i,d] O[i,d]     (same geometry as the forward)
 // =============================================================================================================
-template <typename T, bool DROP = false>
+// PFX: the non-causal prefix, as in the forward; the d(bias) bins of negative distances (rel >= -(Pn - 1)) sit in front of the others and
+// leave by atomics into dbias (which points at the rel = 0 row), the others as before.
+template <typename T, bool DROP = false, bool PFX = false>
 __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_DQ_WPE))) void attn_bwd_dq_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                                  const T* __restrict__ v, const float* __restrict__ bias,
                                                                  const unsigned char* __restrict__ keymask,
@@ -338,7 +349,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                                                                  const float* __restrict__ lse, float* __restrict__ delta,
                                                                  float* __restrict__ dq, float* __restrict__ dbias,
                                                                  int B, int N, int H, float scale, int bias_ld, float* __restrict__ dpart,
-                                                                 const AttnDrop drop) {
+                                                                 const AttnDrop drop, int Pn) {
     constexpr int PLANE = TKV * 128;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Ks = smem;                       // K rows  (S^T = K Q^T)
@@ -353,20 +364,30 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
     const int i0 = qt * TQ;
     const int qi = i0 + (lane & 31);
     const int nb = i0 + TQ;
-    float* bias_l = (float*)(smem + 3 * PLANE) + (size_t)wave * nb;              // [4][nb]
-    float* dbias_l = (float*)(smem + 3 * PLANE) + (size_t)(4 + wave) * nb;       // [4][nb]
+    const int off = PFX ? Pn - 1 : 0;                                              // PFX: negative-distance bins in front
+    const int kend = PFX && i0 < Pn ? max(i0 + TQ, Pn) : i0 + TQ;
+    float* bias_l = (float*)(smem + 3 * PLANE) + (size_t)wave * (nb + off);              // [4][nb + off]
+    float* dbias_l = (float*)(smem + 3 * PLANE) + (size_t)(4 + wave) * (nb + off);       // [4][nb + off]
     // key-mask ballots of every 64-key tile, built once (a global load + ballot per k-tile stalled each iteration)
-    unsigned long long* mbits = (unsigned long long*)(smem + 3 * PLANE + (size_t)8 * (nqt * TQ) * sizeof(float));
+    unsigned long long* mbits = (unsigned long long*)(smem + 3 * PLANE + (size_t)8 * (nqt * TQ + off) * sizeof(float));
     const size_t rowbase = (size_t)b * N;
     const size_t qrow = (rowbase + min(qi, N - 1)) * (size_t)(H * 64) + (active ? h : 0) * 64;
 
     h16x8 qf[4], dof[4], dummy;
     float dl = 0.f, L = 0.f;
     if (active) {
+        if (PFX) {
+            for (int r = lane; r < nb + off; r += 64) {
+                bias_l[r] = bias ? bias[(ptrdiff_t)min(r - off, N - 1) * bias_ld + h] * LOG2E : 0.f;
+                dbias_l[r] = 0.f;
+            }
+        } else
         for (int r = lane; r < nb; r += 64) {
             bias_l[r] = bias ? bias[(size_t)min(r, N - 1) * bias_ld + h] * LOG2E : 0.f;
             dbias_l[r] = 0.f;
         }
+        bias_l += off;                                 // index rel from here on
+        dbias_l += off;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             h16x8 of;
@@ -390,7 +411,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
     // DROP: row key of (b, h, qi) with this half-wave's key bit (see the forward)
     const unsigned rk = DROP ? attn_drop_headkey(attn_drop_seed(drop), b, active ? h : 0) ^ ((unsigned)qi << 15) ^ (2u * (unsigned)hi) : 0u;
 
-    const int nkt = (i0 + TQ + TKV - 1) / TKV;
+    const int nkt = (kend + TKV - 1) / TKV;
     KVRegs<T, false> kr, vr;
     kr.load(k + rowbase * 64, 0, N);
     vr.load(v + rowbase * 64, 0, N);
@@ -416,7 +437,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int jb = j0 + 32 * sub;
-            if (jb > i0 + TQ - 1) break;
+            if (jb > kend - 1) break;
             f32x16 st, dp;
 #pragma unroll
             for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
@@ -459,12 +480,12 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                 for (int r = 0; r < 16; ++r) element(r, (w32 >> ((r & 3) + 8 * (r >> 2))) & 1u);
             } else {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) bv[r] = bias_l[max(min(qi - (j0 + 32 * sub + crow(r, hi)), nb - 1), 0)];
+                for (int r = 0; r < 16; ++r) bv[r] = bias_l[max(min(qi - (j0 + 32 * sub + crow(r, hi)), nb - 1), -off)];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int kr = 32 * sub + crow(r, hi);
                     const int rel = qi - (j0 + kr);
-                    element(r, (rel >= 0) && ((bits >> kr) & 1ull) && (qi < N));
+                    element(r, (rel >= 0 || (PFX && qi < Pn && j0 + kr < Pn)) && ((bits >> kr) & 1ull) && (qi < N));
                 }
             }
             if (dbias) {
@@ -475,7 +496,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                 // of the wave-private table, predicated so that every lane owns a distinct bin.
                 const float dsum = diag_sum_32x32(bv, lane);
                 const int rel = (i0 - j0 - 32 * sub) + (lane - 31);
-                if (rel >= 0 && rel < nb) dbias_l[rel] += dsum;
+                if (rel >= -off && rel < nb) dbias_l[rel] += dsum;
             }
             {   // the four K^T fragments requested together, the packing of dS under their latency, retired pair by pair
                 h16x8 ktf[2][2], dsb[2];
@@ -519,12 +540,17 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
             const float vv = dbias_l[r];
             if (vv != 0.f) unsafeAtomicAdd(dbias + (size_t)r * bias_ld + h, vv);
         }
+        if (PFX && i0 < Pn)                            // negative distances: only query tiles inside the prefix reach them
+            for (int r = lane - off; r < 0; r += 64) {
+                const float vv = dbias_l[r];
+                if (vv != 0.f) unsafeAtomicAdd(dbias + (ptrdiff_t)r * bias_ld + h, vv);
+            }
     }
 }
 
 // The same kernel for fp32 ("bf16x3") operands with hi/lo S and dP, kept as its own function so that the bf16 kernel's code and
 // register allocation (already at the 256-register limit) stay exactly as measured.
-template <typename T, bool DROP = false>
+template <typename T, bool DROP = false, bool PFX = false>
 __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_DQP_WPE))) void attn_bwd_dq_precise_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                                  const T* __restrict__ v, const float* __restrict__ bias,
                                                                  const unsigned char* __restrict__ keymask,
@@ -532,7 +558,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                                                                  const float* __restrict__ lse, float* __restrict__ delta,
                                                                  float* __restrict__ dq, float* __restrict__ dbias,
                                                                  int B, int N, int H, float scale, int bias_ld, float* __restrict__ dpart,
-                                                                 const AttnDrop drop) {
+                                                                 const AttnDrop drop, int Pn) {
     // fp32 operands ("bf16x3"): S and dP -- the two products the probabilities and d(bias) are made of -- are formed from
     // hi/lo splits (3 MFMAs per product), so p, dS and the rel-pos bias gradient are fp32-grade; dQ = dS K itself stays a
     // single bf16 pass (dS rounded once), like every other gradient GEMM operand of this mode's backward.
@@ -554,20 +580,30 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
     const int i0 = qt * TQ;
     const int qi = i0 + (lane & 31);
     const int nb = i0 + TQ;
-    float* bias_l = (float*)(smem + NPL * PLANE) + (size_t)wave * nb;              // [4][nb]
-    float* dbias_l = (float*)(smem + NPL * PLANE) + (size_t)(4 + wave) * nb;       // [4][nb]
+    const int off = PFX ? Pn - 1 : 0;                                              // PFX: negative-distance bins in front
+    const int kend = PFX && i0 < Pn ? max(i0 + TQ, Pn) : i0 + TQ;
+    float* bias_l = (float*)(smem + NPL * PLANE) + (size_t)wave * (nb + off);              // [4][nb + off]
+    float* dbias_l = (float*)(smem + NPL * PLANE) + (size_t)(4 + wave) * (nb + off);       // [4][nb + off]
     // key-mask ballots of every 64-key tile, built once (a global load + ballot per k-tile stalled each iteration)
-    unsigned long long* mbits = (unsigned long long*)(smem + NPL * PLANE + (size_t)8 * (nqt * TQ) * sizeof(float));
+    unsigned long long* mbits = (unsigned long long*)(smem + NPL * PLANE + (size_t)8 * (nqt * TQ + off) * sizeof(float));
     const size_t rowbase = (size_t)b * N;
     const size_t qrow = (rowbase + min(qi, N - 1)) * (size_t)(H * 64) + (active ? h : 0) * 64;
 
     h16x8 qf[4], dof[4], ql[4], dol[4], dummy;
     float dl = 0.f, L = 0.f;
     if (active) {
+        if (PFX) {
+            for (int r = lane; r < nb + off; r += 64) {
+                bias_l[r] = bias ? bias[(ptrdiff_t)min(r - off, N - 1) * bias_ld + h] * LOG2E : 0.f;
+                dbias_l[r] = 0.f;
+            }
+        } else
         for (int r = lane; r < nb; r += 64) {
             bias_l[r] = bias ? bias[(size_t)min(r, N - 1) * bias_ld + h] * LOG2E : 0.f;
             dbias_l[r] = 0.f;
         }
+        bias_l += off;                                 // index rel from here on
+        dbias_l += off;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             h16x8 of;
@@ -591,7 +627,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
     // DROP: row key of (b, h, qi) with this half-wave's key bit (see the forward)
     const unsigned rk = DROP ? attn_drop_headkey(attn_drop_seed(drop), b, active ? h : 0) ^ ((unsigned)qi << 15) ^ (2u * (unsigned)hi) : 0u;
 
-    const int nkt = (i0 + TQ + TKV - 1) / TKV;
+    const int nkt = (kend + TKV - 1) / TKV;
     KVRegs<T, PRECISE> kr, vr;
     kr.load(k + rowbase * 64, 0, N);
     vr.load(v + rowbase * 64, 0, N);
@@ -617,7 +653,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int jb = j0 + 32 * sub;
-            if (jb > i0 + TQ - 1) break;
+            if (jb > kend - 1) break;
             f32x16 st, dp;
 #pragma unroll
             for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
@@ -663,12 +699,12 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                 for (int r = 0; r < 16; ++r) element(r, (w32 >> ((r & 3) + 8 * (r >> 2))) & 1u);
             } else {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) bv[r] = bias_l[max(min(qi - (j0 + 32 * sub + crow(r, hi)), nb - 1), 0)];
+                for (int r = 0; r < 16; ++r) bv[r] = bias_l[max(min(qi - (j0 + 32 * sub + crow(r, hi)), nb - 1), -off)];
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int kr = 32 * sub + crow(r, hi);
                     const int rel = qi - (j0 + kr);
-                    element(r, (rel >= 0) && ((bits >> kr) & 1ull) && (qi < N));
+                    element(r, (rel >= 0 || (PFX && qi < Pn && j0 + kr < Pn)) && ((bits >> kr) & 1ull) && (qi < N));
                 }
             }
             if (dbias) {
@@ -679,7 +715,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
                 // of the wave-private table, predicated so that every lane owns a distinct bin.
                 const float dsum = diag_sum_32x32(bv, lane);
                 const int rel = (i0 - j0 - 32 * sub) + (lane - 31);
-                if (rel >= 0 && rel < nb) dbias_l[rel] += dsum;
+                if (rel >= -off && rel < nb) dbias_l[rel] += dsum;
             }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
@@ -716,6 +752,11 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
             const float vv = dbias_l[r];
             if (vv != 0.f) unsafeAtomicAdd(dbias + (size_t)r * bias_ld + h, vv);
         }
+        if (PFX && i0 < Pn)                            // negative distances: only query tiles inside the prefix reach them
+            for (int r = lane - off; r < 0; r += 64) {
+                const float vv = dbias_l[r];
+                if (vv != 0.f) unsafeAtomicAdd(dbias + (ptrdiff_t)r * bias_ld + h, vv);
+            }
     }
 }
 
@@ -723,14 +764,17 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 // backward, kernel A: dK, dV.  One workgroup per (sample, 32-key tile); its 4 waves split the (query tile, head)
 // work items and reduce their partial dK^T / dV^T through LDS at the end -- no atomics on dK / dV.
 // =============================================================================================================
-template <typename T, bool DROP = false>
+// PFX: the non-causal prefix (see the forward; biasT must be null).  A key tile with j0 < Pn walks every query tile from 0, not from its
+// own, and the staged bias columns also cover the negative distances it can meet, rel >= -min(Pn - 1, j0 + 31) (index rel + off): at most
+// 31 more entries per column than the causal kernel stages.
+template <typename T, bool DROP = false, bool PFX = false>
 __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_DKV_WPE))) void attn_bwd_dkv_kernel(const T* __restrict__ q, const T* __restrict__ k,
                                                                   const T* __restrict__ v, const float* __restrict__ bias,
                                                                   const unsigned char* __restrict__ keymask,
                                                                   const T* __restrict__ dout, const float* __restrict__ lse,
                                                                   const float* __restrict__ delta, float* __restrict__ dk,
                                                                   float* __restrict__ dv, int B, int N, int H, float scale, int bias_ld,
-                                                                  const float* __restrict__ biasT, int ldT, const AttnDrop drop) {
+                                                                  const float* __restrict__ biasT, int ldT, const AttnDrop drop, int Pn) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hi = lane >> 5;
     char* Qs = smem + wave * 8192;            // per-wave private [32][64] bf16 tiles (Q, dO) for the transpose reads
@@ -745,16 +789,24 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
     const int kj = j0 + (lane & 31);          // this lane's key (column of S)
     const size_t rowbase = (size_t)b * N;
     const float c = scale * LOG2E;
-    const int nbk = nqt * TQ - j0;            // rel = i - kj <= nqt*TQ - 1 - j0
+    const int off = PFX ? min(Pn - 1, j0 + 31) : 0;      // PFX: negative distances in front of each staged column
+    const int it0 = PFX && j0 < Pn ? 0 : jt;  // first query tile with a live score for these keys
+    const int nbk = nqt * TQ - j0 + off;      // rel = i - kj <= nqt*TQ - 1 - j0 (PFX: >= -off)
     h16x8 dummy;
     // WIN: the prepared table (omlm_attn_bias_prepare: [head][64 + rel], x log2 e, minus the head's reference point m_h) is there:
     // an item's 63 bias values are one coalesced load per lane, fetched with the item's Q / dO and parked in a 64-float LDS patch
     // per wave.  Without it the whole [H][N - j0] column set is staged below: 117 KiB for musiclm_large's fine stage
     // (H = 16, N = 1817), i.e. ONE 4-wave workgroup per CU.
-    const bool WIN = biasT != nullptr;
+    const bool WIN = !PFX && biasT != nullptr;
 
     // The rel-pos column of every head goes to LDS once.  (Per-element global gathers of bias / lse / delta -- 48
     // dependent L2 round trips per work item -- were >95 % of this kernel: 26k cycles per item for 16 MFMAs.)
+    if (PFX) {
+        for (int idx = threadIdx.x; idx < H * nbk; idx += AT_THREADS) {
+            const int r = idx / H, hh = idx - r * H;
+            bias_s[hh * nbk + r] = bias ? bias[(ptrdiff_t)min(r - off, N - 1) * bias_ld + hh] * LOG2E : 0.f;
+        }
+    } else
     if (!WIN) for (int idx = threadIdx.x; idx < H * nbk; idx += AT_THREADS) {
         const int r = idx / H, hh = idx - r * H;
         bias_s[hh * nbk + r] = bias ? bias[(size_t)min(r, N - 1) * bias_ld + hh] * LOG2E : 0.f;
@@ -776,13 +828,13 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 #pragma unroll
     for (int e = 0; e < 16; ++e) { dkacc[0][e] = 0.f; dkacc[1][e] = 0.f; dvacc[0][e] = 0.f; dvacc[1][e] = 0.f; }
 
-    const int nitems = (nqt - jt) * H;        // (query tile it >= jt) x head
+    const int nitems = (nqt - it0) * H;       // (query tile it >= it0) x head
     // A-operand fragments (rows = queries i0 + (lane&31), dims 16 s + 8 hi) of Q and dO plus the tile's lse / delta
     // (one value per lane = per query); the NEXT item's are fetched while the current item is on the matrix cores.
     h16x8 qa[4], doa[4], qn[4], don[4];
     float La = 0.f, Da = 0.f, Ln = 0.f, Dn = 0.f, Ba = 0.f, Bn = 0.f, Ma = 0.f, Mn = 0.f;
     auto fetch = [&](int item, h16x8 (&fq)[4], h16x8 (&fd)[4], float& fl, float& fdl, float& fb, float& fm) {
-        const int qi_ = (jt + item / H) * TQ + (lane & 31);
+        const int qi_ = (it0 + item / H) * TQ + (lane & 31);
         const int hh = item % H;
         const size_t qrow_ = (rowbase + min(qi_, N - 1)) * (size_t)(H * 64) + hh * 64;
 #pragma unroll
@@ -794,7 +846,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
         fdl = delta[((size_t)b * H + hh) * N + min(qi_, N - 1)];
         if (WIN) {      // window of rel = i - j for the item: from (i0 - j0 - 31); table index 64 + rel; lse made relative to m_h
             const float* row = biasT + (size_t)hh * ldT;
-            fb = row[64 + ((jt + item / H) * TQ - j0 - 31) + min(lane, 62)];
+            fb = row[64 + ((it0 + item / H) * TQ - j0 - 31) + min(lane, 62)];
             fm = row[ldT - 1];      // subtracted where the item is consumed: an arithmetic use here waits for every load issued above
         }
     };
@@ -808,7 +860,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
     asm volatile("" : "+v"(La), "+v"(Da), "+v"(Ba), "+v"(Ma));
     __syncthreads();                           // bias_s staged
     for (int item = wave; item < nitems; item += 4) {
-        const int it = jt + item / H, h = item % H;
+        const int it = it0 + item / H, h = item % H;
         const int i0 = it * TQ;
         if (item + 4 < nitems) fetch(item + 4, qn, don, Ln, Dn, Bn, Mn);
 #pragma unroll
@@ -819,8 +871,8 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
         // lean form (see the forward): the tile's lse / delta go through a 64-float per-wave LDS patch instead of 4 v_readlane +
         // 2 selects per score row, and items whose queries all follow this workgroup's keys (all but the first query tile) skip the
         // causal compare, the i < N compare and the clamp of the bias index (constant LDS offsets from one base)
-        const float* bh = bias_s + h * nbk;
-        float* ld_l = WIN ? (float*)(smem + 32768) + wave * 128 : (float*)(smem + 32768 + (size_t)H * (nqt * TQ) * sizeof(float)) + wave * 64;
+        const float* bh = bias_s + h * nbk + off;
+        float* ld_l = WIN ? (float*)(smem + 32768) + wave * 128 : (float*)(smem + 32768 + (size_t)H * (PFX ? nqt * TQ + 31 : nqt * TQ) * sizeof(float)) + wave * 64;
         if (lane < 32) { ld_l[lane] = La - Ma; ld_l[32 + lane] = Da; }        // Ma: the head's reference point (WIN), else 0
         if (WIN) ld_l[64 + lane] = Ba;
         // window index of (query row crow(r, hi), this lane's key): cr + 4 hi - (lane & 31) + 31
@@ -876,7 +928,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int cr = (r & 3) + 8 * (r >> 2);
-                bvv[r] = WIN ? bwp[cr] : bh[max(min(i0 + crow(r, hi) - kj, nbk - 1), 0)];
+                bvv[r] = WIN ? bwp[cr] : bh[max(min(i0 + crow(r, hi) - kj, nbk - off - 1), -off)];
                 lvv[r] = lp[cr];
             }
 #pragma unroll
@@ -885,7 +937,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
             for (int r = 0; r < 16; ++r) {
                 const int cr = (r & 3) + 8 * (r >> 2);
                 const int i = i0 + crow(r, hi);
-                const bool ok = (i >= kj) && keylive && (i < N);
+                const bool ok = (i >= kj || (PFX && i < Pn && kj < Pn)) && keylive && (i < N);
                 const float x = st[r] * c + bvv[r] - lvv[r];
                 const float p = __builtin_amdgcn_exp2f(ok ? x : NEG_BIG);
                 pp[r] = DROP ? p * zz[r] : p;
@@ -928,8 +980,8 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 }
 
 // =============================================================================================================
-static size_t fwd_lds(int N, bool precise) { return (size_t)(precise ? 4 : 2) * TKV * 128 + (size_t)4 * ((N + TQ - 1) / TQ * TQ) * sizeof(float); }
-static size_t dq_lds(int N, bool precise = false) { return (size_t)(precise ? 5 : 3) * TKV * 128 + (size_t)8 * ((N + TQ - 1) / TQ * TQ) * sizeof(float) + (size_t)8 * ((N + TKV - 1) / TKV + 1); }
+static size_t fwd_lds(int N, bool precise, int off = 0) { return (size_t)(precise ? 4 : 2) * TKV * 128 + (size_t)4 * ((N + TQ - 1) / TQ * TQ + off) * sizeof(float); }
+static size_t dq_lds(int N, bool precise = false, int off = 0) { return (size_t)(precise ? 5 : 3) * TKV * 128 + (size_t)8 * ((N + TQ - 1) / TQ * TQ + off) * sizeof(float) + (size_t)8 * ((N + TKV - 1) / TKV + 1); }
 
 template <typename K>
 static int set_lds(K kernel, size_t bytes) {
@@ -939,7 +991,9 @@ static int set_lds(K kernel, size_t bytes) {
 }
 
 int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
-                     void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop);   // attention2.hip
+                     void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn);   // attention2.hip
+
+bool attn2_prefix_fits(int N, int Pn);      // attention2.hip: whether the second-generation kernels serve a prefix of Pn rows at N
 
 // the forward of omlm_mqa_attn_fwd (drop == NULL) and omlm_mqa_attn_fwd_dropout (drop: p > 0)
 static int attn_fwd_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
@@ -949,7 +1003,7 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, const floa
     OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
     OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
     if (dtype == 1 && (biasT || !bias))
-        return attn2_fwd_launch(q, k, v, biasT, keymask, out, lse, B, N, H, scale, as_stream(stream), drop);
+        return attn2_fwd_launch(q, k, v, biasT, keymask, out, lse, B, N, H, scale, as_stream(stream), drop, 0);
     dim3 grid((N + TQ - 1) / TQ, (H + 3) / 4, B), block(AT_THREADS);
     const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
     const AttnDrop& dr = drop ? *drop : nd;
@@ -962,15 +1016,46 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, const floa
         const size_t lds = fwd_lds(N, true);
         auto kern = drop ? attn_fwd_kernel<float, true> : attn_fwd_kernel<float, false>;
         if ((rc = set_lds(kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const float*)q, (const float*)k, (const float*)v, bias, keymask, (float*)out, lse, B, N, H, scale, bias_ld, dr);
+        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const float*)q, (const float*)k, (const float*)v, bias, keymask, (float*)out, lse, B, N, H, scale, bias_ld, dr, 0);
 #endif
     } else {
         const size_t lds = fwd_lds(N, false);
         auto kern = drop ? attn_fwd_kernel<h16_t, true> : attn_fwd_kernel<h16_t, false>;
         if ((rc = set_lds(kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (h16_t*)out, lse, B, N, H, scale, bias_ld, dr);
+        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (h16_t*)out, lse, B, N, H, scale, bias_ld, dr, 0);
     }
     return omlm_post_launch("omlm_mqa_attn_fwd");
+}
+
+// The forward with a non-causal prefix of Pn = min(P, N) >= 1 rows (omlm_mqa_attn_fwd_prefix): the first-generation kernels' PFX
+// instances for every operand type.  bias: the rel = 0 row of the [N + Pn - 1, bias_ld] table (or null).
+static int attn_fwd_prefix_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
+                                const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype,
+                                int Pn, void* stream, const AttnDrop* drop) {
+    // 16-bit operands with the prepared table (omlm_attn_bias_prepare_group_prefix), or without any bias: attention2.hip's PFX instances
+    if (dtype == 1 && (biasT || !bias) && attn2_prefix_fits(N, Pn))
+        return attn2_fwd_launch(q, k, v, biasT, keymask, out, lse, B, N, H, scale, as_stream(stream), drop, Pn);
+    dim3 grid((N + TQ - 1) / TQ, (H + 3) / 4, B), block(AT_THREADS);
+    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
+    const AttnDrop& dr = drop ? *drop : nd;
+    int rc;
+    if (dtype == 0) {
+#if OMLM_FP16
+        omlm_set_error("omlm_mqa_attn_fwd_prefix: fp32 operands are served by the bf16 copy of the library");
+        return OMLM_ERR_UNSUPPORTED;
+#else
+        const size_t lds = fwd_lds(N, true, Pn - 1);
+        auto kern = drop ? attn_fwd_kernel<float, true, true> : attn_fwd_kernel<float, false, true>;
+        if ((rc = set_lds(kern, lds))) return rc;
+        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const float*)q, (const float*)k, (const float*)v, bias, keymask, (float*)out, lse, B, N, H, scale, bias_ld, dr, Pn);
+#endif
+    } else {
+        const size_t lds = fwd_lds(N, false, Pn - 1);
+        auto kern = drop ? attn_fwd_kernel<h16_t, true, true> : attn_fwd_kernel<h16_t, false, true>;
+        if ((rc = set_lds(kern, lds))) return rc;
+        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (h16_t*)out, lse, B, N, H, scale, bias_ld, dr, Pn);
+    }
+    return omlm_post_launch("omlm_mqa_attn_fwd_prefix");
 }
 
 
@@ -1012,15 +1097,39 @@ extern "C" int OMLM_API(omlm_mqa_attn_fwd_dropout)(const void* q, const void* k,
     return attn_fwd_impl(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, dtype, stream, p > 0.f ? &d : nullptr);
 }
 
+// non-causal prefix of P rows (include/omlm.h); p: attention dropout as in omlm_mqa_attn_fwd_dropout (0: none)
+#if !OMLM_FP16
+extern "C" int omlm_mqa_attn_fwd_prefix_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                          void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
+                                          unsigned long long seed, const unsigned long long* seed_dev, void* stream);
+#endif
+extern "C" int OMLM_API(omlm_mqa_attn_fwd_prefix)(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                                  void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
+                                                  unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+#if !OMLM_FP16
+    if (dtype == OMLM_DT_F16)
+        return omlm_mqa_attn_fwd_prefix_h(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, 1, P, p, seed, seed_dev, stream);
+#endif
+    if (B <= 0 || N <= 0) return OMLM_OK;
+    AttnDrop d;
+    OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
+    OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
+    OMLM_CHECK_ARG(P >= 1, "prefix rows P >= 1 (P = 0: omlm_mqa_attn_fwd_dropout)");
+    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
+    const int Pn = P < N ? P : N;
+    return attn_fwd_prefix_impl(q, k, v, bias ? bias + (size_t)(Pn - 1) * bias_ld : nullptr, biasT, keymask, out, lse, B, N, H, scale, bias_ld,
+                                dtype, Pn, stream, p > 0.f ? &d : nullptr);
+}
+
 // dq [B*N, H*64] fp32, dk, dv [B*N, 64] fp32 (overwritten), dbias [N, bias_ld] fp32 (accumulated, +=), delta [B, H, N] scratch
 int attn2_bwd_dq_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                         const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dbias, int bias_ld,
-                        float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop);   // attention2.hip
+                        float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn);   // attention2.hip
 extern "C" __attribute__((visibility("hidden"))) int omlm_attn_dbias_reduce_launch(const float* dpart, float* dbias, int bias_ld, int B, int N, int H, void* stream);   // attention2.hip (bf16 copy)
 
 int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                          const void* dout, const float* lse, const float* delta, float* dk, float* dv,
-                         int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop);      // attention3.hip
+                         int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn);      // attention3.hip
 #if !OMLM_FP16
 extern "C" int omlm_mqa_attn_bwd_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
                                    const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
@@ -1056,9 +1165,9 @@ static int attn_bwd_impl(const void* q, const void* k, const void* v, const floa
         auto kk = drop ? attn_bwd_dkv_kernel<float, true> : attn_bwd_dkv_kernel<float, false>;
         if ((rc = set_lds(kq, ldsq))) return rc;
         if ((rc = set_lds(kk, ldsk))) return rc;
-        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)out, (const float*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr);
+        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)out, (const float*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, 0);
         if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
-        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr);
+        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr, 0);
 #endif
     } else {
         auto kk = drop ? attn_bwd_dkv_kernel<h16_t, true> : attn_bwd_dkv_kernel<h16_t, false>;
@@ -1069,26 +1178,77 @@ static int attn_bwd_impl(const void* q, const void* k, const void* v, const floa
         // diagonal sums and the d(bias) workspace it is the faster one at both bench shapes (B=32, N=1116, H=8: whole backward 432 against
         // 456 us; before those two changes both kernels spent ~160 us per layer in d(bias) and the first-generation kernel led 316 : 334).
         if (biasT || !bias) {
-            r2 = attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, drop);
+            r2 = attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, drop, 0);
             if (r2 < 0) return r2;
         }
         if (r2 != 0) {
         auto kq = drop ? attn_bwd_dq_kernel<h16_t, true> : attn_bwd_dq_kernel<h16_t, false>;
         if ((rc = set_lds(kq, ldsq))) return rc;
-        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr);
+        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, 0);
         }
         if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
         // dK / dV: the third-generation kernel (attention3.hip: 128 keys per workgroup, Q / dO staged once per workgroup by LDS-DMA) where the
         // prepared table is there (or there is no bias); else the second-generation kernel
         int r3 = 1;
         if (biasT || !bias) {
-            r3 = attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, drop);
+            r3 = attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, drop, 0);
             if (r3 < 0) return r3;
         }
         if (r3 != 0)
-        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr);
+        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr, 0);
     }
     return omlm_post_launch("omlm_mqa_attn_bwd");
+}
+
+// The backward with a non-causal prefix of Pn = min(P, N) >= 1 rows (omlm_mqa_attn_bwd_prefix): the PFX instances of the first-generation
+// dQ and dK / dV kernels.  bias / dbias: the rel = 0 rows of the [N + Pn - 1, bias_ld] tables; d(bias) of rel >= 0 goes through the
+// workspace and its reduction as in attn_bwd_impl, that of rel < 0 by atomics from the dQ kernel.
+static int attn_bwd_prefix_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
+                                float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int Pn, void* stream,
+                                const AttnDrop* drop) {
+    dim3 gridq((N + TQ - 1) / TQ, (H + 3) / 4, B), gridk((N + 31) / 32, 1, B), block(AT_THREADS);
+    const int off = Pn - 1;
+    const size_t ldsq = dq_lds(N, dtype == 0, off);
+    const size_t ldsk = 32 * 1024 + (size_t)H * ((N + TQ - 1) / TQ * TQ + 31) * sizeof(float) + 1024;      // see attn_bwd_dkv_kernel
+    int rc;
+    hipStream_t st = as_stream(stream);
+    float* dpart = dbias ? dbias_ws : nullptr;
+    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
+    const AttnDrop& dr = drop ? *drop : nd;
+    if (dtype == 0) {
+#if OMLM_FP16
+        omlm_set_error("omlm_mqa_attn_bwd_prefix: fp32 operands are served by the bf16 copy of the library");
+        return OMLM_ERR_UNSUPPORTED;
+#else
+        auto kq = drop ? attn_bwd_dq_precise_kernel<float, true, true> : attn_bwd_dq_precise_kernel<float, false, true>;
+        auto kk = drop ? attn_bwd_dkv_kernel<float, true, true> : attn_bwd_dkv_kernel<float, false, true>;
+        if ((rc = set_lds(kq, ldsq))) return rc;
+        if ((rc = set_lds(kk, ldsk))) return rc;
+        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)out, (const float*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
+        if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
+        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, nullptr, 0, dr, Pn);
+#endif
+    } else {
+        auto kq = drop ? attn_bwd_dq_kernel<h16_t, true, true> : attn_bwd_dq_kernel<h16_t, false, true>;
+        auto kk = drop ? attn_bwd_dkv_kernel<h16_t, true, true> : attn_bwd_dkv_kernel<h16_t, false, true>;
+        // the prepared table (or no bias): attention2.hip's dQ and attention3.hip's dK / dV PFX instances where their plans fit -- the same
+        // test as the forward's, whose lse is relative to the table's reference point there
+        if ((biasT || !bias) && attn2_prefix_fits(N, Pn)) {
+            if ((rc = attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, drop, Pn)))
+                return rc < 0 ? rc : OMLM_ERR_UNSUPPORTED;
+            if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
+            if ((rc = attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, drop, Pn)))
+                return rc < 0 ? rc : OMLM_ERR_UNSUPPORTED;
+            return omlm_post_launch("omlm_mqa_attn_bwd_prefix");
+        }
+        if ((rc = set_lds(kq, ldsq))) return rc;
+        if ((rc = set_lds(kk, ldsk))) return rc;
+        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
+        if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
+        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, nullptr, 0, dr, Pn);
+    }
+    return omlm_post_launch("omlm_mqa_attn_bwd_prefix");
 }
 
 extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
@@ -1124,6 +1284,33 @@ extern "C" int OMLM_API(omlm_mqa_attn_bwd_dropout)(const void* q, const void* k,
     OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
     return attn_bwd_impl(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, dtype,
                          stream, p > 0.f ? &d : nullptr);
+}
+
+#if !OMLM_FP16
+extern "C" int omlm_mqa_attn_bwd_prefix_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                          const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
+                                          float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P,
+                                          float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream);
+#endif
+extern "C" int OMLM_API(omlm_mqa_attn_bwd_prefix)(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                                  const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
+                                                  float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P,
+                                                  float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+#if !OMLM_FP16
+    if (dtype == OMLM_DT_F16)
+        return omlm_mqa_attn_bwd_prefix_h(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, 1,
+                                          P, p, seed, seed_dev, stream);
+#endif
+    if (B <= 0 || N <= 0) return OMLM_OK;
+    AttnDrop d;
+    OMLM_CHECK_ARG(q && k && v && out && dout && lse && delta && dq && dk && dv, "null pointer");
+    OMLM_CHECK_ARG(H >= 1 && ((!bias && !dbias) || bias_ld >= H), "heads / bias pitch");
+    OMLM_CHECK_ARG(P >= 1, "prefix rows P >= 1 (P = 0: omlm_mqa_attn_bwd_dropout)");
+    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
+    const int Pn = P < N ? P : N;
+    const size_t r0 = (size_t)(Pn - 1) * bias_ld;
+    return attn_bwd_prefix_impl(q, k, v, bias ? bias + r0 : nullptr, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias ? dbias + r0 : nullptr,
+                                dbias_ws, B, N, H, scale, bias_ld, dtype, Pn, stream, p > 0.f ? &d : nullptr);
 }
 
 }   // namespace OMLM_NS

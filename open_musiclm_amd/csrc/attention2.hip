@@ -62,10 +62,13 @@ __device__ __forceinline__ h16x8 a2_pack(const f32x16& p, int s) {
 //   below); 15 for IEEE half, whose normal range is 2^-14 .. 2^15.99: numerators in (2^-13, 2^15] while 2 c qk_max + range < 28.
 // (round 6) grid.y = layers: every layer's table in ONE launch -- the tables of a forward differ only through their layer's learned scales, and
 // six launches of 8 workgroups were 6 x 14 us of latency per step (omlm_attn_bias_prepare_group; the single-layer entry passes one layer).
+// PFX (non-causal prefix, off = min(P, N) - 1 > 0): bias points at the rel = 0 row of a table that also holds rel = -off .. -1 in front; the
+// prepared row holds them at [A2_PAD, A2_PAD + off) (entry A2_PAD + off + rel), and they count for the maximum and the range.
 #define A2_PREP_MAX 32
 struct A2PrepGroup { float* out[A2_PREP_MAX]; const float* qs[A2_PREP_MAX]; const float* ks[A2_PREP_MAX]; };
+template <bool PFX = false>
 __global__ void attn2_bias_prep_kernel(const float* __restrict__ bias, A2PrepGroup grp, int N, int H, int ld, int ldT,
-                                       float qk_bound, float c, int p_max_log2) {
+                                       float qk_bound, float c, int p_max_log2, int off) {
     __shared__ float red[4][2][8];
     __shared__ float redq[4];
     const int h = blockIdx.x, t = threadIdx.x;
@@ -81,10 +84,10 @@ __global__ void attn2_bias_prep_kernel(const float* __restrict__ bias, A2PrepGro
             float mx[8], mn[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) { mx[j] = -3.0e38f; mn[j] = 3.0e38f; }
-            for (int r = t; r < N; r += 256) {
+            for (int r = PFX ? t - off : t; r < N; r += 256) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const float x = hb + j < H ? bias[(size_t)r * ld + hb + j] * A2_LOG2E : 0.f;
+                    const float x = hb + j < H ? bias[(PFX ? (ptrdiff_t)r : (size_t)r) * ld + hb + j] * A2_LOG2E : 0.f;
                     mx[j] = fmaxf(mx[j], x); mn[j] = fminf(mn[j], x);
                 }
             }
@@ -118,6 +121,13 @@ __global__ void attn2_bias_prep_kernel(const float* __restrict__ bias, A2PrepGro
     // all exponents lie in [p_max_log2 - (2 B + range), p_max_log2]
     const bool fixed = qk > 0.f && (2.f * B + wide) < (p_max_log2 > 0 ? 13.f + (float)p_max_log2 : 80.f);
     const float m = fixed ? B + own_max - (float)p_max_log2 : 0.f;
+    if (PFX) {
+        for (int x = t; x < ldT - 2; x += 256) {
+            const int r = x - A2_PAD - off;
+            const float v = (has && r >= -off && r < N) ? bias[(ptrdiff_t)r * ld + h] * A2_LOG2E : 0.f;
+            row[x] = v - m;
+        }
+    } else
     for (int x = t; x < ldT - 2; x += 256) {
         const int r = x - A2_PAD;
         const float v = (has && r >= 0 && r < N) ? bias[(size_t)r * ld + h] * A2_LOG2E : 0.f;
@@ -211,9 +221,12 @@ struct A4Acc {
 //   others (instead of 32 per-value selects): ~70 of ~260 VALU instructions per tile less in a loop that is VALU-issue bound.
 //   DROP: the numerator MFMAs take P with the dropped keys' entries zeroed (attn_drop_pair_mask on the packed pairs; rk: the two heads' row
 //   keys, see common.h), the denominator MFMA the undropped P -- the 1 / (1 - p) scale is applied with 1 / denominator at the store.
-template <bool FIXED, bool FULL, int QSEL = -1, bool DROP = false>
+//   PFX: the non-causal prefix of Pn rows (include/omlm.h): keys up to kend = max(i0 + 32, Pn) for a query tile inside it, and the blocks
+//   not wholly below the diagonal keep (i, j) iff j <= i or i, j < Pn.
+template <bool FIXED, bool FULL, int QSEL = -1, bool DROP = false, bool PFX = false>
 __device__ __forceinline__ void a4_tile(A4Acc& A, const h16x8 (&qf)[2][4], const char* Ks, const h16_t* live0, const h16_t* live1,
-                                        float c, int i0, int j0, int wave, int lane, const unsigned (&rk)[2], unsigned thr16) {
+                                        float c, int i0, int j0, int wave, int lane, const unsigned (&rk)[2], unsigned thr16, int kend = 0,
+                                        int Pn = 0) {
     const char* Vs = Ks + 8192;
     const int hi = lane >> 5, ql = lane & 31;
     // window index of (head hb, query ql, key 32 sub + 4 hi + cr): hb 128 + 64 + ql - 32 sub - 4 hi - cr, cr = crow(r, 0) <= 27
@@ -224,13 +237,14 @@ __device__ __forceinline__ void a4_tile(A4Acc& A, const h16x8 (&qf)[2][4], const
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
         const int jb = j0 + 32 * sub;
-        if (!FULL && jb > i0 + 31) break;                       // above the diagonal for every query of the workgroup
+        if (!FULL && jb > (PFX ? kend - 1 : i0 + 31)) break;    // above the diagonal (PFX: past the prefix) for every query of the workgroup
         h16x8 kf[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) kf[s] = a2_frag_rows(Ks, 32 * sub, s, lane);
         h16x8 pb[2][2];
         const bool diag = !FULL && !(jb + 31 <= i0);
         const int d0 = (i0 + ql) - (jb + 4 * hi);
+        const bool qpre = PFX && i0 + ql < Pn;                  // PFX: this lane's query row lies in the prefix
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb) {
             if (QSEL >= 0 && hb != QSEL) continue;
@@ -249,7 +263,7 @@ __device__ __forceinline__ void a4_tile(A4Acc& A, const h16x8 (&qf)[2][4], const
                     for (int r = 0; r < 16; ++r) {
                         const int cr = (r & 3) + 8 * (r >> 2);
                         const float e2 = __builtin_amdgcn_exp2f(st[r] * c + bp[27 - cr]);
-                        st[r] = (d0 - cr >= 0) ? e2 : 0.f;
+                        st[r] = (d0 - cr >= 0 || (qpre && jb + 4 * hi + cr < Pn)) ? e2 : 0.f;
                     }
                 }
             } else {
@@ -265,7 +279,7 @@ __device__ __forceinline__ void a4_tile(A4Acc& A, const h16x8 (&qf)[2][4], const
                     for (int r = 0; r < 16; ++r) {
                         const int cr = (r & 3) + 8 * (r >> 2);
                         const float val = st[r] * c + bp[27 - cr];
-                        st[r] = (d0 - cr >= 0) ? val : A2_NEG;
+                        st[r] = (d0 - cr >= 0 || (qpre && jb + 4 * hi + cr < Pn)) ? val : A2_NEG;
                         mloc = fmaxf(mloc, st[r]);
                     }
                 }
@@ -354,11 +368,14 @@ struct A4Stager {
 // the fixed form 10 % slower than this split (103 vs 92 us).
 //   FIXED: both heads in one straight line.  Online (more live state: running maxima, rescale factors): the two heads one after the
 //   other (QSEL), re-reading the K / V fragments per head.
-template <bool FIXED, bool DROP = false>
+// PFX: the non-causal prefix of Pn = min(P, N) rows; the table (omlm_attn_bias_prepare_group_prefix) holds Pn - 1 negative distances in
+// front of the causal layout, so every window offset moves by off = Pn - 1.
+template <bool FIXED, bool DROP = false, bool PFX = false>
 __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__ k,
                                                                   const h16_t* __restrict__ v, const float* __restrict__ biasT, int ldT,
                                                                   const unsigned char* __restrict__ keymask, h16_t* __restrict__ out,
-                                                                  float* __restrict__ lse, int B, int N, int H, float scale, const AttnDrop drop) {
+                                                                  float* __restrict__ lse, int B, int N, int H, float scale, const AttnDrop drop,
+                                                                  int Pn) {
     // the flag of head 0: omlm_attn_bias_prepare decides once for all heads
     if ((biasT && __builtin_amdgcn_readfirstlane(__float_as_int(biasT[ldT - 2])) != 0) != FIXED) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -372,7 +389,9 @@ __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* _
     const int h0 = hy * 8 + 2 * wave;                        // heads h0, h0 + 1
     const int i0 = qt * 32;
     const size_t rowbase = (size_t)b * N;
-    const int nkt = min((i0 + 32 + A2_TKV - 1) / A2_TKV, (N + A2_TKV - 1) / A2_TKV);   // key tiles this query tile needs
+    const int off = PFX ? Pn - 1 : 0;
+    const int kend = PFX && i0 < Pn ? max(i0 + 32, Pn) : i0 + 32;
+    const int nkt = min((kend + A2_TKV - 1) / A2_TKV, (N + A2_TKV - 1) / A2_TKV);   // key tiles this query tile needs
 
     // ---- prologue: liveness of this sample's keys, as a 1/0 array of the operand type (denominator operand) and one ballot word per key
     // tile (V rows of masked keys are DMA'd as zeros).  All byte loads are issued before the first wait.
@@ -417,7 +436,7 @@ __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* _
             a2_dma(rsV, st + 8192 + (2 * wave + u) * 1024, ((lb >> stg.vrow[u]) & 1ull) ? (unsigned)(j0 * 128) + stg.voff[u] : OOB_OFF);
         }
         // bias window of this tile: table index PAD + rel, rel from i0 - j0 - 64 (no table: empty descriptor -> zeros)
-        a2_dma(rsB, st + 16384 + wave * 1024, (unsigned)((A2_PAD + i0 - j0 - 64) * 4) + stg.boff);
+        a2_dma(rsB, st + 16384 + wave * 1024, (unsigned)((A2_PAD + off + i0 - j0 - 64) * 4) + stg.boff);
     };
 
     issue(0, lane);
@@ -483,16 +502,16 @@ __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* _
         const h16_t* live0 = (lane_ & 1) == 0 ? lv : (const h16_t*)zeros;
         const h16_t* live1 = (lane_ & 1) == 1 ? lv : (const h16_t*)zeros;
         if (FIXED) {
-            if (full) a4_tile<true, true, -1, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
-            else      a4_tile<true, false, -1, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
+            if (full) a4_tile<true, true, -1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
+            else      a4_tile<true, false, -1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
         } else if (full) {
-            a4_tile<false, true, 0, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
+            a4_tile<false, true, 0, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
             __builtin_amdgcn_sched_barrier(0);
-            a4_tile<false, true, 1, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
+            a4_tile<false, true, 1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
         } else {
-            a4_tile<false, false, 0, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
+            a4_tile<false, false, 0, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
             __builtin_amdgcn_sched_barrier(0);
-            a4_tile<false, false, 1, DROP>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16);
+            a4_tile<false, false, 1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
         }
     }
     if (qi >= N) return;
@@ -523,14 +542,16 @@ __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* _
 // bias window.  The key mask is an additive 0 / -1e30 vector in LDS (one aligned 16-byte read per 4 scores); the probabilities
 // come straight from the stored log-sum-exp (no maximum to track), so the blocks of a tile are independent.
 #define A2B_STAGE (3 * 8192 + 8 * A2_BWIN * 4)       /* 28 KiB */
-template <bool DROP = false>
+// PFX: the non-causal prefix (see attn4_fwd_kernel); the d(bias) bins of the negative distances sit in front of each wave's bins and leave
+// by atomics into dbias (which points at the rel = 0 row).
+template <bool DROP = false, bool PFX = false>
 __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__ k,
                                                                   const h16_t* __restrict__ v, const float* __restrict__ biasT, int ldT,
                                                                   const unsigned char* __restrict__ keymask, const h16_t* __restrict__ out,
                                                                   const h16_t* __restrict__ dout, const float* __restrict__ lse,
                                                                   float* __restrict__ delta, float* __restrict__ dq, float* __restrict__ dbias,
                                                                   int bias_ld, float* __restrict__ dpart, int B, int N, int H, float scale,
-                                                                  const AttnDrop drop) {
+                                                                  const AttnDrop drop, int Pn) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* ring = smem;
     char* scratch = smem + A2_NST * A2B_STAGE;
@@ -547,8 +568,10 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
     const int i0 = qt * 32, qi = i0 + ql;
     const int nb = i0 + 32;                                   // rel in [0, i0 + 31]
     const size_t rowbase = (size_t)b * N;
-    const int nkt = min((i0 + 32 + A2_TKV - 1) / A2_TKV, (N + A2_TKV - 1) / A2_TKV);
-    float* dbw = dbl + (size_t)wave * nb;
+    const int off = PFX ? Pn - 1 : 0;                         // PFX: negative-distance bins in front
+    const int kend = PFX && i0 < Pn ? max(i0 + 32, Pn) : i0 + 32;
+    const int nkt = min((kend + A2_TKV - 1) / A2_TKV, (N + A2_TKV - 1) / A2_TKV);
+    float* dbw = dbl + (size_t)wave * (nb + off) + off;      // index rel
 
     {   // additive key mask, all byte loads in flight at once; this wave's d(bias) bins zeroed
         unsigned char mk[8];
@@ -563,7 +586,7 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
             const int j = it * A2_THREADS + threadIdx.x;
             if (j < nkt * A2_TKV) mb[j] = (j < N && mk[it] != 0) ? 0.f : A2_NEG;
         }
-        if (dbias) for (int r = lane; r < nb; r += 64) dbw[r] = 0.f;
+        if (dbias) for (int r = lane - off; r < nb; r += 64) dbw[r] = 0.f;
     }
     __syncthreads();
     // per-lane DMA source offsets: K rows and V rows use the row image, K blocked the blocked image (see A2Stager)
@@ -579,7 +602,7 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
         a2_dma(rsK, st + wave * 1024, (unsigned)(j0 * 128) + stg.koff);
         a2_dma(rsK, st + 8192 + wave * 1024, (unsigned)(j0 * 128) + stg.voff);
         a2_dma(rsV, st + 16384 + wave * 1024, (unsigned)(j0 * 128) + stg.koff);
-        const unsigned w0 = (unsigned)((A2_PAD + i0 - j0 - 64) * 4);
+        const unsigned w0 = (unsigned)((A2_PAD + off + i0 - j0 - 64) * 4);
         if (stg.bias_wave) a2_dma(rsB, st + 24576 + (wave & 3) * 1024, w0 + stg.boff);
         else               a2_dma(rsB, scratch_lds + (wave & 3) * 1024, OOB_OFF);
     };
@@ -634,7 +657,7 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub) {
             const int jb = j0 + 32 * sub;
-            if (jb > i0 + 31) break;
+            if (jb > kend - 1) break;
             f32x16 st, dp;
 #pragma unroll
             for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
@@ -667,7 +690,10 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
                 int d0v = d0;
                 asm volatile("" : "+v"(d0v));             // the selects depend on a value defined inside the branch: hipcc otherwise hoists all 16 of them in front of it
 #pragma unroll
-                for (int r = 0; r < 16; ++r) bpv[r] = (d0v - ((r & 3) + 8 * (r >> 2)) >= 0) ? bpv[r] : A2_NEG;
+                for (int r = 0; r < 16; ++r) {
+                    const int cr = (r & 3) + 8 * (r >> 2);
+                    bpv[r] = (d0v - cr >= 0 || (PFX && qi < Pn && jb + 4 * hi + cr < Pn)) ? bpv[r] : A2_NEG;
+                }
             }
             // element arithmetic on register pairs (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32); the softmax scale is applied once to
             // dQ (dQ = scale dS K) instead of to every dS
@@ -698,7 +724,7 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
                 // wave's private table (every lane owns a distinct bin)
                 const float dsum = diag_sum_32x32(bv, lane);
                 const int rel = (i0 - jb) + (lane - 31);
-                if (rel >= 0 && rel < nb) dbw[rel] += dsum;      // (ds_add_f32 instead of this read-add-write: measured 20 us per layer SLOWER)
+                if (rel >= -off && rel < nb) dbw[rel] += dsum;      // (ds_add_f32 instead of this read-add-write: measured 20 us per layer SLOWER)
             }
             {
                 h16x8 ktf[2][2], dsb[2];
@@ -736,29 +762,53 @@ __global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* _
             const float vv = dbw[r];
             if (vv != 0.f) unsafeAtomicAdd(dbias + (size_t)r * bias_ld + h, vv);
         }
+        if (PFX && i0 < Pn)                                   // negative distances: only query tiles inside the prefix reach them
+            for (int r = lane - off; r < 0; r += 64) {
+                const float vv = dbw[r];
+                if (vv != 0.f) unsafeAtomicAdd(dbias + (ptrdiff_t)r * bias_ld + h, vv);
+            }
     }
+}
+
+static size_t a2_dq_lds(int N, int off) {
+    const int nqt = (N + 31) / 32, npad = (N + 63) / 64 * 64;
+    return (size_t)A2_NST * A2B_STAGE + 4096 + (size_t)npad * 4 + (size_t)8 * (nqt * 32 + off) * 4;
+}
+// the non-causal prefix runs forward and backward on the second-generation kernels (prepared table) iff their plans fit: the dQ kernel's LDS
+// (it grows by the Pn - 1 negative-distance bins), the forward's N <= 4096 and the dK / dV kernel's N >= 32; else on attention.hip's
+bool attn2_prefix_fits(int N, int Pn) {
+    return N >= 32 && N <= 4096 && a2_dq_lds(N, Pn - 1) <= 160 * 1024;
 }
 
 int attn2_bwd_dq_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                         const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dbias, int bias_ld,
-                        float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop) {
-    const int ldT = (A2_PAD + N + 2 * A2_BWIN + 3) / 4 * 4;
+                        float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn) {
+    const int off = Pn > 0 ? Pn - 1 : 0;                       // Pn > 0: the non-causal prefix (PFX instances)
+    const int ldT = (A2_PAD + off + N + 2 * A2_BWIN + 3) / 4 * 4;
     const int nqt = (N + 31) / 32, ny = (H + 7) / 8, npad = (N + 63) / 64 * 64;
-    const size_t lds = (size_t)A2_NST * A2B_STAGE + 4096 + (size_t)npad * 4 + (size_t)8 * (nqt * 32) * 4;
+    const size_t lds = (size_t)A2_NST * A2B_STAGE + 4096 + (size_t)npad * 4 + (size_t)8 * (nqt * 32 + off) * 4;
     if (lds > 160 * 1024 || N > 4096) return 1;                // caller falls back to the first-generation kernel
     static bool a1 = false;
     if (!a1) {
         (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         a1 = true;
     }
     const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
+    if (Pn > 0) {
+        hipLaunchKernelGGL((drop ? attn2_bwd_dq_kernel<true, true> : attn2_bwd_dq_kernel<false, true>), dim3(nqt * ny * B), dim3(A2_THREADS), lds, st,
+                           (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta,
+                           dq, dbias, bias_ld, dpart, B, N, H, scale, drop ? *drop : nd, Pn);
+        return omlm_post_launch("omlm_mqa_attn_bwd_prefix");
+    }
     if (drop)
         hipLaunchKernelGGL(attn2_bwd_dq_kernel<true>, dim3(nqt * ny * B), dim3(A2_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
-                           biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, *drop);
+                           biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, *drop, 0);
     else
         hipLaunchKernelGGL(attn2_bwd_dq_kernel<false>, dim3(nqt * ny * B), dim3(A2_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
-                           biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, nd);
+                           biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, nd, 0);
     return omlm_post_launch("omlm_mqa_attn_bwd");
 }
 
@@ -782,21 +832,24 @@ extern "C" int omlm_attn_bias_prepare(const float* bias, float* biasT, int N, in
     A2PrepGroup grp;
     memset(&grp, 0, sizeof(grp));
     grp.out[0] = biasT; grp.qs[0] = q_scale; grp.ks[0] = k_scale;
-    hipLaunchKernelGGL(attn2_bias_prep_kernel, dim3(H8, 1), dim3(256), 0, as_stream(stream), bias, grp, N, H, bias_ld, ldT,
-                       qk_bound, scale * A2_LOG2E, p_max_log2);
+    hipLaunchKernelGGL(attn2_bias_prep_kernel<false>, dim3(H8, 1), dim3(256), 0, as_stream(stream), bias, grp, N, H, bias_ld, ldT,
+                       qk_bound, scale * A2_LOG2E, p_max_log2, 0);
     return omlm_post_launch("omlm_attn_bias_prepare");
 }
 // The tables of `layers` attention layers over ONE rel-pos table in one launch: biasT[l] (omlm_attn_bias_table_floats(N, H) floats each) from
 // the layer's learned scales q_scale[l] / k_scale[l] (64 floats each; all given, or all NULL with qk_bound as in omlm_attn_bias_prepare).
 // biasT / q_scale / k_scale: HOST arrays of device pointers.
-extern "C" int omlm_attn_bias_prepare_group(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
-                                            const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
-                                            int p_max_log2, void* stream) {
+// the group prepare of both layouts; P >= 1: the non-causal prefix's table (bias: [N + Pn - 1, bias_ld] from its first row)
+static int bias_prepare_group(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
+                              const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
+                              int p_max_log2, int P, void* stream) {
     if (layers <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(biasT && N > 0 && H > 0, "null table / sizes");
     OMLM_CHECK_ARG(p_max_log2 == 0 || p_max_log2 == 15, "p_max_log2: 0 (bf16 / fp32 operands) or 15 (half operands)");
     OMLM_CHECK_ARG((q_scale == nullptr) == (k_scale == nullptr), "q_scale and k_scale: both or neither");
-    const int ldT = (A2_PAD + N + 2 * A2_BWIN + 3) / 4 * 4, H8 = (H + 7) / 8 * 8;
+    const int off = P > 0 ? (P < N ? P : N) - 1 : 0;
+    if (bias && off > 0) bias += (size_t)off * bias_ld;      // the kernel reads rows -off .. N - 1 around the rel = 0 row
+    const int ldT = (A2_PAD + off + N + 2 * A2_BWIN + 3) / 4 * 4, H8 = (H + 7) / 8 * 8;
     for (int base = 0; base < layers; base += A2_PREP_MAX) {
         const int n = layers - base < A2_PREP_MAX ? layers - base : A2_PREP_MAX;
         A2PrepGroup grp;
@@ -807,10 +860,31 @@ extern "C" int omlm_attn_bias_prepare_group(const float* bias, float* const* bia
             grp.qs[l] = q_scale ? q_scale[base + l] : nullptr;
             grp.ks[l] = k_scale ? k_scale[base + l] : nullptr;
         }
-        hipLaunchKernelGGL(attn2_bias_prep_kernel, dim3(H8, n), dim3(256), 0, as_stream(stream), bias, grp, N, H, bias_ld, ldT,
-                           qk_bound, scale * A2_LOG2E, p_max_log2);
+        if (P > 0)
+            hipLaunchKernelGGL(attn2_bias_prep_kernel<true>, dim3(H8, n), dim3(256), 0, as_stream(stream), bias, grp, N, H, bias_ld, ldT,
+                               qk_bound, scale * A2_LOG2E, p_max_log2, off);
+        else
+            hipLaunchKernelGGL(attn2_bias_prep_kernel<false>, dim3(H8, n), dim3(256), 0, as_stream(stream), bias, grp, N, H, bias_ld, ldT,
+                               qk_bound, scale * A2_LOG2E, p_max_log2, 0);
     }
     return omlm_post_launch("omlm_attn_bias_prepare_group");
+}
+extern "C" int omlm_attn_bias_prepare_group(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
+                                            const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
+                                            int p_max_log2, void* stream) {
+    return bias_prepare_group(bias, biasT, layers, N, H, bias_ld, q_scale, k_scale, qk_bound, scale, p_max_log2, 0, stream);
+}
+// non-causal prefix of P >= 1 rows: tables of omlm_attn_bias_table_floats_prefix(N, H, P) floats from the [N + min(P, N) - 1, bias_ld] table
+extern "C" long long omlm_attn_bias_table_floats_prefix(int N, int H, int P) {
+    const int off = P > 0 ? (P < N ? P : N) - 1 : 0;
+    const int ldT = (A2_PAD + off + N + 2 * A2_BWIN + 3) / 4 * 4, H8 = (H + 7) / 8 * 8;
+    return (long long)H8 * ldT;
+}
+extern "C" int omlm_attn_bias_prepare_group_prefix(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
+                                                   const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
+                                                   int p_max_log2, int P, void* stream) {
+    OMLM_CHECK_ARG(P >= 1, "prefix rows P >= 1 (P = 0: omlm_attn_bias_prepare_group)");
+    return bias_prepare_group(bias, biasT, layers, N, H, bias_ld, q_scale, k_scale, qk_bound, scale, p_max_log2, P, stream);
 }
 
 // d(bias) partial rows -> the [N, bias_ld] table.  The dQ kernels leave one fp32 row of nqt*32 bins per (sample, head, query tile) in
@@ -929,8 +1003,8 @@ extern "C" int omlm_dropout_residual_bwd(const float* dx1, void* dy, long long M
 
 // bf16 forward.  biasT from omlm_attn_bias_prepare (or null: no bias).
 int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
-                     void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop) {
-    const int ldT = (A2_PAD + N + 2 * A2_BWIN + 3) / 4 * 4;
+                     void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn) {
+    const int ldT = (A2_PAD + (Pn > 0 ? Pn - 1 : 0) + N + 2 * A2_BWIN + 3) / 4 * 4;
     if (N > 64 * 64) { omlm_set_error("attention: N > 4096 keys per sample is not supported (liveness prologue covers 4096 keys)"); return OMLM_ERR_UNSUPPORTED; }
     const int nqt = (N + 31) / 32, ny = (H + 7) / 8;
     const size_t lds = (size_t)A2_NST * A2_STAGE + (size_t)((N + 63) / 64 * 64) * 2 + 64 * 8 + 128;
@@ -940,22 +1014,36 @@ int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* b
         (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         a4 = true;
+    }
+    const AttnDrop nd0 = {0ull, nullptr, 0u, 1.0f};
+    if (Pn > 0) {                                              // the non-causal prefix: the PFX instances of both softmax forms
+        const AttnDrop& dr = drop ? *drop : nd0;
+        if (biasT) hipLaunchKernelGGL((drop ? attn4_fwd_kernel<true, true, true> : attn4_fwd_kernel<true, false, true>), dim3(nqt * ny * B),
+                                      dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask,
+                                      (h16_t*)out, lse, B, N, H, scale, dr, Pn);
+        hipLaunchKernelGGL((drop ? attn4_fwd_kernel<false, true, true> : attn4_fwd_kernel<false, false, true>), dim3(nqt * ny * B), dim3(A4_THREADS),
+                           lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, dr, Pn);
+        return omlm_post_launch("omlm_mqa_attn_fwd_prefix");
     }
     // both softmax forms: the one the table's flag does not name returns at its first instruction (no table: online only)
     const dim3 grid(nqt * ny * B);
     if (drop) {
         if (biasT) hipLaunchKernelGGL((attn4_fwd_kernel<true, true>), grid, dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k,
-                                      (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, *drop);
+                                      (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, *drop, 0);
         hipLaunchKernelGGL((attn4_fwd_kernel<false, true>), grid, dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
-                           biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, *drop);
+                           biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, *drop, 0);
         return omlm_post_launch("omlm_mqa_attn_fwd");
     }
     const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
     if (biasT) hipLaunchKernelGGL(attn4_fwd_kernel<true>, dim3(nqt * ny * B), dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k,
-                                  (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, nd);
+                                  (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, nd, 0);
     hipLaunchKernelGGL(attn4_fwd_kernel<false>, dim3(nqt * ny * B), dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
-                       biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, nd);
+                       biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, nd, 0);
     return omlm_post_launch("omlm_mqa_attn_fwd");
 }
 

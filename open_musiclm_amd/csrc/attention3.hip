@@ -82,13 +82,17 @@ __device__ __forceinline__ void a3_dma4(const void* gsrc, unsigned lds_dst) {
 #ifndef A3_WAVES
 #define A3_WAVES 2                     /* waves per SIMD the register allocation aims at */
 #endif
-template <bool DROP = false>
+// PFX: the non-causal prefix of Pn = min(P, N) rows.  A key range r with 128 r < Pn walks the query tiles from 0 instead of 4 r (its chunks
+// are counted by a3_range_start in the launch's work split too); items above the diagonal keep (i, j) iff i, j < Pn; the prepared table
+// holds off = Pn - 1 negative distances in front of the causal layout, so every window offset moves by off.
+__device__ __host__ __forceinline__ int a3_range_start(int r, int Pn) { return 128 * r < Pn ? 0 : 4 * r; }
+template <bool DROP = false, bool PFX = false>
 __global__ __launch_bounds__(A3_T) __attribute__((amdgpu_waves_per_eu(A3_WAVES)))
 void attn3_bwd_dkv_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__ k, const h16_t* __restrict__ v,
                           const unsigned char* __restrict__ keymask, const h16_t* __restrict__ dout,
                           const float* __restrict__ lse, const float* __restrict__ delta, float* __restrict__ dk, float* __restrict__ dv,
                           const float* __restrict__ biasT, int ldT, int B, int N, int H, float scale, int CH, int wg_per_sample,
-                          const AttnDrop drop) {
+                          const AttnDrop drop, int Pn) {
     extern __shared__ __attribute__((aligned(16))) char smem3[];
     const int lane = threadIdx.x & 63, hi = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -104,11 +108,12 @@ void attn3_bwd_dkv_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__
     const int b = lg / wg_per_sample;
     int rem = lg - b * wg_per_sample, r = 0, chunk = 0;
     for (;; ++r) {                                            // uniform scalar scan: which key range this workgroup belongs to
-        const int nch = (nqt - 4 * r + CH - 1) / CH;
+        const int nch = (nqt - (PFX ? a3_range_start(r, Pn) : 4 * r) + CH - 1) / CH;
         if (rem < nch) { chunk = rem; break; }
         rem -= nch;
     }
-    const int it0 = 4 * r + chunk * CH, it1 = min(nqt, it0 + CH);
+    const int it0 = (PFX ? a3_range_start(r, Pn) : 4 * r) + chunk * CH, it1 = min(nqt, it0 + CH);
+    const int off = PFX ? Pn - 1 : 0;
     const int nitems = (it1 - it0) * H;
     const int j0w = r * A3_KR + 32 * wave;                    // this wave's 32 keys
     const int jtw = 4 * r + wave;                             // ... as a 32-key tile index
@@ -154,7 +159,7 @@ void attn3_bwd_dkv_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__
         qoff = (unsigned)((((int)rowbase + qi) * H) * 64 + colu) * 2u;
         // lanes 0-15: the bias window for this wave's keys, table index A3_PAD + rel - 1 from rel = 32 (it - jtw) - 31 (one entry early:
         // 16-byte aligned); lane 16: the row's tail [.., flag, m_h]; the other lanes repeat lane 16's address
-        const int w0 = max(A3_PAD + 32 * (it - jtw) - 32, 0);
+        const int w0 = max(A3_PAD + off + 32 * (it - jtw) - 32, 0);
         boff = has_bias ? (unsigned)(lane < 16 ? w0 + 4 * lane : ldT - 4) * 4u : 0u;
         ldp = (hi ? delta : lse) + ((size_t)b * H * N + min(32 * it + (lane & 31), N - 1));
     };
@@ -190,7 +195,7 @@ void attn3_bwd_dkv_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__
         __builtin_amdgcn_s_barrier();
         if (item + 2 < nitems) issue_next();
         const int i0 = 32 * it;
-        if (i0 + 31 < j0w) continue;                          // every query of the tile precedes every key of this wave (causal): nothing to do
+        if (i0 + 31 < j0w && !(PFX && i0 < Pn && j0w < Pn)) continue;      // every query of the tile precedes every key of this wave (causal): nothing to do
         const char* Qs = smem3 + stage * A3_STAGE;
         const char* dOs = Qs + A3_IMG;
         const float* axa = (const float*)(Qs + 2 * A3_IMG + wave * A3_AUX);
@@ -239,7 +244,7 @@ void attn3_bwd_dkv_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__
 #pragma unroll
             for (int rr = 0; rr < 16; ++rr) {
                 const int i = i0 + a3_crow(rr, hi);
-                bvv[rr] = (i >= kjv && i < N) ? bvv[rr] : A3_NEG;
+                bvv[rr] = ((i >= kjv || (PFX && i < Pn && kjv < Pn)) && i < N) ? bvv[rr] : A3_NEG;
             }
         }
         // DROP: the lane's key part of the row keys, rows i0 + 4 hi + cr (cr = crow(rr, hi) - 4 hi: bits disjoint from i0 and 4 hi)
@@ -312,18 +317,21 @@ static int a3_chunk(int B, int N) {
 // is not served (caller falls back to the second-generation kernel).
 int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                          const void* dout, const float* lse, const float* delta, float* dk, float* dv,
-                         int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop) {
+                         int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn) {
     if (N < 32 || (long long)B * N * H * 128 >= (1ll << 32)) return 1;      // (32-bit byte offsets into q / dout)
-    const int ldT = ((A3_PAD + N + 2 * 128 + 3) / 4) * 4;    // layout of omlm_attn_bias_prepare (attention2.hip)
+    const int off = Pn > 0 ? Pn - 1 : 0;                       // Pn > 0: the non-causal prefix (PFX instances)
+    const int ldT = ((A3_PAD + off + N + 2 * 128 + 3) / 4) * 4;    // layout of omlm_attn_bias_prepare (attention2.hip)
     const int CH = a3_chunk(B, N);
     const int nqt = (N + 31) / 32, nr = (N + A3_KR - 1) / A3_KR;
     int wps = 0;
-    for (int r = 0; r < nr; ++r) wps += (nqt - 4 * r + CH - 1) / CH;
+    for (int r = 0; r < nr; ++r) wps += (nqt - (Pn > 0 ? a3_range_start(r, Pn) : 4 * r) + CH - 1) / CH;
     const size_t lds = (size_t)A3_NST * A3_STAGE;             // 48 KiB (the final transposes reuse it: 4 x 8448 B)
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr = true;
     }
     // Zero fill by a KERNEL of this library, not hipMemsetAsync: as a memset node of a captured micro-step the fill detached everything
@@ -339,12 +347,18 @@ int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const floa
     if (dv == dk + gfloats) fill(dk, 2 * gfloats);            // one allocation (the host's usual case): one fill launch instead of two
     else { fill(dk, gfloats); fill(dv, gfloats); }
     const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
+    if (Pn > 0) {
+        hipLaunchKernelGGL((drop ? attn3_bwd_dkv_kernel<true, true> : attn3_bwd_dkv_kernel<false, true>), dim3(B * wps), dim3(A3_T), lds, st,
+                           (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask, (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H,
+                           scale, CH, wps, drop ? *drop : nd, Pn);
+        return omlm_post_launch("omlm_mqa_attn_bwd_prefix");
+    }
     if (drop)
         hipLaunchKernelGGL(attn3_bwd_dkv_kernel<true>, dim3(B * wps), dim3(A3_T), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask,
-                           (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps, *drop);
+                           (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps, *drop, 0);
     else
         hipLaunchKernelGGL(attn3_bwd_dkv_kernel<false>, dim3(B * wps), dim3(A3_T), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask,
-                           (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps, nd);
+                           (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps, nd, 0);
     return omlm_post_launch("omlm_mqa_attn_bwd");
 }
 

@@ -359,13 +359,13 @@ extern "C" int omlm_cast_pad(const float* src, void* dst, long long R, int C, in
 
 // ---------------------------------------------------------------------------------------------------------
 // rel-pos MLP helpers (reference transformer.py:36-67): SiLU layers.  pre = a + bias is saved for the backward.
-//   first layer (Linear(1, Hd)): a[r, c] = r * w0[c]
+//   first layer (Linear(1, Hd)): a[r, c] = (x0 + r) * w0[c]; row r is the distance x0 + r (x0 < 0: the non-causal prefix's rows)
 __global__ void relpos_first_kernel(const float* __restrict__ w0, const float* __restrict__ b0, float* __restrict__ pre,
-                                    float* __restrict__ z, int n, int Hd) {
+                                    float* __restrict__ z, int n, int Hd, int x0) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long long)n * Hd) return;
     const int r = (int)(i / Hd), c = (int)(i % Hd);
-    const float s = (float)r * w0[c] + b0[c];
+    const float s = (float)(x0 + r) * w0[c] + b0[c];
     pre[i] = s;
     z[i] = s / (1.0f + __expf(-s));
 }
@@ -391,23 +391,27 @@ __global__ void bias_add_kernel(const float* __restrict__ a, const float* __rest
     const int c = (int)(i % ld);
     out[i] = c < C ? a[i] + b[c] : 0.f;
 }
-// dw0[c] += sum_r r * ds[r, c]   (first-layer weight gradient).  64 columns x 4 row lanes per workgroup, 16 row chunks in grid.y:
+// dw0[c] += sum_r (x0 + r) * ds[r, c]   (first-layer weight gradient).  64 columns x 4 row lanes per workgroup, 16 row chunks in grid.y:
 // the first version walked all n rows with ONE thread per column (2 workgroups, 1116 dependent loads: 201 us per step).
-__global__ __launch_bounds__(256) void relpos_first_bwd_kernel(const float* __restrict__ ds, float* __restrict__ dw0, int n, int Hd) {
+__global__ __launch_bounds__(256) void relpos_first_bwd_kernel(const float* __restrict__ ds, float* __restrict__ dw0, int n, int Hd, int x0) {
     __shared__ float red[4][64];
     const int c = blockIdx.x * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
     float s = 0.f;
-    if (c < Hd) for (int r = blockIdx.y * 4 + rl; r < n; r += 4 * gridDim.y) s += (float)r * ds[(size_t)r * Hd + c];
+    if (c < Hd) for (int r = blockIdx.y * 4 + rl; r < n; r += 4 * gridDim.y) s += (float)(x0 + r) * ds[(size_t)r * Hd + c];
     red[rl][threadIdx.x & 63] = s;
     __syncthreads();
     if (rl == 0 && c < Hd) unsafeAtomicAdd(dw0 + c, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-extern "C" int omlm_relpos_first_fwd(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, void* stream) {
+// rows = distances x0 .. x0 + n - 1 (omlm_relpos_first_fwd: x0 = 0)
+extern "C" int omlm_relpos_first_fwd_from(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, int x0, void* stream) {
     OMLM_CHECK_ARG(w0 && b0 && pre && z && n > 0 && Hd > 0, "relpos_first arguments");
     const long long tot = (long long)n * Hd;
-    hipLaunchKernelGGL(relpos_first_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, as_stream(stream), w0, b0, pre, z, n, Hd);
+    hipLaunchKernelGGL(relpos_first_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, as_stream(stream), w0, b0, pre, z, n, Hd, x0);
     return omlm_post_launch("omlm_relpos_first_fwd");
+}
+extern "C" int omlm_relpos_first_fwd(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, void* stream) {
+    return omlm_relpos_first_fwd_from(w0, b0, pre, z, n, Hd, 0, stream);
 }
 extern "C" int omlm_bias_silu_fwd(const float* a, const float* b, float* pre, float* z, long long R, int C, void* stream) {
     OMLM_CHECK_ARG(a && b && pre && z && R > 0 && C > 0, "bias_silu arguments");
@@ -426,10 +430,13 @@ extern "C" int omlm_bias_add(const float* a, const float* b, float* out, int R, 
     hipLaunchKernelGGL(bias_add_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, as_stream(stream), a, b, out, R, C, ld);
     return omlm_post_launch("omlm_bias_add");
 }
-extern "C" int omlm_relpos_first_bwd(const float* ds, float* dw0, int n, int Hd, void* stream) {
+extern "C" int omlm_relpos_first_bwd_from(const float* ds, float* dw0, int n, int Hd, int x0, void* stream) {
     OMLM_CHECK_ARG(ds && dw0 && n > 0 && Hd > 0, "relpos_first_bwd arguments");
-    hipLaunchKernelGGL(relpos_first_bwd_kernel, dim3((Hd + 63) / 64, 16), dim3(256), 0, as_stream(stream), ds, dw0, n, Hd);
+    hipLaunchKernelGGL(relpos_first_bwd_kernel, dim3((Hd + 63) / 64, 16), dim3(256), 0, as_stream(stream), ds, dw0, n, Hd, x0);
     return omlm_post_launch("omlm_relpos_first_bwd");
+}
+extern "C" int omlm_relpos_first_bwd(const float* ds, float* dw0, int n, int Hd, void* stream) {
+    return omlm_relpos_first_bwd_from(ds, dw0, n, Hd, 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -455,6 +462,7 @@ struct relpos_mlp_params {
     float *ds0, *ds1, *ds2;                                  // backward scratch [n, Hd]: d(pre) of layers 0 .. 2
     float *gw0, *gb0, *gW1, *gb1, *gW2, *gb2, *gW3, *gb3;    // gradient buffers (accumulated into)
     int n, Hd, H, ldb;
+    int x0;                                                  // distance of row 0 (0, or -(P' - 1) for a non-causal prefix of P' rows)
 };
 __device__ __forceinline__ float silu_f(float s) { return s / (1.0f + __expf(-s)); }
 __device__ __forceinline__ float silu_grad_f(float s) { const float sg = 1.0f / (1.0f + __expf(-s)); return sg * (1.0f + s * (1.0f - sg)); }
@@ -472,7 +480,7 @@ __global__ __launch_bounds__(256) void relpos_mlp_fwd_kernel(relpos_mlp_params a
     const int colbase = wave * (HD / 4);
     for (int e = t; e < RP_RB * HD; e += 256) {
         const int r = e / HD, c = e - r * HD, row = r0 + r;
-        const float s = (float)row * a.w0[c] + a.b0[c], z = silu_f(s);
+        const float s = (float)(a.x0 + row) * a.w0[c] + a.b0[c], z = silu_f(s);
         zA[r * ZP + c] = z;
         if (a.pre0 && row < a.n) { a.pre0[(size_t)row * HD + c] = s; a.z0[(size_t)row * HD + c] = z; }
     }
@@ -737,7 +745,7 @@ __global__ __launch_bounds__(256) void relpos_mlp_bwd_params_kernel(relpos_mlp_p
         return;
     }
     b -= TPD;
-    {   // gw0[c] += sum_r r ds0[r][c]; gb0[c] += sum_r ds0[r][c]: 64 columns per workgroup, rows 64 at a time, four row lanes combined in a
+    {   // gw0[c] += sum_r (x0 + r) ds0[r][c]; gb0[c] += sum_r ds0[r][c]: 64 columns per workgroup, rows 64 at a time, four row lanes combined in a
         // fixed order
         float* red = sd;                                     // [2][4][64]
         const int c0 = b * 64, cx = t & 63, rl = t >> 6;
@@ -747,7 +755,7 @@ __global__ __launch_bounds__(256) void relpos_mlp_bwd_params_kernel(relpos_mlp_p
 #pragma unroll
             for (int i = 0; i < 16; ++i) { const int row = r0 + rl + 4 * i; v[i] = row < a.n ? a.ds0[(size_t)row * Hd + c0 + cx] : 0.f; }
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { sw = fmaf((float)(r0 + rl + 4 * i), v[i], sw); sb += v[i]; }
+            for (int i = 0; i < 16; ++i) { sw = fmaf((float)(a.x0 + r0 + rl + 4 * i), v[i], sw); sb += v[i]; }
         }
         red[rl * 64 + cx] = sw; red[256 + rl * 64 + cx] = sb;
         __syncthreads();
@@ -758,9 +766,10 @@ __global__ __launch_bounds__(256) void relpos_mlp_bwd_params_kernel(relpos_mlp_p
     }
 }
 
-extern "C" int omlm_relpos_mlp_fwd(const float* w0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
-                                   const float* W3, const float* b3, float* pre0, float* z0, float* pre1, float* z1, float* pre2, float* z2,
-                                   float* table, int n, int Hd, int H, int ldb, void* stream) {
+// rows = distances x0 .. x0 + n - 1 (omlm_relpos_mlp_fwd: x0 = 0)
+extern "C" int omlm_relpos_mlp_fwd_from(const float* w0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
+                                        const float* W3, const float* b3, float* pre0, float* z0, float* pre1, float* z1, float* pre2, float* z2,
+                                        float* table, int n, int Hd, int H, int ldb, int x0, void* stream) {
     OMLM_CHECK_ARG(w0 && b0 && W1 && b1 && W2 && b2 && W3 && b3 && table && n > 0, "relpos_mlp_fwd: null argument");
     OMLM_CHECK_ARG((Hd == 256 || Hd == 512) && H >= 1 && H <= 16 && ldb >= H && ldb <= 16, "relpos_mlp_fwd: Hd must be 256 or 512, H <= 16");
     OMLM_CHECK_ARG(!pre0 || (z0 && pre1 && z1 && pre2 && z2), "relpos_mlp_fwd: save buffers come all or none");
@@ -768,6 +777,7 @@ extern "C" int omlm_relpos_mlp_fwd(const float* w0, const float* b0, const float
     memset(&a, 0, sizeof(a));
     a.w0 = w0; a.b0 = b0; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.W3 = W3; a.b3 = b3;
     a.pre0 = pre0; a.z0 = z0; a.pre1 = pre1; a.z1 = z1; a.pre2 = pre2; a.z2 = z2; a.table = table; a.n = n; a.Hd = Hd; a.H = H; a.ldb = ldb;
+    a.x0 = x0;
     const size_t lds = (size_t)(2 * RP_RB * (Hd + 4) + Hd * 36) * sizeof(float);
     static bool attr = false;
     if (!attr) {
@@ -780,11 +790,17 @@ extern "C" int omlm_relpos_mlp_fwd(const float* w0, const float* b0, const float
     else           hipLaunchKernelGGL(relpos_mlp_fwd_kernel<256>, grid, dim3(256), lds, as_stream(stream), a);
     return omlm_post_launch("omlm_relpos_mlp_fwd");
 }
+extern "C" int omlm_relpos_mlp_fwd(const float* w0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
+                                   const float* W3, const float* b3, float* pre0, float* z0, float* pre1, float* z1, float* pre2, float* z2,
+                                   float* table, int n, int Hd, int H, int ldb, void* stream) {
+    return omlm_relpos_mlp_fwd_from(w0, b0, W1, b1, W2, b2, W3, b3, pre0, z0, pre1, z1, pre2, z2, table, n, Hd, H, ldb, 0, stream);
+}
 
 // scratch: 3 * n * Hd floats (ds0 | ds1 | ds2).  Gradients are ACCUMULATED into g* (fp32, the optimizer's flat buffer views).
-extern "C" int omlm_relpos_mlp_bwd(const float* dtable, const float* W1, const float* W2, const float* W3, const float* pre0, const float* z0,
-                                   const float* pre1, const float* z1, const float* pre2, const float* z2, float* scratch, float* gw0, float* gb0,
-                                   float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, void* stream) {
+extern "C" int omlm_relpos_mlp_bwd_from(const float* dtable, const float* W1, const float* W2, const float* W3, const float* pre0, const float* z0,
+                                        const float* pre1, const float* z1, const float* pre2, const float* z2, float* scratch, float* gw0, float* gb0,
+                                        float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, int x0,
+                                        void* stream) {
     OMLM_CHECK_ARG(dtable && W1 && W2 && W3 && pre0 && z0 && pre1 && z1 && pre2 && z2 && scratch && gw0 && gb0 && gW1 && gb1 && gW2 && gb2 && gW3 && gb3 && n > 0,
                    "relpos_mlp_bwd: null argument");
     OMLM_CHECK_ARG((Hd == 256 || Hd == 512) && H >= 1 && H <= 16 && ldb >= H && ldb <= 16, "relpos_mlp_bwd: Hd must be 256 or 512, H <= 16");
@@ -793,6 +809,7 @@ extern "C" int omlm_relpos_mlp_bwd(const float* dtable, const float* W1, const f
     a.W1 = W1; a.W2 = W2; a.W3 = W3; a.pre0 = (float*)pre0; a.z0 = (float*)z0; a.pre1 = (float*)pre1; a.z1 = (float*)z1; a.pre2 = (float*)pre2; a.z2 = (float*)z2;
     a.dtable = dtable; a.ds0 = scratch; a.ds1 = scratch + (size_t)n * Hd; a.ds2 = scratch + 2 * (size_t)n * Hd;
     a.gw0 = gw0; a.gb0 = gb0; a.gW1 = gW1; a.gb1 = gb1; a.gW2 = gW2; a.gb2 = gb2; a.gW3 = gW3; a.gb3 = gb3; a.n = n; a.Hd = Hd; a.H = H; a.ldb = ldb;
+    a.x0 = x0;
     const size_t lds = (size_t)(2 * RP_RB * (Hd + 4) + 32 * (Hd + 16) + 256) * sizeof(float);
     static bool attr = false;
     if (!attr) {
@@ -808,6 +825,12 @@ extern "C" int omlm_relpos_mlp_bwd(const float* dtable, const float* W1, const f
     const int tpd = Hd / 64;
     hipLaunchKernelGGL(relpos_mlp_bwd_params_kernel, dim3(2 * tpd * tpd + 2 * tpd), dim3(256), 0, as_stream(stream), a);
     return omlm_post_launch("omlm_relpos_mlp_bwd (parameters)");
+}
+extern "C" int omlm_relpos_mlp_bwd(const float* dtable, const float* W1, const float* W2, const float* W3, const float* pre0, const float* z0,
+                                   const float* pre1, const float* z1, const float* pre2, const float* z2, float* scratch, float* gw0, float* gb0,
+                                   float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, void* stream) {
+    return omlm_relpos_mlp_bwd_from(dtable, W1, W2, W3, pre0, z0, pre1, z1, pre2, z2, scratch, gw0, gb0, gW1, gb1, gW2, gb2, gW3, gb3, n, Hd, H,
+                                    ldb, 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -83,19 +83,24 @@ def max_batch(model, precision: str) -> int:
     return max(0, min(MAX_DECODE_BATCH, (_LDS_BYTES - 1024) // (4 * max(Fp, 1))))
 
 
-def supports(model, batch: int, precision: Optional[str] = None) -> bool:
-    """Whether CachedDecoder (omlm_decode_step) serves `batch` samples of this model; where it does not, generate() re-runs the forward."""
+def supports(model, batch: int, precision: Optional[str] = None, prompt_rows: Optional[int] = None) -> bool:
+    """Whether CachedDecoder (omlm_decode_step) serves `batch` samples of this model; where it does not, generate() re-runs the forward.
+    A non-causal prefix of P rows is served only when the prompt holds all of it (prompt_rows >= P): a row i >= P sees the keys j <= i
+    alone, so the cached rows never change -- a row generated inside the prefix would change the rows before it."""
     tr = model.transformer
     limit = max_batch(model, precision) if precision is not None else min(MAX_DECODE_BATCH, max_batch(model, "bf16x3"))
-    return 1 <= batch <= limit and tr.non_causal_prefix_size == 0 and 1 <= tr.heads <= MAX_DECODE_HEADS
+    P = engine.prefix_rows(tr)
+    prefix_ok = P == 0 or (prompt_rows is not None and P <= prompt_rows)
+    return 1 <= batch <= limit and prefix_ok and 1 <= tr.heads <= MAX_DECODE_HEADS
 
 
 class CachedDecoder:
     def __init__(self, model, batch: int, max_rows: int, precision: str):
-        if not supports(model, batch, precision):
+        # (a non-causal prefix is checked against the prompt in prefill)
+        if not supports(model, batch, precision, prompt_rows=engine.prefix_rows(model.transformer)):
             tr = model.transformer
             raise ValueError(f"cached decode does not serve this model with {batch} samples per call (at most {max_batch(model, precision)} "
-                             f"samples, at most {MAX_DECODE_HEADS} heads, no non-causal prefix; got {tr.heads} heads)")
+                             f"samples, at most {MAX_DECODE_HEADS} heads; got {tr.heads} heads)")
         self.model, self.B, self.Nmax, self.precision = model, batch, int(max_rows), precision
         tr = model.transformer
         dev = model.start_tokens[0].device
@@ -190,6 +195,9 @@ class CachedDecoder:
         ids32, lens = engine.build_ids(model, all_token_ids)
         B, N = ids32.shape
         assert B == self.B and N <= self.Nmax, (B, N, self.B, self.Nmax)
+        P = engine.prefix_rows(tr)
+        if N < P:
+            raise ValueError(f"cached decode of a model with a non-causal prefix of {P} rows needs them all in the prompt; got {N} rows")
         lay = engine.get_layout(model, B, lens, ids32.device, True)
         x = engine.embed_forward(model, ids32, lay)
         y, saved = engine.trunk_forward(tr, self.pw, x, None, B, N, True, False, keep_h1_lo_tail=self.planes)

@@ -378,7 +378,7 @@ class RelposStepCache:
         """Start of an optimizer step: the table of the CURRENT weights into the persistent buffer, d(table) cleared."""
         if not self.enabled or self.n is None:
             return
-        table, saved = relpos_forward(self.tr, self.n, True)
+        table, saved = relpos_forward(self.tr, self.n, True, prefix_rows(self.tr))
         self.table.copy_(table)
         self.saved = saved
         self.dtable.zero_()
@@ -399,33 +399,49 @@ def relpos_step_cache(tr) -> "RelposStepCache":
     return c
 
 
-def relpos_forward(tr, n: int, save: bool):
+def prefix_rows(tr) -> int:
+    """The non-causal prefix P of the model's self-attention (0: causal)."""
+    return int(getattr(tr, "non_causal_prefix_size", 0) or 0)
+
+
+def relpos_rows(n: int, P: int = 0) -> Tuple[int, int]:
+    """(rows, x0) of the rel-pos table of an n-row sequence with a non-causal prefix of P rows: rows x0 .. n - 1 of distance i - j, where
+    x0 = -(min(P, n) - 1) <= 0 -- the table's row x - x0 holds distance x (include/omlm.h, omlm_mqa_attn_fwd_prefix)."""
+    x0 = -(min(P, n) - 1) if P > 0 else 0
+    return n - x0, x0
+
+
+def relpos_forward(tr, n: int, save: bool, P: int = 0):
+    """The rel-pos table [rows, ceil8(H)] fp32 over the distances x0 .. n - 1 (relpos_rows; P = 0: 0 .. n - 1)."""
     rp = tr.rel_pos_bias
     if rp is None:
         return None, None
     H = tr.heads
     ldb = ceil_to(H, 8)
     dev = tr.norm.gamma.device
+    rows, x0 = relpos_rows(n, P)
     if tr.relative_position_bias_type == "t5":
         # 32-bucket embedding lookup (transformer.py:85-117); tiny, index plumbing done with torch
         from .transformer import t5_bucket_of_distance
-        bucket = t5_bucket_of_distance(torch.arange(n, device=dev), rp.num_buckets, rp.max_distance)
-        table = torch.zeros(n, ldb, device=dev, dtype=torch.float32)
+        bucket = t5_bucket_of_distance(torch.arange(x0, n, device=dev), rp.num_buckets, rp.max_distance)
+        table = torch.zeros(rows, ldb, device=dev, dtype=torch.float32)
         table[:, :H] = rp.relative_attention_bias.weight.detach()[bucket]
         return table, ("t5", bucket)
     lin = [rp.net[0][0], rp.net[1][0], rp.net[2][0], rp.net[3]]
     Hd = lin[0].weight.shape[0]
     if Hd in (256, 512) and H <= 16 and len(rp.net) == 4:
         # one launch for the whole MLP (csrc/optim_misc.hip relpos_mlp_fwd_kernel; round 5): a workgroup carries 8 rows through all layers
-        saves = [torch.empty(n, Hd, device=dev) for _ in range(6)] if save else None
-        table = torch.empty(n, ldb, device=dev)
+        saves = [torch.empty(rows, Hd, device=dev) for _ in range(6)] if save else None
+        table = torch.empty(rows, ldb, device=dev)
         ops.relpos_mlp_fwd(lin[0].weight.detach().reshape(-1), lin[0].bias.detach(), lin[1].weight.detach(), lin[1].bias.detach(),
-                           lin[2].weight.detach(), lin[2].bias.detach(), lin[3].weight.detach(), lin[3].bias.detach(), saves, table, n, Hd, H, ldb)
+                           lin[2].weight.detach(), lin[2].bias.detach(), lin[3].weight.detach(), lin[3].bias.detach(), saves, table, rows, Hd, H, ldb,
+                           x0=x0)
         return table, (("mlp_fused", saves) if save else None)
+    n = rows                                    # (below: one row per distance x0 .. x0 + rows - 1)
     pres, zs = [], []
     pre = torch.empty(n, Hd, device=dev)
     z = torch.empty(n, Hd, device=dev)
-    ops.relpos_first_fwd(lin[0].weight.detach().reshape(-1), lin[0].bias.detach(), pre, z, n, Hd)
+    ops.relpos_first_fwd(lin[0].weight.detach().reshape(-1), lin[0].bias.detach(), pre, z, n, Hd, x0=x0)
     pres.append(pre); zs.append(z)
     for k in (1, 2):
         # (the FORWARD GEMMs stay unsplit: a split-K sum is order-of-arrival, and 1e-7 of noise in the table is amplified by the 16-bit
@@ -444,11 +460,13 @@ def relpos_forward(tr, n: int, save: bool):
 
 
 def relpos_backward(tr, n: int, saved, dtable: torch.Tensor):
-    """dtable: [n, ldb] fp32 gradient of the bias table."""
+    """dtable: [rows, ldb] fp32 gradient of the bias table; rows = n + min(P, n) - 1 with a non-causal prefix (relpos_rows)."""
     rp = tr.rel_pos_bias
     H = tr.heads
     ldb = dtable.shape[-1]
     dev = dtable.device
+    x0 = n - dtable.shape[0]
+    n = dtable.shape[0]
     if saved[0] == "t5":
         g = grad_of(rp.relative_attention_bias.weight)
         g.index_add_(0, saved[1], dtable[:, :H])
@@ -459,7 +477,8 @@ def relpos_backward(tr, n: int, saved, dtable: torch.Tensor):
         scratch = torch.empty(3 * n * Hd, device=dev)
         grads = [grad_of(lin[0].weight).view(-1), grad_of(lin[0].bias), grad_of(lin[1].weight), grad_of(lin[1].bias),
                  grad_of(lin[2].weight), grad_of(lin[2].bias), grad_of(lin[3].weight), grad_of(lin[3].bias)]
-        ops.relpos_mlp_bwd(dtable, lin[1].weight.detach(), lin[2].weight.detach(), lin[3].weight.detach(), saved[1], scratch, grads, n, Hd, H, ldb)
+        ops.relpos_mlp_bwd(dtable, lin[1].weight.detach(), lin[2].weight.detach(), lin[3].weight.detach(), saved[1], scratch, grads, n, Hd, H, ldb,
+                           x0=x0)
         return
     _, pres, zs = saved
     # last layer: table = z2 @ W3^T + b3
@@ -479,7 +498,7 @@ def relpos_backward(tr, n: int, saved, dtable: torch.Tensor):
     ds = torch.empty(n, Hd, device=dev)
     ops.silu_bwd(dz, pres[0], ds, n * Hd)
     ops.colsum_accumulate(ds, grad_of(lin[0].bias), n, Hd, Hd)
-    ops.relpos_first_bwd(ds, grad_of(lin[0].weight).view(-1), n, Hd)
+    ops.relpos_first_bwd(ds, grad_of(lin[0].weight).view(-1), n, Hd, x0=x0)
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -540,11 +559,12 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
     dev = x.device
     M, D = x.shape
     H = tr.heads
+    P = prefix_rows(tr)                                           # non-causal prefix: its own attention entries and a table over x0 .. N - 1
     rc = tr.__dict__.get("_omlm_relpos_cache")
     if rc is not None and save and training and rc.usable(N):
         table, rp_saved = rc.table, ("cached", rc)                # (RelposStepCache: computed once for this optimizer step)
     else:
-        table, rp_saved = relpos_forward(tr, N, save)
+        table, rp_saved = relpos_forward(tr, N, save, P)
         # the FIRST training forward is adopted, once: a captured micro-step holds the addresses of the cache's buffers, so they are
         # never replaced (a stale cache -- validation between two optimizer steps -- computes in line and leaves the cache alone)
         if (rc is not None and rc.enabled and rc.n is None and save and training and rp_saved is not None and rp_saved[0] != "t5"
@@ -591,12 +611,15 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
         # learned scales, and a launch per layer was six 14-us latency chains per step)
         if abiases is None:
             abiases = ops.AttnBias.group(table, N, H, dev, [a_.q_scale.detach() for a_, _, _ in tr.layers],
-                                         [a_.k_scale.detach() for a_, _, _ in tr.layers], scale=ATTN_SCALE, half=T == torch.float16)
+                                         [a_.k_scale.detach() for a_, _, _ in tr.layers], scale=ATTN_SCALE, half=T == torch.float16, P=P)
         abias = abiases[li]
         pa, po = aps[li]
         sa = aseeds[li] if pa > 0 else 0
         so = oseeds[li] if po > 0 else 0
-        ops.attn_fwd(q, k, v, abias, keymask, o, lse, B, N, H, ATTN_SCALE, p=pa, seed=sa, seed_dev=salt if pa > 0 else None)
+        if P > 0:
+            ops.attn_fwd_prefix(q, k, v, abias, keymask, o, lse, B, N, H, ATTN_SCALE, P, p=pa, seed=sa, seed_dev=salt if pa > 0 else None)
+        else:
+            ops.attn_fwd(q, k, v, abias, keymask, o, lse, B, N, H, ATTN_SCALE, p=pa, seed=sa, seed_dev=salt if pa > 0 else None)
         x1 = torch.empty(M, D, device=dev)
         if po > 0:                                                # to_out's dropout: x1 = x + keep o (o Wo^T) / (1 - p)
             yo = torch.empty(M, D, device=dev)
@@ -757,8 +780,13 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
         dkv = torch.empty(2, M, DIM_HEAD, device=dev)          # one allocation: the dK/dV kernel zero-fills both with one fill
         dk, dv = dkv[0], dkv[1]
         delta = torch.empty(B, H, N, device=dev)
-        ops.attn_bwd(sv.q, sv.k, sv.v, sv.abias, keymask, sv.o, do, sv.lse, delta, dq, dk, dv, dtable, B, N, H, ATTN_SCALE,
-                     p=sv.pa, seed=sv.sa, seed_dev=saved["salt"] if sv.pa > 0 else None)
+        P = prefix_rows(tr)
+        if P > 0:
+            ops.attn_bwd_prefix(sv.q, sv.k, sv.v, sv.abias, keymask, sv.o, do, sv.lse, delta, dq, dk, dv, dtable, B, N, H, ATTN_SCALE, P,
+                                p=sv.pa, seed=sv.sa, seed_dev=saved["salt"] if sv.pa > 0 else None)
+        else:
+            ops.attn_bwd(sv.q, sv.k, sv.v, sv.abias, keymask, sv.o, do, sv.lse, delta, dq, dk, dv, dtable, B, N, H, ATTN_SCALE,
+                         p=sv.pa, seed=sv.sa, seed_dev=saved["salt"] if sv.pa > 0 else None)
         dq_raw = torch.empty(M, H * DIM_HEAD, dtype=T, device=dev)
         dkv_raw = torch.empty(M, 2 * DIM_HEAD, dtype=T, device=dev)
         if T in _H16:                                                    # sv.q_raw / sv.kv_raw hold the norms [M, H] / [M]
@@ -923,9 +951,6 @@ class ForwardState:
 def run_forward(model, all_token_ids, self_attn_mask, only_final: bool, save: bool, precision: str,
                 want: Optional[Sequence[bool]] = None, final_rows_only: bool = False):
     tr = model.transformer
-    if tr.non_causal_prefix_size != 0:
-        raise NotImplementedError("non_causal_prefix_size > 0 is not supported by the MI355X attention kernel "
-                                  "(every shipped config uses 0)")
     require_gpu(model.start_tokens[0], "model parameters")
     ops.planes_begin()                       # bf16x3 operand planes live for this forward (+ its backward) only: ops.operand_planes
     if isinstance(all_token_ids, PreparedIds):

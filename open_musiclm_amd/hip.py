@@ -53,6 +53,10 @@ SIGNATURES = {
     "omlm_mqa_attn_bwd_workspace_bytes": [i32, i32, i32],
     "omlm_mqa_attn_fwd_dropout": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, f32, u64, vp, vp],
     "omlm_mqa_attn_bwd_dropout": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, f32, u64, vp, vp],
+    "omlm_mqa_attn_fwd_prefix": [vp] * 8 + [i32, i32, i32, f32, i32, i32, i32, f32, u64, vp, vp],
+    "omlm_mqa_attn_bwd_prefix": [vp] * 15 + [i32, i32, i32, f32, i32, i32, i32, f32, u64, vp, vp],
+    "omlm_attn_bias_table_floats_prefix": [i32, i32, i32],
+    "omlm_attn_bias_prepare_group_prefix": [vp, vp, i32, i32, i32, i32, vp, vp, f32, f32, i32, i32, vp],
     "omlm_attn_dropout_keep": [vp, i32, i32, i32, f32, u64, vp, vp],
     "omlm_dropout_residual_fwd": [vp, vp, vp, i64, i32, f32, u64, vp, vp],
     "omlm_dropout_residual_bwd": [vp, vp, i64, i32, f32, u64, vp, i32, vp],
@@ -84,6 +88,10 @@ SIGNATURES = {
     "omlm_bias_add": [vp, vp, vp, i32, i32, i32, vp],
     "omlm_relpos_mlp_fwd": [vp] * 15 + [i32, i32, i32, i32, vp],
     "omlm_relpos_mlp_bwd": [vp] * 19 + [i32, i32, i32, i32, vp],
+    "omlm_relpos_first_fwd_from": [vp, vp, vp, vp, i32, i32, i32, vp],
+    "omlm_relpos_first_bwd_from": [vp, vp, i32, i32, i32, vp],
+    "omlm_relpos_mlp_fwd_from": [vp] * 15 + [i32, i32, i32, i32, i32, vp],
+    "omlm_relpos_mlp_bwd_from": [vp] * 19 + [i32, i32, i32, i32, i32, vp],
     "omlm_rvq_encode": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
     "omlm_nearest_centroid": [vp, vp, vp, i32, i32, i32, vp],
     "omlm_rvq_encode_strided": [vp, vp, vp, i32, vp, i32, i32, i32, vp],
@@ -94,7 +102,7 @@ SIGNATURES = {
     "omlm_probe_tr16": [vp, vp],
 }
 _RESTYPES = {"omlm_last_error": C.c_char_p, "omlm_gemm_tail_workspace_bytes": C.c_longlong, "omlm_gemm_mx16_workspace_bytes": C.c_longlong, "omlm_ffmid_bwd_workspace_bytes": C.c_longlong,
-             "omlm_attn_bias_table_floats": C.c_longlong, "omlm_mqa_attn_bwd_workspace_bytes": C.c_longlong,
+             "omlm_attn_bias_table_floats": C.c_longlong, "omlm_attn_bias_table_floats_prefix": C.c_longlong, "omlm_mqa_attn_bwd_workspace_bytes": C.c_longlong,
              "omlm_layernorm_bwd_workspace_bytes": C.c_longlong, "omlm_set_error": None}
 
 

@@ -193,11 +193,12 @@ class TokenConditionedTransformerWrapper(nn.Module):
         step = 0
         nxt = torch.empty(batch, device=device, dtype=torch.long)
         n_new = max(max_time_steps - first_step, 0) * Q
-        use_cache = kwargs.pop('use_cache', True) and decode.supports(self.transformer, 1) and n_new > 0
+        prompt_rows = sum(t.shape[-1] + 1 for t in cond) + 1 + sampled.shape[-1]
+        use_cache = kwargs.pop('use_cache', True) and decode.supports(self.transformer, 1, prompt_rows=prompt_rows) and n_new > 0
         if use_cache:
             # KV-cached decode (decode.py): one new row per sampled id instead of the reference's full re-forward.
             # Ids are sampled straight into a [steps, B] buffer that the next decode step reads: no per-step cat / copies.
-            rows = sum(t.shape[-1] + 1 for t in cond) + 1 + sampled.shape[-1] + n_new
+            rows = prompt_rows + n_new
             n0 = sampled.shape[-1]
             if exists(uniforms):
                 U = uniforms[:n_new].to(device).float().contiguous()

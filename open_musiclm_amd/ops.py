@@ -409,20 +409,25 @@ class AttnBias:
              ptr(q_scale), ptr(k_scale), float(qk_bound), float(scale), 15 if half else 0, stream_ptr())
 
     @staticmethod
-    def group(table: Optional[torch.Tensor], N: int, H: int, device, q_scales, k_scales, scale: float = 8.0, half: bool = False):
+    def group(table: Optional[torch.Tensor], N: int, H: int, device, q_scales, k_scales, scale: float = 8.0, half: bool = False, P: int = 0):
         """One AttnBias per layer (q_scales[l], k_scales[l]) over the same rel-pos table, written by ONE launch
-        (omlm_attn_bias_prepare_group) instead of one small launch per layer."""
+        (omlm_attn_bias_prepare_group) instead of one small launch per layer.  P >= 1: the non-causal prefix's table ([N + min(P, N) - 1, ld],
+        omlm_attn_bias_prepare_group_prefix) for attn_fwd_prefix / attn_bwd_prefix."""
         L = len(q_scales)
         dev = table.device if table is not None else device
-        nfl = int(hip.lib().omlm_attn_bias_table_floats(N, H))
+        nfl = int(hip.lib().omlm_attn_bias_table_floats_prefix(N, H, P) if P > 0 else hip.lib().omlm_attn_bias_table_floats(N, H))
         buf = torch.empty(L, nfl, device=dev)
         outs = (C.c_void_p * L)(*[buf[l].data_ptr() for l in range(L)])
         qs = (C.c_void_p * L)(*[t.data_ptr() for t in q_scales])
         ks = (C.c_void_p * L)(*[t.data_ptr() for t in k_scales])
         for t in list(q_scales) + list(k_scales):
             hip.require_gpu(t, "scale")
-        call("omlm_attn_bias_prepare_group", ptr(table), C.cast(outs, C.c_void_p), L, N, H, table.shape[-1] if table is not None else 0,
-             C.cast(qs, C.c_void_p), C.cast(ks, C.c_void_p), 0.0, float(scale), 15 if half else 0, stream_ptr())
+        if P > 0:
+            call("omlm_attn_bias_prepare_group_prefix", ptr(table), C.cast(outs, C.c_void_p), L, N, H, table.shape[-1] if table is not None else 0,
+                 C.cast(qs, C.c_void_p), C.cast(ks, C.c_void_p), 0.0, float(scale), 15 if half else 0, int(P), stream_ptr())
+        else:
+            call("omlm_attn_bias_prepare_group", ptr(table), C.cast(outs, C.c_void_p), L, N, H, table.shape[-1] if table is not None else 0,
+                 C.cast(qs, C.c_void_p), C.cast(ks, C.c_void_p), 0.0, float(scale), 15 if half else 0, stream_ptr())
         return [AttnBias(table, N, H, dev, _tableT=buf[l]) for l in range(L)]
 
     def dbias_workspace(self, B: int, N: int, H: int) -> torch.Tensor:
@@ -475,6 +480,34 @@ def attn_bwd(q, k, v, bias, keymask, out, dout, lse, delta, dq, dk, dv, dbias, B
     call("omlm_mqa_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(bias), ptr(ab.tableT), ptr(keymask), ptr(out), ptr(dout), ptr(lse),
          ptr(delta), ptr(dq), ptr(dk), ptr(dv), ptr(dbias), ptr(ws), B, N, H, float(scale),
          bias.shape[-1] if bias is not None else 0, dcode(q.dtype), stream_ptr())
+
+
+def attn_fwd_prefix(q, k, v, bias, keymask, out, lse, B, N, H, scale, P, p=0.0, seed=0, seed_dev=None):
+    """Attention with a non-causal prefix of P >= 1 rows (omlm_mqa_attn_fwd_prefix): score (i, j) is live iff j <= i or i, j < P.
+    bias: an AttnBias of the prefix layout (AttnBias.group(..., P=P)), the plain [N + min(P, N) - 1, ld] fp32 rel-pos table (row
+    i - j + min(P, N) - 1, relpos_forward with P), or None."""
+    table, tableT = (bias.table, bias.tableT) if isinstance(bias, AttnBias) else (bias, None)
+    call("omlm_mqa_attn_fwd_prefix", ptr(q), ptr(k), ptr(v), ptr(table), ptr(tableT), ptr(keymask), ptr(out), ptr(lse), B, N, H, float(scale),
+         table.shape[-1] if table is not None else 0, dcode(q.dtype), int(P), float(p), int(seed), ptr(seed_dev), stream_ptr())
+
+
+def attn_bwd_prefix(q, k, v, bias, keymask, out, dout, lse, delta, dq, dk, dv, dtable, B, N, H, scale, P, workspace=True, p=0.0, seed=0,
+                    seed_dev=None):
+    """Backward of attn_fwd_prefix (bias: the forward's).  dtable: the plain table's layout (accumulated, +=), or None."""
+    table, tableT = (bias.table, bias.tableT) if isinstance(bias, AttnBias) else (bias, None)
+    ws = None
+    if dtable is not None and workspace:
+        n = int(hip.lib().omlm_mqa_attn_bwd_workspace_bytes(B, N, H)) // 4
+        key = str(q.device)
+        ws = _DBIAS_WS.get(key)
+        if ws is None or ws.numel() < n:
+            if ws is not None:
+                _DBIAS_RETIRED.append(ws)                       # (see AttnBias.dbias_workspace: a captured graph may hold it)
+            ws = _DBIAS_WS[key] = torch.empty(n, device=q.device, dtype=torch.float32)
+    ld = table.shape[-1] if table is not None else (dtable.shape[-1] if dtable is not None else 0)
+    call("omlm_mqa_attn_bwd_prefix", ptr(q), ptr(k), ptr(v), ptr(table), ptr(tableT), ptr(keymask), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dq),
+         ptr(dk), ptr(dv), ptr(dtable), ptr(ws), B, N, H, float(scale), ld, dcode(q.dtype), int(P), float(p), int(seed), ptr(seed_dev),
+         stream_ptr())
 
 
 def attn_dropout_keep(B, N, H, p, seed, seed_dev=None, device=None) -> torch.Tensor:
@@ -682,11 +715,18 @@ def colsum_accumulate(part, out, P, C_, ldp):
     call("omlm_colsum_accumulate", ptr(part), ptr(out), P, C_, ldp, stream_ptr())
 
 
-def relpos_first_fwd(w0, b0, pre, z, n, Hd):
+def relpos_first_fwd(w0, b0, pre, z, n, Hd, x0=0):
+    """Rows are the distances x0 .. x0 + n - 1."""
+    if x0:
+        call("omlm_relpos_first_fwd_from", ptr(w0), ptr(b0), ptr(pre), ptr(z), n, Hd, int(x0), stream_ptr())
+        return
     call("omlm_relpos_first_fwd", ptr(w0), ptr(b0), ptr(pre), ptr(z), n, Hd, stream_ptr())
 
 
-def relpos_first_bwd(ds, dw0, n, Hd):
+def relpos_first_bwd(ds, dw0, n, Hd, x0=0):
+    if x0:
+        call("omlm_relpos_first_bwd_from", ptr(ds), ptr(dw0), n, Hd, int(x0), stream_ptr())
+        return
     call("omlm_relpos_first_bwd", ptr(ds), ptr(dw0), n, Hd, stream_ptr())
 
 
@@ -702,15 +742,24 @@ def bias_add(a, b, out, R, C_, ld):
     call("omlm_bias_add", ptr(a), ptr(b), ptr(out), R, C_, ld, stream_ptr())
 
 
-def relpos_mlp_fwd(w0, b0, W1, b1, W2, b2, W3, b3, saves, table, n, Hd, H, ldb):
-    """The whole rel-pos MLP as one launch (omlm_relpos_mlp_fwd).  saves: None or [pre0, z0, pre1, z1, pre2, z2] ([n, Hd] fp32 each)."""
+def relpos_mlp_fwd(w0, b0, W1, b1, W2, b2, W3, b3, saves, table, n, Hd, H, ldb, x0=0):
+    """The whole rel-pos MLP as one launch (omlm_relpos_mlp_fwd).  saves: None or [pre0, z0, pre1, z1, pre2, z2] ([n, Hd] fp32 each).
+    x0: the distance of row 0 (negative for a non-causal prefix)."""
     sv = saves if saves is not None else [None] * 6
+    if x0:
+        call("omlm_relpos_mlp_fwd_from", ptr(w0), ptr(b0), ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(W3), ptr(b3), *[ptr(t) for t in sv],
+             ptr(table), int(n), int(Hd), int(H), int(ldb), int(x0), stream_ptr())
+        return
     call("omlm_relpos_mlp_fwd", ptr(w0), ptr(b0), ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(W3), ptr(b3), *[ptr(t) for t in sv], ptr(table),
          int(n), int(Hd), int(H), int(ldb), stream_ptr())
 
 
-def relpos_mlp_bwd(dtable, W1, W2, W3, saves, scratch, grads, n, Hd, H, ldb):
+def relpos_mlp_bwd(dtable, W1, W2, W3, saves, scratch, grads, n, Hd, H, ldb, x0=0):
     """Backward of the fused MLP: saves = [pre0, z0, pre1, z1, pre2, z2]; grads = [gw0, gb0, gW1, gb1, gW2, gb2, gW3, gb3] (accumulated into)."""
+    if x0:
+        call("omlm_relpos_mlp_bwd_from", ptr(dtable), ptr(W1), ptr(W2), ptr(W3), *[ptr(t) for t in saves], ptr(scratch),
+             *[ptr(g) for g in grads], int(n), int(Hd), int(H), int(ldb), int(x0), stream_ptr())
+        return
     call("omlm_relpos_mlp_bwd", ptr(dtable), ptr(W1), ptr(W2), ptr(W3), *[ptr(t) for t in saves], ptr(scratch), *[ptr(g) for g in grads],
          int(n), int(Hd), int(H), int(ldb), stream_ptr())
 
