@@ -401,7 +401,10 @@ int omlm_vq_kmeans_update(float* means, float* means_T, const float* counts, con
 int omlm_vq_ema_update(float* cluster_size, float* embed_avg, float* embed, float* embed_T, const float* counts, const float* sums,
                        float* total_scratch, int K, int D, float decay, float eps, void* stream);
 
-/* AR sampler: eos suppression + top_k(thres) + gumbel_sample (open_musiclm.py:309-316; utils.py:65-84). */
+/* AR sampler: eos suppression + top_k(thres) + gumbel_sample (open_musiclm.py:309-316; utils.py:65-84).
+ * Kept set: every logit strictly above the k-th largest value, then of the logits equal to it the lowest indices until exactly k are
+ * kept.  Id: the first maximum of l / T + Gumbel(u) over the kept set (0 when every kept logit is -inf).  The same rule holds for
+ * omlm_sample_topk_gumbel_at and omlm_sample_embed_at below. */
 int omlm_sample_topk_gumbel(const float* logits, const float* uniform, long long* out, int B, int V, int ld,
                             int k, float temperature, int forbid_last, void* stream);
 

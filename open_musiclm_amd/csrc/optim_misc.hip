@@ -940,8 +940,10 @@ extern "C" int omlm_nearest_centroid(const float* x, const float* centroids_T, i
 // fused sampler of the AR loop (open_musiclm.py:309-316; utils.py:65-84): last-position logits [B, V] ->
 //   eos logit -> -inf (unless allowed), keep the k = max(int((1-thres) V), 1) largest logits, argmax(l / T + Gumbel(u)).
 // One workgroup per row; V <= 2048.  The k-th largest value is found by a bitwise radix descent on the
-// order-preserving integer image of the floats (exact, no sort); ties at the threshold are kept in index order
-// like torch.topk + scatter (which keeps exactly k entries: the lowest indices among equals).
+// order-preserving integer image of the floats (exact, no sort).  Tie rule (this library's own, deterministic): every entry strictly
+// above the k-th largest value is kept and, of the entries equal to it, the LOWEST indices until exactly k are kept.  (torch.topk
+// also keeps exactly k entries but promises no order among equals: on tied rows its kept set differs from this one.)  The id is the
+// first maximum of l / T + Gumbel(u) over the kept entries; index 0 when every kept entry is -inf (as argmax of an all -inf row).
 __device__ __forceinline__ unsigned f_ord(float f) { unsigned u = f2u(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 
 // One WAVE per row: the row's logits sit in registers (V <= 2048 -> <= 32 per lane, element c = lane + 64 j), every count of the
@@ -1032,6 +1034,7 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
         const int oi = __shfl_xor(besti, o, 64);
         if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
     }
+    if (besti == 0x7fffffff) besti = 0;                 // every kept entry -inf (e.g. V = 1 with forbid_last): no slot won a comparison
     if (lane == 0) { out[row] = besti; if (hist) hist[row] = besti; }
     if (emb_table) {
         long long r = (long long)besti + emb_row_offset;
