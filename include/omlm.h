@@ -98,45 +98,30 @@ int omlm_qk_norm_bwd2(const float* dq, const float* dk, const float* dv, const v
                       const float* q_scale, const float* k_scale, void* dq_raw, void* dkv_raw, float* dq_scale, float* dk_scale,
                       int M, int H, int dtype, void* stream);
 
-/* Causal multi-query attention with rel-pos bias table and key mask (transformer.py:303-331; the same logical
- * inputs as the xformers seam at :275-301, without materialising attn_bias).  bias: [N, bias_ld] fp32, row = i-j,
- * column = head (the un-gathered MLP output of RelativePositionBias, :60-64).  keymask: [B, N] uint8, 1 = attend.
- * lse: [B, H, N] (log2 domain).  bwd: dq [B*N, H*64], dk, dv [B*N, 64] fp32 overwritten; dbias += ; delta scratch [B,H,N]. */
-int omlm_mqa_attn_fwd(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                      const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale, int bias_ld,
-                      int dtype, void* stream);
-/* biasT: the same table transposed to [ceil8(H)][ld'] with 64 leading zeros per row, zero tail, pre-multiplied by log2(e): the
- * layout the bf16 kernels stream per key tile (omlm_attn_bias_table_floats floats; bias == NULL gives an all-zero table).
- * Built once per forward for all layers; fp32 ("bf16x3") operands read `bias` directly and ignore biasT. */
-long long omlm_attn_bias_table_floats(int N, int H);
-/* q_scale / k_scale (64 floats each, optional: the learned scales of transformer.py:269-271) or qk_bound > 0 give the bound
- * |q.k| <= max_d |q_scale_d k_scale_d| that lets the bf16 forward exponentiate against a fixed reference point
- * (m_h = scale log2e bound + max bias_h, subtracted from the table) instead of a running maximum; neither: online softmax.
- * p_max_log2: 0 for bf16 / fp32 attention operands; 15 for IEEE half operands -- the reference point is lowered by 15 so that the
- * probability numerators span half's normal range (2^-13 .. 2^15) and the fixed form is selected while scale log2e 2 bound + the
- * table's range < 28 (wider: the flag in the table stays 0 and the forward runs its online-softmax kernel). */
-int omlm_attn_bias_prepare(const float* bias, float* biasT, int N, int H, int bias_ld, const float* q_scale,
-                           const float* k_scale, float qk_bound, float scale, int p_max_log2, void* stream);
-/* The tables of `layers` attention layers over ONE rel-pos table in ONE launch (transformer.py:402-405 computes the bias once per forward and
- * hands it to every layer; here each layer's copy carries that layer's reference point): biasT[l] from q_scale[l] / k_scale[l].
- * biasT / q_scale / k_scale: HOST arrays (length `layers`) of DEVICE pointers; q_scale and k_scale both given or both NULL (then qk_bound). */
-int omlm_attn_bias_prepare_group(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
-                                 const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
-                                 int p_max_log2, void* stream);
-/* dbias_ws (optional, omlm_mqa_attn_bwd_workspace_bytes(B, N, H) bytes, contents irrelevant on entry and exit): the dQ kernel leaves
- * each wave's d(bias) bins there with plain stores and a small reduction adds them into dbias; without it every wave adds its bins into
- * dbias with device-scope atomics (measured 290 us per layer slower at B = 8, N = 1817, H = 16). */
-long long omlm_mqa_attn_bwd_workspace_bytes(int B, int N, int H);
-int omlm_mqa_attn_bwd(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                      const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
-                      float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
-                      int B, int N, int H, float scale, int bias_ld, int dtype, void* stream);
-
-/* Attention dropout (transformer.py:198,211: nn.Dropout(attn_dropout) on the softmax probabilities before P V).
- * out = (P o Z / (1 - p)) V with Z the keep-mask below; lse stays that of the undropped P (bit-identical to p = 0), and the backward
- * regenerates Z: dV = (P o Z / (1 - p))^T dO, dS = P o (Z o dP~ / (1 - p) - delta), delta = rowsum(dO o O) as before.  Arguments as
- * omlm_mqa_attn_fwd / _bwd plus p in [0, 1) (round(p * 65536) < 65536), seed and the optional per-forward salt seed_dev (one uint64 in
- * device memory, read by the kernels: a captured graph draws new masks when the salt is bumped).  p == 0 is exactly the plain entry.
+/* Multi-query attention with rel-pos bias table and key mask (transformer.py:303-331; the same logical inputs as the xformers seam at
+ * :275-301, without materialising attn_bias), causal or with a non-causal prefix of P >= 0 rows (:315-322, non_causal_prefix_size).
+ * With Pn = min(P, N), score (i, j) is live iff
+ *   j <= i   or   (i < Pn and j < Pn)
+ * and the key mask keeps j (inside the prefix too).  P = 0 is causal; P >= N: every row sees every live key.
+ * q [B*N, H*64], k, v [B*N, 64] (dtype), keymask [B, N] uint8 (1 = attend) or NULL, out [B*N, H*64] (dtype), lse [B, H, N] fp32 (log2 domain).
+ * dtype: 0 = fp32 ("bf16x3" forward), 1 = bf16, 2 = fp16.
+ * bias: the rel-pos table [N + Pn - 1, bias_ld] fp32, column = head, row = i - j + Pn - 1 (the distances -(Pn - 1) .. N - 1 in ascending
+ * order: the negative distances of the scores above the diagonal inside the prefix, then the causal table [N, bias_ld] with row = i - j, the
+ * un-gathered MLP output of RelativePositionBias, :60-64), or NULL.
+ * biasT: that table prepared by omlm_attn_bias_prepare_group with the same P (omlm_attn_bias_prepare for P = 0), or NULL.
+ * p: attention dropout in [0, 1) (round(p * 65536) < 65536; 0: none) with the keep-mask below, seed and the optional per-forward salt seed_dev
+ * (one uint64 in device memory, read by the kernels: a captured graph draws new masks when the salt is bumped).  At p = 0 seed and seed_dev are
+ * not read.  P < 0 or p outside [0, 1) is refused before any launch.
+ * bwd: dq [B*N, H*64], dk, dv [B*N, 64] fp32 overwritten; dbias (bias's layout) accumulated (+=) over all its rows; delta scratch [B, H, N].
+ *
+ * Routes: 16-bit operands with biasT (or without any bias) run the second-generation kernels -- the forward up to N = 4096, a prefix while
+ * their plans fit (N >= 32, N <= 4096 and the dQ kernel's LDS, which holds 8 (ceil32(N) + Pn - 1) d(bias) bins: about N + Pn <= 4000).
+ * Otherwise, and for fp32 operands, the first-generation kernels read `bias`; their bf16x3 dQ kernel caps ceil32(N) + Pn - 1 at about 3800
+ * (an error beyond).  The forward and the backward decide alike, so a backward is always handed the lse its forward wrote.
+ *
+ * Dropout (transformer.py:198,211: nn.Dropout(attn_dropout) on the softmax probabilities before P V), for the prefix's extra scores as for the
+ * others: out = (P o Z / (1 - p)) V with Z the keep-mask below; lse stays that of the undropped P (bit-identical to p = 0), and the backward
+ * regenerates Z: dV = (P o Z / (1 - p))^T dO, dS = P o (Z o dP~ / (1 - p) - delta), delta = rowsum(dO o O) as before.
  *
  * Keep-mask of probability (b, h, i, j) -- sample b, head h, query i, key j (i < 2^17, j < 2^16):
  *   hash(x)  = lowbias32: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (uint32 arithmetic)
@@ -147,38 +132,36 @@ int omlm_mqa_attn_bwd(const void* q, const void* k, const void* v, const float* 
  *   Z        = draw >= round(p * 65536)                                                            (the FF dropout's rule)
  * It depends on nothing else (not on N, the tile shapes, the dtype or the kernel).  Keys j, j + 1 share one hash (16 bits each), and
  * headkey ^ (i << 15) is a per-(b, h, i) key hoisted out of the kernels' key loops. */
-int omlm_mqa_attn_fwd_dropout(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                              const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale, int bias_ld,
-                              int dtype, float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream);
-int omlm_mqa_attn_bwd_dropout(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                              const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
-                              float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
-                              int B, int N, int H, float scale, int bias_ld, int dtype, float p, unsigned long long seed,
-                              const unsigned long long* seed_dev, void* stream);
-/* Non-causal prefix (transformer.py:315-322, non_causal_prefix_size = P >= 1): score (i, j) is live iff
- *   j <= i   or   (i < P and j < P)
- * and the key mask keeps j (the key mask applies inside the prefix too); P >= N: every row sees every live key.  With Pn = min(P, N), the
- * rel-pos table bias / dbias is [N + Pn - 1, bias_ld] fp32, row = i - j + Pn - 1 (distances -(Pn - 1) .. N - 1 in ascending order: the
- * negative distances of the scores above the diagonal inside the prefix, then the table of omlm_mqa_attn_fwd); dbias is accumulated (+=)
- * over all its rows.  p > 0: attention dropout with the keep-mask above, for the prefix's extra scores as for the others (p = 0: none).
- * biasT: the prepared table of omlm_attn_bias_prepare_group_prefix (omlm_attn_bias_table_floats_prefix(N, H, P) floats: the causal layout
- * with the Pn - 1 negative distances in front; the fixed reference point covers them), or NULL.  16-bit operands with biasT (or without any
- * bias) run the second-generation kernels while their plans fit -- N >= 32, N <= 4096 and the dQ kernel's LDS, which holds
- * 8 (ceil32(N) + Pn - 1) d(bias) bins: about N + Pn <= 4000 -- and otherwise, like fp32 operands, the first-generation kernels on the plain
- * table, whose bf16x3 dQ kernel caps ceil32(N) + Pn - 1 at about 3800 (an error beyond).  The forward and the backward decide alike, so a
- * backward is always handed the lse its forward wrote.  Other arguments as omlm_mqa_attn_fwd / _bwd.  P = 0 is refused: the causal
- * entries above serve it. */
-int omlm_mqa_attn_fwd_prefix(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                             void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
-                             unsigned long long seed, const unsigned long long* seed_dev, void* stream);
-int omlm_mqa_attn_bwd_prefix(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                             const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv, float* dbias,
-                             float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p, unsigned long long seed,
-                             const unsigned long long* seed_dev, void* stream);
-long long omlm_attn_bias_table_floats_prefix(int N, int H, int P);
-int omlm_attn_bias_prepare_group_prefix(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
-                                        const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
-                                        int p_max_log2, int P, void* stream);
+int omlm_mqa_attn_fwd(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                      void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
+                      unsigned long long seed, const unsigned long long* seed_dev, void* stream);
+/* biasT: the table transposed to [ceil8(H)][ld'] with 64 leading zeros per row (then the Pn - 1 negative distances), zero tail,
+ * pre-multiplied by log2(e): the layout the 16-bit kernels stream per key tile (omlm_attn_bias_table_floats(N, H, P) floats; bias == NULL
+ * gives an all-zero table).  Built once per forward for all layers; fp32 ("bf16x3") operands read `bias` directly and ignore biasT. */
+long long omlm_attn_bias_table_floats(int N, int H, int P);
+/* The causal table of one layer (P = 0).  q_scale / k_scale (64 floats each, optional: the learned scales of transformer.py:269-271) or
+ * qk_bound > 0 give the bound |q.k| <= max_d |q_scale_d k_scale_d| that lets the 16-bit forward exponentiate against a fixed reference point
+ * (m_h = scale log2e bound + max bias_h, subtracted from the table) instead of a running maximum; neither: online softmax.
+ * p_max_log2: 0 for bf16 / fp32 attention operands; 15 for IEEE half operands -- the reference point is lowered by 15 so that the
+ * probability numerators span half's normal range (2^-13 .. 2^15) and the fixed form is selected while scale log2e 2 bound + the
+ * table's range < 28 (wider: the flag in the table stays 0 and the forward runs its online-softmax kernel). */
+int omlm_attn_bias_prepare(const float* bias, float* biasT, int N, int H, int bias_ld, const float* q_scale,
+                           const float* k_scale, float qk_bound, float scale, int p_max_log2, void* stream);
+/* The tables of `layers` attention layers over ONE rel-pos table in ONE launch (transformer.py:402-405 computes the bias once per forward and
+ * hands it to every layer; here each layer's copy carries that layer's reference point): biasT[l] from q_scale[l] / k_scale[l], for a
+ * prefix of P >= 0 rows (bias: the [N + Pn - 1, bias_ld] table above; the reference point covers the negative distances too).
+ * biasT / q_scale / k_scale: HOST arrays (length `layers`) of DEVICE pointers; q_scale and k_scale both given or both NULL (then qk_bound). */
+int omlm_attn_bias_prepare_group(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
+                                 const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
+                                 int p_max_log2, int P, void* stream);
+/* dbias_ws (optional, omlm_mqa_attn_bwd_workspace_bytes(B, N, H) bytes, contents irrelevant on entry and exit): the dQ kernel leaves
+ * each wave's d(bias) bins there with plain stores and a small reduction adds them into dbias; without it every wave adds its bins into
+ * dbias with device-scope atomics (measured 290 us per layer slower at B = 8, N = 1817, H = 16). */
+long long omlm_mqa_attn_bwd_workspace_bytes(int B, int N, int H);
+int omlm_mqa_attn_bwd(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                      const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv, float* dbias,
+                      float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p, unsigned long long seed,
+                      const unsigned long long* seed_dev, void* stream);
 /* keep [B, H, N, N] uint8 (1 = kept): the mask above, as the attention kernels apply it (a test / integration hook for small shapes). */
 int omlm_attn_dropout_keep(unsigned char* keep, int B, int N, int H, float p, unsigned long long seed,
                            const unsigned long long* seed_dev, void* stream);

@@ -995,16 +995,16 @@ int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* b
 
 bool attn2_prefix_fits(int N, int Pn);      // attention2.hip: whether the second-generation kernels serve a prefix of Pn rows at N
 
-// the forward of omlm_mqa_attn_fwd (drop == NULL) and omlm_mqa_attn_fwd_dropout (drop: p > 0)
+// Pn = min(P, N): 0 is causal, >= 1 the non-causal prefix of include/omlm.h.  bias: the rel = 0 row of the [N + Pn - 1, bias_ld] table (or
+// null).  drop: null for p == 0.
 static int attn_fwd_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
                          const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale,
-                         int bias_ld, int dtype, void* stream, const AttnDrop* drop) {
-    if (B <= 0 || N <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
-    OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
-    if (dtype == 1 && (biasT || !bias))
-        return attn2_fwd_launch(q, k, v, biasT, keymask, out, lse, B, N, H, scale, as_stream(stream), drop, 0);
+                         int bias_ld, int dtype, int Pn, void* stream, const AttnDrop* drop) {
+    // 16-bit operands with the prepared table, or without any bias: attention2.hip (a prefix only while attn2_prefix_fits)
+    if (dtype == 1 && (biasT || !bias) && (Pn == 0 || attn2_prefix_fits(N, Pn)))
+        return attn2_fwd_launch(q, k, v, biasT, keymask, out, lse, B, N, H, scale, as_stream(stream), drop, Pn);
     dim3 grid((N + TQ - 1) / TQ, (H + 3) / 4, B), block(AT_THREADS);
+    const int off = Pn > 0 ? Pn - 1 : 0;
     const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
     const AttnDrop& dr = drop ? *drop : nd;
     int rc;
@@ -1013,112 +1013,44 @@ static int attn_fwd_impl(const void* q, const void* k, const void* v, const floa
         omlm_set_error("omlm_mqa_attn_fwd: fp32 operands are served by the bf16 copy of the library");
         return OMLM_ERR_UNSUPPORTED;
 #else
-        const size_t lds = fwd_lds(N, true);
-        auto kern = drop ? attn_fwd_kernel<float, true> : attn_fwd_kernel<float, false>;
-        if ((rc = set_lds(kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const float*)q, (const float*)k, (const float*)v, bias, keymask, (float*)out, lse, B, N, H, scale, bias_ld, dr, 0);
-#endif
-    } else {
-        const size_t lds = fwd_lds(N, false);
-        auto kern = drop ? attn_fwd_kernel<h16_t, true> : attn_fwd_kernel<h16_t, false>;
-        if ((rc = set_lds(kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (h16_t*)out, lse, B, N, H, scale, bias_ld, dr, 0);
-    }
-    return omlm_post_launch("omlm_mqa_attn_fwd");
-}
-
-// The forward with a non-causal prefix of Pn = min(P, N) >= 1 rows (omlm_mqa_attn_fwd_prefix): the first-generation kernels' PFX
-// instances for every operand type.  bias: the rel = 0 row of the [N + Pn - 1, bias_ld] table (or null).
-static int attn_fwd_prefix_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                                const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype,
-                                int Pn, void* stream, const AttnDrop* drop) {
-    // 16-bit operands with the prepared table (omlm_attn_bias_prepare_group_prefix), or without any bias: attention2.hip's PFX instances
-    if (dtype == 1 && (biasT || !bias) && attn2_prefix_fits(N, Pn))
-        return attn2_fwd_launch(q, k, v, biasT, keymask, out, lse, B, N, H, scale, as_stream(stream), drop, Pn);
-    dim3 grid((N + TQ - 1) / TQ, (H + 3) / 4, B), block(AT_THREADS);
-    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
-    const AttnDrop& dr = drop ? *drop : nd;
-    int rc;
-    if (dtype == 0) {
-#if OMLM_FP16
-        omlm_set_error("omlm_mqa_attn_fwd_prefix: fp32 operands are served by the bf16 copy of the library");
-        return OMLM_ERR_UNSUPPORTED;
-#else
-        const size_t lds = fwd_lds(N, true, Pn - 1);
-        auto kern = drop ? attn_fwd_kernel<float, true, true> : attn_fwd_kernel<float, false, true>;
+        const size_t lds = fwd_lds(N, true, off);
+        auto kern = Pn > 0 ? (drop ? attn_fwd_kernel<float, true, true> : attn_fwd_kernel<float, false, true>)
+                           : (drop ? attn_fwd_kernel<float, true> : attn_fwd_kernel<float, false>);
         if ((rc = set_lds(kern, lds))) return rc;
         hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const float*)q, (const float*)k, (const float*)v, bias, keymask, (float*)out, lse, B, N, H, scale, bias_ld, dr, Pn);
 #endif
     } else {
-        const size_t lds = fwd_lds(N, false, Pn - 1);
-        auto kern = drop ? attn_fwd_kernel<h16_t, true, true> : attn_fwd_kernel<h16_t, false, true>;
+        const size_t lds = fwd_lds(N, false, off);
+        auto kern = Pn > 0 ? (drop ? attn_fwd_kernel<h16_t, true, true> : attn_fwd_kernel<h16_t, false, true>)
+                           : (drop ? attn_fwd_kernel<h16_t, true> : attn_fwd_kernel<h16_t, false>);
         if ((rc = set_lds(kern, lds))) return rc;
         hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (h16_t*)out, lse, B, N, H, scale, bias_ld, dr, Pn);
     }
-    return omlm_post_launch("omlm_mqa_attn_fwd_prefix");
+    return omlm_post_launch("omlm_mqa_attn_fwd");
 }
 
-
-// q [B*N, H*64], k, v [B*N, 64] (dtype), bias [N, bias_ld] fp32 (row = i - j, column = head) or null, keymask [B, N] uint8 or null (1 = attend)
-// biasT: the table prepared by omlm_attn_bias_prepare (bf16 operands take the attention2.hip kernel, which reads it; may be null
-// when bias is null).  out [B*N, H*64] (dtype), lse [B, H, N] fp32 (log2 domain)
-// dtype: 0 = fp32 ("bf16x3"), 1 = bf16, 2 = fp16 (forwarded to the fp16 copy of this file; common.h)
+// include/omlm.h.  dtype: 0 = fp32 ("bf16x3"), 1 = bf16, 2 = fp16 (forwarded to the fp16 copy of this file; common.h)
 #if !OMLM_FP16
-extern "C" int omlm_mqa_attn_fwd_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                                   const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale,
-                                   int bias_ld, int dtype, void* stream);
+extern "C" int omlm_mqa_attn_fwd_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                   void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
+                                   unsigned long long seed, const unsigned long long* seed_dev, void* stream);
 #endif
-extern "C" int OMLM_API(omlm_mqa_attn_fwd)(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                                 const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale,
-                                 int bias_ld, int dtype, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16) return omlm_mqa_attn_fwd_h(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, 1, stream);
-#endif
-    return attn_fwd_impl(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, dtype, stream, nullptr);
-}
-
-// attention dropout (include/omlm.h): p == 0 is omlm_mqa_attn_fwd itself
-#if !OMLM_FP16
-extern "C" int omlm_mqa_attn_fwd_dropout_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                                           const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale,
-                                           int bias_ld, int dtype, float p, unsigned long long seed, const unsigned long long* seed_dev,
-                                           void* stream);
-#endif
-extern "C" int OMLM_API(omlm_mqa_attn_fwd_dropout)(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                                                   const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale,
-                                                   int bias_ld, int dtype, float p, unsigned long long seed,
-                                                   const unsigned long long* seed_dev, void* stream) {
+extern "C" int OMLM_API(omlm_mqa_attn_fwd)(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                           void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
+                                           unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
 #if !OMLM_FP16
     if (dtype == OMLM_DT_F16)
-        return omlm_mqa_attn_fwd_dropout_h(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, 1, p, seed, seed_dev, stream);
+        return omlm_mqa_attn_fwd_h(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, 1, P, p, seed, seed_dev, stream);
 #endif
     AttnDrop d;
+    OMLM_CHECK_ARG(P >= 0, "prefix rows P >= 0");
     OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
-    return attn_fwd_impl(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, dtype, stream, p > 0.f ? &d : nullptr);
-}
-
-// non-causal prefix of P rows (include/omlm.h); p: attention dropout as in omlm_mqa_attn_fwd_dropout (0: none)
-#if !OMLM_FP16
-extern "C" int omlm_mqa_attn_fwd_prefix_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                                          void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
-                                          unsigned long long seed, const unsigned long long* seed_dev, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_mqa_attn_fwd_prefix)(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                                                  void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
-                                                  unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16)
-        return omlm_mqa_attn_fwd_prefix_h(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, 1, P, p, seed, seed_dev, stream);
-#endif
     if (B <= 0 || N <= 0) return OMLM_OK;
-    AttnDrop d;
     OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
     OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
-    OMLM_CHECK_ARG(P >= 1, "prefix rows P >= 1 (P = 0: omlm_mqa_attn_fwd_dropout)");
-    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
     const int Pn = P < N ? P : N;
-    return attn_fwd_prefix_impl(q, k, v, bias ? bias + (size_t)(Pn - 1) * bias_ld : nullptr, biasT, keymask, out, lse, B, N, H, scale, bias_ld,
-                                dtype, Pn, stream, p > 0.f ? &d : nullptr);
+    return attn_fwd_impl(q, k, v, bias && Pn > 0 ? bias + (size_t)(Pn - 1) * bias_ld : bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld,
+                         dtype, Pn, stream, p > 0.f ? &d : nullptr);
 }
 
 // dq [B*N, H*64] fp32, dk, dv [B*N, 64] fp32 (overwritten), dbias [N, bias_ld] fp32 (accumulated, +=), delta [B, H, N] scratch
@@ -1130,25 +1062,22 @@ extern "C" __attribute__((visibility("hidden"))) int omlm_attn_dbias_reduce_laun
 int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                          const void* dout, const float* lse, const float* delta, float* dk, float* dv,
                          int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn);      // attention3.hip
-#if !OMLM_FP16
-extern "C" int omlm_mqa_attn_bwd_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                                   const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
-                                   float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
-                                   int B, int N, int H, float scale, int bias_ld, int dtype, void* stream);
-#endif
+
+// Pn, bias, drop as in attn_fwd_impl; dbias: the rel = 0 row of its table.  d(bias) of rel >= 0 goes through the workspace and its
+// reduction, that of rel < 0 (Pn > 1) by atomics from the dQ kernel.
 static int attn_bwd_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
                          const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
                          float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
-                         int B, int N, int H, float scale, int bias_ld, int dtype, void* stream, const AttnDrop* drop) {
-    if (B <= 0 || N <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(q && k && v && out && dout && lse && delta && dq && dk && dv, "null pointer");
+                         int B, int N, int H, float scale, int bias_ld, int dtype, int Pn, void* stream, const AttnDrop* drop) {
     dim3 gridq((N + TQ - 1) / TQ, (H + 3) / 4, B), gridk((N + 31) / 32, 1, B), block(AT_THREADS);
-    // windowed bias in the dK / dV kernel only where staging every head's column would cost occupancy (> 80 KiB: one workgroup per CU);
-    // below that the staged form measured 2 % faster (B=32, N=1116, H=8: 656 vs 670 us), above it 16 % slower (B=8, N=1817, H=16)
-    const size_t ldsk_staged = 32 * 1024 + (size_t)H * ((N + TQ - 1) / TQ * TQ) * sizeof(float) + 1024;
-    const bool win = biasT != nullptr && ldsk_staged > 80 * 1024;
-    const int ldT = ((64 + N + 2 * 128 + 3) / 4) * 4;                      // layout of omlm_attn_bias_prepare (attention2.hip)
-    const size_t ldsq = dq_lds(N, dtype == 0);
+    const int off = Pn > 0 ? Pn - 1 : 0;
+    // first-generation dK / dV: every head's bias column is staged in LDS (a prefix: with up to 31 negative distances in front; see
+    // attn_bwd_dkv_kernel).  The causal kernel reads the prepared table by windows instead where staging would cost occupancy (> 80 KiB: one
+    // workgroup per CU): below that the staged form measured 2 % faster (B=32, N=1116, H=8: 656 vs 670 us), above it 16 % slower (B=8, N=1817, H=16)
+    const size_t ldsk_staged = 32 * 1024 + (size_t)H * ((N + TQ - 1) / TQ * TQ + (Pn > 0 ? 31 : 0)) * sizeof(float) + 1024;
+    const bool win = Pn == 0 && biasT != nullptr && ldsk_staged > 80 * 1024;
+    const int ldT = Pn == 0 ? ((64 + N + 2 * 128 + 3) / 4) * 4 : 0;       // layout of omlm_attn_bias_prepare (attention2.hip)
+    const size_t ldsq = dq_lds(N, dtype == 0, off);
     const size_t ldsk = win ? 32 * 1024 + 4 * 128 * sizeof(float)
                             : ldsk_staged;
     int rc;
@@ -1161,156 +1090,69 @@ static int attn_bwd_impl(const void* q, const void* k, const void* v, const floa
         omlm_set_error("omlm_mqa_attn_bwd: fp32 operands are served by the bf16 copy of the library");
         return OMLM_ERR_UNSUPPORTED;
 #else
-        auto kq = drop ? attn_bwd_dq_precise_kernel<float, true> : attn_bwd_dq_precise_kernel<float, false>;
-        auto kk = drop ? attn_bwd_dkv_kernel<float, true> : attn_bwd_dkv_kernel<float, false>;
-        if ((rc = set_lds(kq, ldsq))) return rc;
-        if ((rc = set_lds(kk, ldsk))) return rc;
-        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)out, (const float*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, 0);
-        if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
-        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr, 0);
-#endif
-    } else {
-        auto kk = drop ? attn_bwd_dkv_kernel<h16_t, true> : attn_bwd_dkv_kernel<h16_t, false>;
-        if ((rc = set_lds(kk, ldsk))) return rc;
-        // dQ / d(bias) / delta: the attention2.hip kernel when the prepared table is there and the sample fits its LDS plan
-        int r2 = 1;
-        // The attention2.hip kernel (8 heads per workgroup sharing LDS-DMA-staged K / V tiles) wherever its LDS plan fits: with the Horner
-        // diagonal sums and the d(bias) workspace it is the faster one at both bench shapes (B=32, N=1116, H=8: whole backward 432 against
-        // 456 us; before those two changes both kernels spent ~160 us per layer in d(bias) and the first-generation kernel led 316 : 334).
-        if (biasT || !bias) {
-            r2 = attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, drop, 0);
-            if (r2 < 0) return r2;
-        }
-        if (r2 != 0) {
-        auto kq = drop ? attn_bwd_dq_kernel<h16_t, true> : attn_bwd_dq_kernel<h16_t, false>;
-        if ((rc = set_lds(kq, ldsq))) return rc;
-        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, 0);
-        }
-        if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
-        // dK / dV: the third-generation kernel (attention3.hip: 128 keys per workgroup, Q / dO staged once per workgroup by LDS-DMA) where the
-        // prepared table is there (or there is no bias); else the second-generation kernel
-        int r3 = 1;
-        if (biasT || !bias) {
-            r3 = attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, drop, 0);
-            if (r3 < 0) return r3;
-        }
-        if (r3 != 0)
-        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr, 0);
-    }
-    return omlm_post_launch("omlm_mqa_attn_bwd");
-}
-
-// The backward with a non-causal prefix of Pn = min(P, N) >= 1 rows (omlm_mqa_attn_bwd_prefix): the PFX instances of the first-generation
-// dQ and dK / dV kernels.  bias / dbias: the rel = 0 rows of the [N + Pn - 1, bias_ld] tables; d(bias) of rel >= 0 goes through the
-// workspace and its reduction as in attn_bwd_impl, that of rel < 0 by atomics from the dQ kernel.
-static int attn_bwd_prefix_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                                const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
-                                float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int Pn, void* stream,
-                                const AttnDrop* drop) {
-    dim3 gridq((N + TQ - 1) / TQ, (H + 3) / 4, B), gridk((N + 31) / 32, 1, B), block(AT_THREADS);
-    const int off = Pn - 1;
-    const size_t ldsq = dq_lds(N, dtype == 0, off);
-    const size_t ldsk = 32 * 1024 + (size_t)H * ((N + TQ - 1) / TQ * TQ + 31) * sizeof(float) + 1024;      // see attn_bwd_dkv_kernel
-    int rc;
-    hipStream_t st = as_stream(stream);
-    float* dpart = dbias ? dbias_ws : nullptr;
-    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
-    const AttnDrop& dr = drop ? *drop : nd;
-    if (dtype == 0) {
-#if OMLM_FP16
-        omlm_set_error("omlm_mqa_attn_bwd_prefix: fp32 operands are served by the bf16 copy of the library");
-        return OMLM_ERR_UNSUPPORTED;
-#else
-        auto kq = drop ? attn_bwd_dq_precise_kernel<float, true, true> : attn_bwd_dq_precise_kernel<float, false, true>;
-        auto kk = drop ? attn_bwd_dkv_kernel<float, true, true> : attn_bwd_dkv_kernel<float, false, true>;
+        auto kq = Pn > 0 ? (drop ? attn_bwd_dq_precise_kernel<float, true, true> : attn_bwd_dq_precise_kernel<float, false, true>)
+                         : (drop ? attn_bwd_dq_precise_kernel<float, true> : attn_bwd_dq_precise_kernel<float, false>);
+        auto kk = Pn > 0 ? (drop ? attn_bwd_dkv_kernel<float, true, true> : attn_bwd_dkv_kernel<float, false, true>)
+                         : (drop ? attn_bwd_dkv_kernel<float, true> : attn_bwd_dkv_kernel<float, false>);
         if ((rc = set_lds(kq, ldsq))) return rc;
         if ((rc = set_lds(kk, ldsk))) return rc;
         hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)out, (const float*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
         if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
-        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, nullptr, 0, dr, Pn);
+        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr, Pn);
 #endif
     } else {
-        auto kq = drop ? attn_bwd_dq_kernel<h16_t, true, true> : attn_bwd_dq_kernel<h16_t, false, true>;
-        auto kk = drop ? attn_bwd_dkv_kernel<h16_t, true, true> : attn_bwd_dkv_kernel<h16_t, false, true>;
-        // the prepared table (or no bias): attention2.hip's dQ and attention3.hip's dK / dV PFX instances where their plans fit -- the same
-        // test as the forward's, whose lse is relative to the table's reference point there
-        if ((biasT || !bias) && attn2_prefix_fits(N, Pn)) {
-            if ((rc = attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, drop, Pn)))
-                return rc < 0 ? rc : OMLM_ERR_UNSUPPORTED;
-            if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
-            if ((rc = attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, drop, Pn)))
-                return rc < 0 ? rc : OMLM_ERR_UNSUPPORTED;
-            return omlm_post_launch("omlm_mqa_attn_bwd_prefix");
+        auto kq = Pn > 0 ? (drop ? attn_bwd_dq_kernel<h16_t, true, true> : attn_bwd_dq_kernel<h16_t, false, true>)
+                         : (drop ? attn_bwd_dq_kernel<h16_t, true> : attn_bwd_dq_kernel<h16_t, false>);
+        auto kk = Pn > 0 ? (drop ? attn_bwd_dkv_kernel<h16_t, true, true> : attn_bwd_dkv_kernel<h16_t, false, true>)
+                         : (drop ? attn_bwd_dkv_kernel<h16_t, true> : attn_bwd_dkv_kernel<h16_t, false>);
+        // The prepared table (or no bias): attention2.hip's dQ kernel (8 heads per workgroup sharing LDS-DMA-staged K / V tiles) and attention3.hip's
+        // dK / dV kernel (128 keys per workgroup, Q / dO staged once per workgroup by LDS-DMA).  With the Horner diagonal sums and the d(bias)
+        // workspace the dQ kernel is the faster one at both bench shapes (B=32, N=1116, H=8: whole backward 432 against 456 us; before those two
+        // changes both kernels spent ~160 us per layer in d(bias) and the first-generation kernel led 316 : 334).  Causal: each falls back to
+        // its first-generation kernel where its plan does not fit (launcher result 1).  A prefix runs them iff attn2_prefix_fits -- the
+        // forward's test, whose lse is relative to the table's reference point there -- so a "does not fit" is an error, not a fallback.
+        const bool gen2 = (biasT || !bias) && (Pn == 0 || attn2_prefix_fits(N, Pn));
+        if ((Pn == 0 || !gen2) && (rc = set_lds(kk, ldsk))) return rc;
+        int r = gen2 ? attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, drop, Pn) : 1;
+        if (r < 0 || (r > 0 && gen2 && Pn > 0)) return r < 0 ? r : OMLM_ERR_UNSUPPORTED;
+        if (r > 0) {
+            if ((rc = set_lds(kq, ldsq))) return rc;
+            hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
         }
-        if ((rc = set_lds(kq, ldsq))) return rc;
-        if ((rc = set_lds(kk, ldsk))) return rc;
-        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
         if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
-        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, nullptr, 0, dr, Pn);
+        r = gen2 ? attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, drop, Pn) : 1;
+        if (r < 0 || (r > 0 && gen2 && Pn > 0)) return r < 0 ? r : OMLM_ERR_UNSUPPORTED;
+        if (r > 0)
+            hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr, Pn);
     }
-    return omlm_post_launch("omlm_mqa_attn_bwd_prefix");
-}
-
-extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                                 const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
-                                 float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
-                                 int B, int N, int H, float scale, int bias_ld, int dtype, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16)
-        return omlm_mqa_attn_bwd_h(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, 1, stream);
-#endif
-    return attn_bwd_impl(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, dtype,
-                         stream, nullptr);
+    return omlm_post_launch("omlm_mqa_attn_bwd");
 }
 
 #if !OMLM_FP16
-extern "C" int omlm_mqa_attn_bwd_dropout_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                                           const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
-                                           float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
-                                           int B, int N, int H, float scale, int bias_ld, int dtype, float p, unsigned long long seed,
-                                           const unsigned long long* seed_dev, void* stream);
+extern "C" int omlm_mqa_attn_bwd_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                   const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
+                                   float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P,
+                                   float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream);
 #endif
-extern "C" int OMLM_API(omlm_mqa_attn_bwd_dropout)(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                                                   const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
-                                                   float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
-                                                   int B, int N, int H, float scale, int bias_ld, int dtype, float p, unsigned long long seed,
-                                                   const unsigned long long* seed_dev, void* stream) {
+extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                           const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
+                                           float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P,
+                                           float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
 #if !OMLM_FP16
     if (dtype == OMLM_DT_F16)
-        return omlm_mqa_attn_bwd_dropout_h(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale,
-                                           bias_ld, 1, p, seed, seed_dev, stream);
+        return omlm_mqa_attn_bwd_h(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, 1,
+                                   P, p, seed, seed_dev, stream);
 #endif
     AttnDrop d;
+    OMLM_CHECK_ARG(P >= 0, "prefix rows P >= 0");
     OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
-    return attn_bwd_impl(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, dtype,
-                         stream, p > 0.f ? &d : nullptr);
-}
-
-#if !OMLM_FP16
-extern "C" int omlm_mqa_attn_bwd_prefix_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                                          const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
-                                          float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P,
-                                          float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_mqa_attn_bwd_prefix)(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                                                  const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
-                                                  float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P,
-                                                  float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16)
-        return omlm_mqa_attn_bwd_prefix_h(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, 1,
-                                          P, p, seed, seed_dev, stream);
-#endif
     if (B <= 0 || N <= 0) return OMLM_OK;
-    AttnDrop d;
     OMLM_CHECK_ARG(q && k && v && out && dout && lse && delta && dq && dk && dv, "null pointer");
     OMLM_CHECK_ARG(H >= 1 && ((!bias && !dbias) || bias_ld >= H), "heads / bias pitch");
-    OMLM_CHECK_ARG(P >= 1, "prefix rows P >= 1 (P = 0: omlm_mqa_attn_bwd_dropout)");
-    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
     const int Pn = P < N ? P : N;
-    const size_t r0 = (size_t)(Pn - 1) * bias_ld;
-    return attn_bwd_prefix_impl(q, k, v, bias ? bias + r0 : nullptr, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias ? dbias + r0 : nullptr,
-                                dbias_ws, B, N, H, scale, bias_ld, dtype, Pn, stream, p > 0.f ? &d : nullptr);
+    const size_t r0 = Pn > 0 ? (size_t)(Pn - 1) * bias_ld : 0;
+    return attn_bwd_impl(q, k, v, bias ? bias + r0 : nullptr, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias ? dbias + r0 : nullptr,
+                         dbias_ws, B, N, H, scale, bias_ld, dtype, Pn, stream, p > 0.f ? &d : nullptr);
 }
 
 }   // namespace OMLM_NS

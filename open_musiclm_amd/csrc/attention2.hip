@@ -368,7 +368,7 @@ struct A4Stager {
 // the fixed form 10 % slower than this split (103 vs 92 us).
 //   FIXED: both heads in one straight line.  Online (more live state: running maxima, rescale factors): the two heads one after the
 //   other (QSEL), re-reading the K / V fragments per head.
-// PFX: the non-causal prefix of Pn = min(P, N) rows; the table (omlm_attn_bias_prepare_group_prefix) holds Pn - 1 negative distances in
+// PFX: the non-causal prefix of Pn = min(P, N) rows; the table (omlm_attn_bias_prepare_group with P >= 1) holds Pn - 1 negative distances in
 // front of the causal layout, so every window offset moves by off = Pn - 1.
 template <bool FIXED, bool DROP = false, bool PFX = false>
 __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__ k,
@@ -785,8 +785,8 @@ int attn2_bwd_dq_launch(const void* q, const void* k, const void* v, const float
                         float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn) {
     const int off = Pn > 0 ? Pn - 1 : 0;                       // Pn > 0: the non-causal prefix (PFX instances)
     const int ldT = (A2_PAD + off + N + 2 * A2_BWIN + 3) / 4 * 4;
-    const int nqt = (N + 31) / 32, ny = (H + 7) / 8, npad = (N + 63) / 64 * 64;
-    const size_t lds = (size_t)A2_NST * A2B_STAGE + 4096 + (size_t)npad * 4 + (size_t)8 * (nqt * 32 + off) * 4;
+    const int nqt = (N + 31) / 32, ny = (H + 7) / 8;
+    const size_t lds = a2_dq_lds(N, off);
     if (lds > 160 * 1024 || N > 4096) return 1;                // caller falls back to the first-generation kernel
     static bool a1 = false;
     if (!a1) {
@@ -797,29 +797,23 @@ int attn2_bwd_dq_launch(const void* q, const void* k, const void* v, const float
         a1 = true;
     }
     const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
-    if (Pn > 0) {
-        hipLaunchKernelGGL((drop ? attn2_bwd_dq_kernel<true, true> : attn2_bwd_dq_kernel<false, true>), dim3(nqt * ny * B), dim3(A2_THREADS), lds, st,
-                           (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta,
-                           dq, dbias, bias_ld, dpart, B, N, H, scale, drop ? *drop : nd, Pn);
-        return omlm_post_launch("omlm_mqa_attn_bwd_prefix");
-    }
-    if (drop)
-        hipLaunchKernelGGL(attn2_bwd_dq_kernel<true>, dim3(nqt * ny * B), dim3(A2_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
-                           biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, *drop, 0);
-    else
-        hipLaunchKernelGGL(attn2_bwd_dq_kernel<false>, dim3(nqt * ny * B), dim3(A2_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
-                           biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, nd, 0);
+    auto kern = Pn > 0 ? (drop ? attn2_bwd_dq_kernel<true, true> : attn2_bwd_dq_kernel<false, true>)
+                       : (drop ? attn2_bwd_dq_kernel<true> : attn2_bwd_dq_kernel<false>);
+    hipLaunchKernelGGL(kern, dim3(nqt * ny * B), dim3(A2_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask,
+                       (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, drop ? *drop : nd, Pn);
     return omlm_post_launch("omlm_mqa_attn_bwd");
 }
 
 #if !OMLM_FP16      /* the bias table is fp32 in every precision: prepared by the bf16 copy of this file */
 // -------------------------------------------------------------------------------------------------------------------------
-extern "C" long long omlm_attn_bias_table_floats(int N, int H) {
-    const int ldT = (A2_PAD + N + 2 * A2_BWIN + 3) / 4 * 4, H8 = (H + 7) / 8 * 8;
+// the prepared table of a prefix of P rows (0: causal): the min(P, N) - 1 negative distances in front of the causal layout
+extern "C" long long omlm_attn_bias_table_floats(int N, int H, int P) {
+    const int off = P > 0 ? (P < N ? P : N) - 1 : 0;
+    const int ldT = (A2_PAD + off + N + 2 * A2_BWIN + 3) / 4 * 4, H8 = (H + 7) / 8 * 8;
     return (long long)H8 * ldT;
 }
 
-// biasT: omlm_attn_bias_table_floats(N, H) floats.  bias may be null (no rel-pos bias).  q_scale / k_scale (64 floats each, optional):
+// biasT: omlm_attn_bias_table_floats(N, H, 0) floats.  bias may be null (no rel-pos bias).  q_scale / k_scale (64 floats each, optional):
 // the learned per-dim scales applied after the l2 normalisation -- they give the bound max_d |q_scale_d k_scale_d| on |q.k| that
 // selects the fixed-reference softmax; alternatively qk_bound > 0 states the bound directly (callers with unit q, k: 1.0);
 // neither: online softmax.  scale: the attention scale (8).  p_max_log2: 0 for bf16 / fp32 attention operands, 15 for half operands (the
@@ -836,13 +830,14 @@ extern "C" int omlm_attn_bias_prepare(const float* bias, float* biasT, int N, in
                        qk_bound, scale * A2_LOG2E, p_max_log2, 0);
     return omlm_post_launch("omlm_attn_bias_prepare");
 }
-// The tables of `layers` attention layers over ONE rel-pos table in one launch: biasT[l] (omlm_attn_bias_table_floats(N, H) floats each) from
+// The tables of `layers` attention layers over ONE rel-pos table in one launch: biasT[l] (omlm_attn_bias_table_floats(N, H, P) floats each) from
 // the layer's learned scales q_scale[l] / k_scale[l] (64 floats each; all given, or all NULL with qk_bound as in omlm_attn_bias_prepare).
-// biasT / q_scale / k_scale: HOST arrays of device pointers.
-// the group prepare of both layouts; P >= 1: the non-causal prefix's table (bias: [N + Pn - 1, bias_ld] from its first row)
-static int bias_prepare_group(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
-                              const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
-                              int p_max_log2, int P, void* stream) {
+// biasT / q_scale / k_scale: HOST arrays of device pointers.  P >= 1: the non-causal prefix's table (bias: [N + min(P, N) - 1, bias_ld] from
+// its first row).
+extern "C" int omlm_attn_bias_prepare_group(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
+                                            const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
+                                            int p_max_log2, int P, void* stream) {
+    OMLM_CHECK_ARG(P >= 0, "prefix rows P >= 0");
     if (layers <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(biasT && N > 0 && H > 0, "null table / sizes");
     OMLM_CHECK_ARG(p_max_log2 == 0 || p_max_log2 == 15, "p_max_log2: 0 (bf16 / fp32 operands) or 15 (half operands)");
@@ -860,31 +855,10 @@ static int bias_prepare_group(const float* bias, float* const* biasT, int layers
             grp.qs[l] = q_scale ? q_scale[base + l] : nullptr;
             grp.ks[l] = k_scale ? k_scale[base + l] : nullptr;
         }
-        if (P > 0)
-            hipLaunchKernelGGL(attn2_bias_prep_kernel<true>, dim3(H8, n), dim3(256), 0, as_stream(stream), bias, grp, N, H, bias_ld, ldT,
-                               qk_bound, scale * A2_LOG2E, p_max_log2, off);
-        else
-            hipLaunchKernelGGL(attn2_bias_prep_kernel<false>, dim3(H8, n), dim3(256), 0, as_stream(stream), bias, grp, N, H, bias_ld, ldT,
-                               qk_bound, scale * A2_LOG2E, p_max_log2, 0);
+        hipLaunchKernelGGL(P > 0 ? attn2_bias_prep_kernel<true> : attn2_bias_prep_kernel<false>, dim3(H8, n), dim3(256), 0, as_stream(stream),
+                           bias, grp, N, H, bias_ld, ldT, qk_bound, scale * A2_LOG2E, p_max_log2, off);
     }
     return omlm_post_launch("omlm_attn_bias_prepare_group");
-}
-extern "C" int omlm_attn_bias_prepare_group(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
-                                            const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
-                                            int p_max_log2, void* stream) {
-    return bias_prepare_group(bias, biasT, layers, N, H, bias_ld, q_scale, k_scale, qk_bound, scale, p_max_log2, 0, stream);
-}
-// non-causal prefix of P >= 1 rows: tables of omlm_attn_bias_table_floats_prefix(N, H, P) floats from the [N + min(P, N) - 1, bias_ld] table
-extern "C" long long omlm_attn_bias_table_floats_prefix(int N, int H, int P) {
-    const int off = P > 0 ? (P < N ? P : N) - 1 : 0;
-    const int ldT = (A2_PAD + off + N + 2 * A2_BWIN + 3) / 4 * 4, H8 = (H + 7) / 8 * 8;
-    return (long long)H8 * ldT;
-}
-extern "C" int omlm_attn_bias_prepare_group_prefix(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
-                                                   const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
-                                                   int p_max_log2, int P, void* stream) {
-    OMLM_CHECK_ARG(P >= 1, "prefix rows P >= 1 (P = 0: omlm_attn_bias_prepare_group)");
-    return bias_prepare_group(bias, biasT, layers, N, H, bias_ld, q_scale, k_scale, qk_bound, scale, p_max_log2, P, stream);
 }
 
 // d(bias) partial rows -> the [N, bias_ld] table.  The dQ kernels leave one fp32 row of nqt*32 bins per (sample, head, query tile) in
@@ -1020,30 +994,19 @@ int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* b
         (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         a4 = true;
     }
-    const AttnDrop nd0 = {0ull, nullptr, 0u, 1.0f};
-    if (Pn > 0) {                                              // the non-causal prefix: the PFX instances of both softmax forms
-        const AttnDrop& dr = drop ? *drop : nd0;
-        if (biasT) hipLaunchKernelGGL((drop ? attn4_fwd_kernel<true, true, true> : attn4_fwd_kernel<true, false, true>), dim3(nqt * ny * B),
-                                      dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask,
-                                      (h16_t*)out, lse, B, N, H, scale, dr, Pn);
-        hipLaunchKernelGGL((drop ? attn4_fwd_kernel<false, true, true> : attn4_fwd_kernel<false, false, true>), dim3(nqt * ny * B), dim3(A4_THREADS),
-                           lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, dr, Pn);
-        return omlm_post_launch("omlm_mqa_attn_fwd_prefix");
-    }
-    // both softmax forms: the one the table's flag does not name returns at its first instruction (no table: online only)
-    const dim3 grid(nqt * ny * B);
-    if (drop) {
-        if (biasT) hipLaunchKernelGGL((attn4_fwd_kernel<true, true>), grid, dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k,
-                                      (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, *drop, 0);
-        hipLaunchKernelGGL((attn4_fwd_kernel<false, true>), grid, dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
-                           biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, *drop, 0);
-        return omlm_post_launch("omlm_mqa_attn_fwd");
-    }
+    // both softmax forms: the one the table's flag does not name returns at its first instruction (no table: online only); Pn > 0: their
+    // PFX instances (the non-causal prefix)
     const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
-    if (biasT) hipLaunchKernelGGL(attn4_fwd_kernel<true>, dim3(nqt * ny * B), dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k,
-                                  (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, nd, 0);
-    hipLaunchKernelGGL(attn4_fwd_kernel<false>, dim3(nqt * ny * B), dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v,
-                       biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, nd, 0);
+    const AttnDrop& dr = drop ? *drop : nd;
+    const dim3 grid(nqt * ny * B);
+    auto fixed = Pn > 0 ? (drop ? attn4_fwd_kernel<true, true, true> : attn4_fwd_kernel<true, false, true>)
+                        : (drop ? attn4_fwd_kernel<true, true> : attn4_fwd_kernel<true>);
+    auto online = Pn > 0 ? (drop ? attn4_fwd_kernel<false, true, true> : attn4_fwd_kernel<false, false, true>)
+                         : (drop ? attn4_fwd_kernel<false, true> : attn4_fwd_kernel<false>);
+    if (biasT) hipLaunchKernelGGL(fixed, grid, dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask,
+                                  (h16_t*)out, lse, B, N, H, scale, dr, Pn);
+    hipLaunchKernelGGL(online, grid, dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask,
+                       (h16_t*)out, lse, B, N, H, scale, dr, Pn);
     return omlm_post_launch("omlm_mqa_attn_fwd");
 }
 

@@ -347,18 +347,10 @@ int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const floa
     if (dv == dk + gfloats) fill(dk, 2 * gfloats);            // one allocation (the host's usual case): one fill launch instead of two
     else { fill(dk, gfloats); fill(dv, gfloats); }
     const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
-    if (Pn > 0) {
-        hipLaunchKernelGGL((drop ? attn3_bwd_dkv_kernel<true, true> : attn3_bwd_dkv_kernel<false, true>), dim3(B * wps), dim3(A3_T), lds, st,
-                           (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask, (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H,
-                           scale, CH, wps, drop ? *drop : nd, Pn);
-        return omlm_post_launch("omlm_mqa_attn_bwd_prefix");
-    }
-    if (drop)
-        hipLaunchKernelGGL(attn3_bwd_dkv_kernel<true>, dim3(B * wps), dim3(A3_T), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask,
-                           (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps, *drop, 0);
-    else
-        hipLaunchKernelGGL(attn3_bwd_dkv_kernel<false>, dim3(B * wps), dim3(A3_T), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask,
-                           (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps, nd, 0);
+    auto kern = Pn > 0 ? (drop ? attn3_bwd_dkv_kernel<true, true> : attn3_bwd_dkv_kernel<false, true>)
+                       : (drop ? attn3_bwd_dkv_kernel<true> : attn3_bwd_dkv_kernel<false>);
+    hipLaunchKernelGGL(kern, dim3(B * wps), dim3(A3_T), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask, (const h16_t*)dout, lse,
+                       delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps, drop ? *drop : nd, Pn);
     return omlm_post_launch("omlm_mqa_attn_bwd");
 }
 

@@ -406,7 +406,7 @@ def prefix_rows(tr) -> int:
 
 def relpos_rows(n: int, P: int = 0) -> Tuple[int, int]:
     """(rows, x0) of the rel-pos table of an n-row sequence with a non-causal prefix of P rows: rows x0 .. n - 1 of distance i - j, where
-    x0 = -(min(P, n) - 1) <= 0 -- the table's row x - x0 holds distance x (include/omlm.h, omlm_mqa_attn_fwd_prefix)."""
+    x0 = -(min(P, n) - 1) <= 0 -- the table's row x - x0 holds distance x (include/omlm.h, omlm_mqa_attn_fwd)."""
     x0 = -(min(P, n) - 1) if P > 0 else 0
     return n - x0, x0
 
@@ -559,7 +559,7 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
     dev = x.device
     M, D = x.shape
     H = tr.heads
-    P = prefix_rows(tr)                                           # non-causal prefix: its own attention entries and a table over x0 .. N - 1
+    P = prefix_rows(tr)                                           # non-causal prefix rows (0: causal) and a table over x0 .. N - 1
     rc = tr.__dict__.get("_omlm_relpos_cache")
     if rc is not None and save and training and rc.usable(N):
         table, rp_saved = rc.table, ("cached", rc)                # (RelposStepCache: computed once for this optimizer step)
@@ -616,10 +616,7 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
         pa, po = aps[li]
         sa = aseeds[li] if pa > 0 else 0
         so = oseeds[li] if po > 0 else 0
-        if P > 0:
-            ops.attn_fwd_prefix(q, k, v, abias, keymask, o, lse, B, N, H, ATTN_SCALE, P, p=pa, seed=sa, seed_dev=salt if pa > 0 else None)
-        else:
-            ops.attn_fwd(q, k, v, abias, keymask, o, lse, B, N, H, ATTN_SCALE, p=pa, seed=sa, seed_dev=salt if pa > 0 else None)
+        ops.attn_fwd(q, k, v, abias, keymask, o, lse, B, N, H, ATTN_SCALE, P=P, p=pa, seed=sa, seed_dev=salt if pa > 0 else None)
         x1 = torch.empty(M, D, device=dev)
         if po > 0:                                                # to_out's dropout: x1 = x + keep o (o Wo^T) / (1 - p)
             yo = torch.empty(M, D, device=dev)
@@ -780,13 +777,8 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
         dkv = torch.empty(2, M, DIM_HEAD, device=dev)          # one allocation: the dK/dV kernel zero-fills both with one fill
         dk, dv = dkv[0], dkv[1]
         delta = torch.empty(B, H, N, device=dev)
-        P = prefix_rows(tr)
-        if P > 0:
-            ops.attn_bwd_prefix(sv.q, sv.k, sv.v, sv.abias, keymask, sv.o, do, sv.lse, delta, dq, dk, dv, dtable, B, N, H, ATTN_SCALE, P,
-                                p=sv.pa, seed=sv.sa, seed_dev=saved["salt"] if sv.pa > 0 else None)
-        else:
-            ops.attn_bwd(sv.q, sv.k, sv.v, sv.abias, keymask, sv.o, do, sv.lse, delta, dq, dk, dv, dtable, B, N, H, ATTN_SCALE,
-                         p=sv.pa, seed=sv.sa, seed_dev=saved["salt"] if sv.pa > 0 else None)
+        ops.attn_bwd(sv.q, sv.k, sv.v, sv.abias, keymask, sv.o, do, sv.lse, delta, dq, dk, dv, dtable, B, N, H, ATTN_SCALE, P=prefix_rows(tr),
+                     p=sv.pa, seed=sv.sa, seed_dev=saved["salt"] if sv.pa > 0 else None)
         dq_raw = torch.empty(M, H * DIM_HEAD, dtype=T, device=dev)
         dkv_raw = torch.empty(M, 2 * DIM_HEAD, dtype=T, device=dev)
         if T in _H16:                                                    # sv.q_raw / sv.kv_raw hold the norms [M, H] / [M]

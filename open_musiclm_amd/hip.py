@@ -45,18 +45,12 @@ SIGNATURES = {
     "omlm_qk_norm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "omlm_gemm_qknorm": [vp, vp, vp, vp, i32, i32, vp, vp, i32, i32, i64, i64, i32, i32, i32, i32, i32, i32, i32, vp],
     "omlm_qk_norm_bwd2": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-    "omlm_attn_bias_table_floats": [i32, i32],
+    "omlm_attn_bias_table_floats": [i32, i32, i32],
     "omlm_attn_bias_prepare": [vp, vp, i32, i32, i32, vp, vp, f32, f32, i32, vp],
-    "omlm_attn_bias_prepare_group": [vp, vp, i32, i32, i32, i32, vp, vp, f32, f32, i32, vp],
-    "omlm_mqa_attn_fwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp],
-    "omlm_mqa_attn_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp],
+    "omlm_attn_bias_prepare_group": [vp, vp, i32, i32, i32, i32, vp, vp, f32, f32, i32, i32, vp],
+    "omlm_mqa_attn_fwd": [vp] * 8 + [i32, i32, i32, f32, i32, i32, i32, f32, u64, vp, vp],
+    "omlm_mqa_attn_bwd": [vp] * 15 + [i32, i32, i32, f32, i32, i32, i32, f32, u64, vp, vp],
     "omlm_mqa_attn_bwd_workspace_bytes": [i32, i32, i32],
-    "omlm_mqa_attn_fwd_dropout": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, f32, u64, vp, vp],
-    "omlm_mqa_attn_bwd_dropout": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, f32, u64, vp, vp],
-    "omlm_mqa_attn_fwd_prefix": [vp] * 8 + [i32, i32, i32, f32, i32, i32, i32, f32, u64, vp, vp],
-    "omlm_mqa_attn_bwd_prefix": [vp] * 15 + [i32, i32, i32, f32, i32, i32, i32, f32, u64, vp, vp],
-    "omlm_attn_bias_table_floats_prefix": [i32, i32, i32],
-    "omlm_attn_bias_prepare_group_prefix": [vp, vp, i32, i32, i32, i32, vp, vp, f32, f32, i32, i32, vp],
     "omlm_attn_dropout_keep": [vp, i32, i32, i32, f32, u64, vp, vp],
     "omlm_dropout_residual_fwd": [vp, vp, vp, i64, i32, f32, u64, vp, vp],
     "omlm_dropout_residual_bwd": [vp, vp, i64, i32, f32, u64, vp, i32, vp],
@@ -102,7 +96,7 @@ SIGNATURES = {
     "omlm_probe_tr16": [vp, vp],
 }
 _RESTYPES = {"omlm_last_error": C.c_char_p, "omlm_gemm_tail_workspace_bytes": C.c_longlong, "omlm_gemm_mx16_workspace_bytes": C.c_longlong, "omlm_ffmid_bwd_workspace_bytes": C.c_longlong,
-             "omlm_attn_bias_table_floats": C.c_longlong, "omlm_attn_bias_table_floats_prefix": C.c_longlong, "omlm_mqa_attn_bwd_workspace_bytes": C.c_longlong,
+             "omlm_attn_bias_table_floats": C.c_longlong, "omlm_mqa_attn_bwd_workspace_bytes": C.c_longlong,
              "omlm_layernorm_bwd_workspace_bytes": C.c_longlong, "omlm_set_error": None}
 
 

@@ -389,8 +389,9 @@ def qk_norm_bwd2(dq, dk, dv, q, k, qn, kn, q_scale, k_scale, dq_raw, dkv_raw, dq
 
 
 class AttnBias:
-    """Rel-pos bias table of one attention layer in the two layouts the kernels read: `table` [N, ld] fp32 (row = i - j,
-    column = head) and `tableT`, its transposed / zero-padded / log2(e)-scaled form (omlm_attn_bias_prepare).
+    """Rel-pos bias table of one attention layer in the two layouts the kernels read: `table` [N + min(P, N) - 1, ld] fp32 (row =
+    i - j + min(P, N) - 1, column = head; include/omlm.h) and `tableT`, its transposed / zero-padded / log2(e)-scaled form
+    (omlm_attn_bias_prepare).  P: the non-causal prefix the layout is for (0: causal); attn_fwd / attn_bwd take it only with the same P.
 
     q_scale / k_scale (the layer's learned per-dim scales) or qk_bound (an explicit bound on |q . k|, e.g. 1.0 for unit vectors)
     let the 16-bit forward take its exponentials against a fixed reference point instead of a running maximum; without either the
@@ -398,116 +399,86 @@ class AttnBias:
     span half's normal range instead of sitting at its bottom (the kernels fall back to the online softmax if the scales grow too wide)."""
 
     def __init__(self, table: Optional[torch.Tensor], N: int, H: int, device=None, q_scale=None, k_scale=None,
-                 qk_bound: float = 0.0, scale: float = 8.0, half: bool = False, _tableT: Optional[torch.Tensor] = None):
-        self.table, self.N, self.H = table, N, H
+                 qk_bound: float = 0.0, scale: float = 8.0, half: bool = False, _tableT: Optional[torch.Tensor] = None, _P: int = 0):
+        self.table, self.N, self.H, self.P = table, N, H, _P
         dev = table.device if table is not None else device
         if _tableT is not None:                         # (AttnBias.group: the table was written by the grouped launch)
             self.tableT = _tableT
             return
-        self.tableT = torch.empty(int(hip.lib().omlm_attn_bias_table_floats(N, H)), device=dev)
+        self.tableT = torch.empty(int(hip.lib().omlm_attn_bias_table_floats(N, H, 0)), device=dev)
         call("omlm_attn_bias_prepare", ptr(table), ptr(self.tableT), N, H, table.shape[-1] if table is not None else 0,
              ptr(q_scale), ptr(k_scale), float(qk_bound), float(scale), 15 if half else 0, stream_ptr())
 
     @staticmethod
     def group(table: Optional[torch.Tensor], N: int, H: int, device, q_scales, k_scales, scale: float = 8.0, half: bool = False, P: int = 0):
         """One AttnBias per layer (q_scales[l], k_scales[l]) over the same rel-pos table, written by ONE launch
-        (omlm_attn_bias_prepare_group) instead of one small launch per layer.  P >= 1: the non-causal prefix's table ([N + min(P, N) - 1, ld],
-        omlm_attn_bias_prepare_group_prefix) for attn_fwd_prefix / attn_bwd_prefix."""
+        (omlm_attn_bias_prepare_group) instead of one small launch per layer.  P >= 1: the non-causal prefix's layout."""
         L = len(q_scales)
         dev = table.device if table is not None else device
-        nfl = int(hip.lib().omlm_attn_bias_table_floats_prefix(N, H, P) if P > 0 else hip.lib().omlm_attn_bias_table_floats(N, H))
-        buf = torch.empty(L, nfl, device=dev)
+        buf = torch.empty(L, int(hip.lib().omlm_attn_bias_table_floats(N, H, P)), device=dev)
         outs = (C.c_void_p * L)(*[buf[l].data_ptr() for l in range(L)])
         qs = (C.c_void_p * L)(*[t.data_ptr() for t in q_scales])
         ks = (C.c_void_p * L)(*[t.data_ptr() for t in k_scales])
         for t in list(q_scales) + list(k_scales):
             hip.require_gpu(t, "scale")
-        if P > 0:
-            call("omlm_attn_bias_prepare_group_prefix", ptr(table), C.cast(outs, C.c_void_p), L, N, H, table.shape[-1] if table is not None else 0,
-                 C.cast(qs, C.c_void_p), C.cast(ks, C.c_void_p), 0.0, float(scale), 15 if half else 0, int(P), stream_ptr())
-        else:
-            call("omlm_attn_bias_prepare_group", ptr(table), C.cast(outs, C.c_void_p), L, N, H, table.shape[-1] if table is not None else 0,
-                 C.cast(qs, C.c_void_p), C.cast(ks, C.c_void_p), 0.0, float(scale), 15 if half else 0, stream_ptr())
-        return [AttnBias(table, N, H, dev, _tableT=buf[l]) for l in range(L)]
-
-    def dbias_workspace(self, B: int, N: int, H: int) -> torch.Tensor:
-        """Scratch for the backward's d(bias) partial rows (omlm_mqa_attn_bwd_workspace_bytes): ONE buffer per device, shared by every
-        layer and every step (the reduction kernel of a layer consumes it before the next layer's dQ kernel writes it: stream order;
-        like _ln_workspace it assumes one backward at a time per device).  It is quadratic in N (B H ceil(N/32)^2 128 bytes: 40 MB at
-        B = 32, N = 1116), so one copy per layer was 24 x 53 MB for the musiclm_large leg."""
-        n = int(hip.lib().omlm_mqa_attn_bwd_workspace_bytes(B, N, H)) // 4
-        key = str(self.tableT.device)
-        ws = _DBIAS_WS.get(key)
-        if ws is None or ws.numel() < n:
-            if ws is not None:
-                # a captured HIP graph (graph.py) holds the OLD buffer's address in its kernel nodes: a regrown workspace must not free
-                # it, or later replays would write d(bias) partials into memory the allocator has handed to someone else
-                _DBIAS_RETIRED.append(ws)
-            ws = _DBIAS_WS[key] = torch.empty(n, device=self.tableT.device, dtype=torch.float32)
-        return ws
+        call("omlm_attn_bias_prepare_group", ptr(table), C.cast(outs, C.c_void_p), L, N, H, table.shape[-1] if table is not None else 0,
+             C.cast(qs, C.c_void_p), C.cast(ks, C.c_void_p), 0.0, float(scale), 15 if half else 0, int(P), stream_ptr())
+        return [AttnBias(table, N, H, dev, _tableT=buf[l], _P=P) for l in range(L)]
 
 
-def _attn_bias(bias, N, H, device) -> "AttnBias":
-    return bias if isinstance(bias, AttnBias) else AttnBias(bias, N, H, device)
+def _attn_tables(bias, N, H, P, device):
+    """(table, tableT) for the C entries from attn_fwd's / attn_bwd's bias argument.  A raw table (or None) is prepared here for P = 0 --
+    one prepare launch, after which 16-bit operands run the second-generation kernels with the online softmax -- but handed over as it is
+    for P >= 1, which runs the first-generation kernels.  That asymmetry is a route of its own; keep it unless the routes are meant to change."""
+    if isinstance(bias, AttnBias):
+        if bias.P != P:
+            raise ValueError(f"attention with P = {P} handed an AttnBias prepared for P = {bias.P}")
+        return bias.table, bias.tableT
+    return bias, (AttnBias(bias, N, H, device).tableT if P == 0 else None)
 
 
-def attn_fwd(q, k, v, bias, keymask, out, lse, B, N, H, scale, p=0.0, seed=0, seed_dev=None):
-    """bias: an AttnBias (built once per forward by the engine), a raw [N, ld] table, or None.
+def _dbias_workspace(B: int, N: int, H: int, device) -> torch.Tensor:
+    """Scratch for the backward's d(bias) partial rows (omlm_mqa_attn_bwd_workspace_bytes): ONE buffer per device, shared by every
+    layer and every step (the reduction kernel of a layer consumes it before the next layer's dQ kernel writes it: stream order;
+    like _ln_workspace it assumes one backward at a time per device).  It is quadratic in N (B H ceil(N/32)^2 128 bytes: 40 MB at
+    B = 32, N = 1116), so one copy per layer was 24 x 53 MB for the musiclm_large leg."""
+    n = int(hip.lib().omlm_mqa_attn_bwd_workspace_bytes(B, N, H)) // 4
+    key = str(device)
+    ws = _DBIAS_WS.get(key)
+    if ws is None or ws.numel() < n:
+        if ws is not None:
+            # a captured HIP graph (graph.py) holds the OLD buffer's address in its kernel nodes: a regrown workspace must not free
+            # it, or later replays would write d(bias) partials into memory the allocator has handed to someone else
+            _DBIAS_RETIRED.append(ws)
+        ws = _DBIAS_WS[key] = torch.empty(n, device=device, dtype=torch.float32)
+    return ws
+
+
+def attn_fwd(q, k, v, bias, keymask, out, lse, B, N, H, scale, P=0, p=0.0, seed=0, seed_dev=None):
+    """Attention with a non-causal prefix of P rows (omlm_mqa_attn_fwd; 0: causal): score (i, j) is live iff j <= i or i, j < P.
+    bias: an AttnBias of the layout for P (built once per forward by the engine: AttnBias.group(..., P=P)), a raw [N + min(P, N) - 1, ld]
+    fp32 rel-pos table (row i - j + min(P, N) - 1, relpos_forward with P), or None.
     p > 0: dropout on the probabilities with the keep-mask of include/omlm.h (seed, optional device salt seed_dev: int64 [1])."""
-    ab = _attn_bias(bias, N, H, q.device)
-    if p > 0:
-        call("omlm_mqa_attn_fwd_dropout", ptr(q), ptr(k), ptr(v), ptr(ab.table), ptr(ab.tableT), ptr(keymask), ptr(out), ptr(lse),
-             B, N, H, float(scale), ab.table.shape[-1] if ab.table is not None else 0, dcode(q.dtype), float(p), int(seed),
-             ptr(seed_dev), stream_ptr())
-        return
-    call("omlm_mqa_attn_fwd", ptr(q), ptr(k), ptr(v), ptr(ab.table), ptr(ab.tableT), ptr(keymask), ptr(out), ptr(lse),
-         B, N, H, float(scale), ab.table.shape[-1] if ab.table is not None else 0, dcode(q.dtype), stream_ptr())
-
-
-def attn_bwd(q, k, v, bias, keymask, out, dout, lse, delta, dq, dk, dv, dbias, B, N, H, scale, workspace=True, p=0.0, seed=0,
-             seed_dev=None):
-    """bias: the AttnBias the forward used (its tableT carries the reference point lse is relative to), a raw table, or None.
-    workspace=False: d(bias) by device-scope atomics straight into the table (the C ABI's null-workspace form; slower).
-    p, seed, seed_dev: those of the forward (the kernels regenerate its keep-mask)."""
-    ab = _attn_bias(bias, N, H, q.device)
-    bias = ab.table
-    ws = ab.dbias_workspace(B, N, H) if dbias is not None and workspace else None
-    if p > 0:
-        call("omlm_mqa_attn_bwd_dropout", ptr(q), ptr(k), ptr(v), ptr(bias), ptr(ab.tableT), ptr(keymask), ptr(out), ptr(dout), ptr(lse),
-             ptr(delta), ptr(dq), ptr(dk), ptr(dv), ptr(dbias), ptr(ws), B, N, H, float(scale),
-             bias.shape[-1] if bias is not None else 0, dcode(q.dtype), float(p), int(seed), ptr(seed_dev), stream_ptr())
-        return
-    call("omlm_mqa_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(bias), ptr(ab.tableT), ptr(keymask), ptr(out), ptr(dout), ptr(lse),
-         ptr(delta), ptr(dq), ptr(dk), ptr(dv), ptr(dbias), ptr(ws), B, N, H, float(scale),
-         bias.shape[-1] if bias is not None else 0, dcode(q.dtype), stream_ptr())
-
-
-def attn_fwd_prefix(q, k, v, bias, keymask, out, lse, B, N, H, scale, P, p=0.0, seed=0, seed_dev=None):
-    """Attention with a non-causal prefix of P >= 1 rows (omlm_mqa_attn_fwd_prefix): score (i, j) is live iff j <= i or i, j < P.
-    bias: an AttnBias of the prefix layout (AttnBias.group(..., P=P)), the plain [N + min(P, N) - 1, ld] fp32 rel-pos table (row
-    i - j + min(P, N) - 1, relpos_forward with P), or None."""
-    table, tableT = (bias.table, bias.tableT) if isinstance(bias, AttnBias) else (bias, None)
-    call("omlm_mqa_attn_fwd_prefix", ptr(q), ptr(k), ptr(v), ptr(table), ptr(tableT), ptr(keymask), ptr(out), ptr(lse), B, N, H, float(scale),
+    table, tableT = _attn_tables(bias, N, H, P, q.device)
+    call("omlm_mqa_attn_fwd", ptr(q), ptr(k), ptr(v), ptr(table), ptr(tableT), ptr(keymask), ptr(out), ptr(lse), B, N, H, float(scale),
          table.shape[-1] if table is not None else 0, dcode(q.dtype), int(P), float(p), int(seed), ptr(seed_dev), stream_ptr())
 
 
-def attn_bwd_prefix(q, k, v, bias, keymask, out, dout, lse, delta, dq, dk, dv, dtable, B, N, H, scale, P, workspace=True, p=0.0, seed=0,
-                    seed_dev=None):
-    """Backward of attn_fwd_prefix (bias: the forward's).  dtable: the plain table's layout (accumulated, +=), or None."""
-    table, tableT = (bias.table, bias.tableT) if isinstance(bias, AttnBias) else (bias, None)
-    ws = None
-    if dtable is not None and workspace:
-        n = int(hip.lib().omlm_mqa_attn_bwd_workspace_bytes(B, N, H)) // 4
-        key = str(q.device)
-        ws = _DBIAS_WS.get(key)
-        if ws is None or ws.numel() < n:
-            if ws is not None:
-                _DBIAS_RETIRED.append(ws)                       # (see AttnBias.dbias_workspace: a captured graph may hold it)
-            ws = _DBIAS_WS[key] = torch.empty(n, device=q.device, dtype=torch.float32)
-    ld = table.shape[-1] if table is not None else (dtable.shape[-1] if dtable is not None else 0)
-    call("omlm_mqa_attn_bwd_prefix", ptr(q), ptr(k), ptr(v), ptr(table), ptr(tableT), ptr(keymask), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dq),
-         ptr(dk), ptr(dv), ptr(dtable), ptr(ws), B, N, H, float(scale), ld, dcode(q.dtype), int(P), float(p), int(seed), ptr(seed_dev),
+def attn_bwd(q, k, v, bias, keymask, out, dout, lse, delta, dq, dk, dv, dbias, B, N, H, scale, P=0, workspace=True, p=0.0, seed=0,
+             seed_dev=None):
+    """Backward of attn_fwd.  bias: the forward's (an AttnBias: its tableT carries the reference point lse is relative to).  dbias: the raw
+    table's layout (accumulated, +=), or None.  workspace=False: d(bias) by device-scope atomics straight into the table (the C ABI's
+    null-workspace form; slower).  P, p, seed, seed_dev: those of the forward (the kernels regenerate its keep-mask)."""
+    table, tableT = _attn_tables(bias, N, H, P, q.device)
+    ws = _dbias_workspace(B, N, H, q.device) if dbias is not None and workspace else None
+    ld = table.shape[-1] if table is not None else (dbias.shape[-1] if dbias is not None else 0)
+    call("omlm_mqa_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(table), ptr(tableT), ptr(keymask), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dq),
+         ptr(dk), ptr(dv), ptr(dbias), ptr(ws), B, N, H, float(scale), ld, dcode(q.dtype), int(P), float(p), int(seed), ptr(seed_dev),
          stream_ptr())
+
+
+# the former prefix wrappers' names: their arguments were these, P in the same place
+attn_fwd_prefix, attn_bwd_prefix = attn_fwd, attn_bwd
 
 
 def attn_dropout_keep(B, N, H, p, seed, seed_dev=None, device=None) -> torch.Tensor:
@@ -777,6 +748,7 @@ def rvq_encode(x, codebooks_T, indices, residual_out, n, D, C_, nstage, idx_stri
 
 def nearest_centroid(x, centroids_T, indices, n, D, C_):
     """k-means assign (sklearn MiniBatchKMeans.predict, hf_hubert_kmeans.py:87): squared-difference form; indices int32 [n]."""
+    hip.require_gpu(x, "x")                 # a CPU tensor's address would reach the kernel
     call("omlm_nearest_centroid", ptr(x), ptr(centroids_T), ptr(indices), n, D, C_, stream_ptr())
 
 

@@ -117,7 +117,9 @@ def test_attention_dropout_fwd_bwd(ops, dev, dtype, B, N, H, p):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
-def test_dropout_entries_at_p0_equal_the_plain_entries(ops, dev, dtype):
+def test_attn_at_p0_ignores_seed_and_salt(ops, dev, dtype):
+    """p = 0 is no dropout whatever the seed and salt: omlm_mqa_attn_fwd / _bwd with p = 0, seed 77 and a device salt give what the
+    default call (p = 0, seed 0, no salt) gives."""
     from open_musiclm_amd import hip
     from open_musiclm_amd.hip import call, ptr, stream_ptr
     B, N, H = 2, 150, 3
@@ -128,23 +130,17 @@ def test_dropout_entries_at_p0_equal_the_plain_entries(ops, dev, dtype):
     v = torch.randn(M, 64, generator=g).to(dev, dtype)
     bias = torch.randn(N, 8, generator=g).to(dev)
     ab = ops.AttnBias(bias, N, H, dev)
+    salt = torch.tensor([5], dtype=torch.int64, device=dev)
     outs = []
-    for new in (False, True):
+    for seed, seed_dev in ((0, None), (77, salt)):
         out = torch.empty(M, H * 64, device=dev, dtype=dtype); lse = torch.empty(B, H, N, device=dev)
-        args = [ptr(q), ptr(k), ptr(v), ptr(bias), ptr(ab.tableT), None, ptr(out), ptr(lse), B, N, H, 8.0, 8, ops.dcode(dtype)]
-        if new:
-            call("omlm_mqa_attn_fwd_dropout", *args, 0.0, 77, None, stream_ptr())
-        else:
-            call("omlm_mqa_attn_fwd", *args, stream_ptr())
+        call("omlm_mqa_attn_fwd", ptr(q), ptr(k), ptr(v), ptr(bias), ptr(ab.tableT), None, ptr(out), ptr(lse), B, N, H, 8.0, 8, ops.dcode(dtype),
+             0, 0.0, seed, ptr(seed_dev), stream_ptr())
         do = torch.randn(M, H * 64, generator=g).to(dev, dtype) if not outs else outs[0][-1]
         dq = torch.empty(M, H * 64, device=dev); dk = torch.empty(M, 64, device=dev); dv = torch.empty(M, 64, device=dev)
         db = torch.zeros(N, 8, device=dev); delta = torch.empty(B, H, N, device=dev)
-        bargs = [ptr(q), ptr(k), ptr(v), ptr(bias), ptr(ab.tableT), None, ptr(out), ptr(do), ptr(lse), ptr(delta), ptr(dq), ptr(dk),
-                 ptr(dv), ptr(db), None, B, N, H, 8.0, 8, ops.dcode(dtype)]
-        if new:
-            call("omlm_mqa_attn_bwd_dropout", *bargs, 0.0, 77, None, stream_ptr())
-        else:
-            call("omlm_mqa_attn_bwd", *bargs, stream_ptr())
+        call("omlm_mqa_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(bias), ptr(ab.tableT), None, ptr(out), ptr(do), ptr(lse), ptr(delta), ptr(dq),
+             ptr(dk), ptr(dv), ptr(db), None, B, N, H, 8.0, 8, ops.dcode(dtype), 0, 0.0, seed, ptr(seed_dev), stream_ptr())
         outs.append((out, lse, dq, dk, dv, db, do))
     # out, lse and dQ are written without atomics: the same bits; dK / dV / d(bias) are summed with float atomics in a run-dependent order
     for a, b in zip(outs[0][:3], outs[1][:3]):

@@ -1,6 +1,6 @@
 """Non-causal prefix (non_causal_prefix_size = P > 0) on the GPU.
 
-  (1) the prefix attention entries against fp64 torch with the same mask and bias, fp32 / bf16 / fp16 operands, with and without a key
+  (1) the attention entries with P >= 1 against fp64 torch with the same mask and bias, fp32 / bf16 / fp16 operands, with and without a key
       mask, continuous / t5 / no bias, once with dropout (the keep-mask of omlm_attn_dropout_keep): out, lse, dQ, dK, dV and d(bias),
       the negative-distance rows included;
   (2) the prefix is really non-causal: the id at row P - 1 moves the logits of row 0, and at P = 0 it does not;
@@ -108,14 +108,14 @@ def _kernel_case(ops, dev, dtype, B, N, H, P, kind, masked, p=0.0, form="raw"):
         assert bool((tail[:, -2] == 1.0).all()) == (form == "fixed"), "the bound did not select the intended softmax form"
     out = torch.empty(M, H * 64, device=dev, dtype=dtype)
     lse = torch.empty(B, H, N, device=dev)
-    ops.attn_fwd_prefix(q, k, v, ab, km8, out, lse, B, N, H, 8.0, P, p=p, seed=seed, seed_dev=salt if p > 0 else None)
+    ops.attn_fwd(q, k, v, ab, km8, out, lse, B, N, H, 8.0, P=P, p=p, seed=seed, seed_dev=salt if p > 0 else None)
     dq = torch.empty(M, H * 64, device=dev)
     dk = torch.empty(M, 64, device=dev)
     dv = torch.empty(M, 64, device=dev)
     delta = torch.empty(B, H, N, device=dev)
     dtab = torch.zeros_like(table) if table is not None else None
-    ops.attn_bwd_prefix(q, k, v, ab, km8, out, do.reshape(M, -1).to(dtype), lse, delta, dq, dk, dv, dtab, B, N, H, 8.0, P,
-                        p=p, seed=seed, seed_dev=salt if p > 0 else None)
+    ops.attn_bwd(q, k, v, ab, km8, out, do.reshape(M, -1).to(dtype), lse, delta, dq, dk, dv, dtab, B, N, H, 8.0, P=P,
+                 p=p, seed=seed, seed_dev=salt if p > 0 else None)
     torch.cuda.synchronize()
     errs = dict(fwd=relerr(out.view(B, N, -1), ref), lse=float((lse.double().cpu() - ref_lse.detach().cpu()).abs().max()),
                 dq=relerr(dq.view(B, N, -1), qr.grad), dk=relerr(dk.view(B, N, -1), kr.grad), dv=relerr(dv.view(B, N, -1), vr.grad))

@@ -64,6 +64,37 @@ def _semantic(P, **kw):
                                          non_causal_prefix_size=P, precision="bf16", **kw)
 
 
+def test_attention_refuses_an_attn_bias_of_another_prefix():
+    """An AttnBias is the prepared table of ONE layout (its P): attn_fwd / attn_bwd refuse it for another P before any launch."""
+    from open_musiclm_amd import ops
+    B, N, H = 1, 40, 2
+    q, out = torch.zeros(B * N, H * 64), torch.zeros(B * N, H * 64)
+    k = v = torch.zeros(B * N, 64)
+    lse = torch.zeros(B, H, N)
+    for made, used in ((0, 14), (14, 0), (14, 13)):
+        ab = ops.AttnBias(torch.zeros(N + min(made, N) - 1 if made else N, 8), N, H, _tableT=torch.zeros(1), _P=made)
+        with pytest.raises(ValueError, match="prepared for P"):
+            ops.attn_fwd(q, k, v, ab, None, out, lse, B, N, H, 8.0, P=used)
+        with pytest.raises(ValueError, match="prepared for P"):
+            ops.attn_bwd(q, k, v, ab, None, out, out, lse, lse, out, k, v, None, B, N, H, 8.0, P=used)
+
+
+def test_attention_entries_refuse_bad_prefix_and_dropout_args():
+    """P < 0 and p outside [0, 1) are refused by the C entries before anything is launched (null tensors here: no GPU needed)."""
+    import os
+    import __graft_entry__ as G
+    from open_musiclm_amd import hip
+    if not os.path.exists(hip.LIB_PATH):
+        G.build()
+    lib = hip.lib()
+    for dtype in (0, 1, 2):
+        for P, p in ((-1, 0.0), (0, 1.0), (3, -0.1), (0, float("nan"))):
+            assert lib.omlm_mqa_attn_fwd(*[None] * 8, 1, 77, 2, 8.0, 8, dtype, P, p, 0, None, None) != 0, (dtype, P, p)
+            assert lib.omlm_mqa_attn_bwd(*[None] * 15, 1, 77, 2, 8.0, 8, dtype, P, p, 0, None, None) != 0, (dtype, P, p)
+    assert lib.omlm_attn_bias_prepare_group(None, None, 1, 77, 2, 8, None, None, 0.0, 8.0, 0, -1, None) != 0
+    assert lib.omlm_attn_bias_table_floats(77, 2, 17) > lib.omlm_attn_bias_table_floats(77, 2, 0)
+
+
 def test_decode_supports_by_prompt_rows():
     from open_musiclm_amd import decode
     causal, pre = _semantic(0), _semantic(14)

@@ -18,14 +18,13 @@
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); exit(1); } } while (0)
 
-typedef int (*fwd_t)(const void*, const void*, const void*, const float*, const float*, const unsigned char*, void*, float*, int, int, int, float, int, int, void*);
+typedef int (*fwd_t)(const void*, const void*, const void*, const float*, const float*, const unsigned char*, void*, float*, int, int, int, float, int, int,
+                     int, float, unsigned long long, const unsigned long long*, void*);
 typedef int (*bwd_t)(const void*, const void*, const void*, const float*, const float*, const unsigned char*, const void*, const void*, const float*, float*,
-                     float*, float*, float*, float*, int, int, int, float, int, int, void*);
-typedef int (*bwdw_t)(const void*, const void*, const void*, const float*, const float*, const unsigned char*, const void*, const void*, const float*, float*,
-                      float*, float*, float*, float*, float*, int, int, int, float, int, int, void*);      // with the d(bias) workspace (round 3c on)
+                     float*, float*, float*, float*, float*, int, int, int, float, int, int, int, float, unsigned long long, const unsigned long long*, void*);
 typedef long long (*bwsz_t)(int, int, int);
-typedef int (*prep_t)(const float*, float*, int, int, int, const float*, const float*, float, float, void*);
-typedef long long (*tbl_t)(int, int);
+typedef int (*prep_t)(const float*, float*, int, int, int, const float*, const float*, float, float, int, void*);
+typedef long long (*tbl_t)(int, int, int);
 typedef int (*gemm_t)(const void*, const void*, void*, const float*, const int*, const int*, const int*, long long, long long, int, int, int, int, int, int, int,
                       int, int, int, int, float, void*, long long, void*);
 typedef const char* (*err_t)(void);
@@ -44,18 +43,17 @@ typedef int (*planes_t)(const void*, long long, const void*, long long, void*, c
                         int, int, int, int, int, int, int, int, int, int, float, void*, long long, void*);
 
 struct Lib {
-    std::string path; void* h; fwd_t fwd; bwd_t bwd; bwdw_t bwdw; bwsz_t bwsz; prep_t prep; tbl_t tbl; gemm_t gemm; err_t err; wgrad_t wgrad; planes_t planes; ffwd_t ffwd; fws_t fws; fbwd_t fbwd; lnf_t lnf; lnws_t lnws; lnb_t lnb; dstep_t dstep;
+    std::string path; void* h; fwd_t fwd; bwd_t bwd; bwsz_t bwsz; prep_t prep; tbl_t tbl; gemm_t gemm; err_t err; wgrad_t wgrad; planes_t planes; ffwd_t ffwd; fws_t fws; fbwd_t fbwd; lnf_t lnf; lnws_t lnws; lnb_t lnb; dstep_t dstep;
     void load(const char* p) {
         path = p;
         h = dlopen(p, RTLD_NOW | RTLD_LOCAL);
         if (!h) { fprintf(stderr, "dlopen %s: %s\n", p, dlerror()); exit(1); }
-        fwd = (fwd_t)dlsym(h, "omlm_mqa_attn_fwd"); bwd = (bwd_t)dlsym(h, "omlm_mqa_attn_bwd"); bwdw = (bwdw_t)dlsym(h, "omlm_mqa_attn_bwd");
-        bwsz = (bwsz_t)dlsym(h, "omlm_mqa_attn_bwd_workspace_bytes");       // absent in libraries older than the workspace form
+        fwd = (fwd_t)dlsym(h, "omlm_mqa_attn_fwd"); bwd = (bwd_t)dlsym(h, "omlm_mqa_attn_bwd"); bwsz = (bwsz_t)dlsym(h, "omlm_mqa_attn_bwd_workspace_bytes");
         prep = (prep_t)dlsym(h, "omlm_attn_bias_prepare"); tbl = (tbl_t)dlsym(h, "omlm_attn_bias_table_floats");
         gemm = (gemm_t)dlsym(h, "omlm_gemm"); err = (err_t)dlsym(h, "omlm_last_error"); wgrad = (wgrad_t)dlsym(h, "omlm_gemm_wgrad_group"); planes = (planes_t)dlsym(h, "omlm_gemm_planes");
         ffwd = (ffwd_t)dlsym(h, "omlm_ffmid_fwd"); fws = (fws_t)dlsym(h, "omlm_ffmid_bwd_workspace_bytes"); fbwd = (fbwd_t)dlsym(h, "omlm_ffmid_bwd");
         lnf = (lnf_t)dlsym(h, "omlm_layernorm_fwd"); lnws = (lnws_t)dlsym(h, "omlm_layernorm_bwd_workspace_bytes"); lnb = (lnb_t)dlsym(h, "omlm_layernorm_bwd"); dstep = (dstep_t)dlsym(h, "omlm_decode_step");
-        if (!fwd || !bwd || !prep || !tbl || !gemm || !err) { fprintf(stderr, "%s: missing symbol\n", p); exit(1); }
+        if (!fwd || !bwd || !bwsz || !prep || !tbl || !gemm || !err) { fprintf(stderr, "%s: missing symbol\n", p); exit(1); }
     }
     void ok(int rc, const char* what) { if (rc != 0) { fprintf(stderr, "%s: %s failed (%d): %s\n", path.c_str(), what, rc, err()); exit(1); } }
 };
@@ -136,16 +134,16 @@ static void attn_case(Lib& A, Lib& Bl, int B, int N, int H, int dtype = 1) {
     for (int li = 0; li < 2; ++li) {
         Lib& L = *libs[li];
         apply_env(li ? g_env_b : g_env_a);
-        const long long tf = L.tbl(N, H);
+        const long long tf = L.tbl(N, H, 0);
         float* biasT = dev_zero<float>((size_t)tf);
-        L.ok(L.prep(dbias_in, biasT, N, H, ld, nullptr, nullptr, 1.0f, scale, nullptr), "bias_prepare");
-        L.ok(L.fwd(dq_, dk_, dv_, dbias_in, biasT, dmask, out, lse, B, N, H, scale, ld, dtype, nullptr), "attn_fwd");
+        L.ok(L.prep(dbias_in, biasT, N, H, ld, nullptr, nullptr, 1.0f, scale, 0, nullptr), "bias_prepare");
+        L.ok(L.fwd(dq_, dk_, dv_, dbias_in, biasT, dmask, out, lse, B, N, H, scale, ld, dtype, 0, 0.f, 0ull, nullptr, nullptr), "attn_fwd");
         CK(hipDeviceSynchronize());
         float *gq = dev_zero<float>(M * H * 64), *gk = dev_zero<float>(M * 64), *gv = dev_zero<float>(M * 64), *gb = dev_zero<float>((size_t)N * ld);
-        float* wsb = L.bwsz && !getenv("LIB_AB_NO_DBIAS_WS") ? dev_zero<float>((size_t)L.bwsz(B, N, H) / 4) : nullptr;
+        float* wsb = !getenv("LIB_AB_NO_DBIAS_WS") ? dev_zero<float>((size_t)L.bwsz(B, N, H) / 4) : nullptr;
         auto bwd_call = [&](float* gbias) {
-            return L.bwsz ? L.bwdw(dq_, dk_, dv_, dbias_in, biasT, dmask, out, ddo, lse, delta, gq, gk, gv, gbias, wsb, B, N, H, scale, ld, dtype, nullptr)
-                          : L.bwd(dq_, dk_, dv_, dbias_in, biasT, dmask, out, ddo, lse, delta, gq, gk, gv, gbias, B, N, H, scale, ld, dtype, nullptr);
+            return L.bwd(dq_, dk_, dv_, dbias_in, biasT, dmask, out, ddo, lse, delta, gq, gk, gv, gbias, wsb, B, N, H, scale, ld, dtype, 0, 0.f, 0ull,
+                         nullptr, nullptr);
         };
         L.ok(bwd_call(gb), "attn_bwd");
         CK(hipDeviceSynchronize());
@@ -153,7 +151,7 @@ static void attn_case(Lib& A, Lib& Bl, int B, int N, int H, int dtype = 1) {
         float* scratch_b = dev_zero<float>((size_t)N * ld);
         us[li] = time_us([&] { bwd_call(scratch_b); }, 10);
         us_nb[li] = time_us([&] { bwd_call(nullptr); }, 10);
-        fwd_us[li] = time_us([&] { L.fwd(dq_, dk_, dv_, dbias_in, biasT, dmask, out, lse, B, N, H, scale, ld, dtype, nullptr); }, 10);
+        fwd_us[li] = time_us([&] { L.fwd(dq_, dk_, dv_, dbias_in, biasT, dmask, out, lse, B, N, H, scale, ld, dtype, 0, 0.f, 0ull, nullptr, nullptr); }, 10);
         CK(hipFree(gq)); CK(hipFree(gk)); CK(hipFree(gv)); CK(hipFree(gb)); CK(hipFree(scratch_b)); CK(hipFree(biasT)); if (wsb) CK(hipFree(wsb));
     }
     const double flops = 4.0 * H * 64 * (double)N * (N + 1) / 2 * B;
