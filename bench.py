@@ -2,7 +2,7 @@
 """Benchmark of the MI355X TokenConditionedTransformer hot path (BASELINE.json metric:
 "train steps/sec + AR tokens/sec, coarse-stage musiclm_small, 1/2/4/8 MI355X").
 
-    python bench.py --gpus N --steps K --warmup W [--precision fp16|bf16|bf16x3] [--batch B] [--accum A] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--precision fp16|bf16|bf16x3] [--batch B] [--accum A] [--dump-outputs DIR] [--full]
 
 One "step" = one optimizer step of the coarse stage of musiclm_small (dim 1024, depth 6, heads 8, conv-GEGLU FF,
 N = 1116 positions = 3 start + 13 clap + 200 semantic + 900 coarse ids -- the exact length the reference's data
@@ -16,8 +16,11 @@ round 5: IEEE-half operands everywhere, with the forward of the two ConvFeedForw
 products; the two linears carry 86-88 % of the fp16 logits-error variance) -- the mode whose logits meet north_star's 1e-3 against the CPU reference
 WITH MARGIN at both model depths (1.3e-4 .. 1.8e-4 over 5 seeds at this model, 1.6e-4 at the benchmarked batch; 4.6e-4 .. 5.5e-4 at musiclm_large
 depth 24), at 1.3x the fp16 step.  Plain fp16 measures 8.7e-4 .. 9.8e-4 here (inside 1e-3 by a few per cent) and 1.6e-3 at depth 24; bf16, the dtype the
-config names, 7e-3 .. 8e-3.  At N = 1 the same JSON line carries, under "legs", the other modes and configurations of BASELINE.json measured
-in the same run:
+config names, 7e-3 .. 8e-3.
+
+A plain run does only what `value` needs: it sets up, warms up, times the K steps, writes --dump-outputs and prints the JSON line.
+With --full it also measures everything below.  At N = 1 the line then carries, under "legs", the other modes and configurations of
+BASELINE.json measured in the same run:
   legs.fp16         the same train step in plain fp16 (logits 8.7e-4 .. 9.8e-4: inside the tolerance at this depth, without margin)
   legs.bf16         the same train step with bf16 operands (the dtype BASELINE config 2 names; logits 7e-3 .. 8e-3: outside the tolerance)
   legs.bf16x3       the same train step with fp32 operands split hi/lo on the bf16 matrix cores (fp32-grade products)
@@ -415,6 +418,9 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="samples per GPU per optimizer step")
     ap.add_argument("--accum", type=int, default=1, help="micro-batches per optimizer step")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying the captured HIP graph")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the CPU baseline (before the "
+                                                         "headline steps), the GEMM roofline, coarse decode and the other legs (after them); "
+                                                         "the --no-* / --legs options below pick among them")
     ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-legs", action="store_true", help="skip the fp16 / bf16x3 / large_fine / e2e_generate legs")
@@ -453,11 +459,11 @@ def main():
     dev = torch.device("cuda", dev_index)
     dp = DataParallel(device=dev)
     rank = dp.rank
-    legs = [] if (args.no_legs or world > 1) else [l for l in args.legs.split(",") if l]
+    legs = [] if (not args.full or args.no_legs or world > 1) else [l for l in args.legs.split(",") if l]
 
     # ---- CPU baseline first (rank 0, N = 1): the GPU regions then run back to back at the end of the process
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress(f"cpu baseline on {torch.get_num_threads()} torch threads (os.cpu_count()={os.cpu_count()})")
         cpu = cpu_baseline(progress)
 
@@ -497,7 +503,7 @@ def main():
                                 f"one flat fp32 SUM all-reduce per step, torch.distributed backend {torch.distributed.get_backend()}"
                                 + (" -- DRY RUN: ranks share a GPU, not an RCCL / xGMI measurement" if dp.shared_gpu else " (RCCL over xGMI)")),
                    "parity": parity[args.precision] + " (tests/test_gpu_model.py)",
-                   "other_modes": "legs.fp16 (~0.78x this step; logits 8.7e-4 .. 9.8e-4: inside 1e-3 without margin, 1.6e-3 at depth 24), "
+                   "other_modes": "with --full: legs.fp16 (~0.78x this step; logits 8.7e-4 .. 9.8e-4: inside 1e-3 without margin, 1.6e-3 at depth 24), "
                                   "legs.bf16 (the dtype BASELINE config 2 names: ~0.75x this step, logits 7e-3 .. 8e-3 -- outside north_star's 1e-3), "
                                   "legs.bf16x3 (fp32-grade products everywhere, ~2x this step)"},
         "steps_per_sec": round(steps_per_s, 4),
@@ -516,7 +522,7 @@ def main():
             tc = time.perf_counter()
             progress(f"diagnostic step {k}: host enqueue {1e3 * (tb - ta):.1f} ms, until GPU idle {1e3 * (tc - ta):.1f} ms")
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # HBM-side bytes of the same launches (all GEMMs of one step) from the committed PMC passes of tools/pmc_gemm_traffic.sh
         # (separate FETCH_SIZE / WRITE_SIZE runs; counters cannot be read inside this process): B = 32 bf16 only
         traffic = detail = None
@@ -612,6 +618,7 @@ def main():
             if args.precision != "bf16":                   # the dtype BASELINE config 5's sibling configs name, for comparison (outside the tolerance)
                 out["legs"]["e2e_generate_bf16"] = e2e_generate_leg(dev, precision="bf16")
                 progress(f"e2e generate leg, bf16: {out['legs']['e2e_generate_bf16']['ids_per_sec']} ids/s")
+    if rank == 0:
         print(json.dumps(out), flush=True)
     dp.barrier()
     dp.shutdown()

@@ -1080,6 +1080,29 @@ def test_bench_self_launches_without_a_launcher(dev):
     assert np.isfinite(out["final_loss"])
 
 
+def test_bench_plain_run_measures_only_the_headline(dev):
+    """A plain `bench.py --gpus 1` run sets up, warms up, times its steps and prints the headline line; the GEMM roofline probe, decode,
+    the CPU baseline and the other legs come with --full (here without the CPU baseline and the legs, the slow part of --full)."""
+    import subprocess
+    import sys
+
+    def bench_line(*extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", *extra],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0])
+    out = bench_line()
+    assert out["unit"] == "samples/s" and out["higher_is_better"] is True and out["dtype"] == out["config"]["precision"]
+    assert abs(out["value"] - 2 / (out["ms_per_step"] * 1e-3)) < 1e-2 * out["value"] and np.isfinite(out["final_loss"])
+    assert not {"roofline", "ar_tokens_per_sec", "cpu_baseline", "legs"} & set(out)
+    full = bench_line("--full", "--no-cpu-baseline", "--no-legs", "--decode-ids", "3")
+    assert full["roofline"]["launches"] > 0 and full["roofline"]["achieved"] > 0
+    assert full["ar_tokens_per_sec"]["kv_cache_empty_context"] > 0
+    assert "cpu_baseline" not in full and "legs" not in full
+
+
 @pytest.mark.parametrize("stage,B", [("coarse", 5), ("fine", 2), ("semantic", 3)])
 def test_fused_batch_preparation_equals_the_torch_path(dev, stage, B, monkeypatch):
     """omlm_prepare_train_batch (one launch) against the wrapper's torch construction (open_musiclm.py:340-376 + :116-130 + utils.py:49-56

@@ -2,7 +2,7 @@
 # same-box A/B of the training step under environment levers:  tools/env_ab.sh <outdir> VAR=a VAR=b ...   (each setting twice, interleaved)
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/$1; shift; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-legs --no-decode --steps 20 --warmup 5"
+B="python bench.py --full --no-cpu-baseline --no-legs --no-decode --steps 20 --warmup 5"
 for rep in 1 2; do for kv in "$@"; do
   echo -n "$kv  " | tee -a $O/env_ab.log
   env $kv timeout 300 $B 2>/dev/null | python -c "

@@ -5,7 +5,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R; mkdir -p gpurun_out
 for c in FETCH_SIZE WRITE_SIZE; do
-  rm -rf /tmp/ph_$c; timeout 600 rocprofv3 --pmc $c -d /tmp/ph_$c -o p --output-format csv -- python bench.py --steps 2 --warmup 1 --no-decode --no-cpu-baseline --no-legs --no-graph > /tmp/ph_$c.log 2>&1
+  rm -rf /tmp/ph_$c; timeout 600 rocprofv3 --pmc $c -d /tmp/ph_$c -o p --output-format csv -- python bench.py --full --steps 2 --warmup 1 --no-decode --no-cpu-baseline --no-legs --no-graph > /tmp/ph_$c.log 2>&1
 done
 python - <<'PY'
 import csv, glob, collections, re

@@ -2,7 +2,7 @@
 # one SQ counter pass over a short eager training run; prints per-kernel means for the non-GEMM kernels
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
-rm -rf /tmp/pmcs; timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_LDS SQ_ACTIVE_INST_LDS -d /tmp/pmcs -o p --output-format csv -- python bench.py --steps 2 --warmup 1 --no-decode --no-cpu-baseline --no-graph > /tmp/pmcs.log 2>&1
+rm -rf /tmp/pmcs; timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_LDS SQ_ACTIVE_INST_LDS -d /tmp/pmcs -o p --output-format csv -- python bench.py --full --steps 2 --warmup 1 --no-decode --no-cpu-baseline --no-graph > /tmp/pmcs.log 2>&1
 python - <<'PY'
 import csv, glob, collections
 rows = []

@@ -2,7 +2,7 @@
 # same-box A/B of the training step: library variants / environment levers, one bench line each
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/${1:-r4ab}; mkdir -p $O
-B="python bench.py --no-cpu-baseline --no-legs --no-decode --steps 20 --warmup 5"
+B="python bench.py --full --no-cpu-baseline --no-legs --no-decode --steps 20 --warmup 5"
 run() { name=$1; shift; echo "== $name" | tee -a $O/step_ab.log; env "$@" timeout 300 $B 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
