@@ -384,6 +384,37 @@ int omlm_vq_kmeans_update(float* means, float* means_T, const float* counts, con
 int omlm_vq_ema_update(float* cluster_size, float* embed_avg, float* embed, float* embed_T, const float* counts, const float* sums,
                        float* total_scratch, int K, int D, float decay, float eps, void* stream);
 
+/* Fitting the semantic k-means codebook (reference: hf_hubert_kmeans.py:95-149, sklearn's MiniBatchKMeans on the host; these entry
+ * points run the published MiniBatchKMeans rules on the device, csrc/kmeans_fit.hip, driven by open_musiclm_amd/kmeans_fit.py).
+ * k-means++ on rows [m, D] (16-byte aligned): pick number *pick_counter (a device int, advanced by the call) draws `trials` (<= 16)
+ * candidates from uniforms[pick * trials + t] by inverse CDF over closest [m]: cum_i = sum_{j <= i} closest_j in fp64, candidate =
+ * the first row with cum_i > u * cum_{m-1} (rows of weight zero are never drawn), clipped to m - 1; pick 0 takes row
+ * min(floor(uniforms[0] * m), m - 1) and resets closest.  The candidate with the lowest potential sum_i min(closest_i, d_i) (fp64,
+ * fixed order; ties: first) becomes centres[pick] (and column `pick` of centres_T [D, K]); chosen[pick] / pots[pick] record its row and
+ * potential; closest takes the minimum.  Three launches per pick, no host round trip; omlm_kmeans_pp_seed zeroes the counter and queues
+ * all K picks.  workspace: omlm_kmeans_pp_workspace_bytes(m, trials) bytes, 16-byte aligned.  Same draws -> same bits. */
+long long omlm_kmeans_pp_workspace_bytes(int m, int trials);
+int omlm_kmeans_pp_pick(const float* rows, float* closest, const float* uniforms, int* pick_counter, float* centres, float* centres_T,
+                        int* chosen, double* pots, void* workspace, long long workspace_bytes, int m, int D, int K, int trials,
+                        void* stream);
+int omlm_kmeans_pp_seed(const float* rows, float* closest, const float* uniforms, int* pick_counter, float* centres, float* centres_T,
+                        int* chosen, double* pots, void* workspace, long long workspace_bytes, int m, int D, int K, int trials,
+                        void* stream);
+/* One mini-batch step on rows x[idx[0 .. B)] of x [n, D] (out-of-range indices take no part): assignment in the arithmetic of
+ * omlm_nearest_centroid, then for every centre that received m_k rows: counts_k += m_k; c_k += (sum_k - m_k c_k) / counts_k (centres_T
+ * refreshed).  bcounts [K] and sums [K, D] are scratch that is zero on entry and zero again on return; rowmin [B], move_partial [K]
+ * (fp64) scratch.  state: 8 fp64 on the device, zero before the first step: [0] ewa inertia, [1] its minimum, [2] this batch's mean
+ * inertia (centres before the update), [3] squared centre movement, [4] steps done, [5] steps without improvement, [6] stopped (1: no
+ * improvement for max_no_improvement steps, 2: movement <= tol_abs; tol_abs = 0 / max_no_improvement = 0 switch a rule off), [7]
+ * internal.  The rules are sklearn's _mini_batch_convergence (alpha = min(1, 2 B / (n + 1)) is the caller's).  A step that finds
+ * state[6] != 0 changes nothing, so steps may be queued ahead of the host's look at the state. */
+int omlm_kmeans_minibatch_step(const float* x, const int* idx, float* centres, float* centres_T, float* counts, float* bcounts,
+                               float* sums, float* rowmin, double* move_partial, double* state, int n, int B, int D, int K,
+                               double alpha, double tol_abs, int max_no_improvement, void* stream);
+/* out[0] += sum_i min_k |x_i - c_k|^2 over x [n, D] (fp64 on the device, one atomic per workgroup; the caller zeroes out); labels
+ * (int32 [n], may be NULL) receives the assignment, equal to omlm_nearest_centroid's. */
+int omlm_kmeans_inertia(const float* x, const float* centres_T, double* out, int* labels, int n, int D, int K, void* stream);
+
 /* AR sampler: eos suppression + top_k(thres) + gumbel_sample (open_musiclm.py:309-316; utils.py:65-84).
  * Kept set: every logit strictly above the k-th largest value, then of the logits equal to it the lowest indices until exactly k are
  * kept.  Id: the first maximum of l / T + Gumbel(u) over the kept set (0 when every kept logit is -inf).  The same rule holds for

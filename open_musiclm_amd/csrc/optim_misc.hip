@@ -1,5 +1,6 @@
 // Optimizer step, casts/repacks, small element-wise helpers, quantizer argmin and a hardware probe.
 #include "common.h"
+#include "vq_nearest.h"
 #include <string.h>
 #include <math.h>
 
@@ -860,20 +861,14 @@ __global__ __launch_bounds__(256) void rvq_kernel(const float* __restrict__ x, c
     __syncthreads();
     for (int s = 0; s < nstage; ++s) {
         const float* cb = cbT + (size_t)s * D * C;
-        float best = INFINITY;
-        int besti = 0x7fffffff;
-        float x2 = 0.f;
-        if (FORM == FORM_CDIST)                   // every thread forms the same sequential sum (LDS broadcast reads)
+        float bestv[1] = {INFINITY};
+        int bestiv[1] = {0x7fffffff};
+        if (FORM == FORM_SQ) {
+            sq_nearest_thread_rows<1>(r, cb, D, C, bestv, bestiv);                  // vq_nearest.h (shared with kmeans_fit.hip)
+        } else {
+            float x2 = 0.f;                       // every thread forms the same sequential sum (LDS broadcast reads)
             for (int d = 0; d < D; ++d) x2 = __fadd_rn(x2, __fmul_rn(r[d], r[d]));
-        for (int c = threadIdx.x; c < C; c += 256) {
-            float dist;
-            if (FORM == FORM_SQ) {
-                dist = 0.f;
-                for (int d = 0; d < D; ++d) {
-                    const float diff = __fsub_rn(r[d], cb[(size_t)d * C + c]);
-                    dist = __fadd_rn(dist, __fmul_rn(diff, diff));
-                }
-            } else {
+            for (int c = threadIdx.x; c < C; c += 256) {
                 float xy = 0.f, e2 = 0.f;
                 for (int d = 0; d < D; ++d) {
                     const float e = cb[(size_t)d * C + c];
@@ -882,22 +877,18 @@ __global__ __launch_bounds__(256) void rvq_kernel(const float* __restrict__ x, c
                 }
                 // IEEE root: through fp64 (a correctly rounded fp64 root rounded to fp32 IS the correctly rounded fp32 root: 53 >= 2 * 24 + 2);
                 // HIP's __fsqrt_rn is the native 1-ulp v_sqrt_f32, which keeps root-merged near-ties apart
-                dist = (float)sqrt((double)fmaxf(__fsub_rn(__fadd_rn(x2, e2), __fmul_rn(2.f, xy)), 0.f));
+                const float dist = (float)sqrt((double)fmaxf(__fsub_rn(__fadd_rn(x2, e2), __fmul_rn(2.f, xy)), 0.f));
+                if (dist < bestv[0]) { bestv[0] = dist; bestiv[0] = c; }      // ascending c per thread: strict < keeps the lowest index
             }
-            if (dist < best) { best = dist; besti = c; }      // ascending c per thread: strict < keeps the lowest index
         }
-        // lexicographic (dist, index) min over the block
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float od = __shfl_xor(best, o, 64);
-            const int oi = __shfl_xor(besti, o, 64);
-            if (od < best || (od == best && oi < besti)) { best = od; besti = oi; }
-        }
+        float best = bestv[0];
+        int besti = bestiv[0];
+        wave_lexmin(best, besti);                 // lexicographic (dist, index) min over the block
         if ((threadIdx.x & 63) == 0) { bd[threadIdx.x >> 6] = best; bi[threadIdx.x >> 6] = besti; }
         __syncthreads();
         if (threadIdx.x == 0) {
-            float b = bd[0]; int i0 = bi[0];
-            for (int w = 1; w < 4; ++w) if (bd[w] < b || (bd[w] == b && bi[w] < i0)) { b = bd[w]; i0 = bi[w]; }
+            float b; int i0;
+            lexmin4(bd, bi, b, i0);
             chosen = i0;
             idx_out[(size_t)row * idx_stride + s] = i0;
         }

@@ -2,7 +2,8 @@
 pretrained third-party network outside the hot path; the k-means ASSIGN step (:87, sklearn predict) runs as a
 HIP nearest-centroid kernel, bit-exact against oracle.kmeans_assign.  The FIT (:98-149, what scripts/train_hubert_kmeans.py drives
 through HfHubertKmeansTrainer) is sklearn's MiniBatchKMeans in the reference; it is the same call here, so a fit on the same
-features and seed yields the reference's centroids bit for bit (tests/golden/kmeans_fit.npz, produced by the reference itself)."""
+features and seed yields the reference's centroids bit for bit (tests/golden/kmeans_fit.npz, produced by the reference itself).
+`learn_kmeans(..., device='cuda')` fits on the device instead (kmeans_fit.py / csrc/kmeans_fit.hip): same rules, own random stream."""
 from __future__ import annotations
 
 from typing import Optional
@@ -90,10 +91,43 @@ def get_kmeans_model(n_clusters, init, max_iter, batch_size, tol, max_no_improve
                            reassignment_ratio=reassignment_ratio)
 
 
+class FittedKmeans:
+    """What `learn_kmeans(..., device=...)` dumps with joblib: plain host data (numpy centres and scalars, no device tensors, no library
+    handles), so it loads on a machine without a GPU.  `get_hubert_kmeans(kmeans_path=...)` / `HfHubertWithKmeans(kmeans=...)` read
+    `cluster_centers_`, as they do of sklearn's estimator."""
+
+    def __init__(self, cluster_centers_, inertia_, n_steps_, counts_, seed=0, params=None):
+        import numpy as np
+        self.cluster_centers_ = np.ascontiguousarray(cluster_centers_, dtype=np.float32)
+        self.inertia_ = float(inertia_)
+        self.n_steps_ = int(n_steps_)
+        self.counts_ = np.ascontiguousarray(counts_, dtype=np.float32)
+        self.n_features_in_ = int(self.cluster_centers_.shape[1])
+        self.seed = int(seed)
+        self.params = dict(params or {})
+
+    def __repr__(self):
+        return (f"FittedKmeans(n_clusters={self.cluster_centers_.shape[0]}, n_features={self.n_features_in_}, "
+                f"inertia={self.inertia_:.5f}, n_steps={self.n_steps_})")
+
+
 def learn_kmeans(feat, seed, km_path='./results/kmeans.joblib', n_clusters=1024, init="k-means++", max_iter=100, batch_size=10000,
-                 tol=0.0, n_init=20, reassignment_ratio=0.0, max_no_improvement=100, verbose=1):
-    """hf_hubert_kmeans.py:121-149: seeds numpy's global RNG (the estimator has random_state=None), fits, dumps with joblib."""
+                 tol=0.0, n_init=20, reassignment_ratio=0.0, max_no_improvement=100, verbose=1, device=None):
+    """hf_hubert_kmeans.py:121-149: seeds numpy's global RNG (the estimator has random_state=None), fits, dumps with joblib.
+    `device=None`: that call, sklearn on the host.  `device='cuda'` (or a torch.device): the same MiniBatchKMeans rules fitted on the
+    device (kmeans_fit.GpuMiniBatchKMeans: its own random stream seeded with `seed`, so not sklearn's centres); `feat` may be a numpy
+    array or a CUDA fp32 tensor [n, D]; a `FittedKmeans` is dumped at `km_path` and the fitted estimator returned."""
     import joblib
+    if device is not None:
+        from .kmeans_fit import GpuMiniBatchKMeans
+        km_model = GpuMiniBatchKMeans(n_clusters=n_clusters, init=init, max_iter=max_iter, batch_size=batch_size, tol=tol,
+                                      max_no_improvement=max_no_improvement, n_init=n_init, reassignment_ratio=reassignment_ratio,
+                                      seed=seed, device=device, verbose=verbose)
+        km_model.fit(feat)
+        joblib.dump(km_model.fitted(), km_path)
+        print("total intertia: %.5f", km_model.inertia_)
+        print("finished successfully")
+        return km_model
     import numpy as np
     np.random.seed(seed)
     km_model = get_kmeans_model(n_clusters, init, max_iter, batch_size, tol, max_no_improvement, n_init, reassignment_ratio, verbose)

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("OMLM_LIB_PATH") or os.path.join(_HERE, "libomlm_hip.s
 
 _lib: Optional[C.CDLL] = None
 
-vp, i32, i64, f32, u64 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_ulonglong
+vp, i32, i64, f32, u64, f64 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_ulonglong, C.c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/omlm.h one to one
 SIGNATURES = {
@@ -92,12 +92,18 @@ SIGNATURES = {
     "omlm_vq_accumulate": [vp, vp, i32, vp, vp, i32, i32, i32, vp],
     "omlm_vq_kmeans_update": [vp, vp, vp, vp, i32, i32, vp],
     "omlm_vq_ema_update": [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp],
+    "omlm_kmeans_pp_workspace_bytes": [i32, i32],
+    "omlm_kmeans_pp_pick": [vp] * 9 + [i64, i32, i32, i32, i32, vp],
+    "omlm_kmeans_pp_seed": [vp] * 9 + [i64, i32, i32, i32, i32, vp],
+    "omlm_kmeans_minibatch_step": [vp] * 10 + [i32, i32, i32, i32, f64, f64, i32, vp],
+    "omlm_kmeans_inertia": [vp, vp, vp, vp, i32, i32, i32, vp],
     "omlm_sample_topk_gumbel": [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
     "omlm_probe_tr16": [vp, vp],
 }
 _RESTYPES = {"omlm_last_error": C.c_char_p, "omlm_gemm_tail_workspace_bytes": C.c_longlong, "omlm_gemm_mx16_workspace_bytes": C.c_longlong, "omlm_ffmid_bwd_workspace_bytes": C.c_longlong,
              "omlm_attn_bias_table_floats": C.c_longlong, "omlm_mqa_attn_bwd_workspace_bytes": C.c_longlong,
-             "omlm_layernorm_bwd_workspace_bytes": C.c_longlong, "omlm_set_error": None}
+             "omlm_layernorm_bwd_workspace_bytes": C.c_longlong, "omlm_kmeans_pp_workspace_bytes": C.c_longlong,
+             "omlm_set_error": None}
 
 
 class HipLibraryMissing(RuntimeError):

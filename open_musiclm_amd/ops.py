@@ -765,6 +765,63 @@ def vq_ema_update(cluster_size, embed_avg, embed, embed_T, counts, sums, total_s
          ptr(total_scratch), K, D, float(decay), float(eps), stream_ptr())
 
 
+def kmeans_pp_workspace_bytes(m, trials):
+    nbytes = int(hip.lib().omlm_kmeans_pp_workspace_bytes(int(m), int(trials)))
+    if nbytes < 0:
+        raise RuntimeError(f"omlm_kmeans_pp_workspace_bytes: bad sizes m={m}, trials={trials}")
+    return nbytes
+
+
+def _kmeans_pp(name, rows, closest, uniforms, pick_counter, centres, centres_T, chosen, pots, workspace, K, trials):
+    m, D = rows.shape
+    for t, what in ((rows, "rows"), (closest, "closest"), (uniforms, "uniforms"), (pick_counter, "pick_counter"), (centres, "centres"),
+                    (centres_T, "centres_T"), (chosen, "chosen"), (pots, "pots"), (workspace, "workspace")):
+        hip.require_gpu(t, what)
+    assert rows.dtype == closest.dtype == uniforms.dtype == centres.dtype == centres_T.dtype == torch.float32
+    assert pick_counter.dtype == chosen.dtype == torch.int32 and pots.dtype == torch.float64
+    assert rows.is_contiguous() and closest.numel() >= m and uniforms.numel() >= K * trials and centres.numel() >= K * D
+    assert centres_T.numel() >= K * D and chosen.numel() >= K and pots.numel() >= K
+    call(name, ptr(rows), ptr(closest), ptr(uniforms), ptr(pick_counter), ptr(centres), ptr(centres_T), ptr(chosen), ptr(pots),
+         ptr(workspace), workspace.numel() * workspace.element_size(), int(m), int(D), int(K), int(trials), stream_ptr())
+
+
+def kmeans_pp_pick(rows, closest, uniforms, pick_counter, centres, centres_T, chosen, pots, workspace, K, trials):
+    """One greedy k-means++ pick (number `pick_counter[0]` on the device, advanced by the call); include/omlm.h states the rule."""
+    _kmeans_pp("omlm_kmeans_pp_pick", rows, closest, uniforms, pick_counter, centres, centres_T, chosen, pots, workspace, K, trials)
+
+
+def kmeans_pp_seed(rows, closest, uniforms, pick_counter, centres, centres_T, chosen, pots, workspace, K, trials):
+    """A whole seeding: K picks queued from one call, nothing returns to the host."""
+    _kmeans_pp("omlm_kmeans_pp_seed", rows, closest, uniforms, pick_counter, centres, centres_T, chosen, pots, workspace, K, trials)
+
+
+def kmeans_minibatch_step(x, idx, centres, centres_T, counts, bcounts, sums, rowmin, move_partial, state, alpha, tol_abs,
+                          max_no_improvement):
+    """One MiniBatchKMeans step on rows x[idx] (idx int32 [B]); state: 8 fp64 on the device (include/omlm.h)."""
+    n, D = x.shape
+    K = centres.shape[0]
+    B = idx.numel()
+    for t, what in ((x, "x"), (idx, "idx"), (centres, "centres"), (state, "state")):
+        hip.require_gpu(t, what)
+    assert x.dtype == torch.float32 and x.is_contiguous() and idx.dtype == torch.int32 and idx.is_contiguous()
+    assert state.dtype == move_partial.dtype == torch.float64 and state.numel() >= 8 and move_partial.numel() >= K
+    assert counts.numel() >= K and bcounts.numel() >= K and sums.numel() >= K * D and rowmin.numel() >= B
+    call("omlm_kmeans_minibatch_step", ptr(x), ptr(idx), ptr(centres), ptr(centres_T), ptr(counts), ptr(bcounts), ptr(sums), ptr(rowmin),
+         ptr(move_partial), ptr(state), int(n), int(B), int(D), int(K), float(alpha), float(tol_abs), int(max_no_improvement),
+         stream_ptr())
+
+
+def kmeans_inertia(x, centres_T, out, labels=None):
+    """out[0] (fp64, device) += sum over the rows of x of the min squared distance; labels int32 [n] optional."""
+    n, D = x.shape
+    K = centres_T.shape[1]
+    hip.require_gpu(x, "x")
+    hip.require_gpu(centres_T, "centres_T")
+    assert x.dtype == torch.float32 and x.is_contiguous() and centres_T.is_contiguous() and out.dtype == torch.float64
+    assert labels is None or (labels.dtype == torch.int32 and labels.numel() >= n)
+    call("omlm_kmeans_inertia", ptr(x), ptr(centres_T), ptr(out), ptr(labels), int(n), int(D), int(K), stream_ptr())
+
+
 def sample_topk_gumbel(logits, uniform, out, V, k, temperature, forbid_last):
     B, ld = logits.shape
     call("omlm_sample_topk_gumbel", ptr(logits), ptr(uniform), ptr(out), B, V, ld, int(k), float(temperature),

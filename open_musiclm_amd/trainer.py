@@ -557,7 +557,8 @@ class ClapRVQTrainer(nn.Module):
 
 class HfHubertKmeansTrainer(nn.Module):
     """Trainer for the k-means part of HfHubertWithKmeans (trainer.py:748-905): 1) collect `feature_extraction_num_steps` batches
-    of features, 2) fit sklearn's MiniBatchKMeans on them (`learn_kmeans`, the reference's own call) and dump `kmeans.joblib`.
+    of features, 2) fit sklearn's MiniBatchKMeans on them (`learn_kmeans`, the reference's own call) and dump `kmeans.joblib`;
+    `train(device='cuda')` fits on the device instead (kmeans_fit.py) and keeps the features there.
     The MERT / HuBERT extractor is a third-party pretrained network that is not part of this build: when `hubert_kmeans.hubert`
     is None the dataset must yield the features themselves ([t, f] or [b, t, f] float tensors, e.g. precomputed MERT layer-7
     embeddings); with an extractor present the reference's `forward(wav_input=..., return_embed=True)` path is used."""
@@ -615,6 +616,9 @@ class HfHubertKmeansTrainer(nn.Module):
         return self.dp.local_rank == 0
 
     def extract_hubert_features(self):
+        return self._extract_hubert_features().cpu().numpy()
+
+    def _extract_hubert_features(self) -> torch.Tensor:
         batch = next(self.dl_iter)
         item = batch[0] if isinstance(batch, (list, tuple)) else batch
         if self.features_in:
@@ -624,22 +628,34 @@ class HfHubertKmeansTrainer(nn.Module):
             dev = next(self.hubert_kmeans.parameters(), item).device       # the waveform goes to the extractor's device
             embed = self.hubert_kmeans.forward(wav_input=item.to(dev), return_embed=True)
             embed = embed.reshape(-1, embed.shape[-1])
-        embed = _gather_rows(self.dp, embed.detach())
-        return embed.cpu().numpy()
+        return _gather_rows(self.dp, embed.detach())
 
     def train(self, log_fn=noop, seed=0, **kmeans_kwargs):
+        """`train(device='cuda')` (forwarded to learn_kmeans with the other keywords) fits on the device; the gathered features then
+        stay device tensors, NaN-row filter included, instead of the numpy round trip."""
         from .hf_hubert_kmeans import learn_kmeans
+        fit_device = kmeans_kwargs.get('device')
+        if fit_device is not None:
+            from .kmeans_fit import require_cuda_device
+            fit_device = require_cuda_device(fit_device)
         self.print('step 1: extracting features. must wait for this to complete before training kmeans.')
         features = []
         num_steps = -(-self.feature_extraction_num_steps // self.dp.world_size)
         while self.steps < num_steps:
             self.print(f'{int(self.steps.item())} / {num_steps} steps')
-            features.append(self.extract_hubert_features())
+            if fit_device is not None:
+                features.append(self._extract_hubert_features().to(fit_device))
+            else:
+                features.append(self.extract_hubert_features())
             self.steps += 1
-        features = np.concatenate(features, axis=0)
-        features = features[~np.any(np.isnan(features), axis=-1)]
+        if fit_device is not None:
+            features = torch.cat(features, dim=0).float()
+            features = features[~torch.isnan(features).any(dim=-1)].contiguous()
+        else:
+            features = np.concatenate(features, axis=0)
+            features = features[~np.any(np.isnan(features), axis=-1)]
         self.print('step 2: training kmeans')
         if self.is_main:
-            learn_kmeans(features, seed, str(self.results_folder / 'kmeans.joblib'),
-                         n_clusters=self.hubert_kmeans.codebook_size, **kmeans_kwargs)
+            self.kmeans_model = learn_kmeans(features, seed, str(self.results_folder / 'kmeans.joblib'),
+                                             n_clusters=self.hubert_kmeans.codebook_size, **kmeans_kwargs)
         self.print('training complete')
