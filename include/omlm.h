@@ -67,12 +67,10 @@ int omlm_layernorm_fwd(const float* x, const float* gamma, void* y, void* xcast,
 int omlm_layernorm_fwd_planes(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd,
                               int M, int D, int ldy, float eps, int out_dtype, void* stream);
 long long omlm_layernorm_bwd_workspace_bytes(int D);
-int omlm_layernorm_bwd(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
-                       const float* dres, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D,
-                       float dx_scale, int cast_dtype, int dy_dtype, void* stream);   /* dy_dtype: 0 fp32, 1 bf16 / 2 fp16 (GEMM epilogue output) */
-/* the same with a second residual-gradient term dres2 [M, D] (optional) in the type cast_dtype names (dxcast may be null): the K/V
- * projection's input gradient reaches the attention LayerNorm's backward as a 16-bit GEMM output instead of being added to the fp32
- * residual gradient by the GEMM's own epilogue (146 MB read + 146 MB written per layer at B = 32). */
+/* dy_dtype: 0 fp32, 1 bf16 / 2 fp16 (GEMM epilogue output).  dres2 [M, D] (optional): a second residual-gradient term in the type
+ * cast_dtype names (dxcast may be null): the K/V projection's input gradient reaches the attention LayerNorm's backward as a 16-bit GEMM
+ * output instead of being added to the fp32 residual gradient by the GEMM's own epilogue (146 MB read + 146 MB written per layer at
+ * B = 32). */
 int omlm_layernorm_bwd2(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                         const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D,
                         float dx_scale, int cast_dtype, int dy_dtype, void* stream);
@@ -260,11 +258,9 @@ int omlm_loss_scale_update(float* ls_state, const float* gnorm_sq, float growth,
 
 /* operand casts / weight repack */
 int omlm_cast_pad(const float* src, void* dst, long long R, int C, int ld_src, int ld_dst, int out_dtype, void* stream);
-/* dst[c, r] = cast(src[r, c]): k-contiguous W^T copies for the input-gradient GEMMs (the autograd transpose of
- * nn.Linear, transformer.py:203-212,144,149), refreshed once per optimizer step. */
-int omlm_transpose_cast(const float* src, void* dst, int R, int C, int ld_src, int ld_dst, int out_dtype, void* stream);
 /* The per-step weight re-packs of a model as ONE launch: problem i casts src [R, C] (pitch ld_src) into dst [R, ld_dst] with zero pad
- * columns (omlm_cast_pad), or -- transpose != 0 -- writes dst[c, r] = src[r, c] (omlm_transpose_cast; pad entries untouched).
+ * columns (omlm_cast_pad), or -- transpose != 0 -- writes dst[c, r] = cast(src[r, c]) (pad entries untouched): the k-contiguous W^T copies
+ * for the input-gradient GEMMs (the autograd transpose of nn.Linear, transformer.py:203-212,144,149), refreshed once per optimizer step.
  * lo != 0: dst receives the LO PLANE of the cast, rne16(v - rne16(v)), instead of the cast itself (the hi/lo weight planes of precision
  * "fp16ff": omlm_gemm_planes16, omlm_ffmid_fwd_planes). */
 typedef struct omlm_cast_pad_desc { const float* src; void* dst; int R, C, ld_src, ld_dst, transpose, lo; } omlm_cast_pad_desc;
@@ -331,47 +327,37 @@ typedef struct omlm_gemm_wgrad_desc {
 } omlm_gemm_wgrad_desc;
 int omlm_gemm_wgrad_group(const omlm_gemm_wgrad_desc* problems, int count, int splits, int dtype, void* stream);   /* dtype: operands of ALL problems, 1 bf16 / 2 fp16 */
 
-/* RelativePositionBias MLP helpers (transformer.py:55-64): SiLU layers around omlm_gemm. */
-int omlm_relpos_first_fwd(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, void* stream);
-int omlm_relpos_first_bwd(const float* ds, float* dw0, int n, int Hd, void* stream);
-/* The same over the distances x0 .. x0 + n - 1 (row r is distance x0 + r; x0 = -(min(P, N) - 1) gives the non-causal prefix's table). */
-int omlm_relpos_first_fwd_from(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, int x0, void* stream);
-int omlm_relpos_first_bwd_from(const float* ds, float* dw0, int n, int Hd, int x0, void* stream);
+/* RelativePositionBias MLP helpers (transformer.py:55-64): SiLU layers around omlm_gemm, over the distances x0 .. x0 + n - 1 (row r is
+ * distance x0 + r; x0 = 0: the causal table, x0 = -(min(P, N) - 1): the non-causal prefix's). */
+int omlm_relpos_first_fwd(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, int x0, void* stream);
+int omlm_relpos_first_bwd(const float* ds, float* dw0, int n, int Hd, int x0, void* stream);
 int omlm_bias_silu_fwd(const float* a, const float* b, float* pre, float* z, long long R, int C, void* stream);
 int omlm_silu_bwd(const float* dz, const float* pre, float* ds, long long total, void* stream);
 int omlm_bias_add(const float* a, const float* b, float* out, int R, int C, int ld, void* stream);
 /* The whole MLP as ONE forward launch and TWO backward launches (round 5; Hd = 256 or 512, H <= 16: every shipped config), replacing the
- * 21 launches of the layer-by-layer path above.  RelativePositionBias.forward (transformer.py:55-64) restricted to the n causal distances
- * 0 .. n - 1: table[r, h] = net(r)[h].  w0 = net.0.0.weight viewed [Hd]; W1 / W2 = net.1.0 / net.2.0 weights [Hd, Hd]; W3 = net.3.weight
+ * 21 launches of the layer-by-layer path above.  RelativePositionBias.forward (transformer.py:55-64) restricted to the n distances
+ * x0 .. x0 + n - 1: table[r, h] = net(x0 + r)[h].  w0 = net.0.0.weight viewed [Hd]; W1 / W2 = net.1.0 / net.2.0 weights [Hd, Hd]; W3 = net.3.weight
  * [H, Hd].  pre* / z* [n, Hd] are the layers' pre-activations / SiLU outputs, written by the forward when non-null (all or none) and
  * read by the backward; table / dtable are [n, ldb] (ldb <= 16, pad columns zero).  The backward ACCUMULATES into the g* buffers
  * (deterministic: one owner thread per element, rows summed in ascending order); scratch holds 3 * n * Hd floats. */
 int omlm_relpos_mlp_fwd(const float* w0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
                         const float* W3, const float* b3, float* pre0, float* z0, float* pre1, float* z1, float* pre2, float* z2,
-                        float* table, int n, int Hd, int H, int ldb, void* stream);
+                        float* table, int n, int Hd, int H, int ldb, int x0, void* stream);
 int omlm_relpos_mlp_bwd(const float* dtable, const float* W1, const float* W2, const float* W3, const float* pre0, const float* z0,
                         const float* pre1, const float* z1, const float* pre2, const float* z2, float* scratch, float* gw0, float* gb0,
-                        float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, void* stream);
-/* The fused MLP over the distances x0 .. x0 + n - 1: table[r, h] = net(x0 + r)[h] (omlm_relpos_mlp_fwd / _bwd: x0 = 0). */
-int omlm_relpos_mlp_fwd_from(const float* w0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
-                             const float* W3, const float* b3, float* pre0, float* z0, float* pre1, float* z1, float* pre2, float* z2,
-                             float* table, int n, int Hd, int H, int ldb, int x0, void* stream);
-int omlm_relpos_mlp_bwd_from(const float* dtable, const float* W1, const float* W2, const float* W3, const float* pre0, const float* z0,
-                             const float* pre1, const float* z1, const float* pre2, const float* z2, float* scratch, float* gw0, float* gb0,
-                             float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, int x0,
-                             void* stream);
+                        float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, int x0,
+                        void* stream);
 
 /* Nearest-codeword kernels: ClapQuantized.quantize -> ResidualVQ eval path (clap_quantized.py:75-87) and
- * HfHubertWithKmeans assign (hf_hubert_kmeans.py:87).  codebooks_T: [nstage][D][C] (transposed); indices int32 [n, nstage].
- * omlm_rvq_encode / _strided use the distance form of vector-quantize-pytorch's EuclideanCodebook -- argmax(-cdist(x, embed)),
+ * HfHubertWithKmeans assign (hf_hubert_kmeans.py:87).  codebooks_T: [nstage][D][C] (transposed); indices int32 [n, nstage] -- idx_stride
+ * 0 or nstage -- or, with nstage == 1 only, row i's index at indices[i * idx_stride] (a column of an [n, stages] table: the fit step).
+ * omlm_rvq_encode uses the distance form of vector-quantize-pytorch's EuclideanCodebook -- argmax(-cdist(x, embed)),
  * first maximum: dist = sqrt(max((|x|^2 + |e|^2) - 2 x.e, 0)) in fp32, IEEE root (distances whose roots round equal are a tie for
  * the lowest index); pinned bit for bit against torch.cdist on exactly representable inputs (tests/rvq_cases.py).
  * omlm_nearest_centroid uses sum_d (x_d - c_d)^2 (pinned against sklearn.MiniBatchKMeans.predict).  Ties -> lowest index. */
 int omlm_rvq_encode(const float* x, const float* codebooks_T, int* indices, float* residual_out,
-                    int n, int D, int C, int nstage, void* stream);
+                    int n, int D, int C, int nstage, int idx_stride, void* stream);
 int omlm_nearest_centroid(const float* x, const float* centroids_T, int* indices, int n, int D, int C, void* stream);
-int omlm_rvq_encode_strided(const float* x, const float* codebook_T, int* indices, int idx_stride, float* residual_out,
-                            int n, int D, int C, void* stream);
 /* Fitting side of the residual VQ (reference call sites: trainer.py:689-736 -> clap_quantized.py:75-84 with rq.train(True); the
  * arithmetic is vector-quantize-pytorch's EuclideanCodebook, un-vendored: oracle.rvq_fit_step restates the published update rules;
  * the assignment inside it is the -cdist form above).

@@ -528,18 +528,11 @@ extern "C" int OMLM_API(omlm_layernorm_bwd2)(const void* dy, const float* x, con
         hipLaunchKernelGGL((ln_bwd_kernel<h16_t, float>), grid, block, 0, as_stream(stream), (const float*)dy, x, gamma, mean, rstd, dres, (const h16_t*)dres2, dx, (h16_t*)dxcast, dgamma, part, M, D, dx_scale);
     else
         hipLaunchKernelGGL((ln_bwd_kernel<h16_t, h16_t>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, (const h16_t*)dres2, dx, (h16_t*)dxcast, dgamma, part, M, D, dx_scale);
-    int rc = omlm_post_launch("omlm_layernorm_bwd");
+    int rc = omlm_post_launch("omlm_layernorm_bwd2");
     if (rc) return rc;
     if (two_level && dgamma) return omlm_colsum_accumulate(part, dgamma, blocks, D, D, stream);
     return OMLM_OK;
 }
-#if !OMLM_FP16
-extern "C" int omlm_layernorm_bwd(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
-                                  const float* dres, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D,
-                                  float dx_scale, int cast_dtype, int dy_dtype, void* stream) {
-    return omlm_layernorm_bwd2(dy, x, gamma, mean, rstd, dres, nullptr, dx, dxcast, dgamma, workspace, M, D, dx_scale, cast_dtype, dy_dtype, stream);
-}
-#endif
 
 // ---------------------------------------------------------------------------------------------
 // q/k l2norm * scale.  One wave per 64-wide vector, one element per lane (dim_head == 64).

@@ -153,40 +153,6 @@ extern "C" int omlm_loss_scale_update(float* ls_state, const float* gnorm_sq, fl
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// dst[c, r] = (T) src[r, c]  (r < R, c < C): transposed operand copies of the weights, so that the input-gradient GEMMs
-// (dX = dY W) read W^T k-contiguous instead of W k-major.  Measured on MI355X: the same contraction runs at 795 TFLOP/s
-// with a k-contiguous B versus 517 with a k-major B; the weights are tiny next to the activations, so the copy is ~free.
-// 64x64 tile through LDS (pitch 65 floats): 256-byte coalesced reads, 128-byte coalesced bf16 writes.
-template <typename T>
-__global__ __launch_bounds__(256) void transpose_cast_kernel(const float* __restrict__ src, T* __restrict__ dst, int R, int C,
-                                                             int ld_src, int ld_dst) {
-    __shared__ float tile[64][65];
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int r = r0 + ty + 4 * i, c = c0 + tx;
-        tile[ty + 4 * i][tx] = (r < R && c < C) ? src[(long long)r * ld_src + c] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const int c = c0 + ty + 4 * i, r = r0 + tx;
-        if (c < C && r < R) store_from_float(dst + (long long)c * ld_dst + r, tile[tx][ty + 4 * i]);
-    }
-}
-extern "C" int omlm_transpose_cast(const float* src, void* dst, int R, int C, int ld_src, int ld_dst, int out_dtype, void* stream) {
-    if (R <= 0 || C <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(src && dst && ld_src >= C && ld_dst >= R, "transpose_cast arguments");
-    dim3 grid((C + 63) / 64, (R + 63) / 64), block(256);
-    OMLM_CHECK_ARG(out_dtype >= 0 && out_dtype <= 2, "out_dtype: 0 = fp32, 1 = bf16, 2 = fp16");
-    if (out_dtype == 0) hipLaunchKernelGGL(transpose_cast_kernel<float>, grid, block, 0, as_stream(stream), src, (float*)dst, R, C, ld_src, ld_dst);
-    else if (out_dtype == OMLM_DT_F16) hipLaunchKernelGGL(transpose_cast_kernel<f16_t>, grid, block, 0, as_stream(stream), src, (f16_t*)dst, R, C, ld_src, ld_dst);
-    else hipLaunchKernelGGL(transpose_cast_kernel<h16_t>, grid, block, 0, as_stream(stream), src, (h16_t*)dst, R, C, ld_src, ld_dst);
-    return omlm_post_launch("omlm_transpose_cast");
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // The per-step weight re-packs of a model (FF-in value / gate halves, FF-out rows at the padded pitch, conv taps transposed, padded
 // LayerNorm gammas: ~6 small launches per layer, 36 per coarse-small step) as ONE launch: problem i copies / casts src [R, C] (pitch
 // ld_src) to dst [R, ld_dst] with zero pad columns, or -- transpose set -- writes dst[c, r] = src[r, c] (pad untouched).
@@ -404,15 +370,12 @@ __global__ __launch_bounds__(256) void relpos_first_bwd_kernel(const float* __re
     if (rl == 0 && c < Hd) unsafeAtomicAdd(dw0 + c, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-// rows = distances x0 .. x0 + n - 1 (omlm_relpos_first_fwd: x0 = 0)
-extern "C" int omlm_relpos_first_fwd_from(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, int x0, void* stream) {
+// rows = distances x0 .. x0 + n - 1
+extern "C" int omlm_relpos_first_fwd(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, int x0, void* stream) {
     OMLM_CHECK_ARG(w0 && b0 && pre && z && n > 0 && Hd > 0, "relpos_first arguments");
     const long long tot = (long long)n * Hd;
     hipLaunchKernelGGL(relpos_first_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, as_stream(stream), w0, b0, pre, z, n, Hd, x0);
     return omlm_post_launch("omlm_relpos_first_fwd");
-}
-extern "C" int omlm_relpos_first_fwd(const float* w0, const float* b0, float* pre, float* z, int n, int Hd, void* stream) {
-    return omlm_relpos_first_fwd_from(w0, b0, pre, z, n, Hd, 0, stream);
 }
 extern "C" int omlm_bias_silu_fwd(const float* a, const float* b, float* pre, float* z, long long R, int C, void* stream) {
     OMLM_CHECK_ARG(a && b && pre && z && R > 0 && C > 0, "bias_silu arguments");
@@ -431,13 +394,10 @@ extern "C" int omlm_bias_add(const float* a, const float* b, float* out, int R, 
     hipLaunchKernelGGL(bias_add_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, as_stream(stream), a, b, out, R, C, ld);
     return omlm_post_launch("omlm_bias_add");
 }
-extern "C" int omlm_relpos_first_bwd_from(const float* ds, float* dw0, int n, int Hd, int x0, void* stream) {
+extern "C" int omlm_relpos_first_bwd(const float* ds, float* dw0, int n, int Hd, int x0, void* stream) {
     OMLM_CHECK_ARG(ds && dw0 && n > 0 && Hd > 0, "relpos_first_bwd arguments");
     hipLaunchKernelGGL(relpos_first_bwd_kernel, dim3((Hd + 63) / 64, 16), dim3(256), 0, as_stream(stream), ds, dw0, n, Hd, x0);
     return omlm_post_launch("omlm_relpos_first_bwd");
-}
-extern "C" int omlm_relpos_first_bwd(const float* ds, float* dw0, int n, int Hd, void* stream) {
-    return omlm_relpos_first_bwd_from(ds, dw0, n, Hd, 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -767,10 +727,10 @@ __global__ __launch_bounds__(256) void relpos_mlp_bwd_params_kernel(relpos_mlp_p
     }
 }
 
-// rows = distances x0 .. x0 + n - 1 (omlm_relpos_mlp_fwd: x0 = 0)
-extern "C" int omlm_relpos_mlp_fwd_from(const float* w0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
-                                        const float* W3, const float* b3, float* pre0, float* z0, float* pre1, float* z1, float* pre2, float* z2,
-                                        float* table, int n, int Hd, int H, int ldb, int x0, void* stream) {
+// rows = distances x0 .. x0 + n - 1
+extern "C" int omlm_relpos_mlp_fwd(const float* w0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
+                                   const float* W3, const float* b3, float* pre0, float* z0, float* pre1, float* z1, float* pre2, float* z2,
+                                   float* table, int n, int Hd, int H, int ldb, int x0, void* stream) {
     OMLM_CHECK_ARG(w0 && b0 && W1 && b1 && W2 && b2 && W3 && b3 && table && n > 0, "relpos_mlp_fwd: null argument");
     OMLM_CHECK_ARG((Hd == 256 || Hd == 512) && H >= 1 && H <= 16 && ldb >= H && ldb <= 16, "relpos_mlp_fwd: Hd must be 256 or 512, H <= 16");
     OMLM_CHECK_ARG(!pre0 || (z0 && pre1 && z1 && pre2 && z2), "relpos_mlp_fwd: save buffers come all or none");
@@ -791,17 +751,12 @@ extern "C" int omlm_relpos_mlp_fwd_from(const float* w0, const float* b0, const 
     else           hipLaunchKernelGGL(relpos_mlp_fwd_kernel<256>, grid, dim3(256), lds, as_stream(stream), a);
     return omlm_post_launch("omlm_relpos_mlp_fwd");
 }
-extern "C" int omlm_relpos_mlp_fwd(const float* w0, const float* b0, const float* W1, const float* b1, const float* W2, const float* b2,
-                                   const float* W3, const float* b3, float* pre0, float* z0, float* pre1, float* z1, float* pre2, float* z2,
-                                   float* table, int n, int Hd, int H, int ldb, void* stream) {
-    return omlm_relpos_mlp_fwd_from(w0, b0, W1, b1, W2, b2, W3, b3, pre0, z0, pre1, z1, pre2, z2, table, n, Hd, H, ldb, 0, stream);
-}
 
 // scratch: 3 * n * Hd floats (ds0 | ds1 | ds2).  Gradients are ACCUMULATED into g* (fp32, the optimizer's flat buffer views).
-extern "C" int omlm_relpos_mlp_bwd_from(const float* dtable, const float* W1, const float* W2, const float* W3, const float* pre0, const float* z0,
-                                        const float* pre1, const float* z1, const float* pre2, const float* z2, float* scratch, float* gw0, float* gb0,
-                                        float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, int x0,
-                                        void* stream) {
+extern "C" int omlm_relpos_mlp_bwd(const float* dtable, const float* W1, const float* W2, const float* W3, const float* pre0, const float* z0,
+                                   const float* pre1, const float* z1, const float* pre2, const float* z2, float* scratch, float* gw0, float* gb0,
+                                   float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, int x0,
+                                   void* stream) {
     OMLM_CHECK_ARG(dtable && W1 && W2 && W3 && pre0 && z0 && pre1 && z1 && pre2 && z2 && scratch && gw0 && gb0 && gW1 && gb1 && gW2 && gb2 && gW3 && gb3 && n > 0,
                    "relpos_mlp_bwd: null argument");
     OMLM_CHECK_ARG((Hd == 256 || Hd == 512) && H >= 1 && H <= 16 && ldb >= H && ldb <= 16, "relpos_mlp_bwd: Hd must be 256 or 512, H <= 16");
@@ -826,12 +781,6 @@ extern "C" int omlm_relpos_mlp_bwd_from(const float* dtable, const float* W1, co
     const int tpd = Hd / 64;
     hipLaunchKernelGGL(relpos_mlp_bwd_params_kernel, dim3(2 * tpd * tpd + 2 * tpd), dim3(256), 0, as_stream(stream), a);
     return omlm_post_launch("omlm_relpos_mlp_bwd (parameters)");
-}
-extern "C" int omlm_relpos_mlp_bwd(const float* dtable, const float* W1, const float* W2, const float* W3, const float* pre0, const float* z0,
-                                   const float* pre1, const float* z1, const float* pre2, const float* z2, float* scratch, float* gw0, float* gb0,
-                                   float* gW1, float* gb1, float* gW2, float* gb2, float* gW3, float* gb3, int n, int Hd, int H, int ldb, void* stream) {
-    return omlm_relpos_mlp_bwd_from(dtable, W1, W2, W3, pre0, z0, pre1, z1, pre2, z2, scratch, gw0, gb0, gW1, gb1, gW2, gb2, gW3, gb3, n, Hd, H,
-                                    ldb, 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -911,16 +860,14 @@ static int rvq_launch(int form, const float* x, const float* cbT, int* indices, 
         hipLaunchKernelGGL(rvq_kernel<FORM_SQ>, dim3(n), dim3(256), D * sizeof(float), as_stream(stream), x, cbT, indices, residual_out, n, D, C, nstage, idx_stride);
     return omlm_post_launch(what);
 }
-// residual-VQ chain of nstage codebooks in the library's distance form (FORM_CDIST)
+// residual-VQ chain of nstage codebooks in the library's distance form (FORM_CDIST).  idx_stride 0 or nstage: indices is a packed
+// [n, nstage] table.  Any other stride takes ONE stage and writes row i's index to indices[i * idx_stride] (a column of an [n, stages]
+// table: the RVQ fit step walks the layers one launch at a time because every layer's codebook changes between its assignment and the
+// next layer's).
 extern "C" int omlm_rvq_encode(const float* x, const float* codebooks_T, int* indices, float* residual_out,
-                               int n, int D, int C, int nstage, void* stream) {
-    return rvq_launch(FORM_CDIST, x, codebooks_T, indices, residual_out, n, D, C, nstage, nstage, stream, "omlm_rvq_encode");
-}
-// one stage, index of row i written to indices[i * idx_stride] (a column of an [n, stages] table: the RVQ fit step walks the layers
-// one launch at a time because every layer's codebook changes between its assignment and the next layer's); same form
-extern "C" int omlm_rvq_encode_strided(const float* x, const float* codebook_T, int* indices, int idx_stride, float* residual_out,
-                                       int n, int D, int C, void* stream) {
-    return rvq_launch(FORM_CDIST, x, codebook_T, indices, residual_out, n, D, C, 1, idx_stride, stream, "omlm_rvq_encode_strided");
+                               int n, int D, int C, int nstage, int idx_stride, void* stream) {
+    OMLM_CHECK_ARG(idx_stride == 0 || idx_stride == nstage || nstage == 1, "omlm_rvq_encode: an idx_stride other than 0 or nstage needs nstage == 1");
+    return rvq_launch(FORM_CDIST, x, codebooks_T, indices, residual_out, n, D, C, nstage, idx_stride ? idx_stride : nstage, stream, "omlm_rvq_encode");
 }
 // k-means assign (hf_hubert_kmeans.py:87): squared-difference form (FORM_SQ)
 extern "C" int omlm_nearest_centroid(const float* x, const float* centroids_T, int* indices, int n, int D, int C, void* stream) {

@@ -200,9 +200,9 @@ class CachedDecoder:
             raise ValueError(f"cached decode of a model with a non-causal prefix of {P} rows needs them all in the prompt; got {N} rows")
         lay = engine.get_layout(model, B, lens, ids32.device, True)
         x = engine.embed_forward(model, ids32, lay)
-        y, saved = engine.trunk_forward(tr, self.pw, x, None, B, N, True, False, keep_h1_lo_tail=self.planes)
+        y, y_lo, saved = engine.trunk_forward(tr, self.pw, x, None, B, N, True, False, keep_h1_lo_tail=self.planes)
         nseq = len(model.token_sequences)
-        logits = engine.heads_forward(model, self.pw, y, lay, [s == nseq - 1 for s in range(nseq)])[-1]
+        logits = engine.heads_forward(model, self.pw, y, y_lo, lay, [s == nseq - 1 for s in range(nseq)])[-1]
         for l, sv in enumerate(saved["layers"]):
             self.Kc[l][:, :N].copy_(sv.k.view(B, N, -1))
             self.Vc[l][:, :N].copy_(sv.v.view(B, N, -1))

@@ -552,7 +552,8 @@ def dropout_state(tr, dev=None) -> dict:
 
 def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[torch.Tensor], B: int, N: int,
                   save: bool, training: bool, keep_h1_lo_tail: bool = False):
-    """x: [B*N, D] fp32 (consumed as the layer-0 residual).  Returns (final LN output in operand dtype, saved).
+    """x: [B*N, D] fp32 (consumed as the layer-0 residual).  Returns (final LN output y in operand dtype, y_lo, saved); y_lo: the lo plane
+    of y for heads_forward (precision "fp16ff": the final LayerNorm's output leaves as hi/lo planes), else None.
     keep_h1_lo_tail ("fp16ff" prefill of the cached decoder): the lo plane of the last two h1 rows of every sample survives as sv.h1_lo_tail
     [B, 2, 2 Fp] fp32 (rows N-2, N-1; zeros where N < 2) -- the causal conv's state is the un-rounded h1."""
     T = pw.T
@@ -690,15 +691,14 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
             saved_layers.append(sv)
         x = x2
     mf = torch.empty(M, device=dev); rf = torch.empty(M, device=dev)
-    y = torch.empty(M, D, dtype=T, device=dev)
-    if pw.ff3:                                                   # the lo plane rides on the tensor until heads_forward has read it
+    y, y_lo = torch.empty(M, D, dtype=T, device=dev), None
+    if pw.ff3:
         y_lo = torch.empty(M, D, dtype=T, device=dev)
         ops.layernorm_fwd_planes(x, tr.norm.gamma.detach(), y, y_lo, mf, rf)
-        y._omlm_lo = y_lo
     else:
         ops.layernorm_fwd(x, tr.norm.gamma.detach(), y, None, mf, rf)
     saved = dict(layers=saved_layers, xL=x, mf=mf, rf=rf, table=table, rp=rp_saved, keymask=keymask, salt=salt) if save else None
-    return y, saved
+    return y, y_lo, saved
 
 
 def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: int, out_scale: float, head_wgrads=None):
@@ -863,13 +863,13 @@ def embed_backward(model, ids32: torch.Tensor, lay: SeqLayout, dx: torch.Tensor,
                   [grad_of(s) for s in model.start_tokens], dpos, dx.view(B, N, -1), alpha)
 
 
-def heads_forward(model, pw: PreparedWeights, y: torch.Tensor, lay: SeqLayout, want: Sequence[bool]):
-    """y: [B*N, D] operand dtype.  Returns per sequence a padded fp32 logits buffer [B*n_s, ldV] or None.
+def heads_forward(model, pw: PreparedWeights, y: torch.Tensor, y_lo: Optional[torch.Tensor], lay: SeqLayout, want: Sequence[bool]):
+    """y: [B*N, D] operand dtype; y_lo: its lo plane ("fp16ff": three-product heads) or None, as trunk_forward returns them.
+    Returns per sequence a padded fp32 logits buffer [B*n_s, ldV] or None.
     (einsum 'q c d, b n q d -> b n q c' incl. the remainder positions, open_musiclm.py:163-186: the hidden
     position j of a sequence is scored by quantizer head j mod Q.)"""
     D = model.dim
     out = []
-    y_lo = y.__dict__.pop("_omlm_lo", None) if pw.ff3 else None          # "fp16ff": trunk_forward left the final LayerNorm's lo plane on y
     for s, seq in enumerate(model.token_sequences):
         if not want[s]:
             out.append(None)
@@ -961,11 +961,11 @@ def run_forward(model, all_token_ids, self_attn_mask, only_final: bool, save: bo
         assert self_attn_mask.shape == (B, N), f"self_attn_mask must be [{B}, {N}]"
         keymask = self_attn_mask.to(torch.uint8).contiguous()
     x = embed_forward(model, ids32, lay)
-    y, tsaved = trunk_forward(tr, pw, x, keymask, B, N, save, model.training)
+    y, y_lo, tsaved = trunk_forward(tr, pw, x, keymask, B, N, save, model.training)
     nseq = len(model.token_sequences)
     if want is None:
         want = [(not only_final) or s == nseq - 1 for s in range(nseq)]
-    logits = heads_forward(model, pw, y, lay, want)
+    logits = heads_forward(model, pw, y, y_lo, lay, want)
     st = None
     if save:
         st = ForwardState()

@@ -39,7 +39,6 @@ SIGNATURES = {
     "omlm_ffmid_fwd_planes": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, u64, vp, vp, vp, i32, vp],
     "omlm_layernorm_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp],
     "omlm_layernorm_bwd_workspace_bytes": [i32],
-    "omlm_layernorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, i32, vp],
     "omlm_layernorm_bwd2": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, i32, vp],
     "omlm_qk_norm_fwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
     "omlm_qk_norm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
@@ -69,26 +68,20 @@ SIGNATURES = {
     "omlm_adamw_clip_step": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, f32, i32, i32, i32, vp, vp],
     "omlm_loss_scale_update": [vp, vp, f32, f32, i32, f32, f32, vp],
     "omlm_cast_pad": [vp, vp, i64, i32, i32, i32, i32, vp],
-    "omlm_transpose_cast": [vp, vp, i32, i32, i32, i32, i32, vp],
     "omlm_cast_pad_group": [vp, i32, i32, vp],
     "omlm_sample_topk_gumbel_at": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
     "omlm_sample_embed_at": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, i64, i64, vp, i32, vp],
     "omlm_decode_step": [vp, vp, vp],
     "omlm_decode_advance": [vp, vp, vp],
-    "omlm_relpos_first_fwd": [vp, vp, vp, vp, i32, i32, vp],
-    "omlm_relpos_first_bwd": [vp, vp, i32, i32, vp],
+    "omlm_relpos_first_fwd": [vp, vp, vp, vp, i32, i32, i32, vp],
+    "omlm_relpos_first_bwd": [vp, vp, i32, i32, i32, vp],
     "omlm_bias_silu_fwd": [vp, vp, vp, vp, i64, i32, vp],
     "omlm_silu_bwd": [vp, vp, vp, i64, vp],
     "omlm_bias_add": [vp, vp, vp, i32, i32, i32, vp],
-    "omlm_relpos_mlp_fwd": [vp] * 15 + [i32, i32, i32, i32, vp],
-    "omlm_relpos_mlp_bwd": [vp] * 19 + [i32, i32, i32, i32, vp],
-    "omlm_relpos_first_fwd_from": [vp, vp, vp, vp, i32, i32, i32, vp],
-    "omlm_relpos_first_bwd_from": [vp, vp, i32, i32, i32, vp],
-    "omlm_relpos_mlp_fwd_from": [vp] * 15 + [i32, i32, i32, i32, i32, vp],
-    "omlm_relpos_mlp_bwd_from": [vp] * 19 + [i32, i32, i32, i32, i32, vp],
-    "omlm_rvq_encode": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
+    "omlm_relpos_mlp_fwd": [vp] * 15 + [i32, i32, i32, i32, i32, vp],
+    "omlm_relpos_mlp_bwd": [vp] * 19 + [i32, i32, i32, i32, i32, vp],
+    "omlm_rvq_encode": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "omlm_nearest_centroid": [vp, vp, vp, i32, i32, i32, vp],
-    "omlm_rvq_encode_strided": [vp, vp, vp, i32, vp, i32, i32, i32, vp],
     "omlm_vq_accumulate": [vp, vp, i32, vp, vp, i32, i32, i32, vp],
     "omlm_vq_kmeans_update": [vp, vp, vp, vp, i32, i32, vp],
     "omlm_vq_ema_update": [vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp],

@@ -190,19 +190,36 @@ def gemm_mx16(A, A8: Fp8Planes, B, B8: Fp8Planes, C_, C_lo=None, *, M: int, N: i
          Cin.shape[-1] if Cin is not None else 0, ws, wsb, stream_ptr())
 
 
+class _DescGroup:
+    """What the descriptor groups share.  add() appends an item: the fields of `desc` in order, tensors in the place of their pointers (they
+    stay alive until the flush).  flush() issues all items as ONE call of `entry` (descriptor array, count, args, dtype code where the group
+    has one operand / output type, stream) and empties the group."""
+    desc = entry = dtype = None
+
+    def __init__(self):
+        self.items = []
+
+    def _fields(self, item):
+        return [ptr(v) if v is None or isinstance(v, torch.Tensor) else v for v in item]
+
+    def flush(self, *args):
+        if not self.items:
+            return
+        arr = (self.desc * len(self.items))(*[self.desc(*self._fields(it)) for it in self.items])
+        call(self.entry, C.cast(arr, C.c_void_p), len(arr), *args, *([] if self.dtype is None else [dcode(self.dtype)]), stream_ptr())
+        self.items = []
+
+
 class _WgradDesc(C.Structure):
     """omlm_gemm_wgrad_desc (include/omlm.h)"""
     _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("c_map", C.c_void_p),
                 ("M", C.c_int), ("N", C.c_int), ("K", C.c_int), ("lda", C.c_int), ("ldb", C.c_int), ("ldc", C.c_int)]
 
 
-class WgradGroup:
+class WgradGroup(_DescGroup):
     """Collects the weight-gradient contractions dW[M,N] += dY[K,M]^T X[K,N] of a backward pass (16-bit operands of ONE type, rows =
     tokens) and issues them as ONE grouped launch (omlm_gemm_wgrad_group).  The operands are kept alive until :meth:`flush`."""
-
-    def __init__(self):
-        self.items = []
-        self.dtype = None
+    desc, entry = _WgradDesc, "omlm_gemm_wgrad_group"
 
     def add(self, dY: torch.Tensor, X: torch.Tensor, dW: torch.Tensor, *, M: int, N: int, K: int, c_map=None):
         hip.require_gpu(dY, "dY")
@@ -212,15 +229,7 @@ class WgradGroup:
         self.items.append((dY, X, dW, c_map, M, N, K, dY.shape[-1], X.shape[-1], dW.shape[-1]))
 
     def flush(self, splits: int = 0):
-        n = len(self.items)
-        if n == 0:
-            return
-        arr = (_WgradDesc * n)()
-        for d, (dY, X, dW, c_map, M, N, K, lda, ldb, ldc) in zip(arr, self.items):
-            d.A, d.B, d.C, d.c_map = ptr(dY), ptr(X), ptr(dW), ptr(c_map)
-            d.M, d.N, d.K, d.lda, d.ldb, d.ldc = M, N, K, lda, ldb, ldc
-        call("omlm_gemm_wgrad_group", C.cast(arr, C.c_void_p), n, int(splits), dcode(self.dtype), stream_ptr())
-        self.items = []
+        super().flush(int(splits))
 
 
 class _CastDesc(C.Structure):
@@ -229,11 +238,9 @@ class _CastDesc(C.Structure):
                 ("transpose", C.c_int), ("lo", C.c_int)]
 
 
-class CastPadGroup:
-    """Collects weight re-packs (cast_pad / transpose_cast problems with ONE output type) and issues them as one launch."""
-
-    def __init__(self):
-        self.items, self.dtype = [], None
+class CastPadGroup(_DescGroup):
+    """Collects weight re-packs (cast_pad problems, plain or transposed, with ONE output type) and issues them as one launch."""
+    desc, entry = _CastDesc, "omlm_cast_pad_group"
 
     def add(self, src, dst, R, C_, ld_src, ld_dst, transpose=False, lo=False):
         """lo: dst receives the lo plane rne16(v - rne16(v)) of the cast (the hi/lo weight planes of precision "fp16ff")."""
@@ -241,16 +248,6 @@ class CastPadGroup:
         assert src.dtype == torch.float32 and self.dtype in (None, dst.dtype), "fp32 sources, one output type per group"
         self.dtype = dst.dtype
         self.items.append((src, dst, int(R), int(C_), int(ld_src), int(ld_dst), int(bool(transpose)), int(bool(lo))))
-
-    def flush(self):
-        n = len(self.items)
-        if n == 0:
-            return
-        arr = (_CastDesc * n)()
-        for d, (src, dst, R, C_, ld_src, ld_dst, tr, lo) in zip(arr, self.items):
-            d.src, d.dst, d.R, d.C, d.ld_src, d.ld_dst, d.transpose, d.lo = ptr(src), ptr(dst), R, C_, ld_src, ld_dst, tr, lo
-        call("omlm_cast_pad_group", C.cast(arr, C.c_void_p), n, dcode(self.dtype), stream_ptr())
-        self.items = []
 
 
 def layernorm_fwd(x, gamma, y, xcast, mean, rstd, eps=1e-5):
@@ -281,28 +278,19 @@ class _QuantDesc(C.Structure):
                 ("R", C.c_int), ("C", C.c_int), ("ld_src", C.c_int), ("ld8", C.c_int)]
 
 
-class QuantRowsGroup:
+class QuantRowsGroup(_DescGroup):
     """Collects the fp8 re-packs of fp32 weights (rows [row0, row0 + R) of an Fp8Planes from src [R, C]) and issues them as one launch."""
-
-    def __init__(self):
-        self.items = []
+    desc, entry = _QuantDesc, "omlm_quant_rows_mx"
 
     def add(self, src, P: "Fp8Planes", row0: int, R: int, C_: int, ld_src: int):
         hip.require_gpu(src, "src")
         assert src.dtype == torch.float32 and row0 + R <= P.rows and C_ <= 2 * P.ld
         self.items.append((src, P, int(row0), int(R), int(C_), int(ld_src)))
 
-    def flush(self):
-        n = len(self.items)
-        if n == 0:
-            return
-        arr = (_QuantDesc * n)()
-        for d, (src, P, row0, R, C_, ld_src) in zip(arr, self.items):
-            pitch = 2 * P.ld
-            d.src, d.dst8, d.lo_stride, d.scale8 = ptr(src), P.planes.data_ptr() + row0 * pitch, P.stride, P.scale.data_ptr() + row0
-            d.R, d.C, d.ld_src, d.ld8 = R, C_, ld_src, pitch
-        call("omlm_quant_rows_mx", C.cast(arr, C.c_void_p), n, stream_ptr())
-        self.items = []
+    def _fields(self, item):
+        src, P, row0, R, C_, ld_src = item
+        pitch = 2 * P.ld
+        return ptr(src), P.planes.data_ptr() + row0 * pitch, P.stride, P.scale.data_ptr() + row0, R, C_, ld_src, pitch
 
 
 _LN_WS = {}
@@ -320,25 +308,13 @@ class _ColsumDesc(C.Structure):
     _fields_ = [("part", C.c_void_p), ("out", C.c_void_p), ("P", C.c_int), ("C", C.c_int), ("ldp", C.c_int)]
 
 
-class ColsumGroup:
+class ColsumGroup(_DescGroup):
     """Collects column sums out[c] += sum_p part[p, c] (the d(gamma) partial rows of the LayerNorm backwards of one backward pass) and issues
     them as ONE launch (omlm_colsum_group).  The partial buffers are kept alive until :meth:`flush`."""
-
-    def __init__(self):
-        self.items = []
+    desc, entry = _ColsumDesc, "omlm_colsum_group"
 
     def add(self, part: torch.Tensor, out: torch.Tensor, P: int, C_: int, ldp: int):
         self.items.append((part, out, int(P), int(C_), int(ldp)))
-
-    def flush(self):
-        n = len(self.items)
-        if n == 0:
-            return
-        arr = (_ColsumDesc * n)()
-        for d, (part, out, P, C_, ldp) in zip(arr, self.items):
-            d.part, d.out, d.P, d.C, d.ldp = ptr(part), ptr(out), P, C_, ldp
-        call("omlm_colsum_group", C.cast(arr, C.c_void_p), n, stream_ptr())
-        self.items = []
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dx, dxcast, dgamma, dx_scale=1.0, dres2=None, defer: Optional["ColsumGroup"] = None):
@@ -347,16 +323,16 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dx, dxcast, dgamma, dx_scale=1
     M, D = x.shape
     code = dcode(dxcast.dtype) if dxcast is not None else (dcode(dres2.dtype) if dres2 is not None else F32)
     assert dres2 is None or dcode(dres2.dtype) == code, "dres2 must have the cast type"
-    if dgamma is not None and defer is not None:
-        rows = min(M, 2048)
+    deferred = dgamma is not None and defer is not None
+    rows = min(M, 2048)
+    if deferred:
         ws = torch.empty(rows * D, device=x.device)     # private, alive until the group's flush: one partial row per workgroup (min(M, 2048) of them)
-        call("omlm_layernorm_bwd2", ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dres2), ptr(dx),
-             ptr(dxcast), None, ptr(ws), M, D, float(dx_scale), code, dcode(dy.dtype), stream_ptr())
-        defer.add(ws, dgamma, rows, D, D)
-        return
-    ws = _ln_workspace(D, x.device) if dgamma is not None else None       # stream-ordered reuse: one backward at a time
+    else:
+        ws = _ln_workspace(D, x.device) if dgamma is not None else None       # stream-ordered reuse: one backward at a time
     call("omlm_layernorm_bwd2", ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dres2), ptr(dx),
-         ptr(dxcast), ptr(dgamma), ptr(ws), M, D, float(dx_scale), code, dcode(dy.dtype), stream_ptr())
+         ptr(dxcast), ptr(None if deferred else dgamma), ptr(ws), M, D, float(dx_scale), code, dcode(dy.dtype), stream_ptr())
+    if deferred:
+        defer.add(ws, dgamma, rows, D, D)
 
 
 def qk_norm_fwd(q_raw, kv_raw, q_scale, k_scale, q, k, v, H):
@@ -475,10 +451,6 @@ def attn_bwd(q, k, v, bias, keymask, out, dout, lse, delta, dq, dk, dv, dbias, B
     call("omlm_mqa_attn_bwd", ptr(q), ptr(k), ptr(v), ptr(table), ptr(tableT), ptr(keymask), ptr(out), ptr(dout), ptr(lse), ptr(delta), ptr(dq),
          ptr(dk), ptr(dv), ptr(dbias), ptr(ws), B, N, H, float(scale), ld, dcode(q.dtype), int(P), float(p), int(seed), ptr(seed_dev),
          stream_ptr())
-
-
-# the former prefix wrappers' names: their arguments were these, P in the same place
-attn_fwd_prefix, attn_bwd_prefix = attn_fwd, attn_bwd
 
 
 def attn_dropout_keep(B, N, H, p, seed, seed_dev=None, device=None) -> torch.Tensor:
@@ -677,28 +649,17 @@ def cast_pad(src, dst, R, C_, ld_src, ld_dst):
     call("omlm_cast_pad", ptr(src), ptr(dst), R, C_, ld_src, ld_dst, dcode(dst.dtype), stream_ptr())
 
 
-def transpose_cast(src, dst, R, C_, ld_src, ld_dst):
-    """dst[c, r] = cast(src[r, c]) for r < R, c < C_ (fp32 source, dst fp32 or bf16)."""
-    call("omlm_transpose_cast", ptr(src), ptr(dst), R, C_, ld_src, ld_dst, dcode(dst.dtype), stream_ptr())
-
-
 def colsum_accumulate(part, out, P, C_, ldp):
     call("omlm_colsum_accumulate", ptr(part), ptr(out), P, C_, ldp, stream_ptr())
 
 
 def relpos_first_fwd(w0, b0, pre, z, n, Hd, x0=0):
     """Rows are the distances x0 .. x0 + n - 1."""
-    if x0:
-        call("omlm_relpos_first_fwd_from", ptr(w0), ptr(b0), ptr(pre), ptr(z), n, Hd, int(x0), stream_ptr())
-        return
-    call("omlm_relpos_first_fwd", ptr(w0), ptr(b0), ptr(pre), ptr(z), n, Hd, stream_ptr())
+    call("omlm_relpos_first_fwd", ptr(w0), ptr(b0), ptr(pre), ptr(z), n, Hd, int(x0), stream_ptr())
 
 
 def relpos_first_bwd(ds, dw0, n, Hd, x0=0):
-    if x0:
-        call("omlm_relpos_first_bwd_from", ptr(ds), ptr(dw0), n, Hd, int(x0), stream_ptr())
-        return
-    call("omlm_relpos_first_bwd", ptr(ds), ptr(dw0), n, Hd, stream_ptr())
+    call("omlm_relpos_first_bwd", ptr(ds), ptr(dw0), n, Hd, int(x0), stream_ptr())
 
 
 def bias_silu_fwd(a, b, pre, z, R, C_):
@@ -717,33 +678,20 @@ def relpos_mlp_fwd(w0, b0, W1, b1, W2, b2, W3, b3, saves, table, n, Hd, H, ldb, 
     """The whole rel-pos MLP as one launch (omlm_relpos_mlp_fwd).  saves: None or [pre0, z0, pre1, z1, pre2, z2] ([n, Hd] fp32 each).
     x0: the distance of row 0 (negative for a non-causal prefix)."""
     sv = saves if saves is not None else [None] * 6
-    if x0:
-        call("omlm_relpos_mlp_fwd_from", ptr(w0), ptr(b0), ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(W3), ptr(b3), *[ptr(t) for t in sv],
-             ptr(table), int(n), int(Hd), int(H), int(ldb), int(x0), stream_ptr())
-        return
     call("omlm_relpos_mlp_fwd", ptr(w0), ptr(b0), ptr(W1), ptr(b1), ptr(W2), ptr(b2), ptr(W3), ptr(b3), *[ptr(t) for t in sv], ptr(table),
-         int(n), int(Hd), int(H), int(ldb), stream_ptr())
+         int(n), int(Hd), int(H), int(ldb), int(x0), stream_ptr())
 
 
 def relpos_mlp_bwd(dtable, W1, W2, W3, saves, scratch, grads, n, Hd, H, ldb, x0=0):
     """Backward of the fused MLP: saves = [pre0, z0, pre1, z1, pre2, z2]; grads = [gw0, gb0, gW1, gb1, gW2, gb2, gW3, gb3] (accumulated into)."""
-    if x0:
-        call("omlm_relpos_mlp_bwd_from", ptr(dtable), ptr(W1), ptr(W2), ptr(W3), *[ptr(t) for t in saves], ptr(scratch),
-             *[ptr(g) for g in grads], int(n), int(Hd), int(H), int(ldb), int(x0), stream_ptr())
-        return
     call("omlm_relpos_mlp_bwd", ptr(dtable), ptr(W1), ptr(W2), ptr(W3), *[ptr(t) for t in saves], ptr(scratch), *[ptr(g) for g in grads],
-         int(n), int(Hd), int(H), int(ldb), stream_ptr())
+         int(n), int(Hd), int(H), int(ldb), int(x0), stream_ptr())
 
 
 def rvq_encode(x, codebooks_T, indices, residual_out, n, D, C_, nstage, idx_stride=None):
     """Residual-VQ chain in the library's distance form (-cdist, first maximum; csrc/optim_misc.hip FORM_CDIST).
     indices: int32 [n, nstage] (or, with nstage == 1, any int32 view whose rows are idx_stride elements apart)."""
-    if idx_stride is None or idx_stride == nstage:
-        call("omlm_rvq_encode", ptr(x), ptr(codebooks_T), ptr(indices), ptr(residual_out), n, D, C_, nstage, stream_ptr())
-    else:
-        assert nstage == 1
-        call("omlm_rvq_encode_strided", ptr(x), ptr(codebooks_T), ptr(indices), int(idx_stride), ptr(residual_out), n, D, C_,
-             stream_ptr())
+    call("omlm_rvq_encode", ptr(x), ptr(codebooks_T), ptr(indices), ptr(residual_out), n, D, C_, nstage, int(idx_stride or 0), stream_ptr())
 
 
 def nearest_centroid(x, centroids_T, indices, n, D, C_):

@@ -207,9 +207,8 @@ class _TrunkFunction(torch.autograd.Function):
             raise RuntimeError("standalone Transformer.forward needs the module to be owned by a "
                                "TokenConditionedTransformer (weight preparation walks the owner)")
         xf = x.detach().reshape(B * N, D).contiguous().float()
-        y, saved = engine.trunk_forward(tr, pw, xf, keymask, B, N, True, tr.training)
+        y, lo, saved = engine.trunk_forward(tr, pw, xf, keymask, B, N, True, tr.training)    # lo: precision "fp16ff", y as hi/lo planes
         ctx.tr, ctx.pw, ctx.saved, ctx.B, ctx.N, ctx.np = tr, pw, saved, B, N, len(params)
-        lo = y.__dict__.pop("_omlm_lo", None)            # precision "fp16ff": the final LayerNorm's output arrives as hi/lo planes
         out = y.float() if lo is None else y.float() + lo.float()
         return out.view(B, N, D)
 

@@ -1070,6 +1070,8 @@ def test_rvq_and_kmeans_bit_exact(ops, dev, golden_dir):
     i3 = torch.empty(zz["indices"].shape, dtype=torch.int32, device=dev)
     ops.rvq_encode(torch.from_numpy(zz["x"]).to(dev), cq, i3, None, *zz["x"].shape, zz["codebooks"].shape[1], zz["codebooks"].shape[0])
     assert np.array_equal(i3.cpu().numpy().astype(np.int64), zz["indices"])
+    with pytest.raises(RuntimeError, match="omlm_rvq_encode"):               # a row stride belongs to the one-stage form: refused before any launch
+        ops.rvq_encode(torch.from_numpy(x).to(dev), cbT, idx, res, 33, 512, 256, 2, idx_stride=12)
     report("rvq_kmeans", exact=True)
 
 

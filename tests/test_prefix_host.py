@@ -36,7 +36,7 @@ def test_t5_buckets_of_negative_distances_match_the_oracle(n, P):
 
 @pytest.mark.parametrize("n,P", [(50, 14), (90, 90)])
 def test_continuous_rows_of_negative_distances_match_the_oracle(n, P):
-    """The MLP evaluated at x = x0 + row (omlm_relpos_mlp_fwd_from / omlm_relpos_first_fwd_from) is the oracle's table over x0 .. n - 1."""
+    """The MLP evaluated at x = x0 + row (omlm_relpos_mlp_fwd / omlm_relpos_first_fwd with x0) is the oracle's table over x0 .. n - 1."""
     from open_musiclm_amd.engine import relpos_rows
     rows, x0 = relpos_rows(n, P)
     g = torch.Generator().manual_seed(3)

@@ -103,10 +103,10 @@ def diag_trunk_forward(tr, pw16, x, keymask, B, N, save, training):
     mf = torch.empty(Mr, device=dev); rf = torch.empty(Mr, device=dev)
     y = torch.empty(Mr, D, device=dev)
     ops.layernorm_fwd(x, tr.norm.gamma.detach(), y, None, mf, rf)
-    return y, None
+    return y, None, None
 
 
-def diag_heads_forward(model, pw16, y32, lay, want):
+def diag_heads_forward(model, pw16, y32, y_lo, lay, want):
     pw32 = model.__dict__["_diag_pw32"]
     out = []
     for s, seq in enumerate(model.token_sequences):

@@ -37,7 +37,7 @@ typedef int (*fbwd_t)(const void*, const void*, const void*, const void*, const 
                       int, int, int, int, float, unsigned long long, const unsigned long long*, const unsigned char*, const void*, int, void*);
 typedef int (*lnf_t)(const float*, const float*, void*, void*, float*, float*, int, int, int, float, int, void*);
 typedef long long (*lnws_t)(int);
-typedef int (*lnb_t)(const void*, const float*, const float*, const float*, const float*, const float*, float*, void*, float*, float*, int, int, float, int, int, void*);
+typedef int (*lnb_t)(const void*, const float*, const float*, const float*, const float*, const float*, const void*, float*, void*, float*, float*, int, int, float, int, int, void*);
 typedef int (*dstep_t)(const omlm_decode_args*, const long long*, void*);
 typedef int (*planes_t)(const void*, long long, const void*, long long, void*, const float*, const int*, const int*, const int*, long long, long long,
                         int, int, int, int, int, int, int, int, int, int, float, void*, long long, void*);
@@ -52,7 +52,7 @@ struct Lib {
         prep = (prep_t)dlsym(h, "omlm_attn_bias_prepare"); tbl = (tbl_t)dlsym(h, "omlm_attn_bias_table_floats");
         gemm = (gemm_t)dlsym(h, "omlm_gemm"); err = (err_t)dlsym(h, "omlm_last_error"); wgrad = (wgrad_t)dlsym(h, "omlm_gemm_wgrad_group"); planes = (planes_t)dlsym(h, "omlm_gemm_planes");
         ffwd = (ffwd_t)dlsym(h, "omlm_ffmid_fwd"); fws = (fws_t)dlsym(h, "omlm_ffmid_bwd_workspace_bytes"); fbwd = (fbwd_t)dlsym(h, "omlm_ffmid_bwd");
-        lnf = (lnf_t)dlsym(h, "omlm_layernorm_fwd"); lnws = (lnws_t)dlsym(h, "omlm_layernorm_bwd_workspace_bytes"); lnb = (lnb_t)dlsym(h, "omlm_layernorm_bwd"); dstep = (dstep_t)dlsym(h, "omlm_decode_step");
+        lnf = (lnf_t)dlsym(h, "omlm_layernorm_fwd"); lnws = (lnws_t)dlsym(h, "omlm_layernorm_bwd_workspace_bytes"); lnb = (lnb_t)dlsym(h, "omlm_layernorm_bwd2"); dstep = (dstep_t)dlsym(h, "omlm_decode_step");
         if (!fwd || !bwd || !bwsz || !prep || !tbl || !gemm || !err) { fprintf(stderr, "%s: missing symbol\n", p); exit(1); }
     }
     void ok(int rc, const char* what) { if (rc != 0) { fprintf(stderr, "%s: %s failed (%d): %s\n", path.c_str(), what, rc, err()); exit(1); } }
@@ -416,7 +416,7 @@ static void ln_case(Lib& A, Lib& Bl) {
         float *st = dev_zero<float>((size_t)2 * M), *dxo = dev_zero<float>((size_t)M * D), *dg = dev_zero<float>(D);
         float* ws = dev_zero<float>((size_t)(L.lnws(D) + 3) / 4 + 4);
         auto fwd = [&] { L.ok(L.lnf(dx_, dgam, y, xc, st, st + M, M, D, D, 1e-5f, 1, nullptr), "ln_fwd"); };
-        auto bwd = [&] { L.ok(L.lnb(ddy, dx_, dgam, st, st + M, ddres, dxo, dxc, dg, ws, M, D, 1.0f, 1, 1, nullptr), "ln_bwd"); };
+        auto bwd = [&] { L.ok(L.lnb(ddy, dx_, dgam, st, st + M, ddres, nullptr, dxo, dxc, dg, ws, M, D, 1.0f, 1, 1, nullptr), "ln_bwd"); };
         fwd(); bwd(); CK(hipDeviceSynchronize());
         r_y[li] = host(y, (size_t)M * D); r_xc[li] = host(xc, (size_t)M * D); r_dxc[li] = host(dxc, (size_t)M * D);
         r_st[li] = host(st, (size_t)2 * M); r_dx[li] = host(dxo, (size_t)M * D); r_dg[li] = host(dg, (size_t)D);
