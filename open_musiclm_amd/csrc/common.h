@@ -31,6 +31,14 @@ static inline int omlm_post_launch(const char* what) {
     return OMLM_OK;
 }
 
+// Launch with dynamic LDS: sizes above 64 KiB need the opt-in attribute, set once per kernel instantiation.
+template <auto Kernel, typename Args>
+static inline void launch_with_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args& args) {
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args);
+}
+
 // ---- the 16-bit GEMM / attention operand type of this build -----------------------------------------------------------------
 // Every source that touches 16-bit operands is compiled TWICE: once with h16_t = bf16 (precision "bf16"; also hosts the fp32 /
 // "bf16x3" instantiations) and once with -DOMLM_FP16=1, h16_t = IEEE half (precision "fp16": same v_mfma_f32_32x32x16 rate, 11

@@ -38,6 +38,7 @@
 // into C (these GEMMs are "C += ..." by construction: gradients accumulate over micro-batches).
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_plan.h"
 
 namespace OMLM_NS {
 
@@ -618,189 +619,127 @@ template __global__ void gemm_tile8_kernel<false, false, h16pl_t, true>(GemmArgs
 template __global__ void gemm_tile8_kernel<false, false, float, true>(GemmArgs);
 }   // namespace
 #else
+using namespace omlm_plan;         // csrc/gemm_plan.h: every route decision below is taken there
+static_assert(BK == KT && BM == 128 && BN == 128 && NTHREADS == 256, "gemm_plan.h plans for these tiles");
+
+// The CU count, queried once per copy of the library; the planners receive the two numbers as arguments.
+static int gemm_cu_query() {
+    static int cus = -1;
+    if (cus < 0) {
+        int dev = 0, n = 0;
+        cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 0;
+    }
+    return cus;
+}
+__attribute__((visibility("hidden"))) int gemm_ncu() { const int n = gemm_cu_query(); return n > 0 ? n : 256; }
 // workgroups of the persistent walk: one per CU, rounded down to a multiple of 8 (the walk's stride must keep a workgroup on its XCD);
-// 0 = switched off (OMLM_GEMM_PERSIST=0)
-static int gemm_persist_slots() {
-    static int ncu8 = -1;
-    if (ncu8 < 0) {
-        int dev = 0, n = 0;
-        ncu8 = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n >= 8) ? n / 8 * 8 : 0;
-    }
-    const char* e = getenv("OMLM_GEMM_PERSIST");                   // read per call: tests toggle it inside one process
-    return (e && e[0] == '0') ? 0 : ncu8;
+// 0 = none (fewer than 8 CUs, or the query failed)
+__attribute__((visibility("hidden"))) int gemm_persist_slots() { const int n = gemm_cu_query(); return n >= 8 ? n / 8 * 8 : 0; }
+
+static GemmArgs gemm_args() {      // every field zero / NULL (the three retired ones included), alpha = 1
+    GemmArgs g;
+    memset(&g, 0, sizeof(g));
+    g.alpha = 1.f;
+    return g;
 }
 
-// OMLM_GEMM_T8: the half-tile-ring schedule (gemm_tile8_body) for the 256 x 256 tiles: 0 = off, 1 = every eligible launch, 2 (default) =
-// where it measured faster (profiles/r05b_gemm_t8_ab.md, same box, bit-identical results): the grouped weight gradients (557 k-tiles per
-// tile: +6 %) and multi-round launches with K >= 2048 (d(xn2), K = 5504: +3 %; FF-out, K = 2752: +2 %; 8192^3: +15 %).  Short contractions
-// (K = 1024: 16 k-tiles per tile) stay on the persistent walk of the rotated loop, which hides the per-tile prologue / epilogue that this
-// one-tile-per-workgroup form exposes (FF-in 373 vs 399 us).  Read per call (tests and tools/lib_ab toggle it).
-static int gemm_t8_mode() {
-    const char* e = getenv("OMLM_GEMM_T8");
-    return e ? atoi(e) : OMLM_GEMM_T8_DEFAULT;
-}
-static bool gemm_t8_wanted(int K, int tiles, int splits) {
-    const int mode = gemm_t8_mode();
-    if (mode <= 0) return false;
-    if (mode == 1) return true;
-    static int ncu = 0;                                            // more than one round of one-workgroup-per-CU tiles (whatever OMLM_GEMM_PERSIST says)
-    if (ncu == 0) {
-        int dev = 0, n = 0;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return splits == 1 && K >= 2048 && tiles > ncu;
-}
-
-template <int BM_, int BN_, int WM_, int WN_, typename TOUT>
-static int launch_tile(const GemmArgs& g, int a_kmaj, int b_kmaj, int splits, hipStream_t st) {
-    constexpr int NTH = (BM_ / WM_) * (BN_ / WN_) * 64;
-    constexpr size_t LDS = 2 * (size_t)(BM_ + BN_) * BK * 2;
-    const int tiles = ((g.M + BM_ - 1) / BM_) * ((g.N + BN_ - 1) / BN_);
-    dim3 grid(tiles, splits), block(NTH);
-    if constexpr (BM_ == 256 && BN_ == 256) {
-        // whole k-tiles, no maps on the operand side (a scatter map of C and split-K are fine)
-        // (the hi/lo-plane route runs a 3x k-loop: K >= 704 already is a long contraction for it; its instantiations exist in the bf16 copy only)
-        if (gemm_t8_wanted(g.split3 ? 3 * g.K : g.K, tiles, splits) && g.K % BK == 0 && !g.a_map && !g.b_map &&
-            (!g.split3 || !OMLM_FP16)) {
-#define OMLM_T8_LAUNCH(AK, BKM)                                                                                       \
-            do {                                                                                                       \
-                auto k8 = gemm_tile8_kernel<AK, BKM, TOUT>;                                                            \
-                static bool attr8 = false;                                                                             \
-                if (!attr8) { (void)hipFuncSetAttribute((const void*)k8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); attr8 = true; } \
-                if constexpr (!OMLM_FP16) {                                                                            \
-                    auto k83 = gemm_tile8_kernel<AK, BKM, TOUT, true>;                                                 \
-                    static bool attr83 = false;                                                                        \
-                    if (!attr83) { (void)hipFuncSetAttribute((const void*)k83, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); attr83 = true; } \
-                    if (g.split3) { hipLaunchKernelGGL(k83, grid, block, LDS, st, g); break; }                         \
-                }                                                                                                      \
-                hipLaunchKernelGGL(k8, grid, block, LDS, st, g);                                                       \
-            } while (0)
-            if (!a_kmaj && !b_kmaj)      OMLM_T8_LAUNCH(false, false);
-            else if (!a_kmaj && b_kmaj)  OMLM_T8_LAUNCH(false, true);
-            else if (a_kmaj && b_kmaj)   OMLM_T8_LAUNCH(true, true);
-            else                         OMLM_T8_LAUNCH(true, false);
-#undef OMLM_T8_LAUNCH
-            return omlm_post_launch("omlm_gemm");
+// one planned launch of the 16-bit tile kernels: the k-loop form
+template <int BM_, int BN_, int WM_, int WN_, bool AK, bool BKM, typename TOUT>
+static void launch_form(const GemmArgs& g, const GemmLaunch& l, hipStream_t st) {
+    const dim3 grid(l.grid_x, l.grid_y), block(l.threads);
+    switch (l.form) {
+    case FORM_RING:
+        if constexpr (BM_ == 256 && BN_ == 256) {
+            if constexpr (!OMLM_FP16)
+                if (g.split3) return launch_with_lds<gemm_tile8_kernel<AK, BKM, TOUT, true>>(grid, block, l.lds, st, g);
+            return launch_with_lds<gemm_tile8_kernel<AK, BKM, TOUT>>(grid, block, l.lds, st, g);
         }
+        return;
+    case FORM_PERSIST:
+        if constexpr (!AK && BM_ == BN_) {
+            if (g.Cin) return launch_with_lds<gemm_bf16_tile_persist_kernel<BM_, BN_, WM_, WN_, false, BKM, TOUT, true>>(grid, block, l.lds, st, g);
+            return launch_with_lds<gemm_bf16_tile_persist_kernel<BM_, BN_, WM_, WN_, false, BKM, TOUT, false>>(grid, block, l.lds, st, g);
+        }
+        return;
+    case FORM_ROT_SPLIT3:           // (instantiated in the bf16 copy only)
+        if constexpr (!OMLM_FP16) launch_with_lds<gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, true>>(grid, block, l.lds, st, g);
+        return;
+    case FORM_ROT_KMAP:  return launch_with_lds<gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, (AK || BKM) && BM_ == 128>>(grid, block, l.lds, st, g);
+    case FORM_ROT_FASTK: return launch_with_lds<gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, false, true>>(grid, block, l.lds, st, g);
+    default:             return launch_with_lds<gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false>>(grid, block, l.lds, st, g);
     }
-    const bool need_kmap = (a_kmaj && g.a_map) || (b_kmaj && g.b_map);       // host routes these to the 128x128 tile
-    if (need_kmap && BM_ != 128) { omlm_set_error("omlm_gemm: k-row maps are only built for the 128x128 tile"); return OMLM_ERR_UNSUPPORTED; }
-    // The fp16 copy of this file (common.h: OMLM_FP16) instantiates only the production kernel and its k-row-map form: the hi/lo-plane
-    // (SPLIT3) instantiations exist once, in the bf16 copy.
-#define OMLM_TILE_LAUNCH(AK, BKM)                                                                                          \
-    do {                                                                                                                    \
-        auto kfn = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false>;                                        \
-        auto kmap = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, (AK || BKM) && BM_ == 128>;                   \
-        auto kfast = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, false, true>;                         \
-        static bool attr = false;                                                                                           \
-        if (!attr) {                                                                                                        \
-            (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);             \
-            (void)hipFuncSetAttribute((const void*)kfast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);           \
-            (void)hipFuncSetAttribute((const void*)kmap, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);            \
-        }                                                                                                                   \
-        if constexpr (!OMLM_FP16) {                                                                                         \
-            auto ks3 = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, AK, BKM, TOUT, false, true>;                               \
-            if (!attr) (void)hipFuncSetAttribute((const void*)ks3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);  \
-            attr = true;                                                                                                    \
-            if (g.split3) { hipLaunchKernelGGL(ks3, grid, block, LDS, st, g); break; }                                     \
-        }                                                                                                                   \
-        attr = true;                                                                                                        \
-        if (need_kmap) hipLaunchKernelGGL(kmap, grid, block, LDS, st, g);                                                  \
-        else if (g.K % BK == 0) hipLaunchKernelGGL(kfast, grid, block, LDS, st, g);                                        \
-        else           hipLaunchKernelGGL(kfn, grid, block, LDS, st, g);                                                   \
-    } while (0)
-    // Persistent walk (gemm_bf16_tile_persist_kernel) for the wide tile when the problem is more than one round of the machine:
-    // whole k-tiles, k-contiguous A, no maps on the k side, no split, no plane mode.  OMLM_GEMM_PERSIST=0 keeps the one-tile grid.
-    if constexpr ((BM_ == 256 && BN_ == 256) || (BM_ == 128 && BN_ == 128)) {
-        const int slots = gemm_persist_slots() * (BM_ == 128 ? 2 : 1);             // 64 KiB tiles: two workgroups per CU
-        if (slots > 0 && !a_kmaj && splits == 1 && !g.split3 && !g.a_map && !g.b_map && !g.c_map && g.K % BK == 0 && tiles > slots) {
-            constexpr size_t LDSP = LDS + 32 * (WN_ + 4) * 4;
-            static bool pattr = false;
-            auto k0 = gemm_bf16_tile_persist_kernel<BM_, BN_, WM_, WN_, false, false, TOUT, false>;
-            auto k1 = gemm_bf16_tile_persist_kernel<BM_, BN_, WM_, WN_, false, true, TOUT, false>;
-            auto k0c = gemm_bf16_tile_persist_kernel<BM_, BN_, WM_, WN_, false, false, TOUT, true>;
-            auto k1c = gemm_bf16_tile_persist_kernel<BM_, BN_, WM_, WN_, false, true, TOUT, true>;
-            if (!pattr) {
-                (void)hipFuncSetAttribute((const void*)k0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSP);
-                (void)hipFuncSetAttribute((const void*)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSP);
-                (void)hipFuncSetAttribute((const void*)k0c, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSP);
-                (void)hipFuncSetAttribute((const void*)k1c, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSP);
-                pattr = true;
+}
+
+// ... on one tile: the operand layouts and the output type.  The hi/lo-plane route of omlm_gemm_planes16 (row-major A [M, K] and B [N, K]) is
+// built in both copies of the file (TOUT: float, or h16pl_t = the result leaves as planes too).
+template <int BM_, int BN_, int WM_, int WN_>
+static void launch_tile(const GemmArgs& g, const GemmShape& s, const GemmLaunch& l, hipStream_t st) {
+    if (s.planes16) {
+        const dim3 grid(l.grid_x, l.grid_y), block(l.threads);
+        if constexpr (BM_ == 256 && BN_ == 256) {
+            if (l.form == FORM_RING) {
+                if (g.C_lo) return launch_with_lds<gemm_tile8_kernel<false, false, h16pl_t, true>>(grid, block, l.lds, st, g);
+                return launch_with_lds<gemm_tile8_kernel<false, false, float, true>>(grid, block, l.lds, st, g);
             }
-            hipLaunchKernelGGL(g.Cin ? (b_kmaj ? k1c : k0c) : (b_kmaj ? k1 : k0), dim3(slots), block, LDSP, st, g);
-            return omlm_post_launch("omlm_gemm");
         }
+        if (g.C_lo) return launch_with_lds<gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, false, false, h16pl_t, false, true>>(grid, block, l.lds, st, g);
+        return launch_with_lds<gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, false, false, float, false, true>>(grid, block, l.lds, st, g);
     }
-    if (!a_kmaj && !b_kmaj)      OMLM_TILE_LAUNCH(false, false);
-    else if (!a_kmaj && b_kmaj)  OMLM_TILE_LAUNCH(false, true);
-    else if (a_kmaj && b_kmaj)   OMLM_TILE_LAUNCH(true, true);
-    else                         OMLM_TILE_LAUNCH(true, false);
-#undef OMLM_TILE_LAUNCH
-    return omlm_post_launch("omlm_gemm");
+    const bool f32 = s.out_dtype == 0;
+    switch (2 * s.a_kmajor + s.b_kmajor) {
+    case 0:  return f32 ? launch_form<BM_, BN_, WM_, WN_, false, false, float>(g, l, st) : launch_form<BM_, BN_, WM_, WN_, false, false, h16_t>(g, l, st);
+    case 1:  return f32 ? launch_form<BM_, BN_, WM_, WN_, false, true, float>(g, l, st) : launch_form<BM_, BN_, WM_, WN_, false, true, h16_t>(g, l, st);
+    case 3:  return f32 ? launch_form<BM_, BN_, WM_, WN_, true, true, float>(g, l, st) : launch_form<BM_, BN_, WM_, WN_, true, true, h16_t>(g, l, st);
+    default: return f32 ? launch_form<BM_, BN_, WM_, WN_, true, false, float>(g, l, st) : launch_form<BM_, BN_, WM_, WN_, true, false, h16_t>(g, l, st);
+    }
 }
 
-// The hi/lo-plane route of omlm_gemm_planes16 (row-major A [M, K] and B [N, K], no maps, no split-K): the half-tile-ring kernel for the
-// 256 x 256 tiles (whole k-tiles), the rotated-loop SPLIT3 kernel otherwise.  Both copies of the file build it (TOUT: float, or h16pl_t =
-// the result leaves as planes too).
-template <int BM_, int BN_, int WM_, int WN_, typename TOUT>
-static int launch_tile_s3(const GemmArgs& g, hipStream_t st, int splits = 1) {
-    constexpr int NTH = (BM_ / WM_) * (BN_ / WN_) * 64;
-    constexpr size_t LDS = 2 * (size_t)(BM_ + BN_) * BK * 2;
-    const int tiles = ((g.M + BM_ - 1) / BM_) * ((g.N + BN_ - 1) / BN_);
-    dim3 grid(tiles, splits), block(NTH);
-    if constexpr (BM_ == 256 && BN_ == 256) {
-        if (gemm_t8_mode() > 0 && g.K % BK == 0 && !g.a_map && splits == 1) {
-            auto k8 = gemm_tile8_kernel<false, false, TOUT, true>;
-            static bool attr8 = false;
-            if (!attr8) { (void)hipFuncSetAttribute((const void*)k8, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); attr8 = true; }
-            hipLaunchKernelGGL(k8, grid, block, LDS, st, g);
-            return omlm_post_launch("omlm_gemm_planes16");
-        }
+// ... of rows l.M of `g` (s: the shape the launch was planned for): the tile
+static int launch_planned(GemmArgs g, const GemmShape& s, const GemmLaunch& l, hipStream_t st) {
+    if (l.kmap_unbuilt) { omlm_set_error("omlm_gemm: k-row maps are only built for the 128x128 tile"); return OMLM_ERR_UNSUPPORTED; }
+    g.kt_per_split = l.kt_per_split;
+    switch (l.bm + l.bn) {
+    case 512: launch_tile<256, 256, 128, 64>(g, s, l, st); break;
+    case 384: launch_tile<256, 128, 64, 64>(g, s, l, st); break;
+    default:  launch_tile<128, 128, 64, 64>(g, s, l, st); break;
     }
-    auto ks3 = gemm_bf16_tile_kernel<BM_, BN_, WM_, WN_, false, false, TOUT, false, true>;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)ks3, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); attr = true; }
-    hipLaunchKernelGGL(ks3, grid, block, LDS, st, g);
-    return omlm_post_launch("omlm_gemm_planes16");
-}
-
-template <typename T, typename TOUT>
-static int launch_layout(const GemmArgs& g, int a_kmaj, int b_kmaj, int splits, hipStream_t st) {
-    const int tiles = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-    const size_t lds = 4 * (size_t)(BM * BK * 2);            // fp32: 4 planes (A/B x hi/lo); bf16: 2 buffers x (A | B)
-    dim3 grid(tiles, splits), block(NTHREADS);
-    if constexpr (elt_traits<T>::precise) {
-        if (!a_kmaj && !b_kmaj)      hipLaunchKernelGGL((gemm_kernel<T, false, false, TOUT>), grid, block, lds, st, g);
-        else if (!a_kmaj && b_kmaj)  hipLaunchKernelGGL((gemm_kernel<T, false, true, TOUT>), grid, block, lds, st, g);
-        else if (a_kmaj && b_kmaj)   hipLaunchKernelGGL((gemm_kernel<T, true, true, TOUT>), grid, block, lds, st, g);
-        else                         hipLaunchKernelGGL((gemm_kernel<T, true, false, TOUT>), grid, block, lds, st, g);
-    }
-    return omlm_post_launch("omlm_gemm");
+    return omlm_post_launch(s.planes16 ? "omlm_gemm_planes16" : "omlm_gemm");
 }
 
 // ---- the peeled tail as a deterministic split-K (round 5) -------------------------------------------------------------------------
-// The m-tile rows behind the last full round of 256 x 256 tiles run on 128 x 128 tiles (gemm_impl below): 48 ... 190 workgroups whose
+// The m-tile rows behind the last full round of 256 x 256 tiles run on 128 x 128 tiles (gemm_plan): 48 ... 190 workgroups whose
 // k-loops (86 k-tiles for d(xn2), 129 loop tiles for the FF-out plane route) are one serial chain each on a fraction of the machine
-// (80 / 121 us for ~35 / ~50 us of work at the chip's rate).  With a workspace (a per-call argument: gemm_impl's tail_ws) the tail's K range is cut
+// (80 / 121 us for ~35 / ~50 us of work at the chip's rate).  With a workspace (a per-call argument: GemmCall::ws) the tail's K range is cut
 // into S slices that fill the 2-per-CU slots, every slice STORES its fp32 partial tile to its own plane of the workspace (no atomics, no
 // pre-filled C), and gemm_tail_reduce_kernel adds the planes in a fixed order together with the residual and writes the output type
 // (fp32, 16-bit, or 16-bit hi/lo planes): deterministic, two launches.  The workspace belongs to the
 // caller and to ONE stream at a time (the library keeps no pointer: two streams pass two buffers); OMLM_GEMM_TAIL_SPLIT=0 or no workspace keeps the one-launch tail.
 
-static bool gemm_tail_split_on() {
-    const char* e = getenv("OMLM_GEMM_TAIL_SPLIT");                // read per call (tests toggle it)
-    return !(e && e[0] == '0');
-}
+// what a call says beside its GemmArgs.  dtype codes shared with the Python host: 0 = fp32, 1 = bf16
+struct GemmCall {
+    int a_kmajor, b_kmajor, in_dtype, out_dtype;
+    bool planes16, qknorm;         // the omlm_gemm_planes16 route / omlm_gemm_qknorm (its own checks stand in for the ones below)
+    void* ws; long long ws_bytes;  // tail workspace
+    void* stream;
+};
 
-// dtype codes shared with the Python host: 0 = fp32, 1 = bf16
-static int gemm_impl(const void* A, const void* B, void* C, const float* Cin,
-                     const int* a_map, const int* b_map, const int* c_map,
-                     long long a_rows, long long b_rows,
-                     int M, int N, int K, int lda, int ldb, int ldc, int ldcin,
-                     int a_kmajor, int b_kmajor, int in_dtype, int out_dtype, float alpha, void* stream,
-                     int split3, const void* A_lo, const void* B_lo, void* C_lo = nullptr, bool s3_route = false,
-                     float* tail_ws = nullptr, long long tail_ws_bytes = 0) {
+static int gemm_impl(GemmArgs g, const GemmCall& c) {
+    const int M = g.M, N = g.N, K = g.K;
     if (M <= 0 || N <= 0) return OMLM_OK;
+    hipStream_t st = as_stream(c.stream);
+    const GemmHooks hooks = gemm_hooks_from_env();
+    if (c.qknorm) {
+        const GemmLaunch l = qknorm_plan(M, N, K, gemm_persist_slots(), hooks);
+        g.kt_per_split = l.kt_per_split;
+        const dim3 grid(l.grid_x, l.grid_y), block(l.threads);
+        if (l.form == FORM_PERSIST)         launch_with_lds<gemm_bf16_tile_persist_kernel<128, 128, 64, 64, false, false, h16_t, false, 1>>(grid, block, l.lds, st, g);
+        else if (l.form == FORM_ROT_FASTK)  launch_with_lds<gemm_bf16_tile_kernel<128, 128, 64, 64, false, false, h16_t, false, false, true, 1>>(grid, block, l.lds, st, g);
+        else                                launch_with_lds<gemm_bf16_tile_kernel<128, 128, 64, 64, false, false, h16_t, false, false, false, 1>>(grid, block, l.lds, st, g);
+        return omlm_post_launch("omlm_gemm_qknorm");
+    }
+    const void *A = g.A, *B = g.B, *C = g.C;
+    const int lda = g.lda, ldb = g.ldb, a_kmajor = c.a_kmajor, b_kmajor = c.b_kmajor, in_dtype = c.in_dtype, out_dtype = c.out_dtype;
+    const long long a_rows = g.a_rows, b_rows = g.b_rows;
     OMLM_CHECK_ARG(A && B && C, "null operand");
     OMLM_CHECK_ARG(K > 0, "K must be positive");
     OMLM_CHECK_ARG((lda % 8) == 0 && (ldb % 8) == 0, "operand leading dimensions must be multiples of 8 elements");
@@ -814,168 +753,63 @@ static int gemm_impl(const void* A, const void* B, void* C, const float* Cin,
     if (a_kmajor) OMLM_CHECK_ARG(lda >= ((M + 7) / 8) * 8, "k-major A: row pitch shorter than M padded to 8");
     if (b_kmajor) OMLM_CHECK_ARG(ldb >= ((N + 7) / 8) * 8, "k-major B: row pitch shorter than N padded to 8");
     if (!a_kmajor || !b_kmajor) OMLM_CHECK_ARG(K % 8 == 0, "k-contiguous operands need K % 8 == 0 (zero-pad the contraction)");
-    GemmArgs g;
-    g.A = A; g.B = B; g.C = C; g.Cin = Cin; g.a_map = a_map; g.b_map = b_map; g.c_map = c_map;
-    g.a_rows = a_rows; g.b_rows = b_rows; g.M = M; g.N = N; g.K = K;
-    g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin; g.alpha = alpha;
-    g.bal_ck = 0; g.bal_chunks = 0; g.debug = 0;
-    g.split3 = split3; g.A_lo = A_lo; g.B_lo = B_lo; g.C_lo = C_lo; g.c_lo8 = 0; g.c_split_stride = 0;
-    g.epi_scale = nullptr; g.epi_norm = nullptr; g.epi_groups = 0; g.epi_ldnorm = 0; g.C2 = nullptr; g.c2_col0 = 0; g.ldc2 = 0;
-    hipStream_t st = as_stream(stream);
-    // tile shape (bf16 path): 256x256 when both output dims are wide, 256x128 for tall-narrow outputs, else 128x128
-    int bm = BM, bn = BN;
-    const char* force = getenv("OMLM_GEMM_TILE");
-    const bool need_kmap = (a_kmajor && a_map) || (b_kmajor && b_map);
-    if (in_dtype == 1 && !need_kmap) {
-        if (force && force[0]) { if (!strcmp(force, "256x256")) { bm = 256; bn = 256; } else if (!strcmp(force, "256x128")) { bm = 256; bn = 128; } }
-        // Short contractions onto narrow outputs (to_out, d(xn), d(x) of k | v: K <= 512, N <= 1024): with the persistent walk the 128x128
-        // tiles (two walkers per CU, 4 x the tiles to balance) beat the wide ones -- to_out 103 -> 92 us, d(xn) 57 -> 50 us (round 4 probe).
-        else if (K <= 512 && N <= 1024 && K % BK == 0 && !a_kmajor && !a_map && !b_map && !c_map && !split3 && Cin != (const float*)C &&
-                 ((M + 127) / 128) * ((N + 127) / 128) > 2 * gemm_persist_slots() && gemm_persist_slots() > 0) { bm = 128; bn = 128; }
-        else if (M >= 1024 && N >= 1024) { bm = 256; bn = 256; }   // measured (probe, N = 1024): 256x256 514 us, 128x128 543, 256x128 657
-        // N = 512 outputs (q-proj, d(o)): 128x128 (two workgroups per CU) measured 54 / 54 us against 60 / 59 for 256x128 (round 4 tile probe)
-        else if (M >= 2048 && N > 512) { bm = 256; bn = 128; }
-        else if (N >= 2048 && M >= 256) { bm = 256; bn = 256; }
-    }
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ncu = n;
-        else ncu = 256;
-    }
-    // split-K only for accumulate-into-C GEMMs with few output tiles (the weight-gradient contractions).  The 256-wide
-    // tiles run one workgroup per CU, so the split count is chosen for whole rounds of the machine: e.g. dW1 has 88 tiles;
-    // 12 splits = 1056 workgroups = 4.1 rounds (82 % of the last 5 used), 11 splits = 968 = 3.8 rounds (95 %).
-    const int nk = ((K + BK - 1) / BK) * (split3 ? 3 : 1);     // k-tiles of the loop (three plane pairs per real k-tile when split3)
-    const int tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
-    int splits = 1;
-    // fp32 operands (register-staged kernel: the rel-pos MLP's 0.3-GFLOP GEMMs, 36 / 16 output tiles) are latency-bound per k-tile, not per byte:
-    // they split down to TWO k-tiles per workgroup (54 -> ~20 us per launch; round 4), the 16-bit tile kernels keep their >= 8 k-tiles per split
-    const bool fine = in_dtype == 0 && !split3;
-    if (Cin == (const float*)C && out_dtype == 0 && tiles < 512 && nk >= (fine ? 4 : 16)) {
-        const int slots = (bm == 256 ? 1 : 2) * ncu;              // co-resident workgroups (LDS: 128 KiB tiles 1 / CU, 64 KiB 2 / CU)
-        int smax = fine ? nk / 2 : nk / 8; if (smax > 32) smax = 32; if (smax < 1) smax = 1;
-        int smin = (slots + tiles - 1) / tiles; if (smin > smax) smin = smax; if (smin < 1) smin = 1;      // at least one full round
-        float best = -1.f;
-        for (int sp = smin; sp <= smax; ++sp) {
-            const int total = tiles * sp, rounds = (total + slots - 1) / slots;
-            // every split adds one atomic pass over C.  Re-measured after the k-major DMA fix (tools/splitk_probe.py): with the k-loop
-            // faster the atomics weigh more -- 44 tiles (dW2): 5 / 11 splits = 233 / 267 us; 88 tiles (dW1): 5 / 8 / 11 = 479 / 478 / 515 us;
-            // 128x128 tiles (dWq, dWkv: 64 KiB partials) keep the old weight: 16 / 32 splits stay best there.
-            const float util = (float)total / (float)(rounds * slots) - (bm == 256 ? 0.02f : 0.012f) * (float)sp;
-            if (util > best) { best = util; splits = sp; }
-        }
-    }
-    g.kt_per_split = (nk + splits - 1) / splits;
-    splits = (nk + g.kt_per_split - 1) / g.kt_per_split;
-    // (A balanced split-K grid -- every workgroup the same number of k-tiles -- measured slower on dW1: 665 against 642 us; the k-major
-    // main loop, not the partial last round or the atomic volume, is what holds these GEMMs at ~620 TFLOP/s.)
+    GemmShape s;
+    s.M = M; s.N = N; s.K = K; s.a_kmajor = a_kmajor != 0; s.b_kmajor = b_kmajor != 0; s.a_map = g.a_map != nullptr; s.b_map = g.b_map != nullptr;
+    s.c_map = g.c_map != nullptr; s.in_dtype = in_dtype; s.out_dtype = out_dtype; s.split3 = g.split3 != 0; s.planes16 = c.planes16;
+    s.fp16_copy = OMLM_FP16 != 0; s.accumulates = g.Cin == (const float*)C; s.cin = g.Cin != nullptr; s.alpha_one = g.alpha == 1.0f;
+    s.ws_bytes = c.ws ? c.ws_bytes : 0;
+    const GemmPlan p = gemm_plan(s, gemm_ncu(), gemm_persist_slots(), hooks);
     if (in_dtype == 0) {
 #if OMLM_FP16
         omlm_set_error("omlm_gemm: fp32 operands are served by the bf16 copy of the library");
         return OMLM_ERR_UNSUPPORTED;
 #else
-        static bool attr_done = false;   // 64 KiB dynamic LDS needs the opt-in attribute once per kernel
-        if (!attr_done) {
-            (void)hipFuncSetAttribute((const void*)gemm_kernel<float, false, false, float>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-            (void)hipFuncSetAttribute((const void*)gemm_kernel<float, false, true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-            (void)hipFuncSetAttribute((const void*)gemm_kernel<float, true, true, float>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-            (void)hipFuncSetAttribute((const void*)gemm_kernel<float, true, false, float>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-            attr_done = true;
-        }
         OMLM_CHECK_ARG(out_dtype == 0, "fp32 operands produce fp32 output");
-        return launch_layout<float, float>(g, a_kmajor, b_kmajor, splits, st);
+        const GemmLaunch& l = p.main;
+        const dim3 grid(l.grid_x, l.grid_y), block(l.threads);
+        g.kt_per_split = l.kt_per_split;
+        switch (2 * a_kmajor + b_kmajor) {
+        case 0:  launch_with_lds<gemm_kernel<float, false, false, float>>(grid, block, l.lds, st, g); break;
+        case 1:  launch_with_lds<gemm_kernel<float, false, true, float>>(grid, block, l.lds, st, g); break;
+        case 3:  launch_with_lds<gemm_kernel<float, true, true, float>>(grid, block, l.lds, st, g); break;
+        default: launch_with_lds<gemm_kernel<float, true, false, float>>(grid, block, l.lds, st, g); break;
+        }
+        return omlm_post_launch("omlm_gemm");
 #endif
     }
-    auto launch = [&](const GemmArgs& ga, int tm_, int tn_, int sp) -> int {
-        if (s3_route) {                  // omlm_gemm_planes16: splits == 1 (no accumulate-into-C form), out = fp32 or 16-bit planes
-            if (tm_ == 256 && tn_ == 256)
-                return ga.C_lo ? launch_tile_s3<256, 256, 128, 64, h16pl_t>(ga, st) : launch_tile_s3<256, 256, 128, 64, float>(ga, st);
-            if (tm_ == 256 && tn_ == 128)
-                return ga.C_lo ? launch_tile_s3<256, 128, 64, 64, h16pl_t>(ga, st) : launch_tile_s3<256, 128, 64, 64, float>(ga, st);
-            return ga.C_lo ? launch_tile_s3<128, 128, 64, 64, h16pl_t>(ga, st) : launch_tile_s3<128, 128, 64, 64, float>(ga, st);
-        }
-        if (tm_ == 256 && tn_ == 256)
-            return out_dtype == 0 ? launch_tile<256, 256, 128, 64, float>(ga, a_kmajor, b_kmajor, sp, st)
-                                  : launch_tile<256, 256, 128, 64, h16_t>(ga, a_kmajor, b_kmajor, sp, st);
-        if (tm_ == 256 && tn_ == 128)
-            return out_dtype == 0 ? launch_tile<256, 128, 64, 64, float>(ga, a_kmajor, b_kmajor, sp, st)
-                                  : launch_tile<256, 128, 64, 64, h16_t>(ga, a_kmajor, b_kmajor, sp, st);
-        return out_dtype == 0 ? launch_tile<128, 128, 64, 64, float>(ga, a_kmajor, b_kmajor, sp, st)
-                              : launch_tile<128, 128, 64, 64, h16_t>(ga, a_kmajor, b_kmajor, sp, st);
-    };
-    // Tail peeling for the one-workgroup-per-CU 256x256 tiles: dX-type GEMMs have 560 tiles = 2.19 rounds of 256 CUs, i.e. a
-    // third round that is 19 % full.  The m-tile rows that fill whole rounds keep the 256x256 kernel; the remaining rows go to
-    // the 128x128 kernel (2 workgroups per CU, ~1/3 of the time per tile).
-    if (bm == 256 && bn == 256 && splits == 1 && !a_kmajor && !a_map && !c_map && !(force && force[0]) && tiles > ncu) {
-        const int tiles_n = (N + 255) / 256, tiles_m = (M + 255) / 256;
-        const int rem = tiles % ncu;
-        const int m_full = ((tiles / ncu) * ncu) / tiles_n;
-        if (rem > 0 && rem < ncu / 2 && m_full >= 1 && m_full < tiles_m) {
-            const size_t osz = out_dtype == 0 ? 4 : 2;
-            const long long M1 = (long long)m_full * 256;
-            GemmArgs g1 = g, g2 = g;
-            g1.M = (int)M1;
-            g2.M = M - (int)M1;
-            g2.A = (const char*)A + (size_t)M1 * lda * 2;
-            g2.a_rows = a_rows - M1;
-            g2.C = (char*)C + (size_t)M1 * ldc * osz;
-            if (g.A_lo && !a_kmajor) g2.A_lo = (const char*)g.A_lo + (size_t)M1 * lda * 2;
-            if (g.C_lo) g2.C_lo = (char*)g.C_lo + (size_t)M1 * ldc * osz;
-            if (Cin) g2.Cin = Cin + (size_t)M1 * ldcin;
-            const int rc = launch(g1, 256, 256, 1);
-            if (rc != OMLM_OK) return rc;
-            // the tail: deterministic split-K through the workspace when it pays (see gemm_tail_reduce_kernel)
-            if (tail_ws && gemm_tail_split_on() && alpha == 1.0f) {
-                const int Mt = g2.M, Nw = (N + 3) / 4 * 4;
-                const int tiles_t = ((Mt + 127) / 128) * ((N + 127) / 128);
-                int S = (2 * ncu) / tiles_t;
-                if (S > nk / 8) S = nk / 8;
-                if (S > 8) S = 8;
-                if (S >= 2) {
-                    const int ktps = (nk + S - 1) / S;
-                    S = (nk + ktps - 1) / ktps;
-                    const long long slice = (long long)Mt * Nw;
-                    if (S >= 2 && (long long)S * slice * 4 <= tail_ws_bytes) {
-                        GemmArgs gw = g2;
-                        gw.C = tail_ws; gw.C_lo = nullptr; gw.Cin = nullptr; gw.ldc = Nw; gw.ldcin = 0;
-                        gw.c_split_stride = slice; gw.kt_per_split = ktps;
-                        const int rc2 = s3_route ? launch_tile_s3<128, 128, 64, 64, float>(gw, st, S)
-                                                 : launch_tile<128, 128, 64, 64, float>(gw, a_kmajor, b_kmajor, S, st);
-                        if (rc2 != OMLM_OK) return rc2;
-                        const long long quads = (long long)Mt * (Nw / 4);
-                        const int blocks = (int)((quads + 255) / 256 > 4096 ? 4096 : (quads + 255) / 256);
-                        if (out_dtype == 0)
-                            hipLaunchKernelGGL(gemm_tail_reduce_kernel<0>, dim3(blocks), dim3(256), 0, st, tail_ws, S, slice, Mt, N, Nw, g2.C, nullptr, ldc, g2.Cin, ldcin);
-                        else if (g2.C_lo)
-                            hipLaunchKernelGGL(gemm_tail_reduce_kernel<2>, dim3(blocks), dim3(256), 0, st, tail_ws, S, slice, Mt, N, Nw, g2.C, g2.C_lo, ldc, g2.Cin, ldcin);
-                        else
-                            hipLaunchKernelGGL(gemm_tail_reduce_kernel<1>, dim3(blocks), dim3(256), 0, st, tail_ws, S, slice, Mt, N, Nw, g2.C, nullptr, ldc, g2.Cin, ldcin);
-                        return omlm_post_launch("omlm_gemm (tail reduce)");
-                    }
-                }
-            }
-            return launch(g2, 128, 128, 1);
-        }
-    }
-    return launch(g, bm, bn, splits);
+    if (p.M1 == 0) return launch_planned(g, s, p.main, st);
+    GemmArgs g1, g2;
+    peel_rows(g, p.M1, out_dtype == 0 ? 4 : 2, out_dtype == 0 ? 4 : 2, g1, g2);
+    if (g.A_lo) g2.A_lo = (const char*)g.A_lo + (size_t)p.M1 * lda * 2;       // (the peel is for row-major A only)
+    const int rc = launch_planned(g1, s, p.main, st);
+    if (rc != OMLM_OK) return rc;
+    if (p.tail_slices == 0) return launch_planned(g2, s, p.tail, st);
+    GemmShape w = s;
+    w.out_dtype = 0;
+    const GemmArgs gw = slice_args(g2, c.ws);
+    const int rc2 = launch_planned(gw, w, p.tail, st);
+    if (rc2 != OMLM_OK) return rc2;
+    const dim3 blocks(p.reduce_blocks), th(256);
+    const float* ws = (const float*)c.ws;
+    if (p.reduce_kind == 0)      hipLaunchKernelGGL(gemm_tail_reduce_kernel<0>, blocks, th, 0, st, ws, p.tail_slices, gw.c_split_stride, g2.M, N, gw.ldc, g2.C, nullptr, g.ldc, g2.Cin, g.ldcin);
+    else if (p.reduce_kind == 2) hipLaunchKernelGGL(gemm_tail_reduce_kernel<2>, blocks, th, 0, st, ws, p.tail_slices, gw.c_split_stride, g2.M, N, gw.ldc, g2.C, g2.C_lo, g.ldc, g2.Cin, g.ldcin);
+    else                         hipLaunchKernelGGL(gemm_tail_reduce_kernel<1>, blocks, th, 0, st, ws, p.tail_slices, gw.c_split_stride, g2.M, N, gw.ldc, g2.C, nullptr, g.ldc, g2.Cin, g.ldcin);
+    return omlm_post_launch("omlm_gemm (tail reduce)");
 }
-
 // Workspace of the peeled tail's deterministic split-K: a caller-owned scratch buffer handed to every call that may peel a tail (omlm_gemm,
 // omlm_gemm_planes16, omlm_gemm_planes) -- ONE per stream that launches such GEMMs concurrently; NULL / 0: the one-launch tail.  The library keeps no
 // pointer.  omlm_gemm_tail_workspace_bytes: an upper bound of what an M x N output needs (8 fp32 slices of the at most one-machine-round tail).
+// (its CU query stays its own, uncached and with 256 only where the device query fails: folding it into gemm_ncu() could change its value there)
 #if !OMLM_FP16
 extern "C" long long omlm_gemm_tail_workspace_bytes(int M, int N) {
-    if (M <= 0 || N <= 0) return 0;
     int dev = 0, ncu = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-    const long long tiles_n = (N + 255) / 256, tiles_m = (M + 255) / 256;
-    if (tiles_m * tiles_n <= ncu) return 0;
-    long long tail_rows = ((long long)(ncu / 2) / tiles_n + 1) * 256;        // fewer than half a round of tiles ever go to the tail
-    if (tail_rows > M) tail_rows = M;
-    return 8ll * tail_rows * ((N + 3) / 4 * 4) * 4;
+    return gemm_tail_workspace_bytes(M, N, ncu);
 }
 #endif
+
+#define OMLM_CHECK_TAIL_WS() OMLM_CHECK_ARG((workspace == nullptr) == (workspace_bytes == 0) && workspace_bytes >= 0 && ((uintptr_t)workspace % 16) == 0, \
+                                            "tail workspace: 16-byte aligned buffer and its size, or NULL / 0")
 
 // in_dtype / out_dtype: 0 = fp32, 1 = bf16, 2 = fp16 (include/omlm.h).  fp16 operands (with fp32 or fp16 output) are served by the
 // fp16 copy of this file; bf16 and fp32 operands here.
@@ -996,10 +830,11 @@ extern "C" int OMLM_API(omlm_gemm)(const void* A, const void* B, void* C, const 
                            1, OMLM_H_CODE(out_dtype), alpha, workspace, workspace_bytes, stream);
     }
 #endif
-    OMLM_CHECK_ARG((workspace == nullptr) == (workspace_bytes == 0) && workspace_bytes >= 0 && ((uintptr_t)workspace % 16) == 0,
-                   "tail workspace: 16-byte aligned buffer and its size, or NULL / 0");
-    return gemm_impl(A, B, C, Cin, a_map, b_map, c_map, a_rows, b_rows, M, N, K, lda, ldb, ldc, ldcin, a_kmajor, b_kmajor,
-                     in_dtype, out_dtype, alpha, stream, 0, nullptr, nullptr, nullptr, false, (float*)workspace, workspace_bytes);
+    OMLM_CHECK_TAIL_WS();
+    GemmArgs g = gemm_args();
+    g.A = A; g.B = B; g.C = C; g.Cin = Cin; g.a_map = a_map; g.b_map = b_map; g.c_map = c_map; g.a_rows = a_rows; g.b_rows = b_rows;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin; g.alpha = alpha;
+    return gemm_impl(g, GemmCall{a_kmajor, b_kmajor, in_dtype, out_dtype, false, false, workspace, workspace_bytes, stream});
 }
 
 // q / k projections with the attention's l2-norm + learned scale folded into the epilogue (transformer.py:254-271): C = 16-bit
@@ -1024,33 +859,10 @@ extern "C" int OMLM_API(omlm_gemm_qknorm)(const void* A, const void* B, void* C,
                    "gemm_qknorm: 16-byte aligned operands, pitches multiples of 8");
     OMLM_CHECK_ARG(!C2 || ((c2_col0 % 64) == 0 && (ldc2 % 8) == 0 && ((uintptr_t)C2 % 16) == 0), "gemm_qknorm: second output");
     OMLM_CHECK_ARG((unsigned long long)a_rows * lda * 2 < 0xFFFFFFF0ull && (unsigned long long)b_rows * ldb * 2 < 0xFFFFFFF0ull, "operand exceeds the 4 GiB window");
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
+    GemmArgs g = gemm_args();
     g.A = A; g.B = B; g.C = C; g.a_rows = a_rows; g.b_rows = b_rows; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-    g.alpha = 1.f; g.epi_scale = scale; g.epi_norm = norm_out; g.epi_groups = groups; g.epi_ldnorm = ldnorm; g.C2 = C2; g.c2_col0 = c2_col0; g.ldc2 = ldc2;
-    const int nk = (K + BK - 1) / BK;
-    g.kt_per_split = nk;
-    constexpr size_t LDS = 2 * (size_t)(128 + 128) * BK * 2;
-    const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    auto kfast = gemm_bf16_tile_kernel<128, 128, 64, 64, false, false, h16_t, false, false, true, 1>;
-    auto kgen = gemm_bf16_tile_kernel<128, 128, 64, 64, false, false, h16_t, false, false, false, 1>;
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)kfast, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        (void)hipFuncSetAttribute((const void*)kgen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
-        attr = true;
-    }
-    const int slots = 2 * gemm_persist_slots();                    // persistent walk, two workgroups per CU (see gemm_bf16_tile_persist_kernel)
-    if (slots > 0 && tiles > slots && K % BK == 0) {
-        constexpr size_t LDSP = LDS + 32 * (64 + 4) * 4;
-        auto kp = gemm_bf16_tile_persist_kernel<128, 128, 64, 64, false, false, h16_t, false, 1>;
-        static bool pattr = false;
-        if (!pattr) { (void)hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDSP); pattr = true; }
-        hipLaunchKernelGGL(kp, dim3(slots), dim3(256), LDSP, as_stream(stream), g);
-    }
-    else if (K % BK == 0) hipLaunchKernelGGL(kfast, dim3(tiles, 1), dim3(256), LDS, as_stream(stream), g);
-    else                                        hipLaunchKernelGGL(kgen, dim3(tiles, 1), dim3(256), LDS, as_stream(stream), g);
-    return omlm_post_launch("omlm_gemm_qknorm");
+    g.epi_scale = scale; g.epi_norm = norm_out; g.epi_groups = groups; g.epi_ldnorm = ldnorm; g.C2 = C2; g.c2_col0 = c2_col0; g.ldc2 = ldc2;
+    return gemm_impl(g, GemmCall{0, 0, 1, 1, false, true, nullptr, 0, stream});
 }
 
 // C = A B^T (+ Cin) with BOTH operands as hi/lo planes of the 16-bit type `dtype` (1 = bf16, 2 = fp16): A [M, K] and B [N, K] row-major with
@@ -1071,15 +883,17 @@ extern "C" int OMLM_API(omlm_gemm_planes16)(const void* A, const void* A_lo, con
     if (dtype == OMLM_DT_F16) return omlm_gemm_planes16_h(A, A_lo, B, B_lo, C, C_lo, Cin, a_map, c_map, a_rows, b_rows, M, N, K, lda, ldb, ldc, ldcin, 1,
                                                           workspace, workspace_bytes, stream);
 #endif
-    OMLM_CHECK_ARG((workspace == nullptr) == (workspace_bytes == 0) && workspace_bytes >= 0 && ((uintptr_t)workspace % 16) == 0,
-                   "tail workspace: 16-byte aligned buffer and its size, or NULL / 0");
+    OMLM_CHECK_TAIL_WS();
     OMLM_CHECK_ARG(dtype == 1, "gemm_planes16: operand dtype 1 (bf16) or 2 (fp16)");
     OMLM_CHECK_ARG(A_lo && B_lo, "gemm_planes16: null lo plane");
     OMLM_CHECK_ARG(((uintptr_t)A_lo % 16) == 0 && ((uintptr_t)B_lo % 16) == 0 && ((uintptr_t)C_lo % 16) == 0, "gemm_planes16: 16-byte aligned planes");
     OMLM_CHECK_ARG(!(C_lo && Cin), "gemm_planes16: plane output takes no residual");
     // a_map / c_map (optional): physical row of logical row m in A (both planes) / in C and Cin, as in omlm_gemm -- the logit heads
-    return gemm_impl(A, B, C, Cin, a_map, nullptr, c_map, a_rows, b_rows, M, N, K, lda, ldb, ldc, ldcin, 0, 0,
-                     1, C_lo ? 1 : 0, 1.0f, stream, 1, A_lo, B_lo, C_lo, true, (float*)workspace, workspace_bytes);
+    GemmArgs g = gemm_args();
+    g.A = A; g.B = B; g.C = C; g.Cin = Cin; g.a_map = a_map; g.c_map = c_map; g.a_rows = a_rows; g.b_rows = b_rows;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin;
+    g.split3 = 1; g.A_lo = A_lo; g.B_lo = B_lo; g.C_lo = C_lo;
+    return gemm_impl(g, GemmCall{0, 0, 1, C_lo ? 1 : 0, true, false, workspace, workspace_bytes, stream});
 }
 
 #if !OMLM_FP16
@@ -1091,14 +905,15 @@ extern "C" int omlm_gemm_planes(const void* A, long long a_plane_bytes, const vo
                                 const int* a_map, const int* b_map, const int* c_map, long long a_rows, long long b_rows,
                                 int M, int N, int K, int lda, int ldb, int ldc, int ldcin,
                                 int a_kmajor, int b_kmajor, int out_dtype, float alpha, void* workspace, long long workspace_bytes, void* stream) {
-    OMLM_CHECK_ARG((workspace == nullptr) == (workspace_bytes == 0) && workspace_bytes >= 0 && ((uintptr_t)workspace % 16) == 0,
-                   "tail workspace: 16-byte aligned buffer and its size, or NULL / 0");
+    OMLM_CHECK_TAIL_WS();
     OMLM_CHECK_ARG(a_plane_bytes > 0 && b_plane_bytes > 0 && (a_plane_bytes % 16) == 0 && (b_plane_bytes % 16) == 0, "plane strides");
     OMLM_CHECK_ARG(!(a_kmajor && a_map) && !(b_kmajor && b_map), "k-row maps are not supported on operand planes");
     // each plane has its own buffer descriptor (round 5): the lo planes are addressed by pointer, not by an offset inside A's / B's window
-    return gemm_impl(A, B, C, Cin, a_map, b_map, c_map, a_rows, b_rows, M, N, K, lda, ldb, ldc, ldcin, a_kmajor, b_kmajor,
-                     1, out_dtype, alpha, stream, 1, (const char*)A + a_plane_bytes, (const char*)B + b_plane_bytes, nullptr, false,
-                     (float*)workspace, workspace_bytes);
+    GemmArgs g = gemm_args();
+    g.A = A; g.B = B; g.C = C; g.Cin = Cin; g.a_map = a_map; g.b_map = b_map; g.c_map = c_map; g.a_rows = a_rows; g.b_rows = b_rows;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin; g.alpha = alpha;
+    g.split3 = 1; g.A_lo = (const char*)A + a_plane_bytes; g.B_lo = (const char*)B + b_plane_bytes;
+    return gemm_impl(g, GemmCall{a_kmajor, b_kmajor, 1, out_dtype, false, false, workspace, workspace_bytes, stream});
 }
 
 // x [n] fp32 -> planes: hi[i] = x truncated to bf16 at planes[i], lo[i] = RNE(x - hi) at planes[plane_elems + i]  (x ~= hi + lo to 2^-17)
@@ -1151,67 +966,35 @@ extern "C" int OMLM_API(omlm_gemm_wgrad_group)(const omlm_gemm_wgrad_desc* d, in
     if (dtype == OMLM_DT_F16) return omlm_gemm_wgrad_group_h(d, count, splits, 1, stream);
 #endif
     OMLM_CHECK_ARG(dtype == 1, "wgrad group: operand dtype must be 1 (bf16) or 2 (fp16)");
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ncu = n;
-        else ncu = 256;
-    }
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)gemm_wgrad_group_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        (void)hipFuncSetAttribute((const void*)gemm_wgrad_group_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        (void)hipFuncSetAttribute((const void*)gemm_wgrad_group_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072);
-        attr = true;
-    }
+    const GemmHooks hooks = gemm_hooks_from_env();
     for (int base = 0; base < count; base += OMLM_GROUP_MAX) {
         const int n = count - base < OMLM_GROUP_MAX ? count - base : OMLM_GROUP_MAX;
-        long long units = 0;
-        int nk_min = 1 << 30;
-        bool fastk = true;                                    // every problem's K a multiple of the k-tile depth: SGPR-offset DMA form
+        WgradDims dims[OMLM_GROUP_MAX];
         for (int i = 0; i < n; ++i) {
             const omlm_gemm_wgrad_desc& q = d[base + i];
-            if (q.K % BK != 0) fastk = false;
             OMLM_CHECK_ARG(q.A && q.B && q.C && q.M > 0 && q.N > 0 && q.K > 0, "wgrad group: bad problem");
             OMLM_CHECK_ARG((q.lda % 8) == 0 && (q.ldb % 8) == 0 && q.lda >= ((q.M + 7) / 8) * 8 && q.ldb >= ((q.N + 7) / 8) * 8,
                            "wgrad group: k-major operand pitches must be multiples of 8 covering the padded extent");
             OMLM_CHECK_ARG(((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.B % 16) == 0, "wgrad group: operands must be 16-byte aligned");
             OMLM_CHECK_ARG((unsigned long long)q.K * q.lda * 2 < 0xFFFFFFF0ull && (unsigned long long)q.K * q.ldb * 2 < 0xFFFFFFF0ull,
                            "wgrad group: operand exceeds the 4 GiB buffer-descriptor window");
-            units += (long long)((q.M + 255) / 256) * ((q.N + 255) / 256);
-            const int nk = (q.K + BK - 1) / BK;
-            if (nk < nk_min) nk_min = nk;
+            dims[i] = WgradDims{q.M, q.N, q.K};
         }
-        int sp = splits;
-        if (sp <= 0) {
-            // a unit = one full-K tile; s splits cut it into s workgroups of 1/s the work and add s atomic passes over C
-            float best = -1.f;
-            sp = 1;
-            for (int s = 1; s <= 4; ++s) {
-                const long long wgs = units * s, rounds = (wgs + ncu - 1) / ncu;
-                const float util = (float)wgs / (float)(rounds * ncu) - 0.02f * (float)(s - 1);
-                if (util > best) { best = util; sp = s; }
-            }
-        }
-        if (sp > nk_min / 8) sp = nk_min / 8 > 0 ? nk_min / 8 : 1;
+        int ktps[OMLM_GROUP_MAX], start[OMLM_GROUP_MAX];
+        const WgradPlan p = wgrad_group_plan(dims, n, splits, gemm_ncu(), hooks, ktps, start);
         GroupArgs ga;
         memset(&ga, 0, sizeof(ga));
-        ga.n = n;
-        int start = 0;
+        ga.n = n; ga.total = p.total;
         for (int i = 0; i < n; ++i) {
             const omlm_gemm_wgrad_desc& q = d[base + i];
-            GroupProb& p = ga.p[i];
-            p.A = q.A; p.B = q.B; p.C = q.C; p.c_map = q.c_map; p.M = q.M; p.N = q.N; p.K = q.K; p.lda = q.lda; p.ldb = q.ldb; p.ldc = q.ldc;
-            const int nk = (q.K + BK - 1) / BK;
-            p.kt_per_split = (nk + sp - 1) / sp;
-            const int s_eff = (nk + p.kt_per_split - 1) / p.kt_per_split;
-            p.start = start;
-            start += ((q.M + 255) / 256) * ((q.N + 255) / 256) * s_eff;
+            GroupProb& gp = ga.p[i];
+            gp.A = q.A; gp.B = q.B; gp.C = q.C; gp.c_map = q.c_map; gp.M = q.M; gp.N = q.N; gp.K = q.K; gp.lda = q.lda; gp.ldb = q.ldb; gp.ldc = q.ldc;
+            gp.kt_per_split = ktps[i]; gp.start = start[i];
         }
-        ga.total = start;
-        if (fastk && gemm_t8_mode() > 0) hipLaunchKernelGGL((gemm_wgrad_group_kernel<true, true>), dim3(start), dim3(512), 131072, as_stream(stream), ga);
-        else if (fastk) hipLaunchKernelGGL(gemm_wgrad_group_kernel<true>, dim3(start), dim3(512), 131072, as_stream(stream), ga);
-        else       hipLaunchKernelGGL(gemm_wgrad_group_kernel<false>, dim3(start), dim3(512), 131072, as_stream(stream), ga);
+        const dim3 grid(p.total), block(512);
+        if (p.form == FORM_RING)           launch_with_lds<gemm_wgrad_group_kernel<true, true>>(grid, block, 131072, as_stream(stream), ga);
+        else if (p.form == FORM_ROT_FASTK) launch_with_lds<gemm_wgrad_group_kernel<true>>(grid, block, 131072, as_stream(stream), ga);
+        else                               launch_with_lds<gemm_wgrad_group_kernel<false>>(grid, block, 131072, as_stream(stream), ga);
     }
     return omlm_post_launch("omlm_gemm_wgrad_group");
 }

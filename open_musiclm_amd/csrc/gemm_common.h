@@ -7,7 +7,6 @@
 
 namespace OMLM_NS {
 
-#define OMLM_GEMM_T8_DEFAULT 2     // round 5: gemm_tile8_body for the 256 x 256 tiles (see gemm_t8_mode): 2 = where it measured faster
 #define OMLM_SUPER_ROWS 1024       /* C rows per super-tile (tile rows walked column-major inside it) */
 #define BM 128
 #define BN 128

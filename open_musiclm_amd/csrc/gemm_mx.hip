@@ -23,6 +23,7 @@
 // The m-tile rows behind the last full machine round run as a slice-storing split-K of the same kernel (GemmArgs::c_split_stride) through a
 // caller-owned workspace, summed in a fixed order by gemm_tail_reduce_kernel: deterministic, no atomics.
 #include "gemm_common.h"
+#include "gemm_plan.h"
 
 #if OMLM_FP16
 namespace OMLM_NS {
@@ -276,61 +277,25 @@ __global__ __launch_bounds__(512) void gemm_mx_fused_kernel(GemmMxPair pr) {
     gemm_mx_body<TOUT, false, true>(g, tm * 256, tn * 256, kt0, kt1, tail, ksplit, smem, tail);
 }
 template <typename TOUT>
-static int launch_mx_fused(const GemmMxArgs& g, const GemmMxArgs& t, int S, hipStream_t st) {
+static int launch_mx_fused(const GemmMxArgs& g, const GemmMxArgs& t, const omlm_plan::MxPlan& p, hipStream_t st) {
     constexpr size_t LDS = 2 * (size_t)(256 + 256) * BK * 2;
     GemmMxPair pr;
     pr.g = g; pr.t = t;
-    pr.main_tiles = ((g.M + 255) / 256) * ((g.N + 255) / 256);
-    pr.tail_tiles = ((t.M + 255) / 256) * ((t.N + 255) / 256);
-    auto k = gemm_mx_fused_kernel<TOUT>;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); attr = true; }
-    hipLaunchKernelGGL(k, dim3(pr.main_tiles + pr.tail_tiles * S), dim3(512), LDS, st, pr);
+    pr.main_tiles = p.main_tiles;
+    pr.tail_tiles = p.tail_tiles;
+    launch_with_lds<gemm_mx_fused_kernel<TOUT>>(dim3(p.main_tiles + p.tail_tiles * p.S), dim3(512), LDS, st, pr);
     return omlm_post_launch("omlm_gemm_mx16 (full rounds + tail slices)");
 }
-static bool mx_fuse_tail() { const char* e = getenv("OMLM_MX_FUSE_TAIL"); return !(e && e[0] == '0'); }      // (read per call: the kernel test toggles it)
 
-static int mx_ncu() {
-    static int ncu = 0;
-    if (ncu == 0) {
-        int dev = 0, n = 0;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    }
-    return ncu;
-}
-
-// how the launch is cut: rows [0, M1) as whole machine rounds of 256 x 256 tiles, rows [M1, M) as S k-slices through the workspace
-static void mx_plan(int M, int N, int K, long long ws_bytes, long long& M1, int& S, int& ktps) {
-    const int ncu = mx_ncu();
-    const int tiles_n = (N + 255) / 256, tiles_m = (M + 255) / 256, tiles = tiles_m * tiles_n;
-    const int nk_all = ((K / BK + 1) & ~1) + 2 * ((K + 127) / 128);
-    M1 = M; S = 1; ktps = nk_all;
-    if (tiles <= ncu) return;
-    const int rem = tiles % ncu;
-    const int m_full = ((tiles / ncu) * ncu) / tiles_n;
-    if (rem == 0 || m_full < 1 || m_full >= tiles_m) return;
-    const int Mt = M - m_full * 256, Nw = (N + 3) / 4 * 4;
-    const int tiles_t = ((Mt + 255) / 256) * tiles_n;
-    int s = ncu / tiles_t;
-    if (s > nk_all / 8) s = nk_all / 8;
-    if (s > 8) s = 8;
-    if (s < 2) return;
-    const int per = ((nk_all + s - 1) / s + 1) & ~1;           // slices start at even loop tiles (gemm_mx_body's two loops)
-    s = (nk_all + per - 1) / per;
-    if (s < 2 || (long long)s * Mt * Nw * 4 > ws_bytes) return;
-    M1 = (long long)m_full * 256; S = s; ktps = per;
-}
+int gemm_ncu();                    // gemm.hip: the CU count, queried once
 
 }   // namespace OMLM_NS
 
 using namespace OMLM_NS;
+using namespace omlm_plan;         // csrc/gemm_plan.h: mx_plan decides how the launch is cut
 
 // Workspace the tail of an M x N x K launch wants (0: none); see omlm_gemm_mx16.
-extern "C" long long omlm_gemm_mx16_workspace_bytes(int M, int N, int K) {
-    long long M1; int S, ktps;
-    mx_plan(M, N, K, (long long)1 << 62, M1, S, ktps);
-    return S >= 2 ? (long long)S * (M - M1) * ((N + 3) / 4 * 4) * 4 : 0;
-}
+extern "C" long long omlm_gemm_mx16_workspace_bytes(int M, int N, int K) { return mx16_workspace_bytes(M, N, K, gemm_ncu()); }
 
 // C = A B^T (+ Cin) for IEEE-half operands given as planes (include/omlm.h).  A8 / B8: the operand's fp8 planes [hi8 | lo8] at the half plane's row
 // pitch, the lo8 plane a8_stride / b8_stride bytes behind the hi8 plane, rows padded to a multiple of 256 (every byte of both planes readable;
@@ -361,46 +326,33 @@ extern "C" int omlm_gemm_mx16(const void* A, const void* A8, long long a8_stride
     OMLM_CHECK_ARG(!g.c_lo8 || (ldc % 8 == 0 && ((uintptr_t)C_lo % 8) == 0), "bf8 lo plane: 8-byte aligned, pitch a multiple of 8");
     g.a_rows = a_rows; g.b_rows = b_rows; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin; g.alpha = 1.0f;
     g.A8 = A8; g.B8 = B8; g.a8_stride = (unsigned)a8_stride; g.b8_stride = (unsigned)b8_stride; g.a_scale = a_scale; g.b_scale = b_scale;
-    const int nk_all = ((K / BK + 1) & ~1) + 2 * ((K + 127) / 128);
-    g.kt_per_split = nk_all;
     hipStream_t st = as_stream(stream);
-    long long M1; int S, ktps;
-    mx_plan(M, N, K, workspace ? workspace_bytes : 0, M1, S, ktps);
+    const MxPlan p = mx_plan(M, N, K, workspace ? workspace_bytes : 0, gemm_ncu(), gemm_hooks_from_env());
+    g.kt_per_split = p.nk_all;
     auto run = [&](const GemmMxArgs& ga) { return ga.C_lo ? launch_mx<h16pl_t, false>(ga, 1, st) : launch_mx<float, false>(ga, 1, st); };
-    if (S < 2) return run(g);
-    GemmMxArgs g1 = g, g2 = g;
+    if (p.S < 2) return run(g);
+    GemmMxArgs g1, g2;
     const size_t osz = C_lo ? 2 : 4;
-    g1.M = (int)M1;
-    g2.M = M - (int)M1;
-    g2.A = (const char*)A + (size_t)M1 * lda * 2; g2.A8 = (const char*)A8 + (size_t)M1 * lda * 2;          // (both fp8 planes move: the stride stays)
-    g2.a_scale = a_scale + M1;
-    g2.a_rows = a_rows - M1;
-    g2.C = (char*)C + (size_t)M1 * ldc * osz;
-    if (C_lo) g2.C_lo = (char*)C_lo + (size_t)M1 * ldc * (g.c_lo8 ? 1 : osz);
-    if (Cin) g2.Cin = Cin + (size_t)M1 * ldcin;
-    const int Mt = g2.M, Nw = (N + 3) / 4 * 4;
-    const long long slice = (long long)Mt * Nw;
-    GemmMxArgs gw = g2;
-    gw.C = workspace; gw.C_lo = nullptr; gw.Cin = nullptr; gw.ldc = Nw; gw.ldcin = 0; gw.c_split_stride = slice; gw.kt_per_split = ktps;
+    peel_rows(g, p.M1, osz, g.c_lo8 ? 1 : osz, g1, g2);
+    g2.A8 = (const char*)A8 + (size_t)p.M1 * lda * 2;          // (both fp8 planes move: the stride stays)
+    g2.a_scale = a_scale + p.M1;
+    GemmMxArgs gw = slice_args(g2, workspace);
+    gw.kt_per_split = p.ktps;
     int rc;
-    // one grid where the last round of the full tiles leaves CUs idle (FF-in at B = 32: 3058 tiles = 11.95 rounds; the tail's 88 slices start on the
-    // 14 idle CUs and finish ~20 us behind the round instead of 41 us as their own launch: 804 -> 781 us).  A main part of WHOLE rounds (FF-out:
-    // 512 tiles) gains nothing from it (381 -> 392 us measured): two launches.  OMLM_MX_FUSE_TAIL=0: always two launches.
-    const int main_tiles = (int)(M1 / 256) * ((N + 255) / 256);
-    if (mx_fuse_tail() && main_tiles % mx_ncu() != 0) {
-        rc = C_lo ? launch_mx_fused<h16pl_t>(g1, gw, S, st) : launch_mx_fused<float>(g1, gw, S, st);
+    if (p.fused) {
+        rc = C_lo ? launch_mx_fused<h16pl_t>(g1, gw, p, st) : launch_mx_fused<float>(g1, gw, p, st);
         if (rc != OMLM_OK) return rc;
     } else {
         rc = run(g1);
         if (rc != OMLM_OK) return rc;
-        rc = launch_mx<float, true>(gw, S, st);
+        rc = launch_mx<float, true>(gw, p.S, st);
         if (rc != OMLM_OK) return rc;
     }
-    const long long quads = (long long)Mt * (Nw / 4);
-    const int blocks = (int)((quads + 255) / 256 > 4096 ? 4096 : (quads + 255) / 256);
-    if (C_lo && g.c_lo8) hipLaunchKernelGGL(gemm_tail_reduce_kernel<3>, dim3(blocks), dim3(256), 0, st, (const float*)workspace, S, slice, Mt, N, Nw, g2.C, g2.C_lo, ldc, (const float*)nullptr, 0);
-    else if (C_lo) hipLaunchKernelGGL(gemm_tail_reduce_kernel<2>, dim3(blocks), dim3(256), 0, st, (const float*)workspace, S, slice, Mt, N, Nw, g2.C, g2.C_lo, ldc, (const float*)nullptr, 0);
-    else      hipLaunchKernelGGL(gemm_tail_reduce_kernel<0>, dim3(blocks), dim3(256), 0, st, (const float*)workspace, S, slice, Mt, N, Nw, g2.C, (void*)nullptr, ldc, g2.Cin, ldcin);
+    const dim3 blocks(p.reduce_blocks), th(256);
+    const float* ws = (const float*)workspace;
+    if (C_lo && g.c_lo8) hipLaunchKernelGGL(gemm_tail_reduce_kernel<3>, blocks, th, 0, st, ws, p.S, gw.c_split_stride, g2.M, N, gw.ldc, g2.C, g2.C_lo, ldc, (const float*)nullptr, 0);
+    else if (C_lo) hipLaunchKernelGGL(gemm_tail_reduce_kernel<2>, blocks, th, 0, st, ws, p.S, gw.c_split_stride, g2.M, N, gw.ldc, g2.C, g2.C_lo, ldc, (const float*)nullptr, 0);
+    else      hipLaunchKernelGGL(gemm_tail_reduce_kernel<0>, blocks, th, 0, st, ws, p.S, gw.c_split_stride, g2.M, N, gw.ldc, g2.C, (void*)nullptr, ldc, g2.Cin, ldcin);
     return omlm_post_launch("omlm_gemm_mx16 (tail reduce)");
 }
 #endif
