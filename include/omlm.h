@@ -112,10 +112,16 @@ int omlm_qk_norm_bwd2(const float* dq, const float* dk, const float* dv, const v
  * not read.  P < 0 or p outside [0, 1) is refused before any launch.
  * bwd: dq [B*N, H*64], dk, dv [B*N, 64] fp32 overwritten; dbias (bias's layout) accumulated (+=) over all its rows; delta scratch [B, H, N].
  *
- * Routes: 16-bit operands with biasT (or without any bias) run the second-generation kernels -- the forward up to N = 4096, a prefix while
+ * Routes: 16-bit operands with biasT (or without any bias) run the second-generation kernels -- causal up to N = 16384
+ * (omlm_attn_max_positions; 4096 < N runs their long forms: the forward's liveness prologue as a loop, the dQ kernel with a byte per key and a
+ * sliding window of d(bias) bins in LDS, the dK / dV kernel summing per-workgroup slots of the workspace in a fixed order), a prefix while
  * their plans fit (N >= 32, N <= 4096 and the dQ kernel's LDS, which holds 8 (ceil32(N) + Pn - 1) d(bias) bins: about N + Pn <= 4000).
- * Otherwise, and for fp32 operands, the first-generation kernels read `bias`; their bf16x3 dQ kernel caps ceil32(N) + Pn - 1 at about 3800
- * (an error beyond).  The forward and the backward decide alike, so a backward is always handed the lse its forward wrote.
+ * Otherwise, and for fp32 operands, the first-generation kernels read `bias`; they keep the table in LDS, which caps ceil32(N) + Pn - 1 at
+ * about 3800 for the bf16x3 dQ kernel and about 4330 for the 16-bit one.  The forward and the backward decide alike, so a backward is always
+ * handed the lse its forward wrote.
+ * Limits: N past what the route takes is refused (OMLM_ERR_UNSUPPORTED) before any launch, and the message says which case it is -- causal
+ * 16-bit operands past omlm_attn_max_positions(dtype, 0); fp32 operands past their LDS limit; a non-causal prefix, or a raw table without
+ * biasT, past N = 4096 where the first-generation kernels no longer fit.
  *
  * Dropout (transformer.py:198,211: nn.Dropout(attn_dropout) on the softmax probabilities before P V), for the prefix's extra scores as for the
  * others: out = (P o Z / (1 - p)) V with Z the keep-mask below; lse stays that of the undropped P (bit-identical to p = 0), and the backward
@@ -152,9 +158,18 @@ int omlm_attn_bias_prepare(const float* bias, float* biasT, int N, int H, int bi
 int omlm_attn_bias_prepare_group(const float* bias, float* const* biasT, int layers, int N, int H, int bias_ld,
                                  const float* const* q_scale, const float* const* k_scale, float qk_bound, float scale,
                                  int p_max_log2, int P, void* stream);
+/* Most positions per sample omlm_mqa_attn_fwd followed by omlm_mqa_attn_bwd take for operands of `dtype` and a prefix of P rows: 16384 for
+ * bf16 / fp16 causal (P = 0); for fp32 operands, and for 16-bit operands with P > 0, what the first-generation kernels' LDS-resident tables
+ * allow (about 3800 and 4330; with P > 0 never less than the 4096 the second-generation kernels serve while their plan fits).  0 for an
+ * unknown dtype or P < 0.  A forward alone reaches further with fp32 operands (its table is half the dQ kernel's). */
+int omlm_attn_max_positions(int dtype, int P);
 /* dbias_ws (optional, omlm_mqa_attn_bwd_workspace_bytes(B, N, H) bytes, contents irrelevant on entry and exit): the dQ kernel leaves
  * each wave's d(bias) bins there with plain stores and a small reduction adds them into dbias; without it every wave adds its bins into
- * dbias with device-scope atomics (measured 290 us per layer slower at B = 8, N = 1817, H = 16). */
+ * dbias with device-scope atomics (measured 290 us per layer slower at B = 8, N = 1817, H = 16).
+ * N <= 4096: B H ceil(N / 32)^2 128 bytes.  N > 4096 (16-bit operands): the same rows, then 64 KiB per workgroup of the dK / dV kernel
+ * (a few hundred MB at B N = 32768), where each workgroup leaves its dK / dV sums for a reduction in a fixed order: with the workspace dq,
+ * dk, dv and (at B = 1) dbias are the same bits from run to run; without it dK / dV are added with fp32 atomics in order of arrival, as they
+ * are at N <= 4096 in either form.  Size the buffer with this function, not with the formula. */
 long long omlm_mqa_attn_bwd_workspace_bytes(int B, int N, int H);
 int omlm_mqa_attn_bwd(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
                       const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv, float* dbias,

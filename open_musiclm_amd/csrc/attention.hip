@@ -995,6 +995,61 @@ int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* b
 
 bool attn2_prefix_fits(int N, int Pn);      // attention2.hip: whether the second-generation kernels serve a prefix of Pn rows at N
 
+// ---- how many positions per sample the kernels take ------------------------------------------------------------------------------------
+// 16-bit operands, causal, with the prepared table or no bias: OMLM_ATTN_NL (4096 < N runs the long forms of attention2.hip / attention3.hip).
+// Everything else past N = 4096 -- fp32 operands ("bf16x3") at any N, a non-causal prefix, a raw table without its prepared form -- runs the
+// first-generation kernels, which keep the bias table in LDS: the largest N that fits the forward / the dQ kernel (the dK / dV kernel stages
+// H columns where it has no prepared table to read by windows: H (ceil32(N) + 31) floats + 33 KiB, checked per call).
+static int attn1_limit(bool precise, bool backward, int P) {
+    int n = 32;
+    for (int N = 32; N <= 4 * OMLM_ATTN_NL; N += 32) {
+        const int off = P > 0 ? (P < N ? P : N) - 1 : 0;
+        if ((backward ? dq_lds(N, precise, off) : fwd_lds(N, precise, off)) > 160 * 1024) break;
+        n = N;
+    }
+    return n;
+}
+#if !OMLM_FP16
+// include/omlm.h
+extern "C" int omlm_attn_max_positions(int dtype, int P) {
+    if (P < 0) return 0;
+    if (dtype == OMLM_DT_F32) return attn1_limit(true, true, P);
+    if (dtype != OMLM_DT_BF16 && dtype != OMLM_DT_F16) return 0;
+    if (P == 0) return OMLM_ATTN_NL;
+    const int l1 = attn1_limit(false, true, P);
+    return l1 > 4096 ? l1 : 4096;
+}
+#endif
+// Refusals that name their reason, before anything is launched.  dtype: as this copy sees it (1: its 16-bit type).
+static int attn_positions_check(const char* what, int dtype, int N, int P, int H, bool raw_table_only, bool backward) {
+    char buf[400];
+    const char* dir = backward ? "backward" : "forward alone";
+    if (dtype == 0) {
+        const int lim = attn1_limit(true, backward, P);
+        if (N <= lim) return OMLM_OK;
+        snprintf(buf, sizeof(buf), "%s: N = %d positions per sample with fp32 operands (bf16x3): their kernels keep the bias table in LDS and take "
+                 "N <= %d (%s; omlm_attn_max_positions); bf16 / fp16 operands take N <= %d", what, N, lim, dir, OMLM_ATTN_NL);
+    } else {
+        if (N <= 4096) return OMLM_OK;
+        if (P > 0 || raw_table_only) {                         // first-generation kernels, as far as they reach
+            const int lim = attn1_limit(false, backward, P);
+            const bool staged = !backward || 32 * 1024 + (size_t)H * ((N + TQ - 1) / TQ * TQ + (P > 0 ? 31 : 0)) * sizeof(float) + 1024 <= 160 * 1024;
+            if (N <= lim && staged) return OMLM_OK;
+            if (P > 0)
+                snprintf(buf, sizeof(buf), "%s: N = %d positions per sample with a non-causal prefix (P = %d): past N = 4096 a prefix runs the "
+                         "first-generation kernels, whose LDS-resident bias tables take N <= %d (%s) and, in the backward, H (N + 31) <= 31000 "
+                         "(H = %d); the long forms (4096 < N <= %d) are causal", what, N, P, lim, dir, H, OMLM_ATTN_NL);
+            else
+                snprintf(buf, sizeof(buf), "%s: N = %d > 4096 positions per sample needs the prepared table (biasT, omlm_attn_bias_prepare) next "
+                         "to bias; with the raw table alone N <= %d (%s) and, in the backward, H N <= 31000 (H = %d)", what, N, lim, dir, H);
+        } else if (N > OMLM_ATTN_NL)
+            snprintf(buf, sizeof(buf), "%s: N = %d positions per sample is past the limit of %d (omlm_attn_max_positions)", what, N, OMLM_ATTN_NL);
+        else return OMLM_OK;
+    }
+    omlm_set_error(buf);
+    return OMLM_ERR_UNSUPPORTED;
+}
+
 // Pn = min(P, N): 0 is causal, >= 1 the non-causal prefix of include/omlm.h.  bias: the rel = 0 row of the [N + Pn - 1, bias_ld] table (or
 // null).  drop: null for p == 0.
 static int attn_fwd_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
@@ -1049,6 +1104,7 @@ extern "C" int OMLM_API(omlm_mqa_attn_fwd)(const void* q, const void* k, const v
     OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
     OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
     const int Pn = P < N ? P : N;
+    if (int rc = attn_positions_check("omlm_mqa_attn_fwd", dtype, N, P, H, bias && !biasT, false)) return rc;
     return attn_fwd_impl(q, k, v, bias && Pn > 0 ? bias + (size_t)(Pn - 1) * bias_ld : bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld,
                          dtype, Pn, stream, p > 0.f ? &d : nullptr);
 }
@@ -1061,7 +1117,8 @@ extern "C" __attribute__((visibility("hidden"))) int omlm_attn_dbias_reduce_laun
 
 int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                          const void* dout, const float* lse, const float* delta, float* dk, float* dv,
-                         int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn);      // attention3.hip
+                         int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn, float* part);      // attention3.hip
+long long attn3_part_floats(int B, int N);                                                                       // attention3.hip
 
 // Pn, bias, drop as in attn_fwd_impl; dbias: the rel = 0 row of its table.  d(bias) of rel >= 0 goes through the workspace and its
 // reduction, that of rel < 0 (Pn > 1) by atomics from the dQ kernel.
@@ -1112,7 +1169,19 @@ static int attn_bwd_impl(const void* q, const void* k, const void* v, const floa
         // its first-generation kernel where its plan does not fit (launcher result 1).  A prefix runs them iff attn2_prefix_fits -- the
         // forward's test, whose lse is relative to the table's reference point there -- so a "does not fit" is an error, not a fallback.
         const bool gen2 = (biasT || !bias) && (Pn == 0 || attn2_prefix_fits(N, Pn));
-        if ((Pn == 0 || !gen2) && (rc = set_lds(kk, ldsk))) return rc;
+        // N > 4096, causal, with the prepared table or no bias: the long dQ kernel, and with a workspace the dK / dV kernel's slot form -- its slots
+        // follow the d(bias) rows in the workspace (omlm_mqa_attn_bwd_workspace_bytes).  Where the dK / dV kernel's 32-bit offsets refuse the
+        // shape, the first-generation kernel takes over in its windowed mode, which needs the prepared table: refused HERE, before dQ runs.
+        const bool lng = N > 4096 && gen2 && Pn == 0;
+        const long long nqt_ = (N + 31) / 32;
+        float* dkv_part = lng && dbias_ws ? dbias_ws + (size_t)B * H * nqt_ * nqt_ * 32 : nullptr;
+        if (lng && !win && (long long)B * N * H * 128 >= (1ll << 32)) {
+            omlm_set_error("omlm_mqa_attn_bwd: B N H >= 2^25 with N > 4096 and no prepared table (biasT) is not served: the dK / dV kernel addresses q "
+                           "and dout with 32-bit byte offsets (B N H 128 < 2^32), and the windowed first-generation kernel behind it reads biasT -- "
+                           "pass the prepared table (an all-zero one, omlm_attn_bias_prepare with bias = NULL, where there is no bias) or split the batch");
+            return OMLM_ERR_UNSUPPORTED;
+        }
+        if (!(lng && !win) && (Pn == 0 || !gen2) && (rc = set_lds(kk, ldsk))) return rc;
         int r = gen2 ? attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, drop, Pn) : 1;
         if (r < 0 || (r > 0 && gen2 && Pn > 0)) return r < 0 ? r : OMLM_ERR_UNSUPPORTED;
         if (r > 0) {
@@ -1120,7 +1189,7 @@ static int attn_bwd_impl(const void* q, const void* k, const void* v, const floa
             hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
         }
         if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
-        r = gen2 ? attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, drop, Pn) : 1;
+        r = gen2 ? attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, drop, Pn, dkv_part) : 1;
         if (r < 0 || (r > 0 && gen2 && Pn > 0)) return r < 0 ? r : OMLM_ERR_UNSUPPORTED;
         if (r > 0)
             hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr, Pn);
@@ -1151,6 +1220,7 @@ extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const v
     OMLM_CHECK_ARG(H >= 1 && ((!bias && !dbias) || bias_ld >= H), "heads / bias pitch");
     const int Pn = P < N ? P : N;
     const size_t r0 = Pn > 0 ? (size_t)(Pn - 1) * bias_ld : 0;
+    if (int rc = attn_positions_check("omlm_mqa_attn_bwd", dtype, N, P, H, bias && !biasT, true)) return rc;
     return attn_bwd_impl(q, k, v, bias ? bias + r0 : nullptr, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias ? dbias + r0 : nullptr,
                          dbias_ws, B, N, H, scale, bias_ld, dtype, Pn, stream, p > 0.f ? &d : nullptr);
 }

@@ -25,6 +25,7 @@ namespace OMLM_NS {
 #define A2_LOG2E 1.4426950408889634f
 #define A2_STAGE (8192 + 8192 + 8 * A2_BWIN * 4)     /* K rows | V blocked | bias window = 20 KiB */
 #define A2_NST 3
+#define A2_NL OMLM_ATTN_NL    /* most positions per sample of the long forms (4096 < N <= A2_NL: attn4_fwd_long_kernel, attn2_bwd_dq_long_kernel) */
 
 #define MFMA16(a, b, c) OMLM_MFMA_32x32x16(a, b, c)
 
@@ -370,171 +371,16 @@ struct A4Stager {
 //   other (QSEL), re-reading the K / V fragments per head.
 // PFX: the non-causal prefix of Pn = min(P, N) rows; the table (omlm_attn_bias_prepare_group with P >= 1) holds Pn - 1 negative distances in
 // front of the causal layout, so every window offset moves by off = Pn - 1.
-template <bool FIXED, bool DROP = false, bool PFX = false>
-__global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__ k,
-                                                                  const h16_t* __restrict__ v, const float* __restrict__ biasT, int ldT,
-                                                                  const unsigned char* __restrict__ keymask, h16_t* __restrict__ out,
-                                                                  float* __restrict__ lse, int B, int N, int H, float scale, const AttnDrop drop,
-                                                                  int Pn) {
-    // the flag of head 0: omlm_attn_bias_prepare decides once for all heads
-    if ((biasT && __builtin_amdgcn_readfirstlane(__float_as_int(biasT[ldT - 2])) != 0) != FIXED) return;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* ring = smem;                                        // A2_NST stages
-    h16_t* livef = (h16_t*)(smem + A2_NST * A2_STAGE);      // [nkt_all * 64] 1.0 / 0.0 per key of this sample
-    const int nqt = (N + 31) / 32, ny = (H + 7) / 8;
-    int b, qt, hy;
-    a2_item_order(blockIdx.x, nqt, ny, B, b, qt, hy);
-    const int lane = threadIdx.x & 63, hi = lane >> 5, ql = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h0 = hy * 8 + 2 * wave;                        // heads h0, h0 + 1
-    const int i0 = qt * 32;
-    const size_t rowbase = (size_t)b * N;
-    const int off = PFX ? Pn - 1 : 0;
-    const int kend = PFX && i0 < Pn ? max(i0 + 32, Pn) : i0 + 32;
-    const int nkt = min((kend + A2_TKV - 1) / A2_TKV, (N + A2_TKV - 1) / A2_TKV);   // key tiles this query tile needs
-
-    // ---- prologue: liveness of this sample's keys, as a 1/0 array of the operand type (denominator operand) and one ballot word per key
-    // tile (V rows of masked keys are DMA'd as zeros).  All byte loads are issued before the first wait.
-    unsigned long long* livebits = (unsigned long long*)(livef + (size_t)((N + 63) / 64) * 64);     // [64 tiles]
-    unsigned* zeros = (unsigned*)(livebits + 64);                                                 // 128 B of zeros (see a4_tile)
-    {
-        unsigned char mk[16];
-#pragma unroll
-        for (int it = 0; it < 16; ++it) mk[it] = 1;
-        if (keymask) {
-#pragma unroll
-            for (int it = 0; it < 16; ++it)
-                if (it * A4_THREADS < nkt * A2_TKV) mk[it] = keymask[rowbase + min(it * A4_THREADS + (int)threadIdx.x, N - 1)];   // uniform condition, clamped index
-        }
-#pragma unroll
-        for (int it = 0; it < 16; ++it) {
-            const int j = it * A4_THREADS + threadIdx.x;
-            if (it * A4_THREADS < nkt * A2_TKV) {               // uniform
-                const bool lv = j < N && mk[it] != 0;
-                const unsigned long long w = __ballot(lv);
-                if (j < nkt * A2_TKV) livef[j] = lv ? (h16_t)1.0f : (h16_t)0.0f;
-                if (lane == 0 && it * 4 + wave < nkt) livebits[it * 4 + wave] = w;
-            }
-        }
-        if (threadIdx.x < 32) zeros[threadIdx.x] = 0u;
-    }
-    __syncthreads();                                          // livef / livebits visible; no LDS-DMA in flight yet
-    const a2_rsrc rsK = a2_make_rsrc(k + rowbase * 64, (unsigned)N * 128u);
-    const a2_rsrc rsV = a2_make_rsrc(v + rowbase * 64, (unsigned)N * 128u);
-    const a2_rsrc rsB = a2_make_rsrc(biasT ? (const void*)(biasT + (size_t)hy * 8 * ldT) : (const void*)k, biasT ? (unsigned)(8 * ldT * 4) : 0u);
-    const unsigned ring_lds = (unsigned)(size_t)LDS_PTR(char, ring);
-
-    auto issue = [&](int t, int lane_) {                       // 5 DMA wave-instructions per wave per tile
-        A4Stager stg;
-        stg.init(wave, lane_, ldT);
-        const unsigned st = ring_lds + (unsigned)((t % A2_NST) * A2_STAGE);
-        const int j0 = t * A2_TKV;
-        const unsigned long long lb = livebits[t];             // one broadcast LDS read per tile
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            a2_dma(rsK, st + (2 * wave + u) * 1024, (unsigned)(j0 * 128) + stg.koff[u]);           // rows >= N: beyond the descriptor -> zeros
-            a2_dma(rsV, st + 8192 + (2 * wave + u) * 1024, ((lb >> stg.vrow[u]) & 1ull) ? (unsigned)(j0 * 128) + stg.voff[u] : OOB_OFF);
-        }
-        // bias window of this tile: table index PAD + rel, rel from i0 - j0 - 64 (no table: empty descriptor -> zeros)
-        a2_dma(rsB, st + 16384 + wave * 1024, (unsigned)((A2_PAD + off + i0 - j0 - 64) * 4) + stg.boff);
-    };
-
-    issue(0, lane);
-    if (nkt > 1) issue(1, lane);
-    // Q fragments (B operand of S^T = K Q^T): query i0 + ql, dims 16 s + 8 hi .. +7, of the wave's two heads
-    h16x8 qf[2][4];
-    const int qi = i0 + ql;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-        const bool act = h0 + hb < H;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            u32x4 z = {0u, 0u, 0u, 0u};
-            const h16_t* p = q + (rowbase + min(qi, N - 1)) * (size_t)(H * 64) + (size_t)(act ? h0 + hb : 0) * 64 + 16 * s + 8 * hi;
-            u32x4 val = (act && qi < N) ? *(const u32x4*)p : z;
-            qf[hb][s] = __builtin_bit_cast(h16x8, val);
-        }
-    }
-    // Consume the Q loads HERE: hipcc then waits for them before the loop.  Left to their first use inside the loop, its
-    // s_waitcnt vmcnt(0) sat in front of the first MFMA of every tile and drained the DMA ring each iteration (seen in the ISA).
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(qf[hb][s]));
-
-    A4Acc A;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-        A.m[hb] = A2_NEG;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) { A.acc[hb][0][e] = 0.f; A.acc[hb][1][e] = 0.f; }
-    }
-#pragma unroll
-    for (int e = 0; e < 16; ++e) A.accl[e] = 0.f;
-    const float c = scale * A2_LOG2E;
-    float mfix[2] = {0.f, 0.f};                              // fixed reference points of the two heads (table tails)
-    if (FIXED) {
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb)
-            mfix[hb] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(biasT[(size_t)(h0 + hb) * ldT + (ldT - 1)])));
-    }
-    asm volatile("" : "+s"(mfix[0]), "+s"(mfix[1]));          // loaded (and waited for) before the tile loop
-    unsigned rk[2] = {0u, 0u};                               // DROP: row keys of (b, h0 + hb, qi), with this half-wave's key bit (4 hi) / 2
-    if (DROP) {
-        const unsigned long long sd = attn_drop_seed(drop);
-#pragma unroll
-        for (int hb = 0; hb < 2; ++hb) rk[hb] = attn_drop_headkey(sd, b, h0 + hb) ^ ((unsigned)qi << 15) ^ (2u * (unsigned)hi);
-    }
-
-    for (int t = 0; t < nkt; ++t) {
-        // own DMA of tile t retired (tile t+1's five may stay in flight), then everybody's; the barrier also says that all
-        // waves are done with tile t-1, whose stage tile t+2 is about to overwrite
-        if (t + 1 < nkt) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        else             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        int lane_ = lane;                                      // opaque per tile: every lane-derived address is rebuilt, none carried (see A4Stager)
-        asm volatile("" : "+v"(lane_));
-        if (t + 2 < nkt) issue(t + 2, lane_);
-        const char* Ks = ring + (t % A2_NST) * A2_STAGE;
-        const int j0 = t * A2_TKV;
-        const bool full = j0 + A2_TKV - 1 <= i0;               // every block of the tile lies below the diagonal
-        const h16_t* lv = livef + j0 + 4 * (lane_ >> 5);
-        const h16_t* live0 = (lane_ & 1) == 0 ? lv : (const h16_t*)zeros;
-        const h16_t* live1 = (lane_ & 1) == 1 ? lv : (const h16_t*)zeros;
-        if (FIXED) {
-            if (full) a4_tile<true, true, -1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
-            else      a4_tile<true, false, -1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
-        } else if (full) {
-            a4_tile<false, true, 0, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
-            __builtin_amdgcn_sched_barrier(0);
-            a4_tile<false, true, 1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
-        } else {
-            a4_tile<false, false, 0, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
-            __builtin_amdgcn_sched_barrier(0);
-            a4_tile<false, false, 1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
-        }
-    }
-    if (qi >= N) return;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-        const int h = h0 + hb;
-        if (h >= H) continue;
-        const float lsum = A.accl[hb];                  // element e = hb: row crow(hb, hi) has parity hb
-        const float mref = FIXED ? mfix[hb] : A.m[hb];
-        // a query without any live causal key has no defined softmax: emit zeros and an lse that zeroes its backward
-        const float inv = lsum > 0.f ? (DROP ? drop.rs : 1.0f) / lsum : 0.f;
-        h16_t* orow = out + (rowbase + qi) * (size_t)(H * 64) + (size_t)h * 64;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int d = 32 * dt + 8 * g4 + 4 * hi;
-                store4_from_float(orow + d, A.acc[hb][dt][4 * g4] * inv, A.acc[hb][dt][4 * g4 + 1] * inv,
-                                  A.acc[hb][dt][4 * g4 + 2] * inv, A.acc[hb][dt][4 * g4 + 3] * inv);
-            }
-        if (hi == 0 && lse) lse[((size_t)b * H + h) * N + qi] = lsum > 0.f ? mref + log2f(lsum) : 1.0e30f;   // log2 domain
-    }
-}
+#define A4_KERNEL attn4_fwd_kernel
+#define A4_LONG false
+#include "attention2_fwd.inc"
+#undef A4_KERNEL
+#undef A4_LONG
+#define A4_KERNEL attn4_fwd_long_kernel
+#define A4_LONG true
+#include "attention2_fwd.inc"
+#undef A4_KERNEL
+#undef A4_LONG
 
 // =========================================================================================================================
 // backward, dQ / d(bias) / delta kernel on the same skeleton: 8 heads x 32 queries per workgroup, 64-key tiles through the
@@ -544,231 +390,17 @@ __global__ __launch_bounds__(A4_THREADS, 2) void attn4_fwd_kernel(const h16_t* _
 #define A2B_STAGE (3 * 8192 + 8 * A2_BWIN * 4)       /* 28 KiB */
 // PFX: the non-causal prefix (see attn4_fwd_kernel); the d(bias) bins of the negative distances sit in front of each wave's bins and leave
 // by atomics into dbias (which points at the rel = 0 row).
-template <bool DROP = false, bool PFX = false>
-__global__ __launch_bounds__(A2_THREADS) void attn2_bwd_dq_kernel(const h16_t* __restrict__ q, const h16_t* __restrict__ k,
-                                                                  const h16_t* __restrict__ v, const float* __restrict__ biasT, int ldT,
-                                                                  const unsigned char* __restrict__ keymask, const h16_t* __restrict__ out,
-                                                                  const h16_t* __restrict__ dout, const float* __restrict__ lse,
-                                                                  float* __restrict__ delta, float* __restrict__ dq, float* __restrict__ dbias,
-                                                                  int bias_ld, float* __restrict__ dpart, int B, int N, int H, float scale,
-                                                                  const AttnDrop drop, int Pn) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* ring = smem;
-    char* scratch = smem + A2_NST * A2B_STAGE;
-    const int npad = (N + 63) / 64 * 64;
-    float* mb = (float*)(scratch + 4096);                     // [npad] 0 / -1e30 per key of this sample
-    float* dbl = mb + npad;                                   // [8 waves][nbp]
-    const int nqt = (N + 31) / 32, ny = (H + 7) / 8;
-    int b, qt, hy;
-    a2_item_order(blockIdx.x, nqt, ny, B, b, qt, hy);
-    const int lane = threadIdx.x & 63, hi = lane >> 5, ql = lane & 31;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int h = hy * 8 + wave;
-    const bool active = h < H;
-    const int i0 = qt * 32, qi = i0 + ql;
-    const int nb = i0 + 32;                                   // rel in [0, i0 + 31]
-    const size_t rowbase = (size_t)b * N;
-    const int off = PFX ? Pn - 1 : 0;                         // PFX: negative-distance bins in front
-    const int kend = PFX && i0 < Pn ? max(i0 + 32, Pn) : i0 + 32;
-    const int nkt = min((kend + A2_TKV - 1) / A2_TKV, (N + A2_TKV - 1) / A2_TKV);
-    float* dbw = dbl + (size_t)wave * (nb + off) + off;      // index rel
-
-    {   // additive key mask, all byte loads in flight at once; this wave's d(bias) bins zeroed
-        unsigned char mk[8];
-#pragma unroll
-        for (int it = 0; it < 8; ++it) mk[it] = 1;
-        if (keymask) {
-#pragma unroll
-            for (int it = 0; it < 8; ++it) mk[it] = keymask[rowbase + min(it * A2_THREADS + (int)threadIdx.x, N - 1)];
-        }
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int j = it * A2_THREADS + threadIdx.x;
-            if (j < nkt * A2_TKV) mb[j] = (j < N && mk[it] != 0) ? 0.f : A2_NEG;
-        }
-        if (dbias) for (int r = lane - off; r < nb; r += 64) dbw[r] = 0.f;
-    }
-    __syncthreads();
-    // per-lane DMA source offsets: K rows and V rows use the row image, K blocked the blocked image (see A2Stager)
-    A2Stager stg;
-    stg.init(wave, lane, ldT);
-    const a2_rsrc rsK = a2_make_rsrc(k + rowbase * 64, (unsigned)N * 128u);
-    const a2_rsrc rsV = a2_make_rsrc(v + rowbase * 64, (unsigned)N * 128u);
-    const a2_rsrc rsB = a2_make_rsrc(biasT ? (const void*)(biasT + (size_t)hy * 8 * ldT) : (const void*)k, biasT ? (unsigned)(8 * ldT * 4) : 0u);
-    const unsigned ring_lds = (unsigned)(size_t)LDS_PTR(char, ring), scratch_lds = (unsigned)(size_t)LDS_PTR(char, scratch);
-    auto issue = [&](int t) {                                  // 4 DMA wave-instructions per wave per tile
-        const unsigned st = ring_lds + (unsigned)((t % A2_NST) * A2B_STAGE);
-        const int j0 = t * A2_TKV;
-        a2_dma(rsK, st + wave * 1024, (unsigned)(j0 * 128) + stg.koff);
-        a2_dma(rsK, st + 8192 + wave * 1024, (unsigned)(j0 * 128) + stg.voff);
-        a2_dma(rsV, st + 16384 + wave * 1024, (unsigned)(j0 * 128) + stg.koff);
-        const unsigned w0 = (unsigned)((A2_PAD + off + i0 - j0 - 64) * 4);
-        if (stg.bias_wave) a2_dma(rsB, st + 24576 + (wave & 3) * 1024, w0 + stg.boff);
-        else               a2_dma(rsB, scratch_lds + (wave & 3) * 1024, OOB_OFF);
-    };
-    issue(0);
-    if (nkt > 1) issue(1);
-
-    // Q and dO fragments (B operands), delta_i = sum_d dO O, the row's log-sum-exp relative to the table's reference point
-    h16x8 qf[4], dof[4];
-    float dl = 0.f;
-    const size_t qrow = (rowbase + min(qi, N - 1)) * (size_t)(H * 64) + (size_t)(active ? h : 0) * 64;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        u32x4 z = {0u, 0u, 0u, 0u};
-        const bool ok = active && qi < N;
-        const u32x4 qv = ok ? *(const u32x4*)(q + qrow + 16 * s + 8 * hi) : z;
-        const u32x4 dv = ok ? *(const u32x4*)(dout + qrow + 16 * s + 8 * hi) : z;
-        const u32x4 ov = ok ? *(const u32x4*)(out + qrow + 16 * s + 8 * hi) : z;
-        qf[s] = __builtin_bit_cast(h16x8, qv);
-        dof[s] = __builtin_bit_cast(h16x8, dv);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) dl += h16_lo_to_f(dv[e]) * h16_lo_to_f(ov[e]) + h16_hi_to_f(dv[e]) * h16_hi_to_f(ov[e]);
-    }
-    dl += __shfl_xor(dl, 32, 64);
-    float Lp = 0.f;
-    if (active) {
-        Lp = lse[((size_t)b * H + h) * N + min(qi, N - 1)];
-        if (biasT) Lp -= biasT[(size_t)h * ldT + (ldT - 1)];     // the table is stored relative to its reference point m_h
-        if (hi == 0 && qi < N) delta[((size_t)b * H + h) * N + qi] = dl;
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) { asm volatile("" : "+v"(qf[s])); asm volatile("" : "+v"(dof[s])); }
-    asm volatile("" : "+v"(Lp), "+v"(dl));                    // every prologue load is consumed before the tile loop
-    unsigned rk = 0u;                                         // DROP: row key of (b, h, qi) with this half-wave's key bit (see the forward)
-    if (DROP) rk = attn_drop_headkey(attn_drop_seed(drop), b, h) ^ ((unsigned)qi << 15) ^ (2u * (unsigned)hi);
-
-    f32x16 acc[2];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
-    const float c = scale * A2_LOG2E;
-
-    for (int t = 0; t < nkt; ++t) {
-        if (t + 1 < nkt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (t + 2 < nkt) issue(t + 2);
-        if (!active) continue;
-        const char* Kr = ring + (t % A2_NST) * A2B_STAGE;
-        const char* Kb = Kr + 8192;
-        const char* Vr = Kr + 16384;
-        const float* bw = (const float*)(Kr + 24576) + wave * A2_BWIN;
-        const int j0 = t * A2_TKV;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub) {
-            const int jb = j0 + 32 * sub;
-            if (jb > kend - 1) break;
-            f32x16 st, dp;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { st[e] = 0.f; dp[e] = 0.f; }
-            {   // all eight fragment reads in flight before the first MFMA, retired in two groups (hipcc issued them one at a time
-                // through the same four registers: read -> wait -> MFMA, seen in the ISA)
-                h16x8 kfr[4], vfr[4];
-#pragma unroll
-                for (int s = 0; s < 4; ++s) { kfr[s] = a2_frag_rows(Kr, 32 * sub, s, lane); vfr[s] = a2_frag_rows(Vr, 32 * sub, s, lane); }
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    if ((s & 1) == 0) asm volatile("" : "+v"(kfr[s]), "+v"(vfr[s]), "+v"(kfr[s + 1]), "+v"(vfr[s + 1]));
-                    st = MFMA16(kfr[s], qf[s], st);                               // S^T  = K Q^T
-                    dp = MFMA16(vfr[s], dof[s], dp);                              // dP^T = V dO^T
-                }
-            }
-            const float* bp = bw + (64 - 32 * sub) + ql - 4 * hi;
-            const float* mp = mb + jb + 4 * hi;
-            float bv[16];
-            const bool diag = jb + 31 > i0;
-            const int d0 = qi - (jb + 4 * hi);
-            float4 m4s[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) m4s[g] = *(const float4*)(mp + 8 * g);
-            float bpv[16];                     // bias window gathered in one pass (see m4s: nothing waits element by element)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bpv[r] = bp[-((r & 3) + 8 * (r >> 2))];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(bpv[r]));
-            if (diag) {                        // the block on the diagonal: keys above it leave through the bias term (a real branch: one block in nkt)
-                int d0v = d0;
-                asm volatile("" : "+v"(d0v));             // the selects depend on a value defined inside the branch: hipcc otherwise hoists all 16 of them in front of it
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int cr = (r & 3) + 8 * (r >> 2);
-                    bpv[r] = (d0v - cr >= 0 || (PFX && qi < Pn && jb + 4 * hi + cr < Pn)) ? bpv[r] : A2_NEG;
-                }
-            }
-            // element arithmetic on register pairs (v_pk_fma_f32 / v_pk_add_f32 / v_pk_mul_f32); the softmax scale is applied once to
-            // dQ (dQ = scale dS K) instead of to every dS
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float4 m4 = m4s[g];
-                const f32x2 mm2[2] = {{m4.x, m4.y}, {m4.z, m4.w}};
-#pragma unroll
-                for (int pq = 0; pq < 2; ++pq) {
-                    const int r = 4 * g + 2 * pq, cr = 2 * pq + 8 * g;
-                    const f32x2 t2 = (f32x2{bpv[r], bpv[r + 1]} + mm2[pq]) - f32x2{Lp, Lp};
-                    const f32x2 x2 = __builtin_elementwise_fma(f32x2{st[r], st[r + 1]}, f32x2{c, c}, t2);
-                    const f32x2 pr2 = {__builtin_amdgcn_exp2f(x2[0]), __builtin_amdgcn_exp2f(x2[1])};
-                    f32x2 dp2 = {dp[r], dp[r + 1]};
-                    if (DROP) {                // dropout: dS = P (Z dP~ / (1 - p) - delta); keys jb + 4 hi + cr + {0, 1} share one word
-                        const unsigned w = omlm_hash32(rk ^ (unsigned)(jb >> 1) ^ (unsigned)(cr >> 1));
-                        dp2 = dp2 * f32x2{drop.rs, drop.rs};
-                        dp2 = f32x2{(w << 16) >= drop.thr16 ? dp2[0] : 0.f, w >= drop.thr16 ? dp2[1] : 0.f};
-                    }
-                    const f32x2 ds2 = pr2 * (dp2 - f32x2{dl, dl});   // dS = P (dP - delta), 0 where masked; scale: see the dQ store
-                    bv[r] = ds2[0]; bv[r + 1] = ds2[1];
-                    st[r] = ds2[0]; st[r + 1] = ds2[1];
-                }
-            }
-            if (dbias) {
-                // d(bias)[rel] = sum of dS over the diagonal rel = i - j: output lane L stands for t = q - kr = L - 31 and pulls row
-                // kr's element from query column q = t + kr through the cross-lane permute; then one read-add-write of this
-                // wave's private table (every lane owns a distinct bin)
-                const float dsum = diag_sum_32x32(bv, lane);
-                const int rel = (i0 - jb) + (lane - 31);
-                if (rel >= -off && rel < nb) dbw[rel] += dsum;      // (ds_add_f32 instead of this read-add-write: measured 20 us per layer SLOWER)
-            }
-            {
-                h16x8 ktf[2][2], dsb[2];
-#pragma unroll
-                for (int s = 0; s < 2; ++s) { ktf[s][0] = a2_frag_cols_tr(Kb, 32 * sub, s, 0, lane); ktf[s][1] = a2_frag_cols_tr(Kb, 32 * sub, s, 32, lane); }
-#pragma unroll
-                for (int s = 0; s < 2; ++s) dsb[s] = a2_pack(st, s);
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    asm volatile("" : "+v"(ktf[s][0]), "+v"(ktf[s][1]));
-                    acc[0] = MFMA16(ktf[s][0], dsb[s], acc[0]);                                // dQ^T += K^T dS^T
-                    acc[1] = MFMA16(ktf[s][1], dsb[s], acc[1]);
-                }
-            }
-        }
-    }
-    if (!active) return;
-    if (qi < N) {
-        float* drow = dq + (rowbase + qi) * (size_t)(H * 64) + (size_t)h * 64;
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int d = 32 * dt + 8 * g4 + 4 * hi;
-                *(float4*)(drow + d) = make_float4(scale * acc[dt][4 * g4], scale * acc[dt][4 * g4 + 1], scale * acc[dt][4 * g4 + 2], scale * acc[dt][4 * g4 + 3]);
-            }
-    }
-    if (dbias) {
-        __builtin_amdgcn_s_waitcnt(0xc07f);                   // this wave's LDS updates are complete for its own reads
-        if (dpart) {                                          // one row of the partial buffer (see attention.hip's dQ kernel): plain stores
-            float* prow = dpart + (((size_t)b * H + h) * nqt + qt) * (size_t)(nqt * 32);
-            for (int r = lane; r < nb; r += 64) prow[r] = dbw[r];
-        } else
-        for (int r = lane; r < min(nb, N); r += 64) {
-            const float vv = dbw[r];
-            if (vv != 0.f) unsafeAtomicAdd(dbias + (size_t)r * bias_ld + h, vv);
-        }
-        if (PFX && i0 < Pn)                                   // negative distances: only query tiles inside the prefix reach them
-            for (int r = lane - off; r < 0; r += 64) {
-                const float vv = dbw[r];
-                if (vv != 0.f) unsafeAtomicAdd(dbias + (ptrdiff_t)r * bias_ld + h, vv);
-            }
-    }
-}
+#define A2_BINW 128          /* d(bias) bins per wave of the long form's ring */
+#define A2Q_KERNEL attn2_bwd_dq_kernel
+#define A2Q_LONG false
+#include "attention2_dq.inc"
+#undef A2Q_KERNEL
+#undef A2Q_LONG
+#define A2Q_KERNEL attn2_bwd_dq_long_kernel
+#define A2Q_LONG true
+#include "attention2_dq.inc"
+#undef A2Q_KERNEL
+#undef A2Q_LONG
 
 static size_t a2_dq_lds(int N, int off) {
     const int nqt = (N + 31) / 32, npad = (N + 63) / 64 * 64;
@@ -786,8 +418,24 @@ int attn2_bwd_dq_launch(const void* q, const void* k, const void* v, const float
     const int off = Pn > 0 ? Pn - 1 : 0;                       // Pn > 0: the non-causal prefix (PFX instances)
     const int ldT = (A2_PAD + off + N + 2 * A2_BWIN + 3) / 4 * 4;
     const int nqt = (N + 31) / 32, ny = (H + 7) / 8;
+    if (N > 4096) {                                            // the long form (the entry points have refused N > A2_NL and a prefix)
+        if (N > A2_NL || Pn > 0) return OMLM_ERR_UNSUPPORTED;
+        const size_t ldsl = (size_t)A2_NST * A2B_STAGE + 4096 + 8 * A2_BINW * 4 + (size_t)((N + 63) / 64 * 64);
+        static bool a1l = false;
+        if (!a1l) {
+            (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_long_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_long_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            a1l = true;
+        }
+        const AttnDrop ndl = {0ull, nullptr, 0u, 1.0f};
+        auto kernl = drop ? attn2_bwd_dq_long_kernel<true> : attn2_bwd_dq_long_kernel<false>;
+        hipLaunchKernelGGL(kernl, dim3(nqt * ny * B), dim3(A2_THREADS), ldsl, st,
+                           (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta,
+                           dq, dbias, bias_ld, dpart, B, N, H, scale, drop ? *drop : ndl, 0);
+        return omlm_post_launch("omlm_mqa_attn_bwd");
+    }
     const size_t lds = a2_dq_lds(N, off);
-    if (lds > 160 * 1024 || N > 4096) return 1;                // caller falls back to the first-generation kernel
+    if (lds > 160 * 1024) return 1;                            // caller falls back to the first-generation kernel
     static bool a1 = false;
     if (!a1) {
         (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -886,9 +534,14 @@ __global__ __launch_bounds__(256) void attn_dbias_reduce_kernel(const float* __r
     if (t != 0.f) unsafeAtomicAdd(dbias + (size_t)r * bias_ld + h, t);
 }
 
+long long attn3_part_floats(int B, int N);       // attention3.hip
+// N <= 4096: the d(bias) rows.  N > 4096: the same rows, then the slots of the dK / dV kernel (attn3_part_floats: B x workgroups per sample x
+// 64 KiB), which make dK / dV sums of a fixed order there.
 extern "C" long long omlm_mqa_attn_bwd_workspace_bytes(int B, int N, int H) {
+    if (B <= 0 || N <= 0 || H <= 0) return 0;
     const long long nqt = (N + 31) / 32;
-    return (long long)B * H * nqt * nqt * 32 * (long long)sizeof(float);
+    const long long rows = (long long)B * H * nqt * nqt * 32;
+    return (rows + (N > 4096 ? attn3_part_floats(B, N) : 0)) * (long long)sizeof(float);
 }
 
 extern "C" __attribute__((visibility("hidden"))) int omlm_attn_dbias_reduce_launch(const float* dpart, float* dbias, int bias_ld, int B, int N, int H, void* stream) {
@@ -979,8 +632,29 @@ extern "C" int omlm_dropout_residual_bwd(const float* dx1, void* dy, long long M
 int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
                      void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn) {
     const int ldT = (A2_PAD + (Pn > 0 ? Pn - 1 : 0) + N + 2 * A2_BWIN + 3) / 4 * 4;
-    if (N > 64 * 64) { omlm_set_error("attention: N > 4096 keys per sample is not supported (liveness prologue covers 4096 keys)"); return OMLM_ERR_UNSUPPORTED; }
     const int nqt = (N + 31) / 32, ny = (H + 7) / 8;
+    if (N > 64 * 64) {                                          // the long form (the entry points have refused N > A2_NL and a prefix)
+        if (N > A2_NL || Pn > 0) return OMLM_ERR_UNSUPPORTED;
+        const size_t ldsl = (size_t)A2_NST * A2_STAGE + (size_t)((N + 63) / 64) * (64 * 2 + 8) + 128;
+        static bool a4l = false;
+        if (!a4l) {
+            (void)hipFuncSetAttribute((const void*)attn4_fwd_long_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute((const void*)attn4_fwd_long_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute((const void*)attn4_fwd_long_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            (void)hipFuncSetAttribute((const void*)attn4_fwd_long_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            a4l = true;
+        }
+        const AttnDrop ndl = {0ull, nullptr, 0u, 1.0f};
+        const AttnDrop& drl = drop ? *drop : ndl;
+        const dim3 gridl(nqt * ny * B);
+        auto fixedl = drop ? attn4_fwd_long_kernel<true, true> : attn4_fwd_long_kernel<true>;
+        auto onlinel = drop ? attn4_fwd_long_kernel<false, true> : attn4_fwd_long_kernel<false>;
+        if (biasT) hipLaunchKernelGGL(fixedl, gridl, dim3(A4_THREADS), ldsl, st,
+                                      (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, drl, 0);
+        hipLaunchKernelGGL(onlinel, gridl, dim3(A4_THREADS), ldsl, st,
+                           (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, drl, 0);
+        return omlm_post_launch("omlm_mqa_attn_fwd");
+    }
     const size_t lds = (size_t)A2_NST * A2_STAGE + (size_t)((N + 63) / 64 * 64) * 2 + 64 * 8 + 128;
     static bool a4 = false;
     if (!a4) {

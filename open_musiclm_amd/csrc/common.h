@@ -48,6 +48,10 @@ static inline void launch_with_lds(dim3 grid, dim3 block, size_t lds, hipStream_
 #ifndef OMLM_FP16
 #define OMLM_FP16 0
 #endif
+// most positions per sample of causal attention with 16-bit operands (the long forms of attention2.hip / attention3.hip serve 4096 < N <= this);
+// reported by omlm_attn_max_positions.  Bounds: the dropout row key holds the key pair index in 15 bits (N < 65536); the dQ kernel's LDS
+// grows by one byte per position (108 KiB here).
+#define OMLM_ATTN_NL 16384
 #define OMLM_DT_F32 0
 #define OMLM_DT_BF16 1
 #define OMLM_DT_F16 2

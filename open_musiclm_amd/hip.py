@@ -50,6 +50,7 @@ SIGNATURES = {
     "omlm_mqa_attn_fwd": [vp] * 8 + [i32, i32, i32, f32, i32, i32, i32, f32, u64, vp, vp],
     "omlm_mqa_attn_bwd": [vp] * 15 + [i32, i32, i32, f32, i32, i32, i32, f32, u64, vp, vp],
     "omlm_mqa_attn_bwd_workspace_bytes": [i32, i32, i32],
+    "omlm_attn_max_positions": [i32, i32],
     "omlm_attn_dropout_keep": [vp, i32, i32, i32, f32, u64, vp, vp],
     "omlm_dropout_residual_fwd": [vp, vp, vp, i64, i32, f32, u64, vp, vp],
     "omlm_dropout_residual_bwd": [vp, vp, i64, i32, f32, u64, vp, i32, vp],

@@ -417,7 +417,8 @@ def _dbias_workspace(B: int, N: int, H: int, device) -> torch.Tensor:
     """Scratch for the backward's d(bias) partial rows (omlm_mqa_attn_bwd_workspace_bytes): ONE buffer per device, shared by every
     layer and every step (the reduction kernel of a layer consumes it before the next layer's dQ kernel writes it: stream order;
     like _ln_workspace it assumes one backward at a time per device).  It is quadratic in N (B H ceil(N/32)^2 128 bytes: 40 MB at
-    B = 32, N = 1116), so one copy per layer was 24 x 53 MB for the musiclm_large leg."""
+    B = 32, N = 1116), so one copy per layer was 24 x 53 MB for the musiclm_large leg.  Past N = 4096 it also holds the dK / dV kernel's
+    slots (include/omlm.h)."""
     n = int(hip.lib().omlm_mqa_attn_bwd_workspace_bytes(B, N, H)) // 4
     key = str(device)
     ws = _DBIAS_WS.get(key)
@@ -430,11 +431,25 @@ def _dbias_workspace(B: int, N: int, H: int, device) -> torch.Tensor:
     return ws
 
 
+def attn_max_positions(dtype, P: int = 0) -> int:
+    """Most positions per sample attn_fwd + attn_bwd take for operands of `dtype` with a prefix of P rows (omlm_attn_max_positions)."""
+    return int(hip.lib().omlm_attn_max_positions(dcode(dtype), int(P)))
+
+
+def _check_positions(what, N, dtype, P):
+    """16-bit causal attention past its ceiling is refused here, before the bias table is prepared (the library refuses every other case
+    itself, with the limit of the route the call would take)."""
+    if P == 0 and dtype in H16 and N > attn_max_positions(dtype, 0):
+        raise RuntimeError(f"{what}: N = {N} positions per sample is past the limit of {attn_max_positions(dtype, 0)} "
+                           f"(omlm_attn_max_positions) of causal attention with {dtype} operands")
+
+
 def attn_fwd(q, k, v, bias, keymask, out, lse, B, N, H, scale, P=0, p=0.0, seed=0, seed_dev=None):
     """Attention with a non-causal prefix of P rows (omlm_mqa_attn_fwd; 0: causal): score (i, j) is live iff j <= i or i, j < P.
     bias: an AttnBias of the layout for P (built once per forward by the engine: AttnBias.group(..., P=P)), a raw [N + min(P, N) - 1, ld]
     fp32 rel-pos table (row i - j + min(P, N) - 1, relpos_forward with P), or None.
     p > 0: dropout on the probabilities with the keep-mask of include/omlm.h (seed, optional device salt seed_dev: int64 [1])."""
+    _check_positions("attn_fwd", N, q.dtype, P)
     table, tableT = _attn_tables(bias, N, H, P, q.device)
     call("omlm_mqa_attn_fwd", ptr(q), ptr(k), ptr(v), ptr(table), ptr(tableT), ptr(keymask), ptr(out), ptr(lse), B, N, H, float(scale),
          table.shape[-1] if table is not None else 0, dcode(q.dtype), int(P), float(p), int(seed), ptr(seed_dev), stream_ptr())
@@ -445,6 +460,7 @@ def attn_bwd(q, k, v, bias, keymask, out, dout, lse, delta, dq, dk, dv, dbias, B
     """Backward of attn_fwd.  bias: the forward's (an AttnBias: its tableT carries the reference point lse is relative to).  dbias: the raw
     table's layout (accumulated, +=), or None.  workspace=False: d(bias) by device-scope atomics straight into the table (the C ABI's
     null-workspace form; slower).  P, p, seed, seed_dev: those of the forward (the kernels regenerate its keep-mask)."""
+    _check_positions("attn_bwd", N, q.dtype, P)
     table, tableT = _attn_tables(bias, N, H, P, q.device)
     ws = _dbias_workspace(B, N, H, q.device) if dbias is not None and workspace else None
     ld = table.shape[-1] if table is not None else (dbias.shape[-1] if dbias is not None else 0)
