@@ -444,7 +444,17 @@ int omlm_sample_embed_at(const float* logits, const float* uniform_base, const i
  * round_bf16 = 1 rounds the activations the batched path keeps in bf16).  W1p [2*Fp, D] / W2p [D, Fp] / convw [3, 2*Fp] /
  * mid_gamma [Fp] are the padded layouts of omlm_ffmid_fwd.  emb_table (optional): x = emb_table[ids[b] + emb_row_offset]
  * first (open_musiclm.py:123-134); otherwise x must already hold the new row.  head_W (optional) [V1, D]: logits
- * [B, ldV] = LN(x_L) head_W^T.  B <= 8; 16-bit weights with D = 1024 and ln_parts given: B <= 16 (matrix-core step kernels). */
+ * [B, ldV] = LN(x_L) head_W^T.  B <= 8; 16-bit weights with D = 1024 and ln_parts given: B <= 16 (matrix-core step kernels); with
+ * splitk_ws and splitk_cnt as well: B <= 64.
+ * A call of more than 16 samples runs as G = OMLM_DECODE_GROUPS(B) groups of 16 consecutive samples (the last one possibly partial)
+ * carried through ONE launch of every phase: a group is computed exactly as a call of its own sample count would be (same kernels'
+ * branches, same summation order, same bits), and the G workgroups that read the same weight rows share an XCD.  The scratch grows with
+ * G -- sizes for a call of B samples (for B <= 16 they are the per-group sizes named at the members):
+ *   ln_parts    OMLM_DECODE_LN_PARTS_B(B, D, Fp) floats   = 3 * G * OMLM_DECODE_LN_PARTS(D, Fp)
+ *   splitk_ws   OMLM_DECODE_SPLITK_FLOATS_B(B, D) floats  = G * OMLM_DECODE_SPLITK_FLOATS(D)
+ *   splitk_cnt  OMLM_DECODE_SPLITK_CNT_B(B, D) ints       = max(G * ceil(D / 16), B, 16): FF-out takes its tickets per (group, tile), the
+ *               attention combine per sample, in the same array; all zero before the first step, every step leaves them zero.
+ * The library sees pointers only and cannot check these sizes; it checks that the scratch a batch needs is given. */
 typedef struct omlm_decode_args {
     int B, D, H, L, F, Fp, Nmax, w_dtype, round_bf16, nsplit;     /* nsplit >= ceil(Nmax / 64): attention key ranges */
     float eps, scale;
@@ -460,7 +470,7 @@ typedef struct omlm_decode_args {
     int* advance_pos; int* advance_step;   /* optional DEVICE counters (+= 1) bumped by the step's last kernel: pass pos_dev (and the
                                             * sampler's step counter) here instead of launching omlm_decode_advance */
     float* ln_parts;                       /* optional scratch, 3 * OMLM_DECODE_LN_PARTS(D, Fp) floats: the batched matrix-core kernels
-                                            * (2 <= B <= 8) leave per-workgroup partial sums of their outputs there, and the kernel that
+                                            * (B >= 2; B > 16: OMLM_DECODE_LN_PARTS_B floats) leave per-workgroup partial sums of their outputs there, and the kernel that
                                             * applies the next LayerNorm adds them up instead of re-reducing every sample's row; null:
                                             * every consumer reduces the rows itself */
     /* precision "fp16ff" (optional; all NULL: the plain 16-bit step): lo planes of the FF-in / FF-out / head weights in the layout of
@@ -468,15 +478,21 @@ typedef struct omlm_decode_args {
      * the batched forward's omlm_gemm_planes16 (open_musiclm.py:299-319 evaluated fp32-grade where the error budget puts the error).
      * B >= 2: needs the matrix-core kernels (16-bit weights, D = 1024, ln_parts given, L >= 1), Fp <= 3072. */
     const void* const* W1p_lo; const void* const* W2p_lo; const void* head_W_lo;
-    /* optional scratch of the batched FF-out launch (2 <= B <= 16, matrix-core kernels, ln_parts given): with it a tile of 16 output rows
+    /* optional scratch of the batched FF-out launch (2 <= B <= 64, matrix-core kernels, ln_parts given; required for B > 16): with it a tile of 16 output rows
      * is cut into four k-slices (256 workgroups instead of 64) that meet through fp32 slabs, added in slice order by the last to arrive.
      * splitk_ws: OMLM_DECODE_SPLITK_FLOATS(D) floats, contents irrelevant; splitk_cnt: max(ceil(D / 16), 16) ints (the attention kernel's combine
-     * counts per sample b < B <= 16 in the same array), ZERO before the first step
+     * counts per sample in the same array; B > 16: OMLM_DECODE_SPLITK_FLOATS_B / OMLM_DECODE_SPLITK_CNT_B), ZERO before the first step
      * (every step leaves them zero).  One decode stream at a time per scratch pair.  NULL: one workgroup per tile walks the whole row. */
     float* splitk_ws; int* splitk_cnt;
 } omlm_decode_args;
 #define OMLM_DECODE_SPLITK_FLOATS(D) (4 * (((D) + 15) / 16) * 256)
 #define OMLM_DECODE_LN_PARTS(D, Fp) ((((D) + 15) / 16 > ((Fp) + 7) / 8 ? ((D) + 15) / 16 : ((Fp) + 7) / 8) * 32)
+#define OMLM_DECODE_MAX_BATCH 64
+#define OMLM_DECODE_GROUPS(B) (((B) + 15) / 16)
+#define OMLM_DECODE_LN_PARTS_B(B, D, Fp) (3 * OMLM_DECODE_GROUPS(B) * OMLM_DECODE_LN_PARTS(D, Fp))
+#define OMLM_DECODE_SPLITK_FLOATS_B(B, D) (OMLM_DECODE_GROUPS(B) * OMLM_DECODE_SPLITK_FLOATS(D))
+#define OMLM_DECODE_SPLITK_CNT_B(B, D) \
+    (OMLM_DECODE_GROUPS(B) * (((D) + 15) / 16) > ((B) > 16 ? (B) : 16) ? OMLM_DECODE_GROUPS(B) * (((D) + 15) / 16) : ((B) > 16 ? (B) : 16))
 int omlm_decode_step(const omlm_decode_args* args, const long long* ids, void* stream);
 /* *pos_dev += 1, *step_dev += 1 (either may be null): keeps the row / sampler-step counters on the device so that a
  * captured step can be replayed. */

@@ -170,10 +170,11 @@ __device__ void stage_attention(const float* __restrict__ parts, int nsplit, int
 }
 
 // ---- embedding gather of the ids sampled in the previous step (open_musiclm.py:123-134: id + quantizer offset) ----
-// stat_out (optional): the row's (sum, sum of squares) as LayerNorm partial 0 of sample b (layout [partial][8 samples][2], see dec4_kernel)
+// stat_out (optional): the row's (sum, sum of squares) as LayerNorm partial 0 of sample b (layout [partial][16 samples][2] per group of 16
+// samples, the groups' regions gstat floats apart, see dec4_kernel)
 __global__ __launch_bounds__(DEC_T) void dec_embed_kernel(const long long* __restrict__ ids, const float* __restrict__ table,
                                                          long long row_off, long long rows, float* __restrict__ x, int D,
-                                                         float* __restrict__ stat_out) {
+                                                         float* __restrict__ stat_out, int gstat) {
     __shared__ float red[2 * (DEC_T / 64)];
     const int b = blockIdx.x;
     long long r = ids[b] + row_off;
@@ -187,12 +188,13 @@ __global__ __launch_bounds__(DEC_T) void dec_embed_kernel(const long long* __res
     if (threadIdx.x == 0) {
         float ts = 0.f, tq = 0.f;
         for (int w = 0; w < DEC_T / 64; ++w) { ts += red[2 * w]; tq += red[2 * w + 1]; }
-        stat_out[b * 2] = ts; stat_out[b * 2 + 1] = tq;
+        float* so = stat_out + (size_t)(b >> 4) * gstat + (b & 15) * 2;          // (b < 16: stat_out[b * 2])
+        so[0] = ts; so[1] = tq;
     }
 }
 
 // (sum, sum of squares) of each sample's row of x as LayerNorm partial 0 (rows embedded by the caller)
-__global__ __launch_bounds__(DEC_T) void dec_rowstat_kernel(const float* __restrict__ x, int D, float* __restrict__ stat_out) {
+__global__ __launch_bounds__(DEC_T) void dec_rowstat_kernel(const float* __restrict__ x, int D, float* __restrict__ stat_out, int gstat) {
     __shared__ float red[2 * (DEC_T / 64)];
     const int b = blockIdx.x;
     float s = 0.f, q = 0.f;
@@ -203,7 +205,8 @@ __global__ __launch_bounds__(DEC_T) void dec_rowstat_kernel(const float* __restr
     if (threadIdx.x == 0) {
         float ts = 0.f, tq = 0.f;
         for (int w = 0; w < DEC_T / 64; ++w) { ts += red[2 * w]; tq += red[2 * w + 1]; }
-        stat_out[b * 2] = ts; stat_out[b * 2 + 1] = tq;
+        float* so = stat_out + (size_t)(b >> 4) * gstat + (b & 15) * 2;          // (b < 16: stat_out[b * 2])
+        so[0] = ts; so[1] = tq;
     }
 }
 
@@ -595,6 +598,9 @@ struct dec2_args {
     // matrix-core kernels, DEC2_LNGEMV: the k-range of a row cut into nsl slices (grid = tiles * nsl); slabs [tile][slice][16 rows][16 samples]
     // in sk_ws, one arrival counter per tile in sk_cnt (zero on entry and exit)
     int nsl; float* sk_ws; int* sk_cnt;
+    // matrix-core kernels, GRP instantiations (B > 16: groups of 16 samples along gridDim.y): floats between two groups' regions of stat_in /
+    // stat_out, and the tiles of the launch (gridDim.x is padded to a multiple of 8)
+    int gstat, gtiles;
 };
 
 template <typename TW, int NI, int MODE>
@@ -927,6 +933,7 @@ __global__ __launch_bounds__(DEC_T) void dec3_ffin_kernel(dec2_args a) {
 #define DEC4_T 256
 #define DEC4_ROWS 16
 #define DEC4_NB 16
+#define DEC4_GMAX 4            // groups of DEC4_NB samples per call
 typedef __attribute__((ext_vector_type(4))) float dec4_acc;
 
 // Attention output of the new row from the per-split partials, ONCE per step: [B][H * 64] fp32 (rounded to the operand type).  The
@@ -960,9 +967,27 @@ __global__ __launch_bounds__(64) void dec_attn_combine_kernel(const float* __res
 // MFMAs per k-step (hi hi + hi lo + lo hi, the batched forward's omlm_gemm_planes16 arithmetic).  The images hold DEC4_IMG(NS) samples; a
 // larger batch (FF-out rows at B > 8) runs its k-loop twice.  Needs the producers' LayerNorm partials (stat_in).
 #define DEC4_IMG(NS) ((((NS) + 7) / 8) == 1 ? 16 : 8)
-template <int NS, int MODE, bool PL = false>
+// GRP (a call of more than 16 samples): gridDim.y groups of 16 consecutive samples, the last one possibly partial.  A workgroup serves ONE
+// group exactly as it serves a whole call otherwise -- same branches for its own sample count, same summation order -- with every
+// per-sample pointer moved on by 16 g samples and the LayerNorm partials / split-K slabs / tickets in the group's own region.  gridDim.x
+// is a multiple of 8, so the workgroups (x, 0..G-1), which read the same weight rows, have the same id modulo 8: one XCD, one L2.
+template <int NS, int MODE, bool PL = false, bool GRP = false>
 __global__ __launch_bounds__(DEC4_T) void dec4_kernel(dec2_args a) {
     extern __shared__ __attribute__((aligned(16))) char dsm4[];
+    if constexpr (GRP) {
+        if ((int)blockIdx.x >= a.gtiles) return;                // (padding of the grid: whole workgroups, before any barrier)
+        const int g = blockIdx.y;
+        const size_t s0 = (size_t)g * DEC4_NB;
+        a.B = min(DEC4_NB, a.B - g * DEC4_NB);
+        a.in += s0 * a.ldin;
+        if (a.res) a.res += s0 * a.ldres;
+        if (a.out) a.out += s0 * a.ldout;
+        if (MODE == DEC2_QKV) { a.q += s0 * a.H * 64; a.Kc += s0 * a.Nmax * 64; a.Vc += s0 * a.Nmax * 64; }
+        if (MODE == DEC2_FFIN) { a.hist += s0 * 4 * a.Fp; a.u += s0 * a.Fp; }
+        if (a.stat_in) a.stat_in += (size_t)g * a.gstat;
+        if (a.stat_out) a.stat_out += (size_t)g * a.gstat;
+        if (MODE == DEC2_LNGEMV && a.nsl > 1) { a.sk_ws += (size_t)g * gridDim.x * 256; a.sk_cnt += g * (gridDim.x / a.nsl); }
+    }
     // split-K (DEC2_LNGEMV with a.nsl > 1: the FF-out launch, 16 output rows x Fp per tile): 64 workgroups each walking a 2752-long row at
     // B = 16 were 21.6 us of the step (14.1 us without the lo planes) -- a quarter of the CUs, every one of them normalising all 16 x 2752
     // activations in two passes.  Here a tile's row is cut into a.nsl slices (one workgroup each, one pass over 16 samples); the slices
@@ -1344,28 +1369,38 @@ __global__ __launch_bounds__(DEC4_T) void dec4_kernel(dec2_args a) {
                 a.stat_out[(tile * DEC4_NB + threadIdx.x) * 2] = ps; a.stat_out[(tile * DEC4_NB + threadIdx.x) * 2 + 1] = pq;
             }
         }
-        if (MODE == DEC2_LNGEMV && blockIdx.x == 0 && threadIdx.x == 0 && a.adv_pos) {      // see dec3_kernel
+        if (MODE == DEC2_LNGEMV && blockIdx.x == 0 && (!GRP || blockIdx.y == 0) && threadIdx.x == 0 && a.adv_pos) {      // see dec3_kernel
             a.adv_pos[0] += 1;
             if (a.adv_step) a.adv_step[0] += 1;
         }
     }
 }
 
+template <int NS, int MODE, bool PL, bool GRP>
+static void dec4_launch_t(const dec2_args& a, dim3 grid, hipStream_t st) {
+    const int kmax = a.nsl > 1 ? 32 * (((a.K >> 5) + a.nsl - 1) / a.nsl) : a.K;       // longest k-range of a workgroup
+    const int nb = a.B < DEC4_NB ? a.B : DEC4_NB;                                     // samples of a workgroup
+    const size_t lds = (((size_t)(PL ? 2 * DEC4_IMG(NS) : nb) * (kmax + 8) * 2 + 15) & ~(size_t)15) + (size_t)(DEC4_NB * 8 + DEC4_NB * 2 + 4 * 256 + 256) * sizeof(float) +
+                       ((a.gamma && !a.stat_in) ? (size_t)nb * kmax * sizeof(float) : 0);       // fp32 staging copy: own-reduction path only (B <= 8)
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)dec4_kernel<NS, MODE, PL, GRP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+    hipLaunchKernelGGL((dec4_kernel<NS, MODE, PL, GRP>), grid, dim3(DEC4_T), lds, st, a);
+}
+// B <= 16: one group, the plain instantiation on a grid of `grid` workgroups.  B > 16: the GRP instantiation, the group along gridDim.y and
+// gridDim.x padded to a multiple of 8 (the head's 65 tiles) so that a tile's groups share an XCD.
 template <int NS, int MODE, bool PL = false>
 static void dec4_launch(const dec2_args& a, int grid, hipStream_t st) {
-    const int kmax = a.nsl > 1 ? 32 * (((a.K >> 5) + a.nsl - 1) / a.nsl) : a.K;       // longest k-range of a workgroup
-    const size_t lds = (((size_t)(PL ? 2 * DEC4_IMG(NS) : a.B) * (kmax + 8) * 2 + 15) & ~(size_t)15) + (size_t)(DEC4_NB * 8 + DEC4_NB * 2 + 4 * 256 + 256) * sizeof(float) +
-                       ((a.gamma && !a.stat_in) ? (size_t)a.B * kmax * sizeof(float) : 0);      // fp32 staging copy: own-reduction path only (B <= 8)
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)dec4_kernel<NS, MODE, PL>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    hipLaunchKernelGGL((dec4_kernel<NS, MODE, PL>), dim3(grid), dim3(DEC4_T), lds, st, a);
+    if (a.B <= DEC4_NB) { dec4_launch_t<NS, MODE, PL, false>(a, dim3(grid), st); return; }
+    dec2_args w = a;
+    w.gtiles = grid;
+    dec4_launch_t<NS, MODE, PL, true>(w, dim3((grid + 7) & ~7, (a.B + DEC4_NB - 1) / DEC4_NB), st);
 }
 // the matrix-core step kernels serve 16-bit weights with D, H * 64, Fp multiples of 32 and k-loops of at most 4 x 24 steps
 static bool dec4_ok(const omlm_decode_args& a) {
     // B > 8: every LayerNorm in front of a matrix-core kernel must find its statistics in the producers' partials (the own-reduction
     // path stages fp32 rows for at most 8 samples): a.ln_parts given
     const bool wide_ok = a.B <= 8 || a.ln_parts != nullptr;
-    return a.B >= 2 && a.B <= DEC4_NB && wide_ok && a.D % 32 == 0 && a.D <= 1024 && (a.H * 64) % 32 == 0 && a.H * 64 <= 1024 &&
+    return a.B >= 2 && a.B <= DEC4_GMAX * DEC4_NB && wide_ok && a.D % 32 == 0 && a.D <= 1024 && (a.H * 64) % 32 == 0 && a.H * 64 <= 1024 &&
            a.Fp % 32 == 0 && a.Fp <= 3072 && a.Fp % 8 == 0;
 }
 
@@ -1383,20 +1418,22 @@ static int decode_step2_t(const omlm_decode_args& a, const long long* ids, hipSt
     // gather and by every FF-out launch, read by the q rows and the head), x1 (to_out -> FF-in), u (FF-in -> FF-out)
     const int npd = (D + DEC4_ROWS - 1) / DEC4_ROWS, npf = (Fp + 7) / 8, region = (npd > npf ? npd : npf) * 2 * DEC4_NB;
     float* st_x = (mfma && a.ln_parts) ? a.ln_parts : nullptr;
-    float* st_x1 = st_x ? st_x + region : nullptr;
-    float* st_u = st_x ? st_x + 2 * region : nullptr;
+    const int G = (B + DEC4_NB - 1) / DEC4_NB;                    // groups of 16 samples (B > 16: each with a region of its own in every family)
+    float* st_x1 = st_x ? st_x + (size_t)G * region : nullptr;
+    float* st_u = st_x ? st_x + (size_t)2 * G * region : nullptr;
     int n_x = 0;                                                  // partials of x that are valid right now
     if (a.emb_table) {
-        hipLaunchKernelGGL(dec_embed_kernel, dim3(B), dim3(DEC_T), 0, st, ids, a.emb_table, a.emb_row_offset, a.emb_rows, a.x, D, st_x);
+        hipLaunchKernelGGL(dec_embed_kernel, dim3(B), dim3(DEC_T), 0, st, ids, a.emb_table, a.emb_row_offset, a.emb_rows, a.x, D, st_x, region);
         n_x = 1;
     } else if (st_x && B > DEC_BMAX) {
         // the caller embedded the ids itself (sampler + gather kernel): one small launch leaves the rows' sums where the first q rows look for them
-        hipLaunchKernelGGL(dec_rowstat_kernel, dim3(B), dim3(DEC_T), 0, st, a.x, D, st_x);
+        hipLaunchKernelGGL(dec_rowstat_kernel, dim3(B), dim3(DEC_T), 0, st, a.x, D, st_x, region);
         n_x = 1;
     }
     dec2_args g;
     memset(&g, 0, sizeof(g));
     g.B = B; g.round_bf16 = a.round_bf16; g.eps = a.eps; g.H = H; g.nsplit = a.nsplit; g.pos_dev = a.pos_dev; g.Nmax = a.Nmax; g.Fp = Fp;
+    g.gstat = region;
     // "fp16ff": FF-in / FF-out / head read W = hi + lo and keep their activations and h1 un-rounded (round_bf16 = 0 for those launches)
     const bool pl = a.W1p_lo != nullptr;
     // FF-out rows cut into four k-slices (see dec4_kernel): the matrix-core kernels with the producers' LayerNorm partials, scratch given
@@ -1512,7 +1549,7 @@ static int decode_step_t(const omlm_decode_args& a, const long long* ids, hipStr
     const bool pl = a.W1p_lo != nullptr;
     if (pl) OMLM_CHECK_ARG(a.W2p_lo && (!a.head_W || a.head_W_lo), "lo planes: all three families");
     if (a.emb_table)
-        hipLaunchKernelGGL(dec_embed_kernel, dim3(B), dim3(DEC_T), 0, st, ids, a.emb_table, a.emb_row_offset, a.emb_rows, a.x, D, (float*)nullptr);
+        hipLaunchKernelGGL(dec_embed_kernel, dim3(B), dim3(DEC_T), 0, st, ids, a.emb_table, a.emb_row_offset, a.emb_rows, a.x, D, (float*)nullptr, 0);
     for (int l = 0; l < a.L; ++l) {
         hipLaunchKernelGGL((dec_qkv_kernel<TW>), dim3((HD + 128) / DEC_ROWS), dim3(DEC_T), lds_d, st, a.x, a.attn_gamma[l],
                            (const TW*)a.Wq[l], (const TW*)a.Wkv[l], a.q, a.Kc[l], a.Vc[l], B, D, H, a.Nmax, a.pos_dev, a.eps, a.round_bf16);
@@ -1553,9 +1590,11 @@ extern "C" int OMLM_API(omlm_decode_step)(const omlm_decode_args* a, const long 
 #else
     OMLM_CHECK_ARG(a->w_dtype == 1, "the fp16 copy serves fp16 weights only");
 #endif
-    OMLM_CHECK_ARG(a->B >= 1 && a->B <= DEC4_NB, "decode batch must be 1..16");
+    OMLM_CHECK_ARG(a->B >= 1 && a->B <= DEC4_GMAX * DEC4_NB, "decode batch must be 1..64");
     OMLM_CHECK_ARG(a->B <= DEC_BMAX || (a->w_dtype != 0 && a->D == 1024 && dec4_ok(*a)),
-                   "decode batches of 9..16 run on the matrix-core kernels only: 16-bit weights, D = 1024, ln_parts given");
+                   "decode batches of 9..64 run on the matrix-core kernels only (else at most 8): 16-bit weights, D = 1024, ln_parts given");
+    OMLM_CHECK_ARG(a->B <= DEC4_NB || (a->splitk_ws && a->splitk_cnt),
+                   "decode batches of 17..64 need splitk_ws and splitk_cnt (else at most 16)");
     OMLM_CHECK_ARG(a->D % 8 == 0 && a->Fp % 8 == 0 && a->pos_dev && a->parts, "decode geometry");
     OMLM_CHECK_ARG(a->H >= 1 && a->H <= 16 && (a->H * 64 + 128) % DEC_ROWS == 0, "heads");
     OMLM_CHECK_ARG(a->nsplit * DEC_KS >= a->Nmax, "nsplit must cover Nmax keys");

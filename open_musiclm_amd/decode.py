@@ -10,6 +10,9 @@ and the two-row state of the causal depthwise convolution -- that is what :class
 
 ``step`` is one call into libomlm_hip.so (32 kernel launches: embedding gather, 5 per layer, logit head) plus the
 counter advance; the row index lives on the device so that a step can be captured into a HIP graph.
+
+A call holds ``max_batch`` samples (8, or 16 on the matrix-core step kernels); ``CachedDecoder(..., wide=True)`` holds up to
+``max_call_batch`` (64 there): groups of 16 samples ride through one launch of every step kernel, each computed as a 16-sample call.
 """
 from __future__ import annotations
 
@@ -41,7 +44,8 @@ class DecodeArgs(C.Structure):
 
 
 MAX_DECODE_HEADS = 16              # omlm_decode_step: H <= 16
-DEC4_NB = 16                       # decode.hip: samples of the matrix-core step kernels (their split-K counters are indexed by sample too)
+DEC4_NB = 16                       # decode.hip: samples of a group of the matrix-core step kernels (one MFMA column tile)
+DEC4_GMAX = 4                      # decode.hip: groups of DEC4_NB samples one call carries through every launch
 _LDS_BYTES = 150 * 1024            # omlm_decode_step: B * Fp * 4 + 1024 bytes of LDS for the first-generation step kernels (B <= 8)
 
 
@@ -57,8 +61,8 @@ def _second_generation(D: int, H: int, Fp: int) -> bool:
 
 
 def _matrix_core(B: int, D: int, H: int, Fp: int) -> bool:
-    """decode.hip dec4_ok (16-bit weights, the LayerNorm partials always given): the matrix-core step kernels."""
-    return 2 <= B <= DEC4_NB and D % 32 == 0 and D <= 1024 and H * 64 <= 1024 and Fp % 32 == 0 and Fp <= 3072
+    """decode.hip dec4_ok (16-bit weights, the LayerNorm partials and the split-K scratch always given): the matrix-core step kernels."""
+    return 2 <= B <= DEC4_GMAX * DEC4_NB and D % 32 == 0 and D <= 1024 and H * 64 <= 1024 and Fp % 32 == 0 and Fp <= 3072
 
 
 def lo_planes_ok(model, batch: int) -> bool:
@@ -83,23 +87,44 @@ def max_batch(model, precision: str) -> int:
     return max(0, min(MAX_DECODE_BATCH, (_LDS_BYTES - 1024) // (4 * max(Fp, 1))))
 
 
-def supports(model, batch: int, precision: Optional[str] = None, prompt_rows: Optional[int] = None) -> bool:
+def max_call_batch(model, precision: str) -> int:
+    """Samples one WIDE decode call holds (CachedDecoder(..., wide=True)): 64 -- four groups of 16 carried through one launch of every step
+    kernel -- where max_batch is 16 (the matrix-core kernels serve the model); max_batch everywhere else."""
+    mb = max_batch(model, precision)
+    return DEC4_GMAX * DEC4_NB if mb == DEC4_NB else mb
+
+
+def scratch_sizes(batch: int, D: int, Fp: int) -> dict:
+    """Elements of the step's scratch for a call of `batch` samples (include/omlm.h: OMLM_DECODE_LN_PARTS_B floats, OMLM_DECODE_SPLITK_FLOATS_B
+    floats, OMLM_DECODE_SPLITK_CNT_B ints): per group of 16 samples the sizes a 16-sample call has always had."""
+    G = (batch + DEC4_NB - 1) // DEC4_NB
+    tiles = (D + 15) // 16
+    return {"ln_parts": 3 * G * max(tiles, (Fp + 7) // 8) * 32,           # [family][group][partial][16 samples][2]
+            "splitk_ws": G * 4 * tiles * 256,                             # [group][tile][slice][16 rows][16 samples]
+            "splitk_cnt": max(G * tiles, batch, DEC4_NB)}                 # FF-out: per (group, tile); attention combine: per sample
+
+
+def supports(model, batch: int, precision: Optional[str] = None, prompt_rows: Optional[int] = None, wide: bool = False) -> bool:
     """Whether CachedDecoder (omlm_decode_step) serves `batch` samples of this model; where it does not, generate() re-runs the forward.
     A non-causal prefix of P rows is served only when the prompt holds all of it (prompt_rows >= P): a row i >= P sees the keys j <= i
-    alone, so the cached rows never change -- a row generated inside the prefix would change the rows before it."""
+    alone, so the cached rows never change -- a row generated inside the prefix would change the rows before it.
+    wide=True (with a precision): the sample limit is max_call_batch instead of max_batch."""
     tr = model.transformer
     limit = max_batch(model, precision) if precision is not None else min(MAX_DECODE_BATCH, max_batch(model, "bf16x3"))
+    if wide and precision is not None:
+        limit = max_call_batch(model, precision)
     P = engine.prefix_rows(tr)
     prefix_ok = P == 0 or (prompt_rows is not None and P <= prompt_rows)
     return 1 <= batch <= limit and prefix_ok and 1 <= tr.heads <= MAX_DECODE_HEADS
 
 
 class CachedDecoder:
-    def __init__(self, model, batch: int, max_rows: int, precision: str):
+    def __init__(self, model, batch: int, max_rows: int, precision: str, wide: bool = False):
         # (a non-causal prefix is checked against the prompt in prefill)
-        if not supports(model, batch, precision, prompt_rows=engine.prefix_rows(model.transformer)):
+        if not supports(model, batch, precision, prompt_rows=engine.prefix_rows(model.transformer), wide=wide):
             tr = model.transformer
-            raise ValueError(f"cached decode does not serve this model with {batch} samples per call (at most {max_batch(model, precision)} "
+            limit = max_call_batch(model, precision) if wide else max_batch(model, precision)
+            raise ValueError(f"cached decode does not serve this model with {batch} samples per call (at most {limit} "
                              f"samples, at most {MAX_DECODE_HEADS} heads; got {tr.heads} heads)")
         self.model, self.B, self.Nmax, self.precision = model, batch, int(max_rows), precision
         tr = model.transformer
@@ -177,13 +202,14 @@ class CachedDecoder:
         a.emb_table, a.emb_rows = self.emb.data_ptr(), self.emb.shape[0]
         for n in ("x", "x1", "q", "parts", "u", "logits"):
             setattr(a, n, getattr(self, n).data_ptr())
-        # per-workgroup LayerNorm partial sums of the batched step kernels (OMLM_DECODE_LN_PARTS(D, Fp) floats x 3 producers)
-        self.ln_parts = torch.zeros(3 * max((a.D + 15) // 16, (a.Fp + 7) // 8) * 32, device=self.x.device)      # [partial][16 samples][2]
+        # per-workgroup LayerNorm partial sums of the batched step kernels (OMLM_DECODE_LN_PARTS(D, Fp) floats x 3 producers x groups)
+        sizes = scratch_sizes(B, a.D, a.Fp)
+        self.ln_parts = torch.zeros(sizes["ln_parts"], device=self.x.device)      # [partial][16 samples][2] per group
         a.ln_parts = self.ln_parts.data_ptr()
         # split-K scratch of the batched FF-out launch (OMLM_DECODE_SPLITK_FLOATS): slabs + one zeroed arrival counter per 16 output rows; the
-        # attention kernel's combine counts per sample in the same array, so it holds at least DEC4_NB counters
-        self.splitk_ws = torch.empty(4 * ((a.D + 15) // 16) * 256, device=self.x.device)
-        self.splitk_cnt = torch.zeros(max((a.D + 15) // 16, DEC4_NB), dtype=torch.int32, device=self.x.device)
+        # attention kernel's combine counts per sample in the same array, so it holds at least DEC4_NB counters (B > 16: per group, and B)
+        self.splitk_ws = torch.empty(sizes["splitk_ws"], device=self.x.device)
+        self.splitk_cnt = torch.zeros(sizes["splitk_cnt"], dtype=torch.int32, device=self.x.device)
         a.splitk_ws, a.splitk_cnt = self.splitk_ws.data_ptr(), self.splitk_cnt.data_ptr()
         self.args = a
 

@@ -208,13 +208,14 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 U = torch.rand(n_new, batch, V1, device=device)
             forbid = [(not allow_eos_in_output) or (ind != Q - 1) for ind in range(Q)]
             use_graph = kwargs.pop('use_graph', False)
-            # the step kernels hold up to MAX_DECODE_BATCH samples per call: larger batches run as consecutive groups (samples are
-            # independent; every group streams the weights once per id)
+            # a decode call holds up to decode.max_call_batch samples (64 on the matrix-core step kernels, which carry four groups of 16
+            # through every launch): larger batches run as consecutive calls (samples are independent; every call streams the weights
+            # once per id)
             pieces = []
-            group = decode.max_batch(self.transformer, self.transformer._precision())
+            group = decode.max_call_batch(self.transformer, self.transformer._precision())
             for b0 in range(0, batch, group):
                 b1 = min(batch, b0 + group)
-                dec = decode.CachedDecoder(self.transformer, b1 - b0, rows, self.transformer._precision())
+                dec = decode.CachedDecoder(self.transformer, b1 - b0, rows, self.transformer._precision(), wide=True)
                 last = dec.prefill([t[b0:b1] for t in cond] + [sampled[b0:b1]])
                 loop = decode.SamplingLoop(dec, last, U[:, b0:b1].contiguous(), n0, n_new, k, temperature, forbid, use_graph=use_graph)
                 pieces.append(loop.run().t())                      # [b, n_new]
@@ -508,12 +509,31 @@ def _windows(t: torch.Tensor, size: int, step: int):
     return [t[:, i * step: i * step + size] for i in range(max(n, 0))]
 
 
+def _stack_windows(windows: List[torch.Tensor]) -> torch.Tensor:
+    """W windows [B, ...] -> [W * B, ...] along the batch axis: window w of sample b is row w * B + b."""
+    return torch.cat(list(windows), dim=0)
+
+
+def _unstack_windows(stacked: torch.Tensor, n_windows: int) -> List[torch.Tensor]:
+    """Inverse of _stack_windows: [W * B, ...] -> W tensors [B, ...] in window order."""
+    assert n_windows > 0 and stacked.shape[0] % n_windows == 0, (stacked.shape, n_windows)
+    return list(stacked.split(stacked.shape[0] // n_windows, dim=0))
+
+
 class MusicLM(nn.Module):
     """open_musiclm.py:818-1071: hierarchical semantic -> coarse -> fine sliding-window decode.
 
     Extensions over the reference signature (all optional, defaults reproduce the reference):
       clap_token_ids  -- bypass the CLAP text tower with pre-quantised conditioning ids (synthetic benchmarks);
-      return_tokens   -- return (semantic, coarse, fine) id tensors instead of decoding a waveform.
+      return_tokens   -- return (semantic, coarse, fine) id tensors instead of decoding a waveform;
+      fine_windows_together -- a permission, not a demand: where the fine windows do not depend on each other (no overlap, i.e.
+                         fine_sliding_window_step_percent == 1, and no primed fine ids) they may be generated in ONE fine.generate call,
+                         stacked along the batch axis (window w of prompt b is sample w * B + b; a decode call carries up to
+                         decode.max_call_batch samples), instead of one call per window.  Everywhere else the flag changes nothing
+                         and the windows run one after the other.  Each sample sees the same conditioning either way, but the default
+                         random stream is consumed in a different order (one [steps, W * B, V] draw instead of W draws of
+                         [steps, B, V]), so sampled ids differ from the sequential call's unless the uniforms are injected.
+                         Default False: the reference's call-by-call structure.
     ``generate`` is an alias of ``forward``."""
 
     def __init__(self, *, wav2vec=None, clap=None, neural_codec=None, semantic_transformer: TokenConditionedTransformer,
@@ -538,7 +558,7 @@ class MusicLM(nn.Module):
                 semantic_steps_per_second=50, acoustic_steps_per_second=75, return_coarse_generated_wave=False,
                 mask_out_generated_fine_tokens=False, semantic_sliding_window_step_percent=0.5,
                 coarse_sliding_window_step_percent=0.5, fine_sliding_window_step_percent=1,
-                clap_token_ids=None, return_tokens=False):
+                clap_token_ids=None, return_tokens=False, fine_windows_together=False):
         if not exists(clap_token_ids):
             assert exists(text), 'text needs to be passed in if one of the transformer requires conditioning'
             clap_token_ids = get_or_compute_clap_token_ids(None, self.clap, conditioning_audio=None, conditioning_text=text)
@@ -605,7 +625,16 @@ class MusicLM(nn.Module):
         fwin = int(fine_window_seconds * ac_hz)
         fstep = int(fwin * fine_sliding_window_step_percent)
         fine = None
-        for coarse_win in _windows(coarse, fwin, fstep):
+        coarse_wins = _windows(coarse, fwin, fstep)
+        if fine_windows_together and fstep == fwin and not exists(prime_fine) and len(coarse_wins) > 1:
+            # independent windows (all coarse ids are known, keep == 0, no fine conditioning): one call over W * B samples
+            pred = self.fine.generate(clap_token_ids=clap_token_ids.repeat(len(coarse_wins), *([1] * (clap_token_ids.dim() - 1))),
+                                      coarse_token_ids=_stack_windows(coarse_wins), fine_token_ids=None,
+                                      max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4)
+            fine = torch.cat(_unstack_windows(pred, len(coarse_wins)), dim=1)
+            coarse_wins = []
+        for coarse_win in coarse_wins:
             if exists(fine):
                 keep = int(fwin * (1 - fine_sliding_window_step_percent))
                 cond_fine = fine[:, -keep:] if keep > 0 else None
