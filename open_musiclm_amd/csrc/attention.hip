@@ -19,6 +19,7 @@
 //   * T = float inputs select the bf16x3 split (hi*hi + hi*lo + lo*hi) for the forward; the backward
 //     kernels always run single-pass bf16 MFMA with fp32 accumulation.
 #include "common.h"
+#include "attn_plan.h"
 #include <stdlib.h>
 
 namespace OMLM_NS {
@@ -980,109 +981,35 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 }
 
 // =============================================================================================================
-static size_t fwd_lds(int N, bool precise, int off = 0) { return (size_t)(precise ? 4 : 2) * TKV * 128 + (size_t)4 * ((N + TQ - 1) / TQ * TQ + off) * sizeof(float); }
-static size_t dq_lds(int N, bool precise = false, int off = 0) { return (size_t)(precise ? 5 : 3) * TKV * 128 + (size_t)8 * ((N + TQ - 1) / TQ * TQ + off) * sizeof(float) + (size_t)8 * ((N + TKV - 1) / TKV + 1); }
+// Host side.  csrc/attn_plan.h decides what a call runs -- kernels, grids, LDS bytes -- or why it is refused; the entry points below check
+// their arguments, ask for the plan and launch its list.
+using omlm_plan::AttnCall;
+using omlm_plan::AttnLaunch;
+using omlm_plan::AttnPlan;
+static_assert(omlm_plan::ATTN_UNSUPPORTED == OMLM_ERR_UNSUPPORTED && TQ == 32 && TKV == 64, "attn_plan.h states the return code and the first-generation tiles");
 
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {
-    if (bytes > 160 * 1024) { omlm_set_error("attention: sequence too long for the LDS-resident bias table"); return OMLM_ERR_UNSUPPORTED; }
-    if (bytes > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    return OMLM_OK;
-}
+// attention2.hip / attention3.hip: one launch of the plan each
+void attn2_fwd_launch(const AttnLaunch& l, int ldT, const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
+                      void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop& dr, int Pn);
+void attn2_bwd_dq_launch(const AttnLaunch& l, int ldT, const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
+                         const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dbias, int bias_ld,
+                         float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop& dr, int Pn);
+extern "C" __attribute__((visibility("hidden"))) void omlm_attn_dbias_reduce_launch(const AttnLaunch* l, const float* dpart, float* dbias, int bias_ld, int B, int N, int H, void* stream);   // (bf16 copy)
+void attn3_bwd_dkv_launch(const AttnLaunch& l, int ldT, const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
+                          const void* dout, const float* lse, const float* delta, float* dk, float* dv,
+                          int B, int N, int H, float scale, hipStream_t st, const AttnDrop& dr, int Pn, float* part);
 
-int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
-                     void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn);   // attention2.hip
+#define A1_LAUNCH(KERNEL, T, ...)                                                                                                        \
+    with_flags(l.drop, l.pfx, [&](auto D, auto P) {                                                                                      \
+        launch_lds_cap<KERNEL<T, decltype(D)::value, decltype(P)::value>>(dim3(l.gx, l.gy, l.gz), dim3(l.threads), l.lds, st, __VA_ARGS__); \
+    })
 
-bool attn2_prefix_fits(int N, int Pn);      // attention2.hip: whether the second-generation kernels serve a prefix of Pn rows at N
-
-// ---- how many positions per sample the kernels take ------------------------------------------------------------------------------------
-// 16-bit operands, causal, with the prepared table or no bias: OMLM_ATTN_NL (4096 < N runs the long forms of attention2.hip / attention3.hip).
-// Everything else past N = 4096 -- fp32 operands ("bf16x3") at any N, a non-causal prefix, a raw table without its prepared form -- runs the
-// first-generation kernels, which keep the bias table in LDS: the largest N that fits the forward / the dQ kernel (the dK / dV kernel stages
-// H columns where it has no prepared table to read by windows: H (ceil32(N) + 31) floats + 33 KiB, checked per call).
-static int attn1_limit(bool precise, bool backward, int P) {
-    int n = 32;
-    for (int N = 32; N <= 4 * OMLM_ATTN_NL; N += 32) {
-        const int off = P > 0 ? (P < N ? P : N) - 1 : 0;
-        if ((backward ? dq_lds(N, precise, off) : fwd_lds(N, precise, off)) > 160 * 1024) break;
-        n = N;
-    }
-    return n;
-}
 #if !OMLM_FP16
 // include/omlm.h
-extern "C" int omlm_attn_max_positions(int dtype, int P) {
-    if (P < 0) return 0;
-    if (dtype == OMLM_DT_F32) return attn1_limit(true, true, P);
-    if (dtype != OMLM_DT_BF16 && dtype != OMLM_DT_F16) return 0;
-    if (P == 0) return OMLM_ATTN_NL;
-    const int l1 = attn1_limit(false, true, P);
-    return l1 > 4096 ? l1 : 4096;
-}
+extern "C" int omlm_attn_max_positions(int dtype, int P) { return omlm_plan::attn_max_positions(dtype, P); }
 #endif
-// Refusals that name their reason, before anything is launched.  dtype: as this copy sees it (1: its 16-bit type).
-static int attn_positions_check(const char* what, int dtype, int N, int P, int H, bool raw_table_only, bool backward) {
-    char buf[400];
-    const char* dir = backward ? "backward" : "forward alone";
-    if (dtype == 0) {
-        const int lim = attn1_limit(true, backward, P);
-        if (N <= lim) return OMLM_OK;
-        snprintf(buf, sizeof(buf), "%s: N = %d positions per sample with fp32 operands (bf16x3): their kernels keep the bias table in LDS and take "
-                 "N <= %d (%s; omlm_attn_max_positions); bf16 / fp16 operands take N <= %d", what, N, lim, dir, OMLM_ATTN_NL);
-    } else {
-        if (N <= 4096) return OMLM_OK;
-        if (P > 0 || raw_table_only) {                         // first-generation kernels, as far as they reach
-            const int lim = attn1_limit(false, backward, P);
-            const bool staged = !backward || 32 * 1024 + (size_t)H * ((N + TQ - 1) / TQ * TQ + (P > 0 ? 31 : 0)) * sizeof(float) + 1024 <= 160 * 1024;
-            if (N <= lim && staged) return OMLM_OK;
-            if (P > 0)
-                snprintf(buf, sizeof(buf), "%s: N = %d positions per sample with a non-causal prefix (P = %d): past N = 4096 a prefix runs the "
-                         "first-generation kernels, whose LDS-resident bias tables take N <= %d (%s) and, in the backward, H (N + 31) <= 31000 "
-                         "(H = %d); the long forms (4096 < N <= %d) are causal", what, N, P, lim, dir, H, OMLM_ATTN_NL);
-            else
-                snprintf(buf, sizeof(buf), "%s: N = %d > 4096 positions per sample needs the prepared table (biasT, omlm_attn_bias_prepare) next "
-                         "to bias; with the raw table alone N <= %d (%s) and, in the backward, H N <= 31000 (H = %d)", what, N, lim, dir, H);
-        } else if (N > OMLM_ATTN_NL)
-            snprintf(buf, sizeof(buf), "%s: N = %d positions per sample is past the limit of %d (omlm_attn_max_positions)", what, N, OMLM_ATTN_NL);
-        else return OMLM_OK;
-    }
-    omlm_set_error(buf);
-    return OMLM_ERR_UNSUPPORTED;
-}
 
-// Pn = min(P, N): 0 is causal, >= 1 the non-causal prefix of include/omlm.h.  bias: the rel = 0 row of the [N + Pn - 1, bias_ld] table (or
-// null).  drop: null for p == 0.
-static int attn_fwd_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                         const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale,
-                         int bias_ld, int dtype, int Pn, void* stream, const AttnDrop* drop) {
-    // 16-bit operands with the prepared table, or without any bias: attention2.hip (a prefix only while attn2_prefix_fits)
-    if (dtype == 1 && (biasT || !bias) && (Pn == 0 || attn2_prefix_fits(N, Pn)))
-        return attn2_fwd_launch(q, k, v, biasT, keymask, out, lse, B, N, H, scale, as_stream(stream), drop, Pn);
-    dim3 grid((N + TQ - 1) / TQ, (H + 3) / 4, B), block(AT_THREADS);
-    const int off = Pn > 0 ? Pn - 1 : 0;
-    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
-    const AttnDrop& dr = drop ? *drop : nd;
-    int rc;
-    if (dtype == 0) {
-#if OMLM_FP16
-        omlm_set_error("omlm_mqa_attn_fwd: fp32 operands are served by the bf16 copy of the library");
-        return OMLM_ERR_UNSUPPORTED;
-#else
-        const size_t lds = fwd_lds(N, true, off);
-        auto kern = Pn > 0 ? (drop ? attn_fwd_kernel<float, true, true> : attn_fwd_kernel<float, false, true>)
-                           : (drop ? attn_fwd_kernel<float, true> : attn_fwd_kernel<float, false>);
-        if ((rc = set_lds(kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const float*)q, (const float*)k, (const float*)v, bias, keymask, (float*)out, lse, B, N, H, scale, bias_ld, dr, Pn);
-#endif
-    } else {
-        const size_t lds = fwd_lds(N, false, off);
-        auto kern = Pn > 0 ? (drop ? attn_fwd_kernel<h16_t, true, true> : attn_fwd_kernel<h16_t, false, true>)
-                           : (drop ? attn_fwd_kernel<h16_t, true> : attn_fwd_kernel<h16_t, false>);
-        if ((rc = set_lds(kern, lds))) return rc;
-        hipLaunchKernelGGL(kern, grid, block, lds, as_stream(stream), (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (h16_t*)out, lse, B, N, H, scale, bias_ld, dr, Pn);
-    }
-    return omlm_post_launch("omlm_mqa_attn_fwd");
-}
+static const AttnDrop NO_DROP = {0ull, nullptr, 0u, 1.0f};
 
 // include/omlm.h.  dtype: 0 = fp32 ("bf16x3"), 1 = bf16, 2 = fp16 (forwarded to the fp16 copy of this file; common.h)
 #if !OMLM_FP16
@@ -1103,100 +1030,28 @@ extern "C" int OMLM_API(omlm_mqa_attn_fwd)(const void* q, const void* k, const v
     if (B <= 0 || N <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
     OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
-    const int Pn = P < N ? P : N;
-    if (int rc = attn_positions_check("omlm_mqa_attn_fwd", dtype, N, P, H, bias && !biasT, false)) return rc;
-    return attn_fwd_impl(q, k, v, bias && Pn > 0 ? bias + (size_t)(Pn - 1) * bias_ld : bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld,
-                         dtype, Pn, stream, p > 0.f ? &d : nullptr);
-}
-
-// dq [B*N, H*64] fp32, dk, dv [B*N, 64] fp32 (overwritten), dbias [N, bias_ld] fp32 (accumulated, +=), delta [B, H, N] scratch
-int attn2_bwd_dq_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
-                        const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dbias, int bias_ld,
-                        float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn);   // attention2.hip
-extern "C" __attribute__((visibility("hidden"))) int omlm_attn_dbias_reduce_launch(const float* dpart, float* dbias, int bias_ld, int B, int N, int H, void* stream);   // attention2.hip (bf16 copy)
-
-int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
-                         const void* dout, const float* lse, const float* delta, float* dk, float* dv,
-                         int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn, float* part);      // attention3.hip
-long long attn3_part_floats(int B, int N);                                                                       // attention3.hip
-
-// Pn, bias, drop as in attn_fwd_impl; dbias: the rel = 0 row of its table.  d(bias) of rel >= 0 goes through the workspace and its
-// reduction, that of rel < 0 (Pn > 1) by atomics from the dQ kernel.
-static int attn_bwd_impl(const void* q, const void* k, const void* v, const float* bias, const float* biasT,
-                         const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta,
-                         float* dq, float* dk, float* dv, float* dbias, float* dbias_ws,
-                         int B, int N, int H, float scale, int bias_ld, int dtype, int Pn, void* stream, const AttnDrop* drop) {
-    dim3 gridq((N + TQ - 1) / TQ, (H + 3) / 4, B), gridk((N + 31) / 32, 1, B), block(AT_THREADS);
-    const int off = Pn > 0 ? Pn - 1 : 0;
-    // first-generation dK / dV: every head's bias column is staged in LDS (a prefix: with up to 31 negative distances in front; see
-    // attn_bwd_dkv_kernel).  The causal kernel reads the prepared table by windows instead where staging would cost occupancy (> 80 KiB: one
-    // workgroup per CU): below that the staged form measured 2 % faster (B=32, N=1116, H=8: 656 vs 670 us), above it 16 % slower (B=8, N=1817, H=16)
-    const size_t ldsk_staged = 32 * 1024 + (size_t)H * ((N + TQ - 1) / TQ * TQ + (Pn > 0 ? 31 : 0)) * sizeof(float) + 1024;
-    const bool win = Pn == 0 && biasT != nullptr && ldsk_staged > 80 * 1024;
-    const int ldT = Pn == 0 ? ((64 + N + 2 * 128 + 3) / 4) * 4 : 0;       // layout of omlm_attn_bias_prepare (attention2.hip)
-    const size_t ldsq = dq_lds(N, dtype == 0, off);
-    const size_t ldsk = win ? 32 * 1024 + 4 * 128 * sizeof(float)
-                            : ldsk_staged;
-    int rc;
+    const AttnCall c = {false, dtype == 0, OMLM_FP16 != 0, B, N, H, P, bias != nullptr, biasT != nullptr, false, false, p > 0.f, false};
+    const AttnPlan plan = omlm_plan::attn_plan(c);
+    if (plan.rc) { omlm_set_error(plan.msg); return plan.rc; }
+    // Pn = min(P, N): 0 is causal, >= 1 the non-causal prefix of include/omlm.h.  The kernels take the rel = 0 row of the [N + Pn - 1, bias_ld] table.
+    const int Pn = omlm_plan::attn_prefix_rows(N, P);
+    if (bias && Pn > 0) bias += (size_t)(Pn - 1) * bias_ld;
+    const AttnDrop& dr = p > 0.f ? d : NO_DROP;
     hipStream_t st = as_stream(stream);
-    float* dpart = dbias ? dbias_ws : nullptr;      // per-(sample, head, query tile) d(bias) rows, summed by attn_dbias_reduce_launch below
-    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
-    const AttnDrop& dr = drop ? *drop : nd;
-    if (dtype == 0) {
-#if OMLM_FP16
-        omlm_set_error("omlm_mqa_attn_bwd: fp32 operands are served by the bf16 copy of the library");
-        return OMLM_ERR_UNSUPPORTED;
-#else
-        auto kq = Pn > 0 ? (drop ? attn_bwd_dq_precise_kernel<float, true, true> : attn_bwd_dq_precise_kernel<float, false, true>)
-                         : (drop ? attn_bwd_dq_precise_kernel<float, true> : attn_bwd_dq_precise_kernel<float, false>);
-        auto kk = Pn > 0 ? (drop ? attn_bwd_dkv_kernel<float, true, true> : attn_bwd_dkv_kernel<float, false, true>)
-                         : (drop ? attn_bwd_dkv_kernel<float, true> : attn_bwd_dkv_kernel<float, false>);
-        if ((rc = set_lds(kq, ldsq))) return rc;
-        if ((rc = set_lds(kk, ldsk))) return rc;
-        hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)out, (const float*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
-        if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
-        hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr, Pn);
+    for (int i = 0; i < plan.n; ++i) {
+        const AttnLaunch& l = plan.l[i];
+        if (l.family == omlm_plan::ATTN_A4_FWD) attn2_fwd_launch(l, plan.ldT, q, k, v, biasT, keymask, out, lse, B, N, H, scale, st, dr, Pn);
+#if !OMLM_FP16
+        else if (l.precise) A1_LAUNCH(attn_fwd_kernel, float, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (float*)out, lse, B, N, H, scale, bias_ld, dr, Pn);
 #endif
-    } else {
-        auto kq = Pn > 0 ? (drop ? attn_bwd_dq_kernel<h16_t, true, true> : attn_bwd_dq_kernel<h16_t, false, true>)
-                         : (drop ? attn_bwd_dq_kernel<h16_t, true> : attn_bwd_dq_kernel<h16_t, false>);
-        auto kk = Pn > 0 ? (drop ? attn_bwd_dkv_kernel<h16_t, true, true> : attn_bwd_dkv_kernel<h16_t, false, true>)
-                         : (drop ? attn_bwd_dkv_kernel<h16_t, true> : attn_bwd_dkv_kernel<h16_t, false>);
-        // The prepared table (or no bias): attention2.hip's dQ kernel (8 heads per workgroup sharing LDS-DMA-staged K / V tiles) and attention3.hip's
-        // dK / dV kernel (128 keys per workgroup, Q / dO staged once per workgroup by LDS-DMA).  With the Horner diagonal sums and the d(bias)
-        // workspace the dQ kernel is the faster one at both bench shapes (B=32, N=1116, H=8: whole backward 432 against 456 us; before those two
-        // changes both kernels spent ~160 us per layer in d(bias) and the first-generation kernel led 316 : 334).  Causal: each falls back to
-        // its first-generation kernel where its plan does not fit (launcher result 1).  A prefix runs them iff attn2_prefix_fits -- the
-        // forward's test, whose lse is relative to the table's reference point there -- so a "does not fit" is an error, not a fallback.
-        const bool gen2 = (biasT || !bias) && (Pn == 0 || attn2_prefix_fits(N, Pn));
-        // N > 4096, causal, with the prepared table or no bias: the long dQ kernel, and with a workspace the dK / dV kernel's slot form -- its slots
-        // follow the d(bias) rows in the workspace (omlm_mqa_attn_bwd_workspace_bytes).  Where the dK / dV kernel's 32-bit offsets refuse the
-        // shape, the first-generation kernel takes over in its windowed mode, which needs the prepared table: refused HERE, before dQ runs.
-        const bool lng = N > 4096 && gen2 && Pn == 0;
-        const long long nqt_ = (N + 31) / 32;
-        float* dkv_part = lng && dbias_ws ? dbias_ws + (size_t)B * H * nqt_ * nqt_ * 32 : nullptr;
-        if (lng && !win && (long long)B * N * H * 128 >= (1ll << 32)) {
-            omlm_set_error("omlm_mqa_attn_bwd: B N H >= 2^25 with N > 4096 and no prepared table (biasT) is not served: the dK / dV kernel addresses q "
-                           "and dout with 32-bit byte offsets (B N H 128 < 2^32), and the windowed first-generation kernel behind it reads biasT -- "
-                           "pass the prepared table (an all-zero one, omlm_attn_bias_prepare with bias = NULL, where there is no bias) or split the batch");
-            return OMLM_ERR_UNSUPPORTED;
-        }
-        if (!(lng && !win) && (Pn == 0 || !gen2) && (rc = set_lds(kk, ldsk))) return rc;
-        int r = gen2 ? attn2_bwd_dq_launch(q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, drop, Pn) : 1;
-        if (r < 0 || (r > 0 && gen2 && Pn > 0)) return r < 0 ? r : OMLM_ERR_UNSUPPORTED;
-        if (r > 0) {
-            if ((rc = set_lds(kq, ldsq))) return rc;
-            hipLaunchKernelGGL(kq, gridq, block, ldsq, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
-        }
-        if (dpart && (rc = omlm_attn_dbias_reduce_launch(dpart, dbias, bias_ld, B, N, H, st))) return rc;
-        r = gen2 ? attn3_bwd_dkv_launch(q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, drop, Pn, dkv_part) : 1;
-        if (r < 0 || (r > 0 && gen2 && Pn > 0)) return r < 0 ? r : OMLM_ERR_UNSUPPORTED;
-        if (r > 0)
-            hipLaunchKernelGGL(kk, gridk, block, ldsk, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, win ? biasT : nullptr, ldT, dr, Pn);
+        else A1_LAUNCH(attn_fwd_kernel, h16_t, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (h16_t*)out, lse, B, N, H, scale, bias_ld, dr, Pn);
+        if (int rc = omlm_post_launch("omlm_mqa_attn_fwd")) return rc;
     }
-    return omlm_post_launch("omlm_mqa_attn_bwd");
+    return OMLM_OK;
 }
 
+// dq [B*N, H*64] fp32, dk, dv [B*N, 64] fp32 (overwritten), dbias [N, bias_ld] fp32 (accumulated, +=), delta [B, H, N] scratch.
+// d(bias) of rel >= 0 goes through the workspace and its reduction, that of rel < 0 (Pn > 1) by atomics from the dQ kernel.
 #if !OMLM_FP16
 extern "C" int omlm_mqa_attn_bwd_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
                                    const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
@@ -1218,11 +1073,47 @@ extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const v
     if (B <= 0 || N <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(q && k && v && out && dout && lse && delta && dq && dk && dv, "null pointer");
     OMLM_CHECK_ARG(H >= 1 && ((!bias && !dbias) || bias_ld >= H), "heads / bias pitch");
-    const int Pn = P < N ? P : N;
-    const size_t r0 = Pn > 0 ? (size_t)(Pn - 1) * bias_ld : 0;
-    if (int rc = attn_positions_check("omlm_mqa_attn_bwd", dtype, N, P, H, bias && !biasT, true)) return rc;
-    return attn_bwd_impl(q, k, v, bias ? bias + r0 : nullptr, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias ? dbias + r0 : nullptr,
-                         dbias_ws, B, N, H, scale, bias_ld, dtype, Pn, stream, p > 0.f ? &d : nullptr);
+    const AttnCall c = {true, dtype == 0, OMLM_FP16 != 0, B, N, H, P, bias != nullptr, biasT != nullptr, dbias != nullptr, dbias_ws != nullptr, p > 0.f,
+                        dv == dk + (size_t)B * N * 64};
+    const AttnPlan plan = omlm_plan::attn_plan(c);
+    if (plan.rc) { omlm_set_error(plan.msg); return plan.rc; }
+    const int Pn = omlm_plan::attn_prefix_rows(N, P);
+    const size_t r0 = Pn > 0 ? (size_t)(Pn - 1) * bias_ld : 0;      // bias, dbias: the rel = 0 row of their tables
+    if (bias) bias += r0;
+    if (dbias) dbias += r0;
+    float* dpart = dbias ? dbias_ws : nullptr;      // per-(sample, head, query tile) d(bias) rows, summed by the reduction
+    float* dkv_part = plan.dkv_slots >= 0 ? dbias_ws + plan.dkv_slots : nullptr;
+    const AttnDrop& dr = p > 0.f ? d : NO_DROP;
+    hipStream_t st = as_stream(stream);
+    for (int i = 0; i < plan.n; ++i) {
+        const AttnLaunch& l = plan.l[i];
+        switch (l.family) {
+        case omlm_plan::ATTN_A2_DQ:
+            attn2_bwd_dq_launch(l, plan.ldT, q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, dr, Pn);
+            break;
+        case omlm_plan::ATTN_A1_DQ:
+#if !OMLM_FP16
+            if (l.precise) A1_LAUNCH(attn_bwd_dq_precise_kernel, float, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)out, (const float*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
+            else
+#endif
+            A1_LAUNCH(attn_bwd_dq_kernel, h16_t, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
+            break;
+        case omlm_plan::ATTN_DBIAS_REDUCE:
+            omlm_attn_dbias_reduce_launch(&l, dpart, dbias, bias_ld, B, N, H, st);
+            break;
+        case omlm_plan::ATTN_A1_DKV:
+#if !OMLM_FP16
+            if (l.precise) A1_LAUNCH(attn_bwd_dkv_kernel, float, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, l.win ? biasT : nullptr, plan.ldT, dr, Pn);
+            else
+#endif
+            A1_LAUNCH(attn_bwd_dkv_kernel, h16_t, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, l.win ? biasT : nullptr, plan.ldT, dr, Pn);
+            break;
+        default:
+            attn3_bwd_dkv_launch(l, plan.ldT, q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, dr, Pn, dkv_part);
+        }
+        if (int rc = omlm_post_launch("omlm_mqa_attn_bwd")) return rc;
+    }
+    return OMLM_OK;
 }
 
 }   // namespace OMLM_NS

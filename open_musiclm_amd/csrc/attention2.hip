@@ -14,6 +14,7 @@
 //   * the rel-pos bias is read from a per-tile window (LDS, 128 floats per head) with compile-time offsets from one lane base.
 // The arithmetic per score is: fma (scale * log2 e, bias), max, subtract, exp2, pack -- everything else is on the matrix cores.
 #include "common.h"
+#include "attn_plan.h"
 
 namespace OMLM_NS {
 
@@ -26,6 +27,8 @@ namespace OMLM_NS {
 #define A2_STAGE (8192 + 8192 + 8 * A2_BWIN * 4)     /* K rows | V blocked | bias window = 20 KiB */
 #define A2_NST 3
 #define A2_NL OMLM_ATTN_NL    /* most positions per sample of the long forms (4096 < N <= A2_NL: attn4_fwd_long_kernel, attn2_bwd_dq_long_kernel) */
+static_assert(A2_PAD == omlm_plan::ATTN_PAD && A2_BWIN == omlm_plan::ATTN_BWIN && A2_NST * A2_STAGE == omlm_plan::A4_RING,
+              "attn_plan.h states the prepared table's layout and the forward's ring");
 
 #define MFMA16(a, b, c) OMLM_MFMA_32x32x16(a, b, c)
 
@@ -402,63 +405,30 @@ struct A4Stager {
 #undef A2Q_KERNEL
 #undef A2Q_LONG
 
-static size_t a2_dq_lds(int N, int off) {
-    const int nqt = (N + 31) / 32, npad = (N + 63) / 64 * 64;
-    return (size_t)A2_NST * A2B_STAGE + 4096 + (size_t)npad * 4 + (size_t)8 * (nqt * 32 + off) * 4;
-}
-// the non-causal prefix runs forward and backward on the second-generation kernels (prepared table) iff their plans fit: the dQ kernel's LDS
-// (it grows by the Pn - 1 negative-distance bins), the forward's N <= 4096 and the dK / dV kernel's N >= 32; else on attention.hip's
-bool attn2_prefix_fits(int N, int Pn) {
-    return N >= 32 && N <= 4096 && a2_dq_lds(N, Pn - 1) <= 160 * 1024;
-}
+static_assert(A2_NST * A2B_STAGE == omlm_plan::A2Q_RING && A2_BINW == omlm_plan::A2Q_BINW, "attn_plan.h states the dQ kernel's ring and bins");
 
-int attn2_bwd_dq_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
-                        const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dbias, int bias_ld,
-                        float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn) {
-    const int off = Pn > 0 ? Pn - 1 : 0;                       // Pn > 0: the non-causal prefix (PFX instances)
-    const int ldT = (A2_PAD + off + N + 2 * A2_BWIN + 3) / 4 * 4;
-    const int nqt = (N + 31) / 32, ny = (H + 7) / 8;
-    if (N > 4096) {                                            // the long form (the entry points have refused N > A2_NL and a prefix)
-        if (N > A2_NL || Pn > 0) return OMLM_ERR_UNSUPPORTED;
-        const size_t ldsl = (size_t)A2_NST * A2B_STAGE + 4096 + 8 * A2_BINW * 4 + (size_t)((N + 63) / 64 * 64);
-        static bool a1l = false;
-        if (!a1l) {
-            (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_long_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_long_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            a1l = true;
-        }
-        const AttnDrop ndl = {0ull, nullptr, 0u, 1.0f};
-        auto kernl = drop ? attn2_bwd_dq_long_kernel<true> : attn2_bwd_dq_long_kernel<false>;
-        hipLaunchKernelGGL(kernl, dim3(nqt * ny * B), dim3(A2_THREADS), ldsl, st,
-                           (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta,
-                           dq, dbias, bias_ld, dpart, B, N, H, scale, drop ? *drop : ndl, 0);
-        return omlm_post_launch("omlm_mqa_attn_bwd");
-    }
-    const size_t lds = a2_dq_lds(N, off);
-    if (lds > 160 * 1024) return 1;                            // caller falls back to the first-generation kernel
-    static bool a1 = false;
-    if (!a1) {
-        (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn2_bwd_dq_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        a1 = true;
-    }
-    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
-    auto kern = Pn > 0 ? (drop ? attn2_bwd_dq_kernel<true, true> : attn2_bwd_dq_kernel<false, true>)
-                       : (drop ? attn2_bwd_dq_kernel<true> : attn2_bwd_dq_kernel<false>);
-    hipLaunchKernelGGL(kern, dim3(nqt * ny * B), dim3(A2_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask,
-                       (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, drop ? *drop : nd, Pn);
-    return omlm_post_launch("omlm_mqa_attn_bwd");
+// one ATTN_A2_DQ launch of the plan (Pn > 0: the non-causal prefix's PFX instances; the long form is causal)
+void attn2_bwd_dq_launch(const omlm_plan::AttnLaunch& l, int ldT, const void* q, const void* k, const void* v, const float* biasT,
+                         const unsigned char* keymask, const void* out, const void* dout, const float* lse, float* delta, float* dq,
+                         float* dbias, int bias_ld, float* dpart, int B, int N, int H, float scale, hipStream_t st, const AttnDrop& dr, int Pn) {
+    auto go = [&](auto launch) {
+        launch(dim3(l.gx), dim3(l.threads), l.lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (const h16_t*)out,
+               (const h16_t*)dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, dr, Pn);
+    };
+    if (l.form == omlm_plan::ATTN_FORM_LONG) {
+        if (l.drop) go([](auto... a) { launch_lds_cap<attn2_bwd_dq_long_kernel<true>>(a...); });
+        else go([](auto... a) { launch_lds_cap<attn2_bwd_dq_long_kernel<false>>(a...); });
+    } else
+        with_flags(l.drop, l.pfx, [&](auto D, auto P) {
+            go([](auto... a) { launch_lds_cap<attn2_bwd_dq_kernel<decltype(D)::value, decltype(P)::value>>(a...); });
+        });
 }
 
 #if !OMLM_FP16      /* the bias table is fp32 in every precision: prepared by the bf16 copy of this file */
 // -------------------------------------------------------------------------------------------------------------------------
 // the prepared table of a prefix of P rows (0: causal): the min(P, N) - 1 negative distances in front of the causal layout
 extern "C" long long omlm_attn_bias_table_floats(int N, int H, int P) {
-    const int off = P > 0 ? (P < N ? P : N) - 1 : 0;
-    const int ldT = (A2_PAD + off + N + 2 * A2_BWIN + 3) / 4 * 4, H8 = (H + 7) / 8 * 8;
-    return (long long)H8 * ldT;
+    return omlm_plan::attn_bias_table_floats(N, H, P);
 }
 
 // biasT: omlm_attn_bias_table_floats(N, H, 0) floats.  bias may be null (no rel-pos bias).  q_scale / k_scale (64 floats each, optional):
@@ -470,7 +440,7 @@ extern "C" int omlm_attn_bias_prepare(const float* bias, float* biasT, int N, in
                                       const float* k_scale, float qk_bound, float scale, int p_max_log2, void* stream) {
     OMLM_CHECK_ARG(biasT && N > 0 && H > 0, "null table / sizes");
     OMLM_CHECK_ARG(p_max_log2 == 0 || p_max_log2 == 15, "p_max_log2: 0 (bf16 / fp32 operands) or 15 (half operands)");
-    const int ldT = (A2_PAD + N + 2 * A2_BWIN + 3) / 4 * 4, H8 = (H + 7) / 8 * 8;
+    const int ldT = omlm_plan::attn_ldT(N, 0), H8 = (H + 7) / 8 * 8;
     A2PrepGroup grp;
     memset(&grp, 0, sizeof(grp));
     grp.out[0] = biasT; grp.qs[0] = q_scale; grp.ks[0] = k_scale;
@@ -490,9 +460,9 @@ extern "C" int omlm_attn_bias_prepare_group(const float* bias, float* const* bia
     OMLM_CHECK_ARG(biasT && N > 0 && H > 0, "null table / sizes");
     OMLM_CHECK_ARG(p_max_log2 == 0 || p_max_log2 == 15, "p_max_log2: 0 (bf16 / fp32 operands) or 15 (half operands)");
     OMLM_CHECK_ARG((q_scale == nullptr) == (k_scale == nullptr), "q_scale and k_scale: both or neither");
-    const int off = P > 0 ? (P < N ? P : N) - 1 : 0;
+    const int off = omlm_plan::attn_prefix_off(N, P);
     if (bias && off > 0) bias += (size_t)off * bias_ld;      // the kernel reads rows -off .. N - 1 around the rel = 0 row
-    const int ldT = (A2_PAD + off + N + 2 * A2_BWIN + 3) / 4 * 4, H8 = (H + 7) / 8 * 8;
+    const int ldT = omlm_plan::attn_ldT(N, P), H8 = (H + 7) / 8 * 8;
     for (int base = 0; base < layers; base += A2_PREP_MAX) {
         const int n = layers - base < A2_PREP_MAX ? layers - base : A2_PREP_MAX;
         A2PrepGroup grp;
@@ -534,21 +504,11 @@ __global__ __launch_bounds__(256) void attn_dbias_reduce_kernel(const float* __r
     if (t != 0.f) unsafeAtomicAdd(dbias + (size_t)r * bias_ld + h, t);
 }
 
-long long attn3_part_floats(int B, int N);       // attention3.hip
-// N <= 4096: the d(bias) rows.  N > 4096: the same rows, then the slots of the dK / dV kernel (attn3_part_floats: B x workgroups per sample x
-// 64 KiB), which make dK / dV sums of a fixed order there.
-extern "C" long long omlm_mqa_attn_bwd_workspace_bytes(int B, int N, int H) {
-    if (B <= 0 || N <= 0 || H <= 0) return 0;
-    const long long nqt = (N + 31) / 32;
-    const long long rows = (long long)B * H * nqt * nqt * 32;
-    return (rows + (N > 4096 ? attn3_part_floats(B, N) : 0)) * (long long)sizeof(float);
-}
+// include/omlm.h (csrc/attn_plan.h: the d(bias) rows, past N = 4096 followed by the dK / dV kernel's slots)
+extern "C" long long omlm_mqa_attn_bwd_workspace_bytes(int B, int N, int H) { return omlm_plan::attn_bwd_workspace_bytes(B, N, H); }
 
-extern "C" __attribute__((visibility("hidden"))) int omlm_attn_dbias_reduce_launch(const float* dpart, float* dbias, int bias_ld, int B, int N, int H, void* stream) {
-    const int nqt = (N + 31) / 32;
-    hipLaunchKernelGGL(attn_dbias_reduce_kernel, dim3((N + 255) / 256, H, min(B, A2_DBR_S)), dim3(256), 0, as_stream(stream), dpart, dbias,
-                       bias_ld, B, N, H, nqt);
-    return omlm_post_launch("omlm_mqa_attn_bwd");
+extern "C" __attribute__((visibility("hidden"))) void omlm_attn_dbias_reduce_launch(const omlm_plan::AttnLaunch* l, const float* dpart, float* dbias, int bias_ld, int B, int N, int H, void* stream) {
+    hipLaunchKernelGGL(attn_dbias_reduce_kernel, dim3(l->gx, l->gy, l->gz), dim3(l->threads), 0, as_stream(stream), dpart, dbias, bias_ld, B, N, H, (N + 31) / 32);
 }
 
 // ---- attention dropout: the keep-mask the attention kernels apply, written out (a test / integration hook), and the to_out dropout ------
@@ -628,60 +588,20 @@ extern "C" int omlm_dropout_residual_bwd(const float* dx1, void* dy, long long M
 
 #endif
 
-// bf16 forward.  biasT from omlm_attn_bias_prepare (or null: no bias).
-int attn2_fwd_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
-                     void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn) {
-    const int ldT = (A2_PAD + (Pn > 0 ? Pn - 1 : 0) + N + 2 * A2_BWIN + 3) / 4 * 4;
-    const int nqt = (N + 31) / 32, ny = (H + 7) / 8;
-    if (N > 64 * 64) {                                          // the long form (the entry points have refused N > A2_NL and a prefix)
-        if (N > A2_NL || Pn > 0) return OMLM_ERR_UNSUPPORTED;
-        const size_t ldsl = (size_t)A2_NST * A2_STAGE + (size_t)((N + 63) / 64) * (64 * 2 + 8) + 128;
-        static bool a4l = false;
-        if (!a4l) {
-            (void)hipFuncSetAttribute((const void*)attn4_fwd_long_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)attn4_fwd_long_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)attn4_fwd_long_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipFuncSetAttribute((const void*)attn4_fwd_long_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            a4l = true;
-        }
-        const AttnDrop ndl = {0ull, nullptr, 0u, 1.0f};
-        const AttnDrop& drl = drop ? *drop : ndl;
-        const dim3 gridl(nqt * ny * B);
-        auto fixedl = drop ? attn4_fwd_long_kernel<true, true> : attn4_fwd_long_kernel<true>;
-        auto onlinel = drop ? attn4_fwd_long_kernel<false, true> : attn4_fwd_long_kernel<false>;
-        if (biasT) hipLaunchKernelGGL(fixedl, gridl, dim3(A4_THREADS), ldsl, st,
-                                      (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, drl, 0);
-        hipLaunchKernelGGL(onlinel, gridl, dim3(A4_THREADS), ldsl, st,
-                           (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse, B, N, H, scale, drl, 0);
-        return omlm_post_launch("omlm_mqa_attn_fwd");
-    }
-    const size_t lds = (size_t)A2_NST * A2_STAGE + (size_t)((N + 63) / 64 * 64) * 2 + 64 * 8 + 128;
-    static bool a4 = false;
-    if (!a4) {
-        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attn4_fwd_kernel<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        a4 = true;
-    }
-    // both softmax forms: the one the table's flag does not name returns at its first instruction (no table: online only); Pn > 0: their
-    // PFX instances (the non-causal prefix)
-    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
-    const AttnDrop& dr = drop ? *drop : nd;
-    const dim3 grid(nqt * ny * B);
-    auto fixed = Pn > 0 ? (drop ? attn4_fwd_kernel<true, true, true> : attn4_fwd_kernel<true, false, true>)
-                        : (drop ? attn4_fwd_kernel<true, true> : attn4_fwd_kernel<true>);
-    auto online = Pn > 0 ? (drop ? attn4_fwd_kernel<false, true, true> : attn4_fwd_kernel<false, false, true>)
-                         : (drop ? attn4_fwd_kernel<false, true> : attn4_fwd_kernel<false>);
-    if (biasT) hipLaunchKernelGGL(fixed, grid, dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask,
-                                  (h16_t*)out, lse, B, N, H, scale, dr, Pn);
-    hipLaunchKernelGGL(online, grid, dim3(A4_THREADS), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask,
-                       (h16_t*)out, lse, B, N, H, scale, dr, Pn);
-    return omlm_post_launch("omlm_mqa_attn_fwd");
+// one ATTN_A4_FWD launch of the plan: FIXED or online (both are launched where there is a table: the one its flag does not name returns at its
+// first instruction), DROP, and for the short form PFX (the non-causal prefix; the long form is causal)
+void attn2_fwd_launch(const omlm_plan::AttnLaunch& l, int ldT, const void* q, const void* k, const void* v, const float* biasT,
+                      const unsigned char* keymask, void* out, float* lse, int B, int N, int H, float scale, hipStream_t st, const AttnDrop& dr, int Pn) {
+    auto go = [&](auto launch) {
+        launch(dim3(l.gx), dim3(l.threads), l.lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, biasT, ldT, keymask, (h16_t*)out, lse,
+               B, N, H, scale, dr, Pn);
+    };
+    with_flags(l.fixed, l.drop, [&](auto F, auto D) {
+        constexpr bool FIXED = decltype(F)::value, DROP = decltype(D)::value;
+        if (l.form == omlm_plan::ATTN_FORM_LONG) go([](auto... a) { launch_lds_cap<attn4_fwd_long_kernel<FIXED, DROP>>(a...); });
+        else if (l.pfx) go([](auto... a) { launch_lds_cap<attn4_fwd_kernel<FIXED, DROP, true>>(a...); });
+        else go([](auto... a) { launch_lds_cap<attn4_fwd_kernel<FIXED, DROP>>(a...); });
+    });
 }
 
 }   // namespace OMLM_NS

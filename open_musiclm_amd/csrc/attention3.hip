@@ -16,6 +16,7 @@
 //     outputs -- each wave owns its 32 keys, so there is no cross-wave reduction at all.
 // Per element the arithmetic is the second generation's (same exponent form against the prepared table, same roundings).
 #include "common.h"
+#include "attn_plan.h"
 #include <stdlib.h>
 
 namespace OMLM_NS {
@@ -29,6 +30,8 @@ namespace OMLM_NS {
 #define A3_NEG (-1.0e30f)
 #define A3_LOG2E 1.4426950408889634f
 #define A3_PAD 64                      /* zero entries in front of each row of the prepared bias table (attention2.hip: A2_PAD) */
+static_assert(A3_PAD == omlm_plan::ATTN_PAD && A3_KR == omlm_plan::A3_KEYS && A3_NST * A3_STAGE == omlm_plan::A3_LDS,
+              "attn_plan.h states the prepared table's layout, the keys per workgroup and the ring");
 
 __device__ __forceinline__ int a3_crow(int r, int hi) { return (r & 3) + 8 * (r >> 2) + 4 * hi; }
 
@@ -85,7 +88,7 @@ __device__ __forceinline__ void a3_dma4(const void* gsrc, unsigned lds_dst) {
 // PFX: the non-causal prefix of Pn = min(P, N) rows.  A key range r with 128 r < Pn walks the query tiles from 0 instead of 4 r (its chunks
 // are counted by a3_range_start in the launch's work split too); items above the diagonal keep (i, j) iff i, j < Pn; the prepared table
 // holds off = Pn - 1 negative distances in front of the causal layout, so every window offset moves by off.
-__device__ __host__ __forceinline__ int a3_range_start(int r, int Pn) { return 128 * r < Pn ? 0 : 4 * r; }
+using omlm_plan::a3_range_start;
 #define A3_KERNEL attn3_bwd_dkv_kernel
 #define A3_PART false
 #define A3_PART_ARG
@@ -132,77 +135,31 @@ __global__ __launch_bounds__(256) void a3_zero_kernel(float4* __restrict__ p, si
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) p[i] = z;
 }
 
-static int a3_chunk(int B, int N);
-// fp32 elements of the slots attn3_bwd_dkv_part_kernel writes at (B, N): the dK / dV part of the backward's workspace for N > 4096
-long long attn3_part_floats(int B, int N) {
-    const int CH = a3_chunk(B, N), nqt = (N + 31) / 32, nr = (N + A3_KR - 1) / A3_KR;
-    long long wps = 0;
-    for (int r = 0; r < nr; ++r) wps += (nqt - 4 * r + CH - 1) / CH;
-    return (long long)B * wps * 2 * A3_KR * 64;
-}
-static int a3_chunk(int B, int N) {
-    const int nqt = (N + 31) / 32, nr = (N + A3_KR - 1) / A3_KR;
-    long long units = 0;
-    for (int r = 0; r < nr; ++r) units += nqt - 4 * r;
-    long long ch = ((long long)B * units + 1399) / 1400;      // ~5 workgroups per CU (measured: B = 32, N = 1116: CH 4 -> 505 us per layer, 8 -> 522, 2 -> 528)
-    if (ch < 2) ch = 2;
-    if (ch > 16) ch = 16;
-    return (int)ch;
-}
-
-// dk, dv [B * N, 64] fp32 are ZERO-FILLED here (memset node on the stream) and accumulated with atomics.  Returns 1 when the shape
-// is not served (caller falls back to the second-generation kernel).
-int attn3_bwd_dkv_launch(const void* q, const void* k, const void* v, const float* biasT, const unsigned char* keymask,
-                         const void* dout, const float* lse, const float* delta, float* dk, float* dv,
-                         int B, int N, int H, float scale, hipStream_t st, const AttnDrop* drop, int Pn, float* part) {
-    if (N < 32 || (long long)B * N * H * 128 >= (1ll << 32)) return 1;      // (32-bit byte offsets into q / dout)
-    const int off = Pn > 0 ? Pn - 1 : 0;                       // Pn > 0: the non-causal prefix (PFX instances)
-    const int ldT = ((A3_PAD + off + N + 2 * 128 + 3) / 4) * 4;    // layout of omlm_attn_bias_prepare (attention2.hip)
-    const int CH = a3_chunk(B, N);
-    const int nqt = (N + 31) / 32, nr = (N + A3_KR - 1) / A3_KR;
-    int wps = 0;
-    for (int r = 0; r < nr; ++r) wps += (nqt - (Pn > 0 ? a3_range_start(r, Pn) : 4 * r) + CH - 1) / CH;
-    const size_t lds = (size_t)A3_NST * A3_STAGE;             // 48 KiB (the final transposes reuse it: 4 x 8448 B)
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr = true;
-    }
-    // Zero fill by a KERNEL of this library, not hipMemsetAsync: as a memset node of a captured micro-step the fill detached everything
-    // behind it from the graph's completion -- the rest of the backward (this layer's dK / dV onwards) was still running when the launch
-    // had "finished" and the optimizer's kernels started (round 4: after one fp16 overflow the skipped step's gradient clear raced with
-    // those late writes and every later step stayed non-finite; no memset node, or a host sync after the replay, cured it).  A kernel node is ordered like every other launch.
-    const AttnDrop nd = {0ull, nullptr, 0u, 1.0f};
-    if (part) {                                                // N > 4096 with a workspace (causal): slots, then their sums in a fixed order
-        static bool attrp = false;
-        if (!attrp) {
-            (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_part_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute((const void*)attn3_bwd_dkv_part_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attrp = true;
-        }
-        auto kernp = drop ? attn3_bwd_dkv_part_kernel<true> : attn3_bwd_dkv_part_kernel<false>;
-        hipLaunchKernelGGL(kernp, dim3(B * wps), dim3(A3_T), lds, st,
-                           (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask, (const h16_t*)dout, lse, delta, dk, dv, biasT, ldT, B, N, H,
-                           scale, CH, wps, drop ? *drop : nd, 0, part);
-        hipLaunchKernelGGL(a3_part_reduce_kernel, dim3(nr, B, 2), dim3(256), 0, st, part, dk, dv, N, CH, wps);
-        return omlm_post_launch("omlm_mqa_attn_bwd");
-    }
-    const size_t gfloats = (size_t)B * N * 64;
-    auto fill = [&](float* p, size_t n) {
-        const size_t n4 = n / 4;                               // n = B N 64: a multiple of 4; rows are 256-byte aligned
-        unsigned blocks = (unsigned)((n4 + 255) / 256); if (blocks > 8192u) blocks = 8192u;
-        hipLaunchKernelGGL(a3_zero_kernel, dim3(blocks), dim3(256), 0, st, (float4*)p, n4);
+// One launch of the plan's dK / dV part: the zero fill(s) and the kernel that adds into them with atomics, or (N > 4096 with a workspace,
+// causal) the slot form and the sums of its slots in a fixed order.
+// Zero fill by a KERNEL of this library, not hipMemsetAsync: as a memset node of a captured micro-step the fill detached everything
+// behind it from the graph's completion -- the rest of the backward (this layer's dK / dV onwards) was still running when the launch
+// had "finished" and the optimizer's kernels started (round 4: after one fp16 overflow the skipped step's gradient clear raced with
+// those late writes and every later step stayed non-finite; no memset node, or a host sync after the replay, cured it).  A kernel node is ordered like every other launch.
+void attn3_bwd_dkv_launch(const omlm_plan::AttnLaunch& l, int ldT, const void* q, const void* k, const void* v, const float* biasT,
+                          const unsigned char* keymask, const void* dout, const float* lse, const float* delta, float* dk, float* dv,
+                          int B, int N, int H, float scale, hipStream_t st, const AttnDrop& dr, int Pn, float* part) {
+    const dim3 grid(l.gx, l.gy, l.gz), block(l.threads);
+    auto go = [&](auto launch, auto... tail) {
+        launch(grid, block, l.lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask, (const h16_t*)dout, lse, delta, dk, dv, biasT,
+               ldT, B, N, H, scale, l.CH, l.wps, dr, Pn, tail...);
     };
-    if (dv == dk + gfloats) fill(dk, 2 * gfloats);            // one allocation (the host's usual case): one fill launch instead of two
-    else { fill(dk, gfloats); fill(dv, gfloats); }
-    auto kern = Pn > 0 ? (drop ? attn3_bwd_dkv_kernel<true, true> : attn3_bwd_dkv_kernel<false, true>)
-                       : (drop ? attn3_bwd_dkv_kernel<true> : attn3_bwd_dkv_kernel<false>);
-    hipLaunchKernelGGL(kern, dim3(B * wps), dim3(A3_T), lds, st, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, keymask, (const h16_t*)dout, lse,
-                       delta, dk, dv, biasT, ldT, B, N, H, scale, CH, wps, drop ? *drop : nd, Pn);
-    return omlm_post_launch("omlm_mqa_attn_bwd");
+    if (l.family == omlm_plan::ATTN_A3_ZERO)                   // (l.floats: a multiple of 4; rows are 256-byte aligned)
+        hipLaunchKernelGGL(a3_zero_kernel, grid, block, 0, st, (float4*)(l.which ? dv : dk), (size_t)(l.floats / 4));
+    else if (l.family == omlm_plan::ATTN_A3_REDUCE)
+        hipLaunchKernelGGL(a3_part_reduce_kernel, grid, block, 0, st, part, dk, dv, N, l.CH, l.wps);
+    else if (l.form == omlm_plan::ATTN_FORM_PART) {
+        if (l.drop) go([](auto... a) { launch_lds_cap<attn3_bwd_dkv_part_kernel<true>>(a...); }, part);
+        else go([](auto... a) { launch_lds_cap<attn3_bwd_dkv_part_kernel<false>>(a...); }, part);
+    } else
+        with_flags(l.drop, l.pfx, [&](auto D, auto P) {
+            go([](auto... a) { launch_lds_cap<attn3_bwd_dkv_kernel<decltype(D)::value, decltype(P)::value>>(a...); });
+        });
 }
 
 }   // namespace OMLM_NS

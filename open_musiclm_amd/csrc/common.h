@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #define OMLM_OK 0
 #define OMLM_ERR_ARG (-1)
@@ -38,6 +39,20 @@ static inline void launch_with_lds(dim3 grid, dim3 block, size_t lds, hipStream_
     if (!attr) { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr = true; }
     hipLaunchKernelGGL(Kernel, grid, block, lds, st, args);
 }
+// The same for kernels whose LDS grows with the call (the attention family: with N, csrc/attn_plan.h): the first call's size would be too
+// small for a later one, so the instantiation opts in to the 160 KiB a workgroup can have, once.
+template <auto Kernel, typename... Args>
+static inline void launch_lds_cap(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    static bool attr = false;
+    if (!attr) { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+}
+// f(std::bool_constant<a>, std::bool_constant<b>): two run-time flags as template arguments
+template <typename F>
+static inline void with_flags(bool a, bool b, F&& f) {
+    if (a) { if (b) f(std::true_type(), std::true_type()); else f(std::true_type(), std::false_type()); }
+    else   { if (b) f(std::false_type(), std::true_type()); else f(std::false_type(), std::false_type()); }
+}
 
 // ---- the 16-bit GEMM / attention operand type of this build -----------------------------------------------------------------
 // Every source that touches 16-bit operands is compiled TWICE: once with h16_t = bf16 (precision "bf16"; also hosts the fp32 /
@@ -48,10 +63,6 @@ static inline void launch_with_lds(dim3 grid, dim3 block, size_t lds, hipStream_
 #ifndef OMLM_FP16
 #define OMLM_FP16 0
 #endif
-// most positions per sample of causal attention with 16-bit operands (the long forms of attention2.hip / attention3.hip serve 4096 < N <= this);
-// reported by omlm_attn_max_positions.  Bounds: the dropout row key holds the key pair index in 15 bits (N < 65536); the dQ kernel's LDS
-// grows by one byte per position (108 KiB here).
-#define OMLM_ATTN_NL 16384
 #define OMLM_DT_F32 0
 #define OMLM_DT_BF16 1
 #define OMLM_DT_F16 2

@@ -144,19 +144,40 @@ def issue(c, dev):
         raise ValueError(c["entry"])
 
 
+def sentinel(dev):
+    """the launch that marks the start of a call in the trace: omlm_split_planes of 8 floats, one 256-thread workgroup"""
+    import torch
+    from open_musiclm_amd import hip
+    sx, sp = torch.zeros(8, device=dev), torch.zeros(16, dtype=torch.bfloat16, device=dev)
+    return lambda: hip.call("omlm_split_planes", hip.ptr(sx), hip.ptr(sp), 8, 8, hip.stream_ptr())
+
+
+def cut_trace(trace_csv, keep):
+    """the trace's rows in start order, cut at the sentinels: per call the rows whose kernel name `keep` accepts"""
+    rows = sorted(csv.DictReader(open(trace_csv)), key=lambda r: int(r["Start_Timestamp"]))
+    segs = []
+    for r in rows:
+        name = r["Kernel_Name"]
+        if "split_planes_kernel" in name and int(r["Grid_Size_X"]) == 256:
+            segs.append([])
+        elif segs and keep(name):
+            segs[-1].append(r)
+    return segs
+
+
 def run(out):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch
-    from open_musiclm_amd import hip, ops
+    from open_musiclm_amd import ops
     dev = torch.device("cuda:0")
-    sx, sp = torch.zeros(8, device=dev), torch.zeros(16, dtype=torch.bfloat16, device=dev)
+    mark = sentinel(dev)
     done = calls()
     for c in done:
         for h in HOOKS:
             os.environ.pop(h, None)
         os.environ.update(c.get("env", {}))
         torch.cuda.synchronize()
-        hip.call("omlm_split_planes", hip.ptr(sx), hip.ptr(sp), 8, 8, hip.stream_ptr())          # the sentinel
+        mark()
         issue(c, dev)
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
@@ -167,15 +188,12 @@ def run(out):
 def merge(calls_json, trace_csv, out, source):
     rec = json.load(open(calls_json))
     done = rec["calls"]
-    rows = sorted(csv.DictReader(open(trace_csv)), key=lambda r: int(r["Start_Timestamp"]))
     segs = []
-    for r in rows:
-        name = r["Kernel_Name"]
-        if "split_planes_kernel" in name and int(r["Grid_Size_X"]) == 256:
-            segs.append([])
-        elif segs and "gemm" in name:
+    for seg in cut_trace(trace_csv, lambda name: "gemm" in name):
+        segs.append([])
+        for r in seg:
             wg = int(r["Workgroup_Size_X"])
-            segs[-1].append(dict(kernel=name, grid_x=int(r["Grid_Size_X"]) // wg, grid_y=int(r["Grid_Size_Y"]), workgroup=wg,
+            segs[-1].append(dict(kernel=r["Kernel_Name"], grid_x=int(r["Grid_Size_X"]) // wg, grid_y=int(r["Grid_Size_Y"]), workgroup=wg,
                                  lds=int(r.get("LDS_Block_Size", r.get("LDS_Block_Size_v", 0)))))
     assert len(segs) == len(done), (len(segs), len(done))
     for c, s in zip(done, segs):
