@@ -419,7 +419,10 @@ int omlm_kmeans_inertia(const float* x, const float* centres_T, double* out, int
 /* AR sampler: eos suppression + top_k(thres) + gumbel_sample (open_musiclm.py:309-316; utils.py:65-84).
  * Kept set: every logit strictly above the k-th largest value, then of the logits equal to it the lowest indices until exactly k are
  * kept.  Id: the first maximum of l / T + Gumbel(u) over the kept set (0 when every kept logit is -inf).  The same rule holds for
- * omlm_sample_topk_gumbel_at and omlm_sample_embed_at below. */
+ * omlm_sample_topk_gumbel_at and omlm_sample_embed_at below.
+ * Limit: 0 < V <= 65536 (V = codebook size + 1, so codebooks of up to 65535 entries sample; the uint16 token stores end there too),
+ * 1 <= k <= V, temperature > 0; anything else is refused before the launch.  V <= 2048 runs one wave per row, 2048 < V <= 65536 one
+ * workgroup per row; both are the same function of (logits, uniform, k, temperature, forbid_last), id for id. */
 int omlm_sample_topk_gumbel(const float* logits, const float* uniform, long long* out, int B, int V, int ld,
                             int k, float temperature, int forbid_last, void* stream);
 

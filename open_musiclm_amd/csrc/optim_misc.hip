@@ -983,11 +983,196 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
     }
 }
 
+// The same function of (logits, uniforms, k, T, forbid_last) for 2048 < V <= 65536: one WORKGROUP per row (B <= 64 rows: a row is not
+// spread over workgroups), up to 16 waves.  Wave w owns the CONTIGUOUS indices [w * 64 * NV, (w + 1) * 64 * NV), element
+// c = base + lane + 64 j, so slot order then lane order is index order inside a wave and the wave kernel's seen_eq + popc(mask & below)
+// ranks the tied entries of a segment; one scan over the waves' tie counts gives the segment's offset.
+// Residency: a row of 65536 floats (256 KB) does not fit the LDS.  Only the KEYS stay on chip, in registers (NV <= 64 per lane, under
+// the 128-VGPR ceiling of a 1024-thread workgroup); the logit of a kept entry is the exact inverse image of its key, so the logits are
+// read once, and the uniforms are read once, after the kept set is known, for kept entries only (a dropped slot loads element 0 of
+// the row: the load stays unconditional, one broadcast line).  Loads are dword loads: ld and V are arbitrary, rows are not 16-byte
+// aligned.
+// k-th largest key: radix descent by 8-bit digits, 4 rounds of a 256-bin LDS histogram (a per-bit descent as in the wave kernel would
+// meet at 32 barriers).  The bins are integer counts -- the LDS adds commute, the counts and so the id do not depend on arrival order;
+// no float is ever accumulated atomically.  Trained logits share their sign and high exponent bits, so the first round lands in a few
+// bins: every bin has SW_COPIES copies (lane & 7) to spread the same-address adds, and wave 0 sums them when it scans the bins.
+// The pads (key 0, at or below every live key) are counted too: k <= V, so the k-th largest key and kk are those of the live keys alone.
+// The descent ends with t = the k-th largest key and kk = k - count(keys > t), the number of tied entries to keep.
+constexpr int SW_COPIES = 8;
+constexpr int SW_UC = 16;                                 // uniforms in flight per lane in the scoring pass
+template <int NV>
+__global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restrict__ logits, const float* __restrict__ uniform,
+                                                           long long* __restrict__ out, int V, int ld, int k, float temperature,
+                                                           int forbid_last, const int* __restrict__ step_dev, long long* __restrict__ hist,
+                                                           const float* __restrict__ emb_table, long long emb_row_offset,
+                                                           long long emb_rows, float* __restrict__ x, int D) {
+    __shared__ __attribute__((aligned(16))) int s_hist[256 * SW_COPIES];
+    __shared__ int s_sel[2], s_weq[16], s_bi[16];
+    __shared__ float s_bv[16];
+    if (step_dev) {
+        const long long sidx = step_dev[0];
+        uniform += sidx * (long long)gridDim.x * V;
+        if (hist) hist += sidx * gridDim.x;
+    }
+    const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
+    const int base = wave * 64 * NV;
+    // every pass forms its indices from a value of its own (the empty asm): hipcc otherwise keeps the 64 indices, and the 64 `c < V` masks,
+    // of the first pass alive to the last one and spills them
+    int c0 = base + lane;
+    const float* lr = logits + (size_t)row * ld;
+    const float* ur = uniform + (size_t)row * V;
+    unsigned keys[NV];
+    {   // every logit load is requested before the first wait, unconditional on a clamped index (the wave kernel's two lessons)
+        float lv[NV];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = c0 + 64 * j;
+            lv[j] = *(const float*)((const char*)lr + 4u * (unsigned)(c < V ? c : V - 1));       // uniform base + 32-bit lane offset
+        }
+#pragma unroll
+        for (int j = 0; j < NV; ++j) asm volatile("" : "+v"(lv[j]));
+        asm volatile("" : "+v"(c0));
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            const int c = c0 + 64 * j;
+            const float v = (forbid_last && c == V - 1) ? -INFINITY : lv[j];
+            keys[j] = c < V ? f_ord(v) : 0u;
+        }
+    }
+    for (int i = tid; i < 256 * SW_COPIES; i += blockDim.x) s_hist[i] = 0;
+    __syncthreads();
+    unsigned t = 0;
+    int kk = k;                                            // entries still to keep among the keys that share the prefix t
+    for (int r = 0; r < 4; ++r) {
+        const int shift = 24 - 8 * r;
+        const unsigned himask = r == 0 ? 0u : 0xffffffffu << (shift + 8);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            if ((keys[j] & himask) == t) atomicAdd(&s_hist[((keys[j] >> shift) & 255u) * SW_COPIES + (lane & (SW_COPIES - 1))], 1);
+        }
+        __syncthreads();
+        if (wave == 0) {                                   // lane l owns bins 4 l .. 4 l + 3; higher bins hold larger keys
+            int bin[4];
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                int4* p = (int4*)&s_hist[(4 * lane + b) * SW_COPIES];
+                const int4 a0 = p[0], a1 = p[1];
+                bin[b] = a0.x + a0.y + a0.z + a0.w + a1.x + a1.y + a1.z + a1.w;
+                p[0] = make_int4(0, 0, 0, 0);              // zero for the next round (the barrier below is in between)
+                p[1] = make_int4(0, 0, 0, 0);
+            }
+            const int mine = bin[0] + bin[1] + bin[2] + bin[3];
+            int suf = mine;                                // inclusive suffix sum over the lanes: entries in bins >= 4 l
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_down(suf, o, 64);
+                if (lane + o < 64) suf += v;
+            }
+            int above = suf - mine;
+            if (above < kk && kk <= suf) {                 // exactly one lane: the kk-th largest entry lies in one of its bins
+                int d = 3;
+                while (d > 0 && above + bin[d] < kk) { above += bin[d]; --d; }
+                s_sel[0] = 4 * lane + d;
+                s_sel[1] = kk - above;
+            }
+        }
+        __syncthreads();
+        t |= (unsigned)s_sel[0] << shift;
+        kk = s_sel[1];
+    }
+    // of the entries equal to t keep the first kk by index: offset of this wave's segment among the tied entries
+    int myeq = 0;                                          // per lane, then over the wave (64 ballots held for later would spill)
+    int Vq = V;
+    asm volatile("" : "+v"(Vq), "+v"(c0));
+#pragma unroll
+    for (int j = 0; j < NV; ++j) myeq += (keys[j] == t && c0 + 64 * j < Vq) ? 1 : 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) myeq += __shfl_xor(myeq, o, 64);
+    if (lane == 0) s_weq[wave] = myeq;
+    __syncthreads();
+    int seen_eq = 0;
+    for (int w = 0; w < wave; ++w) seen_eq += s_weq[w];
+    const unsigned long long below = (1ull << lane) - 1ull;
+    unsigned long long keepbits = 0;
+    asm volatile("" : "+v"(Vq), "+v"(c0));
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const bool eq = keys[j] == t && c0 + 64 * j < Vq;
+        const unsigned long long eqmask = __ballot(eq);
+        const int rank = seen_eq + __popcll(eqmask & below);
+        if (keys[j] > t || (eq && rank < kk)) keepbits |= 1ull << j;            // a pad's key is 0: never above t
+        seen_eq += __popcll(eqmask);
+    }
+    float best = -INFINITY;
+    int besti = 0x7fffffff;
+#pragma unroll
+    for (int j0 = 0; j0 < NV; j0 += SW_UC) {
+        constexpr int UC = NV < SW_UC ? NV : SW_UC;
+        float uv[UC];
+        unsigned long long kb = keepbits;
+        asm volatile("" : "+v"(c0), "+v"(kb));
+#pragma unroll
+        for (int jj = 0; jj < UC; ++jj) uv[jj] = *(const float*)((const char*)ur + 4u * (unsigned)(((kb >> (j0 + jj)) & 1ull) ? c0 + 64 * (j0 + jj) : 0));
+#pragma unroll
+        for (int jj = 0; jj < UC; ++jj) asm volatile("" : "+v"(uv[jj]));
+#pragma unroll
+        for (int jj = 0; jj < UC; ++jj) {
+            const int j = j0 + jj;
+            const bool keep = (kb >> j) & 1ull;
+            const float l = u2f((keys[j] & 0x80000000u) ? keys[j] ^ 0x80000000u : ~keys[j]);      // f_ord's inverse: the logit's bits
+            const float gum = -logf(-logf(uv[jj] + 1e-20f) + 1e-20f);
+            const float v = keep ? l / temperature + gum : -INFINITY;
+            if (v > best) { best = v; besti = c0 + 64 * j; }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(besti, o, 64);
+        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+    }
+    if (lane == 0) { s_bv[wave] = best; s_bi[wave] = besti; }
+    __syncthreads();
+    best = s_bv[0];
+    besti = s_bi[0];
+    for (int w = 1; w < nw; ++w) {
+        const float ov = s_bv[w];
+        const int oi = s_bi[w];
+        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
+    }
+    if (besti == 0x7fffffff) besti = 0;                    // every kept entry -inf: no slot won a comparison
+    if (tid == 0) { out[row] = besti; if (hist) hist[row] = besti; }
+    if (emb_table) {
+        long long r = (long long)besti + emb_row_offset;
+        r = r < 0 ? 0 : (r >= emb_rows ? emb_rows - 1 : r);
+        const float4* src = (const float4*)(emb_table + r * D);
+        float4* dst = (float4*)(x + (size_t)row * D);
+        for (int i = tid; i < D / 4; i += blockDim.x) dst[i] = src[i];
+    }
+}
+
+// V > 2048: the workgroup kernel with the fewest slots per lane that hold the row, and only the waves that own a live index
+static void sample_wide_launch(const float* logits, const float* uniform, long long* out, int B, int V, int ld, int k, float temperature,
+                               int forbid_last, const int* step_dev, long long* hist, const float* emb_table, long long emb_row_offset,
+                               long long emb_rows, float* x, int D, void* stream) {
+    const int nv = V <= 4096 ? 4 : V <= 16384 ? 16 : 64;
+    const dim3 block(64 * ((V + 64 * nv - 1) / (64 * nv)));
+    if (nv == 4) hipLaunchKernelGGL(sample_wide_kernel<4>, dim3(B), block, 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature,
+                                    forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D);
+    else if (nv == 16) hipLaunchKernelGGL(sample_wide_kernel<16>, dim3(B), block, 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature,
+                                          forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D);
+    else hipLaunchKernelGGL(sample_wide_kernel<64>, dim3(B), block, 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature,
+                            forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D);
+}
+
+#define OMLM_SAMPLER_ARGS_MSG "sampler arguments (0 < V <= 65536, 1 <= k <= V, temperature > 0)"
+
 extern "C" int omlm_sample_topk_gumbel(const float* logits, const float* uniform, long long* out, int B, int V, int ld,
                                        int k, float temperature, int forbid_last, void* stream) {
     if (B <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(logits && uniform && out && V > 0 && V <= 2048 && k >= 1 && k <= V && temperature > 0.f, "sampler arguments");
-    if (V <= 64 * 17) hipLaunchKernelGGL(sample_kernel<17>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature, forbid_last,
+    OMLM_CHECK_ARG(logits && uniform && out && V > 0 && V <= 65536 && k >= 1 && k <= V && temperature > 0.f, OMLM_SAMPLER_ARGS_MSG);
+    if (V > 2048) sample_wide_launch(logits, uniform, out, B, V, ld, k, temperature, forbid_last, nullptr, nullptr, nullptr, 0ll, 0ll, nullptr, 0, stream);
+    else if (V <= 64 * 17) hipLaunchKernelGGL(sample_kernel<17>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature, forbid_last,
                                          (const int*)nullptr, (long long*)nullptr, (const float*)nullptr, 0ll, 0ll, (float*)nullptr, 0);
     else hipLaunchKernelGGL(sample_kernel<32>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature, forbid_last,
                             (const int*)nullptr, (long long*)nullptr, (const float*)nullptr, 0ll, 0ll, (float*)nullptr, 0);
@@ -999,8 +1184,9 @@ extern "C" int omlm_sample_topk_gumbel_at(const float* logits, const float* unif
                                           long long* hist, int B, int V, int ld, int k, float temperature, int forbid_last,
                                           void* stream) {
     if (B <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(logits && uniform_base && step_dev && out && V > 0 && V <= 2048 && k >= 1 && k <= V && temperature > 0.f, "sampler arguments");
-    if (V <= 64 * 17) hipLaunchKernelGGL(sample_kernel<17>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform_base, out, V, ld, k, temperature,
+    OMLM_CHECK_ARG(logits && uniform_base && step_dev && out && V > 0 && V <= 65536 && k >= 1 && k <= V && temperature > 0.f, OMLM_SAMPLER_ARGS_MSG);
+    if (V > 2048) sample_wide_launch(logits, uniform_base, out, B, V, ld, k, temperature, forbid_last, step_dev, hist, nullptr, 0ll, 0ll, nullptr, 0, stream);
+    else if (V <= 64 * 17) hipLaunchKernelGGL(sample_kernel<17>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform_base, out, V, ld, k, temperature,
                                          forbid_last, step_dev, hist, (const float*)nullptr, 0ll, 0ll, (float*)nullptr, 0);
     else hipLaunchKernelGGL(sample_kernel<32>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform_base, out, V, ld, k, temperature,
                             forbid_last, step_dev, hist, (const float*)nullptr, 0ll, 0ll, (float*)nullptr, 0);
@@ -1014,9 +1200,10 @@ extern "C" int omlm_sample_embed_at(const float* logits, const float* uniform_ba
                                     const float* emb_table, long long emb_row_offset, long long emb_rows, float* x, int D,
                                     void* stream) {
     if (B <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(logits && uniform_base && step_dev && out && V > 0 && V <= 2048 && k >= 1 && k <= V && temperature > 0.f, "sampler arguments");
+    OMLM_CHECK_ARG(logits && uniform_base && step_dev && out && V > 0 && V <= 65536 && k >= 1 && k <= V && temperature > 0.f, OMLM_SAMPLER_ARGS_MSG);
     OMLM_CHECK_ARG(emb_table && x && D > 0 && D % 4 == 0 && emb_rows > 0, "embedding arguments");
-    if (V <= 64 * 17) hipLaunchKernelGGL(sample_kernel<17>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform_base, out, V, ld, k, temperature,
+    if (V > 2048) sample_wide_launch(logits, uniform_base, out, B, V, ld, k, temperature, forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D, stream);
+    else if (V <= 64 * 17) hipLaunchKernelGGL(sample_kernel<17>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform_base, out, V, ld, k, temperature,
                                          forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D);
     else hipLaunchKernelGGL(sample_kernel<32>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform_base, out, V, ld, k, temperature,
                             forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D);

@@ -277,6 +277,7 @@ class SamplingLoop:
 
     def __init__(self, dec: CachedDecoder, first_logits: torch.Tensor, uniforms: torch.Tensor, n0: int, n_new: int, topk: int,
                  temperature: float, forbid_by_phase: Sequence[bool], use_graph: bool = True):
+        ops.check_sampler_width(dec.V1)                    # before any launch: the loop's first sampler call would refuse it
         self.dec, self.n0, self.n_new, self.topk, self.temperature = dec, n0, n_new, topk, float(temperature)
         self.forbid = [bool(f) for f in forbid_by_phase]
         dev = dec.logits.device

@@ -168,6 +168,7 @@ class TokenConditionedTransformerWrapper(nn.Module):
         causal); only the last position's logits are formed, and eos suppression + top-k + Gumbel-argmax run in
         one sampler kernel.  ``uniforms`` ([steps, B, V+1]) injects the uniform draws (tests)."""
         assert len(conditioning_token_ids) == len(self.token_sequences) - 1
+        ops.check_sampler_width(self.token_sequences[-1].codebook_size + 1)      # before any device work
         batch, device = conditioning_token_ids[0].shape[0], self.device
         cond = [t.to(device) for t in conditioning_token_ids]
         if exists(pred_token_ids):

@@ -786,7 +786,18 @@ def kmeans_inertia(x, centres_T, out, labels=None):
     call("omlm_kmeans_inertia", ptr(x), ptr(centres_T), ptr(out), ptr(labels), int(n), int(D), int(K), stream_ptr())
 
 
+SAMPLER_MAX_V = 65536             # csrc/optim_misc.hip: widest row the sampler takes (V = codebook_size + 1); the uint16 token stores end there too
+
+
+def check_sampler_width(V):
+    """ValueError before any launch when a row of V logits (a predicted codebook of V - 1 entries) is past the sampler's limit."""
+    if V > SAMPLER_MAX_V:
+        raise ValueError(f"sampler: a predicted codebook of {V - 1} entries needs rows of V = {V} logits, past the limit of "
+                         f"{SAMPLER_MAX_V} (codebooks of up to {SAMPLER_MAX_V - 1} entries sample)")
+
+
 def sample_topk_gumbel(logits, uniform, out, V, k, temperature, forbid_last):
+    check_sampler_width(V)
     B, ld = logits.shape
     call("omlm_sample_topk_gumbel", ptr(logits), ptr(uniform), ptr(out), B, V, ld, int(k), float(temperature),
          int(forbid_last), stream_ptr())
