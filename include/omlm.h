@@ -438,6 +438,28 @@ int omlm_sample_embed_at(const float* logits, const float* uniform_base, const i
                          int B, int V, int ld, int k, float temperature, int forbid_last,
                          const float* emb_table, long long emb_row_offset, long long emb_rows, float* x, int D, void* stream);
 
+/* The three sampler entry points on a counter-based uniform stream: no uniform buffer, u is computed in registers.  Everything else --
+ * kept set, tie rule, l / T + Gumbel(u), first maximum, the all -inf rule, the embedding gather, hist -- is the rule above, and an id equals
+ * the buffer form's when that is fed the stream's values.
+ * Stream -- uniform of step t, sample b, logit index c (c < 65536), from a 64-bit seed = seed_hi * 2^32 + seed_lo; uint32 arithmetic:
+ *   h(x)      = lowbias32: x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16   (the dropout masks' hash)
+ *   s0        = h(h(seed_lo) ^ seed_hi)
+ *   key(t, b) = h(h(s0 + t * 0x9E3779B9) ^ (b * 0x85EBCA6B))
+ *   r(t,b,c)  = h(key(t, b) ^ (c * 0x9E3779B9))
+ *   u(t,b,c)  = (r >> 8) * 2^-24                                  (the 24-bit grid in [0, 1) that torch.rand draws from)
+ * t is `step` (host) or *step_dev: the index of the sampled id within the generate() call.  b = row0 + (row of this call): the GLOBAL
+ * sample index, so ids do not depend on how a batch is cut into calls.  The seed is hashed before t is added: with key = h(t ^ seed_lo) ...
+ * seeds s and s ^ 1 would be one stream with steps swapped pairwise.  It depends on nothing else (not on B, V, ld or the kernel).
+ * Seed halves and row0 are plain arguments (a captured step stays valid for a whole call); same argument checks and limits as above. */
+int omlm_sample_topk_gumbel_rng(const float* logits, unsigned seed_lo, unsigned seed_hi, int step, int row0, long long* out,
+                                int B, int V, int ld, int k, float temperature, int forbid_last, void* stream);
+int omlm_sample_topk_gumbel_at_rng(const float* logits, unsigned seed_lo, unsigned seed_hi, const int* step_dev, int row0,
+                                   long long* out, long long* hist, int B, int V, int ld, int k, float temperature, int forbid_last,
+                                   void* stream);
+int omlm_sample_embed_at_rng(const float* logits, unsigned seed_lo, unsigned seed_hi, const int* step_dev, int row0, long long* out,
+                             long long* hist, int B, int V, int ld, int k, float temperature, int forbid_last,
+                             const float* emb_table, long long emb_row_offset, long long emb_rows, float* x, int D, void* stream);
+
 /* KV-cached AR decode step: ONE new row (index *pos_dev) per sample through all L layers and the logit head of the quantizer
  * that row predicts -- replaces the reference's full re-forward per sampled id (wrapper.generate, open_musiclm.py:301-321;
  * the trunk is strictly causal, so the logits are the same).  State owned by the caller, all fp32:

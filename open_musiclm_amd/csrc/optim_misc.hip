@@ -892,20 +892,47 @@ __device__ __forceinline__ unsigned f_ord(float f) { unsigned u = f2u(f); return
 // single wave is a serial instruction stream (~5-8 cycles per dependent instruction): the round-4 trace showed 43.9 us per call with the
 // slot loops unrolled to 32 behind `j < nv` branches (32 bits x 32 slots of compare / branch / count), so the slot count is a compile-time
 // constant and the descent stops at the first threshold that cuts exactly k keys.
-template <int SAMPLE_NV>
-__global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ logits, const float* __restrict__ uniform,
+//
+// The uniforms come from one of two sources, chosen at compile time (RNG, as the attention kernels take DROP):
+//   RNG = false: a buffer `uniform` [B, V] ([steps, B, V] with step_dev) -- how the golden id tests inject the reference's draws;
+//   RNG = true:  the counter stream stated in include/omlm.h, u(t, b, c) a pure function of a 64-bit seed, the step t (*step_dev, or the
+//                host's `step`), the global sample index b = row0 + row and the logit index c.  No pointer, no load: the per-row key
+//                is hoisted (a handful of scalar hashes) and ONE hash per element is left in the slot loop, next to its two logs.
+// Both are the same function of (logits, u): everything but the origin of u is the same code.
+struct SampleStream { unsigned seed_lo, seed_hi; int step, row0; };
+template <bool RNG> struct sample_src { typedef const float* __restrict__ type; };
+template <> struct sample_src<true> { typedef SampleStream type; };
+// per source: the row's uniforms (buffer) / the row's key (stream: t = *step_dev or the host's step, b = row0 + row).  Overloads, not
+// `if constexpr` around an assignment: the buffer form must still read `const float* ur = uniform + row * V` as ONE initialisation --
+// with `ur = nullptr; if constexpr (RNG) ...; else ur = ...` hipcc emitted the three wide RNG = false instantiations with two
+// independent v_cndmask of the bin scan in the other order (profiles/sampler_stream.md section 1 compares them with the parent's).
+__device__ __forceinline__ const float* sample_row_uniforms(const float* uniform, size_t offset) { return uniform + offset; }
+__device__ __forceinline__ const float* sample_row_uniforms(const SampleStream&, size_t) { return nullptr; }
+__device__ __forceinline__ unsigned sample_row_key(const float*, const int*, int) { return 0u; }
+__device__ __forceinline__ unsigned sample_row_key(const SampleStream& s, const int* step_dev, int row) {
+    const unsigned t = (unsigned)(step_dev ? step_dev[0] : s.step), b = (unsigned)(s.row0 + row);
+    const unsigned s0 = omlm_hash32(omlm_hash32(s.seed_lo) ^ s.seed_hi);      // the seed is hashed BEFORE t is added: otherwise seeds s and
+    return omlm_hash32(omlm_hash32(s0 + t * 0x9E3779B9u) ^ (b * 0x85EBCA6Bu));   // s ^ 1 are one stream with steps swapped pairwise
+}
+__device__ __forceinline__ float sample_stream_u(unsigned key, unsigned c) {      // 24-bit grid in [0, 1): exact in fp32
+    return (float)(omlm_hash32(key ^ (c * 0x9E3779B9u)) >> 8) * 0x1p-24f;
+}
+
+template <int SAMPLE_NV, bool RNG>
+__global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ logits, typename sample_src<RNG>::type uniform,
                                                     long long* __restrict__ out, int V, int ld, int k, float temperature,
                                                     int forbid_last, const int* __restrict__ step_dev, long long* __restrict__ hist,
                                                     const float* __restrict__ emb_table, long long emb_row_offset, long long emb_rows,
                                                     float* __restrict__ x, int D) {
     if (step_dev) {          // graph-replayable form: this step's uniforms / history slot are selected by a DEVICE counter
         const long long sidx = step_dev[0];
-        uniform += sidx * (long long)gridDim.x * V;
+        if constexpr (!RNG) uniform += sidx * (long long)gridDim.x * V;
         if (hist) hist += sidx * gridDim.x;
     }
     const int row = blockIdx.x, lane = threadIdx.x;
     const float* lr = logits + (size_t)row * ld;
-    const float* ur = uniform + (size_t)row * V;
+    const float* ur = sample_row_uniforms(uniform, (size_t)row * V);
+    const unsigned ukey = sample_row_key(uniform, step_dev, row);      // RNG: the stream's key of (step, global sample index), wave-uniform
     unsigned keys[SAMPLE_NV];
     float lv[SAMPLE_NV], uv[SAMPLE_NV];
     constexpr int nv = SAMPLE_NV;                      // every slot is live or clamped: no per-slot branches
@@ -918,10 +945,13 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
     for (int j = 0; j < SAMPLE_NV; ++j) {
         const int c = lane + 64 * j, cc = c < V ? c : V - 1;
         lv[j] = lr[cc];
-        uv[j] = ur[cc];
+        if constexpr (!RNG) uv[j] = ur[cc];
     }
 #pragma unroll
-    for (int j = 0; j < SAMPLE_NV; ++j) asm volatile("" : "+v"(lv[j]), "+v"(uv[j]));
+    for (int j = 0; j < SAMPLE_NV; ++j) {
+        if constexpr (RNG) asm volatile("" : "+v"(lv[j]));
+        else asm volatile("" : "+v"(lv[j]), "+v"(uv[j]));
+    }
 #pragma unroll
     for (int j = 0; j < SAMPLE_NV; ++j) {
         const int c = lane + 64 * j;
@@ -962,6 +992,7 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
         const bool keep = in && (keys[j] > t || (eq && rank < n_equal_keep));
         seen_eq += __popcll(eqmask);
         // branch-free: the Gumbel term of every slot is formed (2 logs per slot), dead slots lose the comparison
+        if constexpr (RNG) uv[j] = sample_stream_u(ukey, (unsigned)c);
         const float gum = -logf(-logf(uv[j] + 1e-20f) + 1e-20f);
         const float v = keep ? lv[j] / temperature + gum : -INFINITY;
         if (v > best) { best = v; besti = c; }
@@ -1000,8 +1031,8 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
 // The descent ends with t = the k-th largest key and kk = k - count(keys > t), the number of tied entries to keep.
 constexpr int SW_COPIES = 8;
 constexpr int SW_UC = 16;                                 // uniforms in flight per lane in the scoring pass
-template <int NV>
-__global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restrict__ logits, const float* __restrict__ uniform,
+template <int NV, bool RNG>
+__global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restrict__ logits, typename sample_src<RNG>::type uniform,
                                                            long long* __restrict__ out, int V, int ld, int k, float temperature,
                                                            int forbid_last, const int* __restrict__ step_dev, long long* __restrict__ hist,
                                                            const float* __restrict__ emb_table, long long emb_row_offset,
@@ -1011,7 +1042,7 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
     __shared__ float s_bv[16];
     if (step_dev) {
         const long long sidx = step_dev[0];
-        uniform += sidx * (long long)gridDim.x * V;
+        if constexpr (!RNG) uniform += sidx * (long long)gridDim.x * V;
         if (hist) hist += sidx * gridDim.x;
     }
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
@@ -1020,7 +1051,8 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
     // of the first pass alive to the last one and spills them
     int c0 = base + lane;
     const float* lr = logits + (size_t)row * ld;
-    const float* ur = uniform + (size_t)row * V;
+    const float* ur = sample_row_uniforms(uniform, (size_t)row * V);
+    const unsigned ukey = sample_row_key(uniform, step_dev, row);      // RNG: the stream's key of (step, global sample index), one per workgroup
     unsigned keys[NV];
     {   // every logit load is requested before the first wait, unconditional on a clamped index (the wave kernel's two lessons)
         float lv[NV];
@@ -1111,18 +1143,24 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
         float uv[UC];
         unsigned long long kb = keepbits;
         asm volatile("" : "+v"(c0), "+v"(kb));
+        if constexpr (!RNG) {
 #pragma unroll
-        for (int jj = 0; jj < UC; ++jj) uv[jj] = *(const float*)((const char*)ur + 4u * (unsigned)(((kb >> (j0 + jj)) & 1ull) ? c0 + 64 * (j0 + jj) : 0));
+            for (int jj = 0; jj < UC; ++jj) uv[jj] = *(const float*)((const char*)ur + 4u * (unsigned)(((kb >> (j0 + jj)) & 1ull) ? c0 + 64 * (j0 + jj) : 0));
 #pragma unroll
-        for (int jj = 0; jj < UC; ++jj) asm volatile("" : "+v"(uv[jj]));
+            for (int jj = 0; jj < UC; ++jj) asm volatile("" : "+v"(uv[jj]));
+        }
 #pragma unroll
         for (int jj = 0; jj < UC; ++jj) {
             const int j = j0 + jj;
             const bool keep = (kb >> j) & 1ull;
             const float l = u2f((keys[j] & 0x80000000u) ? keys[j] ^ 0x80000000u : ~keys[j]);      // f_ord's inverse: the logit's bits
+            if constexpr (RNG) uv[jj] = sample_stream_u(ukey, (unsigned)(c0 + 64 * j));      // every slot, kept or not: one hash, no branch
             const float gum = -logf(-logf(uv[jj] + 1e-20f) + 1e-20f);
             const float v = keep ? l / temperature + gum : -INFINITY;
             if (v > best) { best = v; besti = c0 + 64 * j; }
+            // NV = 64: one slot's hash and logs at a time (16 hashes in flight beside the 64 keys spilt 18 registers; the four waves of a
+            // SIMD fill each other's latencies)
+            if constexpr (RNG && NV > SW_UC) asm volatile("" : "+v"(best));
         }
     }
 #pragma unroll
@@ -1151,31 +1189,36 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
     }
 }
 
-// V > 2048: the workgroup kernel with the fewest slots per lane that hold the row, and only the waves that own a live index
-static void sample_wide_launch(const float* logits, const float* uniform, long long* out, int B, int V, int ld, int k, float temperature,
-                               int forbid_last, const int* step_dev, long long* hist, const float* emb_table, long long emb_row_offset,
-                               long long emb_rows, float* x, int D, void* stream) {
-    const int nv = V <= 4096 ? 4 : V <= 16384 ? 16 : 64;
-    const dim3 block(64 * ((V + 64 * nv - 1) / (64 * nv)));
-    if (nv == 4) hipLaunchKernelGGL(sample_wide_kernel<4>, dim3(B), block, 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature,
-                                    forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D);
-    else if (nv == 16) hipLaunchKernelGGL(sample_wide_kernel<16>, dim3(B), block, 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature,
-                                          forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D);
-    else hipLaunchKernelGGL(sample_wide_kernel<64>, dim3(B), block, 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature,
-                            forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D);
+// The kernel for a row of V logits: V <= 1088 / 2048 the wave kernel with 17 / 32 slots; wider, the workgroup kernel with the fewest slots
+// per lane that hold the row, and only the waves that own a live index.  `src` is the uniform buffer (RNG = false) or the stream's
+// arguments (RNG = true).  The wide kernels are named first: instantiation order is function order in the module, and with the wave kernels
+// first the same two instructions swapped again.
+template <bool RNG>
+static void sample_launch(const float* logits, typename sample_src<RNG>::type src, long long* out, int B, int V, int ld, int k,
+                          float temperature, int forbid_last, const int* step_dev, long long* hist, const float* emb_table,
+                          long long emb_row_offset, long long emb_rows, float* x, int D, void* stream) {
+#define SAMPLE_GO(BLOCK_, ...) hipLaunchKernelGGL((__VA_ARGS__), dim3(B), BLOCK_, 0, as_stream(stream), logits, src, out, V, ld, k, temperature, \
+                                                      forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D)
+    if (V > 2048) {
+        const int nv = V <= 4096 ? 4 : V <= 16384 ? 16 : 64;
+        const dim3 block(64 * ((V + 64 * nv - 1) / (64 * nv)));
+        if (nv == 4) SAMPLE_GO(block, sample_wide_kernel<4, RNG>);
+        else if (nv == 16) SAMPLE_GO(block, sample_wide_kernel<16, RNG>);
+        else SAMPLE_GO(block, sample_wide_kernel<64, RNG>);
+    }
+    else if (V <= 64 * 17) SAMPLE_GO(dim3(64), sample_kernel<17, RNG>);
+    else SAMPLE_GO(dim3(64), sample_kernel<32, RNG>);
+#undef SAMPLE_GO
 }
 
 #define OMLM_SAMPLER_ARGS_MSG "sampler arguments (0 < V <= 65536, 1 <= k <= V, temperature > 0)"
+#define OMLM_SAMPLER_ARGS_OK (V > 0 && V <= 65536 && k >= 1 && k <= V && temperature > 0.f)
 
 extern "C" int omlm_sample_topk_gumbel(const float* logits, const float* uniform, long long* out, int B, int V, int ld,
                                        int k, float temperature, int forbid_last, void* stream) {
     if (B <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(logits && uniform && out && V > 0 && V <= 65536 && k >= 1 && k <= V && temperature > 0.f, OMLM_SAMPLER_ARGS_MSG);
-    if (V > 2048) sample_wide_launch(logits, uniform, out, B, V, ld, k, temperature, forbid_last, nullptr, nullptr, nullptr, 0ll, 0ll, nullptr, 0, stream);
-    else if (V <= 64 * 17) hipLaunchKernelGGL(sample_kernel<17>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature, forbid_last,
-                                         (const int*)nullptr, (long long*)nullptr, (const float*)nullptr, 0ll, 0ll, (float*)nullptr, 0);
-    else hipLaunchKernelGGL(sample_kernel<32>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform, out, V, ld, k, temperature, forbid_last,
-                            (const int*)nullptr, (long long*)nullptr, (const float*)nullptr, 0ll, 0ll, (float*)nullptr, 0);
+    OMLM_CHECK_ARG(logits && uniform && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
+    sample_launch<false>(logits, uniform, out, B, V, ld, k, temperature, forbid_last, nullptr, nullptr, nullptr, 0ll, 0ll, nullptr, 0, stream);
     return omlm_post_launch("omlm_sample_topk_gumbel");
 }
 
@@ -1184,12 +1227,8 @@ extern "C" int omlm_sample_topk_gumbel_at(const float* logits, const float* unif
                                           long long* hist, int B, int V, int ld, int k, float temperature, int forbid_last,
                                           void* stream) {
     if (B <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(logits && uniform_base && step_dev && out && V > 0 && V <= 65536 && k >= 1 && k <= V && temperature > 0.f, OMLM_SAMPLER_ARGS_MSG);
-    if (V > 2048) sample_wide_launch(logits, uniform_base, out, B, V, ld, k, temperature, forbid_last, step_dev, hist, nullptr, 0ll, 0ll, nullptr, 0, stream);
-    else if (V <= 64 * 17) hipLaunchKernelGGL(sample_kernel<17>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform_base, out, V, ld, k, temperature,
-                                         forbid_last, step_dev, hist, (const float*)nullptr, 0ll, 0ll, (float*)nullptr, 0);
-    else hipLaunchKernelGGL(sample_kernel<32>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform_base, out, V, ld, k, temperature,
-                            forbid_last, step_dev, hist, (const float*)nullptr, 0ll, 0ll, (float*)nullptr, 0);
+    OMLM_CHECK_ARG(logits && uniform_base && step_dev && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
+    sample_launch<false>(logits, uniform_base, out, B, V, ld, k, temperature, forbid_last, step_dev, hist, nullptr, 0ll, 0ll, nullptr, 0, stream);
     return omlm_post_launch("omlm_sample_topk_gumbel_at");
 }
 
@@ -1200,14 +1239,43 @@ extern "C" int omlm_sample_embed_at(const float* logits, const float* uniform_ba
                                     const float* emb_table, long long emb_row_offset, long long emb_rows, float* x, int D,
                                     void* stream) {
     if (B <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(logits && uniform_base && step_dev && out && V > 0 && V <= 65536 && k >= 1 && k <= V && temperature > 0.f, OMLM_SAMPLER_ARGS_MSG);
+    OMLM_CHECK_ARG(logits && uniform_base && step_dev && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
     OMLM_CHECK_ARG(emb_table && x && D > 0 && D % 4 == 0 && emb_rows > 0, "embedding arguments");
-    if (V > 2048) sample_wide_launch(logits, uniform_base, out, B, V, ld, k, temperature, forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D, stream);
-    else if (V <= 64 * 17) hipLaunchKernelGGL(sample_kernel<17>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform_base, out, V, ld, k, temperature,
-                                         forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D);
-    else hipLaunchKernelGGL(sample_kernel<32>, dim3(B), dim3(64), 0, as_stream(stream), logits, uniform_base, out, V, ld, k, temperature,
-                            forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D);
+    sample_launch<false>(logits, uniform_base, out, B, V, ld, k, temperature, forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D, stream);
     return omlm_post_launch("omlm_sample_embed_at");
+}
+
+// The three entry points on the counter stream (include/omlm.h): no uniform buffer; row b of the call draws u(t, row0 + b, c) with
+// t = step (host) or *step_dev.  Seed halves and row0 are plain kernel arguments, so a captured cycle stays valid for a whole call.
+extern "C" int omlm_sample_topk_gumbel_rng(const float* logits, unsigned seed_lo, unsigned seed_hi, int step, int row0, long long* out,
+                                           int B, int V, int ld, int k, float temperature, int forbid_last, void* stream) {
+    if (B <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(logits && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
+    sample_launch<true>(logits, SampleStream{seed_lo, seed_hi, step, row0}, out, B, V, ld, k, temperature, forbid_last, nullptr, nullptr,
+                        nullptr, 0ll, 0ll, nullptr, 0, stream);
+    return omlm_post_launch("omlm_sample_topk_gumbel_rng");
+}
+
+extern "C" int omlm_sample_topk_gumbel_at_rng(const float* logits, unsigned seed_lo, unsigned seed_hi, const int* step_dev, int row0,
+                                              long long* out, long long* hist, int B, int V, int ld, int k, float temperature,
+                                              int forbid_last, void* stream) {
+    if (B <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(logits && step_dev && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
+    sample_launch<true>(logits, SampleStream{seed_lo, seed_hi, 0, row0}, out, B, V, ld, k, temperature, forbid_last, step_dev, hist,
+                        nullptr, 0ll, 0ll, nullptr, 0, stream);
+    return omlm_post_launch("omlm_sample_topk_gumbel_at_rng");
+}
+
+extern "C" int omlm_sample_embed_at_rng(const float* logits, unsigned seed_lo, unsigned seed_hi, const int* step_dev, int row0,
+                                        long long* out, long long* hist, int B, int V, int ld, int k, float temperature, int forbid_last,
+                                        const float* emb_table, long long emb_row_offset, long long emb_rows, float* x, int D,
+                                        void* stream) {
+    if (B <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(logits && step_dev && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
+    OMLM_CHECK_ARG(emb_table && x && D > 0 && D % 4 == 0 && emb_rows > 0, "embedding arguments");
+    sample_launch<true>(logits, SampleStream{seed_lo, seed_hi, 0, row0}, out, B, V, ld, k, temperature, forbid_last, step_dev, hist,
+                        emb_table, emb_row_offset, emb_rows, x, D, stream);
+    return omlm_post_launch("omlm_sample_embed_at_rng");
 }
 
 // ---------------------------------------------------------------------------------------------------------

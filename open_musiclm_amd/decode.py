@@ -26,6 +26,27 @@ from .hip import call, ptr, stream_ptr
 
 MAX_DECODE_BATCH = 8
 
+# generate(): the most bytes of uniforms [n_new, B, V1] drawn up front before the default moves to the counter stream
+UNIFORM_BUFFER_MAX_BYTES = 1 << 30
+
+
+def sampler_rng_choice(requested, n_new: int, batch: int, V1: int, injected: bool) -> str:
+    """Where generate() takes its uniforms from: "buffer" (all draws of the call up front, [n_new, batch, V1] floats -- the only way to
+    inject draws) or "counter" (the stream of include/omlm.h, formed in the sampler's registers).  requested None: "buffer", unless no
+    draws are injected and the buffer would exceed UNIFORM_BUFFER_MAX_BYTES.  Injected draws with "counter", or any other string, raise
+    a ValueError."""
+    if requested not in (None, "buffer", "counter"):
+        raise ValueError(f"sampler_rng must be None, 'buffer' or 'counter', not {requested!r}")
+    if requested == "counter" and injected:
+        raise ValueError("sampler_rng='counter' draws its uniforms in the kernel: it cannot be combined with injected draws "
+                         "(uniforms= or UNIFORM_SOURCE)")
+    if requested is not None:
+        return requested
+    if injected or 4 * int(n_new) * int(batch) * int(V1) <= UNIFORM_BUFFER_MAX_BYTES:
+        return "buffer"
+    return "counter"
+
+
 _PTRS = ["Wq", "Wkv", "Wo", "W1p", "W2p", "attn_gamma", "q_scale", "k_scale", "ffin_gamma", "convw", "mid_gamma",
          "Kc", "Vc", "hist"]
 
@@ -269,23 +290,38 @@ class CachedDecoder:
 class SamplingLoop:
     """sample -> embed -> 6 layers -> head -> advance, per id, for one CachedDecoder.
 
+    The uniforms are a buffer [n_new, B, V1] or, with ``rng=(seed, row0)`` and ``uniforms=None``, the counter stream of include/omlm.h
+    (row0: global index of this decoder's first sample).
     All per-step state (row index, step counter, uniforms, id history) is device resident, so the cycle of each quantizer
     phase can be captured into a HIP graph (``use_graph=True``: after one eager cycle per phase, the remaining ids are graph
     replays, ~1 host launch per id instead of ~32).  Measured on MI355X the step is GPU-bound (32 dependent kernels per id) and
     graph replay is no faster than back-to-back eager launches, so eager is the default; the graph path
     is kept (and tested) for hosts that cannot keep up."""
 
-    def __init__(self, dec: CachedDecoder, first_logits: torch.Tensor, uniforms: torch.Tensor, n0: int, n_new: int, topk: int,
-                 temperature: float, forbid_by_phase: Sequence[bool], use_graph: bool = True):
+    def __init__(self, dec: CachedDecoder, first_logits: torch.Tensor, uniforms: Optional[torch.Tensor], n0: int, n_new: int, topk: int,
+                 temperature: float, forbid_by_phase: Sequence[bool], use_graph: bool = True, rng=None):
         ops.check_sampler_width(dec.V1)                    # before any launch: the loop's first sampler call would refuse it
+        if (uniforms is None) == (rng is None):
+            raise ValueError("SamplingLoop: give either the uniforms [n_new, B, V1] or rng=(seed, row0), not both and not neither")
         self.dec, self.n0, self.n_new, self.topk, self.temperature = dec, n0, n_new, topk, float(temperature)
         self.forbid = [bool(f) for f in forbid_by_phase]
         dev = dec.logits.device
-        assert uniforms.shape == (n_new, dec.B, dec.V1) and uniforms.dtype == torch.float32 and uniforms.is_contiguous()
-        self.U = uniforms
+        if rng is None:
+            assert uniforms.shape == (n_new, dec.B, dec.V1) and uniforms.dtype == torch.float32 and uniforms.is_contiguous()
+            self.U = uniforms
+        else:
+            # counter stream (include/omlm.h): sample b of this decoder draws u(step, row0 + b, c) from the seed -- no buffer; seed halves
+            # and row0 are plain arguments, so a captured cycle holds for the whole call
+            self.U = None
+            self.seed, self.row0 = ops.split_seed(rng[0]), int(rng[1])
         self.hist = torch.zeros(n_new, dec.B, device=dev, dtype=torch.long)
         self.cur = torch.zeros(dec.B, device=dev, dtype=torch.long)
         self.step_dev = torch.zeros(1, device=dev, dtype=torch.int32)
+        # which sampler entry points the cycle calls, and their arguments between `logits` and `out`
+        if rng is None:
+            self._sfx, self._src = "", (ptr(self.U), ptr(self.step_dev))
+        else:
+            self._sfx, self._src = "_rng", (*self.seed, ptr(self.step_dev), self.row0)
         dec.logits.copy_(first_logits)
         self.use_graph = use_graph
         self.graphs = {}
@@ -295,12 +331,12 @@ class SamplingLoop:
         dec, a = self.dec, self.dec.args
         phase = k % dec.Q
         if not with_decode:
-            call("omlm_sample_topk_gumbel_at", ptr(dec.logits), ptr(self.U), ptr(self.step_dev), ptr(self.cur), ptr(self.hist),
+            call("omlm_sample_topk_gumbel_at" + self._sfx, ptr(dec.logits), *self._src, ptr(self.cur), ptr(self.hist),
                  dec.B, dec.V1, dec.ldV, self.topk, self.temperature, int(self.forbid[phase]), stream_ptr())
             return
         # 32 launches per id: the sampler also gathers the embedding row of the id it picked (the step's first launch), and the
         # head kernel (the step's last) moves the row index and the sampler's step counter on
-        call("omlm_sample_embed_at", ptr(dec.logits), ptr(self.U), ptr(self.step_dev), ptr(self.cur), ptr(self.hist),
+        call("omlm_sample_embed_at" + self._sfx, ptr(dec.logits), *self._src, ptr(self.cur), ptr(self.hist),
              dec.B, dec.V1, dec.ldV, self.topk, self.temperature, int(self.forbid[phase]),
              dec.emb.data_ptr(), dec.codebook * phase if dec.Q > 1 else 0, dec.emb.shape[0], ptr(dec.x), dec.D, stream_ptr())
         if dec.pos_emb is not None:

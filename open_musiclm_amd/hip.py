@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("OMLM_LIB_PATH") or os.path.join(_HERE, "libomlm_hip.s
 
 _lib: Optional[C.CDLL] = None
 
-vp, i32, i64, f32, u64, f64 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_ulonglong, C.c_double
+vp, i32, i64, f32, u64, f64, u32 = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_ulonglong, C.c_double, C.c_uint
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/omlm.h one to one
 SIGNATURES = {
@@ -92,6 +92,9 @@ SIGNATURES = {
     "omlm_kmeans_minibatch_step": [vp] * 10 + [i32, i32, i32, i32, f64, f64, i32, vp],
     "omlm_kmeans_inertia": [vp, vp, vp, vp, i32, i32, i32, vp],
     "omlm_sample_topk_gumbel": [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
+    "omlm_sample_topk_gumbel_rng": [vp, u32, u32, i32, i32, vp, i32, i32, i32, i32, f32, i32, vp],
+    "omlm_sample_topk_gumbel_at_rng": [vp, u32, u32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, vp],
+    "omlm_sample_embed_at_rng": [vp, u32, u32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, vp, i64, i64, vp, i32, vp],
     "omlm_probe_tr16": [vp, vp],
 }
 _RESTYPES = {"omlm_last_error": C.c_char_p, "omlm_gemm_tail_workspace_bytes": C.c_longlong, "omlm_gemm_mx16_workspace_bytes": C.c_longlong, "omlm_ffmid_bwd_workspace_bytes": C.c_longlong,

@@ -162,11 +162,16 @@ class TokenConditionedTransformerWrapper(nn.Module):
     @torch.no_grad()
     def generate(self, *, conditioning_token_ids: List[torch.Tensor], pred_token_ids: Optional[torch.Tensor] = None,
                  max_time_steps=512, filter_thres=0.9, temperature=1., include_eos_in_output=False,
-                 append_eos_to_conditioning_tokens=True, allow_eos_in_output=False, uniforms=None, **kwargs):
+                 append_eos_to_conditioning_tokens=True, allow_eos_in_output=False, uniforms=None, sampler_rng=None,
+                 sampler_seed=None, **kwargs):
         """AR sampling (open_musiclm.py:253-326).  Every step re-runs the full causal forward over the grown
         sequence like the reference (results are identical to a KV-cached decode because the stack is strictly
         causal); only the last position's logits are formed, and eos suppression + top-k + Gumbel-argmax run in
-        one sampler kernel.  ``uniforms`` ([steps, B, V+1]) injects the uniform draws (tests)."""
+        one sampler kernel.  ``uniforms`` ([steps, B, V+1]) injects the uniform draws (tests).
+        ``sampler_rng``: "buffer" draws every uniform of the call up front (torch.rand, [ids, B, V+1] floats); "counter" forms them in the
+        sampler kernel from the stream of include/omlm.h, seeded by ``sampler_seed`` (None: drawn from torch's generator on the model's
+        device, so torch.manual_seed governs the call either way) -- no buffer, and ids that do not depend on how the batch is cut into
+        decode calls.  None: "buffer" unless the buffer would exceed decode.UNIFORM_BUFFER_MAX_BYTES (decode.sampler_rng_choice)."""
         assert len(conditioning_token_ids) == len(self.token_sequences) - 1
         ops.check_sampler_width(self.token_sequences[-1].codebook_size + 1)      # before any device work
         batch, device = conditioning_token_ids[0].shape[0], self.device
@@ -195,13 +200,18 @@ class TokenConditionedTransformerWrapper(nn.Module):
         nxt = torch.empty(batch, device=device, dtype=torch.long)
         n_new = max(max_time_steps - first_step, 0) * Q
         prompt_rows = sum(t.shape[-1] + 1 for t in cond) + 1 + sampled.shape[-1]
+        counter = decode.sampler_rng_choice(sampler_rng, n_new, batch, V1, exists(uniforms) or UNIFORM_SOURCE is not None) == "counter"
+        if counter and sampler_seed is None and n_new > 0:
+            sampler_seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), device=device, dtype=torch.long)) & 0xFFFFFFFFFFFFFFFF
         use_cache = kwargs.pop('use_cache', True) and decode.supports(self.transformer, 1, prompt_rows=prompt_rows) and n_new > 0
         if use_cache:
             # KV-cached decode (decode.py): one new row per sampled id instead of the reference's full re-forward.
             # Ids are sampled straight into a [steps, B] buffer that the next decode step reads: no per-step cat / copies.
             rows = prompt_rows + n_new
             n0 = sampled.shape[-1]
-            if exists(uniforms):
+            if counter:
+                U = None
+            elif exists(uniforms):
                 U = uniforms[:n_new].to(device).float().contiguous()
             elif UNIFORM_SOURCE is not None:
                 U = UNIFORM_SOURCE(n_new, batch, V1).to(device).float().contiguous()
@@ -218,7 +228,10 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 b1 = min(batch, b0 + group)
                 dec = decode.CachedDecoder(self.transformer, b1 - b0, rows, self.transformer._precision(), wide=True)
                 last = dec.prefill([t[b0:b1] for t in cond] + [sampled[b0:b1]])
-                loop = decode.SamplingLoop(dec, last, U[:, b0:b1].contiguous(), n0, n_new, k, temperature, forbid, use_graph=use_graph)
+                if counter:            # sample b draws u(step, b, c) whichever piece it rides in
+                    loop = decode.SamplingLoop(dec, last, None, n0, n_new, k, temperature, forbid, use_graph=use_graph, rng=(sampler_seed, b0))
+                else:
+                    loop = decode.SamplingLoop(dec, last, U[:, b0:b1].contiguous(), n0, n_new, k, temperature, forbid, use_graph=use_graph)
                 pieces.append(loop.run().t())                      # [b, n_new]
             sampled = torch.cat((sampled, torch.cat(pieces, dim=0)), dim=-1)
         else:
@@ -228,11 +241,14 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 for ind in range(Q):
                     last = self.transformer.last_logits(cond + [sampled])
                     forbid = (not allow_eos_in_output) or (ind != Q - 1)
-                    if exists(uniforms):
-                        u = uniforms[step].to(device).float().contiguous()
+                    if counter:
+                        ops.sample_topk_gumbel_rng(last, sampler_seed, step, 0, nxt, V1, k, temperature, forbid)
                     else:
-                        u = torch.empty(batch, V1, device=device).uniform_(0, 1)
-                    ops.sample_topk_gumbel(last, u, nxt, V1, k, temperature, forbid)
+                        if exists(uniforms):
+                            u = uniforms[step].to(device).float().contiguous()
+                        else:
+                            u = torch.empty(batch, V1, device=device).uniform_(0, 1)
+                        ops.sample_topk_gumbel(last, u, nxt, V1, k, temperature, forbid)
                     sampled = torch.cat((sampled, nxt[:, None]), dim=-1)
                     step += 1
         sampled = mask_out_after_eos_id(sampled, pred_eos_id, keep_eos=include_eos_in_output)
@@ -535,6 +551,9 @@ class MusicLM(nn.Module):
                          random stream is consumed in a different order (one [steps, W * B, V] draw instead of W draws of
                          [steps, B, V]), so sampled ids differ from the sequential call's unless the uniforms are injected.
                          Default False: the reference's call-by-call structure.
+      sampler_rng     -- handed to every stage's generate(): "buffer", "counter" or None (TokenConditionedTransformerWrapper.generate).
+                         With "counter" each generate call draws its own seed from torch's generator; inside one call a sample's
+                         uniforms depend on its index in that call alone, not on how the call is cut into decode calls.
     ``generate`` is an alias of ``forward``."""
 
     def __init__(self, *, wav2vec=None, clap=None, neural_codec=None, semantic_transformer: TokenConditionedTransformer,
@@ -559,7 +578,7 @@ class MusicLM(nn.Module):
                 semantic_steps_per_second=50, acoustic_steps_per_second=75, return_coarse_generated_wave=False,
                 mask_out_generated_fine_tokens=False, semantic_sliding_window_step_percent=0.5,
                 coarse_sliding_window_step_percent=0.5, fine_sliding_window_step_percent=1,
-                clap_token_ids=None, return_tokens=False, fine_windows_together=False):
+                clap_token_ids=None, return_tokens=False, fine_windows_together=False, sampler_rng=None):
         if not exists(clap_token_ids):
             assert exists(text), 'text needs to be passed in if one of the transformer requires conditioning'
             clap_token_ids = get_or_compute_clap_token_ids(None, self.clap, conditioning_audio=None, conditioning_text=text)
@@ -593,12 +612,12 @@ class MusicLM(nn.Module):
         # ---- semantic stage (:930-952): one window, then 50%-overlap continuation windows ----
         sem = self.semantic.generate(clap_token_ids=clap_token_ids, semantic_token_ids=prime_sem,
                                      max_time_steps=int(min(output_seconds, semantic_window_seconds) * sem_hz),
-                                     include_eos_in_output=False, append_eos_to_conditioning_tokens=True)
+                                     include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng)
         while sem.shape[1] < int(output_seconds * sem_hz):
             keep = int(semantic_window_seconds * sem_hz * (1 - semantic_sliding_window_step_percent))
             nxt = self.semantic.generate(clap_token_ids=clap_token_ids, semantic_token_ids=sem[:, -keep:],
                                          max_time_steps=int(semantic_window_seconds * sem_hz),
-                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True)
+                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng)
             sem = torch.cat([sem, nxt[:, keep:]], dim=1)
         sem_all = sem
         sem = sem[:, sem_adjust:]
@@ -616,7 +635,7 @@ class MusicLM(nn.Module):
                                         coarse_token_ids=cond_coarse,
                                         max_time_steps=int(coarse_window_seconds * ac_hz), reconstruct_wave=False,
                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True,
-                                        temperature=0.95)
+                                        temperature=0.95, sampler_rng=sampler_rng)
             coarse = pred if not exists(coarse) else torch.cat([coarse, pred[:, keep:]], dim=1)
         if return_coarse_generated_wave:
             return self.neural_codec.decode_from_codebook_indices(coarse).squeeze(1)
@@ -632,7 +651,7 @@ class MusicLM(nn.Module):
             pred = self.fine.generate(clap_token_ids=clap_token_ids.repeat(len(coarse_wins), *([1] * (clap_token_ids.dim() - 1))),
                                       coarse_token_ids=_stack_windows(coarse_wins), fine_token_ids=None,
                                       max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
-                                      append_eos_to_conditioning_tokens=True, temperature=0.4)
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng)
             fine = torch.cat(_unstack_windows(pred, len(coarse_wins)), dim=1)
             coarse_wins = []
         for coarse_win in coarse_wins:
@@ -643,7 +662,7 @@ class MusicLM(nn.Module):
                 keep, cond_fine = 0, prime_fine
             pred = self.fine.generate(clap_token_ids=clap_token_ids, coarse_token_ids=coarse_win, fine_token_ids=cond_fine,
                                       max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
-                                      append_eos_to_conditioning_tokens=True, temperature=0.4)
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng)
             fine = pred if not exists(fine) else torch.cat([fine, pred[:, keep:]], dim=1)
         fine = fine[:, fine_adjust:]
         if exists(prime_coarse_all) and exists(prime_fine_all):

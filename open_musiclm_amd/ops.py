@@ -803,5 +803,20 @@ def sample_topk_gumbel(logits, uniform, out, V, k, temperature, forbid_last):
          int(forbid_last), stream_ptr())
 
 
+def split_seed(seed):
+    """(seed_lo, seed_hi): the uint32 halves of a 64-bit sampler seed (any Python int; taken modulo 2^64)."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed & 0xFFFFFFFF, seed >> 32
+
+
+def sample_topk_gumbel_rng(logits, seed, step, row0, out, V, k, temperature, forbid_last):
+    """sample_topk_gumbel on the counter stream of include/omlm.h: row b draws u(step, row0 + b, c) from `seed`; no uniform buffer."""
+    check_sampler_width(V)
+    B, ld = logits.shape
+    lo, hi = split_seed(seed)
+    call("omlm_sample_topk_gumbel_rng", ptr(logits), lo, hi, int(step), int(row0), ptr(out), B, V, ld, int(k), float(temperature),
+         int(forbid_last), stream_ptr())
+
+
 def probe_tr16(out):
     call("omlm_probe_tr16", ptr(out), stream_ptr())

@@ -1,5 +1,6 @@
 """Per-step time of the KV-cached sampling loop as the stages run it (graph replays), prefill differenced out: two `generate` calls of
-different lengths, (t_long - t_short) / extra ids.  env: B (1), PREC (fp16ff), REPS (5).  A/B of library builds: OMLM_LIB_PATH=tools/ab/libomlm_<x>.so"""
+different lengths, (t_long - t_short) / extra ids.  env: B (1), PREC (fp16ff), REPS (5), SAMPLER_RNG (unset: generate()'s default; "buffer" or
+"counter").  A/B of library builds: OMLM_LIB_PATH=tools/ab/libomlm_<x>.so"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -13,6 +14,8 @@ stage = M.CoarseStage(coarse_transformer=model).eval()
 g = torch.Generator().manual_seed(99)
 kw = dict(clap_token_ids=torch.randint(0, 1024, (B, 12, 1), generator=g).to(dev),
           semantic_token_ids=torch.randint(0, 1024, (B, 199), generator=g).to(dev), use_cache=True)
+if os.environ.get("SAMPLER_RNG"):
+    kw["sampler_rng"] = os.environ["SAMPLER_RNG"]
 short, long_ = 10, 110
 
 
@@ -29,5 +32,5 @@ for _ in range(reps):
     ts, tl = run(short), run(long_)
     us = 1e6 * (tl - ts) / ((long_ - short) * 3)
     best = us if best is None else min(best, us)
-print(f"B={B} {prec} lib={os.path.basename(os.environ.get('OMLM_LIB_PATH', 'default'))}: {best:.1f} us/step -> {B * 1e6 / best:.0f} ids/s "
+print(f"B={B} {prec} sampler_rng={os.environ.get('SAMPLER_RNG', 'default')} lib={os.path.basename(os.environ.get('OMLM_LIB_PATH', 'default'))}: {best:.1f} us/step -> {B * 1e6 / best:.0f} ids/s "
       f"(short call {1e3 * ts:.1f} ms)")
