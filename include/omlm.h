@@ -460,6 +460,43 @@ int omlm_sample_embed_at_rng(const float* logits, unsigned seed_lo, unsigned see
                              long long* hist, int B, int V, int ld, int k, float temperature, int forbid_last,
                              const float* emb_table, long long emb_row_offset, long long emb_rows, float* x, int D, void* stream);
 
+/* The sampler with a nucleus (top-p), and one entry point over all six forms above.  For a row of V logits, forbid_last, k, T > 0 and
+ * 0 < top_p < 1:
+ *   1. the last logit becomes -inf if forbidden;
+ *   2. S = the top-k kept set above, tie rule unchanged (strictly above the k-th value, then the lowest indices among the equals);
+ *   3. m = the largest logit in S; if m is -inf the id is 0, as above.  Otherwise w_c = exp((l_c - m) / T) for c in S (0 for -inf) and
+ *      W = sum of w_c;
+ *   4. rank S by logit descending, then index ascending: entry c is in the nucleus iff the mass of the entries ranked strictly before
+ *      it is < top_p W (the first-ranked entry is therefore always kept);
+ *   5. the id is the first maximum of l_c / T + Gumbel(u_c) over the nucleus -- the score, the 1e-20 guards and the first-maximum rule
+ *      of the sampler above, u_c the uniform of index c (uniform[row, c], or u(t, b, c) of the counter stream, unchanged).
+ * Equal logits have equal weights and are ranked by index, so the nucleus is every key above a threshold plus the first n entries by
+ * index among the keys equal to it: a second selection of the kind the top-k is.  The kernels form the masses in fixed point,
+ * q_c = floor(w_c 2^40) as 64-bit integers with w_c in fp32, and cut at mass-before < ceil(top_p sum of q): integer sums do not depend
+ * on order, so one row gives one id in every launch and in both kernels.  Against exact arithmetic the cut moves by less than 2^-18 of W.
+ * top_p == 1: no nucleus, the launch of the six entry points above.  top_p <= 0, > 1 or NaN is refused before the launch.
+ * Block: uniform non-null selects the buffer ([B, V], or [steps, B, V] with step_dev), null the counter stream (seed_lo, seed_hi, row0
+ * and step, or *step_dev); step_dev non-null selects the graph-replayable form (hist [steps, B], optional, is indexed by it; without
+ * step_dev hist is [B]); emb_table non-null adds the embedding gather into x [B, D] (D % 4 == 0).  Limits and checks as above. */
+typedef struct omlm_sample_args {
+    const float* logits;
+    int B, V, ld;
+    const float* uniform;
+    unsigned seed_lo, seed_hi;
+    int step, row0;
+    const int* step_dev;
+    long long* out;
+    long long* hist;
+    int k;
+    float temperature, top_p;
+    int forbid_last;
+    const float* emb_table;
+    long long emb_row_offset, emb_rows;
+    float* x;
+    int D;
+} omlm_sample_args;
+int omlm_sample(const omlm_sample_args* args, void* stream);
+
 /* KV-cached AR decode step: ONE new row (index *pos_dev) per sample through all L layers and the logit head of the quantizer
  * that row predicts -- replaces the reference's full re-forward per sampled id (wrapper.generate, open_musiclm.py:301-321;
  * the trunk is strictly causal, so the logits are the same).  State owned by the caller, all fp32:

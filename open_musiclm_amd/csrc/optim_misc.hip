@@ -899,9 +899,20 @@ __device__ __forceinline__ unsigned f_ord(float f) { unsigned u = f2u(f); return
 //                host's `step`), the global sample index b = row0 + row and the logit index c.  No pointer, no load: the per-row key
 //                is hoisted (a handful of scalar hashes) and ONE hash per element is left in the slot loop, next to its two logs.
 // Both are the same function of (logits, u): everything but the origin of u is the same code.
+//
+// The nucleus (NUC, a third compile-time choice; the function is stated in include/omlm.h): a SECOND selection over the keys already on
+// chip, which tightens the top-k pair (t, number of tied entries kept) to (t_p, n_p); the scoring pass then runs on the new pair.  The
+// masses are 64-bit integers q = floor(w 2^40), w = exp((l - m) / T) from ONE function (nucleus_q) of the key's inverse image: integer adds
+// commute, so ballots, shuffles and LDS adds give the same sums in any order and in either kernel.  NUC = false takes the argument types
+// of the parent (a pointer / SampleStream), NUC = true the same with top_p appended, so the existing instantiations keep their kernarg
+// layout: they are compared with the parent's instruction for instruction (profiles/sampler_top_p.md section 1).
 struct SampleStream { unsigned seed_lo, seed_hi; int step, row0; };
-template <bool RNG> struct sample_src { typedef const float* __restrict__ type; };
-template <> struct sample_src<true> { typedef SampleStream type; };
+struct SampleBufferP { const float* u; float top_p; };
+struct SampleStreamP { SampleStream s; float top_p; };
+template <bool RNG, bool NUC = false> struct sample_src { typedef const float* __restrict__ type; };
+template <> struct sample_src<true, false> { typedef SampleStream type; };
+template <> struct sample_src<false, true> { typedef SampleBufferP type; };
+template <> struct sample_src<true, true> { typedef SampleStreamP type; };
 // per source: the row's uniforms (buffer) / the row's key (stream: t = *step_dev or the host's step, b = row0 + row).  Overloads, not
 // `if constexpr` around an assignment: the buffer form must still read `const float* ur = uniform + row * V` as ONE initialisation --
 // with `ur = nullptr; if constexpr (RNG) ...; else ur = ...` hipcc emitted the three wide RNG = false instantiations with two
@@ -917,16 +928,52 @@ __device__ __forceinline__ unsigned sample_row_key(const SampleStream& s, const 
 __device__ __forceinline__ float sample_stream_u(unsigned key, unsigned c) {      // 24-bit grid in [0, 1): exact in fp32
     return (float)(omlm_hash32(key ^ (c * 0x9E3779B9u)) >> 8) * 0x1p-24f;
 }
+// NUC = true: the same two per-source functions on the argument blocks that carry top_p, and top_p itself
+__device__ __forceinline__ const float* sample_row_uniforms(const SampleBufferP& p, size_t offset) { return p.u + offset; }
+__device__ __forceinline__ const float* sample_row_uniforms(const SampleStreamP&, size_t) { return nullptr; }
+__device__ __forceinline__ unsigned sample_row_key(const SampleBufferP&, const int*, int) { return 0u; }
+__device__ __forceinline__ unsigned sample_row_key(const SampleStreamP& p, const int* step_dev, int row) { return sample_row_key(p.s, step_dev, row); }
+__device__ __forceinline__ float sample_top_p(const float*) { return 1.f; }
+__device__ __forceinline__ float sample_top_p(const SampleStream&) { return 1.f; }
+__device__ __forceinline__ float sample_top_p(const SampleBufferP& p) { return p.top_p; }
+__device__ __forceinline__ float sample_top_p(const SampleStreamP& p) { return p.top_p; }
 
-template <int SAMPLE_NV, bool RNG>
-__global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ logits, typename sample_src<RNG>::type uniform,
+// f_ord's inverse: the float whose key this is (a logit is the exact inverse image of its key)
+__device__ __forceinline__ float f_ord_inv(unsigned key) { return u2f((key & 0x80000000u) ? key ^ 0x80000000u : ~key); }
+// The fixed-point mass of a kept entry: floor(exp((l - m) / T) 2^40), l the logit of `key`, m the row's largest kept logit (so w <= 1 and
+// q <= 2^40: 65536 entries sum below 2^57).  The ONE place a weight is formed, for both kernels; exp(-inf) = 0.
+__device__ __forceinline__ unsigned long long nucleus_q(unsigned key, float m, float temperature) {
+    return (unsigned long long)(expf((f_ord_inv(key) - m) / temperature) * 0x1p40f);
+}
+// The cut: an entry is in the nucleus iff the mass ranked strictly before it is < top_p W, i.e. < thr = ceil(top_p W) for integer masses
+// (at least 1: the first-ranked entry is always kept).  Formed once per row, in fp64 (W < 2^57: relative error 2^-53).
+__device__ __forceinline__ unsigned long long nucleus_thr(float top_p, unsigned long long W) {
+    const unsigned long long thr = (unsigned long long)ceil((double)top_p * (double)W);
+    return thr < 1ull ? 1ull : (thr > W ? W : thr);
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {      // every lane gets the sum of the 64 lanes
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)v, o, 64), hi = __shfl_xor((unsigned)(v >> 32), o, 64);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {      // a wave-uniform value, moved to scalar registers
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;              // the builtin returns int: unsigned BEFORE widening, or the low half sign-extends
+}
+
+template <int SAMPLE_NV, bool RNG, bool NUC>
+__global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ logits, typename sample_src<RNG, NUC>::type uniform,
                                                     long long* __restrict__ out, int V, int ld, int k, float temperature,
                                                     int forbid_last, const int* __restrict__ step_dev, long long* __restrict__ hist,
                                                     const float* __restrict__ emb_table, long long emb_row_offset, long long emb_rows,
                                                     float* __restrict__ x, int D) {
     if (step_dev) {          // graph-replayable form: this step's uniforms / history slot are selected by a DEVICE counter
         const long long sidx = step_dev[0];
-        if constexpr (!RNG) uniform += sidx * (long long)gridDim.x * V;
+        if constexpr (!RNG && !NUC) uniform += sidx * (long long)gridDim.x * V;
+        if constexpr (!RNG && NUC) uniform.u += sidx * (long long)gridDim.x * V;
         if (hist) hist += sidx * gridDim.x;
     }
     const int row = blockIdx.x, lane = threadIdx.x;
@@ -977,7 +1024,60 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
 #pragma unroll
         for (int j = 0; j < SAMPLE_NV; ++j) ng += __popcll(__ballot(keys[j] > t));
     }
-    const int n_equal_keep = exact ? 0x7fffffff : k - ng;
+    int n_equal_keep = exact ? 0x7fffffff : k - ng;
+    if constexpr (NUC) {
+        // The nucleus: the largest x >= t whose mass M(x) = sum of q over the kept keys >= x reaches thr; then the entries above x are in,
+        // and of the entries equal to x the first ceil((thr - mass above x) / q_x) by index (they share one q).  The kept entries tied at t
+        // enter as ONE term n q_t, so no slot needs its rank here.  The descent starts below the bits t and the row maximum share (every kept
+        // key lies between them): a mass is 17 / 32 selects and adds per lane plus a 64-bit wave sum, per bit.  Measured, this second
+        // descent costs more than the first (+12.5 us per launch at V = 1025, profiles/sampler_top_p.md section 2): the wave sum is six
+        // dependent steps of two ds_bpermute where a count is a ballot.  Next there: several bits per step, or DPP row sums.
+        unsigned kmax = 0;
+#pragma unroll
+        for (int j = 0; j < SAMPLE_NV; ++j) kmax = keys[j] > kmax ? keys[j] : kmax;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const unsigned ok = __shfl_xor(kmax, o, 64); kmax = ok > kmax ? ok : kmax; }
+        kmax = __builtin_amdgcn_readfirstlane(kmax);
+        const float m = f_ord_inv(kmax);
+        if (m > -INFINITY && m < INFINITY) {                // m = -inf: every kept entry is -inf, the id is 0 as without a nucleus
+            int neq = n_equal_keep;                         // kept entries equal to t
+            if (exact) {
+                neq = 0;
+#pragma unroll
+                for (int j = 0; j < SAMPLE_NV; ++j) neq += __popcll(__ballot(keys[j] == t && lane + 64 * j < V));
+            }
+            unsigned long long q[SAMPLE_NV], part = 0;
+#pragma unroll
+            for (int j = 0; j < SAMPLE_NV; ++j) {           // a pad's key is 0: never above t
+                q[j] = keys[j] > t ? nucleus_q(keys[j], m, temperature) : 0ull;
+                part += q[j];
+            }
+            const unsigned long long qt = neq > 0 ? nucleus_q(t, m, temperature) : 0ull, Qt = (unsigned long long)neq * qt;
+            const unsigned long long thr = nucleus_thr(sample_top_p(uniform), uniform_u64(wave_sum_u64(part)) + Qt);
+            unsigned x = t;
+            if (t != kmax) {
+                const int hb = 31 - __clz(t ^ kmax);       // kmax has this bit, t does not
+                x = t & ~((2u << hb) - 1u);
+                for (int bit = hb; bit >= 0; --bit) {
+                    const unsigned cand = x | (1u << bit);
+                    unsigned long long ms = 0;
+#pragma unroll
+                    for (int j = 0; j < SAMPLE_NV; ++j) ms += keys[j] >= cand ? q[j] : 0ull;
+                    ms = uniform_u64(wave_sum_u64(ms)) + (cand <= t ? Qt : 0ull);
+                    if (ms >= thr) x = cand;
+                }
+            }
+            unsigned long long g = 0;                       // the mass ranked before the entries equal to x
+#pragma unroll
+            for (int j = 0; j < SAMPLE_NV; ++j) g += keys[j] > x ? q[j] : 0ull;
+            g = uniform_u64(wave_sum_u64(g));
+            const unsigned long long qx = x == t ? qt : nucleus_q(x, m, temperature);
+            int np = qx > 0 && thr > g ? (int)((thr - g + qx - 1ull) / qx) : 0x7fffffff;
+            if (x == t && np > neq) np = neq;
+            t = x;
+            n_equal_keep = np;
+        }
+    }
     float best = -INFINITY;
     int besti = 0x7fffffff;
     int seen_eq = 0;
@@ -1031,8 +1131,8 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
 // The descent ends with t = the k-th largest key and kk = k - count(keys > t), the number of tied entries to keep.
 constexpr int SW_COPIES = 8;
 constexpr int SW_UC = 16;                                 // uniforms in flight per lane in the scoring pass
-template <int NV, bool RNG>
-__global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restrict__ logits, typename sample_src<RNG>::type uniform,
+template <int NV, bool RNG, bool NUC>
+__global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restrict__ logits, typename sample_src<RNG, NUC>::type uniform,
                                                            long long* __restrict__ out, int V, int ld, int k, float temperature,
                                                            int forbid_last, const int* __restrict__ step_dev, long long* __restrict__ hist,
                                                            const float* __restrict__ emb_table, long long emb_row_offset,
@@ -1042,7 +1142,8 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
     __shared__ float s_bv[16];
     if (step_dev) {
         const long long sidx = step_dev[0];
-        if constexpr (!RNG) uniform += sidx * (long long)gridDim.x * V;
+        if constexpr (!RNG && !NUC) uniform += sidx * (long long)gridDim.x * V;
+        if constexpr (!RNG && NUC) uniform.u += sidx * (long long)gridDim.x * V;
         if (hist) hist += sidx * gridDim.x;
     }
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
@@ -1111,6 +1212,100 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
         __syncthreads();
         t |= (unsigned)s_sel[0] << shift;
         kk = s_sel[1];
+    }
+    if constexpr (NUC) {
+        // The nucleus on the same machinery: radix rounds over the 8-bit digits with a 64-bit MASS per bin (integer LDS adds: any arrival order
+        // gives the same sums), scanned from the top bin down to the bin where the running mass reaches thr.  Only the keys above t add
+        // their mass; the kk kept entries tied at t are one term kk q_t that wave 0 adds to t's bin, so no rank is needed.  The weights are
+        // formed again from the keys in every round (nothing is stored: the registers hold the keys), and a round whose digit t and the row
+        // maximum share -- every kept key lies between them -- is skipped.  The first round that runs sees the whole kept set: its total is W.
+        __shared__ __attribute__((aligned(16))) unsigned long long s_mass[256 * SW_COPIES];
+        __shared__ unsigned long long s_rem;
+        __shared__ unsigned s_kmax[16];
+        __shared__ int s_dig;
+        unsigned kmax = 0;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) kmax = keys[j] > kmax ? keys[j] : kmax;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const unsigned ok = __shfl_xor(kmax, o, 64); kmax = ok > kmax ? ok : kmax; }
+        if (lane == 0) s_kmax[wave] = kmax;
+        if (tid == 0) { s_dig = 0; s_rem = 1ull; }
+        for (int i = tid; i < 256 * SW_COPIES; i += blockDim.x) s_mass[i] = 0ull;
+        __syncthreads();
+        kmax = s_kmax[0];
+        for (int w = 1; w < nw; ++w) kmax = s_kmax[w] > kmax ? s_kmax[w] : kmax;
+        const float m = f_ord_inv(kmax);
+        if (m > -INFINITY && m < INFINITY) {                // m = -inf: every kept entry is -inf, the id is 0 as without a nucleus
+            const float top_p = sample_top_p(uniform);
+            unsigned x = 0;
+            unsigned long long rem = 0;
+            bool first = true;
+            for (int r = 0; r < 4; ++r) {
+                const int shift = 24 - 8 * r;
+                const unsigned himask = r == 0 ? 0u : 0xffffffffu << (shift + 8);
+                if (((t ^ kmax) >> shift) == 0u) { x |= t & (0xffu << shift); continue; }
+                unsigned tok = 0;                              // one slot's weight at a time: each slot waits for the one before (the empty
+#pragma unroll                                                 // asm), or hipcc forms many exponentials at once beside the keys and spills
+                for (int j = 0; j < NV; ++j) {
+                    unsigned kj = keys[j];
+                    asm volatile("" : "+v"(kj), "+v"(tok));
+                    if (kj > t && (kj & himask) == x) {
+                        const unsigned long long q = nucleus_q(kj, m, temperature);
+                        atomicAdd(&s_mass[((kj >> shift) & 255u) * SW_COPIES + (lane & (SW_COPIES - 1))], q);
+                        tok = (unsigned)q;
+                    }
+                }
+                __syncthreads();
+                if (wave == 0) {                               // lane l owns bins 4 l .. 4 l + 3; higher bins hold larger keys
+                    // the scan forms what it needs from values of its own (the empty asm): hipcc otherwise hoists the shuffle addresses, the
+                    // tied term and top_p out of the round loop, a dozen registers held beside the 64 keys -- one too many at NV = 64
+                    int ln = lane;
+                    unsigned tt = t;
+                    float tp = top_p;
+                    asm volatile("" : "+v"(ln), "+v"(tt), "+v"(tp));
+                    unsigned long long bin[4];
+                    const bool t_here = (tt & himask) == x;
+                    const int t_dig = (int)((tt >> shift) & 255u);
+                    int l4 = 4 * ln;                           // one bin's 64 bytes in flight at a time
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        if (b > 0) asm volatile("" : "+v"(l4) : "v"((unsigned)bin[b - 1]));
+                        ulonglong2* p = (ulonglong2*)&s_mass[(l4 + b) * SW_COPIES];
+                        const ulonglong2 a0 = p[0], a1 = p[1], a2 = p[2], a3 = p[3];
+                        bin[b] = a0.x + a0.y + a1.x + a1.y + a2.x + a2.y + a3.x + a3.y;
+                        if (t_here && t_dig == l4 + b) bin[b] += (unsigned long long)kk * nucleus_q(tt, m, temperature);
+                        p[0] = p[1] = p[2] = p[3] = make_ulonglong2(0ull, 0ull);      // zero for the next round (the barrier below is in between)
+                    }
+                    const unsigned long long mine = bin[0] + bin[1] + bin[2] + bin[3];
+                    unsigned long long suf = mine;             // inclusive suffix sum over the lanes: mass in bins >= 4 l
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) {
+                        const unsigned lo = __builtin_amdgcn_ds_bpermute((ln + o) << 2, (int)(unsigned)suf);
+                        const unsigned hi = __builtin_amdgcn_ds_bpermute((ln + o) << 2, (int)(unsigned)(suf >> 32));
+                        if (ln + o < 64) suf += ((unsigned long long)hi << 32) | lo;
+                    }
+                    if (first) rem = nucleus_thr(tp, uniform_u64(suf));      // lane 0 holds the total
+                    unsigned long long above = suf - mine;
+                    if (above < rem && rem <= suf) {           // exactly one lane: the running mass reaches rem in one of its bins
+                        int d = 3;
+                        while (d > 0 && above + bin[d] < rem) { above += bin[d]; --d; }
+                        s_dig = l4 + d;
+                        s_rem = rem - above;
+                    }
+                }
+                __syncthreads();
+                x |= (unsigned)s_dig << shift;
+                rem = s_rem;
+                first = false;
+            }
+            // x: the lowest key of the nucleus; rem: what is left of thr after the mass above x.  The entries equal to x share one q.
+            const unsigned long long qx = nucleus_q(x, m, temperature);
+            if (first) rem = nucleus_thr(top_p, (unsigned long long)kk * qx);      // t is the row maximum: no round ran, x = t, S = the kk tied entries
+            int np = qx > 0 && rem > 0 ? (int)((rem + qx - 1ull) / qx) : 0x7fffffff;
+            if (x == t && np > kk) np = kk;
+            t = x;
+            kk = np;
+        }
     }
     // of the entries equal to t keep the first kk by index: offset of this wave's segment among the tied entries
     int myeq = 0;                                          // per lane, then over the wave (64 ballots held for later would spill)
@@ -1193,8 +1388,8 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
 // per lane that hold the row, and only the waves that own a live index.  `src` is the uniform buffer (RNG = false) or the stream's
 // arguments (RNG = true).  The wide kernels are named first: instantiation order is function order in the module, and with the wave kernels
 // first the same two instructions swapped again.
-template <bool RNG>
-static void sample_launch(const float* logits, typename sample_src<RNG>::type src, long long* out, int B, int V, int ld, int k,
+template <bool RNG, bool NUC>
+static void sample_launch(const float* logits, typename sample_src<RNG, NUC>::type src, long long* out, int B, int V, int ld, int k,
                           float temperature, int forbid_last, const int* step_dev, long long* hist, const float* emb_table,
                           long long emb_row_offset, long long emb_rows, float* x, int D, void* stream) {
 #define SAMPLE_GO(BLOCK_, ...) hipLaunchKernelGGL((__VA_ARGS__), dim3(B), BLOCK_, 0, as_stream(stream), logits, src, out, V, ld, k, temperature, \
@@ -1202,12 +1397,12 @@ static void sample_launch(const float* logits, typename sample_src<RNG>::type sr
     if (V > 2048) {
         const int nv = V <= 4096 ? 4 : V <= 16384 ? 16 : 64;
         const dim3 block(64 * ((V + 64 * nv - 1) / (64 * nv)));
-        if (nv == 4) SAMPLE_GO(block, sample_wide_kernel<4, RNG>);
-        else if (nv == 16) SAMPLE_GO(block, sample_wide_kernel<16, RNG>);
-        else SAMPLE_GO(block, sample_wide_kernel<64, RNG>);
+        if (nv == 4) SAMPLE_GO(block, sample_wide_kernel<4, RNG, NUC>);
+        else if (nv == 16) SAMPLE_GO(block, sample_wide_kernel<16, RNG, NUC>);
+        else SAMPLE_GO(block, sample_wide_kernel<64, RNG, NUC>);
     }
-    else if (V <= 64 * 17) SAMPLE_GO(dim3(64), sample_kernel<17, RNG>);
-    else SAMPLE_GO(dim3(64), sample_kernel<32, RNG>);
+    else if (V <= 64 * 17) SAMPLE_GO(dim3(64), sample_kernel<17, RNG, NUC>);
+    else SAMPLE_GO(dim3(64), sample_kernel<32, RNG, NUC>);
 #undef SAMPLE_GO
 }
 
@@ -1218,7 +1413,7 @@ extern "C" int omlm_sample_topk_gumbel(const float* logits, const float* uniform
                                        int k, float temperature, int forbid_last, void* stream) {
     if (B <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(logits && uniform && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
-    sample_launch<false>(logits, uniform, out, B, V, ld, k, temperature, forbid_last, nullptr, nullptr, nullptr, 0ll, 0ll, nullptr, 0, stream);
+    sample_launch<false, false>(logits, uniform, out, B, V, ld, k, temperature, forbid_last, nullptr, nullptr, nullptr, 0ll, 0ll, nullptr, 0, stream);
     return omlm_post_launch("omlm_sample_topk_gumbel");
 }
 
@@ -1228,7 +1423,7 @@ extern "C" int omlm_sample_topk_gumbel_at(const float* logits, const float* unif
                                           void* stream) {
     if (B <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(logits && uniform_base && step_dev && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
-    sample_launch<false>(logits, uniform_base, out, B, V, ld, k, temperature, forbid_last, step_dev, hist, nullptr, 0ll, 0ll, nullptr, 0, stream);
+    sample_launch<false, false>(logits, uniform_base, out, B, V, ld, k, temperature, forbid_last, step_dev, hist, nullptr, 0ll, 0ll, nullptr, 0, stream);
     return omlm_post_launch("omlm_sample_topk_gumbel_at");
 }
 
@@ -1241,7 +1436,7 @@ extern "C" int omlm_sample_embed_at(const float* logits, const float* uniform_ba
     if (B <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(logits && uniform_base && step_dev && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
     OMLM_CHECK_ARG(emb_table && x && D > 0 && D % 4 == 0 && emb_rows > 0, "embedding arguments");
-    sample_launch<false>(logits, uniform_base, out, B, V, ld, k, temperature, forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D, stream);
+    sample_launch<false, false>(logits, uniform_base, out, B, V, ld, k, temperature, forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D, stream);
     return omlm_post_launch("omlm_sample_embed_at");
 }
 
@@ -1251,7 +1446,7 @@ extern "C" int omlm_sample_topk_gumbel_rng(const float* logits, unsigned seed_lo
                                            int B, int V, int ld, int k, float temperature, int forbid_last, void* stream) {
     if (B <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(logits && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
-    sample_launch<true>(logits, SampleStream{seed_lo, seed_hi, step, row0}, out, B, V, ld, k, temperature, forbid_last, nullptr, nullptr,
+    sample_launch<true, false>(logits, SampleStream{seed_lo, seed_hi, step, row0}, out, B, V, ld, k, temperature, forbid_last, nullptr, nullptr,
                         nullptr, 0ll, 0ll, nullptr, 0, stream);
     return omlm_post_launch("omlm_sample_topk_gumbel_rng");
 }
@@ -1261,7 +1456,7 @@ extern "C" int omlm_sample_topk_gumbel_at_rng(const float* logits, unsigned seed
                                               int forbid_last, void* stream) {
     if (B <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(logits && step_dev && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
-    sample_launch<true>(logits, SampleStream{seed_lo, seed_hi, 0, row0}, out, B, V, ld, k, temperature, forbid_last, step_dev, hist,
+    sample_launch<true, false>(logits, SampleStream{seed_lo, seed_hi, 0, row0}, out, B, V, ld, k, temperature, forbid_last, step_dev, hist,
                         nullptr, 0ll, 0ll, nullptr, 0, stream);
     return omlm_post_launch("omlm_sample_topk_gumbel_at_rng");
 }
@@ -1273,9 +1468,42 @@ extern "C" int omlm_sample_embed_at_rng(const float* logits, unsigned seed_lo, u
     if (B <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(logits && step_dev && out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
     OMLM_CHECK_ARG(emb_table && x && D > 0 && D % 4 == 0 && emb_rows > 0, "embedding arguments");
-    sample_launch<true>(logits, SampleStream{seed_lo, seed_hi, 0, row0}, out, B, V, ld, k, temperature, forbid_last, step_dev, hist,
+    sample_launch<true, false>(logits, SampleStream{seed_lo, seed_hi, 0, row0}, out, B, V, ld, k, temperature, forbid_last, step_dev, hist,
                         emb_table, emb_row_offset, emb_rows, x, D, stream);
     return omlm_post_launch("omlm_sample_embed_at_rng");
+}
+
+// One entry point over every form above (include/omlm.h): the argument block says where the uniforms come from (uniform / the counter
+// stream), whether the step is a device counter (step_dev) and whether the embedding row is gathered (emb_table).  top_p == 1 launches
+// the instantiations the six entry points above launch; top_p < 1 the NUC = true ones.
+struct omlm_sample_args {                                 // include/omlm.h
+    const float* logits; int B, V, ld;
+    const float* uniform; unsigned seed_lo, seed_hi; int step, row0; const int* step_dev;
+    long long* out; long long* hist;
+    int k; float temperature, top_p; int forbid_last;
+    const float* emb_table; long long emb_row_offset, emb_rows; float* x; int D;
+};
+extern "C" int omlm_sample(const omlm_sample_args* a, void* stream) {
+    OMLM_CHECK_ARG(a != nullptr, "args");
+    if (a->B <= 0) return OMLM_OK;
+    const int V = a->V, k = a->k;
+    const float temperature = a->temperature, top_p = a->top_p;
+    OMLM_CHECK_ARG(a->logits && a->out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
+    OMLM_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "top_p (0 < top_p <= 1; 1 = no nucleus)");
+    if (a->emb_table) OMLM_CHECK_ARG(a->x && a->D > 0 && a->D % 4 == 0 && a->emb_rows > 0, "embedding arguments");
+    const SampleStream st{a->seed_lo, a->seed_hi, a->step_dev ? 0 : a->step, a->row0};
+#define SAMPLE_ARGS_GO(RNG_, NUC_, SRC_) sample_launch<RNG_, NUC_>(a->logits, SRC_, a->out, a->B, V, a->ld, k, temperature, a->forbid_last, a->step_dev, \
+                                                                 a->hist, a->emb_table, a->emb_table ? a->emb_row_offset : 0ll,                       \
+                                                                 a->emb_table ? a->emb_rows : 0ll, a->emb_table ? a->x : nullptr,                    \
+                                                                 a->emb_table ? a->D : 0, stream)
+    if (top_p < 1.f) {
+        if (a->uniform) SAMPLE_ARGS_GO(false, true, (SampleBufferP{a->uniform, top_p}));
+        else SAMPLE_ARGS_GO(true, true, (SampleStreamP{st, top_p}));
+    }
+    else if (a->uniform) SAMPLE_ARGS_GO(false, false, a->uniform);
+    else SAMPLE_ARGS_GO(true, false, st);
+#undef SAMPLE_ARGS_GO
+    return omlm_post_launch("omlm_sample");
 }
 
 // ---------------------------------------------------------------------------------------------------------

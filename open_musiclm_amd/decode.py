@@ -296,11 +296,13 @@ class SamplingLoop:
     phase can be captured into a HIP graph (``use_graph=True``: after one eager cycle per phase, the remaining ids are graph
     replays, ~1 host launch per id instead of ~32).  Measured on MI355X the step is GPU-bound (32 dependent kernels per id) and
     graph replay is no faster than back-to-back eager launches, so eager is the default; the graph path
-    is kept (and tested) for hosts that cannot keep up."""
+    is kept (and tested) for hosts that cannot keep up.
+    ``top_p`` < 1: the sampler keeps the nucleus of the top-k set (include/omlm.h); the cycle then calls omlm_sample."""
 
     def __init__(self, dec: CachedDecoder, first_logits: torch.Tensor, uniforms: Optional[torch.Tensor], n0: int, n_new: int, topk: int,
-                 temperature: float, forbid_by_phase: Sequence[bool], use_graph: bool = True, rng=None):
+                 temperature: float, forbid_by_phase: Sequence[bool], use_graph: bool = True, rng=None, top_p=None):
         ops.check_sampler_width(dec.V1)                    # before any launch: the loop's first sampler call would refuse it
+        self.top_p = ops.check_top_p(top_p)                # 1.0: no nucleus, the cycle calls what it calls without the argument
         if (uniforms is None) == (rng is None):
             raise ValueError("SamplingLoop: give either the uniforms [n_new, B, V1] or rng=(seed, row0), not both and not neither")
         self.dec, self.n0, self.n_new, self.topk, self.temperature = dec, n0, n_new, topk, float(temperature)
@@ -326,19 +328,34 @@ class SamplingLoop:
         self.use_graph = use_graph
         self.graphs = {}
 
+    def _sample_top_p(self, phase: int, embed: bool):
+        """The nucleus forms of the cycle's two sampler calls, through the one entry point that has them (omlm_sample)."""
+        dec = self.dec
+        seed, row0 = ((0, 0), 0) if self.U is not None else (self.seed, self.row0)
+        sa = ops.SampleArgs(ptr(dec.logits), dec.B, dec.V1, dec.ldV, ptr(self.U), *seed, 0, row0, ptr(self.step_dev), ptr(self.cur),
+                            ptr(self.hist), self.topk, self.temperature, self.top_p, int(self.forbid[phase]))
+        if embed:
+            sa.emb_table, sa.emb_row_offset, sa.emb_rows = dec.emb.data_ptr(), dec.codebook * phase if dec.Q > 1 else 0, dec.emb.shape[0]
+            sa.x, sa.D = ptr(dec.x), dec.D
+        call("omlm_sample", C.addressof(sa), stream_ptr())
+
     def _cycle(self, k: int, with_decode: bool):
         """Sample id number k (global index in the predicted sequence) from dec.logits, then compute its row."""
         dec, a = self.dec, self.dec.args
         phase = k % dec.Q
-        if not with_decode:
+        # with_decode, 32 launches per id: the sampler also gathers the embedding row of the id it picked (the step's first launch), and
+        # the head kernel (the step's last) moves the row index and the sampler's step counter on
+        if self.top_p < 1.0:
+            self._sample_top_p(phase, with_decode)
+        elif not with_decode:
             call("omlm_sample_topk_gumbel_at" + self._sfx, ptr(dec.logits), *self._src, ptr(self.cur), ptr(self.hist),
                  dec.B, dec.V1, dec.ldV, self.topk, self.temperature, int(self.forbid[phase]), stream_ptr())
+        else:
+            call("omlm_sample_embed_at" + self._sfx, ptr(dec.logits), *self._src, ptr(self.cur), ptr(self.hist),
+                 dec.B, dec.V1, dec.ldV, self.topk, self.temperature, int(self.forbid[phase]),
+                 dec.emb.data_ptr(), dec.codebook * phase if dec.Q > 1 else 0, dec.emb.shape[0], ptr(dec.x), dec.D, stream_ptr())
+        if not with_decode:
             return
-        # 32 launches per id: the sampler also gathers the embedding row of the id it picked (the step's first launch), and the
-        # head kernel (the step's last) moves the row index and the sampler's step counter on
-        call("omlm_sample_embed_at" + self._sfx, ptr(dec.logits), *self._src, ptr(self.cur), ptr(self.hist),
-             dec.B, dec.V1, dec.ldV, self.topk, self.temperature, int(self.forbid[phase]),
-             dec.emb.data_ptr(), dec.codebook * phase if dec.Q > 1 else 0, dec.emb.shape[0], ptr(dec.x), dec.D, stream_ptr())
         if dec.pos_emb is not None:
             # + absolute position row of id k = n0 + (device step counter): device-side indexing, so a captured cycle stays valid
             dec.x.add_(dec.pos_emb.index_select(0, (self.step_dev + self.n0).long()))

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import List, Optional
+from typing import List, Mapping, Optional
 
 import torch
 import torch.nn.functional as F
@@ -163,7 +163,7 @@ class TokenConditionedTransformerWrapper(nn.Module):
     def generate(self, *, conditioning_token_ids: List[torch.Tensor], pred_token_ids: Optional[torch.Tensor] = None,
                  max_time_steps=512, filter_thres=0.9, temperature=1., include_eos_in_output=False,
                  append_eos_to_conditioning_tokens=True, allow_eos_in_output=False, uniforms=None, sampler_rng=None,
-                 sampler_seed=None, **kwargs):
+                 sampler_seed=None, top_p=None, **kwargs):
         """AR sampling (open_musiclm.py:253-326).  Every step re-runs the full causal forward over the grown
         sequence like the reference (results are identical to a KV-cached decode because the stack is strictly
         causal); only the last position's logits are formed, and eos suppression + top-k + Gumbel-argmax run in
@@ -171,9 +171,13 @@ class TokenConditionedTransformerWrapper(nn.Module):
         ``sampler_rng``: "buffer" draws every uniform of the call up front (torch.rand, [ids, B, V+1] floats); "counter" forms them in the
         sampler kernel from the stream of include/omlm.h, seeded by ``sampler_seed`` (None: drawn from torch's generator on the model's
         device, so torch.manual_seed governs the call either way) -- no buffer, and ids that do not depend on how the batch is cut into
-        decode calls.  None: "buffer" unless the buffer would exceed decode.UNIFORM_BUFFER_MAX_BYTES (decode.sampler_rng_choice)."""
+        decode calls.  None: "buffer" unless the buffer would exceed decode.UNIFORM_BUFFER_MAX_BYTES (decode.sampler_rng_choice).
+        ``top_p``: nucleus sampling inside the top-k set (include/omlm.h) -- of the k kept logits, ranked by value, only those are sampled
+        whose preceding softmax mass (at ``temperature``) is below top_p of the kept mass.  A number in (0, 1]; None or 1: off, the call
+        is the one it is without the argument.  Works on every route and with every source of uniforms."""
         assert len(conditioning_token_ids) == len(self.token_sequences) - 1
         ops.check_sampler_width(self.token_sequences[-1].codebook_size + 1)      # before any device work
+        top_p = ops.check_top_p(top_p)                                          # likewise; 1.0 = off
         batch, device = conditioning_token_ids[0].shape[0], self.device
         cond = [t.to(device) for t in conditioning_token_ids]
         if exists(pred_token_ids):
@@ -229,9 +233,11 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 dec = decode.CachedDecoder(self.transformer, b1 - b0, rows, self.transformer._precision(), wide=True)
                 last = dec.prefill([t[b0:b1] for t in cond] + [sampled[b0:b1]])
                 if counter:            # sample b draws u(step, b, c) whichever piece it rides in
-                    loop = decode.SamplingLoop(dec, last, None, n0, n_new, k, temperature, forbid, use_graph=use_graph, rng=(sampler_seed, b0))
+                    loop = decode.SamplingLoop(dec, last, None, n0, n_new, k, temperature, forbid, use_graph=use_graph, rng=(sampler_seed, b0),
+                                               top_p=top_p)
                 else:
-                    loop = decode.SamplingLoop(dec, last, U[:, b0:b1].contiguous(), n0, n_new, k, temperature, forbid, use_graph=use_graph)
+                    loop = decode.SamplingLoop(dec, last, U[:, b0:b1].contiguous(), n0, n_new, k, temperature, forbid, use_graph=use_graph,
+                                               top_p=top_p)
                 pieces.append(loop.run().t())                      # [b, n_new]
             sampled = torch.cat((sampled, torch.cat(pieces, dim=0)), dim=-1)
         else:
@@ -242,13 +248,19 @@ class TokenConditionedTransformerWrapper(nn.Module):
                     last = self.transformer.last_logits(cond + [sampled])
                     forbid = (not allow_eos_in_output) or (ind != Q - 1)
                     if counter:
-                        ops.sample_topk_gumbel_rng(last, sampler_seed, step, 0, nxt, V1, k, temperature, forbid)
+                        if top_p < 1.0:
+                            ops.sample(last, nxt, V1, k, temperature, forbid, top_p=top_p, seed=sampler_seed, step=step)
+                        else:
+                            ops.sample_topk_gumbel_rng(last, sampler_seed, step, 0, nxt, V1, k, temperature, forbid)
                     else:
                         if exists(uniforms):
                             u = uniforms[step].to(device).float().contiguous()
                         else:
                             u = torch.empty(batch, V1, device=device).uniform_(0, 1)
-                        ops.sample_topk_gumbel(last, u, nxt, V1, k, temperature, forbid)
+                        if top_p < 1.0:
+                            ops.sample(last, nxt, V1, k, temperature, forbid, top_p=top_p, uniform=u)
+                        else:
+                            ops.sample_topk_gumbel(last, u, nxt, V1, k, temperature, forbid)
                     sampled = torch.cat((sampled, nxt[:, None]), dim=-1)
                     step += 1
         sampled = mask_out_after_eos_id(sampled, pred_eos_id, keep_eos=include_eos_in_output)
@@ -537,6 +549,21 @@ def _unstack_windows(stacked: torch.Tensor, n_windows: int) -> List[torch.Tensor
     return list(stacked.split(stacked.shape[0] // n_windows, dim=0))
 
 
+def stage_top_p(top_p):
+    """MusicLM.forward's ``top_p`` as (semantic, coarse, fine) values for the stages' generate(): None, a number for all three, or a
+    mapping with any of "semantic" / "coarse" / "fine".  Every value is checked (ops.check_top_p); a ValueError names what is wrong."""
+    stages = ("semantic", "coarse", "fine")
+    if isinstance(top_p, Mapping):
+        unknown = sorted(set(top_p) - set(stages), key=str)
+        if unknown:
+            raise ValueError(f"top_p: unknown stage(s) {unknown}; a mapping takes any of {list(stages)}")
+        for name in stages:
+            ops.check_top_p(top_p.get(name), f"top_p[{name!r}]")
+        return tuple(top_p.get(name) for name in stages)
+    ops.check_top_p(top_p)
+    return (top_p,) * 3
+
+
 class MusicLM(nn.Module):
     """open_musiclm.py:818-1071: hierarchical semantic -> coarse -> fine sliding-window decode.
 
@@ -554,6 +581,8 @@ class MusicLM(nn.Module):
       sampler_rng     -- handed to every stage's generate(): "buffer", "counter" or None (TokenConditionedTransformerWrapper.generate).
                          With "counter" each generate call draws its own seed from torch's generator; inside one call a sample's
                          uniforms depend on its index in that call alone, not on how the call is cut into decode calls.
+      top_p           -- nucleus sampling in every stage's generate(): a number in (0, 1] for all three stages, or a mapping with any of
+                         "semantic" / "coarse" / "fine" (a stage that is not named samples without a nucleus).  None: off.
     ``generate`` is an alias of ``forward``."""
 
     def __init__(self, *, wav2vec=None, clap=None, neural_codec=None, semantic_transformer: TokenConditionedTransformer,
@@ -578,7 +607,8 @@ class MusicLM(nn.Module):
                 semantic_steps_per_second=50, acoustic_steps_per_second=75, return_coarse_generated_wave=False,
                 mask_out_generated_fine_tokens=False, semantic_sliding_window_step_percent=0.5,
                 coarse_sliding_window_step_percent=0.5, fine_sliding_window_step_percent=1,
-                clap_token_ids=None, return_tokens=False, fine_windows_together=False, sampler_rng=None):
+                clap_token_ids=None, return_tokens=False, fine_windows_together=False, sampler_rng=None, top_p=None):
+        p_sem, p_coarse, p_fine = stage_top_p(top_p)                               # refused by name before any work
         if not exists(clap_token_ids):
             assert exists(text), 'text needs to be passed in if one of the transformer requires conditioning'
             clap_token_ids = get_or_compute_clap_token_ids(None, self.clap, conditioning_audio=None, conditioning_text=text)
@@ -612,12 +642,14 @@ class MusicLM(nn.Module):
         # ---- semantic stage (:930-952): one window, then 50%-overlap continuation windows ----
         sem = self.semantic.generate(clap_token_ids=clap_token_ids, semantic_token_ids=prime_sem,
                                      max_time_steps=int(min(output_seconds, semantic_window_seconds) * sem_hz),
-                                     include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng)
+                                     include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng,
+                                     top_p=p_sem)
         while sem.shape[1] < int(output_seconds * sem_hz):
             keep = int(semantic_window_seconds * sem_hz * (1 - semantic_sliding_window_step_percent))
             nxt = self.semantic.generate(clap_token_ids=clap_token_ids, semantic_token_ids=sem[:, -keep:],
                                          max_time_steps=int(semantic_window_seconds * sem_hz),
-                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng)
+                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng,
+                                         top_p=p_sem)
             sem = torch.cat([sem, nxt[:, keep:]], dim=1)
         sem_all = sem
         sem = sem[:, sem_adjust:]
@@ -635,7 +667,7 @@ class MusicLM(nn.Module):
                                         coarse_token_ids=cond_coarse,
                                         max_time_steps=int(coarse_window_seconds * ac_hz), reconstruct_wave=False,
                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True,
-                                        temperature=0.95, sampler_rng=sampler_rng)
+                                        temperature=0.95, sampler_rng=sampler_rng, top_p=p_coarse)
             coarse = pred if not exists(coarse) else torch.cat([coarse, pred[:, keep:]], dim=1)
         if return_coarse_generated_wave:
             return self.neural_codec.decode_from_codebook_indices(coarse).squeeze(1)
@@ -651,7 +683,7 @@ class MusicLM(nn.Module):
             pred = self.fine.generate(clap_token_ids=clap_token_ids.repeat(len(coarse_wins), *([1] * (clap_token_ids.dim() - 1))),
                                       coarse_token_ids=_stack_windows(coarse_wins), fine_token_ids=None,
                                       max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
-                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng)
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine)
             fine = torch.cat(_unstack_windows(pred, len(coarse_wins)), dim=1)
             coarse_wins = []
         for coarse_win in coarse_wins:
@@ -662,7 +694,7 @@ class MusicLM(nn.Module):
                 keep, cond_fine = 0, prime_fine
             pred = self.fine.generate(clap_token_ids=clap_token_ids, coarse_token_ids=coarse_win, fine_token_ids=cond_fine,
                                       max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
-                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng)
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine)
             fine = pred if not exists(fine) else torch.cat([fine, pred[:, keep:]], dim=1)
         fine = fine[:, fine_adjust:]
         if exists(prime_coarse_all) and exists(prime_fine_all):

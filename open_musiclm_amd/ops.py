@@ -818,5 +818,47 @@ def sample_topk_gumbel_rng(logits, seed, step, row0, out, V, k, temperature, for
          int(forbid_last), stream_ptr())
 
 
+class SampleArgs(C.Structure):
+    """Mirror of ``omlm_sample_args`` (include/omlm.h)."""
+    _fields_ = [("logits", C.c_void_p), ("B", C.c_int), ("V", C.c_int), ("ld", C.c_int),
+                ("uniform", C.c_void_p), ("seed_lo", C.c_uint), ("seed_hi", C.c_uint), ("step", C.c_int), ("row0", C.c_int),
+                ("step_dev", C.c_void_p), ("out", C.c_void_p), ("hist", C.c_void_p),
+                ("k", C.c_int), ("temperature", C.c_float), ("top_p", C.c_float), ("forbid_last", C.c_int),
+                ("emb_table", C.c_void_p), ("emb_row_offset", C.c_longlong), ("emb_rows", C.c_longlong), ("x", C.c_void_p), ("D", C.c_int)]
+
+
+def check_top_p(top_p, name="top_p"):
+    """The nucleus mass as the kernels take it: None -> 1.0 (no nucleus), a number in (0, 1] -> float; anything else (<= 0, > 1, NaN,
+    not a number) raises a ValueError that names the argument.  Pure Python: runs before any device work."""
+    if top_p is None:
+        return 1.0
+    try:
+        p = float(top_p)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name} must be None or a number in (0, 1], not {top_p!r}") from None
+    if not (0.0 < p <= 1.0):
+        raise ValueError(f"{name} must be None or a number in (0, 1], not {top_p!r}")
+    return p
+
+
+def sample(logits, out, V, k, temperature, forbid_last, *, top_p=None, uniform=None, seed=None, step=0, row0=0, step_dev=None,
+           hist=None, emb_table=None, emb_row_offset=0, x=None):
+    """omlm_sample: the sampler with an optional nucleus, one call over every form.  ``uniform`` ([B, V], or [steps, B, V] with
+    ``step_dev``) or ``seed`` (the counter stream: row b draws u(step or *step_dev, row0 + b, c)) -- exactly one of the two;
+    ``step_dev`` (int32 [1], device) selects the graph-replayable form, where ``hist`` is [steps, B]; ``emb_table`` [rows, D] with ``x``
+    [B, D] adds the embedding gather.  top_p None or 1: the launch of sample_topk_gumbel*."""
+    check_sampler_width(V)
+    p = check_top_p(top_p)
+    if (uniform is None) == (seed is None):
+        raise ValueError("sample: give either uniform= or seed=, not both and not neither")
+    B, ld = logits.shape
+    lo, hi = split_seed(seed) if seed is not None else (0, 0)
+    a = SampleArgs(ptr(logits), B, int(V), ld, ptr(uniform), lo, hi, int(step), int(row0), ptr(step_dev), ptr(out), ptr(hist),
+                   int(k), float(temperature), p, int(forbid_last),
+                   ptr(emb_table), int(emb_row_offset), 0 if emb_table is None else emb_table.shape[0], ptr(x),
+                   0 if emb_table is None else emb_table.shape[1])
+    call("omlm_sample", C.addressof(a), stream_ptr())
+
+
 def probe_tr16(out):
     call("omlm_probe_tr16", ptr(out), stream_ptr())
