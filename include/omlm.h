@@ -499,9 +499,14 @@ int omlm_sample(const omlm_sample_args* args, void* stream);
 
 /* KV-cached AR decode step: ONE new row (index *pos_dev) per sample through all L layers and the logit head of the quantizer
  * that row predicts -- replaces the reference's full re-forward per sampled id (wrapper.generate, open_musiclm.py:301-321;
- * the trunk is strictly causal, so the logits are the same).  State owned by the caller, all fp32:
- *   Kc/Vc[l]  [B, Nmax, 64]   l2-normalised keys / values of rows < pos (row `pos` is appended by this call)
- *   hist[l]   [B, 2, 2*Fp]    FF-in outputs of rows pos-2, pos-1 (conv state; advanced by this call)
+ * the trunk is strictly causal, so the logits are the same).  State owned by the caller:
+ *   Kc/Vc[l]  [B, Nmax, 64]   l2-normalised keys / values of rows < pos (row `pos` is appended by this call): fp32, or with kv16 != 0
+ *                             the 16-bit operand type of w_dtype (bf16 / fp16), the pointers then cast to float*
+ *   hist[l]   [B, 2, 2*Fp]    fp32 FF-in outputs of rows pos-2, pos-1 (conv state; advanced by this call)
+ * With 16-bit weights and round_bf16 = 1 the step rounds every key (after its l2 normalisation) and every value to the operand type before
+ * it stores them, so the 16-bit cache holds the fp32 cache's numbers in half the bytes: same logits, bit for bit.  The one number that
+ * must not pass through 16 bits is the step's RAW key: with kv16 it waits in k_new [B, 64] fp32 until the attention kernel has normalised
+ * it.  kv16 is refused (an argument error, before any launch) with w_dtype == 0, with round_bf16 == 0 or without k_new.
  * Pointer-array members are HOST arrays of L device pointers.  w_dtype 0: fp32 weights, 1: bf16 operand copies (then
  * round_bf16 = 1 rounds the activations the batched path keeps in bf16).  W1p [2*Fp, D] / W2p [D, Fp] / convw [3, 2*Fp] /
  * mid_gamma [Fp] are the padded layouts of omlm_ffmid_fwd.  emb_table (optional): x = emb_table[ids[b] + emb_row_offset]
@@ -546,6 +551,9 @@ typedef struct omlm_decode_args {
      * counts per sample in the same array; B > 16: OMLM_DECODE_SPLITK_FLOATS_B / OMLM_DECODE_SPLITK_CNT_B), ZERO before the first step
      * (every step leaves them zero).  One decode stream at a time per scratch pair.  NULL: one workgroup per tile walks the whole row. */
     float* splitk_ws; int* splitk_cnt;
+    /* kv16 != 0: Kc[l] / Vc[l] hold the 16-bit operand type (see above); k_new: fp32 scratch [B, 64] for the step's raw key, contents
+     * irrelevant between steps.  kv16 == 0: fp32 caches, k_new unused (may be NULL). */
+    int kv16; float* k_new;
 } omlm_decode_args;
 #define OMLM_DECODE_SPLITK_FLOATS(D) (4 * (((D) + 15) / 16) * 256)
 #define OMLM_DECODE_LN_PARTS(D, Fp) ((((D) + 15) / 16 > ((Fp) + 7) / 8 ? ((D) + 15) / 16 : ((Fp) + 7) / 8) * 32)

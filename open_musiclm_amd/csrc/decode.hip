@@ -4,7 +4,8 @@
 // (open_musiclm.py:301-321: no KV cache).  Every op of the trunk is causal -- attention (transformer.py:303-331), the
 // depthwise conv of ConvFeedForward (left pad 2, :122-137), LayerNorm per token -- so row p depends on rows <= p only,
 // and the same logits are obtained by computing ONE new row per step against
-//   * the l2-normalised keys / values of rows < p          (K/V cache, fp32, [B, Nmax, 64] per layer), and
+//   * the l2-normalised keys / values of rows < p          (K/V cache, [B, Nmax, 64] per layer: fp32, or the 16-bit operand type
+//                                                            with omlm_decode_args::kv16 -- the same numbers, see new_kv_store), and
 //   * the FF-in outputs of rows p-2, p-1                    (conv state,  fp32, [B, 2, 2*Fp] per layer).
 // One step is weight-bandwidth and latency bound (all 91.6 M parameters are read once for up to 8 samples), so:
 //   * the projections are skinny GEMVs on the vector ALUs, 16 weight rows per workgroup (hundreds of workgroups keep
@@ -54,9 +55,23 @@ struct omlm_decode_args {
     // splitk_ws 4 * ceil(D / 16) * 256 floats, contents irrelevant; splitk_cnt max(ceil(D / 16), 16) ints (the attention combine counts per sample in it too), ZERO before the first step (every launch
     // leaves them zero)
     float* splitk_ws; int* splitk_cnt;
+    // kv16 != 0: Kc[l] / Vc[l] are h16_t [B, Nmax, 64] (needs 16-bit weights and round_bf16: every cached value is then a 16-bit number
+    // already); k_new: fp32 [B, 64], where the step's raw key waits for the attention kernel that normalises it
+    int kv16; float* k_new;
 };
 
 __device__ __forceinline__ float round_if(float v, int on) { return on ? (float)(h16_t)v : v; }
+
+// Element c (0..63 raw key, 64..127 value) of the new row's [k_raw | v], cache row `row` = b * Nmax + pos of sample b.  fp32 cache: the raw
+// key goes to the cache row (the attention kernel normalises it in place).  16-bit cache (kv16): the raw key must reach that kernel
+// un-rounded, so it waits in k_new[b, 64]; the value is rounded to the operand type either way, so its 16-bit store is exact.
+__device__ __forceinline__ void new_kv_store(void* Kc, void* Vc, float* k_new, int kv16, size_t row, int b, int c, float v, int round_bf16) {
+    if (c < 64) {
+        if (kv16) k_new[(size_t)b * 64 + c] = v;
+        else ((float*)Kc)[row * 64 + c] = v;                                          // raw: normalised by dec_attn
+    } else if (kv16) ((h16_t*)Vc)[row * 64 + (c - 64)] = (h16_t)v;
+    else ((float*)Vc)[row * 64 + (c - 64)] = round_if(v, round_bf16);
+}
 
 __device__ __forceinline__ void load_w8(const float* p, float* w) {
     const float4 a = ((const float4*)p)[0], b = ((const float4*)p)[1];
@@ -216,9 +231,9 @@ __global__ __launch_bounds__(DEC_T) void dec_rowstat_kernel(const float* __restr
 template <typename TW>
 __global__ __launch_bounds__(DEC_T) void dec_qkv_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                        const TW* __restrict__ Wq, const TW* __restrict__ Wkv,
-                                                       float* __restrict__ q, float* __restrict__ Kc, float* __restrict__ Vc,
+                                                       float* __restrict__ q, void* __restrict__ Kc, void* __restrict__ Vc,
                                                        int B, int D, int H, int Nmax, const int* __restrict__ pos_dev, float eps,
-                                                       int round_bf16) {
+                                                       int round_bf16, float* __restrict__ k_new, int kv16) {
     extern __shared__ __attribute__((aligned(16))) float dsm[];
     float* xs = dsm;                                   // [B][D]
     float* vals = xs + (size_t)B * D;                  // [16][DEC_BMAX]
@@ -234,8 +249,7 @@ __global__ __launch_bounds__(DEC_T) void dec_qkv_kernel(const float* __restrict_
         const int b = idx / DEC_ROWS, r = idx - b * DEC_ROWS, n = n0 + r;
         const float v = vals[r * DEC_BMAX + b];
         if (isq) q[(size_t)b * HD + n] = v;
-        else if (n < HD + 64) Kc[((size_t)b * Nmax + pos) * 64 + (n - HD)] = v;                       // raw: normalised by dec_attn
-        else Vc[((size_t)b * Nmax + pos) * 64 + (n - HD - 64)] = round_if(v, round_bf16);
+        else new_kv_store(Kc, Vc, k_new, kv16, (size_t)b * Nmax + pos, b, n - HD, v, round_bf16);
     }
 }
 
@@ -243,11 +257,17 @@ __global__ __launch_bounds__(DEC_T) void dec_qkv_kernel(const float* __restrict_
 //   part[b][s][h] = { m = max_j s_j,  l = sum_j e^(s_j - m),  o[d] = sum_j e^(s_j - m) v_j[d] },  s_j = scale <q_h, k_j> + bias[pos - j, h]
 // The split that holds row `pos` finds it un-normalised (written by dec_qkv this step): it l2-normalises it, uses it and
 // stores it back, so the cache holds final keys from then on.  q is l2-normalised here as well.
-__global__ __launch_bounds__(DEC_T) void dec_attn_kernel(const float* __restrict__ q, float* __restrict__ Kc,
-                                                        const float* __restrict__ Vc, const float* __restrict__ q_scale,
+// TC = h16_t (omlm_decode_args::kv16): the cache rows are 16-bit, read as 16-byte chunks of 8 elements and widened on the way into the same
+// fp32 LDS tiles; the raw key comes from k_new[b, 64] (fp32, never rounded before it is normalised) and row `pos` of the cache is only
+// written.  Every cached value is a 16-bit number in either cache, so the two instantiations compute the same bits.
+template <typename TC>
+__global__ __launch_bounds__(DEC_T) void dec_attn_kernel(const float* __restrict__ q, TC* __restrict__ Kc,
+                                                        const TC* __restrict__ Vc, const float* __restrict__ q_scale,
                                                         const float* __restrict__ k_scale, const float* __restrict__ bias, int bias_ld,
                                                         float* __restrict__ parts, int H, int Nmax, int nsplit,
-                                                        const int* __restrict__ pos_dev, float scale, int round_bf16) {
+                                                        const int* __restrict__ pos_dev, float scale, int round_bf16,
+                                                        const float* __restrict__ k_new) {
+    constexpr bool KV16 = !std::is_same<TC, float>::value;
     extern __shared__ __attribute__((aligned(16))) float dsm[];
     const int pos = *pos_dev;
     const int s = blockIdx.x, b = blockIdx.y;
@@ -264,23 +284,38 @@ __global__ __launch_bounds__(DEC_T) void dec_attn_kernel(const float* __restrict
         const float nrm = fmaxf(sqrtf(wave_sum(v * v)), 1e-12f);
         qn[h * 64 + lane] = round_if(v / nrm * q_scale[lane], round_bf16);
     }
-    float* Kb = Kc + ((size_t)b * Nmax + j0) * 64;
-    const float* Vb = Vc + ((size_t)b * Nmax + j0) * 64;
-    for (int idx = threadIdx.x; idx < nk * 16; idx += DEC_T) {            // coalesced float4 rows
-        const int j = idx >> 4, c = idx & 15;
-        const float4 kk = ((const float4*)(Kb + (size_t)j * 64))[c];
-        const float4 vv = ((const float4*)(Vb + (size_t)j * 64))[c];
-        Ks[j * 65 + 4 * c] = kk.x; Ks[j * 65 + 4 * c + 1] = kk.y; Ks[j * 65 + 4 * c + 2] = kk.z; Ks[j * 65 + 4 * c + 3] = kk.w;
-        *(float4*)(Vs + j * 64 + 4 * c) = vv;
+    TC* Kb = Kc + ((size_t)b * Nmax + j0) * 64;
+    const TC* Vb = Vc + ((size_t)b * Nmax + j0) * 64;
+    if constexpr (!KV16) {
+        for (int idx = threadIdx.x; idx < nk * 16; idx += DEC_T) {        // coalesced float4 rows
+            const int j = idx >> 4, c = idx & 15;
+            const float4 kk = ((const float4*)(Kb + (size_t)j * 64))[c];
+            const float4 vv = ((const float4*)(Vb + (size_t)j * 64))[c];
+            Ks[j * 65 + 4 * c] = kk.x; Ks[j * 65 + 4 * c + 1] = kk.y; Ks[j * 65 + 4 * c + 2] = kk.z; Ks[j * 65 + 4 * c + 3] = kk.w;
+            *(float4*)(Vs + j * 64 + 4 * c) = vv;
+        }
+    } else {
+        for (int idx = threadIdx.x; idx < nk * 8; idx += DEC_T) {         // coalesced 16-byte chunks: 8 per 128-byte row
+            const int j = idx >> 3, c = idx & 7;
+            float kf[8], vf[8];
+            load_w8(Kb + (size_t)j * 64 + 8 * c, kf);                     // (row pos - j0 is stale here; replaced below)
+            load_w8(Vb + (size_t)j * 64 + 8 * c, vf);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) Ks[j * 65 + 8 * c + e] = kf[e];
+            *(float4*)(Vs + j * 64 + 8 * c) = make_float4(vf[0], vf[1], vf[2], vf[3]);
+            *(float4*)(Vs + j * 64 + 8 * c + 4) = make_float4(vf[4], vf[5], vf[6], vf[7]);
+        }
     }
     __syncthreads();
     if (pos - j0 < DEC_KS && wave == 0) {                                 // the new key: normalise once, keep it in the cache
         const int j = pos - j0;
-        const float v = Ks[j * 65 + lane];
+        float v;
+        if constexpr (KV16) v = k_new[(size_t)b * 64 + lane];
+        else v = Ks[j * 65 + lane];
         const float nrm = fmaxf(sqrtf(wave_sum(v * v)), 1e-12f);
         const float kn = round_if(v / nrm * k_scale[lane], round_bf16);
         Ks[j * 65 + lane] = kn;
-        Kb[(size_t)j * 64 + lane] = kn;
+        Kb[(size_t)j * 64 + lane] = (TC)kn;                               // (kn is a 16-bit number already: exact)
     }
     __syncthreads();
     for (int h = wave; h < H; h += 4) {                                   // one wave per head: lane = key
@@ -315,12 +350,18 @@ __global__ __launch_bounds__(DEC_T) void dec_attn_kernel(const float* __restrict
 // comb_out / comb_cnt (optional; the batched matrix-core step): the workgroups of a sample count their arrivals in comb_cnt[b] (zero on
 // entry and exit) and the last one combines the sample's partials into comb_out[b, H * 64] -- what dec_attn_combine_kernel did as a
 // launch of its own (5 us of every layer's ~50).  comb_out may be q's buffer: every reader of q[b, :] has arrived by then.
-__global__ __launch_bounds__(DEC_AT2) void dec_attn2_kernel(const float* q, float* __restrict__ Kc,
-                                                           const float* __restrict__ Vc, const float* __restrict__ q_scale,
+// TC = h16_t (omlm_decode_args::kv16): 16-bit cache rows.  A thread loads ONE 16-byte chunk of K and of V (8 chunks per 128-byte row, 64
+// rows in one pass) and widens it into the same fp32 LDS tiles.  The raw key waits in k_new[b, 64] as fp32: the 16 lanes that would hold
+// its row in the fp32 instantiation load it as float4s and normalise it in that instantiation's order (four squares per lane, then the
+// xor-1, 2, 4, 8 swaps), so both caches receive the same 16-bit key and every later operation sees the same operands.
+template <typename TC>
+__global__ __launch_bounds__(DEC_AT2) void dec_attn2_kernel(const float* q, TC* __restrict__ Kc,
+                                                           const TC* __restrict__ Vc, const float* __restrict__ q_scale,
                                                            const float* __restrict__ k_scale, const float* __restrict__ bias, int bias_ld,
                                                            float* parts, int H, int Nmax, int nsplit,
                                                            const int* __restrict__ pos_dev, float scale, int round_bf16,
-                                                           float* comb_out, int* comb_cnt) {
+                                                           float* comb_out, int* comb_cnt, const float* __restrict__ k_new) {
+    constexpr bool KV16 = !std::is_same<TC, float>::value;
     extern __shared__ __attribute__((aligned(16))) float dsm[];
     const int pos = *pos_dev;
     const int s = blockIdx.x, b = blockIdx.y;
@@ -332,17 +373,26 @@ __global__ __launch_bounds__(DEC_AT2) void dec_attn2_kernel(const float* q, floa
     float* qn = Vs + 64 * 64;               // [H][64]
     float* sc = qn + H * 64;                // [8 waves][64]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float* Kb = Kc + ((size_t)b * Nmax + j0) * 64;
-    const float* Vb = Vc + ((size_t)b * Nmax + j0) * 64;
+    TC* Kb = Kc + ((size_t)b * Nmax + j0) * 64;
+    const TC* Vb = Vc + ((size_t)b * Nmax + j0) * 64;
     // ---- all global loads first ----
-    float4 kk[2], vv[2];
-    const int c16 = threadIdx.x & 15;
+    float4 kk[2], vv[2];                                        // fp32 cache: two rows of 16 float4s per 16 lanes
+    u32x4 kh, vh;                                               // 16-bit cache: one chunk of 8 elements of row threadIdx.x >> 3
+    const int c16 = threadIdx.x & 15, c8 = threadIdx.x & 7;
+    const int jn = pos - j0;                                    // tile row of the new key (>= DEC_KS: another range holds it)
+    if constexpr (!KV16) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int j = (threadIdx.x >> 4) + 32 * i;
-        const int jj = min(j, nk - 1);
-        kk[i] = ((const float4*)(Kb + (size_t)jj * 64))[c16];
-        vv[i] = ((const float4*)(Vb + (size_t)jj * 64))[c16];
+        for (int i = 0; i < 2; ++i) {
+            const int j = (threadIdx.x >> 4) + 32 * i;
+            const int jj = min(j, nk - 1);
+            kk[i] = ((const float4*)(Kb + (size_t)jj * 64))[c16];
+            vv[i] = ((const float4*)(Vb + (size_t)jj * 64))[c16];
+        }
+    } else {
+        const int jj = min((int)(threadIdx.x >> 3), nk - 1);     // (a clamped row is dropped below; rows <= pos < Nmax only)
+        kh = *(const u32x4*)(Kb + (size_t)jj * 64 + 8 * c8);
+        vh = *(const u32x4*)(Vb + (size_t)jj * 64 + 8 * c8);
+        kk[0] = ((const float4*)(k_new + (size_t)b * 64))[c16];  // the raw key, fp32 (used where jn < DEC_KS)
     }
     const float4 ks4 = ((const float4*)k_scale)[c16];
     float qv[2] = {0.f, 0.f};
@@ -354,21 +404,43 @@ __global__ __launch_bounds__(DEC_AT2) void dec_attn2_kernel(const float* q, floa
         qn[h * 64 + lane] = round_if(qv[i] / nrm * qs, round_bf16);
     }
     // ---- K / V tiles to LDS; the row written by dec_qkv this step is raw: normalise it here, keep it in the cache ----
+    if constexpr (!KV16) {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int j = (threadIdx.x >> 4) + 32 * i;
-        float4 kx = kk[i];
-        if (j == pos - j0) {                                    // uniform over the 16 lanes that hold this row
+        for (int i = 0; i < 2; ++i) {
+            const int j = (threadIdx.x >> 4) + 32 * i;
+            float4 kx = kk[i];
+            if (j == pos - j0) {                                    // uniform over the 16 lanes that hold this row
+                float ss = kx.x * kx.x + kx.y * kx.y + kx.z * kx.z + kx.w * kx.w;
+                ss += __shfl_xor(ss, 1, 64); ss += __shfl_xor(ss, 2, 64); ss += __shfl_xor(ss, 4, 64); ss += __shfl_xor(ss, 8, 64);
+                const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+                kx.x = round_if(kx.x * inv * ks4.x, round_bf16); kx.y = round_if(kx.y * inv * ks4.y, round_bf16);
+                kx.z = round_if(kx.z * inv * ks4.z, round_bf16); kx.w = round_if(kx.w * inv * ks4.w, round_bf16);
+                ((float4*)(Kb + (size_t)j * 64))[c16] = kx;
+            }
+            if (j < nk) {
+                Ks[j * 65 + 4 * c16] = kx.x; Ks[j * 65 + 4 * c16 + 1] = kx.y; Ks[j * 65 + 4 * c16 + 2] = kx.z; Ks[j * 65 + 4 * c16 + 3] = kx.w;
+                *(float4*)(Vs + j * 64 + 4 * c16) = vv[i];
+            }
+        }
+    } else {
+        if ((int)(threadIdx.x >> 4) == (jn & 31) && jn < DEC_KS) {  // the 16 lanes that hold row jn above: same lanes, same order, same bits
+            float4 kx = kk[0];
             float ss = kx.x * kx.x + kx.y * kx.y + kx.z * kx.z + kx.w * kx.w;
             ss += __shfl_xor(ss, 1, 64); ss += __shfl_xor(ss, 2, 64); ss += __shfl_xor(ss, 4, 64); ss += __shfl_xor(ss, 8, 64);
             const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
             kx.x = round_if(kx.x * inv * ks4.x, round_bf16); kx.y = round_if(kx.y * inv * ks4.y, round_bf16);
             kx.z = round_if(kx.z * inv * ks4.z, round_bf16); kx.w = round_if(kx.w * inv * ks4.w, round_bf16);
-            ((float4*)(Kb + (size_t)j * 64))[c16] = kx;
+            store4_from_float(Kb + (size_t)jn * 64 + 4 * c16, kx.x, kx.y, kx.z, kx.w);      // (16-bit numbers already: exact)
+            Ks[jn * 65 + 4 * c16] = kx.x; Ks[jn * 65 + 4 * c16 + 1] = kx.y; Ks[jn * 65 + 4 * c16 + 2] = kx.z; Ks[jn * 65 + 4 * c16 + 3] = kx.w;
         }
+        const int j = threadIdx.x >> 3;
         if (j < nk) {
-            Ks[j * 65 + 4 * c16] = kx.x; Ks[j * 65 + 4 * c16 + 1] = kx.y; Ks[j * 65 + 4 * c16 + 2] = kx.z; Ks[j * 65 + 4 * c16 + 3] = kx.w;
-            *(float4*)(Vs + j * 64 + 4 * c16) = vv[i];
+            if (j != jn) {                                          // (row jn of the cache is stale until the store above)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { Ks[j * 65 + 8 * c8 + 2 * e] = h16_lo_to_f(kh[e]); Ks[j * 65 + 8 * c8 + 2 * e + 1] = h16_hi_to_f(kh[e]); }
+            }
+            *(float4*)(Vs + j * 64 + 8 * c8) = make_float4(h16_lo_to_f(vh[0]), h16_hi_to_f(vh[0]), h16_lo_to_f(vh[1]), h16_hi_to_f(vh[1]));
+            *(float4*)(Vs + j * 64 + 8 * c8 + 4) = make_float4(h16_lo_to_f(vh[2]), h16_hi_to_f(vh[2]), h16_lo_to_f(vh[3]), h16_hi_to_f(vh[3]));
         }
     }
     __syncthreads();
@@ -588,7 +660,8 @@ struct dec2_args {
     const void* W; const void* W2; long long ldw; int Nout;                       // weight rows (W2: the Wkv rows of DEC2_QKV)
     const void* Wlo;                                                              // PL instantiations ("fp16ff"): lo plane of W, same layout -- the row is W + Wlo
     const float* res; int ldres; float* out; int ldout;                           // out = dot (+ res)
-    float* q; float* Kc; float* Vc; int Nmax;                                     // DEC2_QKV destinations
+    float* q; void* Kc; void* Vc; int Nmax;                                       // DEC2_QKV destinations (cache rows: fp32, or h16_t with kv16)
+    float* k_new; int kv16;                                                       // kv16: the raw key goes to k_new [B, 64] (new_kv_store)
     const float* convw; float* hist; float* u; int Fp;                            // DEC2_FFIN
     int B, round_bf16;
     int* adv_pos; int* adv_step;                                                  // head launch only: counters bumped by its workgroup 0
@@ -703,8 +776,7 @@ __global__ __launch_bounds__(DEC_T) void dec2_kernel(dec2_args a) {
             const int b = idx / DEC2_ROWS, r = idx - b * DEC2_ROWS, n = blockIdx.x * DEC2_ROWS + r;
             const float v = vals[r * DEC_BMAX + b];
             if (n < HD) a.q[(size_t)b * HD + n] = v;
-            else if (n < HD + 64) a.Kc[((size_t)b * a.Nmax + pos) * 64 + (n - HD)] = v;                  // raw: normalised by dec_attn
-            else a.Vc[((size_t)b * a.Nmax + pos) * 64 + (n - HD - 64)] = round_if(v, a.round_bf16);
+            else new_kv_store(a.Kc, a.Vc, a.k_new, a.kv16, (size_t)b * a.Nmax + pos, b, n - HD, v, a.round_bf16);
         }
     } else {
         for (int idx = threadIdx.x; idx < B * DEC2_ROWS; idx += DEC_T) {
@@ -820,8 +892,7 @@ __global__ __launch_bounds__(DEC_T) void dec3_kernel(dec2_args a) {
     if (lane != 0) return;
     if (MODE == DEC2_QKV) {
         if (unit < HD) a.q[unit] = acc;
-        else if (unit < HD + 64) a.Kc[(size_t)pos * 64 + (unit - HD)] = acc;                     // raw: normalised by dec_attn
-        else a.Vc[(size_t)pos * 64 + (unit - HD - 64)] = round_if(acc, a.round_bf16);
+        else new_kv_store(a.Kc, a.Vc, a.k_new, a.kv16, (size_t)pos, 0, unit - HD, acc, a.round_bf16);
     } else {
         a.out[unit] = acc + resv;
         // last kernel of a step (the head): move the row index / sampler step on here instead of in a launch of its own.  Nothing in
@@ -982,7 +1053,11 @@ __global__ __launch_bounds__(DEC4_T) void dec4_kernel(dec2_args a) {
         a.in += s0 * a.ldin;
         if (a.res) a.res += s0 * a.ldres;
         if (a.out) a.out += s0 * a.ldout;
-        if (MODE == DEC2_QKV) { a.q += s0 * a.H * 64; a.Kc += s0 * a.Nmax * 64; a.Vc += s0 * a.Nmax * 64; }
+        if (MODE == DEC2_QKV) {
+            const size_t kvb = s0 * a.Nmax * 64 * (a.kv16 ? sizeof(h16_t) : sizeof(float));      // the group's first cache row, in bytes of the cache type
+            a.q += s0 * a.H * 64; a.Kc = (char*)a.Kc + kvb; a.Vc = (char*)a.Vc + kvb;
+            if (a.kv16) a.k_new += s0 * 64;
+        }
         if (MODE == DEC2_FFIN) { a.hist += s0 * 4 * a.Fp; a.u += s0 * a.Fp; }
         if (a.stat_in) a.stat_in += (size_t)g * a.gstat;
         if (a.stat_out) a.stat_out += (size_t)g * a.gstat;
@@ -1347,8 +1422,7 @@ __global__ __launch_bounds__(DEC4_T) void dec4_kernel(dec2_args a) {
             const int b = idx / DEC4_ROWS, rr = idx - b * DEC4_ROWS, n = blockIdx.x * DEC4_ROWS + rr;
             const float v = vals[rr * 16 + b];
             if (n < HD) a.q[(size_t)b * HD + n] = v;
-            else if (n < HD + 64) a.Kc[((size_t)b * a.Nmax + pos) * 64 + (n - HD)] = v;                  // raw: normalised by dec_attn
-            else if (n < HD + 128) a.Vc[((size_t)b * a.Nmax + pos) * 64 + (n - HD - 64)] = round_if(v, a.round_bf16);
+            else if (n < HD + 128) new_kv_store(a.Kc, a.Vc, a.k_new, a.kv16, (size_t)b * a.Nmax + pos, b, n - HD, v, a.round_bf16);
         }
     } else {
         for (int idx = threadIdx.x; idx < B * DEC4_ROWS; idx += DEC4_T) {
@@ -1446,15 +1520,22 @@ static int decode_step2_t(const omlm_decode_args& a, const long long* ids, hipSt
     for (int l = 0; l < a.L; ++l) {
         dec2_args q = g;                                                               // q / k / v rows of the new token
         q.in = a.x; q.ldin = D; q.K = D; q.Kstat = D; q.gamma = a.attn_gamma[l]; q.W = a.Wq[l]; q.W2 = a.Wkv[l]; q.ldw = D;
-        q.Nout = HD + 128; q.q = a.q; q.Kc = a.Kc[l]; q.Vc = a.Vc[l];
+        q.Nout = HD + 128; q.q = a.q; q.Kc = a.Kc[l]; q.Vc = a.Vc[l]; q.k_new = a.k_new; q.kv16 = a.kv16;
         if (st_x && n_x > 0) { q.stat_in = st_x; q.nstat_in = n_x; }
         if (B == 1) dec3_launch<TW, 2, DEC2_QKV>(q, HD + 128, st);
         else if (mfma) dec4_launch<8, DEC2_QKV>(q, (HD + 128) / DEC4_ROWS, st);
         else        dec2_launch<TW, 2, DEC2_QKV>(q, (HD + 128) / DEC2_ROWS, st);
         const bool comb_in_attn = mfma && a.splitk_cnt != nullptr;                     // the last workgroup of a sample combines its partials
-        hipLaunchKernelGGL(dec_attn2_kernel, dim3(a.nsplit, B), dim3(DEC_AT2), lds_at2, st, a.q, a.Kc[l], a.Vc[l], a.q_scale[l], a.k_scale[l],
-                           a.bias_table, a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16,
-                           comb_in_attn ? a.q : (float*)nullptr, comb_in_attn ? a.splitk_cnt : (int*)nullptr);
+        float* const comb_out = comb_in_attn ? a.q : nullptr;
+        int* const comb_cnt = comb_in_attn ? a.splitk_cnt : nullptr;
+        if (a.kv16)
+            hipLaunchKernelGGL(dec_attn2_kernel<h16_t>, dim3(a.nsplit, B), dim3(DEC_AT2), lds_at2, st, a.q, (h16_t*)a.Kc[l], (const h16_t*)a.Vc[l],
+                               a.q_scale[l], a.k_scale[l], a.bias_table, a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16,
+                               comb_out, comb_cnt, a.k_new);
+        else
+            hipLaunchKernelGGL(dec_attn2_kernel<float>, dim3(a.nsplit, B), dim3(DEC_AT2), lds_at2, st, a.q, a.Kc[l], (const float*)a.Vc[l],
+                               a.q_scale[l], a.k_scale[l], a.bias_table, a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16,
+                               comb_out, comb_cnt, (const float*)nullptr);
         dec2_args o = g;                                                               // x1 = x + attn Wo^T
         o.K = HD; o.parts = a.parts; o.W = a.Wo[l]; o.ldw = HD; o.Nout = D; o.res = a.x; o.ldres = D; o.out = a.x1; o.ldout = D;
         if (mfma) {                                                                    // combine once, then a plain (no LayerNorm) row product
@@ -1542,7 +1623,8 @@ static int decode_step_t(const omlm_decode_args& a, const long long* ids, hipStr
         (void)hipFuncSetAttribute((const void*)dec_gemv_kernel<TW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)dec_qkv_kernel<TW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)dec_ffin_kernel<TW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)dec_attn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)dec_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)dec_attn_kernel<h16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         attr = true;
     }
     const int HD = H * 64;
@@ -1552,9 +1634,16 @@ static int decode_step_t(const omlm_decode_args& a, const long long* ids, hipStr
         hipLaunchKernelGGL(dec_embed_kernel, dim3(B), dim3(DEC_T), 0, st, ids, a.emb_table, a.emb_row_offset, a.emb_rows, a.x, D, (float*)nullptr, 0);
     for (int l = 0; l < a.L; ++l) {
         hipLaunchKernelGGL((dec_qkv_kernel<TW>), dim3((HD + 128) / DEC_ROWS), dim3(DEC_T), lds_d, st, a.x, a.attn_gamma[l],
-                           (const TW*)a.Wq[l], (const TW*)a.Wkv[l], a.q, a.Kc[l], a.Vc[l], B, D, H, a.Nmax, a.pos_dev, a.eps, a.round_bf16);
-        hipLaunchKernelGGL(dec_attn_kernel, dim3(a.nsplit, B), dim3(DEC_T), lds_at, st, a.q, a.Kc[l], a.Vc[l], a.q_scale[l], a.k_scale[l],
-                           a.bias_table, a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16);
+                           (const TW*)a.Wq[l], (const TW*)a.Wkv[l], a.q, (void*)a.Kc[l], (void*)a.Vc[l], B, D, H, a.Nmax, a.pos_dev, a.eps,
+                           a.round_bf16, a.k_new, a.kv16);
+        if (a.kv16)
+            hipLaunchKernelGGL(dec_attn_kernel<h16_t>, dim3(a.nsplit, B), dim3(DEC_T), lds_at, st, a.q, (h16_t*)a.Kc[l], (const h16_t*)a.Vc[l],
+                               a.q_scale[l], a.k_scale[l], a.bias_table, a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale,
+                               a.round_bf16, a.k_new);
+        else
+            hipLaunchKernelGGL(dec_attn_kernel<float>, dim3(a.nsplit, B), dim3(DEC_T), lds_at, st, a.q, a.Kc[l], (const float*)a.Vc[l],
+                               a.q_scale[l], a.k_scale[l], a.bias_table, a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale,
+                               a.round_bf16, (const float*)nullptr);
         hipLaunchKernelGGL((dec_gemv_kernel<TW>), dim3((D + DEC_ROWS - 1) / DEC_ROWS), dim3(DEC_T), lds_hd, st, (const float*)nullptr, 0,
                            (const float*)nullptr, 0, a.eps, a.parts, a.nsplit, H, a.pos_dev, (const TW*)a.Wo[l], (long long)HD, HD, D,
                            a.x, D, a.x1, D, B, a.round_bf16);
@@ -1600,6 +1689,9 @@ extern "C" int OMLM_API(omlm_decode_step)(const omlm_decode_args* a, const long 
     OMLM_CHECK_ARG(a->nsplit * DEC_KS >= a->Nmax, "nsplit must cover Nmax keys");
     OMLM_CHECK_ARG(a->B > DEC_BMAX || (size_t)a->B * a->Fp * sizeof(float) + 1024 <= 150 * 1024, "B * Fp exceeds the LDS budget");
     OMLM_CHECK_ARG(!a->emb_table || ids, "ids required with an embedding table");
+    // a 16-bit cache holds the fp32 cache's numbers only where the steps round every key and value to the operand type anyway
+    OMLM_CHECK_ARG(!a->kv16 || (a->w_dtype != 0 && a->round_bf16 != 0 && a->k_new),
+                   "kv16 (16-bit K/V cache) needs 16-bit weights, round_bf16 and the k_new staging row");
     const bool v2_ok = a->D == 1024 && a->H * 64 <= 1024 && a->Fp <= 4096 && a->Fp % 2 == 0 && (a->H * 64 + 128) % DEC2_ROWS == 0;
     // batches of 9..16 exist only on the second-generation path's matrix-core kernels: the first-generation kernels below are sized for
     // DEC_BMAX samples (LDS B * Fp floats, DEC_ROWS * DEC_BMAX tail) -- refuse instead of overrunning them (odd geometries)

@@ -13,6 +13,10 @@ counter advance; the row index lives on the device so that a step can be capture
 
 A call holds ``max_batch`` samples (8, or 16 on the matrix-core step kernels); ``CachedDecoder(..., wide=True)`` holds up to
 ``max_call_batch`` (64 there): groups of 16 samples ride through one launch of every step kernel, each computed as a 16-sample call.
+
+The K/V cache is fp32 by default.  ``CachedDecoder(..., kv_cache="operand")`` keeps it in the precision's 16-bit operand type: the step kernels
+round every key and value to that type before they store them, so the 16-bit cache holds the same numbers in half the bytes (``cache_bytes``)
+and the logits are the same bit for bit.
 """
 from __future__ import annotations
 
@@ -47,6 +51,32 @@ def sampler_rng_choice(requested, n_new: int, batch: int, V1: int, injected: boo
     return "counter"
 
 
+KV_CACHE_CHOICES = (None, "fp32", "operand")
+
+
+def check_kv_cache(requested):
+    """`requested` if it is one of KV_CACHE_CHOICES; a ValueError that names them otherwise."""
+    if not any(requested is c or (isinstance(requested, str) and requested == c) for c in KV_CACHE_CHOICES):
+        raise ValueError(f"kv_cache must be None, 'fp32' or 'operand', not {requested!r}")
+    return requested
+
+
+def kv_cache_choice(requested, precision: str) -> torch.dtype:
+    """Element type of the decode K/V cache.  None or "fp32": torch.float32.  "operand": the attention operand dtype of `precision` -- bf16
+    for "bf16", fp16 for "fp16" / "fp16ff", and fp32 for "bf16x3" (its operands are fp32, so the cache stays what it is).  Anything else
+    raises a ValueError that names the accepted values."""
+    if precision not in engine._PRECISIONS:
+        raise ValueError(f"unknown precision {precision!r}; one of {sorted(engine._PRECISIONS)}")
+    return engine._PRECISIONS[precision] if check_kv_cache(requested) == "operand" else torch.float32
+
+
+def cache_bytes(model, batch: int, rows: int, precision: str, kv_cache=None) -> int:
+    """Bytes of the K + V caches of all layers for `batch` samples of `rows` rows: batch * rows * 64 * 2 * depth * element size (one K/V head
+    of 64 dims per layer).  kv_cache="operand" halves it on the 16-bit precisions."""
+    esize = torch.empty(0, dtype=kv_cache_choice(kv_cache, precision)).element_size()
+    return int(batch) * int(rows) * engine.DIM_HEAD * 2 * len(model.transformer.layers) * esize
+
+
 _PTRS = ["Wq", "Wkv", "Wo", "W1p", "W2p", "attn_gamma", "q_scale", "k_scale", "ffin_gamma", "convw", "mid_gamma",
          "Kc", "Vc", "hist"]
 
@@ -61,7 +91,8 @@ class DecodeArgs(C.Structure):
                  ("emb_table", C.c_void_p), ("emb_row_offset", C.c_longlong), ("emb_rows", C.c_longlong)] +
                 [(n, C.c_void_p) for n in ("x", "x1", "q", "parts", "u", "logits", "advance_pos", "advance_step", "ln_parts")] +
                 [("W1p_lo", C.POINTER(C.c_void_p)), ("W2p_lo", C.POINTER(C.c_void_p)), ("head_W_lo", C.c_void_p)] +
-                [("splitk_ws", C.c_void_p), ("splitk_cnt", C.c_void_p)])
+                [("splitk_ws", C.c_void_p), ("splitk_cnt", C.c_void_p)] +
+                [("kv16", C.c_int), ("k_new", C.c_void_p)])
 
 
 MAX_DECODE_HEADS = 16              # omlm_decode_step: H <= 16
@@ -140,7 +171,10 @@ def supports(model, batch: int, precision: Optional[str] = None, prompt_rows: Op
 
 
 class CachedDecoder:
-    def __init__(self, model, batch: int, max_rows: int, precision: str, wide: bool = False):
+    def __init__(self, model, batch: int, max_rows: int, precision: str, wide: bool = False, kv_cache=None):
+        """kv_cache: None / "fp32" (fp32 K/V cache) or "operand" (the precision's 16-bit operand type; same logits, half of cache_bytes);
+        self.kv_dtype tells which type the cache holds."""
+        self.kv_dtype = kv_cache_choice(kv_cache, precision)                   # refused by name before any device work
         # (a non-causal prefix is checked against the prompt in prefill)
         if not supports(model, batch, precision, prompt_rows=engine.prefix_rows(model.transformer), wide=wide):
             tr = model.transformer
@@ -162,8 +196,11 @@ class CachedDecoder:
         self.L, self.D, self.H, self.F, self.Fp = L, D, H, F, Fp
         B, Nmax = self.B, self.Nmax
         f32 = dict(device=dev, dtype=torch.float32)
-        self.Kc = [torch.zeros(B, Nmax, engine.DIM_HEAD, **f32) for _ in range(L)]
-        self.Vc = [torch.zeros(B, Nmax, engine.DIM_HEAD, **f32) for _ in range(L)]
+        assert self.kv_dtype in (torch.float32, self.T), (self.kv_dtype, self.T)
+        self.Kc = [torch.zeros(B, Nmax, engine.DIM_HEAD, device=dev, dtype=self.kv_dtype) for _ in range(L)]
+        self.Vc = [torch.zeros(B, Nmax, engine.DIM_HEAD, device=dev, dtype=self.kv_dtype) for _ in range(L)]
+        # 16-bit cache: the step's raw key waits here in fp32 until the attention kernel has normalised it (omlm_decode_args::k_new)
+        self.k_new = torch.zeros(B, engine.DIM_HEAD, **f32) if self.kv_dtype != torch.float32 else None
         self.hist = [torch.zeros(B, 2, 2 * Fp, **f32) for _ in range(L)]
         self.x, self.x1 = torch.empty(B, D, **f32), torch.empty(B, D, **f32)
         self.q = torch.empty(B, H * engine.DIM_HEAD, **f32)
@@ -232,6 +269,7 @@ class CachedDecoder:
         self.splitk_ws = torch.empty(sizes["splitk_ws"], device=self.x.device)
         self.splitk_cnt = torch.zeros(sizes["splitk_cnt"], dtype=torch.int32, device=self.x.device)
         a.splitk_ws, a.splitk_cnt = self.splitk_ws.data_ptr(), self.splitk_cnt.data_ptr()
+        a.kv16, a.k_new = (1, self.k_new.data_ptr()) if self.k_new is not None else (0, None)
         self.args = a
 
     # ---- prompt: the batched forward over all known rows, keeping what the single-row steps need ---------------------
@@ -251,7 +289,7 @@ class CachedDecoder:
         nseq = len(model.token_sequences)
         logits = engine.heads_forward(model, self.pw, y, y_lo, lay, [s == nseq - 1 for s in range(nseq)])[-1]
         for l, sv in enumerate(saved["layers"]):
-            self.Kc[l][:, :N].copy_(sv.k.view(B, N, -1))
+            self.Kc[l][:, :N].copy_(sv.k.view(B, N, -1))         # (sv.k / sv.v are in the operand dtype: a 16-bit cache takes them as they are)
             self.Vc[l][:, :N].copy_(sv.v.view(B, N, -1))
             h1 = sv.h1.view(B, N, -1)
             self.hist[l].zero_()

@@ -163,7 +163,7 @@ class TokenConditionedTransformerWrapper(nn.Module):
     def generate(self, *, conditioning_token_ids: List[torch.Tensor], pred_token_ids: Optional[torch.Tensor] = None,
                  max_time_steps=512, filter_thres=0.9, temperature=1., include_eos_in_output=False,
                  append_eos_to_conditioning_tokens=True, allow_eos_in_output=False, uniforms=None, sampler_rng=None,
-                 sampler_seed=None, top_p=None, **kwargs):
+                 sampler_seed=None, top_p=None, kv_cache=None, **kwargs):
         """AR sampling (open_musiclm.py:253-326).  Every step re-runs the full causal forward over the grown
         sequence like the reference (results are identical to a KV-cached decode because the stack is strictly
         causal); only the last position's logits are formed, and eos suppression + top-k + Gumbel-argmax run in
@@ -174,10 +174,15 @@ class TokenConditionedTransformerWrapper(nn.Module):
         decode calls.  None: "buffer" unless the buffer would exceed decode.UNIFORM_BUFFER_MAX_BYTES (decode.sampler_rng_choice).
         ``top_p``: nucleus sampling inside the top-k set (include/omlm.h) -- of the k kept logits, ranked by value, only those are sampled
         whose preceding softmax mass (at ``temperature``) is below top_p of the kept mass.  A number in (0, 1]; None or 1: off, the call
-        is the one it is without the argument.  Works on every route and with every source of uniforms."""
+        is the one it is without the argument.  Works on every route and with every source of uniforms.
+        ``kv_cache``: element type of the cached decode's K/V cache -- None or "fp32", or "operand": the precision's 16-bit operand type
+        (decode.kv_cache_choice; fp32 for "bf16x3").  The cached values are 16-bit numbers either way, so the ids are the same and the
+        cache takes half the bytes (decode.cache_bytes).  On the re-forward route there is no cache and the value has no effect."""
         assert len(conditioning_token_ids) == len(self.token_sequences) - 1
         ops.check_sampler_width(self.token_sequences[-1].codebook_size + 1)      # before any device work
         top_p = ops.check_top_p(top_p)                                          # likewise; 1.0 = off
+        decode.kv_cache_choice(kv_cache, self.transformer._precision())         # likewise: a ValueError names the accepted values
+        kv_kw = {} if kv_cache is None else dict(kv_cache=kv_cache)             # (None: the decoders are built as they always were)
         batch, device = conditioning_token_ids[0].shape[0], self.device
         cond = [t.to(device) for t in conditioning_token_ids]
         if exists(pred_token_ids):
@@ -230,7 +235,7 @@ class TokenConditionedTransformerWrapper(nn.Module):
             group = decode.max_call_batch(self.transformer, self.transformer._precision())
             for b0 in range(0, batch, group):
                 b1 = min(batch, b0 + group)
-                dec = decode.CachedDecoder(self.transformer, b1 - b0, rows, self.transformer._precision(), wide=True)
+                dec = decode.CachedDecoder(self.transformer, b1 - b0, rows, self.transformer._precision(), wide=True, **kv_kw)
                 last = dec.prefill([t[b0:b1] for t in cond] + [sampled[b0:b1]])
                 if counter:            # sample b draws u(step, b, c) whichever piece it rides in
                     loop = decode.SamplingLoop(dec, last, None, n0, n_new, k, temperature, forbid, use_graph=use_graph, rng=(sampler_seed, b0),
@@ -583,6 +588,8 @@ class MusicLM(nn.Module):
                          uniforms depend on its index in that call alone, not on how the call is cut into decode calls.
       top_p           -- nucleus sampling in every stage's generate(): a number in (0, 1] for all three stages, or a mapping with any of
                          "semantic" / "coarse" / "fine" (a stage that is not named samples without a nucleus).  None: off.
+      kv_cache        -- handed to every stage's generate(): None / "fp32", or "operand" to keep the cached decode's keys and values in the
+                         precision's 16-bit operand type -- the same ids from half the cache bytes (decode.cache_bytes sizes a call).
     ``generate`` is an alias of ``forward``."""
 
     def __init__(self, *, wav2vec=None, clap=None, neural_codec=None, semantic_transformer: TokenConditionedTransformer,
@@ -607,8 +614,10 @@ class MusicLM(nn.Module):
                 semantic_steps_per_second=50, acoustic_steps_per_second=75, return_coarse_generated_wave=False,
                 mask_out_generated_fine_tokens=False, semantic_sliding_window_step_percent=0.5,
                 coarse_sliding_window_step_percent=0.5, fine_sliding_window_step_percent=1,
-                clap_token_ids=None, return_tokens=False, fine_windows_together=False, sampler_rng=None, top_p=None):
+                clap_token_ids=None, return_tokens=False, fine_windows_together=False, sampler_rng=None, top_p=None, kv_cache=None):
         p_sem, p_coarse, p_fine = stage_top_p(top_p)                               # refused by name before any work
+        decode.check_kv_cache(kv_cache)                                            # likewise
+        kv_kw = {} if kv_cache is None else dict(kv_cache=kv_cache)                # (None: every stage is called as it always was)
         if not exists(clap_token_ids):
             assert exists(text), 'text needs to be passed in if one of the transformer requires conditioning'
             clap_token_ids = get_or_compute_clap_token_ids(None, self.clap, conditioning_audio=None, conditioning_text=text)
@@ -643,13 +652,13 @@ class MusicLM(nn.Module):
         sem = self.semantic.generate(clap_token_ids=clap_token_ids, semantic_token_ids=prime_sem,
                                      max_time_steps=int(min(output_seconds, semantic_window_seconds) * sem_hz),
                                      include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng,
-                                     top_p=p_sem)
+                                     top_p=p_sem, **kv_kw)
         while sem.shape[1] < int(output_seconds * sem_hz):
             keep = int(semantic_window_seconds * sem_hz * (1 - semantic_sliding_window_step_percent))
             nxt = self.semantic.generate(clap_token_ids=clap_token_ids, semantic_token_ids=sem[:, -keep:],
                                          max_time_steps=int(semantic_window_seconds * sem_hz),
                                          include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng,
-                                         top_p=p_sem)
+                                         top_p=p_sem, **kv_kw)
             sem = torch.cat([sem, nxt[:, keep:]], dim=1)
         sem_all = sem
         sem = sem[:, sem_adjust:]
@@ -667,7 +676,7 @@ class MusicLM(nn.Module):
                                         coarse_token_ids=cond_coarse,
                                         max_time_steps=int(coarse_window_seconds * ac_hz), reconstruct_wave=False,
                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True,
-                                        temperature=0.95, sampler_rng=sampler_rng, top_p=p_coarse)
+                                        temperature=0.95, sampler_rng=sampler_rng, top_p=p_coarse, **kv_kw)
             coarse = pred if not exists(coarse) else torch.cat([coarse, pred[:, keep:]], dim=1)
         if return_coarse_generated_wave:
             return self.neural_codec.decode_from_codebook_indices(coarse).squeeze(1)
@@ -683,7 +692,7 @@ class MusicLM(nn.Module):
             pred = self.fine.generate(clap_token_ids=clap_token_ids.repeat(len(coarse_wins), *([1] * (clap_token_ids.dim() - 1))),
                                       coarse_token_ids=_stack_windows(coarse_wins), fine_token_ids=None,
                                       max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
-                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine)
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine, **kv_kw)
             fine = torch.cat(_unstack_windows(pred, len(coarse_wins)), dim=1)
             coarse_wins = []
         for coarse_win in coarse_wins:
@@ -694,7 +703,7 @@ class MusicLM(nn.Module):
                 keep, cond_fine = 0, prime_fine
             pred = self.fine.generate(clap_token_ids=clap_token_ids, coarse_token_ids=coarse_win, fine_token_ids=cond_fine,
                                       max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
-                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine)
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine, **kv_kw)
             fine = pred if not exists(fine) else torch.cat([fine, pred[:, keep:]], dim=1)
         fine = fine[:, fine_adjust:]
         if exists(prime_coarse_all) and exists(prime_fine_all):

@@ -1,6 +1,7 @@
 """Per-step time of the KV-cached sampling loop as the stages run it (graph replays), prefill differenced out: two `generate` calls of
 different lengths, (t_long - t_short) / extra ids.  env: B (1), PREC (fp16ff), REPS (5), SAMPLER_RNG (unset: generate()'s default; "buffer" or
-"counter").  A/B of library builds: OMLM_LIB_PATH=tools/ab/libomlm_<x>.so"""
+"counter"), KV (unset: fp32 K/V cache; "operand": generate(kv_cache="operand"), the cache in the 16-bit operand type).  The long call reaches
+a context of 13 + 200 + 1 + 330 = 544 rows.  A/B of library builds: OMLM_LIB_PATH=tools/ab/libomlm_<x>.so"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,6 +17,8 @@ kw = dict(clap_token_ids=torch.randint(0, 1024, (B, 12, 1), generator=g).to(dev)
           semantic_token_ids=torch.randint(0, 1024, (B, 199), generator=g).to(dev), use_cache=True)
 if os.environ.get("SAMPLER_RNG"):
     kw["sampler_rng"] = os.environ["SAMPLER_RNG"]
+if os.environ.get("KV"):
+    kw["kv_cache"] = os.environ["KV"]
 short, long_ = 10, 110
 
 
@@ -27,10 +30,11 @@ def run(n):
 
 
 run(2)
-best = None
+best, total = None, 0.0
 for _ in range(reps):
     ts, tl = run(short), run(long_)
+    total += ts + tl
     us = 1e6 * (tl - ts) / ((long_ - short) * 3)
     best = us if best is None else min(best, us)
-print(f"B={B} {prec} sampler_rng={os.environ.get('SAMPLER_RNG', 'default')} lib={os.path.basename(os.environ.get('OMLM_LIB_PATH', 'default'))}: {best:.1f} us/step -> {B * 1e6 / best:.0f} ids/s "
+print(f"B={B} {prec} sampler_rng={os.environ.get('SAMPLER_RNG', 'default')} kv={os.environ.get('KV', 'fp32')} window={total:.2f}s lib={os.path.basename(os.environ.get('OMLM_LIB_PATH', 'default'))}: {best:.1f} us/step -> {B * 1e6 / best:.0f} ids/s "
       f"(short call {1e3 * ts:.1f} ms)")
