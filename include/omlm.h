@@ -497,6 +497,24 @@ typedef struct omlm_sample_args {
 } omlm_sample_args;
 int omlm_sample(const omlm_sample_args* args, void* stream);
 
+/* The log-probabilities of the sampled id.  For a row of V fp32 logits l_c as the head wrote them, forbid_last, k, T > 0 and
+ * 0 < top_p <= 1, with s the id the sampler returns for the row (natural logarithms):
+ *   lp_model   = l_s - log sum_{c < V} exp(l_c): the model's own distribution -- T = 1, all V entries, the last one included even when
+ *                it is forbidden;
+ *   lp_sampled = l_s / T - log sum_{c in N} exp(l_c / T), N the set s was drawn from: the top-k kept set, cut to the nucleus when
+ *                top_p < 1, the last logit at -inf when forbidden.  It is the log of the probability with which the Gumbel-max rule picks s.
+ * A -inf logit contributes 0.  When the largest kept logit m is -inf (the "id 0" rule) both values are -inf.  When N has one entry
+ * (k == 1, a tiny top_p, V == 1) lp_sampled is exactly 0.0f: the value is formed as (l_s - m) / T - log(sum of exp((l_c - m) / T)).
+ * lp_model is formed as (l_s - M) - log(sum of exp(l_c - M)), M the larger of m and the forbidden last logit.  Rows with +inf or NaN
+ * logits are unspecified, as they are for the id.
+ * Arithmetic: fp32, weights by the precise expf that forms the nucleus masses; the sums run in a fixed order (a lane's slots in order,
+ * the wave's shuffle tree, in the workgroup kernel the waves' partials in wave order), without floating-point atomics: one row gives the
+ * same bits in every launch.  The wave kernel (V <= 2048) and the workgroup kernel may differ from each other in the last bits.
+ *
+ * omlm_sample plus the log-probabilities of the id it returns.  lp_model / lp_sampled: [B] floats, or [steps, B]
+ * indexed by *step_dev when args->step_dev is given (like hist); either may be NULL; both NULL: exactly omlm_sample. */
+int omlm_sample_lp(const omlm_sample_args* args, float* lp_model, float* lp_sampled, void* stream);
+
 /* KV-cached AR decode step: ONE new row (index *pos_dev) per sample through all L layers and the logit head of the quantizer
  * that row predicts -- replaces the reference's full re-forward per sampled id (wrapper.generate, open_musiclm.py:301-321;
  * the trunk is strictly causal, so the logits are the same).  State owned by the caller:

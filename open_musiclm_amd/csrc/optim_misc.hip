@@ -937,6 +937,24 @@ __device__ __forceinline__ float sample_top_p(const float*) { return 1.f; }
 __device__ __forceinline__ float sample_top_p(const SampleStream&) { return 1.f; }
 __device__ __forceinline__ float sample_top_p(const SampleBufferP& p) { return p.top_p; }
 __device__ __forceinline__ float sample_top_p(const SampleStreamP& p) { return p.top_p; }
+// The log-probabilities of the sampled id (LP, a fourth compile-time choice; the two quantities are stated in include/omlm.h): LP = true
+// wraps the source's argument block and appends the two output pointers, so the LP = false instantiations keep the argument types and the
+// kernarg layout they had.  The per-source functions above see through the wrapper.
+template <typename S> struct SampleLP { S s; float* lp_model; float* lp_sampled; };
+template <bool RNG, bool NUC, bool LP> struct sample_arg { typedef typename sample_src<RNG, NUC>::type type; };
+template <bool RNG, bool NUC> struct sample_arg<RNG, NUC, true> { typedef SampleLP<typename sample_src<RNG, NUC>::type> type; };
+template <typename S> __device__ __forceinline__ const float* sample_row_uniforms(const SampleLP<S>& p, size_t offset) { return sample_row_uniforms(p.s, offset); }
+template <typename S> __device__ __forceinline__ unsigned sample_row_key(const SampleLP<S>& p, const int* step_dev, int row) { return sample_row_key(p.s, step_dev, row); }
+template <typename S> __device__ __forceinline__ float sample_top_p(const SampleLP<S>& p) { return sample_top_p(p.s); }
+// The two values from the sums: l_s the sampled id's logit, m the largest kept logit, M = max(m, the forbidden last logit), sum_model the
+// sum of exp(l_c - M) over all V entries, sum_sampled the sum of exp((l_c - m) / T) over the set the id was drawn from.  m = -inf (the
+// "id 0" rule): both -inf.  A one-entry set gives sum_sampled = 1 and l_s = m: exactly 0.
+__device__ __forceinline__ void sample_lp_store(float* lp_model, float* lp_sampled, int row, float ls, float m, float M, float sum_model,
+                                                float sum_sampled, float temperature) {
+    const bool live = m > -INFINITY;
+    if (lp_model) lp_model[row] = live ? (ls - M) - logf(sum_model) : -INFINITY;
+    if (lp_sampled) lp_sampled[row] = live ? (ls - m) / temperature - logf(sum_sampled) : -INFINITY;
+}
 
 // f_ord's inverse: the float whose key this is (a logit is the exact inverse image of its key)
 __device__ __forceinline__ float f_ord_inv(unsigned key) { return u2f((key & 0x80000000u) ? key ^ 0x80000000u : ~key); }
@@ -964,16 +982,22 @@ __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) 
     return ((unsigned long long)hi << 32) | lo;              // the builtin returns int: unsigned BEFORE widening, or the low half sign-extends
 }
 
-template <int SAMPLE_NV, bool RNG, bool NUC>
-__global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ logits, typename sample_src<RNG, NUC>::type uniform,
+template <int SAMPLE_NV, bool RNG, bool NUC, bool LP = false>
+__global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ logits, typename sample_arg<RNG, NUC, LP>::type uniform,
                                                     long long* __restrict__ out, int V, int ld, int k, float temperature,
                                                     int forbid_last, const int* __restrict__ step_dev, long long* __restrict__ hist,
                                                     const float* __restrict__ emb_table, long long emb_row_offset, long long emb_rows,
                                                     float* __restrict__ x, int D) {
     if (step_dev) {          // graph-replayable form: this step's uniforms / history slot are selected by a DEVICE counter
         const long long sidx = step_dev[0];
-        if constexpr (!RNG && !NUC) uniform += sidx * (long long)gridDim.x * V;
-        if constexpr (!RNG && NUC) uniform.u += sidx * (long long)gridDim.x * V;
+        if constexpr (!LP && !RNG && !NUC) uniform += sidx * (long long)gridDim.x * V;
+        if constexpr (!LP && !RNG && NUC) uniform.u += sidx * (long long)gridDim.x * V;
+        if constexpr (LP && !RNG && !NUC) uniform.s += sidx * (long long)gridDim.x * V;
+        if constexpr (LP && !RNG && NUC) uniform.s.u += sidx * (long long)gridDim.x * V;
+        if constexpr (LP) {                                 // [steps, B] like hist
+            if (uniform.lp_model) uniform.lp_model += sidx * gridDim.x;
+            if (uniform.lp_sampled) uniform.lp_sampled += sidx * gridDim.x;
+        }
         if (hist) hist += sidx * gridDim.x;
     }
     const int row = blockIdx.x, lane = threadIdx.x;
@@ -1078,6 +1102,17 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
             n_equal_keep = np;
         }
     }
+    // LP: m = the largest kept logit (the top-k set and the nucleus both keep the row's largest masked logit), M = max(m, the forbidden
+    // last logit, read again: lv[] holds -inf there); two running sums in slot order beside the scores; the winner's logit is one load of lr[besti]
+    float lp_m = -INFINITY, lp_M = -INFINITY, lp_last = -INFINITY, lp_sum_model = 0.f, lp_sum_sampled = 0.f;
+    if constexpr (LP) {
+#pragma unroll
+        for (int j = 0; j < SAMPLE_NV; ++j) lp_m = fmaxf(lp_m, lv[j]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) lp_m = fmaxf(lp_m, __shfl_xor(lp_m, o, 64));
+        if (forbid_last) lp_last = lr[V - 1];
+        lp_M = fmaxf(lp_m, lp_last);
+    }
     float best = -INFINITY;
     int besti = 0x7fffffff;
     int seen_eq = 0;
@@ -1096,6 +1131,10 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
         const float gum = -logf(-logf(uv[j] + 1e-20f) + 1e-20f);
         const float v = keep ? lv[j] / temperature + gum : -INFINITY;
         if (v > best) { best = v; besti = c; }
+        if constexpr (LP) {                             // the precise expf of nucleus_q; exp(-inf) = 0: pads and the forbidden entry add nothing
+            lp_sum_model += expf(lv[j] - lp_M);
+            lp_sum_sampled += keep ? expf((lv[j] - lp_m) / temperature) : 0.f;
+        }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -1105,6 +1144,15 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
     }
     if (besti == 0x7fffffff) besti = 0;                 // every kept entry -inf (e.g. V = 1 with forbid_last): no slot won a comparison
     if (lane == 0) { out[row] = besti; if (hist) hist[row] = besti; }
+    if constexpr (LP) {                                 // a fixed tree: one row gives the same bits in every launch
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lp_sum_model += __shfl_xor(lp_sum_model, o, 64);
+            lp_sum_sampled += __shfl_xor(lp_sum_sampled, o, 64);
+        }
+        lp_sum_model += expf(lp_last - lp_M);           // the forbidden last entry belongs to the model's distribution (0 when it is not forbidden)
+        if (lane == 0) sample_lp_store(uniform.lp_model, uniform.lp_sampled, row, lr[besti], lp_m, lp_M, lp_sum_model, lp_sum_sampled, temperature);
+    }
     if (emb_table) {
         long long r = (long long)besti + emb_row_offset;
         r = r < 0 ? 0 : (r >= emb_rows ? emb_rows - 1 : r);
@@ -1131,8 +1179,8 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
 // The descent ends with t = the k-th largest key and kk = k - count(keys > t), the number of tied entries to keep.
 constexpr int SW_COPIES = 8;
 constexpr int SW_UC = 16;                                 // uniforms in flight per lane in the scoring pass
-template <int NV, bool RNG, bool NUC>
-__global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restrict__ logits, typename sample_src<RNG, NUC>::type uniform,
+template <int NV, bool RNG, bool NUC, bool LP = false>
+__global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restrict__ logits, typename sample_arg<RNG, NUC, LP>::type uniform,
                                                            long long* __restrict__ out, int V, int ld, int k, float temperature,
                                                            int forbid_last, const int* __restrict__ step_dev, long long* __restrict__ hist,
                                                            const float* __restrict__ emb_table, long long emb_row_offset,
@@ -1142,8 +1190,14 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
     __shared__ float s_bv[16];
     if (step_dev) {
         const long long sidx = step_dev[0];
-        if constexpr (!RNG && !NUC) uniform += sidx * (long long)gridDim.x * V;
-        if constexpr (!RNG && NUC) uniform.u += sidx * (long long)gridDim.x * V;
+        if constexpr (!LP && !RNG && !NUC) uniform += sidx * (long long)gridDim.x * V;
+        if constexpr (!LP && !RNG && NUC) uniform.u += sidx * (long long)gridDim.x * V;
+        if constexpr (LP && !RNG && !NUC) uniform.s += sidx * (long long)gridDim.x * V;
+        if constexpr (LP && !RNG && NUC) uniform.s.u += sidx * (long long)gridDim.x * V;
+        if constexpr (LP) {                                 // [steps, B] like hist
+            if (uniform.lp_model) uniform.lp_model += sidx * gridDim.x;
+            if (uniform.lp_sampled) uniform.lp_sampled += sidx * gridDim.x;
+        }
         if (hist) hist += sidx * gridDim.x;
     }
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = blockDim.x >> 6;
@@ -1356,6 +1410,9 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
             // NV = 64: one slot's hash and logs at a time (16 hashes in flight beside the 64 keys spilt 18 registers; the four waves of a
             // SIMD fill each other's latencies)
             if constexpr (RNG && NV > SW_UC) asm volatile("" : "+v"(best));
+            // LP, NV = 64: keepbits outlives this pass, and the winner's index is settled slot by slot (hipcc otherwise keeps the 16
+            // candidate indices of a round for one chain of selects at its end: spilt beside the 64 keys)
+            if constexpr (LP && NV > SW_UC) asm volatile("" : "+v"(best), "+v"(besti));
         }
     }
 #pragma unroll
@@ -1375,6 +1432,54 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
     }
     if (besti == 0x7fffffff) besti = 0;                    // every kept entry -inf: no slot won a comparison
     if (tid == 0) { out[row] = besti; if (hist) hist[row] = besti; }
+    if constexpr (LP) {
+        // Only the keys are resident: a logit is the inverse image of its key (a pad's key is 0, no logit has it), keepbits says which
+        // entries the id was drawn from.  One slot at a time (the empty asm), as in the mass round of the nucleus; per lane in slot order,
+        // the wave's shuffle tree, then the waves' partials through LDS in wave order: no float atomics, one row gives the same bits.
+        __shared__ unsigned s_lpk[16];
+        __shared__ float s_lpm[16], s_lps[16];
+        unsigned kmax = 0;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) kmax = keys[j] > kmax ? keys[j] : kmax;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const unsigned ok = __shfl_xor(kmax, o, 64); kmax = ok > kmax ? ok : kmax; }
+        if (lane == 0) s_lpk[wave] = kmax;
+        __syncthreads();
+        kmax = s_lpk[0];
+        for (int w = 1; w < nw; ++w) kmax = s_lpk[w] > kmax ? s_lpk[w] : kmax;
+        // workgroup-uniform values go to scalar registers: at NV = 64 the 64 keys leave the vector file no room for them
+        const float m = f_ord_inv((unsigned)__builtin_amdgcn_readfirstlane((int)kmax));      // the largest kept logit: top-k and nucleus keep the row's largest masked logit
+        float lastl = -INFINITY;                           // overwritten with -inf before the keys were formed: read again
+        if (forbid_last) lastl = u2f((unsigned)__builtin_amdgcn_readfirstlane((int)f2u(lr[V - 1])));
+        const float M = fmaxf(m, lastl);
+        float sm = 0.f, ss = 0.f;
+        if (m > -INFINITY) {
+            unsigned long long kb = keepbits;
+#pragma unroll
+            for (int j = 0; j < NV; ++j) {
+                unsigned kj = keys[j];
+                asm volatile("" : "+v"(kj), "+v"(sm), "+v"(ss));
+                const float l = f_ord_inv(kj);
+                if (kj != 0u) sm += expf(l - M);
+                asm volatile("" : "+v"(sm), "+v"(kb));         // one exponential at a time
+                if ((kb >> j) & 1ull) ss += expf((l - m) / temperature);
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            sm += __shfl_xor(sm, o, 64);
+            ss += __shfl_xor(ss, o, 64);
+        }
+        if (lane == 0) { s_lpm[wave] = sm; s_lps[wave] = ss; }
+        __syncthreads();
+        if (tid == 0) {
+            sm = s_lpm[0];
+            ss = s_lps[0];
+            for (int w = 1; w < nw; ++w) { sm += s_lpm[w]; ss += s_lps[w]; }
+            sm += expf(lastl - M);                         // the forbidden last entry belongs to the model's distribution
+            sample_lp_store(uniform.lp_model, uniform.lp_sampled, row, lr[besti], m, M, sm, ss, temperature);
+        }
+    }
     if (emb_table) {
         long long r = (long long)besti + emb_row_offset;
         r = r < 0 ? 0 : (r >= emb_rows ? emb_rows - 1 : r);
@@ -1504,6 +1609,50 @@ extern "C" int omlm_sample(const omlm_sample_args* a, void* stream) {
     else SAMPLE_ARGS_GO(true, false, st);
 #undef SAMPLE_ARGS_GO
     return omlm_post_launch("omlm_sample");
+}
+
+// omlm_sample plus the log-probabilities of the id it returns (include/omlm.h): the LP = true instantiations, the same route by V.  Defined
+// after everything above, so the twenty new functions follow the twenty old ones in the module (the note above sample_launch).
+template <bool RNG, bool NUC>
+static void sample_launch_lp(const float* logits, typename sample_arg<RNG, NUC, true>::type src, long long* out, int B, int V, int ld, int k,
+                             float temperature, int forbid_last, const int* step_dev, long long* hist, const float* emb_table,
+                             long long emb_row_offset, long long emb_rows, float* x, int D, void* stream) {
+#define SAMPLE_GO(BLOCK_, ...) hipLaunchKernelGGL((__VA_ARGS__), dim3(B), BLOCK_, 0, as_stream(stream), logits, src, out, V, ld, k, temperature, \
+                                                      forbid_last, step_dev, hist, emb_table, emb_row_offset, emb_rows, x, D)
+    if (V > 2048) {
+        const int nv = V <= 4096 ? 4 : V <= 16384 ? 16 : 64;
+        const dim3 block(64 * ((V + 64 * nv - 1) / (64 * nv)));
+        if (nv == 4) SAMPLE_GO(block, sample_wide_kernel<4, RNG, NUC, true>);
+        else if (nv == 16) SAMPLE_GO(block, sample_wide_kernel<16, RNG, NUC, true>);
+        else SAMPLE_GO(block, sample_wide_kernel<64, RNG, NUC, true>);
+    }
+    else if (V <= 64 * 17) SAMPLE_GO(dim3(64), sample_kernel<17, RNG, NUC, true>);
+    else SAMPLE_GO(dim3(64), sample_kernel<32, RNG, NUC, true>);
+#undef SAMPLE_GO
+}
+
+extern "C" int omlm_sample_lp(const omlm_sample_args* a, float* lp_model, float* lp_sampled, void* stream) {
+    if (!lp_model && !lp_sampled) return omlm_sample(a, stream);
+    OMLM_CHECK_ARG(a != nullptr, "args");
+    if (a->B <= 0) return OMLM_OK;
+    const int V = a->V, k = a->k;
+    const float temperature = a->temperature, top_p = a->top_p;
+    OMLM_CHECK_ARG(a->logits && a->out && OMLM_SAMPLER_ARGS_OK, OMLM_SAMPLER_ARGS_MSG);
+    OMLM_CHECK_ARG(top_p > 0.f && top_p <= 1.f, "top_p (0 < top_p <= 1; 1 = no nucleus)");
+    if (a->emb_table) OMLM_CHECK_ARG(a->x && a->D > 0 && a->D % 4 == 0 && a->emb_rows > 0, "embedding arguments");
+    const SampleStream st{a->seed_lo, a->seed_hi, a->step_dev ? 0 : a->step, a->row0};
+#define SAMPLE_LP_GO(RNG_, NUC_, ...) sample_launch_lp<RNG_, NUC_>(a->logits, {__VA_ARGS__, lp_model, lp_sampled}, a->out, a->B, V, a->ld, k, temperature,       \
+                                                                   a->forbid_last, a->step_dev, a->hist, a->emb_table, a->emb_table ? a->emb_row_offset : 0ll, \
+                                                                   a->emb_table ? a->emb_rows : 0ll, a->emb_table ? a->x : nullptr,                         \
+                                                                   a->emb_table ? a->D : 0, stream)
+    if (top_p < 1.f) {
+        if (a->uniform) SAMPLE_LP_GO(false, true, SampleBufferP{a->uniform, top_p});
+        else SAMPLE_LP_GO(true, true, SampleStreamP{st, top_p});
+    }
+    else if (a->uniform) SAMPLE_LP_GO(false, false, a->uniform);
+    else SAMPLE_LP_GO(true, false, st);
+#undef SAMPLE_LP_GO
+    return omlm_post_launch("omlm_sample_lp");
 }
 
 // ---------------------------------------------------------------------------------------------------------

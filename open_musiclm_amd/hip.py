@@ -96,6 +96,7 @@ SIGNATURES = {
     "omlm_sample_topk_gumbel_at_rng": [vp, u32, u32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, vp],
     "omlm_sample_embed_at_rng": [vp, u32, u32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, vp, i64, i64, vp, i32, vp],
     "omlm_sample": [vp, vp],
+    "omlm_sample_lp": [vp, vp, vp, vp],
     "omlm_probe_tr16": [vp, vp],
 }
 _RESTYPES = {"omlm_last_error": C.c_char_p, "omlm_gemm_tail_workspace_bytes": C.c_longlong, "omlm_gemm_mx16_workspace_bytes": C.c_longlong, "omlm_ffmid_bwd_workspace_bytes": C.c_longlong,

@@ -8,6 +8,7 @@ sliding-window hierarchical decode.  Everything floating point goes through ``en
 from __future__ import annotations
 
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import List, Mapping, Optional
 
@@ -16,7 +17,7 @@ import torch.nn.functional as F
 from torch import nn
 from tqdm import tqdm
 
-from . import decode, engine, ops
+from . import decode, engine, hip, ops
 from .transformer import Transformer
 from .utils import (append_eos_id, batch_unique_consecutive, beartype_jit, default, eval_decorator, exists,
                     float32_to_int16, generate_mask_with_prob, int16_to_float32, mask_out_after_eos_id)
@@ -137,6 +138,17 @@ class TokenConditionedTransformer(nn.Module):
 
 _GENERATE_MASK_ORIG = generate_mask_with_prob
 
+# generate(return_logprobs=True): the two log-probabilities (include/omlm.h) of every id the call sampled, fp32 [B, time steps, Q] each
+LogProbs = namedtuple("LogProbs", ["model", "sampled"])
+
+
+def zero_logprobs_after_eos(values: torch.Tensor, ids: torch.Tensor, eos_id: int, keep_eos: bool) -> torch.Tensor:
+    """values [B, n] beside the LAST n columns of ids [B, m >= n]: 0.0 wherever mask_out_after_eos_id replaces the id (everything after
+    the first eos, and the eos itself unless it is kept), so that a sum over time is the log-probability of the kept part."""
+    replaced = mask_out_after_eos_id(ids, eos_id, keep_eos=keep_eos) != ids
+    n = values.shape[-1]
+    return values.masked_fill(replaced[:, ids.shape[-1] - n:], 0.0)
+
 
 @beartype_jit
 class TokenConditionedTransformerWrapper(nn.Module):
@@ -163,7 +175,7 @@ class TokenConditionedTransformerWrapper(nn.Module):
     def generate(self, *, conditioning_token_ids: List[torch.Tensor], pred_token_ids: Optional[torch.Tensor] = None,
                  max_time_steps=512, filter_thres=0.9, temperature=1., include_eos_in_output=False,
                  append_eos_to_conditioning_tokens=True, allow_eos_in_output=False, uniforms=None, sampler_rng=None,
-                 sampler_seed=None, top_p=None, kv_cache=None, **kwargs):
+                 sampler_seed=None, top_p=None, kv_cache=None, return_logprobs=False, **kwargs):
         """AR sampling (open_musiclm.py:253-326).  Every step re-runs the full causal forward over the grown
         sequence like the reference (results are identical to a KV-cached decode because the stack is strictly
         causal); only the last position's logits are formed, and eos suppression + top-k + Gumbel-argmax run in
@@ -177,7 +189,12 @@ class TokenConditionedTransformerWrapper(nn.Module):
         is the one it is without the argument.  Works on every route and with every source of uniforms.
         ``kv_cache``: element type of the cached decode's K/V cache -- None or "fp32", or "operand": the precision's 16-bit operand type
         (decode.kv_cache_choice; fp32 for "bf16x3").  The cached values are 16-bit numbers either way, so the ids are the same and the
-        cache takes half the bytes (decode.cache_bytes).  On the re-forward route there is no cache and the value has no effect."""
+        cache takes half the bytes (decode.cache_bytes).  On the re-forward route there is no cache and the value has no effect.
+        ``return_logprobs``: returns ``(ids, LogProbs(model, sampled))`` -- fp32 [B, max_time_steps - first_step, Q] each, on the model's
+        device, for the ids THIS call sampled (not a supplied ``pred_token_ids``): ``model`` is the log-probability of the id under the
+        model's own distribution (T = 1, all entries), ``sampled`` under the distribution it was drawn from (top-k, nucleus,
+        temperature, eos rule) -- include/omlm.h.  The sampler kernels write them in the launch that picks the id, on every route and with
+        every source of uniforms; the flag changes no id.  Where the returned id is the after-eos mask value both numbers are 0.0."""
         assert len(conditioning_token_ids) == len(self.token_sequences) - 1
         ops.check_sampler_width(self.token_sequences[-1].codebook_size + 1)      # before any device work
         top_p = ops.check_top_p(top_p)                                          # likewise; 1.0 = off
@@ -231,7 +248,8 @@ class TokenConditionedTransformerWrapper(nn.Module):
             # a decode call holds up to decode.max_call_batch samples (64 on the matrix-core step kernels, which carry four groups of 16
             # through every launch): larger batches run as consecutive calls (samples are independent; every call streams the weights
             # once per id)
-            pieces = []
+            pieces, lp_pieces = [], []
+            lp_kw = dict(logprobs=True) if return_logprobs else {}      # (False: the loops are built as they always were)
             group = decode.max_call_batch(self.transformer, self.transformer._precision())
             for b0 in range(0, batch, group):
                 b1 = min(batch, b0 + group)
@@ -239,20 +257,34 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 last = dec.prefill([t[b0:b1] for t in cond] + [sampled[b0:b1]])
                 if counter:            # sample b draws u(step, b, c) whichever piece it rides in
                     loop = decode.SamplingLoop(dec, last, None, n0, n_new, k, temperature, forbid, use_graph=use_graph, rng=(sampler_seed, b0),
-                                               top_p=top_p)
+                                               top_p=top_p, **lp_kw)
                 else:
                     loop = decode.SamplingLoop(dec, last, U[:, b0:b1].contiguous(), n0, n_new, k, temperature, forbid, use_graph=use_graph,
-                                               top_p=top_p)
+                                               top_p=top_p, **lp_kw)
                 pieces.append(loop.run().t())                      # [b, n_new]
+                if return_logprobs:
+                    lp_pieces.append((loop.lp_model.t(), loop.lp_sampled.t()))
             sampled = torch.cat((sampled, torch.cat(pieces, dim=0)), dim=-1)
+            if return_logprobs:
+                lp_model, lp_sampled = (torch.cat(ps, dim=0) for ps in zip(*lp_pieces))
         else:
             if not exists(uniforms) and UNIFORM_SOURCE is not None and n_new > 0:
                 uniforms = UNIFORM_SOURCE(n_new, batch, V1)
+            if return_logprobs:                                     # [ids, B]: row `step` is written by the launch that samples id `step`
+                lp_model, lp_sampled = (torch.zeros(n_new, batch, device=device) for _ in range(2))
             for _t in tqdm(range(first_step, max_time_steps), desc='generating predicted tokens'):
                 for ind in range(Q):
                     last = self.transformer.last_logits(cond + [sampled])
                     forbid = (not allow_eos_in_output) or (ind != Q - 1)
-                    if counter:
+                    if return_logprobs:
+                        if counter:
+                            src = dict(seed=sampler_seed, step=step)
+                        elif exists(uniforms):
+                            src = dict(uniform=uniforms[step].to(device).float().contiguous())
+                        else:
+                            src = dict(uniform=torch.empty(batch, V1, device=device).uniform_(0, 1))
+                        ops.sample(last, nxt, V1, k, temperature, forbid, top_p=top_p, lp_model=lp_model[step], lp_sampled=lp_sampled[step], **src)
+                    elif counter:
                         if top_p < 1.0:
                             ops.sample(last, nxt, V1, k, temperature, forbid, top_p=top_p, seed=sampler_seed, step=step)
                         else:
@@ -268,8 +300,55 @@ class TokenConditionedTransformerWrapper(nn.Module):
                             ops.sample_topk_gumbel(last, u, nxt, V1, k, temperature, forbid)
                     sampled = torch.cat((sampled, nxt[:, None]), dim=-1)
                     step += 1
+            if return_logprobs:
+                lp_model, lp_sampled = lp_model.t(), lp_sampled.t()      # [B, ids]
+        if return_logprobs:
+            lps = LogProbs(*(zero_logprobs_after_eos(v, sampled, pred_eos_id, include_eos_in_output).reshape(batch, -1, Q)
+                             for v in (lp_model, lp_sampled)))
         sampled = mask_out_after_eos_id(sampled, pred_eos_id, keep_eos=include_eos_in_output)
+        if return_logprobs:
+            return sampled.reshape(batch, -1, Q), lps
         return sampled.reshape(batch, -1, Q)
+
+    @eval_decorator
+    @torch.no_grad()
+    def score(self, *, conditioning_token_ids: List[torch.Tensor], pred_token_ids: torch.Tensor,
+              append_eos_to_conditioning_tokens=True) -> torch.Tensor:
+        """The teacher-forced twin of ``generate(return_logprobs=True).model``: fp32 [B, T, Q], entry (b, t, q) the log-probability
+        (lp_model of include/omlm.h: the model's own distribution, T = 1, all entries) of id ``pred_token_ids[b, t, q]`` given the
+        conditioning and the ids before it -- under the logits ``transformer.last_logits(cond + [pred_flat[:, :t Q + q]])`` gives.
+        One forward over the whole sequence with generate's semantics (no key mask, the conditioning eos appended and embedded);
+        omlm_cross_entropy_fwd writes every row's log-sum-exp, the rest is a gather and a subtract."""
+        assert len(conditioning_token_ids) == len(self.token_sequences) - 1
+        pred_info = self.token_sequences[-1]
+        assert not (self.unique_consecutive and pred_info.unique_consecutive), "score: a unique_consecutive predicted sequence has no [B, T, Q] form"
+        hip.require_gpu(self.transformer.start_tokens[0], "model parameters")
+        device, Q, V1 = self.device, pred_info.num_quantizers, pred_info.codebook_size + 1
+        batch = pred_token_ids.shape[0]
+        pred = _flat(pred_token_ids).to(device).long()                        # [B, T Q]
+        L = pred.shape[-1]
+        assert L % Q == 0 and all(t.shape[0] == batch for t in conditioning_token_ids)
+        if L > 0 and bool(((pred < 0) | (pred >= V1)).any()):
+            raise ValueError(f"score: pred_token_ids must lie in [0, {V1 - 1}] (the codebook and its eos); got "
+                             f"[{int(pred.min())}, {int(pred.max())}]")
+        if L == 0:
+            return torch.zeros(batch, 0, Q, device=device)
+        cond = [t.to(device) for t in conditioning_token_ids]
+        for i, info in enumerate(self.token_sequences[:-1]):
+            if info.unique_consecutive:
+                cond[i] = batch_unique_consecutive(cond[i], pad_value=self.pad_id)
+        if append_eos_to_conditioning_tokens:
+            cond = [append_eos_id(_flat(t).long(), e) for t, e in zip(cond, self.eos_ids)]
+        # row j of the predicted sequence (its start token, then the ids) holds the logits after pred[:, :j]: rows 0 .. L - 1 score the L ids,
+        # the last row (what would follow them) carries the ignore label
+        bufs, _, _ = engine.run_forward(self.transformer, cond + [pred], None, True, False, self.transformer._precision())
+        buf = bufs[-1]
+        assert buf.shape[0] == batch * (L + 1), (buf.shape, batch, L)
+        labels = F.pad(pred, (0, 1), value=-1).to(torch.int32).reshape(-1).contiguous()
+        lse = torch.empty(buf.shape[0], device=device)
+        ops.ce_fwd(buf, labels, lse, torch.zeros(1, device=device), V1)
+        own = buf.view(batch, L + 1, -1)[:, :L].gather(2, pred[:, :, None]).squeeze(-1)
+        return (own - lse.view(batch, L + 1)[:, :L]).reshape(batch, L // Q, Q)
 
     # ---- the trainers' optimizer-step path: id / label / mask construction as ONE kernel launch -------------------------------------
     def _fused_prepare_ok(self, all_token_ids, input_has_eos) -> bool:
@@ -437,6 +516,15 @@ class _Stage(nn.Module):
             append_eos_to_conditioning_tokens=append_eos_to_conditioning_tokens, **kwargs)
 
 
+def _split_logprobs(result, kwargs):
+    """What wrapper.generate returned -> (ids, f): with return_logprobs among the stage's keyword arguments the wrapper returned
+    (ids, LogProbs) and f(out) is (out, LogProbs) -- the stage's own result, ids or wave, beside them; otherwise f is the identity."""
+    if kwargs.get("return_logprobs", False):
+        ids, lps = result
+        return ids, lambda out: (out, lps)
+    return result, lambda out: out
+
+
 class SemanticStage(_Stage):
     def __init__(self, *, semantic_transformer: TokenConditionedTransformer, wav2vec=None, clap=None, pad_id=-1,
                  unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15):
@@ -453,6 +541,7 @@ class SemanticStage(_Stage):
     def generate(self, *, conditioning_text=None, conditioning_audio=None, input_audio=None, clap_token_ids=None,
                  semantic_token_ids=None, filter_thres=0.9, temperature=1., max_time_steps=30 * 25,
                  include_eos_in_output=False, append_eos_to_conditioning_tokens=True, **kwargs):
+        """``return_logprobs=True`` (like every sampling keyword, passed on to the wrapper): returns (ids, LogProbs)."""
         clap_token_ids = get_or_compute_clap_token_ids(clap_token_ids, self.clap, conditioning_audio, conditioning_text)
         if exists(semantic_token_ids) or exists(input_audio):
             semantic_token_ids = get_or_compute_semantic_token_ids(semantic_token_ids, input_audio, self.wav2vec)
@@ -489,11 +578,12 @@ class CoarseStage(_Stage):
         clap_token_ids = get_or_compute_clap_token_ids(clap_token_ids, self.clap, conditioning_audio, conditioning_text)
         sampled = self._sample([clap_token_ids, semantic_token_ids], coarse_token_ids, max_time_steps, filter_thres,
                                temperature, include_eos_in_output, append_eos_to_conditioning_tokens, **kwargs)
+        sampled, with_lps = _split_logprobs(sampled, kwargs)
         if reconstruct_wave:
             assert exists(self.neural_codec)
             wave = self.neural_codec.decode_from_codebook_indices(sampled)
-            return wave.squeeze(1)
-        return sampled
+            return with_lps(wave.squeeze(1))
+        return with_lps(sampled)
 
     def forward(self, *, raw_wave_for_clap=None, raw_wave_for_semantic=None, raw_wave_for_acoustic=None,
                 clap_token_ids=None, semantic_token_ids=None, coarse_token_ids=None, return_loss=False, **kwargs):
@@ -521,11 +611,12 @@ class FineStage(_Stage):
         clap_token_ids = get_or_compute_clap_token_ids(clap_token_ids, self.clap, conditioning_audio, conditioning_text)
         sampled = self._sample([clap_token_ids, coarse_token_ids], fine_token_ids, max_time_steps, filter_thres,
                                temperature, include_eos_in_output, append_eos_to_conditioning_tokens, **kwargs)
+        sampled, with_lps = _split_logprobs(sampled, kwargs)
         if reconstruct_wave:
             assert exists(self.neural_codec)
             wave = self.neural_codec.decode_from_codebook_indices(torch.cat((coarse_token_ids, sampled), dim=-1))
-            return wave.squeeze(1)
-        return sampled
+            return with_lps(wave.squeeze(1))
+        return with_lps(sampled)
 
     def forward(self, *, raw_wave_for_clap=None, raw_wave_for_acoustic=None, clap_token_ids=None,
                 coarse_token_ids=None, fine_token_ids=None, return_loss=False, **kwargs):

@@ -842,11 +842,13 @@ def check_top_p(top_p, name="top_p"):
 
 
 def sample(logits, out, V, k, temperature, forbid_last, *, top_p=None, uniform=None, seed=None, step=0, row0=0, step_dev=None,
-           hist=None, emb_table=None, emb_row_offset=0, x=None):
+           hist=None, emb_table=None, emb_row_offset=0, x=None, lp_model=None, lp_sampled=None):
     """omlm_sample: the sampler with an optional nucleus, one call over every form.  ``uniform`` ([B, V], or [steps, B, V] with
     ``step_dev``) or ``seed`` (the counter stream: row b draws u(step or *step_dev, row0 + b, c)) -- exactly one of the two;
     ``step_dev`` (int32 [1], device) selects the graph-replayable form, where ``hist`` is [steps, B]; ``emb_table`` [rows, D] with ``x``
-    [B, D] adds the embedding gather.  top_p None or 1: the launch of sample_topk_gumbel*."""
+    [B, D] adds the embedding gather.  top_p None or 1: the launch of sample_topk_gumbel*.
+    ``lp_model`` / ``lp_sampled`` (fp32 [B], or [steps, B] with ``step_dev``; either or both): the log-probabilities of the sampled id
+    (include/omlm.h), written by the same launch -- the call is then omlm_sample_lp; the ids are those of the call without them."""
     check_sampler_width(V)
     p = check_top_p(top_p)
     if (uniform is None) == (seed is None):
@@ -857,7 +859,14 @@ def sample(logits, out, V, k, temperature, forbid_last, *, top_p=None, uniform=N
                    int(k), float(temperature), p, int(forbid_last),
                    ptr(emb_table), int(emb_row_offset), 0 if emb_table is None else emb_table.shape[0], ptr(x),
                    0 if emb_table is None else emb_table.shape[1])
-    call("omlm_sample", C.addressof(a), stream_ptr())
+    if lp_model is None and lp_sampled is None:
+        call("omlm_sample", C.addressof(a), stream_ptr())
+        return
+    for t, name in ((lp_model, "lp_model"), (lp_sampled, "lp_sampled")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != B):
+            raise ValueError(f"sample: {name} must be a contiguous fp32 tensor [B] ([steps, B] with step_dev), B = {B}; got "
+                             f"{t.dtype} {tuple(t.shape)}")
+    call("omlm_sample_lp", C.addressof(a), ptr(lp_model), ptr(lp_sampled), stream_ptr())
 
 
 def probe_tr16(out):

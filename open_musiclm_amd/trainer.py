@@ -267,6 +267,7 @@ class SingleStageTrainer(nn.Module):
         self.dp.print(msg)
 
     def generate(self, *args, **kwargs):
+        """The wrapper's generate, every keyword passed on: with ``return_logprobs=True`` it returns (ids, LogProbs)."""
         return self.train_wrapper.generate(*args, **kwargs)
 
     @property
