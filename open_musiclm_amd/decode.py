@@ -335,16 +335,17 @@ class SamplingLoop:
     replays, ~1 host launch per id instead of ~32).  Measured on MI355X the step is GPU-bound (32 dependent kernels per id) and
     graph replay is no faster than back-to-back eager launches, so eager is the default; the graph path
     is kept (and tested) for hosts that cannot keep up.
-    ``top_p`` < 1: the sampler keeps the nucleus of the top-k set (include/omlm.h); the cycle then calls omlm_sample.
+    Both sampler calls of the cycle are omlm_sample on a block built once.  ``top_p`` < 1: the sampler keeps the nucleus of the top-k set
+    (include/omlm.h).
     ``logprobs``: the loop owns ``lp_model`` and ``lp_sampled`` ([n_new, B] fp32, device resident: the two log-probabilities of every
-    sampled id, include/omlm.h) and both sampler calls of the cycle go through omlm_sample_lp, which writes row *step_dev of each -- a
+    sampled id, include/omlm.h) and the calls go through omlm_sample_lp instead, which writes row *step_dev of each -- a
     captured cycle stays valid.  The ids are those of the loop without it; ``run()`` still returns them."""
 
     def __init__(self, dec: CachedDecoder, first_logits: torch.Tensor, uniforms: Optional[torch.Tensor], n0: int, n_new: int, topk: int,
                  temperature: float, forbid_by_phase: Sequence[bool], use_graph: bool = True, rng=None, top_p=None,
                  logprobs: bool = False):
         ops.check_sampler_width(dec.V1)                    # before any launch: the loop's first sampler call would refuse it
-        self.top_p = ops.check_top_p(top_p)                # 1.0: no nucleus, the cycle calls what it calls without the argument
+        self.top_p = ops.check_top_p(top_p)                # 1.0: no nucleus
         if (uniforms is None) == (rng is None):
             raise ValueError("SamplingLoop: give either the uniforms [n_new, B, V1] or rng=(seed, row0), not both and not neither")
         self.dec, self.n0, self.n_new, self.topk, self.temperature = dec, n0, n_new, topk, float(temperature)
@@ -364,29 +365,21 @@ class SamplingLoop:
         self.logprobs = bool(logprobs)
         self.lp_model = torch.zeros(n_new, dec.B, device=dev, dtype=torch.float32) if self.logprobs else None
         self.lp_sampled = torch.zeros(n_new, dec.B, device=dev, dtype=torch.float32) if self.logprobs else None
-        # which sampler entry points the cycle calls, and their arguments between `logits` and `out`
-        if rng is None:
-            self._sfx, self._src = "", (ptr(self.U), ptr(self.step_dev))
-        else:
-            self._sfx, self._src = "_rng", (*self.seed, ptr(self.step_dev), self.row0)
+        # the sampler's argument blocks (ops.SampleArgs), built once: per quantizer phase, without and with the embedding gather of the
+        # sampled id.  Every pointer in them is a fixed buffer of this loop or its decoder.
+        seed, row0 = ((0, 0), 0) if rng is None else (self.seed, self.row0)
+
+        def block(phase: int, embed: bool):
+            sa = ops.SampleArgs(ptr(dec.logits), dec.B, dec.V1, dec.ldV, ptr(self.U), *seed, 0, row0, ptr(self.step_dev), ptr(self.cur),
+                                ptr(self.hist), self.topk, self.temperature, self.top_p, int(self.forbid[phase]))
+            if embed:
+                sa.emb_table, sa.emb_row_offset, sa.emb_rows = dec.emb.data_ptr(), dec.codebook * phase if dec.Q > 1 else 0, dec.emb.shape[0]
+                sa.x, sa.D = ptr(dec.x), dec.D
+            return sa
+        self._blocks = [(block(phase, False), block(phase, True)) for phase in range(dec.Q)]
         dec.logits.copy_(first_logits)
         self.use_graph = use_graph
         self.graphs = {}
-
-    def _sample_top_p(self, phase: int, embed: bool):
-        """The nucleus forms of the cycle's two sampler calls, through the one entry point that has them (omlm_sample); with logprobs,
-        every form of them, through omlm_sample_lp."""
-        dec = self.dec
-        seed, row0 = ((0, 0), 0) if self.U is not None else (self.seed, self.row0)
-        sa = ops.SampleArgs(ptr(dec.logits), dec.B, dec.V1, dec.ldV, ptr(self.U), *seed, 0, row0, ptr(self.step_dev), ptr(self.cur),
-                            ptr(self.hist), self.topk, self.temperature, self.top_p, int(self.forbid[phase]))
-        if embed:
-            sa.emb_table, sa.emb_row_offset, sa.emb_rows = dec.emb.data_ptr(), dec.codebook * phase if dec.Q > 1 else 0, dec.emb.shape[0]
-            sa.x, sa.D = ptr(dec.x), dec.D
-        if self.logprobs:
-            call("omlm_sample_lp", C.addressof(sa), ptr(self.lp_model), ptr(self.lp_sampled), stream_ptr())
-        else:
-            call("omlm_sample", C.addressof(sa), stream_ptr())
 
     def _cycle(self, k: int, with_decode: bool):
         """Sample id number k (global index in the predicted sequence) from dec.logits, then compute its row."""
@@ -394,15 +387,11 @@ class SamplingLoop:
         phase = k % dec.Q
         # with_decode, 32 launches per id: the sampler also gathers the embedding row of the id it picked (the step's first launch), and
         # the head kernel (the step's last) moves the row index and the sampler's step counter on
-        if self.top_p < 1.0 or self.logprobs:
-            self._sample_top_p(phase, with_decode)
-        elif not with_decode:
-            call("omlm_sample_topk_gumbel_at" + self._sfx, ptr(dec.logits), *self._src, ptr(self.cur), ptr(self.hist),
-                 dec.B, dec.V1, dec.ldV, self.topk, self.temperature, int(self.forbid[phase]), stream_ptr())
+        sa = self._blocks[phase][with_decode]
+        if self.logprobs:
+            call("omlm_sample_lp", C.addressof(sa), ptr(self.lp_model), ptr(self.lp_sampled), stream_ptr())
         else:
-            call("omlm_sample_embed_at" + self._sfx, ptr(dec.logits), *self._src, ptr(self.cur), ptr(self.hist),
-                 dec.B, dec.V1, dec.ldV, self.topk, self.temperature, int(self.forbid[phase]),
-                 dec.emb.data_ptr(), dec.codebook * phase if dec.Q > 1 else 0, dec.emb.shape[0], ptr(dec.x), dec.D, stream_ptr())
+            call("omlm_sample", C.addressof(sa), stream_ptr())
         if not with_decode:
             return
         if dec.pos_emb is not None:

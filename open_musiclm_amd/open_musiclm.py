@@ -276,28 +276,14 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 for ind in range(Q):
                     last = self.transformer.last_logits(cond + [sampled])
                     forbid = (not allow_eos_in_output) or (ind != Q - 1)
-                    if return_logprobs:
-                        if counter:
-                            src = dict(seed=sampler_seed, step=step)
-                        elif exists(uniforms):
-                            src = dict(uniform=uniforms[step].to(device).float().contiguous())
-                        else:
-                            src = dict(uniform=torch.empty(batch, V1, device=device).uniform_(0, 1))
-                        ops.sample(last, nxt, V1, k, temperature, forbid, top_p=top_p, lp_model=lp_model[step], lp_sampled=lp_sampled[step], **src)
-                    elif counter:
-                        if top_p < 1.0:
-                            ops.sample(last, nxt, V1, k, temperature, forbid, top_p=top_p, seed=sampler_seed, step=step)
-                        else:
-                            ops.sample_topk_gumbel_rng(last, sampler_seed, step, 0, nxt, V1, k, temperature, forbid)
+                    if counter:
+                        src = dict(seed=sampler_seed, step=step)
+                    elif exists(uniforms):
+                        src = dict(uniform=uniforms[step].to(device).float().contiguous())
                     else:
-                        if exists(uniforms):
-                            u = uniforms[step].to(device).float().contiguous()
-                        else:
-                            u = torch.empty(batch, V1, device=device).uniform_(0, 1)
-                        if top_p < 1.0:
-                            ops.sample(last, nxt, V1, k, temperature, forbid, top_p=top_p, uniform=u)
-                        else:
-                            ops.sample_topk_gumbel(last, u, nxt, V1, k, temperature, forbid)
+                        src = dict(uniform=torch.empty(batch, V1, device=device).uniform_(0, 1))
+                    lp = dict(lp_model=lp_model[step], lp_sampled=lp_sampled[step]) if return_logprobs else {}
+                    ops.sample(last, nxt, V1, k, temperature, forbid, top_p=top_p, **src, **lp)
                     sampled = torch.cat((sampled, nxt[:, None]), dim=-1)
                     step += 1
             if return_logprobs:

@@ -786,7 +786,7 @@ def kmeans_inertia(x, centres_T, out, labels=None):
     call("omlm_kmeans_inertia", ptr(x), ptr(centres_T), ptr(out), ptr(labels), int(n), int(D), int(K), stream_ptr())
 
 
-SAMPLER_MAX_V = 65536             # csrc/optim_misc.hip: widest row the sampler takes (V = codebook_size + 1); the uint16 token stores end there too
+SAMPLER_MAX_V = 65536             # csrc/sampler.hip: widest row the sampler takes (V = codebook_size + 1); the uint16 token stores end there too
 
 
 def check_sampler_width(V):

@@ -1,7 +1,7 @@
 """Plain fp64 restatements of the fused sampler's kept-set rule and of the fp16 loss-scale state machine, used by
 tests/test_gpu_loss_optim_sampler.py (GPU) and tests/test_sampler_ref_host.py (CPU).
 
-Sampler (csrc/optim_misc.hip, sample_kernel): with `forbid_last` the last logit is -inf first; every entry strictly above the k-th
+Sampler (csrc/sampler.hip, sample_kernel): with `forbid_last` the last logit is -inf first; every entry strictly above the k-th
 largest value is kept, and of the entries equal to it the LOWEST indices are kept until k entries are kept; the id is the first maximum of
 l / T - log(-log(u + 1e-20) + 1e-20) over the kept entries (index 0 when every kept entry is -inf, as torch.argmax of an all -inf row)."""
 import torch

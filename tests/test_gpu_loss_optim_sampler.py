@@ -1,5 +1,5 @@
 """GPU: the kernels at both ends of a training step and of a sampled token -- cross-entropy (csrc/embed_ce.hip), the token
-gather, the top-k Gumbel sampler, the Adam/AdamW step with its loss-scale machine and the grad-norm reduction (csrc/optim_misc.hip),
+gather, the top-k Gumbel sampler (csrc/sampler.hip), the Adam/AdamW step with its loss-scale machine and the grad-norm reduction (csrc/optim_misc.hip),
 and FusedAdam end to end -- against fp64 torch on the CPU, on every route their launchers pick (wave / workgroup kernels, 16-byte /
 element paths, <17> / <32> sampler slots) and past their grid caps.  Every bar sits next to its check with its reason; every measured
 error goes to the kernel report through test_gpu_kernels.report()."""

@@ -1,5 +1,5 @@
 """GPU: the log-probabilities of the sampled id -- the LP = true instantiations of sample_kernel / sample_wide_kernel behind
-omlm_sample_lp (include/omlm.h; csrc/optim_misc.hip), ops.sample(lp_model=, lp_sampled=), decode.SamplingLoop(logprobs=True),
+omlm_sample_lp (include/omlm.h; csrc/sampler.hip), ops.sample(lp_model=, lp_sampled=), decode.SamplingLoop(logprobs=True),
 generate(return_logprobs=True) and score().
 
 Against the fp64 restatement (tests/sampler_logprob_ref.py), whose docstring derives the tolerance and the bracket that the nucleus'

@@ -1,4 +1,4 @@
-"""GPU: the sampler on its counter-based uniform stream (include/omlm.h; csrc/optim_misc.hip, the RNG = true instantiations).
+"""GPU: the sampler on its counter-based uniform stream (include/omlm.h; csrc/sampler.hip, the RNG = true instantiations).
 
 The central check: a stream entry point returns, id for id, what the buffer entry point returns when it is fed the numpy restatement of
 the stream (tests/sampler_stream_ref.py).  Both run the same sampler function of (logits, u) and the stream's values are exact in float32,
@@ -170,15 +170,29 @@ def test_generate_on_the_stream_equals_generate_fed_the_restatement(dev, tiny204
         wrapper.generate(conditioning_token_ids=cond, max_time_steps=steps, sampler_rng="philox", **ROUTES[route])
 
 
-def test_ids_do_not_depend_on_how_the_batch_is_cut(dev, tiny2048, monkeypatch):
-    """With one sample per decode call (row0 = 0, 1) the stream gives the ids of the two-sample call."""
+def test_ids_do_not_depend_on_how_the_batch_is_cut(ops, dev, tiny2048, monkeypatch):
+    """With one sample per decode call (row0 = 0, 1) the stream gives the ids of the two-sample call.  And the loop's one sampler path
+    (omlm_sample on a block built once; top_p None, no logprobs) draws the stream of the entry point that predates it: every id of the
+    cut call again, through ops.sample_topk_gumbel_rng on the logits the loop sampled it from, same seed, step and row0."""
     from open_musiclm_amd import decode
     wrapper, cond = tiny2048
     whole = wrapper.generate(conditioning_token_ids=cond, max_time_steps=6, sampler_rng="counter", sampler_seed=11)
     monkeypatch.setattr(decode, "max_call_batch", lambda *a, **k: 1)
+    seen, cycle = [], decode.SamplingLoop._cycle
+
+    def recording_cycle(self, k, with_decode):
+        seen.append((self, k - self.n0, self.dec.logits.clone()))
+        cycle(self, k, with_decode)
+    monkeypatch.setattr(decode.SamplingLoop, "_cycle", recording_cycle)
     cut = wrapper.generate(conditioning_token_ids=cond, max_time_steps=6, sampler_rng="counter", sampler_seed=11)
     assert torch.equal(cut, whole), (cut.tolist(), whole.tolist())
     assert not torch.equal(whole[0], whole[1])                                  # the samples draw from different rows of the stream
+    assert sorted((loop.row0, step) for loop, step, _ in seen) == [(b, t) for b in range(2) for t in range(6)]
+    out = torch.empty(1, device=dev, dtype=torch.long)
+    for loop, step, logits in seen:
+        assert loop.top_p == 1.0 and not loop.logprobs and loop.U is None and loop.dec.Q == 1
+        ops.sample_topk_gumbel_rng(logits, 11, step, loop.row0, out, loop.dec.V1, loop.topk, loop.temperature, loop.forbid[0])
+        assert torch.equal(out, loop.hist[step]), (loop.row0, step, out.tolist(), loop.hist[step].tolist())
 
 
 @pytest.mark.parametrize("use_cache", [True, False])

@@ -1,5 +1,5 @@
 """GPU: the sampler's nucleus (top-p) -- the NUC = true instantiations of sample_kernel / sample_wide_kernel behind omlm_sample
-(include/omlm.h; csrc/optim_misc.hip), ops.sample, decode.SamplingLoop and generate(top_p=...).
+(include/omlm.h; csrc/sampler.hip), ops.sample, decode.SamplingLoop and generate(top_p=...).
 
 Against the fp64 restatement (tests/sampler_top_p_ref.py), whose docstring derives the one allowance: a row whose id depends on where
 inside p (1 +- 2^-16) the cut falls is left out, at most one such row per case; and the existing near-tie allowance on the Gumbel scores.

@@ -1,4 +1,4 @@
-"""GPU: the workgroup-wide sampler (csrc/optim_misc.hip, sample_wide_kernel) that serves rows of 2048 < V <= 65536 logits -- the same
+"""GPU: the workgroup-wide sampler (csrc/sampler.hip, sample_wide_kernel) that serves rows of 2048 < V <= 65536 logits -- the same
 function of (logits, uniforms, k, T, forbid_last) as the wave kernel, checked against the fp64 restatement in loss_optim_sampler_ref.py
 with the recipes of test_gpu_loss_optim_sampler.py, and against the wave kernel itself.
 

@@ -104,7 +104,7 @@ def test_entry_point_is_declared_and_the_host_takes_the_arguments():
     from open_musiclm_amd import decode, hip, ops
     from open_musiclm_amd import open_musiclm as M
     hdr = open(os.path.join(ROOT, "include", "omlm.h")).read()
-    src = open(os.path.join(ROOT, "open_musiclm_amd", "csrc", "optim_misc.hip")).read()
+    src = open(os.path.join(ROOT, "open_musiclm_amd", "csrc", "sampler.hip")).read()
     m = re.search(r"int omlm_sample_lp\(([^)]*)\);", hdr)
     assert m and m.group(1).split(",")[0].strip() == "const omlm_sample_args* args"
     assert len(hip.SIGNATURES["omlm_sample_lp"]) == m.group(1).count(",") + 1 == 4

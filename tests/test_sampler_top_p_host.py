@@ -150,7 +150,7 @@ def test_sample_args_layout_matches_header(tmp_path):
 def test_header_source_and_signatures_name_the_entry_point():
     from open_musiclm_amd import hip
     hdr = open(os.path.join(ROOT, "include", "omlm.h")).read()
-    src = open(os.path.join(ROOT, "open_musiclm_amd", "csrc", "optim_misc.hip")).read()
+    src = open(os.path.join(ROOT, "open_musiclm_amd", "csrc", "sampler.hip")).read()
     m = re.search(r"int omlm_sample\(([^)]*)\);", hdr)
     assert m and len(hip.SIGNATURES["omlm_sample"]) == m.group(1).count(",") + 1
     assert 'extern "C" int omlm_sample(const omlm_sample_args* a, void* stream)' in src

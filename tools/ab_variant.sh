@@ -11,7 +11,7 @@ make -C "$CS" -j16 >/dev/null
 tmp=/tmp/omlm_variant_$name; mkdir -p "$tmp" "$ROOT/.variants"
 F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-value -Wno-inline-asm"
 objs=""
-for o in gemm attention attention2 attention3 norm ffmid ffmid2 embed_ce optim_misc decode vq_fit; do
+for o in gemm attention attention2 attention3 norm ffmid ffmid2 embed_ce optim_misc sampler decode vq_fit kmeans_fit; do
     if [[ " $srcs " == *" $o "* ]]; then
         hipcc $F "$@" -c "$CS/$o.hip" -o "$tmp/$o.o" &
         objs="$objs $tmp/$o.o"
