@@ -539,7 +539,11 @@ int omlm_sample_lp(const omlm_sample_args* args, float* lp_model, float* lp_samp
  *   splitk_ws   OMLM_DECODE_SPLITK_FLOATS_B(B, D) floats  = G * OMLM_DECODE_SPLITK_FLOATS(D)
  *   splitk_cnt  OMLM_DECODE_SPLITK_CNT_B(B, D) ints       = max(G * ceil(D / 16), B, 16): FF-out takes its tickets per (group, tile), the
  *               attention combine per sample, in the same array; all zero before the first step, every step leaves them zero.
- * The library sees pointers only and cannot check these sizes; it checks that the scratch a batch needs is given. */
+ * The library sees pointers only and cannot check these sizes; it checks that the scratch a batch needs is given.
+ * Every refusal of omlm_decode_step (an argument error with its reason in omlm_last_error) is decided from the sizes and from which pointers
+ * are given, and returned BEFORE anything is launched: a refused call leaves x, the caches, hist and every scratch buffer untouched -- the
+ * lo-plane argument checks and the head's missing-partials check included, which used to come after the embedding gather or the row sums
+ * had run. */
 typedef struct omlm_decode_args {
     int B, D, H, L, F, Fp, Nmax, w_dtype, round_bf16, nsplit;     /* nsplit >= ceil(Nmax / 64): attention key ranges */
     float eps, scale;

@@ -18,6 +18,7 @@
 // TW = h16_t: weights are the bf16 operand copies ("bf16" mode; activations that the batched path rounds to bf16 before
 // its GEMMs are rounded here too, so both paths see the same operands); TW = float: fp32 weights, fp32 FMA chains.
 #include "common.h"
+#include "decode_plan.h"     // the step kernels' geometry (DEC_*, DEC2_*, DEC4_*), and what a call runs
 // The step kernels are single dependent chains (load -> LayerNorm statistics -> dot products -> reduction -> store): the wave
 // reductions run on the VALU (DPP row steps + readlanes) instead of six dependent ds_bpermute round trips each.  Measured on the
 // B = 1 step (MI355X, tools/decode_probe.py, same box): 154.6 -> 145.8 us per id with the three reductions of the GEMV kernels alone.
@@ -28,10 +29,8 @@
 
 namespace OMLM_NS {
 
-#define DEC_T 256
-#define DEC_BMAX 8
-#define DEC_ROWS 16            // weight rows per workgroup (4 per wave)
-#define DEC_KS 64              // keys per attention split
+using namespace omlm_plan;      // DEC2_QKV ... DEC2_LNGEMV
+
 #define DEC_PART 66            // floats per (split, head) partial: max, sum, o[64]
 
 struct omlm_decode_args {
@@ -346,7 +345,6 @@ __global__ __launch_bounds__(DEC_T) void dec_attn_kernel(const float* __restrict
 // (q, the 64-key K / V tiles, scales) is requested at the top; the new key is l2-normalised in registers by the 16 lanes that
 // loaded it (sum of squares through 4 lane swaps) before it goes to LDS and back to the cache; the probabilities reach the
 // P.V loop through the wave's own LDS row (same-wave LDS ordering, no barrier).
-#define DEC_AT2 512
 // comb_out / comb_cnt (optional; the batched matrix-core step): the workgroups of a sample count their arrivals in comb_cnt[b] (zero on
 // entry and exit) and the last one combines the sample's partials into comb_out[b, H * 64] -- what dec_attn_combine_kernel did as a
 // launch of its own (5 us of every layer's ~50).  comb_out may be q's buffer: every reader of q[b, :] has arrived by then.
@@ -578,7 +576,6 @@ __global__ __launch_bounds__(DEC_T) void dec_ffin_kernel(const float* __restrict
 //   * the activation is staged raw, with its LayerNorm statistics taken in ONE pass (sum and sum of squares, one barrier);
 //     each lane normalises the pieces it multiplies on the fly;
 //   * the attention partials are combined with all their loads in flight at once.
-#define DEC2_ROWS 4
 
 template <typename TW> struct dec_wreg;
 template <> struct dec_wreg<h16_t> { u32x4 r;
@@ -651,8 +648,6 @@ __device__ __forceinline__ void dec2_stage_attention(const float* __restrict__ p
     }
     __syncthreads();
 }
-
-enum { DEC2_QKV = 0, DEC2_OUT = 1, DEC2_FFIN = 2, DEC2_LNGEMV = 3 };
 
 struct dec2_args {
     const float* in; int ldin; int K, Kstat; const float* gamma; float eps;       // activation (+ LayerNorm over Kstat when gamma)
@@ -792,14 +787,6 @@ __global__ __launch_bounds__(DEC_T) void dec2_kernel(dec2_args a) {
             if (a.adv_step) a.adv_step[0] += 1;
         }
     }
-}
-
-template <typename TW, int NI, int MODE>
-static void dec2_launch(const dec2_args& a, int grid, hipStream_t st) {
-    const size_t lds = ((size_t)a.B * a.K + DEC_BMAX * 8 + DEC_BMAX * 2 + 4 * DEC_BMAX) * sizeof(float);
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)dec2_kernel<TW, NI, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    hipLaunchKernelGGL((dec2_kernel<TW, NI, MODE>), dim3(grid), dim3(DEC_T), lds, st, a);
 }
 
 // ---- B == 1 fast path: no LDS, no barrier.  Every wave loads the whole activation row itself (L2 hits; exactly the pieces its
@@ -1001,10 +988,6 @@ __global__ __launch_bounds__(DEC_T) void dec3_ffin_kernel(dec2_args a) {
 // IS 8 consecutive k of one row), B = the samples (padded to 16 columns with zero operands).  The four waves take interleaved
 // 32-wide k-steps of the same rows (all of a wave's loads requested before anything else, as above) and their partial tiles meet in
 // LDS -- no cross-lane reductions at all.  Same products (16-bit x 16-bit, exact in fp32), fp32 accumulation in a different order.
-#define DEC4_T 256
-#define DEC4_ROWS 16
-#define DEC4_NB 16
-#define DEC4_GMAX 4            // groups of DEC4_NB samples per call
 typedef __attribute__((ext_vector_type(4))) float dec4_acc;
 
 // Attention output of the new row from the per-split partials, ONCE per step: [B][H * 64] fp32 (rounded to the operand type).  The
@@ -1037,7 +1020,6 @@ __global__ __launch_bounds__(64) void dec_attn_combine_kernel(const float* __res
 // PL ("fp16ff": FF-in, FF-out, head): the weights are hi + lo planes and the normalised activations keep a lo image next to the hi one -- three
 // MFMAs per k-step (hi hi + hi lo + lo hi, the batched forward's omlm_gemm_planes16 arithmetic).  The images hold DEC4_IMG(NS) samples; a
 // larger batch (FF-out rows at B > 8) runs its k-loop twice.  Needs the producers' LayerNorm partials (stat_in).
-#define DEC4_IMG(NS) ((((NS) + 7) / 8) == 1 ? 16 : 8)
 // GRP (a call of more than 16 samples): gridDim.y groups of 16 consecutive samples, the last one possibly partial.  A workgroup serves ONE
 // group exactly as it serves a whole call otherwise -- same branches for its own sample count, same summation order -- with every
 // per-sample pointer moved on by 16 g samples and the LayerNorm partials / split-K slabs / tickets in the group's own region.  gridDim.x
@@ -1450,152 +1432,136 @@ __global__ __launch_bounds__(DEC4_T) void dec4_kernel(dec2_args a) {
     }
 }
 
-template <int NS, int MODE, bool PL, bool GRP>
-static void dec4_launch_t(const dec2_args& a, dim3 grid, hipStream_t st) {
-    const int kmax = a.nsl > 1 ? 32 * (((a.K >> 5) + a.nsl - 1) / a.nsl) : a.K;       // longest k-range of a workgroup
-    const int nb = a.B < DEC4_NB ? a.B : DEC4_NB;                                     // samples of a workgroup
-    const size_t lds = (((size_t)(PL ? 2 * DEC4_IMG(NS) : nb) * (kmax + 8) * 2 + 15) & ~(size_t)15) + (size_t)(DEC4_NB * 8 + DEC4_NB * 2 + 4 * 256 + 256) * sizeof(float) +
-                       ((a.gamma && !a.stat_in) ? (size_t)nb * kmax * sizeof(float) : 0);       // fp32 staging copy: own-reduction path only (B <= 8)
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)dec4_kernel<NS, MODE, PL, GRP>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-    hipLaunchKernelGGL((dec4_kernel<NS, MODE, PL, GRP>), grid, dim3(DEC4_T), lds, st, a);
-}
-// B <= 16: one group, the plain instantiation on a grid of `grid` workgroups.  B > 16: the GRP instantiation, the group along gridDim.y and
-// gridDim.x padded to a multiple of 8 (the head's 65 tiles) so that a tile's groups share an XCD.
-template <int NS, int MODE, bool PL = false>
-static void dec4_launch(const dec2_args& a, int grid, hipStream_t st) {
-    if (a.B <= DEC4_NB) { dec4_launch_t<NS, MODE, PL, false>(a, dim3(grid), st); return; }
-    dec2_args w = a;
-    w.gtiles = grid;
-    dec4_launch_t<NS, MODE, PL, true>(w, dim3((grid + 7) & ~7, (a.B + DEC4_NB - 1) / DEC4_NB), st);
-}
-// the matrix-core step kernels serve 16-bit weights with D, H * 64, Fp multiples of 32 and k-loops of at most 4 x 24 steps
-static bool dec4_ok(const omlm_decode_args& a) {
-    // B > 8: every LayerNorm in front of a matrix-core kernel must find its statistics in the producers' partials (the own-reduction
-    // path stages fp32 rows for at most 8 samples): a.ln_parts given
-    const bool wide_ok = a.B <= 8 || a.ln_parts != nullptr;
-    return a.B >= 2 && a.B <= DEC4_GMAX * DEC4_NB && wide_ok && a.D % 32 == 0 && a.D <= 1024 && (a.H * 64) % 32 == 0 && a.H * 64 <= 1024 &&
-           a.Fp % 32 == 0 && a.Fp <= 3072 && a.Fp % 8 == 0;
+// ---- host side.  csrc/decode_plan.h decides what a call runs -- the launches in order, their kernels' template arguments, grids, LDS bytes and
+// per-launch scalars -- or why it is refused; the code below fills the kernels' arguments from omlm_decode_args and launches what the plan
+// lists.  Order of first use: the kernels stand in the module in the order in which the functions below name them, and the compiled
+// kernels depend on it (as sampler.hip notes for its own): the families in the order of decode_launch's switch, inside a family the order of
+// its switch.  tools/sampler_isa_diff.py compares every kernel with its predecessor's.
+using omlm_plan::DecodeCall;
+using omlm_plan::DecodeLaunch;
+using omlm_plan::DecodePlan;
+static_assert(omlm_plan::DEC_ERR_ARG == OMLM_ERR_ARG && omlm_plan::DEC_LDS_CAP == 160 * 1024, "decode_plan.h states the return code and launch_lds_cap's size");
+
+static DecodeCall decode_call(const omlm_decode_args& a, const long long* ids) {
+    DecodeCall c;
+    memset(&c, 0, sizeof(c));
+    c.B = a.B; c.D = a.D; c.H = a.H; c.L = a.L; c.Fp = a.Fp; c.Nmax = a.Nmax; c.nsplit = a.nsplit; c.V1 = a.V1;
+    c.w_dtype = a.w_dtype; c.fp16_copy = OMLM_FP16 != 0; c.round_bf16 = a.round_bf16 != 0; c.kv16 = a.kv16 != 0;
+    c.pos_dev = a.pos_dev != nullptr; c.parts = a.parts != nullptr; c.ids = ids != nullptr; c.emb_table = a.emb_table != nullptr;
+    c.head_W = a.head_W != nullptr; c.ln_parts = a.ln_parts != nullptr; c.splitk_ws = a.splitk_ws != nullptr; c.splitk_cnt = a.splitk_cnt != nullptr;
+    c.W1p_lo = a.W1p_lo != nullptr; c.W2p_lo = a.W2p_lo != nullptr; c.head_W_lo = a.head_W_lo != nullptr; c.k_new = a.k_new != nullptr;
+    c.advance_pos = a.advance_pos != nullptr;
+    return c;
 }
 
-template <typename TW, int NI, int MODE>
-static void dec3_launch(const dec2_args& a, int units, hipStream_t st) {
-    hipLaunchKernelGGL((dec3_kernel<TW, NI, MODE>), dim3((units + 3) / 4), dim3(DEC_T), 0, st, a);
-}
-
-template <typename TW>
-static int decode_step2_t(const omlm_decode_args& a, const long long* ids, hipStream_t st) {
-    const int B = a.B, D = a.D, H = a.H, Fp = a.Fp, HD = H * 64;
-    const size_t lds_at2 = (size_t)(64 * 65 + 64 * 64 + H * 64 + 8 * 64) * sizeof(float);
-    const bool mfma = sizeof(TW) == 2 && dec4_ok(a);              // 16-bit weights, B >= 2: the matrix-core step kernels
-    // LayerNorm partial sums of the matrix-core kernels (see dec2_args::stat_in): three regions of a.ln_parts -- x (written by the embedding
-    // gather and by every FF-out launch, read by the q rows and the head), x1 (to_out -> FF-in), u (FF-in -> FF-out)
-    const int npd = (D + DEC4_ROWS - 1) / DEC4_ROWS, npf = (Fp + 7) / 8, region = (npd > npf ? npd : npf) * 2 * DEC4_NB;
-    float* st_x = (mfma && a.ln_parts) ? a.ln_parts : nullptr;
-    const int G = (B + DEC4_NB - 1) / DEC4_NB;                    // groups of 16 samples (B > 16: each with a region of its own in every family)
-    float* st_x1 = st_x ? st_x + (size_t)G * region : nullptr;
-    float* st_u = st_x ? st_x + (size_t)2 * G * region : nullptr;
-    int n_x = 0;                                                  // partials of x that are valid right now
-    if (a.emb_table) {
-        hipLaunchKernelGGL(dec_embed_kernel, dim3(B), dim3(DEC_T), 0, st, ids, a.emb_table, a.emb_row_offset, a.emb_rows, a.x, D, st_x, region);
-        n_x = 1;
-    } else if (st_x && B > DEC_BMAX) {
-        // the caller embedded the ids itself (sampler + gather kernel): one small launch leaves the rows' sums where the first q rows look for them
-        hipLaunchKernelGGL(dec_rowstat_kernel, dim3(B), dim3(DEC_T), 0, st, a.x, D, st_x, region);
-        n_x = 1;
-    }
+// The argument block of a weight-row launch of the second generation (dec2 / dec3 / dec4 kernels) in layer l.
+static dec2_args dec2_fill(const omlm_decode_args& a, const DecodePlan& p, const DecodeLaunch& k, int l) {
+    const int D = a.D, HD = a.H * 64, Fp = a.Fp;
+    // LayerNorm partial sums of the matrix-core kernels (see dec2_args::stat_in): three families of a.ln_parts, each with a region per group --
+    // x (written by the prologue and by every FF-out launch, read by the q rows and the head), x1 (to_out -> FF-in), u (FF-in -> FF-out)
+    float* const st_x = p.stat_x ? a.ln_parts : nullptr;
+    float* const st_x1 = p.stat_x1 ? a.ln_parts + (size_t)p.G * p.region : nullptr;
+    float* const st_u = p.stat_u ? a.ln_parts + (size_t)2 * p.G * p.region : nullptr;
     dec2_args g;
     memset(&g, 0, sizeof(g));
-    g.B = B; g.round_bf16 = a.round_bf16; g.eps = a.eps; g.H = H; g.nsplit = a.nsplit; g.pos_dev = a.pos_dev; g.Nmax = a.Nmax; g.Fp = Fp;
-    g.gstat = region;
-    // "fp16ff": FF-in / FF-out / head read W = hi + lo and keep their activations and h1 un-rounded (round_bf16 = 0 for those launches)
-    const bool pl = a.W1p_lo != nullptr;
-    // FF-out rows cut into four k-slices (see dec4_kernel): the matrix-core kernels with the producers' LayerNorm partials, scratch given
-    const bool split = mfma && st_x && a.splitk_ws && a.splitk_cnt && (Fp >> 5) >= 8;
-    if (pl) {
-        OMLM_CHECK_ARG(sizeof(TW) == 2 && a.W2p_lo && (!a.head_W || a.head_W_lo), "lo planes: 16-bit weights, all three families");
-        OMLM_CHECK_ARG(B == 1 || (mfma && st_x), "lo planes at B >= 2 run on the matrix-core step kernels (ln_parts given)");
-        OMLM_CHECK_ARG(Fp <= 3072, "lo planes: feed-forward width <= 3072");
+    g.B = a.B; g.round_bf16 = k.unrounded ? 0 : a.round_bf16; g.eps = a.eps; g.H = a.H; g.nsplit = a.nsplit; g.pos_dev = a.pos_dev; g.Nmax = a.Nmax; g.Fp = Fp;
+    g.gstat = p.region; g.gtiles = k.gtiles; g.nstat_in = k.nstat_in; g.nsl = k.nsl;
+    if (k.nsl) { g.sk_ws = a.splitk_ws; g.sk_cnt = a.splitk_cnt; }
+    switch (k.phase) {
+    case omlm_plan::DP_QKV:                                                            // q / k / v rows of the new token
+        g.in = a.x; g.ldin = D; g.K = D; g.Kstat = D; g.gamma = a.attn_gamma[l]; g.W = a.Wq[l]; g.W2 = a.Wkv[l]; g.ldw = D;
+        g.Nout = HD + 128; g.q = a.q; g.Kc = a.Kc[l]; g.Vc = a.Vc[l]; g.k_new = a.k_new; g.kv16 = a.kv16;
+        if (k.nstat_in) g.stat_in = st_x;
+        break;
+    case omlm_plan::DP_OUT:                                                            // x1 = x + attn Wo^T
+        g.K = HD; g.W = a.Wo[l]; g.ldw = HD; g.Nout = D; g.res = a.x; g.ldres = D; g.out = a.x1; g.ldout = D;
+        if (k.kernel == omlm_plan::DK_DEC4) { g.in = a.q; g.ldin = HD; g.Kstat = HD; g.stat_out = st_x1; }   // combined already (a.q is free again: the attention kernel consumed it)
+        else g.parts = a.parts;                                                        // the vector kernels combine while they stage
+        break;
+    case omlm_plan::DP_FFIN:                                                           // FF-in rows + conv + GEGLU
+        g.in = a.x1; g.ldin = D; g.K = D; g.Kstat = D; g.gamma = a.ffin_gamma[l]; g.W = a.W1p[l]; g.ldw = D; g.convw = a.convw[l];
+        g.hist = a.hist[l]; g.u = a.u;
+        if (k.nstat_in) { g.stat_in = st_x1; g.stat_out = st_u; }
+        if (k.pl) g.Wlo = a.W1p_lo[l];
+        break;
+    case omlm_plan::DP_FFOUT:                                                          // x = x1 + LN(u) W2^T
+        g.in = a.u; g.ldin = Fp; g.K = Fp; g.Kstat = a.F; g.gamma = a.mid_gamma[l]; g.W = a.W2p[l]; g.ldw = Fp; g.Nout = D;
+        g.res = a.x1; g.ldres = D; g.out = a.x; g.ldout = D;
+        if (k.nstat_in) { g.stat_in = st_u; g.stat_out = st_x; }
+        if (k.pl) g.Wlo = a.W2p_lo[l];
+        break;
+    default:                                                                           // DP_HEAD; its workgroup 0 moves the counters on
+        g.in = a.x; g.ldin = D; g.K = D; g.Kstat = D; g.gamma = a.final_gamma; g.W = a.head_W; g.ldw = D; g.Nout = a.V1;
+        g.out = a.logits; g.ldout = a.ldV;
+        g.adv_pos = a.advance_pos; g.adv_step = a.advance_step;
+        if (k.nstat_in) g.stat_in = st_x;
+        if (k.pl) g.Wlo = a.head_W_lo;
+        break;
     }
-    for (int l = 0; l < a.L; ++l) {
-        dec2_args q = g;                                                               // q / k / v rows of the new token
-        q.in = a.x; q.ldin = D; q.K = D; q.Kstat = D; q.gamma = a.attn_gamma[l]; q.W = a.Wq[l]; q.W2 = a.Wkv[l]; q.ldw = D;
-        q.Nout = HD + 128; q.q = a.q; q.Kc = a.Kc[l]; q.Vc = a.Vc[l]; q.k_new = a.k_new; q.kv16 = a.kv16;
-        if (st_x && n_x > 0) { q.stat_in = st_x; q.nstat_in = n_x; }
-        if (B == 1) dec3_launch<TW, 2, DEC2_QKV>(q, HD + 128, st);
-        else if (mfma) dec4_launch<8, DEC2_QKV>(q, (HD + 128) / DEC4_ROWS, st);
-        else        dec2_launch<TW, 2, DEC2_QKV>(q, (HD + 128) / DEC2_ROWS, st);
-        const bool comb_in_attn = mfma && a.splitk_cnt != nullptr;                     // the last workgroup of a sample combines its partials
-        float* const comb_out = comb_in_attn ? a.q : nullptr;
-        int* const comb_cnt = comb_in_attn ? a.splitk_cnt : nullptr;
-        if (a.kv16)
-            hipLaunchKernelGGL(dec_attn2_kernel<h16_t>, dim3(a.nsplit, B), dim3(DEC_AT2), lds_at2, st, a.q, (h16_t*)a.Kc[l], (const h16_t*)a.Vc[l],
-                               a.q_scale[l], a.k_scale[l], a.bias_table, a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16,
-                               comb_out, comb_cnt, a.k_new);
-        else
-            hipLaunchKernelGGL(dec_attn2_kernel<float>, dim3(a.nsplit, B), dim3(DEC_AT2), lds_at2, st, a.q, a.Kc[l], (const float*)a.Vc[l],
-                               a.q_scale[l], a.k_scale[l], a.bias_table, a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16,
-                               comb_out, comb_cnt, (const float*)nullptr);
-        dec2_args o = g;                                                               // x1 = x + attn Wo^T
-        o.K = HD; o.parts = a.parts; o.W = a.Wo[l]; o.ldw = HD; o.Nout = D; o.res = a.x; o.ldres = D; o.out = a.x1; o.ldout = D;
-        if (mfma) {                                                                    // combine once, then a plain (no LayerNorm) row product
-            if (!comb_in_attn) hipLaunchKernelGGL(dec_attn_combine_kernel, dim3(H, B), dim3(64), 0, st, a.parts, a.q, a.nsplit, H, a.pos_dev, a.round_bf16);
-            o.in = a.q; o.ldin = HD; o.Kstat = HD; o.gamma = nullptr; o.parts = nullptr;     // a.q is free again: the attention kernel consumed it
-            o.stat_out = st_x1;
-            dec4_launch<8, DEC2_LNGEMV>(o, (D + DEC4_ROWS - 1) / DEC4_ROWS, st);
-        } else if (HD <= 512) dec2_launch<TW, 1, DEC2_OUT>(o, (D + DEC2_ROWS - 1) / DEC2_ROWS, st);
-        else                dec2_launch<TW, 2, DEC2_OUT>(o, (D + DEC2_ROWS - 1) / DEC2_ROWS, st);
-        dec2_args f = g;                                                               // FF-in rows + conv + GEGLU
-        f.in = a.x1; f.ldin = D; f.K = D; f.Kstat = D; f.gamma = a.ffin_gamma[l]; f.W = a.W1p[l]; f.ldw = D; f.convw = a.convw[l];
-        f.hist = a.hist[l]; f.u = a.u;
-        if (st_x1) { f.stat_in = st_x1; f.nstat_in = npd; f.stat_out = st_u; }
-        if (pl) { f.Wlo = a.W1p_lo[l]; f.round_bf16 = 0; }
-        if constexpr (sizeof(TW) == 2) {
-            if (pl && B == 1) hipLaunchKernelGGL((dec3_ffin_kernel<TW, 2, true>), dim3((Fp + 7) / 8), dim3(DEC_T), 0, st, f);
-            else if (pl)      dec4_launch<8, DEC2_FFIN, true>(f, (Fp + 7) / 8, st);
-        }
-        if (pl) {
-        } else if (B == 1) hipLaunchKernelGGL((dec3_ffin_kernel<TW, 4>), dim3((Fp + 15) / 16), dim3(DEC_T), 0, st, f);
-        else if (mfma) dec4_launch<8, DEC2_FFIN>(f, (Fp + 7) / 8, st);
-        else dec2_launch<TW, 2, DEC2_FFIN>(f, Fp / 2, st);
-        dec2_args w = g;                                                               // x = x1 + LN(u) W2^T
-        w.in = a.u; w.ldin = Fp; w.K = Fp; w.Kstat = a.F; w.gamma = a.mid_gamma[l]; w.W = a.W2p[l]; w.ldw = Fp; w.Nout = D;
-        w.res = a.x1; w.ldres = D; w.out = a.x; w.ldout = D;
-        if (st_u) { w.stat_in = st_u; w.nstat_in = npf; w.stat_out = st_x; n_x = npd; }
-        if (pl) { w.Wlo = a.W2p_lo[l]; w.round_bf16 = 0; }
-        if constexpr (sizeof(TW) == 2) {
-            if (pl && B == 1) hipLaunchKernelGGL((dec3_kernel<TW, 6, DEC2_LNGEMV, true>), dim3((D + 3) / 4), dim3(DEC_T), 0, st, w);
-            else if (pl && split) { w.nsl = 4; w.sk_ws = a.splitk_ws; w.sk_cnt = a.splitk_cnt; dec4_launch<6, DEC2_LNGEMV, true>(w, 4 * ((D + DEC4_ROWS - 1) / DEC4_ROWS), st); }
-            else if (pl)      dec4_launch<24, DEC2_LNGEMV, true>(w, (D + DEC4_ROWS - 1) / DEC4_ROWS, st);
-        }
-        if (pl) {
-        } else if (B == 1 && Fp <= 3072) dec3_launch<TW, 6, DEC2_LNGEMV>(w, D, st);
-        else if (mfma && split) { w.nsl = 4; w.sk_ws = a.splitk_ws; w.sk_cnt = a.splitk_cnt; dec4_launch<6, DEC2_LNGEMV>(w, 4 * ((D + DEC4_ROWS - 1) / DEC4_ROWS), st); }
-        else if (mfma) dec4_launch<24, DEC2_LNGEMV>(w, (D + DEC4_ROWS - 1) / DEC4_ROWS, st);
-        else if (Fp <= 3072) dec2_launch<TW, 6, DEC2_LNGEMV>(w, (D + DEC2_ROWS - 1) / DEC2_ROWS, st);
-        else                 dec2_launch<TW, 8, DEC2_LNGEMV>(w, (D + DEC2_ROWS - 1) / DEC2_ROWS, st);
-    }
-    if (a.head_W) {
-        dec2_args h = g;
-        h.in = a.x; h.ldin = D; h.K = D; h.Kstat = D; h.gamma = a.final_gamma; h.W = a.head_W; h.ldw = D; h.Nout = a.V1;
-        h.out = a.logits; h.ldout = a.ldV;
-        h.adv_pos = a.advance_pos; h.adv_step = a.advance_step;
-        if (st_x && n_x > 0) { h.stat_in = st_x; h.nstat_in = n_x; }
-        if (pl) {
-            OMLM_CHECK_ARG(B == 1 || h.stat_in, "lo planes: the head needs the LayerNorm partials of the last FF-out launch (L >= 1)");
-            h.Wlo = a.head_W_lo; h.round_bf16 = 0;
-        }
-        if constexpr (sizeof(TW) == 2) {
-            if (pl && B == 1) hipLaunchKernelGGL((dec3_kernel<TW, 2, DEC2_LNGEMV, true>), dim3((a.V1 + 3) / 4), dim3(DEC_T), 0, st, h);
-            else if (pl)      dec4_launch<8, DEC2_LNGEMV, true>(h, (a.V1 + DEC4_ROWS - 1) / DEC4_ROWS, st);
-        }
-        if (pl) {
-        } else if (B == 1) dec3_launch<TW, 2, DEC2_LNGEMV>(h, a.V1, st);
-        else if (mfma) dec4_launch<8, DEC2_LNGEMV>(h, (a.V1 + DEC4_ROWS - 1) / DEC4_ROWS, st);
-        else        dec2_launch<TW, 2, DEC2_LNGEMV>(h, (a.V1 + DEC2_ROWS - 1) / DEC2_ROWS, st);
-    }
-    return omlm_post_launch("omlm_decode_step");
+    return g;
 }
+
+// From the descriptor to the instantiation: ONE switch per kernel family.  false: the plan names an instantiation this copy does not build.
+constexpr int dec_form(int n, int mode, bool pl) { return n * 8 + mode * 2 + pl; }
+#define DEC_GO_LDS(...) launch_lds_cap<__VA_ARGS__>(dim3(k.gx, k.gy), dim3(k.threads), (size_t)k.lds, st, g); return true
+#define DEC_GO(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(k.gx, k.gy), dim3(k.threads), 0, st, g); return true
+template <typename TW>
+static bool dec3_go(const DecodeLaunch& k, const dec2_args& g, hipStream_t st) {
+    switch (dec_form(k.n, k.mode, k.pl)) {
+    case dec_form(2, DEC2_QKV, false): DEC_GO(dec3_kernel<TW, 2, DEC2_QKV>);
+    case dec_form(6, DEC2_LNGEMV, false): DEC_GO(dec3_kernel<TW, 6, DEC2_LNGEMV>);
+    case dec_form(2, DEC2_LNGEMV, false): DEC_GO(dec3_kernel<TW, 2, DEC2_LNGEMV>);
+    }
+    if constexpr (sizeof(TW) == 2) switch (dec_form(k.n, k.mode, k.pl)) {
+    case dec_form(6, DEC2_LNGEMV, true): DEC_GO(dec3_kernel<TW, 6, DEC2_LNGEMV, true>);
+    case dec_form(2, DEC2_LNGEMV, true): DEC_GO(dec3_kernel<TW, 2, DEC2_LNGEMV, true>);
+    }
+    return false;
+}
+template <typename TW>
+static bool dec3_ffin_go(const DecodeLaunch& k, const dec2_args& g, hipStream_t st) {
+    if (k.n == 4 && !k.pl) { DEC_GO(dec3_ffin_kernel<TW, 4>); }
+    if constexpr (sizeof(TW) == 2) if (k.n == 2 && k.pl) { DEC_GO(dec3_ffin_kernel<TW, 2, true>); }
+    return false;
+}
+template <typename TW>
+static bool dec2_go(const DecodeLaunch& k, const dec2_args& g, hipStream_t st) {
+    switch (dec_form(k.n, k.mode, k.pl)) {
+    case dec_form(2, DEC2_QKV, false): DEC_GO_LDS(dec2_kernel<TW, 2, DEC2_QKV>);
+    case dec_form(1, DEC2_OUT, false): DEC_GO_LDS(dec2_kernel<TW, 1, DEC2_OUT>);
+    case dec_form(2, DEC2_OUT, false): DEC_GO_LDS(dec2_kernel<TW, 2, DEC2_OUT>);
+    case dec_form(2, DEC2_FFIN, false): DEC_GO_LDS(dec2_kernel<TW, 2, DEC2_FFIN>);
+    case dec_form(6, DEC2_LNGEMV, false): DEC_GO_LDS(dec2_kernel<TW, 6, DEC2_LNGEMV>);
+    case dec_form(8, DEC2_LNGEMV, false): DEC_GO_LDS(dec2_kernel<TW, 8, DEC2_LNGEMV>);
+    case dec_form(2, DEC2_LNGEMV, false): DEC_GO_LDS(dec2_kernel<TW, 2, DEC2_LNGEMV>);
+    }
+    return false;
+}
+// B <= 16: one group, the plain instantiation.  B > 16: the GRP instantiation, the group along gridDim.y
+template <int NS, int MODE, bool PL>
+static bool dec4_grp(const DecodeLaunch& k, const dec2_args& g, hipStream_t st) {
+    if (k.grp) { DEC_GO_LDS(dec4_kernel<NS, MODE, PL, true>); }
+    DEC_GO_LDS(dec4_kernel<NS, MODE, PL, false>);
+}
+template <typename TW>
+static bool dec4_go(const DecodeLaunch& k, const dec2_args& g, hipStream_t st) {
+    switch (dec_form(k.n, k.mode, k.pl)) {
+    case dec_form(8, DEC2_QKV, false): return dec4_grp<8, DEC2_QKV, false>(k, g, st);
+    case dec_form(8, DEC2_LNGEMV, false): return dec4_grp<8, DEC2_LNGEMV, false>(k, g, st);
+    case dec_form(8, DEC2_FFIN, false): return dec4_grp<8, DEC2_FFIN, false>(k, g, st);
+    case dec_form(6, DEC2_LNGEMV, false): return dec4_grp<6, DEC2_LNGEMV, false>(k, g, st);
+    case dec_form(24, DEC2_LNGEMV, false): return dec4_grp<24, DEC2_LNGEMV, false>(k, g, st);
+    }
+    if constexpr (sizeof(TW) == 2) switch (dec_form(k.n, k.mode, k.pl)) {
+    case dec_form(8, DEC2_FFIN, true): return dec4_grp<8, DEC2_FFIN, true>(k, g, st);
+    case dec_form(6, DEC2_LNGEMV, true): return dec4_grp<6, DEC2_LNGEMV, true>(k, g, st);
+    case dec_form(24, DEC2_LNGEMV, true): return dec4_grp<24, DEC2_LNGEMV, true>(k, g, st);
+    case dec_form(8, DEC2_LNGEMV, true): return dec4_grp<8, DEC2_LNGEMV, true>(k, g, st);
+    }
+    return false;
+}
+#undef DEC_GO
+#undef DEC_GO_LDS
 
 // ---- end of step: the row index (and the sampler's step counter) move on, on the device ----
 __global__ void dec_advance_kernel(int* pos_dev, int* step_dev) {
@@ -1610,61 +1576,91 @@ extern "C" int omlm_decode_advance(int* pos_dev, int* step_dev, void* stream) {
 }
 #endif
 
+// One launch of the plan, in layer l.  false: see above.
 template <typename TW>
-static int decode_step_t(const omlm_decode_args& a, const long long* ids, hipStream_t st) {
-    const int B = a.B, D = a.D, H = a.H, Fp = a.Fp;
-    const size_t tail = (DEC_ROWS * DEC_BMAX + 16) * sizeof(float);
-    const size_t lds_d = (size_t)B * D * sizeof(float) + tail;
-    const size_t lds_hd = (size_t)B * H * 64 * sizeof(float) + tail;
-    const size_t lds_fp = (size_t)B * Fp * sizeof(float) + tail;
-    const size_t lds_at = (size_t)(64 * 65 + 64 * 64 + 2 * H * 64) * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)dec_gemv_kernel<TW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)dec_qkv_kernel<TW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)dec_ffin_kernel<TW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)dec_attn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)dec_attn_kernel<h16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-    }
-    const int HD = H * 64;
-    const bool pl = a.W1p_lo != nullptr;
-    if (pl) OMLM_CHECK_ARG(a.W2p_lo && (!a.head_W || a.head_W_lo), "lo planes: all three families");
-    if (a.emb_table)
-        hipLaunchKernelGGL(dec_embed_kernel, dim3(B), dim3(DEC_T), 0, st, ids, a.emb_table, a.emb_row_offset, a.emb_rows, a.x, D, (float*)nullptr, 0);
-    for (int l = 0; l < a.L; ++l) {
-        hipLaunchKernelGGL((dec_qkv_kernel<TW>), dim3((HD + 128) / DEC_ROWS), dim3(DEC_T), lds_d, st, a.x, a.attn_gamma[l],
-                           (const TW*)a.Wq[l], (const TW*)a.Wkv[l], a.q, (void*)a.Kc[l], (void*)a.Vc[l], B, D, H, a.Nmax, a.pos_dev, a.eps,
-                           a.round_bf16, a.k_new, a.kv16);
-        if (a.kv16)
-            hipLaunchKernelGGL(dec_attn_kernel<h16_t>, dim3(a.nsplit, B), dim3(DEC_T), lds_at, st, a.q, (h16_t*)a.Kc[l], (const h16_t*)a.Vc[l],
-                               a.q_scale[l], a.k_scale[l], a.bias_table, a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale,
-                               a.round_bf16, a.k_new);
+static bool decode_launch(const DecodePlan& p, const DecodeLaunch& k, const omlm_decode_args& a, const long long* ids, int l, hipStream_t st) {
+    const int B = a.B, D = a.D, H = a.H, Fp = a.Fp, HD = H * 64;
+    const dim3 grid(k.gx, k.gy), wg(k.threads);
+    const size_t lds = (size_t)k.lds;
+    // (a lo-plane launch, "fp16ff": W = hi + lo, its activations and h1 un-rounded)
+    const int rb = k.unrounded ? 0 : a.round_bf16;
+    const float* const f0 = nullptr;
+    switch (k.kernel) {
+    case omlm_plan::DK_EMBED:
+        hipLaunchKernelGGL(dec_embed_kernel, grid, wg, 0, st, ids, a.emb_table, a.emb_row_offset, a.emb_rows, a.x, D, p.stat_x ? a.ln_parts : (float*)nullptr, p.region);
+        return true;
+    case omlm_plan::DK_ROWSTAT:     // the caller embedded the ids itself (sampler + gather kernel): the rows' sums, where the first q rows look for them
+        hipLaunchKernelGGL(dec_rowstat_kernel, grid, wg, 0, st, a.x, D, a.ln_parts, p.region);
+        return true;
+    case omlm_plan::DK_QKV1:
+        launch_lds_cap<dec_qkv_kernel<TW>>(grid, wg, lds, st, a.x, a.attn_gamma[l], (const TW*)a.Wq[l], (const TW*)a.Wkv[l], a.q, (void*)a.Kc[l], (void*)a.Vc[l],
+                                           B, D, H, a.Nmax, a.pos_dev, a.eps, a.round_bf16, a.k_new, a.kv16);
+        return true;
+    case omlm_plan::DK_ATTN1:
+        if (k.c16) launch_lds_cap<dec_attn_kernel<h16_t>>(grid, wg, lds, st, a.q, (h16_t*)a.Kc[l], (const h16_t*)a.Vc[l], a.q_scale[l], a.k_scale[l], a.bias_table,
+                                                          a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16, (const float*)a.k_new);
+        else launch_lds_cap<dec_attn_kernel<float>>(grid, wg, lds, st, a.q, a.Kc[l], (const float*)a.Vc[l], a.q_scale[l], a.k_scale[l], a.bias_table,
+                                                    a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16, f0);
+        return true;
+    case omlm_plan::DK_GEMV1:
+        if (k.phase == omlm_plan::DP_OUT)
+            launch_lds_cap<dec_gemv_kernel<TW>>(grid, wg, lds, st, f0, 0, f0, 0, a.eps, (const float*)a.parts, a.nsplit, H, a.pos_dev, (const TW*)a.Wo[l], (long long)HD, HD, D,
+                                                (const float*)a.x, D, a.x1, D, B, a.round_bf16, (const TW*)nullptr);
+        else if (k.phase == omlm_plan::DP_FFOUT)
+            launch_lds_cap<dec_gemv_kernel<TW>>(grid, wg, lds, st, (const float*)a.u, Fp, a.mid_gamma[l], a.F, a.eps, f0, 0, 0, (const int*)nullptr, (const TW*)a.W2p[l], (long long)Fp, Fp, D,
+                                                (const float*)a.x1, D, a.x, D, B, rb, k.unrounded ? (const TW*)a.W2p_lo[l] : (const TW*)nullptr);
         else
-            hipLaunchKernelGGL(dec_attn_kernel<float>, dim3(a.nsplit, B), dim3(DEC_T), lds_at, st, a.q, a.Kc[l], (const float*)a.Vc[l],
-                               a.q_scale[l], a.k_scale[l], a.bias_table, a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale,
-                               a.round_bf16, (const float*)nullptr);
-        hipLaunchKernelGGL((dec_gemv_kernel<TW>), dim3((D + DEC_ROWS - 1) / DEC_ROWS), dim3(DEC_T), lds_hd, st, (const float*)nullptr, 0,
-                           (const float*)nullptr, 0, a.eps, a.parts, a.nsplit, H, a.pos_dev, (const TW*)a.Wo[l], (long long)HD, HD, D,
-                           a.x, D, a.x1, D, B, a.round_bf16);
-        // (pl, "fp16ff": W = hi + lo for FF-in / FF-out / head, their activations and h1 un-rounded)
-        hipLaunchKernelGGL((dec_ffin_kernel<TW>), dim3(Fp / 8), dim3(DEC_T), lds_d, st, a.x1, a.ffin_gamma[l], (const TW*)a.W1p[l],
-                           a.convw[l], a.hist[l], a.u, B, D, Fp, a.eps, pl ? 0 : a.round_bf16, pl ? (const TW*)a.W1p_lo[l] : (const TW*)nullptr);
-        hipLaunchKernelGGL((dec_gemv_kernel<TW>), dim3((D + DEC_ROWS - 1) / DEC_ROWS), dim3(DEC_T), lds_fp, st, a.u, Fp, a.mid_gamma[l],
-                           a.F, a.eps, (const float*)nullptr, 0, 0, (const int*)nullptr, (const TW*)a.W2p[l], (long long)Fp, Fp, D,
-                           a.x1, D, a.x, D, B, pl ? 0 : a.round_bf16, pl ? (const TW*)a.W2p_lo[l] : (const TW*)nullptr);
+            launch_lds_cap<dec_gemv_kernel<TW>>(grid, wg, lds, st, (const float*)a.x, D, a.final_gamma, D, a.eps, f0, 0, 0, (const int*)nullptr, (const TW*)a.head_W, (long long)D, D, a.V1,
+                                                f0, 0, a.logits, a.ldV, B, rb, k.unrounded ? (const TW*)a.head_W_lo : (const TW*)nullptr);
+        return true;
+    case omlm_plan::DK_FFIN1:
+        launch_lds_cap<dec_ffin_kernel<TW>>(grid, wg, lds, st, (const float*)a.x1, a.ffin_gamma[l], (const TW*)a.W1p[l], a.convw[l], a.hist[l], a.u, B, D, Fp, a.eps, rb,
+                                            k.unrounded ? (const TW*)a.W1p_lo[l] : (const TW*)nullptr);
+        return true;
+    case omlm_plan::DK_ATTN2: {
+        // comb_in_attn: the last workgroup of a sample combines its partials into a.q
+        float* const comb_out = p.comb_in_attn ? a.q : nullptr;
+        int* const comb_cnt = p.comb_in_attn ? a.splitk_cnt : nullptr;
+        if (k.c16)
+            hipLaunchKernelGGL(dec_attn2_kernel<h16_t>, grid, wg, lds, st, a.q, (h16_t*)a.Kc[l], (const h16_t*)a.Vc[l], a.q_scale[l], a.k_scale[l], a.bias_table, a.bias_ld,
+                               a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16, comb_out, comb_cnt, a.k_new);
+        else
+            hipLaunchKernelGGL(dec_attn2_kernel<float>, grid, wg, lds, st, a.q, a.Kc[l], (const float*)a.Vc[l], a.q_scale[l], a.k_scale[l], a.bias_table, a.bias_ld,
+                               a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16, comb_out, comb_cnt, f0);
+        return true;
     }
-    if (a.head_W)
-        hipLaunchKernelGGL((dec_gemv_kernel<TW>), dim3((a.V1 + DEC_ROWS - 1) / DEC_ROWS), dim3(DEC_T), lds_d, st, a.x, D, a.final_gamma,
-                           D, a.eps, (const float*)nullptr, 0, 0, (const int*)nullptr, (const TW*)a.head_W, (long long)D, D, a.V1,
-                           (const float*)nullptr, 0, a.logits, a.ldV, B, pl ? 0 : a.round_bf16, pl ? (const TW*)a.head_W_lo : (const TW*)nullptr);
-    return omlm_post_launch("omlm_decode_step");
+    case omlm_plan::DK_COMBINE:
+        hipLaunchKernelGGL(dec_attn_combine_kernel, grid, wg, 0, st, a.parts, a.q, a.nsplit, H, a.pos_dev, a.round_bf16);
+        return true;
+    case omlm_plan::DK_DEC3: return dec3_go<TW>(k, dec2_fill(a, p, k, l), st);
+    case omlm_plan::DK_DEC3_FFIN: return dec3_ffin_go<TW>(k, dec2_fill(a, p, k, l), st);
+    case omlm_plan::DK_DEC4: return dec4_go<TW>(k, dec2_fill(a, p, k, l), st);
+    case omlm_plan::DK_DEC2: return dec2_go<TW>(k, dec2_fill(a, p, k, l), st);
+    default: return false;          // DK_ADVANCE is decode_run's
+    }
+}
+
+// The plan's launches in order: prologue, the layer's launches L times, head; then the check, and the advance where it is a launch of its own.
+template <typename TW>
+static int decode_run(const DecodePlan& p, const omlm_decode_args& a, const long long* ids, void* stream) {
+    hipStream_t st = as_stream(stream);
+    bool ok = true;
+    for (int i = 0; i < p.layer; ++i) ok = ok && decode_launch<TW>(p, p.l[i], a, ids, 0, st);
+    for (int l = 0; l < a.L; ++l)
+        for (int i = p.layer; i < p.tail; ++i) ok = ok && decode_launch<TW>(p, i == p.layer && l > 0 ? p.q_rest : p.l[i], a, ids, l, st);
+    for (int i = p.tail; i < p.n; ++i)
+        if (p.l[i].kernel != omlm_plan::DK_ADVANCE) ok = ok && decode_launch<TW>(p, p.l[i], a, ids, 0, st);
+    if (!ok) { omlm_set_error("omlm_decode_step: the plan names a kernel instantiation that this library does not build"); return OMLM_ERR_UNSUPPORTED; }
+    const int rc = omlm_post_launch("omlm_decode_step");
+    if (rc == OMLM_OK && p.advance == 2) return omlm_decode_advance(a.advance_pos, a.advance_step, stream);
+    return rc;
 }
 
 // One decode step for the row at index *pos_dev (see include/omlm.h).  ids: [B] int64 sampled in the previous step (used
 // when a->emb_table is set; otherwise a->x already holds the new row's embedding).  *pos_dev is advanced only through
 // a->advance_pos / a->advance_step (optional device counters bumped by the step's last kernel; pass pos_dev there to move on).
 // a->w_dtype: 0 = fp32 weights, 1 = bf16, 2 = fp16 (served by the fp16 copy of this file; a->round_bf16 then rounds to fp16).
+// A refusal is returned before anything is launched.
 #if !OMLM_FP16
 extern "C" int omlm_decode_step_h(const omlm_decode_args* a, const long long* ids, void* stream);
 #endif
@@ -1676,42 +1672,13 @@ extern "C" int OMLM_API(omlm_decode_step)(const omlm_decode_args* a, const long 
         b.w_dtype = 1;
         return omlm_decode_step_h(&b, ids, stream);
     }
-#else
-    OMLM_CHECK_ARG(a->w_dtype == 1, "the fp16 copy serves fp16 weights only");
 #endif
-    OMLM_CHECK_ARG(a->B >= 1 && a->B <= DEC4_GMAX * DEC4_NB, "decode batch must be 1..64");
-    OMLM_CHECK_ARG(a->B <= DEC_BMAX || (a->w_dtype != 0 && a->D == 1024 && dec4_ok(*a)),
-                   "decode batches of 9..64 run on the matrix-core kernels only (else at most 8): 16-bit weights, D = 1024, ln_parts given");
-    OMLM_CHECK_ARG(a->B <= DEC4_NB || (a->splitk_ws && a->splitk_cnt),
-                   "decode batches of 17..64 need splitk_ws and splitk_cnt (else at most 16)");
-    OMLM_CHECK_ARG(a->D % 8 == 0 && a->Fp % 8 == 0 && a->pos_dev && a->parts, "decode geometry");
-    OMLM_CHECK_ARG(a->H >= 1 && a->H <= 16 && (a->H * 64 + 128) % DEC_ROWS == 0, "heads");
-    OMLM_CHECK_ARG(a->nsplit * DEC_KS >= a->Nmax, "nsplit must cover Nmax keys");
-    OMLM_CHECK_ARG(a->B > DEC_BMAX || (size_t)a->B * a->Fp * sizeof(float) + 1024 <= 150 * 1024, "B * Fp exceeds the LDS budget");
-    OMLM_CHECK_ARG(!a->emb_table || ids, "ids required with an embedding table");
-    // a 16-bit cache holds the fp32 cache's numbers only where the steps round every key and value to the operand type anyway
-    OMLM_CHECK_ARG(!a->kv16 || (a->w_dtype != 0 && a->round_bf16 != 0 && a->k_new),
-                   "kv16 (16-bit K/V cache) needs 16-bit weights, round_bf16 and the k_new staging row");
-    const bool v2_ok = a->D == 1024 && a->H * 64 <= 1024 && a->Fp <= 4096 && a->Fp % 2 == 0 && (a->H * 64 + 128) % DEC2_ROWS == 0;
-    // batches of 9..16 exist only on the second-generation path's matrix-core kernels: the first-generation kernels below are sized for
-    // DEC_BMAX samples (LDS B * Fp floats, DEC_ROWS * DEC_BMAX tail) -- refuse instead of overrunning them (odd geometries)
-    OMLM_CHECK_ARG(a->B <= DEC_BMAX || v2_ok, "decode batches above 8 need the second-generation step kernels (D = 1024)");
-    if (v2_ok) {
-#if OMLM_FP16
-        const int rc = decode_step2_t<h16_t>(*a, ids, as_stream(stream));
-#else
-        const int rc = a->w_dtype == 0 ? decode_step2_t<float>(*a, ids, as_stream(stream)) : decode_step2_t<h16_t>(*a, ids, as_stream(stream));
+    const DecodePlan plan = omlm_plan::decode_plan(decode_call(*a, ids));
+    if (plan.rc != OMLM_OK) { omlm_set_error(plan.msg); return plan.rc; }
+#if !OMLM_FP16
+    if (a->w_dtype == 0) return decode_run<float>(plan, *a, ids, stream);
 #endif
-        if (rc == OMLM_OK && a->advance_pos && !a->head_W) return omlm_decode_advance(a->advance_pos, a->advance_step, stream);
-        return rc;
-    }
-#if OMLM_FP16
-    const int rc = decode_step_t<h16_t>(*a, ids, as_stream(stream));
-#else
-    const int rc = a->w_dtype == 0 ? decode_step_t<float>(*a, ids, as_stream(stream)) : decode_step_t<h16_t>(*a, ids, as_stream(stream));
-#endif
-    if (rc == OMLM_OK && a->advance_pos) return omlm_decode_advance(a->advance_pos, a->advance_step, stream);    // first-generation kernels: own launch
-    return rc;
+    return decode_run<h16_t>(plan, *a, ids, stream);
 }
 
 }   // namespace OMLM_NS

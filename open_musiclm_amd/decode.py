@@ -21,6 +21,7 @@ and the logits are the same bit for bit.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 from typing import List, Optional, Sequence
 
 import torch
@@ -96,9 +97,8 @@ class DecodeArgs(C.Structure):
 
 
 MAX_DECODE_HEADS = 16              # omlm_decode_step: H <= 16
-DEC4_NB = 16                       # decode.hip: samples of a group of the matrix-core step kernels (one MFMA column tile)
-DEC4_GMAX = 4                      # decode.hip: groups of DEC4_NB samples one call carries through every launch
-_LDS_BYTES = 150 * 1024            # omlm_decode_step: B * Fp * 4 + 1024 bytes of LDS for the first-generation step kernels (B <= 8)
+DEC4_NB = 16                       # decode_plan.h: samples of a group of the matrix-core step kernels (one MFMA column tile)
+DEC4_GMAX = 4                      # decode_plan.h: groups of DEC4_NB samples one call carries through every launch
 
 
 def _geometry(model):
@@ -107,43 +107,61 @@ def _geometry(model):
     return tr.dim, tr.heads, engine.ceil_to(inner, 64)
 
 
+def step_route(B: int, D: int, H: int, Fp: int, w16: bool, wide: bool = False) -> Optional[str]:
+    """The one mirror of csrc/decode_plan.h (tests/test_decode_plan_host.py pins it to the plan over a grid): the route omlm_decode_step takes
+    for B samples with every scratch pointer given, as CachedDecoder gives them -- "gen1" (first-generation kernels), or at dim 1024 "dec3"
+    (row kernels, B = 1), "dec4" (matrix cores: 16-bit weights, B >= 2, Fp <= 3072 a multiple of 32) or "dec2" (vector kernels); None where
+    no call holds B samples: more than 16 on the matrix cores (wide: 64), more than 8 elsewhere, or B * Fp floats past the 150 KiB the
+    kernels of at most 8 samples stage in LDS.  (The heads limit is MAX_DECODE_HEADS, see supports.)"""
+    gen2 = D == 1024 and H * 64 <= 1024 and Fp <= 4096 and Fp % 2 == 0 and (H * 64 + 128) % 4 == 0
+    mc = bool(w16) and gen2 and B >= 2 and 0 < Fp <= 3072 and Fp % 32 == 0
+    limit = (DEC4_GMAX * DEC4_NB if wide else DEC4_NB) if mc else min(MAX_DECODE_BATCH, (150 * 1024 - 1024) // (4 * max(Fp, 1)))
+    if not 1 <= B <= limit:
+        return None
+    return "gen1" if not gen2 else "dec3" if B == 1 else "dec4" if mc else "dec2"
+
+
 def _second_generation(D: int, H: int, Fp: int) -> bool:
-    """omlm_decode_step's v2_ok: the dec2 / dec3 / dec4 step kernels serve dim 1024 only; everything else runs on the first-generation kernels."""
-    return D == 1024 and H * 64 <= 1024 and Fp <= 4096
+    """The dec2 / dec3 / dec4 step kernels (dim 1024) rather than the first-generation ones: what step_route says of a one-sample call."""
+    return step_route(1, D, H, Fp, True) == "dec3"
 
 
 def _matrix_core(B: int, D: int, H: int, Fp: int) -> bool:
-    """decode.hip dec4_ok (16-bit weights, the LayerNorm partials and the split-K scratch always given): the matrix-core step kernels."""
-    return 2 <= B <= DEC4_GMAX * DEC4_NB and D % 32 == 0 and D <= 1024 and H * 64 <= 1024 and Fp % 32 == 0 and Fp <= 3072
+    """The matrix-core step kernels serve B samples (16-bit weights, every scratch pointer given): step_route's "dec4"."""
+    return step_route(B, D, H, Fp, True, wide=True) == "dec4"
+
+
+@functools.lru_cache(maxsize=None)
+def step_max_batch(D: int, H: int, Fp: int, w16: bool, wide: bool = False) -> int:
+    """The most samples step_route serves."""
+    return max((B for B in range(1, DEC4_GMAX * DEC4_NB + 1) if step_route(B, D, H, Fp, w16, wide)), default=0)
+
+
+def step_lo_planes_ok(B: int, D: int, H: int, Fp: int) -> bool:
+    """Whether omlm_decode_step takes the lo planes of FF-in / FF-out / head for B samples (16-bit weights): everywhere on the first
+    generation; at dim 1024 on the row kernels with Fp <= 3072 and on the matrix cores."""
+    route = step_route(B, D, H, Fp, True, wide=True)
+    if route is None:                                          # no call holds B samples: only the first generation's answer ignores the batch
+        return step_route(1, D, H, Fp, True) == "gen1"
+    return route in ("gen1", "dec4") or (route == "dec3" and Fp <= 3072)
 
 
 def lo_planes_ok(model, batch: int) -> bool:
-    """"fp16ff": whether omlm_decode_step takes the lo planes of FF-in / FF-out / head at this geometry (its own checks: on the second-generation
-    kernels Fp <= 3072, and at B >= 2 the matrix-core kernels), and the batched forward keeps h1's lo plane for the prefill (Fp <= 4096).
-    Elsewhere the steps run on the fp16 kernels with the hi planes, as "fp16" does."""
-    D, H, Fp = _geometry(model)
-    if not engine.ff_planes_ok(Fp):
-        return False
-    if not _second_generation(D, H, Fp):
-        return True
-    return Fp <= 3072 and (batch == 1 or _matrix_core(batch, D, H, Fp))
+    """"fp16ff": whether omlm_decode_step takes the lo planes of FF-in / FF-out / head at this geometry (step_lo_planes_ok), and the batched
+    forward keeps h1's lo plane for the prefill (Fp <= 4096).  Elsewhere the steps run on the fp16 kernels with the hi planes, as "fp16" does."""
+    return engine.ff_planes_ok(_geometry(model)[2]) and step_lo_planes_ok(batch, *_geometry(model))
 
 
 def max_batch(model, precision: str) -> int:
     """Samples one decode call holds: 16 where the matrix-core kernels serve the model (16-bit weights, dim 1024, at most 16 heads,
     feed-forward width <= 3072); otherwise 8, or fewer where B * Fp floats exceed the first-generation kernels' LDS."""
-    D, H, Fp = _geometry(model)
-    wide = (precision in ("bf16", "fp16", "fp16ff") and _second_generation(D, H, Fp) and 0 < Fp and _matrix_core(2, D, H, Fp))
-    if wide:
-        return DEC4_NB
-    return max(0, min(MAX_DECODE_BATCH, (_LDS_BYTES - 1024) // (4 * max(Fp, 1))))
+    return step_max_batch(*_geometry(model), precision in ("bf16", "fp16", "fp16ff"))
 
 
 def max_call_batch(model, precision: str) -> int:
     """Samples one WIDE decode call holds (CachedDecoder(..., wide=True)): 64 -- four groups of 16 carried through one launch of every step
     kernel -- where max_batch is 16 (the matrix-core kernels serve the model); max_batch everywhere else."""
-    mb = max_batch(model, precision)
-    return DEC4_GMAX * DEC4_NB if mb == DEC4_NB else mb
+    return step_max_batch(*_geometry(model), precision in ("bf16", "fp16", "fp16ff"), wide=True)
 
 
 def scratch_sizes(batch: int, D: int, Fp: int) -> dict:

@@ -103,16 +103,16 @@ def _assert_route(case):
     key, precision, B, wide, route = CASES[case]
     model = _MODELS[(key, precision)][0]
     D, H, Fp = decode._geometry(model)
-    gen2, mc = decode._second_generation(D, H, Fp), decode._matrix_core(B, D, H, Fp)
+    assert decode.step_route(B, D, H, Fp, True, wide) == route          # (every precision of CASES has 16-bit weights)
     if route == "gen1":
-        assert not gen2 and D != 1024
+        assert D != 1024
     elif route == "dec3":
-        assert gen2 and B == 1
+        assert D == 1024 and B == 1
     elif route == "dec4":
-        assert gen2 and B >= 2 and mc
+        assert D == 1024 and B >= 2
         assert (B > decode.DEC4_NB) == wide
     else:
-        assert route == "dec2" and gen2 and B >= 2 and not mc and D == 1024 and Fp > 3072
+        assert route == "dec2" and B >= 2 and D == 1024 and Fp > 3072
 
 
 @pytest.mark.parametrize("case", list(CASES))

@@ -309,3 +309,41 @@ def test_decode_supports_mirrors_the_library(dev, gid, precision):
             lg = dec.step(flat[:, DEC_N0].contiguous(), DEC_N0)
             torch.cuda.synchronize(dev)
         assert bool(torch.isfinite(lg[:, :d["V1"]]).all()), (B, mb)
+
+
+# ---- (e) a refused step launches nothing ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("row_id,emb,ln", [("refused/late: lo planes B=2 L=0 no ln_parts, emb_table", True, False),
+                                           ("refused/lo planes head without partials L=0", False, True)])
+def test_refused_step_leaves_x_untouched(dev, row_id, emb, ln):
+    """(e) omlm_decode_step at D = 1024, B = 2, L = 0, H = 2, Fp = 64, V1 = 17 with head_W and all three lo-plane pointers.  With an embedding
+    table and no ln_parts the lo planes are refused (B >= 2 needs the matrix-core kernels' partials) -- by the commit the route table was
+    recorded from only AFTER the embedding gather had overwritten x; with ln_parts and no table the head misses its LayerNorm partials.
+    Both are argument refusals with that commit's return code and message (tests/decode_routes.json), and x still holds its sentinel."""
+    import ctypes as C
+    import json
+    import os
+    from open_musiclm_amd import decode, hip
+    table = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "decode_routes.json")))
+    row = next(r for r in table["rows"] if r["id"] == row_id)
+    B, D, H, Fp, V1 = 2, 1024, 2, 64, 17
+    assert (row["B"], row["D"], row["L"], row["H"], row["Fp"], row["V1"], row["emb"], row["ln"], row["lo"]) == (B, D, 0, H, Fp, V1, emb, ln, "all")
+    z = lambda *s, t=torch.float32: torch.zeros(*s, dtype=t, device=dev)
+    x = torch.full((B, D), 7.25, device=dev)
+    t = dict(pos_dev=z(1, t=torch.int32), parts=z(B, 1, H, 66), head_W=z(V1, D, t=torch.float16), head_W_lo=z(V1, D, t=torch.float16),
+             emb=z(32, D), logits=z(B, 24), ids=z(B, t=torch.int64), x1=z(B, D), q=z(B, H * 64), u=z(B, Fp), adv=z(1, t=torch.int32),
+             ln=z(decode.scratch_sizes(B, D, Fp)["ln_parts"]), lo=z(8, t=torch.float16))
+    planes = (C.c_void_p * 1)(t["lo"].data_ptr())              # L = 0: no layer reads its planes
+    a = decode.DecodeArgs()
+    a.B, a.D, a.H, a.L, a.F, a.Fp, a.Nmax, a.nsplit, a.w_dtype, a.round_bf16 = B, D, H, 0, Fp, Fp, 64, 1, 2, 1
+    a.eps, a.scale, a.V1, a.ldV, a.emb_rows = 1e-5, 8.0, V1, 24, 32
+    a.pos_dev, a.parts, a.head_W, a.head_W_lo, a.logits = (t[n].data_ptr() for n in ("pos_dev", "parts", "head_W", "head_W_lo", "logits"))
+    a.x, a.x1, a.q, a.u, a.advance_pos = x.data_ptr(), t["x1"].data_ptr(), t["q"].data_ptr(), t["u"].data_ptr(), t["adv"].data_ptr()
+    a.W1p_lo = a.W2p_lo = C.cast(planes, C.POINTER(C.c_void_p))
+    a.emb_table = t["emb"].data_ptr() if emb else None
+    a.ln_parts = t["ln"].data_ptr() if ln else None
+    torch.cuda.synchronize(dev)
+    rc = hip.lib().omlm_decode_step(C.addressof(a), t["ids"].data_ptr(), hip.stream_ptr())
+    msg = hip.lib().omlm_last_error().decode()
+    torch.cuda.synchronize(dev)
+    assert (rc, msg) == (row["refused"]["rc"], row["refused"]["message"])
+    assert bool((x == 7.25).all()) and int(t["adv"].item()) == 0 and not bool(t["logits"].any())
