@@ -265,6 +265,21 @@ int omlm_adamw_clip_step(float* p, float* g, float* m, float* v, void* p16, long
    ls_state (optional, precision "fp16"): 5 floats on the device {loss scale, good steps since its last change, skipped steps, applied
    steps, scale of the last finished step}: gradients are divided by ls_state[0] and the bias corrections use step = ls_state[3] + 1
    instead of `step`; omlm_loss_scale_update copies ls_state[0] to ls_state[4] before it halves / doubles the scale. */
+/* The same step with an exponential moving average of the weights riding along (no reference counterpart; off unless this entry is
+   called).  e: flat fp32 like p, read and written in the same pass.  After an APPLIED step with clock t has produced the new p':
+       n    = t - ema_update_after_step
+       d(t) = 0                                       if n <= 0        (the EMA follows the weights)
+            = min(ema_decay, (1 + n) / (10 + n))      if ema_warmup
+            = ema_decay                               otherwise
+       e'   = p' + d * (e - p')                       in fp32; d = 0 gives e' = p' bit for bit
+   t counts from 1: `step`, or ls_state[3] + 1 where ls_state is given -- the clock of the bias corrections.  d is formed in double and
+   rounded to float once per launch (per workgroup under ls_state).  A skipped step (non-finite *gnorm_sq) leaves e untouched bit for bit,
+   like p, m, v.  ema_decay outside [0, 1) (NaN included) or ema_update_after_step < 0 is refused before any device work.  p, g, m, v,
+   p16 come out bit-equal to omlm_adamw_clip_step's.  No 16-bit shadow of e is kept. */
+int omlm_adamw_clip_step_ema(float* p, float* g, float* m, float* v, void* p16, long long n,
+                             float lr, float beta1, float beta2, float eps, float wd, int step,
+                             float gscale, const float* gnorm_sq, float max_norm, int decoupled, int zero_grad, int p16_dtype,
+                             const float* ls_state, float* e, float ema_decay, int ema_update_after_step, int ema_warmup, void* stream);
 /* after the last parameter group of a step: non-finite *gnorm_sq -> scale = max(scale * backoff, scale_min), skipped += 1; else applied += 1
    and after `interval` consecutive good steps scale = min(scale * growth, scale_max).  (No reference counterpart: the reference trains in
    fp32, trainer.py:444-447; this is torch.cuda.amp.GradScaler's rule kept on the device so that the captured step never reads the norm.) */

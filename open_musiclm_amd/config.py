@@ -137,6 +137,10 @@ class SingleStageTrainerConfig:
     save_predicted_tokens: bool
     save_reconstructed_wave: bool
     use_preprocessed_data: bool
+    # weight EMA in the fused optimizer step (ema.py; no reference counterpart): off unless ema_decay is set
+    ema_decay: Optional[float] = None
+    ema_update_after_step: int = 0
+    ema_warmup: bool = True
 
 
 @dataclass

@@ -46,27 +46,41 @@ extern "C" int omlm_sumsq_accumulate(const float* g, long long n, float* out, fl
 // decoupled != 0 -> AdamW (p *= 1 - lr*wd); else Adam with L2 folded into the gradient (wd is 0 on the reference's Adam path).
 // p16 (optional) receives the 16-bit copy of the updated parameters (p16_dtype: 1 = bf16, 2 = fp16: the GEMM operand type of the
 // model's precision mode); zero_grad != 0 clears g in the same pass.  gscale also carries 1 / loss-scale in fp16 mode.
-template <typename T16>
+// EMA (omlm_adamw_clip_step_ema): e, flat fp32 like p, takes e' = p' + d (e - p') from the updated p' in the same trip -- the rule of
+// include/omlm.h.  The EMA arguments sit behind the others, so the EMA = false form reads the kernel arguments it always read.
+
+// d(t) of the EMA rule (include/omlm.h) for the clock t, formed in double and rounded once
+__host__ __device__ inline float ema_decay_at(double t, float decay, int update_after_step, int warmup) {
+    const double nn = t - (double)update_after_step;
+    if (nn <= 0.0) return 0.f;
+    const double w = (1.0 + nn) / (10.0 + nn);
+    return (float)((warmup && w < (double)decay) ? w : (double)decay);
+}
+
+template <typename T16, bool EMA>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, T16* __restrict__ p16, long long n,
                                                     float lr, float beta1, float beta2, float eps, float wd,
                                                     float bc1, float bc2_sqrt, float gscale, const float* __restrict__ gnorm_sq,
-                                                    float max_norm, int decoupled, int zero_grad, const float* __restrict__ ls_state) {
+                                                    float max_norm, int decoupled, int zero_grad, const float* __restrict__ ls_state,
+                                                    float* __restrict__ e, float ema_d, float ema_decay, int ema_after, int ema_warmup) {
     // ls_state (precision "fp16", optional): {loss scale, good steps since its last change, skipped steps, applied steps, the scale the
     // LAST step's gradients carried (written by omlm_loss_scale_update before it moves the scale)}, all on the device: the backward multiplied the loss gradient by ls_state[0] (engine.LossFunction), this kernel divides it out, and the bias
     // corrections count APPLIED steps (ls_state[3] + 1), so a skipped step leaves the Adam clock where it was.
     if (ls_state) {
         gscale /= ls_state[0];
         // the bias corrections of the APPLIED-step clock: formed once per workgroup (two double-precision pow per THREAD before round 5)
-        __shared__ float sbc[2];
+        __shared__ float sbc[EMA ? 3 : 2];
         if (threadIdx.x == 0) {
             const double t = (double)ls_state[3] + 1.0;
             sbc[0] = (float)(1.0 - pow((double)beta1, t));
             sbc[1] = (float)sqrt(1.0 - pow((double)beta2, t));
+            if constexpr (EMA) sbc[2] = ema_decay_at(t, ema_decay, ema_after, ema_warmup);      // the EMA runs on the same clock
         }
         __syncthreads();
         bc1 = sbc[0];
         bc2_sqrt = sbc[1];
+        if constexpr (EMA) ema_d = sbc[2];
     }
     float clip = 1.0f;
     if (gnorm_sq && max_norm > 0.f) {
@@ -79,16 +93,23 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     const bool skip = gnorm_sq && !(gnorm_sq[0] < 3.0e38f);
     const float gs = gscale * clip;
     const float step = lr / bc1;
-    // one element: the update of AdamW / Adam exactly as written above (the vector path below runs the same expression per lane element)
+    // one element: the update of AdamW / Adam exactly as written above (the vector path below runs the same expression per lane element).
+    // Which products fuse into their sums is spelled out -- the fusions the compiler had chosen for the free form, so this is the code it
+    // always was -- because the EMA form must give the same bits: left free, the two instantiations contracted differently.
     auto upd = [&](float& pi, float gi, float& mi, float& vi) {
+#pragma clang fp contract(off)
         gi *= gs;
-        if (decoupled) pi *= (1.0f - lr * wd); else gi += wd * pi;
-        mi = beta1 * mi + (1.0f - beta1) * gi;
-        vi = beta2 * vi + (1.0f - beta2) * gi * gi;
+        if (decoupled) pi *= fmaf(-lr, wd, 1.0f); else gi = fmaf(wd, pi, gi);
+        mi = fmaf(beta1, mi, (1.0f - beta1) * gi);
+        vi = fmaf(beta2, vi, (1.0f - beta2) * gi * gi);
         pi -= step * mi / (sqrtf(vi) / bc2_sqrt + eps);
     };
+    // the blend against the updated parameter; two roundings (the subtract, the fused multiply-add); d == 0 hands p' on as it
+    // is (p' + 0 * (e - p') would turn a p' of -0 into +0)
+    auto blend = [&](float ei, float pi) { return ema_d == 0.f ? pi : fmaf(ema_d, ei - pi, pi); };
     // 16-byte pieces (round 6: dword loads / stores moved 34 B per parameter at 4.9 TB/s; four parameters per lane per trip), scalar tail
-    const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0) && (!p16 || ((uintptr_t)p16 & 7) == 0);
+    const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (EMA ? (uintptr_t)e : 0)) & 15) == 0) &&
+                     (!p16 || ((uintptr_t)p16 & 7) == 0);
     const long long n4 = vec ? n >> 2 : 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         if (skip) { if (zero_grad) ((float4*)g)[i] = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
@@ -96,6 +117,11 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
         const float4 g4 = ((const float4*)g)[i];
         upd(p4.x, g4.x, m4.x, v4.x); upd(p4.y, g4.y, m4.y, v4.y); upd(p4.z, g4.z, m4.z, v4.z); upd(p4.w, g4.w, m4.w, v4.w);
         ((float4*)p)[i] = p4; ((float4*)m)[i] = m4; ((float4*)v)[i] = v4;
+        if constexpr (EMA) {
+            float4 e4 = ((const float4*)e)[i];
+            e4.x = blend(e4.x, p4.x); e4.y = blend(e4.y, p4.y); e4.z = blend(e4.z, p4.z); e4.w = blend(e4.w, p4.w);
+            ((float4*)e)[i] = e4;
+        }
         if (p16) {
             union { T16 h[4]; uint2 u; } pk;
             pk.h[0] = (T16)p4.x; pk.h[1] = (T16)p4.y; pk.h[2] = (T16)p4.z; pk.h[3] = (T16)p4.w;
@@ -108,27 +134,52 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
         float pi = p[i], mi = m[i], vi = v[i];
         upd(pi, g[i], mi, vi);
         p[i] = pi; m[i] = mi; v[i] = vi;
+        if constexpr (EMA) e[i] = blend(e[i], pi);
         if (p16) p16[i] = (T16)pi;
         if (zero_grad) g[i] = 0.f;
     }
+}
+
+// one launcher behind both entries: e == nullptr is the step without the EMA
+static int adamw_launch(const char* who, float* p, float* g, float* m, float* v, void* p16, long long n,
+                        float lr, float beta1, float beta2, float eps, float wd, int step,
+                        float gscale, const float* gnorm_sq, float max_norm, int decoupled, int zero_grad,
+                        int p16_dtype, const float* ls_state, float* e, float ema_decay, int ema_after, int ema_warmup, void* stream) {
+    if (n <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(p && g && m && v && step >= 1, "adamw arguments");
+    OMLM_CHECK_ARG(!p16 || p16_dtype == OMLM_DT_BF16 || p16_dtype == OMLM_DT_F16, "p16_dtype: 1 = bf16, 2 = fp16");
+    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2 = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    const float ema_d = e ? ema_decay_at((double)step, ema_decay, ema_after, ema_warmup) : 0.f;
+    long long blocks = (n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+    with_flags(e != nullptr, p16 && p16_dtype == OMLM_DT_F16, [&](auto ema, auto half) {
+        using T = std::conditional_t<decltype(half)::value, f16_t, h16_t>;
+        hipLaunchKernelGGL((adamw_kernel<T, decltype(ema)::value>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), p, g, m, v,
+                           (T*)p16, n, lr, beta1, beta2, eps, wd, bc1, bc2, gscale, gnorm_sq, max_norm, decoupled, zero_grad, ls_state,
+                           e, ema_d, ema_decay, ema_after, ema_warmup);
+    });
+    return omlm_post_launch(who);
 }
 
 extern "C" int omlm_adamw_clip_step(float* p, float* g, float* m, float* v, void* p16, long long n,
                                     float lr, float beta1, float beta2, float eps, float wd, int step,
                                     float gscale, const float* gnorm_sq, float max_norm, int decoupled, int zero_grad,
                                     int p16_dtype, const float* ls_state, void* stream) {
+    return adamw_launch("omlm_adamw_clip_step", p, g, m, v, p16, n, lr, beta1, beta2, eps, wd, step, gscale, gnorm_sq, max_norm,
+                        decoupled, zero_grad, p16_dtype, ls_state, nullptr, 0.f, 0, 0, stream);
+}
+
+// the same step with the weight EMA e riding along (the rule: include/omlm.h); refusals come before any device work
+extern "C" int omlm_adamw_clip_step_ema(float* p, float* g, float* m, float* v, void* p16, long long n,
+                                        float lr, float beta1, float beta2, float eps, float wd, int step,
+                                        float gscale, const float* gnorm_sq, float max_norm, int decoupled, int zero_grad,
+                                        int p16_dtype, const float* ls_state, float* e, float ema_decay, int ema_update_after_step,
+                                        int ema_warmup, void* stream) {
+    OMLM_CHECK_ARG(ema_decay >= 0.f && ema_decay < 1.f, "ema_decay must lie in [0, 1)");
+    OMLM_CHECK_ARG(ema_update_after_step >= 0, "ema_update_after_step must be >= 0");
     if (n <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(p && g && m && v && step >= 1, "adamw arguments");
-    OMLM_CHECK_ARG(!p16 || p16_dtype == OMLM_DT_BF16 || p16_dtype == OMLM_DT_F16, "p16_dtype: 1 = bf16, 2 = fp16");
-    const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2 = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-    long long blocks = (n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-    if (p16 && p16_dtype == OMLM_DT_F16)
-        hipLaunchKernelGGL(adamw_kernel<f16_t>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), p, g, m, v, (f16_t*)p16, n,
-                           lr, beta1, beta2, eps, wd, bc1, bc2, gscale, gnorm_sq, max_norm, decoupled, zero_grad, ls_state);
-    else
-        hipLaunchKernelGGL(adamw_kernel<h16_t>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), p, g, m, v, (h16_t*)p16, n,
-                           lr, beta1, beta2, eps, wd, bc1, bc2, gscale, gnorm_sq, max_norm, decoupled, zero_grad, ls_state);
-    return omlm_post_launch("omlm_adamw_clip_step");
+    OMLM_CHECK_ARG(e != nullptr, "adamw_ema: null e");
+    return adamw_launch("omlm_adamw_clip_step_ema", p, g, m, v, p16, n, lr, beta1, beta2, eps, wd, step, gscale, gnorm_sq, max_norm,
+                        decoupled, zero_grad, p16_dtype, ls_state, e, ema_decay, ema_update_after_step, ema_warmup, stream);
 }
 
 // Dynamic loss scale of precision "fp16", entirely on the device (no host read of the norm): after the parameter groups of a step,

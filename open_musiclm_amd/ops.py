@@ -12,6 +12,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import hip
+from .ema import check_ema_settings
 from .hip import call, ptr, stream_ptr
 
 F32, BF16, F16 = 0, 1, 2
@@ -648,12 +649,20 @@ def sumsq_accumulate(g, out, partials=None):
 
 
 def adamw_clip_step(p, g, m, v, p16, *, lr, beta1, beta2, eps, wd, step, gscale, gnorm_sq, max_norm,
-                    decoupled, zero_grad, ls_state=None):
+                    decoupled, zero_grad, ls_state=None, ema=None, ema_decay=None, ema_update_after_step=0, ema_warmup=True):
     """p16: optional 16-bit shadow of p (bf16 or fp16: the operand type of the model's precision), written by the same kernel.
-    ls_state: the device-side loss-scale block of precision "fp16" (engine.loss_scale_state)."""
-    call("omlm_adamw_clip_step", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), p.numel(), float(lr), float(beta1),
-         float(beta2), float(eps), float(wd), int(step), float(gscale), ptr(gnorm_sq), float(max_norm or 0.0),
-         int(decoupled), int(zero_grad), dcode(p16.dtype) if p16 is not None else BF16, ptr(ls_state), stream_ptr())
+    ls_state: the device-side loss-scale block of precision "fp16" (engine.loss_scale_state).
+    ema: optional flat fp32 buffer like p that the same launch moves by the EMA rule of include/omlm.h (ema.ema_decay_at); None is the
+    call this function always made."""
+    args = (ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), p.numel(), float(lr), float(beta1),
+            float(beta2), float(eps), float(wd), int(step), float(gscale), ptr(gnorm_sq), float(max_norm or 0.0),
+            int(decoupled), int(zero_grad), dcode(p16.dtype) if p16 is not None else BF16, ptr(ls_state))
+    if ema is None:
+        call("omlm_adamw_clip_step", *args, stream_ptr())
+        return
+    decay, after, warmup = check_ema_settings(ema_decay, ema_update_after_step, ema_warmup)       # refusals by name, before any device work
+    assert ema.dtype == torch.float32 and ema.numel() == p.numel() and ema.device == p.device
+    call("omlm_adamw_clip_step_ema", *args, ptr(ema), decay, after, int(warmup), stream_ptr())
 
 
 def loss_scale_update(ls_state, gnorm_sq, *, growth=2.0, backoff=0.5, interval=2000, scale_min=1.0, scale_max=65536.0):

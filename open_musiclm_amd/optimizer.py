@@ -18,6 +18,7 @@ import torch
 from torch.optim import lr_scheduler
 
 from . import ops
+from .ema import bind_twin, check_ema_settings
 
 
 def separate_weight_decayable_params(params):
@@ -28,7 +29,13 @@ def separate_weight_decayable_params(params):
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, param_groups, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, decoupled=True):
+    def __init__(self, param_groups, lr=1e-4, betas=(0.9, 0.99), eps=1e-8, weight_decay=0.0, decoupled=True,
+                 ema_decay=None, ema_update_after_step=0, ema_warmup=True):
+        """ema_decay (None: off): keep an exponential moving average of the weights in a flat fp32 buffer E, moved by the SAME kernel
+        that updates the weights (the rule: include/omlm.h, ema.ema_decay_at) -- on applied steps only, on the Adam clock."""
+        self._ema = None if ema_decay is None else check_ema_settings(ema_decay, ema_update_after_step, ema_warmup)
+        self._ema_twins = []            # (weakref(twin), weakref(model)) of every ema.EmaTwin on this optimizer
+        self._ema_missing_told = False
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled=decoupled,
                         amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None)
         super().__init__(param_groups, defaults)
@@ -67,6 +74,12 @@ class FusedAdam(torch.optim.Optimizer):
                 V[o:o + n].copy_(old['V'][old['offs'][i]: old['offs'][i] + n])
             p.data = P[o:o + n].view(p.shape)
             p.grad = G[o:o + n].view(p.shape)
+        E = None
+        if self._ema is not None:                       # the weight EMA: starts as the weights, carried across a re-flatten like M and V
+            E = P.clone()
+            if old is not None:
+                for i, (o, n) in enumerate(zip(offs, sizes)):
+                    E[o:o + n].copy_(old['E'][old['offs'][i]: old['offs'][i] + n])
         # 16-bit shadow of every parameter in the operand type of the model's precision (bf16; fp16 for precision "fp16" -- the
         # model tags its parameters, engine.tag_parameters), refreshed by the SAME kernel that updates the fp32 master (adamw p16
         # output): the engine's 16-bit GEMM operands are views of it, so the per-step weight-cast launches disappear.
@@ -85,6 +98,8 @@ class FusedAdam(torch.optim.Optimizer):
             p._omlm_bf16 = P16[o:o + n].view(p.shape)
             p._omlm_bf16_version = p._version
         self._flat = dict(P=P, G=G, M=M, V=V, P16=P16, offs=offs, sizes=sizes, total=tot)
+        if E is not None:
+            self._flat['E'] = E
         self._gnorm_sq = torch.zeros(1, device=dev)
         self._gnorm_partials = torch.empty(2048, device=dev)      # fixed-order grad-norm reduction: replicas clip identically
         # group ranges (groups are contiguous in the flat order by construction)
@@ -97,6 +112,12 @@ class FusedAdam(torch.optim.Optimizer):
                 r.append((offs[k], offs[k + n - 1] + (sizes[k + n - 1] + 7) // 8 * 8))
             k += n
         self._flat['ranges'] = r
+        for tw, mod in self._live_twins():              # their parameters are views of E: follow the new buffer
+            bind_twin(tw, mod, self)
+
+    def _live_twins(self):
+        live = [(t(), m()) for t, m in self._ema_twins]
+        return [(t, m) for t, m in live if t is not None and m is not None]
 
     def _ensure_flat(self):
         if self._flat is None:
@@ -118,6 +139,25 @@ class FusedAdam(torch.optim.Optimizer):
     def flat_param(self) -> torch.Tensor:
         self._ensure_flat()
         return self._flat['P']
+
+    @property
+    def ema_enabled(self) -> bool:
+        return self._ema is not None
+
+    @property
+    def ema_settings(self) -> Optional[dict]:
+        """{'decay', 'update_after_step', 'warmup'}, or None with the EMA off."""
+        if self._ema is None:
+            return None
+        return dict(decay=self._ema[0], update_after_step=self._ema[1], warmup=self._ema[2])
+
+    @property
+    def ema_flat(self) -> torch.Tensor:
+        """The flat fp32 EMA buffer (same offsets as flat_param); read-only for callers, like flat_param."""
+        if self._ema is None:
+            raise ValueError("FusedAdam keeps no EMA: pass ema_decay")
+        self._ensure_flat()
+        return self._flat['E']
 
     # ---- torch.optim API -------------------------------------------------------------------------------
     def zero_grad(self, set_to_none: bool = False):
@@ -144,13 +184,19 @@ class FusedAdam(torch.optim.Optimizer):
             ops.sumsq_accumulate(f['G'], self._gnorm_sq, self._gnorm_partials)
             gn = self._gnorm_sq
         self._last_gnorm_sq_raw = gn
+        ema_kw = {}
+        if self._ema is not None:
+            ema_kw = dict(ema_decay=self._ema[0], ema_update_after_step=self._ema[1], ema_warmup=self._ema[2])
         for g, (a, b) in zip(self.param_groups, f['ranges']):
             if b <= a:
                 continue
             beta1, beta2 = g['betas']
+            if ema_kw:
+                ema_kw['ema'] = f['E'][a:b]
             ops.adamw_clip_step(f['P'][a:b], f['G'][a:b], f['M'][a:b], f['V'][a:b], f['P16'][a:b], lr=g['lr'], beta1=beta1,
                                 beta2=beta2, eps=g['eps'], wd=g['weight_decay'], step=self._t, gscale=grad_scale,
-                                gnorm_sq=gn, max_norm=max_grad_norm or 0.0, decoupled=g['decoupled'], zero_grad=True, ls_state=ls)
+                                gnorm_sq=gn, max_norm=max_grad_norm or 0.0, decoupled=g['decoupled'], zero_grad=True, ls_state=ls,
+                                **ema_kw)
         if ls is not None:
             dyn = os.environ.get("OMLM_FP16_DYNAMIC", "1") != "0"
             ops.loss_scale_update(ls, gn, growth=2.0 if dyn else 1.0, backoff=0.5 if dyn else 1.0,
@@ -165,7 +211,17 @@ class FusedAdam(torch.optim.Optimizer):
             torch._foreach_add_(params, 0.0)
         for p in params:
             p._omlm_bf16_version = p._version           # the shadow written by this very kernel is current
+        self._bump_twins()
         return None
+
+    def _bump_twins(self):
+        """E changed under the twins' parameters through raw pointers: their version counters key engine.prepared_weights' cache."""
+        for tw, _ in self._live_twins():
+            tp = list(tw.parameters())
+            if hasattr(torch._C, "_increment_version"):
+                torch._C._increment_version(tp)
+            else:
+                torch._foreach_add_(tp, 0.0)
 
     def mark_grads_dirty(self):
         self._grads_clean = False
@@ -200,12 +256,13 @@ class FusedAdam(torch.optim.Optimizer):
     def sync_replicas(self, dp, src: int = 0):
         """Make every data-parallel replica start from rank `src`'s state (what DDP's constructor broadcast does in the
         reference, trainer.py:286-304 via accelerator.prepare): ONE broadcast each of the flat parameter buffer and the two
-        Adam moment buffers, then the bf16 operand shadow is refreshed from the received masters."""
+        Adam moment buffers, then the bf16 operand shadow is refreshed from the received masters.  The weight EMA, where kept, goes
+        along: the replicas' E stay identical by themselves (P does), the broadcast serves a resume on rank `src`."""
         self._ensure_flat()
         if not dp.is_distributed:
             return
         f = self._flat
-        for name in ('P', 'M', 'V'):
+        for name in ('P', 'M', 'V') + (('E',) if self._ema is not None else ()):
             dp.broadcast_(f[name], src=src)
         t = torch.tensor([self._t], device=f['P'].device, dtype=torch.int64)
         dp.broadcast_(t, src=src)
@@ -220,6 +277,7 @@ class FusedAdam(torch.optim.Optimizer):
             torch._foreach_add_(params, 0.0)
         for p in params:
             p._omlm_bf16_version = p._version
+        self._bump_twins()
 
     def state_dict(self):
         """torch.optim.Adam(W)-shaped state_dict so checkpoints interoperate with the reference's trainer."""
@@ -242,6 +300,9 @@ class FusedAdam(torch.optim.Optimizer):
         out = dict(state=state if t_now > 0 else {}, param_groups=groups)
         if self._ls_state is not None:                  # extra top-level key (torch's Optimizer.load_state_dict ignores it)
             out["omlm_loss_scale"] = self.loss_scale_report()
+        if self._ema is not None:                       # likewise ignored by torch: the settings and E per parameter, in the index order of `state`
+            out["omlm_ema"] = dict(self.ema_settings, params=[f['E'][o:o + n].view(p.shape).clone()
+                                                               for p, o, n in zip(self._all_params(), f['offs'], f['sizes'])])
         return out
 
     def load_state_dict(self, sd):
@@ -267,6 +328,17 @@ class FusedAdam(torch.optim.Optimizer):
             if rep:
                 self._ls_state[0] = float(rep.get("scale", self._ls_state[0].item()))
                 self._ls_state[2] = float(rep.get("skipped_steps", 0))
+        if self._ema is not None:                       # (the key is ignored with the EMA off)
+            saved = sd.get("omlm_ema")
+            if saved is None:
+                f['E'].copy_(f['P'])
+                if not self._ema_missing_told:
+                    print("FusedAdam: the optimizer state carries no weight EMA (omlm_ema): the EMA restarts from the current weights")
+                    self._ema_missing_told = True
+            else:
+                for e, o, n in zip(saved["params"], f['offs'], f['sizes']):
+                    f['E'][o:o + n].copy_(e.reshape(-1).to(f['E'].device))
+            self._bump_twins()
 
 
 def get_optimizer(params: Iterable[torch.Tensor], lr=1e-4, wd=1e-2, betas=(0.9, 0.99), eps=1e-8,
@@ -275,14 +347,15 @@ def get_optimizer(params: Iterable[torch.Tensor], lr=1e-4, wd=1e-2, betas=(0.9, 
     params = list(params)
     if filter_by_requires_grad:
         params = [p for p in params if p.requires_grad]
+    ema = {k: kwargs[k] for k in ('ema_decay', 'ema_update_after_step', 'ema_warmup') if k in kwargs}      # the rest of **kwargs is ignored
     if wd == 0:
-        return FusedAdam([{'params': params}], lr=lr, betas=betas, eps=eps, weight_decay=0.0, decoupled=False)
+        return FusedAdam([{'params': params}], lr=lr, betas=betas, eps=eps, weight_decay=0.0, decoupled=False, **ema)
     if group_wd_params:
         wd_params, no_wd_params = separate_weight_decayable_params(params)
         groups = [{'params': wd_params}, {'params': no_wd_params, 'weight_decay': 0}]
     else:
         groups = [{'params': params}]
-    return FusedAdam(groups, lr=lr, betas=betas, eps=eps, weight_decay=wd, decoupled=True)
+    return FusedAdam(groups, lr=lr, betas=betas, eps=eps, weight_decay=wd, decoupled=True, **ema)
 
 
 def get_linear_scheduler(optimizer, total_iters=10000, start_factor=1e-7):

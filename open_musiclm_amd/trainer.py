@@ -110,7 +110,11 @@ class SingleStageTrainer(nn.Module):
                  save_results_every=100, save_predicted_tokens=True, save_reconstructed_wave=True,
                  save_model_every=1000, results_folder='./results', accelerate_kwargs: dict = {},
                  config_paths: Optional[List[str]] = None, dataset_yields_tokens: Optional[bool] = None,
-                 use_hip_graph: Optional[bool] = None):
+                 use_hip_graph: Optional[bool] = None, ema_decay: Optional[float] = None, ema_update_after_step: int = 0,
+                 ema_warmup: bool = True):
+        """ema_decay (None: off; no reference counterpart): the fused optimizer step keeps an exponential moving average of the weights
+        (ema.py); ``ema_transformer`` is a read-only twin on it, ``generate(use_ema=True)`` / ``validate(steps, use_ema=True)`` run on
+        it, and checkpoints carry it ({stage}.transformer_ema.{steps}.pt beside the model; the optimizer file alone resumes it)."""
         super().__init__()
         # accelerate_kwargs is accepted for script compatibility: log_with / logging_dir select the JSONL tracker
         self.dp = DataParallel(device=transformer.device)
@@ -137,30 +141,29 @@ class SingleStageTrainer(nn.Module):
 
         if stage == 'semantic':
             assert tokens_in or (exists(audio_conditioner) and exists(wav2vec))
-            self.train_wrapper = SemanticStage(semantic_transformer=transformer, wav2vec=wav2vec, clap=audio_conditioner,
-                                               cross_entropy_loss_weights=default(cross_entropy_loss_weights, [0., 1.]))
             token_fields, wave_fields = ('clap_token_ids', 'semantic_token_ids'), ('raw_wave_for_clap', 'raw_wave_for_semantic')
         elif stage == 'coarse':
             assert tokens_in or (exists(wav2vec) and exists(audio_conditioner) and exists(neural_codec))
-            self.train_wrapper = CoarseStage(coarse_transformer=transformer, neural_codec=neural_codec, wav2vec=wav2vec,
-                                             clap=audio_conditioner,
-                                             cross_entropy_loss_weights=default(cross_entropy_loss_weights, [0., 0., 1.]))
             token_fields = ('clap_token_ids', 'semantic_token_ids', 'coarse_token_ids')
             wave_fields = ('raw_wave_for_clap', 'raw_wave_for_semantic', 'raw_wave_for_acoustic')
         elif stage == 'fine':
             assert tokens_in or (exists(audio_conditioner) and exists(neural_codec))
-            self.train_wrapper = FineStage(fine_transformer=transformer, clap=audio_conditioner, neural_codec=neural_codec,
-                                           cross_entropy_loss_weights=default(cross_entropy_loss_weights, [0., 0., 1.]))
             token_fields = ('clap_token_ids', 'coarse_token_ids', 'fine_token_ids')
             wave_fields = ('raw_wave_for_clap', 'raw_wave_for_acoustic')
         else:
             raise ValueError(f'invalid stage: {stage}')
+        self.cross_entropy_loss_weights = cross_entropy_loss_weights
+        self.train_wrapper = self._make_stage(transformer)
         self.ds_fields = token_fields if tokens_in else wave_fields
 
         self.register_buffer('steps', torch.Tensor([0]))
         self.num_train_steps, self.batch_size, self.grad_accum_every = num_train_steps, batch_size, grad_accum_every
 
-        self.optim = get_optimizer(transformer.parameters(), lr=lr, wd=wd)
+        ema_kw = {} if ema_decay is None else dict(ema_decay=ema_decay, ema_update_after_step=ema_update_after_step, ema_warmup=ema_warmup)
+        self.optim = get_optimizer(transformer.parameters(), lr=lr, wd=wd, **ema_kw)
+        # the twin and its stage wrapper live in __dict__, NOT among the registered submodules: parameters(), .to() and state_dict() of
+        # the trainer must not reach them (the twin's parameters are views of the optimizer's EMA buffer)
+        self.__dict__['_ema_twin'] = self.__dict__['_ema_wrapper'] = None
         self.scheduler = get_linear_scheduler(self.optim, total_iters=lr_warmup) if lr_warmup > 0 else None
         self.max_grad_norm = max_grad_norm
 
@@ -234,19 +237,40 @@ class SingleStageTrainer(nn.Module):
         self.use_hip_graph = tokens_in if use_hip_graph is None else use_hip_graph
         self._graphed = None
 
+    def _make_stage(self, transformer):
+        """The stage wrapper of this trainer around `transformer`: the model (train_wrapper) or its EMA twin."""
+        w = self.cross_entropy_loss_weights
+        if self.stage == 'semantic':
+            return SemanticStage(semantic_transformer=transformer, wav2vec=self.wav2vec, clap=self.audio_conditioner,
+                                 cross_entropy_loss_weights=default(w, [0., 1.]))
+        if self.stage == 'coarse':
+            return CoarseStage(coarse_transformer=transformer, neural_codec=self.neural_codec, wav2vec=self.wav2vec,
+                               clap=self.audio_conditioner, cross_entropy_loss_weights=default(w, [0., 0., 1.]))
+        return FineStage(fine_transformer=transformer, clap=self.audio_conditioner, neural_codec=self.neural_codec,
+                         cross_entropy_loss_weights=default(w, [0., 0., 1.]))
+
     # ---- checkpointing (trainer.py:359-391) ----------------------------------------------------------
-    def save(self, model_path, optim_path, scheduler_path=None):
+    def save(self, model_path, optim_path, scheduler_path=None, ema_path=None):
+        """ema_path: the EMA twin's plain state_dict (the model's keys), for inference scripts; the optimizer file alone resumes the EMA."""
         torch.save({k: v.detach().cpu() for k, v in self.transformer.state_dict().items()}, model_path)
         torch.save(self.optim.state_dict(), optim_path)
         if exists(self.scheduler):
             assert exists(scheduler_path)
             torch.save(self.scheduler.state_dict(), scheduler_path)
+        if exists(ema_path):
+            torch.save({k: v.detach().cpu() for k, v in self._require_ema().state_dict().items()}, ema_path)
 
-    def load(self, model_path, optim_path, scheduler_path=None, steps=0):
+    def load(self, model_path, optim_path, scheduler_path=None, steps=0, ema_path=None):
+        """ema_path: overwrite the EMA the optimizer file restored with a twin state_dict.  Nothing of the EMA clock is reset: it is the
+        Adam clock, which the optimizer file restores."""
         model_path, optim_path = Path(model_path), Path(optim_path)
         assert model_path.exists() and optim_path.exists()
         self.transformer.load_state_dict(torch.load(model_path, map_location=self.device))
         self.optim.load_state_dict(torch.load(optim_path, map_location=self.device, weights_only=False))
+        if exists(ema_path):
+            assert Path(ema_path).exists()
+            self._require_ema().load_state_dict(torch.load(ema_path, map_location=self.device))      # in place: into the views of E
+            self.optim._bump_twins()
         if exists(self.scheduler):
             assert exists(scheduler_path), 'the config specifies lr warmup is used, but no scheduler checkpoint is given. try setting lr_warmup to 0.'
             scheduler_path = Path(scheduler_path)
@@ -266,8 +290,27 @@ class SingleStageTrainer(nn.Module):
     def print(self, msg):
         self.dp.print(msg)
 
-    def generate(self, *args, **kwargs):
-        """The wrapper's generate, every keyword passed on: with ``return_logprobs=True`` it returns (ids, LogProbs)."""
+    @property
+    def ema_transformer(self) -> Optional[TokenConditionedTransformer]:
+        """The read-only twin on the optimizer's weight EMA (ema.EmaTwin), or None with the EMA off.  Built on first use, once the model
+        is on the device (the optimizer's flat buffers exist only there)."""
+        if self._ema_twin is None and self.optim.ema_enabled and self.device.type == 'cuda':
+            from .ema import EmaTwin
+            self.__dict__['_ema_twin'] = EmaTwin(self.transformer, self.optim)
+            self.__dict__['_ema_wrapper'] = self._make_stage(self._ema_twin).eval()
+        return self._ema_twin
+
+    def _require_ema(self):
+        if self.ema_transformer is None:
+            raise ValueError("this trainer keeps no weight EMA: construct it with ema_decay")
+        return self.ema_transformer
+
+    def generate(self, *args, use_ema=False, **kwargs):
+        """The wrapper's generate, every keyword passed on: with ``return_logprobs=True`` it returns (ids, LogProbs).
+        use_ema: sample from the weight EMA (the twin) instead of the training weights."""
+        if use_ema:
+            self._require_ema()
+            return self._ema_wrapper.generate(*args, **kwargs)
         return self.train_wrapper.generate(*args, **kwargs)
 
     @property
@@ -390,18 +433,24 @@ class SingleStageTrainer(nn.Module):
             self.print(f'{steps}: saving model to {str(self.results_folder)}')
             self.save(str(self.results_folder / f'{self.stage}.transformer.{steps}.pt'),
                       str(self.results_folder / f'{self.stage}.optimizer.{steps}.pt'),
-                      str(self.results_folder / f'{self.stage}.scheduler.{steps}.pt'))
+                      str(self.results_folder / f'{self.stage}.scheduler.{steps}.pt'),
+                      **({} if self.ema_transformer is None else
+                         dict(ema_path=str(self.results_folder / f'{self.stage}.transformer_ema.{steps}.pt'))))
             if exists(self.audio_conditioner) and getattr(self.audio_conditioner, 'learn_rvq', False):
                 torch.save(self.audio_conditioner.rq.state_dict(), str(self.results_folder / f'{self.stage}.conditioner_rvq.{steps}.pt'))
         self.steps += 1
         return logs
 
     @torch.no_grad()
-    def validate(self, steps):
-        """trainer.py:457-526: teacher-forced validation loss / token accuracy, token dumps, optional wave reconstruction."""
-        self.train_wrapper.eval()
+    def validate(self, steps, use_ema=False):
+        """trainer.py:457-526: teacher-forced validation loss / token accuracy, token dumps, optional wave reconstruction.
+        use_ema: on the weight EMA (the twin) instead of the training weights."""
+        if use_ema:
+            self._require_ema()
+        wrapper = self._ema_wrapper if use_ema else self.train_wrapper
+        wrapper.eval()
         data_kwargs = self._next_batch(self.valid_dl_iter)
-        valid_loss, all_logits, all_labels = self.train_wrapper(**data_kwargs, return_loss=True)
+        valid_loss, all_logits, all_labels = wrapper(**data_kwargs, return_loss=True)
         valid_loss = float(self.dp.reduce_mean(valid_loss.detach().reshape(1)).item())
         pred = self.dp.all_gather_cat(all_logits[-1].argmax(1).contiguous()).cpu().long()
         gt = self.dp.all_gather_cat(all_labels[-1].contiguous()).cpu().long()
