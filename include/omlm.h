@@ -66,6 +66,23 @@ int omlm_layernorm_fwd(const float* x, const float* gamma, void* y, void* xcast,
  * at pitch ldy (precision "fp16ff": the FF-in omlm_gemm_planes16 reads both, the backward reads y) */
 int omlm_layernorm_fwd_planes(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd,
                               int M, int D, int ldy, float eps, int out_dtype, void* stream);
+/* Row segments (the `_seg` entries here and of the ConvFeedForward forward below).  A segment (n_full, p0, n_live = n_full - p0) names the rows
+ * [p0, n_full) of every sample of a [B * n_full, ..] buffer, held compact as [B * n_live, ..]: compact row r is full row
+ * (r / n_live) * n_full + p0 + r % n_live.  The last layer's feed-forward block runs on such a segment when the heads read only a tail of
+ * every sample (engine.live_rows).  n_full == 0: no segment, the plain entry.
+ * omlm_layernorm_fwd*_seg: x [B * n_full, D] is read at the segment's rows; y, the statistics and every other output are compact ([M, ..],
+ *   M = B * n_live) and bit-equal to the plain entry run on a gathered copy of x; xc (optional, [M, D] fp32) receives the gathered rows of x
+ *   themselves in the same pass.  16-bit outputs, statistics required, no xcast.
+ * omlm_layernorm_bwd2_seg: dy, x, the statistics and dres are compact; dx / dxcast are FULL-size ([B * n_full, D]): the segment's rows receive
+ *   what the plain entry computes from the compact inputs (dgamma likewise), every row in front of the segment is written as zeros by the same
+ *   launch.  16-bit dy and cast type, no dres2. */
+int omlm_layernorm_fwd_seg(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd, float* xc,
+                           int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream);
+int omlm_layernorm_fwd_planes_seg(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd, float* xc,
+                                  int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream);
+int omlm_layernorm_bwd2_seg(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                            const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D,
+                            float dx_scale, int cast_dtype, int dy_dtype, int n_full, int p0, int n_live, void* stream);
 long long omlm_layernorm_bwd_workspace_bytes(int D);
 /* dy_dtype: 0 fp32, 1 bf16 / 2 fp16 (GEMM epilogue output).  dres2 [M, D] (optional): a second residual-gradient term in the type
  * cast_dtype names (dxcast may be null): the K/V projection's input gradient reaches the attention LayerNorm's backward as a 16-bit GEMM
@@ -210,6 +227,18 @@ int omlm_ffmid_fwd(const void* h1, const void* convw, const void* gamma, void* h
 int omlm_ffmid_fwd_planes(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
                           void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp, float eps, float p,
                           unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, void* stream);
+/* The forwards on a row segment (see omlm_layernorm_fwd_seg): every buffer holds the rows [p0, n_full) of each sample compact, nseq = n_full - p0,
+ * and the strip kernels draw the keep bits those rows have in a launch over the full buffer -- drop_bits row r equals the full launch's row of
+ * the same token, and h2 / gh / the statistics are bit-equal from the third row of every sample on (the first two see a zero conv window in
+ * place of rows p0 - 2, p0 - 1).  The backward needs no segment: it reads the keep bits (omlm_ffmid_bwd on the compact buffers, nseq = n_live).
+ * Where the wave-per-row kernels serve the call the mask is a function of the compact row instead. */
+int omlm_ffmid_fwd_seg(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
+                       int M, int nseq, int F, int Fp, float eps, float p, unsigned long long seed,
+                       const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, int n_full, int p0, void* stream);
+int omlm_ffmid_fwd_planes_seg(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
+                              void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp, float eps, float p,
+                              unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype,
+                              int n_full, int p0, void* stream);
 long long omlm_ffmid_bwd_workspace_bytes(int F, int Fp);
 int omlm_ffmid_bwd(const void* dh2, const void* h1, const void* convw, const void* gamma, const float* mean,
                    const float* rstd, void* du_tmp, void* dh1, float* dgamma, float* dconv, float* workspace,
@@ -345,6 +374,13 @@ int omlm_layernorm_fwd_mx(const float* x, const float* gamma, void* y, void* y8,
 int omlm_ffmid_fwd_mx(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
                       void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
                       float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, void* stream);
+/* the same two on a row segment (omlm_layernorm_fwd_seg / omlm_ffmid_fwd_seg) */
+int omlm_layernorm_fwd_mx_seg(const float* x, const float* gamma, void* y, void* y8, long long y8_stride, unsigned char* scale8,
+                              float* mean, float* rstd, float* xc, int M, int D, int ldy, float eps, int n_full, int p0, int n_live, void* stream);
+int omlm_ffmid_fwd_mx_seg(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
+                          void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
+                          float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh,
+                          int n_full, int p0, void* stream);
 typedef struct omlm_quant_rows_desc { const float* src; unsigned char* dst8; long long lo_stride; unsigned char* scale8; int R, C, ld_src, ld8; } omlm_quant_rows_desc;
 int omlm_quant_rows_mx(const omlm_quant_rows_desc* problems, int count, void* stream);
 /* All weight-gradient contractions of a backward pass in one launch (autograd of nn.Linear, transformer.py:203-212,144,149:

@@ -595,7 +595,7 @@ extern "C" int omlm_colsum_accumulate(const float* part, float* out, int P, int 
 bool ffmid2_supported(int Fp);
 int ffmid2_fwd_launch(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd, int M, int nseq,
                       int F, int Fp, float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
-                      unsigned char* drop_bits, void* gh, int dtype, hipStream_t st);
+                      unsigned char* drop_bits, void* gh, int dtype, hipStream_t st, int seg_n_full, int seg_p0);
 int ffmid2_bwd_launch(const void* dh2, const void* h1, const void* convw, const void* gamma, const float* rstd, float* bc,
                       void* dh1, float* part_g, int max_g_rows, float* part_c, int max_c_rows, int* g_rows, int* c_rows,
                       int M, int nseq, int F, int Fp, float p, const unsigned char* drop_bits, const void* gh, int dtype, hipStream_t st);
@@ -624,27 +624,33 @@ extern "C" long long omlm_ffmid_bwd_workspace_bytes(int F, int Fp) {
 #endif
 
 // dtype: 0 = fp32 operands ("bf16x3"), 1 = bf16, 2 = fp16 (forwarded to the fp16 copy of this file)
+// Every forward entry exists in a `_seg` form that carries a row segment (n_full, p0; n_full == 0: none): the buffers hold rows [p0, n_full)
+// of every sample compact (nseq = n_full - p0), and the strip kernels draw the keep bits those rows have in a launch over the full buffer
+// (a compact launch then drops exactly what the full launch drops for the same tokens).  The plain entries are the `_seg` ones without a segment.
+#define FF_CHECK_SEG(n_full, p0, nseq) OMLM_CHECK_ARG((n_full) == 0 || ((p0) > 0 && (p0) + (nseq) == (n_full)), "row segment: nseq must be n_full - p0, p0 > 0")
 #if !OMLM_FP16
-extern "C" int omlm_ffmid_fwd_h(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
-                                int M, int nseq, int F, int Fp, float eps, float p, unsigned long long seed,
-                                const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, void* stream);
+extern "C" int omlm_ffmid_fwd_seg_h(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
+                                    int M, int nseq, int F, int Fp, float eps, float p, unsigned long long seed,
+                                    const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, int n_full, int p0, void* stream);
 #endif
-extern "C" int OMLM_API(omlm_ffmid_fwd)(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
+extern "C" int OMLM_API(omlm_ffmid_fwd_seg)(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
                               int M, int nseq, int F, int Fp, float eps, float p, unsigned long long seed,
-                              const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, void* stream) {
+                              const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, int n_full, int p0, void* stream) {
 #if !OMLM_FP16
-    if (dtype == OMLM_DT_F16) return omlm_ffmid_fwd_h(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, 1, stream);
+    if (dtype == OMLM_DT_F16) return omlm_ffmid_fwd_seg_h(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, 1, n_full, p0, stream);
 #else
     OMLM_CHECK_ARG(dtype == 1, "the fp16 copy serves fp16 operands only");
 #endif
     if (M <= 0) return OMLM_OK;
+    FF_CHECK_SEG(n_full, p0, nseq);
     OMLM_CHECK_ARG(h1 && convw && gamma && h2 && mean && rstd, "null pointer");
     OMLM_CHECK_ARG(Fp % 8 == 0 && Fp >= F && Fp <= 8192 && (size_t)5 * Fp * sizeof(float) <= 160 * 1024, "Fp must be F rounded up to 8 and <= 8192");
     OMLM_CHECK_ARG(nseq > 0 && M % nseq == 0, "M must be batch * nseq");
     OMLM_CHECK_ARG(p >= 0.f && p < 1.f, "dropout p");
     hipStream_t st = as_stream(stream);
     if (ffmid_impl() == 1 && ffmid2_supported(Fp) && (p == 0.f || drop_bits))
-        return ffmid2_fwd_launch(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, dtype, st);
+        return ffmid2_fwd_launch(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, dtype, st, n_full, p0);
+    // (the wave-per-row kernels below know no segment: their mask is a function of the compact row -- still one mask for forward and backward)
     const int rows4 = (M + 3) / 4;
     dim3 grid(rows4 < 4096 ? rows4 : 4096), block(FF_THREADS);
     const size_t lds_fwd = (size_t)4 * Fp * sizeof(float);
@@ -665,28 +671,39 @@ extern "C" int OMLM_API(omlm_ffmid_fwd)(const void* h1, const void* convw, const
     FF_FWD_DISPATCH(h16_t);
     return omlm_post_launch("omlm_ffmid_fwd");
 }
+#if !OMLM_FP16
+extern "C" int omlm_ffmid_fwd(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
+                              int M, int nseq, int F, int Fp, float eps, float p, unsigned long long seed,
+                              const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, void* stream) {
+    return omlm_ffmid_fwd_seg(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, dtype, 0, 0, stream);
+}
+#endif
 
 // The same forward on hi/lo planes of the 16-bit type `dtype` (1 = bf16, 2 = fp16; precision "fp16ff"): h1, the conv taps and gamma are read
 // as hi + lo (each *_lo plane has its hi plane's layout), h2 leaves as planes h2 = rne16(y), h2_lo = rne16(y - h2); gh, the statistics and
 // the keep bits as in omlm_ffmid_fwd.  The strip kernels only (Fp <= 4096, drop_bits present when p > 0).
 int ffmid2_fwd_planes_launch(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
                              void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp, float eps, float p,
-                             unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st);
+                             unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st,
+                             int seg_n_full, int seg_p0);
 #if !OMLM_FP16
-extern "C" int omlm_ffmid_fwd_planes_h(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
-                                       void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp, float eps, float p,
-                                       unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, void* stream);
+extern "C" int omlm_ffmid_fwd_planes_seg_h(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
+                                           void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp, float eps, float p,
+                                           unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype,
+                                           int n_full, int p0, void* stream);
 #endif
-extern "C" int OMLM_API(omlm_ffmid_fwd_planes)(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma,
+extern "C" int OMLM_API(omlm_ffmid_fwd_planes_seg)(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma,
                                                const void* gamma_lo, void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp,
                                                float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
-                                               unsigned char* drop_bits, void* gh, int dtype, void* stream) {
+                                               unsigned char* drop_bits, void* gh, int dtype, int n_full, int p0, void* stream) {
 #if !OMLM_FP16
     if (dtype == OMLM_DT_F16)
-        return omlm_ffmid_fwd_planes_h(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, 1, stream);
+        return omlm_ffmid_fwd_planes_seg_h(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, 1,
+                                           n_full, p0, stream);
 #endif
     OMLM_CHECK_ARG(dtype == 1, "ffmid_fwd_planes: dtype 1 (bf16) or 2 (fp16)");
     if (M <= 0) return OMLM_OK;
+    FF_CHECK_SEG(n_full, p0, nseq);
     OMLM_CHECK_ARG(h1 && h1_lo && convw && convw_lo && gamma && gamma_lo && h2 && h2_lo && mean && rstd, "null pointer");
     OMLM_CHECK_ARG(Fp % 8 == 0 && Fp >= F && ffmid2_supported(Fp), "ffmid_fwd_planes: Fp must be F rounded up to 8 and <= 4096");
     OMLM_CHECK_ARG(nseq > 0 && M % nseq == 0, "M must be batch * nseq");
@@ -694,22 +711,33 @@ extern "C" int OMLM_API(omlm_ffmid_fwd_planes)(const void* h1, const void* h1_lo
     OMLM_CHECK_ARG((((uintptr_t)h1 | (uintptr_t)h1_lo | (uintptr_t)convw | (uintptr_t)convw_lo | (uintptr_t)gamma | (uintptr_t)gamma_lo |
                      (uintptr_t)h2 | (uintptr_t)h2_lo) % 16) == 0, "ffmid_fwd_planes: 16-byte aligned planes");
     return ffmid2_fwd_planes_launch(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev,
-                                    drop_bits, gh, as_stream(stream));
+                                    drop_bits, gh, as_stream(stream), n_full, p0);
 }
+#if !OMLM_FP16
+extern "C" int omlm_ffmid_fwd_planes(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma,
+                                     const void* gamma_lo, void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp,
+                                     float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
+                                     unsigned char* drop_bits, void* gh, int dtype, void* stream) {
+    return omlm_ffmid_fwd_planes_seg(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh,
+                                     dtype, 0, 0, stream);
+}
+#endif
 
 #if OMLM_FP16
 // The plane forward with h2 leaving in omlm_gemm_mx16's operand form (round 6): the half hi plane h2 [M, Fp], fp8 planes [hi8 | lo8] at row pitch
 // 2 Fp bytes (the lo8 plane h2_8_stride bytes behind the hi8 plane) and one E8M0 scale byte per row; everything else as omlm_ffmid_fwd_planes.
 int ffmid2_fwd_mx_launch(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
                          void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
-                         float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st);
+                         float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st,
+                         int seg_n_full, int seg_p0);
 }   // namespace OMLM_NS
-extern "C" int omlm_ffmid_fwd_mx(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
+extern "C" int omlm_ffmid_fwd_mx_seg(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
                                  void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
                                  float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh,
-                                 void* stream) {
+                                 int n_full, int p0, void* stream) {
     using namespace OMLM_NS;
     if (M <= 0) return OMLM_OK;
+    FF_CHECK_SEG(n_full, p0, nseq);
     OMLM_CHECK_ARG(h1 && h1_lo && convw && convw_lo && gamma && gamma_lo && h2 && h2_8 && scale8 && mean && rstd, "null pointer");
     OMLM_CHECK_ARG(Fp % 8 == 0 && Fp >= F && ffmid2_supported(Fp), "ffmid_fwd_mx: Fp must be F rounded up to 8 and <= 4096");
     OMLM_CHECK_ARG(nseq > 0 && M % nseq == 0, "M must be batch * nseq");
@@ -720,7 +748,14 @@ extern "C" int omlm_ffmid_fwd_mx(const void* h1, const void* h1_lo, const void* 
     OMLM_CHECK_ARG((((uintptr_t)h1 | (uintptr_t)h1_lo | (uintptr_t)convw | (uintptr_t)convw_lo | (uintptr_t)gamma | (uintptr_t)gamma_lo |
                      (uintptr_t)h2 | (uintptr_t)h2_8) % 16) == 0, "ffmid_fwd_mx: 16-byte aligned planes");
     return ffmid2_fwd_mx_launch(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_8, h2_8_stride, scale8, mean, rstd, M, nseq, F, Fp, eps, p, seed,
-                                seed_dev, drop_bits, gh, as_stream(stream));
+                                seed_dev, drop_bits, gh, as_stream(stream), n_full, p0);
+}
+extern "C" int omlm_ffmid_fwd_mx(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
+                                 void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
+                                 float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh,
+                                 void* stream) {
+    return omlm_ffmid_fwd_mx_seg(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_8, h2_8_stride, scale8, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev,
+                                 drop_bits, gh, 0, 0, stream);
 }
 namespace OMLM_NS {
 #endif

@@ -190,13 +190,17 @@ __device__ __forceinline__ void keep_words(unsigned long long seed, unsigned lon
 // must be known before a row is written; a LayerNorm output is bounded whatever its input: |y_i| <= sqrt(F - 1) max|gamma / keep|.  Every row takes
 // that bound (3-4 binades above a typical row's largest entry, of the 17 e4m3 spans: profiles/r06_error_budget_fp8corr.md, "one scale per tensor")
 // -- no per-element max / min in a kernel that is bound by instruction issue (a data-derived row bound measured +54 us per launch).
-template <typename T, int NT, bool TRAIN, bool PL = false, bool MX = false>
-__global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kernel(const T* __restrict__ h1, const T* __restrict__ convw,
+// SEG (a row segment, omlm_ffmid_fwd_seg): the launch covers rows [p0, n_full) of every sample, stored compact (nseq = n_full - p0 rows per
+// sample), and draws the keep bits of the rows they are in the full buffer: only the dropout hash's row index is mapped, once per strip; every
+// address and the row loops are those of a plain launch over nseq rows.  Both kernels below inline this one body.
+struct FfSeg { int n_full, p0; };
+template <typename T, int NT, bool TRAIN, bool PL, bool MX, bool SEG>
+__device__ __forceinline__ void ffmid2_fwd_body(const T* __restrict__ h1, const T* __restrict__ convw,
                                                         const T* __restrict__ gamma, T* __restrict__ h2,
                                                         float* __restrict__ mean, float* __restrict__ rstd,
                                                         int nseq, int F, int Fp, int RB, int strips, float eps, float p,
                                                         unsigned long long seed, const unsigned long long* __restrict__ seed_dev,
-                                                        unsigned char* __restrict__ drop_bits, T* __restrict__ gh_out, const FfPlanes pl) {
+                                                        unsigned char* __restrict__ drop_bits, T* __restrict__ gh_out, const FfPlanes pl, const FfSeg seg) {
     constexpr int NW = NT / 64;
     constexpr int RB_ = (sizeof(T) == 2 && !PL) ? FS_R : (FS_R > 2 ? 2 : FS_R);        // rows per batch: fp32 rows (and hi + lo rows) cost twice the registers
     __shared__ float st[2][FS_R][NW][2];
@@ -213,6 +217,7 @@ __global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kern
     const int col = threadIdx.x * 8;
     const int ld = 2 * Fp;
     const size_t row0 = (size_t)b * nseq;
+    const size_t hrow0 = SEG ? (size_t)b * seg.n_full + seg.p0 : row0;      // row 0 of this sample as the dropout hash counts rows
     const float inv = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
     const unsigned thr = (unsigned)(p * 65536.0f + 0.5f);
 
@@ -342,7 +347,7 @@ __global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kern
             for (int i = 0; i < 4; ++i) y[i] = gh[i] * gm[i];
             if (TRAIN || p > 0.f) {
                 unsigned w[4], bits = 0;
-                keep_words(seed, row * (unsigned long long)(Fp >> 3) + (unsigned)(col >> 3), w);
+                keep_words(seed, (SEG ? hrow0 + tb + r : row) * (unsigned long long)(Fp >> 3) + (unsigned)(col >> 3), w);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const bool k0 = (w[i] & 0xFFFFu) >= thr, k1 = (w[i] >> 16) >= thr;
@@ -387,6 +392,25 @@ __global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kern
     for (; tb + 2 * RB_ <= t1; tb += RB_, ++it) batch(std::true_type{}, tb, it);
 #pragma unroll 1
     for (; tb < t1; tb += RB_, ++it) batch(std::false_type{}, tb, it);
+}
+
+template <typename T, int NT, bool TRAIN, bool PL = false, bool MX = false>
+__global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_kernel(const T* __restrict__ h1, const T* __restrict__ convw,
+                                                        const T* __restrict__ gamma, T* __restrict__ h2,
+                                                        float* __restrict__ mean, float* __restrict__ rstd,
+                                                        int nseq, int F, int Fp, int RB, int strips, float eps, float p,
+                                                        unsigned long long seed, const unsigned long long* __restrict__ seed_dev,
+                                                        unsigned char* __restrict__ drop_bits, T* __restrict__ gh_out, const FfPlanes pl) {
+    ffmid2_fwd_body<T, NT, TRAIN, PL, MX, false>(h1, convw, gamma, h2, mean, rstd, nseq, F, Fp, RB, strips, eps, p, seed, seed_dev, drop_bits, gh_out, pl, FfSeg{0, 0});
+}
+template <typename T, int NT, bool TRAIN, bool PL = false, bool MX = false>
+__global__ __launch_bounds__(NT, (FS_OCC * NT + 255) / 256) void ffmid2_fwd_seg_kernel(const T* __restrict__ h1, const T* __restrict__ convw,
+                                                        const T* __restrict__ gamma, T* __restrict__ h2,
+                                                        float* __restrict__ mean, float* __restrict__ rstd,
+                                                        int nseq, int F, int Fp, int RB, int strips, float eps, float p,
+                                                        unsigned long long seed, const unsigned long long* __restrict__ seed_dev,
+                                                        unsigned char* __restrict__ drop_bits, T* __restrict__ gh_out, const FfPlanes pl, const FfSeg seg) {
+    ffmid2_fwd_body<T, NT, TRAIN, PL, MX, true>(h1, convw, gamma, h2, mean, rstd, nseq, F, Fp, RB, strips, eps, p, seed, seed_dev, drop_bits, gh_out, pl, seg);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -825,15 +849,23 @@ bool ffmid2_supported(int Fp) { return Fp % 8 == 0 && Fp / 8 <= 512; }
 template <typename T, bool PL = false, bool MX = false>
 static int fwd_launch_t(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd, int M, int nseq,
                         int F, int Fp, float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
-                        unsigned char* drop_bits, void* gh, hipStream_t st, const FfPlanes pl = FfPlanes{0, 0, 0, nullptr, nullptr, 0, nullptr, nullptr}) {
+                        unsigned char* drop_bits, void* gh, hipStream_t st, int seg_n_full, int seg_p0,
+                        const FfPlanes pl = FfPlanes{0, 0, 0, nullptr, nullptr, 0, nullptr, nullptr}) {
     const int B = M / nseq;
+    // a segment changes nothing but the keep bits drawn: without dropout the plain kernels serve it
+    const bool segd = seg_n_full > 0 && p > 0.f;
+    const FfSeg seg{seg_n_full, seg_p0};
     const int RB = strip_rows(nseq, 36);
     const int strips = (nseq + RB - 1) / RB;
     const int nt = ((Fp / 8 + 63) / 64) * 64;                                  // kernel instantiation: whole waves
     const int nthr = Fp / 8;                                                   // threads launched: one per chunk
     dim3 grid(B * strips);
     const bool train = p > 0.f && drop_bits != nullptr && gh != nullptr;       // the training call: all three row stores are unconditional
-#define FF2_FWD(NT_) do { if (train) hipLaunchKernelGGL((ffmid2_fwd_kernel<T, NT_, true, PL, MX>), grid, dim3(nthr), 0, st, (const T*)h1, (const T*)convw, \
+#define FF2_FWD(NT_) do { if (segd && train) hipLaunchKernelGGL((ffmid2_fwd_seg_kernel<T, NT_, true, PL, MX>), grid, dim3(nthr), 0, st, (const T*)h1, (const T*)convw, \
+        (const T*)gamma, (T*)h2, mean, rstd, nseq, F, Fp, RB, strips, eps, p, seed, seed_dev, drop_bits, (T*)gh, pl, seg); \
+    else if (segd) hipLaunchKernelGGL((ffmid2_fwd_seg_kernel<T, NT_, false, PL, MX>), grid, dim3(nthr), 0, st, (const T*)h1, (const T*)convw, \
+        (const T*)gamma, (T*)h2, mean, rstd, nseq, F, Fp, RB, strips, eps, p, seed, seed_dev, drop_bits, (T*)gh, pl, seg); \
+    else if (train) hipLaunchKernelGGL((ffmid2_fwd_kernel<T, NT_, true, PL, MX>), grid, dim3(nthr), 0, st, (const T*)h1, (const T*)convw, \
         (const T*)gamma, (T*)h2, mean, rstd, nseq, F, Fp, RB, strips, eps, p, seed, seed_dev, drop_bits, (T*)gh, pl); \
     else hipLaunchKernelGGL((ffmid2_fwd_kernel<T, NT_, false, PL, MX>), grid, dim3(nthr), 0, st, (const T*)h1, (const T*)convw, \
         (const T*)gamma, (T*)h2, mean, rstd, nseq, F, Fp, RB, strips, eps, p, seed, seed_dev, drop_bits, (T*)gh, pl); } while (0)
@@ -854,24 +886,25 @@ static int fwd_launch_t(const void* h1, const void* convw, const void* gamma, vo
 // dtype: 0 = fp32 operands ("bf16x3" mode), 1 = bf16
 int ffmid2_fwd_launch(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd, int M, int nseq,
                       int F, int Fp, float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
-                      unsigned char* drop_bits, void* gh, int dtype, hipStream_t st) {
+                      unsigned char* drop_bits, void* gh, int dtype, hipStream_t st, int seg_n_full, int seg_p0) {
 #if !OMLM_FP16
-    if (dtype == 0) return fwd_launch_t<float>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st);
+    if (dtype == 0) return fwd_launch_t<float>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st, seg_n_full, seg_p0);
 #endif
-    return fwd_launch_t<h16_t>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st);
+    return fwd_launch_t<h16_t>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st, seg_n_full, seg_p0);
 }
 
 // the same forward on hi/lo planes of the 16-bit type (omlm_ffmid_fwd_planes): h1, taps and gamma are read as hi + lo, h2 leaves as planes
 int ffmid2_fwd_planes_launch(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
                              void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp, float eps, float p,
-                             unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st) {
+                             unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st,
+                             int seg_n_full, int seg_p0) {
     FfPlanes pl;
     pl.h1_lo = (const h16_t*)h1_lo - (const h16_t*)h1;
     pl.convw_lo = (const h16_t*)convw_lo - (const h16_t*)convw;
     pl.gamma_lo = (const h16_t*)gamma_lo - (const h16_t*)gamma;
     pl.h2_lo = h2_lo;
     pl.h2_8 = nullptr; pl.h2_8_stride = 0; pl.scale8 = nullptr; pl.h1_8 = nullptr;
-    return fwd_launch_t<h16_t, true>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st, pl);
+    return fwd_launch_t<h16_t, true>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st, seg_n_full, seg_p0, pl);
 }
 
 #if OMLM_FP16
@@ -879,7 +912,8 @@ int ffmid2_fwd_planes_launch(const void* h1, const void* h1_lo, const void* conv
 // h1's lo plane arrives as bf8 bytes (h1_lo8, at h1's element pitch: what omlm_gemm_mx16 writes with c_lo_bf8)
 int ffmid2_fwd_mx_launch(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
                          void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
-                         float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st) {
+                         float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st,
+                         int seg_n_full, int seg_p0) {
     FfPlanes pl;
     pl.h1_lo = 0;
     pl.h1_8 = (const unsigned char*)h1_lo;
@@ -887,7 +921,7 @@ int ffmid2_fwd_mx_launch(const void* h1, const void* h1_lo, const void* convw, c
     pl.gamma_lo = (const h16_t*)gamma_lo - (const h16_t*)gamma;
     pl.h2_lo = nullptr;
     pl.h2_8 = (unsigned char*)h2_8; pl.h2_8_stride = h2_8_stride; pl.scale8 = scale8;
-    return fwd_launch_t<h16_t, true, true>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st, pl);
+    return fwd_launch_t<h16_t, true, true>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st, seg_n_full, seg_p0, pl);
 }
 #endif
 

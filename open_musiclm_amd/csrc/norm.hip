@@ -10,6 +10,36 @@ namespace OMLM_NS {
 #define LN_THREADS 256
 #define LN_MAXV 4   // float4 pieces per thread  -> D <= 4096
 
+// A row segment (the `_seg` entry points): rows [p0, n_full) of every sample of a [B * n_full, D] buffer, held compact as [B * n_live, D]
+// (n_live = n_full - p0): compact row r is full row (r / n_live) * n_full + p0 + r % n_live.  The forward kernels READ x at the mapped rows
+// and write everything compact (xc, optional: the fp32 source rows themselves, compact); the backward kernels read everything compact and
+// WRITE dx / its cast copy at the mapped rows, the rows in front of the segment as zeros.  SEG is a template switch: without a segment the
+// kernels are the ones they were (LnSeg<false> is empty).
+template <bool SEG> struct LnSeg {};
+template <> struct LnSeg<true> { int n_full, p0, n_live; float* xc; };
+__device__ __forceinline__ int seg_row(const LnSeg<false>&, int r) { return r; }
+__device__ __forceinline__ int seg_row(const LnSeg<true>& s, int r) { const int b = r / s.n_live; return b * s.n_full + s.p0 + (r - b * s.n_live); }
+__device__ __forceinline__ void seg_keep4(const LnSeg<false>&, int, int, int, const float4&) {}
+__device__ __forceinline__ void seg_keep4(const LnSeg<true>& s, int row, int D, int c, const float4& v) {
+    if (s.xc) ((float4*)(s.xc + (size_t)row * D))[c] = v;
+}
+// the rows in front of the segment (p0 of each of the M / n_live samples) of dx [.., D] fp32 and its cast copy: zeros, from the workgroups of the launch
+template <typename T>
+__device__ __forceinline__ void seg_zero_dead(const LnSeg<true>& s, int M, int D, float* dx, T* dxcast) {
+    const int ndead = (M / s.n_live) * s.p0, nv = D / 4;
+    for (int d = blockIdx.x; d < ndead; d += gridDim.x) {
+        const int b = d / s.p0;
+        const size_t r = (size_t)b * s.n_full + (d - b * s.p0);
+        for (int c = threadIdx.x; c < nv; c += LN_THREADS) {
+            ((float4*)(dx + r * D))[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (dxcast) store4_from_float(dxcast + r * D + 4 * c, 0.f, 0.f, 0.f, 0.f);
+        }
+    }
+}
+template <typename T> __device__ __forceinline__ void seg_zero_dead(const LnSeg<false>&, int, int, float*, T*) {}
+#define LN_CHECK_SEG(M, n_full, p0, n_live) OMLM_CHECK_ARG((p0) > 0 && (n_live) > 0 && (p0) + (n_live) == (n_full) && (M) % (n_live) == 0, \
+                                                          "row segment: n_full = p0 + n_live, p0 > 0, M a multiple of n_live")
+
 // y = (x - mean) * rstd * gamma ; optionally also emit cast(x) (the K/V projection reads the
 // un-normalised residual: reference transformer.py:228 binds kv_input before the pre-norm :250).
 // four outputs as hi/lo planes of the 16-bit type: y = rne16(v), ylo = rne16(v - y)  (precision "fp16ff": the FF-in GEMM reads both)
@@ -25,21 +55,21 @@ __device__ __forceinline__ void store4_planes(h16_t* y, h16_t* ylo, float a, flo
 __device__ __forceinline__ void store4_planes(float*, float*, float, float, float, float) {}      // (fp32 output has no planes)
 
 // LO: `xcast` is the LO PLANE of y (pitch ldy) instead of a cast copy of x
-template <typename T, bool LO = false>
+template <typename T, bool LO = false, bool SEG = false>
 __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                             T* __restrict__ y, T* __restrict__ xcast,
                                                             float* __restrict__ mean, float* __restrict__ rstd,
-                                                            int M, int D, int ldy, float eps) {
+                                                            int M, int D, int ldy, float eps, const LnSeg<SEG> sg) {
     __shared__ float red[LN_THREADS / 64];
     const int nv = D / 4;
     for (int row = blockIdx.x; row < M; row += gridDim.x) {
-        const float4* xr = (const float4*)(x + (size_t)row * D);
+        const float4* xr = (const float4*)(x + (size_t)seg_row(sg, row) * D);
         float4 v[LN_MAXV];
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < LN_MAXV; ++i) {
             const int c = threadIdx.x + i * LN_THREADS;
-            if (c < nv) { v[i] = xr[c]; s += (v[i].x + v[i].y) + (v[i].z + v[i].w); }
+            if (c < nv) { v[i] = xr[c]; s += (v[i].x + v[i].y) + (v[i].z + v[i].w); seg_keep4(sg, row, D, c, v[i]); }
         }
         const float mu = block_sum<LN_THREADS>(s, red) / (float)D;
         float q = 0.f;
@@ -79,10 +109,11 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_kernel(const float* __restr
 // the two reductions use parity-double-buffered LDS slots (two barriers per row instead of four), and no memory instruction sits under a
 // column test or a thread test (the row's statistics are stored by every thread: same value, same address).  XC: cast copy of x wanted.
 // Same summation order as the general kernel: identical bits.
-template <typename T, bool XC, bool LO = false>
+template <typename T, bool XC, bool LO = false, bool SEG = false>
 __global__ __launch_bounds__(LN_THREADS) void ln_fwd_row1_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                                  T* __restrict__ y, T* __restrict__ xcast,
-                                                                 float* __restrict__ mean, float* __restrict__ rstd, int M, int ldy, float eps) {
+                                                                 float* __restrict__ mean, float* __restrict__ rstd, int M, int ldy, float eps,
+                                                                 const LnSeg<SEG> sg) {
     constexpr int D = 4 * LN_THREADS, NW = LN_THREADS / 64;
     __shared__ float red[2][2][NW];
     const int c = threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, G = gridDim.x;
@@ -107,19 +138,20 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_row1_kernel(const float* __
         if constexpr (LO) store4_planes(y + (size_t)row * ldy + 4 * c, xcast + (size_t)row * ldy + 4 * c, a * rs * g.x, b * rs * g.y, cc * rs * g.z, d * rs * g.w);
         else store4_from_float(y + (size_t)row * ldy + 4 * c, a * rs * g.x, b * rs * g.y, cc * rs * g.z, d * rs * g.w);
         if constexpr (XC) store4_from_float(xcast + (size_t)row * D + 4 * c, v.x, v.y, v.z, v.w);
+        seg_keep4(sg, row, D, c, v);
     };
     int row = blockIdx.x;
     if (row >= M) return;
-    float4 A = ((const float4*)(x + (size_t)row * D))[c], B;
+    float4 A = ((const float4*)(x + (size_t)seg_row(sg, row) * D))[c], B;
 #pragma unroll 1
     for (;;) {
         const int r1 = row + G;
-        B = ((const float4*)(x + (size_t)(r1 < M ? r1 : row) * D))[c];         // past the end: a redundant re-read instead of a conditional request
+        B = ((const float4*)(x + (size_t)seg_row(sg, r1 < M ? r1 : row) * D))[c];         // past the end: a redundant re-read instead of a conditional request
         __builtin_amdgcn_sched_barrier(0);
         process(A, row, 0);
         if (r1 >= M) break;
         const int r2 = r1 + G;
-        A = ((const float4*)(x + (size_t)(r2 < M ? r2 : r1) * D))[c];
+        A = ((const float4*)(x + (size_t)seg_row(sg, r2 < M ? r2 : r1) * D))[c];
         __builtin_amdgcn_sched_barrier(0);
         process(B, r1, 1);
         if (r2 >= M) break;
@@ -146,10 +178,11 @@ __device__ __forceinline__ void store4_mx(h16_t* y, unsigned char* y8h, unsigned
     *(unsigned*)y8l = pack4_fp8((a - ha) * sl, (b - hb) * sl, (c - hc) * sl, (d - hd) * sl);
 }
 
-template <int MAXV>
+template <int MAXV, bool SEG = false>
 __global__ __launch_bounds__(LN_THREADS) void ln_fwd_mx_kernel(const float* __restrict__ x, const float* __restrict__ gamma, h16_t* __restrict__ y,
                                                                unsigned char* __restrict__ y8, long long y8_stride, unsigned char* __restrict__ scale8,
-                                                               float* __restrict__ mean, float* __restrict__ rstd, int M, int D, int ldy, float eps) {
+                                                               float* __restrict__ mean, float* __restrict__ rstd, int M, int D, int ldy, float eps,
+                                                               const LnSeg<SEG> sg) {
     constexpr int NW = LN_THREADS / 64;
     __shared__ float red[2][2][NW];                     // [parity][sum | sum of squares][wave]
     __shared__ float gred[NW];
@@ -172,13 +205,13 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_mx_kernel(const float* __re
     const float sh = ldexpf(1.0f, -e), sl = ldexpf(1.0f, 11 - e);
     int par = 0;
     for (int row = blockIdx.x; row < M; row += gridDim.x, par ^= 1) {
-        const float4* xr = (const float4*)(x + (size_t)row * D);
+        const float4* xr = (const float4*)(x + (size_t)seg_row(sg, row) * D);
         float4 v[MAXV];
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < MAXV; ++i) {
             const int c = threadIdx.x + i * LN_THREADS;
-            if (c < nv) { v[i] = xr[c]; s += (v[i].x + v[i].y) + (v[i].z + v[i].w); }
+            if (c < nv) { v[i] = xr[c]; s += (v[i].x + v[i].y) + (v[i].z + v[i].w); seg_keep4(sg, row, D, c, v[i]); }
         }
         s = wave_sum(s);
         if (lane == 0) red[par][0][wave] = s;
@@ -226,8 +259,9 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_mx_kernel(const float* __re
 using namespace OMLM_NS;
 // y: half hi plane [M, ldy]; y8: fp8 planes [hi8 | lo8] at row pitch 2 ldy bytes, the lo8 plane y8_stride bytes behind the hi8 plane; scale8 [M]
 // E8M0 (include/omlm.h).  The hi plane and the statistics are omlm_layernorm_fwd's (bit for bit at D = 1024).
-extern "C" int omlm_layernorm_fwd_mx(const float* x, const float* gamma, void* y, void* y8, long long y8_stride, unsigned char* scale8,
-                                     float* mean, float* rstd, int M, int D, int ldy, float eps, void* stream) {
+// seg (the `_seg` entry): x is read at the segment's rows, every output is compact ([M, ..]); xc (optional): the fp32 source rows, compact
+static int layernorm_fwd_mx_run(const float* x, const float* gamma, void* y, void* y8, long long y8_stride, unsigned char* scale8,
+                                float* mean, float* rstd, int M, int D, int ldy, float eps, const LnSeg<true>* seg, void* stream) {
     if (M <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(x && gamma && y && y8 && scale8 && mean && rstd, "null pointer");
     OMLM_CHECK_ARG(D % 4 == 0 && D <= 4 * LN_THREADS * LN_MAXV, "D must be a multiple of 4 and <= 4096");
@@ -235,11 +269,22 @@ extern "C" int omlm_layernorm_fwd_mx(const float* x, const float* gamma, void* y
     // the kernel zeroes every fp8 row out to a whole 128-byte k-tile: the row pitch must hold it (else the tail runs into the next row)
     OMLM_CHECK_ARG(2 * ldy >= (D + 127) / 128 * 128, "an fp8 plane row (pitch 2 * ldy bytes) must hold D rounded up to 128 bytes");
     dim3 grid(M < 2048 ? M : 2048), block(LN_THREADS);
-    if (D <= 4 * LN_THREADS)
-        hipLaunchKernelGGL((ln_fwd_mx_kernel<1>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (unsigned char*)y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps);
-    else
-        hipLaunchKernelGGL((ln_fwd_mx_kernel<LN_MAXV>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (unsigned char*)y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps);
+#define LN_MX(MV_) do { if (seg) hipLaunchKernelGGL((ln_fwd_mx_kernel<MV_, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (unsigned char*)y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps, *seg); \
+        else hipLaunchKernelGGL((ln_fwd_mx_kernel<MV_, false>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (unsigned char*)y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps, LnSeg<false>{}); } while (0)
+    if (D <= 4 * LN_THREADS) LN_MX(1); else LN_MX(LN_MAXV);
+#undef LN_MX
     return omlm_post_launch("omlm_layernorm_fwd_mx");
+}
+extern "C" int omlm_layernorm_fwd_mx(const float* x, const float* gamma, void* y, void* y8, long long y8_stride, unsigned char* scale8,
+                                     float* mean, float* rstd, int M, int D, int ldy, float eps, void* stream) {
+    return layernorm_fwd_mx_run(x, gamma, y, y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps, nullptr, stream);
+}
+extern "C" int omlm_layernorm_fwd_mx_seg(const float* x, const float* gamma, void* y, void* y8, long long y8_stride, unsigned char* scale8,
+                                         float* mean, float* rstd, float* xc, int M, int D, int ldy, float eps, int n_full, int p0, int n_live, void* stream) {
+    if (M <= 0) return OMLM_OK;
+    LN_CHECK_SEG(M, n_full, p0, n_live);
+    const LnSeg<true> seg{n_full, p0, n_live, xc};
+    return layernorm_fwd_mx_run(x, gamma, y, y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps, &seg, stream);
 }
 namespace OMLM_NS {
 #endif
@@ -254,14 +299,14 @@ __device__ __forceinline__ float4 load4f(const h16_t* p, int c) {
     const u32x2 w = ((const u32x2*)p)[c];
     return make_float4(h16_lo_to_f(w[0]), h16_hi_to_f(w[0]), h16_lo_to_f(w[1]), h16_hi_to_f(w[1]));
 }
-template <typename T, typename TDY>
+template <typename T, typename TDY, bool SEG = false>
 __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const TDY* __restrict__ dy, const float* __restrict__ x,
                                                             const float* __restrict__ gamma, const float* __restrict__ mean,
                                                             const float* __restrict__ rstd, const float* __restrict__ dres,
                                                             const T* __restrict__ dres2,
                                                             float* __restrict__ dx, T* __restrict__ dxcast,
                                                             float* __restrict__ dgamma, float* __restrict__ part, int M, int D,
-                                                            float dx_scale) {
+                                                            float dx_scale, const LnSeg<SEG> sg) {
     __shared__ float red[LN_THREADS / 64];
     const int nv = D / 4;
     float4 dg[LN_MAXV];
@@ -287,6 +332,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const TDY* __restric
         }
         const float m1 = block_sum<LN_THREADS>(s1, red) / (float)D;
         const float m2 = block_sum<LN_THREADS>(s2, red) / (float)D;
+        const size_t orow = (size_t)seg_row(sg, row);                  // (dx and its cast copy are full-size with a segment)
 #pragma unroll
         for (int i = 0; i < LN_MAXV; ++i) {
             const int c = threadIdx.x + i * LN_THREADS;
@@ -302,14 +348,15 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const TDY* __restric
                     r.x += d1.x; r.y += d1.y; r.z += d1.z; r.w += d1.w;
                 }
                 r.x *= dx_scale; r.y *= dx_scale; r.z *= dx_scale; r.w *= dx_scale;
-                ((float4*)(dx + (size_t)row * D))[c] = r;
+                ((float4*)(dx + orow * D))[c] = r;
                 if (dxcast) {
-                    T* o = dxcast + (size_t)row * D + 4 * c;
+                    T* o = dxcast + orow * D + 4 * c;
                     store4_from_float(o, r.x, r.y, r.z, r.w);
                 }
             }
         }
     }
+    seg_zero_dead(sg, M, D, dx, dxcast);
     if (part) {                         // one partial row per workgroup, reduced by colsum afterwards (no contended atomics)
 #pragma unroll
         for (int i = 0; i < LN_MAXV; ++i) {
@@ -353,12 +400,13 @@ template <> struct Raw4<h16_t> {
 // is a second, shorter path, and hipcc's s_waitcnt count for "this row's pieces have landed" is taken from the shortest one -- with
 // the optional pieces really in flight that count stalls every row on the requests it has just issued (seen in the ISA: vmcnt(2) behind
 // four loads).
-template <typename T, typename TDY, int FL>
+template <typename T, typename TDY, int FL, bool SEG = false>
 __global__ __launch_bounds__(LN_THREADS) void ln_bwd_row1_kernel(const TDY* __restrict__ dy, const float* __restrict__ x,
                                                                  const float* __restrict__ gamma, const float* __restrict__ mean,
                                                                  const float* __restrict__ rstd, const float* __restrict__ dres,
                                                                  const T* __restrict__ dres2, float* __restrict__ dx, T* __restrict__ dxcast,
-                                                                 float* __restrict__ dgamma, float* __restrict__ part, int M, float dx_scale) {
+                                                                 float* __restrict__ dgamma, float* __restrict__ part, int M, float dx_scale,
+                                                                 const LnSeg<SEG> sg) {
     constexpr int D = 4 * LN_THREADS, NW = LN_THREADS / 64;
     __shared__ float red[2][NW][2];
     const int c = threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, G = gridDim.x;
@@ -392,8 +440,9 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_row1_kernel(const TDY* __re
         const float4 d1 = cur.d1.get();
         r.x += d1.x; r.y += d1.y; r.z += d1.z; r.w += d1.w;
         r.x *= dx_scale; r.y *= dx_scale; r.z *= dx_scale; r.w *= dx_scale;
-        ((float4*)(dx + (size_t)row * D))[c] = r;
-        if constexpr (FL & 4) store4_from_float(dxcast + (size_t)row * D + 4 * c, r.x, r.y, r.z, r.w);
+        const size_t orow = (size_t)seg_row(sg, row);              // (dx and its cast copy are full-size with a segment)
+        ((float4*)(dx + orow * D))[c] = r;
+        if constexpr (FL & 4) store4_from_float(dxcast + orow * D + 4 * c, r.x, r.y, r.z, r.w);
     };
     int row = blockIdx.x;
     if (row < M) {
@@ -416,6 +465,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_row1_kernel(const TDY* __re
             row = r2;
         }
     }
+    seg_zero_dead(sg, M, D, dx, (FL & 4) ? dxcast : (T*)nullptr);
     if (part) ((float4*)(part + (size_t)blockIdx.x * D))[c] = dg;
     else if (dgamma) {
         unsafeAtomicAdd(dgamma + 4 * c + 0, dg.x); unsafeAtomicAdd(dgamma + 4 * c + 1, dg.y);
@@ -425,45 +475,64 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_row1_kernel(const TDY* __re
 
 static int ln_grid(int M) { return M < 2048 ? M : 2048; }
 
+// The forward entries in their `_seg` form (include/omlm.h): n_full == 0 is "no segment", which is all the plain entries pass.  With a segment
+// x [.. n_full rows per sample] is read at the segment's rows, every output is compact ([M, ..]) and xc (optional) receives the fp32 source rows.
 #if !OMLM_FP16
-extern "C" int omlm_layernorm_fwd_h(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd, int M, int D, int ldy, float eps, int out_dtype, void* stream);
+extern "C" int omlm_layernorm_fwd_seg_h(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd, float* xc, int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream);
 #endif
-extern "C" int OMLM_API(omlm_layernorm_fwd)(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd,
-                                  int M, int D, int ldy, float eps, int out_dtype, void* stream) {
+extern "C" int OMLM_API(omlm_layernorm_fwd_seg)(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd, float* xc,
+                                  int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream) {
 #if !OMLM_FP16
-    if (out_dtype == OMLM_DT_F16) return omlm_layernorm_fwd_h(x, gamma, y, xcast, mean, rstd, M, D, ldy, eps, 1, stream);
+    if (out_dtype == OMLM_DT_F16) return omlm_layernorm_fwd_seg_h(x, gamma, y, xcast, mean, rstd, xc, M, D, ldy, eps, 1, n_full, p0, n_live, stream);
 #endif
     if (M <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(x && gamma && y, "null pointer");
     OMLM_CHECK_ARG(D % 4 == 0 && D <= 4 * LN_THREADS * LN_MAXV, "D must be a multiple of 4 and <= 4096");
     OMLM_CHECK_ARG(ldy >= D, "ldy < D");
     dim3 grid(ln_grid(M)), block(LN_THREADS);
+    if (n_full != 0) {
+        LN_CHECK_SEG(M, n_full, p0, n_live);
+        OMLM_CHECK_ARG(mean && rstd && !xcast && out_dtype == 1, "layernorm_fwd_seg: statistics wanted, no cast copy of x, 16-bit output");
+        const LnSeg<true> sg{n_full, p0, n_live, xc};
+        if (D == 4 * LN_THREADS)
+            hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, false, false, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)nullptr, mean, rstd, M, ldy, eps, sg);
+        else
+            hipLaunchKernelGGL((ln_fwd_kernel<h16_t, false, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)nullptr, mean, rstd, M, D, ldy, eps, sg);
+        return omlm_post_launch("omlm_layernorm_fwd_seg");
+    }
+    const LnSeg<false> ns{};
     if (D == 4 * LN_THREADS && mean && rstd) {        // the row-pair kernels (next-row prefetch, fewer barriers)
         if (out_dtype == 0) {
-            if (xcast) hipLaunchKernelGGL((ln_fwd_row1_kernel<float, true>), grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, ldy, eps);
-            else       hipLaunchKernelGGL((ln_fwd_row1_kernel<float, false>), grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, ldy, eps);
+            if (xcast) hipLaunchKernelGGL((ln_fwd_row1_kernel<float, true>), grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, ldy, eps, ns);
+            else       hipLaunchKernelGGL((ln_fwd_row1_kernel<float, false>), grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, ldy, eps, ns);
         } else {
-            if (xcast) hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)xcast, mean, rstd, M, ldy, eps);
-            else       hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, false>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)xcast, mean, rstd, M, ldy, eps);
+            if (xcast) hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)xcast, mean, rstd, M, ldy, eps, ns);
+            else       hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, false>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)xcast, mean, rstd, M, ldy, eps, ns);
         }
         return omlm_post_launch("omlm_layernorm_fwd");
     }
     if (out_dtype == 0)
-        hipLaunchKernelGGL(ln_fwd_kernel<float>, grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, D, ldy, eps);
+        hipLaunchKernelGGL(ln_fwd_kernel<float>, grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, D, ldy, eps, ns);
     else
-        hipLaunchKernelGGL(ln_fwd_kernel<h16_t>, grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)xcast, mean, rstd, M, D, ldy, eps);
+        hipLaunchKernelGGL(ln_fwd_kernel<h16_t>, grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)xcast, mean, rstd, M, D, ldy, eps, ns);
     return omlm_post_launch("omlm_layernorm_fwd");
 }
+#if !OMLM_FP16
+extern "C" int omlm_layernorm_fwd(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd,
+                                  int M, int D, int ldy, float eps, int out_dtype, void* stream) {
+    return omlm_layernorm_fwd_seg(x, gamma, y, xcast, mean, rstd, nullptr, M, D, ldy, eps, out_dtype, 0, 0, 0, stream);
+}
+#endif
 
 // The same forward with the result as hi/lo planes of the 16-bit type (1 = bf16, 2 = fp16): y = rne16(v), y_lo = rne16(v - y), both at
 // pitch ldy (precision "fp16ff": the FF-in GEMM of the forward reads both planes, the backward reads y alone).
 #if !OMLM_FP16
-extern "C" int omlm_layernorm_fwd_planes_h(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd, int M, int D, int ldy, float eps, int out_dtype, void* stream);
+extern "C" int omlm_layernorm_fwd_planes_seg_h(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd, float* xc, int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream);
 #endif
-extern "C" int OMLM_API(omlm_layernorm_fwd_planes)(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd,
-                                                   int M, int D, int ldy, float eps, int out_dtype, void* stream) {
+extern "C" int OMLM_API(omlm_layernorm_fwd_planes_seg)(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd, float* xc,
+                                                   int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream) {
 #if !OMLM_FP16
-    if (out_dtype == OMLM_DT_F16) return omlm_layernorm_fwd_planes_h(x, gamma, y, y_lo, mean, rstd, M, D, ldy, eps, 1, stream);
+    if (out_dtype == OMLM_DT_F16) return omlm_layernorm_fwd_planes_seg_h(x, gamma, y, y_lo, mean, rstd, xc, M, D, ldy, eps, 1, n_full, p0, n_live, stream);
 #endif
     if (M <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(out_dtype == 1, "layernorm_fwd_planes: out_dtype 1 (bf16) or 2 (fp16)");
@@ -471,12 +540,27 @@ extern "C" int OMLM_API(omlm_layernorm_fwd_planes)(const float* x, const float* 
     OMLM_CHECK_ARG(D % 4 == 0 && D <= 4 * LN_THREADS * LN_MAXV, "D must be a multiple of 4 and <= 4096");
     OMLM_CHECK_ARG(ldy >= D && ldy % 4 == 0, "ldy < D");
     dim3 grid(ln_grid(M)), block(LN_THREADS);
+    if (n_full != 0) {
+        LN_CHECK_SEG(M, n_full, p0, n_live);
+        const LnSeg<true> sg{n_full, p0, n_live, xc};
+        if (D == 4 * LN_THREADS)
+            hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, false, true, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)y_lo, mean, rstd, M, ldy, eps, sg);
+        else
+            hipLaunchKernelGGL((ln_fwd_kernel<h16_t, true, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)y_lo, mean, rstd, M, D, ldy, eps, sg);
+        return omlm_post_launch("omlm_layernorm_fwd_planes_seg");
+    }
     if (D == 4 * LN_THREADS)
-        hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, false, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)y_lo, mean, rstd, M, ldy, eps);
+        hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, false, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)y_lo, mean, rstd, M, ldy, eps, LnSeg<false>{});
     else
-        hipLaunchKernelGGL((ln_fwd_kernel<h16_t, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)y_lo, mean, rstd, M, D, ldy, eps);
+        hipLaunchKernelGGL((ln_fwd_kernel<h16_t, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)y_lo, mean, rstd, M, D, ldy, eps, LnSeg<false>{});
     return omlm_post_launch("omlm_layernorm_fwd_planes");
 }
+#if !OMLM_FP16
+extern "C" int omlm_layernorm_fwd_planes(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd,
+                                         int M, int D, int ldy, float eps, int out_dtype, void* stream) {
+    return omlm_layernorm_fwd_planes_seg(x, gamma, y, y_lo, mean, rstd, nullptr, M, D, ldy, eps, out_dtype, 0, 0, 0, stream);
+}
+#endif
 
 extern "C" int omlm_colsum_accumulate(const float* part, float* out, int P, int C, int ldp, void* stream);
 #if !OMLM_FP16
@@ -484,14 +568,16 @@ extern "C" long long omlm_layernorm_bwd_workspace_bytes(int D) { return (long lo
 #endif
 
 #if !OMLM_FP16
-extern "C" int omlm_layernorm_bwd2_h(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D, float dx_scale, int cast_dtype, int dy_dtype, void* stream);
+extern "C" int omlm_layernorm_bwd2_seg_h(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D, float dx_scale, int cast_dtype, int dy_dtype, int n_full, int p0, int n_live, void* stream);
 #endif
 // dres2 (optional): a second residual-gradient term [M, D] in the type named by cast_dtype (dxcast itself may be null)
-extern "C" int OMLM_API(omlm_layernorm_bwd2)(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+// segment (n_full != 0; the plain entry passes none): dy, x, the statistics and dres are compact [M, ..]; dx / dxcast are full-size
+// ([M / n_live * n_full, D]), written at the segment's rows, the rows in front of it as zeros by the same launch; no dres2
+extern "C" int OMLM_API(omlm_layernorm_bwd2_seg)(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                                   const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D,
-                                  float dx_scale, int cast_dtype, int dy_dtype, void* stream) {
+                                  float dx_scale, int cast_dtype, int dy_dtype, int n_full, int p0, int n_live, void* stream) {
 #if !OMLM_FP16
-    if (cast_dtype == OMLM_DT_F16 || dy_dtype == OMLM_DT_F16) return omlm_layernorm_bwd2_h(dy, x, gamma, mean, rstd, dres, dres2, dx, dxcast, dgamma, workspace, M, D, dx_scale, OMLM_H_CODE(cast_dtype), OMLM_H_CODE(dy_dtype), stream);
+    if (cast_dtype == OMLM_DT_F16 || dy_dtype == OMLM_DT_F16) return omlm_layernorm_bwd2_seg_h(dy, x, gamma, mean, rstd, dres, dres2, dx, dxcast, dgamma, workspace, M, D, dx_scale, OMLM_H_CODE(cast_dtype), OMLM_H_CODE(dy_dtype), n_full, p0, n_live, stream);
 #endif
     if (M <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(dy && x && gamma && mean && rstd && dx, "null pointer");
@@ -506,10 +592,24 @@ extern "C" int OMLM_API(omlm_layernorm_bwd2)(const void* dy, const float* x, con
     dim3 grid(blocks), block(LN_THREADS);
     float* part = two_level ? workspace : nullptr;
     OMLM_CHECK_ARG(dy_dtype == 0 || dy_dtype == 1, "dy_dtype: 0 = fp32, 1 = bf16, 2 = fp16 (same 16-bit type as the cast output)");
+    const LnSeg<false> ns{};
+    if (n_full != 0) {
+        // the one form the trunk uses: 16-bit dy and cast copy (the type is named by cast_dtype even where dxcast is null)
+        LN_CHECK_SEG(M, n_full, p0, n_live);
+        OMLM_CHECK_ARG(!dres2 && cast_dtype == 1 && dy_dtype == 1, "layernorm_bwd2_seg: 16-bit dy and cast type, no dres2");
+        const LnSeg<true> sg{n_full, p0, n_live, nullptr};
+        if (D == 4 * LN_THREADS) {
+#define LN_ROW1S(F) hipLaunchKernelGGL((ln_bwd_row1_kernel<h16_t, h16_t, F, true>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, \
+                                       (const h16_t*)nullptr, dx, (h16_t*)dxcast, dgamma, part, M, dx_scale, sg)
+            switch ((dres ? 1 : 0) | (dxcast ? 4 : 0)) { case 0: LN_ROW1S(0); break; case 1: LN_ROW1S(1); break; case 4: LN_ROW1S(4); break; default: LN_ROW1S(5); break; }
+#undef LN_ROW1S
+        } else
+            hipLaunchKernelGGL((ln_bwd_kernel<h16_t, h16_t, true>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, (const h16_t*)nullptr, dx, (h16_t*)dxcast, dgamma, part, M, D, dx_scale, sg);
+    } else
     if (D == 4 * LN_THREADS) {                        // ln_bwd_row1_kernel (next-row prefetch, one barrier per row)
         const int fl = (dres ? 1 : 0) | (dres2 ? 2 : 0) | (dxcast ? 4 : 0);
 #define LN_ROW1(TT, TD, F) hipLaunchKernelGGL((ln_bwd_row1_kernel<TT, TD, F>), grid, block, 0, as_stream(stream), (const TD*)dy, x, gamma, mean, rstd, dres, \
-                                              (const TT*)dres2, dx, (TT*)dxcast, dgamma, part, M, dx_scale)
+                                              (const TT*)dres2, dx, (TT*)dxcast, dgamma, part, M, dx_scale, ns)
 #define LN_ROW1_FL(TT, TD) do { switch (fl) { case 0: LN_ROW1(TT, TD, 0); break; case 1: LN_ROW1(TT, TD, 1); break; case 2: LN_ROW1(TT, TD, 2); break; \
         case 3: LN_ROW1(TT, TD, 3); break; case 4: LN_ROW1(TT, TD, 4); break; case 5: LN_ROW1(TT, TD, 5); break; case 6: LN_ROW1(TT, TD, 6); break; \
         default: LN_ROW1(TT, TD, 7); break; } } while (0)
@@ -521,18 +621,25 @@ extern "C" int OMLM_API(omlm_layernorm_bwd2)(const void* dy, const float* x, con
 #undef LN_ROW1
     } else
     if (cast_dtype == 0 && dy_dtype == 0)
-        hipLaunchKernelGGL((ln_bwd_kernel<float, float>), grid, block, 0, as_stream(stream), (const float*)dy, x, gamma, mean, rstd, dres, (const float*)dres2, dx, (float*)dxcast, dgamma, part, M, D, dx_scale);
+        hipLaunchKernelGGL((ln_bwd_kernel<float, float>), grid, block, 0, as_stream(stream), (const float*)dy, x, gamma, mean, rstd, dres, (const float*)dres2, dx, (float*)dxcast, dgamma, part, M, D, dx_scale, ns);
     else if (cast_dtype == 0)
-        hipLaunchKernelGGL((ln_bwd_kernel<float, h16_t>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, (const float*)dres2, dx, (float*)dxcast, dgamma, part, M, D, dx_scale);
+        hipLaunchKernelGGL((ln_bwd_kernel<float, h16_t>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, (const float*)dres2, dx, (float*)dxcast, dgamma, part, M, D, dx_scale, ns);
     else if (dy_dtype == 0)
-        hipLaunchKernelGGL((ln_bwd_kernel<h16_t, float>), grid, block, 0, as_stream(stream), (const float*)dy, x, gamma, mean, rstd, dres, (const h16_t*)dres2, dx, (h16_t*)dxcast, dgamma, part, M, D, dx_scale);
+        hipLaunchKernelGGL((ln_bwd_kernel<h16_t, float>), grid, block, 0, as_stream(stream), (const float*)dy, x, gamma, mean, rstd, dres, (const h16_t*)dres2, dx, (h16_t*)dxcast, dgamma, part, M, D, dx_scale, ns);
     else
-        hipLaunchKernelGGL((ln_bwd_kernel<h16_t, h16_t>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, (const h16_t*)dres2, dx, (h16_t*)dxcast, dgamma, part, M, D, dx_scale);
+        hipLaunchKernelGGL((ln_bwd_kernel<h16_t, h16_t>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, (const h16_t*)dres2, dx, (h16_t*)dxcast, dgamma, part, M, D, dx_scale, ns);
     int rc = omlm_post_launch("omlm_layernorm_bwd2");
     if (rc) return rc;
     if (two_level && dgamma) return omlm_colsum_accumulate(part, dgamma, blocks, D, D, stream);
     return OMLM_OK;
 }
+#if !OMLM_FP16
+extern "C" int omlm_layernorm_bwd2(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                                   const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D,
+                                   float dx_scale, int cast_dtype, int dy_dtype, void* stream) {
+    return omlm_layernorm_bwd2_seg(dy, x, gamma, mean, rstd, dres, dres2, dx, dxcast, dgamma, workspace, M, D, dx_scale, cast_dtype, dy_dtype, 0, 0, 0, stream);
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------
 // q/k l2norm * scale.  One wave per 64-wide vector, one element per lane (dim_head == 64).

@@ -176,6 +176,7 @@ class SeqLayout:
     start_col: torch.Tensor                # [N] bool: position is a start token
     final_only: bool = False               # AR decode: only the last row of the last sequence is scored -> [B, ldV]
     head_maps: Dict[Tuple[int, int], Tuple[torch.Tensor, torch.Tensor, int]] = field(default_factory=dict)
+    live_maps: Dict[Tuple[int, int, int], torch.Tensor] = field(default_factory=dict)      # a_map re-based onto a live-row segment (head_map)
 
 
 def build_layout(B: int, lens: Sequence[int], quantizers: Sequence[int], device, final_rows_only: bool = False) -> SeqLayout:
@@ -210,6 +211,73 @@ def build_layout(B: int, lens: Sequence[int], quantizers: Sequence[int], device,
             c_map = (b * n_s + js[None, :]).reshape(-1).to(torch.int32)
             lay.head_maps[(s, qq)] = (a_map.to(device), c_map.to(device), int(a_map.numel()))
     return lay
+
+
+# ------------------------------------------------------------------------------------------------------
+# live rows of the LAST layer's feed-forward block
+# ------------------------------------------------------------------------------------------------------
+# The feed-forward block of the last layer feeds only its own row's final LayerNorm and head (no later layer takes its output as K/V); the one
+# cross-row step in it is the causal 3-tap conv (row i reads h1 of rows i - 2 .. i).  So with only some heads wanted -- the trainers' loss
+# weights [0, 0, 1] -- the rows in front of the first position any wanted head reads, less the conv halo, are computed for nothing, forward
+# and backward (their dres is exactly zero).  The last layer then runs LN2 .. FF-out, the final LayerNorm and the heads on the rows
+# [p0, N) of every sample, stored compact: compact row r is full row (r / n_live) * n_full + p0 + r % n_live.
+CONV_HALO = 2                # rows in front of a row that the causal depthwise conv reads (kernel size 3)
+LIVE_K_MULTIPLE = 64         # B * n_live is the K of the last layer's dW1 / dW2: the grouped weight-gradient launch keeps its SGPR-offset form
+                             # only while every problem's K is a multiple of 64 (one ragged K slows the whole group)
+FF_ONE_PASS_MAX_FP = 3072    # Fp up to which the ConvFeedForward middle runs the strip forward and the one-pass backward (csrc/ffmid2.hip)
+
+
+def first_live_row(lay: SeqLayout, want: Sequence[bool]) -> Optional[int]:
+    """Smallest position that the a_map of any wanted head reads (head_maps: sequence s reads positions starts[s] + j, j < n_out[s])."""
+    firsts = [st for st, n_s, w in zip(lay.starts, lay.n_out, want) if w and n_s > 0]
+    return min(firsts) if firsts else None
+
+
+def live_rows(lay: SeqLayout, want: Sequence[bool], B: int, T: torch.dtype, Fp: int, halo: int = CONV_HALO) -> Optional[Tuple[int, int, int]]:
+    """The segment (n_full = N, p0, n_live = N - p0) the last layer's feed-forward block runs on, or None for "full rows".
+    p0 is the largest value <= first_live - halo for which B * n_live is a multiple of 64.  Full rows: no such p0 >= N / 16 (too little to
+    win), fp32 operands ("bf16x3"), an FF width beyond the one-pass strip kernels, final_rows_only layouts, and OMLM_LIVE_ROWS=0 (a test
+    hook, read at every call)."""
+    if os.environ.get("OMLM_LIVE_ROWS", "1") == "0":
+        return None
+    if lay.final_only or T == torch.float32 or Fp > FF_ONE_PASS_MAX_FP:
+        return None
+    first = first_live_row(lay, want)
+    if first is None:
+        return None
+    N = lay.N
+    g = LIVE_K_MULTIPLE // math.gcd(B, LIVE_K_MULTIPLE)          # B * (N - p0) % 64 == 0  <=>  p0 = N (mod g)
+    top = first - halo
+    if top < 0:
+        return None
+    p0 = top - (top - N) % g
+    if p0 <= 0 or 16 * p0 < N:
+        return None
+    return N, p0, N - p0
+
+
+def live_to_full(r, seg: Tuple[int, int, int]):
+    """Full row of compact row r (an int or an integer tensor)."""
+    n_full, p0, n_live = seg
+    return (r // n_live) * n_full + p0 + r % n_live
+
+
+def full_to_live(r, seg: Tuple[int, int, int]):
+    """Compact row of full row r, which must lie inside the segment (position >= p0)."""
+    n_full, p0, n_live = seg
+    return (r // n_full) * n_live + r % n_full - p0
+
+
+def head_map(lay: SeqLayout, s: int, qq: int, live: Optional[Tuple[int, int, int]]):
+    """head_maps[(s, qq)] with the hidden-state row map re-based onto the live-row segment (cached on the layout)."""
+    ent = lay.head_maps.get((s, qq))
+    if ent is None or live is None:
+        return ent
+    a_map, c_map, rows = ent
+    key = (s, qq, live[1])
+    if key not in lay.live_maps:
+        lay.live_maps[key] = full_to_live(a_map, live).to(torch.int32)
+    return lay.live_maps[key], c_map, rows
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -551,11 +619,13 @@ def dropout_state(tr, dev=None) -> dict:
 
 
 def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[torch.Tensor], B: int, N: int,
-                  save: bool, training: bool, keep_h1_lo_tail: bool = False):
+                  save: bool, training: bool, keep_h1_lo_tail: bool = False, live: Optional[Tuple[int, int, int]] = None):
     """x: [B*N, D] fp32 (consumed as the layer-0 residual).  Returns (final LN output y in operand dtype, y_lo, saved); y_lo: the lo plane
     of y for heads_forward (precision "fp16ff": the final LayerNorm's output leaves as hi/lo planes), else None.
     keep_h1_lo_tail ("fp16ff" prefill of the cached decoder): the lo plane of the last two h1 rows of every sample survives as sv.h1_lo_tail
-    [B, 2, 2 Fp] fp32 (rows N-2, N-1; zeros where N < 2) -- the causal conv's state is the un-rounded h1."""
+    [B, 2, 2 Fp] fp32 (rows N-2, N-1; zeros where N < 2) -- the causal conv's state is the un-rounded h1.
+    live (live_rows): the LAST layer's feed-forward block and the final LayerNorm run on the rows [p0, N) of every sample only; y, y_lo and
+    what the backward keeps of them ([B * n_live, ..]) are compact."""
     T = pw.T
     dev = x.device
     M, D = x.shape
@@ -574,6 +644,7 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
             rp_saved = ("cached", rc)
     saved_layers: List[LayerSaved] = []
     abiases = None
+    assert live is None or (len(tr.layers) > 0 and not keep_h1_lo_tail and live[0] == N)
     salt, seeds, aseeds, oseeds = (None, None, None, None)
     # attention dropout (probabilities, to_out), read at every forward like the FF dropout: off in eval mode
     aps = [(float(a_.attn_dropout.p), float(a_.to_out[1].p)) if training else (0.0, 0.0) for a_, _, _ in tr.layers]
@@ -626,7 +697,15 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
             del yo
         else:
             ops.gemm(o, w["Wo"], x1, M=M, N=D, K=H * DIM_HEAD, Cin=x)
-        # feed-forward
+        # feed-forward: on the live rows only in the last layer (LN2 gathers them and leaves the fp32 residual rows compact next to its output)
+        seg = live if li == len(tr.layers) - 1 else None
+        x1c = None
+        if seg is not None:
+            M = B * seg[2]
+            nff = seg[2]
+            x1c = torch.empty(M, D, device=dev)
+        else:
+            nff = N
         m2 = torch.empty(M, device=dev); r2 = torch.empty(M, device=dev)
         xn2 = torch.empty(M, D, dtype=T, device=dev)
         h1 = torch.empty(M, 2 * Fp, dtype=T, device=dev)
@@ -634,19 +713,21 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
             # "fp16ff", round 6: the FF GEMMs as one half product + two fp8 corrections.  The LayerNorm (and, below, the conv-GEGLU-LN kernel)
             # leaves the hi plane -- what the fp16 backward keeps -- plus fp8 planes and row scales that die with the layer
             P1 = ops.Fp8Planes(M, D, dev, zero=False)
-            ops.layernorm_fwd_mx(x1, ff.norm_in.gamma.detach(), xn2, P1, m2, r2)
+            ops.layernorm_fwd_mx(x1, ff.norm_in.gamma.detach(), xn2, P1, m2, r2, seg=seg, xc=x1c)
             h1_lo = torch.empty(M, 2 * Fp, dtype=torch.uint8, device=dev)      # the lo plane as bf8 (e5m2) bytes: h1 = hi + lo to 2^-14
             ops.gemm_mx16(xn2, P1, w["W1p"], w["W1p8"], h1, h1_lo, M=M, N=2 * Fp, K=D)
         elif pw.ff_planes:
             # "fp16ff": LN output, h1 and h2 exist as hi/lo planes during this layer's forward; the lo planes die with the layer (their
             # consumers are the next launches of this stream), the hi planes are what the fp16 backward keeps
             xn2_lo = torch.empty(M, D, dtype=T, device=dev)
-            ops.layernorm_fwd_planes(x1, ff.norm_in.gamma.detach(), xn2, xn2_lo, m2, r2)
+            ops.layernorm_fwd_planes(x1, ff.norm_in.gamma.detach(), xn2, xn2_lo, m2, r2, seg=seg, xc=x1c)
             h1_lo = torch.empty(M, 2 * Fp, dtype=T, device=dev)
             ops.gemm_planes16(xn2, xn2_lo, w["W1p"], w["W1p_lo"], h1, h1_lo, M=M, N=2 * Fp, K=D)
         else:
-            ops.layernorm_fwd(x1, ff.norm_in.gamma.detach(), xn2, None, m2, r2)
+            ops.layernorm_fwd(x1, ff.norm_in.gamma.detach(), xn2, None, m2, r2, seg=seg, xc=x1c)
             ops.gemm(xn2, w["W1p"], h1, M=M, N=2 * Fp, K=D)
+        if seg is not None:
+            x1 = x1c                                                   # the full x1 dies here: FF-out's residual and LN2's backward read the compact rows
         h2 = torch.empty(M, Fp, dtype=T, device=dev)
         m3 = torch.empty(M, device=dev); r3 = torch.empty(M, device=dev)
         p = float(ff.dropout_p) if training else 0.0
@@ -660,13 +741,13 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
         if pw.ff_planes:
             if pw.mx:
                 P2 = ops.Fp8Planes(M, Fp, dev, zero=False)
-                ops.ffmid_fwd_mx(h1, h1_lo, w["convw"], w["convw_lo"], w["gamma_mid"], w["gamma_mid_lo"], h2, P2, m3, r3, N, F, Fp, p, seed,
-                                 seed_dev=salt if p > 0 else None, drop_bits=drop_bits, gh=gh)
+                ops.ffmid_fwd_mx(h1, h1_lo, w["convw"], w["convw_lo"], w["gamma_mid"], w["gamma_mid_lo"], h2, P2, m3, r3, nff, F, Fp, p, seed,
+                                 seed_dev=salt if p > 0 else None, drop_bits=drop_bits, gh=gh, seg=seg)
                 ops.gemm_mx16(h2, P2, w["W2p"], w["W2p8"], x2, M=M, N=D, K=Fp, Cin=x1)
             else:
                 h2_lo = torch.empty(M, Fp, dtype=T, device=dev)
-                ops.ffmid_fwd_planes(h1, h1_lo, w["convw"], w["convw_lo"], w["gamma_mid"], w["gamma_mid_lo"], h2, h2_lo, m3, r3, N, F, Fp, p, seed,
-                                     seed_dev=salt if p > 0 else None, drop_bits=drop_bits, gh=gh)
+                ops.ffmid_fwd_planes(h1, h1_lo, w["convw"], w["convw_lo"], w["gamma_mid"], w["gamma_mid_lo"], h2, h2_lo, m3, r3, nff, F, Fp, p, seed,
+                                     seed_dev=salt if p > 0 else None, drop_bits=drop_bits, gh=gh, seg=seg)
                 ops.gemm_planes16(h2, h2_lo, w["W2p"], w["W2p_lo"], x2, M=M, N=D, K=Fp, Cin=x1)
                 del xn2_lo, h2_lo
             if keep_h1_lo_tail and save:
@@ -678,8 +759,8 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
                 sv.h1_lo_tail[:, 2 - take:].copy_(tail)
             del h1_lo
         else:
-            ops.ffmid_fwd(h1, w["convw"], w["gamma_mid"], h2, m3, r3, N, F, Fp, p, seed, seed_dev=salt if p > 0 else None,
-                          drop_bits=drop_bits, gh=gh)
+            ops.ffmid_fwd(h1, w["convw"], w["gamma_mid"], h2, m3, r3, nff, F, Fp, p, seed, seed_dev=salt if p > 0 else None,
+                          drop_bits=drop_bits, gh=gh, seg=seg)
             ops.gemm(h2, w["W2p"], x2, M=M, N=D, K=Fp, Cin=x1)
         if save:
             sv.x, sv.m1, sv.r1, sv.xn, sv.xc = x, m1, r1, xn, xc
@@ -697,16 +778,21 @@ def trunk_forward(tr, pw: PreparedWeights, x: torch.Tensor, keymask: Optional[to
         ops.layernorm_fwd_planes(x, tr.norm.gamma.detach(), y, y_lo, mf, rf)
     else:
         ops.layernorm_fwd(x, tr.norm.gamma.detach(), y, None, mf, rf)
-    saved = dict(layers=saved_layers, xL=x, mf=mf, rf=rf, table=table, rp=rp_saved, keymask=keymask, salt=salt) if save else None
+    saved = dict(layers=saved_layers, xL=x, mf=mf, rf=rf, table=table, rp=rp_saved, keymask=keymask, salt=salt, live=live) if save else None
     return y, y_lo, saved
 
 
 def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: int, out_scale: float, head_wgrads=None):
-    """dy: [M, D] fp32 gradient of the final LayerNorm output.  Accumulates parameter grads; returns
-    d(trunk input) * out_scale (fp32).  out_scale carries the grad_shrink factor (utils.py:60-61)."""
+    """dy: [M, D] fp32 gradient of the final LayerNorm output ([B * n_live, D], compact, when the forward ran its last feed-forward block
+    on a live-row segment).  Accumulates parameter grads; returns d(trunk input) * out_scale (fp32).  out_scale carries the grad_shrink
+    factor (utils.py:60-61)."""
     T = pw.T
     dev = dy.device
-    M, D = dy.shape
+    D = dy.shape[1]
+    M_all = B * N
+    live = saved.get("live")
+    M = B * live[2] if live is not None else M_all              # rows of the final LayerNorm and of the last layer's feed-forward block
+    assert dy.shape[0] == M
     H = tr.heads
     table, keymask = saved["table"], saved["keymask"]
     rp_cached = saved["rp"] is not None and saved["rp"][0] == "cached"
@@ -730,17 +816,20 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
             ops.gemm(dYh, Xh, dWh, M=Mo, N=No, K=dYh.shape[0], a_kmajor=True, b_kmajor=True, Cin=dWh)
 
     def wgrad(dY, X, dW, Mo, No, c_map=None):
+        K = dY.shape[0]                                            # the rows contracted over: M, or the live rows in the last layer's FF block
         if wg is not None:
-            wg.add(dY, X, dW, M=Mo, N=No, K=M, c_map=c_map)
+            wg.add(dY, X, dW, M=Mo, N=No, K=K, c_map=c_map)
             if len(wg.items) >= 40:
                 wg.flush()
         else:
-            ops.gemm(dY, X, dW, M=Mo, N=No, K=M, a_kmajor=True, b_kmajor=True, Cin=dW, c_map=c_map)
+            ops.gemm(dY, X, dW, M=Mo, N=No, K=K, a_kmajor=True, b_kmajor=True, Cin=dW, c_map=c_map)
 
     for li in range(nl - 1, -1, -1):
         attn, _, ff = tr.layers[li]
         w, sv = pw.layers[li], saved["layers"][li]
         F, Fp = w["F"], w["Fp"]
+        seg = live if li == nl - 1 else None                       # (M is the live rows in that layer's FF block, all rows from its LN2 backward on)
+        nff = seg[2] if seg is not None else N
         # ---- feed-forward block: x2 = x1 + h2 W2^T ----
         dh2 = torch.empty(M, Fp, dtype=T, device=dev)
         ops.gemm(dres_c, w["W2p"], dh2, M=M, N=Fp, K=D, b_kmajor=True)
@@ -752,7 +841,7 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
         dh1 = torch.empty(M, 2 * Fp, dtype=T, device=dev)
         gconv = grad_of(ff.conv_param()).view(-1) if ff.conv_param() is not None else None
         ops.ffmid_bwd(dh2, sv.h1, w["convw"], w["gamma_mid"], sv.m3, sv.r3, du, dh1,
-                      grad_of(ff.norm_mid.gamma), gconv, ws, N, F, Fp, sv.p, sv.seed,
+                      grad_of(ff.norm_mid.gamma), gconv, ws, nff, F, Fp, sv.p, sv.seed,
                       seed_dev=saved["salt"] if sv.p > 0 else None, drop_bits=sv.drop_bits, gh=sv.gh)
         del du, dh2
         dxn2 = torch.empty(M, D, dtype=T, device=dev)                                 # consumed only by the LayerNorm backward
@@ -760,10 +849,12 @@ def trunk_backward(tr, pw: PreparedWeights, saved, dy: torch.Tensor, B: int, N: 
         gW1 = grad_of(ff.w_in.weight)                                               # [2F, D]
         wgrad(dh1, sv.xn2, gW1, 2 * Fp, D, c_map=w["dW1_cmap"])
         del dh1
+        M = M_all
         dx1 = torch.empty(M, D, device=dev)
         dx1_c = dx1 if T == torch.float32 else torch.empty(M, D, dtype=T, device=dev)
+        # (seg: dxn2, x1, the statistics and dres are compact; dx1 / dx1_c are full, their rows in front of the segment written as zeros)
         ops.layernorm_bwd(dxn2, sv.x1, ff.norm_in.gamma.detach(), sv.m2, sv.r2, dres, dx1,
-                          None if T == torch.float32 else dx1_c, grad_of(ff.norm_in.gamma), defer=cg)
+                          None if T == torch.float32 else dx1_c, grad_of(ff.norm_in.gamma), defer=cg, seg=seg)
         # ---- attention block: x1 = x + o Wo^T ----
         dyo = dx1_c
         if sv.po > 0:                                              # through to_out's dropout: dy = keep o dx1 / (1 - p)
@@ -863,8 +954,10 @@ def embed_backward(model, ids32: torch.Tensor, lay: SeqLayout, dx: torch.Tensor,
                   [grad_of(s) for s in model.start_tokens], dpos, dx.view(B, N, -1), alpha)
 
 
-def heads_forward(model, pw: PreparedWeights, y: torch.Tensor, y_lo: Optional[torch.Tensor], lay: SeqLayout, want: Sequence[bool]):
-    """y: [B*N, D] operand dtype; y_lo: its lo plane ("fp16ff": three-product heads) or None, as trunk_forward returns them.
+def heads_forward(model, pw: PreparedWeights, y: torch.Tensor, y_lo: Optional[torch.Tensor], lay: SeqLayout, want: Sequence[bool],
+                  live: Optional[Tuple[int, int, int]] = None):
+    """y: [B*N, D] operand dtype ([B * n_live, D] with a live-row segment: the heads' row maps are re-based); y_lo: its lo plane ("fp16ff":
+    three-product heads) or None, as trunk_forward returns them.
     Returns per sequence a padded fp32 logits buffer [B*n_s, ldV] or None.
     (einsum 'q c d, b n q d -> b n q c' incl. the remainder positions, open_musiclm.py:163-186: the hidden
     position j of a sequence is scored by quantizer head j mod Q.)"""
@@ -881,7 +974,7 @@ def heads_forward(model, pw: PreparedWeights, y: torch.Tensor, y_lo: Optional[to
         # handed back): no 147 MB zero fill per step
         buf = torch.empty(lay.B if lay.final_only else lay.B * n_s, ldV, device=y.device)
         for qq in range(seq.num_quantizers):
-            ent = lay.head_maps.get((s, qq))
+            ent = head_map(lay, s, qq, live)
             if ent is None:
                 continue
             a_map, c_map, rows = ent
@@ -896,8 +989,9 @@ def heads_forward(model, pw: PreparedWeights, y: torch.Tensor, y_lo: Optional[to
 
 
 def heads_backward(model, pw: PreparedWeights, y: torch.Tensor, lay: SeqLayout, dlogits: Sequence[Optional[torch.Tensor]],
-                   deferred: Optional[list] = None):
-    """dlogits[s]: [B*n_s, ldV] in the operand dtype with zeroed pad columns, or None.  Returns dy fp32 [B*N, D].
+                   deferred: Optional[list] = None, live: Optional[Tuple[int, int, int]] = None):
+    """dlogits[s]: [B*n_s, ldV] in the operand dtype with zeroed pad columns, or None.  Returns dy fp32 [B*N, D] (y's rows: compact with a
+    live-row segment).
     deferred (16-bit operands): the heads' weight gradients are not launched here but appended as (dY, X, dW, M, N) for the trunk's
     grouped launch -- as their own row-mapped split-K GEMMs they ran at 158 TFLOP/s (3 x 128 us per step); gathered into contiguous
     rows they are 60 more full-K tiles of the ~900-tile group."""
@@ -911,7 +1005,7 @@ def heads_backward(model, pw: PreparedWeights, y: torch.Tensor, lay: SeqLayout, 
         ldV = dl.shape[-1]
         gW = grad_of(model.logit_weights[s])                                   # [Q, V1, D]
         for qq in range(seq.num_quantizers):
-            ent = lay.head_maps.get((s, qq))
+            ent = head_map(lay, s, qq, live)
             if ent is None:
                 continue
             a_map, c_map, rows = ent
@@ -961,11 +1055,12 @@ def run_forward(model, all_token_ids, self_attn_mask, only_final: bool, save: bo
         assert self_attn_mask.shape == (B, N), f"self_attn_mask must be [{B}, {N}]"
         keymask = self_attn_mask.to(torch.uint8).contiguous()
     x = embed_forward(model, ids32, lay)
-    y, y_lo, tsaved = trunk_forward(tr, pw, x, keymask, B, N, save, model.training)
     nseq = len(model.token_sequences)
     if want is None:
         want = [(not only_final) or s == nseq - 1 for s in range(nseq)]
-    logits = heads_forward(model, pw, y, y_lo, lay, want)
+    live = live_rows(lay, want, B, pw.T, pw.layers[-1]["Fp"]) if pw.layers else None
+    y, y_lo, tsaved = trunk_forward(tr, pw, x, keymask, B, N, save, model.training, live=live)
+    logits = heads_forward(model, pw, y, y_lo, lay, want, live)
     st = None
     if save:
         st = ForwardState()
@@ -978,7 +1073,7 @@ def run_forward(model, all_token_ids, self_attn_mask, only_final: bool, save: bo
 def run_backward(st: ForwardState, dlogits: Sequence[Optional[torch.Tensor]]):
     model = st.model
     deferred = [] if st.pw.T in _H16 else None
-    dy = heads_backward(model, st.pw, st.y, st.lay, dlogits, deferred)
+    dy = heads_backward(model, st.pw, st.y, st.lay, dlogits, deferred, st.trunk["live"])
     alpha = float(model.transformer.grad_shrink_alpha)
     dx = trunk_backward(model.transformer, st.pw, st.trunk, dy, st.B, st.N, out_scale=alpha, head_wgrads=deferred)
     embed_backward(model, st.ids32, st.lay, dx, 1.0)

@@ -34,10 +34,15 @@ SIGNATURES = {
     "omlm_gemm_mx16_workspace_bytes": [i32, i32, i32],
     "omlm_layernorm_fwd_mx": [vp, vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, f32, vp],
     "omlm_ffmid_fwd_mx": [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, f32, f32, u64, vp, vp, vp, vp],
+    "omlm_layernorm_fwd_mx_seg": [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, vp],
+    "omlm_ffmid_fwd_mx_seg": [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, f32, f32, u64, vp, vp, vp, i32, i32, vp],
     "omlm_quant_rows_mx": [vp, i32, vp],
     "omlm_layernorm_fwd_planes": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp],
     "omlm_ffmid_fwd_planes": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, u64, vp, vp, vp, i32, vp],
     "omlm_layernorm_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp],
+    "omlm_layernorm_fwd_seg": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, vp],
+    "omlm_layernorm_fwd_planes_seg": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, i32, i32, vp],
+    "omlm_layernorm_bwd2_seg": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, i32, i32, i32, i32, vp],
     "omlm_layernorm_bwd_workspace_bytes": [i32],
     "omlm_layernorm_bwd2": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, i32, i32, vp],
     "omlm_qk_norm_fwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
@@ -55,6 +60,8 @@ SIGNATURES = {
     "omlm_dropout_residual_fwd": [vp, vp, vp, i64, i32, f32, u64, vp, vp],
     "omlm_dropout_residual_bwd": [vp, vp, i64, i32, f32, u64, vp, i32, vp],
     "omlm_ffmid_fwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, u64, vp, vp, vp, i32, vp],
+    "omlm_ffmid_fwd_seg": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, u64, vp, vp, vp, i32, i32, i32, vp],
+    "omlm_ffmid_fwd_planes_seg": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, u64, vp, vp, vp, i32, i32, i32, vp],
     "omlm_ffmid_bwd_workspace_bytes": [i32, i32],
     "omlm_ffmid_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, u64, vp, vp, vp, i32, vp],
     "omlm_colsum_accumulate": [vp, vp, i32, i32, i32, vp],

@@ -251,23 +251,50 @@ class CastPadGroup(_DescGroup):
         self.items.append((src, dst, int(R), int(C_), int(ld_src), int(ld_dst), int(bool(transpose)), int(bool(lo))))
 
 
-def layernorm_fwd(x, gamma, y, xcast, mean, rstd, eps=1e-5):
+def _seg_rows(x, y, seg, xc):
+    """A row segment (n_full, p0, n_live) of x [B * n_full, D] (include/omlm.h, "Row segments"): the compact row count, checked against the outputs."""
+    n_full, p0, n_live = seg
+    assert x.shape[0] % n_full == 0 and p0 + n_live == n_full and p0 > 0
+    M = x.shape[0] // n_full * n_live
+    assert y.shape[0] == M and (xc is None or (xc.shape == (M, x.shape[1]) and xc.dtype == torch.float32))
+    return M
+
+
+def layernorm_fwd(x, gamma, y, xcast, mean, rstd, eps=1e-5, seg=None, xc=None):
+    """seg (n_full, p0, n_live): x is read at the segment's rows and y, mean, rstd leave compact ([B * n_live, ..]); xc (optional) receives the
+    fp32 source rows compact in the same pass."""
     M, D = x.shape
+    if seg is not None:
+        assert xcast is None and mean.numel() == rstd.numel() == y.shape[0]
+        call("omlm_layernorm_fwd_seg", ptr(x), ptr(gamma), ptr(y), None, ptr(mean), ptr(rstd), ptr(xc),
+             _seg_rows(x, y, seg, xc), D, y.shape[-1], float(eps), dcode(y.dtype), *seg, stream_ptr())
+        return
     call("omlm_layernorm_fwd", ptr(x), ptr(gamma), ptr(y), ptr(xcast), ptr(mean), ptr(rstd),
          M, D, y.shape[-1], float(eps), dcode(y.dtype), stream_ptr())
 
 
-def layernorm_fwd_planes(x, gamma, y, y_lo, mean, rstd, eps=1e-5):
+def layernorm_fwd_planes(x, gamma, y, y_lo, mean, rstd, eps=1e-5, seg=None, xc=None):
     """layernorm_fwd with the result as hi/lo planes of y's 16-bit type: y = rne16(v), y_lo = rne16(v - y) (omlm_layernorm_fwd_planes)."""
     M, D = x.shape
     assert y.dtype in H16 and y_lo.dtype == y.dtype and y_lo.shape == y.shape
+    if seg is not None:
+        assert mean.numel() == rstd.numel() == y.shape[0]
+        call("omlm_layernorm_fwd_planes_seg", ptr(x), ptr(gamma), ptr(y), ptr(y_lo), ptr(mean), ptr(rstd), ptr(xc),
+             _seg_rows(x, y, seg, xc), D, y.shape[-1], float(eps), dcode(y.dtype), *seg, stream_ptr())
+        return
     call("omlm_layernorm_fwd_planes", ptr(x), ptr(gamma), ptr(y), ptr(y_lo), ptr(mean), ptr(rstd),
          M, D, y.shape[-1], float(eps), dcode(y.dtype), stream_ptr())
 
 
-def layernorm_fwd_mx(x, gamma, y, P: "Fp8Planes", mean, rstd, eps=1e-5):
+def layernorm_fwd_mx(x, gamma, y, P: "Fp8Planes", mean, rstd, eps=1e-5, seg=None, xc=None):
     """layernorm_fwd with y as omlm_gemm_mx16's A operand: the half hi plane y (bit for bit layernorm_fwd's) + its fp8 planes and row scales in P."""
     M, D = x.shape
+    if seg is not None:
+        M = _seg_rows(x, y, seg, xc)
+        assert y.dtype == torch.float16 and P.ld == y.shape[-1] and P.rows >= M and mean.numel() == rstd.numel() == M
+        call("omlm_layernorm_fwd_mx_seg", ptr(x), ptr(gamma), ptr(y), ptr(P.planes), P.stride, ptr(P.scale), ptr(mean), ptr(rstd), ptr(xc),
+             M, D, y.shape[-1], float(eps), *seg, stream_ptr())
+        return
     assert y.dtype == torch.float16 and P.ld == y.shape[-1] and P.rows >= M
     call("omlm_layernorm_fwd_mx", ptr(x), ptr(gamma), ptr(y), ptr(P.planes), P.stride, ptr(P.scale), ptr(mean), ptr(rstd),
          M, D, y.shape[-1], float(eps), stream_ptr())
@@ -318,10 +345,16 @@ class ColsumGroup(_DescGroup):
         self.items.append((part, out, int(P), int(C_), int(ldp)))
 
 
-def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dx, dxcast, dgamma, dx_scale=1.0, dres2=None, defer: Optional["ColsumGroup"] = None):
+def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dx, dxcast, dgamma, dx_scale=1.0, dres2=None, defer: Optional["ColsumGroup"] = None, seg=None):
     """dres2 (optional): a second residual-gradient term in the cast type (dxcast's dtype; with dxcast None its own dtype names it).
-    defer: the d(gamma) partial rows stay in a workspace of this call's own and their column sum joins the group's one launch."""
+    defer: the d(gamma) partial rows stay in a workspace of this call's own and their column sum joins the group's one launch.
+    seg (n_full, p0, n_live): dy, x, the statistics and dres are compact ([B * n_live, ..]); dx / dxcast are full-size ([B * n_full, D]): the
+    segment's rows are written, the rows in front of it as zeros by the same launch (no dres2)."""
     M, D = x.shape
+    if seg is not None:
+        n_full, p0, n_live = seg
+        assert dres2 is None and M % n_live == 0 and p0 + n_live == n_full and dy.shape[0] == M
+        assert dx.shape[0] == M // n_live * n_full and (dxcast is None or dxcast.shape[0] == dx.shape[0]) and (dres is None or dres.shape[0] == M)
     code = dcode(dxcast.dtype) if dxcast is not None else (dcode(dres2.dtype) if dres2 is not None else F32)
     assert dres2 is None or dcode(dres2.dtype) == code, "dres2 must have the cast type"
     deferred = dgamma is not None and defer is not None
@@ -330,8 +363,13 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dx, dxcast, dgamma, dx_scale=1
         ws = torch.empty(rows * D, device=x.device)     # private, alive until the group's flush: one partial row per workgroup (min(M, 2048) of them)
     else:
         ws = _ln_workspace(D, x.device) if dgamma is not None else None       # stream-ordered reuse: one backward at a time
-    call("omlm_layernorm_bwd2", ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dres2), ptr(dx),
-         ptr(dxcast), ptr(None if deferred else dgamma), ptr(ws), M, D, float(dx_scale), code, dcode(dy.dtype), stream_ptr())
+    if seg is not None:
+        call("omlm_layernorm_bwd2_seg", ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), None, ptr(dx),
+             ptr(dxcast), ptr(None if deferred else dgamma), ptr(ws), M, D, float(dx_scale), dcode(dy.dtype) if dxcast is None else code,
+             dcode(dy.dtype), *seg, stream_ptr())
+    else:
+        call("omlm_layernorm_bwd2", ptr(dy), ptr(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dres2), ptr(dx),
+             ptr(dxcast), ptr(None if deferred else dgamma), ptr(ws), M, D, float(dx_scale), code, dcode(dy.dtype), stream_ptr())
     if deferred:
         defer.add(ws, dgamma, rows, D, D)
 
@@ -502,38 +540,48 @@ def pad_vector(v: torch.Tensor, n: int) -> torch.Tensor:
     return out
 
 
-def ffmid_fwd(h1, convw, gamma, h2, mean, rstd, nseq, F, Fp, p, seed, eps=1e-5, seed_dev=None, drop_bits=None, gh=None):
-    """convw: packed taps [3, 2*Fp] (pack_conv_taps); gamma: padded [Fp] (pad_vector)."""
+def _ff_seg(seg, nseq):
+    """(n_full, p0) of a row segment for the ConvFeedForward forwards (nseq is its n_live), or (0, 0): none."""
+    if seg is None:
+        return 0, 0
+    assert seg[2] == nseq and seg[1] + seg[2] == seg[0]
+    return int(seg[0]), int(seg[1])
+
+
+def ffmid_fwd(h1, convw, gamma, h2, mean, rstd, nseq, F, Fp, p, seed, eps=1e-5, seed_dev=None, drop_bits=None, gh=None, seg=None):
+    """convw: packed taps [3, 2*Fp] (pack_conv_taps); gamma: padded [Fp] (pad_vector).
+    seg (n_full, p0, n_live = nseq): the buffers hold rows [p0, n_full) of every sample compact; the keep bits drawn are those of a launch
+    over the full rows (include/omlm.h: omlm_ffmid_fwd_seg)."""
     assert convw.shape == (3, 2 * Fp) and gamma.numel() == Fp
     assert convw.dtype == h1.dtype and gamma.dtype == h1.dtype, "taps / gamma travel in the operand dtype of h1"
-    call("omlm_ffmid_fwd", ptr(h1), ptr(convw), ptr(gamma), ptr(h2), ptr(mean), ptr(rstd),
+    call("omlm_ffmid_fwd_seg", ptr(h1), ptr(convw), ptr(gamma), ptr(h2), ptr(mean), ptr(rstd),
          h1.shape[0], nseq, F, Fp, float(eps), float(p), int(seed), ptr(seed_dev), ptr(drop_bits), ptr(gh), dcode(h1.dtype),
-         stream_ptr())
+         *_ff_seg(seg, nseq), stream_ptr())
 
 
 def ffmid_fwd_planes(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo, mean, rstd, nseq, F, Fp, p, seed, eps=1e-5, seed_dev=None,
-                     drop_bits=None, gh=None):
+                     drop_bits=None, gh=None, seg=None):
     """ffmid_fwd on hi/lo planes (precision "fp16ff"): h1, taps and gamma are read as hi + lo, h2 leaves as planes (omlm_ffmid_fwd_planes)."""
     assert convw.shape == (3, 2 * Fp) and gamma.numel() == Fp and h1.dtype in H16
     for t in (h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo):
         assert t.dtype == h1.dtype, "every plane travels in the operand dtype of h1"
     assert h1_lo.shape == h1.shape and h2_lo.shape == h2.shape and convw_lo.shape == convw.shape
-    call("omlm_ffmid_fwd_planes", ptr(h1), ptr(h1_lo), ptr(convw), ptr(convw_lo), ptr(gamma), ptr(gamma_lo), ptr(h2), ptr(h2_lo), ptr(mean),
+    call("omlm_ffmid_fwd_planes_seg", ptr(h1), ptr(h1_lo), ptr(convw), ptr(convw_lo), ptr(gamma), ptr(gamma_lo), ptr(h2), ptr(h2_lo), ptr(mean),
          ptr(rstd), h1.shape[0], nseq, F, Fp, float(eps), float(p), int(seed), ptr(seed_dev), ptr(drop_bits), ptr(gh), dcode(h1.dtype),
-         stream_ptr())
+         *_ff_seg(seg, nseq), stream_ptr())
 
 
 def ffmid_fwd_mx(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, P: "Fp8Planes", mean, rstd, nseq, F, Fp, p, seed, eps=1e-5, seed_dev=None,
-                 drop_bits=None, gh=None):
+                 drop_bits=None, gh=None, seg=None):
     """ffmid_fwd_planes with h2 leaving as omlm_gemm_mx16's A operand: the half hi plane h2 + its fp8 planes and row scales in P.
     h1_lo: the lo plane of h1 as bf8 bytes (uint8, h1's shape: gemm_mx16's plane output)."""
     assert convw.shape == (3, 2 * Fp) and gamma.numel() == Fp and h1.dtype == torch.float16 and h1_lo.dtype == torch.uint8
     for t in (convw, convw_lo, gamma, gamma_lo, h2):
         assert t.dtype == h1.dtype, "every plane travels in the operand dtype of h1"
     assert h1_lo.shape == h1.shape and convw_lo.shape == convw.shape and P.ld == Fp and P.rows >= h1.shape[0]
-    call("omlm_ffmid_fwd_mx", ptr(h1), ptr(h1_lo), ptr(convw), ptr(convw_lo), ptr(gamma), ptr(gamma_lo), ptr(h2), ptr(P.planes), P.stride,
+    call("omlm_ffmid_fwd_mx_seg", ptr(h1), ptr(h1_lo), ptr(convw), ptr(convw_lo), ptr(gamma), ptr(gamma_lo), ptr(h2), ptr(P.planes), P.stride,
          ptr(P.scale), ptr(mean), ptr(rstd), h1.shape[0], nseq, F, Fp, float(eps), float(p), int(seed), ptr(seed_dev), ptr(drop_bits), ptr(gh),
-         stream_ptr())
+         *_ff_seg(seg, nseq), stream_ptr())
 
 
 def ffmid_set_impl(impl: int):

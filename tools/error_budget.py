@@ -52,7 +52,8 @@ def lin(c, a32, w32, w16, out, **kw):
     ops.gemm(A.contiguous(), W, out, **kw)
 
 
-def diag_trunk_forward(tr, pw16, x, keymask, B, N, save, training):
+def diag_trunk_forward(tr, pw16, x, keymask, B, N, save, training, live=None):
+    assert live is None                     # (main() keeps the engine on full rows: OMLM_LIVE_ROWS=0)
     model = tr.__dict__["_omlm_owner"]
     pw32 = model.__dict__.get("_diag_pw32")
     if pw32 is None:
@@ -106,7 +107,7 @@ def diag_trunk_forward(tr, pw16, x, keymask, B, N, save, training):
     return y, None, None
 
 
-def diag_heads_forward(model, pw16, y32, y_lo, lay, want):
+def diag_heads_forward(model, pw16, y32, y_lo, lay, want, live=None):
     pw32 = model.__dict__["_diag_pw32"]
     out = []
     for s, seq in enumerate(model.token_sequences):
@@ -147,6 +148,7 @@ def main():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(root, "gpurun_out", "error_budget.md")
     max_seeds = int(sys.argv[2]) if len(sys.argv) > 2 else 2
+    os.environ["OMLM_LIVE_ROWS"] = "0"        # this re-sequenced trunk computes every row of every layer
     E.trunk_forward = diag_trunk_forward
     E.heads_forward = diag_heads_forward
     rows = []
