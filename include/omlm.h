@@ -249,7 +249,7 @@ int omlm_colsum_accumulate(const float* part, float* out, int P, int C, int ldp,
  * pass (omlm_layernorm_bwd2 with dgamma NULL and a workspace leaves its [min(M, 2048), D] partial rows there instead of summing them). */
 typedef struct omlm_colsum_desc { const float* part; float* out; int P, C, ldp; } omlm_colsum_desc;
 int omlm_colsum_group(const omlm_colsum_desc* problems, int count, void* stream);
-/* 1 (default, or $OMLM_FFMID_IMPL): the column-strip kernels where their preconditions hold (Fp <= 4096, drop_bits present when
+/* 1 (default): the column-strip kernels where their preconditions hold (Fp <= 4096, drop_bits present when
  * p > 0, and gh present for the backward); 0: the wave-per-row kernels (A/B runs, tests). */
 int omlm_ffmid_set_impl(int impl);
 

@@ -47,6 +47,13 @@ static inline void launch_lds_cap(dim3 grid, dim3 block, size_t lds, hipStream_t
     if (!attr) { (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
     hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
 }
+// The same for kernels most of whose calls stay below the 48 KiB every kernel may have (the ConvFeedForward middle: LDS grows with Fp,
+// csrc/ffmid_plan.h): the instantiation about to be launched opts in, on the calls that need it.
+template <auto Kernel, typename... Args>
+static inline void launch_lds_optin(dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+}
 // f(std::bool_constant<a>, std::bool_constant<b>): two run-time flags as template arguments
 template <typename F>
 static inline void with_flags(bool a, bool b, F&& f) {

@@ -12,12 +12,12 @@
 // HBM-bound: forward reads h1 once (the two halo rows come from L2) and writes h2; nothing but the
 // per-row LN statistics is saved -- the backward recomputes u and g from h1.
 #include "common.h"
+#include "ffmid_plan.h"     // FF_THREADS, FF_MAXC_LIMIT (8-channel chunks per lane of the wave-per-row kernels -> Fp <= 8192), and every route
+#include <initializer_list>
 #include <stdlib.h>
 
 namespace OMLM_NS {
-
-#define FF_THREADS 256
-#define FF_MAXC_LIMIT 16   // 8-channel chunks per lane (wave-per-row kernels) -> Fp <= 8192
+using namespace omlm_plan;
 
 template <typename T> struct vec8;
 template <> struct vec8<float> {
@@ -572,8 +572,7 @@ extern "C" int omlm_colsum_group(const omlm_colsum_desc* d, int count, void* str
             if (q.C > cmax) cmax = q.C;
             if (q.P > pmax) pmax = q.P;
         }
-        const int ysplit = pmax >= 1024 ? 128 : (pmax >= 64 ? 16 : 1);
-        hipLaunchKernelGGL(colsum_group_kernel, dim3((cmax + 255) / 256, ysplit, ga.n), dim3(256), 0, as_stream(stream), ga);
+        hipLaunchKernelGGL(colsum_group_kernel, dim3((cmax + 255) / 256, colsum_ysplit(pmax), ga.n), dim3(256), 0, as_stream(stream), ga);
     }
     return omlm_post_launch("omlm_colsum_group");
 }
@@ -581,53 +580,112 @@ extern "C" int omlm_colsum_group(const omlm_colsum_desc* d, int count, void* str
 extern "C" int omlm_colsum_accumulate(const float* part, float* out, int P, int C, int ldp, void* stream) {
     if (P <= 0 || C <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(part && out && ldp >= C, "colsum arguments");
-    const int ysplit = P >= 1024 ? 128 : (P >= 64 ? 16 : 1);      // enough workgroups to stream a [2048, D] partial buffer
-    hipLaunchKernelGGL(colsum_kernel, dim3((C + 255) / 256, ysplit), dim3(256), 0, as_stream(stream), part, out, P, C, ldp);
+    hipLaunchKernelGGL(colsum_kernel, dim3((C + 255) / 256, colsum_ysplit(P)), dim3(256), 0, as_stream(stream), part, out, P, C, ldp);
     return omlm_post_launch("omlm_colsum_accumulate");
 }
 
 #endif
 
-#define FF_BWD1_BLOCKS 1024
-#define FF_BWD2_STRIPS 512
+// ---- host side: csrc/ffmid_plan.h decides what a call runs; the launcher below runs this file's kernels, ffmid2.hip's launcher the strip kernels ----
+static_assert(FF_ERR_ARG == OMLM_ERR_ARG && FF_LDS_CAP == 160 * 1024 && FF_LDS_OPT_IN == 48 * 1024, "ffmid_plan.h states the return code and launch_lds_optin's sizes");
+int ffmid2_launch(const FfmidLaunch& l, const FfmidArgs& a);        // ffmid2.hip
 
-// second-generation kernels for bf16 operands (ffmid2.hip: column strips, fused backward)
-bool ffmid2_supported(int Fp);
-int ffmid2_fwd_launch(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd, int M, int nseq,
-                      int F, int Fp, float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
-                      unsigned char* drop_bits, void* gh, int dtype, hipStream_t st, int seg_n_full, int seg_p0);
-int ffmid2_bwd_launch(const void* dh2, const void* h1, const void* convw, const void* gamma, const float* rstd, float* bc,
-                      void* dh1, float* part_g, int max_g_rows, float* part_c, int max_c_rows, int* g_rows, int* c_rows,
-                      int M, int nseq, int F, int Fp, float p, const unsigned char* drop_bits, const void* gh, int dtype, hipStream_t st);
-// 1 (default): the column-strip kernels (both operand dtypes) where their preconditions hold; 0: the wave-per-row kernels.  Set by
-// omlm_ffmid_set_impl (tests).  The two generations share every buffer layout; their dropout streams differ
-// (the keep-mask travels from forward to backward as drop_bits, so a step may not mix them only when drop_bits is null).
-static int g_ffmid_impl = 1;
+// this file's kernels of operand type T
+template <typename T>
+static int ffmid_launch_t(const FfmidLaunch& l, const FfmidArgs& a, float* part_g, float* part_c) {
+    const hipStream_t st = as_stream(a.stream);
+    const dim3 grid(l.gx, l.gy), block(l.threads);
+    switch (l.kernel) {
+    case FK_FWD1: {
+#define FF_FWD(MC_) launch_lds_optin<ffmid_fwd_kernel<T, MC_>>(grid, block, (size_t)l.lds, st, (const T*)a.h1, (const T*)a.convw, (const T*)a.gamma, (T*)a.h2, a.mean, a.rstd, \
+                                                               a.M, a.nseq, a.F, a.Fp, a.eps, a.p, a.seed, a.seed_dev, a.drop_bits, (T*)a.gh)
+        switch (l.n) { case 2: FF_FWD(2); break; case 6: FF_FWD(6); break; case 8: FF_FWD(8); break; default: FF_FWD(16); break; }
+#undef FF_FWD
+        return omlm_post_launch("omlm_ffmid_fwd");
+    }
+    case FK_BWD1: {
+#define FF_B1G(MC_, GH_) launch_lds_optin<ffmid_bwd1_kernel<T, MC_, GH_>>(grid, block, (size_t)l.lds, st, (const T*)a.dh2, (const T*)a.h1, (const T*)a.convw, (const T*)a.gamma, \
+                             (const float*)a.mean, (const float*)a.rstd, (T*)a.du_tmp, part_g, a.M, a.nseq, a.F, a.Fp, a.p, a.seed, a.seed_dev, \
+                             (const unsigned char*)a.drop_bits, (const T*)a.gh)
+#define FF_B1(MC_) do { if (l.gh) FF_B1G(MC_, true); else FF_B1G(MC_, false); } while (0)
+        switch (l.n) { case 2: FF_B1(2); break; case 6: FF_B1(6); break; case 8: FF_B1(8); break; default: FF_B1(16); break; }
+#undef FF_B1
+#undef FF_B1G
+        return omlm_post_launch("omlm_ffmid_bwd (row pass)");
+    }
+    default:        // FK_BWD2
+        hipLaunchKernelGGL(ffmid_bwd2_kernel<T>, grid, block, 0, st, (const T*)a.du_tmp, (const T*)a.h1, (const T*)a.convw, (T*)a.dh1, part_c, a.M, a.nseq, a.F, a.Fp);
+        return omlm_post_launch("omlm_ffmid_bwd");
+    }
+}
+
+// one launch of the plan: this file's kernels, the column sums behind a backward, or ffmid2.hip's kernels
+static int ffmid_launch(const FfmidLaunch& l, const FfmidArgs& a) {
+    float* part_g = a.workspace;
+    float* part_c = a.workspace ? a.workspace + ffmid_ws_dconv_at(a.Fp) : nullptr;     // (the forwards have no workspace)
+    switch (l.kernel) {
+    case FK_FWD1: case FK_BWD1: case FK_BWD2:
 #if !OMLM_FP16
-extern "C" int omlm_ffmid_set_impl_h(int impl);
+        if (!l.t16) return ffmid_launch_t<float>(l, a, part_g, part_c);
 #endif
-extern "C" int OMLM_API(omlm_ffmid_set_impl)(int impl) {
-    OMLM_CHECK_ARG(impl == 0 || impl == 1, "impl: 0 = wave-per-row, 1 = column strips");
-    g_ffmid_impl = impl;
-#if !OMLM_FP16
-    return omlm_ffmid_set_impl_h(impl);         // the fp16 copy of this file keeps its own switch
-#else
+        return ffmid_launch_t<h16_t>(l, a, part_g, part_c);
+    // the partial rows the backward kernels left, summed into dgamma / dconv (+=)
+    case FK_COLSUM_GROUP: {
+        const omlm_colsum_desc two[2] = {{part_g, a.dgamma, l.g_rows, a.F, a.Fp}, {part_c, a.dconv, l.c_rows, 2 * a.F * 3, 2 * a.F * 3}};
+        return omlm_colsum_group(two, 2, a.stream);
+    }
+    case FK_COLSUM_G: return omlm_colsum_accumulate(part_g, a.dgamma, l.g_rows, a.F, a.Fp, a.stream);
+    case FK_COLSUM_C: return omlm_colsum_accumulate(part_c, a.dconv, l.c_rows, 2 * a.F * 3, 2 * a.F * 3, a.stream);
+    default: return ffmid2_launch(l, a);
+    }
+}
+
+// plan, then launch in order
+static int ffmid_run(const FfmidCall& c, const FfmidArgs& a) {
+    const FfmidPlan plan = ffmid_plan(c);
+    if (plan.rc != OMLM_OK) { omlm_set_error(plan.msg); return plan.rc; }
+    for (int i = 0; i < plan.n; ++i) {
+        const int rc = ffmid_launch(plan.l[i], a);
+        if (rc) return rc;
+    }
     return OMLM_OK;
-#endif
 }
-static int ffmid_impl() { return g_ffmid_impl; }
 
+// 1 (default): the column-strip kernels (both operand dtypes) where their preconditions hold; 0: the wave-per-row kernels.  Set by
+// omlm_ffmid_set_impl (tests); one variable for the library, read once per call into FfmidCall.  The two generations share every buffer
+// layout; their dropout streams differ (the keep-mask travels from forward to backward as drop_bits, so a step may not mix them only when
+// drop_bits is null).
 #if !OMLM_FP16
-extern "C" long long omlm_ffmid_bwd_workspace_bytes(int F, int Fp) {
-    return (long long)sizeof(float) * ((long long)FF_BWD1_BLOCKS * Fp + (long long)FF_BWD2_STRIPS * 2 * F * 3);
+extern "C" { __attribute__((visibility("hidden"))) int omlm_ffmid_impl_value = 1; }
+extern "C" int omlm_ffmid_set_impl(int impl) {
+    OMLM_CHECK_ARG(impl == 0 || impl == 1, "impl: 0 = wave-per-row, 1 = column strips");
+    omlm_ffmid_impl_value = impl;
+    return OMLM_OK;
 }
+extern "C" long long omlm_ffmid_bwd_workspace_bytes(int F, int Fp) { return ffmid_bwd_workspace_bytes(F, Fp); }
+#else
+extern "C" { extern __attribute__((visibility("hidden"))) int omlm_ffmid_impl_value; }
 #endif
+
+// the call of an entry whose arguments are in `a`; operands: every pointer the entry requires is there
+static FfmidCall ffmid_call(FfOp op, const FfmidArgs& a, int dtype, bool operands) {
+    FfmidCall c;
+    memset(&c, 0, sizeof(c));
+    c.op = op; c.M = a.M; c.nseq = a.nseq; c.F = a.F; c.Fp = a.Fp; c.dtype = dtype; c.fp16_copy = OMLM_FP16 != 0; c.p = a.p; c.operands = operands;
+    c.drop_bits = a.drop_bits != nullptr; c.gh = a.gh != nullptr; c.dgamma = a.dgamma != nullptr; c.dconv = a.dconv != nullptr;
+    c.n_full = a.n_full; c.p0 = a.p0; c.h2_8_stride = a.h2_8_stride; c.impl = omlm_ffmid_impl_value;
+    return c;
+}
+static bool ffmid_aligned16(std::initializer_list<const void*> ps) {
+    uintptr_t all = 0;
+    for (const void* q : ps) all |= (uintptr_t)q;
+    return all % 16 == 0;
+}
 
 // dtype: 0 = fp32 operands ("bf16x3"), 1 = bf16, 2 = fp16 (forwarded to the fp16 copy of this file)
 // Every forward entry exists in a `_seg` form that carries a row segment (n_full, p0; n_full == 0: none): the buffers hold rows [p0, n_full)
 // of every sample compact (nseq = n_full - p0), and the strip kernels draw the keep bits those rows have in a launch over the full buffer
 // (a compact launch then drops exactly what the full launch drops for the same tokens).  The plain entries are the `_seg` ones without a segment.
-#define FF_CHECK_SEG(n_full, p0, nseq) OMLM_CHECK_ARG((n_full) == 0 || ((p0) > 0 && (p0) + (nseq) == (n_full)), "row segment: nseq must be n_full - p0, p0 > 0")
 #if !OMLM_FP16
 extern "C" int omlm_ffmid_fwd_seg_h(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
                                     int M, int nseq, int F, int Fp, float eps, float p, unsigned long long seed,
@@ -638,38 +696,13 @@ extern "C" int OMLM_API(omlm_ffmid_fwd_seg)(const void* h1, const void* convw, c
                               const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, int n_full, int p0, void* stream) {
 #if !OMLM_FP16
     if (dtype == OMLM_DT_F16) return omlm_ffmid_fwd_seg_h(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, 1, n_full, p0, stream);
-#else
-    OMLM_CHECK_ARG(dtype == 1, "the fp16 copy serves fp16 operands only");
 #endif
-    if (M <= 0) return OMLM_OK;
-    FF_CHECK_SEG(n_full, p0, nseq);
-    OMLM_CHECK_ARG(h1 && convw && gamma && h2 && mean && rstd, "null pointer");
-    OMLM_CHECK_ARG(Fp % 8 == 0 && Fp >= F && Fp <= 8192 && (size_t)5 * Fp * sizeof(float) <= 160 * 1024, "Fp must be F rounded up to 8 and <= 8192");
-    OMLM_CHECK_ARG(nseq > 0 && M % nseq == 0, "M must be batch * nseq");
-    OMLM_CHECK_ARG(p >= 0.f && p < 1.f, "dropout p");
-    hipStream_t st = as_stream(stream);
-    if (ffmid_impl() == 1 && ffmid2_supported(Fp) && (p == 0.f || drop_bits))
-        return ffmid2_fwd_launch(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, dtype, st, n_full, p0);
-    // (the wave-per-row kernels below know no segment: their mask is a function of the compact row -- still one mask for forward and backward)
-    const int rows4 = (M + 3) / 4;
-    dim3 grid(rows4 < 4096 ? rows4 : 4096), block(FF_THREADS);
-    const size_t lds_fwd = (size_t)4 * Fp * sizeof(float);
-    if (lds_fwd > 48 * 1024) {
-#if !OMLM_FP16
-        (void)hipFuncSetAttribute((const void*)ffmid_fwd_kernel<float, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)ffmid_fwd_kernel<float, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-#endif
-        (void)hipFuncSetAttribute((const void*)ffmid_fwd_kernel<h16_t, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)ffmid_fwd_kernel<h16_t, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
-#define FF_FWD(T_, MC_) hipLaunchKernelGGL((ffmid_fwd_kernel<T_, MC_>), grid, block, lds_fwd, st, (const T_*)h1, (const T_*)convw, (const T_*)gamma, (T_*)h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, (T_*)gh)
-#define FF_FWD_DISPATCH(T_) do { const int mc = (Fp / 8 + 63) / 64; \
-        if (mc <= 2) FF_FWD(T_, 2); else if (mc <= 6) FF_FWD(T_, 6); else if (mc <= 8) FF_FWD(T_, 8); else FF_FWD(T_, 16); } while (0)
-#if !OMLM_FP16
-    if (dtype == 0) FF_FWD_DISPATCH(float); else
-#endif
-    FF_FWD_DISPATCH(h16_t);
-    return omlm_post_launch("omlm_ffmid_fwd");
+    FfmidArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h1 = h1; a.convw = convw; a.gamma = gamma; a.h2 = h2; a.mean = mean; a.rstd = rstd;
+    a.M = M; a.nseq = nseq; a.F = F; a.Fp = Fp; a.eps = eps; a.p = p; a.seed = seed; a.seed_dev = seed_dev; a.drop_bits = drop_bits; a.gh = gh;
+    a.n_full = n_full; a.p0 = p0; a.stream = stream;
+    return ffmid_run(ffmid_call(FF_FWD, a, dtype, h1 && convw && gamma && h2 && mean && rstd), a);
 }
 #if !OMLM_FP16
 extern "C" int omlm_ffmid_fwd(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
@@ -682,10 +715,6 @@ extern "C" int omlm_ffmid_fwd(const void* h1, const void* convw, const void* gam
 // The same forward on hi/lo planes of the 16-bit type `dtype` (1 = bf16, 2 = fp16; precision "fp16ff"): h1, the conv taps and gamma are read
 // as hi + lo (each *_lo plane has its hi plane's layout), h2 leaves as planes h2 = rne16(y), h2_lo = rne16(y - h2); gh, the statistics and
 // the keep bits as in omlm_ffmid_fwd.  The strip kernels only (Fp <= 4096, drop_bits present when p > 0).
-int ffmid2_fwd_planes_launch(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
-                             void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp, float eps, float p,
-                             unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st,
-                             int seg_n_full, int seg_p0);
 #if !OMLM_FP16
 extern "C" int omlm_ffmid_fwd_planes_seg_h(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
                                            void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp, float eps, float p,
@@ -701,17 +730,14 @@ extern "C" int OMLM_API(omlm_ffmid_fwd_planes_seg)(const void* h1, const void* h
         return omlm_ffmid_fwd_planes_seg_h(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, 1,
                                            n_full, p0, stream);
 #endif
-    OMLM_CHECK_ARG(dtype == 1, "ffmid_fwd_planes: dtype 1 (bf16) or 2 (fp16)");
-    if (M <= 0) return OMLM_OK;
-    FF_CHECK_SEG(n_full, p0, nseq);
-    OMLM_CHECK_ARG(h1 && h1_lo && convw && convw_lo && gamma && gamma_lo && h2 && h2_lo && mean && rstd, "null pointer");
-    OMLM_CHECK_ARG(Fp % 8 == 0 && Fp >= F && ffmid2_supported(Fp), "ffmid_fwd_planes: Fp must be F rounded up to 8 and <= 4096");
-    OMLM_CHECK_ARG(nseq > 0 && M % nseq == 0, "M must be batch * nseq");
-    OMLM_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || drop_bits), "dropout p (keep bits required when p > 0)");
-    OMLM_CHECK_ARG((((uintptr_t)h1 | (uintptr_t)h1_lo | (uintptr_t)convw | (uintptr_t)convw_lo | (uintptr_t)gamma | (uintptr_t)gamma_lo |
-                     (uintptr_t)h2 | (uintptr_t)h2_lo) % 16) == 0, "ffmid_fwd_planes: 16-byte aligned planes");
-    return ffmid2_fwd_planes_launch(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev,
-                                    drop_bits, gh, as_stream(stream), n_full, p0);
+    FfmidArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h1 = h1; a.h1_lo = h1_lo; a.convw = convw; a.convw_lo = convw_lo; a.gamma = gamma; a.gamma_lo = gamma_lo; a.h2 = h2; a.h2_lo = h2_lo;
+    a.mean = mean; a.rstd = rstd; a.M = M; a.nseq = nseq; a.F = F; a.Fp = Fp; a.eps = eps; a.p = p; a.seed = seed; a.seed_dev = seed_dev;
+    a.drop_bits = drop_bits; a.gh = gh; a.n_full = n_full; a.p0 = p0; a.stream = stream;
+    FfmidCall c = ffmid_call(FF_FWD_PLANES, a, dtype, h1 && h1_lo && convw && convw_lo && gamma && gamma_lo && h2 && h2_lo && mean && rstd);
+    c.planes_aligned = ffmid_aligned16({h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo});
+    return ffmid_run(c, a);
 }
 #if !OMLM_FP16
 extern "C" int omlm_ffmid_fwd_planes(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma,
@@ -725,30 +751,22 @@ extern "C" int omlm_ffmid_fwd_planes(const void* h1, const void* h1_lo, const vo
 
 #if OMLM_FP16
 // The plane forward with h2 leaving in omlm_gemm_mx16's operand form (round 6): the half hi plane h2 [M, Fp], fp8 planes [hi8 | lo8] at row pitch
-// 2 Fp bytes (the lo8 plane h2_8_stride bytes behind the hi8 plane) and one E8M0 scale byte per row; everything else as omlm_ffmid_fwd_planes.
-int ffmid2_fwd_mx_launch(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
-                         void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
-                         float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st,
-                         int seg_n_full, int seg_p0);
+// 2 Fp bytes (the lo8 plane h2_8_stride bytes behind the hi8 plane) and one E8M0 scale byte per row; h1's lo plane arrives as bf8 bytes
+// (h1_lo, at h1's element pitch: what omlm_gemm_mx16 writes with c_lo_bf8); everything else as omlm_ffmid_fwd_planes.
 }   // namespace OMLM_NS
 extern "C" int omlm_ffmid_fwd_mx_seg(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
                                  void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
                                  float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh,
                                  int n_full, int p0, void* stream) {
     using namespace OMLM_NS;
-    if (M <= 0) return OMLM_OK;
-    FF_CHECK_SEG(n_full, p0, nseq);
-    OMLM_CHECK_ARG(h1 && h1_lo && convw && convw_lo && gamma && gamma_lo && h2 && h2_8 && scale8 && mean && rstd, "null pointer");
-    OMLM_CHECK_ARG(Fp % 8 == 0 && Fp >= F && ffmid2_supported(Fp), "ffmid_fwd_mx: Fp must be F rounded up to 8 and <= 4096");
-    OMLM_CHECK_ARG(nseq > 0 && M % nseq == 0, "M must be batch * nseq");
-    OMLM_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || drop_bits), "dropout p (keep bits required when p > 0)");
-    OMLM_CHECK_ARG(h2_8_stride >= (long long)M * 2 * Fp && h2_8_stride % 16 == 0, "ffmid_fwd_mx: fp8 plane stride");
-    // the kernel zeroes every fp8 row out to a whole 128-byte k-tile: the row pitch 2 Fp must hold it (Fp >= 64)
-    OMLM_CHECK_ARG(2 * Fp >= (Fp + 127) / 128 * 128, "ffmid_fwd_mx: an fp8 plane row (pitch 2 * Fp bytes) must hold Fp rounded up to 128 bytes");
-    OMLM_CHECK_ARG((((uintptr_t)h1 | (uintptr_t)h1_lo | (uintptr_t)convw | (uintptr_t)convw_lo | (uintptr_t)gamma | (uintptr_t)gamma_lo |
-                     (uintptr_t)h2 | (uintptr_t)h2_8) % 16) == 0, "ffmid_fwd_mx: 16-byte aligned planes");
-    return ffmid2_fwd_mx_launch(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_8, h2_8_stride, scale8, mean, rstd, M, nseq, F, Fp, eps, p, seed,
-                                seed_dev, drop_bits, gh, as_stream(stream), n_full, p0);
+    FfmidArgs a;
+    memset(&a, 0, sizeof(a));
+    a.h1 = h1; a.h1_lo = h1_lo; a.convw = convw; a.convw_lo = convw_lo; a.gamma = gamma; a.gamma_lo = gamma_lo; a.h2 = h2; a.h2_8 = h2_8;
+    a.h2_8_stride = h2_8_stride; a.scale8 = scale8; a.mean = mean; a.rstd = rstd; a.M = M; a.nseq = nseq; a.F = F; a.Fp = Fp; a.eps = eps; a.p = p;
+    a.seed = seed; a.seed_dev = seed_dev; a.drop_bits = drop_bits; a.gh = gh; a.n_full = n_full; a.p0 = p0; a.stream = stream;
+    FfmidCall c = ffmid_call(FF_FWD_MX, a, 1, h1 && h1_lo && convw && convw_lo && gamma && gamma_lo && h2 && h2_8 && scale8 && mean && rstd);
+    c.planes_aligned = ffmid_aligned16({h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_8});
+    return ffmid_run(c, a);
 }
 extern "C" int omlm_ffmid_fwd_mx(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
                                  void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
@@ -778,67 +796,15 @@ extern "C" int OMLM_API(omlm_ffmid_bwd)(const void* dh2, const void* h1, const v
     if (dtype == OMLM_DT_F16)
         return omlm_ffmid_bwd_h(dh2, h1, convw, gamma, mean, rstd, du_tmp, dh1, dgamma, dconv, workspace, M, nseq, F, Fp, p, seed, seed_dev,
                                 drop_bits, gh, 1, stream);
-#else
-    OMLM_CHECK_ARG(dtype == 1, "the fp16 copy serves fp16 operands only");
 #endif
-    if (M <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(dh2 && h1 && convw && gamma && mean && rstd && du_tmp && dh1 && workspace, "null pointer");
-    OMLM_CHECK_ARG(Fp % 8 == 0 && Fp >= F && Fp <= 8192 && (size_t)5 * Fp * sizeof(float) <= 160 * 1024, "Fp must be F rounded up to 8 and <= 8192");
-    OMLM_CHECK_ARG(nseq > 0 && M % nseq == 0, "M must be batch * nseq");
-    hipStream_t st = as_stream(stream);
-    float* part_g = workspace;
-    float* part_c = workspace + (size_t)FF_BWD1_BLOCKS * Fp;
-    if (ffmid_impl() == 1 && ffmid2_supported(Fp) && gh && (p == 0.f || drop_bits)) {
-        // du_tmp is not needed by the fused kernel: its first M * 2 floats carry the per-row LayerNorm^T sums
-        OMLM_CHECK_ARG(((uintptr_t)du_tmp % 8) == 0, "du_tmp must be 8-byte aligned");
-        int g_rows = 0, c_rows = 0;
-        int rc2 = ffmid2_bwd_launch(dh2, h1, convw, gamma, rstd, (float*)du_tmp, dh1, part_g, FF_BWD1_BLOCKS, part_c, FF_BWD2_STRIPS,
-                                    &g_rows, &c_rows, M, nseq, F, Fp, p, drop_bits, gh, dtype, st);
-        if (rc2) return rc2;
-        if (dgamma && dconv) {
-            const omlm_colsum_desc two[2] = {{part_g, dgamma, g_rows, F, Fp}, {part_c, dconv, c_rows, 2 * F * 3, 2 * F * 3}};
-            return omlm_colsum_group(two, 2, stream);
-        }
-        if (dgamma) { rc2 = omlm_colsum_accumulate(part_g, dgamma, g_rows, F, Fp, stream); if (rc2) return rc2; }
-        if (dconv)  { rc2 = omlm_colsum_accumulate(part_c, dconv, c_rows, 2 * F * 3, 2 * F * 3, stream); if (rc2) return rc2; }
-        return OMLM_OK;
-    }
-    const int rows4 = (M + 3) / 4;
-    const int b1 = rows4 < FF_BWD1_BLOCKS ? rows4 : FF_BWD1_BLOCKS;
-    const int strips = M < FF_BWD2_STRIPS ? M : FF_BWD2_STRIPS;
-    dim3 g2((2 * Fp / 8 + FF_THREADS - 1) / FF_THREADS, strips);
-    const size_t lds1 = (size_t)4 * Fp * sizeof(float);
-#define FF_B1_ATTR(T_, MC_) do { (void)hipFuncSetAttribute((const void*)ffmid_bwd1_kernel<T_, MC_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        (void)hipFuncSetAttribute((const void*)ffmid_bwd1_kernel<T_, MC_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); } while (0)
-    if (lds1 > 48 * 1024) {
-#if !OMLM_FP16
-        FF_B1_ATTR(float, 6); FF_B1_ATTR(float, 8); FF_B1_ATTR(float, 16);
-#endif
-        FF_B1_ATTR(h16_t, 6); FF_B1_ATTR(h16_t, 8); FF_B1_ATTR(h16_t, 16);
-    }
-#define FF_B1G(T_, MC_, GH_) hipLaunchKernelGGL((ffmid_bwd1_kernel<T_, MC_, GH_>), dim3(b1), dim3(FF_THREADS), lds1, st, (const T_*)dh2, (const T_*)h1, (const T_*)convw, (const T_*)gamma, mean, rstd, (T_*)du_tmp, part_g, M, nseq, F, Fp, p, seed, seed_dev, drop_bits, (const T_*)gh)
-#define FF_B1(T_, MC_) do { if (gh) FF_B1G(T_, MC_, true); else FF_B1G(T_, MC_, false); } while (0)
-#define FF_B1_DISPATCH(T_) do { const int mc = (Fp / 8 + 63) / 64; \
-        if (mc <= 2) FF_B1(T_, 2); else if (mc <= 6) FF_B1(T_, 6); else if (mc <= 8) FF_B1(T_, 8); else FF_B1(T_, 16); } while (0)
-#if !OMLM_FP16
-    if (dtype == 0) {
-        FF_B1_DISPATCH(float);
-        hipLaunchKernelGGL(ffmid_bwd2_kernel<float>, g2, dim3(FF_THREADS), 0, st, (const float*)du_tmp, (const float*)h1, (const float*)convw, (float*)dh1, part_c, M, nseq, F, Fp);
-    } else
-#endif
-    {
-        FF_B1_DISPATCH(h16_t);
-        hipLaunchKernelGGL(ffmid_bwd2_kernel<h16_t>, g2, dim3(FF_THREADS), 0, st, (const h16_t*)du_tmp, (const h16_t*)h1, (const h16_t*)convw, (h16_t*)dh1, part_c, M, nseq, F, Fp);
-    }
-    int rc = omlm_post_launch("omlm_ffmid_bwd");
-    if (rc) return rc;
-    if (dgamma && dconv) {
-        const omlm_colsum_desc two[2] = {{part_g, dgamma, b1, F, Fp}, {part_c, dconv, strips, 2 * F * 3, 2 * F * 3}};
-        return omlm_colsum_group(two, 2, stream);
-    }
-    if (dgamma) { rc = omlm_colsum_accumulate(part_g, dgamma, b1, F, Fp, stream); if (rc) return rc; }
-    if (dconv)  { rc = omlm_colsum_accumulate(part_c, dconv, strips, 2 * F * 3, 2 * F * 3, stream); if (rc) return rc; }
-    return OMLM_OK;
+    FfmidArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dh2 = dh2; a.h1 = h1; a.convw = convw; a.gamma = gamma; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd);      // (read only here)
+    a.du_tmp = du_tmp; a.dh1 = dh1; a.dgamma = dgamma; a.dconv = dconv; a.workspace = workspace; a.M = M; a.nseq = nseq; a.F = F; a.Fp = Fp; a.p = p;
+    a.seed = seed; a.seed_dev = seed_dev; a.drop_bits = const_cast<unsigned char*>(drop_bits); a.gh = const_cast<void*>(gh); a.stream = stream;
+    FfmidCall c = ffmid_call(FF_BWD, a, dtype, dh2 && h1 && convw && gamma && mean && rstd && du_tmp && dh1 && workspace);
+    c.du_aligned = (uintptr_t)du_tmp % 8 == 0;
+    return ffmid_run(c, a);
 }
 
 }   // namespace OMLM_NS

@@ -20,9 +20,11 @@
 //     d(conv taps) in ONE pass, du never exists in memory (first generation: bwd1 wrote it, bwd2 re-read it: 0.8 GB per
 //     layer).  conv^T runs as two pending output rows in registers; a strip recomputes du for the 2 rows past its end.
 #include "common.h"
+#include "ffmid_plan.h"
 #include <type_traits>
 
 namespace OMLM_NS {
+using namespace omlm_plan;
 
 typedef f32x2 v2;
 
@@ -838,155 +840,80 @@ __global__ __launch_bounds__(NT) void ffmid3_bwd_kernel(const T* __restrict__ dh
     }
 }
 
-// ---- host side (called by the C-ABI entry points of ffmid.hip) ----------------------------------------------------------
-static int strip_rows(int nseq, int target) {
-    const int n = (nseq + target - 1) / target;
-    return (nseq + n - 1) / n;
-}
-
-bool ffmid2_supported(int Fp) { return Fp % 8 == 0 && Fp / 8 <= 512; }
-
-template <typename T, bool PL = false, bool MX = false>
-static int fwd_launch_t(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd, int M, int nseq,
-                        int F, int Fp, float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
-                        unsigned char* drop_bits, void* gh, hipStream_t st, int seg_n_full, int seg_p0,
-                        const FfPlanes pl = FfPlanes{0, 0, 0, nullptr, nullptr, 0, nullptr, nullptr}) {
-    const int B = M / nseq;
-    // a segment changes nothing but the keep bits drawn: without dropout the plain kernels serve it
-    const bool segd = seg_n_full > 0 && p > 0.f;
-    const FfSeg seg{seg_n_full, seg_p0};
-    const int RB = strip_rows(nseq, 36);
-    const int strips = (nseq + RB - 1) / RB;
-    const int nt = ((Fp / 8 + 63) / 64) * 64;                                  // kernel instantiation: whole waves
-    const int nthr = Fp / 8;                                                   // threads launched: one per chunk
-    dim3 grid(B * strips);
-    const bool train = p > 0.f && drop_bits != nullptr && gh != nullptr;       // the training call: all three row stores are unconditional
-#define FF2_FWD(NT_) do { if (segd && train) hipLaunchKernelGGL((ffmid2_fwd_seg_kernel<T, NT_, true, PL, MX>), grid, dim3(nthr), 0, st, (const T*)h1, (const T*)convw, \
-        (const T*)gamma, (T*)h2, mean, rstd, nseq, F, Fp, RB, strips, eps, p, seed, seed_dev, drop_bits, (T*)gh, pl, seg); \
-    else if (segd) hipLaunchKernelGGL((ffmid2_fwd_seg_kernel<T, NT_, false, PL, MX>), grid, dim3(nthr), 0, st, (const T*)h1, (const T*)convw, \
-        (const T*)gamma, (T*)h2, mean, rstd, nseq, F, Fp, RB, strips, eps, p, seed, seed_dev, drop_bits, (T*)gh, pl, seg); \
-    else if (train) hipLaunchKernelGGL((ffmid2_fwd_kernel<T, NT_, true, PL, MX>), grid, dim3(nthr), 0, st, (const T*)h1, (const T*)convw, \
-        (const T*)gamma, (T*)h2, mean, rstd, nseq, F, Fp, RB, strips, eps, p, seed, seed_dev, drop_bits, (T*)gh, pl); \
-    else hipLaunchKernelGGL((ffmid2_fwd_kernel<T, NT_, false, PL, MX>), grid, dim3(nthr), 0, st, (const T*)h1, (const T*)convw, \
-        (const T*)gamma, (T*)h2, mean, rstd, nseq, F, Fp, RB, strips, eps, p, seed, seed_dev, drop_bits, (T*)gh, pl); } while (0)
-    switch (nt) {
-        case 64: FF2_FWD(64); break;
-        case 128: FF2_FWD(128); break;
-        case 192: FF2_FWD(192); break;
-        case 256: FF2_FWD(256); break;
-        case 320: FF2_FWD(320); break;
-        case 384: FF2_FWD(384); break;
-        case 448: FF2_FWD(448); break;
-        default: FF2_FWD(512); break;
-    }
+// ---- host side: the launcher of this file's kernels (csrc/ffmid_plan.h decides what it is handed; ffmid.hip's entries call it) --------------
+template <typename T, bool PL, bool MX>
+static void strip_fwd_go(const FfmidLaunch& l, const FfmidArgs& a, const FfPlanes& pl) {
+    const hipStream_t st = as_stream(a.stream);
+    const dim3 grid(l.gx, l.gy), block(l.threads);
+    const FfSeg seg{a.n_full, a.p0};
+#define FF2_FWD(K_, NT_, ...) do { \
+        if (l.train) hipLaunchKernelGGL((K_<T, NT_, true, PL, MX>), grid, block, 0, st, (const T*)a.h1, (const T*)a.convw, (const T*)a.gamma, (T*)a.h2, a.mean, a.rstd, \
+                                        a.nseq, a.F, a.Fp, l.RB, l.strips, a.eps, a.p, a.seed, a.seed_dev, a.drop_bits, (T*)a.gh, pl, ##__VA_ARGS__); \
+        else hipLaunchKernelGGL((K_<T, NT_, false, PL, MX>), grid, block, 0, st, (const T*)a.h1, (const T*)a.convw, (const T*)a.gamma, (T*)a.h2, a.mean, a.rstd, \
+                                a.nseq, a.F, a.Fp, l.RB, l.strips, a.eps, a.p, a.seed, a.seed_dev, a.drop_bits, (T*)a.gh, pl, ##__VA_ARGS__); } while (0)
+#define FF2_FWD_NT(K_, ...) switch (l.n) { \
+        case 64: FF2_FWD(K_, 64, ##__VA_ARGS__); break; case 128: FF2_FWD(K_, 128, ##__VA_ARGS__); break; case 192: FF2_FWD(K_, 192, ##__VA_ARGS__); break; \
+        case 256: FF2_FWD(K_, 256, ##__VA_ARGS__); break; case 320: FF2_FWD(K_, 320, ##__VA_ARGS__); break; case 384: FF2_FWD(K_, 384, ##__VA_ARGS__); break; \
+        case 448: FF2_FWD(K_, 448, ##__VA_ARGS__); break; default: FF2_FWD(K_, 512, ##__VA_ARGS__); break; }
+    if (l.kernel == FK_STRIP_FWD_SEG) FF2_FWD_NT(ffmid2_fwd_seg_kernel, seg)
+    else FF2_FWD_NT(ffmid2_fwd_kernel)
+#undef FF2_FWD_NT
 #undef FF2_FWD
-    return omlm_post_launch("omlm_ffmid_fwd (strip)");
 }
 
-// dtype: 0 = fp32 operands ("bf16x3" mode), 1 = bf16
-int ffmid2_fwd_launch(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd, int M, int nseq,
-                      int F, int Fp, float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
-                      unsigned char* drop_bits, void* gh, int dtype, hipStream_t st, int seg_n_full, int seg_p0) {
-#if !OMLM_FP16
-    if (dtype == 0) return fwd_launch_t<float>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st, seg_n_full, seg_p0);
-#endif
-    return fwd_launch_t<h16_t>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st, seg_n_full, seg_p0);
-}
-
-// the same forward on hi/lo planes of the 16-bit type (omlm_ffmid_fwd_planes): h1, taps and gamma are read as hi + lo, h2 leaves as planes
-int ffmid2_fwd_planes_launch(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
-                             void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp, float eps, float p,
-                             unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st,
-                             int seg_n_full, int seg_p0) {
-    FfPlanes pl;
-    pl.h1_lo = (const h16_t*)h1_lo - (const h16_t*)h1;
-    pl.convw_lo = (const h16_t*)convw_lo - (const h16_t*)convw;
-    pl.gamma_lo = (const h16_t*)gamma_lo - (const h16_t*)gamma;
-    pl.h2_lo = h2_lo;
-    pl.h2_8 = nullptr; pl.h2_8_stride = 0; pl.scale8 = nullptr; pl.h1_8 = nullptr;
-    return fwd_launch_t<h16_t, true>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st, seg_n_full, seg_p0, pl);
-}
-
-#if OMLM_FP16
-// the plane forward with h2 leaving in omlm_gemm_mx16's operand form: half hi plane + fp8 planes [hi8 | lo8] (row pitch 2 Fp bytes) + row scales;
-// h1's lo plane arrives as bf8 bytes (h1_lo8, at h1's element pitch: what omlm_gemm_mx16 writes with c_lo_bf8)
-int ffmid2_fwd_mx_launch(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
-                         void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
-                         float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, hipStream_t st,
-                         int seg_n_full, int seg_p0) {
-    FfPlanes pl;
-    pl.h1_lo = 0;
-    pl.h1_8 = (const unsigned char*)h1_lo;
-    pl.convw_lo = (const h16_t*)convw_lo - (const h16_t*)convw;
-    pl.gamma_lo = (const h16_t*)gamma_lo - (const h16_t*)gamma;
-    pl.h2_lo = nullptr;
-    pl.h2_8 = (unsigned char*)h2_8; pl.h2_8_stride = h2_8_stride; pl.scale8 = scale8;
-    return fwd_launch_t<h16_t, true, true>(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, st, seg_n_full, seg_p0, pl);
-}
-#endif
-
-// bc: [M][2] floats of scratch; part_g: [>= rowsum blocks][Fp]; part_c: [>= NY][2F*3]
 template <typename T>
-static int bwd_launch_t(const void* dh2, const void* h1, const void* convw, const void* gamma, const float* rstd, float* bc,
-                        void* dh1, float* part_g, int max_g_rows, float* part_c, int max_c_rows, int* g_rows, int* c_rows,
-                        int M, int nseq, int F, int Fp, float p, const unsigned char* drop_bits, const void* gh, hipStream_t st) {
-    const int B = M / nseq;
-    if (Fp / 4 <= 768) {
-        // one pass: a workgroup covers all channels of its rows (ffmid3_bwd_kernel); `bc` is not used
-        const int RB = strip_rows(nseq, 35);
-        const int strips = (nseq + RB - 1) / RB;
-        const int total = B * strips;
-        const int per = (total + 255) / 256;                 // strips per workgroup: one workgroup of 8-12 waves per CU
-        int ny = (total + per - 1) / per;
-        if (ny > max_c_rows) ny = max_c_rows;
-        if (ny > max_g_rows) ny = max_g_rows;
-        const int nthr = (Fp / 4 + 63) / 64 * 64;
-#define FF3_BWD(NT_) hipLaunchKernelGGL((ffmid3_bwd_kernel<T, NT_>), dim3(1, ny), dim3(NT_), 0, st, (const T*)dh2, (const T*)h1, (const T*)convw, \
-                       (const T*)gamma, rstd, (const T*)gh, drop_bits, (T*)dh1, part_c, part_g, nseq, F, Fp, RB, strips, total, p)
-        if (nthr <= 128) FF3_BWD(128); else if (nthr <= 256) FF3_BWD(256); else if (nthr <= 512) FF3_BWD(512); else FF3_BWD(768);
+static int ffmid2_launch_t(const FfmidLaunch& l, const FfmidArgs& a) {
+    const hipStream_t st = as_stream(a.stream);
+    const dim3 grid(l.gx, l.gy), block(l.threads);
+    float* part_g = a.workspace;
+    float* part_c = a.workspace ? a.workspace + ffmid_ws_dconv_at(a.Fp) : nullptr;     // (the forwards have no workspace)
+    float* bc = (float*)a.du_tmp;                  // two-pass backward: [M][2] row sums in the scratch the fused kernels do not need
+    switch (l.kernel) {
+    case FK_STRIP_FWD: case FK_STRIP_FWD_SEG: {
+        FfPlanes pl{0, 0, 0, nullptr, nullptr, 0, nullptr, nullptr};
+        if (!l.pl) strip_fwd_go<T, false, false>(l, a, pl);
+        else if constexpr (sizeof(T) == 2) {        // the taps and gamma are read as hi + lo; h1's lo plane as a plane of T, or -- MX -- as bf8 bytes at h1's element pitch
+            pl.convw_lo = (const T*)a.convw_lo - (const T*)a.convw;
+            pl.gamma_lo = (const T*)a.gamma_lo - (const T*)a.gamma;
+            if (!l.mx) {
+                pl.h1_lo = (const T*)a.h1_lo - (const T*)a.h1; pl.h2_lo = a.h2_lo;
+                strip_fwd_go<T, true, false>(l, a, pl);
+            }
+#if OMLM_FP16
+            else {
+                pl.h1_8 = (const unsigned char*)a.h1_lo; pl.h2_8 = (unsigned char*)a.h2_8; pl.h2_8_stride = a.h2_8_stride; pl.scale8 = a.scale8;
+                strip_fwd_go<T, true, true>(l, a, pl);
+            }
+#endif
+        }
+        return omlm_post_launch("omlm_ffmid_fwd (strip)");
+    }
+    case FK_BWD3: {             // one pass: a workgroup covers all channels of its rows; `bc` is not used
+#define FF3_BWD(NT_) hipLaunchKernelGGL((ffmid3_bwd_kernel<T, NT_>), grid, block, 0, st, (const T*)a.dh2, (const T*)a.h1, (const T*)a.convw, (const T*)a.gamma, \
+                       (const float*)a.rstd, (const T*)a.gh, (const unsigned char*)a.drop_bits, (T*)a.dh1, part_c, part_g, a.nseq, a.F, a.Fp, l.RB, l.strips, l.total, a.p)
+        switch (l.n) { case 128: FF3_BWD(128); break; case 256: FF3_BWD(256); break; case 512: FF3_BWD(512); break; default: FF3_BWD(768); break; }
 #undef FF3_BWD
-        *g_rows = ny;
-        *c_rows = ny;
         return omlm_post_launch("omlm_ffmid_bwd (fused strip)");
     }
-    // prepass
-    const int rows4 = (M + 3) / 4;
-    const int b1 = rows4 < max_g_rows ? rows4 : max_g_rows;
-    const size_t lds = (size_t)4 * Fp * sizeof(float);
-    const int mc = (Fp / 8 + 63) / 64;
-#define FF2_RS(MC_) do { if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)ffmid2_rowsum_kernel<T, MC_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        hipLaunchKernelGGL((ffmid2_rowsum_kernel<T, MC_>), dim3(b1), dim3(256), lds, st, (const T*)dh2, (const T*)gamma, (const T*)gh, \
-                           drop_bits, rstd, bc, part_g, M, F, Fp, p); } while (0)
-    if (mc <= 1) FF2_RS(1); else if (mc <= 2) FF2_RS(2); else if (mc <= 4) FF2_RS(4); else if (mc <= 6) FF2_RS(6); else FF2_RS(8);
-#undef FF2_RS
-    int rc = omlm_post_launch("omlm_ffmid_bwd (row sums)");
-    if (rc) return rc;
-    // main
-    const int RB = strip_rows(nseq, 35);
-    const int strips = (nseq + RB - 1) / RB;
-    const int total = B * strips;
-    int per = (total + 255) / 256;                       // strips per workgroup-y: ~3 workgroups of 4 waves per CU
-    int ny = (total + per - 1) / per;
-    if (ny > max_c_rows) ny = max_c_rows;
-    dim3 grid((Fp / 4 + 255) / 256, ny);
-    hipLaunchKernelGGL(ffmid2_bwd_kernel<T>, grid, dim3(256), 0, st, (const T*)dh2, (const T*)h1, (const T*)convw,
-                       (const T*)gamma, rstd, (const float*)bc, (const T*)gh, drop_bits, (T*)dh1, part_c,
-                       nseq, F, Fp, RB, strips, total, p);
-    *g_rows = b1;
-    *c_rows = ny;
-    return omlm_post_launch("omlm_ffmid_bwd (strip)");
+    case FK_ROWSUM:             // two passes: the rows' LayerNorm^T sums and d(gamma) first
+        launch_lds_optin<ffmid2_rowsum_kernel<T, FF_ROWSUM_MC>>(grid, block, (size_t)l.lds, st, (const T*)a.dh2, (const T*)a.gamma, (const T*)a.gh,
+                                                                 (const unsigned char*)a.drop_bits, (const float*)a.rstd, bc, part_g, a.M, a.F, a.Fp, a.p);
+        return omlm_post_launch("omlm_ffmid_bwd (row sums)");
+    case FK_STRIP_BWD:
+        hipLaunchKernelGGL(ffmid2_bwd_kernel<T>, grid, block, 0, st, (const T*)a.dh2, (const T*)a.h1, (const T*)a.convw, (const T*)a.gamma, (const float*)a.rstd,
+                           (const float*)bc, (const T*)a.gh, (const unsigned char*)a.drop_bits, (T*)a.dh1, part_c, a.nseq, a.F, a.Fp, l.RB, l.strips, l.total, a.p);
+        return omlm_post_launch("omlm_ffmid_bwd (strip)");
+    default:
+        omlm_set_error("omlm_ffmid: the plan names a kernel that ffmid2.hip does not build");
+        return OMLM_ERR_UNSUPPORTED;
+    }
 }
 
-int ffmid2_bwd_launch(const void* dh2, const void* h1, const void* convw, const void* gamma, const float* rstd, float* bc,
-                      void* dh1, float* part_g, int max_g_rows, float* part_c, int max_c_rows, int* g_rows, int* c_rows,
-                      int M, int nseq, int F, int Fp, float p, const unsigned char* drop_bits, const void* gh, int dtype, hipStream_t st) {
+int ffmid2_launch(const FfmidLaunch& l, const FfmidArgs& a) {
 #if !OMLM_FP16
-    if (dtype == 0)
-        return bwd_launch_t<float>(dh2, h1, convw, gamma, rstd, bc, dh1, part_g, max_g_rows, part_c, max_c_rows, g_rows, c_rows,
-                                   M, nseq, F, Fp, p, drop_bits, gh, st);
+    if (!l.t16) return ffmid2_launch_t<float>(l, a);
 #endif
-    return bwd_launch_t<h16_t>(dh2, h1, convw, gamma, rstd, bc, dh1, part_g, max_g_rows, part_c, max_c_rows, g_rows, c_rows,
-                                M, nseq, F, Fp, p, drop_bits, gh, st);
+    return ffmid2_launch_t<h16_t>(l, a);
 }
 
 }   // namespace OMLM_NS

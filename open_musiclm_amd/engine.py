@@ -62,7 +62,7 @@ _H16 = (torch.bfloat16, torch.float16)
 #   profiles/r06_error_budget_fp8corr.md.
 
 
-FF_PLANES_MAX_FP = 4096      # omlm_ffmid_fwd_planes / omlm_ffmid_fwd_mx: Fp <= 4096 (ffmid2_supported)
+FF_PLANES_MAX_FP = 4096      # omlm_ffmid_fwd_planes / omlm_ffmid_fwd_mx: Fp <= 4096 (csrc/ffmid_plan.h: ffmid_strip_ok; tests/test_ffmid_plan_host.py pins it)
 
 
 def ff_planes_ok(Fp: int) -> bool:
@@ -224,7 +224,7 @@ def build_layout(B: int, lens: Sequence[int], quantizers: Sequence[int], device,
 CONV_HALO = 2                # rows in front of a row that the causal depthwise conv reads (kernel size 3)
 LIVE_K_MULTIPLE = 64         # B * n_live is the K of the last layer's dW1 / dW2: the grouped weight-gradient launch keeps its SGPR-offset form
                              # only while every problem's K is a multiple of 64 (one ragged K slows the whole group)
-FF_ONE_PASS_MAX_FP = 3072    # Fp up to which the ConvFeedForward middle runs the strip forward and the one-pass backward (csrc/ffmid2.hip)
+FF_ONE_PASS_MAX_FP = 3072    # Fp up to which the ConvFeedForward middle runs the strip forward and the one-pass backward (csrc/ffmid_plan.h: ffmid_one_pass; pinned by the same test)
 
 
 def first_live_row(lay: SeqLayout, want: Sequence[bool]) -> Optional[int]:
