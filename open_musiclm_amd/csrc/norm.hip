@@ -4,11 +4,10 @@
 // Residual stream and statistics are fp32; the operand copies handed to the MFMA GEMMs are
 // written in the same pass in the GEMM operand type T (bf16, or fp32 for the bf16x3 mode).
 #include "common.h"
+#include "norm_plan.h"      // LN_THREADS, LN_MAXV, QKB_BLOCKS, QKB2_THREADS (the kernels are written against them), and every route
 
 namespace OMLM_NS {
-
-#define LN_THREADS 256
-#define LN_MAXV 4   // float4 pieces per thread  -> D <= 4096
+using namespace omlm_plan;
 
 // A row segment (the `_seg` entry points): rows [p0, n_full) of every sample of a [B * n_full, D] buffer, held compact as [B * n_live, D]
 // (n_live = n_full - p0): compact row r is full row (r / n_live) * n_full + p0 + r % n_live.  The forward kernels READ x at the mapped rows
@@ -37,8 +36,11 @@ __device__ __forceinline__ void seg_zero_dead(const LnSeg<true>& s, int M, int D
     }
 }
 template <typename T> __device__ __forceinline__ void seg_zero_dead(const LnSeg<false>&, int, int, float*, T*) {}
-#define LN_CHECK_SEG(M, n_full, p0, n_live) OMLM_CHECK_ARG((p0) > 0 && (n_live) > 0 && (p0) + (n_live) == (n_full) && (M) % (n_live) == 0, \
-                                                          "row segment: n_full = p0 + n_live, p0 > 0, M a multiple of n_live")
+// host: the kernels' segment argument from an entry's arguments (the backward passes no xc)
+template <bool SEG> static inline LnSeg<SEG> ln_seg(const NormArgs& a) {
+    if constexpr (SEG) return LnSeg<true>{a.n_full, a.p0, a.n_live, a.xc};
+    else return LnSeg<false>{};
+}
 
 // y = (x - mean) * rstd * gamma ; optionally also emit cast(x) (the K/V projection reads the
 // un-normalised residual: reference transformer.py:228 binds kv_input before the pre-norm :250).
@@ -255,38 +257,16 @@ __global__ __launch_bounds__(LN_THREADS) void ln_fwd_mx_kernel(const float* __re
         }
     }
 }
-}   // namespace OMLM_NS
-using namespace OMLM_NS;
-// y: half hi plane [M, ldy]; y8: fp8 planes [hi8 | lo8] at row pitch 2 ldy bytes, the lo8 plane y8_stride bytes behind the hi8 plane; scale8 [M]
+// host: y: half hi plane [M, ldy]; y8: fp8 planes [hi8 | lo8] at row pitch 2 ldy bytes, the lo8 plane y8_stride bytes behind the hi8 plane; scale8 [M]
 // E8M0 (include/omlm.h).  The hi plane and the statistics are omlm_layernorm_fwd's (bit for bit at D = 1024).
-// seg (the `_seg` entry): x is read at the segment's rows, every output is compact ([M, ..]); xc (optional): the fp32 source rows, compact
-static int layernorm_fwd_mx_run(const float* x, const float* gamma, void* y, void* y8, long long y8_stride, unsigned char* scale8,
-                                float* mean, float* rstd, int M, int D, int ldy, float eps, const LnSeg<true>* seg, void* stream) {
-    if (M <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(x && gamma && y && y8 && scale8 && mean && rstd, "null pointer");
-    OMLM_CHECK_ARG(D % 4 == 0 && D <= 4 * LN_THREADS * LN_MAXV, "D must be a multiple of 4 and <= 4096");
-    OMLM_CHECK_ARG(ldy >= D && ldy % 4 == 0 && y8_stride >= (long long)M * 2 * ldy, "ldy / plane stride");
-    // the kernel zeroes every fp8 row out to a whole 128-byte k-tile: the row pitch must hold it (else the tail runs into the next row)
-    OMLM_CHECK_ARG(2 * ldy >= (D + 127) / 128 * 128, "an fp8 plane row (pitch 2 * ldy bytes) must hold D rounded up to 128 bytes");
-    dim3 grid(M < 2048 ? M : 2048), block(LN_THREADS);
-#define LN_MX(MV_) do { if (seg) hipLaunchKernelGGL((ln_fwd_mx_kernel<MV_, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (unsigned char*)y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps, *seg); \
-        else hipLaunchKernelGGL((ln_fwd_mx_kernel<MV_, false>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (unsigned char*)y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps, LnSeg<false>{}); } while (0)
-    if (D <= 4 * LN_THREADS) LN_MX(1); else LN_MX(LN_MAXV);
-#undef LN_MX
-    return omlm_post_launch("omlm_layernorm_fwd_mx");
+static void ln_fwd_mx_launch(const NormLaunch& l, const NormArgs& a) {
+    with_flags(l.maxv == 1, l.seg, [&](auto one, auto seg) {
+        constexpr int MAXV = decltype(one)::value ? 1 : LN_MAXV;
+        constexpr bool SEG = decltype(seg)::value;
+        hipLaunchKernelGGL((ln_fwd_mx_kernel<MAXV, SEG>), dim3(l.gx), dim3(l.threads), 0, as_stream(a.stream), a.x, a.gamma, (h16_t*)a.y, (unsigned char*)a.y8,
+                           a.y8_stride, a.scale8, a.mean, a.rstd, a.M, a.D, a.ldy, a.eps, ln_seg<SEG>(a));
+    });
 }
-extern "C" int omlm_layernorm_fwd_mx(const float* x, const float* gamma, void* y, void* y8, long long y8_stride, unsigned char* scale8,
-                                     float* mean, float* rstd, int M, int D, int ldy, float eps, void* stream) {
-    return layernorm_fwd_mx_run(x, gamma, y, y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps, nullptr, stream);
-}
-extern "C" int omlm_layernorm_fwd_mx_seg(const float* x, const float* gamma, void* y, void* y8, long long y8_stride, unsigned char* scale8,
-                                         float* mean, float* rstd, float* xc, int M, int D, int ldy, float eps, int n_full, int p0, int n_live, void* stream) {
-    if (M <= 0) return OMLM_OK;
-    LN_CHECK_SEG(M, n_full, p0, n_live);
-    const LnSeg<true> seg{n_full, p0, n_live, xc};
-    return layernorm_fwd_mx_run(x, gamma, y, y8, y8_stride, scale8, mean, rstd, M, D, ldy, eps, &seg, stream);
-}
-namespace OMLM_NS {
 #endif
 
 // dx = dres + rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma ; dgamma += dy * xhat
@@ -473,174 +453,6 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_row1_kernel(const TDY* __re
     }
 }
 
-static int ln_grid(int M) { return M < 2048 ? M : 2048; }
-
-// The forward entries in their `_seg` form (include/omlm.h): n_full == 0 is "no segment", which is all the plain entries pass.  With a segment
-// x [.. n_full rows per sample] is read at the segment's rows, every output is compact ([M, ..]) and xc (optional) receives the fp32 source rows.
-#if !OMLM_FP16
-extern "C" int omlm_layernorm_fwd_seg_h(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd, float* xc, int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_layernorm_fwd_seg)(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd, float* xc,
-                                  int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream) {
-#if !OMLM_FP16
-    if (out_dtype == OMLM_DT_F16) return omlm_layernorm_fwd_seg_h(x, gamma, y, xcast, mean, rstd, xc, M, D, ldy, eps, 1, n_full, p0, n_live, stream);
-#endif
-    if (M <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(x && gamma && y, "null pointer");
-    OMLM_CHECK_ARG(D % 4 == 0 && D <= 4 * LN_THREADS * LN_MAXV, "D must be a multiple of 4 and <= 4096");
-    OMLM_CHECK_ARG(ldy >= D, "ldy < D");
-    dim3 grid(ln_grid(M)), block(LN_THREADS);
-    if (n_full != 0) {
-        LN_CHECK_SEG(M, n_full, p0, n_live);
-        OMLM_CHECK_ARG(mean && rstd && !xcast && out_dtype == 1, "layernorm_fwd_seg: statistics wanted, no cast copy of x, 16-bit output");
-        const LnSeg<true> sg{n_full, p0, n_live, xc};
-        if (D == 4 * LN_THREADS)
-            hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, false, false, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)nullptr, mean, rstd, M, ldy, eps, sg);
-        else
-            hipLaunchKernelGGL((ln_fwd_kernel<h16_t, false, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)nullptr, mean, rstd, M, D, ldy, eps, sg);
-        return omlm_post_launch("omlm_layernorm_fwd_seg");
-    }
-    const LnSeg<false> ns{};
-    if (D == 4 * LN_THREADS && mean && rstd) {        // the row-pair kernels (next-row prefetch, fewer barriers)
-        if (out_dtype == 0) {
-            if (xcast) hipLaunchKernelGGL((ln_fwd_row1_kernel<float, true>), grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, ldy, eps, ns);
-            else       hipLaunchKernelGGL((ln_fwd_row1_kernel<float, false>), grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, ldy, eps, ns);
-        } else {
-            if (xcast) hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)xcast, mean, rstd, M, ldy, eps, ns);
-            else       hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, false>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)xcast, mean, rstd, M, ldy, eps, ns);
-        }
-        return omlm_post_launch("omlm_layernorm_fwd");
-    }
-    if (out_dtype == 0)
-        hipLaunchKernelGGL(ln_fwd_kernel<float>, grid, block, 0, as_stream(stream), x, gamma, (float*)y, (float*)xcast, mean, rstd, M, D, ldy, eps, ns);
-    else
-        hipLaunchKernelGGL(ln_fwd_kernel<h16_t>, grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)xcast, mean, rstd, M, D, ldy, eps, ns);
-    return omlm_post_launch("omlm_layernorm_fwd");
-}
-#if !OMLM_FP16
-extern "C" int omlm_layernorm_fwd(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd,
-                                  int M, int D, int ldy, float eps, int out_dtype, void* stream) {
-    return omlm_layernorm_fwd_seg(x, gamma, y, xcast, mean, rstd, nullptr, M, D, ldy, eps, out_dtype, 0, 0, 0, stream);
-}
-#endif
-
-// The same forward with the result as hi/lo planes of the 16-bit type (1 = bf16, 2 = fp16): y = rne16(v), y_lo = rne16(v - y), both at
-// pitch ldy (precision "fp16ff": the FF-in GEMM of the forward reads both planes, the backward reads y alone).
-#if !OMLM_FP16
-extern "C" int omlm_layernorm_fwd_planes_seg_h(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd, float* xc, int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_layernorm_fwd_planes_seg)(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd, float* xc,
-                                                   int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream) {
-#if !OMLM_FP16
-    if (out_dtype == OMLM_DT_F16) return omlm_layernorm_fwd_planes_seg_h(x, gamma, y, y_lo, mean, rstd, xc, M, D, ldy, eps, 1, n_full, p0, n_live, stream);
-#endif
-    if (M <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(out_dtype == 1, "layernorm_fwd_planes: out_dtype 1 (bf16) or 2 (fp16)");
-    OMLM_CHECK_ARG(x && gamma && y && y_lo && mean && rstd, "null pointer");
-    OMLM_CHECK_ARG(D % 4 == 0 && D <= 4 * LN_THREADS * LN_MAXV, "D must be a multiple of 4 and <= 4096");
-    OMLM_CHECK_ARG(ldy >= D && ldy % 4 == 0, "ldy < D");
-    dim3 grid(ln_grid(M)), block(LN_THREADS);
-    if (n_full != 0) {
-        LN_CHECK_SEG(M, n_full, p0, n_live);
-        const LnSeg<true> sg{n_full, p0, n_live, xc};
-        if (D == 4 * LN_THREADS)
-            hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, false, true, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)y_lo, mean, rstd, M, ldy, eps, sg);
-        else
-            hipLaunchKernelGGL((ln_fwd_kernel<h16_t, true, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)y_lo, mean, rstd, M, D, ldy, eps, sg);
-        return omlm_post_launch("omlm_layernorm_fwd_planes_seg");
-    }
-    if (D == 4 * LN_THREADS)
-        hipLaunchKernelGGL((ln_fwd_row1_kernel<h16_t, false, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)y_lo, mean, rstd, M, ldy, eps, LnSeg<false>{});
-    else
-        hipLaunchKernelGGL((ln_fwd_kernel<h16_t, true>), grid, block, 0, as_stream(stream), x, gamma, (h16_t*)y, (h16_t*)y_lo, mean, rstd, M, D, ldy, eps, LnSeg<false>{});
-    return omlm_post_launch("omlm_layernorm_fwd_planes");
-}
-#if !OMLM_FP16
-extern "C" int omlm_layernorm_fwd_planes(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd,
-                                         int M, int D, int ldy, float eps, int out_dtype, void* stream) {
-    return omlm_layernorm_fwd_planes_seg(x, gamma, y, y_lo, mean, rstd, nullptr, M, D, ldy, eps, out_dtype, 0, 0, 0, stream);
-}
-#endif
-
-extern "C" int omlm_colsum_accumulate(const float* part, float* out, int P, int C, int ldp, void* stream);
-#if !OMLM_FP16
-extern "C" long long omlm_layernorm_bwd_workspace_bytes(int D) { return (long long)2048 * D * sizeof(float); }
-#endif
-
-#if !OMLM_FP16
-extern "C" int omlm_layernorm_bwd2_seg_h(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd, const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D, float dx_scale, int cast_dtype, int dy_dtype, int n_full, int p0, int n_live, void* stream);
-#endif
-// dres2 (optional): a second residual-gradient term [M, D] in the type named by cast_dtype (dxcast itself may be null)
-// segment (n_full != 0; the plain entry passes none): dy, x, the statistics and dres are compact [M, ..]; dx / dxcast are full-size
-// ([M / n_live * n_full, D]), written at the segment's rows, the rows in front of it as zeros by the same launch; no dres2
-extern "C" int OMLM_API(omlm_layernorm_bwd2_seg)(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
-                                  const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D,
-                                  float dx_scale, int cast_dtype, int dy_dtype, int n_full, int p0, int n_live, void* stream) {
-#if !OMLM_FP16
-    if (cast_dtype == OMLM_DT_F16 || dy_dtype == OMLM_DT_F16) return omlm_layernorm_bwd2_seg_h(dy, x, gamma, mean, rstd, dres, dres2, dx, dxcast, dgamma, workspace, M, D, dx_scale, OMLM_H_CODE(cast_dtype), OMLM_H_CODE(dy_dtype), n_full, p0, n_live, stream);
-#endif
-    if (M <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(dy && x && gamma && mean && rstd && dx, "null pointer");
-    OMLM_CHECK_ARG(D % 4 == 0 && D <= 4 * LN_THREADS * LN_MAXV, "D must be a multiple of 4 and <= 4096");
-    // Each row is a dependent chain (load -> two block reductions -> load dres -> store), so the rate is set by the rows
-    // in flight.  With a workspace (omlm_layernorm_bwd_workspace_bytes) 2048 workgroups each leave one partial dgamma row
-    // for colsum; without it dgamma is accumulated with atomics, which only scale to 512 workgroups (2048: 194 -> 273 us).
-    // dgamma null WITH a workspace (round 5): the partial rows are left in the workspace ([min(M, 2048), D]) and the caller sums them later --
-    // engine.trunk_backward folds the column sums of all LayerNorms of a backward pass into one omlm_colsum_group launch.
-    const bool two_level = workspace != nullptr;
-    const int blocks = two_level ? (M < 2048 ? M : 2048) : (M < 512 ? M : 512);
-    dim3 grid(blocks), block(LN_THREADS);
-    float* part = two_level ? workspace : nullptr;
-    OMLM_CHECK_ARG(dy_dtype == 0 || dy_dtype == 1, "dy_dtype: 0 = fp32, 1 = bf16, 2 = fp16 (same 16-bit type as the cast output)");
-    const LnSeg<false> ns{};
-    if (n_full != 0) {
-        // the one form the trunk uses: 16-bit dy and cast copy (the type is named by cast_dtype even where dxcast is null)
-        LN_CHECK_SEG(M, n_full, p0, n_live);
-        OMLM_CHECK_ARG(!dres2 && cast_dtype == 1 && dy_dtype == 1, "layernorm_bwd2_seg: 16-bit dy and cast type, no dres2");
-        const LnSeg<true> sg{n_full, p0, n_live, nullptr};
-        if (D == 4 * LN_THREADS) {
-#define LN_ROW1S(F) hipLaunchKernelGGL((ln_bwd_row1_kernel<h16_t, h16_t, F, true>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, \
-                                       (const h16_t*)nullptr, dx, (h16_t*)dxcast, dgamma, part, M, dx_scale, sg)
-            switch ((dres ? 1 : 0) | (dxcast ? 4 : 0)) { case 0: LN_ROW1S(0); break; case 1: LN_ROW1S(1); break; case 4: LN_ROW1S(4); break; default: LN_ROW1S(5); break; }
-#undef LN_ROW1S
-        } else
-            hipLaunchKernelGGL((ln_bwd_kernel<h16_t, h16_t, true>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, (const h16_t*)nullptr, dx, (h16_t*)dxcast, dgamma, part, M, D, dx_scale, sg);
-    } else
-    if (D == 4 * LN_THREADS) {                        // ln_bwd_row1_kernel (next-row prefetch, one barrier per row)
-        const int fl = (dres ? 1 : 0) | (dres2 ? 2 : 0) | (dxcast ? 4 : 0);
-#define LN_ROW1(TT, TD, F) hipLaunchKernelGGL((ln_bwd_row1_kernel<TT, TD, F>), grid, block, 0, as_stream(stream), (const TD*)dy, x, gamma, mean, rstd, dres, \
-                                              (const TT*)dres2, dx, (TT*)dxcast, dgamma, part, M, dx_scale, ns)
-#define LN_ROW1_FL(TT, TD) do { switch (fl) { case 0: LN_ROW1(TT, TD, 0); break; case 1: LN_ROW1(TT, TD, 1); break; case 2: LN_ROW1(TT, TD, 2); break; \
-        case 3: LN_ROW1(TT, TD, 3); break; case 4: LN_ROW1(TT, TD, 4); break; case 5: LN_ROW1(TT, TD, 5); break; case 6: LN_ROW1(TT, TD, 6); break; \
-        default: LN_ROW1(TT, TD, 7); break; } } while (0)
-        if (cast_dtype == 0 && dy_dtype == 0) LN_ROW1_FL(float, float);
-        else if (cast_dtype == 0)              LN_ROW1_FL(float, h16_t);
-        else if (dy_dtype == 0)                LN_ROW1_FL(h16_t, float);
-        else                                   LN_ROW1_FL(h16_t, h16_t);
-#undef LN_ROW1_FL
-#undef LN_ROW1
-    } else
-    if (cast_dtype == 0 && dy_dtype == 0)
-        hipLaunchKernelGGL((ln_bwd_kernel<float, float>), grid, block, 0, as_stream(stream), (const float*)dy, x, gamma, mean, rstd, dres, (const float*)dres2, dx, (float*)dxcast, dgamma, part, M, D, dx_scale, ns);
-    else if (cast_dtype == 0)
-        hipLaunchKernelGGL((ln_bwd_kernel<float, h16_t>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, (const float*)dres2, dx, (float*)dxcast, dgamma, part, M, D, dx_scale, ns);
-    else if (dy_dtype == 0)
-        hipLaunchKernelGGL((ln_bwd_kernel<h16_t, float>), grid, block, 0, as_stream(stream), (const float*)dy, x, gamma, mean, rstd, dres, (const h16_t*)dres2, dx, (h16_t*)dxcast, dgamma, part, M, D, dx_scale, ns);
-    else
-        hipLaunchKernelGGL((ln_bwd_kernel<h16_t, h16_t>), grid, block, 0, as_stream(stream), (const h16_t*)dy, x, gamma, mean, rstd, dres, (const h16_t*)dres2, dx, (h16_t*)dxcast, dgamma, part, M, D, dx_scale, ns);
-    int rc = omlm_post_launch("omlm_layernorm_bwd2");
-    if (rc) return rc;
-    if (two_level && dgamma) return omlm_colsum_accumulate(part, dgamma, blocks, D, D, stream);
-    return OMLM_OK;
-}
-#if !OMLM_FP16
-extern "C" int omlm_layernorm_bwd2(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
-                                   const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D,
-                                   float dx_scale, int cast_dtype, int dy_dtype, void* stream) {
-    return omlm_layernorm_bwd2_seg(dy, x, gamma, mean, rstd, dres, dres2, dx, dxcast, dgamma, workspace, M, D, dx_scale, cast_dtype, dy_dtype, 0, 0, 0, stream);
-}
-#endif
-
 // ---------------------------------------------------------------------------------------------
 // q/k l2norm * scale.  One wave per 64-wide vector, one element per lane (dim_head == 64).
 //   q_raw [M, H*64] fp32, kv_raw [M, 128] fp32  ->  q [M, H*64] T, k [M, 64] T, v [M, 64] T
@@ -693,7 +505,6 @@ __global__ __launch_bounds__(256) void qk_norm_bwd_kernel(const float* __restric
     // several vectors per lane per trip, all their loads requested before the first reduction (one vector per trip with a 64-bit
     // division in front of its loads ran at 2.7 TB/s -- 83 us at M = 35712, H = 8: one dependent round trip at a time per wave; now 51 us)
 #define QKB_U 4                 /* vectors per lane per trip */
-#define QKB_BLOCKS 512          /* workgroups: each ends with 128 atomics into the two scale gradients (2048 workgroups: 69 us, 512: 51 us) */
     constexpr int U = QKB_U;
     const unsigned stride = gridDim.x * 16u;
     for (unsigned base = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 4u; base < nvec; base += stride * U) {
@@ -767,8 +578,6 @@ __global__ __launch_bounds__(256) void qk_norm_bwd_kernel(const float* __restric
 // holds elements 8 (l & 7) .. + 7 of vector (l >> 3), a wave-instruction reads 1 KiB of q / 2 x 1 KiB of dq contiguously.  Whole units
 // run two at a time without a single condition (counted waits); the ragged tail and the k | v rows (1 / (H + 1) of the bytes) take
 // the predicated body.
-#define QKB2_THREADS 1024       /* 16 waves per workgroup: a quarter of the atomics of 256-thread workgroups at the same waves per CU (1024 workgroups x 128 atomics onto 128
-                                   addresses were ~10 us of serialised tail) */
 struct QkUnit { u32x4 y; float4 d0, d1; float nr; };
 
 template <typename T>
@@ -885,66 +694,215 @@ __global__ __launch_bounds__(QKB2_THREADS) void qk_norm_bwd2_kernel(const float*
     flush(dk_scale);
 }
 
-#if !OMLM_FP16
-extern "C" int omlm_qk_norm_bwd2_h(const float* dq, const float* dk, const float* dv, const void* q, const void* k, const float* qn, const float* kn, const float* q_scale, const float* k_scale, void* dq_raw, void* dkv_raw, float* dq_scale, float* dk_scale, int M, int H, int dtype, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_qk_norm_bwd2)(const float* dq, const float* dk, const float* dv, const void* q, const void* k, const float* qn,
-                                           const float* kn, const float* q_scale, const float* k_scale, void* dq_raw, void* dkv_raw,
-                                           float* dq_scale, float* dk_scale, int M, int H, int dtype, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16) return omlm_qk_norm_bwd2_h(dq, dk, dv, q, k, qn, kn, q_scale, k_scale, dq_raw, dkv_raw, dq_scale, dk_scale, M, H, 1, stream);
-#endif
-    if (M <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(dtype == 1, "qk_norm_bwd2: 16-bit operand types only (1 = bf16, 2 = fp16)");
-    OMLM_CHECK_ARG(dq && dk && dv && q && k && qn && kn && dq_raw && dkv_raw && dq_scale && dk_scale, "null pointer");
-    long long nvec = (long long)M * (H + 2);
-    OMLM_CHECK_ARG(nvec < (1ll << 31), "qk_norm_bwd2: M * (H + 2) must stay below 2^31 (32-bit vector index)");
-#define QKB2_BLOCKS 256         /* workgroups (QKB2_THREADS / 64 waves each; 128 atomics per workgroup at the end) */
-    long long want = ((long long)M * H / 8 + 2 * (QKB2_THREADS / 64) - 1) / (2 * (QKB2_THREADS / 64));      // ~2 units per wave at least
-    int blocks = want > QKB2_BLOCKS ? QKB2_BLOCKS : (want < 1 ? 1 : (int)want);
-    hipLaunchKernelGGL(qk_norm_bwd2_kernel<h16_t>, dim3(blocks), dim3(QKB2_THREADS), 0, as_stream(stream), dq, dk, dv, (const h16_t*)q, (const h16_t*)k, qn, kn,
-                       q_scale, k_scale, (h16_t*)dq_raw, (h16_t*)dkv_raw, dq_scale, dk_scale, M, H);
-    return omlm_post_launch("omlm_qk_norm_bwd2");
+// ---- host side: csrc/norm_plan.h decides what a call runs; one launcher per kernel family runs it --------------------------------------------------
+static_assert(NORM_ERR_ARG == OMLM_ERR_ARG, "norm_plan.h states the return code");
+extern "C" int omlm_colsum_accumulate(const float* part, float* out, int P, int C, int ldp, void* stream);     // ffmid.hip, bf16 copy
+
+// f(T()): the operand type a launch names -- float, or this copy's 16-bit type.  The fp16 copy builds no fp32 forms: the plan refuses them there
+// (norm_fp32_only)
+template <typename F>
+static inline void with_type(bool t16, F&& f) {
+    if constexpr (!OMLM_FP16) { if (!t16) { f(float()); return; } }
+    f(h16_t());
+}
+// f(T(), TDY()): the backward's (cast, dy) pair; the fp16 copy builds every pair but (float, float)
+template <typename F>
+static inline void with_pair(bool t16, bool tdy16, F&& f) {
+    if (t16) { if (tdy16) f(h16_t(), h16_t()); else f(h16_t(), float()); }
+    else if (tdy16) f(float(), h16_t());
+    else if constexpr (!OMLM_FP16) f(float(), float());
 }
 
-#if !OMLM_FP16
-extern "C" int omlm_qk_norm_fwd_h(const float* q_raw, const float* kv_raw, const float* q_scale, const float* k_scale, void* q, void* k, void* v, int M, int H, int out_dtype, void* stream);
+// ln_fwd_kernel<T, LO, SEG> / ln_fwd_row1_kernel<T, XC, LO, SEG> (D is a constant there)
+template <typename T, bool LO, bool SEG>
+static void ln_fwd_go(const NormLaunch& l, const NormArgs& a) {
+    auto go = [&](auto kernel, auto... d) {
+        hipLaunchKernelGGL(kernel, dim3(l.gx), dim3(l.threads), 0, as_stream(a.stream), a.x, a.gamma, (T*)a.y, (T*)a.y2, a.mean, a.rstd, a.M, d..., a.ldy, a.eps, ln_seg<SEG>(a));
+    };
+    if (l.kernel == NK_LN_FWD) return go(ln_fwd_kernel<T, LO, SEG>, a.D);
+    if constexpr (!LO && !SEG) { if (l.xc) return go(ln_fwd_row1_kernel<T, true, false, false>); }      // (a cast copy of x: the plain forward's only)
+    go(ln_fwd_row1_kernel<T, false, LO, SEG>);
+}
+static void ln_fwd_launch(const NormLaunch& l, const NormArgs& a) {
+    if (!l.lo && !l.seg) return with_type(l.t16, [&](auto t) { ln_fwd_go<decltype(t), false, false>(l, a); });
+    // planes and segments: 16-bit outputs only
+    with_flags(l.lo, l.seg, [&](auto lo, auto seg) { ln_fwd_go<h16_t, decltype(lo)::value, decltype(seg)::value>(l, a); });
+}
+
+// ln_bwd_kernel<T, TDY, SEG> / ln_bwd_row1_kernel<T, TDY, FL, SEG> (D is a constant there); the workspace, where there is one, receives the
+// partial dgamma rows
+template <typename T, typename TDY, bool SEG>
+static void ln_bwd_go(const NormLaunch& l, const NormArgs& a) {
+    auto go = [&](auto kernel, auto... d) {
+        hipLaunchKernelGGL(kernel, dim3(l.gx), dim3(l.threads), 0, as_stream(a.stream), (const TDY*)a.dy, a.x, a.gamma, (const float*)a.mean, (const float*)a.rstd,
+                           a.dres, (const T*)a.dres2, a.dx, (T*)a.dxcast, a.dgamma, a.workspace, a.M, d..., a.dx_scale, ln_seg<SEG>(a));
+    };
+    if (l.kernel == NK_LN_BWD) return go(ln_bwd_kernel<T, TDY, SEG>, a.D);
+    with_flags(l.fl & 1, l.fl & 4, [&](auto dres, auto dxcast) {
+        constexpr int FL = decltype(dres)::value | 4 * decltype(dxcast)::value;
+        if constexpr (!SEG) { if (l.fl & 2) return go(ln_bwd_row1_kernel<T, TDY, FL | 2, false>); }       // (a segment takes no dres2)
+        go(ln_bwd_row1_kernel<T, TDY, FL, SEG>);
+    });
+}
+static void ln_bwd_launch(const NormLaunch& l, const NormArgs& a) {
+    if (l.seg) return ln_bwd_go<h16_t, h16_t, true>(l, a);        // the one form the trunk uses
+    with_pair(l.t16, l.tdy16, [&](auto t, auto tdy) { ln_bwd_go<decltype(t), decltype(tdy), false>(l, a); });
+}
+
+// qk_norm_fwd_kernel<T> / qk_norm_bwd_kernel<T> / qk_norm_bwd2_kernel<h16_t>
+static void qk_launch(const NormLaunch& l, const NormArgs& a) {
+    const dim3 grid(l.gx), block(l.threads);
+    const hipStream_t st = as_stream(a.stream);
+    if (l.kernel == NK_QK_BWD2) {
+        hipLaunchKernelGGL(qk_norm_bwd2_kernel<h16_t>, grid, block, 0, st, a.dq, a.dk, a.dv, (const h16_t*)a.q, (const h16_t*)a.k, a.qn, a.kn, a.q_scale, a.k_scale,
+                           (h16_t*)a.dq_raw, (h16_t*)a.dkv_raw, a.dq_scale, a.dk_scale, a.M, a.H);
+        return;
+    }
+    with_type(l.t16, [&](auto t) {
+        using T = decltype(t);
+        if (l.kernel == NK_QK_FWD)
+            hipLaunchKernelGGL(qk_norm_fwd_kernel<T>, grid, block, 0, st, a.q_raw, a.kv_raw, a.q_scale, a.k_scale, (T*)a.q, (T*)a.k, (T*)a.v, a.M, a.H);
+        else
+            hipLaunchKernelGGL(qk_norm_bwd_kernel<T>, grid, block, 0, st, a.dq, a.dk, a.dv, a.q_raw, a.kv_raw, a.q_scale, a.k_scale, (T*)a.dq_raw, (T*)a.dkv_raw,
+                               a.dq_scale, a.dk_scale, a.M, a.H);
+    });
+}
+
+// plan, then launch in order: the call's own kernel, and behind a two-level backward with dgamma the column sum over the partial rows it left
+static int norm_run_here(NormCall c, const NormArgs& a) {
+    c.fp16_copy = OMLM_FP16 != 0;
+    const NormPlan plan = norm_plan(c);
+    if (plan.rc != OMLM_OK) { omlm_set_error(plan.msg); return plan.rc; }
+    for (int i = 0; i < plan.n; ++i) {
+        const NormLaunch& l = plan.l[i];
+        switch (l.kernel) {
+        case NK_COLSUM: return omlm_colsum_accumulate(a.workspace, a.dgamma, l.rows, a.D, a.D, a.stream);
+        case NK_LN_FWD: case NK_LN_FWD_ROW1: ln_fwd_launch(l, a); break;
+#if OMLM_FP16
+        case NK_LN_FWD_MX: ln_fwd_mx_launch(l, a); break;
 #endif
-extern "C" int OMLM_API(omlm_qk_norm_fwd)(const float* q_raw, const float* kv_raw, const float* q_scale, const float* k_scale,
+        case NK_LN_BWD: case NK_LN_BWD_ROW1: ln_bwd_launch(l, a); break;
+        default: qk_launch(l, a); break;
+        }
+        const int rc = omlm_post_launch(plan.label);
+        if (rc) return rc;
+    }
+    return OMLM_OK;
+}
+
+#if OMLM_FP16
+// the fp16 copy has one way in: a call the bf16 copy handed over (norm_to_fp16_copy)
+extern "C" __attribute__((visibility("hidden"))) int omlm_norm_run_h(const NormCall* c, const NormArgs* a) { return norm_run_here(*c, *a); }
+#else
+extern "C" int omlm_norm_run_h(const NormCall* c, const NormArgs* a);
+static int norm_run(NormCall c, const NormArgs& a) { return norm_to_fp16_copy(c) ? omlm_norm_run_h(&c, &a) : norm_run_here(c, a); }
+
+// the call of an entry whose arguments are in `a`; operands: every pointer the entry requires is there
+static NormCall norm_call(NormOp op, const NormArgs& a, int dtype, bool operands) {
+    NormCall c;
+    memset(&c, 0, sizeof(c));
+    c.op = op; c.M = a.M; c.D = a.D; c.ldy = a.ldy; c.H = a.H; c.dtype = dtype; c.operands = operands;
+    c.xcast = a.y2 != nullptr; c.stats = a.mean && a.rstd; c.xc = a.xc != nullptr;
+    c.dres = a.dres != nullptr; c.dres2 = a.dres2 != nullptr; c.dxcast = a.dxcast != nullptr; c.dgamma = a.dgamma != nullptr; c.workspace = a.workspace != nullptr;
+    c.n_full = a.n_full; c.p0 = a.p0; c.n_live = a.n_live; c.y8_stride = a.y8_stride;
+    return c;
+}
+
+// ---- the C entries (include/omlm.h).  dtype codes: 0 = fp32, 1 = bf16, 2 = fp16 ------------------------------------------------------------------
+// The LayerNorm entries in their `_seg` form: n_full == 0 is "no segment", which is all the plain entries pass.  With a segment x [.. n_full rows
+// per sample] is read at the segment's rows, every forward output is compact ([M, ..]) and xc (optional) receives the fp32 source rows; the
+// backward reads everything compact and writes dx / dxcast full-size, the rows in front of the segment as zeros by the same launch.
+extern "C" int omlm_layernorm_fwd_seg(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd, float* xc,
+                                      int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream) {
+    NormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.gamma = gamma; a.y = y; a.y2 = xcast; a.mean = mean; a.rstd = rstd; a.xc = xc; a.M = M; a.D = D; a.ldy = ldy; a.eps = eps;
+    a.n_full = n_full; a.p0 = p0; a.n_live = n_live; a.stream = stream;
+    return norm_run(norm_call(LN_FWD, a, out_dtype, x && gamma && y), a);
+}
+extern "C" int omlm_layernorm_fwd(const float* x, const float* gamma, void* y, void* xcast, float* mean, float* rstd,
+                                  int M, int D, int ldy, float eps, int out_dtype, void* stream) {
+    return omlm_layernorm_fwd_seg(x, gamma, y, xcast, mean, rstd, nullptr, M, D, ldy, eps, out_dtype, 0, 0, 0, stream);
+}
+
+// The same forward with the result as hi/lo planes of the 16-bit type (1 = bf16, 2 = fp16): y = rne16(v), y_lo = rne16(v - y), both at
+// pitch ldy (precision "fp16ff": the FF-in GEMM of the forward reads both planes, the backward reads y alone).
+extern "C" int omlm_layernorm_fwd_planes_seg(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd, float* xc,
+                                             int M, int D, int ldy, float eps, int out_dtype, int n_full, int p0, int n_live, void* stream) {
+    NormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.gamma = gamma; a.y = y; a.y2 = y_lo; a.mean = mean; a.rstd = rstd; a.xc = xc; a.M = M; a.D = D; a.ldy = ldy; a.eps = eps;
+    a.n_full = n_full; a.p0 = p0; a.n_live = n_live; a.stream = stream;
+    return norm_run(norm_call(LN_FWD_PLANES, a, out_dtype, x && gamma && y && y_lo && mean && rstd), a);
+}
+extern "C" int omlm_layernorm_fwd_planes(const float* x, const float* gamma, void* y, void* y_lo, float* mean, float* rstd,
+                                         int M, int D, int ldy, float eps, int out_dtype, void* stream) {
+    return omlm_layernorm_fwd_planes_seg(x, gamma, y, y_lo, mean, rstd, nullptr, M, D, ldy, eps, out_dtype, 0, 0, 0, stream);
+}
+
+// The same forward for omlm_gemm_mx16 (fp16 only: ln_fwd_mx_kernel above).  The `_seg` entry always carries a segment: an op of its own.
+extern "C" int omlm_layernorm_fwd_mx(const float* x, const float* gamma, void* y, void* y8, long long y8_stride, unsigned char* scale8,
+                                     float* mean, float* rstd, int M, int D, int ldy, float eps, void* stream) {
+    NormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.gamma = gamma; a.y = y; a.y8 = y8; a.y8_stride = y8_stride; a.scale8 = scale8; a.mean = mean; a.rstd = rstd;
+    a.M = M; a.D = D; a.ldy = ldy; a.eps = eps; a.stream = stream;
+    return norm_run(norm_call(LN_FWD_MX, a, 1, x && gamma && y && y8 && scale8 && mean && rstd), a);
+}
+extern "C" int omlm_layernorm_fwd_mx_seg(const float* x, const float* gamma, void* y, void* y8, long long y8_stride, unsigned char* scale8,
+                                         float* mean, float* rstd, float* xc, int M, int D, int ldy, float eps, int n_full, int p0, int n_live, void* stream) {
+    NormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.x = x; a.gamma = gamma; a.y = y; a.y8 = y8; a.y8_stride = y8_stride; a.scale8 = scale8; a.mean = mean; a.rstd = rstd; a.xc = xc;
+    a.M = M; a.D = D; a.ldy = ldy; a.eps = eps; a.n_full = n_full; a.p0 = p0; a.n_live = n_live; a.stream = stream;
+    return norm_run(norm_call(LN_FWD_MX_SEG, a, 1, x && gamma && y && y8 && scale8 && mean && rstd), a);
+}
+
+extern "C" long long omlm_layernorm_bwd_workspace_bytes(int D) { return ln_bwd_workspace_bytes(D); }
+// dres2 (optional): a second residual-gradient term [M, D] in the type named by cast_dtype (dxcast itself may be null)
+extern "C" int omlm_layernorm_bwd2_seg(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                                       const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D,
+                                       float dx_scale, int cast_dtype, int dy_dtype, int n_full, int p0, int n_live, void* stream) {
+    NormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dy = dy; a.x = x; a.gamma = gamma; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd);        // (read only here)
+    a.dres = dres; a.dres2 = dres2; a.dx = dx; a.dxcast = dxcast; a.dgamma = dgamma; a.workspace = workspace; a.M = M; a.D = D; a.dx_scale = dx_scale;
+    a.n_full = n_full; a.p0 = p0; a.n_live = n_live; a.stream = stream;
+    NormCall c = norm_call(LN_BWD, a, cast_dtype, dy && x && gamma && mean && rstd && dx);
+    c.dy_dtype = dy_dtype;
+    return norm_run(c, a);
+}
+extern "C" int omlm_layernorm_bwd2(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                                   const float* dres, const void* dres2, float* dx, void* dxcast, float* dgamma, float* workspace, int M, int D,
+                                   float dx_scale, int cast_dtype, int dy_dtype, void* stream) {
+    return omlm_layernorm_bwd2_seg(dy, x, gamma, mean, rstd, dres, dres2, dx, dxcast, dgamma, workspace, M, D, dx_scale, cast_dtype, dy_dtype, 0, 0, 0, stream);
+}
+
+extern "C" int omlm_qk_norm_fwd(const float* q_raw, const float* kv_raw, const float* q_scale, const float* k_scale,
                                 void* q, void* k, void* v, int M, int H, int out_dtype, void* stream) {
-#if !OMLM_FP16
-    if (out_dtype == OMLM_DT_F16) return omlm_qk_norm_fwd_h(q_raw, kv_raw, q_scale, k_scale, q, k, v, M, H, 1, stream);
-#endif
-    if (M <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(q_raw && kv_raw && q_scale && k_scale && q && k && v, "null pointer");
-    long long nvec = (long long)M * (H + 2);
-    int blocks = (int)((nvec + 15) / 16); if (blocks > 4096) blocks = 4096;
-    if (out_dtype == 0)
-        hipLaunchKernelGGL(qk_norm_fwd_kernel<float>, dim3(blocks), dim3(256), 0, as_stream(stream), q_raw, kv_raw, q_scale, k_scale, (float*)q, (float*)k, (float*)v, M, H);
-    else
-        hipLaunchKernelGGL(qk_norm_fwd_kernel<h16_t>, dim3(blocks), dim3(256), 0, as_stream(stream), q_raw, kv_raw, q_scale, k_scale, (h16_t*)q, (h16_t*)k, (h16_t*)v, M, H);
-    return omlm_post_launch("omlm_qk_norm_fwd");
+    NormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.q_raw = q_raw; a.kv_raw = kv_raw; a.q_scale = q_scale; a.k_scale = k_scale; a.q = q; a.k = k; a.v = v; a.M = M; a.H = H; a.stream = stream;
+    return norm_run(norm_call(QK_FWD, a, out_dtype, q_raw && kv_raw && q_scale && k_scale && q && k && v), a);
 }
-
-#if !OMLM_FP16
-extern "C" int omlm_qk_norm_bwd_h(const float* dq, const float* dk, const float* dv, const float* q_raw, const float* kv_raw, const float* q_scale, const float* k_scale, void* dq_raw, void* dkv_raw, float* dq_scale, float* dk_scale, int M, int H, int out_dtype, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_qk_norm_bwd)(const float* dq, const float* dk, const float* dv, const float* q_raw, const float* kv_raw,
+extern "C" int omlm_qk_norm_bwd(const float* dq, const float* dk, const float* dv, const float* q_raw, const float* kv_raw,
                                 const float* q_scale, const float* k_scale, void* dq_raw, void* dkv_raw,
                                 float* dq_scale, float* dk_scale, int M, int H, int out_dtype, void* stream) {
-#if !OMLM_FP16
-    if (out_dtype == OMLM_DT_F16) return omlm_qk_norm_bwd_h(dq, dk, dv, q_raw, kv_raw, q_scale, k_scale, dq_raw, dkv_raw, dq_scale, dk_scale, M, H, 1, stream);
-#endif
-    if (M <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(dq && dk && dv && q_raw && kv_raw && dq_raw && dkv_raw && dq_scale && dk_scale, "null pointer");
-    long long nvec = (long long)M * (H + 2);
-    OMLM_CHECK_ARG(nvec < (1ll << 31), "qk_norm_bwd: M * (H + 2) must stay below 2^31 (32-bit vector index)");
-    int blocks = (int)((nvec + 15) / 16); if (blocks > QKB_BLOCKS) blocks = QKB_BLOCKS;
-    if (out_dtype == 0)
-        hipLaunchKernelGGL(qk_norm_bwd_kernel<float>, dim3(blocks), dim3(256), 0, as_stream(stream), dq, dk, dv, q_raw, kv_raw, q_scale, k_scale, (float*)dq_raw, (float*)dkv_raw, dq_scale, dk_scale, M, H);
-    else
-        hipLaunchKernelGGL(qk_norm_bwd_kernel<h16_t>, dim3(blocks), dim3(256), 0, as_stream(stream), dq, dk, dv, q_raw, kv_raw, q_scale, k_scale, (h16_t*)dq_raw, (h16_t*)dkv_raw, dq_scale, dk_scale, M, H);
-    return omlm_post_launch("omlm_qk_norm_bwd");
+    NormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dq = dq; a.dk = dk; a.dv = dv; a.q_raw = q_raw; a.kv_raw = kv_raw; a.q_scale = q_scale; a.k_scale = k_scale; a.dq_raw = dq_raw; a.dkv_raw = dkv_raw;
+    a.dq_scale = dq_scale; a.dk_scale = dk_scale; a.M = M; a.H = H; a.stream = stream;
+    return norm_run(norm_call(QK_BWD, a, out_dtype, dq && dk && dv && q_raw && kv_raw && dq_raw && dkv_raw && dq_scale && dk_scale), a);
 }
+extern "C" int omlm_qk_norm_bwd2(const float* dq, const float* dk, const float* dv, const void* q, const void* k, const float* qn,
+                                 const float* kn, const float* q_scale, const float* k_scale, void* dq_raw, void* dkv_raw,
+                                 float* dq_scale, float* dk_scale, int M, int H, int dtype, void* stream) {
+    NormArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dq = dq; a.dk = dk; a.dv = dv; a.q = const_cast<void*>(q); a.k = const_cast<void*>(k); a.qn = qn; a.kn = kn; a.q_scale = q_scale; a.k_scale = k_scale;      // (read only here)
+    a.dq_raw = dq_raw; a.dkv_raw = dkv_raw; a.dq_scale = dq_scale; a.dk_scale = dk_scale; a.M = M; a.H = H; a.stream = stream;
+    return norm_run(norm_call(QK_BWD2, a, dtype, dq && dk && dv && q && k && qn && kn && dq_raw && dkv_raw && dq_scale && dk_scale), a);
+}
+#endif
 
 }   // namespace OMLM_NS

@@ -322,6 +322,7 @@ class QuantRowsGroup(_DescGroup):
 
 
 _LN_WS = {}
+LN_BWD_PARTIAL_ROWS = 2048      # a two-level LayerNorm backward leaves min(M, this) partial d(gamma) rows, one per workgroup (csrc/norm_plan.h: LN_GRID)
 
 
 def _ln_workspace(D: int, device) -> torch.Tensor:
@@ -358,7 +359,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dx, dxcast, dgamma, dx_scale=1
     code = dcode(dxcast.dtype) if dxcast is not None else (dcode(dres2.dtype) if dres2 is not None else F32)
     assert dres2 is None or dcode(dres2.dtype) == code, "dres2 must have the cast type"
     deferred = dgamma is not None and defer is not None
-    rows = min(M, 2048)
+    rows = min(M, LN_BWD_PARTIAL_ROWS)
     if deferred:
         ws = torch.empty(rows * D, device=x.device)     # private, alive until the group's flush: one partial row per workgroup (min(M, 2048) of them)
     else:

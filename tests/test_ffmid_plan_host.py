@@ -18,6 +18,8 @@ import subprocess
 
 import pytest
 
+from kernel_names import parse_kernel
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "open_musiclm_amd", "csrc")
 TABLE = json.load(open(os.path.join(ROOT, "tests", "ffmid_routes.json")))
@@ -41,29 +43,6 @@ def plan(tmp_path_factory):
     lib.omlm_plan_ffmid.argtypes = [C.POINTER(C.c_int), C.c_double, C.c_longlong, C.POINTER(C.c_longlong), C.c_char_p]
     lib.omlm_plan_ffmid_bwd_workspace_bytes.restype = lib.omlm_plan_ffmid_ws_dconv_at.restype = C.c_longlong
     return lib
-
-
-def parse_kernel(name):
-    """(copy namespace, kernel, template arguments) of a kernel name as the trace has it -- demangled, or Itanium-mangled where the
-    demangler does not know the 16-bit types; types as h16 / float, numbers and flags as ints"""
-    m = re.match(r"(?:void )?(omlm_\w+)::(\w+)(?:<([^>]*)>)?\(", name)
-    if m:
-        # The profiler's demangler reads the bf16 type (DF16b) as a fixed-point type and swallows the `L` behind it: `DF16bLi2ELb1E` comes out
-        # as "bool _Accum, int, EL, bool, E" (the digits read as the lengths of names); every other bf16 instantiation stays mangled.
-        args = {"bool _Accum, int, EL, bool, E": "__bf16, 2, true"}.get(m.group(3), m.group(3) or "")
-        words = {"true": 1, "false": 0, "float": "float", "__bf16": "h16", "_Float16": "h16"}
-        return m.group(1), m.group(2), [words[a] if a in words else int(a) for a in args.split(", ")] if args else []
-    m = re.match(r"_ZN(\d+)", name)
-    assert m, name
-    at = 3 + len(m.group(1))
-    ns, at = name[at:at + int(m.group(1))], at + int(m.group(1))
-    m = re.match(r"(\d+)", name[at:])
-    at += len(m.group(1))
-    kernel, rest = name[at:at + int(m.group(1))], name[at + int(m.group(1)):]
-    m = re.match(r"I((?:Li\d+E|Lb[01]E|DF16_|DF16b|f)+)E", rest)
-    assert m, name
-    args = [int(t[2:-1]) if t[0] == "L" else "float" if t == "f" else "h16" for t in re.findall(r"Li\d+E|Lb[01]E|DF16_|DF16b|f", m.group(1))]
-    return ns, kernel, args
 
 
 def call(op, M, nseq, F, Fp, dtype, fp16_copy=False, p=0.0, operands=True, drop_bits=False, gh=False, dgamma=False, dconv=False, seg=(0, 0),

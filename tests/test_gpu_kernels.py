@@ -438,7 +438,7 @@ def test_cast_pad_group(ops, dev, dtype):
         assert float(taps[:, F:Fp].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize("M,D", [(333, 1024), (6700, 1024), (333, 768)])       # one row per workgroup; 3-4 rows per workgroup (the row-pair walk of the
+@pytest.mark.parametrize("M,D", [(333, 1024), (6700, 1024), (333, 768), (5, 1028), (3, 4096)])       # one row per workgroup; 3-4 rows per workgroup (the row-pair walk of the
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])   # d = 1024 backward: both register sets, both LDS parities); the general kernel
 def test_layernorm_fwd_bwd(ops, dev, dtype, M, D):
     g = torch.Generator().manual_seed(1)
@@ -1451,7 +1451,7 @@ def test_gemm_mx16_vs_fp64(ops, dev, M, N, K, planes_out):
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
-@pytest.mark.parametrize("M,D", [(333, 1024), (6700, 1024), (150, 768)])
+@pytest.mark.parametrize("M,D", [(333, 1024), (6700, 1024), (150, 768), (5, 1028), (3, 4096)])
 def test_layernorm_fwd_planes(ops, dev, dtype, M, D):
     """omlm_layernorm_fwd_planes: the hi plane is bit for bit omlm_layernorm_fwd's output, hi + lo is the fp32 result to the lo plane's
     rounding; statistics identical."""
@@ -1546,7 +1546,7 @@ def _check_mx_planes(P, rows, K, hi, lo_ref, name, bound):
     return err
 
 
-@pytest.mark.parametrize("M,D", [(333, 1024), (6700, 1024), (150, 768), (40, 64)])
+@pytest.mark.parametrize("M,D", [(333, 1024), (6700, 1024), (150, 768), (40, 64), (9, 1028), (8, 4096)])       # (rows 5 and 7 are special below)
 def test_layernorm_fwd_mx(ops, dev, M, D):
     """omlm_layernorm_fwd_mx: the half hi plane and the statistics are bit for bit omlm_layernorm_fwd's; the fp8 planes and row scales are
     what omlm_gemm_mx16 defines (written into an UNINITIALISED buffer: the kernel owns the row tails)."""
