@@ -272,10 +272,14 @@ int omlm_embed_gather_bwd(const int* ids, const int* seg, const int* posidx,
    (TokenConditionedTransformer.forward, :116-130,:139-145) and the forgetful mask (generate_mask_with_prob, utils.py:49-56: the n_drop
    largest of scores[b, 1:] are dropped).  ids[s]: int64 [B, len[s]]; labels[s]: int32 [B, len[s] + 1] or null; ids32 int32 [B, N]
    (-2 = start token, offsets applied); keymask uint8 [B, N]; scores fp32 [B, N] or null (no forgetful mask);
-   N = sum_s (len[s] + 1) + (nseq - 1). */
+   N = sum_s (len[s] + 1) + (nseq - 1).
+   Condition drop (training side of classifier-free guidance, below): null_u fp32 [B] or null.  With null_u, sample b trains on the null
+   condition iff null_u[b] < null_p: at every id position p < len[0] of sequence 0 ids32 is -1 (the pad embedding's zero row) and the key
+   mask is 1 before the forgetful mask is ANDed in, whatever the raw id was; the appended eos of sequence 0, every other sequence and all
+   labels are what they are without it.  null_u == NULL: null_p is not read and the launch does what it always did.  nseq >= 2 then. */
 int omlm_prepare_train_batch(const long long* const* ids, int* const* labels, const int* len, const int* eos, const int* Q,
                              const int* codebook, int nseq, int B, int pad_id, const float* scores, int n_drop,
-                             int* ids32, unsigned char* keymask, int N, void* stream);
+                             int* ids32, unsigned char* keymask, int N, const float* null_u, float null_p, void* stream);
 
 /* F.cross_entropy(logits, labels) pieces (open_musiclm.py:401-405): per-row lse + NLL sum; (softmax-onehot)*coef*g. */
 int omlm_cross_entropy_fwd(const float* logits, const int* labels, float* row_lse, float* nll_sum,
@@ -565,6 +569,24 @@ int omlm_sample(const omlm_sample_args* args, void* stream);
  * omlm_sample plus the log-probabilities of the id it returns.  lp_model / lp_sampled: [B] floats, or [steps, B]
  * indexed by *step_dev when args->step_dev is given (like hist); either may be NULL; both NULL: exactly omlm_sample. */
 int omlm_sample_lp(const omlm_sample_args* args, float* lp_model, float* lp_sampled, void* stream);
+
+/* Classifier-free guidance on the condition (token sequence 0, the CLAP tokens).  The null condition is the pad embedding at every id
+ * position of that sequence: raw id -1 - codebook (p mod Q) at position p, which is -1 after the per-quantizer offset and therefore the
+ * zero row of the gather; the appended eos, the start tokens and every other sequence are unchanged.  A guided call of P prompts decodes
+ * 2P rows: rows [0, P) conditional, rows [P, 2P) their null twins.  For one row, with l the conditional logits, n the null twin's and
+ * s = scale, in fp32 with exactly three roundings and no contraction:
+ *     g_c = n_c + (s * (l_c - n_c))        i.e. __fadd_rn(n_c, __fmul_rn(s, __fsub_rn(l_c, n_c)))
+ * so float32 arithmetic in that order reproduces it bit for bit (s = 1 does not return l_c bit for bit; callers do not launch for s = 1).
+ * Everything downstream is the sampler above applied to g: forbidden eos, top-k, nucleus, Gumbel, lp_sampled -- and lp_model, which
+ * on a guided row is therefore the log-softmax of g at T = 1, not of the model's conditional logits.
+ * cond / null / out: [rows, ld] fp32, columns V .. ld - 1 are not written; out may alias cond.  16-byte loads where ld % 4 == 0 and the
+ * three bases are 16-byte aligned, scalar loads otherwise and on the tail of a row.  One launch; scale finite and >= 0, V <= 2^24. */
+int omlm_guide_logits(const float* cond, const float* null, float* out, int rows, int V, int ld, float scale, void* stream);
+
+/* The twin copy of a guided decode cycle, one launch: ids_twin[r] = ids[r] and x_twin[r, :] = x[r, :] for r < rows -- the ids the sampler
+ * picked for the conditional rows and the embedding rows it gathered, handed to the null twins.  Either pair of pointers may be NULL
+ * (both NULL: no launch); a source without its twin is refused.  x / x_twin: [rows, D] fp32. */
+int omlm_decode_twin(const long long* ids, long long* ids_twin, const float* x, float* x_twin, int rows, int D, void* stream);
 
 /* KV-cached AR decode step: ONE new row (index *pos_dev) per sample through all L layers and the logit head of the quantizer
  * that row predicts -- replaces the reference's full re-forward per sampled id (wrapper.generate, open_musiclm.py:301-321;

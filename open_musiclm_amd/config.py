@@ -141,6 +141,8 @@ class SingleStageTrainerConfig:
     ema_decay: Optional[float] = None
     ema_update_after_step: int = 0
     ema_warmup: bool = True
+    # condition drop for classifier-free guidance (TokenConditionedTransformerWrapper; no reference counterpart): off at 0
+    null_cond_prob: float = 0.
 
 
 @dataclass

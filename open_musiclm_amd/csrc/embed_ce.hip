@@ -304,7 +304,8 @@ extern "C" int omlm_cross_entropy_bwd(const float* logits, const int* labels, co
 //                  largest of scores[b, 1:] are dropped (position 0 never is; ties by lowest index, like the sampler)
 #define PREP_NV_MAX 64                               /* register slots per lane: N <= 4096 */
 struct PrepSeq { const long long* ids; int* labels; int len; int eos; int Q; int codebook; int start; };
-struct PrepArgs { PrepSeq s[MAX_SEQ]; int nseq; int B; int N; int pad_id; const float* scores; int n_drop; int* ids32; unsigned char* keymask; };
+struct PrepArgs { PrepSeq s[MAX_SEQ]; int nseq; int B; int N; int pad_id; const float* scores; int n_drop; int* ids32; unsigned char* keymask;
+                  const float* null_u; float null_p; };
 
 __device__ __forceinline__ unsigned prep_ord(float v) { const unsigned u = f2u(v); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 
@@ -349,6 +350,9 @@ __global__ __launch_bounds__(64) void prepare_train_batch_kernel(PrepArgs a) {
         thr = t; n_eq_keep = exact ? 0x7fffffff : a.n_drop - ng;
     }
     // ---- ids / labels / mask ----
+    // condition drop (classifier-free guidance, include/omlm.h): sample b with null_u[b] < null_p trains on the null condition -- every id
+    // position of sequence 0 becomes the pad embedding's zero row (-1 after the offset) and stays attended; its appended eos is untouched
+    const bool null_cond = a.null_u != nullptr && a.null_u[b] < a.null_p;
     int seen_eq = 0;
     const unsigned long long below = (1ull << lane) - 1ull;
 #pragma unroll
@@ -378,6 +382,7 @@ __global__ __launch_bounds__(64) void prepare_train_batch_kernel(PrepArgs a) {
                 if (!live) raw = 0;
             }
             id = (int)raw + (sq.Q > 1 ? sq.codebook * (p % sq.Q) : 0);
+            if (null_cond && si == 0 && p < sq.len) { id = -1; live = 1; }
         }
         idrow[n] = id;
         mrow[n] = (live && !drop) ? 1 : 0;
@@ -393,9 +398,10 @@ __global__ __launch_bounds__(64) void prepare_train_batch_kernel(PrepArgs a) {
 
 // ids[s]: int64 [B, len[s]] (flattened 'b ... -> b (...)'); labels[s]: int32 [B, len[s] + 1] or null; ids32 / keymask: [B, N] with
 // N = sum_s (len[s] + 1) + (nseq - 1) ... i.e. one start token per sequence, an appended eos for every sequence but the last.
+// null_u: fp32 [B] or null (no condition drop; null_p is then not read); with it, sequence 0 must be a conditioning sequence (nseq >= 2).
 extern "C" int omlm_prepare_train_batch(const long long* const* ids, int* const* labels, const int* len, const int* eos, const int* Q,
                                         const int* codebook, int nseq, int B, int pad_id, const float* scores, int n_drop,
-                                        int* ids32, unsigned char* keymask, int N, void* stream) {
+                                        int* ids32, unsigned char* keymask, int N, const float* null_u, float null_p, void* stream) {
     if (B <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(ids && len && eos && Q && codebook && ids32 && keymask && nseq >= 1 && nseq <= MAX_SEQ, "prepare_train_batch arguments");
     OMLM_CHECK_ARG(N >= 1 && N <= 64 * PREP_NV_MAX, "prepare_train_batch: N must be 1..4096");
@@ -410,7 +416,9 @@ extern "C" int omlm_prepare_train_batch(const long long* const* ids, int* const*
     }
     OMLM_CHECK_ARG(pos == N, "prepare_train_batch: N does not match the sequence lengths");
     OMLM_CHECK_ARG(!scores || (n_drop >= 0 && n_drop < N), "prepare_train_batch: n_drop");
+    OMLM_CHECK_ARG(!null_u || (nseq >= 2 && null_p >= 0.f && null_p <= 1.f), "prepare_train_batch: the condition drop needs two sequences and 0 <= null_p <= 1");
     a.nseq = nseq; a.B = B; a.N = N; a.pad_id = pad_id; a.scores = scores; a.n_drop = scores ? n_drop : 0; a.ids32 = ids32; a.keymask = keymask;
+    a.null_u = null_u; a.null_p = null_u ? null_p : 0.f;
     const int nv = (N + 63) / 64;
     if (nv <= 9)       hipLaunchKernelGGL(prepare_train_batch_kernel<9>, dim3(B), dim3(64), 0, as_stream(stream), a);
     else if (nv <= 18) hipLaunchKernelGGL(prepare_train_batch_kernel<18>, dim3(B), dim3(64), 0, as_stream(stream), a);

@@ -736,3 +736,72 @@ extern "C" int omlm_sample_embed_at_rng(const float* logits, unsigned seed_lo, u
                              emb_table, emb_row_offset, emb_rows, x, D};
     return sample_checked("omlm_sample_embed_at_rng", a, NEED_STEP_DEV | NEED_EMBED, nullptr, nullptr, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Classifier-free guidance around the sampler (include/omlm.h).  Two small kernels that sit in front of and behind the sampler launch
+// of a guided decode cycle; the sampler kernels above are what they were.
+//
+// guide: out[r, c] = null[r, c] + scale * (cond[r, c] - null[r, c]) for c < V, three fp32 roundings (sub, mul, add) and no contraction,
+// so a float32 restatement gives the same bits.  One thread forms four neighbouring columns: a 16-byte load of each row where VEC (ld a
+// multiple of 4 and the three bases 16-byte aligned), four scalar loads otherwise; a group that reaches past V is finished by scalars, and
+// columns V .. ld - 1 are never written.  out may be cond: a thread reads its columns before it writes them and no other thread reads them.
+// The rule is __fadd_rn(n, __fmul_rn(s, __fsub_rn(l, n))).  It is written with plain operators under `fp contract(off)`: this compiler's
+// __fmul_rn / __fadd_rn are the plain operators themselves, compiled with contraction allowed, and fuse into one v_fma after inlining.
+__device__ __forceinline__ float guide_one(float l, float n, float s) {
+#pragma clang fp contract(off)
+    const float d = l - n;
+    const float m = s * d;
+    return n + m;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void guide_logits_kernel(const float* cond, const float* null, float* out, int V, int ld, float s) {
+    const size_t base = (size_t)blockIdx.x * ld;                       // one row per blockIdx.x, 1024 columns per blockIdx.y
+    const int c0 = 4 * (blockIdx.y * 256 + threadIdx.x);
+    if (c0 >= V) return;
+    if (VEC && c0 + 3 < V) {
+        const float4 l = *(const float4*)(cond + base + c0);
+        const float4 n = *(const float4*)(null + base + c0);
+        float4 g;
+        g.x = guide_one(l.x, n.x, s); g.y = guide_one(l.y, n.y, s); g.z = guide_one(l.z, n.z, s); g.w = guide_one(l.w, n.w, s);
+        *(float4*)(out + base + c0) = g;
+        return;
+    }
+    const int c1 = c0 + 4 < V ? c0 + 4 : V;
+    for (int c = c0; c < c1; ++c) out[base + c] = guide_one(cond[base + c], null[base + c], s);
+}
+
+extern "C" int omlm_guide_logits(const float* cond, const float* null, float* out, int rows, int V, int ld, float scale, void* stream) {
+    if (rows <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(cond && null && out && V > 0 && ld >= V && V <= (1 << 24), "guide_logits arguments (0 < V <= ld, V <= 2^24)");
+    OMLM_CHECK_ARG(scale >= 0.f && scale <= 3.4028234e38f, "guide_logits: scale must be a finite number >= 0");
+    const bool vec = ld % 4 == 0 && (((size_t)cond | (size_t)null | (size_t)out) & 15) == 0;
+    const dim3 grid(rows, (V + 1023) / 1024);
+    if (vec) hipLaunchKernelGGL(guide_logits_kernel<true>, grid, dim3(256), 0, as_stream(stream), cond, null, out, V, ld, scale);
+    else     hipLaunchKernelGGL(guide_logits_kernel<false>, grid, dim3(256), 0, as_stream(stream), cond, null, out, V, ld, scale);
+    return omlm_post_launch("omlm_guide_logits");
+}
+
+// twin: what the sampler left for the conditional rows -- the sampled ids [rows] and their gathered embedding rows [rows, D] -- copied to
+// the null twins' halves, in one launch.  Workgroup r copies id r (thread 0) and row r; either pair of pointers may be null.
+template <bool VEC>
+__global__ __launch_bounds__(256) void decode_twin_kernel(const long long* ids, long long* ids_twin, const float* x, float* x_twin, int D) {
+    const int r = blockIdx.x;
+    if (ids && threadIdx.x == 0) ids_twin[r] = ids[r];
+    if (!x) return;
+    const float* src = x + (size_t)r * D;
+    float* dst = x_twin + (size_t)r * D;
+    if (VEC) for (int i = threadIdx.x; i < D / 4; i += 256) ((float4*)dst)[i] = ((const float4*)src)[i];
+    else     for (int i = threadIdx.x; i < D; i += 256) dst[i] = src[i];
+}
+
+extern "C" int omlm_decode_twin(const long long* ids, long long* ids_twin, const float* x, float* x_twin, int rows, int D, void* stream) {
+    if (rows <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG((ids != nullptr) == (ids_twin != nullptr) && (x != nullptr) == (x_twin != nullptr), "decode_twin: a source without its twin");
+    if (!ids && !x) return OMLM_OK;
+    OMLM_CHECK_ARG(!x || D > 0, "decode_twin: D");
+    const bool vec = x && D % 4 == 0 && (((size_t)x | (size_t)x_twin) & 15) == 0;
+    if (vec) hipLaunchKernelGGL(decode_twin_kernel<true>, dim3(rows), dim3(256), 0, as_stream(stream), ids, ids_twin, x, x_twin, D);
+    else     hipLaunchKernelGGL(decode_twin_kernel<false>, dim3(rows), dim3(256), 0, as_stream(stream), ids, ids_twin, x, x_twin, D);
+    return omlm_post_launch("omlm_decode_twin");
+}

@@ -17,6 +17,10 @@ A call holds ``max_batch`` samples (8, or 16 on the matrix-core step kernels); `
 The K/V cache is fp32 by default.  ``CachedDecoder(..., kv_cache="operand")`` keeps it in the precision's 16-bit operand type: the step kernels
 round every key and value to that type before they store them, so the 16-bit cache holds the same numbers in half the bytes (``cache_bytes``)
 and the logits are the same bit for bit.
+
+Classifier-free guidance on the condition (token sequence 0; include/omlm.h): a guided call of P prompts is a decoder of 2P rows, the
+prompts followed by their null twins, and ``SamplingLoop(..., guidance=s)`` samples P ids per step from ``null + s (cond - null)`` --
+one combine launch in front of the sampler, one twin copy behind it, the step kernels untouched.
 """
 from __future__ import annotations
 
@@ -357,38 +361,52 @@ class SamplingLoop:
     (include/omlm.h).
     ``logprobs``: the loop owns ``lp_model`` and ``lp_sampled`` ([n_new, B] fp32, device resident: the two log-probabilities of every
     sampled id, include/omlm.h) and the calls go through omlm_sample_lp instead, which writes row *step_dev of each -- a
-    captured cycle stays valid.  The ids are those of the loop without it; ``run()`` still returns them."""
+    captured cycle stays valid.  The ids are those of the loop without it; ``run()`` still returns them.
+    ``guidance`` = s (classifier-free guidance, include/omlm.h; None or 1: off, the loop is the one it is without the argument): the
+    decoder holds B = 2P rows -- rows [0, P) the prompts, rows [P, 2P) their null twins, stacked by the caller for ``prefill`` -- and the
+    loop samples P ids per step: the uniforms are [n_new, P, V1] (counter stream: row0 is the global PROMPT index), ``hist``, ``lp_*`` and
+    the result are sized P.  Per id: omlm_guide_logits forms g = null + s (cond - null) from the two halves of dec.logits into a buffer of
+    the loop that the sampler reads (so ``lp_model`` is the log-softmax of g); the sampler gathers the embedding rows of the P ids;
+    omlm_decode_twin hands ids and rows to the null half; then the step runs on all 2P rows as it is.  Two more launches per id, all
+    pointers fixed: the captured cycle holds all of it."""
 
     def __init__(self, dec: CachedDecoder, first_logits: torch.Tensor, uniforms: Optional[torch.Tensor], n0: int, n_new: int, topk: int,
                  temperature: float, forbid_by_phase: Sequence[bool], use_graph: bool = True, rng=None, top_p=None,
-                 logprobs: bool = False):
+                 logprobs: bool = False, guidance=None):
         ops.check_sampler_width(dec.V1)                    # before any launch: the loop's first sampler call would refuse it
         self.top_p = ops.check_top_p(top_p)                # 1.0: no nucleus
+        self.guidance = ops.check_cond_scale(guidance, "guidance")        # None: off
+        if self.guidance is not None and dec.B % 2:
+            raise ValueError(f"SamplingLoop: guidance needs a decoder of 2P rows (prompts, then their null twins); it holds {dec.B}")
         if (uniforms is None) == (rng is None):
             raise ValueError("SamplingLoop: give either the uniforms [n_new, B, V1] or rng=(seed, row0), not both and not neither")
         self.dec, self.n0, self.n_new, self.topk, self.temperature = dec, n0, n_new, topk, float(temperature)
         self.forbid = [bool(f) for f in forbid_by_phase]
         dev = dec.logits.device
+        P = self.P = dec.B // 2 if self.guidance is not None else dec.B          # rows the sampler serves
         if rng is None:
-            assert uniforms.shape == (n_new, dec.B, dec.V1) and uniforms.dtype == torch.float32 and uniforms.is_contiguous()
+            assert uniforms.shape == (n_new, P, dec.V1) and uniforms.dtype == torch.float32 and uniforms.is_contiguous()
             self.U = uniforms
         else:
             # counter stream (include/omlm.h): sample b of this decoder draws u(step, row0 + b, c) from the seed -- no buffer; seed halves
             # and row0 are plain arguments, so a captured cycle holds for the whole call
             self.U = None
             self.seed, self.row0 = ops.split_seed(rng[0]), int(rng[1])
-        self.hist = torch.zeros(n_new, dec.B, device=dev, dtype=torch.long)
-        self.cur = torch.zeros(dec.B, device=dev, dtype=torch.long)
+        self.hist = torch.zeros(n_new, P, device=dev, dtype=torch.long)
+        self.cur = torch.zeros(dec.B, device=dev, dtype=torch.long)             # guided: the sampler writes [0, P), the twin copy [P, 2P)
         self.step_dev = torch.zeros(1, device=dev, dtype=torch.int32)
         self.logprobs = bool(logprobs)
-        self.lp_model = torch.zeros(n_new, dec.B, device=dev, dtype=torch.float32) if self.logprobs else None
-        self.lp_sampled = torch.zeros(n_new, dec.B, device=dev, dtype=torch.float32) if self.logprobs else None
+        self.lp_model = torch.zeros(n_new, P, device=dev, dtype=torch.float32) if self.logprobs else None
+        self.lp_sampled = torch.zeros(n_new, P, device=dev, dtype=torch.float32) if self.logprobs else None
+        # guided: the sampler reads the combined rows from here, dec.logits keeps both branches
+        self.guided = torch.zeros(P, dec.ldV, device=dev, dtype=torch.float32) if self.guidance is not None else None
+        src = dec.logits if self.guidance is None else self.guided
         # the sampler's argument blocks (ops.SampleArgs), built once: per quantizer phase, without and with the embedding gather of the
         # sampled id.  Every pointer in them is a fixed buffer of this loop or its decoder.
         seed, row0 = ((0, 0), 0) if rng is None else (self.seed, self.row0)
 
         def block(phase: int, embed: bool):
-            sa = ops.SampleArgs(ptr(dec.logits), dec.B, dec.V1, dec.ldV, ptr(self.U), *seed, 0, row0, ptr(self.step_dev), ptr(self.cur),
+            sa = ops.SampleArgs(ptr(src), P, dec.V1, dec.ldV, ptr(self.U), *seed, 0, row0, ptr(self.step_dev), ptr(self.cur),
                                 ptr(self.hist), self.topk, self.temperature, self.top_p, int(self.forbid[phase]))
             if embed:
                 sa.emb_table, sa.emb_row_offset, sa.emb_rows = dec.emb.data_ptr(), dec.codebook * phase if dec.Q > 1 else 0, dec.emb.shape[0]
@@ -406,12 +424,17 @@ class SamplingLoop:
         # with_decode, 32 launches per id: the sampler also gathers the embedding row of the id it picked (the step's first launch), and
         # the head kernel (the step's last) moves the row index and the sampler's step counter on
         sa = self._blocks[phase][with_decode]
+        P = self.P
+        if self.guidance is not None:      # g = null + s (cond - null) from the two halves of dec.logits, into the sampler's rows
+            call("omlm_guide_logits", ptr(dec.logits), dec.logits[P:].data_ptr(), ptr(self.guided), P, dec.V1, dec.ldV, self.guidance, stream_ptr())
         if self.logprobs:
             call("omlm_sample_lp", C.addressof(sa), ptr(self.lp_model), ptr(self.lp_sampled), stream_ptr())
         else:
             call("omlm_sample", C.addressof(sa), stream_ptr())
         if not with_decode:
             return
+        if self.guidance is not None:      # the null twins decode the same ids: ids and gathered embedding rows to rows [P, 2P)
+            call("omlm_decode_twin", ptr(self.cur), self.cur[P:].data_ptr(), ptr(dec.x), dec.x[P:].data_ptr(), P, dec.D, stream_ptr())
         if dec.pos_emb is not None:
             # + absolute position row of id k = n0 + (device step counter): device-side indexing, so a captured cycle stays valid
             dec.x.add_(dec.pos_emb.index_select(0, (self.step_dev + self.n0).long()))

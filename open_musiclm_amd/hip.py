@@ -69,7 +69,7 @@ SIGNATURES = {
     "omlm_ffmid_set_impl": [i32],
     "omlm_embed_gather_fwd": [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp],
     "omlm_embed_gather_bwd": [vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, f32, vp, vp, vp, vp],
-    "omlm_prepare_train_batch": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp],
+    "omlm_prepare_train_batch": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, f32, vp],
     "omlm_cross_entropy_fwd": [vp, vp, vp, vp, i32, i32, i32, vp, vp],
     "omlm_cross_entropy_bwd": [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, vp],
     "omlm_sumsq_accumulate": [vp, i64, vp, vp, vp],
@@ -105,6 +105,8 @@ SIGNATURES = {
     "omlm_sample_embed_at_rng": [vp, u32, u32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, vp, i64, i64, vp, i32, vp],
     "omlm_sample": [vp, vp],
     "omlm_sample_lp": [vp, vp, vp, vp],
+    "omlm_guide_logits": [vp, vp, vp, i32, i32, i32, f32, vp],
+    "omlm_decode_twin": [vp, vp, vp, vp, i32, i32, vp],
     "omlm_probe_tr16": [vp, vp],
 }
 _RESTYPES = {"omlm_last_error": C.c_char_p, "omlm_gemm_tail_workspace_bytes": C.c_longlong, "omlm_gemm_mx16_workspace_bytes": C.c_longlong, "omlm_ffmid_bwd_workspace_bytes": C.c_longlong,

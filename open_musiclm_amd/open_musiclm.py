@@ -138,6 +138,28 @@ class TokenConditionedTransformer(nn.Module):
 
 _GENERATE_MASK_ORIG = generate_mask_with_prob
 
+
+def null_condition_ids(info: TokenSequenceInfo, n: int, device=None) -> torch.Tensor:
+    """The null condition of classifier-free guidance (include/omlm.h) as raw ids of `n` positions of a sequence described by `info`:
+    -1 - codebook_size * (p mod Q) at position p -- -1 after the per-quantizer offset, which every embedding path (get_embeds, the gather
+    kernel, the oracle) gives the zero row of the pad embedding."""
+    p = torch.arange(n, device=device, dtype=torch.long)
+    return -1 - info.codebook_size * (p % info.num_quantizers) if info.num_quantizers > 1 else torch.full_like(p, -1)
+
+
+def null_twin(cond_ids: torch.Tensor, info: TokenSequenceInfo, n_ids: int) -> torch.Tensor:
+    """cond_ids [B, L] (the flattened condition, an eos possibly appended behind its n_ids id positions) with every id position replaced by
+    the null condition; what lies behind them (the eos) is kept."""
+    out = cond_ids.clone()
+    out[:, :n_ids] = null_condition_ids(info, n_ids, cond_ids.device)
+    return out
+
+
+def _require_condition(token_sequences, what: str):
+    if len(token_sequences) < 2:
+        raise ValueError(f"{what}: the condition is token sequence 0 in front of a predicted sequence; this model has a single token "
+                         "sequence and nothing to drop or guide on")
+
 # generate(return_logprobs=True): the two log-probabilities (include/omlm.h) of every id the call sampled, fp32 [B, time steps, Q] each
 LogProbs = namedtuple("LogProbs", ["model", "sampled"])
 
@@ -155,8 +177,16 @@ class TokenConditionedTransformerWrapper(nn.Module):
     """open_musiclm.py:219-410."""
 
     def __init__(self, *, transformer: TokenConditionedTransformer, pad_id=-1, unique_consecutive=True,
-                 cross_entropy_loss_weights: Optional[List[float]] = None, mask_prob=0.15):
+                 cross_entropy_loss_weights: Optional[List[float]] = None, mask_prob=0.15, null_cond_prob=0.):
+        """null_cond_prob (extension; default 0: off, nothing is drawn): the training side of classifier-free guidance.  In training mode
+        sample b of a batch trains on the null condition (null_condition_ids at every id position of token sequence 0, ATTENDED; its
+        appended eos, every other sequence and all labels untouched) iff u_b < null_cond_prob, u one torch.rand(B) drawn after the forgetful
+        mask's randn.  A number in [0, 1) (1: every sample; tests).  eval() never drops.  ``generate(cond_scale=...)`` is meaningful only
+        on weights trained with it."""
         super().__init__()
+        self.null_cond_prob = ops.check_null_cond_prob(null_cond_prob)          # refused by name
+        if self.null_cond_prob > 0:
+            _require_condition(transformer.token_sequences, "null_cond_prob")
         self.transformer = transformer
         self.token_sequences = transformer.token_sequences
         self.unique_consecutive = unique_consecutive
@@ -175,7 +205,7 @@ class TokenConditionedTransformerWrapper(nn.Module):
     def generate(self, *, conditioning_token_ids: List[torch.Tensor], pred_token_ids: Optional[torch.Tensor] = None,
                  max_time_steps=512, filter_thres=0.9, temperature=1., include_eos_in_output=False,
                  append_eos_to_conditioning_tokens=True, allow_eos_in_output=False, uniforms=None, sampler_rng=None,
-                 sampler_seed=None, top_p=None, kv_cache=None, return_logprobs=False, **kwargs):
+                 sampler_seed=None, top_p=None, kv_cache=None, return_logprobs=False, cond_scale=None, **kwargs):
         """AR sampling (open_musiclm.py:253-326).  Every step re-runs the full causal forward over the grown
         sequence like the reference (results are identical to a KV-cached decode because the stack is strictly
         causal); only the last position's logits are formed, and eos suppression + top-k + Gumbel-argmax run in
@@ -194,7 +224,18 @@ class TokenConditionedTransformerWrapper(nn.Module):
         device, for the ids THIS call sampled (not a supplied ``pred_token_ids``): ``model`` is the log-probability of the id under the
         model's own distribution (T = 1, all entries), ``sampled`` under the distribution it was drawn from (top-k, nucleus,
         temperature, eos rule) -- include/omlm.h.  The sampler kernels write them in the launch that picks the id, on every route and with
-        every source of uniforms; the flag changes no id.  Where the returned id is the after-eos mask value both numbers are 0.0."""
+        every source of uniforms; the flag changes no id.  Where the returned id is the after-eos mask value both numbers are 0.0.
+        ``cond_scale`` = s: classifier-free guidance on the condition, token sequence 0 (include/omlm.h).  Every prompt is decoded beside
+        its null twin (null_twin: the pad embedding's zero row at every id position of the condition, everything else the same) and the
+        ids are sampled from g = null + s (cond - null), formed in fp32 by omlm_guide_logits; top-k, nucleus, temperature, the eos rule
+        and both log-probabilities apply to g (``LogProbs.model`` is then the log-softmax of g).  A finite number >= 0; None or 1: off,
+        the call launches exactly what it launches without the argument.  A guided call of P prompts is a decode call of 2P rows, so a
+        decode call holds decode.max_call_batch // 2 prompts; uniforms (``uniforms``: [steps, P, V+1]), ids and log-probabilities cover
+        the P prompts only.  Meaningful only on weights trained with ``null_cond_prob``: any other checkpoint has never seen the null
+        condition."""
+        cond_scale = ops.check_cond_scale(cond_scale)                           # before any device work; None = off
+        if cond_scale is not None:
+            _require_condition(self.token_sequences, "cond_scale")
         assert len(conditioning_token_ids) == len(self.token_sequences) - 1
         ops.check_sampler_width(self.token_sequences[-1].codebook_size + 1)      # before any device work
         top_p = ops.check_top_p(top_p)                                          # likewise; 1.0 = off
@@ -216,8 +257,15 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 cond[i] = batch_unique_consecutive(cond[i], pad_value=self.pad_id)
         if pred_info.unique_consecutive:
             sampled = batch_unique_consecutive(sampled, pad_value=self.pad_id)
+        n_cond_ids = _flat(cond[0]).shape[-1] if cond_scale is not None else 0      # id positions of the condition (before its eos)
         if append_eos_to_conditioning_tokens:
             cond = [append_eos_id(_flat(t).long(), e) for t, e in zip(cond, self.eos_ids)]
+        if cond_scale is not None:          # rows [0, P) the prompts, rows [P, 2P) their null twins: only the condition differs
+            cond = [_flat(t).long() for t in cond]
+            twin = [null_twin(cond[0], self.token_sequences[0], n_cond_ids)] + cond[1:]
+            guide_kw = dict(guidance=cond_scale)
+        else:
+            guide_kw = {}                                                       # (off: the loops are built as they always were)
 
         V1 = pred_info.codebook_size + 1
         k = max(int((1 - filter_thres) * V1), 1)
@@ -230,6 +278,8 @@ class TokenConditionedTransformerWrapper(nn.Module):
         if counter and sampler_seed is None and n_new > 0:
             sampler_seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), device=device, dtype=torch.long)) & 0xFFFFFFFFFFFFFFFF
         use_cache = kwargs.pop('use_cache', True) and decode.supports(self.transformer, 1, prompt_rows=prompt_rows) and n_new > 0
+        if use_cache and cond_scale is not None:       # a pair is two rows of a decode call; where no call holds two, the re-forward route
+            use_cache = decode.supports(self.transformer, 2, self.transformer._precision(), prompt_rows=prompt_rows, wide=True)
         if use_cache:
             # KV-cached decode (decode.py): one new row per sampled id instead of the reference's full re-forward.
             # Ids are sampled straight into a [steps, B] buffer that the next decode step reads: no per-step cat / copies.
@@ -251,16 +301,23 @@ class TokenConditionedTransformerWrapper(nn.Module):
             pieces, lp_pieces = [], []
             lp_kw = dict(logprobs=True) if return_logprobs else {}      # (False: the loops are built as they always were)
             group = decode.max_call_batch(self.transformer, self.transformer._precision())
+            if cond_scale is not None:
+                group //= 2                                                     # pairs per call
             for b0 in range(0, batch, group):
                 b1 = min(batch, b0 + group)
-                dec = decode.CachedDecoder(self.transformer, b1 - b0, rows, self.transformer._precision(), wide=True, **kv_kw)
-                last = dec.prefill([t[b0:b1] for t in cond] + [sampled[b0:b1]])
+                if cond_scale is not None:
+                    dec = decode.CachedDecoder(self.transformer, 2 * (b1 - b0), rows, self.transformer._precision(), wide=True, **kv_kw)
+                    last = dec.prefill([torch.cat((c[b0:b1], t[b0:b1]), dim=0) for c, t in zip(cond, twin)] +
+                                       [torch.cat((sampled[b0:b1], sampled[b0:b1]), dim=0)])
+                else:
+                    dec = decode.CachedDecoder(self.transformer, b1 - b0, rows, self.transformer._precision(), wide=True, **kv_kw)
+                    last = dec.prefill([t[b0:b1] for t in cond] + [sampled[b0:b1]])
                 if counter:            # sample b draws u(step, b, c) whichever piece it rides in
                     loop = decode.SamplingLoop(dec, last, None, n0, n_new, k, temperature, forbid, use_graph=use_graph, rng=(sampler_seed, b0),
-                                               top_p=top_p, **lp_kw)
+                                               top_p=top_p, **lp_kw, **guide_kw)
                 else:
                     loop = decode.SamplingLoop(dec, last, U[:, b0:b1].contiguous(), n0, n_new, k, temperature, forbid, use_graph=use_graph,
-                                               top_p=top_p, **lp_kw)
+                                               top_p=top_p, **lp_kw, **guide_kw)
                 pieces.append(loop.run().t())                      # [b, n_new]
                 if return_logprobs:
                     lp_pieces.append((loop.lp_model.t(), loop.lp_sampled.t()))
@@ -272,9 +329,16 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 uniforms = UNIFORM_SOURCE(n_new, batch, V1)
             if return_logprobs:                                     # [ids, B]: row `step` is written by the launch that samples id `step`
                 lp_model, lp_sampled = (torch.zeros(n_new, batch, device=device) for _ in range(2))
+            if cond_scale is not None:
+                cond2 = [torch.cat((c, t), dim=0) for c, t in zip(cond, twin)]
             for _t in tqdm(range(first_step, max_time_steps), desc='generating predicted tokens'):
                 for ind in range(Q):
-                    last = self.transformer.last_logits(cond + [sampled])
+                    if cond_scale is not None:      # one 2B forward, then the combine in place over the conditional half
+                        both = self.transformer.last_logits(cond2 + [torch.cat((sampled, sampled), dim=0)])
+                        last = both[:batch]
+                        ops.guide_logits(last, both[batch:], last, V1, cond_scale)
+                    else:
+                        last = self.transformer.last_logits(cond + [sampled])
                     forbid = (not allow_eos_in_output) or (ind != Q - 1)
                     if counter:
                         src = dict(seed=sampler_seed, step=step)
@@ -299,12 +363,17 @@ class TokenConditionedTransformerWrapper(nn.Module):
     @eval_decorator
     @torch.no_grad()
     def score(self, *, conditioning_token_ids: List[torch.Tensor], pred_token_ids: torch.Tensor,
-              append_eos_to_conditioning_tokens=True) -> torch.Tensor:
+              append_eos_to_conditioning_tokens=True, cond_scale=None) -> torch.Tensor:
         """The teacher-forced twin of ``generate(return_logprobs=True).model``: fp32 [B, T, Q], entry (b, t, q) the log-probability
         (lp_model of include/omlm.h: the model's own distribution, T = 1, all entries) of id ``pred_token_ids[b, t, q]`` given the
         conditioning and the ids before it -- under the logits ``transformer.last_logits(cond + [pred_flat[:, :t Q + q]])`` gives.
         One forward over the whole sequence with generate's semantics (no key mask, the conditioning eos appended and embedded);
-        omlm_cross_entropy_fwd writes every row's log-sum-exp, the rest is a gather and a subtract."""
+        omlm_cross_entropy_fwd writes every row's log-sum-exp, the rest is a gather and a subtract.
+        ``cond_scale`` = s (None or 1: off): the twin of ``generate(return_logprobs=True, cond_scale=s).model`` -- one forward over the 2B
+        rows of prompts and null twins, omlm_guide_logits over every row, then the same; the log-softmax of g."""
+        cond_scale = ops.check_cond_scale(cond_scale)                           # before any device work; None = off
+        if cond_scale is not None:
+            _require_condition(self.token_sequences, "cond_scale")
         assert len(conditioning_token_ids) == len(self.token_sequences) - 1
         pred_info = self.token_sequences[-1]
         assert not (self.unique_consecutive and pred_info.unique_consecutive), "score: a unique_consecutive predicted sequence has no [B, T, Q] form"
@@ -323,12 +392,22 @@ class TokenConditionedTransformerWrapper(nn.Module):
         for i, info in enumerate(self.token_sequences[:-1]):
             if info.unique_consecutive:
                 cond[i] = batch_unique_consecutive(cond[i], pad_value=self.pad_id)
+        n_cond_ids = _flat(cond[0]).shape[-1] if cond_scale is not None else 0
         if append_eos_to_conditioning_tokens:
             cond = [append_eos_id(_flat(t).long(), e) for t, e in zip(cond, self.eos_ids)]
+        rows_pred = pred
+        if cond_scale is not None:          # rows [0, B) the prompts, rows [B, 2B) their null twins
+            cond = [_flat(t).long() for t in cond]
+            cond = [torch.cat((cond[0], null_twin(cond[0], self.token_sequences[0], n_cond_ids)), dim=0)] + [torch.cat((t, t), dim=0) for t in cond[1:]]
+            rows_pred = torch.cat((pred, pred), dim=0)
         # row j of the predicted sequence (its start token, then the ids) holds the logits after pred[:, :j]: rows 0 .. L - 1 score the L ids,
         # the last row (what would follow them) carries the ignore label
-        bufs, _, _ = engine.run_forward(self.transformer, cond + [pred], None, True, False, self.transformer._precision())
+        bufs, _, _ = engine.run_forward(self.transformer, cond + [rows_pred], None, True, False, self.transformer._precision())
         buf = bufs[-1]
+        if cond_scale is not None:
+            assert buf.shape[0] == 2 * batch * (L + 1), (buf.shape, batch, L)
+            buf, null = buf[:batch * (L + 1)], buf[batch * (L + 1):]
+            ops.guide_logits(buf, null, buf, V1, cond_scale)
         assert buf.shape[0] == batch * (L + 1), (buf.shape, batch, L)
         labels = F.pad(pred, (0, 1), value=-1).to(torch.int32).reshape(-1).contiguous()
         lse = torch.empty(buf.shape[0], device=device)
@@ -359,11 +438,14 @@ class TokenConditionedTransformerWrapper(nn.Module):
         if self.mask_prob > 0 and self.training:
             n_drop = min(int(N * self.mask_prob), N - 1)
             scores = torch.randn((B, N), device=device)
+        null_kw = {}
+        if self.null_cond_prob > 0 and self.training:      # the condition drop of _prepare: the same draw, in the same place
+            null_kw = dict(null_u=torch.rand(B, device=device), null_p=self.null_cond_prob)
         weights = [float(w) for w in self.cross_entropy_loss_weights]
         seqs = self.token_sequences
         ids32, keymask, labels, lens = ops.prepare_train_batch(ids, [int(e) for e in self.eos_ids], [s.num_quantizers for s in seqs],
                                                                [s.codebook_size for s in seqs], self.pad_id, scores, n_drop,
-                                                               [True] * len(ids))
+                                                               [True] * len(ids), **null_kw)
         prepared = engine.PreparedIds(ids32, lens)
         ignore = [False] * len(ids)
         if torch.is_grad_enabled():
@@ -375,7 +457,8 @@ class TokenConditionedTransformerWrapper(nn.Module):
         return loss, [l.transpose(1, 2) if l is not None else None for l in logits], labels
 
     def _prepare(self, all_token_ids, return_loss, input_has_eos):
-        """eos append, labels, last-token drop, key mask (open_musiclm.py:340-376)."""
+        """eos append, labels, last-token drop, key mask (open_musiclm.py:340-376); in training mode with null_cond_prob > 0 the
+        condition drop behind them (the constructor's docstring)."""
         batch, device = all_token_ids[0].shape[0], self.device
         ids = [_flat(t).to(device).long() for t in all_token_ids]
         if self.training:
@@ -397,8 +480,16 @@ class TokenConditionedTransformerWrapper(nn.Module):
             pieces.append(F.pad(live, (1, 0), value=True))            # the sequence's start token is always attended
         mask = torch.cat(pieces, dim=-1) if pieces else torch.empty((batch, 0), device=device, dtype=torch.bool)
         mask = F.pad(mask, (0, ids[-1].shape[-1] + 1), value=True)   # predicted tokens + their start token
-        if self.mask_prob > 0 and self.training:
-            mask = mask & generate_mask_with_prob(mask.shape, self.mask_prob, device=mask.device)
+        forget = generate_mask_with_prob(mask.shape, self.mask_prob, device=mask.device) if self.mask_prob > 0 and self.training else None
+        if self.null_cond_prob > 0 and self.training:
+            # u is drawn after the forgetful mask's randn; a dropped sample's condition ids become the null ids and are attended
+            n0 = ids[0].shape[-1] - (0 if input_has_eos else 1)               # id positions of the condition: not its appended eos
+            dropped = torch.rand(batch, device=device) < self.null_cond_prob
+            ids[0] = torch.where(dropped[:, None] & (torch.arange(ids[0].shape[-1], device=device) < n0)[None],
+                                 null_twin(ids[0], self.token_sequences[0], n0), ids[0])
+            mask[:, 1:1 + n0] |= dropped[:, None]
+        if forget is not None:
+            mask = mask & forget
         return ids, labels, mask
 
     def forward(self, *, all_token_ids: List[torch.Tensor], return_loss: bool = False, input_has_eos: bool = False,
@@ -485,10 +576,10 @@ def get_or_compute_acoustic_token_ids(coarse_token_ids, fine_token_ids, raw_audi
 class _Stage(nn.Module):
     """Shared plumbing of SemanticStage / CoarseStage / FineStage (open_musiclm.py:514-814)."""
 
-    def _make_wrapper(self, transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob):
+    def _make_wrapper(self, transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob=0.):
         self.transformer_wrapper = TokenConditionedTransformerWrapper(
             transformer=transformer, pad_id=pad_id, unique_consecutive=unique_consecutive,
-            cross_entropy_loss_weights=cross_entropy_loss_weights, mask_prob=mask_prob)
+            cross_entropy_loss_weights=cross_entropy_loss_weights, mask_prob=mask_prob, null_cond_prob=null_cond_prob)
 
     @property
     def device(self):
@@ -513,21 +604,22 @@ def _split_logprobs(result, kwargs):
 
 class SemanticStage(_Stage):
     def __init__(self, *, semantic_transformer: TokenConditionedTransformer, wav2vec=None, clap=None, pad_id=-1,
-                 unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15):
+                 unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15, null_cond_prob=0.):
         super().__init__()
         self.wav2vec, self.clap = wav2vec, clap
         num_semantic_tokens = semantic_transformer.token_sequences[1].codebook_size
         if exists(wav2vec):
             assert wav2vec.codebook_size == num_semantic_tokens, \
                 f'num_semantic_tokens on SemanticTransformer must be set to {wav2vec.codebook_size}'
-        self._make_wrapper(semantic_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob)
+        self._make_wrapper(semantic_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob)
 
     @eval_decorator
     @torch.no_grad()
     def generate(self, *, conditioning_text=None, conditioning_audio=None, input_audio=None, clap_token_ids=None,
                  semantic_token_ids=None, filter_thres=0.9, temperature=1., max_time_steps=30 * 25,
                  include_eos_in_output=False, append_eos_to_conditioning_tokens=True, **kwargs):
-        """``return_logprobs=True`` (like every sampling keyword, passed on to the wrapper): returns (ids, LogProbs)."""
+        """``return_logprobs=True`` (like every sampling keyword, passed on to the wrapper): returns (ids, LogProbs).  ``cond_scale``
+        (classifier-free guidance on the CLAP tokens) is such a keyword in every stage's generate."""
         clap_token_ids = get_or_compute_clap_token_ids(clap_token_ids, self.clap, conditioning_audio, conditioning_text)
         if exists(semantic_token_ids) or exists(input_audio):
             semantic_token_ids = get_or_compute_semantic_token_ids(semantic_token_ids, input_audio, self.wav2vec)
@@ -546,7 +638,7 @@ class SemanticStage(_Stage):
 
 class CoarseStage(_Stage):
     def __init__(self, *, coarse_transformer: TokenConditionedTransformer, wav2vec=None, clap=None, neural_codec=None,
-                 pad_id=-1, unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15):
+                 pad_id=-1, unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15, null_cond_prob=0.):
         super().__init__()
         self.wav2vec, self.clap, self.neural_codec = wav2vec, clap, neural_codec
         num_semantic_tokens = coarse_transformer.token_sequences[1].codebook_size
@@ -554,7 +646,7 @@ class CoarseStage(_Stage):
             assert wav2vec.codebook_size == num_semantic_tokens, \
                 f'num_semantic_tokens on CoarseTransformer must be set to {wav2vec.codebook_size}'
         self.num_coarse_quantizers = coarse_transformer.token_sequences[-1].num_quantizers
-        self._make_wrapper(coarse_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob)
+        self._make_wrapper(coarse_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob)
 
     @eval_decorator
     @torch.no_grad()
@@ -583,11 +675,11 @@ class CoarseStage(_Stage):
 
 class FineStage(_Stage):
     def __init__(self, *, fine_transformer: TokenConditionedTransformer, clap=None, neural_codec=None, pad_id=-1,
-                 unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15):
+                 unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15, null_cond_prob=0.):
         super().__init__()
         self.clap, self.neural_codec = clap, neural_codec
         self.num_coarse_quantizers = fine_transformer.token_sequences[1].num_quantizers
-        self._make_wrapper(fine_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob)
+        self._make_wrapper(fine_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob)
 
     @eval_decorator
     @torch.no_grad()
@@ -646,6 +738,22 @@ def stage_top_p(top_p):
     return (top_p,) * 3
 
 
+def stage_cond_scale(cond_scale):
+    """MusicLM.forward's ``cond_scale`` as (semantic, coarse, fine) values for the stages' generate(): None, a number for all three, or a
+    mapping with any of "semantic" / "coarse" / "fine" (a stage that is not named decodes unguided).  Every value is checked
+    (ops.check_cond_scale); a ValueError names what is wrong."""
+    stages = ("semantic", "coarse", "fine")
+    if isinstance(cond_scale, Mapping):
+        unknown = sorted(set(cond_scale) - set(stages), key=str)
+        if unknown:
+            raise ValueError(f"cond_scale: unknown stage(s) {unknown}; a mapping takes any of {list(stages)}")
+        for name in stages:
+            ops.check_cond_scale(cond_scale.get(name), f"cond_scale[{name!r}]")
+        return tuple(cond_scale.get(name) for name in stages)
+    ops.check_cond_scale(cond_scale)
+    return (cond_scale,) * 3
+
+
 class MusicLM(nn.Module):
     """open_musiclm.py:818-1071: hierarchical semantic -> coarse -> fine sliding-window decode.
 
@@ -667,6 +775,11 @@ class MusicLM(nn.Module):
                          "semantic" / "coarse" / "fine" (a stage that is not named samples without a nucleus).  None: off.
       kv_cache        -- handed to every stage's generate(): None / "fp32", or "operand" to keep the cached decode's keys and values in the
                          precision's 16-bit operand type -- the same ids from half the cache bytes (decode.cache_bytes sizes a call).
+      cond_scale      -- classifier-free guidance on the CLAP tokens in every stage's generate() (TokenConditionedTransformerWrapper
+                         .generate): a finite number >= 0 for all three stages, or a mapping with any of "semantic" / "coarse" / "fine"
+                         (a stage that is not named decodes unguided).  None or 1: off.  Each guided decode call carries a prompt and
+                         its null twin, so fine_windows_together stacks half as many windows into one decode call.  Meaningful only on
+                         stages trained with null_cond_prob.
     ``generate`` is an alias of ``forward``."""
 
     def __init__(self, *, wav2vec=None, clap=None, neural_codec=None, semantic_transformer: TokenConditionedTransformer,
@@ -691,8 +804,11 @@ class MusicLM(nn.Module):
                 semantic_steps_per_second=50, acoustic_steps_per_second=75, return_coarse_generated_wave=False,
                 mask_out_generated_fine_tokens=False, semantic_sliding_window_step_percent=0.5,
                 coarse_sliding_window_step_percent=0.5, fine_sliding_window_step_percent=1,
-                clap_token_ids=None, return_tokens=False, fine_windows_together=False, sampler_rng=None, top_p=None, kv_cache=None):
+                clap_token_ids=None, return_tokens=False, fine_windows_together=False, sampler_rng=None, top_p=None, kv_cache=None,
+                cond_scale=None):
         p_sem, p_coarse, p_fine = stage_top_p(top_p)                               # refused by name before any work
+        s_sem, s_coarse, s_fine = ({} if s is None else dict(cond_scale=s) for s in stage_cond_scale(cond_scale))      # likewise; None:
+        #                                                                            the stage is called as it always was
         decode.check_kv_cache(kv_cache)                                            # likewise
         kv_kw = {} if kv_cache is None else dict(kv_cache=kv_cache)                # (None: every stage is called as it always was)
         if not exists(clap_token_ids):
@@ -729,13 +845,13 @@ class MusicLM(nn.Module):
         sem = self.semantic.generate(clap_token_ids=clap_token_ids, semantic_token_ids=prime_sem,
                                      max_time_steps=int(min(output_seconds, semantic_window_seconds) * sem_hz),
                                      include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng,
-                                     top_p=p_sem, **kv_kw)
+                                     top_p=p_sem, **kv_kw, **s_sem)
         while sem.shape[1] < int(output_seconds * sem_hz):
             keep = int(semantic_window_seconds * sem_hz * (1 - semantic_sliding_window_step_percent))
             nxt = self.semantic.generate(clap_token_ids=clap_token_ids, semantic_token_ids=sem[:, -keep:],
                                          max_time_steps=int(semantic_window_seconds * sem_hz),
                                          include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng,
-                                         top_p=p_sem, **kv_kw)
+                                         top_p=p_sem, **kv_kw, **s_sem)
             sem = torch.cat([sem, nxt[:, keep:]], dim=1)
         sem_all = sem
         sem = sem[:, sem_adjust:]
@@ -753,7 +869,7 @@ class MusicLM(nn.Module):
                                         coarse_token_ids=cond_coarse,
                                         max_time_steps=int(coarse_window_seconds * ac_hz), reconstruct_wave=False,
                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True,
-                                        temperature=0.95, sampler_rng=sampler_rng, top_p=p_coarse, **kv_kw)
+                                        temperature=0.95, sampler_rng=sampler_rng, top_p=p_coarse, **kv_kw, **s_coarse)
             coarse = pred if not exists(coarse) else torch.cat([coarse, pred[:, keep:]], dim=1)
         if return_coarse_generated_wave:
             return self.neural_codec.decode_from_codebook_indices(coarse).squeeze(1)
@@ -769,7 +885,7 @@ class MusicLM(nn.Module):
             pred = self.fine.generate(clap_token_ids=clap_token_ids.repeat(len(coarse_wins), *([1] * (clap_token_ids.dim() - 1))),
                                       coarse_token_ids=_stack_windows(coarse_wins), fine_token_ids=None,
                                       max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
-                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine, **kv_kw)
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine, **kv_kw, **s_fine)
             fine = torch.cat(_unstack_windows(pred, len(coarse_wins)), dim=1)
             coarse_wins = []
         for coarse_win in coarse_wins:
@@ -780,7 +896,7 @@ class MusicLM(nn.Module):
                 keep, cond_fine = 0, prime_fine
             pred = self.fine.generate(clap_token_ids=clap_token_ids, coarse_token_ids=coarse_win, fine_token_ids=cond_fine,
                                       max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
-                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine, **kv_kw)
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine, **kv_kw, **s_fine)
             fine = pred if not exists(fine) else torch.cat([fine, pred[:, keep:]], dim=1)
         fine = fine[:, fine_adjust:]
         if exists(prime_coarse_all) and exists(prime_fine_all):

@@ -660,12 +660,84 @@ def embed_bwd(ids, seg, posidx, dtables, dstarts, dpos_tables, dx, alpha):
          ptr(index_error_flag(dx.device)), stream_ptr())
 
 
-def prepare_train_batch(raw_ids, eos_ids, quantizers, codebooks, pad_id, scores, n_drop, want_labels):
+def check_null_cond_prob(p, name="null_cond_prob"):
+    """The condition-drop probability as a float: a number in [0, 1), or exactly 1 (every sample; tests).  Anything else raises a
+    ValueError that names the argument.  Pure Python: runs before any device work."""
+    try:
+        v = float("nan") if isinstance(p, (str, bytes, bool)) else float(p)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not (0.0 <= v <= 1.0):
+        raise ValueError(f"{name} must be a number in [0, 1], not {p!r}")
+    return v
+
+
+FP32_MAX = 3.4028234663852886e38            # the largest finite fp32: a scale past it would reach the kernel as inf
+
+
+def check_cond_scale(cond_scale, name="cond_scale"):
+    """The guidance scale as generate / score take it: None -> None (off), 1 -> None (off: g = l), any other finite number >= 0 -> float.
+    Anything else (negative, NaN, inf, not a number) raises a ValueError that names the argument.  Pure Python: before any device work."""
+    if cond_scale is None:
+        return None
+    try:
+        s = float("nan") if isinstance(cond_scale, (str, bytes, bool)) else float(cond_scale)
+    except (TypeError, ValueError):
+        s = float("nan")
+    if not (0.0 <= s <= FP32_MAX):
+        raise ValueError(f"{name} must be None or a finite number >= 0 (as fp32), not {cond_scale!r}")
+    return None if s == 1.0 else s
+
+
+def guide_logits(cond, null, out, V, scale):
+    """omlm_guide_logits (include/omlm.h): out[r, c] = null[r, c] + scale * (cond[r, c] - null[r, c]) for c < V, three fp32 roundings.
+    cond / null / out: fp32 [rows, ld] of one leading dimension (row-contiguous views such as the halves of a [2P, ld] block); out may be
+    cond.  Columns V .. ld - 1 of out are not written."""
+    s = check_cond_scale(scale, "scale")
+    rows, ld = cond.shape
+    for t, name in ((cond, "cond"), (null, "null"), (out, "out")):
+        hip.require_gpu(t, name)
+        if t.dtype != torch.float32 or t.shape != (rows, ld) or t.stride() != (ld, 1):
+            raise ValueError(f"guide_logits: {name} must be fp32 [{rows}, {ld}] with contiguous rows; got {t.dtype} {tuple(t.shape)} {t.stride()}")
+    if not 0 < int(V) <= ld:
+        raise ValueError(f"guide_logits: V must lie in [1, {ld}], not {V}")
+    call("omlm_guide_logits", ptr(cond), ptr(null), ptr(out), rows, int(V), ld, 1.0 if s is None else s, stream_ptr())
+
+
+def decode_twin(ids=None, ids_twin=None, x=None, x_twin=None):
+    """omlm_decode_twin (include/omlm.h): ids_twin[:] = ids (int64 [rows]) and x_twin[:] = x (fp32 [rows, D]) in one launch; either pair may
+    be left out."""
+    if (ids is None) != (ids_twin is None) or (x is None) != (x_twin is None):
+        raise ValueError("decode_twin: give ids with ids_twin and x with x_twin")
+    if ids is None and x is None:
+        return
+    rows = ids.shape[0] if ids is not None else x.shape[0]
+    if ids is not None:
+        for t in (ids, ids_twin):
+            hip.require_gpu(t, "ids")
+            assert t.dtype == torch.int64 and t.shape == (rows,) and t.is_contiguous()
+    D = 0
+    if x is not None:
+        D = x.shape[1]
+        for t in (x, x_twin):
+            hip.require_gpu(t, "x")
+            assert t.dtype == torch.float32 and t.shape == (rows, D) and t.is_contiguous()
+    call("omlm_decode_twin", ptr(ids), ptr(ids_twin), ptr(x), ptr(x_twin), rows, D, stream_ptr())
+
+
+def prepare_train_batch(raw_ids, eos_ids, quantizers, codebooks, pad_id, scores, n_drop, want_labels, *, null_u=None, null_p=0.):
     """One launch for the wrapper's id / label / key-mask construction (omlm_prepare_train_batch).  raw_ids: list of int64 [B, len_s]
     contiguous; returns (ids32 [B, N], keymask uint8 [B, N], labels: list of int32 [B, len_s + 1] or None, lens: the per-sequence token
-    counts the engine's layout wants -- len_s + 1 for conditioning sequences, len_last for the predicted one)."""
+    counts the engine's layout wants -- len_s + 1 for conditioning sequences, len_last for the predicted one).
+    null_u (fp32 [B]) with null_p: the condition drop of include/omlm.h -- sample b with null_u[b] < null_p gets the null condition."""
     n = len(raw_ids)
     B, dev = raw_ids[0].shape[0], raw_ids[0].device
+    if null_u is not None:
+        null_p = check_null_cond_prob(null_p, "null_p")
+        if n < 2:
+            raise ValueError("prepare_train_batch: the condition drop needs a conditioning sequence (at least two token sequences)")
+        hip.require_gpu(null_u, "null_u")
+        assert null_u.dtype == torch.float32 and null_u.shape == (B,) and null_u.is_contiguous()
     for t in raw_ids:
         hip.require_gpu(t, "token ids")
         assert t.dtype == torch.int64 and t.dim() == 2 and t.is_contiguous() and t.shape[0] == B
@@ -676,7 +748,8 @@ def prepare_train_batch(raw_ids, eos_ids, quantizers, codebooks, pad_id, scores,
     labels = [torch.empty(B, l + 1, dtype=torch.int32, device=dev) if w else None for l, w in zip(lens, want_labels)]
     arr_i = lambda v: (C.c_int * n)(*[int(x) for x in v])
     call("omlm_prepare_train_batch", _ptr_array(raw_ids), _ptr_array(labels), arr_i(lens), arr_i(eos_ids), arr_i(quantizers), arr_i(codebooks),
-         n, B, int(pad_id), ptr(scores), int(n_drop), ptr(ids32), ptr(keymask), N, stream_ptr())
+         n, B, int(pad_id), ptr(scores), int(n_drop), ptr(ids32), ptr(keymask), N, ptr(null_u), float(null_p) if null_u is not None else 0.,
+         stream_ptr())
     return ids32, keymask, labels, [l + 1 for l in lens[:-1]] + [lens[-1]]
 
 

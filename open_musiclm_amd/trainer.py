@@ -111,8 +111,11 @@ class SingleStageTrainer(nn.Module):
                  save_model_every=1000, results_folder='./results', accelerate_kwargs: dict = {},
                  config_paths: Optional[List[str]] = None, dataset_yields_tokens: Optional[bool] = None,
                  use_hip_graph: Optional[bool] = None, ema_decay: Optional[float] = None, ema_update_after_step: int = 0,
-                 ema_warmup: bool = True):
-        """ema_decay (None: off; no reference counterpart): the fused optimizer step keeps an exponential moving average of the weights
+                 ema_warmup: bool = True, null_cond_prob: float = 0.):
+        """null_cond_prob (0: off; no reference counterpart): the share of training samples whose CLAP condition is replaced by the null
+        condition (TokenConditionedTransformerWrapper), the training side of ``generate(cond_scale=...)``.  validate, generate and the
+        EMA twin's wrapper never drop.
+        ema_decay (None: off; no reference counterpart): the fused optimizer step keeps an exponential moving average of the weights
         (ema.py); ``ema_transformer`` is a read-only twin on it, ``generate(use_ema=True)`` / ``validate(steps, use_ema=True)`` run on
         it, and checkpoints carry it ({stage}.transformer_ema.{steps}.pt beside the model; the optimizer file alone resumes it)."""
         super().__init__()
@@ -153,7 +156,8 @@ class SingleStageTrainer(nn.Module):
         else:
             raise ValueError(f'invalid stage: {stage}')
         self.cross_entropy_loss_weights = cross_entropy_loss_weights
-        self.train_wrapper = self._make_stage(transformer)
+        self.null_cond_prob = null_cond_prob
+        self.train_wrapper = self._make_stage(transformer, null_cond_prob)
         self.ds_fields = token_fields if tokens_in else wave_fields
 
         self.register_buffer('steps', torch.Tensor([0]))
@@ -237,17 +241,19 @@ class SingleStageTrainer(nn.Module):
         self.use_hip_graph = tokens_in if use_hip_graph is None else use_hip_graph
         self._graphed = None
 
-    def _make_stage(self, transformer):
-        """The stage wrapper of this trainer around `transformer`: the model (train_wrapper) or its EMA twin."""
+    def _make_stage(self, transformer, null_cond_prob=0.):
+        """The stage wrapper of this trainer around `transformer`: the model (train_wrapper, with the trainer's condition drop) or its EMA
+        twin (none)."""
         w = self.cross_entropy_loss_weights
         if self.stage == 'semantic':
             return SemanticStage(semantic_transformer=transformer, wav2vec=self.wav2vec, clap=self.audio_conditioner,
-                                 cross_entropy_loss_weights=default(w, [0., 1.]))
+                                 cross_entropy_loss_weights=default(w, [0., 1.]), null_cond_prob=null_cond_prob)
         if self.stage == 'coarse':
             return CoarseStage(coarse_transformer=transformer, neural_codec=self.neural_codec, wav2vec=self.wav2vec,
-                               clap=self.audio_conditioner, cross_entropy_loss_weights=default(w, [0., 0., 1.]))
+                               clap=self.audio_conditioner, cross_entropy_loss_weights=default(w, [0., 0., 1.]),
+                               null_cond_prob=null_cond_prob)
         return FineStage(fine_transformer=transformer, clap=self.audio_conditioner, neural_codec=self.neural_codec,
-                         cross_entropy_loss_weights=default(w, [0., 0., 1.]))
+                         cross_entropy_loss_weights=default(w, [0., 0., 1.]), null_cond_prob=null_cond_prob)
 
     # ---- checkpointing (trainer.py:359-391) ----------------------------------------------------------
     def save(self, model_path, optim_path, scheduler_path=None, ema_path=None):
@@ -306,7 +312,8 @@ class SingleStageTrainer(nn.Module):
         return self.ema_transformer
 
     def generate(self, *args, use_ema=False, **kwargs):
-        """The wrapper's generate, every keyword passed on: with ``return_logprobs=True`` it returns (ids, LogProbs).
+        """The wrapper's generate, every keyword passed on: with ``return_logprobs=True`` it returns (ids, LogProbs), with ``cond_scale`` it
+        decodes under classifier-free guidance.
         use_ema: sample from the weight EMA (the twin) instead of the training weights."""
         if use_ema:
             self._require_ema()
