@@ -286,6 +286,27 @@ int omlm_cross_entropy_fwd(const float* logits, const int* labels, float* row_ls
                            int R, int V, int ld, int* err_flag, void* stream);
 int omlm_cross_entropy_bwd(const float* logits, const int* labels, const float* row_lse, const float* gscale,
                            float coef, void* dlogits, int R, int V, int ld, int ldd, int out_dtype, void* stream);
+/* Label smoothing (eps = label_smoothing in [0, 1), torch's F.cross_entropy(label_smoothing=) convention) and z-loss (zeta = z_loss,
+   finite and >= 0; PaLM / T5X: zeta * lse^2 per row): extensions, training mode only; no reference counterpart.
+   A live row (label y in [0, V)) with logits l[0..V), lse = log sum_c exp l[c], p = exp(l - lse):
+       nll    = lse - l[y]
+       smooth = lse - (1 / V) sum_c l[c]        (the mean over all V entries of -log p[c]; V counts the eos entry)
+       z      = lse^2
+       row loss = (1 - eps) nll + eps smooth + zeta z
+       d row loss / d l[c] = p[c] (1 + 2 zeta lse) - (1 - eps) [c == y] - eps / V
+   The loss over all sequences is sum_s w_s ((1 - eps) NLL_s + eps S_s + zeta Z_s) / total with NLL_s, S_s, Z_s the sums of nll, smooth, z
+   over the rows of sequence s and w_s, total the weights and the count of non-ignored labels of the plain loss.  Ignored rows (label < 0)
+   and rows whose label is >= V (err_flag |= 4) add nothing to any sum and get exact-zero gradients; pad columns [V, ldd) are exact zeros.
+   _fwd_reg: the arguments of omlm_cross_entropy_fwd with `sums`, 3 floats {nll, smooth, z}, each ACCUMULATED onto, in place of nll_sum
+   (eps and zeta enter where the host combines the sums).  _bwd_reg: the arguments of omlm_cross_entropy_bwd plus eps and zeta, on every
+   route of it; a value outside the ranges above (NaN and inf included) is refused by name before anything else is looked at.
+   The same four kernels serve both pairs through one template flag; the plain pair is the instructions and the launches it always was, and with
+   eps = zeta = 0 the _reg pair gives the same row_lse and dlogits bit for bit. */
+int omlm_cross_entropy_fwd_reg(const float* logits, const int* labels, float* row_lse, float* sums,
+                               int R, int V, int ld, int* err_flag, void* stream);
+int omlm_cross_entropy_bwd_reg(const float* logits, const int* labels, const float* row_lse, const float* gscale,
+                               float coef, void* dlogits, int R, int V, int ld, int ldd, int out_dtype,
+                               float label_smoothing, float z_loss, void* stream);
 
 /* clip_grad_norm_ + Adam/AdamW on flat buffers (optimizer.py:10-34; trainer.py:444-447). */
 /* out[0] += sum g^2; partials (optional, >= 2048 floats) selects the bit-reproducible two-pass form (identical clip on every replica). */

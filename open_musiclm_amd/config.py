@@ -143,6 +143,9 @@ class SingleStageTrainerConfig:
     ema_warmup: bool = True
     # condition drop for classifier-free guidance (TokenConditionedTransformerWrapper; no reference counterpart): off at 0
     null_cond_prob: float = 0.
+    # label smoothing and z-loss in the fused cross entropy (include/omlm.h; no reference counterpart): training mode only, off at 0
+    label_smoothing: float = 0.
+    z_loss: float = 0.
 
 
 @dataclass

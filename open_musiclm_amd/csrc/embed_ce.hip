@@ -130,12 +130,21 @@ extern "C" int omlm_embed_gather_bwd(const int* ids, const int* seg, const int* 
 // index and consumed together -- predicated loads were serialised by hipcc, one wait each), maximum and sum are two wave reductions, no LDS,
 // no barrier.  The workgroup-per-row form below walks its rows through three barriers each with 4-byte loads (83 us for 118 MB at coarse-small:
 // 1.5 TB/s); it stays for wider rows.
+//
+// REG (label smoothing and z-loss, include/omlm.h): the same four kernels with one template flag.  Forward: `sums` is {nll, smooth, z}
+// instead of the one nll word, smooth = lse - mean_c l[c] formed as log(s) - mean_c (l[c] - mx) (the row maximum leaves before the sum, so
+// a common offset of the row costs no bits), z = lse^2; one more reduction per row, one atomic per workgroup per sum.  Backward: softmax
+// times (1 + 2 zeta lse), the one-hot times (1 - eps), eps / V off every entry.  REG = false compiles to the instructions it always was; the
+// backward kernels' argument block is 8 bytes longer (eps and zeta, which those instantiations never read).
 #define CE_NV 17
+template <bool REG>
 __global__ __launch_bounds__(256) void ce_fwd_wave_kernel(const float* __restrict__ logits, const int* __restrict__ labels,
                                                           float* __restrict__ row_lse, float* __restrict__ nll_sum,
                                                           int R, int V, int ld, int* __restrict__ err) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float local = 0.f;
+    [[maybe_unused]] float local_s = 0.f, local_z = 0.f;
+    [[maybe_unused]] const float inv_V = 1.0f / (float)V;
     for (int row = blockIdx.x * 4 + wave; row < R; row += gridDim.x * 4) {
         const float* lr = logits + (size_t)row * ld;
         float v[CE_NV];
@@ -153,29 +162,49 @@ __global__ __launch_bounds__(256) void ce_fwd_wave_kernel(const float* __restric
 #pragma unroll
         for (int j = 0; j < CE_NV; ++j) s += __expf(v[j] - mx);          // (exp(-inf) = 0 for the slots past V)
         s = wave_sum(s);
+        [[maybe_unused]] float sd = 0.f;                                  // sum_c (l[c] - mx) over the V live slots
+        if constexpr (REG) {
+#pragma unroll
+            for (int j = 0; j < CE_NV; ++j) sd += lane + 64 * j < V ? v[j] - mx : 0.f;
+            sd = wave_sum(sd);
+        }
         const float lse = mx + __logf(s);
         if (lane == 0) {
             row_lse[row] = lse;
             if (lb >= V) { if (err) atomicOr(err, 4); }            // a label past the vocabulary: row ignored, flag raised
-            else if (lb >= 0) local += lse - own;
+            else if (lb >= 0) {
+                local += lse - own;
+                if constexpr (REG) { local_s += __logf(s) - sd * inv_V; local_z += lse * lse; }
+            }
         }
     }
     // one atomic per WORKGROUP, and few workgroups: every add lands on the same word, and same-address atomics retire one at a time
     // (one per wave -- 16 k of them -- made this launch 370 us)
-    __shared__ float wsum[4];
-    if (lane == 0) wsum[wave] = local;
+    __shared__ float wsum[REG ? 12 : 4];
+    if (lane == 0) {
+        wsum[wave] = local;
+        if constexpr (REG) { wsum[4 + wave] = local_s; wsum[8 + wave] = local_z; }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         const float t = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
         if (t != 0.f) unsafeAtomicAdd(nll_sum, t);
+        if constexpr (REG) {
+            const float ts = (wsum[4] + wsum[5]) + (wsum[6] + wsum[7]), tz = (wsum[8] + wsum[9]) + (wsum[10] + wsum[11]);
+            if (ts != 0.f) unsafeAtomicAdd(nll_sum + 1, ts);
+            if (tz != 0.f) unsafeAtomicAdd(nll_sum + 2, tz);
+        }
     }
 }
 
+template <bool REG>
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, const int* __restrict__ labels,
                                                      float* __restrict__ row_lse, float* __restrict__ nll_sum,
                                                      int R, int V, int ld, int* __restrict__ err) {
     __shared__ float red[4];
     float local = 0.f;
+    [[maybe_unused]] float local_s = 0.f, local_z = 0.f;
+    [[maybe_unused]] const float inv_V = 1.0f / (float)V;
     for (int row = blockIdx.x; row < R; row += gridDim.x) {
         const float* lr = logits + (size_t)row * ld;
         float mx = -INFINITY;
@@ -186,33 +215,54 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
         __syncthreads();
         mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
         float s = 0.f;
-        for (int c = threadIdx.x; c < V; c += 256) s += __expf(lr[c] - mx);
+        [[maybe_unused]] float sd = 0.f;
+        for (int c = threadIdx.x; c < V; c += 256) {
+            const float d = lr[c] - mx;
+            s += __expf(d);
+            if constexpr (REG) sd += d;
+        }
         s = block_sum<256>(s, red);
+        if constexpr (REG) sd = block_sum<256>(sd, red);
         const float lse = mx + __logf(s);
         if (threadIdx.x == 0) {
             row_lse[row] = lse;
             const int lb = labels[row];
             if (lb >= V) { if (err) atomicOr(err, 4); }            // a label past the vocabulary: row ignored, flag raised
-            else if (lb >= 0) local += lse - lr[lb];
+            else if (lb >= 0) {
+                local += lse - lr[lb];
+                if constexpr (REG) { local_s += __logf(s) - sd * inv_V; local_z += lse * lse; }
+            }
         }
     }
     if (threadIdx.x == 0 && local != 0.f) unsafeAtomicAdd(nll_sum, local);
+    if constexpr (REG) {
+        if (threadIdx.x == 0 && local_s != 0.f) unsafeAtomicAdd(nll_sum + 1, local_s);
+        if (threadIdx.x == 0 && local_z != 0.f) unsafeAtomicAdd(nll_sum + 2, local_z);
+    }
 }
 
 // dlogits[row, c] = coef * g * (softmax - onehot) for c < V, 0 for V <= c < ldd
-template <typename T>
+// REG: coef * g * (softmax * (1 + 2 zeta lse) - (1 - eps) * onehot - eps / V)
+template <typename T, bool REG>
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, const int* __restrict__ labels,
                                                      const float* __restrict__ row_lse, const float* __restrict__ gscale,
-                                                     float coef, T* __restrict__ dlogits, int R, int V, int ld, int ldd) {
+                                                     float coef, T* __restrict__ dlogits, int R, int V, int ld, int ldd,
+                                                     float eps, float zeta) {
     const float g = coef * (gscale ? gscale[0] : 1.0f);
+    [[maybe_unused]] const float hot = 1.0f - eps, off = eps / (float)V;
     for (int row = blockIdx.x; row < R; row += gridDim.x) {
         const float* lr = logits + (size_t)row * ld;
         T* dr = dlogits + (size_t)row * ldd;
         const int lb = labels[row];
         const float lse = row_lse[row];
+        [[maybe_unused]] const float pz = 1.0f + 2.0f * zeta * lse;
         for (int c = threadIdx.x; c < ldd; c += 256) {
             float v = 0.f;
-            if (c < V && lb >= 0 && lb < V) v = g * (__expf(lr[c] - lse) - (c == lb ? 1.0f : 0.0f));
+            if constexpr (REG) {
+                if (c < V && lb >= 0 && lb < V) v = g * (__expf(lr[c] - lse) * pz - (c == lb ? hot : 0.0f) - off);
+            } else {
+                if (c < V && lb >= 0 && lb < V) v = g * (__expf(lr[c] - lse) - (c == lb ? 1.0f : 0.0f));
+            }
             store_from_float(dr + c, v);
         }
     }
@@ -220,11 +270,13 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
 
 // 16-bit outputs, one WAVE per row (round 6): a lane owns 8 consecutive columns per trip (two 16-byte loads, one 16-byte store) instead of one
 // column per thread per trip with 2-byte stores (50 us for 125 MB in + 60 MB out at coarse-small)
-template <typename T>
+template <typename T, bool REG>
 __global__ __launch_bounds__(256) void ce_bwd_wave_kernel(const float* __restrict__ logits, const int* __restrict__ labels,
                                                           const float* __restrict__ row_lse, const float* __restrict__ gscale,
-                                                          float coef, T* __restrict__ dlogits, int R, int V, int ld, int ldd) {
+                                                          float coef, T* __restrict__ dlogits, int R, int V, int ld, int ldd,
+                                                          float eps, float zeta) {
     const float g = coef * (gscale ? gscale[0] : 1.0f);
+    [[maybe_unused]] const float hot = 1.0f - eps, off = eps / (float)V;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int row = blockIdx.x * 4 + wave; row < R; row += gridDim.x * 4) {
         const float* lr = logits + (size_t)row * ld;
@@ -232,6 +284,7 @@ __global__ __launch_bounds__(256) void ce_bwd_wave_kernel(const float* __restric
         const int lb = labels[row];
         const float lse = row_lse[row];
         const bool live = lb >= 0 && lb < V;
+        [[maybe_unused]] const float pz = 1.0f + 2.0f * zeta * lse;
         for (int c = lane * 8; c < ldd; c += 512) {
             float x[8];
             if (c + 8 <= V) {
@@ -245,7 +298,11 @@ __global__ __launch_bounds__(256) void ce_bwd_wave_kernel(const float* __restric
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 float v = 0.f;
-                if (c + e < V && live) v = g * (__expf(x[e] - lse) - (c + e == lb ? 1.0f : 0.0f));
+                if constexpr (REG) {
+                    if (c + e < V && live) v = g * (__expf(x[e] - lse) * pz - (c + e == lb ? hot : 0.0f) - off);
+                } else {
+                    if (c + e < V && live) v = g * (__expf(x[e] - lse) - (c + e == lb ? 1.0f : 0.0f));
+                }
                 pk.h[e] = (T)v;
             }
             *(uint4*)(dr + c) = pk.u;
@@ -253,20 +310,28 @@ __global__ __launch_bounds__(256) void ce_bwd_wave_kernel(const float* __restric
     }
 }
 
-extern "C" int omlm_cross_entropy_fwd(const float* logits, const int* labels, float* row_lse, float* nll_sum,
-                                      int R, int V, int ld, int* err_flag, void* stream) {
+// One launcher per direction; the plain and the regularised entries differ in the template flag alone.  REG: `sums` holds 3 floats
+// {nll, smooth, z}, else the one nll word.  eps / zeta are refused by name before anything else is looked at.
+#define CE_CHECK_REG(eps, zeta) \
+    OMLM_CHECK_ARG((eps) >= 0.f && (eps) < 1.f, "label_smoothing must lie in [0, 1)"); \
+    OMLM_CHECK_ARG((zeta) >= 0.f && (zeta) <= 3.402823466e38f, "z_loss must be finite and >= 0")
+
+template <bool REG>
+static int ce_fwd_launch(const char* name, const float* logits, const int* labels, float* row_lse, float* sums,
+                         int R, int V, int ld, int* err_flag, void* stream) {
     if (R <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(logits && labels && row_lse && nll_sum && ld >= V, "cross entropy arguments");
+    OMLM_CHECK_ARG(logits && labels && row_lse && sums && ld >= V, "cross entropy arguments");
     if (V <= 64 * CE_NV) {
         const int blocks = (R + 3) / 4;
-        hipLaunchKernelGGL(ce_fwd_wave_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, as_stream(stream), logits, labels, row_lse, nll_sum, R, V, ld, err_flag);
+        hipLaunchKernelGGL(ce_fwd_wave_kernel<REG>, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, as_stream(stream), logits, labels, row_lse, sums, R, V, ld, err_flag);
     } else
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3(R < 4096 ? R : 4096), dim3(256), 0, as_stream(stream), logits, labels, row_lse, nll_sum, R, V, ld, err_flag);
-    return omlm_post_launch("omlm_cross_entropy_fwd");
+    hipLaunchKernelGGL(ce_fwd_kernel<REG>, dim3(R < 4096 ? R : 4096), dim3(256), 0, as_stream(stream), logits, labels, row_lse, sums, R, V, ld, err_flag);
+    return omlm_post_launch(name);
 }
 
-extern "C" int omlm_cross_entropy_bwd(const float* logits, const int* labels, const float* row_lse, const float* gscale,
-                                      float coef, void* dlogits, int R, int V, int ld, int ldd, int out_dtype, void* stream) {
+template <bool REG>
+static int ce_bwd_launch(const char* name, const float* logits, const int* labels, const float* row_lse, const float* gscale,
+                         float coef, void* dlogits, int R, int V, int ld, int ldd, int out_dtype, float eps, float zeta, void* stream) {
     if (R <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(logits && labels && row_lse && dlogits && ld >= V && ldd >= V, "cross entropy arguments");
     dim3 grid(R < 8192 ? R : 8192), block(256);
@@ -277,18 +342,42 @@ extern "C" int omlm_cross_entropy_bwd(const float* logits, const int* labels, co
         const int blocks = (R + 3) / 4;
         dim3 wgrid(blocks < 8192 ? blocks : 8192);
         if (out_dtype == OMLM_DT_F16)
-            hipLaunchKernelGGL(ce_bwd_wave_kernel<f16_t>, wgrid, block, 0, as_stream(stream), logits, labels, row_lse, gscale, coef, (f16_t*)dlogits, R, V, ld, ldd);
+            hipLaunchKernelGGL((ce_bwd_wave_kernel<f16_t, REG>), wgrid, block, 0, as_stream(stream), logits, labels, row_lse, gscale, coef, (f16_t*)dlogits, R, V, ld, ldd, eps, zeta);
         else
-            hipLaunchKernelGGL(ce_bwd_wave_kernel<h16_t>, wgrid, block, 0, as_stream(stream), logits, labels, row_lse, gscale, coef, (h16_t*)dlogits, R, V, ld, ldd);
-        return omlm_post_launch("omlm_cross_entropy_bwd");
+            hipLaunchKernelGGL((ce_bwd_wave_kernel<h16_t, REG>), wgrid, block, 0, as_stream(stream), logits, labels, row_lse, gscale, coef, (h16_t*)dlogits, R, V, ld, ldd, eps, zeta);
+        return omlm_post_launch(name);
     }
     if (out_dtype == 0)
-        hipLaunchKernelGGL(ce_bwd_kernel<float>, grid, block, 0, as_stream(stream), logits, labels, row_lse, gscale, coef, (float*)dlogits, R, V, ld, ldd);
+        hipLaunchKernelGGL((ce_bwd_kernel<float, REG>), grid, block, 0, as_stream(stream), logits, labels, row_lse, gscale, coef, (float*)dlogits, R, V, ld, ldd, eps, zeta);
     else if (out_dtype == OMLM_DT_F16)
-        hipLaunchKernelGGL(ce_bwd_kernel<f16_t>, grid, block, 0, as_stream(stream), logits, labels, row_lse, gscale, coef, (f16_t*)dlogits, R, V, ld, ldd);
+        hipLaunchKernelGGL((ce_bwd_kernel<f16_t, REG>), grid, block, 0, as_stream(stream), logits, labels, row_lse, gscale, coef, (f16_t*)dlogits, R, V, ld, ldd, eps, zeta);
     else
-        hipLaunchKernelGGL(ce_bwd_kernel<h16_t>, grid, block, 0, as_stream(stream), logits, labels, row_lse, gscale, coef, (h16_t*)dlogits, R, V, ld, ldd);
-    return omlm_post_launch("omlm_cross_entropy_bwd");
+        hipLaunchKernelGGL((ce_bwd_kernel<h16_t, REG>), grid, block, 0, as_stream(stream), logits, labels, row_lse, gscale, coef, (h16_t*)dlogits, R, V, ld, ldd, eps, zeta);
+    return omlm_post_launch(name);
+}
+
+extern "C" int omlm_cross_entropy_fwd(const float* logits, const int* labels, float* row_lse, float* nll_sum,
+                                      int R, int V, int ld, int* err_flag, void* stream) {
+    return ce_fwd_launch<false>("omlm_cross_entropy_fwd", logits, labels, row_lse, nll_sum, R, V, ld, err_flag, stream);
+}
+
+extern "C" int omlm_cross_entropy_bwd(const float* logits, const int* labels, const float* row_lse, const float* gscale,
+                                      float coef, void* dlogits, int R, int V, int ld, int ldd, int out_dtype, void* stream) {
+    return ce_bwd_launch<false>("omlm_cross_entropy_bwd", logits, labels, row_lse, gscale, coef, dlogits, R, V, ld, ldd, out_dtype, 0.f, 0.f, stream);
+}
+
+// label smoothing + z-loss (include/omlm.h): sums = {nll, smooth, z}, each accumulated onto
+extern "C" int omlm_cross_entropy_fwd_reg(const float* logits, const int* labels, float* row_lse, float* sums,
+                                          int R, int V, int ld, int* err_flag, void* stream) {
+    return ce_fwd_launch<true>("omlm_cross_entropy_fwd_reg", logits, labels, row_lse, sums, R, V, ld, err_flag, stream);
+}
+
+extern "C" int omlm_cross_entropy_bwd_reg(const float* logits, const int* labels, const float* row_lse, const float* gscale,
+                                          float coef, void* dlogits, int R, int V, int ld, int ldd, int out_dtype,
+                                          float label_smoothing, float z_loss, void* stream) {
+    CE_CHECK_REG(label_smoothing, z_loss);
+    return ce_bwd_launch<true>("omlm_cross_entropy_bwd_reg", logits, labels, row_lse, gscale, coef, dlogits, R, V, ld, ldd, out_dtype,
+                               label_smoothing, z_loss, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

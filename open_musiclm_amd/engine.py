@@ -1132,24 +1132,30 @@ class LossFunction(torch.autograd.Function):
     """Wrapper.forward(return_loss=True) (open_musiclm.py:378-410) fused: logits + cross entropy.
 
     Returns (loss, *logits) with the logits marked non-differentiable; the backward regenerates
-    softmax - onehot from the saved logits / row lse directly in the GEMM operand dtype."""
+    softmax - onehot from the saved logits / row lse directly in the GEMM operand dtype.
+
+    reg = (label_smoothing, z_loss), checked floats (include/omlm.h): with either set the forward takes the three sums {nll, smooth, z} of
+    every weighted sequence from omlm_cross_entropy_fwd_reg and the loss is sum_s w_s ((1 - eps) NLL_s + eps S_s + zeta Z_s) / total; the
+    backward hands both to omlm_cross_entropy_bwd_reg.  (0, 0): the calls and tensor ops it always made."""
 
     @staticmethod
-    def forward(ctx, model, all_token_ids, labels, self_attn_mask, loss_weights, ignore_negative, precision, all_logits, *params):
+    def forward(ctx, model, all_token_ids, labels, self_attn_mask, loss_weights, ignore_negative, precision, all_logits, reg, *params):
         nseq = len(model.token_sequences)
+        eps, zeta = reg
+        plain = eps == 0.0 and zeta == 0.0
         bufs, lay, st = run_forward(model, all_token_ids, self_attn_mask, False, True, precision,
                                     want=[bool(all_logits) or w > 0 for w in loss_weights])
         dev = next(b for b in bufs if b is not None).device
         total = 0
         total_dev = None                       # device-side part of the normaliser: non-ignored labels of padded sequences
-        nll = torch.zeros(nseq, device=dev)
+        nll = torch.zeros(nseq, device=dev) if plain else torch.zeros(nseq, 3, device=dev)
         st.labels, st.lse_rows, st.coefs = [], [], []
         for s, (seq, buf, lb, w) in enumerate(zip(model.token_sequences, bufs, labels, loss_weights)):
             if w > 0:
                 lb32 = lb.reshape(-1).to(torch.int32).contiguous()
                 assert lb32.numel() == buf.shape[0], (lb32.numel(), buf.shape)
                 lse_rows = torch.empty(buf.shape[0], device=dev)
-                ops.ce_fwd(buf, lb32, lse_rows, nll[s:s + 1], seq.codebook_size + 1)
+                ops.ce_fwd(buf, lb32, lse_rows, nll[s:s + 1] if plain else nll[s], seq.codebook_size + 1, label_smoothing=eps, z_loss=zeta)
                 if ignore_negative[s]:
                     cnt = (lb32 >= 0).sum().to(torch.float32)
                     total_dev = cnt if total_dev is None else total_dev + cnt
@@ -1160,6 +1166,8 @@ class LossFunction(torch.autograd.Function):
                 st.labels.append(None); st.lse_rows.append(None)
         # loss = sum_s w_s * nll_sum_s / total   (== sum_s mean_s * n_s * w_s / sum n_s, :407-410); python-scalar
         # multiplies only: nothing is uploaded from the host here (graph-capture safe)
+        if not plain:                      # [nseq, 3] sums -> [nseq]: (1 - eps) NLL_s + eps S_s + zeta Z_s
+            nll = nll[:, 0] * (1.0 - eps) + nll[:, 1] * eps + nll[:, 2] * zeta
         loss = None
         if total_dev is None:
             for s, w in enumerate(loss_weights):
@@ -1178,6 +1186,7 @@ class LossFunction(torch.autograd.Function):
             st.coefs = [float(w) if w > 0 else 0.0 for w in loss_weights]
             ctx.inv_total = inv_total
         ctx.st = st
+        ctx.reg = (eps, zeta)
         ctx.nparams = len(params)
         ctx.ls = loss_scale_state(model) if is_half(precision) else None
         views = logits_views(model, lay, bufs)
@@ -1200,8 +1209,9 @@ class LossFunction(torch.autograd.Function):
                 continue
             buf = st.logits[s]
             d = torch.empty(buf.shape[0], buf.shape[1], dtype=T, device=buf.device)
-            ops.ce_bwd(buf, st.labels[s], st.lse_rows[s], g, st.coefs[s], d, seq.codebook_size + 1)
+            ops.ce_bwd(buf, st.labels[s], st.lse_rows[s], g, st.coefs[s], d, seq.codebook_size + 1,
+                       label_smoothing=ctx.reg[0], z_loss=ctx.reg[1])
             dl.append(d)
         run_backward(st, dl)
         ctx.st = None
-        return (None,) * (8 + ctx.nparams)
+        return (None,) * (9 + ctx.nparams)

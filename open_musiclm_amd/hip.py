@@ -72,6 +72,8 @@ SIGNATURES = {
     "omlm_prepare_train_batch": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp, i32, vp, f32, vp],
     "omlm_cross_entropy_fwd": [vp, vp, vp, vp, i32, i32, i32, vp, vp],
     "omlm_cross_entropy_bwd": [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, vp],
+    "omlm_cross_entropy_fwd_reg": [vp, vp, vp, vp, i32, i32, i32, vp, vp],
+    "omlm_cross_entropy_bwd_reg": [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, f32, f32, vp],
     "omlm_sumsq_accumulate": [vp, i64, vp, vp, vp],
     "omlm_adamw_clip_step": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, f32, i32, i32, i32, vp, vp],
     "omlm_adamw_clip_step_ema": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, f32, i32, i32, i32, vp, vp, f32, i32, i32, vp],

@@ -127,13 +127,18 @@ class TokenConditionedTransformer(nn.Module):
         bufs, _, _ = engine.run_forward(self, ids, None, True, False, self._precision(), final_rows_only=True)
         return bufs[-1]
 
-    def loss_and_logits(self, ids, labels, self_attn_mask, loss_weights, ignore_negative=None, all_logits=True):
+    def loss_and_logits(self, ids, labels, self_attn_mask, loss_weights, ignore_negative=None, all_logits=True,
+                        label_smoothing=0., z_loss=0.):
         """ignore_negative[s]: labels < 0 of sequence s are ignore_index rows AND leave the loss normaliser (the padded labels of
         a unique_consecutive sequence, open_musiclm.py:396-404).  all_logits=False: the heads of zero-weight sequences are not
-        evaluated (their logits come back as None)."""
+        evaluated (their logits come back as None).
+        label_smoothing / z_loss (extensions; include/omlm.h): the loss is sum_s w_s ((1 - eps) NLL_s + eps S_s + zeta Z_s) / total, formed
+        and differentiated in the cross-entropy kernels.  Both 0 (the default): the plain cross entropy, the calls it always made.  This
+        method applies what it is given; the wrapper passes them in training mode only."""
         ign = tuple(bool(v) for v in ignore_negative) if ignore_negative is not None else (False,) * len(labels)
+        reg = (ops.check_label_smoothing(label_smoothing), ops.check_z_loss(z_loss))
         return engine.LossFunction.apply(self, ids, labels, self_attn_mask, tuple(loss_weights), ign, self._precision(),
-                                         bool(all_logits), *self.parameters())
+                                         bool(all_logits), reg, *self.parameters())
 
 
 _GENERATE_MASK_ORIG = generate_mask_with_prob
@@ -177,14 +182,24 @@ class TokenConditionedTransformerWrapper(nn.Module):
     """open_musiclm.py:219-410."""
 
     def __init__(self, *, transformer: TokenConditionedTransformer, pad_id=-1, unique_consecutive=True,
-                 cross_entropy_loss_weights: Optional[List[float]] = None, mask_prob=0.15, null_cond_prob=0.):
-        """null_cond_prob (extension; default 0: off, nothing is drawn): the training side of classifier-free guidance.  In training mode
+                 cross_entropy_loss_weights: Optional[List[float]] = None, mask_prob=0.15, null_cond_prob=0.,
+                 label_smoothing=0., z_loss=0.):
+        """label_smoothing = eps in [0, 1) and z_loss = zeta >= 0 (extensions; default 0: off, the plain cross entropy and the launches it
+        always made): the training loss of a live row becomes (1 - eps) nll + eps smooth + zeta lse^2 (include/omlm.h; eps is
+        F.cross_entropy's label_smoothing over the codebook_size + 1 entries, zeta the z-loss of PaLM / T5X, which keeps log Z near 0 --
+        what the 16-bit head logits of "fp16" / "fp16ff" want).  Both terms live in the cross-entropy kernels, forward and backward.
+        Training mode only, like mask_prob, dropout and null_cond_prob: eval(), trainer.validate() and score() report the plain cross
+        entropy, bit for bit what they report without the keywords, so valid_loss stays comparable across runs and is the plain-CE
+        monitor of a regularised run.
+        null_cond_prob (extension; default 0: off, nothing is drawn): the training side of classifier-free guidance.  In training mode
         sample b of a batch trains on the null condition (null_condition_ids at every id position of token sequence 0, ATTENDED; its
         appended eos, every other sequence and all labels untouched) iff u_b < null_cond_prob, u one torch.rand(B) drawn after the forgetful
         mask's randn.  A number in [0, 1) (1: every sample; tests).  eval() never drops.  ``generate(cond_scale=...)`` is meaningful only
         on weights trained with it."""
         super().__init__()
         self.null_cond_prob = ops.check_null_cond_prob(null_cond_prob)          # refused by name
+        self.label_smoothing = ops.check_label_smoothing(label_smoothing)
+        self.z_loss = ops.check_z_loss(z_loss)
         if self.null_cond_prob > 0:
             _require_condition(transformer.token_sequences, "null_cond_prob")
         self.transformer = transformer
@@ -199,6 +214,10 @@ class TokenConditionedTransformerWrapper(nn.Module):
     @property
     def device(self):
         return next(self.parameters()).device
+
+    def _loss_reg(self) -> dict:
+        """label_smoothing / z_loss as loss_and_logits takes them: the constructor's values in training mode, nothing in eval()."""
+        return dict(label_smoothing=self.label_smoothing, z_loss=self.z_loss) if self.training else {}
 
     @eval_decorator
     @torch.no_grad()
@@ -449,10 +468,10 @@ class TokenConditionedTransformerWrapper(nn.Module):
         prepared = engine.PreparedIds(ids32, lens)
         ignore = [False] * len(ids)
         if torch.is_grad_enabled():
-            loss, *logits = self.transformer.loss_and_logits(prepared, labels, keymask, weights, ignore, False)
+            loss, *logits = self.transformer.loss_and_logits(prepared, labels, keymask, weights, ignore, False, **self._loss_reg())
         else:
             with torch.enable_grad():
-                loss, *logits = self.transformer.loss_and_logits(prepared, labels, keymask, weights, ignore, False)
+                loss, *logits = self.transformer.loss_and_logits(prepared, labels, keymask, weights, ignore, False, **self._loss_reg())
             loss = loss.detach()
         return loss, [l.transpose(1, 2) if l is not None else None for l in logits], labels
 
@@ -508,10 +527,10 @@ class TokenConditionedTransformerWrapper(nn.Module):
         ignore = [bool(info.unique_consecutive and self.unique_consecutive) for info in self.token_sequences]
         loss_labels = [lb.masked_fill(lb == self.pad_id, -1) if ig else lb for lb, ig in zip(labels, ignore)]
         if torch.is_grad_enabled():
-            loss, *logits = self.transformer.loss_and_logits(ids, loss_labels, mask, weights, ignore, return_logits)
+            loss, *logits = self.transformer.loss_and_logits(ids, loss_labels, mask, weights, ignore, return_logits, **self._loss_reg())
         else:
             with torch.enable_grad():
-                loss, *logits = self.transformer.loss_and_logits(ids, loss_labels, mask, weights, ignore, return_logits)
+                loss, *logits = self.transformer.loss_and_logits(ids, loss_labels, mask, weights, ignore, return_logits, **self._loss_reg())
             loss = loss.detach()
         all_logits = [l.transpose(1, 2) if l is not None else None for l in logits]               # 'b n c -> b c n' (:389)
         return loss, all_logits, labels
@@ -576,10 +595,13 @@ def get_or_compute_acoustic_token_ids(coarse_token_ids, fine_token_ids, raw_audi
 class _Stage(nn.Module):
     """Shared plumbing of SemanticStage / CoarseStage / FineStage (open_musiclm.py:514-814)."""
 
-    def _make_wrapper(self, transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob=0.):
+    def _make_wrapper(self, transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob=0.,
+                      label_smoothing=0., z_loss=0.):
+        """label_smoothing / z_loss: the wrapper's training-mode loss terms (its constructor's docstring); eval() is the plain cross entropy."""
         self.transformer_wrapper = TokenConditionedTransformerWrapper(
             transformer=transformer, pad_id=pad_id, unique_consecutive=unique_consecutive,
-            cross_entropy_loss_weights=cross_entropy_loss_weights, mask_prob=mask_prob, null_cond_prob=null_cond_prob)
+            cross_entropy_loss_weights=cross_entropy_loss_weights, mask_prob=mask_prob, null_cond_prob=null_cond_prob,
+            label_smoothing=label_smoothing, z_loss=z_loss)
 
     @property
     def device(self):
@@ -604,14 +626,16 @@ def _split_logprobs(result, kwargs):
 
 class SemanticStage(_Stage):
     def __init__(self, *, semantic_transformer: TokenConditionedTransformer, wav2vec=None, clap=None, pad_id=-1,
-                 unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15, null_cond_prob=0.):
+                 unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15, null_cond_prob=0.,
+                 label_smoothing=0., z_loss=0.):
         super().__init__()
         self.wav2vec, self.clap = wav2vec, clap
         num_semantic_tokens = semantic_transformer.token_sequences[1].codebook_size
         if exists(wav2vec):
             assert wav2vec.codebook_size == num_semantic_tokens, \
                 f'num_semantic_tokens on SemanticTransformer must be set to {wav2vec.codebook_size}'
-        self._make_wrapper(semantic_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob)
+        self._make_wrapper(semantic_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob,
+                           label_smoothing, z_loss)
 
     @eval_decorator
     @torch.no_grad()
@@ -638,7 +662,8 @@ class SemanticStage(_Stage):
 
 class CoarseStage(_Stage):
     def __init__(self, *, coarse_transformer: TokenConditionedTransformer, wav2vec=None, clap=None, neural_codec=None,
-                 pad_id=-1, unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15, null_cond_prob=0.):
+                 pad_id=-1, unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15, null_cond_prob=0.,
+                 label_smoothing=0., z_loss=0.):
         super().__init__()
         self.wav2vec, self.clap, self.neural_codec = wav2vec, clap, neural_codec
         num_semantic_tokens = coarse_transformer.token_sequences[1].codebook_size
@@ -646,7 +671,8 @@ class CoarseStage(_Stage):
             assert wav2vec.codebook_size == num_semantic_tokens, \
                 f'num_semantic_tokens on CoarseTransformer must be set to {wav2vec.codebook_size}'
         self.num_coarse_quantizers = coarse_transformer.token_sequences[-1].num_quantizers
-        self._make_wrapper(coarse_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob)
+        self._make_wrapper(coarse_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob,
+                           label_smoothing, z_loss)
 
     @eval_decorator
     @torch.no_grad()
@@ -675,11 +701,13 @@ class CoarseStage(_Stage):
 
 class FineStage(_Stage):
     def __init__(self, *, fine_transformer: TokenConditionedTransformer, clap=None, neural_codec=None, pad_id=-1,
-                 unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15, null_cond_prob=0.):
+                 unique_consecutive=False, cross_entropy_loss_weights: List[float] = None, mask_prob=0.15, null_cond_prob=0.,
+                 label_smoothing=0., z_loss=0.):
         super().__init__()
         self.clap, self.neural_codec = clap, neural_codec
         self.num_coarse_quantizers = fine_transformer.token_sequences[1].num_quantizers
-        self._make_wrapper(fine_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob)
+        self._make_wrapper(fine_transformer, pad_id, unique_consecutive, cross_entropy_loss_weights, mask_prob, null_cond_prob,
+                           label_smoothing, z_loss)
 
     @eval_decorator
     @torch.no_grad()

@@ -753,16 +753,56 @@ def prepare_train_batch(raw_ids, eos_ids, quantizers, codebooks, pad_id, scores,
     return ids32, keymask, labels, [l + 1 for l in lens[:-1]] + [lens[-1]]
 
 
-def ce_fwd(logits, labels, row_lse, nll_sum, V):
+def _check_number(x):
+    try:
+        return float("nan") if isinstance(x, (str, bytes, bool)) else float(x)
+    except (TypeError, ValueError):
+        return float("nan")
+
+
+def check_label_smoothing(eps, name="label_smoothing"):
+    """The label-smoothing weight as a float: a number in [0, 1) (include/omlm.h; 0: off).  Anything else (negative, 1 and above, NaN,
+    inf, not a number) raises a ValueError that names the argument.  Pure Python: runs before any device work."""
+    v = _check_number(eps)
+    if not (0.0 <= v < 1.0):
+        raise ValueError(f"{name} must be a number in [0, 1), not {eps!r}")
+    return v
+
+
+def check_z_loss(zeta, name="z_loss"):
+    """The z-loss weight as a float: a finite number >= 0 as fp32 (include/omlm.h; 0: off).  Anything else (negative, NaN, inf, not a
+    number) raises a ValueError that names the argument.  Pure Python: runs before any device work."""
+    v = _check_number(zeta)
+    if not (0.0 <= v <= FP32_MAX):
+        raise ValueError(f"{name} must be a finite number >= 0 (as fp32), not {zeta!r}")
+    return v
+
+
+def ce_fwd(logits, labels, row_lse, nll_sum, V, *, label_smoothing=0., z_loss=0.):
+    """omlm_cross_entropy_fwd: row_lse written, nll_sum[0] accumulated onto.  With label_smoothing or z_loss set (include/omlm.h) the call
+    is omlm_cross_entropy_fwd_reg and `nll_sum` is the 3 floats {nll, smooth, z}; with both 0 it is the call it always was."""
+    eps, zeta = check_label_smoothing(label_smoothing), check_z_loss(z_loss)
     R, ld = logits.shape
-    call("omlm_cross_entropy_fwd", ptr(logits), ptr(labels), ptr(row_lse), ptr(nll_sum), R, V, ld,
+    if eps == 0.0 and zeta == 0.0:
+        call("omlm_cross_entropy_fwd", ptr(logits), ptr(labels), ptr(row_lse), ptr(nll_sum), R, V, ld,
+             ptr(index_error_flag(logits.device)), stream_ptr())
+        return
+    if nll_sum.dtype != torch.float32 or nll_sum.numel() != 3 or not nll_sum.is_contiguous():
+        raise ValueError(f"ce_fwd: with label_smoothing / z_loss the sums are 3 contiguous fp32 {{nll, smooth, z}}; got {nll_sum.dtype} {tuple(nll_sum.shape)}")
+    call("omlm_cross_entropy_fwd_reg", ptr(logits), ptr(labels), ptr(row_lse), ptr(nll_sum), R, V, ld,
          ptr(index_error_flag(logits.device)), stream_ptr())
 
 
-def ce_bwd(logits, labels, row_lse, gscale, coef, dlogits, V):
+def ce_bwd(logits, labels, row_lse, gscale, coef, dlogits, V, *, label_smoothing=0., z_loss=0.):
+    """omlm_cross_entropy_bwd; with label_smoothing or z_loss set, omlm_cross_entropy_bwd_reg (the gradient rule of include/omlm.h)."""
+    eps, zeta = check_label_smoothing(label_smoothing), check_z_loss(z_loss)
     R, ld = logits.shape
-    call("omlm_cross_entropy_bwd", ptr(logits), ptr(labels), ptr(row_lse), ptr(gscale), float(coef), ptr(dlogits),
-         R, V, ld, dlogits.shape[-1], dcode(dlogits.dtype), stream_ptr())
+    if eps == 0.0 and zeta == 0.0:
+        call("omlm_cross_entropy_bwd", ptr(logits), ptr(labels), ptr(row_lse), ptr(gscale), float(coef), ptr(dlogits),
+             R, V, ld, dlogits.shape[-1], dcode(dlogits.dtype), stream_ptr())
+        return
+    call("omlm_cross_entropy_bwd_reg", ptr(logits), ptr(labels), ptr(row_lse), ptr(gscale), float(coef), ptr(dlogits),
+         R, V, ld, dlogits.shape[-1], dcode(dlogits.dtype), eps, zeta, stream_ptr())
 
 
 def sumsq_accumulate(g, out, partials=None):

@@ -111,8 +111,12 @@ class SingleStageTrainer(nn.Module):
                  save_model_every=1000, results_folder='./results', accelerate_kwargs: dict = {},
                  config_paths: Optional[List[str]] = None, dataset_yields_tokens: Optional[bool] = None,
                  use_hip_graph: Optional[bool] = None, ema_decay: Optional[float] = None, ema_update_after_step: int = 0,
-                 ema_warmup: bool = True, null_cond_prob: float = 0.):
-        """null_cond_prob (0: off; no reference counterpart): the share of training samples whose CLAP condition is replaced by the null
+                 ema_warmup: bool = True, null_cond_prob: float = 0., label_smoothing: float = 0., z_loss: float = 0.):
+        """label_smoothing / z_loss (0: off; no reference counterpart): the train wrapper's loss becomes (1 - eps) nll + eps smooth +
+        zeta lse^2 per row (TokenConditionedTransformerWrapper, include/omlm.h), in the cross-entropy kernels.  Training mode only:
+        ``validate`` (on the model or the EMA twin) reports the plain cross entropy, so valid_loss stays comparable across runs and is
+        the plain-CE monitor of a regularised run, while the logged train loss carries both terms.
+        null_cond_prob (0: off; no reference counterpart): the share of training samples whose CLAP condition is replaced by the null
         condition (TokenConditionedTransformerWrapper), the training side of ``generate(cond_scale=...)``.  validate, generate and the
         EMA twin's wrapper never drop.
         ema_decay (None: off; no reference counterpart): the fused optimizer step keeps an exponential moving average of the weights
@@ -157,6 +161,7 @@ class SingleStageTrainer(nn.Module):
             raise ValueError(f'invalid stage: {stage}')
         self.cross_entropy_loss_weights = cross_entropy_loss_weights
         self.null_cond_prob = null_cond_prob
+        self.label_smoothing, self.z_loss = label_smoothing, z_loss            # checked by the wrapper, by name
         self.train_wrapper = self._make_stage(transformer, null_cond_prob)
         self.ds_fields = token_fields if tokens_in else wave_fields
 
@@ -243,17 +248,18 @@ class SingleStageTrainer(nn.Module):
 
     def _make_stage(self, transformer, null_cond_prob=0.):
         """The stage wrapper of this trainer around `transformer`: the model (train_wrapper, with the trainer's condition drop) or its EMA
-        twin (none)."""
+        twin (none).  Both carry label_smoothing / z_loss, which act in training mode only (the twin's wrapper lives in eval())."""
         w = self.cross_entropy_loss_weights
+        reg = dict(label_smoothing=self.label_smoothing, z_loss=self.z_loss)
         if self.stage == 'semantic':
             return SemanticStage(semantic_transformer=transformer, wav2vec=self.wav2vec, clap=self.audio_conditioner,
-                                 cross_entropy_loss_weights=default(w, [0., 1.]), null_cond_prob=null_cond_prob)
+                                 cross_entropy_loss_weights=default(w, [0., 1.]), null_cond_prob=null_cond_prob, **reg)
         if self.stage == 'coarse':
             return CoarseStage(coarse_transformer=transformer, neural_codec=self.neural_codec, wav2vec=self.wav2vec,
                                clap=self.audio_conditioner, cross_entropy_loss_weights=default(w, [0., 0., 1.]),
-                               null_cond_prob=null_cond_prob)
+                               null_cond_prob=null_cond_prob, **reg)
         return FineStage(fine_transformer=transformer, clap=self.audio_conditioner, neural_codec=self.neural_codec,
-                         cross_entropy_loss_weights=default(w, [0., 0., 1.]), null_cond_prob=null_cond_prob)
+                         cross_entropy_loss_weights=default(w, [0., 0., 1.]), null_cond_prob=null_cond_prob, **reg)
 
     # ---- checkpointing (trainer.py:359-391) ----------------------------------------------------------
     def save(self, model_path, optim_path, scheduler_path=None, ema_path=None):

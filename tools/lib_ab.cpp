@@ -3,7 +3,7 @@
 // (tolerance only where fp32 atomics make the order free: d(bias), split-K), and times each with HIP events.  A whole run is a few
 // seconds -- no Python import on the GPU box.
 //   build (here):  hipcc -O2 tools/lib_ab.cpp -o tools/lib_ab -ldl
-//   run (GPU box): tools/lib_ab base.so [ENV=V@]variant.so ... -- attn attn_large gemm gemm_edge wgrad ffmid ln
+//   run (GPU box): tools/lib_ab base.so [ENV=V@]variant.so ... -- attn attn_large gemm gemm_edge wgrad ffmid ln ce
 #include <hip/hip_runtime.h>
 #include "../include/omlm.h"        // struct layouts only (omlm_decode_args); every call goes through dlsym
 #include <dlfcn.h>
@@ -39,11 +39,15 @@ typedef int (*lnf_t)(const float*, const float*, void*, void*, float*, float*, i
 typedef long long (*lnws_t)(int);
 typedef int (*lnb_t)(const void*, const float*, const float*, const float*, const float*, const float*, const void*, float*, void*, float*, float*, int, int, float, int, int, void*);
 typedef int (*dstep_t)(const omlm_decode_args*, const long long*, void*);
+typedef int (*cef_t)(const float*, const int*, float*, float*, int, int, int, int*, void*);
+typedef int (*ceb_t)(const float*, const int*, const float*, const float*, float, void*, int, int, int, int, int, void*);
+typedef int (*cebr_t)(const float*, const int*, const float*, const float*, float, void*, int, int, int, int, int, float, float, void*);
 typedef int (*planes_t)(const void*, long long, const void*, long long, void*, const float*, const int*, const int*, const int*, long long, long long,
                         int, int, int, int, int, int, int, int, int, int, float, void*, long long, void*);
 
 struct Lib {
     std::string path; void* h; fwd_t fwd; bwd_t bwd; bwsz_t bwsz; prep_t prep; tbl_t tbl; gemm_t gemm; err_t err; wgrad_t wgrad; planes_t planes; ffwd_t ffwd; fws_t fws; fbwd_t fbwd; lnf_t lnf; lnws_t lnws; lnb_t lnb; dstep_t dstep;
+    cef_t cef, cefr; ceb_t ceb; cebr_t cebr;           // cefr / cebr: null in a library older than the regularised cross entropy
     void load(const char* p) {
         path = p;
         h = dlopen(p, RTLD_NOW | RTLD_LOCAL);
@@ -53,6 +57,8 @@ struct Lib {
         gemm = (gemm_t)dlsym(h, "omlm_gemm"); err = (err_t)dlsym(h, "omlm_last_error"); wgrad = (wgrad_t)dlsym(h, "omlm_gemm_wgrad_group"); planes = (planes_t)dlsym(h, "omlm_gemm_planes");
         ffwd = (ffwd_t)dlsym(h, "omlm_ffmid_fwd"); fws = (fws_t)dlsym(h, "omlm_ffmid_bwd_workspace_bytes"); fbwd = (fbwd_t)dlsym(h, "omlm_ffmid_bwd");
         lnf = (lnf_t)dlsym(h, "omlm_layernorm_fwd"); lnws = (lnws_t)dlsym(h, "omlm_layernorm_bwd_workspace_bytes"); lnb = (lnb_t)dlsym(h, "omlm_layernorm_bwd2"); dstep = (dstep_t)dlsym(h, "omlm_decode_step");
+        cef = (cef_t)dlsym(h, "omlm_cross_entropy_fwd"); ceb = (ceb_t)dlsym(h, "omlm_cross_entropy_bwd");
+        cefr = (cef_t)dlsym(h, "omlm_cross_entropy_fwd_reg"); cebr = (cebr_t)dlsym(h, "omlm_cross_entropy_bwd_reg");
         if (!fwd || !bwd || !bwsz || !prep || !tbl || !gemm || !err) { fprintf(stderr, "%s: missing symbol\n", p); exit(1); }
     }
     void ok(int rc, const char* what) { if (rc != 0) { fprintf(stderr, "%s: %s failed (%d): %s\n", path.c_str(), what, rc, err()); exit(1); } }
@@ -489,6 +495,55 @@ static void decode_case(Lib& A, Lib& Bl, int B) {
     report("logits", compare(res[0], res[1]), true);
 }
 
+// Cross entropy at the coarse bench step (R = 32 x 1116 rows, V = 1025, ld = ldd = 1032, fp16 gradient: the wave kernels of both
+// directions): the plain pair of A against the plain pair of B (row_lse and dlogits bit for bit) and, where B has them, against B's
+// regularised pair at (eps, zeta) = (0.1, 1e-4).  Interleaved rounds, device events.
+static void ce_case(Lib& A, Lib& Bl) {
+    const int R = 35712, V = 1025, ld = 1032;
+    printf("== cross entropy  R=%d V=%d ld=%d (fp32 logits, fp16 dlogits)\n", R, V, ld);
+    if (!A.cef || !A.ceb || !Bl.cef || !Bl.ceb) { printf("  a library lacks the cross-entropy entries\n"); return; }
+    std::vector<float> lg((size_t)R * ld); fill_f32(lg, 2.f, 41);
+    std::vector<int> lb(R); for (int r = 0; r < R; ++r) lb[r] = (r % 7 == 6) ? -1 : (int)(((long long)r * 7919 + 13) % V);
+    float* dlg = dev(lg); int* dlb = dev(lb);
+    float one = 0.25f; std::vector<float> gs(1, one); float* dgs = dev(gs);
+    Lib* libs[2] = {&A, &Bl};
+    float *lse[3], *sums[3]; uint16_t* dl[3];
+    for (int i = 0; i < 3; ++i) { lse[i] = dev_zero<float>(R); sums[i] = dev_zero<float>(4); dl[i] = dev_zero<uint16_t>((size_t)R * ld); }
+    const bool reg = Bl.cefr && Bl.cebr;
+    auto fwd = [&](int i) {
+        if (i < 2) libs[i]->ok(libs[i]->cef(dlg, dlb, lse[i], sums[i], R, V, ld, nullptr, nullptr), "ce_fwd");
+        else Bl.ok(Bl.cefr(dlg, dlb, lse[i], sums[i], R, V, ld, nullptr, nullptr), "ce_fwd_reg");
+    };
+    auto bwd = [&](int i) {
+        if (i < 2) libs[i]->ok(libs[i]->ceb(dlg, dlb, lse[i], dgs, 1.f / R, dl[i], R, V, ld, ld, 2, nullptr), "ce_bwd");
+        else Bl.ok(Bl.cebr(dlg, dlb, lse[i], dgs, 1.f / R, dl[i], R, V, ld, ld, 2, 0.1f, 1e-4f, nullptr), "ce_bwd_reg");
+    };
+    const int arms = reg ? 3 : 2, rounds = 6;
+    for (int i = 0; i < arms; ++i) { fwd(i); bwd(i); }
+    CK(hipDeviceSynchronize());
+    double sum[3][2] = {{0}}, best[3][2]; for (auto& r : best) for (auto& v : r) v = 1e30;
+    for (int r = 0; r < rounds + 1; ++r)
+        for (int i = 0; i < arms; ++i) {
+            const float f = time_us([&] { fwd(i); }, 20), b = time_us([&] { bwd(i); }, 20);
+            if (r > 0) { sum[i][0] += f; sum[i][1] += b; best[i][0] = std::fmin(best[i][0], (double)f); best[i][1] = std::fmin(best[i][1], (double)b); }
+        }
+    const char* names[3] = {"A plain", "B plain", "B regularised (0.1, 1e-4)"};
+    const double fb = (double)R * V * 4, bb = (double)R * V * 4 + (double)R * ld * 2;
+    for (int i = 0; i < arms; ++i)
+        printf("  %-26s %-40s fwd %7.1f us (min %7.1f, %4.2f TB/s)  bwd %7.1f us (min %7.1f, %4.2f TB/s)\n", names[i], (i ? Bl : A).path.c_str(),
+               sum[i][0] / rounds, best[i][0], fb / (sum[i][0] / rounds) / 1e6, sum[i][1] / rounds, best[i][1], bb / (sum[i][1] / rounds) / 1e6);
+    // one clean pass each for the comparison (the timed loops accumulated onto the sums)
+    for (int i = 0; i < arms; ++i) { CK(hipMemset(sums[i], 0, 16)); fwd(i); bwd(i); }
+    CK(hipDeviceSynchronize());
+    report("lse", compare(host(lse[0], R), host(lse[1], R)), true);
+    printf("  dlogits A plain vs B plain: %zu of %zu differ bitwise (expected 0)\n", count_diff(host(dl[0], (size_t)R * ld), host(dl[1], (size_t)R * ld)), (size_t)R * ld);
+    auto s0 = host(sums[0], 4), s1 = host(sums[1], 4);
+    printf("  nll sum A %.6e B %.6e\n", s0[0], s1[0]);
+    if (reg) { auto s2 = host(sums[2], 4); report("lse_r", compare(host(lse[1], R), host(lse[2], R)), true); printf("  regularised sums: nll %.6e smooth %.6e z %.6e\n", s2[0], s2[1], s2[2]); }
+    for (int i = 0; i < 3; ++i) { CK(hipFree(lse[i])); CK(hipFree(sums[i])); CK(hipFree(dl[i])); }
+    CK(hipFree(dlg)); CK(hipFree(dlb)); CK(hipFree(dgs));
+}
+
 int main(int argc, char** argv) {
     // usage: lib_ab base.so [NAME=VALUE@]variant.so ... -- case ...      (NAME=VALUE is exported before that library's first call:
     //        the libraries cache their OMLM_* switches per instance, so the same code can be timed under two settings from two copies)
@@ -500,7 +555,7 @@ int main(int argc, char** argv) {
         Lib* L = new Lib; L->load(a.c_str()); if (!env.empty()) L->path = env + "@" + a;
         libs.push_back(L); envs.push_back(env);
     }
-    if (libs.size() < 2 || i >= argc) { fprintf(stderr, "usage: %s base.so [ENV=V@]variant.so ... -- attn|attn_large|attn32|gemm|gemm_edge|wgrad|ffmid|ln|decode ...\n", argv[0]); return 2; }
+    if (libs.size() < 2 || i >= argc) { fprintf(stderr, "usage: %s base.so [ENV=V@]variant.so ... -- attn|attn_large|attn32|gemm|gemm_edge|wgrad|ffmid|ln|decode|ce ...\n", argv[0]); return 2; }
     hipDeviceProp_t pr; CK(hipGetDeviceProperties(&pr, 0)); printf("device: %s, %d CUs\n", pr.name, pr.multiProcessorCount);
     for (++i; i < argc; ++i)
         for (size_t v = 1; v < libs.size(); ++v) {
@@ -516,6 +571,7 @@ int main(int argc, char** argv) {
             else if (!strcmp(argv[i], "wgrad5")) wgrad_case(*libs[0], *libs[v], 64);        // K = 35648: whole 64-deep k-tiles (the step's own K = 35712 is one too)
             else if (!strcmp(argv[i], "ffmid")) ffmid_case(*libs[0], *libs[v]);
             else if (!strcmp(argv[i], "ln")) ln_case(*libs[0], *libs[v]);
+            else if (!strcmp(argv[i], "ce")) ce_case(*libs[0], *libs[v]);
             else if (!strcmp(argv[i], "decode")) { decode_case(*libs[0], *libs[v], 1); decode_case(*libs[0], *libs[v], 8); }
         }
     return 0;
