@@ -591,6 +591,30 @@ int omlm_sample(const omlm_sample_args* args, void* stream);
  * indexed by *step_dev when args->step_dev is given (like hist); either may be NULL; both NULL: exactly omlm_sample. */
 int omlm_sample_lp(const omlm_sample_args* args, float* lp_model, float* lp_sampled, void* stream);
 
+/* Per-row sampling parameters: omlm_sample_lp with k, temperature, top_p, the stream's seed and the stream's sample index of every row
+ * taken from [B] device arrays.  Row r of the call is the function stated above evaluated with k_r, T_r and top_p_r: tie rule,
+ * fixed-point nucleus masses, first maximum, the all -inf rule, both log-probabilities (at T_r), hist, step_dev, the embedding gather --
+ * id for id and bit for bit what omlm_sample_lp gives row r with those three as its scalars.  forbid_last stays one value per call (it
+ * belongs to the quantizer phase).  On the counter stream row r draws u(t, sample_r, c) from seed_r (seed_r = seed_hi * 2^32 + seed_lo
+ * of the stream above): a row's uniforms then depend on its own pair alone, not on its place in the call.
+ * A NULL member leaves the block's scalar in force for every row (seed: seed_lo / seed_hi; sample: row0 + row).  The arrays are indexed
+ * by the row alone, also with step_dev (one value per row for the whole call).  top_p_r == 1: no nucleus for that row -- it takes the
+ * path of a call with top_p == 1, beside rows that run one.
+ * Checks, all before the launch: rows == NULL or every member NULL is exactly the launch of omlm_sample_lp; seed or sample together
+ * with args->uniform is refused by name (they belong to the counter stream); a scalar whose array is given is neither read nor
+ * checked; everything else keeps the checks above.  The library sees pointers, not values: k_r is clamped into [1, V]; a temperature that
+ * is not > 0 or a top_p outside (0, 1] (NaN included) gives an unspecified id in [0, V) and unspecified log-probabilities for that row,
+ * never an out-of-range access.  One launch; lp_model / lp_sampled as for omlm_sample_lp, either or both NULL. */
+typedef struct omlm_sample_row_params {
+    const int*   k;                    /* [B] device, or NULL: args->k           */
+    const float* temperature;          /* [B] device, or NULL: args->temperature */
+    const float* top_p;                /* [B] device, or NULL: args->top_p       */
+    const unsigned long long* seed;    /* [B] device, or NULL: args->seed_lo/hi  (counter stream only) */
+    const int*   sample;               /* [B] device, or NULL: args->row0 + row  (counter stream only) */
+} omlm_sample_row_params;
+int omlm_sample_rows(const omlm_sample_args* args, const omlm_sample_row_params* rows,
+                     float* lp_model, float* lp_sampled, void* stream);
+
 /* Classifier-free guidance on the condition (token sequence 0, the CLAP tokens).  The null condition is the pad embedding at every id
  * position of that sequence: raw id -1 - codebook (p mod Q) at position p, which is -1 after the per-quantizer offset and therefore the
  * zero row of the gather; the appended eos, the start tokens and every other sequence are unchanged.  A guided call of P prompts decodes
@@ -603,6 +627,11 @@ int omlm_sample_lp(const omlm_sample_args* args, float* lp_model, float* lp_samp
  * cond / null / out: [rows, ld] fp32, columns V .. ld - 1 are not written; out may alias cond.  16-byte loads where ld % 4 == 0 and the
  * three bases are 16-byte aligned, scalar loads otherwise and on the tail of a row.  One launch; scale finite and >= 0, V <= 2^24. */
 int omlm_guide_logits(const float* cond, const float* null, float* out, int rows, int V, int ld, float scale, void* stream);
+/* The same with one scale per row: g_c = n_c + (s_r * (l_c - n_c)) in row r, the same three roundings, loads, aliasing and untouched
+ * columns.  scale: fp32 [rows] on the device; its values are not checked -- a non-finite scale gives non-finite g in its own row and
+ * nothing out of range. */
+int omlm_guide_logits_rows(const float* cond, const float* null, float* out, int rows, int V, int ld,
+                           const float* scale /* [rows] device */, void* stream);
 
 /* The twin copy of a guided decode cycle, one launch: ids_twin[r] = ids[r] and x_twin[r, :] = x[r, :] for r < rows -- the ids the sampler
  * picked for the conditional rows and the embedding rows it gathered, handed to the null twins.  Either pair of pointers may be NULL

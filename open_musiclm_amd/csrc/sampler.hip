@@ -70,11 +70,35 @@ __device__ __forceinline__ float sample_top_p(const SampleStreamP& p) { return p
 // wraps the source's argument block and appends the two output pointers, so the LP = false instantiations keep the argument types and the
 // kernarg layout they had.  The per-source functions above see through the wrapper.
 template <typename S> struct SampleLP { S s; float* lp_model; float* lp_sampled; };
-template <bool RNG, bool NUC, bool LP> struct sample_arg { typedef typename sample_src<RNG, NUC>::type type; };
-template <bool RNG, bool NUC> struct sample_arg<RNG, NUC, true> { typedef SampleLP<typename sample_src<RNG, NUC>::type> type; };
+// The per-row parameters (ROWS, a fifth compile-time choice; omlm_sample_rows in include/omlm.h): [B] device arrays, each or null, that
+// stand in for k, temperature, top_p, the stream's seed and the stream's sample index of a row.  ROWS = true extends the nucleus- and
+// log-prob-capable block (a base class: every member, and every per-source function above, is reached as before) by the five pointers,
+// so the ROWS = false instantiations keep their argument types and their kernarg layout.  Only that one form is built per kernel width
+// and source: top_p_r == 1 skips the nucleus by a wave-uniform branch, null lp pointers skip the stores.
+struct SampleRowParams { const int* k; const float* temperature; const float* top_p; const unsigned long long* seed; const int* sample; };
+template <typename S> struct SampleRows : S { SampleRowParams r; };
+template <bool RNG, bool NUC, bool LP, bool ROWS = false> struct sample_arg { typedef typename sample_src<RNG, NUC>::type type; };
+template <bool RNG, bool NUC> struct sample_arg<RNG, NUC, true, false> { typedef SampleLP<typename sample_src<RNG, NUC>::type> type; };
+template <bool RNG> struct sample_arg<RNG, true, true, true> { typedef SampleRows<SampleLP<typename sample_src<RNG, true>::type>> type; };
 template <typename S> __device__ __forceinline__ const float* sample_row_uniforms(const SampleLP<S>& p, size_t offset) { return sample_row_uniforms(p.s, offset); }
 template <typename S> __device__ __forceinline__ unsigned sample_row_key(const SampleLP<S>& p, const int* step_dev, int row) { return sample_row_key(p.s, step_dev, row); }
 template <typename S> __device__ __forceinline__ float sample_top_p(const SampleLP<S>& p) { return sample_top_p(p.s); }
+// ROWS: the row's values replace the call's, once, before anything reads them -- in the kernel's own copy of its arguments, so the stream
+// key, the nucleus and the slot loops below are the code they are for a call-wide value.  The loads are wave-uniform (indexed by the row
+// alone, also with step_dev): scalar loads.  k is clamped into [1, V]; the other values are the caller's (include/omlm.h: a temperature
+// that is not > 0 or a top_p outside (0, 1] gives an unspecified id in [0, V), every index below is bounded whatever they are).  The
+// stream's global sample index is row0 + row: row0 becomes sample_r - row.
+__device__ __forceinline__ void sample_row_stream(SampleBufferP&, const SampleRowParams&, int) {}
+__device__ __forceinline__ void sample_row_stream(SampleStreamP& p, const SampleRowParams& r, int row) {
+    if (r.seed) { const unsigned long long s = r.seed[row]; p.s.seed_lo = (unsigned)s; p.s.seed_hi = (unsigned)(s >> 32); }
+    if (r.sample) p.s.row0 = r.sample[row] - row;
+}
+template <typename S> __device__ __forceinline__ void sample_row_params(SampleRows<SampleLP<S>>& p, int row, int V, int& k, float& temperature) {
+    if (p.r.k) { const int kr = p.r.k[row]; k = kr < 1 ? 1 : (kr > V ? V : kr); }
+    if (p.r.temperature) temperature = p.r.temperature[row];
+    if (p.r.top_p) p.s.top_p = p.r.top_p[row];
+    sample_row_stream(p.s, p.r, row);
+}
 // The two values from the sums: l_s the sampled id's logit, m the largest kept logit, M = max(m, the forbidden last logit), sum_model the
 // sum of exp(l_c - M) over all V entries, sum_sampled the sum of exp((l_c - m) / T) over the set the id was drawn from.  m = -inf (the
 // "id 0" rule): both -inf.  A one-entry set gives sum_sampled = 1 and l_s = m: exactly 0.
@@ -111,8 +135,8 @@ __device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) 
     return ((unsigned long long)hi << 32) | lo;              // the builtin returns int: unsigned BEFORE widening, or the low half sign-extends
 }
 
-template <int SAMPLE_NV, bool RNG, bool NUC, bool LP = false>
-__global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ logits, typename sample_arg<RNG, NUC, LP>::type uniform,
+template <int SAMPLE_NV, bool RNG, bool NUC, bool LP = false, bool ROWS = false>
+__global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ logits, typename sample_arg<RNG, NUC, LP, ROWS>::type uniform,
                                                     long long* __restrict__ out, int V, int ld, int k, float temperature,
                                                     int forbid_last, const int* __restrict__ step_dev, long long* __restrict__ hist,
                                                     const float* __restrict__ emb_table, long long emb_row_offset, long long emb_rows,
@@ -130,6 +154,7 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
         if (hist) hist += sidx * gridDim.x;
     }
     const int row = blockIdx.x, lane = threadIdx.x;
+    if constexpr (ROWS) sample_row_params(uniform, row, V, k, temperature);
     const float* lr = logits + (size_t)row * ld;
     const float* ur = sample_row_uniforms(uniform, (size_t)row * V);
     const unsigned ukey = sample_row_key(uniform, step_dev, row);      // RNG: the stream's key of (step, global sample index), wave-uniform
@@ -178,7 +203,7 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
         for (int j = 0; j < SAMPLE_NV; ++j) ng += __popcll(__ballot(keys[j] > t));
     }
     int n_equal_keep = exact ? 0x7fffffff : k - ng;
-    if constexpr (NUC) {
+    if constexpr (NUC) if (!ROWS || sample_top_p(uniform) < 1.f) {      // ROWS: a row of top_p 1 takes the NUC = false path (wave-uniform)
         // The nucleus: the largest x >= t whose mass M(x) = sum of q over the kept keys >= x reaches thr; then the entries above x are in,
         // and of the entries equal to x the first ceil((thr - mass above x) / q_x) by index (they share one q).  The kept entries tied at t
         // enter as ONE term n q_t, so no slot needs its rank here.  The descent starts below the bits t and the row maximum share (every kept
@@ -308,8 +333,8 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* __restrict__ lo
 // The descent ends with t = the k-th largest key and kk = k - count(keys > t), the number of tied entries to keep.
 constexpr int SW_COPIES = 8;
 constexpr int SW_UC = 16;                                 // uniforms in flight per lane in the scoring pass
-template <int NV, bool RNG, bool NUC, bool LP = false>
-__global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restrict__ logits, typename sample_arg<RNG, NUC, LP>::type uniform,
+template <int NV, bool RNG, bool NUC, bool LP = false, bool ROWS = false>
+__global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restrict__ logits, typename sample_arg<RNG, NUC, LP, ROWS>::type uniform,
                                                            long long* __restrict__ out, int V, int ld, int k, float temperature,
                                                            int forbid_last, const int* __restrict__ step_dev, long long* __restrict__ hist,
                                                            const float* __restrict__ emb_table, long long emb_row_offset,
@@ -334,6 +359,7 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
     // every pass forms its indices from a value of its own (the empty asm): hipcc otherwise keeps the 64 indices, and the 64 `c < V` masks,
     // of the first pass alive to the last one and spills them
     int c0 = base + lane;
+    if constexpr (ROWS) sample_row_params(uniform, row, V, k, temperature);
     const float* lr = logits + (size_t)row * ld;
     const float* ur = sample_row_uniforms(uniform, (size_t)row * V);
     const unsigned ukey = sample_row_key(uniform, step_dev, row);      // RNG: the stream's key of (step, global sample index), one per workgroup
@@ -396,7 +422,7 @@ __global__ __launch_bounds__(1024) void sample_wide_kernel(const float* __restri
         t |= (unsigned)s_sel[0] << shift;
         kk = s_sel[1];
     }
-    if constexpr (NUC) {
+    if constexpr (NUC) if (!ROWS || sample_top_p(uniform) < 1.f) {      // ROWS: a row of top_p 1 takes the NUC = false path (workgroup-uniform)
         // The nucleus on the same machinery: radix rounds over the 8-bit digits with a 64-bit MASS per bin (integer LDS adds: any arrival order
         // gives the same sums), scanned from the top bin down to the bin where the running mass reaches thr.  Only the keys above t add
         // their mass; the kk kept entries tied at t are one term kk q_t that wave 0 adds to t's bin, so no rank is needed.  The weights are
@@ -630,8 +656,8 @@ struct omlm_sample_args {                                 // include/omlm.h
 // per lane that hold the row, and only the waves that own a live index.  `src` is the kernel's second argument (sample_arg).  The wide
 // kernels are named first: instantiation order is function order in the module, and with the wave kernels first two independent
 // instructions of the wide kernels' bin scan swap (profiles/sampler_stream.md section 1).
-template <bool RNG, bool NUC, bool LP>
-static void sample_launch(const omlm_sample_args& a, typename sample_arg<RNG, NUC, LP>::type src, void* stream) {
+template <bool RNG, bool NUC, bool LP, bool ROWS = false>
+static void sample_launch(const omlm_sample_args& a, typename sample_arg<RNG, NUC, LP, ROWS>::type src, void* stream) {
     const bool emb = a.emb_table != nullptr;
 #define SAMPLE_GO(BLOCK_, ...) hipLaunchKernelGGL((__VA_ARGS__), dim3(a.B), BLOCK_, 0, as_stream(stream), a.logits, src, a.out, a.V, a.ld, a.k,   \
                                                   a.temperature, a.forbid_last, a.step_dev, a.hist, a.emb_table, emb ? a.emb_row_offset : 0ll, \
@@ -639,12 +665,12 @@ static void sample_launch(const omlm_sample_args& a, typename sample_arg<RNG, NU
     if (a.V > 2048) {
         const int nv = a.V <= 4096 ? 4 : a.V <= 16384 ? 16 : 64;
         const dim3 block(64 * ((a.V + 64 * nv - 1) / (64 * nv)));
-        if (nv == 4) SAMPLE_GO(block, sample_wide_kernel<4, RNG, NUC, LP>);
-        else if (nv == 16) SAMPLE_GO(block, sample_wide_kernel<16, RNG, NUC, LP>);
-        else SAMPLE_GO(block, sample_wide_kernel<64, RNG, NUC, LP>);
+        if (nv == 4) SAMPLE_GO(block, sample_wide_kernel<4, RNG, NUC, LP, ROWS>);
+        else if (nv == 16) SAMPLE_GO(block, sample_wide_kernel<16, RNG, NUC, LP, ROWS>);
+        else SAMPLE_GO(block, sample_wide_kernel<64, RNG, NUC, LP, ROWS>);
     }
-    else if (a.V <= 64 * 17) SAMPLE_GO(dim3(64), sample_kernel<17, RNG, NUC, LP>);
-    else SAMPLE_GO(dim3(64), sample_kernel<32, RNG, NUC, LP>);
+    else if (a.V <= 64 * 17) SAMPLE_GO(dim3(64), sample_kernel<17, RNG, NUC, LP, ROWS>);
+    else SAMPLE_GO(dim3(64), sample_kernel<32, RNG, NUC, LP, ROWS>);
 #undef SAMPLE_GO
 }
 
@@ -737,6 +763,39 @@ extern "C" int omlm_sample_embed_at_rng(const float* logits, unsigned seed_lo, u
     return sample_checked("omlm_sample_embed_at_rng", a, NEED_STEP_DEV | NEED_EMBED, nullptr, nullptr, stream);
 }
 
+// The row-parameter form (include/omlm.h): per-row k / temperature / top_p / seed / sample index from [B] device arrays.  No array: the
+// launch of omlm_sample_lp.  Otherwise one launch of the ROWS form of the kernel the block selects -- named here, after every other
+// form (the note in sample_checked) -- with the scalars of the arrays that are given neither read nor checked.
+struct omlm_sample_row_params {                          // include/omlm.h
+    const int* k; const float* temperature; const float* top_p; const unsigned long long* seed; const int* sample;
+};
+extern "C" int omlm_sample_rows(const omlm_sample_args* args, const omlm_sample_row_params* rows, float* lp_model, float* lp_sampled,
+                                void* stream) {
+    OMLM_CHECK_ARG(args != nullptr, "args");
+    if (!rows || (!rows->k && !rows->temperature && !rows->top_p && !rows->seed && !rows->sample))
+        return sample_checked("omlm_sample_rows", *args, 0, lp_model, lp_sampled, stream);
+    const omlm_sample_args& a = *args;
+    if (a.B <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(!(a.uniform && rows->seed), "omlm_sample_rows: rows->seed belongs to the counter stream; args->uniform selects the buffer");
+    OMLM_CHECK_ARG(!(a.uniform && rows->sample), "omlm_sample_rows: rows->sample belongs to the counter stream; args->uniform selects the buffer");
+    OMLM_CHECK_ARG(a.logits && a.out && a.V > 0 && a.V <= 65536 && (rows->k || (a.k >= 1 && a.k <= a.V)) &&
+                   (rows->temperature || a.temperature > 0.f),
+                   "sampler arguments (0 < V <= 65536, 1 <= k <= V, temperature > 0)");
+    OMLM_CHECK_ARG(rows->top_p || (a.top_p > 0.f && a.top_p <= 1.f), "top_p (0 < top_p <= 1; 1 = no nucleus)");
+    if (a.emb_table) OMLM_CHECK_ARG(a.x && a.D > 0 && a.D % 4 == 0 && a.emb_rows > 0, "embedding arguments");
+    omlm_sample_args b = a;                               // the scalars a row array replaces: any valid value, the kernel overwrites it
+    if (rows->k) b.k = 1;
+    if (rows->temperature) b.temperature = 1.f;
+    const float top_p = rows->top_p ? 1.f : a.top_p;
+    const SampleRowParams rp{rows->k, rows->temperature, rows->top_p, rows->seed, rows->sample};
+    if (a.uniform) sample_launch<false, true, true, true>(b, {{SampleBufferP{a.uniform, top_p}, lp_model, lp_sampled}, rp}, stream);
+    else {
+        const SampleStream st{a.seed_lo, a.seed_hi, a.step_dev ? 0 : a.step, a.row0};
+        sample_launch<true, true, true, true>(b, {{SampleStreamP{st, top_p}, lp_model, lp_sampled}, rp}, stream);
+    }
+    return omlm_post_launch("omlm_sample_rows");
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Classifier-free guidance around the sampler (include/omlm.h).  Two small kernels that sit in front of and behind the sampler launch
 // of a guided decode cycle; the sampler kernels above are what they were.
@@ -755,7 +814,7 @@ __device__ __forceinline__ float guide_one(float l, float n, float s) {
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(256) void guide_logits_kernel(const float* cond, const float* null, float* out, int V, int ld, float s) {
+__device__ __forceinline__ void guide_logits_row(const float* cond, const float* null, float* out, int V, int ld, float s) {
     const size_t base = (size_t)blockIdx.x * ld;                       // one row per blockIdx.x, 1024 columns per blockIdx.y
     const int c0 = 4 * (blockIdx.y * 256 + threadIdx.x);
     if (c0 >= V) return;
@@ -770,6 +829,16 @@ __global__ __launch_bounds__(256) void guide_logits_kernel(const float* cond, co
     const int c1 = c0 + 4 < V ? c0 + 4 : V;
     for (int c = c0; c < c1; ++c) out[base + c] = guide_one(cond[base + c], null[base + c], s);
 }
+template <bool VEC>
+__global__ __launch_bounds__(256) void guide_logits_kernel(const float* cond, const float* null, float* out, int V, int ld, float s) {
+    guide_logits_row<VEC>(cond, null, out, V, ld, s);
+}
+// the same with a scale per row (omlm_guide_logits_rows): one workgroup-uniform load, then the code above
+template <bool VEC>
+__global__ __launch_bounds__(256) void guide_logits_rows_kernel(const float* cond, const float* null, float* out, int V, int ld,
+                                                                const float* __restrict__ scale) {
+    guide_logits_row<VEC>(cond, null, out, V, ld, scale[blockIdx.x]);
+}
 
 extern "C" int omlm_guide_logits(const float* cond, const float* null, float* out, int rows, int V, int ld, float scale, void* stream) {
     if (rows <= 0) return OMLM_OK;
@@ -780,6 +849,18 @@ extern "C" int omlm_guide_logits(const float* cond, const float* null, float* ou
     if (vec) hipLaunchKernelGGL(guide_logits_kernel<true>, grid, dim3(256), 0, as_stream(stream), cond, null, out, V, ld, scale);
     else     hipLaunchKernelGGL(guide_logits_kernel<false>, grid, dim3(256), 0, as_stream(stream), cond, null, out, V, ld, scale);
     return omlm_post_launch("omlm_guide_logits");
+}
+// scale [rows] on the device: not checked (a non-finite value gives non-finite g in its own row, nothing out of range)
+extern "C" int omlm_guide_logits_rows(const float* cond, const float* null, float* out, int rows, int V, int ld, const float* scale,
+                                      void* stream) {
+    if (rows <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(cond && null && out && V > 0 && ld >= V && V <= (1 << 24), "guide_logits_rows arguments (0 < V <= ld, V <= 2^24)");
+    OMLM_CHECK_ARG(scale != nullptr, "guide_logits_rows: scale (fp32 [rows], device)");
+    const bool vec = ld % 4 == 0 && (((size_t)cond | (size_t)null | (size_t)out) & 15) == 0;
+    const dim3 grid(rows, (V + 1023) / 1024);
+    if (vec) hipLaunchKernelGGL(guide_logits_rows_kernel<true>, grid, dim3(256), 0, as_stream(stream), cond, null, out, V, ld, scale);
+    else     hipLaunchKernelGGL(guide_logits_rows_kernel<false>, grid, dim3(256), 0, as_stream(stream), cond, null, out, V, ld, scale);
+    return omlm_post_launch("omlm_guide_logits_rows");
 }
 
 // twin: what the sampler left for the conditional rows -- the sampled ids [rows] and their gathered embedding rows [rows, D] -- copied to

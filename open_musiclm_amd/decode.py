@@ -347,6 +347,20 @@ class CachedDecoder:
         return self.logits
 
 
+def _guided(guidance) -> bool:
+    """Whether a guidance argument (not yet checked) turns guidance on: a per-row sequence always does; a number unless it is None or 1."""
+    if isinstance(guidance, (list, tuple)) or getattr(guidance, "ndim", 0) == 1:
+        return True
+    return ops.check_cond_scale(guidance, "guidance") is not None
+
+
+def _per_row_topk(topk, P: int, V1: int):
+    """The sampler's count k: a number as it is; a sequence of length P as a list of ints, each in [1, V1] (a ValueError names the entry)."""
+    def entry(v):
+        return int(v) if isinstance(v, int) and not isinstance(v, bool) and 1 <= v <= V1 else None
+    return ops.per_row_checked(topk, P, "topk", lambda s: s, entry, f"an integer in [1, {V1}]")
+
+
 class SamplingLoop:
     """sample -> embed -> 6 layers -> head -> advance, per id, for one CachedDecoder.
 
@@ -368,22 +382,31 @@ class SamplingLoop:
     the result are sized P.  Per id: omlm_guide_logits forms g = null + s (cond - null) from the two halves of dec.logits into a buffer of
     the loop that the sampler reads (so ``lp_model`` is the log-softmax of g); the sampler gathers the embedding rows of the P ids;
     omlm_decode_twin hands ids and rows to the null half; then the step runs on all 2P rows as it is.  Two more launches per id, all
-    pointers fixed: the captured cycle holds all of it."""
+    pointers fixed: the captured cycle holds all of it.
+    Per-row settings: ``temperature``, ``topk`` (the counts k), ``top_p``, ``guidance`` and the seed of ``rng`` may each be a sequence of
+    length P, one value per row the sampler serves (checked here, before any device work: ops.per_row_*).  The loop uploads them once as
+    [P] device arrays and stores the pointers beside the argument blocks it builds once per phase, so a captured cycle stays valid; the
+    sampler calls are then omlm_sample_rows and a per-row ``guidance`` is combined by omlm_guide_logits_rows (every row beside its twin,
+    the rows of scale 1 included).  With per-row seeds every row draws with stream sample index 0 -- u(t, 0, c) of its own seed, what a
+    one-sample loop with that seed draws -- and ``rng[1]`` is not read.  With scalars the blocks and the calls are what they always were."""
 
     def __init__(self, dec: CachedDecoder, first_logits: torch.Tensor, uniforms: Optional[torch.Tensor], n0: int, n_new: int, topk: int,
                  temperature: float, forbid_by_phase: Sequence[bool], use_graph: bool = True, rng=None, top_p=None,
                  logprobs: bool = False, guidance=None):
         ops.check_sampler_width(dec.V1)                    # before any launch: the loop's first sampler call would refuse it
-        self.top_p = ops.check_top_p(top_p)                # 1.0: no nucleus
-        self.guidance = ops.check_cond_scale(guidance, "guidance")        # None: off
+        P = self.P = dec.B // 2 if _guided(guidance) else dec.B                  # rows the sampler serves
+        self.top_p = ops.per_row_top_p(top_p, P)           # 1.0: no nucleus
+        self.guidance = ops.per_row_cond_scale(guidance, P, "guidance")        # None: off
         if self.guidance is not None and dec.B % 2:
             raise ValueError(f"SamplingLoop: guidance needs a decoder of 2P rows (prompts, then their null twins); it holds {dec.B}")
         if (uniforms is None) == (rng is None):
             raise ValueError("SamplingLoop: give either the uniforms [n_new, B, V1] or rng=(seed, row0), not both and not neither")
-        self.dec, self.n0, self.n_new, self.topk, self.temperature = dec, n0, n_new, topk, float(temperature)
+        temperature, topk = ops.per_row_temperature(temperature, P), _per_row_topk(topk, P, dec.V1)
+        seeds = ops.per_row_seed(rng[0], P, "rng seed") if rng is not None else None
+        self.dec, self.n0, self.n_new, self.topk = dec, n0, n_new, topk
+        self.temperature = temperature if isinstance(temperature, list) else float(temperature)
         self.forbid = [bool(f) for f in forbid_by_phase]
         dev = dec.logits.device
-        P = self.P = dec.B // 2 if self.guidance is not None else dec.B          # rows the sampler serves
         if rng is None:
             assert uniforms.shape == (n_new, P, dec.V1) and uniforms.dtype == torch.float32 and uniforms.is_contiguous()
             self.U = uniforms
@@ -391,7 +414,7 @@ class SamplingLoop:
             # counter stream (include/omlm.h): sample b of this decoder draws u(step, row0 + b, c) from the seed -- no buffer; seed halves
             # and row0 are plain arguments, so a captured cycle holds for the whole call
             self.U = None
-            self.seed, self.row0 = ops.split_seed(rng[0]), int(rng[1])
+            self.seed, self.row0 = ((0, 0), 0) if isinstance(seeds, list) else (ops.split_seed(seeds), int(rng[1]))
         self.hist = torch.zeros(n_new, P, device=dev, dtype=torch.long)
         self.cur = torch.zeros(dec.B, device=dev, dtype=torch.long)             # guided: the sampler writes [0, P), the twin copy [P, 2P)
         self.step_dev = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -401,13 +424,23 @@ class SamplingLoop:
         # guided: the sampler reads the combined rows from here, dec.logits keeps both branches
         self.guided = torch.zeros(P, dec.ldV, device=dev, dtype=torch.float32) if self.guidance is not None else None
         src = dec.logits if self.guidance is None else self.guided
+        # per-row settings: uploaded once, [P] each; the block's scalar of an uploaded array is not read (a valid placeholder)
+        as_rows = lambda v, member: ops.row_tensor(v if isinstance(v, list) else None, member, dev)
+        self.row_k, self.row_temperature, self.row_top_p = as_rows(topk, "k"), as_rows(temperature, "temperature"), as_rows(self.top_p, "top_p")
+        self.row_seed = as_rows(seeds, "seed")
+        self.row_sample = torch.zeros(P, device=dev, dtype=torch.int32) if self.row_seed is not None else None
+        self.row_guidance = as_rows(self.guidance, "scale")
+        self._rows = ops.sample_row_params(P, k=self.row_k, temperature=self.row_temperature, top_p=self.row_top_p, seed=self.row_seed,
+                                           sample=self.row_sample)              # None: the calls the loop has always made
+        scalar = lambda v, placeholder: placeholder if isinstance(v, list) else v
         # the sampler's argument blocks (ops.SampleArgs), built once: per quantizer phase, without and with the embedding gather of the
         # sampled id.  Every pointer in them is a fixed buffer of this loop or its decoder.
         seed, row0 = ((0, 0), 0) if rng is None else (self.seed, self.row0)
 
         def block(phase: int, embed: bool):
             sa = ops.SampleArgs(ptr(src), P, dec.V1, dec.ldV, ptr(self.U), *seed, 0, row0, ptr(self.step_dev), ptr(self.cur),
-                                ptr(self.hist), self.topk, self.temperature, self.top_p, int(self.forbid[phase]))
+                                ptr(self.hist), scalar(self.topk, 1), scalar(self.temperature, 1.0), scalar(self.top_p, 1.0),
+                                int(self.forbid[phase]))
             if embed:
                 sa.emb_table, sa.emb_row_offset, sa.emb_rows = dec.emb.data_ptr(), dec.codebook * phase if dec.Q > 1 else 0, dec.emb.shape[0]
                 sa.x, sa.D = ptr(dec.x), dec.D
@@ -425,9 +458,14 @@ class SamplingLoop:
         # the head kernel (the step's last) moves the row index and the sampler's step counter on
         sa = self._blocks[phase][with_decode]
         P = self.P
-        if self.guidance is not None:      # g = null + s (cond - null) from the two halves of dec.logits, into the sampler's rows
+        if self.row_guidance is not None:  # the same with the scale of every row
+            call("omlm_guide_logits_rows", ptr(dec.logits), dec.logits[P:].data_ptr(), ptr(self.guided), P, dec.V1, dec.ldV,
+                 ptr(self.row_guidance), stream_ptr())
+        elif self.guidance is not None:    # g = null + s (cond - null) from the two halves of dec.logits, into the sampler's rows
             call("omlm_guide_logits", ptr(dec.logits), dec.logits[P:].data_ptr(), ptr(self.guided), P, dec.V1, dec.ldV, self.guidance, stream_ptr())
-        if self.logprobs:
+        if self._rows is not None:
+            call("omlm_sample_rows", C.addressof(sa), C.addressof(self._rows), ptr(self.lp_model), ptr(self.lp_sampled), stream_ptr())
+        elif self.logprobs:
             call("omlm_sample_lp", C.addressof(sa), ptr(self.lp_model), ptr(self.lp_sampled), stream_ptr())
         else:
             call("omlm_sample", C.addressof(sa), stream_ptr())

@@ -107,7 +107,9 @@ SIGNATURES = {
     "omlm_sample_embed_at_rng": [vp, u32, u32, vp, i32, vp, vp, i32, i32, i32, i32, f32, i32, vp, i64, i64, vp, i32, vp],
     "omlm_sample": [vp, vp],
     "omlm_sample_lp": [vp, vp, vp, vp],
+    "omlm_sample_rows": [vp, vp, vp, vp, vp],
     "omlm_guide_logits": [vp, vp, vp, i32, i32, i32, f32, vp],
+    "omlm_guide_logits_rows": [vp, vp, vp, i32, i32, i32, vp, vp],
     "omlm_decode_twin": [vp, vp, vp, vp, i32, i32, vp],
     "omlm_probe_tr16": [vp, vp],
 }

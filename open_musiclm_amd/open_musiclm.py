@@ -251,13 +251,35 @@ class TokenConditionedTransformerWrapper(nn.Module):
         the call launches exactly what it launches without the argument.  A guided call of P prompts is a decode call of 2P rows, so a
         decode call holds decode.max_call_batch // 2 prompts; uniforms (``uniforms``: [steps, P, V+1]), ids and log-probabilities cover
         the P prompts only.  Meaningful only on weights trained with ``null_cond_prob``: any other checkpoint has never seen the null
-        condition."""
-        cond_scale = ops.check_cond_scale(cond_scale)                           # before any device work; None = off
+        condition.
+        Per-row settings: ``temperature``, ``filter_thres``, ``top_p``, ``cond_scale`` and ``sampler_seed`` each take a number, as above,
+        or a list / tuple / 1-D tensor of length B with one value per row (ranges as for the numbers; a wrong length or a bad entry raises a
+        ValueError that names the argument, before any device work).  The rows of one call are then sampled each in its own way by the same
+        launches (omlm_sample_rows, omlm_guide_logits_rows; include/omlm.h) on every route, with every source of uniforms and with
+        ``return_logprobs``; row r gets what a call with row r's numbers gives it.  A per-row ``cond_scale`` decodes every row beside its
+        null twin, the rows of scale 1 included: such a row's g is formed by the rule above and is not promised to equal the unguided call.
+        A per-row ``sampler_seed`` needs the counter stream (``sampler_rng`` None chooses it; "buffer" or injected ``uniforms`` are
+        refused): every row then draws u(t, 0, c) of its own seed, what a one-sample call with that seed draws, so a row's uniforms depend on
+        its seed alone, not on its place in the batch or on its neighbours.  Its ids equal that one-sample call's wherever the step kernels
+        give a row the same logits at both batch sizes -- not promised between B = 1 and B >= 2 at dim 1024, where different kernels run.
+        With a number the stream index stays the global sample index."""
+        # rows of the call, as the checks below need them (no conditioning sequence: a model the checks further down refuse or serve as before)
+        batch = conditioning_token_ids[0].shape[0] if len(conditioning_token_ids) else (pred_token_ids.shape[0] if exists(pred_token_ids) else 0)
+        cond_scale = ops.per_row_cond_scale(cond_scale, batch)                  # before any device work; None = off
         if cond_scale is not None:
             _require_condition(self.token_sequences, "cond_scale")
         assert len(conditioning_token_ids) == len(self.token_sequences) - 1
         ops.check_sampler_width(self.token_sequences[-1].codebook_size + 1)      # before any device work
-        top_p = ops.check_top_p(top_p)                                          # likewise; 1.0 = off
+        top_p = ops.per_row_top_p(top_p, batch)                                 # likewise; 1.0 = off
+        temperature = ops.per_row_temperature(temperature, batch)               # likewise (a number: as it is)
+        filter_thres = ops.per_row_filter_thres(filter_thres, batch)
+        sampler_seed = ops.per_row_seed(sampler_seed, batch)
+        if isinstance(sampler_seed, list):
+            decode.sampler_rng_choice(sampler_rng, 0, batch, 1, False)          # an unknown sampler_rng is refused as in every call
+            if sampler_rng == "buffer" or exists(uniforms):
+                raise ValueError("a per-row sampler_seed seeds the counter stream: it cannot be combined with sampler_rng='buffer' or "
+                                 "injected uniforms (sampler_rng=None or 'counter', uniforms=None)")
+            sampler_rng = "counter"
         decode.kv_cache_choice(kv_cache, self.transformer._precision())         # likewise: a ValueError names the accepted values
         kv_kw = {} if kv_cache is None else dict(kv_cache=kv_cache)             # (None: the decoders are built as they always were)
         batch, device = conditioning_token_ids[0].shape[0], self.device
@@ -287,7 +309,7 @@ class TokenConditionedTransformerWrapper(nn.Module):
             guide_kw = {}                                                       # (off: the loops are built as they always were)
 
         V1 = pred_info.codebook_size + 1
-        k = max(int((1 - filter_thres) * V1), 1)
+        k = ops.topk_count(filter_thres, V1)
         Q = pred_info.num_quantizers
         step = 0
         nxt = torch.empty(batch, device=device, dtype=torch.long)
@@ -324,6 +346,9 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 group //= 2                                                     # pairs per call
             for b0 in range(0, batch, group):
                 b1 = min(batch, b0 + group)
+                cut = lambda v: v[b0:b1] if isinstance(v, list) else v      # a call's rows of a per-row setting
+                if isinstance(cond_scale, list):
+                    guide_kw = dict(guidance=cut(cond_scale))
                 if cond_scale is not None:
                     dec = decode.CachedDecoder(self.transformer, 2 * (b1 - b0), rows, self.transformer._precision(), wide=True, **kv_kw)
                     last = dec.prefill([torch.cat((c[b0:b1], t[b0:b1]), dim=0) for c, t in zip(cond, twin)] +
@@ -332,11 +357,11 @@ class TokenConditionedTransformerWrapper(nn.Module):
                     dec = decode.CachedDecoder(self.transformer, b1 - b0, rows, self.transformer._precision(), wide=True, **kv_kw)
                     last = dec.prefill([t[b0:b1] for t in cond] + [sampled[b0:b1]])
                 if counter:            # sample b draws u(step, b, c) whichever piece it rides in
-                    loop = decode.SamplingLoop(dec, last, None, n0, n_new, k, temperature, forbid, use_graph=use_graph, rng=(sampler_seed, b0),
-                                               top_p=top_p, **lp_kw, **guide_kw)
+                    loop = decode.SamplingLoop(dec, last, None, n0, n_new, cut(k), cut(temperature), forbid, use_graph=use_graph,
+                                               rng=(cut(sampler_seed), b0), top_p=cut(top_p), **lp_kw, **guide_kw)
                 else:
-                    loop = decode.SamplingLoop(dec, last, U[:, b0:b1].contiguous(), n0, n_new, k, temperature, forbid, use_graph=use_graph,
-                                               top_p=top_p, **lp_kw, **guide_kw)
+                    loop = decode.SamplingLoop(dec, last, U[:, b0:b1].contiguous(), n0, n_new, cut(k), cut(temperature), forbid,
+                                               use_graph=use_graph, top_p=cut(top_p), **lp_kw, **guide_kw)
                 pieces.append(loop.run().t())                      # [b, n_new]
                 if return_logprobs:
                     lp_pieces.append((loop.lp_model.t(), loop.lp_sampled.t()))
@@ -350,23 +375,31 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 lp_model, lp_sampled = (torch.zeros(n_new, batch, device=device) for _ in range(2))
             if cond_scale is not None:
                 cond2 = [torch.cat((c, t), dim=0) for c, t in zip(cond, twin)]
+            # per-row settings: [B] device arrays, uploaded once (None for a number: the calls below are then what they always were)
+            as_rows = lambda v, member: ops.row_tensor(v if isinstance(v, list) else None, member, device)
+            rows_kw = dict(row_k=as_rows(k, "k"), row_temperature=as_rows(temperature, "temperature"), row_top_p=as_rows(top_p, "top_p"))
+            rows_kw = {n: t for n, t in rows_kw.items() if t is not None}
+            row_scale = as_rows(cond_scale, "scale")
+            if isinstance(sampler_seed, list):      # every row: u(t, 0, c) of its own seed
+                rows_kw.update(row_seed=as_rows(sampler_seed, "seed"), row_sample=torch.zeros(batch, device=device, dtype=torch.int32))
+            scalar = lambda v: None if isinstance(v, list) else v
             for _t in tqdm(range(first_step, max_time_steps), desc='generating predicted tokens'):
                 for ind in range(Q):
                     if cond_scale is not None:      # one 2B forward, then the combine in place over the conditional half
                         both = self.transformer.last_logits(cond2 + [torch.cat((sampled, sampled), dim=0)])
                         last = both[:batch]
-                        ops.guide_logits(last, both[batch:], last, V1, cond_scale)
+                        ops.guide_logits(last, both[batch:], last, V1, cond_scale if row_scale is None else row_scale)
                     else:
                         last = self.transformer.last_logits(cond + [sampled])
                     forbid = (not allow_eos_in_output) or (ind != Q - 1)
                     if counter:
-                        src = dict(seed=sampler_seed, step=step)
+                        src = dict(seed=scalar(sampler_seed), step=step)
                     elif exists(uniforms):
                         src = dict(uniform=uniforms[step].to(device).float().contiguous())
                     else:
                         src = dict(uniform=torch.empty(batch, V1, device=device).uniform_(0, 1))
                     lp = dict(lp_model=lp_model[step], lp_sampled=lp_sampled[step]) if return_logprobs else {}
-                    ops.sample(last, nxt, V1, k, temperature, forbid, top_p=top_p, **src, **lp)
+                    ops.sample(last, nxt, V1, scalar(k), scalar(temperature), forbid, top_p=scalar(top_p), **src, **lp, **rows_kw)
                     sampled = torch.cat((sampled, nxt[:, None]), dim=-1)
                     step += 1
             if return_logprobs:
@@ -643,7 +676,9 @@ class SemanticStage(_Stage):
                  semantic_token_ids=None, filter_thres=0.9, temperature=1., max_time_steps=30 * 25,
                  include_eos_in_output=False, append_eos_to_conditioning_tokens=True, **kwargs):
         """``return_logprobs=True`` (like every sampling keyword, passed on to the wrapper): returns (ids, LogProbs).  ``cond_scale``
-        (classifier-free guidance on the CLAP tokens) is such a keyword in every stage's generate."""
+        (classifier-free guidance on the CLAP tokens) is such a keyword in every stage's generate.  ``temperature``, ``filter_thres``,
+        ``top_p``, ``cond_scale`` and ``sampler_seed`` are handed on as they are in every stage's generate: a number, or one value per row
+        (TokenConditionedTransformerWrapper.generate)."""
         clap_token_ids = get_or_compute_clap_token_ids(clap_token_ids, self.clap, conditioning_audio, conditioning_text)
         if exists(semantic_token_ids) or exists(input_audio):
             semantic_token_ids = get_or_compute_semantic_token_ids(semantic_token_ids, input_audio, self.wav2vec)

@@ -692,15 +692,25 @@ def check_cond_scale(cond_scale, name="cond_scale"):
 def guide_logits(cond, null, out, V, scale):
     """omlm_guide_logits (include/omlm.h): out[r, c] = null[r, c] + scale * (cond[r, c] - null[r, c]) for c < V, three fp32 roundings.
     cond / null / out: fp32 [rows, ld] of one leading dimension (row-contiguous views such as the halves of a [2P, ld] block); out may be
-    cond.  Columns V .. ld - 1 of out are not written."""
-    s = check_cond_scale(scale, "scale")
+    cond.  Columns V .. ld - 1 of out are not written.
+    scale: a number, or a contiguous fp32 [rows] device tensor -- one scale per row, omlm_guide_logits_rows (its values are the caller's
+    to check: per_row_cond_scale)."""
+    by_row = isinstance(scale, torch.Tensor) and scale.dim() == 1
+    s = None if by_row else check_cond_scale(scale, "scale")
     rows, ld = cond.shape
+    if by_row:
+        hip.require_gpu(scale, "scale")
+        if scale.dtype != torch.float32 or scale.shape != (rows,) or not scale.is_contiguous():
+            raise ValueError(f"guide_logits: a per-row scale must be a contiguous fp32 tensor [{rows}]; got {scale.dtype} {tuple(scale.shape)}")
     for t, name in ((cond, "cond"), (null, "null"), (out, "out")):
         hip.require_gpu(t, name)
         if t.dtype != torch.float32 or t.shape != (rows, ld) or t.stride() != (ld, 1):
             raise ValueError(f"guide_logits: {name} must be fp32 [{rows}, {ld}] with contiguous rows; got {t.dtype} {tuple(t.shape)} {t.stride()}")
     if not 0 < int(V) <= ld:
         raise ValueError(f"guide_logits: V must lie in [1, {ld}], not {V}")
+    if by_row:
+        call("omlm_guide_logits_rows", ptr(cond), ptr(null), ptr(out), rows, int(V), ld, ptr(scale), stream_ptr())
+        return
     call("omlm_guide_logits", ptr(cond), ptr(null), ptr(out), rows, int(V), ld, 1.0 if s is None else s, stream_ptr())
 
 
@@ -1012,32 +1022,167 @@ def check_top_p(top_p, name="top_p"):
     return p
 
 
+class SampleRowParams(C.Structure):
+    """Mirror of ``omlm_sample_row_params`` (include/omlm.h): [B] device arrays, each or None."""
+    _fields_ = [("k", C.c_void_p), ("temperature", C.c_void_p), ("top_p", C.c_void_p), ("seed", C.c_void_p), ("sample", C.c_void_p)]
+
+
+# member of omlm_sample_row_params -> element type of its [B] array (a seed is 64 bits: uint64 held as int64)
+_ROW_DTYPES = {"k": torch.int32, "temperature": torch.float32, "top_p": torch.float32, "seed": torch.int64, "sample": torch.int32}
+
+
+def sample_row_params(B, **rows):
+    """SampleRowParams over the given [B] tensors (``k`` int32, ``temperature`` / ``top_p`` fp32, ``seed`` int64 holding the uint64,
+    ``sample`` int32; each contiguous on the device, or None), or None when none is given.  A wrong tensor raises a ValueError that
+    names it.  The VALUES are the caller's to check (the per_row_* functions below): the library sees pointers."""
+    if all(t is None for t in rows.values()):
+        return None
+    for name, t in rows.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != _ROW_DTYPES[name] or t.shape != (B,) or not t.is_contiguous():
+            got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else repr(t)
+            raise ValueError(f"sample: row_{name} must be a contiguous {_ROW_DTYPES[name]} tensor [{B}]; got {got}")
+        hip.require_gpu(t, f"row_{name}")
+    return SampleRowParams(*(ptr(rows[n]) for n, _ in SampleRowParams._fields_))
+
+
 def sample(logits, out, V, k, temperature, forbid_last, *, top_p=None, uniform=None, seed=None, step=0, row0=0, step_dev=None,
-           hist=None, emb_table=None, emb_row_offset=0, x=None, lp_model=None, lp_sampled=None):
+           hist=None, emb_table=None, emb_row_offset=0, x=None, lp_model=None, lp_sampled=None,
+           row_k=None, row_temperature=None, row_top_p=None, row_seed=None, row_sample=None):
     """omlm_sample: the sampler with an optional nucleus, one call over every form.  ``uniform`` ([B, V], or [steps, B, V] with
     ``step_dev``) or ``seed`` (the counter stream: row b draws u(step or *step_dev, row0 + b, c)) -- exactly one of the two;
     ``step_dev`` (int32 [1], device) selects the graph-replayable form, where ``hist`` is [steps, B]; ``emb_table`` [rows, D] with ``x``
     [B, D] adds the embedding gather.  top_p None or 1: the launch of sample_topk_gumbel*.
     ``lp_model`` / ``lp_sampled`` (fp32 [B], or [steps, B] with ``step_dev``; either or both): the log-probabilities of the sampled id
-    (include/omlm.h), written by the same launch -- the call is then omlm_sample_lp; the ids are those of the call without them."""
+    (include/omlm.h), written by the same launch -- the call is then omlm_sample_lp; the ids are those of the call without them.
+    ``row_k`` / ``row_temperature`` / ``row_top_p`` / ``row_seed`` / ``row_sample`` ([B] device tensors: int32 / fp32 / fp32 / the uint64
+    seeds as int64 / int32; any subset): per-row values in place of ``k`` / ``temperature`` / ``top_p`` / ``seed`` / ``row0 + b`` -- the
+    call is then omlm_sample_rows, and a scalar whose tensor is given is not read (pass None).  ``row_seed`` and ``row_sample`` belong
+    to the counter stream: ``row_seed`` stands for ``seed``, and either of them with ``uniform`` is refused.  Without them the call is
+    the one it has always been."""
     check_sampler_width(V)
-    p = check_top_p(top_p)
-    if (uniform is None) == (seed is None):
-        raise ValueError("sample: give either uniform= or seed=, not both and not neither")
     B, ld = logits.shape
+    rows = sample_row_params(B, k=row_k, temperature=row_temperature, top_p=row_top_p, seed=row_seed, sample=row_sample)
+    p = 1.0 if row_top_p is not None else check_top_p(top_p)
+    if uniform is not None and (row_seed is not None or row_sample is not None):
+        raise ValueError("sample: row_seed / row_sample belong to the counter stream and cannot be combined with uniform=")
+    if (uniform is None) == (seed is None and row_seed is None):
+        raise ValueError("sample: give either uniform= or seed=, not both and not neither")
     lo, hi = split_seed(seed) if seed is not None else (0, 0)
     a = SampleArgs(ptr(logits), B, int(V), ld, ptr(uniform), lo, hi, int(step), int(row0), ptr(step_dev), ptr(out), ptr(hist),
-                   int(k), float(temperature), p, int(forbid_last),
+                   1 if row_k is not None else int(k), 1.0 if row_temperature is not None else float(temperature), p, int(forbid_last),
                    ptr(emb_table), int(emb_row_offset), 0 if emb_table is None else emb_table.shape[0], ptr(x),
                    0 if emb_table is None else emb_table.shape[1])
-    if lp_model is None and lp_sampled is None:
+    if lp_model is None and lp_sampled is None and rows is None:
         call("omlm_sample", C.addressof(a), stream_ptr())
         return
     for t, name in ((lp_model, "lp_model"), (lp_sampled, "lp_sampled")):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != B):
             raise ValueError(f"sample: {name} must be a contiguous fp32 tensor [B] ([steps, B] with step_dev), B = {B}; got "
                              f"{t.dtype} {tuple(t.shape)}")
-    call("omlm_sample_lp", C.addressof(a), ptr(lp_model), ptr(lp_sampled), stream_ptr())
+    if rows is None:
+        call("omlm_sample_lp", C.addressof(a), ptr(lp_model), ptr(lp_sampled), stream_ptr())
+    else:
+        call("omlm_sample_rows", C.addressof(a), C.addressof(rows), ptr(lp_model), ptr(lp_sampled), stream_ptr())
+
+
+# ---- per-row sampling arguments: one pure-Python normaliser per argument of generate() / SamplingLoop -----------------------------
+# A plain number (or None) comes back as the scalar the call has always used; a list, tuple or 1-D tensor / array of length `batch`
+# comes back as a LIST of checked numbers, one per row.  Everything runs before any device work; a ValueError names the argument and,
+# for a bad entry, its index.
+
+def _row_sequence(x, batch, name):
+    """None for a scalar; the entries of a per-row sequence as a list of Python objects (length checked against `batch`)."""
+    if isinstance(x, (torch.Tensor,)) or type(x).__module__ == "numpy":
+        if getattr(x, "ndim", 0) == 0:
+            return None
+        if x.ndim != 1:
+            raise ValueError(f"{name}: a per-row value is a number or a 1-D sequence of length {batch}, not an array of shape {tuple(x.shape)}")
+        x = x.tolist()
+    if not isinstance(x, (list, tuple)):
+        return None
+    if len(x) != int(batch):
+        raise ValueError(f"{name}: a per-row sequence holds one value per row: its length is {len(x)}, the batch is {int(batch)}")
+    return list(x)
+
+
+def per_row_checked(x, batch, name, scalar, entry, what):
+    """The normaliser behind every per_row_* function: `scalar(x)` for a number; for a sequence of length `batch` the list of
+    `entry(v)`, where `entry` returns None for a value it refuses (`what` says what it accepts)."""
+    seq = _row_sequence(x, batch, name)
+    if seq is None:
+        return scalar(x)
+    out = []
+    for i, v in enumerate(seq):
+        r = None if v is None else entry(v)
+        if r is None:
+            raise ValueError(f"{name}[{i}] must be {what}, not {v!r}")
+        out.append(r)
+    return out
+
+
+def _as_fp32(v):
+    return C.c_float(v).value
+
+
+def per_row_temperature(temperature, batch, name="temperature"):
+    """A number: returned as it is (the sampler refuses what is not > 0).  A sequence: a list of floats, each finite and > 0 as fp32."""
+    def entry(v):
+        f = _check_number(v)
+        return f if 0.0 < f <= FP32_MAX and _as_fp32(f) > 0.0 else None
+    return per_row_checked(temperature, batch, name, lambda s: s, entry, "a finite number > 0")
+
+
+def per_row_filter_thres(filter_thres, batch, name="filter_thres"):
+    """A number: returned as it is.  A sequence: a list of floats, each in [0, 1] (row r keeps k_r = max(int((1 - thres_r) * V), 1))."""
+    def entry(v):
+        f = _check_number(v)
+        return f if 0.0 <= f <= 1.0 else None
+    return per_row_checked(filter_thres, batch, name, lambda s: s, entry, "a number in [0, 1]")
+
+
+def per_row_top_p(top_p, batch, name="top_p"):
+    """A number or None: check_top_p's float (1.0: no nucleus).  A sequence: a list of floats, each in (0, 1] (1: no nucleus for the row)."""
+    def entry(v):
+        f = _check_number(v)
+        return f if 0.0 < f <= 1.0 and _as_fp32(f) > 0.0 else None
+    return per_row_checked(top_p, batch, name, lambda s: check_top_p(s, name), entry, "a number in (0, 1]")
+
+
+def per_row_cond_scale(cond_scale, batch, name="cond_scale"):
+    """A number or None: check_cond_scale's value (None: off).  A sequence: a list of floats, each finite and >= 0 -- guidance is then on
+    for every row, the rows of scale 1 included."""
+    def entry(v):
+        f = _check_number(v)
+        return f if 0.0 <= f <= FP32_MAX else None
+    return per_row_checked(cond_scale, batch, name, lambda s: check_cond_scale(s, name), entry, "a finite number >= 0 (as fp32)")
+
+
+def per_row_seed(seed, batch, name="sampler_seed"):
+    """A number or None: returned as it is.  A sequence: a list of ints in [0, 2^64) (any Python int, taken modulo 2^64)."""
+    def entry(v):
+        if isinstance(v, bool) or not isinstance(v, int):
+            return None
+        return v & 0xFFFFFFFFFFFFFFFF
+    return per_row_checked(seed, batch, name, lambda s: s, entry, "an integer (taken modulo 2^64)")
+
+
+def topk_count(filter_thres, V1):
+    """k of a row of V1 logits: max(int((1 - thres) * V1), 1); a list for a list."""
+    if isinstance(filter_thres, list):
+        return [max(int((1 - t) * V1), 1) for t in filter_thres]
+    return max(int((1 - filter_thres) * V1), 1)
+
+
+def row_tensor(values, member, device):
+    """The [B] device tensor of a list of checked per-row values, in the element type of `member` of omlm_sample_row_params (a seed's
+    uint64 as the int64 of the same bits) or, for "scale", of omlm_guide_logits_rows' scale (fp32); None for None."""
+    if values is None:
+        return None
+    if member == "seed":
+        values = [v - (1 << 64) if v >= (1 << 63) else v for v in values]
+    return torch.tensor(values, dtype=torch.float32 if member == "scale" else _ROW_DTYPES[member]).to(device)
 
 
 def probe_tr16(out):

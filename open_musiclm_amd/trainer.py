@@ -319,7 +319,8 @@ class SingleStageTrainer(nn.Module):
 
     def generate(self, *args, use_ema=False, **kwargs):
         """The wrapper's generate, every keyword passed on: with ``return_logprobs=True`` it returns (ids, LogProbs), with ``cond_scale`` it
-        decodes under classifier-free guidance.
+        decodes under classifier-free guidance; ``temperature``, ``filter_thres``, ``top_p``, ``cond_scale`` and ``sampler_seed`` take a
+        number or one value per row.
         use_ema: sample from the weight EMA (the twin) instead of the training weights."""
         if use_ema:
             self._require_ema()
