@@ -128,6 +128,10 @@ int omlm_qk_norm_bwd2(const float* dq, const float* dk, const float* dv, const v
  * (one uint64 in device memory, read by the kernels: a captured graph draws new masks when the salt is bumped).  At p = 0 seed and seed_dev are
  * not read.  P < 0 or p outside [0, 1) is refused before any launch.
  * bwd: dq [B*N, H*64], dk, dv [B*N, 64] fp32 overwritten; dbias (bias's layout) accumulated (+=) over all its rows; delta scratch [B, H, N].
+ * A query row without any live score (its key mask drops every key it could see, e.g. key 0 for row 0) has no softmax: on every route its out
+ * row is 0 and its lse the sentinel 1e30, and the backward handed that lse gives it dq = 0 and lets it add nothing to dk, dv or dbias; no
+ * NaN or Inf is produced, and the other rows of the call are not affected.  A masked key's score never enters another row's result: it sets
+ * neither sum nor the running maximum (tests/test_gpu_attn_edges.py).  dk and dv rows of masked keys are exactly 0.
  *
  * Routes: 16-bit operands with biasT (or without any bias) run the second-generation kernels -- causal up to N = 16384
  * (omlm_attn_max_positions; 4096 < N runs their long forms: the forward's liveness prologue as a loop, the dQ kernel with a byte per key and a

@@ -325,7 +325,10 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
     }
     if (!active || qi >= N) return;
     lsum += __shfl_xor(lsum, 32, 64);
-    const float inv = (DROP ? drop.rs : 1.0f) / lsum;
+    // a query without any live key (include/omlm.h): m never left NEG_BIG, every visited score counted as exp2(0) and acc holds a plain
+    // average of the visited V rows -- emit zeros and the lse that zeroes its backward, as attention2.hip's forward does
+    const bool seen = m > NEG_BIG;                  // (both half-waves hold the same m)
+    const float inv = seen ? (DROP ? drop.rs : 1.0f) / lsum : 0.f;
     T* orow = out + (rowbase + qi) * (size_t)(H * 64) + h * 64;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
@@ -334,7 +337,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(2)))
             const int d = 32 * dt + 8 * g4 + 4 * hi;
             store4_from_float(orow + d, acc[dt][4 * g4] * inv, acc[dt][4 * g4 + 1] * inv, acc[dt][4 * g4 + 2] * inv, acc[dt][4 * g4 + 3] * inv);
         }
-    if (hi == 0 && lse) lse[((size_t)b * H + h) * N + qi] = m + log2f(lsum);   // log2 domain (DROP: the same value)
+    if (hi == 0 && lse) lse[((size_t)b * H + h) * N + qi] = seen ? m + log2f(lsum) : 1.0e30f;   // log2 domain (DROP: the same value)
 }
 
 // =============================================================================================================

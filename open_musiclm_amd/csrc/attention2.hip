@@ -23,6 +23,16 @@ namespace OMLM_NS {
 #define A2_PAD 64            /* zero entries in front of each row of the transposed bias table (rel >= -64) */
 #define A2_BWIN 128          /* floats per head in a tile's bias window */
 #define A2_NEG (-1.0e30f)
+// the online forward's masked keys: A2_MASKED is added to q.k (the lowest finite half; bf16: -65536), and a running maximum under A2_DEAD c
+// (c = scale log2 e) has seen no live score -- live ones have |q.k| far below 16384
+#if OMLM_FP16
+#define A2_MASKED_BITS 0xFBFFu
+#define A2_ONE_BITS 0x3C00u
+#else
+#define A2_MASKED_BITS 0xC780u
+#define A2_ONE_BITS 0x3F80u
+#endif
+#define A2_DEAD (-16384.0f)
 #define A2_LOG2E 1.4426950408889634f
 #define A2_STAGE (8192 + 8192 + 8 * A2_BWIN * 4)     /* K rows | V blocked | bias window = 20 KiB */
 #define A2_NST 3
@@ -227,10 +237,12 @@ struct A4Acc {
 //   keys, see common.h), the denominator MFMA the undropped P -- the 1 / (1 - p) scale is applied with 1 / denominator at the store.
 //   PFX: the non-causal prefix of Pn rows (include/omlm.h): keys up to kend = max(i0 + 32, Pn) for a query tile inside it, and the blocks
 //   not wholly below the diagonal keep (i, j) iff j <= i or i, j < Pn.
+//   lb (online form): the tile's liveness ballot (uniform); the scores of a tile's dead keys start from A2_MASKED, so that the running
+//   maximum is taken over live keys only.
 template <bool FIXED, bool FULL, int QSEL = -1, bool DROP = false, bool PFX = false>
 __device__ __forceinline__ void a4_tile(A4Acc& A, const h16x8 (&qf)[2][4], const char* Ks, const h16_t* live0, const h16_t* live1,
                                         float c, int i0, int j0, int wave, int lane, const unsigned (&rk)[2], unsigned thr16, int kend = 0,
-                                        int Pn = 0) {
+                                        int Pn = 0, unsigned long long lb = ~0ull) {
     const char* Vs = Ks + 8192;
     const int hi = lane >> 5, ql = lane & 31;
     // window index of (head hb, query ql, key 32 sub + 4 hi + cr): hb 128 + 64 + ql - 32 sub - 4 hi - cr, cr = crow(r, 0) <= 27
@@ -249,12 +261,27 @@ __device__ __forceinline__ void a4_tile(A4Acc& A, const h16x8 (&qf)[2][4], const
         const bool diag = !FULL && !(jb + 31 <= i0);
         const int d0 = (i0 + ql) - (jb + 4 * hi);
         const bool qpre = PFX && i0 + ql < Pn;                  // PFX: this lane's query row lies in the prefix
+        // lb: the tile's ballot word (uniform).  A masked key (or one past N) must not set the running maximum: neither sum takes its P,
+        // but the live keys' exp2(s - m) would sit that far lower -- 14 octaves under a masked score they leave half's normal range, 24
+        // under they are zero and the row comes out as one without a live key.  A tile with a dead key therefore starts its scores from
+        // a rank-one product, (A2_MASKED per dead key) x (1 per query), in k-slot 0 of ONE extra MFMA per head: no work per score.
+        const bool masked = !FIXED && lb != ~0ull;
+        h16x8 mka, mkb;
+        if (masked) {
+            const unsigned w = (unsigned)(lb >> (32 * sub));
+            u32x4 ua = {0u, 0u, 0u, 0u}, ub = {0u, 0u, 0u, 0u};
+            ua[0] = (hi == 0 && !((w >> ql) & 1u)) ? A2_MASKED_BITS : 0u;      // A rows are keys 32 sub + ql
+            ub[0] = hi == 0 ? A2_ONE_BITS : 0u;
+            mka = __builtin_bit_cast(h16x8, ua);
+            mkb = __builtin_bit_cast(h16x8, ub);
+        }
 #pragma unroll
         for (int hb = 0; hb < 2; ++hb) {
             if (QSEL >= 0 && hb != QSEL) continue;
             f32x16 st;
 #pragma unroll
             for (int e = 0; e < 16; ++e) st[e] = 0.f;
+            if (masked) st = MFMA16(mka, mkb, st);              // + A2_MASKED for the tile's dead keys, every query alike
 #pragma unroll
             for (int s = 0; s < 4; ++s) st = MFMA16(kf[s], qf[hb][s], st);
             const __attribute__((address_space(3))) float* bp = bb + (hb * A2_BWIN + 64 - 32 * sub - 27);       // entries [27 - cr]: offsets >= 0
@@ -291,8 +318,11 @@ __device__ __forceinline__ void a4_tile(A4Acc& A, const h16x8 (&qf)[2][4], const
                 const float mnew = fmaxf(A.m[hb], mloc);
                 const float alpha = __builtin_amdgcn_exp2f(A.m[hb] - mnew);
                 A.m[hb] = mnew;
+                // no live key yet (a masked score is about A2_MASKED c, one above the diagonal A2_NEG): the excluded scores must come out as
+                // 0, not as exp2(0) = 1 -- the denominator's live vector covers the masked keys, but not the live ones above the diagonal
+                const float msub = mnew > A2_DEAD * c ? mnew : 0.f;
 #pragma unroll
-                for (int r = 0; r < 16; ++r) st[r] = __builtin_amdgcn_exp2f(st[r] - mnew);
+                for (int r = 0; r < 16; ++r) st[r] = __builtin_amdgcn_exp2f(st[r] - msub);
                 if (!__all(alpha == 1.0f)) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) { A.acc[hb][0][e] *= alpha; A.acc[hb][1][e] *= alpha; }

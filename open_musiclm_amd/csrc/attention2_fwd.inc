@@ -161,17 +161,22 @@ __global__ __launch_bounds__(A4_THREADS, 2) void A4_KERNEL(const h16_t* __restri
         const h16_t* lv = livef + j0 + 4 * (lane_ >> 5);
         const h16_t* live0 = (lane_ & 1) == 0 ? lv : (const h16_t*)zeros;
         const h16_t* live1 = (lane_ & 1) == 1 ? lv : (const h16_t*)zeros;
+        unsigned long long lbt = ~0ull;                         // online form: the running maximum is taken over live keys (a4_tile)
+        if (!FIXED) {
+            const unsigned long long lw = livebits[t];
+            lbt = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(lw >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)lw);
+        }
         if (FIXED) {
             if (full) a4_tile<true, true, -1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
             else      a4_tile<true, false, -1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
         } else if (full) {
-            a4_tile<false, true, 0, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
+            a4_tile<false, true, 0, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn, lbt);
             __builtin_amdgcn_sched_barrier(0);
-            a4_tile<false, true, 1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
+            a4_tile<false, true, 1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn, lbt);
         } else {
-            a4_tile<false, false, 0, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
+            a4_tile<false, false, 0, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn, lbt);
             __builtin_amdgcn_sched_barrier(0);
-            a4_tile<false, false, 1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn);
+            a4_tile<false, false, 1, DROP, PFX>(A, qf, Ks, live0, live1, c, i0, j0, wave, lane_, rk, drop.thr16, kend, Pn, lbt);
         }
     }
     if (qi >= N) return;
