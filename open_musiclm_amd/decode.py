@@ -388,7 +388,9 @@ class SamplingLoop:
     [P] device arrays and stores the pointers beside the argument blocks it builds once per phase, so a captured cycle stays valid; the
     sampler calls are then omlm_sample_rows and a per-row ``guidance`` is combined by omlm_guide_logits_rows (every row beside its twin,
     the rows of scale 1 included).  With per-row seeds every row draws with stream sample index 0 -- u(t, 0, c) of its own seed, what a
-    one-sample loop with that seed draws -- and ``rng[1]`` is not read.  With scalars the blocks and the calls are what they always were."""
+    one-sample loop with that seed draws -- and ``rng[1]`` is not read.
+    Which sampler and guidance entries the cycle calls follows from the settings alone (ops.sampler_call, ops.guide_call) and is resolved
+    once, here: ``_cycle`` makes the calls it finds."""
 
     def __init__(self, dec: CachedDecoder, first_logits: torch.Tensor, uniforms: Optional[torch.Tensor], n0: int, n_new: int, topk: int,
                  temperature: float, forbid_by_phase: Sequence[bool], use_graph: bool = True, rng=None, top_p=None,
@@ -409,12 +411,10 @@ class SamplingLoop:
         dev = dec.logits.device
         if rng is None:
             assert uniforms.shape == (n_new, P, dec.V1) and uniforms.dtype == torch.float32 and uniforms.is_contiguous()
-            self.U = uniforms
-        else:
-            # counter stream (include/omlm.h): sample b of this decoder draws u(step, row0 + b, c) from the seed -- no buffer; seed halves
-            # and row0 are plain arguments, so a captured cycle holds for the whole call
-            self.U = None
-            self.seed, self.row0 = ((0, 0), 0) if isinstance(seeds, list) else (ops.split_seed(seeds), int(rng[1]))
+        self.U = uniforms
+        # counter stream (include/omlm.h): sample b of this decoder draws u(step, row0 + b, c) from the seed -- no buffer; seed halves
+        # and row0 are plain arguments, so a captured cycle holds for the whole call.  Zeros where they are not read (a buffer; row seeds)
+        self.seed, self.row0 = ((0, 0), 0) if rng is None or isinstance(seeds, list) else (ops.split_seed(seeds), int(rng[1]))
         self.hist = torch.zeros(n_new, P, device=dev, dtype=torch.long)
         self.cur = torch.zeros(dec.B, device=dev, dtype=torch.long)             # guided: the sampler writes [0, P), the twin copy [P, 2P)
         self.step_dev = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -424,28 +424,25 @@ class SamplingLoop:
         # guided: the sampler reads the combined rows from here, dec.logits keeps both branches
         self.guided = torch.zeros(P, dec.ldV, device=dev, dtype=torch.float32) if self.guidance is not None else None
         src = dec.logits if self.guidance is None else self.guided
-        # per-row settings: uploaded once, [P] each; the block's scalar of an uploaded array is not read (a valid placeholder)
-        as_rows = lambda v, member: ops.row_tensor(v if isinstance(v, list) else None, member, dev)
-        self.row_k, self.row_temperature, self.row_top_p = as_rows(topk, "k"), as_rows(temperature, "temperature"), as_rows(self.top_p, "top_p")
-        self.row_seed = as_rows(seeds, "seed")
-        self.row_sample = torch.zeros(P, device=dev, dtype=torch.int32) if self.row_seed is not None else None
-        self.row_guidance = as_rows(self.guidance, "scale")
-        self._rows = ops.sample_row_params(P, k=self.row_k, temperature=self.row_temperature, top_p=self.row_top_p, seed=self.row_seed,
-                                           sample=self.row_sample)              # None: the calls the loop has always made
-        scalar = lambda v, placeholder: placeholder if isinstance(v, list) else v
+        # per-row settings: uploaded once, [P] each, and kept here beside the row block that points at them (None: no list was given)
+        up = self._upload = ops.SamplerSettings(P, topk, self.temperature, self.top_p, self.guidance, seeds, self.logprobs).upload(dev)
+        self._rows = up.block()
         # the sampler's argument blocks (ops.SampleArgs), built once: per quantizer phase, without and with the embedding gather of the
         # sampled id.  Every pointer in them is a fixed buffer of this loop or its decoder.
-        seed, row0 = ((0, 0), 0) if rng is None else (self.seed, self.row0)
 
         def block(phase: int, embed: bool):
-            sa = ops.SampleArgs(ptr(src), P, dec.V1, dec.ldV, ptr(self.U), *seed, 0, row0, ptr(self.step_dev), ptr(self.cur),
-                                ptr(self.hist), scalar(self.topk, 1), scalar(self.temperature, 1.0), scalar(self.top_p, 1.0),
-                                int(self.forbid[phase]))
+            sa = ops.SampleArgs(ptr(src), P, dec.V1, dec.ldV, ptr(self.U), *self.seed, 0, self.row0, ptr(self.step_dev), ptr(self.cur),
+                                ptr(self.hist), up.k, up.temperature, up.top_p, int(self.forbid[phase]))
             if embed:
                 sa.emb_table, sa.emb_row_offset, sa.emb_rows = dec.emb.data_ptr(), dec.codebook * phase if dec.Q > 1 else 0, dec.emb.shape[0]
                 sa.x, sa.D = ptr(dec.x), dec.D
             return sa
         self._blocks = [(block(phase, False), block(phase, True)) for phase in range(dec.Q)]
+        # which entry points the cycle calls, with their arguments in front of the stream: resolved here, once (ops.sampler_call /
+        # ops.guide_call); g = null + s (cond - null) goes from the two halves of dec.logits into the sampler's rows
+        self._sample_calls = [tuple(ops.sampler_call(sa, self._rows, self.lp_model, self.lp_sampled) for sa in pair) for pair in self._blocks]
+        self._guide_call = None if self.guidance is None else ops.guide_call(ptr(dec.logits), dec.logits[P:].data_ptr(), ptr(self.guided), P,
+                                                                             dec.V1, dec.ldV, up.guidance)
         dec.logits.copy_(first_logits)
         self.use_graph = use_graph
         self.graphs = {}
@@ -453,24 +450,15 @@ class SamplingLoop:
     def _cycle(self, k: int, with_decode: bool):
         """Sample id number k (global index in the predicted sequence) from dec.logits, then compute its row."""
         dec, a = self.dec, self.dec.args
-        phase = k % dec.Q
         # with_decode, 32 launches per id: the sampler also gathers the embedding row of the id it picked (the step's first launch), and
         # the head kernel (the step's last) moves the row index and the sampler's step counter on
-        sa = self._blocks[phase][with_decode]
-        P = self.P
-        if self.row_guidance is not None:  # the same with the scale of every row
-            call("omlm_guide_logits_rows", ptr(dec.logits), dec.logits[P:].data_ptr(), ptr(self.guided), P, dec.V1, dec.ldV,
-                 ptr(self.row_guidance), stream_ptr())
-        elif self.guidance is not None:    # g = null + s (cond - null) from the two halves of dec.logits, into the sampler's rows
-            call("omlm_guide_logits", ptr(dec.logits), dec.logits[P:].data_ptr(), ptr(self.guided), P, dec.V1, dec.ldV, self.guidance, stream_ptr())
-        if self._rows is not None:
-            call("omlm_sample_rows", C.addressof(sa), C.addressof(self._rows), ptr(self.lp_model), ptr(self.lp_sampled), stream_ptr())
-        elif self.logprobs:
-            call("omlm_sample_lp", C.addressof(sa), ptr(self.lp_model), ptr(self.lp_sampled), stream_ptr())
-        else:
-            call("omlm_sample", C.addressof(sa), stream_ptr())
+        if self._guide_call is not None:
+            call(self._guide_call[0], *self._guide_call[1], stream_ptr())
+        name, args = self._sample_calls[k % dec.Q][with_decode]
+        call(name, *args, stream_ptr())
         if not with_decode:
             return
+        P = self.P
         if self.guidance is not None:      # the null twins decode the same ids: ids and gathered embedding rows to rows [P, 2P)
             call("omlm_decode_twin", ptr(self.cur), self.cur[P:].data_ptr(), ptr(dec.x), dec.x[P:].data_ptr(), P, dec.D, stream_ptr())
         if dec.pos_emb is not None:

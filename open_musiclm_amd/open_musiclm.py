@@ -34,6 +34,7 @@ class TokenSequenceInfo():
 # Test hook: callable (n_draws, batch, V + 1) -> [n_draws, batch, V + 1] uniforms consumed by `generate` in place of the device
 # RNG when no `uniforms` argument is given (the golden test of MusicLM.forward replays the reference's draws through it).
 UNIFORM_SOURCE = None
+_DEVICE_RNG = object()            # generate(): the uniforms of a call that are drawn from torch's generator on the device
 
 
 def _flat(t: torch.Tensor) -> torch.Tensor:
@@ -265,25 +266,25 @@ class TokenConditionedTransformerWrapper(nn.Module):
         With a number the stream index stays the global sample index."""
         # rows of the call, as the checks below need them (no conditioning sequence: a model the checks further down refuse or serve as before)
         batch = conditioning_token_ids[0].shape[0] if len(conditioning_token_ids) else (pred_token_ids.shape[0] if exists(pred_token_ids) else 0)
-        cond_scale = ops.per_row_cond_scale(cond_scale, batch)                  # before any device work; None = off
-        if cond_scale is not None:
-            _require_condition(self.token_sequences, "cond_scale")
-        assert len(conditioning_token_ids) == len(self.token_sequences) - 1
-        ops.check_sampler_width(self.token_sequences[-1].codebook_size + 1)      # before any device work
-        top_p = ops.per_row_top_p(top_p, batch)                                 # likewise; 1.0 = off
-        temperature = ops.per_row_temperature(temperature, batch)               # likewise (a number: as it is)
-        filter_thres = ops.per_row_filter_thres(filter_thres, batch)
-        sampler_seed = ops.per_row_seed(sampler_seed, batch)
-        if isinstance(sampler_seed, list):
+        pred_info, pred_eos_id = self.token_sequences[-1], self.eos_ids[-1]
+        V1, Q = pred_info.codebook_size + 1, pred_info.num_quantizers
+
+        def model_checks(guidance):
+            if guidance is not None:
+                _require_condition(self.token_sequences, "cond_scale")
+            assert len(conditioning_token_ids) == len(self.token_sequences) - 1
+            ops.check_sampler_width(V1)
+        # every sampling argument, checked before any device work
+        s = ops.SamplerSettings.checked(batch, V1, temperature=temperature, filter_thres=filter_thres, top_p=top_p, cond_scale=cond_scale,
+                                        sampler_seed=sampler_seed, logprobs=return_logprobs, after_guidance=model_checks)
+        if isinstance(s.seed, list):
             decode.sampler_rng_choice(sampler_rng, 0, batch, 1, False)          # an unknown sampler_rng is refused as in every call
             if sampler_rng == "buffer" or exists(uniforms):
                 raise ValueError("a per-row sampler_seed seeds the counter stream: it cannot be combined with sampler_rng='buffer' or "
                                  "injected uniforms (sampler_rng=None or 'counter', uniforms=None)")
             sampler_rng = "counter"
         decode.kv_cache_choice(kv_cache, self.transformer._precision())         # likewise: a ValueError names the accepted values
-        kv_kw = {} if kv_cache is None else dict(kv_cache=kv_cache)             # (None: the decoders are built as they always were)
         batch, device = conditioning_token_ids[0].shape[0], self.device
-        cond = [t.to(device) for t in conditioning_token_ids]
         if exists(pred_token_ids):
             assert pred_token_ids.shape[0] == batch
             first_step = pred_token_ids.shape[1]
@@ -291,126 +292,126 @@ class TokenConditionedTransformerWrapper(nn.Module):
         else:
             first_step = 0
             sampled = torch.empty((batch, 0), device=device, dtype=torch.long)
-        pred_info, pred_eos_id = self.token_sequences[-1], self.eos_ids[-1]
-
-        for i, info in enumerate(self.token_sequences[:-1]):
-            if info.unique_consecutive:
-                cond[i] = batch_unique_consecutive(cond[i], pad_value=self.pad_id)
+        cond, twin = self._condition_rows(conditioning_token_ids, append_eos_to_conditioning_tokens, s.guidance is not None)
         if pred_info.unique_consecutive:
             sampled = batch_unique_consecutive(sampled, pad_value=self.pad_id)
-        n_cond_ids = _flat(cond[0]).shape[-1] if cond_scale is not None else 0      # id positions of the condition (before its eos)
-        if append_eos_to_conditioning_tokens:
-            cond = [append_eos_id(_flat(t).long(), e) for t, e in zip(cond, self.eos_ids)]
-        if cond_scale is not None:          # rows [0, P) the prompts, rows [P, 2P) their null twins: only the condition differs
-            cond = [_flat(t).long() for t in cond]
-            twin = [null_twin(cond[0], self.token_sequences[0], n_cond_ids)] + cond[1:]
-            guide_kw = dict(guidance=cond_scale)
-        else:
-            guide_kw = {}                                                       # (off: the loops are built as they always were)
 
-        V1 = pred_info.codebook_size + 1
-        k = ops.topk_count(filter_thres, V1)
-        Q = pred_info.num_quantizers
-        step = 0
-        nxt = torch.empty(batch, device=device, dtype=torch.long)
         n_new = max(max_time_steps - first_step, 0) * Q
         prompt_rows = sum(t.shape[-1] + 1 for t in cond) + 1 + sampled.shape[-1]
         counter = decode.sampler_rng_choice(sampler_rng, n_new, batch, V1, exists(uniforms) or UNIFORM_SOURCE is not None) == "counter"
-        if counter and sampler_seed is None and n_new > 0:
-            sampler_seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), device=device, dtype=torch.long)) & 0xFFFFFFFFFFFFFFFF
+        if counter and s.seed is None and n_new > 0:
+            s = s._replace(seed=int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), device=device, dtype=torch.long)) & 0xFFFFFFFFFFFFFFFF)
+        # where the uniforms come from, for either route: None -- the counter stream, formed in the sampler kernel; a tensor
+        # [n_new, B, V1] -- injected, or UNIFORM_SOURCE's; _DEVICE_RNG -- the route draws them from torch's generator on the device
+        if counter:
+            U = None
+        elif exists(uniforms):
+            U = uniforms
+        elif UNIFORM_SOURCE is not None and n_new > 0:
+            U = UNIFORM_SOURCE(n_new, batch, V1)
+        else:
+            U = _DEVICE_RNG
         use_cache = kwargs.pop('use_cache', True) and decode.supports(self.transformer, 1, prompt_rows=prompt_rows) and n_new > 0
-        if use_cache and cond_scale is not None:       # a pair is two rows of a decode call; where no call holds two, the re-forward route
+        if use_cache and s.guidance is not None:       # a pair is two rows of a decode call; where no call holds two, the re-forward route
             use_cache = decode.supports(self.transformer, 2, self.transformer._precision(), prompt_rows=prompt_rows, wide=True)
         if use_cache:
-            # KV-cached decode (decode.py): one new row per sampled id instead of the reference's full re-forward.
-            # Ids are sampled straight into a [steps, B] buffer that the next decode step reads: no per-step cat / copies.
-            rows = prompt_rows + n_new
-            n0 = sampled.shape[-1]
-            if counter:
-                U = None
-            elif exists(uniforms):
-                U = uniforms[:n_new].to(device).float().contiguous()
-            elif UNIFORM_SOURCE is not None:
-                U = UNIFORM_SOURCE(n_new, batch, V1).to(device).float().contiguous()
-            else:
-                U = torch.rand(n_new, batch, V1, device=device)
-            forbid = [(not allow_eos_in_output) or (ind != Q - 1) for ind in range(Q)]
-            use_graph = kwargs.pop('use_graph', False)
-            # a decode call holds up to decode.max_call_batch samples (64 on the matrix-core step kernels, which carry four groups of 16
-            # through every launch): larger batches run as consecutive calls (samples are independent; every call streams the weights
-            # once per id)
-            pieces, lp_pieces = [], []
-            lp_kw = dict(logprobs=True) if return_logprobs else {}      # (False: the loops are built as they always were)
-            group = decode.max_call_batch(self.transformer, self.transformer._precision())
-            if cond_scale is not None:
-                group //= 2                                                     # pairs per call
-            for b0 in range(0, batch, group):
-                b1 = min(batch, b0 + group)
-                cut = lambda v: v[b0:b1] if isinstance(v, list) else v      # a call's rows of a per-row setting
-                if isinstance(cond_scale, list):
-                    guide_kw = dict(guidance=cut(cond_scale))
-                if cond_scale is not None:
-                    dec = decode.CachedDecoder(self.transformer, 2 * (b1 - b0), rows, self.transformer._precision(), wide=True, **kv_kw)
-                    last = dec.prefill([torch.cat((c[b0:b1], t[b0:b1]), dim=0) for c, t in zip(cond, twin)] +
-                                       [torch.cat((sampled[b0:b1], sampled[b0:b1]), dim=0)])
-                else:
-                    dec = decode.CachedDecoder(self.transformer, b1 - b0, rows, self.transformer._precision(), wide=True, **kv_kw)
-                    last = dec.prefill([t[b0:b1] for t in cond] + [sampled[b0:b1]])
-                if counter:            # sample b draws u(step, b, c) whichever piece it rides in
-                    loop = decode.SamplingLoop(dec, last, None, n0, n_new, cut(k), cut(temperature), forbid, use_graph=use_graph,
-                                               rng=(cut(sampler_seed), b0), top_p=cut(top_p), **lp_kw, **guide_kw)
-                else:
-                    loop = decode.SamplingLoop(dec, last, U[:, b0:b1].contiguous(), n0, n_new, cut(k), cut(temperature), forbid,
-                                               use_graph=use_graph, top_p=cut(top_p), **lp_kw, **guide_kw)
-                pieces.append(loop.run().t())                      # [b, n_new]
-                if return_logprobs:
-                    lp_pieces.append((loop.lp_model.t(), loop.lp_sampled.t()))
-            sampled = torch.cat((sampled, torch.cat(pieces, dim=0)), dim=-1)
-            if return_logprobs:
-                lp_model, lp_sampled = (torch.cat(ps, dim=0) for ps in zip(*lp_pieces))
+            new, lps = self._generate_cached(cond, twin, sampled, s, U, n_new, prompt_rows + n_new, allow_eos_in_output,
+                                             kwargs.pop('use_graph', False), {} if kv_cache is None else dict(kv_cache=kv_cache))
         else:
-            if not exists(uniforms) and UNIFORM_SOURCE is not None and n_new > 0:
-                uniforms = UNIFORM_SOURCE(n_new, batch, V1)
-            if return_logprobs:                                     # [ids, B]: row `step` is written by the launch that samples id `step`
-                lp_model, lp_sampled = (torch.zeros(n_new, batch, device=device) for _ in range(2))
-            if cond_scale is not None:
-                cond2 = [torch.cat((c, t), dim=0) for c, t in zip(cond, twin)]
-            # per-row settings: [B] device arrays, uploaded once (None for a number: the calls below are then what they always were)
-            as_rows = lambda v, member: ops.row_tensor(v if isinstance(v, list) else None, member, device)
-            rows_kw = dict(row_k=as_rows(k, "k"), row_temperature=as_rows(temperature, "temperature"), row_top_p=as_rows(top_p, "top_p"))
-            rows_kw = {n: t for n, t in rows_kw.items() if t is not None}
-            row_scale = as_rows(cond_scale, "scale")
-            if isinstance(sampler_seed, list):      # every row: u(t, 0, c) of its own seed
-                rows_kw.update(row_seed=as_rows(sampler_seed, "seed"), row_sample=torch.zeros(batch, device=device, dtype=torch.int32))
-            scalar = lambda v: None if isinstance(v, list) else v
-            for _t in tqdm(range(first_step, max_time_steps), desc='generating predicted tokens'):
-                for ind in range(Q):
-                    if cond_scale is not None:      # one 2B forward, then the combine in place over the conditional half
-                        both = self.transformer.last_logits(cond2 + [torch.cat((sampled, sampled), dim=0)])
-                        last = both[:batch]
-                        ops.guide_logits(last, both[batch:], last, V1, cond_scale if row_scale is None else row_scale)
-                    else:
-                        last = self.transformer.last_logits(cond + [sampled])
-                    forbid = (not allow_eos_in_output) or (ind != Q - 1)
-                    if counter:
-                        src = dict(seed=scalar(sampler_seed), step=step)
-                    elif exists(uniforms):
-                        src = dict(uniform=uniforms[step].to(device).float().contiguous())
-                    else:
-                        src = dict(uniform=torch.empty(batch, V1, device=device).uniform_(0, 1))
-                    lp = dict(lp_model=lp_model[step], lp_sampled=lp_sampled[step]) if return_logprobs else {}
-                    ops.sample(last, nxt, V1, scalar(k), scalar(temperature), forbid, top_p=scalar(top_p), **src, **lp, **rows_kw)
-                    sampled = torch.cat((sampled, nxt[:, None]), dim=-1)
-                    step += 1
-            if return_logprobs:
-                lp_model, lp_sampled = lp_model.t(), lp_sampled.t()      # [B, ids]
+            new, lps = self._generate_reforward(cond, twin, sampled, s, U, n_new, allow_eos_in_output)
+        sampled = torch.cat((sampled, new), dim=-1)
         if return_logprobs:
-            lps = LogProbs(*(zero_logprobs_after_eos(v, sampled, pred_eos_id, include_eos_in_output).reshape(batch, -1, Q)
-                             for v in (lp_model, lp_sampled)))
+            lps = LogProbs(*(zero_logprobs_after_eos(v, sampled, pred_eos_id, include_eos_in_output).reshape(batch, -1, Q) for v in lps))
         sampled = mask_out_after_eos_id(sampled, pred_eos_id, keep_eos=include_eos_in_output)
         if return_logprobs:
             return sampled.reshape(batch, -1, Q), lps
         return sampled.reshape(batch, -1, Q)
+
+    def _condition_rows(self, conditioning_token_ids, append_eos: bool, guided: bool):
+        """The conditioning sequences as generate() and score() feed them -> (cond, twin): on the device, unique_consecutive where the
+        sequence asks for it, the eos appended (``append_eos``).  ``guided``: flattened, and ``twin`` is the same list with the null twin
+        (null_twin) in place of the condition -- only the condition differs between a prompt and its twin; otherwise ``twin`` is None."""
+        cond = [t.to(self.device) for t in conditioning_token_ids]
+        for i, info in enumerate(self.token_sequences[:-1]):
+            if info.unique_consecutive:
+                cond[i] = batch_unique_consecutive(cond[i], pad_value=self.pad_id)
+        n_cond_ids = _flat(cond[0]).shape[-1] if guided else 0      # id positions of the condition (before its eos)
+        if append_eos:
+            cond = [append_eos_id(_flat(t).long(), e) for t, e in zip(cond, self.eos_ids)]
+        if not guided:
+            return cond, None
+        cond = [_flat(t).long() for t in cond]
+        return cond, [null_twin(cond[0], self.token_sequences[0], n_cond_ids)] + cond[1:]
+
+    def _generate_cached(self, cond, twin, sampled, s, U, n_new, rows, allow_eos, use_graph, kv_kw):
+        """generate()'s KV-cached route (decode.py): one new row per sampled id instead of the reference's full re-forward; the ids are
+        sampled straight into a [steps, B] buffer that the next decode step reads.  -> (the new ids [B, n_new], the two log-probability
+        planes [B, n_new] or None).  A decode call holds up to decode.max_call_batch samples (64 on the matrix-core step kernels, which
+        carry four groups of 16 through every launch) -- guided: half as many pairs, rows [0, P) the prompts and rows [P, 2P) their null
+        twins -- and larger batches run as consecutive calls: samples are independent, and every call streams the weights once per id.
+        Arguments as generate() prepared them: ``cond`` / ``twin`` (_condition_rows), ``sampled`` (the given ids, [B, n0]), ``s`` (the
+        call's ops.SamplerSettings), ``U`` (the source of uniforms), ``rows`` (prompt rows + n_new: what a decoder must hold)."""
+        batch, device, precision = sampled.shape[0], self.device, self.transformer._precision()
+        Q, n0, guided = self.token_sequences[-1].num_quantizers, sampled.shape[-1], twin is not None
+        if U is _DEVICE_RNG:
+            U = torch.rand(n_new, batch, self.token_sequences[-1].codebook_size + 1, device=device)
+        elif U is not None:
+            U = U[:n_new].to(device).float().contiguous()
+        forbid = [(not allow_eos) or (ind != Q - 1) for ind in range(Q)]
+        group = decode.max_call_batch(self.transformer, precision) // (2 if guided else 1)
+        pieces, lp_pieces = [], []
+        for b0 in range(0, batch, group):
+            b1 = min(batch, b0 + group)
+            c = s.cut(b0, b1)
+            prompt = [t[b0:b1] for t in cond] + [sampled[b0:b1]]
+            if guided:
+                prompt = [torch.cat((t, n[b0:b1]), dim=0) for t, n in zip(prompt, twin + [sampled])]
+            dec = decode.CachedDecoder(self.transformer, (2 if guided else 1) * (b1 - b0), rows, precision, wide=True, **kv_kw)
+            last = dec.prefill(prompt)
+            # a keyword at its default is not passed.  Counter stream: sample b draws u(step, b, c) whichever piece it rides in
+            loop_kw = dict(rng=(c.seed, b0)) if U is None else {}
+            if s.logprobs:
+                loop_kw.update(logprobs=True)
+            if guided:
+                loop_kw.update(guidance=c.guidance)
+            loop = decode.SamplingLoop(dec, last, None if U is None else U[:, b0:b1].contiguous(), n0, n_new, c.k, c.temperature, forbid,
+                                       use_graph=use_graph, top_p=c.top_p, **loop_kw)
+            pieces.append(loop.run().t())                      # [b, n_new]
+            if s.logprobs:
+                lp_pieces.append((loop.lp_model.t(), loop.lp_sampled.t()))
+        return torch.cat(pieces, dim=0), tuple(torch.cat(ps, dim=0) for ps in zip(*lp_pieces)) if s.logprobs else None
+
+    def _generate_reforward(self, cond, twin, sampled, s, U, n_new, allow_eos):
+        """generate()'s re-forward route: every id re-runs the full causal forward over the grown sequence like the reference, one sampler
+        call per id.  -> (the new ids [B, n_new], the two log-probability planes [B, n_new] or None).  Guided: one forward over 2B rows
+        (the prompts, then their null twins), then the combine in place over the conditional half.  Arguments as for _generate_cached;
+        per-row settings are uploaded once, here."""
+        batch, n0, device = sampled.shape[0], sampled.shape[-1], self.device
+        Q, V1 = self.token_sequences[-1].num_quantizers, self.token_sequences[-1].codebook_size + 1
+        nxt = torch.empty(batch, device=device, dtype=torch.long)
+        # [ids, B]: row `step` is written by the launch that samples id `step`
+        lps = tuple(torch.zeros(n_new, batch, device=device) for _ in range(2)) if s.logprobs else None
+        if twin is not None:
+            cond2 = [torch.cat((c, t), dim=0) for c, t in zip(cond, twin)]
+        up = s.upload(device)
+        rows_kw = {f"row_{m}": t for m, t in up.tensors.items() if t is not None}
+        for step in (t * Q + ind for t in tqdm(range(n_new // Q), desc='generating predicted tokens') for ind in range(Q)):
+            if twin is not None:
+                both = self.transformer.last_logits(cond2 + [torch.cat((sampled, sampled), dim=0)])
+                last = both[:batch]
+                ops.guide_logits(last, both[batch:], last, V1, up.guidance)
+            else:
+                last = self.transformer.last_logits(cond + [sampled])
+            if U is None:
+                src = dict(seed=up.seed, step=step)
+            elif U is _DEVICE_RNG:
+                src = dict(uniform=torch.empty(batch, V1, device=device).uniform_(0, 1))
+            else:
+                src = dict(uniform=U[step].to(device).float().contiguous())
+            lp = dict(lp_model=lps[0][step], lp_sampled=lps[1][step]) if s.logprobs else {}
+            ops.sample(last, nxt, V1, up.k, up.temperature, (not allow_eos) or (step % Q != Q - 1), top_p=up.top_p, **src, **lp, **rows_kw)
+            sampled = torch.cat((sampled, nxt[:, None]), dim=-1)
+        return sampled[:, n0:], tuple(v.t() for v in lps) if s.logprobs else None
 
     @eval_decorator
     @torch.no_grad()
@@ -440,17 +441,10 @@ class TokenConditionedTransformerWrapper(nn.Module):
                              f"[{int(pred.min())}, {int(pred.max())}]")
         if L == 0:
             return torch.zeros(batch, 0, Q, device=device)
-        cond = [t.to(device) for t in conditioning_token_ids]
-        for i, info in enumerate(self.token_sequences[:-1]):
-            if info.unique_consecutive:
-                cond[i] = batch_unique_consecutive(cond[i], pad_value=self.pad_id)
-        n_cond_ids = _flat(cond[0]).shape[-1] if cond_scale is not None else 0
-        if append_eos_to_conditioning_tokens:
-            cond = [append_eos_id(_flat(t).long(), e) for t, e in zip(cond, self.eos_ids)]
+        cond, twin = self._condition_rows(conditioning_token_ids, append_eos_to_conditioning_tokens, cond_scale is not None)
         rows_pred = pred
         if cond_scale is not None:          # rows [0, B) the prompts, rows [B, 2B) their null twins
-            cond = [_flat(t).long() for t in cond]
-            cond = [torch.cat((cond[0], null_twin(cond[0], self.token_sequences[0], n_cond_ids)), dim=0)] + [torch.cat((t, t), dim=0) for t in cond[1:]]
+            cond = [torch.cat((c, t), dim=0) for c, t in zip(cond, twin)]
             rows_pred = torch.cat((pred, pred), dim=0)
         # row j of the predicted sequence (its start token, then the ids) holds the logits after pred[:, :j]: rows 0 .. L - 1 score the L ids,
         # the last row (what would follow them) carries the ignore label
@@ -786,35 +780,30 @@ def _unstack_windows(stacked: torch.Tensor, n_windows: int) -> List[torch.Tensor
     return list(stacked.split(stacked.shape[0] // n_windows, dim=0))
 
 
-def stage_top_p(top_p):
-    """MusicLM.forward's ``top_p`` as (semantic, coarse, fine) values for the stages' generate(): None, a number for all three, or a
-    mapping with any of "semantic" / "coarse" / "fine".  Every value is checked (ops.check_top_p); a ValueError names what is wrong."""
+def _per_stage(value, check, name):
+    """(semantic, coarse, fine) values of a MusicLM.forward argument `name` for the stages' generate(): None, a number for all three, or a
+    mapping with any of "semantic" / "coarse" / "fine".  Every value goes through check(value, name); a ValueError names what is wrong."""
     stages = ("semantic", "coarse", "fine")
-    if isinstance(top_p, Mapping):
-        unknown = sorted(set(top_p) - set(stages), key=str)
+    if isinstance(value, Mapping):
+        unknown = sorted(set(value) - set(stages), key=str)
         if unknown:
-            raise ValueError(f"top_p: unknown stage(s) {unknown}; a mapping takes any of {list(stages)}")
-        for name in stages:
-            ops.check_top_p(top_p.get(name), f"top_p[{name!r}]")
-        return tuple(top_p.get(name) for name in stages)
-    ops.check_top_p(top_p)
-    return (top_p,) * 3
+            raise ValueError(f"{name}: unknown stage(s) {unknown}; a mapping takes any of {list(stages)}")
+        for stage in stages:
+            check(value.get(stage), f"{name}[{stage!r}]")
+        return tuple(value.get(stage) for stage in stages)
+    check(value, name)
+    return (value,) * 3
+
+
+def stage_top_p(top_p):
+    """MusicLM.forward's ``top_p`` per stage (_per_stage), every value checked by ops.check_top_p."""
+    return _per_stage(top_p, ops.check_top_p, "top_p")
 
 
 def stage_cond_scale(cond_scale):
-    """MusicLM.forward's ``cond_scale`` as (semantic, coarse, fine) values for the stages' generate(): None, a number for all three, or a
-    mapping with any of "semantic" / "coarse" / "fine" (a stage that is not named decodes unguided).  Every value is checked
-    (ops.check_cond_scale); a ValueError names what is wrong."""
-    stages = ("semantic", "coarse", "fine")
-    if isinstance(cond_scale, Mapping):
-        unknown = sorted(set(cond_scale) - set(stages), key=str)
-        if unknown:
-            raise ValueError(f"cond_scale: unknown stage(s) {unknown}; a mapping takes any of {list(stages)}")
-        for name in stages:
-            ops.check_cond_scale(cond_scale.get(name), f"cond_scale[{name!r}]")
-        return tuple(cond_scale.get(name) for name in stages)
-    ops.check_cond_scale(cond_scale)
-    return (cond_scale,) * 3
+    """MusicLM.forward's ``cond_scale`` per stage (_per_stage; a stage that is not named decodes unguided), every value checked by
+    ops.check_cond_scale."""
+    return _per_stage(cond_scale, ops.check_cond_scale, "cond_scale")
 
 
 class MusicLM(nn.Module):
@@ -869,11 +858,12 @@ class MusicLM(nn.Module):
                 coarse_sliding_window_step_percent=0.5, fine_sliding_window_step_percent=1,
                 clap_token_ids=None, return_tokens=False, fine_windows_together=False, sampler_rng=None, top_p=None, kv_cache=None,
                 cond_scale=None):
-        p_sem, p_coarse, p_fine = stage_top_p(top_p)                               # refused by name before any work
-        s_sem, s_coarse, s_fine = ({} if s is None else dict(cond_scale=s) for s in stage_cond_scale(cond_scale))      # likewise; None:
-        #                                                                            the stage is called as it always was
+        top_ps, scales = stage_top_p(top_p), stage_cond_scale(cond_scale)          # refused by name before any work
         decode.check_kv_cache(kv_cache)                                            # likewise
-        kv_kw = {} if kv_cache is None else dict(kv_cache=kv_cache)                # (None: every stage is called as it always was)
+        # the sampling keywords of each stage's generate(); kv_cache and cond_scale only when given (a keyword at its default is not passed)
+        kv_kw = {} if kv_cache is None else dict(kv_cache=kv_cache)
+        kw_sem, kw_coarse, kw_fine = (dict(sampler_rng=sampler_rng, top_p=p, **kv_kw, **({} if g is None else dict(cond_scale=g)))
+                                      for p, g in zip(top_ps, scales))
         if not exists(clap_token_ids):
             assert exists(text), 'text needs to be passed in if one of the transformer requires conditioning'
             clap_token_ids = get_or_compute_clap_token_ids(None, self.clap, conditioning_audio=None, conditioning_text=text)
@@ -907,14 +897,12 @@ class MusicLM(nn.Module):
         # ---- semantic stage (:930-952): one window, then 50%-overlap continuation windows ----
         sem = self.semantic.generate(clap_token_ids=clap_token_ids, semantic_token_ids=prime_sem,
                                      max_time_steps=int(min(output_seconds, semantic_window_seconds) * sem_hz),
-                                     include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng,
-                                     top_p=p_sem, **kv_kw, **s_sem)
+                                     include_eos_in_output=False, append_eos_to_conditioning_tokens=True, **kw_sem)
         while sem.shape[1] < int(output_seconds * sem_hz):
             keep = int(semantic_window_seconds * sem_hz * (1 - semantic_sliding_window_step_percent))
             nxt = self.semantic.generate(clap_token_ids=clap_token_ids, semantic_token_ids=sem[:, -keep:],
                                          max_time_steps=int(semantic_window_seconds * sem_hz),
-                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True, sampler_rng=sampler_rng,
-                                         top_p=p_sem, **kv_kw, **s_sem)
+                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True, **kw_sem)
             sem = torch.cat([sem, nxt[:, keep:]], dim=1)
         sem_all = sem
         sem = sem[:, sem_adjust:]
@@ -932,7 +920,7 @@ class MusicLM(nn.Module):
                                         coarse_token_ids=cond_coarse,
                                         max_time_steps=int(coarse_window_seconds * ac_hz), reconstruct_wave=False,
                                         include_eos_in_output=False, append_eos_to_conditioning_tokens=True,
-                                        temperature=0.95, sampler_rng=sampler_rng, top_p=p_coarse, **kv_kw, **s_coarse)
+                                        temperature=0.95, **kw_coarse)
             coarse = pred if not exists(coarse) else torch.cat([coarse, pred[:, keep:]], dim=1)
         if return_coarse_generated_wave:
             return self.neural_codec.decode_from_codebook_indices(coarse).squeeze(1)
@@ -948,7 +936,7 @@ class MusicLM(nn.Module):
             pred = self.fine.generate(clap_token_ids=clap_token_ids.repeat(len(coarse_wins), *([1] * (clap_token_ids.dim() - 1))),
                                       coarse_token_ids=_stack_windows(coarse_wins), fine_token_ids=None,
                                       max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
-                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine, **kv_kw, **s_fine)
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4, **kw_fine)
             fine = torch.cat(_unstack_windows(pred, len(coarse_wins)), dim=1)
             coarse_wins = []
         for coarse_win in coarse_wins:
@@ -959,7 +947,7 @@ class MusicLM(nn.Module):
                 keep, cond_fine = 0, prime_fine
             pred = self.fine.generate(clap_token_ids=clap_token_ids, coarse_token_ids=coarse_win, fine_token_ids=cond_fine,
                                       max_time_steps=fwin, reconstruct_wave=False, include_eos_in_output=False,
-                                      append_eos_to_conditioning_tokens=True, temperature=0.4, sampler_rng=sampler_rng, top_p=p_fine, **kv_kw, **s_fine)
+                                      append_eos_to_conditioning_tokens=True, temperature=0.4, **kw_fine)
             fine = pred if not exists(fine) else torch.cat([fine, pred[:, keep:]], dim=1)
         fine = fine[:, fine_adjust:]
         if exists(prime_coarse_all) and exists(prime_fine_all):

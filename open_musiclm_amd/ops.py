@@ -7,7 +7,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -708,10 +708,16 @@ def guide_logits(cond, null, out, V, scale):
             raise ValueError(f"guide_logits: {name} must be fp32 [{rows}, {ld}] with contiguous rows; got {t.dtype} {tuple(t.shape)} {t.stride()}")
     if not 0 < int(V) <= ld:
         raise ValueError(f"guide_logits: V must lie in [1, {ld}], not {V}")
-    if by_row:
-        call("omlm_guide_logits_rows", ptr(cond), ptr(null), ptr(out), rows, int(V), ld, ptr(scale), stream_ptr())
-        return
-    call("omlm_guide_logits", ptr(cond), ptr(null), ptr(out), rows, int(V), ld, 1.0 if s is None else s, stream_ptr())
+    name, args = guide_call(ptr(cond), ptr(null), ptr(out), rows, int(V), ld, scale if by_row else 1.0 if s is None else s)
+    call(name, *args, stream_ptr())
+
+
+def guide_call(cond, null, out, rows, V, ld, scale):
+    """The guidance entry for a scale, as (name, arguments in front of the stream): omlm_guide_logits for a number, omlm_guide_logits_rows
+    for a [rows] device tensor.  cond / null / out: device addresses.  Nothing is checked or launched here."""
+    if isinstance(scale, torch.Tensor):
+        return "omlm_guide_logits_rows", (cond, null, out, rows, V, ld, ptr(scale))
+    return "omlm_guide_logits", (cond, null, out, rows, V, ld, scale)
 
 
 def decode_twin(ids=None, ids_twin=None, x=None, x_twin=None):
@@ -1059,8 +1065,8 @@ def sample(logits, out, V, k, temperature, forbid_last, *, top_p=None, uniform=N
     ``row_k`` / ``row_temperature`` / ``row_top_p`` / ``row_seed`` / ``row_sample`` ([B] device tensors: int32 / fp32 / fp32 / the uint64
     seeds as int64 / int32; any subset): per-row values in place of ``k`` / ``temperature`` / ``top_p`` / ``seed`` / ``row0 + b`` -- the
     call is then omlm_sample_rows, and a scalar whose tensor is given is not read (pass None).  ``row_seed`` and ``row_sample`` belong
-    to the counter stream: ``row_seed`` stands for ``seed``, and either of them with ``uniform`` is refused.  Without them the call is
-    the one it has always been."""
+    to the counter stream: ``row_seed`` stands for ``seed``, and either of them with ``uniform`` is refused.  Which of the three entries
+    the call takes: sampler_call."""
     check_sampler_width(V)
     B, ld = logits.shape
     rows = sample_row_params(B, k=row_k, temperature=row_temperature, top_p=row_top_p, seed=row_seed, sample=row_sample)
@@ -1074,17 +1080,23 @@ def sample(logits, out, V, k, temperature, forbid_last, *, top_p=None, uniform=N
                    1 if row_k is not None else int(k), 1.0 if row_temperature is not None else float(temperature), p, int(forbid_last),
                    ptr(emb_table), int(emb_row_offset), 0 if emb_table is None else emb_table.shape[0], ptr(x),
                    0 if emb_table is None else emb_table.shape[1])
-    if lp_model is None and lp_sampled is None and rows is None:
-        call("omlm_sample", C.addressof(a), stream_ptr())
-        return
     for t, name in ((lp_model, "lp_model"), (lp_sampled, "lp_sampled")):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.shape[-1] != B):
             raise ValueError(f"sample: {name} must be a contiguous fp32 tensor [B] ([steps, B] with step_dev), B = {B}; got "
                              f"{t.dtype} {tuple(t.shape)}")
-    if rows is None:
-        call("omlm_sample_lp", C.addressof(a), ptr(lp_model), ptr(lp_sampled), stream_ptr())
-    else:
-        call("omlm_sample_rows", C.addressof(a), C.addressof(rows), ptr(lp_model), ptr(lp_sampled), stream_ptr())
+    name, args = sampler_call(a, rows, lp_model, lp_sampled)
+    call(name, *args, stream_ptr())
+
+
+def sampler_call(args: SampleArgs, rows: Optional[SampleRowParams], lp_model=None, lp_sampled=None):
+    """The sampler entry for a filled block, as (name, arguments in front of the stream): omlm_sample_rows with a row block,
+    omlm_sample_lp with a log-probability tensor and no row block, omlm_sample with neither.  The caller keeps `args`, `rows` and the
+    tensors alive for as long as it uses the result.  Nothing is checked or launched here."""
+    if rows is not None:
+        return "omlm_sample_rows", (C.addressof(args), C.addressof(rows), ptr(lp_model), ptr(lp_sampled))
+    if lp_model is not None or lp_sampled is not None:
+        return "omlm_sample_lp", (C.addressof(args), ptr(lp_model), ptr(lp_sampled))
+    return "omlm_sample", (C.addressof(args),)
 
 
 # ---- per-row sampling arguments: one pure-Python normaliser per argument of generate() / SamplingLoop -----------------------------
@@ -1183,6 +1195,66 @@ def row_tensor(values, member, device):
     if member == "seed":
         values = [v - (1 << 64) if v >= (1 << 63) else v for v in values]
     return torch.tensor(values, dtype=torch.float32 if member == "scale" else _ROW_DTYPES[member]).to(device)
+
+
+class SamplerUpload(NamedTuple):
+    """SamplerSettings.upload: what the launches of `rows` prompts take.  ``tensors``: member of omlm_sample_row_params -> its [rows]
+    device tensor or None; ``k`` / ``temperature`` / ``top_p``: the scalars of omlm_sample_args, a valid placeholder (1, 1.0, 1.0; not
+    read) where a tensor stands in; ``seed``: the one seed, None with a seed per row (or none at all); ``guidance``: the scale as a number,
+    a [rows] fp32 tensor, or None."""
+    rows: int
+    tensors: dict
+    k: object
+    temperature: object
+    top_p: object
+    seed: object
+    guidance: object
+
+    def block(self) -> Optional[SampleRowParams]:
+        """The row block over ``tensors`` (sample_row_params: None when there is none)."""
+        return sample_row_params(self.rows, **self.tensors)
+
+
+class SamplerSettings(NamedTuple):
+    """The checked sampling arguments of a call over `rows` prompts, host side: each of ``k`` (the top-k counts), ``temperature``,
+    ``top_p`` (1.0: no nucleus), ``guidance`` (None: off) and ``seed`` is a number or a list of `rows` numbers, as the per_row_*
+    functions return them."""
+    rows: int
+    k: object
+    temperature: object
+    top_p: object
+    guidance: object
+    seed: object
+    logprobs: bool = False
+
+    @classmethod
+    def checked(cls, rows, V1, *, temperature, filter_thres, top_p, cond_scale, sampler_seed, logprobs=False, after_guidance=None):
+        """From generate()'s raw arguments, for rows of V1 logits, in the order generate() has always checked them: the first thing wrong
+        raises its ValueError, which names the argument.  ``after_guidance(guidance)`` runs between the guidance check and the rest (what
+        the caller must refuse once it knows whether guidance is on).  Pure Python: before any device work."""
+        guidance = per_row_cond_scale(cond_scale, rows)
+        if after_guidance is not None:
+            after_guidance(guidance)
+        top_p = per_row_top_p(top_p, rows)
+        temperature = per_row_temperature(temperature, rows)
+        filter_thres = per_row_filter_thres(filter_thres, rows)
+        seed = per_row_seed(sampler_seed, rows)
+        return cls(rows, topk_count(filter_thres, V1), temperature, top_p, guidance, seed, bool(logprobs))
+
+    def cut(self, b0: int, b1: int) -> "SamplerSettings":
+        """The settings of rows [b0, b1): lists sliced, numbers kept."""
+        return self._replace(rows=b1 - b0, **{f: v[b0:b1] for f, v in self._asdict().items() if isinstance(v, list)})
+
+    def upload(self, device) -> SamplerUpload:
+        """The per-row lists as [rows] device tensors (row_tensor), uploaded once.  With a seed per row every row draws with stream sample
+        index 0 -- u(t, 0, c) of its own seed -- so ``sample`` is a zero array and the call's first global index is not read."""
+        per_row = {m: v if isinstance(v, list) else None
+                   for m, v in (("k", self.k), ("temperature", self.temperature), ("top_p", self.top_p), ("seed", self.seed))}
+        tensors = {m: row_tensor(v, m, device) for m, v in per_row.items()}
+        tensors["sample"] = None if tensors["seed"] is None else torch.zeros(self.rows, device=device, dtype=torch.int32)
+        scalar = lambda m, placeholder: getattr(self, m) if tensors[m] is None else placeholder  # noqa: E731
+        return SamplerUpload(self.rows, tensors, scalar("k", 1), scalar("temperature", 1.0), scalar("top_p", 1.0), scalar("seed", None),
+                             row_tensor(self.guidance, "scale", device) if isinstance(self.guidance, list) else self.guidance)
 
 
 def probe_tr16(out):

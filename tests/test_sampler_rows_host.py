@@ -146,6 +146,121 @@ def test_ops_sample_refuses_wrong_row_tensors_by_name():
     assert ops.row_tensor([0.5, 3], "scale", "cpu").dtype == torch.float32
 
 
+def test_settings_cut_slices_lists_and_keeps_scalars():
+    from open_musiclm_amd import ops
+    temps, scales, seeds = [0.5 + 0.1 * r for r in range(9)], [float(r) for r in range(9)], list(range(100, 109))
+    s = ops.SamplerSettings.checked(9, 41, temperature=temps, filter_thres=0.5, top_p=None, cond_scale=scales, sampler_seed=seeds, logprobs=True)
+    assert s == ops.SamplerSettings(9, 20, temps, 1.0, scales, seeds, True)
+    head, tail = s.cut(0, 8), s.cut(8, 9)
+    assert head == ops.SamplerSettings(8, 20, temps[:8], 1.0, scales[:8], seeds[:8], True)
+    assert tail == ops.SamplerSettings(1, 20, temps[8:], 1.0, scales[8:], seeds[8:], True)
+    assert s.temperature == temps and s.rows == 9                       # the whole is untouched
+    t = ops.SamplerSettings.checked(9, 41, temperature=0.8, filter_thres=[0.0] * 8 + [1.0], top_p=[0.7] * 9, cond_scale=3, sampler_seed=None)
+    assert t.cut(8, 9) == ops.SamplerSettings(1, [1], 0.8, [0.7], 3.0, None, False) and t.cut(0, 8).k == [41] * 8
+    with pytest.raises(AttributeError):
+        s.k = 1                                                         # immutable
+    # the checks run in generate()'s order, with the caller's own between the guidance and the rest
+    order = []
+    with pytest.raises(ValueError, match="top_p"):
+        ops.SamplerSettings.checked(2, 41, temperature=[0, 0], filter_thres=0.9, top_p=2, cond_scale=3, sampler_seed=None,
+                                    after_guidance=order.append)
+    assert order == [3.0]
+    with pytest.raises(ValueError, match="cond_scale"):
+        ops.SamplerSettings.checked(2, 41, temperature=1, filter_thres=0.9, top_p=2, cond_scale=-1, sampler_seed=None, after_guidance=order.append)
+    assert order == [3.0]
+
+
+@pytest.fixture
+def recorded_calls(monkeypatch):
+    """ops.call replaced by a recorder; no device: tensors count as resident and the stream is 0."""
+    from open_musiclm_amd import hip, ops
+    calls = []
+    monkeypatch.setattr(ops, "call", lambda name, *a: calls.append((name, a)))
+    monkeypatch.setattr(ops, "stream_ptr", lambda: 0)
+    monkeypatch.setattr(hip, "require_gpu", lambda t, what="tensor": None)
+    return calls
+
+
+def test_one_place_picks_the_sampler_entry(recorded_calls, monkeypatch):
+    from open_musiclm_amd import ops
+    B, V = 4, 8
+    lg, out, lpm, lps = torch.zeros(B, V), torch.zeros(B, dtype=torch.long), torch.zeros(B), torch.zeros(B)
+    arrays = dict(row_k=torch.ones(B, dtype=torch.int32), row_temperature=torch.ones(B), row_top_p=torch.ones(B),
+                  row_seed=torch.ones(B, dtype=torch.int64), row_sample=torch.zeros(B, dtype=torch.int32))
+    lp_forms = (dict(), dict(lp_model=lpm), dict(lp_sampled=lps), dict(lp_model=lpm, lp_sampled=lps))
+
+    blocks = []           # the row block as the call sees it (it lives as long as the call)
+
+    def snapshot(name, *a):
+        recorded_calls.append((name, a))
+        if name == "omlm_sample_rows":
+            block = ops.SampleRowParams.from_address(a[1])
+            blocks.append({n: getattr(block, n) for n, _ in block._fields_})
+    monkeypatch.setattr(ops, "call", snapshot)
+
+    def entry(**kw):
+        del recorded_calls[:]
+        ops.sample(lg, out, V, 2, 1.0, False, seed=1, **kw)
+        (name, args), = recorded_calls
+        return name, args
+    assert entry()[0] == "omlm_sample" and len(entry()[1]) == 2            # the block and the stream
+    for lp in lp_forms[1:]:
+        name, args = entry(**lp)
+        assert name == "omlm_sample_lp" and args[1:] == (ops.ptr(lp.get("lp_model")), ops.ptr(lp.get("lp_sampled")), 0)
+    for row, lp in ((r, lp) for r in arrays for lp in lp_forms):             # any one row array, with or without lp
+        name, args = entry(**{row: arrays[row]}, **lp)
+        assert name == "omlm_sample_rows" and args[2:] == (ops.ptr(lp.get("lp_model")), ops.ptr(lp.get("lp_sampled")), 0), (row, lp)
+        assert blocks[-1] == {n: arrays[row].data_ptr() if "row_" + n == row else None for n, _ in ops.SampleRowParams._fields_}
+    # the pure form SamplingLoop resolves once: the same table, the stream left to the caller
+    sa, rows = ops.SampleArgs(), ops.sample_row_params(B, k=arrays["row_k"], temperature=None, top_p=None, seed=None, sample=None)
+    assert ops.sampler_call(sa, None) == ("omlm_sample", (C.addressof(sa),))
+    assert ops.sampler_call(sa, None, lpm, None) == ("omlm_sample_lp", (C.addressof(sa), lpm.data_ptr(), None))
+    assert ops.sampler_call(sa, rows) == ("omlm_sample_rows", (C.addressof(sa), C.addressof(rows), None, None))
+    assert ops.sampler_call(sa, rows, lpm, lps) == ("omlm_sample_rows", (C.addressof(sa), C.addressof(rows), lpm.data_ptr(), lps.data_ptr()))
+
+
+def test_one_place_picks_the_guide_entry(recorded_calls):
+    from open_musiclm_amd import ops
+    cond, null = torch.zeros(3, 8), torch.ones(3, 8)
+    ptrs = (cond.data_ptr(), null.data_ptr(), cond.data_ptr(), 3, 5, 8)
+    for given, scale in ((2.5, 2.5), (None, 1.0), (1, 1.0), (0, 0.0)):       # a number: the scalar entry (off is scale 1)
+        del recorded_calls[:]
+        ops.guide_logits(cond, null, cond, 5, given)
+        assert recorded_calls == [("omlm_guide_logits", ptrs + (scale, 0))]
+    up = ops.SamplerSettings(3, 1, 1.0, 1.0, [0.0, 1.0, 2.5], None).upload("cpu")       # a list: the row entry
+    assert up.guidance.dtype == torch.float32 and up.guidance.tolist() == [0.0, 1.0, 2.5]
+    del recorded_calls[:]
+    ops.guide_logits(cond, null, cond, 5, up.guidance)
+    assert recorded_calls == [("omlm_guide_logits_rows", ptrs + (up.guidance.data_ptr(), 0))]
+    assert ops.guide_call(*ptrs, 2.5) == ("omlm_guide_logits", ptrs + (2.5,))
+    assert ops.guide_call(*ptrs, up.guidance) == ("omlm_guide_logits_rows", ptrs + (up.guidance.data_ptr(),))
+    assert ops.SamplerSettings(3, 1, 1.0, 1.0, 2.5, None).upload("cpu").guidance == 2.5
+    assert ops.SamplerSettings(3, 1, 1.0, 1.0, None, None).upload("cpu").guidance is None
+
+
+def test_upload_puts_placeholders_exactly_where_an_array_stands_in(recorded_calls):
+    from open_musiclm_amd import ops
+    given = dict(k=[1, 5, 9], temperature=[0.5, 1.0, 1.5], top_p=[0.25, 0.5, 1.0])
+    number, placeholder = dict(k=7, temperature=0.75, top_p=0.5), dict(k=1, temperature=1.0, top_p=1.0)
+    for lists in ((), ("k",), ("temperature",), ("top_p",), ("k", "top_p"), ("k", "temperature", "top_p")):
+        s = ops.SamplerSettings(3, **{m: given[m] if m in lists else number[m] for m in given}, guidance=None, seed=11)
+        up = s.upload("cpu")
+        for m in given:
+            assert getattr(up, m) == (placeholder[m] if m in lists else number[m]) and type(getattr(up, m)) is type(number[m]), (lists, m)
+            assert (up.tensors[m].tolist() == given[m] and up.tensors[m].dtype == ops._ROW_DTYPES[m]) if m in lists else up.tensors[m] is None
+        assert up.seed == 11 and up.tensors["seed"] is None and up.tensors["sample"] is None and up.rows == 3
+        block = up.block()
+        assert (block is None) == (not lists)
+        if lists:
+            assert {n for n, _ in block._fields_ if getattr(block, n)} == set(lists)
+    # a seed per row: the seeds as int64 bits, a zero sample index for every row, and no scalar seed
+    up = ops.SamplerSettings(3, 7, 0.75, 0.5, None, [0, 2 ** 63, 2 ** 64 - 1]).upload("cpu")
+    assert up.seed is None and up.tensors["seed"].tolist() == [0, -2 ** 63, -1] and up.tensors["sample"].tolist() == [0, 0, 0]
+    assert up.tensors["sample"].dtype == torch.int32 and (up.k, up.temperature, up.top_p) == (7, 0.75, 0.5)
+    block = up.block()
+    assert {n for n, _ in block._fields_ if getattr(block, n)} == {"seed", "sample"}
+
+
 def test_ctypes_mirror_matches_the_header():
     from open_musiclm_amd import hip, ops
     text = open(os.path.join(ROOT, "include", "omlm.h")).read()
