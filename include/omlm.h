@@ -311,6 +311,31 @@ int omlm_cross_entropy_fwd_reg(const float* logits, const int* labels, float* ro
 int omlm_cross_entropy_bwd_reg(const float* logits, const int* labels, const float* row_lse, const float* gscale,
                                float coef, void* dlogits, int R, int V, int ld, int ldd, int out_dtype,
                                float label_smoothing, float z_loss, void* stream);
+/* Per-quantizer diagnostics of the cross entropy (extension, off unless called; no reference counterpart): a second, read-only pass over
+   the rows the loss has just walked, and an ordered reduce that bins the rows per quantizer.  The kernels live in a translation unit of
+   their own (csrc/ce_metrics.hip): the four cross-entropy kernels above, their launches and their results are what they are without it.
+   Row rule (omlm_ce_metrics).  Row r has logits l[0..V) -- columns [V, ld) are never read into any result -- and label y:
+       y < 0 (ignored)   row_nll = 0, row_rank = -1, row_entropy = 0
+       y >= V            the same, and err_flag |= 4 as in omlm_cross_entropy_fwd
+       live row          row_nll     = lse - l[y], lse formed as the forward kernels form row_lse (maximum, __expf, __logf, the same reduction
+                                       order: bit for bit their row_lse on the same row)
+                         row_rank    = #{c : l[c] > l[y]} + #{c < y : l[c] == l[y]}, integer counts only: 0 exactly where
+                                       argmax(l) == y under the first-occurrence tie rule; rank < k: y survives a top-k filter
+                         row_entropy = log s - (sum_c e_c d_c) / s with d_c = l[c] - max, e_c = exp(d_c), s = sum_c e_c: -sum_c p log p.
+                                       A column with e_c == 0 (a -inf logit) adds exactly 0.  A row holding a NaN logit is unspecified.
+   Any of the three outputs may be NULL: that output alone is skipped.  One wave per row while V <= 1088 (the row in registers), one
+   workgroup per row above; the route is a function of V alone (csrc/ce_metrics_plan.h).
+   Bin rule (omlm_ce_metrics_bins).  Rows are in [B, n] order, t = r mod n; R % n == 0.  The bin of a live row is Q where y == V - 1 (the
+   eos entry) and t mod Q otherwise; ignored rows and rows with y >= V enter no bin.  bins is [Q + 1][5] doubles
+   {count, nll, entropy, top1 (rank == 0), topk (rank < k_top)}, each ACCUMULATED onto: several batches cost no host read.  One workgroup
+   per bin adds its rows in a fixed order in fp64 -- no float atomics -- so the same input gives the same bits on every launch and the
+   three counts are exact.
+   Refused by name before any launch: R < 0, V < 1, ld < V, n < 1, R % n != 0, Q < 1, k_top outside [1, V], and null pointers when
+   R > 0 (the three per-row outputs of omlm_ce_metrics excepted).  R == 0 returns 0 and launches nothing. */
+int omlm_ce_metrics(const float* logits, const int* labels, float* row_nll, int* row_rank, float* row_entropy,
+                    int R, int V, int ld, int* err_flag, void* stream);
+int omlm_ce_metrics_bins(const float* row_nll, const int* row_rank, const float* row_entropy, const int* labels,
+                         int R, int n, int Q, int V, int k_top, double* bins, void* stream);
 
 /* clip_grad_norm_ + Adam/AdamW on flat buffers (optimizer.py:10-34; trainer.py:444-447). */
 /* out[0] += sum g^2; partials (optional, >= 2048 floats) selects the bit-reproducible two-pass form (identical clip on every replica). */

@@ -146,6 +146,12 @@ class SingleStageTrainerConfig:
     # label smoothing and z-loss in the fused cross entropy (include/omlm.h; no reference counterpart): training mode only, off at 0
     label_smoothing: float = 0.
     z_loss: float = 0.
+    # per-quantizer loss / accuracy / top-k accuracy / entropy in the logs (metrics.QuantizerMetrics; no reference counterpart): off by
+    # default.  metrics_top_k: the k of the top-k counter (None: what the sampler keeps at filter_thres = 0.9); valid_batches: validation
+    # batches the metrics (and, above 1, valid_loss / valid_accuracy) are taken over
+    quantizer_metrics: bool = False
+    metrics_top_k: Optional[int] = None
+    valid_batches: int = 1
 
 
 @dataclass

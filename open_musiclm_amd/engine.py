@@ -1136,10 +1136,15 @@ class LossFunction(torch.autograd.Function):
 
     reg = (label_smoothing, z_loss), checked floats (include/omlm.h): with either set the forward takes the three sums {nll, smooth, z} of
     every weighted sequence from omlm_cross_entropy_fwd_reg and the loss is sum_s w_s ((1 - eps) NLL_s + eps S_s + zeta Z_s) / total; the
-    backward hands both to omlm_cross_entropy_bwd_reg.  (0, 0): the calls and tensor ops it always made."""
+    backward hands both to omlm_cross_entropy_bwd_reg.  (0, 0): the calls and tensor ops it always made.
+
+    metrics: None, or a metrics.QuantizerMetrics: every weighted sequence then gets the two launches of csrc/ce_metrics.hip right after
+    its ops.ce_fwd, on the same logits buffer and labels, accumulated onto the object.  Both launches only read what the loss reads: the
+    loss, the logits, what is saved for the backward, the backward and the RNG consumption are bit for bit what they are without it.  The
+    rows describe the PLAIN nll of these logits, whatever `reg` is.  None: the launches it always made."""
 
     @staticmethod
-    def forward(ctx, model, all_token_ids, labels, self_attn_mask, loss_weights, ignore_negative, precision, all_logits, reg, *params):
+    def forward(ctx, model, all_token_ids, labels, self_attn_mask, loss_weights, ignore_negative, precision, all_logits, reg, metrics, *params):
         nseq = len(model.token_sequences)
         eps, zeta = reg
         plain = eps == 0.0 and zeta == 0.0
@@ -1150,12 +1155,16 @@ class LossFunction(torch.autograd.Function):
         total_dev = None                       # device-side part of the normaliser: non-ignored labels of padded sequences
         nll = torch.zeros(nseq, device=dev) if plain else torch.zeros(nseq, 3, device=dev)
         st.labels, st.lse_rows, st.coefs = [], [], []
+        # the per-row scratch of the metrics launches, shared by the weighted sequences (same stream: one sequence after the other)
+        scratch = metrics.scratch(max(b.shape[0] for b, w in zip(bufs, loss_weights) if w > 0)) if metrics is not None else None
         for s, (seq, buf, lb, w) in enumerate(zip(model.token_sequences, bufs, labels, loss_weights)):
             if w > 0:
                 lb32 = lb.reshape(-1).to(torch.int32).contiguous()
                 assert lb32.numel() == buf.shape[0], (lb32.numel(), buf.shape)
                 lse_rows = torch.empty(buf.shape[0], device=dev)
                 ops.ce_fwd(buf, lb32, lse_rows, nll[s:s + 1] if plain else nll[s], seq.codebook_size + 1, label_smoothing=eps, z_loss=zeta)
+                if metrics is not None:
+                    metrics.accumulate(s, buf, lb32, lb32.numel() // lay.B, scratch)
                 if ignore_negative[s]:
                     cnt = (lb32 >= 0).sum().to(torch.float32)
                     total_dev = cnt if total_dev is None else total_dev + cnt
@@ -1214,4 +1223,4 @@ class LossFunction(torch.autograd.Function):
             dl.append(d)
         run_backward(st, dl)
         ctx.st = None
-        return (None,) * (9 + ctx.nparams)
+        return (None,) * (10 + ctx.nparams)

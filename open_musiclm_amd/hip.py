@@ -74,6 +74,8 @@ SIGNATURES = {
     "omlm_cross_entropy_bwd": [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, vp],
     "omlm_cross_entropy_fwd_reg": [vp, vp, vp, vp, i32, i32, i32, vp, vp],
     "omlm_cross_entropy_bwd_reg": [vp, vp, vp, vp, f32, vp, i32, i32, i32, i32, i32, f32, f32, vp],
+    "omlm_ce_metrics": [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp],
+    "omlm_ce_metrics_bins": [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp],
     "omlm_sumsq_accumulate": [vp, i64, vp, vp, vp],
     "omlm_adamw_clip_step": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, f32, i32, i32, i32, vp, vp],
     "omlm_adamw_clip_step_ema": [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, vp, f32, i32, i32, i32, vp, vp, f32, i32, i32, vp],

@@ -129,8 +129,11 @@ class TokenConditionedTransformer(nn.Module):
         return bufs[-1]
 
     def loss_and_logits(self, ids, labels, self_attn_mask, loss_weights, ignore_negative=None, all_logits=True,
-                        label_smoothing=0., z_loss=0.):
-        """ignore_negative[s]: labels < 0 of sequence s are ignore_index rows AND leave the loss normaliser (the padded labels of
+                        label_smoothing=0., z_loss=0., metrics=None):
+        """metrics (extension): a metrics.QuantizerMetrics that every weighted sequence's rows are accumulated onto by the two launches of
+        csrc/ce_metrics.hip, behind the loss's own forward launch and on the same logits; the loss, the logits and the backward are bit for
+        bit what they are without it.  None (the default): the launches it always made.
+        ignore_negative[s]: labels < 0 of sequence s are ignore_index rows AND leave the loss normaliser (the padded labels of
         a unique_consecutive sequence, open_musiclm.py:396-404).  all_logits=False: the heads of zero-weight sequences are not
         evaluated (their logits come back as None).
         label_smoothing / z_loss (extensions; include/omlm.h): the loss is sum_s w_s ((1 - eps) NLL_s + eps S_s + zeta Z_s) / total, formed
@@ -139,7 +142,7 @@ class TokenConditionedTransformer(nn.Module):
         ign = tuple(bool(v) for v in ignore_negative) if ignore_negative is not None else (False,) * len(labels)
         reg = (ops.check_label_smoothing(label_smoothing), ops.check_z_loss(z_loss))
         return engine.LossFunction.apply(self, ids, labels, self_attn_mask, tuple(loss_weights), ign, self._precision(),
-                                         bool(all_logits), reg, *self.parameters())
+                                         bool(all_logits), reg, metrics, *self.parameters())
 
 
 _GENERATE_MASK_ORIG = generate_mask_with_prob
@@ -219,6 +222,29 @@ class TokenConditionedTransformerWrapper(nn.Module):
     def _loss_reg(self) -> dict:
         """label_smoothing / z_loss as loss_and_logits takes them: the constructor's values in training mode, nothing in eval()."""
         return dict(label_smoothing=self.label_smoothing, z_loss=self.z_loss) if self.training else {}
+
+    def new_metrics(self, top_k=None):
+        """A zeroed metrics.QuantizerMetrics for this wrapper's token sequences and loss weights, on the model's device (no host sync).
+        top_k: the k of its top-k counter (None: what the sampler keeps at the default filter_thres = 0.9)."""
+        from .metrics import QuantizerMetrics
+        return QuantizerMetrics.for_model(self.transformer, [float(w) for w in self.cross_entropy_loss_weights], top_k, self.device)
+
+    def _metrics_arg(self, return_metrics, return_loss):
+        """forward's ``return_metrics`` -> the QuantizerMetrics to accumulate onto, or None; refusals by name, before any device work."""
+        from .metrics import QuantizerMetrics
+        if return_metrics is None or return_metrics is False:
+            return None
+        if not return_loss:
+            raise ValueError("return_metrics needs return_loss=True: the metrics are formed from the rows the loss walks")
+        if isinstance(return_metrics, QuantizerMetrics):
+            if (return_metrics.quantizers, return_metrics.vocab, return_metrics.weights) != \
+                    ([s.num_quantizers for s in self.token_sequences], [s.codebook_size + 1 for s in self.token_sequences],
+                     [float(w) for w in self.cross_entropy_loss_weights]):
+                raise ValueError("return_metrics: the QuantizerMetrics given describes other token sequences or loss weights than this wrapper's")
+            return return_metrics
+        if return_metrics is True:
+            return self.new_metrics()
+        raise ValueError(f"return_metrics must be False, True or a QuantizerMetrics, not {return_metrics!r}")
 
     @eval_decorator
     @torch.no_grad()
@@ -472,7 +498,7 @@ class TokenConditionedTransformerWrapper(nn.Module):
         n_tot = sum(int(t.numel() // t.shape[0]) + 1 for t in all_token_ids) + len(all_token_ids) - 1
         return all(t.is_cuda for t in all_token_ids) and n_tot <= 4096
 
-    def _forward_loss_fused(self, all_token_ids):
+    def _forward_loss_fused(self, all_token_ids, metrics=None):
         """Same arithmetic as _prepare + TokenConditionedTransformer.forward's id flattening + generate_mask_with_prob, in one launch
         (ops.prepare_train_batch); consumes the RNG exactly like the torch path (one randn of the mask's shape).  Labels come back as
         int32 tensors [B, len + 1]."""
@@ -494,13 +520,15 @@ class TokenConditionedTransformerWrapper(nn.Module):
                                                                [True] * len(ids), **null_kw)
         prepared = engine.PreparedIds(ids32, lens)
         ignore = [False] * len(ids)
+        kw = self._loss_reg() if metrics is None else dict(self._loss_reg(), metrics=metrics)
         if torch.is_grad_enabled():
-            loss, *logits = self.transformer.loss_and_logits(prepared, labels, keymask, weights, ignore, False, **self._loss_reg())
+            loss, *logits = self.transformer.loss_and_logits(prepared, labels, keymask, weights, ignore, False, **kw)
         else:
             with torch.enable_grad():
-                loss, *logits = self.transformer.loss_and_logits(prepared, labels, keymask, weights, ignore, False, **self._loss_reg())
+                loss, *logits = self.transformer.loss_and_logits(prepared, labels, keymask, weights, ignore, False, **kw)
             loss = loss.detach()
-        return loss, [l.transpose(1, 2) if l is not None else None for l in logits], labels
+        out = (loss, [l.transpose(1, 2) if l is not None else None for l in logits], labels)
+        return out if metrics is None else (*out, metrics)
 
     def _prepare(self, all_token_ids, return_loss, input_has_eos):
         """eos append, labels, last-token drop, key mask (open_musiclm.py:340-376); in training mode with null_cond_prob > 0 the
@@ -539,12 +567,22 @@ class TokenConditionedTransformerWrapper(nn.Module):
         return ids, labels, mask
 
     def forward(self, *, all_token_ids: List[torch.Tensor], return_loss: bool = False, input_has_eos: bool = False,
-                return_logits: bool = True, **kwargs):
+                return_logits: bool = True, return_metrics=False, **kwargs):
         """return_logits=False (extension, return_loss=True only): the logits of sequences whose loss weight is 0 are not computed
-        and come back as None -- the trainers' optimizer steps read only the loss (trainer.py:428-447)."""
+        and come back as None -- the trainers' optimizer steps read only the loss (trainer.py:428-447).
+        return_metrics (extension, return_loss=True only; False: off, the call launches exactly what it launches without the argument):
+        True -- the result gains a fourth element, a metrics.QuantizerMetrics of this call: per weighted sequence and per quantizer the
+        count, nll, entropy, top-1 and top-k hits of its rows, formed on the device by two launches behind the loss's own
+        (csrc/ce_metrics.hip; include/omlm.h) -- no host sync; ``.to_dict()`` reads it.  A QuantizerMetrics (``new_metrics()``) -- accumulated onto
+        and returned: what the trainer uses under HIP-graph capture, where the buffer exists before the capture and every replay adds to
+        it.  Works on both preparation routes; loss, logits and gradients are bit for bit those of the call without it.  The metrics
+        describe the PLAIN nll of the logits this call formed: in training mode those are the training-mode logits (dropout, the forgetful
+        mask and the condition drop are on), and label smoothing and z-loss are not part of the numbers.  The padded labels of a
+        unique_consecutive sequence are ignored rows, as in the loss."""
         assert len(all_token_ids) == len(self.token_sequences)
+        metrics = self._metrics_arg(return_metrics, return_loss)
         if return_loss and not return_logits and self._fused_prepare_ok(all_token_ids, input_has_eos):
-            return self._forward_loss_fused(all_token_ids)
+            return self._forward_loss_fused(all_token_ids, metrics)
         ids, labels, mask = self._prepare(all_token_ids, return_loss, input_has_eos)
         if not return_loss:
             return self.transformer(all_token_ids=ids, self_attn_mask=mask, **kwargs)
@@ -553,14 +591,15 @@ class TokenConditionedTransformerWrapper(nn.Module):
         # .sum() in the reference (:396-404); the fused loss ignores negative labels and counts the rest on the device
         ignore = [bool(info.unique_consecutive and self.unique_consecutive) for info in self.token_sequences]
         loss_labels = [lb.masked_fill(lb == self.pad_id, -1) if ig else lb for lb, ig in zip(labels, ignore)]
+        kw = self._loss_reg() if metrics is None else dict(self._loss_reg(), metrics=metrics)
         if torch.is_grad_enabled():
-            loss, *logits = self.transformer.loss_and_logits(ids, loss_labels, mask, weights, ignore, return_logits, **self._loss_reg())
+            loss, *logits = self.transformer.loss_and_logits(ids, loss_labels, mask, weights, ignore, return_logits, **kw)
         else:
             with torch.enable_grad():
-                loss, *logits = self.transformer.loss_and_logits(ids, loss_labels, mask, weights, ignore, return_logits, **self._loss_reg())
+                loss, *logits = self.transformer.loss_and_logits(ids, loss_labels, mask, weights, ignore, return_logits, **kw)
             loss = loss.detach()
         all_logits = [l.transpose(1, 2) if l is not None else None for l in logits]               # 'b n c -> b c n' (:389)
-        return loss, all_logits, labels
+        return (loss, all_logits, labels) if metrics is None else (loss, all_logits, labels, metrics)
 
 
 def create_semantic_transformer(dim=1024, depth=6, clap_codebook_size=1024, semantic_codebook_size=1024,

@@ -821,6 +821,42 @@ def ce_bwd(logits, labels, row_lse, gscale, coef, dlogits, V, *, label_smoothing
          R, V, ld, dlogits.shape[-1], dcode(dlogits.dtype), eps, zeta, stream_ptr())
 
 
+METRICS_FILTER_THRES = 0.9                    # generate()'s default filter_thres: what default_metrics_top_k keeps
+
+
+def default_metrics_top_k(V):
+    """The k the sampler keeps of V entries at the default filter_thres = 0.9 -- the expression of utils.top_k (102 at V = 1025)."""
+    return max(int((1 - METRICS_FILTER_THRES) * V), 1)
+
+
+def check_metrics_top_k(k, V, name="metrics_top_k"):
+    """The k of the top-k hit counter of the quantizer metrics (include/omlm.h: rank < k) as an int: None -> default_metrics_top_k(V);
+    otherwise an integer in [1, V].  Anything else raises a ValueError that names the argument.  Pure Python: before any device work."""
+    if k is None:
+        return default_metrics_top_k(V)
+    if isinstance(k, bool) or not isinstance(k, int) or not (1 <= k <= V):
+        raise ValueError(f"{name} must be an integer in [1, {V}] (the entries of a row, eos included) or None, not {k!r}")
+    return int(k)
+
+
+def ce_metrics(logits, labels, V, *, row_nll=None, row_rank=None, row_entropy=None):
+    """omlm_ce_metrics over fp32 logits [R, ld] and int32 labels [R]: per live row nll (fp32), the exact rank of the label (int32) and the
+    predictive entropy (fp32) into whichever of the three [R] outputs is given (include/omlm.h; ignored rows: 0 / -1 / 0).  Read-only on
+    the logits; a label >= V raises the device flag of index_error_flag like the loss."""
+    R, ld = logits.shape
+    call("omlm_ce_metrics", ptr(logits), ptr(labels), ptr(row_nll), ptr(row_rank), ptr(row_entropy), R, V, ld,
+         ptr(index_error_flag(logits.device)), stream_ptr())
+
+
+def ce_metrics_bins(row_nll, row_rank, row_entropy, labels, n, Q, V, k_top, bins):
+    """omlm_ce_metrics_bins: the rows of ce_metrics ([B, n] order) ACCUMULATED onto bins, fp64 [Q + 1, 5] {count, nll, entropy, top1, topk},
+    bin t mod Q and bin Q for eos labels, in a fixed order (include/omlm.h)."""
+    if bins.dtype != torch.float64 or tuple(bins.shape) != (Q + 1, 5) or not bins.is_contiguous():
+        raise ValueError(f"ce_metrics_bins: bins must be contiguous fp64 [{Q + 1}, 5]; got {bins.dtype} {tuple(bins.shape)}")
+    call("omlm_ce_metrics_bins", ptr(row_nll), ptr(row_rank), ptr(row_entropy), ptr(labels), labels.numel(), int(n), int(Q), int(V),
+         int(k_top), ptr(bins), stream_ptr())
+
+
 def sumsq_accumulate(g, out, partials=None):
     """out[0] += sum g^2; with `partials` (>= 2048 floats) the reduction order is fixed (bit-reproducible)."""
     call("omlm_sumsq_accumulate", ptr(g), g.numel(), ptr(out), ptr(partials), stream_ptr())

@@ -145,6 +145,13 @@ class DataParallel:
             t /= self.world_size
         return t
 
+    def sum_across_ranks_(self, t: torch.Tensor) -> torch.Tensor:
+        """In-place SUM all-reduce of a small tensor in ITS OWN dtype -- fp64 counters stay fp64 (RCCL and gloo both reduce doubles) and never
+        take the gradient exchange's bf16 wire format or its buckets."""
+        if self.is_distributed:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        return t
+
     def all_gather_cat(self, t: torch.Tensor) -> torch.Tensor:
         if not self.is_distributed:
             return t

@@ -111,8 +111,18 @@ class SingleStageTrainer(nn.Module):
                  save_model_every=1000, results_folder='./results', accelerate_kwargs: dict = {},
                  config_paths: Optional[List[str]] = None, dataset_yields_tokens: Optional[bool] = None,
                  use_hip_graph: Optional[bool] = None, ema_decay: Optional[float] = None, ema_update_after_step: int = 0,
-                 ema_warmup: bool = True, null_cond_prob: float = 0., label_smoothing: float = 0., z_loss: float = 0.):
-        """label_smoothing / z_loss (0: off; no reference counterpart): the train wrapper's loss becomes (1 - eps) nll + eps smooth +
+                 ema_warmup: bool = True, null_cond_prob: float = 0., label_smoothing: float = 0., z_loss: float = 0.,
+                 quantizer_metrics: bool = False, metrics_top_k: Optional[int] = None, valid_batches: int = 1):
+        """quantizer_metrics (False: off, every step and ``validate`` run exactly what they run without it; no reference counterpart): per
+        quantizer of every weighted sequence the mean nll, top-1 and top-k accuracy, mean entropy and count (metrics.QuantizerMetrics), formed
+        on the device from the rows the loss walks.  Training: the micro-batches of an optimizer step accumulate onto one trainer-owned buffer
+        (eager and HIP-graph route alike), ``train_step`` reads it beside its loss read, puts ``train_``-prefixed entries into its logs and the
+        tracker record and zeroes it; the numbers are rank-local like logs['loss'] and describe the plain nll of the training-mode logits
+        (label smoothing / z-loss excluded).  Validation: accumulated over ``valid_batches`` batches, summed over ranks, logged with the
+        ``valid_`` prefix and kept as ``last_valid_metrics``.  metrics_top_k: the k of the top-k accuracy (None: what the sampler keeps at the
+        default filter_thres = 0.9).  valid_batches > 1 (needs quantizer_metrics): valid_loss is the mean of the batch losses and
+        valid_accuracy top1 / count of the last sequence; token dump and reconstructed waves still come from the first batch.
+        label_smoothing / z_loss (0: off; no reference counterpart): the train wrapper's loss becomes (1 - eps) nll + eps smooth +
         zeta lse^2 per row (TokenConditionedTransformerWrapper, include/omlm.h), in the cross-entropy kernels.  Training mode only:
         ``validate`` (on the model or the EMA twin) reports the plain cross entropy, so valid_loss stays comparable across runs and is
         the plain-CE monitor of a regularised run, while the logged train loss carries both terms.
@@ -163,6 +173,20 @@ class SingleStageTrainer(nn.Module):
         self.null_cond_prob = null_cond_prob
         self.label_smoothing, self.z_loss = label_smoothing, z_loss            # checked by the wrapper, by name
         self.train_wrapper = self._make_stage(transformer, null_cond_prob)
+        # refusals by name, before any device work
+        if isinstance(valid_batches, bool) or not isinstance(valid_batches, int) or valid_batches < 1:
+            raise ValueError(f"valid_batches must be an integer >= 1, not {valid_batches!r}")
+        if valid_batches > 1 and not quantizer_metrics:
+            raise ValueError("valid_batches > 1 needs quantizer_metrics=True: the validation accuracy over several batches comes from the metrics' bins")
+        self.quantizer_metrics, self.metrics_top_k, self.valid_batches = bool(quantizer_metrics), metrics_top_k, valid_batches
+        if self.quantizer_metrics:
+            from . import ops
+            for seq, w in zip(transformer.token_sequences, self.train_wrapper.transformer_wrapper.cross_entropy_loss_weights):
+                if w > 0:
+                    ops.check_metrics_top_k(metrics_top_k, seq.codebook_size + 1)
+        # the buffer the training micro-steps accumulate onto: made on first use, once the model is on its device, and before any capture
+        self.__dict__['_train_metrics_buf'] = None
+        self.last_valid_metrics = None
         self.ds_fields = token_fields if tokens_in else wave_fields
 
         self.register_buffer('steps', torch.Tensor([0]))
@@ -350,17 +374,32 @@ class SingleStageTrainer(nn.Module):
         return {k: v.to(self.device, non_blocking=True) for k, v in zip(self.ds_fields, batch)}
 
     # ---- one optimizer step (trainer.py:415-552) -------------------------------------------------------
+    def train_metrics(self):
+        """The trainer-owned metrics.QuantizerMetrics of the training micro-steps (None with quantizer_metrics off): one device buffer that
+        exists before the micro-step is captured, so every replay adds to it."""
+        if not self.quantizer_metrics:
+            return None
+        buf = self._train_metrics_buf
+        if buf is None or buf.bins.device != self.device:
+            buf = self.__dict__['_train_metrics_buf'] = self.train_wrapper.transformer_wrapper.new_metrics(self.metrics_top_k)
+        return buf
+
     def micro_step(self, data_kwargs):
-        """forward + backward of ONE micro-batch; gradients accumulate in the optimizer's flat buffer."""
+        """forward + backward of ONE micro-batch; gradients accumulate in the optimizer's flat buffer, and with quantizer_metrics the rows'
+        metrics onto ``train_metrics()``."""
+        # part of what the captured callable closes over: the flag decides the launches, the buffer is the one every replay adds to
+        mkw = dict(return_metrics=self.train_metrics()) if self.quantizer_metrics else {}
         if self.use_hip_graph and self.device.type == 'cuda':
             if self._graphed is None:
                 from .graph import GraphedForwardBackward
-                self._graphed = GraphedForwardBackward(lambda **kw: self.train_wrapper(**kw, return_loss=True, return_logits=False)[0],
+                self._graphed = GraphedForwardBackward(lambda **kw: self.train_wrapper(**kw, return_loss=True, return_logits=False, **mkw)[0],
                                                        loss_scale=1.0 / self.grad_accum_every)
 
-                def discard():                          # warm-up steps really ran: throw their gradients away
+                def discard():                          # warm-up steps really ran: throw their gradients (and metrics) away
                     self.optim.mark_grads_dirty()
                     self.optim.zero_grad()
+                    if mkw:
+                        mkw['return_metrics'].zero_()
                     rc = self._relpos_cache()
                     if rc is not None:
                         rc.reset_accum()
@@ -370,7 +409,7 @@ class SingleStageTrainer(nn.Module):
             loss = self._graphed(**data_kwargs)
             self.optim.mark_grads_dirty()
             return loss.clone()
-        loss, _, _ = self.train_wrapper(**data_kwargs, return_loss=True, return_logits=False)
+        loss = self.train_wrapper(**data_kwargs, return_loss=True, return_logits=False, **mkw)[0]
         (loss / self.grad_accum_every).backward()
         self.optim.mark_grads_dirty()
         return loss.detach()
@@ -423,6 +462,11 @@ class SingleStageTrainer(nn.Module):
             rc.flush()                                  # the MLP's backward on the micro-batches' summed d(table), before the exchange
         self.optimizer_step()
         logs = {'loss': float(loss_acc.item()) / self.grad_accum_every}       # single host sync per optimizer step
+        train_metrics = {}
+        if self.quantizer_metrics:                   # the host has just waited for the device: this read waits for nothing new
+            train_metrics = self.train_metrics().to_dict("train_")
+            self.train_metrics().zero_()
+            logs.update(train_metrics)
         if self.device.type == 'cuda':
             # the host has just waited for the device: a token id / label past its table (wrong codebook size, damaged token store)
             # was skipped by the kernels and flagged -- surface it like torch's device assert would
@@ -439,9 +483,13 @@ class SingleStageTrainer(nn.Module):
         self.print(f"{steps}: loss: {logs['loss']}")
 
         valid_loss = valid_accuracy = None
+        valid_metrics = {}
         if not (steps % self.save_results_every):
             valid_loss, valid_accuracy = self.validate(steps)
-        self.tracker.log({"train_loss": logs['loss'], "valid_loss": valid_loss, "valid_accuracy": valid_accuracy}, step=steps)
+            if self.quantizer_metrics:
+                valid_metrics = self.last_valid_metrics
+        self.tracker.log({"train_loss": logs['loss'], "valid_loss": valid_loss, "valid_accuracy": valid_accuracy,
+                          **train_metrics, **valid_metrics}, step=steps)
 
         if self.is_main and not (steps % self.save_model_every):
             self.print(f'{steps}: saving model to {str(self.results_folder)}')
@@ -458,17 +506,36 @@ class SingleStageTrainer(nn.Module):
     @torch.no_grad()
     def validate(self, steps, use_ema=False):
         """trainer.py:457-526: teacher-forced validation loss / token accuracy, token dumps, optional wave reconstruction.
-        use_ema: on the weight EMA (the twin) instead of the training weights."""
+        use_ema: on the weight EMA (the twin) instead of the training weights.
+        With quantizer_metrics: additionally the per-quantizer metrics of ``valid_batches`` batches (the batches after the first run with
+        return_logits=False: no logits leave the device), summed over ranks, in ``last_valid_metrics`` (``valid_`` prefix); every host read
+        comes after the last batch's launches.  The return value stays (valid_loss, valid_accuracy); with valid_batches > 1 they are the mean
+        of the batch losses and top1 / count of the last sequence from the bins."""
         if use_ema:
             self._require_ema()
         wrapper = self._ema_wrapper if use_ema else self.train_wrapper
         wrapper.eval()
         data_kwargs = self._next_batch(self.valid_dl_iter)
-        valid_loss, all_logits, all_labels = wrapper(**data_kwargs, return_loss=True)
-        valid_loss = float(self.dp.reduce_mean(valid_loss.detach().reshape(1)).item())
+        if not self.quantizer_metrics:
+            valid_loss, all_logits, all_labels = wrapper(**data_kwargs, return_loss=True)
+            valid_loss = float(self.dp.reduce_mean(valid_loss.detach().reshape(1)).item())
+        else:
+            vm = wrapper.transformer_wrapper.new_metrics(self.metrics_top_k)
+            loss_sum, all_logits, all_labels, _ = wrapper(**data_kwargs, return_loss=True, return_metrics=vm)
+            loss_sum = loss_sum.detach().reshape(1)
+            for _ in range(self.valid_batches - 1):
+                more = wrapper(**self._next_batch(self.valid_dl_iter), return_loss=True, return_logits=False, return_metrics=vm)
+                loss_sum = loss_sum + more[0].detach().reshape(1)
+            self.dp.sum_across_ranks_(vm.bins)                  # fp64 counters, in their own dtype
+            valid_loss = float(self.dp.reduce_mean(loss_sum / self.valid_batches).item())
+            host = vm._host()
+            self.last_valid_metrics = vm.to_dict("valid_", host=host)
         pred = self.dp.all_gather_cat(all_logits[-1].argmax(1).contiguous()).cpu().long()
         gt = self.dp.all_gather_cat(all_labels[-1].contiguous()).cpu().long()
         valid_accuracy = (pred == gt).float().mean().item()
+        if self.valid_batches > 1:
+            last = host[-1, :vm.quantizers[-1] + 1]
+            valid_accuracy = float(last[:, 3].sum()) / max(float(last[:, 0].sum()), 1.0)
         self.print(f'{steps}: valid loss {valid_loss}, valid acc {valid_accuracy}')
         if self.is_main and self.save_predicted_tokens:
             inter = torch.empty((pred.shape[0] + gt.shape[0], pred.shape[1]), dtype=pred.dtype)
