@@ -738,6 +738,18 @@ typedef struct omlm_decode_args {
 #define OMLM_DECODE_SPLITK_CNT_B(B, D) \
     (OMLM_DECODE_GROUPS(B) * (((D) + 15) / 16) > ((B) > 16 ? (B) : 16) ? OMLM_DECODE_GROUPS(B) * (((D) + 15) / 16) : ((B) > 16 ? (B) : 16))
 int omlm_decode_step(const omlm_decode_args* args, const long long* ids, void* stream);
+/* omlm_decode_step under a key mask: the same step, its attention launches replaced by their masked forms (same grids, same LDS, every
+ * other launch the same), so the new row attends only to the keys the training forward attends to
+ * (TokenConditionedTransformerWrapper._prepare: conditioning positions that hold a pad or an eos id are no keys).
+ *   key_live  [B, Nmax] bytes on the device, row-major; byte (b, j) nonzero: sample b attends to cache row j.  Bytes of rows > *pos_dev
+ *             are not read.  Byte *pos_dev of EVERY sample must be 1: the new key is always attended, and it is what guarantees a
+ *             nonzero softmax sum.  That is the caller's duty -- the library sees a pointer only.  The buffer is read by every layer's
+ *             attention launch and never written; it may stay the same over a captured graph's replays.
+ * A masked key has score -3.0e38f and weight 0 exactly, like a key past *pos_dev.  A 64-key range whose keys are all masked leaves the
+ * partial {max = -3.0e38f, sum = 0, o = 0} in parts, which every combine weighs with exp(-3.0e38f - live max) = 0; such ranges still
+ * load their K / V and count in the per-sample tickets, so splitk_cnt is zero again after the step.  A mask of all ones gives
+ * omlm_decode_step's logits bit for bit.  The refusals are omlm_decode_step's, made before any launch, plus "null key_live". */
+int omlm_decode_step_masked(const omlm_decode_args* args, const unsigned char* key_live, const long long* ids, void* stream);
 /* *pos_dev += 1, *step_dev += 1 (either may be null): keeps the row / sampler-step counters on the device so that a
  * captured step can be replayed. */
 int omlm_decode_advance(int* pos_dev, int* step_dev, void* stream);

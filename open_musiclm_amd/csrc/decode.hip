@@ -496,6 +496,8 @@ __global__ __launch_bounds__(DEC_AT2) void dec_attn2_kernel(const float* q, TC* 
     }
 }
 
+#include "decode_keymask.inc"     // dec_attn_masked_kernel, dec_attn2_masked_kernel: the two kernels above under a key mask (omlm_decode_step_masked)
+
 // ---- B2: out[b, n] = sum_k act[b, k] W[n, k] (+ res[b, n]); 16 output features per workgroup.
 //      act = LN?(in[b, :]) or (parts != null) the combined attention output ----
 template <typename TW>
@@ -1442,7 +1444,7 @@ using omlm_plan::DecodeLaunch;
 using omlm_plan::DecodePlan;
 static_assert(omlm_plan::DEC_ERR_ARG == OMLM_ERR_ARG && omlm_plan::DEC_LDS_CAP == 160 * 1024, "decode_plan.h states the return code and launch_lds_cap's size");
 
-static DecodeCall decode_call(const omlm_decode_args& a, const long long* ids) {
+static DecodeCall decode_call(const omlm_decode_args& a, const long long* ids, bool masked, const unsigned char* key_live) {
     DecodeCall c;
     memset(&c, 0, sizeof(c));
     c.B = a.B; c.D = a.D; c.H = a.H; c.L = a.L; c.Fp = a.Fp; c.Nmax = a.Nmax; c.nsplit = a.nsplit; c.V1 = a.V1;
@@ -1451,6 +1453,7 @@ static DecodeCall decode_call(const omlm_decode_args& a, const long long* ids) {
     c.head_W = a.head_W != nullptr; c.ln_parts = a.ln_parts != nullptr; c.splitk_ws = a.splitk_ws != nullptr; c.splitk_cnt = a.splitk_cnt != nullptr;
     c.W1p_lo = a.W1p_lo != nullptr; c.W2p_lo = a.W2p_lo != nullptr; c.head_W_lo = a.head_W_lo != nullptr; c.k_new = a.k_new != nullptr;
     c.advance_pos = a.advance_pos != nullptr;
+    c.masked = masked; c.key_live = key_live != nullptr;
     return c;
 }
 
@@ -1578,7 +1581,8 @@ extern "C" int omlm_decode_advance(int* pos_dev, int* step_dev, void* stream) {
 
 // One launch of the plan, in layer l.  false: see above.
 template <typename TW>
-static bool decode_launch(const DecodePlan& p, const DecodeLaunch& k, const omlm_decode_args& a, const long long* ids, int l, hipStream_t st) {
+static bool decode_launch(const DecodePlan& p, const DecodeLaunch& k, const omlm_decode_args& a, const long long* ids, int l, hipStream_t st,
+                          const unsigned char* key_live) {
     const int B = a.B, D = a.D, H = a.H, Fp = a.Fp, HD = H * 64;
     const dim3 grid(k.gx, k.gy), wg(k.threads);
     const size_t lds = (size_t)k.lds;
@@ -1632,6 +1636,23 @@ static bool decode_launch(const DecodePlan& p, const DecodeLaunch& k, const omlm
     case omlm_plan::DK_COMBINE:
         hipLaunchKernelGGL(dec_attn_combine_kernel, grid, wg, 0, st, a.parts, a.q, a.nsplit, H, a.pos_dev, a.round_bf16);
         return true;
+    case omlm_plan::DK_ATTN1_MASKED:        // (omlm_decode_step_masked: DK_ATTN1 / DK_ATTN2 with the key mask)
+        if (k.c16) launch_lds_cap<dec_attn_masked_kernel<h16_t>>(grid, wg, lds, st, a.q, (h16_t*)a.Kc[l], (const h16_t*)a.Vc[l], a.q_scale[l], a.k_scale[l], a.bias_table,
+                                                                 a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16, (const float*)a.k_new, key_live);
+        else launch_lds_cap<dec_attn_masked_kernel<float>>(grid, wg, lds, st, a.q, a.Kc[l], (const float*)a.Vc[l], a.q_scale[l], a.k_scale[l], a.bias_table,
+                                                           a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16, f0, key_live);
+        return true;
+    case omlm_plan::DK_ATTN2_MASKED: {
+        float* const comb_out = p.comb_in_attn ? a.q : nullptr;
+        int* const comb_cnt = p.comb_in_attn ? a.splitk_cnt : nullptr;
+        if (k.c16)
+            hipLaunchKernelGGL(dec_attn2_masked_kernel<h16_t>, grid, wg, lds, st, a.q, (h16_t*)a.Kc[l], (const h16_t*)a.Vc[l], a.q_scale[l], a.k_scale[l], a.bias_table,
+                               a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16, comb_out, comb_cnt, (const float*)a.k_new, key_live);
+        else
+            hipLaunchKernelGGL(dec_attn2_masked_kernel<float>, grid, wg, lds, st, a.q, a.Kc[l], (const float*)a.Vc[l], a.q_scale[l], a.k_scale[l], a.bias_table,
+                               a.bias_ld, a.parts, H, a.Nmax, a.nsplit, a.pos_dev, a.scale, a.round_bf16, comb_out, comb_cnt, f0, key_live);
+        return true;
+    }
     case omlm_plan::DK_DEC3: return dec3_go<TW>(k, dec2_fill(a, p, k, l), st);
     case omlm_plan::DK_DEC3_FFIN: return dec3_ffin_go<TW>(k, dec2_fill(a, p, k, l), st);
     case omlm_plan::DK_DEC4: return dec4_go<TW>(k, dec2_fill(a, p, k, l), st);
@@ -1642,16 +1663,21 @@ static bool decode_launch(const DecodePlan& p, const DecodeLaunch& k, const omlm
 
 // The plan's launches in order: prologue, the layer's launches L times, head; then the check, and the advance where it is a launch of its own.
 template <typename TW>
-static int decode_run(const DecodePlan& p, const omlm_decode_args& a, const long long* ids, void* stream) {
+static int decode_run(const DecodePlan& p, const omlm_decode_args& a, const long long* ids, void* stream, const unsigned char* key_live) {
+    const bool masked = key_live != nullptr;             // (omlm_decode_step_masked: the plan has refused a null mask)
     hipStream_t st = as_stream(stream);
     bool ok = true;
-    for (int i = 0; i < p.layer; ++i) ok = ok && decode_launch<TW>(p, p.l[i], a, ids, 0, st);
+    for (int i = 0; i < p.layer; ++i) ok = ok && decode_launch<TW>(p, p.l[i], a, ids, 0, st, key_live);
     for (int l = 0; l < a.L; ++l)
-        for (int i = p.layer; i < p.tail; ++i) ok = ok && decode_launch<TW>(p, i == p.layer && l > 0 ? p.q_rest : p.l[i], a, ids, l, st);
+        for (int i = p.layer; i < p.tail; ++i) ok = ok && decode_launch<TW>(p, i == p.layer && l > 0 ? p.q_rest : p.l[i], a, ids, l, st, key_live);
     for (int i = p.tail; i < p.n; ++i)
-        if (p.l[i].kernel != omlm_plan::DK_ADVANCE) ok = ok && decode_launch<TW>(p, p.l[i], a, ids, 0, st);
-    if (!ok) { omlm_set_error("omlm_decode_step: the plan names a kernel instantiation that this library does not build"); return OMLM_ERR_UNSUPPORTED; }
-    const int rc = omlm_post_launch("omlm_decode_step");
+        if (p.l[i].kernel != omlm_plan::DK_ADVANCE) ok = ok && decode_launch<TW>(p, p.l[i], a, ids, 0, st, key_live);
+    if (!ok) {
+        omlm_set_error(masked ? "omlm_decode_step_masked: the plan names a kernel instantiation that this library does not build"
+                              : "omlm_decode_step: the plan names a kernel instantiation that this library does not build");
+        return OMLM_ERR_UNSUPPORTED;
+    }
+    const int rc = omlm_post_launch(masked ? "omlm_decode_step_masked" : "omlm_decode_step");
     if (rc == OMLM_OK && p.advance == 2) return omlm_decode_advance(a.advance_pos, a.advance_step, stream);
     return rc;
 }
@@ -1663,22 +1689,31 @@ static int decode_run(const DecodePlan& p, const omlm_decode_args& a, const long
 // A refusal is returned before anything is launched.
 #if !OMLM_FP16
 extern "C" int omlm_decode_step_h(const omlm_decode_args* a, const long long* ids, void* stream);
+extern "C" int omlm_decode_step_masked_h(const omlm_decode_args* a, const unsigned char* key_live, const long long* ids, void* stream);
 #endif
-extern "C" int OMLM_API(omlm_decode_step)(const omlm_decode_args* a, const long long* ids, void* stream) {
+// masked: omlm_decode_step_masked's call (the attention launches read key_live)
+static int decode_step(const omlm_decode_args* a, const long long* ids, void* stream, bool masked, const unsigned char* key_live) {
     OMLM_CHECK_ARG(a != nullptr, "null argument block");
 #if !OMLM_FP16
     if (a->w_dtype == OMLM_DT_F16) {
         omlm_decode_args b = *a;
         b.w_dtype = 1;
-        return omlm_decode_step_h(&b, ids, stream);
+        return masked ? omlm_decode_step_masked_h(&b, key_live, ids, stream) : omlm_decode_step_h(&b, ids, stream);
     }
 #endif
-    const DecodePlan plan = omlm_plan::decode_plan(decode_call(*a, ids));
+    const DecodePlan plan = omlm_plan::decode_plan(decode_call(*a, ids, masked, key_live));
     if (plan.rc != OMLM_OK) { omlm_set_error(plan.msg); return plan.rc; }
 #if !OMLM_FP16
-    if (a->w_dtype == 0) return decode_run<float>(plan, *a, ids, stream);
+    if (a->w_dtype == 0) return decode_run<float>(plan, *a, ids, stream, key_live);
 #endif
-    return decode_run<h16_t>(plan, *a, ids, stream);
+    return decode_run<h16_t>(plan, *a, ids, stream, key_live);
+}
+extern "C" int OMLM_API(omlm_decode_step)(const omlm_decode_args* a, const long long* ids, void* stream) {
+    return decode_step(a, ids, stream, false, nullptr);
+}
+// omlm_decode_step under the key mask key_live[B, Nmax] (include/omlm.h): the masked attention kernels in place of the plain ones.
+extern "C" int OMLM_API(omlm_decode_step_masked)(const omlm_decode_args* a, const unsigned char* key_live, const long long* ids, void* stream) {
+    return decode_step(a, ids, stream, true, key_live);
 }
 
 }   // namespace OMLM_NS

@@ -94,6 +94,9 @@ struct DecodeCall {
     bool round_bf16, kv16;
     // which of the optional pointers are there
     bool pos_dev, parts, ids, emb_table, head_W, ln_parts, splitk_ws, splitk_cnt, W1p_lo, W2p_lo, head_W_lo, k_new, advance_pos;
+    // omlm_decode_step_masked: the attention launches are the masked kernels, which read key_live[B, Nmax]; everything else of the plan --
+    // route, grids, LDS bytes, every other launch -- is the unmasked call's
+    bool masked, key_live;
 };
 enum DecodeRoute { DEC_GEN1, DEC_DEC3, DEC_DEC2, DEC_DEC4 };      // first generation; second: row kernels (B = 1), vector kernels, matrix-core kernels
 enum DecodeKernel {
@@ -101,7 +104,8 @@ enum DecodeKernel {
     DK_QKV1, DK_ATTN1, DK_GEMV1, DK_FFIN1,              // first generation: dec_qkv_kernel, dec_attn_kernel, dec_gemv_kernel, dec_ffin_kernel
     DK_ATTN2, DK_COMBINE,                               // dec_attn2_kernel, dec_attn_combine_kernel
     DK_DEC2, DK_DEC3, DK_DEC3_FFIN, DK_DEC4,            // dec2_kernel, dec3_kernel, dec3_ffin_kernel, dec4_kernel
-    DK_ADVANCE                                          // omlm_decode_advance, after the step's own launches have been checked
+    DK_ADVANCE,                                         // omlm_decode_advance, after the step's own launches have been checked
+    DK_ATTN1_MASKED, DK_ATTN2_MASKED                    // dec_attn_masked_kernel, dec_attn2_masked_kernel (DecodeCall::masked)
 };
 enum DecodePhase { DP_PROLOGUE, DP_QKV, DP_ATTN, DP_COMBINE, DP_OUT, DP_FFIN, DP_FFOUT, DP_HEAD, DP_ADVANCE };
 struct DecodeLaunch {
@@ -182,6 +186,7 @@ static inline DecodePlan decode_plan(const DecodeCall& c) {
     DEC_REFUSE_UNLESS(!c.kv16 || (w16 && c.round_bf16 && c.k_new),
                       "kv16 (16-bit K/V cache) needs 16-bit weights, round_bf16 and the k_new staging row "
                       "[!a->kv16 || (a->w_dtype != 0 && a->round_bf16 != 0 && a->k_new)]");
+    DEC_REFUSE_UNLESS(!c.masked || c.key_live, "null key_live [key_live]");
     // (a batch above 8 has passed the matrix-core rule, which implies the second generation: the first-generation kernels never see one)
     const bool gen2 = decode_second_generation(D, H, Fp);
     if (!gen2) {
@@ -192,7 +197,7 @@ static inline DecodePlan decode_plan(const DecodeCall& c) {
         p.layer = p.n;
         if (c.L > 0) {
             decode_push(p, DK_QKV1, DP_QKV, c, (HD + 128) / DEC_ROWS, 1, DEC_T, dec1_row_lds(B, D));
-            decode_push(p, DK_ATTN1, DP_ATTN, c, c.nsplit, B, DEC_T, dec1_attn_lds(H));
+            decode_push(p, c.masked ? DK_ATTN1_MASKED : DK_ATTN1, DP_ATTN, c, c.nsplit, B, DEC_T, dec1_attn_lds(H));
             decode_push(p, DK_GEMV1, DP_OUT, c, (D + DEC_ROWS - 1) / DEC_ROWS, 1, DEC_T, dec1_row_lds(B, HD));
             decode_push(p, DK_FFIN1, DP_FFIN, c, Fp / 8, 1, DEC_T, dec1_row_lds(B, D)).unrounded = pl;
             decode_push(p, DK_GEMV1, DP_FFOUT, c, (D + DEC_ROWS - 1) / DEC_ROWS, 1, DEC_T, dec1_row_lds(B, Fp)).unrounded = pl;
@@ -237,7 +242,7 @@ static inline DecodePlan decode_plan(const DecodeCall& c) {
             else decode_push_rows(p, DP_QKV, c, DK_DEC2, 2, DEC2_QKV, false, (HD + 128) / DEC2_ROWS, D, true, ns);
             if (rest) p.q_rest = p.l[--p.n];
         }
-        decode_push(p, DK_ATTN2, DP_ATTN, c, c.nsplit, B, DEC_AT2, dec_attn2_lds(H));
+        decode_push(p, c.masked ? DK_ATTN2_MASKED : DK_ATTN2, DP_ATTN, c, c.nsplit, B, DEC_AT2, dec_attn2_lds(H));
         // x1 = x + attn Wo^T.  Matrix cores: combine once (in the attention kernel, or by a launch), then a plain row product
         if (mfma && !p.comb_in_attn) decode_push(p, DK_COMBINE, DP_COMBINE, c, H, B, 64, 0);
         if (mfma) decode_push_rows(p, DP_OUT, c, DK_DEC4, 8, DEC2_LNGEMV, false, p.npd, HD, false, 0);
@@ -272,13 +277,13 @@ static inline DecodePlan decode_plan(const DecodeCall& c) {
 // call: B D H L Fp Nmax nsplit V1 w_dtype fp16_copy round_bf16 kv16, then one flag per pointer: pos_dev parts ids emb_table head_W ln_parts
 // splitk_ws splitk_cnt W1p_lo W2p_lo head_W_lo k_new advance_pos.  out: rc route G region npd npf stat_x stat_x1 stat_u split comb_in_attn
 // rowstat advance n layer tail, then 16 values per launch (l[0 .. n), then q_rest): kernel phase w16 c16 n mode pl grp gx gy threads lds nsl
-// nstat_in gtiles unrounded.  msg: 320 bytes.
-static omlm_plan::DecodeCall omlm_plan_decode_call(const int* v) {
+// nstat_in gtiles unrounded.  msg: 320 bytes.  omlm_plan_decode: masked off.  omlm_plan_decode_masked: the plan of omlm_decode_step_masked for
+// the same 25 values, key_live given or not; same output format.
+static omlm_plan::DecodeCall omlm_plan_decode_call(const int* v, bool masked, bool key_live) {
     return {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9] != 0, v[10] != 0, v[11] != 0, v[12] != 0, v[13] != 0, v[14] != 0, v[15] != 0,
-            v[16] != 0, v[17] != 0, v[18] != 0, v[19] != 0, v[20] != 0, v[21] != 0, v[22] != 0, v[23] != 0, v[24] != 0};
+            v[16] != 0, v[17] != 0, v[18] != 0, v[19] != 0, v[20] != 0, v[21] != 0, v[22] != 0, v[23] != 0, v[24] != 0, masked, key_live};
 }
-extern "C" void omlm_plan_decode(const int* v, long long* out, char* msg) {
-    const omlm_plan::DecodePlan p = omlm_plan::decode_plan(omlm_plan_decode_call(v));
+static void omlm_plan_decode_out(const omlm_plan::DecodePlan& p, long long* out, char* msg) {
     const long long h[16] = {p.rc, p.route, p.G, p.region, p.npd, p.npf, p.stat_x, p.stat_x1, p.stat_u, p.split, p.comb_in_attn, p.rowstat,
                              p.advance, p.n, p.layer, p.tail};
     memcpy(out, h, sizeof(h));
@@ -288,6 +293,10 @@ extern "C" void omlm_plan_decode(const int* v, long long* out, char* msg) {
         memcpy(out + 16 + 16 * i, w, sizeof(w));
     }
     memcpy(msg, p.msg, sizeof(p.msg));
+}
+extern "C" void omlm_plan_decode(const int* v, long long* out, char* msg) { omlm_plan_decode_out(omlm_plan::decode_plan(omlm_plan_decode_call(v, false, false)), out, msg); }
+extern "C" void omlm_plan_decode_masked(const int* v, int key_live, long long* out, char* msg) {
+    omlm_plan_decode_out(omlm_plan::decode_plan(omlm_plan_decode_call(v, true, key_live != 0)), out, msg);
 }
 extern "C" int omlm_plan_decode_second_generation(int D, int H, int Fp) { return omlm_plan::decode_second_generation(D, H, Fp); }
 extern "C" int omlm_plan_decode_matrix_core(int B, int D, int H, int Fp, int w16, int ln_parts) { return omlm_plan::decode_matrix_core(B, D, H, Fp, w16 != 0, ln_parts != 0); }

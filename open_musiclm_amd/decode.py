@@ -21,6 +21,11 @@ and the logits are the same bit for bit.
 Classifier-free guidance on the condition (token sequence 0; include/omlm.h): a guided call of P prompts is a decoder of 2P rows, the
 prompts followed by their null twins, and ``SamplingLoop(..., guidance=s)`` samples P ids per step from ``null + s (cond - null)`` --
 one combine launch in front of the sampler, one twin copy behind it, the step kernels untouched.
+
+Key mask (``CachedDecoder(..., key_mask=True)``; include/omlm.h: omlm_decode_step_masked): the decoder owns ``key_live`` [B, Nmax] bytes,
+all ones; ``prefill(ids, key_mask=m)`` runs the batched forward under m and copies it into the first columns, and every step then goes
+through the masked attention kernels, so a new row attends to the keys m allows and to every row after the prompt.  Off (the default):
+``key_live`` is None and every call is omlm_decode_step, as it has always been.
 """
 from __future__ import annotations
 
@@ -193,10 +198,14 @@ def supports(model, batch: int, precision: Optional[str] = None, prompt_rows: Op
 
 
 class CachedDecoder:
-    def __init__(self, model, batch: int, max_rows: int, precision: str, wide: bool = False, kv_cache=None):
+    def __init__(self, model, batch: int, max_rows: int, precision: str, wide: bool = False, kv_cache=None, key_mask: bool = False):
         """kv_cache: None / "fp32" (fp32 K/V cache) or "operand" (the precision's 16-bit operand type; same logits, half of cache_bytes);
-        self.kv_dtype tells which type the cache holds."""
+        self.kv_dtype tells which type the cache holds.
+        key_mask: True -- the steps run under self.key_live ([B, Nmax] uint8, nonzero = attend; all ones until prefill is given a mask)
+        through omlm_decode_step_masked; False -- self.key_live is None and the steps are omlm_decode_step."""
         self.kv_dtype = kv_cache_choice(kv_cache, precision)                   # refused by name before any device work
+        if not isinstance(key_mask, bool):
+            raise ValueError(f"key_mask must be a bool, not {key_mask!r}")
         # (a non-causal prefix is checked against the prompt in prefill)
         if not supports(model, batch, precision, prompt_rows=engine.prefix_rows(model.transformer), wide=wide):
             tr = model.transformer
@@ -229,6 +238,8 @@ class CachedDecoder:
         self.nsplit = (Nmax + 63) // 64
         self.parts = torch.zeros(B, self.nsplit, H, 66, **f32)                 # attention partials (max, sum, o[64])
         self.pos_dev = torch.zeros(1, device=dev, dtype=torch.int32)           # row index, kept on the device
+        # key mask of the masked steps: static for the decoder's life (a captured cycle holds its address); rows past the prompt stay live
+        self.key_live = torch.ones(B, Nmax, device=dev, dtype=torch.uint8) if key_mask else None
         self.u = torch.empty(B, Fp, **f32)
         seq = model.token_sequences[-1]
         self.Q, self.V1 = seq.num_quantizers, seq.codebook_size + 1
@@ -295,9 +306,13 @@ class CachedDecoder:
         self.args = a
 
     # ---- prompt: the batched forward over all known rows, keeping what the single-row steps need ---------------------
-    def prefill(self, all_token_ids: List[torch.Tensor]) -> torch.Tensor:
+    def prefill(self, all_token_ids: List[torch.Tensor], key_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """all_token_ids: the conditioning sequences followed by the ids sampled so far (may be empty).  Returns the
-        [B, ldV] logits of the last row (they predict the next id) and leaves the caches filled for rows < N."""
+        [B, ldV] logits of the last row (they predict the next id) and leaves the caches filled for rows < N.
+        key_mask (a decoder built with key_mask=True only): [B, N] bool / uint8, True = attend -- the batched forward runs under it and the
+        steps keep it for the prompt's rows; None: every row is attended."""
+        if key_mask is not None and self.key_live is None:
+            raise ValueError("prefill: a key mask needs a decoder built with key_mask=True")
         model, tr = self.model, self.model.transformer
         ids32, lens = engine.build_ids(model, all_token_ids)
         B, N = ids32.shape
@@ -307,7 +322,12 @@ class CachedDecoder:
             raise ValueError(f"cached decode of a model with a non-causal prefix of {P} rows needs them all in the prompt; got {N} rows")
         lay = engine.get_layout(model, B, lens, ids32.device, True)
         x = engine.embed_forward(model, ids32, lay)
-        y, y_lo, saved = engine.trunk_forward(tr, self.pw, x, None, B, N, True, False, keep_h1_lo_tail=self.planes)
+        km = None
+        if key_mask is not None:
+            if tuple(key_mask.shape) != (B, N):
+                raise ValueError(f"prefill: key_mask must be [{B}, {N}], got {tuple(key_mask.shape)}")
+            km = key_mask.to(device=ids32.device, dtype=torch.uint8).contiguous()
+        y, y_lo, saved = engine.trunk_forward(tr, self.pw, x, km, B, N, True, False, keep_h1_lo_tail=self.planes)
         nseq = len(model.token_sequences)
         logits = engine.heads_forward(model, self.pw, y, y_lo, lay, [s == nseq - 1 for s in range(nseq)])[-1]
         for l, sv in enumerate(saved["layers"]):
@@ -319,9 +339,20 @@ class CachedDecoder:
             self.hist[l][:, 2 - take:].copy_(h1[:, N - take:])
             if self.planes:                                  # the conv state of "fp16ff" is the un-rounded h1 = hi + lo
                 self.hist[l][:, 2 - take:].add_(sv.h1_lo_tail[:, 2 - take:])
+        if self.key_live is not None:
+            self.key_live.fill_(1)
+            if km is not None:
+                self.key_live[:, :N].copy_(km)
         self.rows = N
         self.pos_dev.fill_(N)
         return logits
+
+    def _step_call(self, ids: torch.Tensor):
+        """The step's library call on the decoder's argument block: omlm_decode_step, or under a key mask omlm_decode_step_masked."""
+        if self.key_live is None:
+            call("omlm_decode_step", C.addressof(self.args), ptr(ids), stream_ptr())
+        else:
+            call("omlm_decode_step_masked", C.addressof(self.args), ptr(self.key_live), ptr(ids), stream_ptr())
 
     def step(self, new_ids: torch.Tensor, k: int) -> torch.Tensor:
         """Append the row of ``new_ids`` ([B] int64: the k-th sampled id of every sample, k counted from 0) and return the
@@ -342,7 +373,7 @@ class CachedDecoder:
             self.x.copy_(self.emb[rows] + self.pos_emb[k])
             a.emb_table = None
         a.advance_pos, a.advance_step = self.pos_dev.data_ptr(), None        # the head kernel moves the row index on
-        call("omlm_decode_step", C.addressof(a), ptr(ids), stream_ptr())
+        self._step_call(ids)
         self.rows += 1
         return self.logits
 
@@ -468,7 +499,7 @@ class SamplingLoop:
         a.head_W = dec.pw.heads[-1][(k + 1) % dec.Q].data_ptr()
         a.head_W_lo = dec.pw.heads_lo[-1][(k + 1) % dec.Q].data_ptr() if dec.planes else None
         a.advance_pos, a.advance_step = dec.pos_dev.data_ptr(), self.step_dev.data_ptr()
-        call("omlm_decode_step", C.addressof(a), ptr(self.cur), stream_ptr())
+        dec._step_call(self.cur)
 
     def run(self) -> torch.Tensor:
         """Returns the [n_new, B] sampled ids."""

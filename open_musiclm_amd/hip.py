@@ -85,6 +85,7 @@ SIGNATURES = {
     "omlm_sample_topk_gumbel_at": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp],
     "omlm_sample_embed_at": [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, i64, i64, vp, i32, vp],
     "omlm_decode_step": [vp, vp, vp],
+    "omlm_decode_step_masked": [vp, vp, vp, vp],
     "omlm_decode_advance": [vp, vp, vp],
     "omlm_relpos_first_fwd": [vp, vp, vp, vp, i32, i32, i32, vp],
     "omlm_relpos_first_bwd": [vp, vp, i32, i32, i32, vp],

@@ -123,9 +123,10 @@ class TokenConditionedTransformer(nn.Module):
         return [None if a is None else b + (a - b) * cond_scale for a, b in zip(logits, null_logits)]
 
     # ---- fast paths used by the wrapper ---------------------------------------------------------------
-    def last_logits(self, ids: List[torch.Tensor]) -> torch.Tensor:
-        """[B, ldV] logits of the final position of the final sequence only (AR decode step, no autograd)."""
-        bufs, _, _ = engine.run_forward(self, ids, None, True, False, self._precision(), final_rows_only=True)
+    def last_logits(self, ids: List[torch.Tensor], self_attn_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[B, ldV] logits of the final position of the final sequence only (AR decode step, no autograd).  self_attn_mask: the key
+        mask [B, rows] of forward(), True = attend; None: every key is attended."""
+        bufs, _, _ = engine.run_forward(self, ids, self_attn_mask, True, False, self._precision(), final_rows_only=True)
         return bufs[-1]
 
     def loss_and_logits(self, ids, labels, self_attn_mask, loss_weights, ignore_negative=None, all_logits=True,
@@ -162,6 +163,51 @@ def null_twin(cond_ids: torch.Tensor, info: TokenSequenceInfo, n_ids: int) -> to
     out = cond_ids.clone()
     out[:, :n_ids] = null_condition_ids(info, n_ids, cond_ids.device)
     return out
+
+
+def check_mask_conditioning(value, name: str = "mask_conditioning") -> bool:
+    """generate() / score(): ``mask_conditioning`` must be a bool; anything else is a ValueError that names it."""
+    if not isinstance(value, bool):
+        raise ValueError(f"{name} must be a bool (True: decode under the training key mask), not {value!r}")
+    return value
+
+
+def _require_conditioning(token_sequences):
+    """mask_conditioning=True on a model without a conditioning sequence: there is no position the rule could take out of the keys."""
+    if len(token_sequences) < 2:
+        raise ValueError("mask_conditioning: the key mask covers the conditioning sequences in front of the predicted one; this model has a "
+                         "single token sequence and nothing to mask")
+
+
+def stage_mask_conditioning(mask_conditioning):
+    """MusicLM.forward's ``mask_conditioning`` per stage (_per_stage; None and a stage that is not named: off), every other value checked
+    by check_mask_conditioning."""
+    return _per_stage(mask_conditioning, lambda v, name: None if v is None else check_mask_conditioning(v, name), "mask_conditioning")
+
+
+def live_conditioning(cond_ids: List[torch.Tensor], eos_ids, pad_id: int, batch: int, device):
+    """THE rule of which conditioning positions are fed and attended (open_musiclm.py:358-371), stated once for the training forward
+    (_prepare), generate() and score().  cond_ids: the flattened conditioning sequences [B, n_i] as they are fed -- after unique_consecutive
+    and after the optional eos append.  live = (id != pad_id) & (id != eos_id of its sequence).  -> (the ids with every non-live position
+    set to 0, the key mask [B, sum(n_i + 1)] bool, True = attend, with every sequence's start token in front of it as True).  The rows of
+    the predicted sequence -- its start token, given ids (pads included), generated ids -- are always attended: the caller pads the
+    mask with True for them."""
+    out, pieces = [], []
+    for t, eos in zip(cond_ids, eos_ids):
+        live = (t != pad_id) & (t != eos)
+        out.append(t.masked_fill(~live, 0))
+        pieces.append(F.pad(live, (1, 0), value=True))            # the sequence's start token is always attended
+    mask = torch.cat(pieces, dim=-1) if pieces else torch.empty((batch, 0), device=device, dtype=torch.bool)
+    return out, mask
+
+
+def twin_live_conditioning(cond_live: List[torch.Tensor], mask: torch.Tensor, info: TokenSequenceInfo, n_ids: int):
+    """The null twin of a prompt under the key mask (the training rule of a dropped sample, ``mask[:, 1:1 + n0] |= dropped``): cond_live /
+    mask as live_conditioning returned them for the prompt -> (the twin's ids: the null ids at the condition's n_ids id positions,
+    everything else the prompt's zeroed ids; its mask: the prompt's with those n_ids positions attended)."""
+    twin_mask = mask.clone()
+    twin_mask[:, 1:1 + n_ids] = True
+    return [null_twin(cond_live[0], info, n_ids)] + list(cond_live[1:]), twin_mask
 
 
 def _require_condition(token_sequences, what: str):
@@ -251,7 +297,7 @@ class TokenConditionedTransformerWrapper(nn.Module):
     def generate(self, *, conditioning_token_ids: List[torch.Tensor], pred_token_ids: Optional[torch.Tensor] = None,
                  max_time_steps=512, filter_thres=0.9, temperature=1., include_eos_in_output=False,
                  append_eos_to_conditioning_tokens=True, allow_eos_in_output=False, uniforms=None, sampler_rng=None,
-                 sampler_seed=None, top_p=None, kv_cache=None, return_logprobs=False, cond_scale=None, **kwargs):
+                 sampler_seed=None, top_p=None, kv_cache=None, return_logprobs=False, cond_scale=None, mask_conditioning=False, **kwargs):
         """AR sampling (open_musiclm.py:253-326).  Every step re-runs the full causal forward over the grown
         sequence like the reference (results are identical to a KV-cached decode because the stack is strictly
         causal); only the last position's logits are formed, and eos suppression + top-k + Gumbel-argmax run in
@@ -289,7 +335,18 @@ class TokenConditionedTransformerWrapper(nn.Module):
         refused): every row then draws u(t, 0, c) of its own seed, what a one-sample call with that seed draws, so a row's uniforms depend on
         its seed alone, not on its place in the batch or on its neighbours.  Its ids equal that one-sample call's wherever the step kernels
         give a row the same logits at both batch sizes -- not promised between B = 1 and B >= 2 at dim 1024, where different kernels run.
-        With a number the stream index stays the global sample index."""
+        With a number the stream index stays the global sample index.
+        ``mask_conditioning`` (a bool; False, the default: the reference's sampler, which passes no key mask, and exactly the launches of
+        a call without the argument): True decodes under the key mask of the training forward (live_conditioning) -- every conditioning
+        position that holds a pad or an eos id, the appended eos included, is fed as id 0 and is no key; start tokens, given
+        ``pred_token_ids`` (their pads too) and every generated row are attended.  The ids are then sampled from the distribution that
+        training, validate() and the per-quantizer metrics describe.  On the cached route the prefill runs under the mask and every step
+        goes through omlm_decode_step_masked (captured cycles included); the re-forward route grows the mask by one attended column per id.
+        Works with every source of uniforms, ``top_p``, ``return_logprobs``, per-row settings, ``kv_cache`` and ``cond_scale`` -- a null
+        twin takes its prompt's mask with the condition's id positions attended (twin_live_conditioning), as a dropped training sample does.
+        With ``append_eos_to_conditioning_tokens=False`` the rule applies to the ids as given, like forward(input_has_eos=True)."""
+        if check_mask_conditioning(mask_conditioning):                        # refused by name before any device work
+            _require_conditioning(self.token_sequences)
         # rows of the call, as the checks below need them (no conditioning sequence: a model the checks further down refuse or serve as before)
         batch = conditioning_token_ids[0].shape[0] if len(conditioning_token_ids) else (pred_token_ids.shape[0] if exists(pred_token_ids) else 0)
         pred_info, pred_eos_id = self.token_sequences[-1], self.eos_ids[-1]
@@ -319,6 +376,9 @@ class TokenConditionedTransformerWrapper(nn.Module):
             first_step = 0
             sampled = torch.empty((batch, 0), device=device, dtype=torch.long)
         cond, twin = self._condition_rows(conditioning_token_ids, append_eos_to_conditioning_tokens, s.guidance is not None)
+        masks = None
+        if mask_conditioning:
+            cond, twin, masks = self._masked_condition_rows(cond, twin, append_eos_to_conditioning_tokens)
         if pred_info.unique_consecutive:
             sampled = batch_unique_consecutive(sampled, pad_value=self.pad_id)
 
@@ -342,9 +402,9 @@ class TokenConditionedTransformerWrapper(nn.Module):
             use_cache = decode.supports(self.transformer, 2, self.transformer._precision(), prompt_rows=prompt_rows, wide=True)
         if use_cache:
             new, lps = self._generate_cached(cond, twin, sampled, s, U, n_new, prompt_rows + n_new, allow_eos_in_output,
-                                             kwargs.pop('use_graph', False), {} if kv_cache is None else dict(kv_cache=kv_cache))
+                                             kwargs.pop('use_graph', False), {} if kv_cache is None else dict(kv_cache=kv_cache), masks)
         else:
-            new, lps = self._generate_reforward(cond, twin, sampled, s, U, n_new, allow_eos_in_output)
+            new, lps = self._generate_reforward(cond, twin, sampled, s, U, n_new, allow_eos_in_output, masks)
         sampled = torch.cat((sampled, new), dim=-1)
         if return_logprobs:
             lps = LogProbs(*(zero_logprobs_after_eos(v, sampled, pred_eos_id, include_eos_in_output).reshape(batch, -1, Q) for v in lps))
@@ -369,14 +429,32 @@ class TokenConditionedTransformerWrapper(nn.Module):
         cond = [_flat(t).long() for t in cond]
         return cond, [null_twin(cond[0], self.token_sequences[0], n_cond_ids)] + cond[1:]
 
-    def _generate_cached(self, cond, twin, sampled, s, U, n_new, rows, allow_eos, use_graph, kv_kw):
+    def _masked_condition_rows(self, cond, twin, append_eos: bool):
+        """mask_conditioning=True: (cond, twin) of _condition_rows -> (cond, twin, (mask, twin_mask)) under the training key mask -- the ids
+        with every non-live position zeroed and the [B, conditioning rows] bool masks of live_conditioning / twin_live_conditioning
+        (twin and twin_mask None where the call is not guided).  The predicted sequence's rows are not in the masks: _rows_mask adds them."""
+        cond = [_flat(t).long() for t in cond]              # (at least one sequence: generate() and score() refuse the flag otherwise)
+        cond, mask = live_conditioning(cond, self.eos_ids, self.pad_id, cond[0].shape[0], self.device)
+        if twin is None:
+            return cond, None, (mask, None)
+        n_cond_ids = cond[0].shape[-1] - (1 if append_eos else 0)
+        twin, twin_mask = twin_live_conditioning(cond, mask, self.token_sequences[0], n_cond_ids)
+        return cond, twin, (mask, twin_mask)
+
+    @staticmethod
+    def _rows_mask(mask: torch.Tensor, n_pred: int) -> torch.Tensor:
+        """A conditioning mask grown by the predicted sequence's start token and its n_pred ids, all attended: the key mask of the rows."""
+        return F.pad(mask, (0, 1 + n_pred), value=True)
+
+    def _generate_cached(self, cond, twin, sampled, s, U, n_new, rows, allow_eos, use_graph, kv_kw, masks=None):
         """generate()'s KV-cached route (decode.py): one new row per sampled id instead of the reference's full re-forward; the ids are
         sampled straight into a [steps, B] buffer that the next decode step reads.  -> (the new ids [B, n_new], the two log-probability
         planes [B, n_new] or None).  A decode call holds up to decode.max_call_batch samples (64 on the matrix-core step kernels, which
         carry four groups of 16 through every launch) -- guided: half as many pairs, rows [0, P) the prompts and rows [P, 2P) their null
         twins -- and larger batches run as consecutive calls: samples are independent, and every call streams the weights once per id.
         Arguments as generate() prepared them: ``cond`` / ``twin`` (_condition_rows), ``sampled`` (the given ids, [B, n0]), ``s`` (the
-        call's ops.SamplerSettings), ``U`` (the source of uniforms), ``rows`` (prompt rows + n_new: what a decoder must hold)."""
+        call's ops.SamplerSettings), ``U`` (the source of uniforms), ``rows`` (prompt rows + n_new: what a decoder must hold), ``masks``
+        (None, or _masked_condition_rows' pair: the decoders are then built with key_mask=True and prefilled under the rows' mask)."""
         batch, device, precision = sampled.shape[0], self.device, self.transformer._precision()
         Q, n0, guided = self.token_sequences[-1].num_quantizers, sampled.shape[-1], twin is not None
         if U is _DEVICE_RNG:
@@ -392,8 +470,13 @@ class TokenConditionedTransformerWrapper(nn.Module):
             prompt = [t[b0:b1] for t in cond] + [sampled[b0:b1]]
             if guided:
                 prompt = [torch.cat((t, n[b0:b1]), dim=0) for t, n in zip(prompt, twin + [sampled])]
-            dec = decode.CachedDecoder(self.transformer, (2 if guided else 1) * (b1 - b0), rows, precision, wide=True, **kv_kw)
-            last = dec.prefill(prompt)
+            if masks is None:
+                dec = decode.CachedDecoder(self.transformer, (2 if guided else 1) * (b1 - b0), rows, precision, wide=True, **kv_kw)
+                last = dec.prefill(prompt)
+            else:
+                km = torch.cat((masks[0][b0:b1], masks[1][b0:b1]), dim=0) if guided else masks[0][b0:b1]
+                dec = decode.CachedDecoder(self.transformer, (2 if guided else 1) * (b1 - b0), rows, precision, wide=True, key_mask=True, **kv_kw)
+                last = dec.prefill(prompt, key_mask=self._rows_mask(km, n0))
             # a keyword at its default is not passed.  Counter stream: sample b draws u(step, b, c) whichever piece it rides in
             loop_kw = dict(rng=(c.seed, b0)) if U is None else {}
             if s.logprobs:
@@ -407,11 +490,11 @@ class TokenConditionedTransformerWrapper(nn.Module):
                 lp_pieces.append((loop.lp_model.t(), loop.lp_sampled.t()))
         return torch.cat(pieces, dim=0), tuple(torch.cat(ps, dim=0) for ps in zip(*lp_pieces)) if s.logprobs else None
 
-    def _generate_reforward(self, cond, twin, sampled, s, U, n_new, allow_eos):
+    def _generate_reforward(self, cond, twin, sampled, s, U, n_new, allow_eos, masks=None):
         """generate()'s re-forward route: every id re-runs the full causal forward over the grown sequence like the reference, one sampler
         call per id.  -> (the new ids [B, n_new], the two log-probability planes [B, n_new] or None).  Guided: one forward over 2B rows
         (the prompts, then their null twins), then the combine in place over the conditional half.  Arguments as for _generate_cached;
-        per-row settings are uploaded once, here."""
+        per-row settings are uploaded once, here.  ``masks``: every forward runs under the rows' key mask, one attended column more per id."""
         batch, n0, device = sampled.shape[0], sampled.shape[-1], self.device
         Q, V1 = self.token_sequences[-1].num_quantizers, self.token_sequences[-1].codebook_size + 1
         nxt = torch.empty(batch, device=device, dtype=torch.long)
@@ -419,15 +502,19 @@ class TokenConditionedTransformerWrapper(nn.Module):
         lps = tuple(torch.zeros(n_new, batch, device=device) for _ in range(2)) if s.logprobs else None
         if twin is not None:
             cond2 = [torch.cat((c, t), dim=0) for c, t in zip(cond, twin)]
+        cmask = None if masks is None else torch.cat(masks, dim=0) if twin is not None else masks[0]
         up = s.upload(device)
         rows_kw = {f"row_{m}": t for m, t in up.tensors.items() if t is not None}
+
+        def mask_arg(ids):          # () without a mask: the call it has always been
+            return () if cmask is None else (self._rows_mask(cmask, ids.shape[-1]),)
         for step in (t * Q + ind for t in tqdm(range(n_new // Q), desc='generating predicted tokens') for ind in range(Q)):
             if twin is not None:
-                both = self.transformer.last_logits(cond2 + [torch.cat((sampled, sampled), dim=0)])
+                both = self.transformer.last_logits(cond2 + [torch.cat((sampled, sampled), dim=0)], *mask_arg(sampled))
                 last = both[:batch]
                 ops.guide_logits(last, both[batch:], last, V1, up.guidance)
             else:
-                last = self.transformer.last_logits(cond + [sampled])
+                last = self.transformer.last_logits(cond + [sampled], *mask_arg(sampled))
             if U is None:
                 src = dict(seed=up.seed, step=step)
             elif U is _DEVICE_RNG:
@@ -442,14 +529,18 @@ class TokenConditionedTransformerWrapper(nn.Module):
     @eval_decorator
     @torch.no_grad()
     def score(self, *, conditioning_token_ids: List[torch.Tensor], pred_token_ids: torch.Tensor,
-              append_eos_to_conditioning_tokens=True, cond_scale=None) -> torch.Tensor:
+              append_eos_to_conditioning_tokens=True, cond_scale=None, mask_conditioning=False) -> torch.Tensor:
         """The teacher-forced twin of ``generate(return_logprobs=True).model``: fp32 [B, T, Q], entry (b, t, q) the log-probability
         (lp_model of include/omlm.h: the model's own distribution, T = 1, all entries) of id ``pred_token_ids[b, t, q]`` given the
         conditioning and the ids before it -- under the logits ``transformer.last_logits(cond + [pred_flat[:, :t Q + q]])`` gives.
         One forward over the whole sequence with generate's semantics (no key mask, the conditioning eos appended and embedded);
         omlm_cross_entropy_fwd writes every row's log-sum-exp, the rest is a gather and a subtract.
         ``cond_scale`` = s (None or 1: off): the twin of ``generate(return_logprobs=True, cond_scale=s).model`` -- one forward over the 2B
-        rows of prompts and null twins, omlm_guide_logits over every row, then the same; the log-softmax of g."""
+        rows of prompts and null twins, omlm_guide_logits over every row, then the same; the log-softmax of g.
+        ``mask_conditioning`` (a bool; False: off): the twin of ``generate(return_logprobs=True, mask_conditioning=True).model`` -- the one
+        forward runs under generate's key mask (live_conditioning; every row of the predicted sequence attended)."""
+        if check_mask_conditioning(mask_conditioning):                          # refused by name before any device work
+            _require_conditioning(self.token_sequences)
         cond_scale = ops.check_cond_scale(cond_scale)                           # before any device work; None = off
         if cond_scale is not None:
             _require_condition(self.token_sequences, "cond_scale")
@@ -468,13 +559,17 @@ class TokenConditionedTransformerWrapper(nn.Module):
         if L == 0:
             return torch.zeros(batch, 0, Q, device=device)
         cond, twin = self._condition_rows(conditioning_token_ids, append_eos_to_conditioning_tokens, cond_scale is not None)
+        kmask = None
+        if mask_conditioning:
+            cond, twin, masks = self._masked_condition_rows(cond, twin, append_eos_to_conditioning_tokens)
+            kmask = self._rows_mask(torch.cat(masks, dim=0) if cond_scale is not None else masks[0], L)
         rows_pred = pred
         if cond_scale is not None:          # rows [0, B) the prompts, rows [B, 2B) their null twins
             cond = [torch.cat((c, t), dim=0) for c, t in zip(cond, twin)]
             rows_pred = torch.cat((pred, pred), dim=0)
         # row j of the predicted sequence (its start token, then the ids) holds the logits after pred[:, :j]: rows 0 .. L - 1 score the L ids,
         # the last row (what would follow them) carries the ignore label
-        bufs, _, _ = engine.run_forward(self.transformer, cond + [rows_pred], None, True, False, self.transformer._precision())
+        bufs, _, _ = engine.run_forward(self.transformer, cond + [rows_pred], kmask, True, False, self.transformer._precision())
         buf = bufs[-1]
         if cond_scale is not None:
             assert buf.shape[0] == 2 * batch * (L + 1), (buf.shape, batch, L)
@@ -547,12 +642,7 @@ class TokenConditionedTransformerWrapper(nn.Module):
         if return_loss:
             labels = [t.clone() for t in ids]
             ids[-1] = ids[-1][:, :-1]
-        pieces = []
-        for i in range(len(ids) - 1):
-            live = (ids[i] != self.pad_id) & (ids[i] != self.eos_ids[i])
-            ids[i] = ids[i].masked_fill(~live, 0)
-            pieces.append(F.pad(live, (1, 0), value=True))            # the sequence's start token is always attended
-        mask = torch.cat(pieces, dim=-1) if pieces else torch.empty((batch, 0), device=device, dtype=torch.bool)
+        ids[:-1], mask = live_conditioning(ids[:-1], self.eos_ids, self.pad_id, batch, device)
         mask = F.pad(mask, (0, ids[-1].shape[-1] + 1), value=True)   # predicted tokens + their start token
         forget = generate_mask_with_prob(mask.shape, self.mask_prob, device=mask.device) if self.mask_prob > 0 and self.training else None
         if self.null_cond_prob > 0 and self.training:
@@ -871,6 +961,9 @@ class MusicLM(nn.Module):
                          (a stage that is not named decodes unguided).  None or 1: off.  Each guided decode call carries a prompt and
                          its null twin, so fine_windows_together stacks half as many windows into one decode call.  Meaningful only on
                          stages trained with null_cond_prob.
+      mask_conditioning -- decode under the training key mask in every stage's generate() (TokenConditionedTransformerWrapper.generate):
+                         a bool for all three stages, or a mapping with any of "semantic" / "coarse" / "fine" (a stage that is not
+                         named decodes as the reference does).  None or False: off.
     ``generate`` is an alias of ``forward``."""
 
     def __init__(self, *, wav2vec=None, clap=None, neural_codec=None, semantic_transformer: TokenConditionedTransformer,
@@ -896,13 +989,15 @@ class MusicLM(nn.Module):
                 mask_out_generated_fine_tokens=False, semantic_sliding_window_step_percent=0.5,
                 coarse_sliding_window_step_percent=0.5, fine_sliding_window_step_percent=1,
                 clap_token_ids=None, return_tokens=False, fine_windows_together=False, sampler_rng=None, top_p=None, kv_cache=None,
-                cond_scale=None):
+                cond_scale=None, mask_conditioning=None):
         top_ps, scales = stage_top_p(top_p), stage_cond_scale(cond_scale)          # refused by name before any work
+        key_masks = stage_mask_conditioning(mask_conditioning)                     # likewise
         decode.check_kv_cache(kv_cache)                                            # likewise
         # the sampling keywords of each stage's generate(); kv_cache and cond_scale only when given (a keyword at its default is not passed)
         kv_kw = {} if kv_cache is None else dict(kv_cache=kv_cache)
-        kw_sem, kw_coarse, kw_fine = (dict(sampler_rng=sampler_rng, top_p=p, **kv_kw, **({} if g is None else dict(cond_scale=g)))
-                                      for p, g in zip(top_ps, scales))
+        kw_sem, kw_coarse, kw_fine = (dict(sampler_rng=sampler_rng, top_p=p, **kv_kw, **({} if g is None else dict(cond_scale=g)),
+                                           **({} if m is None else dict(mask_conditioning=m)))
+                                      for p, g, m in zip(top_ps, scales, key_masks))
         if not exists(clap_token_ids):
             assert exists(text), 'text needs to be passed in if one of the transformer requires conditioning'
             clap_token_ids = get_or_compute_clap_token_ids(None, self.clap, conditioning_audio=None, conditioning_text=text)
