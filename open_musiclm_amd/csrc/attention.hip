@@ -986,9 +986,7 @@ __global__ __launch_bounds__(AT_THREADS) __attribute__((amdgpu_waves_per_eu(AT_D
 // =============================================================================================================
 // Host side.  csrc/attn_plan.h decides what a call runs -- kernels, grids, LDS bytes -- or why it is refused; the entry points below check
 // their arguments, ask for the plan and launch its list.
-using omlm_plan::AttnCall;
-using omlm_plan::AttnLaunch;
-using omlm_plan::AttnPlan;
+using omlm_plan::AttnArgs; using omlm_plan::AttnCall; using omlm_plan::AttnLaunch; using omlm_plan::AttnPlan;
 static_assert(omlm_plan::ATTN_UNSUPPORTED == OMLM_ERR_UNSUPPORTED && TQ == 32 && TKV == 64, "attn_plan.h states the return code and the first-generation tiles");
 
 // attention2.hip / attention3.hip: one launch of the plan each
@@ -1007,116 +1005,115 @@ void attn3_bwd_dkv_launch(const AttnLaunch& l, int ldT, const void* q, const voi
         launch_lds_cap<KERNEL<T, decltype(D)::value, decltype(P)::value>>(dim3(l.gx, l.gy, l.gz), dim3(l.threads), l.lds, st, __VA_ARGS__); \
     })
 
-#if !OMLM_FP16
-// include/omlm.h
-extern "C" int omlm_attn_max_positions(int dtype, int P) { return omlm_plan::attn_max_positions(dtype, P); }
-#endif
-
-static const AttnDrop NO_DROP = {0ull, nullptr, 0u, 1.0f};
-
-// include/omlm.h.  dtype: 0 = fp32 ("bf16x3"), 1 = bf16, 2 = fp16 (forwarded to the fp16 copy of this file; common.h)
-#if !OMLM_FP16
-extern "C" int omlm_mqa_attn_fwd_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                                   void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
-                                   unsigned long long seed, const unsigned long long* seed_dev, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_mqa_attn_fwd)(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                                           void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
-                                           unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16)
-        return omlm_mqa_attn_fwd_h(q, k, v, bias, biasT, keymask, out, lse, B, N, H, scale, bias_ld, 1, P, p, seed, seed_dev, stream);
-#endif
-    AttnDrop d;
-    OMLM_CHECK_ARG(P >= 0, "prefix rows P >= 0");
-    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
-    if (B <= 0 || N <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
-    OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
-    const AttnCall c = {false, dtype == 0, OMLM_FP16 != 0, B, N, H, P, bias != nullptr, biasT != nullptr, false, false, p > 0.f, false};
-    const AttnPlan plan = omlm_plan::attn_plan(c);
-    if (plan.rc) { omlm_set_error(plan.msg); return plan.rc; }
+// The launch loops.  The entry has checked the arguments, attn_run_here has the plan and the kernels' dropout argument.
+static int attn_fwd_run_here(const AttnPlan& plan, const AttnCall& c, const AttnArgs& a, const AttnDrop& dr) {
     // Pn = min(P, N): 0 is causal, >= 1 the non-causal prefix of include/omlm.h.  The kernels take the rel = 0 row of the [N + Pn - 1, bias_ld] table.
-    const int Pn = omlm_plan::attn_prefix_rows(N, P);
-    if (bias && Pn > 0) bias += (size_t)(Pn - 1) * bias_ld;
-    const AttnDrop& dr = p > 0.f ? d : NO_DROP;
-    hipStream_t st = as_stream(stream);
+    const int B = c.B, N = c.N, H = c.H, bias_ld = a.bias_ld, Pn = omlm_plan::attn_prefix_rows(N, c.P);
+    const float scale = a.scale, *bias = a.bias && Pn > 0 ? a.bias + (size_t)(Pn - 1) * bias_ld : a.bias;
+    hipStream_t st = as_stream(a.stream);
     for (int i = 0; i < plan.n; ++i) {
         const AttnLaunch& l = plan.l[i];
-        if (l.family == omlm_plan::ATTN_A4_FWD) attn2_fwd_launch(l, plan.ldT, q, k, v, biasT, keymask, out, lse, B, N, H, scale, st, dr, Pn);
+        if (l.family == omlm_plan::ATTN_A4_FWD) attn2_fwd_launch(l, plan.ldT, a.q, a.k, a.v, a.biasT, a.keymask, a.out, a.lse, B, N, H, scale, st, dr, Pn);
 #if !OMLM_FP16
-        else if (l.precise) A1_LAUNCH(attn_fwd_kernel, float, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (float*)out, lse, B, N, H, scale, bias_ld, dr, Pn);
+        else if (l.precise) A1_LAUNCH(attn_fwd_kernel, float, (const float*)a.q, (const float*)a.k, (const float*)a.v, bias, a.keymask, (float*)a.out, a.lse, B, N, H, scale, bias_ld, dr, Pn);
 #endif
-        else A1_LAUNCH(attn_fwd_kernel, h16_t, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (h16_t*)out, lse, B, N, H, scale, bias_ld, dr, Pn);
+        else A1_LAUNCH(attn_fwd_kernel, h16_t, (const h16_t*)a.q, (const h16_t*)a.k, (const h16_t*)a.v, bias, a.keymask, (h16_t*)a.out, a.lse, B, N, H, scale, bias_ld, dr, Pn);
         if (int rc = omlm_post_launch("omlm_mqa_attn_fwd")) return rc;
     }
     return OMLM_OK;
 }
-
-// dq [B*N, H*64] fp32, dk, dv [B*N, 64] fp32 (overwritten), dbias [N, bias_ld] fp32 (accumulated, +=), delta [B, H, N] scratch.
 // d(bias) of rel >= 0 goes through the workspace and its reduction, that of rel < 0 (Pn > 1) by atomics from the dQ kernel.
-#if !OMLM_FP16
-extern "C" int omlm_mqa_attn_bwd_h(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                                   const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
-                                   float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P,
-                                   float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_mqa_attn_bwd)(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
-                                           const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
-                                           float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P,
-                                           float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16)
-        return omlm_mqa_attn_bwd_h(q, k, v, bias, biasT, keymask, out, dout, lse, delta, dq, dk, dv, dbias, dbias_ws, B, N, H, scale, bias_ld, 1,
-                                   P, p, seed, seed_dev, stream);
-#endif
-    AttnDrop d;
-    OMLM_CHECK_ARG(P >= 0, "prefix rows P >= 0");
-    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
-    if (B <= 0 || N <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(q && k && v && out && dout && lse && delta && dq && dk && dv, "null pointer");
-    OMLM_CHECK_ARG(H >= 1 && ((!bias && !dbias) || bias_ld >= H), "heads / bias pitch");
-    const AttnCall c = {true, dtype == 0, OMLM_FP16 != 0, B, N, H, P, bias != nullptr, biasT != nullptr, dbias != nullptr, dbias_ws != nullptr, p > 0.f,
-                        dv == dk + (size_t)B * N * 64};
-    const AttnPlan plan = omlm_plan::attn_plan(c);
-    if (plan.rc) { omlm_set_error(plan.msg); return plan.rc; }
-    const int Pn = omlm_plan::attn_prefix_rows(N, P);
+static int attn_bwd_run_here(const AttnPlan& plan, const AttnCall& c, const AttnArgs& a, const AttnDrop& dr) {
+    const int B = c.B, N = c.N, H = c.H, bias_ld = a.bias_ld, Pn = omlm_plan::attn_prefix_rows(N, c.P);
     const size_t r0 = Pn > 0 ? (size_t)(Pn - 1) * bias_ld : 0;      // bias, dbias: the rel = 0 row of their tables
-    if (bias) bias += r0;
-    if (dbias) dbias += r0;
-    float* dpart = dbias ? dbias_ws : nullptr;      // per-(sample, head, query tile) d(bias) rows, summed by the reduction
-    float* dkv_part = plan.dkv_slots >= 0 ? dbias_ws + plan.dkv_slots : nullptr;
-    const AttnDrop& dr = p > 0.f ? d : NO_DROP;
-    hipStream_t st = as_stream(stream);
+    const float scale = a.scale, *bias = a.bias ? a.bias + r0 : nullptr;
+    float* dbias = a.dbias ? a.dbias + r0 : nullptr;
+    float* dpart = dbias ? a.dbias_ws : nullptr;      // per-(sample, head, query tile) d(bias) rows, summed by the reduction
+    float* dkv_part = plan.dkv_slots >= 0 ? a.dbias_ws + plan.dkv_slots : nullptr;
+    hipStream_t st = as_stream(a.stream);
     for (int i = 0; i < plan.n; ++i) {
         const AttnLaunch& l = plan.l[i];
         switch (l.family) {
         case omlm_plan::ATTN_A2_DQ:
-            attn2_bwd_dq_launch(l, plan.ldT, q, k, v, biasT, keymask, out, dout, lse, delta, dq, dbias, bias_ld, dpart, B, N, H, scale, st, dr, Pn);
+            attn2_bwd_dq_launch(l, plan.ldT, a.q, a.k, a.v, a.biasT, a.keymask, a.out, a.dout, a.lse, a.delta, a.dq, dbias, bias_ld, dpart, B, N, H, scale, st, dr, Pn);
             break;
         case omlm_plan::ATTN_A1_DQ:
 #if !OMLM_FP16
-            if (l.precise) A1_LAUNCH(attn_bwd_dq_precise_kernel, float, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)out, (const float*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
+            if (l.precise) A1_LAUNCH(attn_bwd_dq_precise_kernel, float, (const float*)a.q, (const float*)a.k, (const float*)a.v, bias, a.keymask, (const float*)a.out, (const float*)a.dout, a.lse, a.delta, a.dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
             else
 #endif
-            A1_LAUNCH(attn_bwd_dq_kernel, h16_t, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)out, (const h16_t*)dout, lse, delta, dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
+            A1_LAUNCH(attn_bwd_dq_kernel, h16_t, (const h16_t*)a.q, (const h16_t*)a.k, (const h16_t*)a.v, bias, a.keymask, (const h16_t*)a.out, (const h16_t*)a.dout, a.lse, a.delta, a.dq, dbias, B, N, H, scale, bias_ld, dpart, dr, Pn);
             break;
         case omlm_plan::ATTN_DBIAS_REDUCE:
             omlm_attn_dbias_reduce_launch(&l, dpart, dbias, bias_ld, B, N, H, st);
             break;
         case omlm_plan::ATTN_A1_DKV:
 #if !OMLM_FP16
-            if (l.precise) A1_LAUNCH(attn_bwd_dkv_kernel, float, (const float*)q, (const float*)k, (const float*)v, bias, keymask, (const float*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, l.win ? biasT : nullptr, plan.ldT, dr, Pn);
+            if (l.precise) A1_LAUNCH(attn_bwd_dkv_kernel, float, (const float*)a.q, (const float*)a.k, (const float*)a.v, bias, a.keymask, (const float*)a.dout, a.lse, a.delta, a.dk, a.dv, B, N, H, scale, bias_ld, l.win ? a.biasT : nullptr, plan.ldT, dr, Pn);
             else
 #endif
-            A1_LAUNCH(attn_bwd_dkv_kernel, h16_t, (const h16_t*)q, (const h16_t*)k, (const h16_t*)v, bias, keymask, (const h16_t*)dout, lse, delta, dk, dv, B, N, H, scale, bias_ld, l.win ? biasT : nullptr, plan.ldT, dr, Pn);
+            A1_LAUNCH(attn_bwd_dkv_kernel, h16_t, (const h16_t*)a.q, (const h16_t*)a.k, (const h16_t*)a.v, bias, a.keymask, (const h16_t*)a.dout, a.lse, a.delta, a.dk, a.dv, B, N, H, scale, bias_ld, l.win ? a.biasT : nullptr, plan.ldT, dr, Pn);
             break;
         default:
-            attn3_bwd_dkv_launch(l, plan.ldT, q, k, v, biasT, keymask, dout, lse, delta, dk, dv, B, N, H, scale, st, dr, Pn, dkv_part);
+            attn3_bwd_dkv_launch(l, plan.ldT, a.q, a.k, a.v, a.biasT, a.keymask, a.dout, a.lse, a.delta, a.dk, a.dv, B, N, H, scale, st, dr, Pn, dkv_part);
         }
         if (int rc = omlm_post_launch("omlm_mqa_attn_bwd")) return rc;
     }
     return OMLM_OK;
 }
+static int attn_run_here(AttnCall c, const AttnArgs& a) {
+    c.fp16_copy = OMLM_FP16 != 0;
+    const AttnPlan plan = omlm_plan::attn_plan(c);
+    if (plan.rc) { omlm_set_error(plan.msg); return plan.rc; }
+    AttnDrop dr = {0ull, nullptr, 0u, 1.0f};
+    if (c.drop) (void)attn_drop_args(a.p, a.seed, a.seed_dev, dr);      // (p: checked by the entry)
+    return c.backward ? attn_bwd_run_here(plan, c, a, dr) : attn_fwd_run_here(plan, c, a, dr);
+}
+
+static_assert(sizeof(AttnCall) == 36 && sizeof(AttnArgs) == 160, "AttnCall / AttnArgs: one layout in both copies");
+#if OMLM_FP16
+// the fp16 copy has one way in: a call the bf16 copy handed over (attn_to_fp16_copy)
+extern "C" __attribute__((visibility("hidden"))) int omlm_attn_run_h(const AttnCall* c, const AttnArgs* a) { return attn_run_here(*c, *a); }
+#else
+extern "C" int omlm_attn_run_h(const AttnCall* c, const AttnArgs* a);
+static int attn_run(AttnCall c, const AttnArgs& a) { return omlm_plan::attn_to_fp16_copy(c) ? omlm_attn_run_h(&c, &a) : attn_run_here(c, a); }
+
+// ---- the C entries (include/omlm.h).  dtype: 0 = fp32 ("bf16x3"), 1 = bf16, 2 = fp16 ----------------------------------------------------------------
+extern "C" int omlm_attn_max_positions(int dtype, int P) { return omlm_plan::attn_max_positions(dtype, P); }
+
+extern "C" int omlm_mqa_attn_fwd(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                 void* out, float* lse, int B, int N, int H, float scale, int bias_ld, int dtype, int P, float p,
+                                 unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+    AttnDrop d;
+    OMLM_CHECK_ARG(P >= 0, "prefix rows P >= 0");
+    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
+    if (B <= 0 || N <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(q && k && v && out && lse, "null pointer");
+    OMLM_CHECK_ARG(H >= 1 && (!bias || bias_ld >= H), "heads / bias pitch");
+    AttnArgs a = {};
+    a.q = q; a.k = k; a.v = v; a.bias = bias; a.biasT = biasT; a.keymask = keymask; a.out = out; a.lse = lse; a.scale = scale; a.bias_ld = bias_ld;
+    a.p = p; a.seed = seed; a.seed_dev = seed_dev; a.stream = stream;
+    return attn_run({false, dtype, false, B, N, H, P, bias != nullptr, biasT != nullptr, false, false, p > 0.f, false}, a);
+}
+
+// dq [B*N, H*64] fp32, dk, dv [B*N, 64] fp32 (overwritten), dbias [N, bias_ld] fp32 (accumulated, +=), delta [B, H, N] scratch.
+extern "C" int omlm_mqa_attn_bwd(const void* q, const void* k, const void* v, const float* bias, const float* biasT, const unsigned char* keymask,
+                                 const void* out, const void* dout, const float* lse, float* delta, float* dq, float* dk, float* dv,
+                                 float* dbias, float* dbias_ws, int B, int N, int H, float scale, int bias_ld, int dtype, int P,
+                                 float p, unsigned long long seed, const unsigned long long* seed_dev, void* stream) {
+    AttnDrop d;
+    OMLM_CHECK_ARG(P >= 0, "prefix rows P >= 0");
+    OMLM_CHECK_ARG(attn_drop_args(p, seed, seed_dev, d), "dropout p in [0, 1)");
+    if (B <= 0 || N <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(q && k && v && out && dout && lse && delta && dq && dk && dv, "null pointer");
+    OMLM_CHECK_ARG(H >= 1 && ((!bias && !dbias) || bias_ld >= H), "heads / bias pitch");
+    AttnArgs a = {};
+    a.q = q; a.k = k; a.v = v; a.bias = bias; a.biasT = biasT; a.keymask = keymask; a.out = const_cast<void*>(out); a.lse = const_cast<float*>(lse);      // (read only here)
+    a.dout = dout; a.delta = delta; a.dq = dq; a.dk = dk; a.dv = dv; a.dbias = dbias; a.dbias_ws = dbias_ws; a.scale = scale; a.bias_ld = bias_ld;
+    a.p = p; a.seed = seed; a.seed_dev = seed_dev; a.stream = stream;
+    return attn_run({true, dtype, false, B, N, H, P, bias != nullptr, biasT != nullptr, dbias != nullptr, dbias_ws != nullptr, p > 0.f,
+                     dv == dk + (size_t)B * N * 64}, a);
+}
+#endif
 
 }   // namespace OMLM_NS

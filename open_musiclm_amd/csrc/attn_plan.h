@@ -123,12 +123,31 @@ inline bool attn2_prefix_fits(int N, int Pn) { return N >= 32 && N <= ATTN_SHORT
 // ---- the call, and what it runs ------------------------------------------------------------------------------------------------------------
 struct AttnCall {
     bool backward;
-    bool fp32;              // fp32 operands ("bf16x3"); else the copy's 16-bit type
+    int dtype;              // as the copy sees it: 0 fp32 operands ("bf16x3"), anything else its 16-bit type (attn_to_fp16_copy below)
     bool fp16_copy;         // the fp16 copy of the three files: it builds no fp32 kernels
     int B, N, H, P;
     bool bias, biasT, dbias, ws;     // which of the raw table, the prepared table, d(bias) and the workspace are there
     bool drop;              // dropout p > 0
     bool dkv_adjacent;      // dv == dk + B N 64: one zero fill instead of two
+};
+// The bf16 copy holds the public entries and hands a call that names fp16 (dtype code 2) to the fp16 copy, which sees its 16-bit type as code 1.
+inline bool attn_to_fp16_copy(AttnCall& c) {
+    if (c.dtype != 2) return false;
+    c.dtype = 1;
+    return true;
+}
+// what the launch loops of attention.hip take next to the plan: the entry's pointers and scalars, filled once (host only: no kernel takes it)
+struct AttnArgs {
+    const void *q, *k, *v, *dout;
+    const float *bias, *biasT;
+    const unsigned char* keymask;
+    void* out;                       // (the backward reads it, and lse)
+    float *lse, *delta, *dq, *dk, *dv, *dbias, *dbias_ws;
+    float scale, p;                  // p, seed, seed_dev: dropout
+    int bias_ld;
+    unsigned long long seed;
+    const unsigned long long* seed_dev;
+    void* stream;
 };
 enum AttnFamily {
     ATTN_A1_FWD, ATTN_A1_DQ, ATTN_A1_DKV,      // attention.hip: attn_fwd_kernel, attn_bwd_dq_kernel / attn_bwd_dq_precise_kernel, attn_bwd_dkv_kernel
@@ -160,7 +179,7 @@ struct AttnPlan {
 inline void attn_push(AttnPlan& p, AttnFamily f, AttnForm form, const AttnCall& c, int gx, int gy, int gz, int threads, long long lds) {
     AttnLaunch& l = p.l[p.n++];
     memset(&l, 0, sizeof(l));
-    l.family = f; l.form = form; l.precise = c.fp32 && f <= ATTN_A1_DKV; l.pfx = c.P > 0; l.drop = c.drop;
+    l.family = f; l.form = form; l.precise = c.dtype == 0 && f <= ATTN_A1_DKV; l.pfx = c.P > 0; l.drop = c.drop;
     l.gx = gx; l.gy = gy; l.gz = gz; l.threads = threads; l.lds = lds;
 }
 inline AttnPlan& attn_refuse(AttnPlan& p) { p.rc = ATTN_UNSUPPORTED; p.n = 0; return p; }
@@ -169,7 +188,7 @@ inline AttnPlan& attn_refuse(AttnPlan& p) { p.rc = ATTN_UNSUPPORTED; p.n = 0; re
 inline bool attn_positions_ok(const AttnCall& c, const char* what, AttnPlan& p) {
     const int N = c.N, P = c.P, H = c.H;
     const char* dir = c.backward ? "backward" : "forward alone";
-    if (c.fp32) {
+    if (c.dtype == 0) {
         const int lim = attn1_limit(true, c.backward, P);
         if (N <= lim) return true;
         snprintf(p.msg, sizeof(p.msg), "%s: N = %d positions per sample with fp32 operands (bf16x3): their kernels keep the bias table in LDS and take "
@@ -203,7 +222,7 @@ inline bool attn_lds_ok(long long bytes, AttnPlan& p) {
 // SAME test forward and backward, whose lse is relative to the table's reference point there)
 inline bool attn_second_generation(const AttnCall& c) {
     const int Pn = attn_prefix_rows(c.N, c.P);
-    return !c.fp32 && (c.biasT || !c.bias) && (Pn == 0 || attn2_prefix_fits(c.N, Pn));
+    return c.dtype != 0 && (c.biasT || !c.bias) && (Pn == 0 || attn2_prefix_fits(c.N, Pn));
 }
 
 inline AttnPlan attn_plan(const AttnCall& c) {
@@ -213,7 +232,7 @@ inline AttnPlan attn_plan(const AttnCall& c) {
     const char* what = c.backward ? "omlm_mqa_attn_bwd" : "omlm_mqa_attn_fwd";
     const int B = c.B, N = c.N, H = c.H, Pn = attn_prefix_rows(N, c.P), off = attn_prefix_off(N, c.P);
     if (!attn_positions_ok(c, what, p)) return attn_refuse(p);
-    if (c.fp32 && c.fp16_copy) {
+    if (c.dtype == 0 && c.fp16_copy) {
         snprintf(p.msg, sizeof(p.msg), "%s: fp32 operands are served by the bf16 copy of the library", what);
         return attn_refuse(p);
     }
@@ -231,7 +250,7 @@ inline AttnPlan attn_plan(const AttnCall& c) {
             }
             return p;
         }
-        const long long lds = a1_fwd_lds(N, c.fp32, off);
+        const long long lds = a1_fwd_lds(N, c.dtype == 0, off);
         if (!attn_lds_ok(lds, p)) return attn_refuse(p);
         attn_push(p, ATTN_A1_FWD, ATTN_FORM_SHORT, c, nqt, (H + 3) / 4, B, 256, lds);
         return p;
@@ -246,7 +265,7 @@ inline AttnPlan attn_plan(const AttnCall& c) {
     const bool win = a1_dkv_windowed(N, H, Pn, c.biasT);
     const bool dq2 = gen2 && (lng || a2_dq_lds(N, off, false) <= ATTN_LDS_CAP);
     const bool dkv3 = gen2 && a3_serves(B, N, H);
-    const long long ldsq = a1_dq_lds(N, c.fp32, off), ldsk = win ? A1_DKV_WIN_LDS : a1_dkv_staged_lds(N, H, Pn > 0);
+    const long long ldsq = a1_dq_lds(N, c.dtype == 0, off), ldsk = win ? A1_DKV_WIN_LDS : a1_dkv_staged_lds(N, H, Pn > 0);
     // N > 4096, causal, with the prepared table or no bias: the long dQ kernel, and with a workspace the dK / dV kernel's slot form -- its slots
     // follow the d(bias) rows in the workspace.  Where the dK / dV kernel's 32-bit offsets refuse the shape, the first-generation kernel takes
     // over in its windowed mode, which needs the prepared table.
@@ -264,7 +283,7 @@ inline AttnPlan attn_plan(const AttnCall& c) {
     }
     // As found: the first-generation dK / dV kernel's LDS is checked for every causal call below the long forms, also where attention3.hip
     // serves the call and that kernel never runs (no table at all, H (N + 31) > 31000: refused although servable).
-    const bool dkv1_checked = c.fp32 || (!(gen2 && lng && !win) && (Pn == 0 || !gen2));
+    const bool dkv1_checked = c.dtype == 0 || (!(gen2 && lng && !win) && (Pn == 0 || !gen2));
     if ((!dq2 && !attn_lds_ok(ldsq, p)) || (dkv1_checked && !attn_lds_ok(ldsk, p))) return attn_refuse(p);
     if (dq2) attn_push(p, ATTN_A2_DQ, lng ? ATTN_FORM_LONG : ATTN_FORM_SHORT, c, nqt * ((H + 7) / 8) * B, 1, 1, 512, a2_dq_lds(N, off, lng));
     else attn_push(p, ATTN_A1_DQ, ATTN_FORM_SHORT, c, nqt, (H + 3) / 4, B, 256, ldsq);
@@ -294,10 +313,18 @@ inline AttnPlan attn_plan(const AttnCall& c) {
 }   // namespace omlm_plan
 
 #ifdef OMLM_PLAN_TEST_ABI       /* tests/test_attn_plan_host.py: the plan behind a flat C interface, built by the host c++ */
-// call: backward fp32 fp16_copy B N H P bias biasT dbias ws drop dkv_adjacent.  out: rc, n, ldT, dkv_slots, then 16 values per launch:
-// family form precise pfx drop fixed win gx gy gz threads lds CH wps which floats.  msg: 480 bytes.
+// call: backward operands copy B N H P bias biasT dbias ws drop dkv_adjacent.
+//   copy: 0 / 1 the call as the bf16 / fp16 copy sees it, operands != 0: fp32; 2 a call of the public entry: operands is its dtype code
+//   (attn_to_fp16_copy decides; omlm_plan_attn_fp16_copy: whether the fp16 copy serves the call).
+// out: rc, n, ldT, dkv_slots, then 16 values per launch: family form precise pfx drop fixed win gx gy gz threads lds CH wps which floats.
+// msg: 480 bytes.
+static omlm_plan::AttnCall omlm_plan_attn_call(const int* v) {
+    omlm_plan::AttnCall c = {v[0] != 0, v[2] == 2 ? v[1] : v[1] ? 0 : 1, v[2] == 1, v[3], v[4], v[5], v[6], v[7] != 0, v[8] != 0, v[9] != 0, v[10] != 0, v[11] != 0, v[12] != 0};
+    if (v[2] == 2) c.fp16_copy = omlm_plan::attn_to_fp16_copy(c);
+    return c;
+}
 extern "C" void omlm_plan_attn(const int* v, long long* out, char* msg) {
-    const omlm_plan::AttnCall c = {v[0] != 0, v[1] != 0, v[2] != 0, v[3], v[4], v[5], v[6], v[7] != 0, v[8] != 0, v[9] != 0, v[10] != 0, v[11] != 0, v[12] != 0};
+    const omlm_plan::AttnCall c = omlm_plan_attn_call(v);
     const omlm_plan::AttnPlan p = omlm_plan::attn_plan(c);
     out[0] = p.rc; out[1] = p.n; out[2] = p.ldT; out[3] = p.dkv_slots;
     for (int i = 0; i < p.n; ++i) {
@@ -307,11 +334,9 @@ extern "C" void omlm_plan_attn(const int* v, long long* out, char* msg) {
     }
     memcpy(msg, p.msg, sizeof(p.msg));
 }
+extern "C" int omlm_plan_attn_fp16_copy(const int* v) { return omlm_plan_attn_call(v).fp16_copy; }
 extern "C" long long omlm_plan_attn_table_floats(int N, int H, int P) { return omlm_plan::attn_bias_table_floats(N, H, P); }
 extern "C" long long omlm_plan_attn_workspace_bytes(int B, int N, int H) { return omlm_plan::attn_bwd_workspace_bytes(B, N, H); }
 extern "C" int omlm_plan_attn_max_positions(int dtype, int P) { return omlm_plan::attn_max_positions(dtype, P); }
-extern "C" int omlm_plan_attn_second_generation(const int* v) {
-    const omlm_plan::AttnCall c = {v[0] != 0, v[1] != 0, v[2] != 0, v[3], v[4], v[5], v[6], v[7] != 0, v[8] != 0, v[9] != 0, v[10] != 0, v[11] != 0, v[12] != 0};
-    return omlm_plan::attn_second_generation(c);
-}
+extern "C" int omlm_plan_attn_second_generation(const int* v) { return omlm_plan::attn_second_generation(omlm_plan_attn_call(v)); }
 #endif

@@ -21,6 +21,15 @@ extern "C" void omlm_set_error(const char* msg);
         }                                                                             \
     } while (0)
 
+// the same with the whole text given: a check whose condition is no longer spelled the way its message has always quoted it
+#define OMLM_CHECK_ARG_AS(cond, text)                                                 \
+    do {                                                                              \
+        if (!(cond)) {                                                                \
+            omlm_set_error("bad argument: " text);                                    \
+            return OMLM_ERR_ARG;                                                      \
+        }                                                                             \
+    } while (0)
+
 static inline int omlm_post_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
@@ -65,23 +74,23 @@ static inline void with_flags(bool a, bool b, F&& f) {
 // Every source that touches 16-bit operands is compiled TWICE: once with h16_t = bf16 (precision "bf16"; also hosts the fp32 /
 // "bf16x3" instantiations) and once with -DOMLM_FP16=1, h16_t = IEEE half (precision "fp16": same v_mfma_f32_32x32x16 rate, 11
 // instead of 8 significand bits).  The two copies live in different namespaces (kernel host stubs of the same name must not
-// merge) and the fp16 copy's entry points are hidden `<name>_h` functions that the public entry point forwards to when it is
-// handed dtype code 2 (OMLM_DT_F16), so include/omlm.h has ONE function per operation.
+// merge).  The C entries of include/omlm.h exist once, in the bf16 copy.  Each fills its family's argument block and call struct; a pure
+// rule next to the call struct (`<family>_to_fp16_copy`, in the plan header) says whether the call names fp16 (dtype code 2, OMLM_DT_F16)
+// and rewrites that code to 1, the 16-bit type as the fp16 copy sees it; such a call is handed, as pointers to the two blocks, to the ONE
+// hidden function `omlm_<family>_run_h` that the fp16 copy of the file defines.  No member of a block that crosses has a type that
+// depends on OMLM_FP16 (each file static_asserts the sizes in both copies).
 #ifndef OMLM_FP16
 #define OMLM_FP16 0
 #endif
 #define OMLM_DT_F32 0
 #define OMLM_DT_BF16 1
 #define OMLM_DT_F16 2
-// dtype code as the fp16 copy sees it: its 16-bit type is "code 1" there
-#define OMLM_H_CODE(c) ((c) == OMLM_DT_F16 ? 1 : (c))
 #if OMLM_FP16
 typedef _Float16 h16_t;
 typedef __attribute__((ext_vector_type(8))) _Float16 h16x8;
 typedef __attribute__((ext_vector_type(4))) _Float16 h16x4;
 typedef __attribute__((ext_vector_type(2))) _Float16 h16x2;
 #define OMLM_NS omlm_f16
-#define OMLM_API(name) __attribute__((visibility("hidden"))) name##_h
 #define OMLM_MFMA_32x32x16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
 #define OMLM_MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 #else
@@ -90,7 +99,6 @@ typedef __attribute__((ext_vector_type(8))) __bf16 h16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 h16x4;
 typedef __attribute__((ext_vector_type(2))) __bf16 h16x2;
 #define OMLM_NS omlm_bf16
-#define OMLM_API(name) name
 #define OMLM_MFMA_32x32x16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_bf16((a), (b), (c), 0, 0, 0)
 #define OMLM_MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 #endif

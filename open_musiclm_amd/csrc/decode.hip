@@ -1439,16 +1439,14 @@ __global__ __launch_bounds__(DEC4_T) void dec4_kernel(dec2_args a) {
 // lists.  Order of first use: the kernels stand in the module in the order in which the functions below name them, and the compiled
 // kernels depend on it (as sampler.hip notes for its own): the families in the order of decode_launch's switch, inside a family the order of
 // its switch.  tools/sampler_isa_diff.py compares every kernel with its predecessor's.
-using omlm_plan::DecodeCall;
-using omlm_plan::DecodeLaunch;
-using omlm_plan::DecodePlan;
+using omlm_plan::DecodeCall; using omlm_plan::DecodeLaunch; using omlm_plan::DecodePlan;
 static_assert(omlm_plan::DEC_ERR_ARG == OMLM_ERR_ARG && omlm_plan::DEC_LDS_CAP == 160 * 1024, "decode_plan.h states the return code and launch_lds_cap's size");
 
 static DecodeCall decode_call(const omlm_decode_args& a, const long long* ids, bool masked, const unsigned char* key_live) {
     DecodeCall c;
     memset(&c, 0, sizeof(c));
     c.B = a.B; c.D = a.D; c.H = a.H; c.L = a.L; c.Fp = a.Fp; c.Nmax = a.Nmax; c.nsplit = a.nsplit; c.V1 = a.V1;
-    c.w_dtype = a.w_dtype; c.fp16_copy = OMLM_FP16 != 0; c.round_bf16 = a.round_bf16 != 0; c.kv16 = a.kv16 != 0;
+    c.w_dtype = a.w_dtype; c.round_bf16 = a.round_bf16 != 0; c.kv16 = a.kv16 != 0;
     c.pos_dev = a.pos_dev != nullptr; c.parts = a.parts != nullptr; c.ids = ids != nullptr; c.emb_table = a.emb_table != nullptr;
     c.head_W = a.head_W != nullptr; c.ln_parts = a.ln_parts != nullptr; c.splitk_ws = a.splitk_ws != nullptr; c.splitk_cnt = a.splitk_cnt != nullptr;
     c.W1p_lo = a.W1p_lo != nullptr; c.W2p_lo = a.W2p_lo != nullptr; c.head_W_lo = a.head_W_lo != nullptr; c.k_new = a.k_new != nullptr;
@@ -1570,14 +1568,7 @@ static bool dec4_go(const DecodeLaunch& k, const dec2_args& g, hipStream_t st) {
 __global__ void dec_advance_kernel(int* pos_dev, int* step_dev) {
     if (threadIdx.x == 0) { if (pos_dev) pos_dev[0] += 1; if (step_dev) step_dev[0] += 1; }
 }
-#if OMLM_FP16
-extern "C" int omlm_decode_advance(int* pos_dev, int* step_dev, void* stream);      // bf16 copy of this file
-#else
-extern "C" int omlm_decode_advance(int* pos_dev, int* step_dev, void* stream) {
-    hipLaunchKernelGGL(dec_advance_kernel, dim3(1), dim3(64), 0, as_stream(stream), pos_dev, step_dev);
-    return omlm_post_launch("omlm_decode_advance");
-}
-#endif
+extern "C" int omlm_decode_advance(int* pos_dev, int* step_dev, void* stream);      // exists once, in the bf16 copy (with the other C entries below)
 
 // One launch of the plan, in layer l.  false: see above.
 template <typename TW>
@@ -1682,38 +1673,45 @@ static int decode_run(const DecodePlan& p, const omlm_decode_args& a, const long
     return rc;
 }
 
+// plan, then launch.  c: the call as this copy sees it (w_dtype: 0 fp32 weights, 1 the copy's 16-bit type)
+static int decode_run_here(DecodeCall c, const omlm_decode_args& a, const long long* ids, const unsigned char* key_live, void* stream) {
+    c.fp16_copy = OMLM_FP16 != 0;
+    const DecodePlan plan = omlm_plan::decode_plan(c);
+    if (plan.rc != OMLM_OK) { omlm_set_error(plan.msg); return plan.rc; }
+#if !OMLM_FP16
+    if (c.w_dtype == 0) return decode_run<float>(plan, a, ids, stream, key_live);
+#endif
+    return decode_run<h16_t>(plan, a, ids, stream, key_live);
+}
+
+static_assert(sizeof(DecodeCall) == 56 && sizeof(omlm_decode_args) == 360, "DecodeCall / omlm_decode_args: one layout in both copies");
+#if OMLM_FP16
+// the fp16 copy has one way in: a call the bf16 copy handed over (decode_to_fp16_copy)
+extern "C" __attribute__((visibility("hidden")))
+int omlm_decode_run_h(const DecodeCall* c, const omlm_decode_args* a, const long long* ids, const unsigned char* key_live, void* stream) { return decode_run_here(*c, *a, ids, key_live, stream); }
+#else
+extern "C" int omlm_decode_run_h(const DecodeCall* c, const omlm_decode_args* a, const long long* ids, const unsigned char* key_live, void* stream);
+extern "C" int omlm_decode_advance(int* pos_dev, int* step_dev, void* stream) {
+    hipLaunchKernelGGL(dec_advance_kernel, dim3(1), dim3(64), 0, as_stream(stream), pos_dev, step_dev);
+    return omlm_post_launch("omlm_decode_advance");
+}
+
 // One decode step for the row at index *pos_dev (see include/omlm.h).  ids: [B] int64 sampled in the previous step (used
 // when a->emb_table is set; otherwise a->x already holds the new row's embedding).  *pos_dev is advanced only through
 // a->advance_pos / a->advance_step (optional device counters bumped by the step's last kernel; pass pos_dev there to move on).
 // a->w_dtype: 0 = fp32 weights, 1 = bf16, 2 = fp16 (served by the fp16 copy of this file; a->round_bf16 then rounds to fp16).
 // A refusal is returned before anything is launched.
-#if !OMLM_FP16
-extern "C" int omlm_decode_step_h(const omlm_decode_args* a, const long long* ids, void* stream);
-extern "C" int omlm_decode_step_masked_h(const omlm_decode_args* a, const unsigned char* key_live, const long long* ids, void* stream);
-#endif
 // masked: omlm_decode_step_masked's call (the attention launches read key_live)
 static int decode_step(const omlm_decode_args* a, const long long* ids, void* stream, bool masked, const unsigned char* key_live) {
     OMLM_CHECK_ARG(a != nullptr, "null argument block");
-#if !OMLM_FP16
-    if (a->w_dtype == OMLM_DT_F16) {
-        omlm_decode_args b = *a;
-        b.w_dtype = 1;
-        return masked ? omlm_decode_step_masked_h(&b, key_live, ids, stream) : omlm_decode_step_h(&b, ids, stream);
-    }
-#endif
-    const DecodePlan plan = omlm_plan::decode_plan(decode_call(*a, ids, masked, key_live));
-    if (plan.rc != OMLM_OK) { omlm_set_error(plan.msg); return plan.rc; }
-#if !OMLM_FP16
-    if (a->w_dtype == 0) return decode_run<float>(plan, *a, ids, stream, key_live);
-#endif
-    return decode_run<h16_t>(plan, *a, ids, stream, key_live);
+    DecodeCall c = decode_call(*a, ids, masked, key_live);
+    return omlm_plan::decode_to_fp16_copy(c) ? omlm_decode_run_h(&c, a, ids, key_live, stream) : decode_run_here(c, *a, ids, key_live, stream);
 }
-extern "C" int OMLM_API(omlm_decode_step)(const omlm_decode_args* a, const long long* ids, void* stream) {
-    return decode_step(a, ids, stream, false, nullptr);
-}
+extern "C" int omlm_decode_step(const omlm_decode_args* a, const long long* ids, void* stream) { return decode_step(a, ids, stream, false, nullptr); }
 // omlm_decode_step under the key mask key_live[B, Nmax] (include/omlm.h): the masked attention kernels in place of the plain ones.
-extern "C" int OMLM_API(omlm_decode_step_masked)(const omlm_decode_args* a, const unsigned char* key_live, const long long* ids, void* stream) {
+extern "C" int omlm_decode_step_masked(const omlm_decode_args* a, const unsigned char* key_live, const long long* ids, void* stream) {
     return decode_step(a, ids, stream, true, key_live);
 }
+#endif
 
 }   // namespace OMLM_NS

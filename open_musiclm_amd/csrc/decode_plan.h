@@ -89,7 +89,7 @@ static inline long long dec4_lds(int NS, bool PL, int B, int K, int nsl, bool ga
 // ---- the call, and what it runs --------------------------------------------------------------------------------------------------------------
 struct DecodeCall {
     int B, D, H, L, Fp, Nmax, nsplit, V1;
-    int w_dtype;            // as the copy sees it: 0 fp32, else its 16-bit type (the bf16 copy forwards fp16 weights to the fp16 copy as 1)
+    int w_dtype;            // as the copy sees it: 0 fp32, else its 16-bit type (decode_to_fp16_copy below)
     bool fp16_copy;         // the fp16 copy of decode.hip: it builds no fp32-weight kernels
     bool round_bf16, kv16;
     // which of the optional pointers are there
@@ -98,6 +98,13 @@ struct DecodeCall {
     // route, grids, LDS bytes, every other launch -- is the unmasked call's
     bool masked, key_live;
 };
+// The bf16 copy holds the public entries and hands a call whose weights are fp16 (w_dtype code 2) to the fp16 copy, which sees its 16-bit
+// type as code 1.
+inline bool decode_to_fp16_copy(DecodeCall& c) {
+    if (c.w_dtype != 2) return false;
+    c.w_dtype = 1;
+    return true;
+}
 enum DecodeRoute { DEC_GEN1, DEC_DEC3, DEC_DEC2, DEC_DEC4 };      // first generation; second: row kernels (B = 1), vector kernels, matrix-core kernels
 enum DecodeKernel {
     DK_EMBED, DK_ROWSTAT,                               // dec_embed_kernel, dec_rowstat_kernel
@@ -274,14 +281,18 @@ static inline DecodePlan decode_plan(const DecodeCall& c) {
 }   // namespace omlm_plan
 
 #ifdef OMLM_PLAN_TEST_ABI       /* tests/test_decode_plan_host.py: the plan behind a flat C interface, built by the host c++ */
-// call: B D H L Fp Nmax nsplit V1 w_dtype fp16_copy round_bf16 kv16, then one flag per pointer: pos_dev parts ids emb_table head_W ln_parts
-// splitk_ws splitk_cnt W1p_lo W2p_lo head_W_lo k_new advance_pos.  out: rc route G region npd npf stat_x stat_x1 stat_u split comb_in_attn
-// rowstat advance n layer tail, then 16 values per launch (l[0 .. n), then q_rest): kernel phase w16 c16 n mode pl grp gx gy threads lds nsl
-// nstat_in gtiles unrounded.  msg: 320 bytes.  omlm_plan_decode: masked off.  omlm_plan_decode_masked: the plan of omlm_decode_step_masked for
+// call: B D H L Fp Nmax nsplit V1 w_dtype copy round_bf16 kv16, then one flag per pointer: pos_dev parts ids emb_table head_W ln_parts
+// splitk_ws splitk_cnt W1p_lo W2p_lo head_W_lo k_new advance_pos.
+//   copy: 0 / 1 the call as the bf16 / fp16 copy sees it; 2 a call of the public entry (decode_to_fp16_copy decides).
+// out: rc route G region npd npf stat_x stat_x1 stat_u split comb_in_attn rowstat advance n layer tail, then 16 values per launch (l[0 .. n),
+// then q_rest): kernel phase w16 c16 n mode pl grp gx gy threads lds nsl nstat_in gtiles unrounded.  msg: 320 bytes.
+// omlm_plan_decode_fp16_copy: whether the fp16 copy serves the call.  omlm_plan_decode: masked off.  omlm_plan_decode_masked: the plan of omlm_decode_step_masked for
 // the same 25 values, key_live given or not; same output format.
 static omlm_plan::DecodeCall omlm_plan_decode_call(const int* v, bool masked, bool key_live) {
-    return {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9] != 0, v[10] != 0, v[11] != 0, v[12] != 0, v[13] != 0, v[14] != 0, v[15] != 0,
-            v[16] != 0, v[17] != 0, v[18] != 0, v[19] != 0, v[20] != 0, v[21] != 0, v[22] != 0, v[23] != 0, v[24] != 0, masked, key_live};
+    omlm_plan::DecodeCall c = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9] == 1, v[10] != 0, v[11] != 0, v[12] != 0, v[13] != 0, v[14] != 0,
+                               v[15] != 0, v[16] != 0, v[17] != 0, v[18] != 0, v[19] != 0, v[20] != 0, v[21] != 0, v[22] != 0, v[23] != 0, v[24] != 0, masked, key_live};
+    if (v[9] == 2) c.fp16_copy = omlm_plan::decode_to_fp16_copy(c);
+    return c;
 }
 static void omlm_plan_decode_out(const omlm_plan::DecodePlan& p, long long* out, char* msg) {
     const long long h[16] = {p.rc, p.route, p.G, p.region, p.npd, p.npf, p.stat_x, p.stat_x1, p.stat_u, p.split, p.comb_in_attn, p.rowstat,
@@ -294,6 +305,7 @@ static void omlm_plan_decode_out(const omlm_plan::DecodePlan& p, long long* out,
     }
     memcpy(msg, p.msg, sizeof(p.msg));
 }
+extern "C" int omlm_plan_decode_fp16_copy(const int* v) { return omlm_plan_decode_call(v, false, false).fp16_copy; }
 extern "C" void omlm_plan_decode(const int* v, long long* out, char* msg) { omlm_plan_decode_out(omlm_plan::decode_plan(omlm_plan_decode_call(v, false, false)), out, msg); }
 extern "C" void omlm_plan_decode_masked(const int* v, int key_live, long long* out, char* msg) {
     omlm_plan_decode_out(omlm_plan::decode_plan(omlm_plan_decode_call(v, true, key_live != 0)), out, msg);

@@ -553,38 +553,9 @@ __global__ void colsum_group_kernel(ColsumGroupArgs ga) {
     if (p1 > p0) unsafeAtomicAdd(q.out + c, s);
 }
 
-#if OMLM_FP16
-extern "C" int omlm_colsum_accumulate(const float* part, float* out, int P, int C, int ldp, void* stream);     // bf16 copy
+// omlm_colsum_accumulate / omlm_colsum_group exist once, in the bf16 copy (with the other C entries, at the end of this file)
+extern "C" int omlm_colsum_accumulate(const float* part, float* out, int P, int C, int ldp, void* stream);
 extern "C" int omlm_colsum_group(const omlm_colsum_desc* d, int count, void* stream);
-#else
-extern "C" int omlm_colsum_group(const omlm_colsum_desc* d, int count, void* stream) {
-    if (count <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(d, "colsum_group: null descriptor array");
-    for (int base = 0; base < count; base += OMLM_COLSUM_MAX) {
-        ColsumGroupArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.n = count - base < OMLM_COLSUM_MAX ? count - base : OMLM_COLSUM_MAX;
-        int cmax = 0, pmax = 0;
-        for (int i = 0; i < ga.n; ++i) {
-            const omlm_colsum_desc& q = d[base + i];
-            OMLM_CHECK_ARG(q.part && q.out && q.P > 0 && q.C > 0 && q.ldp >= q.C, "colsum_group: bad problem");
-            ga.p[i] = q;
-            if (q.C > cmax) cmax = q.C;
-            if (q.P > pmax) pmax = q.P;
-        }
-        hipLaunchKernelGGL(colsum_group_kernel, dim3((cmax + 255) / 256, colsum_ysplit(pmax), ga.n), dim3(256), 0, as_stream(stream), ga);
-    }
-    return omlm_post_launch("omlm_colsum_group");
-}
-
-extern "C" int omlm_colsum_accumulate(const float* part, float* out, int P, int C, int ldp, void* stream) {
-    if (P <= 0 || C <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(part && out && ldp >= C, "colsum arguments");
-    hipLaunchKernelGGL(colsum_kernel, dim3((C + 255) / 256, colsum_ysplit(P)), dim3(256), 0, as_stream(stream), part, out, P, C, ldp);
-    return omlm_post_launch("omlm_colsum_accumulate");
-}
-
-#endif
 
 // ---- host side: csrc/ffmid_plan.h decides what a call runs; the launcher below runs this file's kernels, ffmid2.hip's launcher the strip kernels ----
 static_assert(FF_ERR_ARG == OMLM_ERR_ARG && FF_LDS_CAP == 160 * 1024 && FF_LDS_OPT_IN == 48 * 1024, "ffmid_plan.h states the return code and launch_lds_optin's sizes");
@@ -641,7 +612,8 @@ static int ffmid_launch(const FfmidLaunch& l, const FfmidArgs& a) {
 }
 
 // plan, then launch in order
-static int ffmid_run(const FfmidCall& c, const FfmidArgs& a) {
+static int ffmid_run_here(FfmidCall c, const FfmidArgs& a) {
+    c.fp16_copy = OMLM_FP16 != 0;
     const FfmidPlan plan = ffmid_plan(c);
     if (plan.rc != OMLM_OK) { omlm_set_error(plan.msg); return plan.rc; }
     for (int i = 0; i < plan.n; ++i) {
@@ -651,29 +623,61 @@ static int ffmid_run(const FfmidCall& c, const FfmidArgs& a) {
     return OMLM_OK;
 }
 
+// the two blocks cross from the bf16 copy to the fp16 copy: no member's type depends on the copy
+static_assert(sizeof(FfmidCall) == 64 && sizeof(FfmidArgs) == 224, "FfmidCall / FfmidArgs: one layout in both copies");
+#if OMLM_FP16
+// the fp16 copy has one way in: a call the bf16 copy handed over (ffmid_to_fp16_copy)
+extern "C" __attribute__((visibility("hidden"))) int omlm_ffmid_run_h(const FfmidCall* c, const FfmidArgs* a) { return ffmid_run_here(*c, *a); }
+#else
+extern "C" int omlm_ffmid_run_h(const FfmidCall* c, const FfmidArgs* a);
+static int ffmid_run(FfmidCall c, const FfmidArgs& a) { return ffmid_to_fp16_copy(c) ? omlm_ffmid_run_h(&c, &a) : ffmid_run_here(c, a); }
+
+extern "C" int omlm_colsum_group(const omlm_colsum_desc* d, int count, void* stream) {
+    if (count <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(d, "colsum_group: null descriptor array");
+    for (int base = 0; base < count; base += OMLM_COLSUM_MAX) {
+        ColsumGroupArgs ga;
+        memset(&ga, 0, sizeof(ga));
+        ga.n = count - base < OMLM_COLSUM_MAX ? count - base : OMLM_COLSUM_MAX;
+        int cmax = 0, pmax = 0;
+        for (int i = 0; i < ga.n; ++i) {
+            const omlm_colsum_desc& q = d[base + i];
+            OMLM_CHECK_ARG(q.part && q.out && q.P > 0 && q.C > 0 && q.ldp >= q.C, "colsum_group: bad problem");
+            ga.p[i] = q;
+            if (q.C > cmax) cmax = q.C;
+            if (q.P > pmax) pmax = q.P;
+        }
+        hipLaunchKernelGGL(colsum_group_kernel, dim3((cmax + 255) / 256, colsum_ysplit(pmax), ga.n), dim3(256), 0, as_stream(stream), ga);
+    }
+    return omlm_post_launch("omlm_colsum_group");
+}
+
+extern "C" int omlm_colsum_accumulate(const float* part, float* out, int P, int C, int ldp, void* stream) {
+    if (P <= 0 || C <= 0) return OMLM_OK;
+    OMLM_CHECK_ARG(part && out && ldp >= C, "colsum arguments");
+    hipLaunchKernelGGL(colsum_kernel, dim3((C + 255) / 256, colsum_ysplit(P)), dim3(256), 0, as_stream(stream), part, out, P, C, ldp);
+    return omlm_post_launch("omlm_colsum_accumulate");
+}
+
 // 1 (default): the column-strip kernels (both operand dtypes) where their preconditions hold; 0: the wave-per-row kernels.  Set by
 // omlm_ffmid_set_impl (tests); one variable for the library, read once per call into FfmidCall.  The two generations share every buffer
 // layout; their dropout streams differ (the keep-mask travels from forward to backward as drop_bits, so a step may not mix them only when
 // drop_bits is null).
-#if !OMLM_FP16
-extern "C" { __attribute__((visibility("hidden"))) int omlm_ffmid_impl_value = 1; }
+static int ffmid_impl_value = 1;
 extern "C" int omlm_ffmid_set_impl(int impl) {
     OMLM_CHECK_ARG(impl == 0 || impl == 1, "impl: 0 = wave-per-row, 1 = column strips");
-    omlm_ffmid_impl_value = impl;
+    ffmid_impl_value = impl;
     return OMLM_OK;
 }
 extern "C" long long omlm_ffmid_bwd_workspace_bytes(int F, int Fp) { return ffmid_bwd_workspace_bytes(F, Fp); }
-#else
-extern "C" { extern __attribute__((visibility("hidden"))) int omlm_ffmid_impl_value; }
-#endif
 
 // the call of an entry whose arguments are in `a`; operands: every pointer the entry requires is there
 static FfmidCall ffmid_call(FfOp op, const FfmidArgs& a, int dtype, bool operands) {
     FfmidCall c;
     memset(&c, 0, sizeof(c));
-    c.op = op; c.M = a.M; c.nseq = a.nseq; c.F = a.F; c.Fp = a.Fp; c.dtype = dtype; c.fp16_copy = OMLM_FP16 != 0; c.p = a.p; c.operands = operands;
+    c.op = op; c.M = a.M; c.nseq = a.nseq; c.F = a.F; c.Fp = a.Fp; c.dtype = dtype; c.p = a.p; c.operands = operands;
     c.drop_bits = a.drop_bits != nullptr; c.gh = a.gh != nullptr; c.dgamma = a.dgamma != nullptr; c.dconv = a.dconv != nullptr;
-    c.n_full = a.n_full; c.p0 = a.p0; c.h2_8_stride = a.h2_8_stride; c.impl = omlm_ffmid_impl_value;
+    c.n_full = a.n_full; c.p0 = a.p0; c.h2_8_stride = a.h2_8_stride; c.impl = ffmid_impl_value;
     return c;
 }
 static bool ffmid_aligned16(std::initializer_list<const void*> ps) {
@@ -682,21 +686,13 @@ static bool ffmid_aligned16(std::initializer_list<const void*> ps) {
     return all % 16 == 0;
 }
 
-// dtype: 0 = fp32 operands ("bf16x3"), 1 = bf16, 2 = fp16 (forwarded to the fp16 copy of this file)
+// ---- the C entries (include/omlm.h).  dtype: 0 = fp32 operands ("bf16x3"), 1 = bf16, 2 = fp16 ---------------------------------------------------
 // Every forward entry exists in a `_seg` form that carries a row segment (n_full, p0; n_full == 0: none): the buffers hold rows [p0, n_full)
 // of every sample compact (nseq = n_full - p0), and the strip kernels draw the keep bits those rows have in a launch over the full buffer
 // (a compact launch then drops exactly what the full launch drops for the same tokens).  The plain entries are the `_seg` ones without a segment.
-#if !OMLM_FP16
-extern "C" int omlm_ffmid_fwd_seg_h(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
-                                    int M, int nseq, int F, int Fp, float eps, float p, unsigned long long seed,
-                                    const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, int n_full, int p0, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_ffmid_fwd_seg)(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
-                              int M, int nseq, int F, int Fp, float eps, float p, unsigned long long seed,
-                              const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, int n_full, int p0, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16) return omlm_ffmid_fwd_seg_h(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, 1, n_full, p0, stream);
-#endif
+extern "C" int omlm_ffmid_fwd_seg(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
+                                  int M, int nseq, int F, int Fp, float eps, float p, unsigned long long seed,
+                                  const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, int n_full, int p0, void* stream) {
     FfmidArgs a;
     memset(&a, 0, sizeof(a));
     a.h1 = h1; a.convw = convw; a.gamma = gamma; a.h2 = h2; a.mean = mean; a.rstd = rstd;
@@ -704,32 +700,19 @@ extern "C" int OMLM_API(omlm_ffmid_fwd_seg)(const void* h1, const void* convw, c
     a.n_full = n_full; a.p0 = p0; a.stream = stream;
     return ffmid_run(ffmid_call(FF_FWD, a, dtype, h1 && convw && gamma && h2 && mean && rstd), a);
 }
-#if !OMLM_FP16
 extern "C" int omlm_ffmid_fwd(const void* h1, const void* convw, const void* gamma, void* h2, float* mean, float* rstd,
                               int M, int nseq, int F, int Fp, float eps, float p, unsigned long long seed,
                               const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype, void* stream) {
     return omlm_ffmid_fwd_seg(h1, convw, gamma, h2, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, dtype, 0, 0, stream);
 }
-#endif
 
 // The same forward on hi/lo planes of the 16-bit type `dtype` (1 = bf16, 2 = fp16; precision "fp16ff"): h1, the conv taps and gamma are read
 // as hi + lo (each *_lo plane has its hi plane's layout), h2 leaves as planes h2 = rne16(y), h2_lo = rne16(y - h2); gh, the statistics and
 // the keep bits as in omlm_ffmid_fwd.  The strip kernels only (Fp <= 4096, drop_bits present when p > 0).
-#if !OMLM_FP16
-extern "C" int omlm_ffmid_fwd_planes_seg_h(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
-                                           void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp, float eps, float p,
-                                           unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh, int dtype,
-                                           int n_full, int p0, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_ffmid_fwd_planes_seg)(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma,
-                                               const void* gamma_lo, void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp,
-                                               float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
-                                               unsigned char* drop_bits, void* gh, int dtype, int n_full, int p0, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16)
-        return omlm_ffmid_fwd_planes_seg_h(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh, 1,
-                                           n_full, p0, stream);
-#endif
+extern "C" int omlm_ffmid_fwd_planes_seg(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma,
+                                         const void* gamma_lo, void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp,
+                                         float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
+                                         unsigned char* drop_bits, void* gh, int dtype, int n_full, int p0, void* stream) {
     FfmidArgs a;
     memset(&a, 0, sizeof(a));
     a.h1 = h1; a.h1_lo = h1_lo; a.convw = convw; a.convw_lo = convw_lo; a.gamma = gamma; a.gamma_lo = gamma_lo; a.h2 = h2; a.h2_lo = h2_lo;
@@ -739,7 +722,6 @@ extern "C" int OMLM_API(omlm_ffmid_fwd_planes_seg)(const void* h1, const void* h
     c.planes_aligned = ffmid_aligned16({h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo});
     return ffmid_run(c, a);
 }
-#if !OMLM_FP16
 extern "C" int omlm_ffmid_fwd_planes(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma,
                                      const void* gamma_lo, void* h2, void* h2_lo, float* mean, float* rstd, int M, int nseq, int F, int Fp,
                                      float eps, float p, unsigned long long seed, const unsigned long long* seed_dev,
@@ -747,18 +729,15 @@ extern "C" int omlm_ffmid_fwd_planes(const void* h1, const void* h1_lo, const vo
     return omlm_ffmid_fwd_planes_seg(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_lo, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev, drop_bits, gh,
                                      dtype, 0, 0, stream);
 }
-#endif
 
-#if OMLM_FP16
-// The plane forward with h2 leaving in omlm_gemm_mx16's operand form (round 6): the half hi plane h2 [M, Fp], fp8 planes [hi8 | lo8] at row pitch
-// 2 Fp bytes (the lo8 plane h2_8_stride bytes behind the hi8 plane) and one E8M0 scale byte per row; h1's lo plane arrives as bf8 bytes
-// (h1_lo, at h1's element pitch: what omlm_gemm_mx16 writes with c_lo_bf8); everything else as omlm_ffmid_fwd_planes.
-}   // namespace OMLM_NS
+// The plane forward with h2 leaving in omlm_gemm_mx16's operand form (round 6; fp16 only, so the call always goes to the fp16 copy): the half hi
+// plane h2 [M, Fp], fp8 planes [hi8 | lo8] at row pitch 2 Fp bytes (the lo8 plane h2_8_stride bytes behind the hi8 plane) and one E8M0 scale
+// byte per row; h1's lo plane arrives as bf8 bytes (h1_lo, at h1's element pitch: what omlm_gemm_mx16 writes with c_lo_bf8); everything else
+// as omlm_ffmid_fwd_planes.
 extern "C" int omlm_ffmid_fwd_mx_seg(const void* h1, const void* h1_lo, const void* convw, const void* convw_lo, const void* gamma, const void* gamma_lo,
-                                 void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
-                                 float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh,
-                                 int n_full, int p0, void* stream) {
-    using namespace OMLM_NS;
+                                     void* h2, void* h2_8, long long h2_8_stride, unsigned char* scale8, float* mean, float* rstd, int M, int nseq, int F, int Fp,
+                                     float eps, float p, unsigned long long seed, const unsigned long long* seed_dev, unsigned char* drop_bits, void* gh,
+                                     int n_full, int p0, void* stream) {
     FfmidArgs a;
     memset(&a, 0, sizeof(a));
     a.h1 = h1; a.h1_lo = h1_lo; a.convw = convw; a.convw_lo = convw_lo; a.gamma = gamma; a.gamma_lo = gamma_lo; a.h2 = h2; a.h2_8 = h2_8;
@@ -775,28 +754,14 @@ extern "C" int omlm_ffmid_fwd_mx(const void* h1, const void* h1_lo, const void* 
     return omlm_ffmid_fwd_mx_seg(h1, h1_lo, convw, convw_lo, gamma, gamma_lo, h2, h2_8, h2_8_stride, scale8, mean, rstd, M, nseq, F, Fp, eps, p, seed, seed_dev,
                                  drop_bits, gh, 0, 0, stream);
 }
-namespace OMLM_NS {
-#endif
 
 // du_tmp: [M, 2*Fp] scratch of the operand dtype; dh1: [M, 2*Fp] output; workspace: omlm_ffmid_bwd_workspace_bytes.
 // dgamma [F], dconv [2F*3] are accumulated into (+=).
-#if !OMLM_FP16
-extern "C" int omlm_ffmid_bwd_h(const void* dh2, const void* h1, const void* convw, const void* gamma, const float* mean,
-                                const float* rstd, void* du_tmp, void* dh1, float* dgamma, float* dconv, float* workspace,
-                                int M, int nseq, int F, int Fp, float p, unsigned long long seed,
-                                const unsigned long long* seed_dev, const unsigned char* drop_bits, const void* gh, int dtype,
-                                void* stream);
-#endif
-extern "C" int OMLM_API(omlm_ffmid_bwd)(const void* dh2, const void* h1, const void* convw, const void* gamma, const float* mean,
+extern "C" int omlm_ffmid_bwd(const void* dh2, const void* h1, const void* convw, const void* gamma, const float* mean,
                               const float* rstd, void* du_tmp, void* dh1, float* dgamma, float* dconv, float* workspace,
                               int M, int nseq, int F, int Fp, float p, unsigned long long seed,
                               const unsigned long long* seed_dev, const unsigned char* drop_bits, const void* gh, int dtype,
                               void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16)
-        return omlm_ffmid_bwd_h(dh2, h1, convw, gamma, mean, rstd, du_tmp, dh1, dgamma, dconv, workspace, M, nseq, F, Fp, p, seed, seed_dev,
-                                drop_bits, gh, 1, stream);
-#endif
     FfmidArgs a;
     memset(&a, 0, sizeof(a));
     a.dh2 = dh2; a.h1 = h1; a.convw = convw; a.gamma = gamma; a.mean = const_cast<float*>(mean); a.rstd = const_cast<float*>(rstd);      // (read only here)
@@ -806,5 +771,6 @@ extern "C" int OMLM_API(omlm_ffmid_bwd)(const void* dh2, const void* h1, const v
     c.du_aligned = (uintptr_t)du_tmp % 8 == 0;
     return ffmid_run(c, a);
 }
+#endif
 
 }   // namespace OMLM_NS

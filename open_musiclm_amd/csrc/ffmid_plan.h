@@ -51,7 +51,7 @@ enum FfOp { FF_FWD, FF_FWD_PLANES, FF_FWD_MX, FF_BWD };
 struct FfmidCall {
     FfOp op;
     int M, nseq, F, Fp;
-    int dtype;              // as the copy sees it: 0 fp32, 1 its 16-bit type (the bf16 copy forwards fp16 operands to the fp16 copy as 1)
+    int dtype;              // as the copy sees it: 0 fp32, 1 its 16-bit type (ffmid_to_fp16_copy below)
     bool fp16_copy;         // the fp16 copy: it builds no fp32 kernels
     float p;                // dropout: the route depends on p > 0 only; the forwards check the range
     bool operands;          // every pointer the entry requires is there (the lo / fp8 planes and the workspace among them)
@@ -84,6 +84,14 @@ struct FfmidPlan {
     int n;
     FfmidLaunch l[4];
 };
+
+// The bf16 copy holds the public entries and hands a call that names fp16 (dtype code 2) to the fp16 copy, which sees its 16-bit type as
+// code 1.  The mx forward exists in the fp16 copy only.
+static inline bool ffmid_to_fp16_copy(FfmidCall& c) {
+    if (c.op != FF_FWD_MX && c.dtype != 2) return false;
+    if (c.dtype == 2) c.dtype = 1;
+    return true;
+}
 
 static inline FfmidPlan& ffmid_refuse(FfmidPlan& p, const char* text) {
     p.rc = FF_ERR_ARG; p.n = 0;
@@ -218,12 +226,19 @@ struct FfmidArgs {
 }   // namespace omlm_plan
 
 #ifdef OMLM_PLAN_TEST_ABI       /* tests/test_ffmid_plan_host.py: the plan behind a flat C interface, built by the host c++ */
-// call: op M nseq F Fp dtype fp16_copy operands drop_bits gh dgamma dconv n_full p0 planes_aligned du_aligned impl; p and h2_8_stride apart.
+// call: op M nseq F Fp dtype copy operands drop_bits gh dgamma dconv n_full p0 planes_aligned du_aligned impl; p and h2_8_stride apart.
+//   copy: 0 / 1 the call as the bf16 / fp16 copy sees it; 2 a call of the public entry (ffmid_to_fp16_copy decides).
 // out: rc strips n, then 16 values per launch: kernel t16 n train pl mx gh gx gy threads lds RB strips total g_rows c_rows.  msg: 384 bytes.
+// omlm_plan_ffmid_fp16_copy: whether the fp16 copy serves the call.
+static omlm_plan::FfmidCall omlm_plan_ffmid_call(const int* v, double p, long long h2_8_stride) {
+    omlm_plan::FfmidCall c = {(omlm_plan::FfOp)v[0], v[1], v[2], v[3], v[4], v[5], v[6] == 1, (float)p, v[7] != 0, v[8] != 0, v[9] != 0, v[10] != 0,
+                              v[11] != 0, v[12], v[13], h2_8_stride, v[14] != 0, v[15] != 0, v[16]};
+    if (v[6] == 2) c.fp16_copy = omlm_plan::ffmid_to_fp16_copy(c);
+    return c;
+}
+extern "C" int omlm_plan_ffmid_fp16_copy(const int* v) { return omlm_plan_ffmid_call(v, 0, 0).fp16_copy; }
 extern "C" void omlm_plan_ffmid(const int* v, double p, long long h2_8_stride, long long* out, char* msg) {
-    const omlm_plan::FfmidCall c = {(omlm_plan::FfOp)v[0], v[1], v[2], v[3], v[4], v[5], v[6] != 0, (float)p, v[7] != 0, v[8] != 0, v[9] != 0, v[10] != 0,
-                                    v[11] != 0, v[12], v[13], h2_8_stride, v[14] != 0, v[15] != 0, v[16]};
-    const omlm_plan::FfmidPlan q = omlm_plan::ffmid_plan(c);
+    const omlm_plan::FfmidPlan q = omlm_plan::ffmid_plan(omlm_plan_ffmid_call(v, p, h2_8_stride));
     out[0] = q.rc; out[1] = q.strips; out[2] = q.n;
     for (int i = 0; i < q.n; ++i) {
         const omlm_plan::FfmidLaunch& l = q.l[i];

@@ -759,11 +759,8 @@ static int gemm_impl(GemmArgs g, const GemmCall& c) {
     s.fp16_copy = OMLM_FP16 != 0; s.accumulates = g.Cin == (const float*)C; s.cin = g.Cin != nullptr; s.alpha_one = g.alpha == 1.0f;
     s.ws_bytes = c.ws ? c.ws_bytes : 0;
     const GemmPlan p = gemm_plan(s, gemm_ncu(), gemm_persist_slots(), hooks);
+#if !OMLM_FP16      /* (the fp16 copy is entered with its 16-bit operands only: gemm_to_fp16_copy) */
     if (in_dtype == 0) {
-#if OMLM_FP16
-        omlm_set_error("omlm_gemm: fp32 operands are served by the bf16 copy of the library");
-        return OMLM_ERR_UNSUPPORTED;
-#else
         OMLM_CHECK_ARG(out_dtype == 0, "fp32 operands produce fp32 output");
         const GemmLaunch& l = p.main;
         const dim3 grid(l.grid_x, l.grid_y), block(l.threads);
@@ -775,8 +772,8 @@ static int gemm_impl(GemmArgs g, const GemmCall& c) {
         default: launch_with_lds<gemm_kernel<float, true, false, float>>(grid, block, l.lds, st, g); break;
         }
         return omlm_post_launch("omlm_gemm");
-#endif
     }
+#endif
     if (p.M1 == 0) return launch_planned(g, s, p.main, st);
     GemmArgs g1, g2;
     peel_rows(g, p.M1, out_dtype == 0 ? 4 : 2, out_dtype == 0 ? 4 : 2, g1, g2);
@@ -796,63 +793,89 @@ static int gemm_impl(GemmArgs g, const GemmCall& c) {
     else                         hipLaunchKernelGGL(gemm_tail_reduce_kernel<1>, blocks, th, 0, st, ws, p.tail_slices, gw.c_split_stride, g2.M, N, gw.ldc, g2.C, nullptr, g.ldc, g2.Cin, g.ldcin);
     return omlm_post_launch("omlm_gemm (tail reduce)");
 }
+// the grouped weight gradients of omlm_gemm_wgrad_group, in the 16-bit type of this copy
+static int wgrad_group_here(const omlm_gemm_wgrad_desc* d, int count, int splits, void* stream) {
+    const GemmHooks hooks = gemm_hooks_from_env();
+    for (int base = 0; base < count; base += OMLM_GROUP_MAX) {
+        const int n = count - base < OMLM_GROUP_MAX ? count - base : OMLM_GROUP_MAX;
+        WgradDims dims[OMLM_GROUP_MAX];
+        for (int i = 0; i < n; ++i) {
+            const omlm_gemm_wgrad_desc& q = d[base + i];
+            OMLM_CHECK_ARG(q.A && q.B && q.C && q.M > 0 && q.N > 0 && q.K > 0, "wgrad group: bad problem");
+            OMLM_CHECK_ARG((q.lda % 8) == 0 && (q.ldb % 8) == 0 && q.lda >= ((q.M + 7) / 8) * 8 && q.ldb >= ((q.N + 7) / 8) * 8,
+                           "wgrad group: k-major operand pitches must be multiples of 8 covering the padded extent");
+            OMLM_CHECK_ARG(((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.B % 16) == 0, "wgrad group: operands must be 16-byte aligned");
+            OMLM_CHECK_ARG((unsigned long long)q.K * q.lda * 2 < 0xFFFFFFF0ull && (unsigned long long)q.K * q.ldb * 2 < 0xFFFFFFF0ull,
+                           "wgrad group: operand exceeds the 4 GiB buffer-descriptor window");
+            dims[i] = WgradDims{q.M, q.N, q.K};
+        }
+        int ktps[OMLM_GROUP_MAX], start[OMLM_GROUP_MAX];
+        const WgradPlan p = wgrad_group_plan(dims, n, splits, gemm_ncu(), hooks, ktps, start);
+        GroupArgs ga;
+        memset(&ga, 0, sizeof(ga));
+        ga.n = n; ga.total = p.total;
+        for (int i = 0; i < n; ++i) {
+            const omlm_gemm_wgrad_desc& q = d[base + i];
+            GroupProb& gp = ga.p[i];
+            gp.A = q.A; gp.B = q.B; gp.C = q.C; gp.c_map = q.c_map; gp.M = q.M; gp.N = q.N; gp.K = q.K; gp.lda = q.lda; gp.ldb = q.ldb; gp.ldc = q.ldc;
+            gp.kt_per_split = ktps[i]; gp.start = start[i];
+        }
+        const dim3 grid(p.total), block(512);
+        if (p.form == FORM_RING)           launch_with_lds<gemm_wgrad_group_kernel<true, true>>(grid, block, 131072, as_stream(stream), ga);
+        else if (p.form == FORM_ROT_FASTK) launch_with_lds<gemm_wgrad_group_kernel<true>>(grid, block, 131072, as_stream(stream), ga);
+        else                               launch_with_lds<gemm_wgrad_group_kernel<false>>(grid, block, 131072, as_stream(stream), ga);
+    }
+    return omlm_post_launch("omlm_gemm_wgrad_group");
+}
+
+static_assert(sizeof(GemmArgs) == 208 && sizeof(GemmCall) == 48, "GemmArgs / GemmCall: one layout in both copies");
+#if OMLM_FP16
+// the fp16 copy has two ways in: a call the bf16 copy handed over (gemm_to_fp16_copy), and the descriptor array of a grouped one
+extern "C" __attribute__((visibility("hidden"))) int omlm_gemm_run_h(const GemmArgs* g, const GemmCall* c) { return gemm_impl(*g, *c); }
+extern "C" __attribute__((visibility("hidden"))) int omlm_gemm_wgrad_group_run_h(const omlm_gemm_wgrad_desc* d, int count, int splits, void* stream) {
+    return wgrad_group_here(d, count, splits, stream);
+}
+#else
+extern "C" int omlm_gemm_run_h(const GemmArgs* g, const GemmCall* c);
+extern "C" int omlm_gemm_wgrad_group_run_h(const omlm_gemm_wgrad_desc* d, int count, int splits, void* stream);
+static int gemm_run(const GemmArgs& g, GemmCall c) { return gemm_to_fp16_copy(c.in_dtype, c.out_dtype) ? omlm_gemm_run_h(&g, &c) : gemm_impl(g, c); }
+
+// ---- the C entries (include/omlm.h).  dtype codes: 0 = fp32, 1 = bf16, 2 = fp16 --------------------------------------------------------------------
 // Workspace of the peeled tail's deterministic split-K: a caller-owned scratch buffer handed to every call that may peel a tail (omlm_gemm,
 // omlm_gemm_planes16, omlm_gemm_planes) -- ONE per stream that launches such GEMMs concurrently; NULL / 0: the one-launch tail.  The library keeps no
 // pointer.  omlm_gemm_tail_workspace_bytes: an upper bound of what an M x N output needs (8 fp32 slices of the at most one-machine-round tail).
 // (its CU query stays its own, uncached and with 256 only where the device query fails: folding it into gemm_ncu() could change its value there)
-#if !OMLM_FP16
 extern "C" long long omlm_gemm_tail_workspace_bytes(int M, int N) {
     int dev = 0, ncu = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     return gemm_tail_workspace_bytes(M, N, ncu);
 }
-#endif
 
 #define OMLM_CHECK_TAIL_WS() OMLM_CHECK_ARG((workspace == nullptr) == (workspace_bytes == 0) && workspace_bytes >= 0 && ((uintptr_t)workspace % 16) == 0, \
                                             "tail workspace: 16-byte aligned buffer and its size, or NULL / 0")
 
-// in_dtype / out_dtype: 0 = fp32, 1 = bf16, 2 = fp16 (include/omlm.h).  fp16 operands (with fp32 or fp16 output) are served by the
-// fp16 copy of this file; bf16 and fp32 operands here.
-#if !OMLM_FP16
-extern "C" int omlm_gemm_h(const void* A, const void* B, void* C, const float* Cin, const int* a_map, const int* b_map, const int* c_map,
-                           long long a_rows, long long b_rows, int M, int N, int K, int lda, int ldb, int ldc, int ldcin,
-                           int a_kmajor, int b_kmajor, int in_dtype, int out_dtype, float alpha, void* workspace, long long workspace_bytes, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_gemm)(const void* A, const void* B, void* C, const float* Cin,
+// fp16 operands (with fp32 or fp16 output) are served by the fp16 copy of this file; bf16 and fp32 operands here.
+extern "C" int omlm_gemm(const void* A, const void* B, void* C, const float* Cin,
                          const int* a_map, const int* b_map, const int* c_map,
                          long long a_rows, long long b_rows,
                          int M, int N, int K, int lda, int ldb, int ldc, int ldcin,
                          int a_kmajor, int b_kmajor, int in_dtype, int out_dtype, float alpha, void* workspace, long long workspace_bytes, void* stream) {
-#if !OMLM_FP16
-    if (in_dtype == OMLM_DT_F16) {
-        OMLM_CHECK_ARG(out_dtype == OMLM_DT_F32 || out_dtype == OMLM_DT_F16, "fp16 operands produce fp32 or fp16 output");
-        return omlm_gemm_h(A, B, C, Cin, a_map, b_map, c_map, a_rows, b_rows, M, N, K, lda, ldb, ldc, ldcin, a_kmajor, b_kmajor,
-                           1, OMLM_H_CODE(out_dtype), alpha, workspace, workspace_bytes, stream);
-    }
-#endif
+    if (in_dtype == OMLM_DT_F16) OMLM_CHECK_ARG(out_dtype == OMLM_DT_F32 || out_dtype == OMLM_DT_F16, "fp16 operands produce fp32 or fp16 output");
     OMLM_CHECK_TAIL_WS();
     GemmArgs g = gemm_args();
     g.A = A; g.B = B; g.C = C; g.Cin = Cin; g.a_map = a_map; g.b_map = b_map; g.c_map = c_map; g.a_rows = a_rows; g.b_rows = b_rows;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin; g.alpha = alpha;
-    return gemm_impl(g, GemmCall{a_kmajor, b_kmajor, in_dtype, out_dtype, false, false, workspace, workspace_bytes, stream});
+    return gemm_run(g, GemmCall{a_kmajor, b_kmajor, in_dtype, out_dtype, false, false, workspace, workspace_bytes, stream});
 }
 
 // q / k projections with the attention's l2-norm + learned scale folded into the epilogue (transformer.py:254-271): C = 16-bit
 // [M, N] (+ C2 for columns >= c2_col0, e.g. v of the fused k | v projection), epi_groups leading 64-column heads normalised, their norms
 // to norm_out [M, ldnorm] fp32 (what the backward needs instead of the fp32 pre-norm projections).  A [M, K], B [N, K] row-major 16-bit.
-#if !OMLM_FP16
-extern "C" int omlm_gemm_qknorm_h(const void* A, const void* B, void* C, void* C2, int c2_col0, int ldc2, const float* scale, float* norm_out,
-                                  int ldnorm, int groups, long long a_rows, long long b_rows, int M, int N, int K, int lda, int ldb, int ldc,
-                                  int dtype, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_gemm_qknorm)(const void* A, const void* B, void* C, void* C2, int c2_col0, int ldc2, const float* scale,
-                                          float* norm_out, int ldnorm, int groups, long long a_rows, long long b_rows, int M, int N, int K,
-                                          int lda, int ldb, int ldc, int dtype, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16) return omlm_gemm_qknorm_h(A, B, C, C2, c2_col0, ldc2, scale, norm_out, ldnorm, groups, a_rows, b_rows, M, N, K, lda, ldb, ldc, 1, stream);
-#endif
+extern "C" int omlm_gemm_qknorm(const void* A, const void* B, void* C, void* C2, int c2_col0, int ldc2, const float* scale,
+                                float* norm_out, int ldnorm, int groups, long long a_rows, long long b_rows, int M, int N, int K,
+                                int lda, int ldb, int ldc, int dtype, void* stream) {
     if (M <= 0 || N <= 0) return OMLM_OK;
-    OMLM_CHECK_ARG(dtype == 1, "gemm_qknorm: operand dtype 1 (bf16) or 2 (fp16)");
+    OMLM_CHECK_ARG_AS(dtype == 1 || dtype == 2, "gemm_qknorm: operand dtype 1 (bf16) or 2 (fp16) [dtype == 1]");
     OMLM_CHECK_ARG(A && B && C && scale && norm_out && K > 0 && (K % 8) == 0, "gemm_qknorm: null operand / K");
     OMLM_CHECK_ARG((N % 64) == 0 && groups >= 0 && groups * 64 <= N && ldnorm >= groups, "gemm_qknorm: N must be whole 64-wide heads");
     OMLM_CHECK_ARG((lda % 8) == 0 && (ldb % 8) == 0 && (ldc % 8) == 0 && ((uintptr_t)A % 16) == 0 && ((uintptr_t)B % 16) == 0 && ((uintptr_t)C % 16) == 0,
@@ -862,7 +885,7 @@ extern "C" int OMLM_API(omlm_gemm_qknorm)(const void* A, const void* B, void* C,
     GemmArgs g = gemm_args();
     g.A = A; g.B = B; g.C = C; g.a_rows = a_rows; g.b_rows = b_rows; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.epi_scale = scale; g.epi_norm = norm_out; g.epi_groups = groups; g.epi_ldnorm = ldnorm; g.C2 = C2; g.c2_col0 = c2_col0; g.ldc2 = ldc2;
-    return gemm_impl(g, GemmCall{0, 0, 1, 1, false, true, nullptr, 0, stream});
+    return gemm_run(g, GemmCall{0, 0, dtype, dtype, false, true, nullptr, 0, stream});
 }
 
 // C = A B^T (+ Cin) with BOTH operands as hi/lo planes of the 16-bit type `dtype` (1 = bf16, 2 = fp16): A [M, K] and B [N, K] row-major with
@@ -871,20 +894,11 @@ extern "C" int OMLM_API(omlm_gemm_qknorm)(const void* A, const void* B, void* C,
 // C = rne16(v), C_lo = rne16(v - C), so that the next consumer reads the un-rounded value and a 16-bit backward reads C alone.
 // Precision "fp16ff" (round 5): the two ConvFeedForward GEMMs of the forward, which carry 86-88 % of the fp16 logits-error variance
 // (profiles/r05_error_budget.md).
-#if !OMLM_FP16
-extern "C" int omlm_gemm_planes16_h(const void* A, const void* A_lo, const void* B, const void* B_lo, void* C, void* C_lo, const float* Cin,
-                                    const int* a_map, const int* c_map, long long a_rows, long long b_rows, int M, int N, int K,
-                                    int lda, int ldb, int ldc, int ldcin, int dtype, void* workspace, long long workspace_bytes, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_gemm_planes16)(const void* A, const void* A_lo, const void* B, const void* B_lo, void* C, void* C_lo, const float* Cin,
-                                            const int* a_map, const int* c_map, long long a_rows, long long b_rows, int M, int N, int K,
-                                            int lda, int ldb, int ldc, int ldcin, int dtype, void* workspace, long long workspace_bytes, void* stream) {
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16) return omlm_gemm_planes16_h(A, A_lo, B, B_lo, C, C_lo, Cin, a_map, c_map, a_rows, b_rows, M, N, K, lda, ldb, ldc, ldcin, 1,
-                                                          workspace, workspace_bytes, stream);
-#endif
+extern "C" int omlm_gemm_planes16(const void* A, const void* A_lo, const void* B, const void* B_lo, void* C, void* C_lo, const float* Cin,
+                                  const int* a_map, const int* c_map, long long a_rows, long long b_rows, int M, int N, int K,
+                                  int lda, int ldb, int ldc, int ldcin, int dtype, void* workspace, long long workspace_bytes, void* stream) {
     OMLM_CHECK_TAIL_WS();
-    OMLM_CHECK_ARG(dtype == 1, "gemm_planes16: operand dtype 1 (bf16) or 2 (fp16)");
+    OMLM_CHECK_ARG_AS(dtype == 1 || dtype == 2, "gemm_planes16: operand dtype 1 (bf16) or 2 (fp16) [dtype == 1]");
     OMLM_CHECK_ARG(A_lo && B_lo, "gemm_planes16: null lo plane");
     OMLM_CHECK_ARG(((uintptr_t)A_lo % 16) == 0 && ((uintptr_t)B_lo % 16) == 0 && ((uintptr_t)C_lo % 16) == 0, "gemm_planes16: 16-byte aligned planes");
     OMLM_CHECK_ARG(!(C_lo && Cin), "gemm_planes16: plane output takes no residual");
@@ -893,10 +907,9 @@ extern "C" int OMLM_API(omlm_gemm_planes16)(const void* A, const void* A_lo, con
     g.A = A; g.B = B; g.C = C; g.Cin = Cin; g.a_map = a_map; g.c_map = c_map; g.a_rows = a_rows; g.b_rows = b_rows;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.ldcin = ldcin;
     g.split3 = 1; g.A_lo = A_lo; g.B_lo = B_lo; g.C_lo = C_lo;
-    return gemm_impl(g, GemmCall{0, 0, 1, C_lo ? 1 : 0, true, false, workspace, workspace_bytes, stream});
+    return gemm_run(g, GemmCall{0, 0, dtype, C_lo ? dtype : 0, true, false, workspace, workspace_bytes, stream});
 }
 
-#if !OMLM_FP16
 // fp32-grade GEMM on bf16 hi/lo planes ("bf16x3" through the LDS-DMA tile kernels).  A and B are bf16 hi planes in the layout
 // omlm_gemm takes for bf16 operands; the matching lo plane lies a_plane_bytes / b_plane_bytes behind each (omlm_split_planes
 // writes such a pair).  One launch whose k-loop is three times as long: hi*hi + hi*lo + lo*hi, accumulated in fp32 -- the same
@@ -951,53 +964,17 @@ extern "C" int omlm_split_planes(const float* x, void* planes, long long n, long
     return omlm_post_launch("omlm_split_planes");
 }
 
-#endif   // !OMLM_FP16 (operand planes: bf16 copy only)
-
 // C_i[M_i, N_i] += A_i^T B_i for `count` problems with 16-bit k-major operands A_i [K_i, M_i], B_i [K_i, N_i] in ONE launch of 256x256
 // full-K (or lightly split) tiles.  splits: K-splits per tile for every problem (0 = chosen here for whole machine rounds);
 // dtype: operand type of ALL problems (1 = bf16, 2 = fp16).
-#if !OMLM_FP16
-extern "C" int omlm_gemm_wgrad_group_h(const omlm_gemm_wgrad_desc* d, int count, int splits, int dtype, void* stream);
-#endif
-extern "C" int OMLM_API(omlm_gemm_wgrad_group)(const omlm_gemm_wgrad_desc* d, int count, int splits, int dtype, void* stream) {
+extern "C" int omlm_gemm_wgrad_group(const omlm_gemm_wgrad_desc* d, int count, int splits, int dtype, void* stream) {
     if (count <= 0) return OMLM_OK;
     OMLM_CHECK_ARG(d, "null descriptor array");
-#if !OMLM_FP16
-    if (dtype == OMLM_DT_F16) return omlm_gemm_wgrad_group_h(d, count, splits, 1, stream);
-#endif
-    OMLM_CHECK_ARG(dtype == 1, "wgrad group: operand dtype must be 1 (bf16) or 2 (fp16)");
-    const GemmHooks hooks = gemm_hooks_from_env();
-    for (int base = 0; base < count; base += OMLM_GROUP_MAX) {
-        const int n = count - base < OMLM_GROUP_MAX ? count - base : OMLM_GROUP_MAX;
-        WgradDims dims[OMLM_GROUP_MAX];
-        for (int i = 0; i < n; ++i) {
-            const omlm_gemm_wgrad_desc& q = d[base + i];
-            OMLM_CHECK_ARG(q.A && q.B && q.C && q.M > 0 && q.N > 0 && q.K > 0, "wgrad group: bad problem");
-            OMLM_CHECK_ARG((q.lda % 8) == 0 && (q.ldb % 8) == 0 && q.lda >= ((q.M + 7) / 8) * 8 && q.ldb >= ((q.N + 7) / 8) * 8,
-                           "wgrad group: k-major operand pitches must be multiples of 8 covering the padded extent");
-            OMLM_CHECK_ARG(((uintptr_t)q.A % 16) == 0 && ((uintptr_t)q.B % 16) == 0, "wgrad group: operands must be 16-byte aligned");
-            OMLM_CHECK_ARG((unsigned long long)q.K * q.lda * 2 < 0xFFFFFFF0ull && (unsigned long long)q.K * q.ldb * 2 < 0xFFFFFFF0ull,
-                           "wgrad group: operand exceeds the 4 GiB buffer-descriptor window");
-            dims[i] = WgradDims{q.M, q.N, q.K};
-        }
-        int ktps[OMLM_GROUP_MAX], start[OMLM_GROUP_MAX];
-        const WgradPlan p = wgrad_group_plan(dims, n, splits, gemm_ncu(), hooks, ktps, start);
-        GroupArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.n = n; ga.total = p.total;
-        for (int i = 0; i < n; ++i) {
-            const omlm_gemm_wgrad_desc& q = d[base + i];
-            GroupProb& gp = ga.p[i];
-            gp.A = q.A; gp.B = q.B; gp.C = q.C; gp.c_map = q.c_map; gp.M = q.M; gp.N = q.N; gp.K = q.K; gp.lda = q.lda; gp.ldb = q.ldb; gp.ldc = q.ldc;
-            gp.kt_per_split = ktps[i]; gp.start = start[i];
-        }
-        const dim3 grid(p.total), block(512);
-        if (p.form == FORM_RING)           launch_with_lds<gemm_wgrad_group_kernel<true, true>>(grid, block, 131072, as_stream(stream), ga);
-        else if (p.form == FORM_ROT_FASTK) launch_with_lds<gemm_wgrad_group_kernel<true>>(grid, block, 131072, as_stream(stream), ga);
-        else                               launch_with_lds<gemm_wgrad_group_kernel<false>>(grid, block, 131072, as_stream(stream), ga);
-    }
-    return omlm_post_launch("omlm_gemm_wgrad_group");
+    OMLM_CHECK_ARG_AS(dtype == 1 || dtype == 2, "wgrad group: operand dtype must be 1 (bf16) or 2 (fp16) [dtype == 1]");
+    int out_dtype = 0;        // (fp32 accumulation into C_i)
+    return gemm_to_fp16_copy(dtype, out_dtype) ? omlm_gemm_wgrad_group_run_h(d, count, splits, stream) : wgrad_group_here(d, count, splits, stream);
 }
+#endif
 
 }   // namespace OMLM_NS
 #endif   // OMLM_ISA_ONLY

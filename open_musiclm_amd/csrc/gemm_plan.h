@@ -56,6 +56,15 @@ struct GemmShape {
     long long ws_bytes;          // tail workspace (0: none)
 };
 
+// The bf16 copy of gemm.hip holds the public entries and hands a call whose operands are fp16 (code 2) to the fp16 copy, which sees its
+// 16-bit type as code 1 -- as output type too.  (omlm_gemm_qknorm, omlm_gemm_planes16 and omlm_gemm_wgrad_group name one type: `dtype`.)
+inline bool gemm_to_fp16_copy(int& in_dtype, int& out_dtype) {
+    if (in_dtype != 2) return false;
+    in_dtype = 1;
+    if (out_dtype == 2) out_dtype = 1;
+    return true;
+}
+
 // k-loop forms
 enum GemmForm { FORM_FP32_STAGED, FORM_ROT_GENERAL, FORM_ROT_FASTK, FORM_ROT_KMAP, FORM_ROT_SPLIT3, FORM_PERSIST, FORM_RING };
 
@@ -356,15 +365,24 @@ static int put(int* o, const GemmLaunch& l) {
     memcpy(o, v, sizeof(v));
     return 10;
 }
-// sh: M N K a_kmajor b_kmajor a_map b_map c_map in_dtype out_dtype split3 planes16 fp16_copy accumulates cin alpha_one.
-// out: M1, tail_slices, reduce_kind, reduce_blocks, then main and tail as put() writes them
-extern "C" void omlm_plan_gemm(const int* sh, long long ws_bytes, int ncu, int persist_slots, const int* hooks, int* out) {
+// sh: M N K a_kmajor b_kmajor a_map b_map c_map in_dtype out_dtype split3 planes16 copy accumulates cin alpha_one.
+//   copy: 0 / 1 the call as the bf16 / fp16 copy sees it; 2 a call of the public entry (gemm_to_fp16_copy decides).
+// out: M1, tail_slices, reduce_kind, reduce_blocks, then main and tail as put() writes them.  omlm_plan_gemm_fp16_copy: whether the fp16 copy
+// serves the call.
+static GemmShape shape_of(const int* sh, long long ws_bytes) {
     GemmShape s = {sh[0], sh[1], sh[2], sh[3] != 0, sh[4] != 0, sh[5] != 0, sh[6] != 0, sh[7] != 0, sh[8], sh[9], sh[10] != 0, sh[11] != 0,
-                   sh[12] != 0, sh[13] != 0, sh[14] != 0, sh[15] != 0, ws_bytes};
-    const GemmPlan p = gemm_plan(s, ncu, persist_slots, hooks_of(hooks));
+                   sh[12] == 1, sh[13] != 0, sh[14] != 0, sh[15] != 0, ws_bytes};
+    if (sh[12] == 2) s.fp16_copy = gemm_to_fp16_copy(s.in_dtype, s.out_dtype);
+    return s;
+}
+extern "C" int omlm_plan_gemm_fp16_copy(const int* sh) { return shape_of(sh, 0).fp16_copy; }
+extern "C" void omlm_plan_gemm(const int* sh, long long ws_bytes, int ncu, int persist_slots, const int* hooks, int* out) {
+    const GemmPlan p = gemm_plan(shape_of(sh, ws_bytes), ncu, persist_slots, hooks_of(hooks));
     out[0] = p.M1; out[1] = p.tail_slices; out[2] = p.reduce_kind; out[3] = p.reduce_blocks;
     put(out + 4 + put(out + 4, p.main), p.tail);
 }
+// the copy that serves an entry that names one type (omlm_gemm_qknorm, omlm_gemm_planes16, omlm_gemm_wgrad_group), and the code it sees
+extern "C" int omlm_plan_gemm_copy_of(int* dtype) { int out = *dtype; return gemm_to_fp16_copy(*dtype, out); }
 extern "C" void omlm_plan_mx(int M, int N, int K, long long ws_bytes, int ncu, const int* hooks, int* out) {
     const MxPlan p = mx_plan(M, N, K, ws_bytes, ncu, hooks_of(hooks));
     const int v[] = {p.nk_all, p.M1, p.S, p.ktps, p.fused, p.main_tiles, p.tail_tiles, p.reduce_blocks};

@@ -26,6 +26,8 @@ UNSUPPORTED = -3
 FAMILIES = ("a1_fwd", "a1_dq", "a1_dkv", "a4_fwd", "a2_dq", "dbias_reduce", "a3_zero", "a3_dkv", "a3_reduce")
 FORMS = ("short", "long", "part")
 # kernels of attention2.hip that serve other entry points (table preparation, the keep-mask hook, the to_out dropout)
+CODE = {"float32": 0, "bfloat16": 1, "float16": 2}
+BF16_COPY, FP16_COPY, PUBLIC = 0, 1, 2
 OTHER_ENTRIES = {"attn2_bias_prep_kernel", "attn_dropout_keep_kernel", "dropout_residual_fwd_kernel", "dropout_residual_bwd_kernel"}
 
 
@@ -68,10 +70,10 @@ def parse_kernel(name):
 
 
 def call_of(row, backward=None):
-    """the call description of a recorded row as the test ABI takes it"""
+    """the call of a recorded row as the public entry receives it: the rule of the plan decides which copy serves it"""
     bias, biasT = row["bias"] in ("T", "raw"), row["bias"] in ("T", "zeroT")
     bwd = row["dir"] == "bwd" if backward is None else backward
-    return (C.c_int * 13)(bwd, row["dt"] == "float32", row["dt"] == "float16", row["B"], row["N"], row["H"], row["P"], bias, biasT,
+    return (C.c_int * 13)(bwd, CODE[row["dt"]], PUBLIC, row["B"], row["N"], row["H"], row["P"], bias, biasT,
                           bool(row.get("dbias")), bool(row.get("dbias")) and row.get("ws", True), row.get("drop", 0.0) > 0, not row.get("split", False))
 
 
@@ -82,7 +84,7 @@ def run_plan(plan, call):
     launches = [dict(zip(keys, out[4 + 16 * i:20 + 16 * i])) for i in range(out[1])]
     for l in launches:
         l["family"], l["form"] = FAMILIES[l["family"]], FORMS[l["form"]]
-    return dict(rc=out[0], ldT=out[2], dkv_slots=out[3], launches=launches, msg=msg.value.decode())
+    return dict(rc=out[0], ldT=out[2], dkv_slots=out[3], fp16_copy=bool(plan.omlm_plan_attn_fp16_copy(call)), launches=launches, msg=msg.value.decode())
 
 
 def implied(l, ns):
@@ -144,9 +146,11 @@ def test_plan_implies_the_recorded_launches(plan, row):
         return
     assert got["rc"] == 0, got["msg"]
     ns = "omlm_f16" if row["dt"] == "float16" else "omlm_bf16"
+    assert got["fp16_copy"] == (ns == "omlm_f16")              # the copy the plan names: fp16 wherever the code names it
     want = [(*parse_kernel(l["kernel"]), l["grid"], l["workgroup"]) for l in row["launches"]]
     have = [(*implied(l, ns), [l["gx"], l["gy"], l["gz"]], l["threads"]) for l in got["launches"]]
     assert have == want
+    assert all(w[0] == ns for w in want if w[1] != "attn_dbias_reduce_kernel")     # ... is the one whose namespace the recorded kernels carry
     for l, (_, kernel, args, _, _) in zip(got["launches"], want):
         assert l["lds"] == needed_lds(kernel, args, row) <= 160 * 1024, kernel
     if got["ldT"]:

@@ -69,6 +69,8 @@ def parse_kernel(name):
     return ns, kernel, args
 
 
+CODE = {"float32": 0, "bfloat16": 1, "float16": 2}
+BF16_COPY, FP16_COPY, PUBLIC = 0, 1, 2                         # (fp16_copy=False / True are the first two)
 FLAGS = ("pos_dev", "parts", "ids", "emb_table", "head_W", "ln_parts", "splitk_ws", "splitk_cnt", "W1p_lo", "W2p_lo", "head_W_lo", "k_new", "advance_pos")
 
 
@@ -80,10 +82,10 @@ def call(B, D, H, Fp, w_dtype, L=1, Nmax=64, nsplit=1, V1=17, fp16_copy=False, r
 
 
 def call_of(row):
-    """the call of a recorded row: the bf16 copy forwards fp16 weights to the fp16 copy as w_dtype 1"""
+    """the call of a recorded row, as the public entry receives it"""
     null, lo, head = row["null"], row["lo"], row["head"]
-    return call(row["B"], row["D"], row["H"], row["Fp"], 0 if row["w"] == "float32" else 1, L=row["L"], Nmax=row["Nmax"], nsplit=row["nsplit"],
-                V1=row["V1"], fp16_copy=row["w"] == "float16", round_bf16=row["round"], kv16=row["kv16"],
+    return call(row["B"], row["D"], row["H"], row["Fp"], CODE[row["w"]], L=row["L"], Nmax=row["Nmax"], nsplit=row["nsplit"],
+                V1=row["V1"], fp16_copy=PUBLIC, round_bf16=row["round"], kv16=row["kv16"],
                 pos_dev=null != "pos_dev", parts=null != "parts", ids=null != "ids", emb_table=row["emb"], head_W=head, ln_parts=row["ln"],
                 splitk_ws=row["ws"], splitk_cnt=row["cnt"], W1p_lo=bool(lo), W2p_lo=bool(lo) and lo != "no_w2",
                 head_W_lo=bool(lo) and head and lo != "no_head", k_new=bool(row["kv16"]) and null != "k_new", advance_pos=row["adv"])
@@ -96,7 +98,7 @@ def run_plan(plan, c):
     ls = [dict(zip(LAUNCH, out[16 + 16 * i:32 + 16 * i])) for i in range(got["n"] + 1)]
     for l in ls:
         l["kernel"], l["phase"] = KERNELS[l["kernel"]], PHASES[l["phase"]]
-    got.update(route=ROUTES[got["route"]], launches=ls[:-1], q_rest=ls[-1], msg=msg.value.decode(), L=c[3])
+    got.update(route=ROUTES[got["route"]], launches=ls[:-1], q_rest=ls[-1], msg=msg.value.decode(), L=c[3], fp16_copy=bool(plan.omlm_plan_decode_fp16_copy(c)))
     return got
 
 
@@ -174,10 +176,12 @@ def test_plan_implies_the_recorded_launches(plan, row):
         return
     assert got["rc"] == 0, got["msg"]
     ns = "omlm_f16" if row["w"] == "float16" else "omlm_bf16"
+    assert got["fp16_copy"] == (ns == "omlm_f16")              # the copy the plan names: fp16 wherever w_dtype names it
     want = [(*parse_kernel(l["kernel"]), l["grid"], l["workgroup"]) for l in row["launches"]]
     step = expand(got)
     have = [(*implied(l, ns), [l["gx"], l["gy"]], l["threads"]) for l, _ in step]
     assert have == want
+    assert all(w[0] == ns for w in want if w[1] != "dec_advance_kernel")       # ... is the one whose namespace the recorded kernels carry
     for (l, layer), (_, kernel, args, _, _) in zip(step, want):
         assert l["lds"] == needed_lds(kernel, args, l["phase"], layer, row) <= 160 * 1024, (kernel, l)
     names = {kernel for _, kernel, _, _, _ in want}

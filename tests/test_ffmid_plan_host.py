@@ -29,6 +29,8 @@ OPS = ("fwd", "fwd_planes", "fwd_mx", "bwd")
 KERNELS = ("fwd1", "bwd1", "bwd2", "strip_fwd", "strip_fwd_seg", "rowsum", "strip_bwd", "bwd3", "colsum_g", "colsum_c", "colsum_group")
 LAUNCH = ("kernel", "t16", "n", "train", "pl", "mx", "gh", "gx", "gy", "threads", "lds", "RB", "strips", "total", "g_rows", "c_rows")
 WS_G_ROWS, WS_C_ROWS = 1024, 512                               # the workspace's partial rows of d(gamma) / of d(conv taps)
+CODE = {"float32": 0, "bfloat16": 1, "float16": 2}
+BF16_COPY, FP16_COPY, PUBLIC = 0, 1, 2                         # (fp16_copy=False / True are the first two)
 
 
 @pytest.fixture(scope="module")
@@ -54,12 +56,12 @@ def call(op, M, nseq, F, Fp, dtype, fp16_copy=False, p=0.0, operands=True, drop_
 
 
 def call_of(row):
-    """the call of a recorded row: the bf16 copy forwards fp16 operands to the fp16 copy as dtype 1"""
+    """the call of a recorded row, as the public entry receives it (the mx forward has no dtype argument: its entry passes 1)"""
     op, M, Fp, bwd = row["op"], row["M"], row["Fp"], row["op"] == "bwd"
     rows = max(M, 1)
     stride = {"ok": (rows + 255) // 256 * 256 * 2 * Fp, "small": rows * 2 * Fp - 16, "odd": (rows + 255) // 256 * 256 * 2 * Fp + 8}[row["stride"]]
-    dtype = (0 if row["dt"] == "float32" else 1) if row["dtype"] is None else row["dtype"]
-    return call(op, M, row["nseq"], row["F"], Fp, dtype, fp16_copy=row["dt"] == "float16", p=row["p"], operands=row["null"] is None,
+    dtype = (1 if op == "fwd_mx" else CODE[row["dt"]]) if row["dtype"] is None else row["dtype"]
+    return call(op, M, row["nseq"], row["F"], Fp, dtype, fp16_copy=PUBLIC, p=row["p"], operands=row["null"] is None,
                 drop_bits=row["drop"], gh=row["gh"], dgamma=bwd and row["dgamma"], dconv=bwd and row["dconv"], seg=row["seg"] or (0, 0),
                 h2_8_stride=stride if op == "fwd_mx" else 0, planes_aligned=row["misalign"] != "planes", du_aligned=row["misalign"] != "du_tmp",
                 impl=row["impl"])
@@ -71,7 +73,7 @@ def run_plan(plan, c):
     ls = [dict(zip(LAUNCH, out[3 + 16 * i:19 + 16 * i])) for i in range(out[2])]
     for l in ls:
         l["kernel"] = KERNELS[l["kernel"]]
-    return dict(rc=out[0], strips=bool(out[1]), launches=ls, msg=msg.value.decode())
+    return dict(rc=out[0], strips=bool(out[1]), fp16_copy=bool(plan.omlm_plan_ffmid_fp16_copy(c[0])), launches=ls, msg=msg.value.decode())
 
 
 def implied(l, ns):
@@ -99,9 +101,12 @@ def test_plan_implies_the_recorded_launches(plan, row):
         return
     assert got["rc"] == 0, got["msg"]
     ns = "omlm_f16" if row["dt"] == "float16" else "omlm_bf16"
+    # the copy that serves the call: the one whose namespace the recorded kernels carry -- fp16 wherever the code names it, and the mx forward
+    assert got["fp16_copy"] == (ns == "omlm_f16") == (row["op"] == "fwd_mx" or call_of(row)[0][5] == 2)
     want = [(*parse_kernel(l["kernel"]), l["grid"], l["workgroup"]) for l in row["launches"]]
     have = [(*implied(l, ns), [l["gx"], l["gy"]], l["threads"]) for l in got["launches"]]
     assert have == want
+    assert all(w[0] == ns for w in want if "colsum" not in w[1])
     for l, (_, kernel, _, _, _) in zip(got["launches"], want):
         assert l["lds"] == needed_lds(kernel, row["Fp"]) <= 160 * 1024, (kernel, l)
     second = any(k.startswith(("ffmid2_", "ffmid3_")) for _, k, _, _, _ in want)

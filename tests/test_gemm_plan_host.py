@@ -22,6 +22,8 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = json.load(open(os.path.join(ROOT, "tests", "gemm_routes.json")))
 FORMS = ("fp32", "general", "fastk", "kmap", "split3", "persist", "ring")
+CODE = {"float32": 0, "bfloat16": 1, "float16": 2}
+PUBLIC = 2                                                     # the test ABI's copy value of a call as the public entry receives it
 TYPES = {"DF16_": "h16", "DF16b": "h16", "f": "float", "float": "float", "h16pl_t": "h16pl"}
 
 
@@ -87,8 +89,12 @@ def needed_lds(kernel, a):
 
 
 def expected(plan, c, ncu, slots, ws_bytes):
+    """the launches the planners imply for a recorded call, taken as the public entry receives it: with the dtype codes of its tensors"""
     hooks = hooks_of(c.get("env", {}))
     ns = "omlm_f16" if c["dt"] == "float16" else "omlm_bf16"
+    if c["entry"] in ("qknorm", "wgrad_group", "planes16"):    # the entries that name one type: the rule alone says which copy serves them
+        code = C.c_int(CODE[c["dt"]])
+        assert plan.omlm_plan_gemm_copy_of(C.byref(code)) == (ns == "omlm_f16") and code.value == 1
     M, N, K = c.get("M"), c.get("N"), c.get("K")
     reduce = lambda kind, blocks: (ns, "gemm_tail_reduce_kernel", [kind], blocks, 1, 256, 0)
     if c["entry"] == "qknorm":
@@ -118,13 +124,15 @@ def expected(plan, c, ncu, slots, ws_bytes):
     # ops.gemm sends fp32 operands of large enough products to omlm_gemm_planes (bf16 hi/lo planes, three products) unless a k-major operand is mapped
     x3 = (c["dt"] == "float32" and c.get("planes", True) and M * N * K >= 1 << 26 and not (ak and c.get("a_map")) and not (bk and c.get("b_map"))
           and (ak and bk or K % 8 == 0))
-    in_dtype = 1 if planes16 or x3 or c["dt"] != "float32" else 0
+    in_dtype = 1 if x3 else CODE[c["dt"]]                      # (omlm_gemm_planes takes bf16 planes)
     out16 = bool(c.get("c_lo")) if planes16 else c["out"] != "float32"
+    out_dtype = (in_dtype if out16 else 0) if planes16 else CODE[c["out"]]
     cin = c.get("cin")
-    sh = (C.c_int * 16)(M, N, K, ak, bk, bool(c.get("a_map")), bool(c.get("b_map")), bool(c.get("c_map")), in_dtype, int(out16), planes16 or x3,
-                        planes16, ns == "omlm_f16", cin == "c", cin is not None, c.get("alpha", 1.0) == 1.0)
+    sh = (C.c_int * 16)(M, N, K, ak, bk, bool(c.get("a_map")), bool(c.get("b_map")), bool(c.get("c_map")), in_dtype, out_dtype, planes16 or x3,
+                        planes16, PUBLIC, cin == "c", cin is not None, c.get("alpha", 1.0) == 1.0)
     v = (C.c_int * 24)()
     plan.omlm_plan_gemm(sh, C.c_longlong(ws_bytes), ncu, slots, hooks, v)
+    assert plan.omlm_plan_gemm_fp16_copy(sh) == (ns == "omlm_f16")                        # the copy the rule names: the one whose kernels the trace saw (checked by the caller)
     M1, S, kind, blocks = v[0:4]
     tout = ("h16pl" if out16 else "float") if planes16 else ("h16" if out16 else "float")
     kw = dict(planes16=planes16, split3=planes16 or x3)
@@ -146,6 +154,7 @@ def test_plan_implies_the_recorded_launches(plan, row):
         want.append((ns, kernel, args, l["grid_x"], l["grid_y"], l["workgroup"], needed_lds(kernel, args)))
     got = expected(plan, row, TABLE["ncu"], TABLE["persist_slots"], TABLE["ws_bytes"])
     assert [tuple(map(str, g)) for g in got] == [tuple(map(str, w)) for w in want]
+    assert {w[0] for w in want} == {"omlm_f16" if row["dt"] == "float16" else "omlm_bf16"}
 
 
 def test_table_covers_every_form_and_hook():
